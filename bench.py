@@ -50,6 +50,7 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
 F_FEATURES, ELEM = 5, 4
 BYTES_PER_TREE_SAMPLE_SINGLE = (F_FEATURES + 1) * ELEM  # 24 B: one tree per pass over X
+DUMP_BYTES, DUMP_SEED = 64 * 10**6, 0xD0  # --dump-outputs: size bound of the dump's files, seed of its sample of the samples axis
 
 WORKLOADS = {
     "headline": dict(n_trees=1000, N=10**7, desc="1000 random depth<=15 20-node trees x (5 x 10^7) Float32"),
@@ -345,6 +346,17 @@ def wide_x_leg(ctx, lib, ops, device, F=60, n_trees=1000, N=10**6, steps=10):
     return res
 
 
+def write_outputs(path, arrs):
+    """--dump-outputs: DIR/<name>.npy for each array (finite float32 / float64 only, DUMP_BYTES in all); returns {name: shape}."""
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    files = [os.path.join(path, name + ".npy") for name in arrs]
+    for f, a in zip(files, arrs.values()):
+        np.save(f, a)
+    assert sum(os.path.getsize(f) for f in files) <= DUMP_BYTES
+    return {name: list(a.shape) for name, a in arrs.items()}
+
+
 def search_generation_leg(ctx, lib, ops, X, n_trees=10000, rows=1000):
     """de_program_create / de_eval / de_program_destroy of n_trees FRESH trees on `rows` samples through the C ABI."""
     import ctypes as C
@@ -398,7 +410,15 @@ def main():
     ap.add_argument("--no-full-eval-leg", action="store_true", help="skip the secondary timing without the early exit (DE_OPT_FULL_EVAL)")
     ap.add_argument("--no-complete-leg", action="store_true",
                     help="skip the `complete_only` leg: the same generator rejection-sampled to a population of COMPLETE trees (the kernel-quality number)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step of the workload returned to its caller as DIR/<name>.npy "
+                         "(float32; samples.npy: the sample indices, float64): a fixed, seeded sample of the samples axis, <= 64 MB in all.  "
+                         "Every value is finite: the rows of a tree whose flag is 0 (unspecified, include/de_hip.h) are written as 0, ok.npy holds the flags; "
+                         "a non-finite value of a complete tree (an overflowed fused loss) is written as 0 and counted in the result line.  "
+                         "N > 1 GPUs: rank 0's shard")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher of N ranks (one per GPU, RCCL over xGMI) and relay
@@ -565,10 +585,12 @@ def main():
             np.cumsum(ng_c[:-1] * N, out=goffs[1:])
             ps_grad = bool(wl.get("per_sample_grad"))
             gradc = None if (wl.get("by_class") or (per_sample and not ps_grad)) else torch.empty(max(int((ng_c * N).sum()), 1), device=dev, dtype=torch.float32)
+            # the eval call's flags, kept apart from those of the gradient / pullback call that follows it in the step
+            ok_ev = ok if (per_sample and not ps_grad) else torch.empty_like(ok)
 
         def step():
             if is_param:
-                ctx.check(lib.de_eval(ctx._h, pop._h, X.data_ptr(), N, 5, pa_ref, out.data_ptr(), N, ok.data_ptr()))
+                ctx.check(lib.de_eval(ctx._h, pop._h, X.data_ptr(), N, 5, pa_ref, out.data_ptr(), N, ok_ev.data_ptr()))
                 if per_sample and not ps_grad:
                     pass
                 elif by_class:
@@ -599,6 +621,57 @@ def main():
             if world > 1:
                 torch.distributed.barrier()
             torch.cuda.synchronize()
+
+        def step_outputs():
+            """--dump-outputs: what the last step returned to its caller, as host arrays.  The [n_trees, N]-shaped outputs (`out`, the
+            gradient rows) at a fixed, seeded sample of the samples axis, as many samples as DUMP_BYTES allows; the per-tree ones whole.
+            The rows of a tree whose flag is 0 are unspecified (include/de_hip.h): 0 here, so that two builds compare on what is defined
+            (ok.npy says which rows that is).  Returns (arrays, {name: non-finite values of complete trees, written as 0})."""
+            n = len(trees)
+            okh = ok.cpu().numpy().astype(bool)
+            arrs = {"ok": okh.astype(np.float32)}
+
+            def per_tree(v, counts):  # entries packed tree after tree, `counts[t]` of them for tree t
+                v = v[:int(counts.sum())].cpu().numpy().astype(np.float32)
+                v[np.repeat(~okh, counts)] = 0
+                return v
+            if is_loss or is_lossgrad or by_class:
+                arrs["loss"] = per_tree(lossv, np.ones(n, dtype=np.int64))
+            if is_lossgrad:
+                arrs["dloss"] = per_tree(dlossv, np.array([pop.n_grad(t, 1) for t in range(n)], dtype=np.int64))
+            if by_class:
+                arrs["dloss"] = per_tree(dlossv, ng_b)
+                arrs["dparams"] = dparv.cpu().numpy()
+                arrs["dparams"][~okh] = 0
+            ok_out = okh
+            if is_param and ok_ev is not ok:
+                ok_out = ok_ev.cpu().numpy().astype(bool)
+                arrs["ok_eval"] = ok_out.astype(np.float32)
+            ng = ng_c if (is_param and gradc is not None) else None
+            rows = (n if out is not None else 0) + (5 * n if is_grad else 0) + (int(ng.sum()) if ng is not None else 0)
+            if rows:
+                m = min(N, (DUMP_BYTES - 4096 - sum(a.nbytes for a in arrs.values())) // (4 * rows + 8))  # (4096: the .npy headers)
+                cols = np.arange(N) if m == N else np.sort(np.random.default_rng(DUMP_SEED).choice(N, m, replace=False))
+                arrs["samples"] = cols.astype(np.float64)
+                ci = torch.from_numpy(cols).to(dev)
+                if out is not None:
+                    arrs["out"] = out[:, ci].cpu().numpy()
+                    arrs["out"][~ok_out] = 0
+                if is_grad:  # tree t: an [n_grad = 5, N] column-major matrix, packed -> [n, m, 5]
+                    arrs["grad"] = grad.view(n, N, 5)[:, ci, :].cpu().numpy()
+                    arrs["grad"][~okh] = 0
+                elif ng is not None:  # tree t: an [ng[t], N] column-major matrix at goffs[t] -> its [m, ng[t]] sample, tree after tree
+                    g = torch.cat([gradc[int(goffs[t]):int(goffs[t] + ng[t] * N)].view(N, int(ng[t]))[ci].reshape(-1) for t in range(n)])
+                    arrs["grad"] = g.cpu().numpy()
+                    arrs["grad"][np.repeat(~okh, ng * m)] = 0
+            # what is left non-finite belongs to complete trees: a fused loss (and its gradient) can overflow where every value was finite
+            nonfinite = {}
+            for name, a in arrs.items():
+                bad = ~np.isfinite(a)
+                if bad.any():
+                    nonfinite[name] = int(bad.sum())
+                    a[bad] = 0
+            return arrs, nonfinite
 
         # N > 1: gather the flags through the library's own RCCL communicator (what a Julia / C caller uses, csrc/de_dist.cpp);
         # torch.distributed only ships the 128-byte unique id.  Checked against the torch.distributed gather once; any failure
@@ -697,6 +770,10 @@ def main():
             t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             elapsed = float(t.item())
+        dumped = None
+        if primary and args.dump_outputs and rank == 0:  # (before the secondary legs: they reuse the output buffers)
+            arrs, nonfinite = step_outputs()
+            dumped = {"dir": args.dump_outputs, "shapes": write_outputs(args.dump_outputs, arrs), "nonfinite_written_as_zero": nonfinite}
 
         turbo_res = None
         if primary and not args.turbo and not args.no_turbo_leg and not (is_param or is_grad or is_lossgrad or is_loss):
@@ -932,6 +1009,8 @@ def main():
                                      "VALU/scalar-issue bound (DESIGN.md §Roofline)"},
             }
             res["config"]["turbo"] = bool(args.turbo)
+            if dumped is not None:
+                res["outputs_dumped"] = dumped
             if args.turbo and plain_eval:
                 res["roofline"]["valu"] = valu_ceiling(pop, len(trees), units_all, k_avg_ms, turbo=True, complete=okh)
             if turbo_res is not None:

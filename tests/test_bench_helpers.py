@@ -4,6 +4,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,3 +36,46 @@ def test_default_run_lists_every_baseline_config():
         assert k in bench.WORKLOADS
     assert bench.WORKLOADS["C4"]["shards"] == 8 and bench.WORKLOADS["C4"]["n_trees"] * 8 == 10000
     assert bench.WORKLOADS["C5pb"].get("reverse_grad") is True  # (reverse accumulation is an opt-in since ABI 3: the workload that measures it says so)
+
+
+def test_dump_writer_keeps_to_float_arrays_within_the_bound(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, finite float32 / float64 only, DUMP_BYTES in all (files, headers included)"""
+    arrs = {"ok": np.array([1, 0, 1], dtype=np.float32), "out": np.arange(12, dtype=np.float32).reshape(3, 4),
+            "samples": np.array([0, 5, 9, 11], dtype=np.float64)}
+    assert bench.write_outputs(str(tmp_path / "d"), arrs) == {"ok": [3], "out": [3, 4], "samples": [4]}
+    for name, a in arrs.items():
+        b = np.load(tmp_path / "d" / f"{name}.npy")
+        assert b.dtype == a.dtype and np.array_equal(a, b)
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "e"), {"ok": np.array([1, 0], dtype=np.uint8)})
+    for bad in (np.nan, np.inf):
+        with pytest.raises(AssertionError):
+            bench.write_outputs(str(tmp_path / "g"), {"out": np.array([1.0, bad], dtype=np.float32)})
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "f"), {"out": np.zeros(bench.DUMP_BYTES // 4, dtype=np.float32)})
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_for_any_number_of_steps(tmp_path):
+    """`bench.py --dump-outputs DIR` on the GPU: the last timed step's outputs, identical whatever --steps (the inputs are seeded), float
+    only, finite and within the bound; the rows of incomplete trees (unspecified) are 0, those of complete trees are what the kernel
+    wrote, finite without any replacement (their sum is: the reference's flag)."""
+    import json
+    import subprocess
+    dumps = []
+    for steps in (1, 3):
+        d = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert line["outputs_dumped"]["shapes"] == {"ok": [64], "samples": [10**5], "out": [64, 10**5]}
+        assert line["outputs_dumped"]["nonfinite_written_as_zero"] == {}
+        files = sorted(os.listdir(d))
+        assert files == ["ok.npy", "out.npy", "samples.npy"] and sum(os.path.getsize(d / f) for f in files) <= bench.DUMP_BYTES
+        dumps.append({f: np.load(d / f) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, dumps[1][f]), f
+    ok, out = dumps[0]["ok.npy"].astype(bool), dumps[0]["out.npy"]
+    assert 0 < ok.sum() < len(ok) and (out[~ok] == 0).all()
