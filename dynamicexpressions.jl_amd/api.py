@@ -35,7 +35,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DE_HIP_LIB (the variable the Julia shim reads too) selects another build of the same library
 LIB_PATH = os.environ.get("DE_HIP_LIB") or os.path.join(_HERE, "csrc", "libde_hip.so")
 
-DE_F32, DE_F64 = 0, 1
+DE_F32, DE_F64, DE_F16 = 0, 1, 2
 GRAD_VARIABLE, GRAD_CONSTANT, GRAD_BOTH = 0, 1, 2
 ABI_VERSION = 3  # DE_HIP_ABI_VERSION of include/de_hip.h this module was written for
 OPT_EARLY_EXIT, OPT_FUSE_DEG1, OPT_FUSE_DEG2, OPT_BUMPER_CHECKS, OPT_TURBO, OPT_FULL_EVAL, OPT_FORWARD_GRAD, OPT_REVERSE_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
@@ -170,9 +170,17 @@ def _dtype_code(dtype) -> int:
         return DE_F32
     if dtype == np.float64:
         return DE_F64
+    if dtype == np.float16:  # evaluation only: binary16 buffers, every operator step rounded to binary16
+        return DE_F16
     # the reference asserts T in (Float32, Float64) for its accelerated back-ends
     # (src/Evaluate.jl:287-289)
-    raise TypeError(f"MI355X back-end supports Float32/Float64, got {dtype}")
+    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64, got {dtype}")
+
+
+def _torch_dtype(dtype):
+    import torch
+    return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
+            np.dtype(np.float16): torch.float16}[np.dtype(dtype)]
 
 
 @dataclass
@@ -339,7 +347,7 @@ def _prep_X(X, dtype):
         import torch
         if X.dim() == 1:  # eval_tree_array(tree, cX::AbstractVector) (src/Evaluate.jl:311-315)
             X = X.reshape(-1, 1)
-        tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+        tdt = _torch_dtype(dtype)
         if X.dtype != tdt:
             X = X.to(tdt)
         F, N = X.shape
@@ -541,8 +549,7 @@ class Population:
         pa = ParamArgs()
         if _is_torch(params):
             import torch
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            params = params.to(tdt)
+            params = params.to(_torch_dtype(self.dtype))
             if params.stride(0) != 1 and params.numel() > 0:
                 params = params.t().contiguous().t()
             P, ncls = params.shape
@@ -589,6 +596,13 @@ class Population:
         pa.n_classes, pa.class_base = ncls, class_base
         keep.extend([params, classes])
         return pa
+
+    def _refuse_f16(self, what: str) -> None:
+        # Float16 populations evaluate only (eval, sum_certificate): the library answers DE_ERR_UNSUPPORTED for the binary16 gradient and
+        # loss entry points, said here before any buffer is prepared
+        if self.dtype == np.float16:
+            name = library().de_status_string(7).decode()
+            raise DeviceError(f"{name}: {what} of a Float16 population (DE_ERR_UNSUPPORTED): Float16 is evaluation only")
 
     def eval(self, X, params=None, classes=None, class_base: int = 1):
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
@@ -650,6 +664,7 @@ class Population:
         "L1") without materialising the [n_trees, N] output: what the reference's optimisation
         consumers compute right after eval_tree_array (``sum(abs2, tree(X, operators) .- y)``,
         test/test_optim.jl:95,99).  Returns (loss[n_trees], ok[n_trees]); loss is NaN where not ok."""
+        self._refuse_f16("eval_loss")
         kind = {"L2": 0, "L1": 1}[loss]
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -697,6 +712,7 @@ class Population:
         2(yhat_j - y_j) * dyhat_dconstants[i, j]``) without the [n_grad, N] Jacobian.  ``loss="pullback"``
         treats ``y`` as the cotangent dY of the ChainRules pullback (src/ChainRules.jl:56-77).
         Returns (loss[n_trees], [dloss_t[n_grad_t] per tree], ok)."""
+        self._refuse_f16("eval_loss_grad")
         kind = {"L2": 0, "L1": 1, "pullback": 2}[loss]
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
@@ -754,6 +770,7 @@ class Population:
         The library reduces class by class over sample ranges, so the samples are ordered by class
         first (a stable sort, done here unless ``grouped=True`` says the caller already did: classes are
         part of the dataset, so a search loop orders it once)."""
+        self._refuse_f16("eval_loss_grad_by_class")
         kind = {"L2": 0, "L1": 1, "pullback": 2}[loss]
         mode = _grad_mode(variable)
         is_t = _is_torch(X)
@@ -832,6 +849,7 @@ class Population:
         """All trees' forward-mode gradients.  Returns (out[n_trees,N], grads, ok) where
         grads is a list of per-tree [n_grad_t, N] Fortran-ordered arrays (views of one
         packed buffer)."""
+        self._refuse_f16("eval_grad")
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -867,6 +885,7 @@ class Population:
         ``dX[t][f, j] = d tree_t / d x_f (x_j) * dY[j]`` — ``dX_dY .* reshape(dY, 1, :)`` — NaN-filled where the
         evaluation is incomplete (:62-64).  Returns (dX[n_trees, n_rows, N], ok); rows = (params,) features.  The
         other half of the pullback, ``dtree``, is ``eval_loss_grad(..., loss="pullback")``."""
+        self._refuse_f16("eval_pullback_dX")
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()
@@ -897,6 +916,7 @@ class Population:
 
     def eval_diff(self, X, direction: int):
         """``direction`` is the 1-based feature index, as in the reference."""
+        self._refuse_f16("eval_diff")
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()
@@ -942,15 +962,17 @@ def _grad_mode(variable) -> int:
 def _x_dtype(X, tree_dtype=None):
     if _is_torch(X):
         import torch
-        return np.dtype(np.float64 if X.dtype == torch.float64 else np.float32)
+        return np.dtype(np.float64 if X.dtype == torch.float64 else np.float16 if X.dtype == torch.float16 else np.float32)
     dt = np.asarray(X).dtype
     if dt == np.float64:
         return np.dtype(np.float64)
     if dt == np.float32:
         return np.dtype(np.float32)
+    if dt == np.float16:
+        return np.dtype(np.float16)
     if dt.kind in "iu":
         return np.dtype(np.float64)
-    raise TypeError(f"MI355X back-end supports Float32/Float64, got {dt}")
+    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64, got {dt}")
 
 
 def eval_tree_array(tree: Node, cX, operators: OperatorEnum, eval_context: Optional[EvalContext] = None,

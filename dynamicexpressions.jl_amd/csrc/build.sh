@@ -107,8 +107,9 @@ for spec in f:float d:double; do  # the reverse-accumulation kernel: one module 
   build_kernels de_rev_threaded.hip $OBJ/de_rt_$tag.o -DDE_RT_T=$ty -DDE_RT_TAG=$tag &
 done
 build_obj de_grad_kernels.hip $OBJ/de_grad_kernels.o &
+build_obj de_half.hip $OBJ/de_half.o & # the binary16 eval kernel (DE_F16): plain hipcc, none of the IR / assembly passes
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_half.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_half.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

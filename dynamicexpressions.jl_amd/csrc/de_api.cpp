@@ -480,6 +480,8 @@ int de_ctx_device(de_ctx_t *c) { return c ? c->device : -1; }
 // later call on this context whose (X, N, ldX) are the declared ones skips its own pass.  X == NULL withdraws the declaration.
 int de_ctx_declare_dataset(de_ctx_t *c, int dtype, const void *X, int64_t N, int64_t ldX, int32_t n_features) {
     if (!c) return DE_ERR_INVALID_ARG;
+    // (a DE_F16 program never runs the priority tiles these keys order: nothing to declare, the declaration in force stays)
+    if (dtype == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_ctx_declare_dataset: DE_F16 evaluation has no priority tiles");
     c->ds_X = nullptr;
     if (!X) return DE_OK;
     if ((dtype != DE_F32 && dtype != DE_F64) || N < 1 || n_features < 1 || ldX < n_features) return fail(c, DE_ERR_INVALID_ARG, "bad dataset shape");

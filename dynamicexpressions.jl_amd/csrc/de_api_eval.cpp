@@ -134,6 +134,7 @@ int de_eval(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
 int de_eval_loss(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                  const void *y, const void *w, int32_t loss_kind, void *loss, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
     if (N < 0 || !ok || (p->n_trees > 0 && (!loss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (loss_kind != DE_LOSS_L2 && loss_kind != DE_LOSS_L1) return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", loss_kind);
     if (!p->threaded)
@@ -150,7 +151,9 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     if (rc != DE_OK) return rc;
     if (p->n_trees == 0) return DE_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    const size_t es = dtype_bytes(p->io);                // the caller's buffers
+    const size_t ces = p->dtype == DE_F32 ? 4 : 8;       // the certificate's per-tree maxima (the compute type)
+    const bool half = p->io == DE_F16;
     const bool ok_dev = is_device_ptr(ok);
     if (N == 0) { // nothing to evaluate: only the constant part of the flag (sum(empty) is finite)
         if (ok_dev) HIP_TRY(c, hipMemcpyAsync(ok, p->host_ok_eval.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
@@ -202,8 +205,8 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     if (cr) {
         rc = ensure_cert_program(c, p);
         if (rc) return rc;
-        HIP_TRY(c, c->sCert.reserve((size_t)p->n_trees * es));
-        HIP_TRY(c, hipMemsetAsync(c->sCert.p, 0, (size_t)p->n_trees * es, c->stream));
+        HIP_TRY(c, c->sCert.reserve((size_t)p->n_trees * ces));
+        HIP_TRY(c, hipMemsetAsync(c->sCert.p, 0, (size_t)p->n_trees * ces, c->stream));
     }
     // ok[] starts as the host-side (constant) part of the flag; the kernel only clears bytes
     if (ok_dev) {
@@ -254,7 +257,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     a.loss = lr ? &la : nullptr;
     HIP_TRY(c, c->sPrio.reserve((size_t)3 * DE_PRIO_MAX_F * sizeof(unsigned long long)));
     a.prio_keys = c->sPrio.p;
-    a.prio_keys_ready = !sX.staged && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &a.prio_keys);
+    a.prio_keys_ready = !half && !sX.staged && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &a.prio_keys);
     a.compact_code = p->d_compact_code;
     a.compact_ints = p->d_compact_ints;
     a.waves = p->waves; // (wave groups: de_api_internal.h)
@@ -273,7 +276,13 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     HIP_TRY(c, time_begin(c));
     a.compacted = &p->last_compacted;
     p->last_compacted = false;
-    HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
+    if (half) { // de_half.hip: no threaded kernel, priority tiles or compaction (de_api_internal.h de_program::io)
+        a.threaded = false;
+        a.prio_keys = nullptr;
+        a.compact_code = nullptr;
+        a.compact_ints = nullptr;
+        HIP_TRY(c, launch_eval_f16(a, c->stream, &c->last_kernel));
+    } else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
     HIP_TRY(c, time_end(c));
     if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
     if (sOut.staged) {
@@ -290,17 +299,28 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         // certified[t]: the reference's `complete` provably equals ok[t].  It tests isfinite(sum(x)) over N values (src/ValueInterface.jl:9)
         // where the device tests every element: the two differ only when all elements are finite and a (partial) sum overflows — impossible
         // while N * max|x| stays below the largest finite value.  ok[t] == 0 means some element is non-finite: its sum is too.
-        std::vector<unsigned char> mx((size_t)p->n_trees * es);
+        std::vector<unsigned char> mx((size_t)p->n_trees * ces);
         std::vector<uint8_t> okh((size_t)p->n_trees);
         HIP_TRY(c, hipMemcpyAsync(mx.data(), c->sCert.p, mx.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(okh.data(), sOk.dev, okh.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const double top = p->dtype == DE_F32 ? (double)std::numeric_limits<float>::max() : std::numeric_limits<double>::max();
+        // (floatmax of the caller's type: a DE_F16 program's sum overflows past 65504 — the reference's Float16 sum accumulates in Float16)
+        const double top = half ? 65504.0 : p->dtype == DE_F32 ? (double)std::numeric_limits<float>::max() : std::numeric_limits<double>::max();
+        // The margin: the summation's own roundings.  A computed partial sum is at most (1 + u)^d * sum|x_i| for a summation tree of depth d
+        // (every addition rounds once, u = half an ulp).  Julia's `sum` is pairwise over blocks of 1024 (Base.pairwise_blocksize), each block
+        // a (possibly @simd-reassociated) loop: d <= 1024 + ceil(log2(N / 1024)) + 8 (the SIMD lanes' combination).  Float32 / Float64:
+        // 1.001 covers (1 + 2^-24)^d with room; binary16 (u = 2^-11) needs the product itself — (1 + 2^-11)^1034 = 1.66: 2049 x 31.90625
+        // (N * max = 65375) sums to Inf16, so it must not be certified.
+        double margin = 1.001;
+        if (half) {
+            const double d = 1024.0 + std::ceil(std::log2(std::max(1.0, (double)N / 1024.0))) + 8.0;
+            margin = std::exp(d * std::log1p(std::ldexp(1.0, -11)));
+        }
         for (int64_t t = 0; t < p->n_trees; t++) {
             double m = p->dtype == DE_F32 ? (double)reinterpret_cast<float *>(mx.data())[t] : reinterpret_cast<double *>(mx.data())[t];
             m = std::max(m, p->cert_cmax[(size_t)t]);
             if (cr->max_abs) cr->max_abs[t] = m;
-            cr->certified[t] = (!okh[(size_t)t] || m * (double)N * 1.001 < top || !(m == m)) ? 1 : 0; // (the margin: the summation's own roundings)
+            cr->certified[t] = (!okh[(size_t)t] || m * (double)N * margin < top || !(m == m)) ? 1 : 0;
             if (!std::isfinite(m) && okh[(size_t)t]) cr->certified[t] = 0;
         }
     }
@@ -319,7 +339,8 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         }
         for (int64_t t = 0; t < p->n_trees; t++) {
             if (okp[t]) continue;
-            if (p->dtype == DE_F32) std::fill_n(static_cast<float *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, std::nanf(""));
+            if (half) std::fill_n(static_cast<_Float16 *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, (_Float16)std::nanf(""));
+            else if (p->dtype == DE_F32) std::fill_n(static_cast<float *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, std::nanf(""));
             else std::fill_n(static_cast<double *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, std::nan(""));
         }
     }

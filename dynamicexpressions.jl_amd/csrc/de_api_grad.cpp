@@ -1115,9 +1115,16 @@ struct ByClassPlan {
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
                           const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan);
+// DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
+static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
+    return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
+}
+#define DE_REFUSE_F16(WHAT) do { if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT); } while (0)
+
 int de_eval_loss_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                       int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
                       const int64_t *dloss_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_grad");
     DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, loss_kind, loss, dloss, dloss_offsets, ok, nullptr));
 }
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
@@ -1332,6 +1339,7 @@ int de_eval_loss_grad_by_class(de_ctx_t *c, de_program_t *p, const void *X, int6
                                const de_param_args_t *pa, int mode, const void *y, const void *w, int32_t loss_kind,
                                const int64_t *class_starts, void *loss, void *dloss, const int64_t *dloss_offsets,
                                void *dparams, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_grad_by_class");
     DE_NOTHROW(c, by_class_impl(c, p, X, N, ldX, pa, mode, y, w, loss_kind, class_starts, loss, dloss, dloss_offsets, dparams, ok));
 }
 static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
@@ -1456,17 +1464,20 @@ static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
 
 int de_eval_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                  int mode, void *out, int64_t ld_out, void *grad, const int64_t *grad_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_grad");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, pa, mode, -1, out, ld_out, grad, grad_offsets, ok));
 }
 
 int de_eval_pullback_dX(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                         const void *dY, void *dX, const int64_t *dX_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_pullback_dX");
     if (c && N > 0 && !dY) return fail(c, DE_ERR_INVALID_ARG, "null cotangent dY");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, pa, DE_GRAD_VARIABLE, -1, nullptr, N, dX, dX_offsets, ok, dY));
 }
 
 int de_eval_diff(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, int32_t direction, void *out,
                  void *dout, int64_t ld_out, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_diff");
     if (direction < 0) return fail(c, DE_ERR_INVALID_ARG, "direction < 0");
     if (p && p->uses_params) return fail(c, DE_ERR_UNSUPPORTED, "eval_diff on parametric trees");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, nullptr, DE_GRAD_VARIABLE, direction, out, ld_out, dout, nullptr, ok));

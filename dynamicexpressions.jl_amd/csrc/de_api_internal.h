@@ -93,7 +93,11 @@ struct de_ctx {
 
 struct de_program {
     de_ctx *ctx = nullptr;
-    int dtype = DE_F32;
+    int dtype = DE_F32; // element type of the COMPUTE (and of every host-side stream): DE_F32 or DE_F64
+    // element type of the caller's buffers — X, constants, parameters, outputs: DE_F16 programs compute in Float32
+    // (dtype == DE_F32, constants are binary16 values Float32 holds exactly) and run de_half.hip's kernel, which rounds every operator
+    // step to binary16; never the threaded kernel, wave groups, priority tiles or compaction
+    int io = DE_F32;
     uint32_t options = 0;
     int32_t n_features = 0, n_params = 0;
     int64_t n_trees = 0, n_nodes = 0;
@@ -259,6 +263,24 @@ int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, 
 // the pool of host threads (de_api.cpp): job(k) for k = 0 .. n - 1 on the pool (false: busy, nothing was run); threads a pass of n items gets
 bool host_pool_run(int n, const std::function<void(int)> &job);
 unsigned host_threads_for(int64_t n, int64_t grain);
+}
+
+// Bytes of one element of a dtype's buffers, and element k of such a buffer as / from double (binary16 rounds to nearest even).
+static inline size_t dtype_bytes(int dtype) { return dtype == DE_F64 ? 8 : dtype == DE_F16 ? 2 : 4; }
+static inline double load_elem(int dtype, const void *p, size_t k) {
+    if (dtype == DE_F64) return static_cast<const double *>(p)[k];
+    if (dtype == DE_F16) return (double)static_cast<const _Float16 *>(p)[k];
+    return (double)static_cast<const float *>(p)[k];
+}
+static inline void store_elem(int dtype, void *p, size_t k, double v) {
+    if (dtype == DE_F64) static_cast<double *>(p)[k] = v;
+    else if (dtype == DE_F16) static_cast<_Float16 *>(p)[k] = (_Float16)v;
+    else static_cast<float *>(p)[k] = (float)v;
+}
+// de_half.hip: the binary16 eval kernel (flat switch over the bound program, PARAMS and CERT variants); EvalArgs as for launch_eval
+namespace de {
+hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **kernel_name);
+void eval_plan_f16(int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk); // (de_eval_plan)
 }
 
 static inline bool in_one_window(const void *ptr, size_t bytes) {

@@ -3,8 +3,10 @@
 #include "de_api_internal.h"
 
 // (src/Evaluate.jl:1002-1067: every node's output is validity-tested; the arithmetic goes on, IEEE propagates what it must).
+// half: a DE_F16 program (T = float) — every result rounded to binary16, as de_half.hip does (+ - * / in Float32 rounded once more to
+// binary16 are the correctly rounded binary16 results: 24 >= 2 * 11 + 2).
 template <typename T>
-static bool host_fold_eval(const de_tape_node_t *nd, int64_t n, const double *consts, const int64_t *csrc, T *value) {
+static bool host_fold_eval(const de_tape_node_t *nd, int64_t n, const double *consts, const int64_t *csrc, T *value, bool half = false) {
     T stack_small[32];
     std::vector<T> stack_big;
     T *st = stack_small;
@@ -22,6 +24,7 @@ static bool host_fold_eval(const de_tape_node_t *nd, int64_t n, const double *co
             case DE_B_MUL: v = a * b; break;
             default: v = a / b; break; // DE_B_DIV (host_foldable admits nothing else)
             }
+            if (half) v = (T)(_Float16)v;
         }
         ok = ok && std::isfinite(v);
         st[sp++] = v;
@@ -122,6 +125,7 @@ static int make_threaded(de_ctx *c, de_program *p) {
     dbg_lap(nullptr);
     // the LDS-staged kernels need (n_features + n_slots) rows of 4112 B; wider X uses the direct variant
     p->direct = (size_t)eval_rows(p) * 257 * 16 > 150 * 1024; // (the flat-switch kernel's geometry: 256 threads x 16 bytes per row; it gathers the features of a wider X from global memory)
+    if (p->io == DE_F16) return DE_OK; // binary16 programs run de_half.hip's flat-switch kernel only
     // the threaded kernel's rows are a quarter of that (one wave's 64 vectors): it stages X up to ~140 rows — and shares them among the
     // waves of a wave group (round 6: F = 36 ... 120 ran the gathering flat-switch kernel, 14 - 20 ms per 10^6 samples x 1000 trees)
     // (a program the flat-switch kernel would gather for takes the threaded kernel while a group of FOUR waves fits: one wave per CU
@@ -378,6 +382,7 @@ static int upload_ok_eval(de_ctx *c, de_program *p) {
 static int refresh_folds(de_ctx *c, de_program *p, bool aux_current = false) {
     if (!p->folded || p->folds.empty()) return DE_OK; // (a CSE-only eval program has no constant subtrees to evaluate)
     const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    const size_t ies = dtype_bytes(p->io); // (the auxiliary program's buffers: a DE_F16 program's auxiliary program is DE_F16 too)
     const size_t nf = p->folds.size();
     p->fold_ok.assign(nf, 0);
     parallel_for_trees((int64_t)nf, [&](int64_t j) {
@@ -387,7 +392,7 @@ static int refresh_folds(de_ctx *c, de_program *p, bool aux_current = false) {
         const int64_t *csrc = p->aux_const_src.data() + p->fold_coff[(size_t)j];
         double v;
         bool ok;
-        if (p->dtype == DE_F32) { float f; ok = host_fold_eval<float>(nd, n, p->consts.data(), csrc, &f); v = (double)f; }
+        if (p->dtype == DE_F32) { float f; ok = host_fold_eval<float>(nd, n, p->consts.data(), csrc, &f, p->io == DE_F16); v = (double)f; }
         else ok = host_fold_eval<double>(nd, n, p->consts.data(), csrc, &v);
         p->fold_ok[(size_t)j] = ok ? 1 : 0;
         write_imm(p->fcode[(size_t)p->folds[(size_t)j].instr], p->dtype, v);
@@ -424,23 +429,18 @@ static int refresh_folds(de_ctx *c, de_program *p, bool aux_current = false) {
     const size_t na = p->aux_fold.size();
     int rc = DE_OK;
     if (!aux_current) {
-        std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * es);
-        for (size_t k = 0; k < p->aux_csrc.size(); k++) {
-            const double v = p->consts[(size_t)p->aux_csrc[k]];
-            if (p->dtype == DE_F32) reinterpret_cast<float *>(ac.data())[k] = (float)v;
-            else reinterpret_cast<double *>(ac.data())[k] = v;
-        }
+        std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * ies);
+        for (size_t k = 0; k < p->aux_csrc.size(); k++) store_elem(p->io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]]);
         rc = de_program_set_consts(p->aux, ac.data());
         if (rc != DE_OK) return fail(c, rc, "constant folding: %s", p->aux->ctx->err.c_str());
     }
-    std::vector<unsigned char> X(std::max<size_t>((size_t)p->n_features, 1) * es, 0), out(na * es);
+    std::vector<unsigned char> X(std::max<size_t>((size_t)p->n_features, 1) * ies, 0), out(na * ies);
     std::vector<uint8_t> aok(na, 0);
     rc = de_eval(c, p->aux, X.data(), 1, std::max<int64_t>(p->n_features, 1), nullptr, out.data(), 1, aok.data());
     if (rc != DE_OK) return rc;
     for (size_t a = 0; a < na; a++) {
         const size_t j = (size_t)p->aux_fold[a];
-        const double v = p->dtype == DE_F32 ? (double)reinterpret_cast<float *>(out.data())[a]
-                                            : reinterpret_cast<double *>(out.data())[a];
+        const double v = load_elem(p->io, out.data(), a);
         p->fold_ok[j] = aok[a];
         write_imm(p->fcode[(size_t)p->folds[j].instr], p->dtype, v);
     }
@@ -478,7 +478,10 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
     if (!ctx) return DE_ERR_INVALID_ARG;
     if (!out_program) return fail(ctx, DE_ERR_INVALID_ARG, "out_program is null");
     *out_program = nullptr;
-    if (dtype != DE_F32 && dtype != DE_F64) return fail(ctx, DE_ERR_INVALID_ARG, "dtype must be DE_F32 or DE_F64");
+    if (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16) return fail(ctx, DE_ERR_INVALID_ARG, "dtype must be DE_F32, DE_F64 or DE_F16");
+    // DE_F16: binary16 buffers, a Float32 program (de_api_internal.h de_program::io)
+    const int io = dtype;
+    if (dtype == DE_F16) dtype = DE_F32;
     if (n_trees < 0 || n_features < 0 || n_params < 0 || n_features > 65535 || n_params > 65535)
         return fail(ctx, DE_ERR_INVALID_ARG, "bad sizes");
     if (n_trees > 0 && (!nodes || !node_offsets || !const_offsets))
@@ -500,6 +503,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
     try {
         p->ctx = ctx;
         p->dtype = dtype;
+        p->io = io;
         p->options = options;
         p->n_features = n_features;
         p->n_params = n_params;
@@ -597,8 +601,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                     p->n_consts_tree[(size_t)t] = (int32_t)(c1 - c0);
                     const int32_t ib = p->code_off[(size_t)t];
                     for (int64_t k = 0; k < c1 - c0; k++) {
-                        const double v = dtype == DE_F32 ? (double)static_cast<const float *>(consts)[c0 + k]
-                                                         : static_cast<const double *>(consts)[c0 + k];
+                        const double v = load_elem(io, consts, (size_t)(c0 + k));
                         p->consts[(size_t)(cb + k)] = v;
                         // (a CSE lowering has no instruction for the later occurrences of a constant inside a shared subtree: -1)
                         p->const_instr[(size_t)(cb + k)] = tp.const_instr[(size_t)k] >= 0 ? ib + tp.const_instr[(size_t)k] : -1;
@@ -701,11 +704,12 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                 // which folds stay on the host: subtrees of + - * / only (the turbo division is not IEEE: such programs fold everything on
                 // the device, with the operators they evaluate with; DE_NO_HOST_FOLD=1: everything on the device, for A/B tests)
                 const char *nh = getenv("DE_NO_HOST_FOLD");
-                const bool host_fold = !(nh && *nh == '1') && !(options & DE_OPT_TURBO);
+                const bool host_fold = !(nh && *nh == '1') && !(io != DE_F16 && (options & DE_OPT_TURBO)); // (DE_F16 ignores the turbo bit)
                 // ... and which go to de_fold_kernel (everything else whose evaluation stack fits; a turbo program evaluates with other
                 // operators than that kernel has: its subtrees stay with the auxiliary program; DE_NO_KERNEL_FOLD=1 for A/B tests)
                 const char *nk_env = getenv("DE_NO_KERNEL_FOLD");
-                const bool kernel_fold = !(nk_env && *nk_env == '1') && !(options & DE_OPT_TURBO);
+                // (a DE_F16 program's subtrees: de_fold_kernel does not round to binary16 — the auxiliary program, which runs de_half.hip, does)
+                const bool kernel_fold = !(nk_env && *nk_env == '1') && !(options & DE_OPT_TURBO) && io != DE_F16;
                 p->fold_host.assign(n_folds, 0);
                 parallel_for_trees((int64_t)n_folds, [&](int64_t j) {
                     const de_tape_node_t *nd = anodes.data() + anoff[(size_t)j];
@@ -776,13 +780,9 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                 p->folded = true;
                 lap("folds: classify, kernel image, auxiliary tapes");
                 if (!p->aux_fold.empty()) {
-                    std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * es, 0);
-                    for (size_t k = 0; k < p->aux_csrc.size(); k++) {
-                        const double v = p->consts[(size_t)p->aux_csrc[k]];
-                        if (dtype == DE_F32) reinterpret_cast<float *>(ac.data())[k] = (float)v;
-                        else reinterpret_cast<double *>(ac.data())[k] = v;
-                    }
-                    int rc = create_impl(ctx, dtype, xnodes.data(), xnoff.data(), (int64_t)p->aux_fold.size(), ac.data(),
+                    std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * dtype_bytes(io), 0);
+                    for (size_t k = 0; k < p->aux_csrc.size(); k++) store_elem(io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]]);
+                    int rc = create_impl(ctx, io, xnodes.data(), xnoff.data(), (int64_t)p->aux_fold.size(), ac.data(),
                                          xcoff.data(), n_features, 0, options, false, &p->aux);
                     if (rc != DE_OK) return rc;
                     lap("aux program (create)");
@@ -901,8 +901,7 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
     try {
         parallel_tree_ranges((int64_t)p->consts.size(), [&](int, int64_t kb, int64_t ke) {
             for (size_t k = (size_t)kb; k < (size_t)ke; k++) {
-                const double v = p->dtype == DE_F32 ? (double)static_cast<const float *>(consts)[k]
-                                                    : static_cast<const double *>(consts)[k];
+                const double v = load_elem(p->io, consts, k);
                 p->consts[k] = v;
                 if (p->const_instr[k] >= 0) write_imm(p->code[(size_t)p->const_instr[k]], p->dtype, v);
                 if (p->folded && p->fconst_instr[k] >= 0) write_imm(p->fcode[(size_t)p->fconst_instr[k]], p->dtype, v);
@@ -1094,7 +1093,8 @@ int de_prio_tiles_wanted(int64_t N, int32_t n_features, int64_t n_trees) { retur
 
 int de_eval_plan(const de_program_t *p, int64_t N, int32_t *plan) {
     if (!p || !plan || N < 0) return DE_ERR_INVALID_ARG;
-    eval_plan(p->dtype, p->n_trees, N, &plan[0], &plan[1], &plan[2], p->threaded ? p->waves : 1);
+    if (p->io == DE_F16) eval_plan_f16(p->n_trees, N, &plan[0], &plan[1], &plan[2]);
+    else eval_plan(p->dtype, p->n_trees, N, &plan[0], &plan[1], &plan[2], p->threaded ? p->waves : 1);
     return DE_OK;
 }
 
@@ -1316,7 +1316,9 @@ int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, in
 int64_t de_lower_tape(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
                       int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, uint32_t *words,
                       int64_t cap, int32_t *meta) {
-    if (!nodes || (dtype != DE_F32 && dtype != DE_F64) || (n_consts > 0 && !consts)) return -DE_ERR_INVALID_ARG;
+    if (!nodes || (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16) || (n_consts > 0 && !consts)) return -DE_ERR_INVALID_ARG;
+    const int io = dtype; // DE_F16: binary16 constants, lowered like a Float32 tape
+    if (dtype == DE_F16) dtype = DE_F32;
     try {
         LowerOptions lo;
         lo.early_exit = (options & DE_OPT_EARLY_EXIT) != 0;
@@ -1334,8 +1336,7 @@ int64_t de_lower_tape(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, c
         if (rc != DE_OK) return -rc;
         bool ok_eval = true, ok_grad = true;
         for (int64_t k = 0; k < n_consts; k++) {
-            const double v = dtype == DE_F32 ? (double)static_cast<const float *>(consts)[k]
-                                             : static_cast<const double *>(consts)[k];
+            const double v = load_elem(io, consts, (size_t)k);
             if (tp.const_instr[(size_t)k] >= 0) write_imm(tp.code[(size_t)tp.const_instr[(size_t)k]], dtype, v);
             const bool fin = finite_in(dtype, v);
             ok_grad = ok_grad && fin;
@@ -1370,7 +1371,7 @@ int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_no
         if (nw < 0) return nw;
         std::vector<BoundInstr> b, f;
         bind_tree(reinterpret_cast<const Instr *>(g.data()), (size_t)nw / 4, (options & DE_OPT_EARLY_EXIT) != 0, n_features, &b);
-        if (stage == 3) fuse_tree(b.data(), b.size(), &f);
+        if (stage == 3 && dtype != DE_F16) fuse_tree(b.data(), b.size(), &f); // (a DE_F16 program never runs the threaded kernel: no fused form)
         const std::vector<BoundInstr> &o = stage == 3 ? f : b;
         const int64_t n = (int64_t)o.size() * 4;
         if (!words || cap < n) return n;

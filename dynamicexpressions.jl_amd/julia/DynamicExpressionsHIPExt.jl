@@ -31,7 +31,7 @@ const DE_OK = Cint(0)
 const DE_ERR_UNSUPPORTED_OP = Cint(3)
 const DE_LEAF_CONST, DE_LEAF_FEATURE, DE_LEAF_PARAM, DE_LEAF_SHARED = UInt8(0), UInt8(1), UInt8(2), UInt8(3)
 const DE_OP_SHARE = UInt8(0xFE)   # include/de_opcodes.h: "the subtree just emitted is shared subtree `arg`"
-const DE_F32, DE_F64 = Cint(0), Cint(1)
+const DE_F32, DE_F64, DE_F16 = Cint(0), Cint(1), Cint(2)
 const DE_OPT_EARLY_EXIT, DE_OPT_FUSE_DEG1, DE_OPT_FUSE_DEG2, DE_OPT_BUMPER_CHECKS, DE_OPT_TURBO, DE_OPT_FULL_EVAL, DE_OPT_FORWARD_GRAD, DE_OPT_REVERSE_GRAD =
     UInt32(1), UInt32(2), UInt32(4), UInt32(8), UInt32(16), UInt32(32), UInt32(64), UInt32(128)
 # The ABI this file was written for (include/de_hip.h lists what changed between versions).  Version 2: the rows / gradients of a tree
@@ -51,6 +51,9 @@ end
 const OPERATOR_LIMIT_BEFORE_SLOWDOWN = 15   # src/Evaluate.jl:14
 dtype_code(::Type{Float32}) = DE_F32
 dtype_code(::Type{Float64}) = DE_F64
+# Float16: evaluation only (every operator step rounded to binary16, DESIGN.md §13); the gradient methods below stay
+# Float32 / Float64, so a Float16 gradient keeps the reference CPU path
+dtype_code(::Type{Float16}) = DE_F16
 
 struct UnsupportedOperator <: Exception
     f::Any
@@ -314,7 +317,7 @@ Drop-in for `eval_tree_array`'s body: same `(output, complete)` tuple, `cX` is t
 function _hip_eval_tree_array(
     tree::AbstractExpressionNode{T}, cX::AbstractMatrix{T}, operators::OperatorEnum,
     eval_context::EvalContext; full_eval::Bool=false,
-) where {T<:Union{Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64}}
     optable = try
         opcode_table(operators)
     catch e
@@ -381,7 +384,7 @@ function HIPPopulation(
     trees::AbstractVector{<:AbstractExpressionNode{T}}, operators::OperatorEnum, n_features::Integer;
     eval_context::EvalContext=EvalContext(), n_params::Integer=0, full_eval::Bool=false, forward_grad::Bool=false,
     reverse_grad::Bool=false,
-) where {T<:Union{Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64}}
     optable = opcode_table(operators)
     nodes, consts, cse = TapeNode[], T[], TapeNode[]
     node_off, const_off, cse_off = Int64[0], Int64[0], Int64[0]

@@ -208,6 +208,12 @@ def max_feature(tree: Node) -> int:
                 and not getattr(n, "is_parameter", False)), default=0)
 
 
+def _consts_as(consts, dtype) -> np.ndarray:
+    # a constant beyond the element type's range IS Inf there (Float16(1e5) == Inf16 in Julia): data, not a warning
+    with np.errstate(over="ignore"):
+        return np.asarray(consts, dtype=dtype)
+
+
 def flatten(tree: Node, operators: OperatorEnum, dtype=np.float32) -> Tuple[np.ndarray, np.ndarray]:
     """Tree -> (tape, consts).
 
@@ -221,7 +227,7 @@ def flatten(tree: Node, operators: OperatorEnum, dtype=np.float32) -> Tuple[np.n
     arg: List[int] = []
     consts: List[float] = []
     _flatten_into(tree, operators, deg, op, arg, consts, {})
-    return _tape_of(deg, op, arg), np.asarray(consts, dtype=dtype)
+    return _tape_of(deg, op, arg), _consts_as(consts, dtype)
 
 
 def _flatten_into(tree: Node, operators: OperatorEnum, deg: List[int], op: List[int], arg: List[int], consts: List[float],
@@ -365,7 +371,7 @@ def flatten_population(trees: Sequence[Node], operators: OperatorEnum, dtype=np.
         _flatten_into(t, operators, deg, op, arg, consts, opcache)
         node_offsets[k + 1] = len(deg)
         const_offsets[k + 1] = len(consts)
-    return _tape_of(deg, op, arg), node_offsets, np.asarray(consts, dtype=dtype), const_offsets
+    return _tape_of(deg, op, arg), node_offsets, _consts_as(consts, dtype), const_offsets
 
 
 def string_tree(tree: Node, operators: OperatorEnum) -> str:

@@ -67,7 +67,10 @@ extern "C" {
  *      (d) a process may hold contexts on several devices (the handler caches are per device).
  *   3  round 6.  (a) de_eval_loss_grad / de_eval_loss_grad_by_class run FORWARD duals unless the program carries the new option bit
  *      DE_OPT_REVERSE_GRAD (ABI 2 picked reverse accumulation from 8 gradient rows per tree on; DE_OPT_FORWARD_GRAD asked for what is now
- *      the default): same values to rounding, the reference's flags exactly; (b) new exports, all additive (see below). */
+ *      the default): same values to rounding, the reference's flags exactly; (b) new exports, all additive (see below).
+ *      Additive since: (c) dtype DE_F16 (IEEE binary16 X / constants / parameters / outputs, every operator rounded to binary16 —
+ *      Julia's Float16 arithmetic) for de_program_create(_cse), de_program_set_consts, de_eval, de_eval_sum_certificate,
+ *      de_eval_tree_array and the host-only / debug hooks; the gradient, loss and dataset entry points answer DE_ERR_UNSUPPORTED for it. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -82,7 +85,12 @@ typedef enum de_status {
     DE_ERR_RCCL = 8            /* librccl.so missing or an RCCL call failed (de_dist_last_error) */
 } de_status_t;
 
-typedef enum de_dtype { DE_F32 = 0, DE_F64 = 1 } de_dtype_t;
+/* DE_F16: binary16 elements (2 bytes) everywhere the dtype sizes a buffer; computed in Float32 registers and rounded to binary16 after
+ * every operator step.  Evaluation only: de_eval_grad / _diff / _pullback_dX, de_eval_loss(_grad, _grad_by_class) and
+ * de_ctx_declare_dataset return DE_ERR_UNSUPPORTED for an F16 program or dtype and leave their outputs untouched.  F16 programs never
+ * run the threaded kernel (de_eval_plan / de_program_dump report the flat-switch kernel's form); a feature matrix too wide for its LDS
+ * tile is gathered from global memory as for Float32.  de_eval_sum_certificate refuses such wide programs for every dtype. */
+typedef enum de_dtype { DE_F32 = 0, DE_F64 = 1, DE_F16 = 2 } de_dtype_t;
 
 /* Gradient modes of eval_grad_tree_array (src/EvaluateDerivative.jl:200-210). */
 typedef enum de_grad_mode {
@@ -312,8 +320,9 @@ int de_eval(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t
  * (src/ValueInterface.jl:9); the kernels test every element.  The two agree unless all elements are finite and the SUM overflows — values
  * of ~floatmax / N.  This call evaluates the population once more through a certificate pass (every operator result tested, nothing stored)
  * and reports per tree: ok[t] as de_eval would (host or device array), certified[t] (host) = 1 when the reference's `complete` provably
- * equals ok[t] — some element is non-finite (its sum is too), or N * max|tested value or constant operand| stays below the largest finite
- * value —, max_abs[t] (host doubles, may be NULL) = that maximum.  Trees with certified[t] == 0 are the only ones whose flag a caller who
+ * equals ok[t] — some element is non-finite (its sum is too), or N * max|tested value or constant operand| times the summation's rounding
+ * margin stays below the largest finite value (1.001 for Float32 / Float64; (1 + 2^-11)^d for DE_F16, d = the depth of Julia's pairwise sum,
+ * 1.66 at N = 2049) —, max_abs[t] (host doubles, may be NULL) = that maximum.  Trees with certified[t] == 0 are the only ones whose flag a caller who
  * needs the reference's bit has to re-derive on the CPU.  Programs without DE_OPT_EARLY_EXIT sum nothing: all certified.  Slower than
  * de_eval (the flat-switch kernel): a checker, not the hot path. */
 int de_eval_sum_certificate(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
