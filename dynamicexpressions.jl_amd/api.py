@@ -35,7 +35,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DE_HIP_LIB (the variable the Julia shim reads too) selects another build of the same library
 LIB_PATH = os.environ.get("DE_HIP_LIB") or os.path.join(_HERE, "csrc", "libde_hip.so")
 
-DE_F32, DE_F64, DE_F16 = 0, 1, 2
+DE_F32, DE_F64, DE_F16, DE_CF32, DE_CF64 = 0, 1, 2, 3, 4
+COMPLEX_DTYPES = (np.dtype(np.complex64), np.dtype(np.complex128))
 GRAD_VARIABLE, GRAD_CONSTANT, GRAD_BOTH = 0, 1, 2
 ABI_VERSION = 3  # DE_HIP_ABI_VERSION of include/de_hip.h this module was written for
 OPT_EARLY_EXIT, OPT_FUSE_DEG1, OPT_FUSE_DEG2, OPT_BUMPER_CHECKS, OPT_TURBO, OPT_FULL_EVAL, OPT_FORWARD_GRAD, OPT_REVERSE_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
@@ -45,7 +46,7 @@ EXPORTS = [
     "de_opcode_degree", "de_status_string", "de_ctx_create", "de_ctx_destroy", "de_ctx_set_stream",
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
     "de_program_set_consts", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
-    "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
+    "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
@@ -130,6 +131,10 @@ def library() -> C.CDLL:
     lib.de_lower_tape.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, vp, i64, vp]
     lib.de_lower_tape_stage.restype = i64
     lib.de_lower_tape_stage.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, C.c_int, vp, i64]
+    for fn in (lib.de_lower_tape_complex, lib.de_lower_tape_stage_complex):  # (complex tapes: the same arguments)
+        fn.restype = i64
+    lib.de_lower_tape_complex.argtypes = lib.de_lower_tape.argtypes
+    lib.de_lower_tape_stage_complex.argtypes = lib.de_lower_tape_stage.argtypes
     lib.de_eval.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, i64, vp]
     lib.de_eval_loss.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.c_int32, vp, vp]
     lib.de_eval_loss_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.c_int32, vp, vp, vp, vp]
@@ -172,15 +177,20 @@ def _dtype_code(dtype) -> int:
         return DE_F64
     if dtype == np.float16:  # evaluation only: binary16 buffers, every operator step rounded to binary16
         return DE_F16
+    if dtype == np.complex64:  # evaluation only: interleaved (re, im) buffers, Julia's Complex methods
+        return DE_CF32
+    if dtype == np.complex128:
+        return DE_CF64
     # the reference asserts T in (Float32, Float64) for its accelerated back-ends
     # (src/Evaluate.jl:287-289)
-    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64, got {dtype}")
+    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64/ComplexF32/ComplexF64, got {dtype}")
 
 
 def _torch_dtype(dtype):
     import torch
     return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-            np.dtype(np.float16): torch.float16}[np.dtype(dtype)]
+            np.dtype(np.float16): torch.float16, np.dtype(np.complex64): torch.complex64,
+            np.dtype(np.complex128): torch.complex128}[np.dtype(dtype)]
 
 
 @dataclass
@@ -371,8 +381,9 @@ def lower_tape(tape, consts, n_features: int, n_params: int = 0, options: int = 
     consts = np.ascontiguousarray(consts, dtype=dtype)
     meta = np.zeros(4, dtype=np.int32)
     cp = consts.ctypes.data if consts.size else None
-    n = lib.de_lower_tape(_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features,
-                          n_params, options, None, 0, meta.ctypes.data)
+    lower = lib.de_lower_tape_complex if dtype in COMPLEX_DTYPES else lib.de_lower_tape
+    n = lower(_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features,
+              n_params, options, None, 0, meta.ctypes.data)
     if n < 0:
         code = int(-n)
         name = lib.de_status_string(code).decode()
@@ -381,8 +392,8 @@ def lower_tape(tape, consts, n_features: int, n_params: int = 0, options: int = 
             raise UnsupportedOperatorError(name)
         raise ValueError(name)
     w = np.zeros(max(int(n), 1), dtype=np.uint32)
-    lib.de_lower_tape(_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features,
-                      n_params, options, w.ctypes.data, w.size, meta.ctypes.data)
+    lower(_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features,
+          n_params, options, w.ctypes.data, w.size, meta.ctypes.data)
     return w[:int(n)].reshape(-1, 4), dict(n_slots=int(meta[0]), host_ok_eval=bool(meta[1]),
                                            host_ok_grad=bool(meta[2]), uses_params=bool(meta[3]))
 
@@ -396,11 +407,12 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     consts = np.ascontiguousarray(consts, dtype=dtype)
     cp = consts.ctypes.data if consts.size else None
     args = (_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features, n_params, options, stage)
-    n = lib.de_lower_tape_stage(*args, None, 0)
+    stage_fn = lib.de_lower_tape_stage_complex if dtype in COMPLEX_DTYPES else lib.de_lower_tape_stage
+    n = stage_fn(*args, None, 0)
     if n < 0:
         raise ValueError(lib.de_status_string(int(-n)).decode())
     w = np.zeros(max(int(n), 1), dtype=np.uint32)
-    lib.de_lower_tape_stage(*args, w.ctypes.data, w.size)
+    stage_fn(*args, w.ctypes.data, w.size)
     return w[:int(n)].reshape(-1, 4)
 
 
@@ -598,11 +610,14 @@ class Population:
         return pa
 
     def _refuse_f16(self, what: str) -> None:
-        # Float16 populations evaluate only (eval, sum_certificate): the library answers DE_ERR_UNSUPPORTED for the binary16 gradient and
-        # loss entry points, said here before any buffer is prepared
+        # Float16 and complex populations evaluate only (eval, sum_certificate): the library answers DE_ERR_UNSUPPORTED for their gradient
+        # and loss entry points, said here before any buffer is prepared
         if self.dtype == np.float16:
             name = library().de_status_string(7).decode()
             raise DeviceError(f"{name}: {what} of a Float16 population (DE_ERR_UNSUPPORTED): Float16 is evaluation only")
+        if self.dtype in COMPLEX_DTYPES:
+            name = library().de_status_string(7).decode()
+            raise DeviceError(f"{name}: {what} of a {self.dtype} population (DE_ERR_UNSUPPORTED): complex data is evaluation only")
 
     def eval(self, X, params=None, classes=None, class_base: int = 1):
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
@@ -962,8 +977,11 @@ def _grad_mode(variable) -> int:
 def _x_dtype(X, tree_dtype=None):
     if _is_torch(X):
         import torch
-        return np.dtype(np.float64 if X.dtype == torch.float64 else np.float16 if X.dtype == torch.float16 else np.float32)
+        return np.dtype({torch.float64: np.float64, torch.float16: np.float16, torch.complex64: np.complex64,
+                         torch.complex128: np.complex128}.get(X.dtype, np.float32))
     dt = np.asarray(X).dtype
+    if dt in COMPLEX_DTYPES:
+        return dt
     if dt == np.float64:
         return np.dtype(np.float64)
     if dt == np.float32:
@@ -972,7 +990,7 @@ def _x_dtype(X, tree_dtype=None):
         return np.dtype(np.float16)
     if dt.kind in "iu":
         return np.dtype(np.float64)
-    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64, got {dt}")
+    raise TypeError(f"MI355X back-end supports Float16/Float32/Float64/ComplexF32/ComplexF64, got {dt}")
 
 
 def eval_tree_array(tree: Node, cX, operators: OperatorEnum, eval_context: Optional[EvalContext] = None,
@@ -1029,7 +1047,8 @@ class Expression:
             raise ValueError("expression references a feature beyond size(X, 1)")
         out, ok = eval_tree_array(self.tree, X, self.operators, eval_context)
         if not ok:
-            out[...] = float("nan")  # set_nan!, src/Utils.jl:73-76
+            # set_nan!, src/Utils.jl:73-76 (complex: NaN + NaN im)
+            out[...] = complex(float("nan"), float("nan")) if (out.is_complex() if _is_torch(out) else np.iscomplexobj(out)) else float("nan")
         return out
 
     def grad(self, X, variable: Union[bool, str] = True):

@@ -482,6 +482,7 @@ int de_ctx_declare_dataset(de_ctx_t *c, int dtype, const void *X, int64_t N, int
     if (!c) return DE_ERR_INVALID_ARG;
     // (a DE_F16 program never runs the priority tiles these keys order: nothing to declare, the declaration in force stays)
     if (dtype == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_ctx_declare_dataset: DE_F16 evaluation has no priority tiles");
+    if (dtype == DE_CF32 || dtype == DE_CF64) return fail(c, DE_ERR_UNSUPPORTED, "de_ctx_declare_dataset: complex evaluation has no priority tiles");
     c->ds_X = nullptr;
     if (!X) return DE_OK;
     if ((dtype != DE_F32 && dtype != DE_F64) || N < 1 || n_features < 1 || ldX < n_features) return fail(c, DE_ERR_INVALID_ARG, "bad dataset shape");

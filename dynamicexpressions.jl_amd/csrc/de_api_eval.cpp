@@ -81,7 +81,13 @@ static int ensure_cert_program(de_ctx *c, de_program *p) {
         double cm = 0.0;
         for (Instr &ins : tmp) {
             if ((ins.hdr & H_OP_MASK) != DOP_LOAD) ins.hdr |= H_CHECK_OUT;
-            if (((ins.hdr >> H_SRC_SHIFT) & H_SRC_MASK) == SRC_CONST) {
+            if (((ins.hdr >> H_SRC_SHIFT) & H_SRC_MASK) == SRC_CONST && is_complex_io(p->io)) { // (the immediate indexes the constant table)
+                const size_t e = ins.imm.u32[0];
+                for (int q = 0; q < 2 && 2 * e + 1 < p->ctab.size(); q++) {
+                    const double v = p->ctab[2 * e + (size_t)q];
+                    if (v == v) cm = std::max(cm, std::fabs(v));
+                }
+            } else if (((ins.hdr >> H_SRC_SHIFT) & H_SRC_MASK) == SRC_CONST) {
                 const double v = p->dtype == DE_F32 ? (double)ins.imm.f32 : ins.imm.f64;
                 if (v == v) cm = std::max(cm, std::fabs(v));
             }
@@ -135,6 +141,7 @@ int de_eval_loss(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t
                  const void *y, const void *w, int32_t loss_kind, void *loss, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
     if (N < 0 || !ok || (p->n_trees > 0 && (!loss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (loss_kind != DE_LOSS_L2 && loss_kind != DE_LOSS_L1) return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", loss_kind);
     if (!p->threaded)
@@ -154,6 +161,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     const size_t es = dtype_bytes(p->io);                // the caller's buffers
     const size_t ces = p->dtype == DE_F32 ? 4 : 8;       // the certificate's per-tree maxima (the compute type)
     const bool half = p->io == DE_F16;
+    const bool cplx = is_complex_io(p->io);
     const bool ok_dev = is_device_ptr(ok);
     if (N == 0) { // nothing to evaluate: only the constant part of the flag (sum(empty) is finite)
         if (ok_dev) HIP_TRY(c, hipMemcpyAsync(ok, p->host_ok_eval.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
@@ -257,7 +265,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     a.loss = lr ? &la : nullptr;
     HIP_TRY(c, c->sPrio.reserve((size_t)3 * DE_PRIO_MAX_F * sizeof(unsigned long long)));
     a.prio_keys = c->sPrio.p;
-    a.prio_keys_ready = !half && !sX.staged && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &a.prio_keys);
+    a.prio_keys_ready = !half && !cplx && !sX.staged && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &a.prio_keys);
     a.compact_code = p->d_compact_code;
     a.compact_ints = p->d_compact_ints;
     a.waves = p->waves; // (wave groups: de_api_internal.h)
@@ -282,6 +290,12 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         a.compact_code = nullptr;
         a.compact_ints = nullptr;
         HIP_TRY(c, launch_eval_f16(a, c->stream, &c->last_kernel));
+    } else if (cplx) { // de_complex.hip: the same restrictions, plus the program's constant table
+        a.threaded = false;
+        a.prio_keys = nullptr;
+        a.compact_code = nullptr;
+        a.compact_ints = nullptr;
+        HIP_TRY(c, launch_eval_complex(p->io, a, p->d_ctab, c->stream, &c->last_kernel));
     } else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
     HIP_TRY(c, time_end(c));
     if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
@@ -339,7 +353,10 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         }
         for (int64_t t = 0; t < p->n_trees; t++) {
             if (okp[t]) continue;
-            if (half) std::fill_n(static_cast<_Float16 *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, (_Float16)std::nanf(""));
+            // (complex: NaN + NaN im — both components of the N elements)
+            if (cplx && p->dtype == DE_F32) std::fill_n(static_cast<float *>(out) + 2 * (size_t)t * (size_t)ld_out, 2 * (size_t)N, std::nanf(""));
+            else if (cplx) std::fill_n(static_cast<double *>(out) + 2 * (size_t)t * (size_t)ld_out, 2 * (size_t)N, std::nan(""));
+            else if (half) std::fill_n(static_cast<_Float16 *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, (_Float16)std::nanf(""));
             else if (p->dtype == DE_F32) std::fill_n(static_cast<float *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, std::nanf(""));
             else std::fill_n(static_cast<double *>(out) + (size_t)t * (size_t)ld_out, (size_t)N, std::nan(""));
         }

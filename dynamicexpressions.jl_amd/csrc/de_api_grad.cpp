@@ -1119,7 +1119,15 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
 static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
 }
-#define DE_REFUSE_F16(WHAT) do { if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT); } while (0)
+// ... and so do they complex programs
+static int refuse_complex(de_ctx_t *c, const char *what) {
+    return fail(c, DE_ERR_UNSUPPORTED, "%s: complex (DE_CF32 / DE_CF64) programs evaluate only (de_eval, de_eval_sum_certificate); no complex gradients or losses", what);
+}
+#define DE_REFUSE_F16(WHAT)                                                 \
+    do {                                                                    \
+        if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT);      \
+        if (c && p && is_complex_io(p->io)) return refuse_complex(c, WHAT); \
+    } while (0)
 
 int de_eval_loss_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                       int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,

@@ -98,6 +98,12 @@ struct de_program {
     // (dtype == DE_F32, constants are binary16 values Float32 holds exactly) and run de_half.hip's kernel, which rounds every operator
     // step to binary16; never the threaded kernel, wave groups, priority tiles or compaction
     int io = DE_F32;
+    // complex programs (io DE_CF32 / DE_CF64): dtype is the component type; consts[] holds the real parts, consts_im[] the
+    // imaginary ones.  A constant operand's immediate is an index into the constant table — (re, im) pairs of the component type: the
+    // constants (slot k at k), then the folded subtrees (fold j at consts.size() + j) — host copy ctab (doubles), device copy d_ctab, read by
+    // de_complex.hip with scalar loads; set_consts rewrites the table, never the instruction stream
+    std::vector<double> consts_im, ctab;
+    void *d_ctab = nullptr;
     uint32_t options = 0;
     int32_t n_features = 0, n_params = 0;
     int64_t n_trees = 0, n_nodes = 0;
@@ -266,14 +272,25 @@ unsigned host_threads_for(int64_t n, int64_t grain);
 }
 
 // Bytes of one element of a dtype's buffers, and element k of such a buffer as / from double (binary16 rounds to nearest even).
-static inline size_t dtype_bytes(int dtype) { return dtype == DE_F64 ? 8 : dtype == DE_F16 ? 2 : 4; }
+static inline bool is_complex_io(int dtype) { return dtype == DE_CF32 || dtype == DE_CF64; }
+static inline size_t dtype_bytes(int dtype) { return dtype == DE_CF64 ? 16 : (dtype == DE_F64 || dtype == DE_CF32) ? 8 : dtype == DE_F16 ? 2 : 4; }
+// (a complex dtype: the real part; load_elem_im the imaginary one, 0 for real dtypes)
 static inline double load_elem(int dtype, const void *p, size_t k) {
+    if (dtype == DE_CF64) return static_cast<const double *>(p)[2 * k];
+    if (dtype == DE_CF32) return (double)static_cast<const float *>(p)[2 * k];
     if (dtype == DE_F64) return static_cast<const double *>(p)[k];
     if (dtype == DE_F16) return (double)static_cast<const _Float16 *>(p)[k];
     return (double)static_cast<const float *>(p)[k];
 }
-static inline void store_elem(int dtype, void *p, size_t k, double v) {
-    if (dtype == DE_F64) static_cast<double *>(p)[k] = v;
+static inline double load_elem_im(int dtype, const void *p, size_t k) {
+    if (dtype == DE_CF64) return static_cast<const double *>(p)[2 * k + 1];
+    if (dtype == DE_CF32) return (double)static_cast<const float *>(p)[2 * k + 1];
+    return 0.0;
+}
+static inline void store_elem(int dtype, void *p, size_t k, double v, double im = 0.0) {
+    if (dtype == DE_CF64) { static_cast<double *>(p)[2 * k] = v; static_cast<double *>(p)[2 * k + 1] = im; }
+    else if (dtype == DE_CF32) { static_cast<float *>(p)[2 * k] = (float)v; static_cast<float *>(p)[2 * k + 1] = (float)im; }
+    else if (dtype == DE_F64) static_cast<double *>(p)[k] = v;
     else if (dtype == DE_F16) static_cast<_Float16 *>(p)[k] = (_Float16)v;
     else static_cast<float *>(p)[k] = (float)v;
 }
@@ -281,6 +298,11 @@ static inline void store_elem(int dtype, void *p, size_t k, double v) {
 namespace de {
 hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **kernel_name);
 void eval_plan_f16(int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk); // (de_eval_plan)
+// de_complex.hip: the complex eval kernel (DE_CF32 / DE_CF64); ctab = the program's device constant table (de_program::d_ctab)
+hipError_t launch_eval_complex(int io, const EvalArgs &a, const void *ctab, hipStream_t stream, const char **kernel_name);
+void eval_plan_complex(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk);
+size_t complex_row_bytes(int io); // bytes of one LDS row (X feature / spill slot) of the complex kernel
+bool complex_opcode_ok(int degree, int op); // the 19 opcodes with a Complex method and a Complex result
 }
 
 static inline bool in_one_window(const void *ptr, size_t bytes) {

@@ -55,6 +55,45 @@ bool tree_skip_enabled() {
     return on;
 }
 static bool finite_in(int dtype, double v) { return dtype == DE_F32 ? std::isfinite((float)v) : std::isfinite(v); }
+// A complex program's constant operand: the immediate is the index of its (re, im) pair in the constant table (de_program::ctab)
+static void write_cidx(Instr &ins, size_t idx) {
+    ins.imm.u32[0] = (uint32_t)idx;
+    ins.imm.u32[1] = 0;
+}
+// The constants part of a complex program's table (the folded subtrees' entries follow: refresh_folds)
+static void fill_ctab_consts(de_program *p) {
+    p->ctab.resize(2 * (p->consts.size() + p->folds.size()), 0.0);
+    for (size_t k = 0; k < p->consts.size(); k++) {
+        p->ctab[2 * k] = p->consts[k];
+        p->ctab[2 * k + 1] = p->consts_im[k];
+    }
+}
+// The device copy of the table: (re, im) pairs of the component type
+static int upload_ctab(de_ctx *c, de_program *p) {
+    const size_t n = std::max<size_t>(p->ctab.size() / 2, 1), es = p->dtype == DE_F32 ? 4 : 8;
+    std::vector<unsigned char> img(2 * n * es, 0);
+    for (size_t i = 0; i < p->ctab.size(); i++) {
+        if (es == 4) reinterpret_cast<float *>(img.data())[i] = (float)p->ctab[i];
+        else reinterpret_cast<double *>(img.data())[i] = p->ctab[i];
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!p->d_ctab) HIP_TRY(c, hipMalloc(&p->d_ctab, img.size()));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (work already queued may read the table)
+    HIP_TRY(c, hipMemcpy(p->d_ctab, img.data(), img.size(), hipMemcpyHostToDevice));
+    return DE_OK;
+}
+// The first opcode of a tape a complex program refuses (DE_ERR_UNSUPPORTED_OP), or -1
+static int complex_refused_op(const de_tape_node_t *nd, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        if (nd[i].degree == 0 || (nd[i].degree == 1 && nd[i].op == DE_OP_SHARE)) continue;
+        if (!complex_opcode_ok(nd[i].degree, nd[i].op)) return nd[i].op;
+    }
+    return -1;
+}
+static int fail_complex_op(de_ctx *c, int op) {
+    const char *nm = de_opcode_name(op);
+    return fail(c, DE_ERR_UNSUPPORTED_OP, "opcode %s (%d) is not supported on complex data (DESIGN.md §14.1)", nm ? nm : "?", op);
+}
 
 // Parameters as staged rows (round 3): every use of a parameter was a gather of its samples' values through the vector cache (h_param:
 // 4 loads per lane and use; per-sample parameters, C = N, ran at 27 % VALU utilisation).  With <= 16 parameters the eval kernels
@@ -126,6 +165,10 @@ static int make_threaded(de_ctx *c, de_program *p) {
     // the LDS-staged kernels need (n_features + n_slots) rows of 4112 B; wider X uses the direct variant
     p->direct = (size_t)eval_rows(p) * 257 * 16 > 150 * 1024; // (the flat-switch kernel's geometry: 256 threads x 16 bytes per row; it gathers the features of a wider X from global memory)
     if (p->io == DE_F16) return DE_OK; // binary16 programs run de_half.hip's flat-switch kernel only
+    if (is_complex_io(p->io)) { // complex programs: de_complex.hip's flat-switch kernel, whose rows are complex_row_bytes
+        p->direct = (size_t)eval_rows(p) * complex_row_bytes(p->io) > 64 * 1024;
+        return DE_OK;
+    }
     // the threaded kernel's rows are a quarter of that (one wave's 64 vectors): it stages X up to ~140 rows — and shares them among the
     // waves of a wave group (round 6: F = 36 ... 120 ran the gathering flat-switch kernel, 14 - 20 ms per 10^6 samples x 1000 trees)
     // (a program the flat-switch kernel would gather for takes the threaded kernel while a group of FOUR waves fits: one wave per CU
@@ -342,7 +385,7 @@ static void recompute_host_ok(de_program *p) {
     parallel_for_trees(p->n_trees, [&](int64_t t) {
         bool ok_eval = true, ok_grad = true;
         for (int64_t k = p->const_off[t]; k < p->const_off[t + 1]; k++) {
-            const bool fin = finite_in(p->dtype, p->consts[k]);
+            const bool fin = finite_in(p->dtype, p->consts[k]) && (p->consts_im.empty() || finite_in(p->dtype, p->consts_im[k]));
             ok_grad = ok_grad && fin;
             const uint8_t ch = p->const_checks[k];
             if (!fin && ((ch & CONST_CHECK_ALWAYS) || (ee && (ch & CONST_CHECK_EE)))) ok_eval = false;
@@ -430,7 +473,8 @@ static int refresh_folds(de_ctx *c, de_program *p, bool aux_current = false) {
     int rc = DE_OK;
     if (!aux_current) {
         std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * ies);
-        for (size_t k = 0; k < p->aux_csrc.size(); k++) store_elem(p->io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]]);
+        for (size_t k = 0; k < p->aux_csrc.size(); k++)
+            store_elem(p->io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]], p->consts_im.empty() ? 0.0 : p->consts_im[(size_t)p->aux_csrc[k]]);
         rc = de_program_set_consts(p->aux, ac.data());
         if (rc != DE_OK) return fail(c, rc, "constant folding: %s", p->aux->ctx->err.c_str());
     }
@@ -442,7 +486,12 @@ static int refresh_folds(de_ctx *c, de_program *p, bool aux_current = false) {
         const size_t j = (size_t)p->aux_fold[a];
         const double v = load_elem(p->io, out.data(), a);
         p->fold_ok[j] = aok[a];
-        write_imm(p->fcode[(size_t)p->folds[j].instr], p->dtype, v);
+        if (is_complex_io(p->io)) { // table entry consts.size() + j
+            const size_t e = p->consts.size() + j;
+            p->ctab[2 * e] = v;
+            p->ctab[2 * e + 1] = load_elem_im(p->io, out.data(), a);
+            write_cidx(p->fcode[(size_t)p->folds[j].instr], e);
+        } else write_imm(p->fcode[(size_t)p->folds[j].instr], p->dtype, v);
     }
     return DE_OK;
 }
@@ -478,10 +527,14 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
     if (!ctx) return DE_ERR_INVALID_ARG;
     if (!out_program) return fail(ctx, DE_ERR_INVALID_ARG, "out_program is null");
     *out_program = nullptr;
-    if (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16) return fail(ctx, DE_ERR_INVALID_ARG, "dtype must be DE_F32, DE_F64 or DE_F16");
-    // DE_F16: binary16 buffers, a Float32 program (de_api_internal.h de_program::io)
+    if (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16 && !is_complex_io(dtype))
+        return fail(ctx, DE_ERR_INVALID_ARG, "dtype must be DE_F32, DE_F64, DE_F16, DE_CF32 or DE_CF64");
+    // DE_F16: binary16 buffers, a Float32 program; DE_CF32 / DE_CF64: complex buffers, the component type's program (de_api_internal.h de_program::io)
     const int io = dtype;
-    if (dtype == DE_F16) dtype = DE_F32;
+    const bool cplx = is_complex_io(io);
+    if (dtype == DE_F16 || dtype == DE_CF32) dtype = DE_F32;
+    else if (dtype == DE_CF64) dtype = DE_F64;
+    if (cplx && n_params > 0) return fail(ctx, DE_ERR_UNSUPPORTED, "complex programs take no parameters (n_params = %d): parametric complex expressions are not supported", (int)n_params);
     if (n_trees < 0 || n_features < 0 || n_params < 0 || n_features > 65535 || n_params > 65535)
         return fail(ctx, DE_ERR_INVALID_ARG, "bad sizes");
     if (n_trees > 0 && (!nodes || !node_offsets || !const_offsets))
@@ -530,6 +583,13 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         for (int64_t t = 0; t < n_trees; t++)
             if (node_offsets[t + 1] < node_offsets[t] || const_offsets[t + 1] < const_offsets[t])
                 return fail(ctx, DE_ERR_INVALID_ARG, "offsets not monotone at tree %lld", (long long)t);
+        if (cplx) { // (the expanded tape holds every operator of the CSE one)
+            p->consts_im.resize((size_t)total_consts);
+            for (int64_t t = 0; t < n_trees; t++) {
+                const int op = complex_refused_op(nodes + node_offsets[t], node_offsets[t + 1] - node_offsets[t]);
+                if (op >= 0) return fail_complex_op(ctx, op);
+            }
+        }
         // both lowerings of every tree (plain, and with constant subtrees folded), on host threads
         struct Lowered { TreeProgram plain, folded; int rc = DE_OK, rcf = DE_OK; bool cse = false, cse_plain = false; std::string why; };
         std::vector<Lowered> low((size_t)n_trees);
@@ -603,10 +663,14 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                     for (int64_t k = 0; k < c1 - c0; k++) {
                         const double v = load_elem(io, consts, (size_t)(c0 + k));
                         p->consts[(size_t)(cb + k)] = v;
+                        if (cplx) p->consts_im[(size_t)(cb + k)] = load_elem_im(io, consts, (size_t)(c0 + k));
                         // (a CSE lowering has no instruction for the later occurrences of a constant inside a shared subtree: -1)
                         p->const_instr[(size_t)(cb + k)] = tp.const_instr[(size_t)k] >= 0 ? ib + tp.const_instr[(size_t)k] : -1;
                         p->const_checks[(size_t)(cb + k)] = tp.const_checks[(size_t)k];
-                        if (tp.const_instr[(size_t)k] >= 0) write_imm(tp.code[(size_t)tp.const_instr[(size_t)k]], dtype, v);
+                        if (tp.const_instr[(size_t)k] >= 0) {
+                            if (cplx) write_cidx(tp.code[(size_t)tp.const_instr[(size_t)k]], (size_t)(cb + k));
+                            else write_imm(tp.code[(size_t)tp.const_instr[(size_t)k]], dtype, v);
+                        }
                     }
                     std::copy(tp.code.begin(), tp.code.end(), p->code.begin() + ib);
                     pt.cse = pt.cse || low[(size_t)t].cse_plain;
@@ -674,7 +738,8 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                         const int32_t ci = tp.const_instr[(size_t)k];
                         if (ci < 0) continue; // constant lives inside a folded subtree
                         p->fconst_instr[(size_t)(cb + k)] = ib + ci;
-                        write_imm(tp.code[(size_t)ci], dtype, p->consts[(size_t)(cb + k)]);
+                        if (cplx) write_cidx(tp.code[(size_t)ci], (size_t)(cb + k));
+                        else write_imm(tp.code[(size_t)ci], dtype, p->consts[(size_t)(cb + k)]);
                     }
                     size_t an = (size_t)anode0[(size_t)t], ac = (size_t)acs0[(size_t)t];
                     for (size_t f = 0; f < tp.folds.size(); f++) {
@@ -704,12 +769,13 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                 // which folds stay on the host: subtrees of + - * / only (the turbo division is not IEEE: such programs fold everything on
                 // the device, with the operators they evaluate with; DE_NO_HOST_FOLD=1: everything on the device, for A/B tests)
                 const char *nh = getenv("DE_NO_HOST_FOLD");
-                const bool host_fold = !(nh && *nh == '1') && !(io != DE_F16 && (options & DE_OPT_TURBO)); // (DE_F16 ignores the turbo bit)
+                // (complex programs: every subtree with the auxiliary program, which runs de_complex.hip — the unfolded bits by construction)
+                const bool host_fold = !(nh && *nh == '1') && !(io != DE_F16 && (options & DE_OPT_TURBO)) && !cplx; // (DE_F16 ignores the turbo bit)
                 // ... and which go to de_fold_kernel (everything else whose evaluation stack fits; a turbo program evaluates with other
                 // operators than that kernel has: its subtrees stay with the auxiliary program; DE_NO_KERNEL_FOLD=1 for A/B tests)
                 const char *nk_env = getenv("DE_NO_KERNEL_FOLD");
                 // (a DE_F16 program's subtrees: de_fold_kernel does not round to binary16 — the auxiliary program, which runs de_half.hip, does)
-                const bool kernel_fold = !(nk_env && *nk_env == '1') && !(options & DE_OPT_TURBO) && io != DE_F16;
+                const bool kernel_fold = !(nk_env && *nk_env == '1') && !(options & DE_OPT_TURBO) && io != DE_F16 && !cplx;
                 p->fold_host.assign(n_folds, 0);
                 parallel_for_trees((int64_t)n_folds, [&](int64_t j) {
                     const de_tape_node_t *nd = anodes.data() + anoff[(size_t)j];
@@ -778,10 +844,12 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                     HIP_TRY(ctx, hipMemcpy(p->d_kf, img.data(), img.size(), hipMemcpyHostToDevice));
                 }
                 p->folded = true;
+                if (cplx) fill_ctab_consts(p.get());
                 lap("folds: classify, kernel image, auxiliary tapes");
                 if (!p->aux_fold.empty()) {
                     std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * dtype_bytes(io), 0);
-                    for (size_t k = 0; k < p->aux_csrc.size(); k++) store_elem(io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]]);
+                    for (size_t k = 0; k < p->aux_csrc.size(); k++)
+                        store_elem(io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]], cplx ? p->consts_im[(size_t)p->aux_csrc[k]] : 0.0);
                     int rc = create_impl(ctx, io, xnodes.data(), xnoff.data(), (int64_t)p->aux_fold.size(), ac.data(),
                                          xcoff.data(), n_features, 0, options, false, &p->aux);
                     if (rc != DE_OK) return rc;
@@ -800,6 +868,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         // the per-tree lowerings are ~16 small vectors each: released on the threads that allocated them (one thread took 5 ms for 10^4 trees)
         if (!allow_fold) parallel_for_trees(n_trees, [&](int64_t t) { Lowered done; std::swap(done, low[(size_t)t]); }); // (with folding: released in the merge above)
         lap("release lowerings");
+        if (cplx) fill_ctab_consts(p.get()); // (the folds' entries stay: refresh_folds wrote them)
         recompute_host_ok(p.get());
         rebind(p.get());
         lap("bind");
@@ -813,6 +882,10 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         if (rc != DE_OK) return rc;
     }
     lap("threaded + chained records");
+    if (cplx) {
+        const int rc = upload_ctab(ctx, p.get());
+        if (rc != DE_OK) return rc;
+    }
     // one trailing pad instruction: the flat-switch interpreter prefetches code[pc + 1]; the chained form of the
     // threaded kernel has one end record per tree and a head record (and the fused form is never longer than the bound one)
     const size_t cbytes = (p->bcode.size() + (size_t)p->n_trees + 2) * sizeof(BoundInstr); // + head record + one of padding
@@ -897,18 +970,21 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
     const auto t0 = now();
+    const bool cplx = is_complex_io(p->io);
     // (every loop of this function over constants, trees or sites writes slots of its own: on the host pool; 10^4 trees: 0.85 -> see DESIGN 9.1)
     try {
         parallel_tree_ranges((int64_t)p->consts.size(), [&](int, int64_t kb, int64_t ke) {
             for (size_t k = (size_t)kb; k < (size_t)ke; k++) {
                 const double v = load_elem(p->io, consts, k);
                 p->consts[k] = v;
+                if (cplx) { p->consts_im[k] = load_elem_im(p->io, consts, k); continue; } // (the immediates are table indices)
                 if (p->const_instr[k] >= 0) write_imm(p->code[(size_t)p->const_instr[k]], p->dtype, v);
                 if (p->folded && p->fconst_instr[k] >= 0) write_imm(p->fcode[(size_t)p->fconst_instr[k]], p->dtype, v);
             }
         }, 4096);
     } catch (const std::bad_alloc &) { return fail(ctx, DE_ERR_HIP, "out of host memory"); }
     const auto t1 = now();
+    if (cplx) fill_ctab_consts(p);
     if (p->folded) {
         int rc = DE_OK;
         try { rc = refresh_folds(ctx, p); } catch (const std::bad_alloc &) { rc = fail(ctx, DE_ERR_HIP, "out of host memory"); }
@@ -922,6 +998,7 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
         if (rc != DE_OK) return rc;
     }
     const auto t3 = now();
+    if (cplx) return upload_ctab(ctx, p); // a complex program's stream does not change: its constants and folds are the table
     // Same tree shapes, new immediates: patch the bits where they live (the optimiser calls this once per
     // step — re-binding 10^4 trees costs milliseconds, the kernel it feeds a few hundred microseconds).
     const char *nopatch = getenv("DE_NO_CONST_PATCH");
@@ -1038,6 +1115,7 @@ int de_program_destroy(de_program_t *p) {
         if (p->d_compact_ints) (void)hipFree(p->d_compact_ints);
     }
     if (p->d_cert_code) (void)hipFree(p->d_cert_code);
+    if (p->d_ctab) (void)hipFree(p->d_ctab);
     if (p->d_cert_off) (void)hipFree(p->d_cert_off);
     dbg_lap("destroy: eval streams");
     if (p->aux) de_program_destroy(p->aux);
@@ -1094,6 +1172,7 @@ int de_prio_tiles_wanted(int64_t N, int32_t n_features, int64_t n_trees) { retur
 int de_eval_plan(const de_program_t *p, int64_t N, int32_t *plan) {
     if (!p || !plan || N < 0) return DE_ERR_INVALID_ARG;
     if (p->io == DE_F16) eval_plan_f16(p->n_trees, N, &plan[0], &plan[1], &plan[2]);
+    else if (is_complex_io(p->io)) eval_plan_complex(p->io, p->n_trees, N, &plan[0], &plan[1], &plan[2]);
     else eval_plan(p->dtype, p->n_trees, N, &plan[0], &plan[1], &plan[2], p->threaded ? p->waves : 1);
     return DE_OK;
 }
@@ -1113,6 +1192,7 @@ uint64_t de_program_stream_hash(const de_program_t *p) {
     vec(p->code); vec(p->code_off); vec(p->fcode); vec(p->fcode_off); vec(p->bcode); vec(p->bcode_off);
     vec(p->fbcode); vec(p->tcode); vec(p->tcode_off); vec(p->ccode); vec(p->ccode_off); vec(p->bsite); vec(p->tsite);
     vec(p->consts); vec(p->const_off); vec(p->const_instr); vec(p->fconst_instr); vec(p->const_checks); vec(p->n_consts_tree);
+    vec(p->consts_im); vec(p->ctab); // (complex programs: the imaginary parts and the constant table)
     vec(p->aux_const_src); vec(p->host_ok_eval); vec(p->host_ok_grad); vec(p->fold_ok);
     vec(p->fold_host); vec(p->fold_noff); vec(p->fold_coff); vec(p->aux_fold); vec(p->aux_csrc); vec(p->kfold); vec(p->kf_csrc);
     mix(p->fold_nodes.data(), p->fold_nodes.size() * sizeof(de_tape_node_t));
@@ -1170,6 +1250,18 @@ int de_program_verify(const de_program_t *p) {
             b.bop != BOP_INJ_ACC && !(b.bop >= BOP_UN_BASE && b.bop < BOP_UN_END && !((b.bop - BOP_UN_BASE) & 2)) &&
             (int64_t)(b.arg & 0xFFFFFFu) >= rows)
             return bad("bound operand row", -1, (int64_t)i, b.arg);
+    }
+    if (is_complex_io(p->io)) { // every constant operand of a complex program indexes the constant table
+        const size_t n_entries = p->ctab.size() / 2;
+        for (size_t i = 0; i < p->bcode.size(); i++)
+            if (bop_is_const_source(p->bcode[i].bop) && p->bcode[i].lo >= n_entries) return bad("constant-table index", -1, (int64_t)i, p->bcode[i].lo);
+        for (size_t i = 0; i < p->bcode.size(); i++) {
+            const uint32_t bop = p->bcode[i].bop, op = p->bcode[i].arg >> 24;
+            const bool gen = bop == BOP_GEN_ROW || bop == BOP_GEN_CONST || bop == BOP_GEN_ACC || bop == BOP_INJ_ACC || bop == BOP_INJ_ROW || bop == BOP_TERN;
+            if (bop == BOP_GEN_PARAM) return bad("parameter operand in a complex program", -1, (int64_t)i, bop);
+            if (gen && op != DOP_RSUB && op != DOP_RDIV && !complex_opcode_ok(op >= DE_T_FMA ? 3 : op >= DE_B_ADD ? 2 : 1, (int)op))
+                return bad("opcode without a complex kernel", -1, (int64_t)i, op);
+        }
     }
     if (p->threaded) {
         uint64_t table[TOPX_TABLE];
@@ -1313,12 +1405,45 @@ int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, in
     return nw;
 }
 
+// The host lowering hooks: de_lower_tape / de_lower_tape_stage take the real dtypes (DE_F32, DE_F64, DE_F16) — their dtype domain
+// is pinned as it was before complex programs existed —, de_lower_tape_complex / de_lower_tape_stage_complex the complex ones; one body.
+static int64_t lower_tape_impl(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                               int32_t n_features, int32_t n_params, uint32_t options, uint32_t *words, int64_t cap, int32_t *meta);
+static int64_t lower_tape_stage_impl(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                                     int32_t n_features, int32_t n_params, uint32_t options, int stage, uint32_t *words, int64_t cap);
 int64_t de_lower_tape(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
                       int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, uint32_t *words,
                       int64_t cap, int32_t *meta) {
-    if (!nodes || (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16) || (n_consts > 0 && !consts)) return -DE_ERR_INVALID_ARG;
-    const int io = dtype; // DE_F16: binary16 constants, lowered like a Float32 tape
-    if (dtype == DE_F16) dtype = DE_F32;
+    if (is_complex_io(dtype)) return -DE_ERR_INVALID_ARG;
+    return lower_tape_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, words, cap, meta);
+}
+int64_t de_lower_tape_complex(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
+                              int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, uint32_t *words,
+                              int64_t cap, int32_t *meta) {
+    if (!is_complex_io(dtype)) return -DE_ERR_INVALID_ARG;
+    return lower_tape_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, words, cap, meta);
+}
+int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
+                            int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, int stage,
+                            uint32_t *words, int64_t cap) {
+    if (is_complex_io(dtype)) return -DE_ERR_INVALID_ARG;
+    return lower_tape_stage_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, stage, words, cap);
+}
+int64_t de_lower_tape_stage_complex(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
+                                    int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, int stage,
+                                    uint32_t *words, int64_t cap) {
+    if (!is_complex_io(dtype)) return -DE_ERR_INVALID_ARG;
+    return lower_tape_stage_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, stage, words, cap);
+}
+static int64_t lower_tape_impl(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                               int32_t n_features, int32_t n_params, uint32_t options, uint32_t *words, int64_t cap, int32_t *meta) {
+    if (!nodes || (dtype != DE_F32 && dtype != DE_F64 && dtype != DE_F16 && !is_complex_io(dtype)) || (n_consts > 0 && !consts)) return -DE_ERR_INVALID_ARG;
+    const int io = dtype; // DE_F16: binary16 constants, lowered like a Float32 tape; complex: the component type's tape, table-index immediates
+    const bool cplx = is_complex_io(io);
+    if (dtype == DE_F16 || dtype == DE_CF32) dtype = DE_F32;
+    else if (dtype == DE_CF64) dtype = DE_F64;
+    if (cplx && complex_refused_op(nodes, n_nodes) >= 0) return -DE_ERR_UNSUPPORTED_OP;
+    if (cplx && n_params > 0) return -DE_ERR_UNSUPPORTED;
     try {
         LowerOptions lo;
         lo.early_exit = (options & DE_OPT_EARLY_EXIT) != 0;
@@ -1337,8 +1462,11 @@ int64_t de_lower_tape(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, c
         bool ok_eval = true, ok_grad = true;
         for (int64_t k = 0; k < n_consts; k++) {
             const double v = load_elem(io, consts, (size_t)k);
-            if (tp.const_instr[(size_t)k] >= 0) write_imm(tp.code[(size_t)tp.const_instr[(size_t)k]], dtype, v);
-            const bool fin = finite_in(dtype, v);
+            if (tp.const_instr[(size_t)k] >= 0) {
+                if (cplx) write_cidx(tp.code[(size_t)tp.const_instr[(size_t)k]], (size_t)k); // (the index of the constant's pair)
+                else write_imm(tp.code[(size_t)tp.const_instr[(size_t)k]], dtype, v);
+            }
+            const bool fin = finite_in(dtype, v) && finite_in(dtype, load_elem_im(io, consts, (size_t)k));
             ok_grad = ok_grad && fin;
             const uint8_t ch = tp.const_checks[(size_t)k];
             if (!fin && ((ch & CONST_CHECK_ALWAYS) || (lo.early_exit && (ch & CONST_CHECK_EE)))) ok_eval = false;
@@ -1358,20 +1486,19 @@ int64_t de_lower_tape(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, c
     }
 }
 
-int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
-                            int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options, int stage,
-                            uint32_t *words, int64_t cap) {
+static int64_t lower_tape_stage_impl(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                                     int32_t n_features, int32_t n_params, uint32_t options, int stage, uint32_t *words, int64_t cap) {
     if (stage != 2 && stage != 3) return -DE_ERR_INVALID_ARG;
     std::vector<uint32_t> g;
-    int64_t nw = de_lower_tape(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, nullptr, 0, nullptr);
+    int64_t nw = lower_tape_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, nullptr, 0, nullptr);
     if (nw < 0) return nw;
     try {
         g.resize((size_t)nw);
-        nw = de_lower_tape(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, g.data(), nw, nullptr);
+        nw = lower_tape_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, g.data(), nw, nullptr);
         if (nw < 0) return nw;
         std::vector<BoundInstr> b, f;
         bind_tree(reinterpret_cast<const Instr *>(g.data()), (size_t)nw / 4, (options & DE_OPT_EARLY_EXIT) != 0, n_features, &b);
-        if (stage == 3 && dtype != DE_F16) fuse_tree(b.data(), b.size(), &f); // (a DE_F16 program never runs the threaded kernel: no fused form)
+        if (stage == 3 && dtype != DE_F16 && !is_complex_io(dtype)) fuse_tree(b.data(), b.size(), &f); // (a DE_F16 program never runs the threaded kernel: no fused form)
         const std::vector<BoundInstr> &o = stage == 3 ? f : b;
         const int64_t n = (int64_t)o.size() * 4;
         if (!words || cap < n) return n;

@@ -31,7 +31,7 @@ const DE_OK = Cint(0)
 const DE_ERR_UNSUPPORTED_OP = Cint(3)
 const DE_LEAF_CONST, DE_LEAF_FEATURE, DE_LEAF_PARAM, DE_LEAF_SHARED = UInt8(0), UInt8(1), UInt8(2), UInt8(3)
 const DE_OP_SHARE = UInt8(0xFE)   # include/de_opcodes.h: "the subtree just emitted is shared subtree `arg`"
-const DE_F32, DE_F64, DE_F16 = Cint(0), Cint(1), Cint(2)
+const DE_F32, DE_F64, DE_F16, DE_CF32, DE_CF64 = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
 const DE_OPT_EARLY_EXIT, DE_OPT_FUSE_DEG1, DE_OPT_FUSE_DEG2, DE_OPT_BUMPER_CHECKS, DE_OPT_TURBO, DE_OPT_FULL_EVAL, DE_OPT_FORWARD_GRAD, DE_OPT_REVERSE_GRAD =
     UInt32(1), UInt32(2), UInt32(4), UInt32(8), UInt32(16), UInt32(32), UInt32(64), UInt32(128)
 # The ABI this file was written for (include/de_hip.h lists what changed between versions).  Version 2: the rows / gradients of a tree
@@ -54,6 +54,10 @@ dtype_code(::Type{Float64}) = DE_F64
 # Float16: evaluation only (every operator step rounded to binary16, DESIGN.md §13); the gradient methods below stay
 # Float32 / Float64, so a Float16 gradient keeps the reference CPU path
 dtype_code(::Type{Float16}) = DE_F16
+# ComplexF32 / ComplexF64: evaluation only (Julia's Complex methods of 19 opcodes, DESIGN.md §14); a tree with another operator and every
+# complex gradient keep the reference CPU path
+dtype_code(::Type{ComplexF32}) = DE_CF32
+dtype_code(::Type{ComplexF64}) = DE_CF64
 
 struct UnsupportedOperator <: Exception
     f::Any
@@ -317,7 +321,7 @@ Drop-in for `eval_tree_array`'s body: same `(output, complete)` tuple, `cX` is t
 function _hip_eval_tree_array(
     tree::AbstractExpressionNode{T}, cX::AbstractMatrix{T}, operators::OperatorEnum,
     eval_context::EvalContext; full_eval::Bool=false,
-) where {T<:Union{Float16,Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64,ComplexF32,ComplexF64}}
     optable = try
         opcode_table(operators)
     catch e
@@ -331,14 +335,17 @@ function _hip_eval_tree_array(
     out = Vector{T}(undef, N)
     ok = Ref{UInt8}(0)
     ctx = task_context()
-    with_ctx(ctx) do h
-        check(ctx, GC.@preserve nodes consts X out ccall(
+    rc = with_ctx(ctx) do h
+        GC.@preserve nodes consts X out ccall(
             (:de_eval_tree_array, LIBDE), Cint,
             (Ptr{Cvoid}, Cint, Ptr{TapeNode}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Int64, UInt32,
              Ptr{Cvoid}, Ref{UInt8}),
             h, dtype_code(T), nodes, length(nodes), consts, length(consts), X, F, N,
-            option_bits(operators, eval_context; full_eval), out, ok))
+            option_bits(operators, eval_context; full_eval), out, ok)
     end
+    # a complex tree with an operator that has no complex kernel (abs, max, ...): the reference CPU path
+    T <: Complex && rc == DE_ERR_UNSUPPORTED_OP && return nothing
+    check(ctx, rc)
     return (out, ok[] != 0x00)   # ok == false: `out` is all NaN unless full_eval (only the flag is contractual, SURVEY.md §8a)
 end
 
@@ -384,7 +391,7 @@ function HIPPopulation(
     trees::AbstractVector{<:AbstractExpressionNode{T}}, operators::OperatorEnum, n_features::Integer;
     eval_context::EvalContext=EvalContext(), n_params::Integer=0, full_eval::Bool=false, forward_grad::Bool=false,
     reverse_grad::Bool=false,
-) where {T<:Union{Float16,Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64,ComplexF32,ComplexF64}}
     optable = opcode_table(operators)
     nodes, consts, cse = TapeNode[], T[], TapeNode[]
     node_off, const_off, cse_off = Int64[0], Int64[0], Int64[0]

@@ -50,7 +50,7 @@ class Node:
         elif val is not None:
             self.degree = 0
             self.constant = True
-            self.val = float(val)
+            self.val = _scalar(val)
         elif feature is not None:
             self.degree = 0
             self.feature = int(feature)
@@ -193,14 +193,23 @@ def postorder(tree: Node) -> List[Node]:
 
 def get_scalar_constants(tree: Node) -> Tuple[np.ndarray, List[Node]]:
     """Constants in depth-first left-to-right order (src/NodeUtils.jl:99-120) — the same
-    order as index_constant_nodes (:184-201), i.e. the constant-gradient row order."""
+    order as index_constant_nodes (:184-201), i.e. the constant-gradient row order.  complex128 when a constant is complex
+    (a Node{ComplexF64} tree), float64 otherwise."""
     refs = [n for n in (_unique_postorder(tree) if preserve_sharing(tree) else postorder(tree)) if is_node_constant(n)]
-    return np.array([n.val for n in refs], dtype=np.float64), refs
+    vals = [n.val for n in refs]
+    return np.array(vals, dtype=np.complex128 if any(isinstance(v, complex) for v in vals) else np.float64), refs
 
 
 def set_scalar_constants(tree: Node, constants: Sequence[float], refs: List[Node]) -> None:
     for n, v in zip(refs, constants):  # src/NodeUtils.jl:130-143
-        n.val = float(v)
+        n.val = _scalar(v)
+
+
+def _scalar(v):
+    """A constant's value: a Python float, or a Python complex when it has a non-real type (its imaginary part is kept, even 0)."""
+    if isinstance(v, (complex, np.complexfloating)):
+        return complex(v)
+    return float(v)
 
 
 def max_feature(tree: Node) -> int:

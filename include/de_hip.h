@@ -70,7 +70,11 @@ extern "C" {
  *      the default): same values to rounding, the reference's flags exactly; (b) new exports, all additive (see below).
  *      Additive since: (c) dtype DE_F16 (IEEE binary16 X / constants / parameters / outputs, every operator rounded to binary16 —
  *      Julia's Float16 arithmetic) for de_program_create(_cse), de_program_set_consts, de_eval, de_eval_sum_certificate,
- *      de_eval_tree_array and the host-only / debug hooks; the gradient, loss and dataset entry points answer DE_ERR_UNSUPPORTED for it. */
+ *      de_eval_tree_array and the host-only / debug hooks; the gradient, loss and dataset entry points answer DE_ERR_UNSUPPORTED for it.
+ *      (d) dtypes DE_CF32 / DE_CF64 (interleaved complex X / constants / outputs, Julia's ComplexF32 / ComplexF64 arithmetic over the
+ *      19 opcodes that have a Complex method with a Complex result) for the same calls, except that the host lowering
+ *      hooks keep their real dtype domain and complex tapes lower through the new de_lower_tape_complex / de_lower_tape_stage_complex;
+ *      the same entry points answer DE_ERR_UNSUPPORTED, and so does de_program_create with n_params > 0. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -90,7 +94,12 @@ typedef enum de_status {
  * de_ctx_declare_dataset return DE_ERR_UNSUPPORTED for an F16 program or dtype and leave their outputs untouched.  F16 programs never
  * run the threaded kernel (de_eval_plan / de_program_dump report the flat-switch kernel's form); a feature matrix too wide for its LDS
  * tile is gathered from global memory as for Float32.  de_eval_sum_certificate refuses such wide programs for every dtype. */
-typedef enum de_dtype { DE_F32 = 0, DE_F64 = 1, DE_F16 = 2 } de_dtype_t;
+/* DE_CF32 / DE_CF64: complex elements, (re, im) interleaved — 8 bytes (numpy complex64, Julia ComplexF32) / 16 bytes (complex128,
+ * ComplexF64) everywhere the dtype sizes a buffer; a constant is one (re, im) pair.  Opcodes: neg square cube inv sqrt exp log sin cos
+ * tan sinh cosh tanh custom_cos + - * / +(x, y, z); every other one fails program creation with DE_ERR_UNSUPPORTED_OP (de_last_error names
+ * it).  A value is valid when both components are finite.  Evaluation only, as DE_F16 (parameters included: n_params > 0 is refused);
+ * DE_OPT_TURBO is ignored.  de_eval_sum_certificate certifies when N * max(|re|, |im|) * 1.001 stays below the component type's floatmax. */
+typedef enum de_dtype { DE_F32 = 0, DE_F64 = 1, DE_F16 = 2, DE_CF32 = 3, DE_CF64 = 4 } de_dtype_t;
 
 /* Gradient modes of eval_grad_tree_array (src/EvaluateDerivative.jl:200-210). */
 typedef enum de_grad_mode {
@@ -294,6 +303,16 @@ int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_no
                             const void *consts, int64_t n_consts, int32_t n_features,
                             int32_t n_params, uint32_t options, int stage, uint32_t *words,
                             int64_t cap);
+/* The two hooks above take the real dtypes (DE_F32, DE_F64, DE_F16) and answer -DE_ERR_INVALID_ARG for any other code; complex tapes
+ * (DE_CF32 / DE_CF64, interleaved (re, im) constants) lower through these two, which take nothing else.  The generic words carry, for a
+ * constant operand, the index of its (re, im) pair in the program's constant table (slot k of the tape: index k) instead of its value. */
+int64_t de_lower_tape_complex(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts,
+                              int64_t n_consts, int32_t n_features, int32_t n_params, uint32_t options,
+                              uint32_t *words, int64_t cap, int32_t *meta);
+int64_t de_lower_tape_stage_complex(int dtype, const de_tape_node_t *nodes, int64_t n_nodes,
+                                    const void *consts, int64_t n_consts, int32_t n_features,
+                                    int32_t n_params, uint32_t options, int stage, uint32_t *words,
+                                    int64_t cap);
 
 /* ---- evaluation ------------------------------------------------------------ */
 /* Optional per-call inputs of a parametric population
