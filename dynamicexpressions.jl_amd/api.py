@@ -45,7 +45,7 @@ EXPORTS = [
     "de_abi_version", "de_opcode_table_version", "de_opcode_by_name", "de_opcode_name",
     "de_opcode_degree", "de_status_string", "de_ctx_create", "de_ctx_destroy", "de_ctx_set_stream",
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
-    "de_program_set_consts", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
+    "de_program_set_consts", "de_program_update", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
     "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
@@ -113,6 +113,7 @@ def library() -> C.CDLL:
     lib.de_program_create.argtypes = [vp, C.c_int, vp, vp, i64, vp, vp, i32, i32, u32, C.POINTER(vp)]
     lib.de_program_create_cse.argtypes = [vp, C.c_int, vp, vp, vp, vp, i64, vp, vp, i32, i32, u32, C.POINTER(vp)]
     lib.de_program_set_consts.argtypes = [vp, vp]
+    lib.de_program_update.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.de_program_destroy.argtypes = [vp]
     lib.de_program_n_trees.restype = i64
     lib.de_program_n_trees.argtypes = [vp]
@@ -416,6 +417,26 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     return w[:int(n)].reshape(-1, 4)
 
 
+def check_update_ids(indices, n_new: int, n_trees: int) -> np.ndarray:
+    """The tree ids of ``Population.update`` as int64, checked before the library is called: one id per new tree, integers in
+    [0, n_trees), no id twice (ValueError otherwise)."""
+    ids = np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices)
+    if ids.ndim != 1:
+        raise ValueError("update: indices must be one-dimensional")
+    if len(ids) != n_new:
+        raise ValueError(f"update: {len(ids)} indices for {n_new} trees")
+    if len(ids) == 0:
+        return np.zeros(0, dtype=np.int64)
+    if ids.dtype.kind not in "iu":
+        raise ValueError(f"update: indices must be integers, got {ids.dtype}")
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    if ids.min() < 0 or ids.max() >= n_trees:
+        raise ValueError(f"update: tree index outside [0, {n_trees})")
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError("update: a tree index appears twice")
+    return ids
+
+
 class Population:
     """A population of trees lowered once to a device program (``de_program_t``).
 
@@ -455,10 +476,11 @@ class Population:
                 self._occ = occ
                 self.n_consts = np.array([len(np.unique(o)) if o is not None else int(n) for o, n in zip(occ, np.diff(coff))], dtype=np.int64)
             if any(len(c) for c in cse_tapes):
-                self._cse_nodes = np.concatenate(cse_tapes) if cse_tapes else np.zeros(0, dtype=TAPE_DTYPE)
-                self._cse_off = np.zeros(len(trees) + 1, dtype=np.int64)
-                np.cumsum([len(c) for c in cse_tapes], out=self._cse_off[1:])
-                cse_ptrs = (self._cse_nodes.ctypes.data, self._cse_off.ctypes.data)
+                # (the library keeps the CSE tapes it is given — de_program_update splices them: no Python copy outlives the call)
+                cse_nodes = np.concatenate(cse_tapes) if cse_tapes else np.zeros(0, dtype=TAPE_DTYPE)
+                cse_off = np.zeros(len(trees) + 1, dtype=np.int64)
+                np.cumsum([len(c) for c in cse_tapes], out=cse_off[1:])
+                cse_ptrs = (cse_nodes.ctypes.data, cse_off.ctypes.data)
         self._slots_per_tree = np.diff(coff).astype(np.int64)
         if cse_ptrs[0] is not None:
             self.ctx.check(lib.de_program_create_cse(
@@ -472,6 +494,43 @@ class Population:
                 self.eval_context.option_bits(operators), C.byref(self._h)))
         self.n_nodes = int(lib.de_program_n_nodes(self._h))
         self.uncertified = np.zeros(0, dtype=np.int64)  # EvalContext(strict_flags=True): set by every eval()
+
+    # -- incremental update (de_program_update) -----------------------
+    def update(self, indices, trees: Sequence[Node]) -> None:
+        """Replace trees ``indices[i]`` by ``trees[i]`` in place; the result is what a fresh ``Population`` of the resulting tree list
+        would be (same bits from every entry point).  A captured graph of this population must be re-captured afterwards."""
+        ids = check_update_ids(indices, len(trees), self.n_trees)
+        if not len(ids):
+            return
+        lib = library()
+        nodes, noff, consts, coff = flatten_population(trees, self.operators, self.dtype)
+        occ = [None] * len(trees)
+        cse_ptrs, keep = (None, None), []
+        if any(preserve_sharing(t) for t in trees):
+            cse_tapes = []
+            for i, t in enumerate(trees):
+                _, _, cse, o = flatten_graph(t, self.operators, self.dtype) if preserve_sharing(t) else (None, None, None, None)
+                occ[i] = o if o is not None and len(o) and len(np.unique(o)) < len(o) else None
+                cse_tapes.append(cse if cse is not None else np.zeros(0, dtype=TAPE_DTYPE))
+            if any(len(c) for c in cse_tapes):
+                cse_nodes = np.concatenate(cse_tapes)
+                cse_off = np.zeros(len(trees) + 1, dtype=np.int64)
+                np.cumsum([len(c) for c in cse_tapes], out=cse_off[1:])
+                keep += [cse_nodes, cse_off]
+                cse_ptrs = (cse_nodes.ctypes.data, cse_off.ctypes.data)
+        self.ctx.check(lib.de_program_update(
+            self._h, ids.ctypes.data, len(ids), nodes.ctypes.data, noff.ctypes.data, cse_ptrs[0], cse_ptrs[1],
+            consts.ctypes.data if len(consts) else None, coff.ctypes.data))
+        # the Python-side metadata of the new trees: constant counts (GraphNode: unique constants), occurrence maps, slots per tree
+        slots = np.diff(coff).astype(np.int64)
+        all_occ = list(self._occ) if self._occ is not None else [None] * self.n_trees
+        for i, t in enumerate(ids):
+            all_occ[t] = occ[i]
+            self._slots_per_tree[t] = slots[i]
+            self.n_consts[t] = len(np.unique(occ[i])) if occ[i] is not None else int(slots[i])
+        self._occ = all_occ if any(o is not None for o in all_occ) else None
+        self.n_nodes = int(lib.de_program_n_nodes(self._h))
+        self.__dict__.pop("_ng_cache", None)
 
     # -- constants (optimiser inner loop, src/NodeUtils.jl:99-143) ------------------
     def set_constants(self, consts: np.ndarray) -> None:

@@ -291,7 +291,8 @@ void prog_free(de_ctx *c, void *ptr) {
     X(code) X(code_off) X(const_off) X(const_instr) X(const_checks) X(n_consts_tree) X(host_ok_eval) X(host_ok_grad) X(consts) X(fcode) \
     X(fcode_off) X(fconst_instr) X(folds) X(aux_const_src) X(fold_ok) X(bcode) X(tcode) X(fbcode) X(tcode_off) X(ccode) X(ccode_off) \
     X(bcode_off) X(gbcode) X(gbcode_off) X(gtcode) X(gtcode_off) X(bsite) X(tsite) X(gbsite) X(gtsite_of_gb) X(rtcode) X(rtcode_off) \
-    X(rtcode_mid) X(rtsite_of_gb) X(fold_host) X(fold_nodes) X(fold_noff) X(fold_coff) X(aux_fold) X(aux_csrc) X(kfold) X(kf_csrc)
+    X(rtcode_mid) X(rtsite_of_gb) X(fold_host) X(fold_nodes) X(fold_noff) X(fold_coff) X(aux_fold) X(aux_csrc) X(kfold) X(kf_csrc) \
+    X(in_nodes) X(in_cse) X(in_noff) X(in_coff) X(tree_slots) X(tree_bits)
 static constexpr size_t PARKED_MAX = 4, PARKED_BYTES = 512u << 20;
 static size_t program_host_bytes(const de_program *p) {
     size_t b = 0;

@@ -235,7 +235,15 @@ struct de_program {
     size_t gt_cap = 0;            // records d_gtcode has room for
     int gt_n_buckets = 0;
     GradArgs::Bucket gt_buckets[24];
+    // de_program_update: the population as it was created — expanded tapes and CSE tapes (in_coff all 0: none), offsets
+    // rebased to 0 — and per tree what its lowerings reported, so that an update lowers the new trees only and copies the others' slices
+    std::vector<de_tape_node_t> in_nodes, in_cse;
+    std::vector<int64_t> in_noff, in_coff;
+    std::vector<int32_t> tree_slots;    // per tree: spill slots of its plain and folded lowerings (the larger)
+    std::vector<uint8_t> tree_bits;     // per tree: TREE_PARAMS | TREE_CSE_PLAIN | TREE_CSE_FOLDED
+    bool allow_fold = true;             // the creation folded constant subtrees (DE_NO_FOLD unset; false for an auxiliary program)
 };
+enum : uint8_t { TREE_PARAMS = 1, TREE_CSE_PLAIN = 2, TREE_CSE_FOLDED = 4 };
 
 #define HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                     \

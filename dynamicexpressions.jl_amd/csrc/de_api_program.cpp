@@ -103,8 +103,22 @@ static bool param_rows_enabled() { // (read at every de_program_create: the test
     const char *v = getenv("DE_NO_PARAM_ROWS");
     return !(v && *v == '1');
 }
+// de_program_update: a creation that takes tree t's lowerings, folds and bound / fused code from tree src[t] of the
+// program `old` (src[t] < 0: lower it) — the same records a lowering of the same tape would produce, copied instead of recomputed
+struct Reuse {
+    const de_program *old = nullptr;
+    std::vector<int32_t> src;       // per tree of the new population: the old tree it is, or -1
+    std::vector<int64_t> fold0;     // per old tree: its first fold (old->folds is ordered by tree), n_trees + 1 entries
+    bool reuse(int64_t t) const { return old && src[(size_t)t] >= 0; }
+};
 static int64_t eval_rows(const de_program *p) { return (int64_t)p->n_features + p->n_slots + (p->prows ? p->n_params : 0); }
-static void rebind(de_program *p) {
+// `ru` (de_program_update): a kept tree's bound code is copied when the binder's inputs are the old program's — the same source stream
+// (folded or not), spill slots and parameter rows; a tree's bound code depends on its own instructions and those only
+static bool same_binding(const de_program *p, const de_program *old) {
+    return old->folded == p->folded && old->prows == p->prows && old->n_slots == p->n_slots && old->n_features == p->n_features &&
+           old->n_params == p->n_params && old->options == p->options && old->dtype == p->dtype;
+}
+static void rebind(de_program *p, const Reuse *ru = nullptr) {
     const bool ee = (p->options & DE_OPT_EARLY_EXIT) != 0;
     p->prows = p->uses_params && p->n_params > 0 && p->n_params <= 16 && param_rows_enabled() &&
                ((size_t)p->n_features + (size_t)p->n_slots + (size_t)p->n_params) * 257 * 16 <= 150 * 1024;
@@ -112,7 +126,13 @@ static void rebind(de_program *p) {
     const std::vector<Instr> &src = p->folded ? p->fcode : p->code;
     const std::vector<int32_t> &off = p->folded ? p->fcode_off : p->code_off;
     const int nf = p->n_features;
+    const de_program *old = ru && ru->old && same_binding(p, ru->old) ? ru->old : nullptr;
     build_stream_by_trees<BoundInstr>(p->n_trees, &p->bcode, &p->bcode_off, [&](int64_t t, std::vector<BoundInstr> *out) {
+        if (old && ru->src[(size_t)t] >= 0) {
+            const size_t s = (size_t)ru->src[(size_t)t];
+            out->insert(out->end(), old->bcode.begin() + old->bcode_off[s], old->bcode.begin() + old->bcode_off[s + 1]);
+            return;
+        }
         const int32_t i0 = off[(size_t)t], i1 = off[(size_t)t + 1];
         bind_tree(src.data() + i0, (size_t)(i1 - i0), ee, nf, out, prb);
     });
@@ -156,7 +176,7 @@ static int choose_waves(const de_program *p) {
     }
     return best;
 }
-static int make_threaded(de_ctx *c, de_program *p) {
+static int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr) {
     p->threaded = false;
     p->waves = 1;
     p->var_stride = 0;
@@ -196,7 +216,15 @@ static int make_threaded(de_ctx *c, de_program *p) {
     const int W = fuse ? p->waves_choice : 1;
     const int wave_prows = p->prows ? p->n_params : 0;
     const FuseRows rows0{(uint32_t)p->n_features, (uint32_t)(p->n_features + p->n_slots), 0, W > 1 ? wave_prows + (W - 1) * p->n_slots : 0};
+    // (de_program_update: a kept tree's fused code and wave-variant operand words are copied when the old program was threaded with the
+    // same binding and the same wave count — fuse_tree reads the tree's bound code and those only)
+    const de_program *old = ru && ru->old && ru->old->threaded && ru->old->waves_choice == p->waves_choice && same_binding(p, ru->old) ? ru->old : nullptr;
     build_stream_by_trees<BoundInstr>(p->n_trees, &p->fbcode, &p->tcode_off, [&](int64_t t, std::vector<BoundInstr> *out) {
+        if (old && ru->src[(size_t)t] >= 0) {
+            const size_t s = (size_t)ru->src[(size_t)t];
+            out->insert(out->end(), old->fbcode.begin() + old->tcode_off[s], old->fbcode.begin() + old->tcode_off[s + 1]);
+            return;
+        }
         const int32_t b0 = p->bcode_off[(size_t)t], b1 = p->bcode_off[(size_t)t + 1];
         if (fuse) fuse_tree(p->bcode.data() + b0, (size_t)(b1 - b0), out, W > 1 && p->n_slots > 0 ? &rows0 : nullptr);
         else out->insert(out->end(), p->bcode.begin() + b0, p->bcode.begin() + b1);
@@ -257,6 +285,7 @@ static int make_threaded(de_ctx *c, de_program *p) {
         const size_t n_rec = p->ccode.size();
         p->ccode_w.resize(n_rec * (size_t)(W - 1));
         std::atomic<bool> same{true};
+        const bool wold = old && old->waves == W && old->var_stride != 0 && old->ccode_w.size() == old->ccode.size() * (size_t)(W - 1);
         for (int w = 1; w < W; w++) {
             BoundInstr *cw = p->ccode_w.data() + n_rec * (size_t)(w - 1);
             const int shift = n_prows + w * p->n_slots; // [X | slots of wave 0 | parameter rows | slots of wave 1 | ...]: slot s of wave w = row F + S + P + (w - 1) S + s
@@ -267,6 +296,18 @@ static int make_threaded(de_ctx *c, de_program *p) {
                 const size_t r0 = (size_t)p->ccode_off[(size_t)tb] - 1, r1 = te < p->n_trees ? (size_t)p->ccode_off[(size_t)te] - 1 : n_rec;
                 std::copy(p->ccode.begin() + (long)r0, p->ccode.begin() + (long)r1, cw + r0);
                 for (int64_t t = tb; t < te; t++) {
+                    if (wold && ru->src[(size_t)t] >= 0) { // the old variant's operand words of the same records
+                        const size_t s = (size_t)ru->src[(size_t)t], h = (size_t)p->ccode_off[(size_t)t], ho = (size_t)old->ccode_off[s];
+                        const BoundInstr *ow = old->ccode_w.data() + old->ccode.size() * (size_t)(w - 1);
+                        for (int32_t i = 0; i < p->tcode_off[(size_t)t + 1] - p->tcode_off[(size_t)t]; i++) {
+                            BoundInstr &r = cw[h + (size_t)i];
+                            const BoundInstr &o = ow[ho + (size_t)i];
+                            r.bop = o.bop;
+                            if (f32) r.arg = o.arg;
+                            else { r.lo = o.lo; r.hi = o.hi; }
+                        }
+                        continue;
+                    }
                     b.clear();
                     f.clear();
                     bind_tree(src.data() + off[(size_t)t], (size_t)(off[(size_t)t + 1] - off[(size_t)t]), ee, p->n_features, &b, prb, shift);
@@ -405,7 +446,8 @@ static void recompute_host_ok(de_program *p) {
 static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, const int64_t *node_offsets,
                        int64_t n_trees, const void *consts, const int64_t *const_offsets, int32_t n_features,
                        int32_t n_params, uint32_t options, bool allow_fold, de_program_t **out_program,
-                       const de_tape_node_t *cse_nodes = nullptr, const int64_t *cse_offsets = nullptr);
+                       const de_tape_node_t *cse_nodes = nullptr, const int64_t *cse_offsets = nullptr, const Reuse *reuse = nullptr,
+                       bool keep_input = true);
 
 // Device copy of the host part of the eval flag: every de_eval starts from it with one device-to-device copy
 // (a pageable host-to-device copy per call costs ~10 us, a fifth of a small-population call).
@@ -518,12 +560,98 @@ int de_program_create_cse(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes,
                                 fold && cse ? cse_nodes : nullptr, cse_offsets));
 }
 
+// de_program_update: the resulting population's input is spliced from the retained one and the new trees, and a creation
+// with a Reuse map builds the program in scratch — only the new trees are lowered, bound and fused; every other per-tree slice (generic and
+// folded code, constant bookkeeping, folds, auxiliary trees, bound, fused and wave-variant code) is copied from the old program, and the
+// program-wide passes (fold evaluation, flags, threaded words, chained records, upload) run as at creation.  On success the scratch program
+// takes the old one's place; the old state is destroyed after a stream synchronisation (work already queued completes with it).
+static int update_impl(de_program_t *p, const int64_t *tree_ids, int64_t n_update, const de_tape_node_t *nodes, const int64_t *node_offsets,
+                       const de_tape_node_t *cse_nodes, const int64_t *cse_offsets, const void *consts, const int64_t *const_offsets) {
+    de_ctx *ctx = p->ctx;
+    if (n_update < 0) return fail(ctx, DE_ERR_INVALID_ARG, "n_update < 0");
+    if (n_update == 0) return DE_OK;
+    if (!tree_ids || !nodes || !node_offsets || !const_offsets) return fail(ctx, DE_ERR_INVALID_ARG, "null tree ids or tape pointers");
+    if (cse_nodes && !cse_offsets) return fail(ctx, DE_ERR_INVALID_ARG, "cse_offsets is null");
+    const int64_t n = p->n_trees;
+    if (p->in_noff.size() != (size_t)n + 1) return fail(ctx, DE_ERR_UNSUPPORTED, "the program keeps no input to update (an auxiliary program)");
+    std::vector<int32_t> slot((size_t)n, -1); // tree -> its position in the update, -1: kept
+    for (int64_t u = 0; u < n_update; u++) {
+        const int64_t t = tree_ids[u];
+        if (t < 0 || t >= n) return fail(ctx, DE_ERR_OUT_OF_RANGE, "tree id %lld outside [0, %lld)", (long long)t, (long long)n);
+        if (slot[(size_t)t] >= 0) return fail(ctx, DE_ERR_INVALID_ARG, "tree id %lld appears twice", (long long)t);
+        slot[(size_t)t] = (int32_t)u;
+    }
+    for (int64_t u = 0; u < n_update; u++)
+        if (node_offsets[u + 1] < node_offsets[u] || const_offsets[u + 1] < const_offsets[u] || (cse_nodes && cse_offsets[u + 1] < cse_offsets[u]))
+            return fail(ctx, DE_ERR_INVALID_ARG, "offsets not monotone at new tree %lld", (long long)u);
+    if (const_offsets[n_update] > const_offsets[0] && !consts) return fail(ctx, DE_ERR_INVALID_ARG, "consts is null");
+    // the CSE tapes as de_program_create_cse would take them now
+    const char *nc = getenv("DE_NO_CSE");
+    if (!p->allow_fold || (nc && *nc == '1')) cse_nodes = nullptr;
+    // the resulting population's input: tapes, CSE tapes, constants in the caller's element type, offsets
+    const size_t es = dtype_bytes(p->io);
+    std::vector<de_tape_node_t> nn, cn;
+    std::vector<int64_t> noff((size_t)n + 1, 0), coff((size_t)n + 1, 0), koff((size_t)n + 1, 0);
+    for (int64_t t = 0; t < n; t++) {
+        const int64_t u = slot[(size_t)t];
+        noff[(size_t)t + 1] = noff[(size_t)t] + (u >= 0 ? node_offsets[u + 1] - node_offsets[u] : p->in_noff[(size_t)t + 1] - p->in_noff[(size_t)t]);
+        coff[(size_t)t + 1] = coff[(size_t)t] + (u >= 0 ? (cse_nodes ? cse_offsets[u + 1] - cse_offsets[u] : 0) : p->in_coff[(size_t)t + 1] - p->in_coff[(size_t)t]);
+        koff[(size_t)t + 1] = koff[(size_t)t] + (u >= 0 ? const_offsets[u + 1] - const_offsets[u] : p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]);
+    }
+    nn.resize((size_t)noff[(size_t)n]);
+    cn.resize((size_t)coff[(size_t)n]);
+    std::vector<unsigned char> kv(std::max<size_t>((size_t)koff[(size_t)n], 1) * es, 0);
+    parallel_tree_ranges(n, [&](int, int64_t tb, int64_t te) {
+        for (int64_t t = tb; t < te; t++) {
+            const int64_t u = slot[(size_t)t];
+            if (u >= 0) {
+                std::copy(nodes + node_offsets[u], nodes + node_offsets[u + 1], nn.begin() + noff[(size_t)t]);
+                if (cse_nodes) std::copy(cse_nodes + cse_offsets[u], cse_nodes + cse_offsets[u + 1], cn.begin() + coff[(size_t)t]);
+                if (koff[(size_t)t + 1] > koff[(size_t)t])
+                    std::memcpy(kv.data() + (size_t)koff[(size_t)t] * es, static_cast<const unsigned char *>(consts) + (size_t)const_offsets[u] * es,
+                                (size_t)(koff[(size_t)t + 1] - koff[(size_t)t]) * es);
+            } else {
+                std::copy(p->in_nodes.begin() + p->in_noff[(size_t)t], p->in_nodes.begin() + p->in_noff[(size_t)t + 1], nn.begin() + noff[(size_t)t]);
+                std::copy(p->in_cse.begin() + p->in_coff[(size_t)t], p->in_cse.begin() + p->in_coff[(size_t)t + 1], cn.begin() + coff[(size_t)t]);
+                for (int64_t k = 0; k < koff[(size_t)t + 1] - koff[(size_t)t]; k++) {
+                    const size_t ok = (size_t)(p->const_off[(size_t)t] + k);
+                    store_elem(p->io, kv.data(), (size_t)(koff[(size_t)t] + k), p->consts[ok], p->consts_im.empty() ? 0.0 : p->consts_im[ok]);
+                }
+            }
+        }
+    }, 256);
+    // Float32 / Float64 programs splice; binary16 and complex ones (their constant-table indices and rounding) are rebuilt whole, as is a
+    // program whose creation had no folded stream to copy from
+    Reuse ru;
+    if ((p->io == DE_F32 || p->io == DE_F64) && (!p->allow_fold || p->folded) && !(getenv("DE_NO_UPDATE_SPLICE") && *getenv("DE_NO_UPDATE_SPLICE") == '1')) {
+        ru.old = p;
+        ru.src.resize((size_t)n);
+        for (int64_t t = 0; t < n; t++) ru.src[(size_t)t] = slot[(size_t)t] >= 0 ? -1 : (int32_t)t;
+        ru.fold0.assign((size_t)n + 1, 0);
+        for (const de_program::Fold &f : p->folds) ru.fold0[(size_t)f.tree + 1]++;
+        for (int64_t t = 0; t < n; t++) ru.fold0[(size_t)t + 1] += ru.fold0[(size_t)t];
+    }
+    const bool any_cse = coff[(size_t)n] > 0;
+    de_program_t *q = nullptr;
+    const int rc = create_impl(ctx, p->io, nn.data(), noff.data(), n, kv.data(), koff.data(), p->n_features, p->n_params, p->options, p->allow_fold, &q,
+                               any_cse ? cn.data() : nullptr, any_cse ? coff.data() : nullptr, ru.old ? &ru : nullptr);
+    if (rc != DE_OK) return rc; // (create_impl released its scratch program: the old one is untouched)
+    std::swap(*p, *q);
+    return de_program_destroy(q); // (synchronises the stream first)
+}
+
+int de_program_update(de_program_t *prog, const int64_t *tree_ids, int64_t n_update, const de_tape_node_t *nodes, const int64_t *node_offsets,
+                      const de_tape_node_t *cse_nodes, const int64_t *cse_offsets, const void *consts, const int64_t *const_offsets) {
+    if (!prog) return DE_ERR_INVALID_ARG;
+    DE_NOTHROW(prog->ctx, update_impl(prog, tree_ids, n_update, nodes, node_offsets, cse_nodes, cse_offsets, consts, const_offsets));
+}
+
 // The eval program of tree t is lowered from its CSE tape when the caller supplied one (a GraphNode tree: shared subtrees
 // appear once, de_program_create_cse); everything else — gradients, constant bookkeeping, flags — follows the expanded tape.
 static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, const int64_t *node_offsets,
                        int64_t n_trees, const void *consts, const int64_t *const_offsets, int32_t n_features,
                        int32_t n_params, uint32_t options, bool allow_fold, de_program_t **out_program,
-                       const de_tape_node_t *cse_nodes, const int64_t *cse_offsets) {
+                       const de_tape_node_t *cse_nodes, const int64_t *cse_offsets, const Reuse *reuse, bool keep_input) {
     if (!ctx) return DE_ERR_INVALID_ARG;
     if (!out_program) return fail(ctx, DE_ERR_INVALID_ARG, "out_program is null");
     *out_program = nullptr;
@@ -561,6 +689,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         p->n_features = n_features;
         p->n_params = n_params;
         p->n_trees = n_trees;
+        p->allow_fold = allow_fold;
         LowerOptions lo;
         lo.early_exit = (options & DE_OPT_EARLY_EXIT) != 0;
         lo.fuse1 = (options & DE_OPT_FUSE_DEG1) != 0;
@@ -574,6 +703,8 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         p->n_consts_tree.assign((size_t)n_trees, 0);
         p->host_ok_eval.assign((size_t)n_trees, 1);
         p->host_ok_grad.assign((size_t)n_trees, 1);
+        p->tree_slots.assign((size_t)n_trees, 0);
+        p->tree_bits.assign((size_t)n_trees, 0);
         const int64_t total_consts = n_trees ? const_offsets[n_trees] - const_offsets[0] : 0;
         if (total_consts < 0) return fail(ctx, DE_ERR_INVALID_ARG, "const_offsets not monotone");
         if (total_consts > 0 && !consts) return fail(ctx, DE_ERR_INVALID_ARG, "consts is null");
@@ -598,6 +729,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
             lof.fold = true;
             std::atomic<bool> oom{false};
             parallel_for_trees(n_trees, [&](int64_t t) {
+                if (reuse && reuse->reuse(t)) return; // (de_program_update: a kept tree — its lowerings are the old program's slices)
                 Lowered &L = low[(size_t)t];
                 const int64_t n0 = node_offsets[t], c0 = const_offsets[t];
                 try {
@@ -644,19 +776,67 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
             uint64_t total = 0;
             for (int64_t t = 0; t < n_trees; t++) {
                 if (low[(size_t)t].rc != DE_OK) return fail(ctx, low[(size_t)t].rc, "tree %lld: %s", (long long)t, low[(size_t)t].why.c_str());
-                total += low[(size_t)t].plain.code.size();
+                if (reuse && reuse->reuse(t)) {
+                    const size_t s = (size_t)reuse->src[(size_t)t];
+                    total += (uint64_t)(reuse->old->code_off[s + 1] - reuse->old->code_off[s]);
+                } else total += low[(size_t)t].plain.code.size();
                 if (total > 0x7fff0000u) return fail(ctx, DE_ERR_UNSUPPORTED, "program too large");
                 p->code_off[(size_t)t + 1] = (int32_t)total;
             }
             p->code.resize((size_t)total);
+            // the input, retained for de_program_update (copied per tree below; not for an auxiliary program, which is never updated by a
+            // caller: an update of its parent rebuilds it from the parent's fold tapes)
+            p->in_noff.clear();
+            p->in_coff.clear();
+            p->in_nodes.clear();
+            p->in_cse.clear();
+            if (keep_input) {
+                p->in_noff.resize((size_t)n_trees + 1);
+                p->in_coff.assign((size_t)n_trees + 1, 0);
+                for (int64_t t = 0; t <= n_trees; t++) p->in_noff[(size_t)t] = n_trees ? node_offsets[t] - node_offsets[0] : 0;
+                if (cse_nodes)
+                    for (int64_t t = 0; t <= n_trees; t++) p->in_coff[(size_t)t] = n_trees ? cse_offsets[t] - cse_offsets[0] : 0;
+                p->in_nodes.resize((size_t)p->in_noff[(size_t)n_trees]);
+                p->in_cse.resize((size_t)p->in_coff[(size_t)n_trees]);
+            }
             struct Part { int32_t n_slots = 0; bool cse = false, params = false; int64_t nodes = 0; } part[HOST_RANGES_MAX];
             parallel_tree_ranges(n_trees, [&](int wk, int64_t tb, int64_t te) {
                 Part &pt = part[wk];
                 for (int64_t t = tb; t < te; t++) {
                     const int64_t n0 = node_offsets[t], n1 = node_offsets[t + 1];
                     const int64_t c0 = const_offsets[t], c1 = const_offsets[t + 1];
-                    TreeProgram &tp = low[(size_t)t].plain;
+                    if (keep_input) std::copy(nodes + n0, nodes + n1, p->in_nodes.begin() + p->in_noff[(size_t)t]);
+                    if (keep_input && cse_nodes) std::copy(cse_nodes + cse_offsets[t], cse_nodes + cse_offsets[t + 1], p->in_cse.begin() + p->in_coff[(size_t)t]);
                     const int64_t cb = c0 - const_offsets[0];
+                    if (reuse && reuse->reuse(t)) { // the old tree's generic code: its constant instructions at the same places in the slice
+                        const de_program *o = reuse->old;
+                        const size_t s = (size_t)reuse->src[(size_t)t];
+                        const int64_t ocb = o->const_off[s];
+                        const int32_t ib = p->code_off[(size_t)t], ob = o->code_off[s];
+                        p->const_off[(size_t)t + 1] = cb + (c1 - c0);
+                        p->n_consts_tree[(size_t)t] = (int32_t)(c1 - c0);
+                        std::copy(o->code.begin() + ob, o->code.begin() + o->code_off[s + 1], p->code.begin() + ib);
+                        for (int64_t k = 0; k < c1 - c0; k++) {
+                            const double v = load_elem(io, consts, (size_t)(c0 + k));
+                            p->consts[(size_t)(cb + k)] = v;
+                            if (cplx) p->consts_im[(size_t)(cb + k)] = load_elem_im(io, consts, (size_t)(c0 + k));
+                            const int32_t oi = o->const_instr[(size_t)(ocb + k)];
+                            p->const_instr[(size_t)(cb + k)] = oi >= 0 ? ib + (oi - ob) : -1;
+                            p->const_checks[(size_t)(cb + k)] = o->const_checks[(size_t)(ocb + k)];
+                            if (oi >= 0) {
+                                if (cplx) write_cidx(p->code[(size_t)(ib + (oi - ob))], (size_t)(cb + k));
+                                else write_imm(p->code[(size_t)(ib + (oi - ob))], dtype, v);
+                            }
+                        }
+                        p->tree_slots[(size_t)t] = o->tree_slots[s];
+                        p->tree_bits[(size_t)t] = o->tree_bits[s];
+                        pt.cse = pt.cse || (o->tree_bits[s] & TREE_CSE_PLAIN);
+                        pt.n_slots = std::max(pt.n_slots, o->tree_slots[s]);
+                        pt.params = pt.params || (o->tree_bits[s] & TREE_PARAMS);
+                        pt.nodes += n1 - n0;
+                        continue;
+                    }
+                    TreeProgram &tp = low[(size_t)t].plain;
                     p->const_off[(size_t)t + 1] = cb + (c1 - c0); // (entry t is tree t - 1's, entry 0 stays 0)
                     p->n_consts_tree[(size_t)t] = (int32_t)(c1 - c0);
                     const int32_t ib = p->code_off[(size_t)t];
@@ -673,6 +853,8 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                         }
                     }
                     std::copy(tp.code.begin(), tp.code.end(), p->code.begin() + ib);
+                    p->tree_slots[(size_t)t] = tp.n_slots;
+                    p->tree_bits[(size_t)t] = (uint8_t)((tp.uses_params ? TREE_PARAMS : 0) | (low[(size_t)t].cse_plain ? TREE_CSE_PLAIN : 0));
                     pt.cse = pt.cse || low[(size_t)t].cse_plain;
                     pt.n_slots = std::max(pt.n_slots, tp.n_slots);
                     pt.params = pt.params || tp.uses_params;
@@ -700,6 +882,18 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
             {
                 uint64_t total = 0;
                 for (int64_t t = 0; t < n_trees; t++) {
+                    if (reuse && reuse->reuse(t)) {
+                        const de_program *o = reuse->old;
+                        const size_t s = (size_t)reuse->src[(size_t)t];
+                        const int64_t j0 = reuse->fold0[s], j1 = reuse->fold0[s + 1];
+                        total += (uint64_t)(o->fcode_off[s + 1] - o->fcode_off[s]);
+                        if (total > 0x7fff0000u) return fail(ctx, DE_ERR_UNSUPPORTED, "program too large");
+                        p->fcode_off[(size_t)t + 1] = (int32_t)total;
+                        fold0[(size_t)t + 1] = fold0[(size_t)t] + (j1 - j0);
+                        anode0[(size_t)t + 1] = anode0[(size_t)t] + (o->fold_noff[(size_t)j1] - o->fold_noff[(size_t)j0]);
+                        acs0[(size_t)t + 1] = acs0[(size_t)t] + (o->fold_coff[(size_t)j1] - o->fold_coff[(size_t)j0]);
+                        continue;
+                    }
                     const TreeProgram &tp = low[(size_t)t].folded;
                     if (low[(size_t)t].rcf != DE_OK)
                         return fail(ctx, low[(size_t)t].rcf, "tree %lld (folded): %s", (long long)t, low[(size_t)t].why.c_str());
@@ -727,11 +921,40 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                 for (int64_t t = tb; t < te; t++) {
                     const int64_t n0 = node_offsets[t];
                     const int64_t c0 = const_offsets[t], c1 = const_offsets[t + 1];
+                    if (reuse && reuse->reuse(t)) { // the old tree's folded code, its folds and their tape slices, renumbered
+                        const de_program *o = reuse->old;
+                        const size_t s = (size_t)reuse->src[(size_t)t];
+                        const int64_t cb = c0 - const_offsets[0], ocb = o->const_off[s];
+                        const int32_t ib = p->fcode_off[(size_t)t], ob = o->fcode_off[s];
+                        pt.cse = pt.cse || (o->tree_bits[s] & TREE_CSE_FOLDED);
+                        pt.n_slots = std::max(pt.n_slots, o->tree_slots[s]);
+                        std::copy(o->fcode.begin() + ob, o->fcode.begin() + o->fcode_off[s + 1], p->fcode.begin() + ib);
+                        for (int64_t k = 0; k < c1 - c0; k++) {
+                            const int32_t ci = o->fconst_instr[(size_t)(ocb + k)];
+                            if (ci < 0) continue;
+                            p->fconst_instr[(size_t)(cb + k)] = ib + (ci - ob);
+                            if (cplx) write_cidx(p->fcode[(size_t)(ib + (ci - ob))], (size_t)(cb + k));
+                            else write_imm(p->fcode[(size_t)(ib + (ci - ob))], dtype, p->consts[(size_t)(cb + k)]);
+                        }
+                        size_t an = (size_t)anode0[(size_t)t], ac = (size_t)acs0[(size_t)t];
+                        for (int64_t oj = reuse->fold0[s]; oj < reuse->fold0[s + 1]; oj++) {
+                            const size_t fi = (size_t)(fold0[(size_t)t] + (oj - reuse->fold0[s]));
+                            const de_program::Fold &of = o->folds[(size_t)oj];
+                            p->folds[fi] = {(int32_t)t, ib + (of.instr - ob), of.tested_always};
+                            for (int64_t q = o->fold_noff[(size_t)oj]; q < o->fold_noff[(size_t)oj + 1]; q++) anodes[an++] = o->fold_nodes[(size_t)q];
+                            for (int64_t q = o->fold_coff[(size_t)oj]; q < o->fold_coff[(size_t)oj + 1]; q++) p->aux_const_src[ac++] = o->aux_const_src[(size_t)q] - ocb + cb;
+                            anoff[fi + 1] = (int64_t)an;
+                            acoff[fi + 1] = (int64_t)ac;
+                        }
+                        continue;
+                    }
                     TreeProgram &tp = low[(size_t)t].folded;
                     const bool is_cse = low[(size_t)t].cse;
                     const de_tape_node_t *src_nodes = is_cse ? cse_nodes + cse_offsets[t] : nodes + n0; // the tape the fold spans index
                     pt.cse = pt.cse || is_cse;
                     pt.n_slots = std::max(pt.n_slots, tp.n_slots); // a CSE program keeps one persistent row per shared subtree
+                    p->tree_slots[(size_t)t] = std::max(p->tree_slots[(size_t)t], tp.n_slots);
+                    if (is_cse) p->tree_bits[(size_t)t] |= TREE_CSE_FOLDED;
                     const int64_t cb = c0 - const_offsets[0];
                     const int32_t ib = p->fcode_off[(size_t)t];
                     for (int64_t k = 0; k < c1 - c0; k++) {
@@ -850,8 +1073,28 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
                     std::vector<unsigned char> ac(std::max<size_t>(p->aux_csrc.size(), 1) * dtype_bytes(io), 0);
                     for (size_t k = 0; k < p->aux_csrc.size(); k++)
                         store_elem(io, ac.data(), k, p->consts[(size_t)p->aux_csrc[k]], cplx ? p->consts_im[(size_t)p->aux_csrc[k]] : 0.0);
+                    // (de_program_update: an auxiliary tree of a kept tree's fold is the old auxiliary program's tree of the same fold)
+                    Reuse aru;
+                    if (reuse && reuse->old->aux) {
+                        const de_program *o = reuse->old;
+                        std::vector<int32_t> oaux(o->folds.size(), -1);
+                        for (size_t a = 0; a < o->aux_fold.size(); a++) oaux[(size_t)o->aux_fold[a]] = (int32_t)a;
+                        aru.old = o->aux;
+                        aru.src.assign(p->aux_fold.size(), -1);
+                        for (size_t a = 0; a < p->aux_fold.size(); a++) {
+                            const size_t j = (size_t)p->aux_fold[a];
+                            const int64_t t = p->folds[j].tree;
+                            if (!reuse->reuse(t)) continue;
+                            const size_t s = (size_t)reuse->src[(size_t)t];
+                            aru.src[a] = oaux[(size_t)(reuse->fold0[s] + ((int64_t)j - fold0[(size_t)t]))];
+                        }
+                        aru.fold0.assign((size_t)o->aux->n_trees + 1, 0);
+                        for (const de_program::Fold &f : o->aux->folds) aru.fold0[(size_t)f.tree + 1]++;
+                        for (size_t q = 0; q < (size_t)o->aux->n_trees; q++) aru.fold0[q + 1] += aru.fold0[q];
+                    }
                     int rc = create_impl(ctx, io, xnodes.data(), xnoff.data(), (int64_t)p->aux_fold.size(), ac.data(),
-                                         xcoff.data(), n_features, 0, options, false, &p->aux);
+                                         xcoff.data(), n_features, 0, options, false, &p->aux, nullptr, nullptr, aru.old ? &aru : nullptr,
+                                         false);
                     if (rc != DE_OK) return rc;
                     lap("aux program (create)");
                 }
@@ -870,7 +1113,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         lap("release lowerings");
         if (cplx) fill_ctab_consts(p.get()); // (the folds' entries stay: refresh_folds wrote them)
         recompute_host_ok(p.get());
-        rebind(p.get());
+        rebind(p.get(), reuse);
         lap("bind");
     } catch (const std::bad_alloc &) {
         return fail(ctx, DE_ERR_HIP, "out of host memory");
@@ -878,7 +1121,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
         int rc = DE_OK;
-        try { rc = make_threaded(ctx, p.get()); } catch (const std::bad_alloc &) { rc = fail(ctx, DE_ERR_HIP, "out of host memory"); }
+        try { rc = make_threaded(ctx, p.get(), reuse); } catch (const std::bad_alloc &) { rc = fail(ctx, DE_ERR_HIP, "out of host memory"); }
         if (rc != DE_OK) return rc;
     }
     lap("threaded + chained records");
@@ -1035,6 +1278,8 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
                 p->bcode[(size_t)e.b].hi = hi;
                 p->tcode[(size_t)e.t].lo = lo;
                 p->tcode[(size_t)e.t].hi = hi;
+                p->fbcode[(size_t)e.t].lo = lo; // (the fused form too: de_program_update copies a kept tree's fused code from it)
+                p->fbcode[(size_t)e.t].hi = hi;
                 patch_chained_imm(p, e.c, lo, hi);
             }
         }, 4096);

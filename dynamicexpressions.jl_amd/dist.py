@@ -47,6 +47,20 @@ def scatter_population(trees, rank: int, world: int):
     return [trees[i] for i in shard_indices(len(trees), rank, world)]
 
 
+def shard_update(ids, trees, rank: int, world: int):
+    """The part of a population update (global tree ids, new trees) that lands on `rank`: (local ids, trees) for that rank's
+    ``Population.update``.  Global tree t lives on rank t mod world as local tree t // world (``shard_indices``)."""
+    ids = [int(t) for t in ids]
+    if len(ids) != len(trees):
+        raise ValueError(f"shard_update: {len(ids)} ids for {len(trees)} trees")
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_update: rank {rank} outside [0, {world})")
+    if any(t < 0 for t in ids):
+        raise ValueError("shard_update: negative tree id")
+    pick = [i for i, t in enumerate(ids) if t % world == rank]
+    return [ids[i] // world for i in pick], [trees[i] for i in pick]
+
+
 def unshard_order(n_trees: int, world: int) -> np.ndarray:
     """Permutation p with global_tree = p[k] for the concatenation of rank shards."""
     return np.concatenate([np.arange(r, n_trees, world) for r in range(world)]) if n_trees else np.zeros(0, int)

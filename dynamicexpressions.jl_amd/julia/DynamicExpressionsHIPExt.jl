@@ -363,6 +363,7 @@ mutable struct HIPPopulation{T}
     occ::Vector{Union{Nothing,Vector{Int}}}
     n_slots::Vector{Int}
     n_consts::Vector{Int}
+    optable::Any                                  # opcode_table of the population's operators (update_population! flattens with it)
 end
 function finalize_population(p::HIPPopulation)
     c = p.ctx
@@ -423,8 +424,57 @@ function HIPPopulation(
             hc, dtype_code(T), nodes, node_off, isempty(cse) ? C_NULL : pointer(cse), cse_off, length(trees), consts,
             const_off, n_features, n_params, option_bits(operators, eval_context; full_eval, forward_grad, reverse_grad), h))
     end
-    pop = HIPPopulation{T}(ctx, h[], length(trees), n_features, occ, n_slots, n_consts)
+    pop = HIPPopulation{T}(ctx, h[], length(trees), n_features, occ, n_slots, n_consts, optable)
     finalizer(finalize_population, pop)
+    return pop
+end
+"""
+    update_population!(pop, ids, trees)
+
+Replace trees `ids` (1-based) of `pop` by `trees` in place (`de_program_update`, DESIGN.md §3.4): flattened as `HIPPopulation` does,
+the result is what a fresh `HIPPopulation` of the resulting trees would be.  A captured graph of the population must be re-captured.
+"""
+function update_population!(
+    pop::HIPPopulation{T}, ids::AbstractVector{<:Integer}, trees::AbstractVector{<:AbstractExpressionNode{T}},
+) where {T}
+    length(ids) == length(trees) || throw(ArgumentError("update_population!: $(length(ids)) ids for $(length(trees)) trees"))
+    allunique(ids) || throw(ArgumentError("update_population!: a tree id appears twice"))
+    all(t -> 1 <= t <= pop.n_trees, ids) || throw(ArgumentError("update_population!: tree id outside 1:$(pop.n_trees)"))
+    isempty(ids) && return pop
+    optable = pop.optable
+    nodes, consts, cse = TapeNode[], T[], TapeNode[]
+    node_off, const_off, cse_off = Int64[0], Int64[0], Int64[0]
+    occ = Union{Nothing,Vector{Int}}[]
+    n_slots, n_consts = Int[], Int[]
+    for t in trees
+        c0 = length(consts)
+        flatten!(nodes, consts, t, optable, c0)
+        push!(node_off, length(nodes)); push!(const_off, length(consts))
+        o = nothing
+        if preserve_sharing(typeof(t))
+            mark = length(cse)
+            flatten_cse!(cse, t, optable) == 0 && resize!(cse, mark)
+            om = occurrence_map(t)
+            (!isempty(om) && maximum(om) < length(om)) && (o = om)
+        end
+        push!(cse_off, length(cse))
+        push!(occ, o)
+        push!(n_slots, length(consts) - c0)
+        push!(n_consts, o === nothing ? length(consts) - c0 : maximum(o))
+    end
+    ids0 = Int64[t - 1 for t in ids]
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve ids0 nodes consts node_off const_off cse cse_off ccall(
+            (:de_program_update, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{TapeNode}, Ptr{Int64}, Ptr{TapeNode}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}),
+            hp, ids0, length(ids0), nodes, node_off, isempty(cse) ? C_NULL : pointer(cse), isempty(cse) ? C_NULL : pointer(cse_off),
+            isempty(consts) ? C_NULL : pointer(consts), const_off))
+    end
+    for (i, t) in enumerate(ids)
+        pop.occ[t] = occ[i]
+        pop.n_slots[t] = n_slots[i]
+        pop.n_consts[t] = n_consts[i]
+    end
     return pop
 end
 """Gradient rows (or entries) of tree `t` in the library's per-occurrence layout -> the reference's layout: the rows of a shared

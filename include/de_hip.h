@@ -74,7 +74,8 @@ extern "C" {
  *      (d) dtypes DE_CF32 / DE_CF64 (interleaved complex X / constants / outputs, Julia's ComplexF32 / ComplexF64 arithmetic over the
  *      19 opcodes that have a Complex method with a Complex result) for the same calls, except that the host lowering
  *      hooks keep their real dtype domain and complex tapes lower through the new de_lower_tape_complex / de_lower_tape_stage_complex;
- *      the same entry points answer DE_ERR_UNSUPPORTED, and so does de_program_create with n_params > 0. */
+ *      the same entry points answer DE_ERR_UNSUPPORTED, and so does de_program_create with n_params > 0.
+ *      (e) de_program_update: replace some trees of a program in place, for every dtype. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -256,6 +257,29 @@ int de_program_create_cse(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes,
 /* Replace all constants (same counts, same order) without re-flattening: the
  * optimiser inner loop of get/set_scalar_constants (src/NodeUtils.jl:99-143). */
 int de_program_set_consts(de_program_t *prog, const void *consts);
+/* Replace trees tree_ids[0 .. n_update) of `prog` with the n_update trees given in de_program_create's layout
+ * (nodes / node_offsets / consts / const_offsets describe the NEW trees only, in the order of tree_ids).
+ * cse_nodes / cse_offsets may be NULL (no sharing in the new trees), else as de_program_create_cse.
+ * The population keeps its size, its order, dtype, n_features, n_params and options.  Afterwards the program is
+ * indistinguishable from a fresh creation of the resulting population: every entry point returns the same bits,
+ * de_program_stream_hash is equal, de_program_n_grad / _n_nodes / _dump agree.  On any error the program is unchanged.
+ *   - Everything is checked before anything changes: DE_ERR_INVALID_ARG for a duplicate id, a null buffer when n_update > 0
+ *     or offsets that are not monotone; DE_ERR_OUT_OF_RANGE for an id outside [0, n_trees) or a feature / parameter index at or
+ *     above the counts the program was created with; DE_ERR_BAD_TAPE / DE_ERR_UNSUPPORTED_OP as de_program_create returns them
+ *     (a complex program names the refused opcode in de_last_error, as at creation).
+ *   - n_update == 0 is a no-op and returns DE_OK.
+ *   - A tree's constant count may change: the constant vector is renumbered as a fresh creation numbers it, and
+ *     de_program_set_consts afterwards takes the new total.
+ *   - Every dtype is accepted.  DE_F32 / DE_F64 programs lower only the new trees and copy every other tree's code; DE_F16 and
+ *     complex programs are rebuilt whole from the retained population (same result).
+ *   - Stream ordering as de_program_set_consts: work already queued on the context's stream that reads the program completes
+ *     with the old trees (the call synchronises the stream before it releases them).
+ *   - A hipGraph / torch.cuda.graph that captured a launch of this program names device buffers the update releases: it must
+ *     be re-captured after an update, exactly as after de_program_destroy.  Never replay such a graph. */
+int de_program_update(de_program_t *prog, const int64_t *tree_ids, int64_t n_update,
+                      const de_tape_node_t *nodes, const int64_t *node_offsets,
+                      const de_tape_node_t *cse_nodes, const int64_t *cse_offsets,
+                      const void *consts, const int64_t *const_offsets);
 int de_program_destroy(de_program_t *prog);
 int64_t de_program_n_trees(const de_program_t *prog);
 /* Sum over trees of count_nodes (src/base.jl:271-280): the node-evals unit. */
