@@ -16,6 +16,11 @@ form produces the N-GPU line as well.  `--workload C4` is BASELINE config 4: 10 
 10^7 samples tree-sharded 8 ways (rank r owns trees {t : t mod 8 = r}, 1 250 trees and 50 GB of
 output per GPU); with fewer than 8 ranks the job covers the first N shards (N=1: rank 0's shard).
 
+A plain run sets up, does the W warm-up and K timed steps, writes --dump-outputs, and prints the line.  `--full` adds every
+secondary leg, each of which times steps of its own after the timed ones: `turbo`, `full_evaluation`, `complete_only`,
+`dataset_declared`, `rounds_1_4_x`, `forward_default`, `search_generation`, `cpu_baseline` and, for the 1-GPU headline,
+`configs` (BASELINE configs 2-5) and `wide_x`.  The `--no-*` switches drop single legs from a `--full` run.
+
 Rank 0 prints ONE JSON line: metric node-evals/s (whole job), plus
   roofline     — the dominant kernel's ALGORITHMIC bytes / its average launch duration measured
                  with hipEvents on the launch stream inside the timed region, against 8 TB/s HBM3E.
@@ -29,7 +34,7 @@ Rank 0 prints ONE JSON line: metric node-evals/s (whole job), plus
                  population's dispatch histogram x the per-handler ISA slot counts of
                  profiles/valu_slots.json, tools/valu_slots.py) -> SIMD cycles at 2.4 GHz -> the
                  fraction of that floor the measured kernel time reaches.
-  cpu_baseline — the CPU oracle (C restatement of the reference algorithm) timed on bounded samples
+  cpu_baseline — (--full) the CPU oracle (C restatement of the reference algorithm) timed on bounded samples
                  of the same workload on this box's host cores: one tree per task on ALL host cores
                  (`value`, `cores`) and on ONE thread (`single_thread`), plus the result of probing
                  for a `julia` binary (`julia_probe`; the reference itself cannot run on this box).
@@ -396,20 +401,24 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="headline", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (other modes, populations and configs, CPU baseline): without it a run does the "
+                         "warm-up and timed steps of the workload and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and `search_generation`")
     ap.add_argument("--no-configs", action="store_true",
-                    help="the default run (--workload headline, 1 GPU) also times BASELINE configs 2, 3, 4 (rank 0's shard) and the config-5 family "
+                    help="--full with --workload headline on 1 GPU also times BASELINE configs 2, 3, 4 (rank 0's shard) and the config-5 family "
                          "and reports them under `configs`; this skips them")
     ap.add_argument("--turbo", action="store_true",
                     help="EvalContext(turbo=true): the relaxed-accuracy Float32 operators (DE_OPT_TURBO) for the whole run; "
-                         "without it the plain-eval workloads time the exact mode and report turbo in a `turbo` sub-object")
+                         "without it the plain-eval workloads time the exact mode and (--full) report turbo in a `turbo` sub-object")
     ap.add_argument("--scaling", choices=["auto", "strong", "weak"], default="auto",
                     help="N > 1: 'strong' = the workload's population split over the N ranks (the metric of BASELINE.json: 1000 trees x "
                          "10^7 samples at 1/2/4/8 GPUs), 'weak' = the workload's population PER rank.  auto = strong (C4: its 8-way shards)")
-    ap.add_argument("--no-turbo-leg", action="store_true", help="skip the secondary turbo timing (profiling runs: one kernel variant per process)")
-    ap.add_argument("--no-full-eval-leg", action="store_true", help="skip the secondary timing without the early exit (DE_OPT_FULL_EVAL)")
+    ap.add_argument("--no-turbo-leg", action="store_true", help="--full: skip the secondary turbo timing (profiling runs: one kernel variant per process)")
+    ap.add_argument("--no-full-eval-leg", action="store_true", help="--full: skip the secondary timing without the early exit (DE_OPT_FULL_EVAL)")
     ap.add_argument("--no-complete-leg", action="store_true",
-                    help="skip the `complete_only` leg: the same generator rejection-sampled to a population of COMPLETE trees (the kernel-quality number)")
+                    help="--full: skip the `complete_only` leg (the same generator rejection-sampled to a population of COMPLETE trees: the "
+                         "kernel-quality number) and the `dataset_declared`, `rounds_1_4_x` and `forward_default` legs")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step of the workload returned to its caller as DIR/<name>.npy "
                          "(float32; samples.npy: the sample indices, float64): a fixed, seeded sample of the samples axis, <= 64 MB in all.  "
@@ -419,6 +428,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # every secondary leg of run_workload() and main() is behind one of these switches
+        args.no_cpu_baseline = args.no_configs = args.no_turbo_leg = args.no_full_eval_leg = args.no_complete_leg = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher of N ranks (one per GPU, RCCL over xGMI) and relay
@@ -509,7 +521,7 @@ def main():
             X = torch.randn((N, 5), generator=g, device=dev, dtype=torch.float32).t()  # [5, N] feature-fastest
             x_source = "torch.randn(device generator, seed 1) [DE_BENCH_TORCH_X=1]"
         else:
-            if N not in x_cache:  # (one X per sample count: the `configs` legs of the default run share the 10^6-sample X)
+            if N not in x_cache:  # (one X per sample count: the `configs` legs of a --full run share the 10^6-sample X)
                 Xh = de.synth.random_X(5, N, seed=1, dtype=np.float32)  # (5, N) Fortran-ordered = [N, 5] row-major storage
                 x_cache[N] = torch.from_numpy(np.ascontiguousarray(Xh.T)).to(dev).t()  # [5, N] feature-fastest, strides (1, 5)
                 del Xh
@@ -742,7 +754,7 @@ def main():
         for _ in range(args.warmup):
             step()
         if not primary:
-            # the `configs` legs of the default run: W warm-up steps of a 1 ms workload are 5 ms — the device has not reached its steady
+            # the `configs` legs of a --full run: W warm-up steps of a 1 ms workload are 5 ms — the device has not reached its steady
             # clocks by then (measured in round 6, same box: C2 1.025 ms after 5 warm-up steps, 0.937 after 50 or 200; the headline, C3 and C5
             # do not move: their W steps already take tens of ms).  These legs therefore warm up for at least 80 ms of wall time; the PRIMARY
             # workload of a run (what --warmup W is the contract for) does exactly W steps.
@@ -1078,7 +1090,7 @@ def main():
                     kw = dict(kind="param", params=np.asfortranarray(params.cpu().numpy().T), classes=classes[:Ns].cpu().numpy())
                 elif is_grad:
                     kw = dict(kind="grad")
-                # the default run carries several baselines: the headline's keeps its budgets (<= 11 s on all cores + 7 s on one
+                # a --full run carries several baselines: the headline's keeps its budgets (<= 11 s on all cores + 7 s on one
                 # thread), the configs' legs get <= 8 s on all cores + 3 s on one thread each
                 b_all, b_one = (11.0, 7.0) if primary else (8.0, 3.0)
                 res["cpu_baseline"] = cpu_baseline(all_trees, ops, Xh, b_all, b_one, **kw)

@@ -1,4 +1,4 @@
-"""bench.py's CPU-side helpers (no GPU): the `cpu_baseline` legs of the three reference calls the default run times at the configs' shapes —
+"""bench.py's CPU-side helpers (no GPU): the `cpu_baseline` legs of the three reference calls a --full run times at the configs' shapes —
 eval_tree_array (C2), eval_grad_tree_array(variable=true) (C3), the ParametricExpression eval + constant-mode gradient (C5) — on tiny inputs."""
 import os
 import sys
@@ -29,7 +29,7 @@ def test_cpu_baseline_kinds_time_the_reference_calls_of_the_configs():
 
 
 def test_default_run_lists_every_baseline_config():
-    """the `configs` legs of the default run = BASELINE.json's configs 2-5 (config 4 as rank 0's shard, config 5 in its three readings)"""
+    """the `configs` legs of a --full run = BASELINE.json's configs 2-5 (config 4 as rank 0's shard, config 5 in its three readings)"""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'for k in ("C2", "C3", "C4", "C5", "C5N", "C5Ng", "C5pb")' in src
     for k in ("C2", "C3", "C4", "C5", "C5N", "C5Ng", "C5pb"):
@@ -79,3 +79,25 @@ def test_dump_outputs_are_the_same_for_any_number_of_steps(tmp_path):
         assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, dumps[1][f]), f
     ok, out = dumps[0]["ok.npy"].astype(bool), dumps[0]["out.npy"]
     assert 0 < ok.sum() < len(ok) and (out[~ok] == 0).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_does_the_timed_steps_only_and_full_adds_the_legs():
+    """A plain `bench.py` run warms up, times the steps and prints the line; `--full` adds the secondary legs on top of the same line."""
+    import json
+    import subprocess
+    lines = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--gpus", "1", "--steps", "2", "--warmup", "1"] + extra,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = lines
+    for d in (plain, full):
+        assert d["metric"] == "node-evals/sec" and d["unit"] == "node-evals/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["frac"] > 0
+    legs = ("turbo", "full_evaluation", "complete_only", "dataset_declared", "rounds_1_4_x", "forward_default", "search_generation",
+            "cpu_baseline", "configs", "wide_x")
+    assert not [k for k in legs if k in plain]
+    assert all(k in full for k in ("turbo", "full_evaluation", "dataset_declared"))
+    assert plain["config"]["complete_fraction"] == full["config"]["complete_fraction"]

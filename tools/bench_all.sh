@@ -1,6 +1,6 @@
 O=gpurun_out/$1; mkdir -p $O
 for wl in C2 C3 C4 C5 C5N C5Ng loss lossgrad C5pb; do
-  timeout 900 python bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "bench $wl failed rc=$?"
+  timeout 900 python bench.py --workload $wl --steps 10 --warmup 2 --full --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "bench $wl failed rc=$?"
   python - <<PY
 import json
 try:

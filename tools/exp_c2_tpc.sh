@@ -3,7 +3,7 @@
 # of a launch that fills the chip only ~4 times, against one more staging of the X tile per chunk.   gpurun -- 'bash tools/exp_c2_tpc.sh'
 O=gpurun_out/c2_tpc; mkdir -p $O
 for tpc in ${TPCS:-63 48 40 32 24 16}; do
-  DE_EVAL_TPC=$tpc timeout 600 python bench.py --workload ${WL:-C2} --steps 100 --warmup 5 --no-cpu-baseline --no-turbo-leg --no-full-eval-leg > $O/tpc_$tpc.json 2> $O/tpc_$tpc.err
+  DE_EVAL_TPC=$tpc timeout 600 python bench.py --workload ${WL:-C2} --steps 100 --warmup 5 --full --no-cpu-baseline --no-turbo-leg --no-full-eval-leg > $O/tpc_$tpc.json 2> $O/tpc_$tpc.err
   python - $tpc $O/tpc_$tpc.json <<'P'
 import json, sys
 d = json.load(open(sys.argv[2]))
