@@ -107,10 +107,12 @@ for spec in f:float d:double; do  # the reverse-accumulation kernel: one module 
   build_kernels de_rev_threaded.hip $OBJ/de_rt_$tag.o -DDE_RT_T=$ty -DDE_RT_TAG=$tag &
 done
 build_obj de_grad_kernels.hip $OBJ/de_grad_kernels.o &
-build_obj de_half.hip $OBJ/de_half.o & # the binary16 eval kernel (DE_F16): plain hipcc, none of the IR / assembly passes
-build_obj de_complex.hip $OBJ/de_complex.o & # the complex eval kernel (DE_CF32 / DE_CF64): plain hipcc, likewise
+# the flat-switch interpreter (de_flat.h), one translation unit per value policy: plain hipcc, none of the IR / assembly passes (no handler in them)
+build_obj de_flat_real.hip $OBJ/de_flat_real.o & # Float32 / Float64
+build_obj de_half.hip $OBJ/de_half.o &           # binary16 (DE_F16)
+build_obj de_complex.hip $OBJ/de_complex.o &     # complex (DE_CF32 / DE_CF64)
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

@@ -284,19 +284,15 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     HIP_TRY(c, time_begin(c));
     a.compacted = &p->last_compacted;
     p->last_compacted = false;
-    if (half) { // de_half.hip: no threaded kernel, priority tiles or compaction (de_api_internal.h de_program::io)
+    if (half || cplx) { // the flat-switch interpreter only: no threaded kernel, priority tiles or compaction (de_api_internal.h de_program::io)
         a.threaded = false;
         a.prio_keys = nullptr;
         a.compact_code = nullptr;
         a.compact_ints = nullptr;
-        HIP_TRY(c, launch_eval_f16(a, c->stream, &c->last_kernel));
-    } else if (cplx) { // de_complex.hip: the same restrictions, plus the program's constant table
-        a.threaded = false;
-        a.prio_keys = nullptr;
-        a.compact_code = nullptr;
-        a.compact_ints = nullptr;
-        HIP_TRY(c, launch_eval_complex(p->io, a, p->d_ctab, c->stream, &c->last_kernel));
-    } else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
+    }
+    if (half) HIP_TRY(c, launch_eval_f16(a, c->stream, &c->last_kernel));
+    else if (cplx) HIP_TRY(c, launch_eval_complex(p->io, a, p->d_ctab, c->stream, &c->last_kernel)); // (+ the program's constant table)
+    else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
     HIP_TRY(c, time_end(c));
     if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
     if (sOut.staged) {

@@ -302,14 +302,8 @@ static inline void store_elem(int dtype, void *p, size_t k, double v, double im 
     else if (dtype == DE_F16) static_cast<_Float16 *>(p)[k] = (_Float16)v;
     else static_cast<float *>(p)[k] = (float)v;
 }
-// de_half.hip: the binary16 eval kernel (flat switch over the bound program, PARAMS and CERT variants); EvalArgs as for launch_eval
 namespace de {
-hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **kernel_name);
-void eval_plan_f16(int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk); // (de_eval_plan)
-// de_complex.hip: the complex eval kernel (DE_CF32 / DE_CF64); ctab = the program's device constant table (de_program::d_ctab)
-hipError_t launch_eval_complex(int io, const EvalArgs &a, const void *ctab, hipStream_t stream, const char **kernel_name);
-void eval_plan_complex(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk);
-size_t complex_row_bytes(int io); // bytes of one LDS row (X feature / spill slot) of the complex kernel
+size_t complex_row_bytes(int io); // bytes of one LDS row (X feature / spill slot) of the complex policy (de_complex.hip)
 bool complex_opcode_ok(int degree, int op); // the 19 opcodes with a Complex method and a Complex result
 }
 

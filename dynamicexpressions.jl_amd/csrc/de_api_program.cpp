@@ -183,7 +183,7 @@ static int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr) {
     p->ccode_w.clear();
     dbg_lap(nullptr);
     // the LDS-staged kernels need (n_features + n_slots) rows of 4112 B; wider X uses the direct variant
-    p->direct = (size_t)eval_rows(p) * 257 * 16 > 150 * 1024; // (the flat-switch kernel's geometry: 256 threads x 16 bytes per row; it gathers the features of a wider X from global memory)
+    p->direct = (size_t)eval_rows(p) * FLAT_ROW_BYTES > 150 * 1024; // (the flat-switch kernel's geometry: 256 threads x 16 bytes per row; it gathers the features of a wider X from global memory)
     if (p->io == DE_F16) return DE_OK; // binary16 programs run de_half.hip's flat-switch kernel only
     if (is_complex_io(p->io)) { // complex programs: de_complex.hip's flat-switch kernel, whose rows are complex_row_bytes
         p->direct = (size_t)eval_rows(p) * complex_row_bytes(p->io) > 64 * 1024;
@@ -1416,9 +1416,7 @@ int de_prio_tiles_wanted(int64_t N, int32_t n_features, int64_t n_trees) { retur
 
 int de_eval_plan(const de_program_t *p, int64_t N, int32_t *plan) {
     if (!p || !plan || N < 0) return DE_ERR_INVALID_ARG;
-    if (p->io == DE_F16) eval_plan_f16(p->n_trees, N, &plan[0], &plan[1], &plan[2]);
-    else if (is_complex_io(p->io)) eval_plan_complex(p->io, p->n_trees, N, &plan[0], &plan[1], &plan[2]);
-    else eval_plan(p->dtype, p->n_trees, N, &plan[0], &plan[1], &plan[2], p->threaded ? p->waves : 1);
+    eval_plan(p->io, p->n_trees, N, &plan[0], &plan[1], &plan[2], p->threaded ? p->waves : 1);
     return DE_OK;
 }
 

@@ -1,5 +1,5 @@
 // de_kernels.h — launch interface between the C ABI (de_api*.cpp) and the gfx950
-// kernels (de_kernels.hip).
+// kernels (de_kernels.hip, de_flat_real.hip, de_half.hip, de_complex.hip, de_grad_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +34,9 @@ constexpr int TG_F32 = DE_TG, TG_F64 = 1;
 constexpr int tg_planes(int dtype) { return dtype == DE_F32 ? TG_F32 : TG_F64; }
 constexpr int ttile_samples(int dtype) { return TBLK * tg_planes(dtype) * (dtype == DE_F32 ? 4 : 2); } // samples per workgroup tile
 constexpr size_t trow_bytes(int dtype) { return (size_t)(TBLK * tg_planes(dtype) + 1) * 16; } // LDS row stride: the planes + one vector of padding (bank spread)
+// The flat-switch interpreter (de_flat.h): 256 lanes x the value policy's samples per lane; the real and binary16 policies' LDS row
+constexpr int flat_tile_samples(int io) { return io == DE_F32 || io == DE_F16 ? 1024 : (io == DE_CF64 ? 256 : 512); }
+constexpr size_t FLAT_ROW_BYTES = 257 * 16; // 256 16-byte vectors + one of padding (bank spread for the staging writes)
 
 // Fused loss epilogue of the threaded eval kernel (de_eval_loss): instead of storing out[t][j] the
 // kernel reduces sum_j w_j * l(out[t][j] - y[j]) per tree (per-wave partials + two fixed-order passes).
@@ -161,6 +164,11 @@ struct GradArgs {
 // Returns hipSuccess or the failing HIP error.  `kernel_name` receives the symbol
 // name of the launched kernel (for matching rocprofv3 kernel-trace rows).
 hipError_t launch_eval(int dtype, const EvalArgs &a, hipStream_t stream, const char **kernel_name);
+// The flat-switch interpreter (de_flat.h launch_flat), one entry per translation unit: Float32 / Float64 (de_flat_real.hip), binary16
+// (de_half.hip), complex (de_complex.hip; ctab = the program's device constant table, de_program::d_ctab)
+hipError_t launch_eval_flat(int dtype, const EvalArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t launch_eval_complex(int io, const EvalArgs &a, const void *ctab, hipStream_t stream, const char **kernel_name);
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);
 
 // Threaded gradient kernel: window width used for a population whose widest gradient has max_grad rows,
@@ -201,8 +209,8 @@ hipError_t handler_device_slot(int *slot);
 hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table);
 bool eval_uses_threaded();
 
-// Launch plan of the eval kernel for (n_trees, N): samples per workgroup tile, tree chunks.
-void eval_plan(int dtype, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk, int waves = 1); // (waves: de_program::waves — wave groups)
+// Launch plan of the eval kernel for (n_trees, N): samples per workgroup tile, tree chunks.  io = the program's io type, any of the five.
+void eval_plan(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk, int waves = 1); // (waves: de_program::waves — wave groups)
 
 // Scratch the fused-loss reduction needs for (dtype, n_trees, N).
 void loss_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_bytes, size_t *seg_bytes);
@@ -212,8 +220,5 @@ void loss_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_b
 hipError_t launch_loss_reduce_tiles(int dtype, const void *partial, int64_t n_cols, int64_t n_tiles, void *seg_sum,
                                     int32_t *n_segs, hipStream_t stream);
 int32_t loss_segments(int64_t n_tiles);
-
-// LDS bytes the eval kernel needs for (dtype, F, n_slots); 0 if it cannot fit.
-size_t eval_lds_bytes(int dtype, int F, int n_slots, int *K_out);
 
 } // namespace de

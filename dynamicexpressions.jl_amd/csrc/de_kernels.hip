@@ -8,7 +8,7 @@
 //    TILE = 256 consecutive Float32 samples (4 per lane; 128 Float64) and runs a chunk of <= 63 trees as ONE chain of
 //    direct-threaded handlers — or, when LDS rows leave such a workgroup short of resident waves (staged parameter rows, many features),
 //    a WAVE GROUP of 2 / 4 / 8 waves on one tile that share the staged rows and run a chunk each (KArgs::var_stride, round 6);
-//    the flat-switch fall-back kernel uses 256 threads = 4 wave64 and G vectors per thread.
+//    the flat-switch interpreter (de_flat.h: wide X, the certificate pass, DE_EVAL_THREADED=0, Float16 and complex) is not in this module.
 //    Large early-exit launches are three launches: the priority tiles as a probe, the compaction of the live trees
 //    (de_compact_live_kernel), the launch proper over the re-linked stream.
 //  * The X tile ([F, TILE], feature-fastest in HBM) is read ONCE per workgroup with
@@ -39,15 +39,11 @@
 #include "de_bind.h"
 #include "de_device_ops.h"
 #include "de_kernels.h"
+#include "de_plan.h"
+#include "de_real_vec.h"
 
 namespace de {
 
-// Wave-uniform read-only data is addressed through the constant address space so
-// the compiler emits scalar loads (s_load_*) for it.
-#define DE_CONSTANT __attribute__((address_space(4)))
-typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
-typedef const DE_CONSTANT U32x4 *ConstU4Ptr;
-typedef const DE_CONSTANT int32_t *ConstI32Ptr;
 
 template <typename T> struct KArgs {
     const BoundInstr *code;  // bound program, padded with one trailing instruction (prefetch reads pc+1)
@@ -84,8 +80,7 @@ template <typename T> struct KArgs {
     const int32_t *ctrl;
     // threaded kernel: sample tiles per XCD that run one chunk before the next chunk starts (map_block_grouped); 0 = chunk-fastest (map_block)
     int32_t map_group;
-    // flat-switch kernel, CERT variant (de_eval_sum_certificate): per tree the largest |value| among the values the kernel validity-tests,
-    // as the bits of a non-negative T in an unsigned word (atomicMax); nothing is stored to `out`
+    // always null (the certificate pass runs the flat-switch interpreter, de_flat.h): holds the place, so the fields behind it keep their offsets
     void *cert_max;
     // threaded kernel: the LAST chunk of the plan runs as `tail_split` sub-chunks (1 = as it is): the workgroups that finish a launch are
     // short ones — the tail of a launch that fills the chip only a few times (10^6 samples: ~9 times, one 60-tree workgroup = 100 us of 900)
@@ -99,252 +94,6 @@ template <typename T> struct KArgs {
     uint32_t list_off;
 };
 
-// Chunk plan of a launch over n trees and n_tiles sample tiles (host: plan_chunks; device: de_compact_live_kernel for the live trees):
-// chunks of <= tpc_max trees, more of them while the grid would not cover the chip `want_blocks` times, never fewer than 8 trees per chunk.
-// nc0 = the chunk count before trees are spread evenly: an upper bound of the final count that is monotone in n.
-__host__ __device__ inline void chunk_plan(int64_t n, int64_t n_tiles, int64_t tpc_max, int64_t want_blocks, int32_t *n_chunks_out, int32_t *tpc_out, int32_t *nc0_out) {
-    if (tpc_max < 1) tpc_max = 63;
-    int64_t n_chunks = (n + tpc_max - 1) / tpc_max;
-    if (n_tiles > 0 && n_tiles * n_chunks < want_blocks) n_chunks = (want_blocks + n_tiles - 1) / n_tiles;
-    const int64_t max_chunks = (n + 7) / 8; // >= 8 trees per chunk
-    if (n_chunks > max_chunks) n_chunks = max_chunks;
-    if (n_chunks < 1) n_chunks = 1;
-    if (nc0_out) *nc0_out = (int32_t)n_chunks;
-    const int64_t tpc = n > 0 ? (n + n_chunks - 1) / n_chunks : 1;
-    *tpc_out = (int32_t)tpc;
-    *n_chunks_out = (int32_t)(n > 0 ? (n + tpc - 1) / tpc : 0);
-}
-
-// A thread owns G groups of VW consecutive samples (VW*sizeof(T) = 16 bytes, one
-// ds_read_b128 / global_store_dwordx4 per group): samples base + g*(BLOCK*VW) + tid*VW + i.
-template <typename T> struct VecOf;
-template <> struct VecOf<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int W = 4; };
-template <> struct VecOf<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int W = 2; };
-
-template <typename T> __device__ __forceinline__ T imm_of(uint32_t w2, uint32_t w3);
-template <> __device__ __forceinline__ float imm_of<float>(uint32_t w2, uint32_t) { return __uint_as_float(w2); }
-template <> __device__ __forceinline__ double imm_of<double>(uint32_t w2, uint32_t w3) {
-    return __longlong_as_double((long long)(((unsigned long long)w3 << 32) | w2));
-}
-
-#define DE_UNROLL _Pragma("unroll")
-#define FOR_G DE_UNROLL for (int g = 0; g < G; g++)
-#define FOR_I DE_UNROLL for (int i = 0; i < VW; i++)
-
-// acc = f(b) for every sample
-#define U_CASE(OPC, EXPR)                                    \
-    case OPC:                                                \
-        FOR_G FOR_I {                                        \
-            const T x = b[g][i];                             \
-            acc[g][i] = (EXPR);                              \
-        }                                                    \
-        break;
-// acc = f(acc, b)
-#define B_CASE(OPC, EXPR)                                    \
-    case OPC:                                                \
-        FOR_G FOR_I {                                        \
-            const T x = acc[g][i], y = b[g][i];              \
-            acc[g][i] = (EXPR);                              \
-        }                                                    \
-        break;
-
-// The interpreter's inner loop must contain ONLY wave-uniform control flow: one divergent
-// branch anywhere inside it makes LLVM structurize the whole loop and bury the scalar
-// dispatch under "Flow" blocks (the kernel is scalar-issue bound).  Anything
-// with lane-divergent branches (OCML pow/fmod/tgamma/Payne-Hanek ...) therefore lives in
-// __noinline__ functions that take and return register-resident values.
-template <typename T, int G> struct VG { typename VecOf<T>::type v[G]; };
-
-// Everything that is not on the fast path of the interpreter loop.
-template <typename T, int G>
-__device__ __noinline__ VG<T, G> cold_op(uint32_t op, VG<T, G> accv, VG<T, G> bv) {
-    using m = M<T>;
-    typedef typename VecOf<T>::type V;
-    constexpr int VW = VecOf<T>::W;
-    V (&acc)[G] = accv.v;
-    const V (&b)[G] = bv.v;
-    switch (op) {
-        U_CASE(DE_U_NEG, -x)
-        U_CASE(DE_U_ABS, m::abs(x))
-        U_CASE(DE_U_SQUARE, x * x)
-        U_CASE(DE_U_CUBE, (x * x) * x)
-        U_CASE(DE_U_RELU, x < T(0) ? T(0) : x)
-        U_CASE(DE_U_SIGN, jl_sign(x))
-        U_CASE(DE_U_ROUND, m::rint(x))
-        U_CASE(DE_U_FLOOR, m::floor(x))
-        U_CASE(DE_U_CEIL, m::ceil(x))
-        U_CASE(DE_U_INV, T(1) / x)
-        U_CASE(DE_U_SQRT, m::sqrt(x))
-        U_CASE(DE_U_CBRT, m::cbrt(x))
-        U_CASE(DE_U_EXP, m::exp(x))
-        U_CASE(DE_U_COS, m::cos(x))
-        U_CASE(DE_U_EXP2, m::exp2(x))
-        U_CASE(DE_U_LOG, m::log(x))
-        U_CASE(DE_U_LOG2, m::log2(x))
-        U_CASE(DE_U_LOG10, m::log10(x))
-        U_CASE(DE_U_LOG1P, m::log1p(x))
-        U_CASE(DE_U_SIN, m::sin(x))
-        U_CASE(DE_U_TAN, m::tan(x))
-        U_CASE(DE_U_SINH, m::sinh(x))
-        U_CASE(DE_U_COSH, m::cosh(x))
-        U_CASE(DE_U_TANH, m::tanh(x))
-        U_CASE(DE_U_ASIN, m::asin(x))
-        U_CASE(DE_U_ACOS, m::acos(x))
-        U_CASE(DE_U_ATAN, m::atan(x))
-        U_CASE(DE_U_ASINH, m::asinh(x))
-        U_CASE(DE_U_ACOSH, m::acosh(x))
-        U_CASE(DE_U_ATANH, m::atanh(x))
-        U_CASE(DE_U_SAFE_LOG, x <= T(0) ? m::nan() : m::log(x))
-        U_CASE(DE_U_SAFE_LOG2, x <= T(0) ? m::nan() : m::log2(x))
-        U_CASE(DE_U_SAFE_LOG10, x <= T(0) ? m::nan() : m::log10(x))
-        U_CASE(DE_U_SAFE_LOG1P, x <= T(-1) ? m::nan() : m::log1p(x))
-        U_CASE(DE_U_SAFE_SQRT, x < T(0) ? m::nan() : m::sqrt(x))
-        U_CASE(DE_U_SAFE_ACOSH, x < T(1) ? m::nan() : m::acosh(x))
-    case DE_U_COS2:
-        FOR_G FOR_I {
-            const T c = m::cos(b[g][i]);
-            acc[g][i] = c * c;
-        }
-        break;
-        U_CASE(DE_U_GAMMA, m::tgamma(x))
-        B_CASE(DE_B_ADD, x + y)
-        B_CASE(DE_B_SUB, x - y)
-        B_CASE(DOP_RSUB, y - x)
-        B_CASE(DE_B_MUL, x * y)
-        B_CASE(DE_B_DIV, x / y)
-        B_CASE(DOP_RDIV, y / x)
-        B_CASE(DE_B_POW, m::pow(x, y))
-        B_CASE(DOP_RPOW, m::pow(y, x))
-        B_CASE(DE_B_MAX, jl_max(x, y))
-        B_CASE(DE_B_MIN, jl_min(x, y))
-        B_CASE(DE_B_MOD, jl_mod(x, y))
-        B_CASE(DOP_RMOD, jl_mod(y, x))
-        B_CASE(DE_B_REM, m::fmod(x, y))
-        B_CASE(DOP_RREM, m::fmod(y, x))
-        B_CASE(DE_B_GREATER, x > y ? T(1) : T(0))
-        B_CASE(DOP_RGREATER, y > x ? T(1) : T(0))
-        B_CASE(DE_B_POW_ABS2, jl_pow_abs2(x, y))
-        B_CASE(DOP_RPOW_ABS2, jl_pow_abs2(y, x))
-    default: break;
-    }
-    return accv;
-}
-
-// acc = op3(b, c, acc): b, c from spill slots, acc = third argument
-template <typename T, int G>
-__device__ __noinline__ VG<T, G> cold_op3(uint32_t op, VG<T, G> accv, VG<T, G> bv, VG<T, G> cv) {
-    using m = M<T>;
-    typedef typename VecOf<T>::type V;
-    constexpr int VW = VecOf<T>::W;
-    V (&acc)[G] = accv.v;
-    const V (&b)[G] = bv.v;
-    const V (&c)[G] = cv.v;
-    FOR_G FOR_I {
-        const T x = b[g][i], y = c[g][i], z = acc[g][i];
-        T r;
-        switch (op) {
-        case DE_T_FMA: r = m::fma(x, y, z); break;
-        case DE_T_CLAMP: r = x > z ? z : (x < y ? y : x); break;
-        case DE_T_ADD3: r = (x + y) + z; break;
-        default: r = jl_max(jl_max(x, y), z); break;
-        }
-        acc[g][i] = r;
-    }
-    return accv;
-}
-
-// Validity accumulation without touching the scalar unit: poison = fma(v, 0, poison) stays
-// +0 while every tested value is finite and turns (and stays) NaN at the first Inf/NaN.
-template <typename T, int G, typename V>
-__device__ __forceinline__ void poison_with(T &poison, const V (&v)[G]) {
-    constexpr int VW = VecOf<T>::W;
-    FOR_G FOR_I poison = M<T>::fma(v[g][i], T(0), poison);
-}
-// ... and, in the CERT variant of the flat-switch kernel, the running maximum of |tested value| (NaN is dropped by fmax: the poison has it)
-template <typename T, int G, typename V, bool CERT>
-__device__ __forceinline__ void test_with(T &poison, T &vmax, const V (&v)[G]) {
-    constexpr int VW = VecOf<T>::W;
-    poison_with<T, G, V>(poison, v);
-    if constexpr (CERT) { FOR_G FOR_I vmax = M<T>::abs(v[g][i]) > vmax ? M<T>::abs(v[g][i]) : vmax; }
-}
-
-// cos/sin/exp over the G*VW samples of a thread.  Float32 uses the fast versions of
-// de_device_ops.h with ONE divergent fix-up region for out-of-range arguments.
-template <int G, bool SIN>
-__device__ __noinline__ VG<float, G> trig_fixup(VG<float, G> r, VG<float, G> x) {
-    DE_UNROLL for (int g = 0; g < G; g++) DE_UNROLL for (int i = 0; i < 4; i++)
-        if (fabsf(x.v[g][i]) > DE_TRIG_FAST_BOUND) r.v[g][i] = SIN ? sinf(x.v[g][i]) : cosf(x.v[g][i]);
-    return r;
-}
-template <int G, bool SIN>
-__device__ __noinline__ VG<double, G> trig_f64(VG<double, G> x) {
-    DE_UNROLL for (int g = 0; g < G; g++) DE_UNROLL for (int i = 0; i < 2; i++)
-        x.v[g][i] = SIN ? ::sin(x.v[g][i]) : ::cos(x.v[g][i]);
-    return x;
-}
-template <typename T, int G, typename V, bool SIN>
-__device__ __forceinline__ void vec_trig(V (&out)[G], const V (&x)[G]) {
-    constexpr int VW = VecOf<T>::W;
-    if constexpr (sizeof(T) == 4) {
-        bool big = false;
-        VG<float, G> r, xv;
-        FOR_G FOR_I {
-            r.v[g][i] = fast_trig_f32<SIN>(x[g][i]);
-            big |= M<T>::abs(x[g][i]) > DE_TRIG_FAST_BOUND;
-        }
-        if (__ballot(big) != 0ull) { // wave-uniform: keeps the interpreter loop free of divergent branches
-            FOR_G xv.v[g] = x[g];
-            r = trig_fixup<G, SIN>(r, xv);
-        }
-        FOR_G out[g] = r.v[g];
-    } else {
-        VG<double, G> xv;
-        FOR_G xv.v[g] = x[g];
-        xv = trig_f64<G, SIN>(xv);
-        FOR_G out[g] = xv.v[g];
-    }
-}
-template <typename T, int G, typename V>
-__device__ __forceinline__ void vec_exp(V (&out)[G], const V (&x)[G]) {
-    constexpr int VW = VecOf<T>::W;
-    V r[G];
-    if constexpr (sizeof(T) == 4) { FOR_G FOR_I r[g][i] = fast_exp_f32(x[g][i]); }
-    else { FOR_G FOR_I r[g][i] = M<T>::exp(x[g][i]); } // OCML exp (f64) is branch-free
-    FOR_G out[g] = r[g];
-}
-
-#define COLD_CALL(BV)                                          \
-    {                                                          \
-        VG<T, G> av_, bv_;                                     \
-        FOR_G { av_.v[g] = acc[g]; bv_.v[g] = BV[g]; }         \
-        av_ = cold_op<T, G>(op, av_, bv_);                     \
-        FOR_G acc[g] = av_.v[g];                               \
-    }
-
-// XCD-aware block mapping: hardware dispatches block b to XCD b % 8 (observed, used
-// for L2 affinity only — correctness never depends on it).  All chunks of a sample
-// tile get block ids with the same residue, i.e. run on one XCD back to back.
-struct TileMap {
-    int64_t tile;
-    int32_t chunk;
-    bool valid;
-};
-__device__ __forceinline__ TileMap map_block(uint32_t bid, int32_t n_chunks, int64_t n_tiles) {
-    TileMap m;
-    if (n_tiles < 64) {
-        // few sample tiles (the many-trees x few-rows shape): X fits in every L2 anyway, and the XCD-aware
-        // order below would put all work of tile t on XCD t mod 8 (one eighth of the chip for a single tile)
-        m.tile = (int64_t)(bid % (uint32_t)n_tiles);
-        m.chunk = (int32_t)(bid / (uint32_t)n_tiles);
-        m.valid = m.chunk < n_chunks;
-        return m;
-    }
-    const uint32_t xcd = bid & 7u, idx = bid >> 3;
-    m.chunk = (int32_t)(idx % (uint32_t)n_chunks);
-    m.tile = (int64_t)(idx / (uint32_t)n_chunks) * 8 + xcd;
-    m.valid = m.tile < n_tiles;
-    return m;
-}
 
 // The same map with the CHUNK slower than a group of `grp` sample tiles (per XCD): the workgroups resident on a CU at one time then walk
 // ONE record stream (~10 KB for 64 trees) instead of all of them (n_chunks x 10 KB against a 16 KB scalar cache), and a group's X tiles
@@ -374,209 +123,10 @@ __device__ __forceinline__ void stage_param_rows(const KArgs<T> &a, T *__restric
         for (int p = 0; p < a.n_prows; p++) rows[(size_t)(a.prow_base + p) * row_elems + j] = col[p];
     }
 }
-template <typename T, int G>
-__device__ __noinline__ void store_ragged(T *o, VG<T, G> v, int64_t remaining, int plane) {
-    constexpr int VW = VecOf<T>::W;
-    FOR_G FOR_I if ((int64_t)g * plane + i < remaining) o[g * plane + i] = v.v[g][i];
-}
-__device__ __noinline__ void flag_incomplete(uint8_t *ok, int agent) { // agent scope: workgroups that start later skip the tree (early exit)
-    if ((threadIdx.x & 63) == 0) {
-        if (agent) __hip_atomic_store(ok, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *ok = 0;
-    }
-}
-
-// DIRECT = true: wide feature matrices whose X tile does not fit in LDS — feature operands are
-// gathered from global memory (L1/L2 absorb the re-reads), LDS holds only the spill rows.
-template <typename T, int G, int BLK, bool EE, bool PARAMS, bool DIRECT = false, bool CERT = false>
-__global__ void __launch_bounds__(BLK) de_eval_tape_kernel(const KArgs<T> a) {
-    typedef typename VecOf<T>::type V;
-    constexpr int VW = VecOf<T>::W;
-    constexpr int GT = BLK * VW;        // samples per group plane
-    constexpr int TILE = GT * G;        // samples per workgroup
-    constexpr int ROWV = BLK * G + 1;   // LDS row stride in vectors (+1: bank spread for the staging writes)
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    T *__restrict__ rows = reinterpret_cast<T *>(smem_raw);  // rows 0..F-1: X tile; row F+s: spill slot s
-    V *__restrict__ rowsv = reinterpret_cast<V *>(smem_raw);
-
-    const TileMap tm = map_block(blockIdx.x, a.n_chunks, a.n_tiles);
-    if (!tm.valid) return;
-    const int tid = threadIdx.x;
-    const int64_t base = tm.tile * TILE;
-    const int64_t last = a.N - 1;
-
-    // ---- stage the X tile: coalesced HBM/L2 read, transposed LDS write ----------
-    // sample j of the tile lives at rows[f*ROWV*VW + j]  (plane g = j / GT, lane = (j % GT) / VW)
-    if (!DIRECT) {
-        const uint32_t F = (uint32_t)a.F;
-        const uint32_t total = (uint32_t)TILE * F;
-        if (a.ldX == (int64_t)F && base + TILE <= a.N) {
-            const T *__restrict__ src = a.X + base * (int64_t)F; // contiguous TILE*F elements
-            for (uint32_t e = tid; e < total; e += BLK) {
-                const uint32_t j = e / F, f = e - j * F;
-                rows[f * (ROWV * VW) + j] = src[e];
-            }
-        } else { // ragged tail / strided X: clamp to the last real sample
-            for (uint32_t e = tid; e < total; e += BLK) {
-                const uint32_t j = e / F, f = e - j * F;
-                int64_t jj = base + j;
-                jj = jj < last ? jj : last;
-                rows[f * (ROWV * VW) + j] = a.X[f + a.ldX * jj];
-            }
-        }
-    }
-    if (PARAMS && !DIRECT && a.n_prows > 0) stage_param_rows<T>(a, rows, ROWV * VW, base, TILE, tid, BLK);
-    int64_t cls[G][VW];
-    if (PARAMS) {
-        FOR_G FOR_I {
-            int64_t jj = base + g * GT + tid * VW + i;
-            jj = jj < last ? jj : last;
-            cls[g][i] = clamp_class((a.classes_is_i64 ? reinterpret_cast<const int64_t *>(a.classes)[jj]
-                                                      : (int64_t) reinterpret_cast<const int32_t *>(a.classes)[jj]) -
-                                        a.class_base, a.n_classes);
-        }
-    }
-    __syncthreads();
-
-    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)a.code;
-    const ConstI32Ptr code_off = (ConstI32Ptr)(uintptr_t)a.code_off;
-    const int t0 = tm.chunk * a.trees_per_chunk;
-    const int t1 = (t0 + a.trees_per_chunk < a.n_trees) ? t0 + a.trees_per_chunk : a.n_trees;
-    const bool full = base + TILE <= a.N;
-    uint64_t skip = 0ull; // trees of the chunk already known to be incomplete (see de_eval_threaded_kernel): not evaluated
-    if (EE && a.skip_flagged && t1 - t0 <= 64) {
-        const int i = t0 + (tid & 63);
-        const uint8_t f = i >= t1 ? (uint8_t)1 : skip_flag_load(a.ok + i, a.skip_flagged, tm.tile);
-        skip = __ballot(f == 0);
-    }
-
-    int pe = code_off[t0];
-    for (int tree = t0; tree < t1; ++tree) {
-        int pc = pe;
-        pe = code_off[tree + 1];
-        if ((skip >> (tree - t0)) & 1ull) continue;
-        V acc[G];
-        FOR_G FOR_I acc[g][i] = T(0);
-        T poison = T(0);
-        T vmax = T(0); // (CERT) largest |tested value| of this thread's samples
-        U32x4 nxt = code[pc]; // scalar load; a tree has at least one instruction
-        for (; pc < pe; ++pc) {
-            const U32x4 w = nxt;
-            nxt = code[pc + 1]; // prefetch (the code buffer carries one trailing pad instruction)
-            // One flat, wave-uniform switch over the bound handler id (de_bind.h): every case is
-            // straight-line code.  ROW(r) = this thread's vectors of LDS row r.
-#define ROWP(r) (rowsv + ((r) - (DIRECT ? (uint32_t)a.F : 0u)) * ROWV + tid)
-#define LOAD_ROW(dst, r)                                                                              \
-    {                                                                                                 \
-        if (DIRECT && (r) < (uint32_t)a.F) {                                                          \
-            FOR_G FOR_I {                                                                             \
-                int64_t jj_ = base + g * GT + tid * VW + i;                                           \
-                jj_ = jj_ < last ? jj_ : last;                                                        \
-                dst[g][i] = a.X[(r) + a.ldX * jj_];                                                   \
-            }                                                                                         \
-        } else {                                                                                      \
-            const V *__restrict__ s_ = ROWP(r);                                                       \
-            FOR_G dst[g] = s_[g * BLK];                                                               \
-        }                                                                                             \
-    }
-#define BIN4(K, EXPR)                                                                                   \
-    case BOP_BIN_BASE + 4 * K + 0: { V b[G]; LOAD_ROW(b, w.y) FOR_G FOR_I { const T x = acc[g][i], y = b[g][i]; acc[g][i] = (EXPR); } } break; \
-    case BOP_BIN_BASE + 4 * K + 1: { V b[G]; LOAD_ROW(b, w.y) FOR_G FOR_I { const T x = acc[g][i], y = b[g][i]; acc[g][i] = (EXPR); } test_with<T, G, V, CERT>(poison, vmax, acc); } break; \
-    case BOP_BIN_BASE + 4 * K + 2: { const T y = imm_of<T>(w.z, w.w); FOR_G FOR_I { const T x = acc[g][i]; acc[g][i] = (EXPR); } } break; \
-    case BOP_BIN_BASE + 4 * K + 3: { const T y = imm_of<T>(w.z, w.w); FOR_G FOR_I { const T x = acc[g][i]; acc[g][i] = (EXPR); } test_with<T, G, V, CERT>(poison, vmax, acc); } break;
-#define UN4(K, CALL)                                                                                    \
-    case BOP_UN_BASE + 4 * K + 0: { V x_[G]; FOR_G x_[g] = acc[g]; CALL; } break;                      \
-    case BOP_UN_BASE + 4 * K + 1: { V x_[G]; FOR_G x_[g] = acc[g]; CALL; test_with<T, G, V, CERT>(poison, vmax, acc); } break; \
-    case BOP_UN_BASE + 4 * K + 2: { V x_[G]; LOAD_ROW(x_, w.y) CALL; } break;                          \
-    case BOP_UN_BASE + 4 * K + 3: { V x_[G]; LOAD_ROW(x_, w.y) CALL; test_with<T, G, V, CERT>(poison, vmax, acc); } break;
-            switch (w.x) {
-            case BOP_LOAD_ROW: LOAD_ROW(acc, w.y) break;
-            case BOP_LOAD_CONST: { const T c = imm_of<T>(w.z, w.w); FOR_G FOR_I acc[g][i] = c; } break;
-            case BOP_PUSH: { V *__restrict__ s_ = ROWP(w.y); FOR_G s_[g * BLK] = acc[g]; } break;
-            case BOP_CHECK_ROW: { V b[G]; LOAD_ROW(b, w.y) test_with<T, G, V, CERT>(poison, vmax, b); } break;
-            case BOP_CHECK_ACC: test_with<T, G, V, CERT>(poison, vmax, acc); break;
-            BIN4(0, x + y)
-            BIN4(1, x - y)
-            BIN4(2, y - x)
-            BIN4(3, x * y)
-            BIN4(4, x / y)
-            BIN4(5, y / x)
-            UN4(0, (vec_trig<T, G, V, false>(acc, x_)))
-            UN4(1, (vec_exp<T, G, V>(acc, x_)))
-            UN4(2, (vec_trig<T, G, V, true>(acc, x_)))
-            case BOP_GEN_ROW: { const uint32_t op = w.y >> 24; V b[G]; LOAD_ROW(b, w.y & 0xFFFFFFu) COLD_CALL(b) } break;
-            case BOP_GEN_CONST: { const uint32_t op = w.y >> 24; V b[G]; const T c = imm_of<T>(w.z, w.w); FOR_G FOR_I b[g][i] = c; COLD_CALL(b) } break;
-            case BOP_GEN_ACC: { const uint32_t op = w.y >> 24; COLD_CALL(acc) } break;
-            case BOP_TERN: {
-                const uint32_t op = w.y >> 24;
-                VG<T, G> av, bv, cv;
-                const V *__restrict__ s1 = ROWP(w.y & 0xFFFFFFu);
-                const V *__restrict__ s2 = ROWP(w.z);
-                FOR_G { av.v[g] = acc[g]; bv.v[g] = s1[g * BLK]; cv.v[g] = s2[g * BLK]; }
-                av = cold_op3<T, G>(op, av, bv, cv);
-                FOR_G acc[g] = av.v[g];
-            } break;
-            case BOP_INJ_ACC: { // is_valid(x_l) ? op(x_l) : Inf   (src/Evaluate.jl:722,787)
-                const uint32_t op = w.y >> 24;
-                V inj[G];
-                FOR_G inj[g] = acc[g];
-                COLD_CALL(inj)
-                FOR_G FOR_I acc[g][i] = M<T>::isfinite(inj[g][i]) ? acc[g][i] : M<T>::inf();
-            } break;
-            case BOP_INJ_ROW: {
-                const uint32_t op = w.y >> 24;
-                V inj[G];
-                LOAD_ROW(inj, w.y & 0xFFFFFFu)
-                COLD_CALL(inj)
-                FOR_G FOR_I acc[g][i] = M<T>::isfinite(inj[g][i]) ? acc[g][i] : M<T>::inf();
-            } break;
-            case BOP_GEN_PARAM:
-                if constexpr (PARAMS) {
-                    const uint32_t op = w.y >> 24;
-                    V b[G];
-                    const T *__restrict__ s_ = a.params + (w.y & 0xFFFFu);
-                    FOR_G FOR_I b[g][i] = s_[a.ld_params * cls[g][i]];
-                    if (EE && (w.y & (1u << 23))) test_with<T, G, V, CERT>(poison, vmax, b);
-                    if (op == DOP_LOAD) { FOR_G acc[g] = b[g]; }
-                    else COLD_CALL(b)
-                }
-                break;
-            default: break;
-            }
-        }
-        // ---- store out[tree][...]: one 16-byte store per group, coalesced over the wave
-        if constexpr (CERT) {
-            // the largest |tested value| of the tree so far: wave maximum, one atomicMax per wave on the value's bits (non-negative
-            // floats order like unsigned integers); samples past N repeat the last real one, so they add nothing
-            typedef typename std::conditional<sizeof(T) == 4, unsigned int, unsigned long long>::type UB;
-            DE_UNROLL for (int m = 32; m >= 1; m >>= 1) {
-                const T o2 = __shfl_xor(vmax, m, 64);
-                vmax = o2 > vmax ? o2 : vmax;
-            }
-            if ((tid & 63) == 0 && vmax > T(0)) {
-                UB bits;
-                __builtin_memcpy(&bits, &vmax, sizeof bits);
-                atomicMax(reinterpret_cast<UB *>(a.cert_max) + tree, bits);
-            }
-            if (__ballot(poison != poison) != 0ull) flag_incomplete(a.ok + tree, a.skip_flagged == 1);
-            continue;
-        }
-        T *__restrict__ o = a.out + (int64_t)tree * a.ld_out + base + tid * VW;
-        if (full && a.vec_store) {
-            FOR_G *reinterpret_cast<V *>(o + g * GT) = acc[g];
-        } else {
-            VG<T, G> av;
-            FOR_G av.v[g] = acc[g];
-            store_ragged<T, G>(o, av, a.N - (base + tid * VW), GT);
-        }
-        // ---- completion flag: one ballot per wave, one byte store per failing wave
-        if (__ballot(poison != poison) != 0ull) flag_incomplete(a.ok + tree, a.skip_flagged == 1);
-    }
-}
 
 // ===========================================================================
 // Threaded-code variant: every bound handler is its own function and the interpreter loop is
-// {prefetch, handler address = base + offset, s_swappc}.  The flat switch above costs ~37
+// {prefetch, handler address = base + offset, s_swappc}.  The flat switch (de_flat.h) costs ~37
 // scalar+branch instructions per interpreted instruction (LLVM lowers a switch to a compare
 // tree and then structurizes it); an indirect call costs ~20, and each handler is compiled
 // as clean straight-line code.  Handler addresses are taken on the device
@@ -2079,146 +1629,15 @@ __global__ void __launch_bounds__(256) de_loss_finish_kernel(const double *__res
 }
 
 // ---------------------------------------------------------------------------
-static int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// Kernel geometry: G groups of 16-byte vectors per thread, BLK threads per workgroup.
-// Defaults chosen on MI355X; DE_EVAL_G / DE_EVAL_BLOCK override
-// them for experiments.
-static void eval_geometry(int dtype, int *G, int *BLK) {
-    *G = env_int("DE_EVAL_G", 1);
-    *BLK = env_int("DE_EVAL_BLOCK", 256);
-    if (*G != 1 && *G != 2) *G = 1;
-    if (*BLK != 128 && *BLK != 256) *BLK = 256;
-    if (dtype != DE_F32) { *G = 1; *BLK = 256; }
-}
-
-size_t eval_lds_bytes(int dtype, int F, int n_slots, int *K_out) {
-    int G, BLK;
-    eval_geometry(dtype, &G, &BLK);
-    const size_t rowv = (size_t)BLK * G + 1;
-    const size_t bytes = (size_t)(F + n_slots) * rowv * 16;
-    if (K_out) *K_out = (dtype == DE_F32 ? 4 : 2) * G;
-    return bytes <= 160 * 1024 ? bytes : 0;
-}
-
-static void eval_geometry(int dtype, int *G, int *BLK);
-bool eval_uses_threaded();
-static int g_cu_count = 0;
-
-static int cu_count() {
-    if (g_cu_count == 0) {
-        const int forced = env_int("DE_CU_COUNT", 0); // experiments: < 0 disables the small-grid re-split
-        if (forced != 0) { g_cu_count = forced; return forced < 0 ? 0 : forced; }
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_cu_count = prop.multiProcessorCount;
-        if (g_cu_count <= 0) g_cu_count = 256; // MI355X
-    }
-    return g_cu_count < 0 ? 0 : g_cu_count;
-}
-
-// Tree chunking: chunks of ~64 trees keep workgroups short (fine-grained tail) while the
-// X-tile staging (one L2 read of the tile per chunk) stays a few percent of the work; with few
-// sample tiles, split further so the grid still covers the chip several times.
-// (`waves` > 1: the chunks of a wave group — one per wave, 1 / waves of the trees each: a workgroup keeps the trees, and the record
-// footprint, of a one-wave workgroup)
-static int32_t plan_tpc_max(int waves) {
-    const int64_t tpc_env = env_int("DE_EVAL_TPC", 63); // trees per chunk (experiments: X staging per tree against the tail of a short launch)
-    const int64_t t = (tpc_env < 1 ? 63 : (tpc_env > 63 && waves > 1 ? 63 : tpc_env)) / (waves > 1 ? waves : 1);
-    return (int32_t)(t < 1 ? 1 : t);
-}
-static void plan_chunks(int64_t n_trees, int64_t n_tiles, int32_t *n_chunks_out, int32_t *tpc_out, int32_t *nc0_out = nullptr, int waves = 1) {
-    chunk_plan(n_trees, n_tiles, plan_tpc_max(waves), (int64_t)cu_count() * 4 * 8, n_chunks_out, tpc_out, nc0_out);
-    if (*n_chunks_out < 1) *n_chunks_out = 1;
-}
-
-void eval_plan(int dtype, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk, int waves) {
-    int G, BLK;
-    eval_geometry(dtype, &G, &BLK);
-    if (eval_uses_threaded()) { G = tg_planes(dtype); BLK = TBLK; }
-    *tile = BLK * G * (dtype == DE_F32 ? 4 : 2);
-    plan_chunks(n_trees, (N + *tile - 1) / *tile, n_chunks, trees_per_chunk, nullptr, eval_uses_threaded() ? waves : 1);
-    if (eval_uses_threaded() && waves > 1) { // a wave group: the workgroups per sample tile, and the trees of one (they share its staged X tile)
+// (io: DE_F32 / DE_F64 run the threaded kernel unless DE_EVAL_THREADED=0; everything else is the flat-switch interpreter, de_flat.h launch_flat)
+void eval_plan(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chunks, int32_t *trees_per_chunk, int waves) {
+    const bool threaded = (io == DE_F32 || io == DE_F64) && eval_uses_threaded();
+    *tile = threaded ? ttile_samples(io) : flat_tile_samples(io);
+    plan_chunks(n_trees, (N + *tile - 1) / *tile, n_chunks, trees_per_chunk, nullptr, threaded ? waves : 1);
+    if (threaded && waves > 1) { // a wave group: the workgroups per sample tile, and the trees of one (they share its staged X tile)
         *n_chunks = (*n_chunks + waves - 1) / waves;
         *trees_per_chunk *= waves;
     }
-}
-
-template <typename T, int G, int BLK>
-static hipError_t launch_eval_t(const EvalArgs &e, hipStream_t stream, const char **kname) {
-    constexpr int VW = VecOf<T>::W;
-    constexpr int TILE = BLK * VW * G;
-    KArgs<T> a;
-    a.code = e.code;
-    a.code_off = e.code_off;
-    a.X = static_cast<const T *>(e.X);
-    a.out = static_cast<T *>(e.out);
-    a.ok = e.ok;
-    a.params = static_cast<const T *>(e.params);
-    a.classes = e.classes;
-    a.N = e.N;
-    a.ldX = e.ldX;
-    a.ld_out = e.ld_out;
-    a.ld_params = e.ld_params;
-    a.prow_base = e.prow_base;
-    a.n_prows = e.n_prows;
-    a.n_tiles = (e.N + TILE - 1) / TILE;
-    a.F = e.F;
-    a.n_trees = e.n_trees;
-    a.n_slots = e.n_slots;
-    a.xstride = 0;
-    a.classes_is_i64 = e.classes_is_i64;
-    a.class_base = e.class_base;
-    a.n_classes = e.n_classes > 0 ? e.n_classes : 1;
-    a.vec_store = (reinterpret_cast<uintptr_t>(e.out) % 16 == 0 && (e.ld_out * sizeof(T)) % 16 == 0) ? 1 : 0;
-
-    int32_t tpc, nch;
-    plan_chunks(e.n_trees, a.n_tiles, &nch, &tpc);
-    a.trees_per_chunk = tpc;
-    a.n_chunks = nch;
-    a.skip_flagged = (e.early_exit && e.skip_flagged && tpc <= 64) ? 2 : 0; // (2: the flag protocol of launch_threaded_t)
-    a.x_vec = 0;
-    a.f_magic = 0;
-
-    const int64_t tile_groups = (a.n_tiles + 7) / 8;
-    const int64_t blocks = tile_groups * 8 * a.n_chunks;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    void (*kern)(const KArgs<T>);
-    if (e.early_exit) kern = e.uses_params ? de_eval_tape_kernel<T, G, BLK, true, true> : de_eval_tape_kernel<T, G, BLK, true, false>;
-    else kern = e.uses_params ? de_eval_tape_kernel<T, G, BLK, false, true> : de_eval_tape_kernel<T, G, BLK, false, false>;
-    a.cert_max = e.cert_max;
-    if constexpr (G == 1 && BLK == 256) {
-        if (e.cert_max) { // the certificate pass (de_eval_sum_certificate): early-exit flag semantics, no output
-            if (!e.early_exit || e.direct) return hipErrorInvalidValue;
-            kern = e.uses_params ? de_eval_tape_kernel<T, 1, 256, true, true, false, true> : de_eval_tape_kernel<T, 1, 256, true, false, false, true>;
-        }
-    } else if (e.cert_max) return hipErrorInvalidValue;
-    if (kname) *kname = e.cert_max ? "de_eval_tape_kernel<cert>" : "de_eval_tape_kernel";
-    size_t lds = (size_t)(a.F + a.n_slots) * ((size_t)BLK * G + 1) * 16;
-    if constexpr (G == 1 && BLK == 256) {
-        if (e.direct) {
-            kern = e.early_exit ? (e.uses_params ? de_eval_tape_kernel<T, 1, 256, true, true, true> : de_eval_tape_kernel<T, 1, 256, true, false, true>)
-                                : (e.uses_params ? de_eval_tape_kernel<T, 1, 256, false, true, true> : de_eval_tape_kernel<T, 1, 256, false, false, true>);
-            lds = (size_t)(a.n_slots > 0 ? a.n_slots : 1) * 257 * 16;
-            if (kname) *kname = "de_eval_tape_kernel<direct>";
-        }
-    }
-    if (lds > 64 * 1024) {
-        hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (st != hipSuccess) return st;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BLK), lds, stream, a);
-    return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t launch_eval_geo(const EvalArgs &a, hipStream_t stream, const char **kn, int G, int BLK) {
-    if (G == 2) return BLK == 128 ? launch_eval_t<T, 2, 128>(a, stream, kn) : launch_eval_t<T, 2, 256>(a, stream, kn);
-    return BLK == 128 ? launch_eval_t<T, 1, 128>(a, stream, kn) : launch_eval_t<T, 1, 256>(a, stream, kn);
 }
 
 // ---- threaded variant: handler table + launch ---------------------------------------------
@@ -2264,7 +1683,7 @@ hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table) {
     return hipSuccess;
 }
 
-bool eval_uses_threaded() { return env_int("DE_EVAL_THREADED", 1) != 0 && env_int("DE_EVAL_G", 1) == 1 && env_int("DE_EVAL_BLOCK", 256) == 256; }
+bool eval_uses_threaded() { return env_int("DE_EVAL_THREADED", 1) != 0; }
 
 // The same statistics for PACKED, 16-byte aligned Float32 X (ldX == F): a thread takes groups of four consecutive samples = F 16-byte
 // vectors (4 F consecutive floats), so the pass issues a quarter of the load instructions of the scalar loop — which reads X at 1.8 TB/s
@@ -2699,17 +2118,8 @@ hipError_t launch_dist_unpack(uint8_t *ok_global_dev, const uint8_t *recv, int64
 }
 
 hipError_t launch_eval(int dtype, const EvalArgs &a, hipStream_t stream, const char **kernel_name) {
-    if (a.ok_init && !(a.threaded && !a.cert_max && !a.direct)) { // (the threaded launch sets the flags itself: fused into its pre-pass when that runs)
-        const hipError_t cs = hipMemcpyAsync(a.ok, a.ok_init, (size_t)a.n_trees, hipMemcpyDeviceToDevice, stream);
-        if (cs != hipSuccess) return cs;
-    }
-    if (a.cert_max && !a.direct) return dtype == DE_F32 ? launch_eval_t<float, 1, 256>(a, stream, kernel_name) : launch_eval_t<double, 1, 256>(a, stream, kernel_name);
-    if (a.direct) return dtype == DE_F32 ? launch_eval_t<float, 1, 256>(a, stream, kernel_name) : launch_eval_t<double, 1, 256>(a, stream, kernel_name);
-    if (a.threaded) return dtype == DE_F32 ? launch_threaded_t<float>(a, stream, kernel_name) : launch_threaded_t<double>(a, stream, kernel_name);
-    int G, BLK;
-    eval_geometry(dtype, &G, &BLK);
-    if (dtype == DE_F32) return launch_eval_geo<float>(a, stream, kernel_name, G, BLK);
-    return launch_eval_t<double, 1, 256>(a, stream, kernel_name);
+    if (a.cert_max || a.direct || !a.threaded) return launch_eval_flat(dtype, a, stream, kernel_name);
+    return dtype == DE_F32 ? launch_threaded_t<float>(a, stream, kernel_name) : launch_threaded_t<double>(a, stream, kernel_name);
 }
 
 } // namespace de

@@ -1,7 +1,7 @@
 """Complex (DE_CF32 / DE_CF64) evaluation against the real kernels on one MI355X: 1000 random 20-node trees of
 + - * / cos exp x 10^6 and 10^7 samples, each with DE_OPT_FULL_EVAL (equal work in every leg) and with the early exit, and the one-tree call
 (de_eval_tree_array, one 20-node tree x 10^6 samples, device pointers) — each in ComplexF32, ComplexF64, Float32 / Float64 (the threaded
-kernel, the default) and Float32 / Float64 with DE_EVAL_THREADED=0 (the flat-switch kernel: the one de_complex.hip is built like).  The
+kernel, the default) and Float32 / Float64 with DE_EVAL_THREADED=0 (the flat-switch interpreter of csrc/de_flat.h with its real policy; complex data is another policy of it).  The
 complex legs evaluate the same trees (real constants, imaginary part 0) on X with random real and imaginary parts.  Every leg runs in a
 fresh child process.  Device time of the eval kernels (hipEvents, de_ctx_last_kernel_ms), median of the timed steps; bytes/s = (X + output)
 bytes / time.  One JSON line per leg, then a table.

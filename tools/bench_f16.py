@@ -1,7 +1,7 @@
 """DE_F16 (Float16) evaluation against Float32 on one MI355X: the headline population (1000 random 20-node trees x 10^7
 samples) and C2 (1000 trees x 10^6), each with DE_OPT_FULL_EVAL (equal work in every leg) and with the early exit, and the one-tree call (de_eval_tree_array, one 20-node tree x 10^6 samples, device pointers) — each in
-Float16, in Float32 (the threaded kernel, the default) and in Float32 with DE_EVAL_THREADED=0 (the flat-switch kernel: the one de_half.hip
-is built like).  Every leg runs in a fresh child process (the kernel choice is read once per process).  Device time of the eval kernels
+Float16, in Float32 (the threaded kernel, the default) and in Float32 with DE_EVAL_THREADED=0 (the flat-switch interpreter of csrc/de_flat.h
+with its Float32 policy; DE_F16 runs the same interpreter with the binary16 policy).  Every leg runs in a fresh child process (the kernel choice is read once per process).  Device time of the eval kernels
 (hipEvents, de_ctx_last_kernel_ms), median of the timed steps; bytes/s = (X + output) bytes / time.  One JSON line per leg, then a table.
     python tools/bench_f16.py [--steps 10] [--warmup 3]"""
 import argparse
