@@ -92,10 +92,12 @@ build_kernels() { # src obj [extra flags...]
 build_kernels de_kernels.hip $OBJ/de_kernels.o &
 # the threaded gradient kernel: one module per (element type, window width), see de_grad_threaded.hip
 GT_OBJS=""
-for spec in f:float:1:1 f:float:2:1 f:float:3:1 f:float:4:1 f:float:5:1 f:float:6:1 f:float:8:1 \
-            f:float:1:2 f:float:2:2 f:float:3:2 f:float:4:2 f:float:5:2 f:float:6:2 \
-            d:double:1:1 d:double:2:1 d:double:3:1 d:double:4:1 d:double:5:1; do  # = DE_GT_ALL in de_grad_kernels.hip
-  IFS=: read tag ty gc vs <<< "$spec"
+# the modules are the X(tag, window, samples per lane) entries of DE_GT_ALL in de_grad_kernels.hip: the one list
+GT_SPECS=$(grep -o 'X([fd], [0-9]*, [0-9]*)' de_grad_kernels.hip | sed -E 's/X\(([fd]), ([0-9]+), ([0-9]+)\)/\1:\2:\3/' || true)
+[ -n "$GT_SPECS" ] || { echo "build.sh: no module list (DE_GT_ALL) found in de_grad_kernels.hip" >&2; exit 1; }
+for spec in $GT_SPECS; do
+  IFS=: read tag gc vs <<< "$spec"
+  if [ $tag = f ]; then ty=float; else ty=double; fi
   GT_OBJS="$GT_OBJS $OBJ/de_gt_$tag${gc}v$vs.o"
   while [ "$(jobs -r | wc -l)" -ge "${DE_BUILD_JOBS:-8}" ]; do sleep 0.2; done
   build_kernels de_grad_threaded.hip $OBJ/de_gt_$tag${gc}v$vs.o -DDE_GT_T=$ty -DDE_GT_TAG=$tag -DDE_GT_GC=$gc -DDE_GT_VS=$vs &

@@ -2,6 +2,15 @@
 // generic gradient program, its direct-threaded and reverse-accumulation forms, launch planning of the bucketed gradient kernels.
 #include "de_api_internal.h"
 
+// Direct threading (de_grad_threaded.hip, de_rev_threaded.hip): the handler word of a record names the handler of the record BEHIND it, the
+// last record of the chain [a0, b0) — a tree, or one sweep of it — names the chain's first handler.
+static void successor_words(std::vector<BoundInstr> &code, int32_t a0, int32_t b0) {
+    if (b0 - a0 < 2) return;
+    const uint32_t first = code[(size_t)a0].bop;
+    for (int32_t i = a0; i < b0 - 1; i++) code[(size_t)i].bop = code[(size_t)i + 1].bop;
+    code[(size_t)b0 - 1].bop = first;
+}
+
 extern "C" {
 static int ensure_generic_code(de_ctx *c, de_program *p) {
     if (p->gcode_stale || !p->d_gcode) {
@@ -331,14 +340,9 @@ static int ensure_grad_threaded(de_ctx *c, de_program *p, int mode, const std::v
             if (copied != p->gtcode.size()) { p->gtsite_of_gb.clear(); p->site_gen++; return fail(c, DE_ERR_HIP, "gradient program: the host threads' partitions disagree"); }
         }
         dbg_lap("grad threaded: concatenate + sites");
-        // the handler word of a record names the handler of the record BEHIND it, the end record names the tree's first handler
-        // (de_grad_threaded.hip: a handler knows its successor at entry and jumps without waiting for the record it loads)
+        // (a handler knows its successor at entry and jumps without waiting for the record it loads)
         parallel_for_trees(p->n_trees, [&](int64_t t) {
-            const int32_t a0 = p->gtcode_off[(size_t)t], b0 = p->gtcode_off[(size_t)t + 1];
-            if (b0 - a0 < 2) return;
-            const uint32_t first = p->gtcode[(size_t)a0].bop;
-            for (int32_t i = a0; i < b0 - 1; i++) p->gtcode[(size_t)i].bop = p->gtcode[(size_t)i + 1].bop;
-            p->gtcode[(size_t)b0 - 1].bop = first;
+            successor_words(p->gtcode, p->gtcode_off[(size_t)t], p->gtcode_off[(size_t)t + 1]);
         });
         dbg_lap("grad threaded: successor words");
         p->gt_share = false;
@@ -845,17 +849,9 @@ static int ensure_rev_threaded(de_ctx *c, de_program *p, int mode, GradArgs *g) 
             std::sort(ids.begin() + k, ids.begin() + e); // tree order inside a group: adjacent trees share staging batches
             k = e;
         }
-        // the handler word of a record names the handler of the record BEHIND it; the end record of a sweep names the sweep's first
-        // handler (de_rev_threaded.hip: a handler knows its successor at entry)
         for (int64_t t = 0; t < p->n_trees; t++) {
-            const int32_t lim[3] = {p->rtcode_off[(size_t)t], p->rtcode_mid[(size_t)t], p->rtcode_off[(size_t)t + 1]};
-            for (int sw = 0; sw < 2; sw++) {
-                const int32_t a0 = lim[sw], b0 = lim[sw + 1];
-                if (b0 - a0 < 2) continue;
-                const uint32_t first = p->rtcode[(size_t)a0].bop;
-                for (int32_t i = a0; i < b0 - 1; i++) p->rtcode[(size_t)i].bop = p->rtcode[(size_t)i + 1].bop;
-                p->rtcode[(size_t)b0 - 1].bop = first;
-            }
+            successor_words(p->rtcode, p->rtcode_off[(size_t)t], p->rtcode_mid[(size_t)t]);
+            successor_words(p->rtcode, p->rtcode_mid[(size_t)t], p->rtcode_off[(size_t)t + 1]);
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // the previous form may be in use by queued work
         if (p->d_rtcode) { // sizes depend on the mode

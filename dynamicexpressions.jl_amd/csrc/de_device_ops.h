@@ -28,7 +28,7 @@ __device__ __forceinline__ uint8_t skip_flag_load(uint8_t *q, int protocol, int6
     // protocol 3 (experiment): as 2, but the load is non-temporal — the vector L1 does not keep the line, so a CU cannot sit on a stale
     // copy in a kernel that writes little; the XCD's L2 answers
     uint8_t f = protocol == 3 ? __builtin_nontemporal_load(q) : *q;
-    if (((tile >> 3) & 31) == 0) { // (tiles of one XCD are 8 apart: map_block / gmap_block)
+    if (((tile >> 3) & 31) == 0) { // (tiles of one XCD are 8 apart: map_block)
         const uint8_t m = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (m == 0 && f != 0) { *q = 0; f = 0; }
         else if (f == 0 && m != 0) __hip_atomic_store(q, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

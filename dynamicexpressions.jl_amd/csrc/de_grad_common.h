@@ -1,6 +1,8 @@
-// de_grad_common.h — device code shared by the two gradient kernels (de_grad_kernels.hip: flat switch,
-// eval_diff and wide gradients; de_grad_threaded.hip: threaded code): kernel arguments, value+partial
-// functions of every operator (ChainRules scalar rules, same table as oracle/de_oracle_ops.h), tile map.
+// de_grad_common.h — device code shared by the three gradient kernels (de_grad_kernels.hip: flat switch,
+// eval_diff and wide gradients; de_grad_threaded.hip: threaded code; de_rev_threaded.hip: reverse accumulation):
+// kernel arguments, value+partial functions of every operator (ChainRules scalar rules, same table as
+// oracle/de_oracle_ops.h), tile map, tile prologue (X rows, parameter rows), loss term.  What a module of the two
+// threaded kernels exports (GradModule).  The launch itself is host code in de_grad_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,14 +10,10 @@
 
 #include "de_device_ops.h"
 #include "de_kernels.h"
+#include "de_plan.h"
 
 namespace de {
 
-#define DE_CONSTANT __attribute__((address_space(4)))
-typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
-typedef const DE_CONSTANT U32x4 *ConstU4Ptr;
-typedef const DE_CONSTANT int32_t *ConstI32Ptr;
-typedef const DE_CONSTANT int64_t *ConstI64Ptr;
 #define DE_UNROLL _Pragma("unroll")
 
 template <typename T> struct GArgs {
@@ -30,7 +28,8 @@ template <typename T> struct GArgs {
     const T *params;
     const void *classes;
     int64_t N, ldX, ld_out, ld_params, n_tiles, n_classes;
-    int32_t F, P, n_trees, trees_per_chunk, n_chunks, n_slots, mode;
+    int32_t F, P, n_trees, trees_per_chunk, n_chunks, n_slots;
+    int32_t mode; // mode, uses_params and check are read by the flat kernel only (the threaded kernels: template parameter PARAMS, always checked)
     int32_t FX; // threaded kernels: rows of X; F - FX further leaf rows hold the parameters gathered by class (0 elsewhere)
     int32_t classes_is_i64, class_base, uses_params, check;
     int32_t skip_flagged; // early exit at tree granularity: the trees of a chunk whose flag is already 0 are not evaluated (de_kernels.hip)
@@ -44,9 +43,6 @@ template <typename T> struct GArgs {
     const int64_t *col_off;  // n_trees + 1
     const int32_t *tree_ids; // threaded kernel: the n_trees trees this launch evaluates (null = 0..n_trees-1)
     int32_t n_all_trees;     // trees of the program (col_off has n_all_trees + 1 entries)
-    // threaded kernels: a parameter table of <= GPTAB_MAX elements is copied to LDS behind the rows
-    int32_t ptab_elems;      // ld_params * n_classes, or 0: read the table from global memory
-    uint32_t ptab_offset;    // LDS byte offset of the copy
     const int64_t *tile_range; // de_rev_threaded.hip, by-class reduction: (first sample, last sample) of every tile, or null
     const int32_t *rev_mid;  // de_rev_threaded.hip: first backward instruction of every tree
     int32_t rev_rows;        // ... and LDS rows per wave (X + slots + partial rows + staging)
@@ -61,7 +57,6 @@ template <typename T> struct GArgs {
     int64_t var_stride;
 };
 
-constexpr int GPTAB_MAX = 2048;
 // Early exit at tree granularity (src/Evaluate.jl:26-32, src/EvaluateDerivative.jl:230-243: the reference returns at the first
 // non-finite array): bit i = the i-th tree of this workgroup's chunk was already flagged incomplete when the workgroup started —
 // by a workgroup that ran earlier or by the host (non-finite constant).  Its values / Jacobian rows are unspecified then (SURVEY
@@ -226,27 +221,10 @@ template <typename T> __device__ __noinline__ TG<T> ternary_vg(uint32_t op, T x,
     return r;
 }
 
-struct GTileMap { int64_t tile; int32_t chunk; bool valid; bool prio = false; };
-__device__ __forceinline__ GTileMap gmap_block(uint32_t bid, int32_t n_chunks, int64_t n_tiles) {
-    GTileMap m;
-    if (n_tiles < 64) {
-        // few sample tiles (the many-trees x few-rows shape): X fits in every L2 anyway, and the XCD-aware
-        // order below would put all work of tile t on XCD t mod 8 (one eighth of the chip for a single tile)
-        m.tile = (int64_t)(bid % (uint32_t)n_tiles);
-        m.chunk = (int32_t)(bid / (uint32_t)n_tiles);
-        m.valid = m.chunk < n_chunks;
-        return m;
-    }
-    const uint32_t xcd = bid & 7u, idx = bid >> 3;
-    m.chunk = (int32_t)(idx % (uint32_t)n_chunks);
-    m.tile = (int64_t)(idx / (uint32_t)n_chunks) * 8 + xcd;
-    m.valid = m.tile < n_tiles;
-    return m;
-}
-
-// ... with the launch's priority tiles in front (their flags travel at agent scope whatever the launch's protocol is)
+// map_block (de_plan.h) with the launch's priority tiles in front (their flags travel at agent scope whatever the launch's protocol is)
+struct GTileMap : TileMap { bool prio; };
 template <typename T> __device__ __forceinline__ GTileMap gmap_block_prio(const GArgs<T> &a, uint32_t bid) {
-    if (bid >= a.n_prio_blocks) return gmap_block(bid - a.n_prio_blocks, a.n_chunks, a.n_tiles);
+    if (bid >= a.n_prio_blocks) return GTileMap{map_block(bid - a.n_prio_blocks, a.n_chunks, a.n_tiles), false};
     GTileMap m;
     const uint32_t k = bid / (uint32_t)a.n_chunks;
     m.chunk = (int32_t)(bid % (uint32_t)a.n_chunks);
@@ -255,16 +233,6 @@ template <typename T> __device__ __forceinline__ GTileMap gmap_block_prio(const 
     m.prio = true;
     return m;
 }
-// (host) fills the priority fields of a launch with n_chunks chunks and tile_samples per tile; returns the blocks to add to the grid
-template <typename T> inline int64_t gprio_setup(GArgs<T> &a, const void *keys, int x_features, int tile_samples) {
-    a.prio = static_cast<const unsigned long long *>(keys);
-    a.n_prio = (uint32_t)(3 * x_features);
-    a.prio_shift = 0;
-    while ((64 << a.prio_shift) < tile_samples) ++a.prio_shift;
-    a.n_prio_blocks = (uint32_t)(((int64_t)a.n_prio * a.n_chunks + 7) / 8 * 8);
-    return (int64_t)a.n_prio_blocks;
-}
-
 __device__ __noinline__ void gflag_incomplete(uint8_t *ok, int agent) { // agent scope (written through): workgroups that start later skip the tree
     if ((threadIdx.x & 63) == 0) {
         if (agent) __hip_atomic_store(ok, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -273,5 +241,52 @@ __device__ __noinline__ void gflag_incomplete(uint8_t *ok, int agent) { // agent
 }
 
 constexpr int GBLK = 256;
+
+// ---- tile prologue -----------------------------------------------------------------------------------------------------------------
+// Stage leaf rows of a tile of `samples` samples that starts at sample `base` (samples behind `last` are copies of `last`); at(j, f) = the
+// LDS element of (sample j of the tile, leaf row f), which is all the kernels' layouts differ in.  Plain values, not the kernel-argument
+// struct (g_epilogue_loss, de_grad_threaded.hip: handing that around by address makes its loads look divergent).
+// ... rows [0, n_rows): X
+template <typename T, typename AT>
+__device__ __forceinline__ void stage_x_rows(T *rows, const T *X, int64_t ldX, uint32_t n_rows, uint32_t samples, int64_t base, int64_t last, AT at) {
+    const uint32_t total = samples * n_rows;
+    for (uint32_t e = threadIdx.x; e < total; e += GBLK) {
+        const uint32_t j = e / n_rows, f = e - j * n_rows;
+        int64_t jj = base + j;
+        jj = jj < last ? jj : last;
+        rows[at(j, f)] = X[f + ldX * jj];
+    }
+}
+// ... rows [row0, row0 + n_rows): params[:, class of the sample] (src/ParametricExpression.jl:381-389), read through the caches
+template <typename T, typename AT>
+__device__ __forceinline__ void stage_param_rows(T *rows, const T *params, int64_t ld_params, const void *classes, int32_t classes_is_i64, int32_t class_base,
+                                                 int64_t n_classes, uint32_t row0, uint32_t n_rows, uint32_t samples, int64_t base, int64_t last, AT at) {
+    const uint32_t total = samples * n_rows;
+    for (uint32_t e = threadIdx.x; e < total; e += GBLK) {
+        const uint32_t j = e / n_rows, q = e - j * n_rows;
+        int64_t jj = base + j;
+        jj = jj < last ? jj : last;
+        const int64_t cl = clamp_class((classes_is_i64 ? reinterpret_cast<const int64_t *>(classes)[jj] : (int64_t) reinterpret_cast<const int32_t *>(classes)[jj]) - class_base, n_classes);
+        rows[at(j, row0 + q)] = params[q + ld_params * cl];
+    }
+}
+
+// Loss term of one sample — value x, target yv, weight wv —: l = w * l(x - y) and lp = w * l'(x - y), the factor of the pullback.
+// loss_mode = 1 + de_loss_kind; weight 0 (and samples past N) really excludes the sample.
+template <typename T> struct LossTerm { T l, lp; };
+template <typename T> __device__ __forceinline__ LossTerm<T> loss_term(int loss_mode, T x, T yv, T wv) {
+    const T e = x - yv;
+    LossTerm<T> r;
+    if (loss_mode == 1 + DE_LOSS_L2) { r.l = wv * (e * e); r.lp = wv * (T(2) * e); }
+    else if (loss_mode == 1 + DE_LOSS_L1) { r.l = wv * M<T>::abs(e); r.lp = wv * jl_sign(e); }
+    else { r.l = wv * (x * yv); r.lp = wv * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
+    if (wv == T(0)) { r.l = T(0); r.lp = T(0); }
+    return r;
+}
+
+// What a module of the threaded kernels (de_grad_threaded.hip: 18, de_rev_threaded.hip: 2) hands to the one launch path
+// (de_grad_kernels.hip): the host stubs of its handler-table fill kernel and of its kernel, kernel[PARAMS][SHARE] (the reverse kernel
+// has no SHARE form).  Every kernel takes (GArgs<T>, handler base, parameter handler offset).
+struct GradModule { const void *fill; const void *kernel[2][2]; };
 
 } // namespace de

@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
     extern __shared__ __align__(16) unsigned char gsmem[];
     T *__restrict__ rows = reinterpret_cast<T *>(gsmem);
 
-    const GTileMap tm = gmap_block(blockIdx.x, a.n_chunks, a.n_tiles);
+    const TileMap tm = map_block(blockIdx.x, a.n_chunks, a.n_tiles);
     if (!tm.valid) return;
     const int tid = threadIdx.x;
     const int64_t base = tm.tile * GBLK;
@@ -39,16 +39,7 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
     const int g0 = a.diff_g0 >= 0 ? a.diff_g0 : (int)blockIdx.y * GC; // first gradient component of this window
     const int F = a.F, P = a.P;
 
-    {
-        const uint32_t Fu = (uint32_t)F;
-        const uint32_t total = (uint32_t)GBLK * Fu;
-        for (uint32_t e = tid; e < total; e += GBLK) {
-            const uint32_t j = e / Fu, f = e - j * Fu;
-            int64_t jj = base + j;
-            jj = jj < last ? jj : last;
-            rows[f * RS + j] = a.X[f + a.ldX * jj];
-        }
-    }
+    stage_x_rows<T>(rows, a.X, a.ldX, (uint32_t)F, GBLK, base, last, [](uint32_t j, uint32_t f) { return f * RS + j; });
     int64_t jj0 = base + tid;
     const bool live = jj0 < a.N;
     jj0 = jj0 < last ? jj0 : last;
@@ -226,22 +217,16 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
             DE_UNROLL for (int k = 0; k < GC; k++) poison = M<T>::fma(g0 + k < G ? d[k] : T(0), T(0), poison); // real rows only
         }
         if (a.loss_mode) {
-            const T e = x - yv;
-            T lp; // w * l'(e)
-            T l;  // w * l(e)
-            if (a.loss_mode == 1 + DE_LOSS_L2) { l = wv * (e * e); lp = wv * (T(2) * e); }
-            else if (a.loss_mode == 1 + DE_LOSS_L1) { l = wv * M<T>::abs(e); lp = wv * jl_sign(e); }
-            else { l = wv * (x * yv); lp = wv * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
-            if (wv == T(0)) { l = T(0); lp = T(0); }  // weight 0 (and samples past N) really excludes the sample
+            const LossTerm<T> lt = loss_term<T>(a.loss_mode, x, yv, wv);
             const int64_t n_cols = col_off[a.n_trees];
             T *__restrict__ pp = a.partial + ((int64_t)tm.tile * n_cols + col_off[tree]) * 4 + (tid >> 6);
             if (g0 == 0) {
-                const T s = wave_sum_to_lane63(l);
+                const T s = wave_sum_to_lane63(lt.l);
                 if ((tid & 63) == 63) pp[0] = s;
             }
             DE_UNROLL for (int k = 0; k < GC; k++) {
                 if (g0 + k < G) { // wave-uniform
-                    const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : lp * d[k]);
+                    const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : lt.lp * d[k]);
                     if ((tid & 63) == 63) pp[(int64_t)(1 + g0 + k) * 4] = s;
                 }
             }
@@ -266,7 +251,7 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
 template <typename T>
 __global__ void __launch_bounds__(256) de_loss_grad_finish_kernel(const double *__restrict__ seg_sum, int64_t n_trees, int64_t n_cols,
                                                                  int32_t n_segs, const int64_t *__restrict__ col_off,
-                                                                 const int32_t *__restrict__ n_grad, const uint8_t *__restrict__ ok,
+                                                                 const uint8_t *__restrict__ ok,
                                                                  T *__restrict__ loss, T *__restrict__ dloss,
                                                                  const int64_t *__restrict__ dloss_off) {
     const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -287,14 +272,13 @@ __global__ void __launch_bounds__(256) de_loss_grad_finish_kernel(const double *
     else dloss[dloss_off[t] + c - 1] = v;
 }
 
-static int g_gcu = 0;
-
-template <typename T, int GC>
-static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t stream) {
+// ---- one launch path for the three gradient kernels ----------------------------------------------------------------------------------
+// The kernel arguments every gradient kernel shares, from the caller's GradArgs; every other field is 0.  What is particular to a
+// kernel — its code pointers, the trees of the launch (tree_ids / n_trees), n_slots, n_tiles, the parameter rows behind F, share /
+// var_stride, rev_*, tile_range, diff_g0 / check — is set by that kernel's own lines below.
+template <typename T> static GArgs<T> make_gargs(const GradArgs &ga) {
     const EvalArgs &e = ga.e;
-    GArgs<T> a;
-    a.code = nullptr;
-    a.code_off = e.code_off;
+    GArgs<T> a = {};
     a.X = static_cast<const T *>(e.X);
     a.out = static_cast<T *>(e.out);
     a.grad = static_cast<T *>(ga.grad);
@@ -307,26 +291,17 @@ static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t str
     a.ldX = e.ldX;
     a.ld_out = e.ld_out;
     a.ld_params = e.ld_params;
-    a.n_tiles = (e.N + GBLK - 1) / GBLK;
-    a.F = e.F;
+    a.F = a.FX = e.F;
     a.P = ga.P;
-    a.n_trees = e.n_trees;
-    a.n_slots = e.n_slots;
+    a.n_all_trees = e.n_trees;
     a.mode = ga.mode;
     a.classes_is_i64 = e.classes_is_i64;
     a.class_base = e.class_base;
     a.n_classes = e.n_classes > 0 ? e.n_classes : 1;
     a.uses_params = e.uses_params ? 1 : 0;
-    a.check = ga.diff_direction >= 0 ? 0 : 1;
+    a.check = 1;
     a.skip_flagged = e.skip_flagged ? 1 : 0;
-    a.diff_g0 = ga.diff_direction >= 0 ? ga.P + ga.diff_direction : -1;
-    a.code = ga.generic_code;
-    a.tree_ids = nullptr;
-    a.n_all_trees = e.n_trees;
-    a.loss_mode = 0;
-    a.y = a.w = nullptr;
-    a.partial = nullptr;
-    a.col_off = nullptr;
+    a.diff_g0 = -1;
     if (ga.loss) {
         a.loss_mode = 1 + ga.loss->kind;
         a.y = static_cast<const T *>(ga.loss->y);
@@ -334,32 +309,54 @@ static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t str
         a.partial = static_cast<T *>(ga.loss->partial);
         a.col_off = ga.col_off;
     }
-    if (g_gcu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_gcu = prop.multiProcessorCount;
-        if (g_gcu <= 0) g_gcu = 256;
-    }
-    int64_t n_chunks = (e.n_trees + 31) / 32;
-    const int64_t want_blocks = (int64_t)g_gcu * 4 * 8;
-    if (a.n_tiles * n_chunks * windows < want_blocks) n_chunks = (want_blocks + a.n_tiles * windows - 1) / (a.n_tiles * windows);
-    const int64_t max_chunks = (e.n_trees + 3) / 4;
-    if (n_chunks > max_chunks) n_chunks = max_chunks;
-    if (n_chunks < 1) n_chunks = 1;
-    a.trees_per_chunk = (int32_t)((e.n_trees + n_chunks - 1) / n_chunks);
-    if (a.skip_flagged) a.skip_flagged = a.trees_per_chunk >= 8 ? 1 : 2; // flag protocol (skip_flag_load, de_device_ops.h): these kernels write little, their L1 lines go stale under 2 (reverse kernel 17.0 / 16.0 ms); 2 only for tiny chunks (many tiles on one flag line)
-    a.n_chunks = (int32_t)((e.n_trees + a.trees_per_chunk - 1) / a.trees_per_chunk);
+    return a;
+}
+
+// Plans and starts one gradient launch: a.n_trees trees x a.n_tiles sample tiles x `windows` gradient windows (grid.y) of `kern`, the
+// host stub of a kernel that takes (GArgs<T>, handler base, parameter handler offset) — the flat kernel: the first of them —, with
+// `lds` bytes of dynamic LDS.  prio_keys != null: the launch has priority tiles (de_kernels.hip de_tile_extremes_kernel) of
+// prio_tile_samples samples each; prio_cached: grad_flag_protocol (de_plan.h).
+template <typename T>
+static hipError_t launch_grad_kernel(const void *kern, GArgs<T> a, int windows, size_t lds, const void *prio_keys, int prio_tile_samples,
+                                     bool prio_cached, uint64_t handler_base, uint32_t param_off, hipStream_t stream) {
+    grad_chunk_plan(a.n_trees, a.n_tiles, windows, cu_count(), &a.trees_per_chunk, &a.n_chunks);
+    if (a.skip_flagged) a.skip_flagged = grad_flag_protocol(a.trees_per_chunk, prio_cached, env_int("DE_SKIP_PROTOCOL", 0));
     const int64_t blocks = ((a.n_tiles + 7) / 8) * 8 * a.n_chunks;
     if (blocks <= 0 || blocks > 0x7fffffffLL || windows > 65535) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(a.F + (size_t)a.n_slots * (1 + GC)) * (GBLK + 4) * sizeof(T);
-    auto kern = de_grad_tape_kernel<T, GC>;
     if (lds > 64 * 1024) {
         if (lds > 160 * 1024) return hipErrorInvalidValue;
-        hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t st = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (st != hipSuccess) return st;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), lds, stream, a);
-    hipError_t st = hipGetLastError();
+    if (a.skip_flagged && prio_keys) { // the priority tiles as a launch of their own in front, in short chunks (de_kernels.hip launch_threaded_t: no blind first wave)
+        GArgs<T> pa = a;
+        pa.prio = static_cast<const unsigned long long *>(prio_keys);
+        pa.n_prio = (uint32_t)(3 * a.FX);
+        while ((64 << pa.prio_shift) < prio_tile_samples) ++pa.prio_shift;
+        pa.trees_per_chunk = 4;
+        pa.n_chunks = (int32_t)((a.n_trees + 3) / 4);
+        pa.n_prio_blocks = (uint32_t)(((int64_t)pa.n_prio * pa.n_chunks + 7) / 8 * 8);
+        void *pargs[] = {&pa, &handler_base, &param_off};
+        const hipError_t ps = hipLaunchKernel(kern, dim3(pa.n_prio_blocks, (unsigned)windows), dim3(GBLK), pargs, lds, stream);
+        if (ps != hipSuccess) return ps;
+    }
+    void *args[] = {&a, &handler_base, &param_off};
+    return hipLaunchKernel(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), args, lds, stream);
+}
+
+template <typename T, int GC>
+static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t stream) {
+    const EvalArgs &e = ga.e;
+    GArgs<T> a = make_gargs<T>(ga);
+    a.code = ga.generic_code;
+    a.code_off = e.code_off;
+    a.n_trees = e.n_trees;
+    a.n_slots = e.n_slots;
+    a.n_tiles = (e.N + GBLK - 1) / GBLK;
+    a.check = ga.diff_direction >= 0 ? 0 : 1;
+    a.diff_g0 = ga.diff_direction >= 0 ? ga.P + ga.diff_direction : -1;
+    const size_t lds = (size_t)(a.F + (size_t)a.n_slots * (1 + GC)) * (GBLK + 4) * sizeof(T);
+    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
     if (st != hipSuccess || !ga.loss) return st;
     return launch_loss_grad_finish(sizeof(T) == 4 ? DE_F32 : DE_F64, ga, a.n_tiles, stream);
 }
@@ -371,7 +368,7 @@ template <typename T> static hipError_t loss_grad_finish_t(const GradArgs &ga, i
                                              &n_segs, stream);
     if (st != hipSuccess) return st;
     hipLaunchKernelGGL(de_loss_grad_finish_kernel<T>, dim3((unsigned)((ga.n_cols + 255) / 256)), dim3(256), 0, stream,
-                       static_cast<const double *>(ga.loss->seg_sum), (int64_t)ga.e.n_trees, ga.n_cols, n_segs, ga.col_off, ga.n_grad,
+                       static_cast<const double *>(ga.loss->seg_sum), (int64_t)ga.e.n_trees, ga.n_cols, n_segs, ga.col_off,
                        ga.e.ok, static_cast<T *>(ga.loss->loss), static_cast<T *>(ga.dloss), ga.dloss_off);
     return hipGetLastError();
 }
@@ -386,11 +383,6 @@ hipError_t launch_loss_grad_finish_range(int dtype, const GradArgs &ga, int64_t 
 }
 hipError_t launch_loss_grad_finish(int dtype, const GradArgs &ga, int64_t n_tiles, hipStream_t stream) {
     return dtype == DE_F32 ? loss_grad_finish_t<float>(ga, n_tiles, stream) : loss_grad_finish_t<double>(ga, n_tiles, stream);
-}
-
-int grad_window(int max_grad) {
-    const int m = max_grad < 1 ? 1 : max_grad;
-    return m <= 6 ? m : 8; // smallest window that covers the widest gradient in one pass, else windows of 8
 }
 
 template <typename T> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
@@ -475,44 +467,35 @@ hipError_t launch_by_class_combine(int dtype, const ByClassArgs &a, hipStream_t 
     return hipGetLastError();
 }
 
-// ---- threaded variant: one module per (type, window, samples per lane) — de_grad_threaded.hip ----------
-#define DE_GT_DECL(TAG, GC, V)                                                       \
-    hipError_t grad_thr_fetch_##TAG##GC##v##V(uint64_t *host_table);                  \
-    hipError_t grad_thr_launch_##TAG##GC##v##V(const GradArgs &ga, int bucket, hipStream_t stream);
-// must agree with build.sh
+// ---- threaded variants: one module per (type, window, samples per lane) — de_grad_threaded.hip — and, for reverse accumulation, one
+// per element type — de_rev_threaded.hip.  DE_GT_ALL is THE list of the former: build.sh reads its entries from this file.
+// (Float64: windows of <= 5 rows — wider states than 16 dwords would be passed through scratch memory)
 #define DE_GT_ALL(X)                                                                                     \
     X(f, 1, 1) X(f, 2, 1) X(f, 3, 1) X(f, 4, 1) X(f, 5, 1) X(f, 6, 1) X(f, 8, 1)                          \
     X(f, 1, 2) X(f, 2, 2) X(f, 3, 2) X(f, 4, 2) X(f, 5, 2) X(f, 6, 2)                                     \
     X(d, 1, 1) X(d, 2, 1) X(d, 3, 1) X(d, 4, 1) X(d, 5, 1)
+#define DE_GT_DECL(TAG, GC, V) GradModule grad_thr_module_##TAG##GC##v##V();
 DE_GT_ALL(DE_GT_DECL)
+GradModule rev_thr_module_f();
+GradModule rev_thr_module_d();
 
-bool grad_threaded_has(int dtype, int GC, int VS) {
-    if (GC < 1 || GC > 8 || GC == 7) return false;
-    if (dtype == DE_F32) return VS == 1 || (VS == 2 && GC <= 6);
-    return VS == 1 && GC <= 5; // Float64 states wider than 16 dwords would be passed through scratch memory
+static bool grad_thr_module(int dtype, int GC, int VS, GradModule *m) {
+    static const struct { int dtype, GC, VS; GradModule (*get)(); } all[] = {
+#define DE_GT_ROW(TAG, GC, V) {#TAG[0] == 'f' ? DE_F32 : DE_F64, GC, V, grad_thr_module_##TAG##GC##v##V},
+        DE_GT_ALL(DE_GT_ROW)};
+    for (const auto &r : all)
+        if (r.dtype == dtype && r.GC == GC && r.VS == VS) { if (m) *m = r.get(); return true; }
+    return false;
 }
+bool grad_threaded_has(int dtype, int GC, int VS) { return grad_thr_module(dtype, GC, VS, nullptr); }
 
 hipError_t grad_handler_table(int dtype, int GC, int VS, uint64_t *table) {
-    struct Cache { uint64_t t[2][9][3][GOP_MAX]; bool have[2][9][3] = {}; };
-    static std::unique_ptr<Cache> caches[DE_MAX_DEVICES]; // per device (de_kernels.hip handler_device_slot)
-    static std::mutex mu; // contexts on several host threads may ask at once
-    int dev = 0;
-    { const hipError_t dst = handler_device_slot(&dev); if (dst != hipSuccess) return dst; }
-    const std::lock_guard<std::mutex> lock(mu);
-    if (!caches[dev]) caches[dev].reset(new Cache());
-    auto &cache = caches[dev]->t;
-    auto &have = caches[dev]->have;
-    const int k = dtype == DE_F32 ? 0 : 1;
-    if (!grad_threaded_has(dtype, GC, VS)) return hipErrorInvalidValue;
-    if (!have[k][GC][VS]) {
-        hipError_t st = hipErrorInvalidValue;
-#define DE_GT_FETCH(TAG, G, V) if (k == (#TAG[0] == 'f' ? 0 : 1) && GC == G && VS == V) st = grad_thr_fetch_##TAG##G##v##V(cache[k][GC][VS]);
-        DE_GT_ALL(DE_GT_FETCH)
-        if (st != hipSuccess) return st;
-        have[k][GC][VS] = true;
-    }
-    for (int i = 0; i < (int)gop_count(GC); i++) table[i] = cache[k][GC][VS][i];
-    return hipSuccess;
+    GradModule m;
+    if (!grad_thr_module(dtype, GC, VS, &m)) return hipErrorInvalidValue;
+    return handler_table(m.fill, gop_count(GC), table);
+}
+hipError_t rev_handler_table(int dtype, uint64_t *table) {
+    return handler_table((dtype == DE_F32 ? rev_thr_module_f() : rev_thr_module_d()).fill, ROP_COUNT, table);
 }
 
 // Side streams of a caller's stream: the buckets of one gradient call (one launch — with its probe launch in front — per window width and
@@ -605,11 +588,35 @@ hipError_t launch_loss_grad_finish_ranges(int dtype, const GradArgs &ga, int64_t
 }
 
 static hipError_t grad_prio_prepass(int dtype, const GradArgs &a, hipStream_t stream, GradArgs *with);
+// one bucket of a gradient call: the forward threaded kernel of the module built for its window width and samples per lane
+template <typename T> static hipError_t launch_grad_bucket(const GradArgs &ga, const GradArgs::Bucket &bk, hipStream_t stream) {
+    const EvalArgs &e = ga.e;
+    GradModule m;
+    if (!grad_thr_module(sizeof(T) == 4 ? DE_F32 : DE_F64, bk.GC, bk.VS, &m)) return hipErrorInvalidValue;
+    const int GC = bk.GC, VS = bk.VS;
+    GArgs<T> a = make_gargs<T>(ga);
+    a.code = ga.threaded_code;
+    a.code_off = e.code_off;
+    a.tree_ids = bk.ids;
+    a.n_trees = bk.n;
+    a.n_slots = bk.n_slots; // spill slots the trees of this bucket need
+    a.F += e.uses_params ? ga.P : 0; // leaf rows: X, then the parameters gathered by class
+    const bool share = ga.gt_share;
+    a.share = share ? 1 : 0;
+    a.var_stride = share ? ga.gt_var_stride : 0;
+    const int tile_samples = share ? 64 * VS : GBLK * VS;
+    // (shared rows: whole groups of four tiles — a fused-loss launch must write every (tile of 256 x VS samples, wave) entry of the partial
+    // sums, also the all-padding quarter tiles behind N, as the four-wave workgroup did)
+    a.n_tiles = share ? 4 * ((e.N + GBLK * VS - 1) / (GBLK * VS)) : (e.N + tile_samples - 1) / tile_samples;
+    const size_t slot_rows = std::max<size_t>((size_t)a.n_slots * (1 + GC), (size_t)GC);
+    const size_t lds = (share ? (size_t)a.F + 4 * slot_rows : 4 * ((size_t)a.F + slot_rows)) * 64 * VS * sizeof(T); // 4 waves x rows x one wave's samples (shared leaf rows: once)
+    return launch_grad_kernel(m.kernel[e.uses_params ? 1 : 0][share ? 1 : 0], a, bk.windows, lds, ga.prio_ready ? e.prio_keys : nullptr, tile_samples,
+                              ga.prio_ready, bk.handler_base, bk.param_handler_off, stream); // the loss reduction passes run once, after the last bucket
+}
 hipError_t launch_grad_threaded(int dtype, const GradArgs &a0, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "de_grad_threaded_kernel";
     GradArgs a;
     { const hipError_t ps = grad_prio_prepass(dtype, a0, stream, &a); if (ps != hipSuccess) return ps; }
-    const int k = dtype == DE_F32 ? 0 : 1;
     if (a.loss) { // two-sample modules use 512-sample tiles: the 256-sample tile slots they never write must read as 0
         bool wide = false;
         for (int b = 0; b < a.n_buckets; b++) wide = wide || (a.buckets[b].n > 0 && a.buckets[b].VS > 1);
@@ -628,9 +635,7 @@ hipError_t launch_grad_threaded(int dtype, const GradArgs &a0, hipStream_t strea
         const GradArgs::Bucket &bk = a.buckets[b];
         if (bk.n <= 0) continue;
         const hipStream_t bs = fj.next();
-        hipError_t st = hipErrorInvalidValue;
-#define DE_GT_LAUNCH(TAG, G, V) if (k == (#TAG[0] == 'f' ? 0 : 1) && bk.GC == G && bk.VS == V) st = grad_thr_launch_##TAG##G##v##V(a, b, bs);
-        DE_GT_ALL(DE_GT_LAUNCH)
+        const hipError_t st = dtype == DE_F32 ? launch_grad_bucket<float>(a, bk, bs) : launch_grad_bucket<double>(a, bk, bs);
         if (st != hipSuccess) { first_err = st; break; }
     }
     { const hipError_t js = fj.join(); if (first_err == hipSuccess) first_err = js; }
@@ -640,28 +645,27 @@ hipError_t launch_grad_threaded(int dtype, const GradArgs &a0, hipStream_t strea
 }
 
 // ---- reverse accumulation: one module per element type (de_rev_threaded.hip) --------------------------
-hipError_t rev_thr_fetch_f(uint64_t *host_table);
-hipError_t rev_thr_fetch_d(uint64_t *host_table);
-hipError_t rev_thr_launch_f(const GradArgs &ga, int group, hipStream_t stream);
-hipError_t rev_thr_launch_d(const GradArgs &ga, int group, hipStream_t stream);
-hipError_t rev_handler_table(int dtype, uint64_t *table) {
-    struct Cache { uint64_t t[2][ROP_COUNT]; bool have[2] = {false, false}; };
-    static std::unique_ptr<Cache> caches[DE_MAX_DEVICES]; // per device
-    static std::mutex mu; // contexts on several host threads may ask at once
-    int dev = 0;
-    { const hipError_t dst = handler_device_slot(&dev); if (dst != hipSuccess) return dst; }
-    const std::lock_guard<std::mutex> lock(mu);
-    if (!caches[dev]) caches[dev].reset(new Cache());
-    auto &cache = caches[dev]->t;
-    auto &have = caches[dev]->have;
-    const int k = dtype == DE_F32 ? 0 : 1;
-    if (!have[k]) {
-        const hipError_t st = k == 0 ? rev_thr_fetch_f(cache[k]) : rev_thr_fetch_d(cache[k]);
-        if (st != hipSuccess) return st;
-        have[k] = true;
-    }
-    for (int i = 0; i < (int)ROP_COUNT; i++) table[i] = cache[k][i];
-    return hipSuccess;
+// one LDS-need group of trees
+template <typename T> static hipError_t launch_rev_group(const GradArgs &ga, const GradArgs::RevGroup &grp, hipStream_t stream) {
+    const EvalArgs &e = ga.e;
+    if (grp.n <= 0) return hipSuccess;
+    const GradModule m = sizeof(T) == 4 ? rev_thr_module_f() : rev_thr_module_d();
+    GArgs<T> a = make_gargs<T>(ga);
+    a.code = ga.rev_code;
+    a.code_off = ga.rev_code_off;
+    a.rev_mid = ga.rev_code_mid;
+    a.rev_rows = grp.rows;
+    a.rev_stage_cols = ga.rev_stage_cols;
+    a.rev_stage_rows = (int32_t)(((size_t)ga.rev_stage_cols * sizeof(T) + 64 * sizeof(T) - 1) / (64 * sizeof(T)));
+    a.tree_ids = ga.rev_ids + grp.first;
+    a.n_trees = grp.n;
+    a.n_slots = e.n_slots;
+    a.F += e.uses_params ? ga.P : 0; // leaf rows: X, then the parameters gathered by class
+    a.n_tiles = ga.rev_tile_range ? ga.rev_n_tiles : (e.N + GBLK - 1) / GBLK;
+    a.tile_range = ga.rev_tile_range;
+    const size_t lds = 4 * (size_t)a.rev_rows * 64 * sizeof(T);
+    return launch_grad_kernel(m.kernel[e.uses_params ? 1 : 0][0], a, 1, lds, ga.prio_ready && !ga.rev_tile_range ? e.prio_keys : nullptr, GBLK, // (class-aligned tiles: no priority tiles)
+                              false, ga.rev_handler_base, ga.rev_param_off, stream);
 }
 // the priority tiles of a gradient / reverse launch: one pre-pass over X for all its buckets (de_kernels.hip de_tile_extremes_kernel)
 static hipError_t grad_prio_prepass(int dtype, const GradArgs &a, hipStream_t stream, GradArgs *with) {
@@ -681,7 +685,7 @@ hipError_t launch_rev_threaded(int dtype, const GradArgs &a0, hipStream_t stream
     hipError_t first_err = fj.fork();
     if (first_err != hipSuccess) return first_err;
     for (int k = 0; k < a.rev_n_groups; k++) { // one launch per LDS-need group of trees, spread over the side streams
-        const hipError_t st = dtype == DE_F32 ? rev_thr_launch_f(a, k, fj.next()) : rev_thr_launch_d(a, k, fj.next());
+        const hipError_t st = dtype == DE_F32 ? launch_rev_group<float>(a, a.rev_groups[k], fj.next()) : launch_rev_group<double>(a, a.rev_groups[k], fj.next());
         if (st != hipSuccess) { first_err = st; break; }
     }
     { const hipError_t js = fj.join(); if (first_err == hipSuccess) first_err = js; }

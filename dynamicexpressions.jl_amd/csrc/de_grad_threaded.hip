@@ -33,8 +33,6 @@
 // most one spill slot (11 rows x 512 B x 4 waves = 22.5 KB: 7 workgroups per CU); with two slots (34.8 KB: 4
 // workgroups) the lost occupancy costs more than the packed arithmetic saves (measured).  The state must stay
 // within the 16 dwords the calling convention passes in registers (2*(1 + GC) + poison + g0).
-#include <algorithm>
-
 #include "de_grad_common.h"
 
 #ifndef DE_GT_T
@@ -378,13 +376,9 @@ __device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const
         const int64_t jj = j < last ? j : last;
         const T yv = y[jj];
         wv[i] = j <= last ? (w ? w[jj] : T(1)) : T(0);
-        const T e = st.x[i] - yv;
-        T li;
-        if (loss_mode == 1 + DE_LOSS_L2) { li = wv[i] * (e * e); lp[i] = wv[i] * (T(2) * e); }
-        else if (loss_mode == 1 + DE_LOSS_L1) { li = wv[i] * M<T>::abs(e); lp[i] = wv[i] * jl_sign(e); }
-        else { li = wv[i] * (st.x[i] * yv); lp[i] = wv[i] * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
-        if (wv[i] == T(0)) { li = T(0); lp[i] = T(0); } // weight 0 (and samples past N) really excludes the sample
-        l += li;
+        const LossTerm<T> lt = loss_term<T>(loss_mode, st.x[i], yv, wv[i]);
+        lp[i] = lt.lp;
+        l += lt.l;
     }
     pp += wave;
     if (g0 == 0) {
@@ -480,6 +474,8 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
     const int slot_rows = a.n_slots * (1 + GC) > GC ? a.n_slots * (1 + GC) : GC;
     const int R = F + slot_rows; // rows per wave
     if (share) {
+        // (stage_x_rows / stage_param_rows of de_grad_common.h with the map (j, f) -> f * WSAMP + j, spelled out: through the helpers this
+        // branch alone compiles to other code — same IR, other block order; Float32 +2 instructions, Float64 up to +38 — TUNING_LOG.md)
         const uint32_t Fu = (uint32_t)a.FX, total = (uint32_t)WSAMP * Fu;
         for (uint32_t e = tid; e < total; e += GBLK) {
             const uint32_t j = e / Fu, f = e - j * Fu;
@@ -497,28 +493,12 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
                 rows[((uint32_t)a.FX + q) * WSAMP + j] = a.params[q + a.ld_params * cl];
             }
         }
-    } else {
-    {
-        const uint32_t Fu = (uint32_t)a.FX;
-        const uint32_t total = (uint32_t)TILE * Fu;
-        for (uint32_t e = tid; e < total; e += GBLK) {
-            const uint32_t j = e / Fu, f = e - j * Fu;
-            int64_t jj = base + j;
-            jj = jj < last ? jj : last;
-            rows[((j / WSAMP) * (uint32_t)R + f) * WSAMP + (j % WSAMP)] = a.X[f + a.ldX * jj];
-        }
+    } else { // one copy of the leaf rows per wave
+        const uint32_t FX = (uint32_t)a.FX, Ru = (uint32_t)R;
+        const auto at = [Ru](uint32_t j, uint32_t f) { return ((j / WSAMP) * Ru + f) * WSAMP + (j % WSAMP); };
+        stage_x_rows<T>(rows, a.X, a.ldX, FX, TILE, base, last, at);
+        if (PARAMS) stage_param_rows<T>(rows, a.params, a.ld_params, a.classes, a.classes_is_i64, a.class_base, a.n_classes, FX, (uint32_t)F - FX, TILE, base, last, at);
     }
-    if (PARAMS) { // rows FX .. F: params[:, class of the sample] (src/ParametricExpression.jl:381-389), read through the caches
-        const uint32_t Pu = (uint32_t)(F - a.FX), total = (uint32_t)TILE * Pu;
-        for (uint32_t e = tid; e < total; e += GBLK) {
-            const uint32_t j = e / Pu, q = e - j * Pu;
-            int64_t jj = base + j;
-            jj = jj < last ? jj : last;
-            const int64_t cl = clamp_class((a.classes_is_i64 ? reinterpret_cast<const int64_t *>(a.classes)[jj] : (int64_t) reinterpret_cast<const int32_t *>(a.classes)[jj]) - a.class_base, a.n_classes);
-            rows[((j / WSAMP) * (uint32_t)R + (uint32_t)a.FX + q) * WSAMP + (j % WSAMP)] = a.params[q + a.ld_params * cl];
-        }
-    }
-    } // one copy of the leaf rows per wave
     __syncthreads();
 
     const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)(a.code + (share ? (int64_t)wave * a.var_stride : (int64_t)0));
@@ -571,123 +551,20 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
     }
 }
 
-// ---- host side: entry points of this (type, window) module -----------------------------------------
 } // module namespace
 
-hipError_t DE_GT_NAME(grad_thr_fetch_)(uint64_t *host_table) {
+// ---- host side: what this (type, window, samples per lane) module exports; the launch is de_grad_kernels.hip launch_grad_kernel --------
+GradModule DE_GT_NAME(grad_thr_module_)() {
     using namespace DE_GT_NAME(gtm_);
-    uint64_t *d = nullptr;
-    hipError_t st = hipMalloc(reinterpret_cast<void **>(&d), GOP_MAX * sizeof(uint64_t));
-    if (st != hipSuccess) return st;
-    hipLaunchKernelGGL((de_grad_fill_handlers<DE_GT_T, DE_GT_GC>), dim3(1), dim3(1), 0, 0, d);
-    st = hipMemcpy(host_table, d, gop_count(DE_GT_GC) * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return st;
-}
-
-hipError_t DE_GT_NAME(grad_thr_launch_)(const GradArgs &ga, int bucket, hipStream_t stream) {
-    using namespace DE_GT_NAME(gtm_);
-    const GradArgs::Bucket &bk = ga.buckets[bucket];
-    const int windows = bk.windows;
     typedef DE_GT_T T;
     constexpr int GC = DE_GT_GC;
-    static int gt_gcu = 0;
-    const EvalArgs &e = ga.e;
-    GArgs<T> a;
-    a.code = ga.threaded_code;
-    a.code_off = e.code_off;
-    a.X = static_cast<const T *>(e.X);
-    a.out = static_cast<T *>(e.out);
-    a.grad = static_cast<T *>(ga.grad);
-    a.grad_off = ga.grad_off;
-    a.n_grad = ga.n_grad;
-    a.ok = e.ok;
-    a.params = static_cast<const T *>(e.params);
-    a.classes = e.classes;
-    a.N = e.N;
-    a.ldX = e.ldX;
-    a.ld_out = e.ld_out;
-    a.ld_params = e.ld_params;
-    const bool share = ga.gt_share;
-    a.share = share ? 1 : 0;
-    a.var_stride = share ? ga.gt_var_stride : 0;
-    const int tile_samples = share ? 64 * VS : GBLK * VS;
-    // (shared rows: whole groups of four tiles — a fused-loss launch must write every (tile of 256 x VS samples, wave) entry of the partial
-    // sums, also the all-padding quarter tiles behind N, as the four-wave workgroup did)
-    a.n_tiles = share ? 4 * ((e.N + GBLK * VS - 1) / (GBLK * VS)) : (e.N + tile_samples - 1) / tile_samples;
-    a.FX = e.F;
-    a.F = e.F + (e.uses_params ? ga.P : 0); // leaf rows: X, then the parameters gathered by class
-    a.P = ga.P;
-    a.n_trees = bk.n;
-    a.n_all_trees = e.n_trees;
-    a.tree_ids = bk.ids;
-    a.n_slots = bk.n_slots; // spill slots the trees of this bucket need
-    a.mode = ga.mode;
-    a.classes_is_i64 = e.classes_is_i64;
-    a.class_base = e.class_base;
-    a.n_classes = e.n_classes > 0 ? e.n_classes : 1;
-    a.uses_params = e.uses_params ? 1 : 0;
-    a.check = 1;
-    a.skip_flagged = e.skip_flagged ? 1 : 0;
-    a.diff_g0 = -1;
-    a.loss_mode = 0;
-    a.y = a.w = nullptr;
-    a.partial = nullptr;
-    a.col_off = nullptr;
-    if (ga.loss) {
-        a.loss_mode = 1 + ga.loss->kind;
-        a.y = static_cast<const T *>(ga.loss->y);
-        a.w = static_cast<const T *>(ga.loss->w);
-        a.partial = static_cast<T *>(ga.loss->partial);
-        a.col_off = ga.col_off;
-    }
-    if (gt_gcu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) gt_gcu = prop.multiProcessorCount;
-        if (gt_gcu <= 0) gt_gcu = 256;
-    }
-    int64_t n_chunks = (bk.n + 31) / 32;
-    const int64_t want_blocks = (int64_t)gt_gcu * 4 * 8;
-    if (a.n_tiles * n_chunks * windows < want_blocks) n_chunks = (want_blocks + a.n_tiles * windows - 1) / (a.n_tiles * windows);
-    const int64_t max_chunks = (bk.n + 3) / 4;
-    if (n_chunks > max_chunks) n_chunks = max_chunks;
-    if (n_chunks < 1) n_chunks = 1;
-    a.trees_per_chunk = (int32_t)((bk.n + n_chunks - 1) / n_chunks);
-    // ... unless the launch has priority tiles (below): the flags are then down before most workgroups first look, a stale line is rare and
-    // the cached protocol wins (fused loss gradient 6.65 -> 5.98 ms; the reverse kernel keeps protocol 1: 15.9 against 16.9 ms)
-    if (a.skip_flagged) a.skip_flagged = (a.trees_per_chunk >= 8 && !ga.prio_ready) ? 1 : 2;
-    if (a.skip_flagged) { const char *pv = getenv("DE_SKIP_PROTOCOL"); if (pv && *pv >= '1' && *pv <= '3') a.skip_flagged = *pv - '0'; } // (experiments) // flag protocol (skip_flag_load, de_device_ops.h): these kernels write little, their L1 lines go stale under 2 (reverse kernel 17.0 / 16.0 ms); 2 only for tiny chunks (many tiles on one flag line)
-    a.n_chunks = (int32_t)((bk.n + a.trees_per_chunk - 1) / a.trees_per_chunk);
-    int64_t blocks = ((a.n_tiles + 7) / 8) * 8 * a.n_chunks;
-    a.prio = nullptr;
-    a.n_prio = a.n_prio_blocks = a.prio_shift = 0;
-    if (a.skip_flagged && ga.prio_ready) blocks += gprio_setup(a, e.prio_keys, e.F, tile_samples);
-    if (blocks <= 0 || blocks > 0x7fffffffLL || windows > 65535) return hipErrorInvalidValue;
-    const size_t slot_rows = std::max<size_t>((size_t)a.n_slots * (1 + GC), (size_t)GC);
-    const size_t lds = (share ? (size_t)a.F + 4 * slot_rows : 4 * ((size_t)a.F + slot_rows)) * 64 * VS * sizeof(T); // 4 waves x rows x one wave's samples (shared leaf rows: once)
-    void (*kern)(const GArgs<T>, uint64_t, uint32_t) = e.uses_params ? de_grad_threaded_kernel<T, GC, true> : de_grad_threaded_kernel<T, GC, false>;
-    if (share) kern = e.uses_params ? de_grad_threaded_kernel<T, GC, true, true> : de_grad_threaded_kernel<T, GC, false, true>;
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (st != hipSuccess) return st;
-    }
-    if (a.n_prio) { // the priority tiles as a launch of their own in front, in short chunks (de_kernels.hip launch_threaded_t: no blind first wave)
-        GArgs<T> pa = a;
-        pa.trees_per_chunk = 4;
-        pa.n_chunks = (int32_t)((bk.n + 3) / 4);
-        pa.n_prio_blocks = (uint32_t)(((int64_t)pa.n_prio * pa.n_chunks + 7) / 8 * 8);
-        hipLaunchKernelGGL(kern, dim3(pa.n_prio_blocks, (unsigned)windows), dim3(GBLK), lds, stream, pa, bk.handler_base, bk.param_handler_off);
-        const hipError_t ps = hipGetLastError();
-        if (ps != hipSuccess) return ps;
-        blocks -= a.n_prio_blocks;
-        a.n_prio = a.n_prio_blocks = 0;
-        a.prio = nullptr;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), lds, stream, a, bk.handler_base, bk.param_handler_off);
-    return hipGetLastError(); // the loss reduction passes run once, after the last bucket (de_grad_kernels.hip)
+    GradModule m;
+    m.fill = reinterpret_cast<const void *>(&de_grad_fill_handlers<T, GC>);
+    m.kernel[1][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, false>);
+    m.kernel[0][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, false>);
+    m.kernel[1][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, true>);
+    m.kernel[0][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, true>);
+    return m;
 }
-
 
 } // namespace de

@@ -171,13 +171,11 @@ hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **k
 hipError_t launch_eval_complex(int io, const EvalArgs &a, const void *ctab, hipStream_t stream, const char **kernel_name);
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);
 
-// Threaded gradient kernel: window width used for a population whose widest gradient has max_grad rows,
-// handler addresses for (dtype, window), launch; pass 2+3 of the fused loss-gradient reduction.
-int grad_window(int max_grad);
+// Threaded gradient kernels: handler addresses for (dtype, window, samples per lane), launch; pass 2+3 of the fused loss-gradient reduction.
 hipError_t grad_handler_table(int dtype, int GC, int VS, uint64_t *table); // GOP_MAX entries, gop_count(GC) used
-bool grad_threaded_has(int dtype, int GC, int VS);
+bool grad_threaded_has(int dtype, int GC, int VS);                         // is there a module for (type, window, samples per lane)?
 hipError_t rev_handler_table(int dtype, uint64_t *table); // ROP_COUNT entries
-hipError_t launch_rev_threaded(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);                            // is there a module for (type, window, samples per lane)?
+hipError_t launch_rev_threaded(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t launch_grad_threaded(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t launch_loss_grad_finish(int dtype, const GradArgs &ga, int64_t n_tiles, hipStream_t stream);
 // the same over tiles [tile0, tile0 + n_tiles) only, results to loss / dloss (by-class reduction: one call per class)
@@ -205,6 +203,9 @@ hipError_t launch_pullback_scale(int dtype, void *grad, const int64_t *grad_off,
 // The cached handler addresses are per device (every device loads its own copy of the code object): slot = the current device.
 constexpr int DE_MAX_DEVICES = 64;
 hipError_t handler_device_slot(int *slot);
+// ... and the one cache behind eval_handler_table, grad_handler_table and rev_handler_table (de_kernels.hip): the n addresses the kernel
+// stub `fill` writes, fetched once per device
+hipError_t handler_table(const void *fill, size_t n, uint64_t *table);
 // Threaded-code eval kernel: addresses of the TOPX_TABLE device handlers (cached per device).
 hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table);
 bool eval_uses_threaded();

@@ -29,9 +29,11 @@
 //    all chunks of one X tile back to back on one XCD, the tile re-served by that XCD's L2 (map_block / map_block_grouped).
 //  * No MFMA: this is an elementwise map, not a contraction.
 #include <hip/hip_runtime.h>
-#include <memory>
+#include <algorithm>
+#include <map>
 #include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include <cstdlib>
 #include <cstring>
@@ -1641,18 +1643,8 @@ void eval_plan(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chu
 }
 
 // ---- threaded variant: handler table + launch ---------------------------------------------
-template <typename T, bool TB> static hipError_t fetch_handlers(uint64_t *host_table) {
-    uint64_t *d = nullptr;
-    hipError_t st = hipMalloc(reinterpret_cast<void **>(&d), TOPX_TABLE * sizeof(uint64_t));
-    if (st != hipSuccess) return st;
-    hipLaunchKernelGGL((de_fill_handlers<T, TB>), dim3(1), dim3(1), 0, 0, d);
-    st = hipMemcpy(host_table, d, TOPX_TABLE * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return st;
-}
-
 // Handler addresses are baked into every record of the instruction streams and belong to ONE device's copy of the code object
-// (every device loads its own): the caches of the three handler tables (eval here, gradient and reverse in de_grad_kernels.hip) are
+// (every device loads its own): the cache of the handler tables (handler_table below: eval, gradient and reverse) is
 // keyed by the CURRENT device — the device of the context that creates the program (de_api_program.cpp sets it before it asks).  A process may
 // therefore hold contexts on several GPUs (round 3 refused every device but the first: ADVICE r3).
 hipError_t handler_device_slot(int *slot) {
@@ -1664,23 +1656,36 @@ hipError_t handler_device_slot(int *slot) {
     return hipSuccess;
 }
 
-hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table) {
-    struct Cache { uint64_t t[3][TOPX_TABLE]; bool have[3] = {false, false, false}; }; // Float32, Float64, Float32 turbo (Float64 has no relaxed operators)
-    static std::unique_ptr<Cache> caches[DE_MAX_DEVICES];
+// The one cache of the three kinds of table (eval, gradient, reverse): per device, keyed by the host stub of the kernel that fills the
+// table (`fill`, a __global__ taking the device table: one per module and element type); the first request on a device runs it and copies
+// the n entries back, every request copies them to `table`.
+hipError_t handler_table(const void *fill, size_t n, uint64_t *table) {
+    static std::map<const void *, std::vector<uint64_t>> caches[DE_MAX_DEVICES];
     static std::mutex mu; // contexts on several host threads may ask at once
     int dev = 0;
     { const hipError_t dst = handler_device_slot(&dev); if (dst != hipSuccess) return dst; }
     const std::lock_guard<std::mutex> lock(mu);
-    if (!caches[dev]) caches[dev].reset(new Cache());
-    Cache &c = *caches[dev];
-    const int k = dtype == DE_F32 ? (turbo ? 2 : 0) : 1;
-    if (!c.have[k]) {
-        hipError_t st = k == 0 ? fetch_handlers<float, false>(c.t[k]) : (k == 2 ? fetch_handlers<float, true>(c.t[k]) : fetch_handlers<double, false>(c.t[k]));
+    std::vector<uint64_t> &t = caches[dev][fill];
+    if (t.empty()) {
+        uint64_t *d = nullptr;
+        hipError_t st = hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(uint64_t));
         if (st != hipSuccess) return st;
-        c.have[k] = true;
+        std::vector<uint64_t> h(n);
+        void *args[] = {&d};
+        st = hipLaunchKernel(fill, dim3(1), dim3(1), args, 0, 0);
+        if (st == hipSuccess) st = hipMemcpy(h.data(), d, n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (st != hipSuccess) return st;
+        t.swap(h);
     }
-    for (int i = 0; i < (int)TOPX_TABLE; i++) table[i] = c.t[k][i];
+    std::copy(t.begin(), t.end(), table);
     return hipSuccess;
+}
+
+hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table) { // Float32, Float64, Float32 turbo (Float64 has no relaxed operators)
+    const void *const fill[3] = {reinterpret_cast<const void *>(&de_fill_handlers<float, false>), reinterpret_cast<const void *>(&de_fill_handlers<float, true>),
+                                 reinterpret_cast<const void *>(&de_fill_handlers<double, false>)};
+    return handler_table(fill[dtype == DE_F32 ? (turbo ? 1 : 0) : 2], TOPX_TABLE, table);
 }
 
 bool eval_uses_threaded() { return env_int("DE_EVAL_THREADED", 1) != 0; }

@@ -1,5 +1,6 @@
-// de_plan.h — what every eval kernel's launch shares: the scalar-load pointer types, the chunk plan, the blockIdx -> (tile, chunk) map and
-// the host's CU count.  Included by the threaded kernel's module (de_kernels.hip) and by the flat-switch interpreter (de_flat.h).
+// de_plan.h — what every kernel's launch shares: the scalar-load pointer types, the chunk plans (eval: chunk_plan / plan_chunks; gradient:
+// grad_chunk_plan, grad_flag_protocol), the blockIdx -> (tile, chunk) map and the host's CU count.  Included by the threaded kernel's module
+// (de_kernels.hip), by the flat-switch interpreter (de_flat.h) and by the gradient kernels (de_grad_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@ namespace de {
 typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
 typedef const DE_CONSTANT U32x4 *ConstU4Ptr;
 typedef const DE_CONSTANT int32_t *ConstI32Ptr;
+typedef const DE_CONSTANT int64_t *ConstI64Ptr;
 
 // Chunk plan of a launch over n trees and n_tiles sample tiles (host: plan_chunks; device: de_compact_live_kernel for the live trees):
 // chunks of <= tpc_max trees, more of them while the grid would not cover the chip `want_blocks` times, never fewer than 8 trees per chunk.
@@ -88,6 +90,33 @@ inline int32_t plan_tpc_max(int waves) {
 inline void plan_chunks(int64_t n_trees, int64_t n_tiles, int32_t *n_chunks_out, int32_t *tpc_out, int32_t *nc0_out = nullptr, int waves = 1) {
     chunk_plan(n_trees, n_tiles, plan_tpc_max(waves), (int64_t)cu_count() * 4 * 8, n_chunks_out, tpc_out, nc0_out);
     if (*n_chunks_out < 1) *n_chunks_out = 1;
+}
+
+// ---- the gradient kernels (launch_grad_kernel, de_grad_kernels.hip) -----------------------------------------------------------------
+// Chunk plan of a gradient launch over n trees, n_tiles sample tiles and `windows` gradient windows (grid.y): chunks of <= 32 trees, more of
+// them while the grid is below cus * 4 * 8 workgroups, never fewer than 4 trees per chunk; then the trees are spread evenly.  (Not
+// chunk_plan: other constants, no nc0.)  Plain arithmetic, the CU count is passed in.
+inline void grad_chunk_plan(int64_t n, int64_t n_tiles, int64_t windows, int64_t cus, int32_t *tpc_out, int32_t *n_chunks_out) {
+    *tpc_out = *n_chunks_out = 0;
+    if (n < 1 || n_tiles < 1 || windows < 1) return; // (an empty grid: the launch refuses it)
+    int64_t n_chunks = (n + 31) / 32;
+    const int64_t want_blocks = cus * 4 * 8;
+    if (n_tiles * n_chunks * windows < want_blocks) n_chunks = (want_blocks + n_tiles * windows - 1) / (n_tiles * windows);
+    const int64_t max_chunks = (n + 3) / 4;
+    if (n_chunks > max_chunks) n_chunks = max_chunks;
+    if (n_chunks < 1) n_chunks = 1;
+    const int64_t tpc = (n + n_chunks - 1) / n_chunks;
+    *tpc_out = (int32_t)tpc;
+    *n_chunks_out = (int32_t)((n + tpc - 1) / tpc);
+}
+// Flag protocol of a gradient launch that skips flagged trees (skip_flag_load, de_device_ops.h): these kernels write little, their L1 lines
+// go stale under 2 (reverse kernel 17.0 / 16.0 ms), so 1 (agent scope); 2 only for tiny chunks (many tiles on one flag line).
+// prio_cached — the one difference between the kernels: the FORWARD threaded kernel takes 2 when its launch has priority tiles (the flags
+// are then down before most workgroups first look, a stale line is rare and the cached protocol wins: fused loss gradient 6.65 -> 5.98 ms);
+// the reverse kernel keeps 1 (15.9 against 16.9 ms) and so does the flat one.  forced: DE_SKIP_PROTOCOL = 1 .. 3 (experiments), else 0.
+inline int32_t grad_flag_protocol(int32_t trees_per_chunk, bool prio_cached, int forced) {
+    if (forced >= 1 && forced <= 3) return forced;
+    return trees_per_chunk >= 8 && !prio_cached ? 1 : 2;
 }
 
 } // namespace de

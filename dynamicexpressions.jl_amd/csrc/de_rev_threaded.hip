@@ -27,8 +27,6 @@
 #include "de_grad_common.h"
 #include "de_bind.h"
 
-#include <cstring>
-
 #if !defined(DE_RT_T) || !defined(DE_RT_TAG)
 #error "compile with -DDE_RT_T=<float|double> -DDE_RT_TAG=<f|d>"
 #endif
@@ -398,23 +396,10 @@ __global__ void __launch_bounds__(GBLK) de_rev_threaded_kernel(const GArgs<T> a,
     const int64_t last = a.tile_range ? tile_range[2 * tm.tile + 1] : a.N - 1;
     const int F = a.F, R = a.rev_rows; // rows per wave
     {
-        const uint32_t Fu = (uint32_t)a.FX, total = (uint32_t)GBLK * Fu;
-        for (uint32_t e = tid; e < total; e += GBLK) {
-            const uint32_t j = e / Fu, f = e - j * Fu;
-            int64_t jj = base + j;
-            jj = jj < last ? jj : last;
-            rows[((j >> 6) * (uint32_t)R + f) * 64 + (j & 63)] = a.X[f + a.ldX * jj];
-        }
-    }
-    if (PARAMS) { // rows FX .. F: params[:, class of the sample] (src/ParametricExpression.jl:381-389), read through the caches
-        const uint32_t Pu = (uint32_t)(F - a.FX), total = (uint32_t)GBLK * Pu;
-        for (uint32_t e = tid; e < total; e += GBLK) {
-            const uint32_t j = e / Pu, q = e - j * Pu;
-            int64_t jj = base + j;
-            jj = jj < last ? jj : last;
-            const int64_t cl = clamp_class((a.classes_is_i64 ? reinterpret_cast<const int64_t *>(a.classes)[jj] : (int64_t) reinterpret_cast<const int32_t *>(a.classes)[jj]) - a.class_base, a.n_classes);
-            rows[((j >> 6) * (uint32_t)R + (uint32_t)a.FX + q) * 64 + (j & 63)] = a.params[q + a.ld_params * cl];
-        }
+        const uint32_t FX = (uint32_t)a.FX, Ru = (uint32_t)R;
+        const auto at = [Ru](uint32_t j, uint32_t f) { return ((j >> 6) * Ru + f) * 64 + (j & 63); };
+        stage_x_rows<T>(rows, a.X, a.ldX, FX, GBLK, base, last, at);
+        if (PARAMS) stage_param_rows<T>(rows, a.params, a.ld_params, a.classes, a.classes_is_i64, a.class_base, a.n_classes, FX, (uint32_t)F - FX, GBLK, base, last, at);
     }
     const int64_t j = base + tid, jj = j < last ? j : last;
     const T yv = a.y[jj];
@@ -469,15 +454,10 @@ __global__ void __launch_bounds__(GBLK) de_rev_threaded_kernel(const GArgs<T> a,
         }
         rpoison<T>(st.vpoison, st.x);
         { // loss term and the seed of the backward sweep
-            const T e = st.x - yv;
-            T l, lp;
-            if (a.loss_mode == 1 + DE_LOSS_L2) { l = wv * (e * e); lp = wv * (T(2) * e); }
-            else if (a.loss_mode == 1 + DE_LOSS_L1) { l = wv * M<T>::abs(e); lp = wv * jl_sign(e); }
-            else { l = wv * (st.x * yv); lp = wv * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
-            if (wv == T(0)) { l = T(0); lp = T(0); }
-            const T s = wave_sum_to_lane63(l);
+            const LossTerm<T> lt = loss_term<T>(a.loss_mode, st.x, yv, wv);
+            const T s = wave_sum_to_lane63(lt.l);
             if (RT_LANE() == 63) *RLDS(T, st.stage) = s;
-            st.lp = lp;
+            st.lp = lt.lp;
             st.x = T(1);
         }
         {   // backward sweep (instructions stored in execution order), ending in the tree's last record
@@ -494,104 +474,15 @@ __global__ void __launch_bounds__(GBLK) de_rev_threaded_kernel(const GArgs<T> a,
 
 } // module namespace
 
-hipError_t DE_RT_NAME(rev_thr_fetch_)(uint64_t *host_table) {
-    using namespace DE_RT_NAME(rtm_);
-    uint64_t *d = nullptr;
-    hipError_t st = hipMalloc(reinterpret_cast<void **>(&d), ROP_COUNT * sizeof(uint64_t));
-    if (st != hipSuccess) return st;
-    hipLaunchKernelGGL((de_rev_fill_handlers<DE_RT_T>), dim3(1), dim3(1), 0, 0, d);
-    st = hipMemcpy(host_table, d, ROP_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return st;
-}
-
-hipError_t DE_RT_NAME(rev_thr_launch_)(const GradArgs &ga, int group, hipStream_t stream) {
+// ---- host side: what this module exports; the launch is de_grad_kernels.hip launch_grad_kernel ---------------------------------------
+GradModule DE_RT_NAME(rev_thr_module_)() {
     using namespace DE_RT_NAME(rtm_);
     typedef DE_RT_T T;
-    static int rt_gcu = 0;
-    const EvalArgs &e = ga.e;
-    const GradArgs::RevGroup &grp = ga.rev_groups[group];
-    if (grp.n <= 0) return hipSuccess;
-    GArgs<T> a;
-    std::memset(&a, 0, sizeof a);
-    a.code = ga.rev_code;
-    a.code_off = ga.rev_code_off;
-    a.rev_mid = ga.rev_code_mid;
-    a.rev_rows = grp.rows;
-    a.rev_stage_cols = ga.rev_stage_cols;
-    a.rev_stage_rows = (int32_t)(((size_t)ga.rev_stage_cols * sizeof(T) + 64 * sizeof(T) - 1) / (64 * sizeof(T)));
-    a.X = static_cast<const T *>(e.X);
-    a.n_grad = ga.n_grad;
-    a.ok = e.ok;
-    a.params = static_cast<const T *>(e.params);
-    a.classes = e.classes;
-    a.N = e.N;
-    a.ldX = e.ldX;
-    a.ld_params = e.ld_params;
-    a.n_tiles = ga.rev_tile_range ? ga.rev_n_tiles : (e.N + GBLK - 1) / GBLK;
-    a.tile_range = ga.rev_tile_range;
-    a.FX = e.F;
-    a.F = e.F + (e.uses_params ? ga.P : 0); // leaf rows: X, then the parameters gathered by class
-    a.P = ga.P;
-    a.n_trees = grp.n;
-    a.n_all_trees = e.n_trees;
-    a.tree_ids = ga.rev_ids + grp.first;
-    a.n_slots = e.n_slots;
-    a.mode = ga.mode;
-    a.classes_is_i64 = e.classes_is_i64;
-    a.class_base = e.class_base;
-    a.n_classes = e.n_classes > 0 ? e.n_classes : 1;
-    a.uses_params = e.uses_params ? 1 : 0;
-    a.check = 1;
-    a.skip_flagged = e.skip_flagged ? 1 : 0;
-    a.diff_g0 = -1;
-    a.loss_mode = 1 + ga.loss->kind;
-    a.y = static_cast<const T *>(ga.loss->y);
-    a.w = static_cast<const T *>(ga.loss->w);
-    a.partial = static_cast<T *>(ga.loss->partial);
-    a.col_off = ga.col_off;
-    if (rt_gcu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) rt_gcu = prop.multiProcessorCount;
-        if (rt_gcu <= 0) rt_gcu = 256;
-    }
-    int64_t n_chunks = (grp.n + 31) / 32;
-    const int64_t want_blocks = (int64_t)rt_gcu * 4 * 8;
-    if (a.n_tiles * n_chunks < want_blocks) n_chunks = (want_blocks + a.n_tiles - 1) / a.n_tiles;
-    const int64_t max_chunks = (grp.n + 3) / 4;
-    if (n_chunks > max_chunks) n_chunks = max_chunks;
-    if (n_chunks < 1) n_chunks = 1;
-    a.trees_per_chunk = (int32_t)((grp.n + n_chunks - 1) / n_chunks);
-    if (a.skip_flagged) a.skip_flagged = a.trees_per_chunk >= 8 ? 1 : 2;
-    if (a.skip_flagged) { const char *pv = getenv("DE_SKIP_PROTOCOL"); if (pv && *pv >= '1' && *pv <= '3') a.skip_flagged = *pv - '0'; } // (experiments) // flag protocol (skip_flag_load, de_device_ops.h): these kernels write little, their L1 lines go stale under 2 (reverse kernel 17.0 / 16.0 ms); 2 only for tiny chunks (many tiles on one flag line)
-    a.n_chunks = (int32_t)((grp.n + a.trees_per_chunk - 1) / a.trees_per_chunk);
-    int64_t blocks = ((a.n_tiles + 7) / 8) * 8 * a.n_chunks;
-    a.prio = nullptr;
-    a.n_prio = a.n_prio_blocks = a.prio_shift = 0;
-    if (a.skip_flagged && ga.prio_ready && !ga.rev_tile_range) blocks += gprio_setup(a, e.prio_keys, e.F, GBLK); // (class-aligned tiles: no)
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    const size_t lds = 4 * (size_t)a.rev_rows * 64 * sizeof(T);
-    void (*kern)(const GArgs<T>, uint64_t, uint32_t) = e.uses_params ? de_rev_threaded_kernel<T, true> : de_rev_threaded_kernel<T, false>;
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (st != hipSuccess) return st;
-    }
-    if (a.n_prio) { // the priority tiles as a launch of their own in front, in short chunks (de_kernels.hip launch_threaded_t: no blind first wave)
-        GArgs<T> pa = a;
-        pa.trees_per_chunk = 4;
-        pa.n_chunks = (int32_t)((grp.n + 3) / 4);
-        pa.n_prio_blocks = (uint32_t)(((int64_t)pa.n_prio * pa.n_chunks + 7) / 8 * 8);
-        hipLaunchKernelGGL(kern, dim3(pa.n_prio_blocks), dim3(GBLK), lds, stream, pa, ga.rev_handler_base, ga.rev_param_off);
-        const hipError_t ps = hipGetLastError();
-        if (ps != hipSuccess) return ps;
-        blocks -= a.n_prio_blocks;
-        a.n_prio = a.n_prio_blocks = 0;
-        a.prio = nullptr;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(GBLK), lds, stream, a, ga.rev_handler_base, ga.rev_param_off);
-    return hipGetLastError();
+    GradModule m = {};
+    m.fill = reinterpret_cast<const void *>(&de_rev_fill_handlers<T>);
+    m.kernel[1][0] = reinterpret_cast<const void *>(&de_rev_threaded_kernel<T, true>);
+    m.kernel[0][0] = reinterpret_cast<const void *>(&de_rev_threaded_kernel<T, false>);
+    return m;
 }
 
 } // namespace de
