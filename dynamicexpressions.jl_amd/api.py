@@ -47,6 +47,7 @@ EXPORTS = [
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
     "de_program_set_consts", "de_program_update", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
     "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
+    "de_loss_spec_check", "de_eval_loss_ex", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
@@ -66,6 +67,27 @@ class UncertifiedFlag(DeviceError):
 class ParamArgs(C.Structure):
     _fields_ = [("params", C.c_void_p), ("ld_params", C.c_int64), ("n_classes", C.c_int64),
                 ("classes", C.c_void_p), ("classes_is_i64", C.c_int32), ("class_base", C.c_int32)]
+
+
+class LossSpec(C.Structure):
+    """``de_loss_spec_t``: a loss kind of ``de_loss_kind_t`` and its one scalar parameter."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("param", C.c_double)]
+
+
+# de_loss_kind_t (include/de_hip.h): name -> enum value.  "pullback" belongs to the gradient entry points only.
+LOSS_KINDS = {"L2": 0, "L1": 1, "pullback": 2, "huber": 16, "logcosh": 17, "l1_eps": 18, "l2_eps": 19, "quantile": 20, "lp": 21,
+              "logit_dist": 22, "logit_margin": 23, "l1_hinge": 24}
+
+
+def loss_spec(loss: str, loss_param: float = 0.0, with_gradient: bool = True) -> LossSpec:
+    """The ``LossSpec`` of a loss name and its parameter, checked by ``de_loss_spec_check``: an unknown name is a ``KeyError`` (and so is
+    "pullback" without a gradient), a parameter that is not finite or outside the kind's range a ``ValueError``."""
+    if loss == "pullback" and not with_gradient:
+        raise KeyError(loss)
+    spec = LossSpec(LOSS_KINDS[loss], 0, float(loss_param))
+    if library().de_loss_spec_check(C.byref(spec), int(with_gradient)) != 0:
+        raise ValueError(f"loss {loss!r}: parameter {loss_param!r} is not finite or outside the kind's range (include/de_hip.h de_loss_kind_t)")
+    return spec
 
 
 _lib: Optional[C.CDLL] = None
@@ -140,6 +162,10 @@ def library() -> C.CDLL:
     lib.de_eval_loss.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.c_int32, vp, vp]
     lib.de_eval_loss_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.c_int32, vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.de_loss_spec_check.argtypes = [C.POINTER(LossSpec), C.c_int]
+    lib.de_eval_loss_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), vp, vp]
+    lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
+    lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
     lib.de_eval_diff.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
     lib.de_eval_pullback_dX.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, vp, vp]
@@ -733,13 +759,15 @@ class Population:
                                                          ok.ctypes.data, cert.ctypes.data, mx.ctypes.data))
         return ok.astype(bool), cert.astype(bool), mx
 
-    def eval_loss(self, X, y, weights=None, loss: str = "L2", params=None, classes=None, class_base: int = 1):
+    def eval_loss(self, X, y, weights=None, loss: str = "L2", params=None, classes=None, class_base: int = 1, loss_param: float = 0.0):
         """Fused ``sum_j w_j * l(tree_t(X[:, j]) - y[j])`` for every tree (l = abs2 for "L2", abs for
         "L1") without materialising the [n_trees, N] output: what the reference's optimisation
         consumers compute right after eval_tree_array (``sum(abs2, tree(X, operators) .- y)``,
-        test/test_optim.jl:95,99).  Returns (loss[n_trees], ok[n_trees]); loss is NaN where not ok."""
+        test/test_optim.jl:95,99).  ``loss`` may also name a parameterised kind of ``LOSS_KINDS`` ("huber", "logcosh", "l1_eps", "l2_eps",
+        "quantile", "lp", "logit_dist", "logit_margin", "l1_hinge"; include/de_hip.h de_loss_kind_t has the formulas) with its parameter
+        in ``loss_param``.  Returns (loss[n_trees], ok[n_trees]); loss is NaN where not ok."""
         self._refuse_f16("eval_loss")
-        kind = {"L2": 0, "L1": 1}[loss]
+        spec = loss_spec(loss, loss_param, with_gradient=False)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()
@@ -770,24 +798,24 @@ class Population:
             import torch
             out = torch.empty(self.n_trees, dtype=keep_x.dtype, device=keep_x.device)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
-            self.ctx.check(lib.de_eval_loss(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
-                                            yp, wp, kind, out.data_ptr(), ok.data_ptr()))
+            self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
+                                               yp, wp, C.byref(spec), out.data_ptr(), ok.data_ptr()))
             return out, ok.bool()
         out = np.empty(self.n_trees, dtype=self.dtype)
         ok = np.zeros(self.n_trees, dtype=np.uint8)
-        self.ctx.check(lib.de_eval_loss(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
-                                        yp, wp, kind, out.ctypes.data, ok.ctypes.data))
+        self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
+                                           yp, wp, C.byref(spec), out.ctypes.data, ok.ctypes.data))
         return out, ok.astype(bool)
 
     def eval_loss_grad(self, X, y, weights=None, loss: str = "L2", variable: Union[bool, str] = False,
-                       params=None, classes=None, class_base: int = 1):
+                       params=None, classes=None, class_base: int = 1, loss_param: float = 0.0):
         """Fused loss and its gradient w.r.t. the rows ``variable`` selects (default: the constants) —
         the body of the reference's optimiser callback (test/test_optim.jl:42-51: ``G[i] = sum_j
         2(yhat_j - y_j) * dyhat_dconstants[i, j]``) without the [n_grad, N] Jacobian.  ``loss="pullback"``
-        treats ``y`` as the cotangent dY of the ChainRules pullback (src/ChainRules.jl:56-77).
-        Returns (loss[n_trees], [dloss_t[n_grad_t] per tree], ok)."""
+        treats ``y`` as the cotangent dY of the ChainRules pullback (src/ChainRules.jl:56-77); the parameterised kinds of ``eval_loss``
+        take their parameter in ``loss_param``.  Returns (loss[n_trees], [dloss_t[n_grad_t] per tree], ok)."""
         self._refuse_f16("eval_loss_grad")
-        kind = {"L2": 0, "L1": 1, "pullback": 2}[loss]
+        spec = loss_spec(loss, loss_param)
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -825,18 +853,18 @@ class Population:
             lo = torch.empty(self.n_trees, dtype=keep_x.dtype, device=keep_x.device)
             dl = torch.empty(total, dtype=keep_x.dtype, device=keep_x.device)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
-            self.ctx.check(lib.de_eval_loss_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode,
-                                                 yp, wp, kind, lo.data_ptr(), dl.data_ptr(), offs.ctypes.data, ok.data_ptr()))
+            self.ctx.check(lib.de_eval_loss_grad_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode,
+                                                    yp, wp, C.byref(spec), lo.data_ptr(), dl.data_ptr(), offs.ctypes.data, ok.data_ptr()))
             return lo, [self._combine_rows(t, d, mode) for t, d in enumerate(torch.split(dl[:int(offs[-1])], ng.tolist()))], ok.bool()
         lo = np.empty(self.n_trees, dtype=self.dtype)
         dl = np.empty(total, dtype=self.dtype)
         ok = np.zeros(self.n_trees, dtype=np.uint8)
-        self.ctx.check(lib.de_eval_loss_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode,
-                                             yp, wp, kind, lo.ctypes.data, dl.ctypes.data, offs.ctypes.data, ok.ctypes.data))
+        self.ctx.check(lib.de_eval_loss_grad_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode,
+                                                yp, wp, C.byref(spec), lo.ctypes.data, dl.ctypes.data, offs.ctypes.data, ok.ctypes.data))
         return lo, [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))], ok.astype(bool)
 
     def eval_loss_grad_by_class(self, X, y, params, classes, weights=None, loss: str = "L2",
-                                variable: Union[bool, str] = "both", class_base: int = 1, grouped: bool = False):
+                                variable: Union[bool, str] = "both", class_base: int = 1, grouped: bool = False, loss_param: float = 0.0):
         """Fused loss + gradient of a parametric population with the parameter rows reduced by class:
         returns (loss[n_trees], [dloss_t], dparams[n_trees, n_params, n_classes], ok) where
         ``dparams[t]`` is the gradient w.r.t. the parameter MATRIX — Zygote's
@@ -845,7 +873,7 @@ class Population:
         first (a stable sort, done here unless ``grouped=True`` says the caller already did: classes are
         part of the dataset, so a search loop orders it once)."""
         self._refuse_f16("eval_loss_grad_by_class")
-        kind = {"L2": 0, "L1": 1, "pullback": 2}[loss]
+        spec = loss_spec(loss, loss_param)
         mode = _grad_mode(variable)
         is_t = _is_torch(X)
         if is_t:
@@ -906,14 +934,14 @@ class Population:
             lo, dl = torch.empty(self.n_trees, **kw), torch.empty(total, **kw)
             dp = torch.empty((self.n_trees, n_cls, P), **kw)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
-            self.ctx.check(lib.de_eval_loss_grad_by_class(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa), mode, yp, wp, kind,
+            self.ctx.check(lib.de_eval_loss_grad_by_class_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa), mode, yp, wp, C.byref(spec),
                                                           starts.ctypes.data, lo.data_ptr(), dl.data_ptr(), offs.ctypes.data,
                                                           dp.data_ptr(), ok.data_ptr()))
             return lo, list(torch.split(dl[:int(offs[-1])], ng.tolist())), dp.transpose(1, 2), ok.bool()
         lo, dl = np.empty(self.n_trees, dtype=self.dtype), np.empty(total, dtype=self.dtype)
         dp = np.empty((self.n_trees, n_cls, P), dtype=self.dtype)
         ok = np.zeros(self.n_trees, dtype=np.uint8)
-        self.ctx.check(lib.de_eval_loss_grad_by_class(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa), mode, yp, wp, kind,
+        self.ctx.check(lib.de_eval_loss_grad_by_class_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa), mode, yp, wp, C.byref(spec),
                                                       starts.ctypes.data, lo.ctypes.data, dl.ctypes.data, offs.ctypes.data,
                                                       dp.ctypes.data, ok.ctypes.data))
         return lo, np.split(dl[:int(offs[-1])], offs[1:-1]), dp.transpose(0, 2, 1), ok.astype(bool)

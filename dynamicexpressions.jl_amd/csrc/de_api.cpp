@@ -506,6 +506,10 @@ bool dataset_keys(const de_ctx *c, int dtype, const void *X, int64_t N, int64_t 
     return true;
 }
 
+int de_loss_spec_check(const de_loss_spec_t *spec, int with_gradient) {
+    char buf[160];
+    return loss_spec_problem(spec, with_gradient, buf, sizeof buf) ? DE_ERR_INVALID_ARG : DE_OK;
+}
 const char *de_last_error(de_ctx_t *c) { return c ? c->err.c_str() : "null context"; }
 
 int de_ctx_last_kernel_ms(de_ctx_t *c, float *ms) {
@@ -577,3 +581,29 @@ int64_t de_host_pool_selftest(int64_t n, int32_t *n_ranges) {
 // records, offsets, constant sites, fold list, flags, and the auxiliary program's) — the per-tree passes run on a pool of host threads
 // and must build what one thread builds (tests/test_gpu_round5.py: DE_HOST_THREADS=1 against the default).  FNV-1a, 64 bits.
 } // extern "C"
+
+// The table of include/de_hip.h de_loss_kind_t: name, whether the kind has a parameter, and the parameter's range.
+const char *loss_spec_problem(const de_loss_spec_t *spec, int with_gradient, char *buf, size_t cap) {
+    if (!spec) { std::snprintf(buf, cap, "null loss spec"); return buf; }
+    if (spec->reserved != 0) { std::snprintf(buf, cap, "loss spec (loss_kind %d): reserved must be 0", (int)spec->kind); return buf; }
+    const double v = spec->param;
+    const char *name = nullptr, *range = nullptr;
+    bool good = true;
+    switch (spec->kind) {
+    case DE_LOSS_L2: case DE_LOSS_L1: return nullptr;
+    case DE_LOSS_PULLBACK:
+        if (with_gradient) return nullptr;
+        std::snprintf(buf, cap, "unknown loss_kind %d (DE_LOSS_PULLBACK belongs to the gradient entry points)", (int)spec->kind);
+        return buf;
+    case DE_LOSS_HUBER: name = "DE_LOSS_HUBER"; range = "delta > 0"; good = v > 0.0; break;
+    case DE_LOSS_L1_EPS: name = "DE_LOSS_L1_EPS"; range = "eps >= 0"; good = v >= 0.0; break;
+    case DE_LOSS_L2_EPS: name = "DE_LOSS_L2_EPS"; range = "eps >= 0"; good = v >= 0.0; break;
+    case DE_LOSS_QUANTILE: name = "DE_LOSS_QUANTILE"; range = "tau in [0, 1]"; good = v >= 0.0 && v <= 1.0; break;
+    case DE_LOSS_LP: name = "DE_LOSS_LP"; range = "p >= 1"; good = v >= 1.0; break;
+    case DE_LOSS_LOGCOSH: case DE_LOSS_LOGIT_DIST: case DE_LOSS_LOGIT_MARGIN: case DE_LOSS_L1_HINGE: return nullptr; // (no parameter: ignored)
+    default: std::snprintf(buf, cap, "unknown loss_kind %d", (int)spec->kind); return buf;
+    }
+    if (good && std::isfinite(v)) return nullptr;
+    std::snprintf(buf, cap, "%s: parameter %g is not finite or outside its range (%s)", name, v, range);
+    return buf;
+}

@@ -50,6 +50,7 @@ int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, 
 struct LossReq {
     const void *y, *w;
     int32_t kind;
+    double param; // de_loss_spec_t::param
     void *loss;
 };
 
@@ -146,7 +147,20 @@ int de_eval_loss(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t
     if (loss_kind != DE_LOSS_L2 && loss_kind != DE_LOSS_L1) return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", loss_kind);
     if (!p->threaded)
         return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss needs the LDS-tiled kernel (feature matrix too wide for this build)");
-    const LossReq lr{y, w, loss_kind, loss};
+    const de_loss_spec_t spec{loss_kind, 0, 0.0};
+    return de_eval_loss_ex(c, p, X, N, ldX, pa, y, w, &spec, loss, ok);
+}
+int de_eval_loss_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                    const void *y, const void *w, const de_loss_spec_t *spec, void *loss, uint8_t *ok) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (N < 0 || !ok || (p->n_trees > 0 && (!loss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    char why[160];
+    if (loss_spec_problem(spec, 0, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+    if (!p->threaded)
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss needs the LDS-tiled kernel (feature matrix too wide for this build)");
+    const LossReq lr{y, w, spec->kind, spec->param, loss};
     DE_NOTHROW(c, eval_impl(c, p, X, N, ldX, pa, nullptr, N, ok, &lr));
 }
 
@@ -203,6 +217,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         la.y = sY.dev;
         la.w = lr->w ? sW.dev : nullptr;
         la.kind = lr->kind;
+        la.param = lr->param;
         la.partial = c->sPartial.p;
         la.seg_sum = c->sSeg.p;
         la.loss = sLoss.dev;

@@ -1109,8 +1109,8 @@ struct ByClassPlan {
     bool done;
 };
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                          int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan);
+                          int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false);
 // DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
 static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
@@ -1129,18 +1129,27 @@ int de_eval_loss_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, in
                       int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
                       const int64_t *dloss_offsets, uint8_t *ok) {
     DE_REFUSE_F16("de_eval_loss_grad");
-    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, loss_kind, loss, dloss, dloss_offsets, ok, nullptr));
+    const de_loss_spec_t spec{loss_kind, 0, 0.0}; // (de_eval_loss_grad_ex, held to the three kinds this entry point has always taken)
+    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, loss, dloss, dloss_offsets, ok, nullptr, true));
+}
+int de_eval_loss_grad_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                         int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
+                         const int64_t *dloss_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_grad");
+    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr));
 }
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                          int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan) {
+                          int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (N < 0 || !ok || (p->n_trees > 0 && (!dloss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
     if (mode != DE_GRAD_VARIABLE && mode != DE_GRAD_CONSTANT && mode != DE_GRAD_BOTH) return fail(c, DE_ERR_INVALID_ARG, "bad gradient mode");
-    if (loss_kind != DE_LOSS_L2 && loss_kind != DE_LOSS_L1 && loss_kind != DE_LOSS_PULLBACK)
-        return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", loss_kind);
+    if (first_kinds_only && spec->kind != DE_LOSS_L2 && spec->kind != DE_LOSS_L1 && spec->kind != DE_LOSS_PULLBACK)
+        return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", (int)spec->kind);
+    char why[160];
+    if (loss_spec_problem(spec, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
     int rc = check_param_args(c, p, pa, N);
     if (rc != DE_OK) return rc;
     if (p->n_trees == 0) return DE_OK;
@@ -1248,7 +1257,8 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     std::memset(&la, 0, sizeof la);
     la.y = sY.dev;
     la.w = w ? sW.dev : nullptr;
-    la.kind = loss_kind;
+    la.kind = spec->kind;
+    la.param = spec->param;
     la.partial = c->sPartial.p;
     la.seg_sum = c->sSeg.p;
     la.loss = loss ? sLoss.dev : nullptr;
@@ -1336,23 +1346,36 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
 }
 
 static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
-                               const de_param_args_t *pa, int mode, const void *y, const void *w, int32_t loss_kind,
+                               const de_param_args_t *pa, int mode, const void *y, const void *w, const de_loss_spec_t *spec,
                                const int64_t *class_starts, void *loss, void *dloss, const int64_t *dloss_offsets,
-                               void *dparams, uint8_t *ok);
+                               void *dparams, uint8_t *ok, bool first_kinds_only = false);
 int de_eval_loss_grad_by_class(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
                                const de_param_args_t *pa, int mode, const void *y, const void *w, int32_t loss_kind,
                                const int64_t *class_starts, void *loss, void *dloss, const int64_t *dloss_offsets,
                                void *dparams, uint8_t *ok) {
     DE_REFUSE_F16("de_eval_loss_grad_by_class");
-    DE_NOTHROW(c, by_class_impl(c, p, X, N, ldX, pa, mode, y, w, loss_kind, class_starts, loss, dloss, dloss_offsets, dparams, ok));
+    const de_loss_spec_t spec{loss_kind, 0, 0.0};
+    DE_NOTHROW(c, by_class_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, class_starts, loss, dloss, dloss_offsets, dparams, ok, true));
+}
+int de_eval_loss_grad_by_class_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
+                                  const de_param_args_t *pa, int mode, const void *y, const void *w, const de_loss_spec_t *spec,
+                                  const int64_t *class_starts, void *loss, void *dloss, const int64_t *dloss_offsets,
+                                  void *dparams, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_grad_by_class");
+    DE_NOTHROW(c, by_class_impl(c, p, X, N, ldX, pa, mode, y, w, spec, class_starts, loss, dloss, dloss_offsets, dparams, ok));
 }
 static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
-                               const de_param_args_t *pa, int mode, const void *y, const void *w, int32_t loss_kind,
+                               const de_param_args_t *pa, int mode, const void *y, const void *w, const de_loss_spec_t *spec,
                                const int64_t *class_starts, void *loss, void *dloss, const int64_t *dloss_offsets,
-                               void *dparams, uint8_t *ok) {
+                               void *dparams, uint8_t *ok, bool first_kinds_only) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (p->n_params <= 0 || !pa) return fail(c, DE_ERR_INVALID_ARG, "not a parametric population (n_params = 0 or no parameter arguments)");
+    // the spec first, as loss_grad_impl: before any reservation or copy, and whatever path (one pass, per class, no tree, no sample) follows
+    if (first_kinds_only && spec && spec->kind != DE_LOSS_L2 && spec->kind != DE_LOSS_L1 && spec->kind != DE_LOSS_PULLBACK)
+        return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", (int)spec->kind);
+    char why[160];
+    if (loss_spec_problem(spec, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
     if (mode != DE_GRAD_VARIABLE && mode != DE_GRAD_BOTH)
         return fail(c, DE_ERR_INVALID_ARG, "by-class reduction needs a mode with parameter rows (DE_GRAD_VARIABLE / DE_GRAD_BOTH)");
     if (!pa->params || !pa->classes || pa->ld_params < p->n_params || pa->n_classes <= 0)
@@ -1395,8 +1418,8 @@ static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
         const char *env1 = getenv("DE_BY_CLASS_ONE_PASS");
         if (!(env1 && *env1 == '0') && N > 0) {
             c->nested++;
-            const int rc1 = loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, loss_kind, c->sBcLoss.p, c->sBcDloss.p, dloss_offsets,
-                                           static_cast<uint8_t *>(c->sBcOk.p), &plan);
+            const int rc1 = loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, c->sBcLoss.p, c->sBcDloss.p, dloss_offsets,
+                                           static_cast<uint8_t *>(c->sBcOk.p), &plan, first_kinds_only);
             c->nested--;
             if (rc1 != DE_OK) return rc1;
             shared_ok = plan.done;
@@ -1415,9 +1438,9 @@ static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
         const int64_t j0 = class_starts[k], n = class_starts[k + 1] - j0;
         de_param_args_t sub = *pa;
         sub.classes = static_cast<const char *>(pa->classes) + (size_t)j0 * cls_es;
-        rc = de_eval_loss_grad(c, p, static_cast<const char *>(X) + (size_t)j0 * (size_t)ldX * es, n, ldX, &sub, mode,
+        rc = de_eval_loss_grad_ex(c, p, static_cast<const char *>(X) + (size_t)j0 * (size_t)ldX * es, n, ldX, &sub, mode,
                                y ? static_cast<const char *>(y) + (size_t)j0 * es : nullptr,
-                               w ? static_cast<const char *>(w) + (size_t)j0 * es : nullptr, loss_kind,
+                               w ? static_cast<const char *>(w) + (size_t)j0 * es : nullptr, spec,
                                static_cast<char *>(c->sBcLoss.p) + (size_t)k * (size_t)p->n_trees * es,
                                static_cast<char *>(c->sBcDloss.p) + (size_t)k * (size_t)span * es, dloss_offsets,
                                static_cast<uint8_t *>(c->sBcOk.p) + (size_t)k * (size_t)p->n_trees);

@@ -279,6 +279,9 @@ bool host_pool_run(int n, const std::function<void(int)> &job);
 unsigned host_threads_for(int64_t n, int64_t grain);
 }
 
+// de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)
+const char *loss_spec_problem(const de_loss_spec_t *spec, int with_gradient, char *buf, size_t cap);
+
 // Bytes of one element of a dtype's buffers, and element k of such a buffer as / from double (binary16 rounds to nearest even).
 static inline bool is_complex_io(int dtype) { return dtype == DE_CF32 || dtype == DE_CF64; }
 static inline size_t dtype_bytes(int dtype) { return dtype == DE_CF64 ? 16 : (dtype == DE_F64 || dtype == DE_CF32) ? 8 : dtype == DE_F16 ? 2 : 4; }

@@ -10,6 +10,7 @@
 
 #include "de_device_ops.h"
 #include "de_kernels.h"
+#include "de_loss_kinds.h"
 #include "de_plan.h"
 
 namespace de {
@@ -55,6 +56,7 @@ template <typename T> struct GArgs {
     // runs every fourth tree of the chunk through stream variant w (var_stride records apart); tiles are 64 x VS samples
     int32_t share;
     int64_t var_stride;
+    T loss_param; // the parameter of a parameterised loss kind (de_loss_kinds.h), in T; 0 for the kinds that have none
 };
 
 // Early exit at tree granularity (src/Evaluate.jl:26-32, src/EvaluateDerivative.jl:230-243: the reference returns at the first
@@ -272,14 +274,18 @@ __device__ __forceinline__ void stage_param_rows(T *rows, const T *params, int64
 }
 
 // Loss term of one sample — value x, target yv, weight wv —: l = w * l(x - y) and lp = w * l'(x - y), the factor of the pullback.
-// loss_mode = 1 + de_loss_kind; weight 0 (and samples past N) really excludes the sample.
+// loss_mode = 1 + de_loss_kind; weight 0 (and samples past N) really excludes the sample.  p = GArgs::loss_param: the parameter of the
+// kinds of de_loss_kinds.h (wave-uniform dispatch on loss_mode, the three first kinds first).
 template <typename T> struct LossTerm { T l, lp; };
-template <typename T> __device__ __forceinline__ LossTerm<T> loss_term(int loss_mode, T x, T yv, T wv) {
+// (out of line: the table's transcendental arms stay out of the kernels' and epilogues' own code, which L2 / L1 / PULLBACK run as before)
+template <typename T> __device__ __noinline__ LossKindTerm<T> loss_kind_term_ool(int kind, T x, T yv, T p) { return loss_kind_term<T>(kind, x, yv, p); }
+template <typename T> __device__ __forceinline__ LossTerm<T> loss_term(int loss_mode, T x, T yv, T wv, T p) {
     const T e = x - yv;
     LossTerm<T> r;
     if (loss_mode == 1 + DE_LOSS_L2) { r.l = wv * (e * e); r.lp = wv * (T(2) * e); }
     else if (loss_mode == 1 + DE_LOSS_L1) { r.l = wv * M<T>::abs(e); r.lp = wv * jl_sign(e); }
-    else { r.l = wv * (x * yv); r.lp = wv * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
+    else if (loss_mode <= 1 + DE_LOSS_PULLBACK) { r.l = wv * (x * yv); r.lp = wv * yv; } // DE_LOSS_PULLBACK: y holds the cotangent dY
+    else { const LossKindTerm<T> k = loss_kind_term_ool<T>(loss_mode - 1, x, yv, p); r.l = wv * k.l; r.lp = wv * k.lp; }
     if (wv == T(0)) { r.l = T(0); r.lp = T(0); }
     return r;
 }

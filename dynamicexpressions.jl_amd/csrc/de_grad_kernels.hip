@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
             DE_UNROLL for (int k = 0; k < GC; k++) poison = M<T>::fma(g0 + k < G ? d[k] : T(0), T(0), poison); // real rows only
         }
         if (a.loss_mode) {
-            const LossTerm<T> lt = loss_term<T>(a.loss_mode, x, yv, wv);
+            const LossTerm<T> lt = loss_term<T>(a.loss_mode, x, yv, wv, a.loss_param);
             const int64_t n_cols = col_off[a.n_trees];
             T *__restrict__ pp = a.partial + ((int64_t)tm.tile * n_cols + col_off[tree]) * 4 + (tid >> 6);
             if (g0 == 0) {
@@ -304,6 +304,7 @@ template <typename T> static GArgs<T> make_gargs(const GradArgs &ga) {
     a.diff_g0 = -1;
     if (ga.loss) {
         a.loss_mode = 1 + ga.loss->kind;
+        a.loss_param = (T)ga.loss->param;
         a.y = static_cast<const T *>(ga.loss->y);
         a.w = static_cast<const T *>(ga.loss->w);
         a.partial = static_cast<T *>(ga.loss->partial);

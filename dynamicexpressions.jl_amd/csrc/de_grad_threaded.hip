@@ -363,7 +363,7 @@ template <typename T, int GC> __global__ void de_grad_fill_handlers(uint64_t *t)
 // (taking the address of the kernel-argument struct would make every load from it look divergent): nothing
 // of the epilogue stays live in VGPRs across the handler calls of the interpreter loop.
 template <typename T, int GC, bool SHARE>
-__device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const T *w, T *pp, int64_t N, int loss_mode, int G, int g0, int64_t tile) {
+__device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const T *w, T *pp, int64_t N, int loss_mode, T loss_param, int G, int g0, int64_t tile) {
     // pp = the partial sums of the (tile of 256 x VS samples, tree) pair this wave's samples belong to: [1 + n_grad][4 waves]
     // (shared leaf rows: `tile` counts 64 x VS samples — a quarter of such a tile, entry tile & 3 of its four)
     constexpr int TILE = GBLK * VS, WSAMP = 64 * VS;
@@ -376,7 +376,7 @@ __device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const
         const int64_t jj = j < last ? j : last;
         const T yv = y[jj];
         wv[i] = j <= last ? (w ? w[jj] : T(1)) : T(0);
-        const LossTerm<T> lt = loss_term<T>(loss_mode, st.x[i], yv, wv[i]);
+        const LossTerm<T> lt = loss_term<T>(loss_mode, st.x[i], yv, wv[i], loss_param);
         lp[i] = lt.lp;
         l += lt.l;
     }
@@ -543,7 +543,7 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
         DE_UNROLL for (int k = 0; k < GC; k++) gpoison<T>(poison, g0 + k < G ? st.d[k] : lv_splat<T>(T(0)));
         if (a.loss_mode) {
             const int64_t n_cols = col_off[a.n_all_trees];
-            g_epilogue_loss<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, a.loss_mode, G, g0, (int64_t)tm.tile);
+            g_epilogue_loss<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, a.loss_mode, a.loss_param, G, g0, (int64_t)tm.tile);
         } else {
             g_epilogue_store<T, GC, SHARE>(st, a.out ? a.out + (int64_t)tree * a.ld_out : nullptr, a.grad + grad_off[tree], a.N, G, g0, (int64_t)tm.tile, stage0);
         }

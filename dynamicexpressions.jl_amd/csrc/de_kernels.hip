@@ -41,6 +41,7 @@
 #include "de_bind.h"
 #include "de_device_ops.h"
 #include "de_kernels.h"
+#include "de_loss_kinds.h"
 #include "de_plan.h"
 #include "de_real_vec.h"
 
@@ -94,6 +95,9 @@ template <typename T> struct KArgs {
     // list (wave w: + (w - 1) * DE_SKIPLIST_BYTES; wave 0 keeps the list at 0), behind the rows.
     int64_t var_stride;
     uint32_t list_off;
+    // fused loss, parameterised kinds (loss_kind >= DE_LOSS_HUBER; de_loss_kinds.h): the kind's parameter.  The LOSS kernel writes it to
+    // LDS (LossParamLds) before the first chain call — a handler has no kernel arguments (h_tree_end_loss)
+    T loss_param;
 };
 
 
@@ -252,7 +256,15 @@ enum : uint32_t { HF_SLOW_STORE = 1u << 30, HF_NO_STORE = 1u << 29, HF_VALID_MAS
                   // ... of a full tile without weights: sum of e^2 / |e| without the per-sample weight selects (14 instead of ~40 VALU instructions
                   // per tree and wavefront: the fused loss was SLOWER than the eval it replaces, 75 cycles per tree-wave of loss arithmetic
                   // against one store)
-                  HF_LOSS_PLAIN = 1u << 25 };
+                  HF_LOSS_PLAIN = 1u << 25,
+                  // fused loss, a parameterised kind (de_loss_kinds.h): HF_LOSS_KIND INSTEAD of HF_LOSS (the bit of HF_LOSS_L1, which says this
+                  // without HF_LOSS) and the de_loss_kind value (16 .. 31) in the bits of HF_VALID_MASK, which only the ragged STORE reads.
+                  // h_tree_end_slow hands such a tree's end to h_tree_end_loss; HF_LOSS_PLAIN as above
+                  // (bits 10 .. 31 are all taken, so the marker SHARES bit 26: it means "L1" only together with HF_LOSS and "a parameterised
+                  // kind" only without it; a loss launch sets exactly one of the two, and h_tree_end_slow tests HF_LOSS first)
+                  HF_LOSS_KIND = 1u << 26, HF_LOSS_KIND_MASK = 0x1Fu };
+static_assert(HF_LOSS_KIND == HF_LOSS_L1 && (HF_LOSS_KIND & HF_LOSS) == 0, "bit 26 is read as a parameterised kind only where HF_LOSS is clear");
+static_assert((HF_LOSS_KIND_MASK & ~HF_VALID_MASK) == 0 && DE_LOSS_L1_HINGE <= (int)HF_LOSS_KIND_MASK, "the kind travels in store-only bits of flags");
 template <typename T> __device__ __forceinline__ HandlerFn<T> arg_next(uint32_t w1, uint64_t w23);
 template <> __device__ __forceinline__ HandlerFn<float> arg_next<float>(uint32_t, uint64_t w23) { return reinterpret_cast<HandlerFn<float>>(w23); }
 template <> __device__ __forceinline__ HandlerFn<double> arg_next<double>(uint32_t w1, uint64_t) {
@@ -371,6 +383,42 @@ template <typename T> __device__ __noinline__ HState<T> h_tree_skip(HCHAIN_ARGS)
 #define DE_OUT_STORE(VT, PTR, VAL) (*reinterpret_cast<__attribute__((address_space(1))) VT *>(PTR) = (VAL))
 #endif
 typedef __attribute__((address_space(1))) char *GPtr; // global, not flat: a flat store also ties up lgkmcnt
+// The parameter of a parameterised loss kind reaches the end of a tree through LDS: bytes 8 .. 15 of the padding vector behind row 0 (the
+// kernel's mask_slot uses bytes 0 .. 7; no lane's vector lies there), written by the LOSS kernel from KArgs::loss_param.
+template <typename T> struct LossParamLds { static constexpr uint32_t ADDR = DE_SKIPLIST_BYTES + (uint32_t)(DE_TBLK * TG<T>::G) * 16u + 8u; };
+__device__ __forceinline__ float lds_uniform_load(const __attribute__((address_space(3))) float *q) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(*q)));
+}
+__device__ __forceinline__ double lds_uniform_load(const __attribute__((address_space(3))) double *q) {
+    const long long b = __double_as_longlong(*q);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// The end of a tree in a fused-loss launch of a PARAMETERISED kind (flags & HF_LOSS_KIND; h_tree_end_slow tail-calls it): the same
+// partial as there — sum_j w_j * l_j over this wave's samples -> partial[tile, tree, wave] — with l from the table of de_loss_kinds.h.
+// The kind is wave-uniform (a scalar switch); HF_LOSS_PLAIN (a full tile without weights) drops the weight selects as it does for L2 / L1.
+template <typename T> __device__ __noinline__ HState<T> h_tree_end_loss(HCHAIN_ARGS) { // la = the tree's index
+    constexpr int VW = VecOf<T>::W;
+    const U32x4 w = *code;
+    const uint32_t tree = la;
+    const GPtr row = reinterpret_cast<GPtr>(outp + (uint64_t)tree * ldo);
+#if !DE_NO_LOSS
+    const int kind = (int)(flags & HF_LOSS_KIND_MASK);
+    const T p = lds_uniform_load(reinterpret_cast<const __attribute__((address_space(3))) T *>((uintptr_t)LossParamLds<T>::ADDR));
+    T s = T(0);
+    HL_BOTH(ly, lw);
+    typename VecOf<T>::type l[TG<T>::G];
+    DE_LOSS_KIND_SWITCH(kind, FOR_PLANES DE_UNROLL for (int i = 0; i < VW; i++) l[g][i] = (loss_kind_one<KIND, T>(st.acc[g][i], ly.v[g][i], p).l))
+    FOR_PLANES DE_UNROLL for (int i = 0; i < VW; i++) {
+        if (flags & HF_LOSS_PLAIN) s += l[g][i];
+        else s += lw.v[g][i] != T(0) ? lw.v[g][i] * l[g][i] : T(0); // weight 0 really excludes the sample
+    }
+    const int lane = (int)(((lds0 - DE_SKIPLIST_BYTES) >> 4) & 63u);
+    s = wave_sum_to_lane63(s, lane);
+    if (lane == 63) *reinterpret_cast<__attribute__((address_space(1))) T *>(row) = s;
+#endif
+    HTREE_END_TAIL(w, code_at(code, 1), code_at(code, -1));
+}
 // The other ends of a tree (flags & HF_SLOW), out of line so that h_tree_end itself is straight-line code: HF_LOSS (fused loss:
 // the tree's loss partial of this tile), HF_SLOW_STORE (ragged last tile / output rows that are not 16-byte aligned; LDS base = 0:
 // lds0 = DE_SKIPLIST_BYTES + 16 * thread), HF_NO_STORE (DE_DEBUG_NO_STORE, measurement only: keep the value alive, write nothing).
@@ -408,6 +456,14 @@ template <typename T> __device__ __noinline__ HState<T> h_tree_end_slow(HCHAIN_A
         s = wave_sum_to_lane63(s, lane);
         if (lane == 63) *reinterpret_cast<__attribute__((address_space(1))) T *>(row) = s;
         HTREE_END_TAIL(w, code_at(code, 1), code_at(code, -1));
+    }
+    if (!DE_NO_LOSS && (flags & HF_LOSS_KIND)) { // a parameterised kind (tested behind the L2 / L1 arm: that one's path is as it was)
+        // an INDIRECT tail call (the address goes through an empty asm): behind a direct one the backend hands the registers
+        // h_tree_end_loss uses — the transcendental kinds take callee-saved ones — up the chain of tail calls, and h_tree_end_slow,
+        // h_tree_end and every h_chain_end would open with a stack frame that saves them (Float64: 225 instead of 64 instructions)
+        uint64_t fa = (uint64_t)(uintptr_t)&h_tree_end_loss<T>;
+        asm volatile("" : "+s"(fa));
+        [[clang::musttail]] return reinterpret_cast<HandlerFn<T>>(fa)(st, HL_PASS_C lds0, code, outp, la, w1, w23, okp, ldo, skip, left, flags);
     }
     if (flags & HF_SLOW_STORE) {
         FOR_PLANES {
@@ -1487,6 +1543,9 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
             }
         }
     }
+    if constexpr (LOSS) { // the parameter of a parameterised loss kind, for h_tree_end_loss (visible behind the barrier below)
+        if (a.loss_kind >= DE_LOSS_HUBER && stid == 0) *reinterpret_cast<T *>(smem_base + LossParamLds<T>::ADDR) = a.loss_param;
+    }
     uint64_t m_first = 0ull; // (wave group: every wave has trees and flags of its own — its mask stays in registers)
     if constexpr (WW > 1) {
         if (a.skip_flagged) m_first = __ballot(f_first == 0);
@@ -1583,6 +1642,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
         uint64_t outp, ldo_arg = ldo;
         if constexpr (LOSS) {
             flags |= HF_SLOW | HF_LOSS | (a.loss_kind == DE_LOSS_L1 ? (uint32_t)HF_LOSS_L1 : 0u) | ((full && !a.w) ? (uint32_t)HF_LOSS_PLAIN : 0u);
+            if (a.loss_kind >= DE_LOSS_HUBER) flags = (flags & ~(uint32_t)(HF_LOSS | HF_LOSS_L1)) | HF_LOSS_KIND | ((uint32_t)a.loss_kind & HF_LOSS_KIND_MASK);
             outp = (uint64_t)(uintptr_t)(a.partial + ((int64_t)tm.tile * a.n_trees) * TWAVES + __builtin_amdgcn_readfirstlane(tid >> 6)); // (wave-uniform: an SGPR argument; a wave group: tid < 64)
             ldo_arg = (uint64_t)TWAVES * sizeof(T);
         } else {
@@ -1913,6 +1973,7 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
     a.y = a.w = nullptr;
     a.partial = nullptr;
     a.loss_kind = 0;
+    a.loss_param = T(0);
     if (e.loss && DE_NO_LOSS) return hipErrorInvalidValue; // (a build without the loss arguments)
     if (e.loss) {
         kern = e.uses_params ? de_eval_threaded_kernel<T, true, true> : de_eval_threaded_kernel<T, false, true>;
@@ -1925,6 +1986,8 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
         a.w = static_cast<const T *>(e.loss->w);
         a.partial = static_cast<T *>(e.loss->partial);
         a.loss_kind = e.loss->kind;
+        a.loss_param = (T)e.loss->param;
+        if (a.loss_kind >= DE_LOSS_HUBER && ((uint32_t)a.loss_kind & ~(uint32_t)HF_LOSS_KIND_MASK)) return hipErrorInvalidValue; // (the kind travels in five bits of `flags`)
     }
     if (kname) *kname = "de_eval_threaded_kernel";
     if (lds > 64 * 1024) {

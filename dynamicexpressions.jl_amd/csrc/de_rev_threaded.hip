@@ -454,7 +454,7 @@ __global__ void __launch_bounds__(GBLK) de_rev_threaded_kernel(const GArgs<T> a,
         }
         rpoison<T>(st.vpoison, st.x);
         { // loss term and the seed of the backward sweep
-            const LossTerm<T> lt = loss_term<T>(a.loss_mode, st.x, yv, wv);
+            const LossTerm<T> lt = loss_term<T>(a.loss_mode, st.x, yv, wv, a.loss_param);
             const T s = wave_sum_to_lane63(lt.l);
             if (RT_LANE() == 63) *RLDS(T, st.stage) = s;
             st.lp = lt.lp;

@@ -589,26 +589,46 @@ function eval_population(
     return out, ok .!= 0x00
 end
 
+struct LossSpec             # de_loss_spec_t
+    kind::Int32
+    reserved::Int32
+    param::Float64
+end
+# de_loss_kind_t (include/de_hip.h has the formulas): e = ŷ - y, a = y * ŷ for the two margin kinds
+const LOSS_KINDS = Dict{Symbol,Int32}(
+    :L2 => 0, :L1 => 1, :pullback => 2, :huber => 16, :logcosh => 17, :l1_eps => 18, :l2_eps => 19, :quantile => 20, :lp => 21,
+    :logit_dist => 22, :logit_margin => 23, :l1_hinge => 24,
+)
+"""The `de_loss_spec_t` of a loss name and its parameter (`:pullback` belongs to the gradient entry points).  The library checks the
+parameter's range (`de_loss_spec_check`) inside the call and answers `DE_ERR_INVALID_ARG`, naming the kind, before it touches an output."""
+function loss_spec(loss::Symbol, loss_param::Real; with_gradient::Bool=true)
+    (haskey(LOSS_KINDS, loss) && (with_gradient || loss !== :pullback)) || throw(ArgumentError("unknown loss $loss"))
+    return Ref(LossSpec(LOSS_KINDS[loss], Int32(0), Float64(loss_param)))
+end
+
 """
-    eval_population_loss(pop, X, y; weights=nothing, loss=:L2) -> (loss::Vector{T}, ok)
+    eval_population_loss(pop, X, y; weights=nothing, loss=:L2, loss_param=0.0) -> (loss::Vector{T}, ok)
 
 `sum(abs2, trees[t](X) .- y)` (test/test_optim.jl:95,99) for every tree, reduced on the device:
 the `N × n_trees` output matrix is never written.  `loss[t]` is NaN where `ok[t]` is false.
+`loss` is `:L2`, `:L1` or a parameterised kind — `:huber` (δ), `:logcosh`, `:l1_eps` (ε), `:l2_eps` (ε), `:quantile` (τ), `:lp` (p),
+`:logit_dist`, `:logit_margin`, `:l1_hinge` — with its parameter in `loss_param`.
 """
 function eval_population_loss(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
-    loss::Symbol=:L2,
+    loss::Symbol=:L2, loss_param::Real=0.0,
 ) where {T}
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
+    spec = loss_spec(loss, loss_param; with_gradient=false)
     out = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
     with_pop(pop) do hc, hp
         check(pop.ctx, GC.@preserve X y weights out ok ccall(
-            (:de_eval_loss, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32,
+            (:de_eval_loss_ex, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec},
              Ptr{Cvoid}, Ptr{UInt8}),
-            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), loss === :L1 ? 1 : 0, out, ok))
+            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), spec, out, ok))
     end
     return out, ok .!= 0x00
 end
@@ -650,39 +670,40 @@ function grad_widths(hp::Ptr{Cvoid}, n_trees::Int, mode::Cint)
 end
 
 """
-    eval_population_loss_grad(pop, X, y; weights=nothing, loss=:L2, variable=Val(false))
+    eval_population_loss_grad(pop, X, y; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(false))
         -> (loss::Vector{T}, dloss::Vector{Vector{T}}, ok)
 
 The optimiser callback of test/test_optim.jl:42-51 for a whole population in one launch:
 `dloss[t][i] = sum_j 2 (ŷ_j - y_j) * dŷ_dconstants[i, j]` without the `n_grad × N` Jacobian.
 `loss=:pullback` treats `y` as the cotangent `dY` of the ChainRules pullback
-(src/ChainRules.jl:56-77) and returns its `dtree` gradient.
+(src/ChainRules.jl:56-77) and returns its `dtree` gradient; the parameterised kinds of
+`eval_population_loss` take their parameter in `loss_param`.
 """
 function eval_population_loss_grad(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
-    loss::Symbol=:L2, variable=Val(false),
+    loss::Symbol=:L2, loss_param::Real=0.0, variable=Val(false),
 ) where {T}
     mode = grad_mode(variable)
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
-    kind = loss === :L1 ? 1 : loss === :pullback ? 2 : 0
+    spec = loss_spec(loss, loss_param)
     dl, offs = with_pop(pop) do hc, hp
         ng, offs = grad_widths(hp, pop.n_trees, mode)
         dl = Vector{T}(undef, max(offs[end], 1))
         check(pop.ctx, GC.@preserve X y weights lossv dl offs ok ccall(
-            (:de_eval_loss_grad, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int32,
+            (:de_eval_loss_grad_ex, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec},
              Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
-            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), kind, lossv, dl, offs, ok))
+            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), spec, lossv, dl, offs, ok))
         (dl, offs)
     end
     return lossv, [combine_rows(pop, t, dl[(offs[t] + 1):offs[t + 1]], mode) for t in 1:pop.n_trees], ok .!= 0x00
 end
 
 """
-    eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, variable=Val(:both))
+    eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(:both))
         -> (loss, dloss::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)
 
 Parametric population: the fused loss gradient with the parameter rows reduced BY CLASS —
@@ -694,7 +715,7 @@ that keeps its dataset ordered passes `grouped=true`.
 """
 function eval_population_loss_grad_by_class(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}, parameters::Matrix{T}, classes::Vector{Int64};
-    weights::Union{Nothing,Vector{T}}=nothing, loss::Symbol=:L2, variable=Val(:both), grouped::Bool=false,
+    weights::Union{Nothing,Vector{T}}=nothing, loss::Symbol=:L2, loss_param::Real=0.0, variable=Val(:both), grouped::Bool=false,
 ) where {T}
     mode = variable isa Val{true} || variable === true ? Cint(0) : Cint(2)
     F, N = size(X)
@@ -714,16 +735,16 @@ function eval_population_loss_grad_by_class(
     lossv = Vector{T}(undef, pop.n_trees)
     dp = Array{T,3}(undef, P, C, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
-    kind = loss === :L1 ? 1 : loss === :pullback ? 2 : 0
+    spec = loss_spec(loss, loss_param)
     dl, offs = with_pop(pop) do hc, hp
         ng, offs = grad_widths(hp, pop.n_trees, mode)
         dl = Vector{T}(undef, max(offs[end], 1))
         check(pop.ctx, GC.@preserve X y weights parameters classes starts lossv dl dp offs ok begin
             pa = Ref(ParamArgs(pointer(parameters), P, C, pointer(classes), 1, 1))
-            ccall((:de_eval_loss_grad_by_class, LIBDE), Cint,
-                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{ParamArgs}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int32,
+            ccall((:de_eval_loss_grad_by_class_ex, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{ParamArgs}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec},
                  Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{UInt8}),
-                hc, hp, X, N, F, pa, mode, y, weights === nothing ? C_NULL : pointer(weights), kind, starts, lossv, dl, offs,
+                hc, hp, X, N, F, pa, mode, y, weights === nothing ? C_NULL : pointer(weights), spec, starts, lossv, dl, offs,
                 dp, ok)
         end)
         (dl, offs)

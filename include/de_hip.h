@@ -387,7 +387,8 @@ int de_eval_diff(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, in
                  int32_t direction, void *out, void *dout, int64_t ld_out, uint8_t *ok);
 
 /* ---- fused loss (the consumer either side of the path) --------
- * loss[t] = sum_j w_j * l(tree_t(X[:, j]) - y[j]),  l = abs2 (DE_LOSS_L2) or abs (DE_LOSS_L1);
+ * loss[t] = sum_j w_j * l(tree_t(X[:, j]) - y[j]),  l = abs2 (DE_LOSS_L2) or abs (DE_LOSS_L1) — or, through de_eval_loss_ex, any
+ * parameterised kind of the table below;
  * w == NULL means w_j = 1; w_j == 0 excludes sample j.  This is what every consumer of
  * eval_tree_array in the reference's optimisation loop computes right after the call —
  * `sum(abs2, tree(X, operators) .- y)` (test/test_optim.jl:95,99), the objective handed to Optim
@@ -399,11 +400,37 @@ int de_eval_diff(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, in
 typedef enum de_loss_kind {
     DE_LOSS_L2 = 0,      /* l(e) = e^2,  l'(e) = 2e                                              */
     DE_LOSS_L1 = 1,      /* l(e) = |e|,  l'(e) = sign(e)                                         */
-    DE_LOSS_PULLBACK = 2 /* de_eval_loss_grad only: `y` holds a cotangent dY (see there)         */
+    DE_LOSS_PULLBACK = 2, /* de_eval_loss_grad only: `y` holds a cotangent dY (see there)        */
+    /* Parameterised kinds: the *_ex entry points only (de_loss_spec_t below).  e = yhat - y, a = y * yhat (margin kinds; y in
+     * {-1, +1} by convention, any real value is accepted), sign(0) = 0, l' = dl/dyhat; every l >= 0.       param            */
+    DE_LOSS_HUBER = 16,        /* |e| <= delta ? e^2 / 2 : delta (|e| - delta / 2)                          delta > 0        */
+    DE_LOSS_LOGCOSH = 17,      /* log(cosh(e)),  l' = tanh(e)                                               -                */
+    DE_LOSS_L1_EPS = 18,       /* max(0, |e| - eps),  l' = |e| > eps ? sign(e) : 0                          eps >= 0         */
+    DE_LOSS_L2_EPS = 19,       /* max(0, |e| - eps)^2,  l' = |e| > eps ? 2 sign(e) (|e| - eps) : 0          eps >= 0         */
+    DE_LOSS_QUANTILE = 20,     /* e ((e > 0) - tau),  l' = (e > 0) - tau                                    tau in [0, 1]    */
+    DE_LOSS_LP = 21,           /* |e|^p,  l' = p sign(e) |e|^(p - 1)                                        p >= 1           */
+    DE_LOSS_LOGIT_DIST = 22,   /* 2 log(cosh(e / 2)) = -log(4 exp(e) / (1 + exp(e))^2),  l' = tanh(e / 2)   -                */
+    DE_LOSS_LOGIT_MARGIN = 23, /* log(1 + exp(-a)),  l' = -y / (1 + exp(a))                                 -                */
+    DE_LOSS_L1_HINGE = 24      /* max(0, 1 - a),  l' = a < 1 ? -y : 0                                       -                */
 } de_loss_kind_t;
+/* A loss kind and its one scalar parameter.  `param` is converted once, on the host, to the program's element type; the kinds that
+ * have no parameter ignore it.  `reserved` must be 0. */
+typedef struct de_loss_spec {
+    int32_t kind;     /* de_loss_kind_t */
+    int32_t reserved;
+    double param;
+} de_loss_spec_t;
+/* DE_OK, or DE_ERR_INVALID_ARG for a null spec, a non-zero `reserved`, an unknown kind, a parameter that is not finite or lies outside the kind's range (see the
+ * table), and — with_gradient == 0 — DE_LOSS_PULLBACK, which only the gradient entry points know.  Needs no context and touches no device. */
+int de_loss_spec_check(const de_loss_spec_t *spec, int with_gradient);
 int de_eval_loss(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
                  const de_param_args_t *pargs, const void *y, const void *w, int32_t loss_kind,
                  void *loss, uint8_t *ok);
+/* The same with any kind of the enumeration above; de_eval_loss itself accepts DE_LOSS_L2 / DE_LOSS_L1 only and forwards here.  A bad spec is
+ * DE_ERR_INVALID_ARG with a de_last_error text that names the kind. */
+int de_eval_loss_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                    const de_param_args_t *pargs, const void *y, const void *w, const de_loss_spec_t *spec,
+                    void *loss, uint8_t *ok);
 
 /* Fused loss + its gradient (the pullback of the reduction through eval_grad_tree_array):
  *   loss[t]              = sum_j w_j * l(tree_t(x_j) - y_j)
@@ -420,6 +447,11 @@ int de_eval_loss_grad(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t 
                       const de_param_args_t *pargs, int mode, const void *y, const void *w,
                       int32_t loss_kind, void *loss, void *dloss, const int64_t *dloss_offsets,
                       uint8_t *ok);
+/* ... with any kind of the enumeration, l' from its table. */
+int de_eval_loss_grad_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                         const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                         const de_loss_spec_t *spec, void *loss, void *dloss, const int64_t *dloss_offsets,
+                         uint8_t *ok);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
@@ -440,6 +472,11 @@ int de_eval_loss_grad_by_class(de_ctx_t *ctx, de_program_t *prog, const void *X,
                                const de_param_args_t *pargs, int mode, const void *y, const void *w,
                                int32_t loss_kind, const int64_t *class_starts, void *loss, void *dloss,
                                const int64_t *dloss_offsets, void *dparams, uint8_t *ok);
+/* ... with any kind of de_loss_kind_t. */
+int de_eval_loss_grad_by_class_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                                  const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                                  const de_loss_spec_t *spec, const int64_t *class_starts, void *loss, void *dloss,
+                                  const int64_t *dloss_offsets, void *dparams, uint8_t *ok);
 
 /* The `dX` of the ChainRules pullback of eval_tree_array (EvalPullback, src/ChainRules.jl:56-77):
  *   dX_t[f, j] = d tree_t(x_j) / d x_f * dY[j]      (`dX = dX_dY .* reshape(dY, 1, length(dY))`, :74)
