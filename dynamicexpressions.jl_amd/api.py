@@ -46,7 +46,7 @@ EXPORTS = [
     "de_opcode_degree", "de_status_string", "de_ctx_create", "de_ctx_destroy", "de_ctx_set_stream",
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
     "de_program_set_consts", "de_program_update", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
-    "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
+    "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_lower_tape_grad", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
     "de_loss_spec_check", "de_eval_loss_ex", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
@@ -158,6 +158,8 @@ def library() -> C.CDLL:
         fn.restype = i64
     lib.de_lower_tape_complex.argtypes = lib.de_lower_tape.argtypes
     lib.de_lower_tape_stage_complex.argtypes = lib.de_lower_tape_stage.argtypes
+    lib.de_lower_tape_grad.restype = i64
+    lib.de_lower_tape_grad.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, C.c_int, C.c_int, vp, i64, vp]
     lib.de_eval.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, i64, vp]
     lib.de_eval_loss.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.c_int32, vp, vp]
     lib.de_eval_loss_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.c_int32, vp, vp, vp, vp]
@@ -441,6 +443,24 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     w = np.zeros(max(int(n), 1), dtype=np.uint32)
     stage_fn(*args, w.ctypes.data, w.size)
     return w[:int(n)].reshape(-1, 4)
+
+
+def lower_tape_grad(tape, consts, n_features: int, mode: int, form: int, n_params: int = 0, options: int = 7, dtype=np.float32):
+    """Host-only: the threaded gradient stream of one tape (``de_lower_tape_grad``): ([n, 4] uint32 records, meta int32[8]); the records
+    are empty when the tree has no such stream.  form 0 / 1 / 2: forward duals (plain, wide, shared leaf rows), 3: reverse accumulation."""
+    lib = library()
+    dtype = np.dtype(dtype)
+    tape = np.ascontiguousarray(tape)
+    consts = np.ascontiguousarray(consts, dtype=dtype)
+    cp = consts.ctypes.data if consts.size else None
+    meta = np.zeros(8, dtype=np.int32)
+    args = (_dtype_code(dtype), tape.ctypes.data, len(tape), cp, consts.size, n_features, n_params, options, mode, form)
+    n = lib.de_lower_tape_grad(*args, None, 0, meta.ctypes.data)
+    if n < 0:
+        raise ValueError(lib.de_status_string(int(-n)).decode())
+    w = np.zeros(max(int(n), 1), dtype=np.uint32)
+    lib.de_lower_tape_grad(*args, w.ctypes.data, w.size, meta.ctypes.data)
+    return w[:int(n)].reshape(-1, 4), meta
 
 
 def check_update_ids(indices, n_new: int, n_trees: int) -> np.ndarray:

@@ -24,6 +24,7 @@ build_obj de_api_program.cpp $OBJ/de_api_program.o &
 build_obj de_api_eval.cpp $OBJ/de_api_eval.o &
 build_obj de_api_grad.cpp $OBJ/de_api_grad.o &
 build_obj de_bind.cpp $OBJ/de_bind.o &
+build_obj de_grad_encode.cpp $OBJ/de_grad_encode.o &
 build_obj de_dist.cpp $OBJ/de_dist.o &
 # de_kernels.hip goes through the same steps hipcc runs internally, with one extra pass over the optimised
 # device IR (irpatch.py: the interpreter's indirect handler calls need none of the implicit kernel inputs).
@@ -115,6 +116,6 @@ build_obj de_half.hip $OBJ/de_half.o &           # binary16 (DE_F16)
 build_obj de_complex.hip $OBJ/de_complex.o &     # complex (DE_CF32 / DE_CF64)
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

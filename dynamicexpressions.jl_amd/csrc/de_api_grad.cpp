@@ -1,14 +1,27 @@
 // de_api_grad.cpp — C ABI (include/de_hip.h): de_eval_grad / de_eval_diff / de_eval_pullback_dX, de_eval_loss_grad, de_eval_loss_grad_by_class: the
-// generic gradient program, its direct-threaded and reverse-accumulation forms, launch planning of the bucketed gradient kernels.
+// generic gradient program, the glue around the host encoders of its direct-threaded and reverse-accumulation forms (de_grad_encode.cpp)
+// with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels.
 #include "de_api_internal.h"
+#include "de_grad_encode.h"
 
-// Direct threading (de_grad_threaded.hip, de_rev_threaded.hip): the handler word of a record names the handler of the record BEHIND it, the
-// last record of the chain [a0, b0) — a tree, or one sweep of it — names the chain's first handler.
-static void successor_words(std::vector<BoundInstr> &code, int32_t a0, int32_t b0) {
-    if (b0 - a0 < 2) return;
-    const uint32_t first = code[(size_t)a0].bop;
-    for (int32_t i = a0; i < b0 - 1; i++) code[(size_t)i].bop = code[(size_t)i + 1].bop;
-    code[(size_t)b0 - 1].bop = first;
+// A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
+static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
+    const size_t bytes = records * sizeof(BoundInstr);
+    const hipError_t ast = prog_malloc(c, reinterpret_cast<void **>(d), bytes);
+    if (ast != hipSuccess) return fail(c, DE_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(ast));
+    if (!in_one_window(*d, bytes)) return fail(c, DE_ERR_HIP, "%s instruction stream straddles a 4 GiB boundary", what);
+    HIP_TRY(c, hipMemset(*d, 0, bytes));
+    return DE_OK;
+}
+// the switches both encoders (and the host hook de_lower_tape_grad) read
+static GradEncodeOptions grad_encode_env() {
+    GradEncodeOptions opt;
+    opt.hot_const_unary = !getenv("DE_NO_CONST_UNARY_HOT"); // unary operators outside the binder's hot set through hot handlers
+    opt.rfuse = !getenv("DE_REV_NO_FUSE"); // fused pairs / triples (de_rev_threaded.hip rh_pushload ...): same bits, fewer dispatches
+    return opt;
+}
+template <class T> static hipError_t upload(T *dst, const std::vector<T> &v) {
+    return v.empty() ? hipSuccess : hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 extern "C" {
@@ -44,10 +57,8 @@ static int ensure_generic_code(de_ctx *c, de_program *p) {
     return DE_OK;
 }
 
-// Threaded form of the gradient program (de_grad_threaded.hip) for `mode`.  Trees are grouped into
-// buckets by gradient width n_grad(t, mode): widths 1..6 and 7-8 each run in the module built for that
-// window (every seed is known here and compiled into the handler choice), wider trees in windows of 8
-// with run-time seeds.  Fills g->threaded_code & co. when the program can be expressed this way; otherwise
+// Threaded form of the gradient program (de_grad_threaded.hip) for `mode`, encoded by encode_grad_forward (de_grad_encode.cpp: buckets by
+// gradient width, one module per window).  Fills g->threaded_code & co. when the program can be expressed this way; otherwise
 // leaves them null and the flat-switch kernel runs.  Call after ensure_generic_code().
 static int ensure_grad_threaded(de_ctx *c, de_program *p, int mode, const std::vector<int32_t> &ng, int64_t N, GradArgs *g) {
     g->threaded_code = nullptr;
@@ -56,331 +67,55 @@ static int ensure_grad_threaded(de_ctx *c, de_program *p, int mode, const std::v
     g->gt_var_stride = 0;
     const char *env = getenv("DE_GRAD_THREADED");
     if (env && *env == '0') return DE_OK;
-    const int F = p->n_features, P = p->n_params;
     // Parameter leaves are LDS rows of their own: the kernel gathers params[:, class] into P rows behind the X rows when it
     // stages a tile (the reference's formulation, src/ParametricExpression.jl:381-389), so every hot handler serves them.
-    const int FE = F + (p->uses_params ? P : 0);
-    const bool hot_const_unary = !getenv("DE_NO_CONST_UNARY_HOT"); // unary operators outside the binder's hot set through hot handlers
-    const bool fuse_push = true;                                   // PUSH + LOAD pairs as one instruction
-    auto gun_of = [&](uint32_t op) { // hot unary index of a de_opcode (de_bind.h), or -1
-        return hot_const_unary ? gun_index((int)op, DE_U_COS, DE_U_EXP, DE_U_SIN, DE_U_NEG, DE_U_SQUARE, DE_U_CUBE, DE_U_ABS, DE_U_LOG, DE_U_SAFE_LOG,
-                                           DE_U_SQRT, DE_U_SAFE_SQRT, DE_U_TANH, DE_U_RELU) : -1;
-    };
+    const int FE = p->n_features + (p->uses_params ? p->n_params : 0);
+    GradEncodeOptions opt = grad_encode_env();
     // Two samples per lane double the buckets (launches) and the tile: they pay from ~10^5 samples on (10^4 trees x
     // 10^3 rows: 0.55 ms with them, 0.35 ms without; 10^3 trees x 10^6 rows: 12.1 against 13.4 ms)
     const char *envn = getenv("DE_GRAD_VS2_MIN_N");
-    const bool wide = N >= (envn ? atoll(envn) : 65536);
-    if (!(p->gt_valid && p->gt_mode == mode && p->gt_wide == wide)) {
-        dbg_lap(nullptr);
-        // bucket of a tree: (width index 0..6 = single window of width 1,2,3,4,5,6,8; 7 = several windows of 8)
-        // x (samples per lane - 1).  The two-sample modules exist for Float32 windows <= 6; their rows are
-        // twice as long, so they only pay while a workgroup's LDS stays small: at most DE_GRAD_VS2_ROWS (15) rows per wave.
-        // width index 0..6 = single window of width 1,2,3,4,5,6,8; 7,8,9 = several windows of 8,5,6 (the
-        // narrowest module that covers the gradient in ceil(G/8) windows: 9-10 rows -> 2x5, 11-12 -> 2x6, 17-18 -> 3x6)
-        static const int WIDTH[10] = {1, 2, 3, 4, 5, 6, 8, 8, 5, 6};
-        constexpr int NW = 10, NB = 2 * NW;
+    opt.wide = N >= (envn ? atoll(envn) : 65536);
+    if (!(p->gt_valid && p->gt_mode == mode && p->gt_wide == opt.wide)) {
         const char *env2 = getenv("DE_GRAD_VS2_ROWS"); // most LDS rows per wave (X + parameters + slots) that still run two samples per lane
         // 15 rows x 512 B x 4 waves = 30.7 KB: 5 workgroups per CU.  Parametric populations (their P parameter rows come on top of X) take 18:
         // measured in round 6 (tools/experiments/sweep_vs2_rows.sh, same box): C5 7.98 / 7.82 / 7.81 / 8.06 / 8.42 ms and C5Ng 7.30 / 7.06 / 7.14 /
         // 7.40 / 7.66 ms at 15 / 18 / 20 / 22 / 24 rows — two samples per lane pay a little further out when most rows are shared inputs
-        const int vs2_rows = env2 ? atoi(env2) : (p->uses_params ? 18 : 15);
+        opt.vs2_rows = env2 ? atoi(env2) : (p->uses_params ? 18 : 15);
         // SHARED LEAF ROWS (GradArgs::gt_share): with many leaf rows most of a wave's LDS is a copy of inputs the other three waves could
         // read as well — the four waves then take different trees on the same samples.  Measured (round 6, constant-mode Jacobians of 1000
         // trees x 10^5 samples, tools/experiments/wide_x_grad.py): F = 5 0.80 -> 0.86 ms (worse: the staging is spread over fewer samples),
         // F = 20 1.14 -> 1.03, F = 40 1.82 -> 1.05, F = 60 2.58 -> 1.18, F = 120 5.82 -> 1.91; 5 features + 8 parameter rows (C5): 7.42 -> 7.35 ms,
         // nothing — those kernels are not short of resident waves.  From 16 leaf rows on; DE_GRAD_SHARE = 0 | 1 overrides.
         const char *envs = getenv("DE_GRAD_SHARE"), *envf = getenv("DE_GRAD_SHARE_MIN_ROWS");
-        const bool share = envs ? *envs == '1' : FE >= (envf ? atoi(envf) : 16);
-        std::vector<int32_t> tslots((size_t)p->n_trees, 0); // spill slots of each tree (rows >= F the code names)
-        parallel_for_trees(p->n_trees, [&](int64_t t) {
-            int32_t need = 0;
-            for (int32_t i = p->gbcode_off[(size_t)t]; i < p->gbcode_off[(size_t)t + 1]; i++) {
-                const BoundInstr &b = p->gbcode[(size_t)i];
-                const uint32_t row = b.arg & 0xFFFFFFu;
-                const bool names_row = b.bop == BOP_PUSH || b.bop == BOP_LOAD_ROW || b.bop == BOP_GEN_ROW || b.bop == BOP_TERN ||
-                                       (b.bop >= BOP_BIN_BASE && b.bop < BOP_BIN_END && !((b.bop - BOP_BIN_BASE) & 2)) ||
-                                       (b.bop >= BOP_UN_BASE && b.bop < BOP_UN_END && ((b.bop - BOP_UN_BASE) & 2));
-                if (names_row && row >= (uint32_t)F) need = std::max(need, (int32_t)(row - (uint32_t)F) + 1);
-                if (b.bop == BOP_TERN && b.lo >= (uint32_t)F) need = std::max(need, (int32_t)(b.lo - (uint32_t)F) + 1);
-            }
-            tslots[(size_t)t] = need;
-        });
-        dbg_lap("grad threaded: spill slots per tree");
-        auto bucket_of = [&](int64_t t) {
-            const int32_t G = ng[(size_t)t];
-            int w;
-            if (G <= 6) w = G < 1 ? 0 : G - 1;
-            else if (G <= 8) w = 6;
-            else {
-                const int windows = (G + 7) / 8, per = (G + windows - 1) / windows;
-                w = per <= 5 ? 8 : (per <= 6 ? 9 : 7);
-                if (!grad_threaded_has(p->dtype, WIDTH[w], 1)) w = 7;
-            }
-            const int rows2 = FE + std::max(tslots[(size_t)t] * (1 + WIDTH[w]), WIDTH[w]);
-            const bool two = wide && p->dtype == DE_F32 && WIDTH[w] <= 6 && rows2 <= vs2_rows && grad_threaded_has(p->dtype, WIDTH[w], 2);
-            return w + (two ? NW : 0);
+        opt.share = envs ? *envs == '1' : FE >= (envf ? atoi(envf) : 16);
+        opt.lap = dbg_lap;
+        std::vector<std::array<uint64_t, GOP_MAX>> tables;
+        tables.reserve(GRAD_BUCKETS_MAX); // (the encoder keeps pointers into it)
+        hipError_t hst = hipSuccess;
+        const GradHandlerSource handlers = [&](int GC, int VS, GradHandlers *h) -> int {
+            tables.emplace_back();
+            hst = grad_handler_table(p->dtype, GC, VS, tables.back().data());
+            if (hst != hipSuccess) return -DE_ERR_HIP;
+            h->table = tables.back().data();
+            return handler_base(h->table, gop_count(GC), &h->base) ? GRAD_ENC_OK : GRAD_ENC_NO_PLAN;
         };
-        int32_t count[NB] = {0}, maxg[NB] = {0}, slots[NB] = {0};
-        for (int64_t t = 0; t < p->n_trees; t++) {
-            const int32_t G = ng[(size_t)t];
-            if (G > 240) return DE_OK; // gradient rows travel in 8 bits
-            const int b = bucket_of(t);
-            // Float64 states wider than 16 dwords are passed through scratch memory by the calling convention
-            if (!grad_threaded_has(p->dtype, WIDTH[b % NW], 1 + b / NW)) return DE_OK;
-            count[b]++;
-            maxg[b] = std::max(maxg[b], G);
-            slots[b] = std::max(slots[b], tslots[(size_t)t]);
-        }
-        const uint32_t es32 = p->dtype == DE_F32 ? 4u : 8u;
-        std::vector<std::array<uint64_t, GOP_MAX>> tables(NB);
-        uint64_t bases[NB] = {0};
-        for (int b = 0; b < NB; b++) {
-            if (!count[b]) continue;
-            const int GC = WIDTH[b % NW], VS = 1 + b / NW;
-            const uint64_t RBb = 64ull * VS * es32; // one wave's row
-            const uint64_t rows = (uint64_t)FE + std::max<uint64_t>((uint64_t)slots[b] * (1 + GC), (uint64_t)GC);
-            const uint64_t srows = std::max<uint64_t>((uint64_t)slots[b] * (1 + GC), (uint64_t)GC);
-            if ((share ? ((uint64_t)FE + 4 * srows) : 4 * rows) * RBb > 160 * 1024) return DE_OK; // four waves' rows must fit the CU's LDS
-            hipError_t st = grad_handler_table(p->dtype, GC, VS, tables[b].data());
-            if (st != hipSuccess) return fail(c, DE_ERR_HIP, "gradient handler table: %s", hipGetErrorString(st));
-            uint64_t base = tables[b][0];
-            for (int i = 0; i < (int)gop_count(GC); i++) base = std::min<uint64_t>(base, tables[b][i]);
-            for (int i = 0; i < (int)gop_count(GC); i++)
-                if (tables[b][i] - base > 0xFFFFFFFFull) return DE_OK;
-            bases[b] = base;
-        }
-        dbg_lap("grad threaded: buckets, handler tables");
-        auto leaf_seed = [&](uint32_t f) -> uint32_t { return mode != DE_GRAD_CONSTANT ? (uint32_t)P + f : 0xFFu; };
-        auto const_seed = [&](uint32_t ord) -> uint32_t {
-            return mode == DE_GRAD_CONSTANT ? ord : (mode == DE_GRAD_BOTH ? (uint32_t)(P + F) + ord : 0xFFu);
-        };
-        p->gtcode.clear();
-        p->gtcode_off.assign((size_t)p->n_trees + 1, 0);
-        p->gtsite_of_gb.assign(p->gbcode.size(), -1);
+        const GradSource src{p->gbcode, p->gbcode_off, p->n_trees, p->n_features, p->n_params, p->uses_params, p->dtype, mode, ng.data()};
+        GradForwardStream r;
+        const int enc = encode_grad_forward(src, opt, grad_threaded_has, handlers, &r);
+        if (hst != hipSuccess) return fail(c, DE_ERR_HIP, "gradient handler table: %s", hipGetErrorString(hst));
+        if (enc == GRAD_ENC_NO_PLAN) return DE_OK;
+        p->gtsite_of_gb.clear();
         p->site_gen++;
-        std::atomic<bool> ok{true};
-        // encoded per worker into a vector of its own (sites = positions in that vector), concatenated afterwards
-        std::vector<BoundInstr> parts[HOST_RANGES_MAX];
-        // ... and per record what a stream variant of the shared-leaf-row launch adds the wave's slot bytes to: 0 nothing, 1 the operand
-        // word (a slot operand, a push, the spilled operands of a ternary operator), 2 the immediate (push + load of a leaf: row -> slot distance)
-        std::vector<uint8_t> kparts[HOST_RANGES_MAX];
-        std::vector<int32_t> tree_cnt((size_t)p->n_trees, 0);
-        int64_t part_first[HOST_RANGES_MAX], part_last[HOST_RANGES_MAX];
-        for (int k = 0; k < HOST_RANGES_MAX; k++) part_first[k] = part_last[k] = 0;
-        parallel_tree_ranges(p->n_trees, [&](int wk, int64_t tb, int64_t te) {
-        std::vector<BoundInstr> &out = parts[wk];
-        std::vector<uint8_t> &kout = kparts[wk];
-        part_first[wk] = tb;
-        part_last[wk] = te;
-        for (int64_t t = tb; t < te && ok; t++) {
-            const size_t out_before = out.size();
-            const int bkt = bucket_of(t);
-            const int GC = WIDTH[bkt % NW];
-            const uint32_t RB = 64u * (uint32_t)(1 + bkt / NW) * es32; // bytes of one wave's row
-            const bool one_window = bkt % NW < 7; // then g0 = 0 and every seed is known here
-            const uint64_t *table = tables[bkt].data();
-            const uint64_t base = bases[bkt];
-            auto slot_off = [&](uint32_t row) { return (uint32_t)((FE + (row - (uint32_t)F) * (1 + GC)) * RB); };
-            // seed variant of a handler (de_bind.h): 0 run-time, 1 none, 2 + k
-            auto seed_variant = [&](uint32_t sd) -> int { return !one_window ? 0 : (sd == 0xFFu ? 1 : (sd < (uint32_t)GC ? 2 + (int)sd : 0)); };
-            for (int32_t i = p->gbcode_off[(size_t)t]; i < p->gbcode_off[(size_t)t + 1] && ok; i++) {
-                const BoundInstr &b = p->gbcode[(size_t)i];
-                const uint32_t row = b.arg & 0xFFFFFFu, aux = b.arg >> 24;
-                BoundInstr o = b;
-                int src = GSRC_ACC, sv = 0;
-                auto row_operand = [&](bool rt = false) { // sets src, sv and o.arg for a row operand (rt: handler reads the seed at run time)
-                    if (row < (uint32_t)F) {
-                        const uint32_t sd = leaf_seed(row);
-                        if (sd != 0xFFu && sd >= 0xF0u) ok = false;
-                        src = GSRC_LEAF;
-                        sv = rt ? 0 : seed_variant(sd);
-                        o.arg = (row * RB) | (sv == 0 ? sd << 24 : 0u); // known seeds are compiled into the handler
-                    } else {
-                        src = GSRC_SLOT;
-                        o.arg = slot_off(row);
-                    }
-                };
-                auto const_operand = [&](uint32_t ord, uint32_t low, bool rt = false) {
-                    const uint32_t sd = const_seed(ord);
-                    if (sd != 0xFFu && sd >= 0xF0u) ok = false;
-                    src = GSRC_CONST;
-                    sv = rt ? 0 : seed_variant(sd);
-                    o.arg = low | (sv == 0 ? sd << 24 : 0u);
-                };
-                auto param_operand = [&](uint32_t prm, bool rt = false) { // parameter row prm = LDS row F + prm, seed = its gradient row
-                    const uint32_t sd = mode != DE_GRAD_CONSTANT ? prm : 0xFFu;
-                    if (sd != 0xFFu && sd >= 0xF0u) ok = false;
-                    src = GSRC_LEAF;
-                    sv = rt ? 0 : seed_variant(sd);
-                    o.arg = (((uint32_t)F + prm) * RB) | (sv == 0 ? sd << 24 : 0u);
-                };
-                uint32_t gop = 0;
-                if (b.bop == BOP_CHECK_ROW) continue; // leaf operands are tested where they are read
-                if (b.bop == BOP_LOAD_ROW) { row_operand(); gop = gop_load(GC, src, sv); }
-                else if (b.bop == BOP_LOAD_CONST) { const_operand(b.arg & 0xFFFFu, 0); gop = gop_load(GC, src, sv); }
-                else if (b.bop == BOP_PUSH && fuse_push && i + 1 < p->gbcode_off[(size_t)t + 1] &&
-                         (p->gbcode[(size_t)i + 1].bop == BOP_LOAD_CONST ||
-                          (p->gbcode[(size_t)i + 1].bop == BOP_LOAD_ROW && (p->gbcode[(size_t)i + 1].arg & 0xFFFFFFu) < (uint32_t)F))) {
-                    // PUSH followed by the LOAD that starts the next subtree: one dispatch (g_pushload)
-                    const BoundInstr &b2 = p->gbcode[(size_t)i + 1];
-                    const uint32_t slot = slot_off(row);
-                    if (b2.bop == BOP_LOAD_CONST) {
-                        const_operand(b2.arg & 0xFFFFu, slot);
-                        o.lo = b2.lo;
-                        o.hi = b2.hi;
-                        p->gtsite_of_gb[(size_t)i + 1] = (int32_t)out.size(); // the constant lives in the fused instruction
-                    } else {
-                        const uint32_t row2 = b2.arg & 0xFFFFFFu, sd = leaf_seed(row2);
-                        if (sd != 0xFFu && sd >= 0xF0u) ok = false;
-                        src = GSRC_LEAF;
-                        sv = seed_variant(sd);
-                        o.arg = (row2 * RB) | (sv == 0 ? sd << 24 : 0u);
-                        o.lo = slot - row2 * RB; // byte distance row -> slot
-                        o.hi = 0;
-                    }
-                    if (!ok) break;
-                    o.bop = (uint32_t)(table[gop_pushload(GC, src, sv)] - base);
-                    out.push_back(o);
-                    kout.push_back(b2.bop == BOP_LOAD_CONST ? 1 : 2);
-                    i++; // the LOAD is part of this instruction
-                    continue;
-                }
-                else if (b.bop == BOP_PUSH) { gop = gop_push(GC); o.arg = slot_off(row); }
-                else if (b.bop == BOP_CHECK_ACC) { gop = gop_check_acc(GC); o.arg = 0; }
-                else if (b.bop >= BOP_BIN_BASE && b.bop < BOP_BIN_END) {
-                    const uint32_t v = b.bop - BOP_BIN_BASE;
-                    if (v & 2) const_operand(b.arg & 0xFFFFu, 0);
-                    else row_operand();
-                    gop = gop_bin(GC, (int)(v >> 2), src, sv, (v & 1) != 0);
-                } else if (b.bop >= BOP_UN_BASE && b.bop < BOP_UN_END) {
-                    const uint32_t v = b.bop - BOP_UN_BASE;
-                    if (v & 2) row_operand();
-                    else o.arg = 0;
-                    gop = gop_un(GC, (int)(v >> 2), src, sv, (v & 1) != 0);
-                } else if (b.bop == BOP_GEN_ROW && hot_const_unary && (aux == (uint32_t)DE_B_MAX || aux == (uint32_t)DE_B_MIN)) {
-                    row_operand(); gop = gop_bin(GC, aux == (uint32_t)DE_B_MAX ? 6 : 7, src, sv, false); o.lo = o.hi = 0;
-                } else if (b.bop == BOP_GEN_ROW && gun_of(aux) >= 0) { row_operand(); gop = gop_un(GC, gun_of(aux), src, sv, false); o.lo = o.hi = 0; }
-                else if (b.bop == BOP_GEN_ROW) { row_operand(true); gop = gop_gen(GC, src); o.lo = aux; o.hi = 0; }
-                else if (b.bop == BOP_GEN_CONST && hot_const_unary && (aux == (uint32_t)DE_B_MAX || aux == (uint32_t)DE_B_MIN)) {
-                    const_operand(b.arg & 0xFFFFu, 0); gop = gop_bin(GC, aux == (uint32_t)DE_B_MAX ? 6 : 7, src, sv, false);
-                }
-                else if (b.bop == BOP_GEN_CONST && gun_of(aux) >= 0) {
-                    // cos / exp / sin of a constant leaf (common: half the leaves are constants and the gradient program
-                    // is not folded): load the constant, then the hot unary handler on the accumulator — not the generic
-                    // handler (out-of-line operator switch, OCML functions, scratch traffic of its spills)
-                    const_operand(b.arg & 0xFFFFu, 0);
-                    o.bop = (uint32_t)(table[gop_load(GC, src, sv)] - base);
-                    p->gtsite_of_gb[(size_t)i] = (int32_t)out.size();
-                    out.push_back(o);
-                    kout.push_back(0);
-                    BoundInstr u = b;
-                    u.arg = 0;
-                    u.lo = u.hi = 0;
-                    u.bop = (uint32_t)(table[gop_un(GC, gun_of(aux), GSRC_ACC, 0, false)] - base);
-                    out.push_back(u);
-                    kout.push_back(0);
-                    continue;
-                }
-                else if (b.bop == BOP_GEN_CONST) { const_operand(b.arg & 0xFFFFu, aux << 16, true); gop = gop_gen(GC, GSRC_CONST); }
-                else if (b.bop == BOP_GEN_ACC && gun_of(aux) >= 0) { gop = gop_un(GC, gun_of(aux), GSRC_ACC, 0, false); o.arg = 0; o.lo = o.hi = 0; }
-                else if (b.bop == BOP_GEN_ACC) { gop = gop_gen(GC, GSRC_ACC); o.arg = 0; o.lo = aux; o.hi = 0; }
-                else if (b.bop == BOP_GEN_PARAM) { // operand = parameter row (b.arg & 0xFFFF), operator aux: the leaf-operand handlers
-                    const uint32_t prm = b.arg & 0xFFFFu;
-                    int k = -1, ku = -1;
-                    switch (aux) {
-                    case DE_B_ADD: k = 0; break;
-                    case DE_B_SUB: k = 1; break;
-                    case DOP_RSUB: k = 2; break;
-                    case DE_B_MUL: k = 3; break;
-                    case DE_B_DIV: k = 4; break;
-                    case DOP_RDIV: k = 5; break;
-                    case DE_B_MAX: k = hot_const_unary ? 6 : -1; break;
-                    case DE_B_MIN: k = hot_const_unary ? 7 : -1; break;
-                    default: ku = gun_of(aux); break;
-                    }
-                    o.lo = o.hi = 0;
-                    if (aux == (uint32_t)DOP_LOAD) { param_operand(prm); gop = gop_load(GC, src, sv); }
-                    else if (k >= 0) { param_operand(prm); gop = gop_bin(GC, k, src, sv, false); }
-                    else if (ku >= 0) { param_operand(prm); gop = gop_un(GC, ku, src, sv, false); }
-                    else { param_operand(prm, true); gop = gop_gen(GC, GSRC_LEAF); o.lo = aux; }
-                }
-                else if (b.bop == BOP_TERN) {
-                    if (row < (uint32_t)F || b.lo < (uint32_t)F) ok = false; // both operands are spilled duals
-                    else { gop = gop_tern(GC); o.arg = slot_off(row) | (aux << 24); o.lo = slot_off(b.lo) - slot_off(row); o.hi = 0; }
-                } else ok = false; // INJ_*: only bound with early_exit=false, never for gradients
-                if (!ok) break;
-                o.bop = (uint32_t)(table[gop] - base);
-                p->gtsite_of_gb[(size_t)i] = (int32_t)out.size();
-                out.push_back(o);
-                kout.push_back((src == GSRC_SLOT || b.bop == BOP_PUSH || b.bop == BOP_TERN) ? 1 : 0);
-            }
-            // the end record: every tree's chain finishes in g_end (the table slot of round 1's parameter handler)
-            out.push_back(BoundInstr{(uint32_t)(table[gop_param(GC)] - base), 0u, 0u, 0u});
-            kout.push_back(0);
-            tree_cnt[(size_t)t] = (int32_t)(out.size() - out_before);
-        }
-        });
-        dbg_lap("grad threaded: encode (host threads)");
-        if (!ok) { p->gtsite_of_gb.clear(); p->site_gen++; return DE_OK; }
-        for (int64_t t = 0; t < p->n_trees; t++) p->gtcode_off[(size_t)t + 1] = p->gtcode_off[(size_t)t] + tree_cnt[(size_t)t];
-        p->gtcode.resize((size_t)p->gtcode_off[(size_t)p->n_trees]);
-        // ranges are in tree order; sites move from worker-local to global positions (the same partition as the encoding pass: worker k
-        // copies the piece it encoded)
-        parallel_tree_ranges(p->n_trees, [&](int k, int64_t tb, int64_t te) {
-            if (part_first[k] != tb || part_last[k] != te) return; // (never: the partition depends on n_trees only)
-            const int32_t base_k = p->gtcode_off[(size_t)tb];
-            if (!parts[k].empty()) std::memcpy(static_cast<void *>(p->gtcode.data() + base_k), parts[k].data(), parts[k].size() * sizeof(BoundInstr));
-            if (base_k != 0)
-                for (int32_t i = p->gbcode_off[(size_t)tb]; i < p->gbcode_off[(size_t)te]; i++)
-                    if (p->gtsite_of_gb[(size_t)i] >= 0) p->gtsite_of_gb[(size_t)i] += base_k;
-        });
-        {
-            size_t copied = 0;
-            for (int k = 0; k < HOST_RANGES_MAX; k++) copied += parts[k].size();
-            if (copied != p->gtcode.size()) { p->gtsite_of_gb.clear(); p->site_gen++; return fail(c, DE_ERR_HIP, "gradient program: the host threads' partitions disagree"); }
-        }
-        dbg_lap("grad threaded: concatenate + sites");
-        // (a handler knows its successor at entry and jumps without waiting for the record it loads)
-        parallel_for_trees(p->n_trees, [&](int64_t t) {
-            successor_words(p->gtcode, p->gtcode_off[(size_t)t], p->gtcode_off[(size_t)t + 1]);
-        });
-        dbg_lap("grad threaded: successor words");
-        p->gt_share = false;
-        p->gt_stride = 0;
-        if (share) { // the stream variants of waves 1 .. 3: the same records with the wave's slot bytes added where a record names a slot
-            const size_t n0 = p->gtcode.size();
-            std::vector<uint8_t> kinds(n0, 0);
-            parallel_tree_ranges(p->n_trees, [&](int k, int64_t tb, int64_t) {
-                if (!kparts[k].empty()) std::memcpy(kinds.data() + p->gtcode_off[(size_t)tb], kparts[k].data(), kparts[k].size());
-            });
-            p->gtcode.resize(4 * n0);
-            parallel_for_trees(p->n_trees, [&](int64_t t) {
-                const int bkt = bucket_of(t), GC = WIDTH[bkt % NW];
-                const uint32_t RB = 64u * (uint32_t)(1 + bkt / NW) * es32;
-                const uint32_t sbytes = (uint32_t)std::max<int64_t>((int64_t)slots[bkt] * (1 + GC), (int64_t)GC) * RB; // one wave's slot area
-                for (int32_t i = p->gtcode_off[(size_t)t]; i < p->gtcode_off[(size_t)t + 1]; i++)
-                    for (uint32_t w = 1; w < 4; w++) {
-                        BoundInstr r = p->gtcode[(size_t)i];
-                        if (kinds[(size_t)i] == 1) r.arg += w * sbytes; // (the low 24 bits: an LDS offset < 2^18)
-                        else if (kinds[(size_t)i] == 2) r.lo += w * sbytes;
-                        p->gtcode[(size_t)w * n0 + (size_t)i] = r;
-                    }
-            });
-            p->gt_share = true;
-            p->gt_stride = (int64_t)n0;
-            dbg_lap("grad threaded: stream variants (shared leaf rows)");
-        }
-        std::vector<int32_t> ids((size_t)p->n_trees);
-        int32_t start[NB], run = 0;
-        for (int b = 0; b < NB; b++) { start[b] = run; run += count[b]; }
-        {
-            int32_t fill[NB];
-            for (int b = 0; b < NB; b++) fill[b] = start[b];
-            for (int64_t t = 0; t < p->n_trees; t++) ids[(size_t)fill[bucket_of(t)]++] = (int32_t)t;
-        }
+        if (enc < 0) return fail(c, DE_ERR_HIP, "gradient program: the host threads' partitions disagree");
+        if (enc != GRAD_ENC_OK) return DE_OK;
+        p->gtcode = std::move(r.gtcode);
+        p->gtcode_off = std::move(r.gtcode_off);
+        p->gtsite_of_gb = std::move(r.gtsite_of_gb);
+        p->gt_share = r.share;
+        p->gt_stride = r.stride;
         // a unary operator on a constant leaf becomes two instructions: at most twice the bound program
         // ... plus one end record per tree and one of padding (every handler reads the record behind its own)
-        const size_t gt_cap = (2 * p->gbcode.size() + (size_t)p->n_trees + 1) * (share ? 4 : 1);
+        const size_t gt_cap = (2 * p->gbcode.size() + (size_t)p->n_trees + 1) * (r.share ? 4 : 1);
         if (p->d_gtcode && p->gt_cap < gt_cap) { // (DE_GRAD_SHARE switched between two encodings of one program: tests)
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             prog_free(c, p->d_gtcode);
@@ -390,39 +125,24 @@ static int ensure_grad_threaded(de_ctx *c, de_program *p, int mode, const std::v
         }
         if (!p->d_gtcode) {
             p->gt_cap = gt_cap;
-            // (inside one 4 GiB window: the handlers bump the record pointer without a carry; a straddling allocation is set aside and redone)
-            {
-                const hipError_t ast = prog_malloc(c, reinterpret_cast<void **>(&p->d_gtcode), gt_cap * sizeof(BoundInstr));
-                if (ast != hipSuccess) return fail(c, DE_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(ast));
-                if (!in_one_window(p->d_gtcode, gt_cap * sizeof(BoundInstr))) return fail(c, DE_ERR_HIP, "gradient instruction stream straddles a 4 GiB boundary");
-            }
-            HIP_TRY(c, hipMemset(p->d_gtcode, 0, gt_cap * sizeof(BoundInstr)));
+            const int rc = stream_alloc(c, &p->d_gtcode, gt_cap, "gradient");
+            if (rc != DE_OK) return rc;
             HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_gtcode_off), p->gtcode_off.size() * sizeof(int32_t)));
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_gt_ids), std::max<size_t>(ids.size(), 1) * sizeof(int32_t)));
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_gt_ids), std::max<size_t>(r.ids.size(), 1) * sizeof(int32_t)));
         }
         dbg_lap("grad threaded: ids, hipMalloc, memset");
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // the previous form may be in use by queued work
-        if (!p->gtcode.empty())
-            HIP_TRY(c, hipMemcpy(p->d_gtcode, p->gtcode.data(), p->gtcode.size() * sizeof(BoundInstr), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(p->d_gtcode_off, p->gtcode_off.data(), p->gtcode_off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!ids.empty()) HIP_TRY(c, hipMemcpy(p->d_gt_ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        p->gt_n_buckets = 0;
-        for (int b = 0; b < NB; b++) {
-            if (!count[b]) continue;
-            GradArgs::Bucket &bk = p->gt_buckets[p->gt_n_buckets++];
-            bk.GC = WIDTH[b % NW];
-            bk.VS = 1 + b / NW;
-            bk.windows = b % NW >= 7 ? (maxg[b] + bk.GC - 1) / bk.GC : 1;
-            bk.max_grad = maxg[b];
-            bk.n_slots = slots[b];
-            bk.ids = p->d_gt_ids + start[b];
-            bk.n = count[b];
-            bk.handler_base = bases[b];
-            bk.param_handler_off = (uint32_t)(tables[b][gop_param(WIDTH[b % NW])] - bases[b]);
+        HIP_TRY(c, upload(p->d_gtcode, p->gtcode));
+        HIP_TRY(c, upload(p->d_gtcode_off, p->gtcode_off));
+        HIP_TRY(c, upload(p->d_gt_ids, r.ids));
+        p->gt_n_buckets = r.n_buckets;
+        for (int b = 0; b < r.n_buckets; b++) {
+            const GradForwardStream::Bucket &rb = r.buckets[b];
+            p->gt_buckets[b] = GradArgs::Bucket{rb.GC, rb.VS, rb.windows, rb.max_grad, rb.slots, p->d_gt_ids + rb.start, rb.count, rb.handler_base, rb.param_handler_off};
         }
         dbg_lap("grad threaded: upload");
         p->gt_mode = mode;
-        p->gt_wide = wide;
+        p->gt_wide = opt.wide;
         p->gt_valid = true;
     }
     g->threaded_code = p->d_gtcode;
@@ -459,427 +179,47 @@ static int ensure_rev_threaded(de_ctx *c, de_program *p, int mode, GradArgs *g) 
         for (int64_t t = 0; t < p->n_trees; t++) total += de_program_n_grad(p, t, mode);
         if (total < 8 * p->n_trees) return DE_OK;
     }
-    const int F = p->n_features, P = p->n_params;
     if (!(p->rt_valid && p->rt_mode == mode)) {
-        const uint32_t es32 = p->dtype == DE_F32 ? 4u : 8u, RB = 64u * es32;
-        // parameter leaves are LDS rows F .. F+P (gathered by class when the kernel stages a tile), slots follow
-        const uint32_t FE = (uint32_t)F + (p->uses_params ? (uint32_t)P : 0u);
-        const bool hot_const_unary = !getenv("DE_NO_CONST_UNARY_HOT");
-        auto gun_of = [&](uint32_t op) { // hot unary index of a de_opcode (de_bind.h), or -1
-            return hot_const_unary ? gun_index((int)op, DE_U_COS, DE_U_EXP, DE_U_SIN, DE_U_NEG, DE_U_SQUARE, DE_U_CUBE, DE_U_ABS, DE_U_LOG, DE_U_SAFE_LOG,
-                                               DE_U_SQRT, DE_U_SAFE_SQRT, DE_U_TANH, DE_U_RELU) : -1;
-        };
-        const uint32_t PR0 = FE + (uint32_t)p->n_slots; // first partial row
         uint64_t table[ROP_COUNT];
         hipError_t hst = rev_handler_table(p->dtype, table);
         if (hst != hipSuccess) return fail(c, DE_ERR_HIP, "reverse handler table: %s", hipGetErrorString(hst));
-        uint64_t base = table[0];
-        for (int i = 0; i < (int)ROP_COUNT; i++) base = std::min<uint64_t>(base, table[i]);
-        for (int i = 0; i < (int)ROP_COUNT; i++)
-            if (table[i] - base > 0xFFFFFFFFull) return DE_OK;
-        constexpr uint32_t NONE = 0xFFFFFFFFu, ACC = 0x80000000u;
-        auto leaf_col = [&](uint32_t f) -> uint32_t { return mode != DE_GRAD_CONSTANT ? (1u + (uint32_t)P + f) | ACC : NONE; };
-        auto param_col = [&](uint32_t r) -> uint32_t { return mode != DE_GRAD_CONSTANT ? (1u + r) | ACC : NONE; };
-        auto const_col = [&](uint32_t ord) -> uint32_t {
-            return mode == DE_GRAD_CONSTANT ? 1u + ord : (mode == DE_GRAD_BOTH ? 1u + (uint32_t)(P + F) + ord : NONE);
-        };
-        auto rowb = [&](uint32_t row) { return (row < (uint32_t)F ? row : row + (FE - (uint32_t)F)) * RB; }; // LDS byte offset of a bound row
-        p->rtcode.clear();
-        p->rtcode_off.assign((size_t)p->n_trees + 1, 0);
-        p->rtcode_mid.assign((size_t)p->n_trees, 0);
-        p->rtsite_of_gb.assign(p->gbcode.size(), -1);
+        GradHandlers h{table, 0};
+        if (!handler_base(table, ROP_COUNT, &h.base)) return DE_OK;
+        const GradEncodeOptions opt = grad_encode_env();
+        std::vector<int32_t> ng((size_t)p->n_trees);
+        for (int64_t t = 0; t < p->n_trees; t++) ng[(size_t)t] = (int32_t)de_program_n_grad(p, t, mode);
+        const GradSource src{p->gbcode, p->gbcode_off, p->n_trees, p->n_features, p->n_params, p->uses_params, p->dtype, mode, ng.data()};
+        GradReverseStream r;
+        const int enc = encode_grad_reverse(src, opt, p->n_slots, p->cse_generic, h, &r);
+        p->rtsite_of_gb.clear();
         p->site_gen++;
-        uint32_t max_prows = 0;
-        bool ok = true;
-        std::vector<uint32_t> need((size_t)p->n_trees, 0);
-        std::vector<BoundInstr> rv;
-        std::vector<uint8_t> rv_col; // rv[k] carries a gradient column word in .lo
-        std::vector<uint32_t> rv_rop; // rop of rv[k]
-        std::vector<BoundInstr> bw;   // a tree's backward records in execution order
-        std::vector<uint32_t> bw_rop;
-        std::vector<uint8_t> acc_use; // per instruction of the tree: reads a shared row and is not its last reader (adds its adjoint)
-        std::map<uint32_t, std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> occ; // column -> (leaves, (seen, row))
-        std::map<uint32_t, uint32_t> rop_of_off; // handler offset -> rop id (DE_REV_STATS)
-        uint32_t mk_rop = 0;                     // rop of the record `mk` made last (the emitters below read it)
-        const bool rfuse = !getenv("DE_REV_NO_FUSE"); // fused pairs / triples (de_rev_threaded.hip rh_pushload ...): same bits, fewer dispatches
-        auto mk = [&](uint32_t rop, uint32_t y, uint32_t z, uint32_t w) {
-            BoundInstr o;
-            o.bop = (uint32_t)(table[rop] - base);
-            rop_of_off[o.bop] = rop;
-            mk_rop = rop;
-            o.arg = y;
-            o.lo = z;
-            o.hi = w;
-            return o;
-        };
-        for (int64_t t = 0; t < p->n_trees && ok; t++) {
-            uint32_t n_prows = 0;
-            rv.clear();
-            rv_col.clear();
-            rv_rop.clear();
-            auto alloc = [&](uint32_t n) { const uint32_t r = (PR0 + n_prows) * RB; n_prows += n; return r; };
-            uint32_t last_f_rop = 0xFFFFFFFFu; // rop of this tree's last forward record
-            auto F_ = [&](const BoundInstr &o) -> int32_t {
-                const uint32_t rop = mk_rop;
-                if (rfuse && last_f_rop == ROP_PUSH) { // PUSH + the load / unary function of a leaf that starts the next subtree: one record
-                    const uint32_t push_off = p->rtcode.back().arg;
-                    const bool un_leaf = rop >= ROP_UN_BASE && rop < ROP_GEN_BASE && (((rop - ROP_UN_BASE) >> 1) & 1u);
-                    BoundInstr f{0u, 0u, 0u, 0u};
-                    bool fused = false;
-                    if (rop == rop_load(RSRC_LEAF) && push_off < 65536u && o.arg < 65536u) { f = mk(ROP_F_PUSHLOAD_BASE + 0, push_off | (o.arg << 16), 0, 0); fused = true; }
-                    else if (rop == rop_load(RSRC_CONST) && push_off < 65536u) { f = mk(ROP_F_PUSHLOAD_BASE + 1, push_off, o.lo, o.hi); fused = true; }
-                    else if (un_leaf && push_off < 65536u && o.arg < 65536u) {
-                        const uint32_t v = rop - ROP_UN_BASE;
-                        f = mk(rop_pushun((int)(v >> 2), (v & 1u) != 0), push_off | (o.arg << 16), o.lo, 0);
-                        fused = true;
-                    }
-                    if (fused) {
-                        p->rtcode.back() = f;
-                        last_f_rop = 0xFFFFFFFEu;
-                        return (int32_t)p->rtcode.size() - 1;
-                    }
-                }
-                p->rtcode.push_back(o);
-                last_f_rop = rop;
-                return (int32_t)p->rtcode.size() - 1; // (the record that carries o's immediate: de_program_set_consts patches it there)
-            };
-            auto R_ = [&](const BoundInstr &o, bool has_col = false) { rv.push_back(o); rv_col.push_back(has_col ? 1 : 0); rv_rop.push_back(mk_rop); }; // pushed in forward order, reversed below
-            // SHARED ROWS.  A slot row is written by a PUSH and normally read once; a GraphNode program reads a persistent row from several
-            // consumers.  Backwards the consumers run in reverse order and the definition's r_pop last: the consumer that runs FIRST in the
-            // backward sweep (the last reader in program order) stores its adjoint contribution into the row, every other one adds to it.
-            // acc_use[i] = instruction i reads a slot row and is NOT that row's last reader before its next PUSH.
-            acc_use.assign((size_t)(p->gbcode_off[(size_t)t + 1] - p->gbcode_off[(size_t)t]), 0);
-            {
-                std::map<uint32_t, int32_t> last_reader; // slot row -> the last instruction seen reading it since its PUSH
-                for (int32_t i = p->gbcode_off[(size_t)t]; i < p->gbcode_off[(size_t)t + 1]; i++) {
-                    const BoundInstr &b = p->gbcode[(size_t)i];
-                    const uint32_t row = b.arg & 0xFFFFFFu;
-                    if (b.bop == BOP_PUSH) { last_reader.erase(row); continue; }
-                    const bool reads_row = b.bop == BOP_LOAD_ROW || b.bop == BOP_GEN_ROW || (b.bop >= BOP_BIN_BASE && b.bop < BOP_BIN_END && !((b.bop - BOP_BIN_BASE) & 2)) ||
-                                           (b.bop >= BOP_UN_BASE && b.bop < BOP_UN_END && ((b.bop - BOP_UN_BASE) & 2));
-                    if (!reads_row || row < (uint32_t)F) continue;
-                    auto it = last_reader.find(row);
-                    if (it != last_reader.end()) acc_use[(size_t)(it->second - p->gbcode_off[(size_t)t])] = 1; // no longer the last reader: it adds
-                    last_reader[row] = i;
-                }
-            }
-            auto accumulates = [&](int32_t i) { return acc_use[(size_t)(i - p->gbcode_off[(size_t)t])] != 0; };
-            // backward of "acc' = op(acc, operand)" whose partial rows (d/d acc, d/d operand) start at pr
-            auto back_binary = [&](int pk, uint32_t pr, bool slot, uint32_t slot_byte, uint32_t col, bool add = false) {
-                if (slot && add) R_(mk(ROP_R_BINACC_BASE + (uint32_t)pk, pk == 0 ? pr : 0, slot_byte, 0));
-                else if (slot) R_(mk(rop_rbin(pk, 0), pk == 0 ? pr : 0, slot_byte, 0));
-                else if (col != NONE) R_(mk(rop_rbin(pk, 1), pk == 0 ? pr : 0, col, 0), true);
-                else if (pk == 0) R_(mk(ROP_R_UN, pr, 0, 0));
-                else if (pk == 3) R_(mk(ROP_R_NEG, 0, 0, 0));
-            };
-            // backward of "acc' = f(leaf)": first the unary partial, then the leaf's row — pushed in reverse
-            auto back_unary_leaf = [&](uint32_t pr, uint32_t col) {
-                if (col != NONE) R_(mk(ROP_R_LEAF, 0, col, 0), true);
-                R_(mk(ROP_R_UN, pr, 0, 0));
-            };
-            // backward of "acc' = f(shared row)": the unary partial, then the row's adjoint receives the result
-            auto back_unary_slot = [&](uint32_t pr, uint32_t slot_byte, bool add) {
-                R_(mk(ROP_R_SLOTACC_BASE + (add ? 1u : 0u), slot_byte, 0, 0));
-                R_(mk(ROP_R_UN, pr, 0, 0));
-            };
-            for (int32_t i = p->gbcode_off[(size_t)t]; i < p->gbcode_off[(size_t)t + 1] && ok; i++) {
-                const BoundInstr &b = p->gbcode[(size_t)i];
-                const uint32_t row = b.arg & 0xFFFFFFu, aux = b.arg >> 24, ord = b.arg & 0xFFFFu;
-                const bool is_leaf = row < (uint32_t)F;
-                if (b.bop == BOP_CHECK_ROW) continue; // leaf operands are tested where they are read
-                if (b.bop == BOP_LOAD_ROW && !is_leaf) { // acc = a shared (persistent) row
-                    F_(mk(rop_load(RSRC_SLOT), rowb(row), 0, 0));
-                    R_(mk(ROP_R_SLOTACC_BASE + (accumulates(i) ? 1u : 0u), rowb(row), 0, 0));
-                } else if (b.bop == BOP_LOAD_ROW) {
-                    F_(mk(rop_load(RSRC_LEAF), rowb(row), 0, 0));
-                    if (leaf_col(row) != NONE) R_(mk(ROP_R_LEAF, 0, leaf_col(row), 0), true);
-                } else if (b.bop == BOP_LOAD_CONST) {
-                    p->rtsite_of_gb[(size_t)i] = F_(mk(rop_load(RSRC_CONST), 0, b.lo, b.hi));
-                    if (const_col(ord) != NONE) R_(mk(ROP_R_LEAF, 0, const_col(ord), 0), true);
-                } else if (b.bop == BOP_PUSH) {
-                    // A spill is followed by the load that starts the next subtree (the accumulator's value is dead: the backward sweep
-                    // continues with the slot's adjoint).  A SHARED definition that is used at once stays in the accumulator: the next
-                    // instruction reads it, and backwards BOTH adjoints — the accumulator's and the row's — flow into the definition.
-                    bool acc_live = false;
-                    for (int32_t q = i + 1; q < p->gbcode_off[(size_t)t + 1]; q++) {
-                        const BoundInstr &nx = p->gbcode[(size_t)q];
-                        if (nx.bop == BOP_CHECK_ROW || nx.bop == BOP_CHECK_ACC || nx.bop == BOP_PUSH) continue;
-                        const uint32_t nau = nx.arg >> 24;
-                        acc_live = top_reads_acc(nx.bop, nau == (uint32_t)DOP_LOAD ? 0 : de_opcode_degree((int)nau));
-                        break;
-                    }
-                    F_(mk(ROP_PUSH, rowb(row), 0, 0));
-                    R_(mk(acc_live ? (uint32_t)ROP_R_POPADD : (uint32_t)ROP_R_POP, rowb(row), 0, 0));
-                } else if (b.bop == BOP_CHECK_ACC) {
-                    F_(mk(ROP_CHECK, 0, 0, 0));
-                } else if (b.bop >= BOP_BIN_BASE && b.bop < BOP_BIN_END) {
-                    const uint32_t v = b.bop - BOP_BIN_BASE;
-                    const int k = (int)(v >> 2);
-                    const bool cst = (v & 2) != 0, chk = (v & 1) != 0;
-                    const uint32_t pr = k >= 3 ? alloc(2) : 0;
-                    const int pk = k == 0 ? 1 : (k == 1 ? 2 : (k == 2 ? 3 : 0));
-                    if (cst) {
-                                                p->rtsite_of_gb[(size_t)i] = F_(mk(rop_bin(k, RSRC_CONST, chk), pr, b.lo, b.hi));
-                        back_binary(pk, pr, false, 0, const_col(ord));
-                    } else {
-                        F_(mk(rop_bin(k, is_leaf ? RSRC_LEAF : RSRC_SLOT, chk), rowb(row), pr, 0));
-                        back_binary(pk, pr, !is_leaf, rowb(row), is_leaf ? leaf_col(row) : NONE, !is_leaf && accumulates(i));
-                    }
-                } else if (b.bop >= BOP_UN_BASE && b.bop < BOP_UN_END) {
-                    const uint32_t v = b.bop - BOP_UN_BASE;
-                    const int k = (int)(v >> 2);
-                    const bool from_row = (v & 2) != 0, chk = (v & 1) != 0;
-                    const uint32_t pr = alloc(1);
-                    if (from_row && !is_leaf) { // unary function of a shared row
-                        F_(mk(rop_un_slot(k, chk), rowb(row), pr, 0));
-                        back_unary_slot(pr, rowb(row), accumulates(i));
-                    } else if (from_row) {
-                        F_(mk(rop_un(k, RSRC_LEAF, chk), rowb(row), pr, 0));
-                        back_unary_leaf(pr, leaf_col(row));
-                    } else {
-                        F_(mk(rop_un(k, RSRC_ACC, chk), pr, 0, 0));
-                        R_(mk(ROP_R_UN, pr, 0, 0));
-                    }
-                } else if (b.bop == BOP_GEN_ROW && hot_const_unary && (aux == (uint32_t)DE_B_MAX || aux == (uint32_t)DE_B_MIN)) {
-                    const uint32_t pr = alloc(2);
-                    F_(mk(rop_bin(aux == (uint32_t)DE_B_MAX ? 6 : 7, is_leaf ? RSRC_LEAF : RSRC_SLOT, false), rowb(row), pr, 0));
-                    back_binary(0, pr, !is_leaf, rowb(row), is_leaf ? leaf_col(row) : NONE, !is_leaf && accumulates(i));
-                } else if (b.bop == BOP_GEN_ROW && gun_of(aux) >= 0 && is_leaf) {
-                    const uint32_t pr = alloc(1);
-                    F_(mk(rop_un(gun_of(aux), RSRC_LEAF, false), rowb(row), pr, 0));
-                    back_unary_leaf(pr, leaf_col(row));
-                } else if (b.bop == BOP_GEN_ROW) {
-                    const bool unary = aux < (uint32_t)DE_B_ADD;
-                    const uint32_t pr = alloc(unary ? 1 : 2);
-                    F_(mk(rop_gen(is_leaf ? RSRC_LEAF : RSRC_SLOT), rowb(row), pr | (aux << 24), 0));
-                    if (unary && !is_leaf) back_unary_slot(pr, rowb(row), accumulates(i));
-                    else if (unary) back_unary_leaf(pr, leaf_col(row));
-                    else back_binary(0, pr, !is_leaf, rowb(row), is_leaf ? leaf_col(row) : NONE, !is_leaf && accumulates(i));
-                } else if (b.bop == BOP_GEN_CONST && hot_const_unary && (aux == (uint32_t)DE_B_MAX || aux == (uint32_t)DE_B_MIN)) {
-                    const uint32_t pr = alloc(2);
-                    p->rtsite_of_gb[(size_t)i] = F_(mk(rop_bin(aux == (uint32_t)DE_B_MAX ? 6 : 7, RSRC_CONST, false), pr, b.lo, b.hi));
-                    back_binary(0, pr, false, 0, const_col(ord));
-                } else if (b.bop == BOP_GEN_CONST && gun_of(aux) >= 0) {
-                    // cos / exp / sin of a constant leaf: load + hot unary handler instead of the generic one
-                    const uint32_t pr = alloc(1);
-                    p->rtsite_of_gb[(size_t)i] = F_(mk(rop_load(RSRC_CONST), 0, b.lo, b.hi));
-                    F_(mk(rop_un(gun_of(aux), RSRC_ACC, false), pr, 0, 0));
-                    back_unary_leaf(pr, const_col(ord));
-                } else if (b.bop == BOP_GEN_CONST) {
-                    const bool unary = aux < (uint32_t)DE_B_ADD;
-                    const uint32_t pr = alloc(unary ? 1 : 2);
-                    p->rtsite_of_gb[(size_t)i] = F_(mk(rop_gen(RSRC_CONST), pr | (aux << 24), b.lo, b.hi));
-                    if (unary) back_unary_leaf(pr, const_col(ord));
-                    else back_binary(0, pr, false, 0, const_col(ord));
-                } else if (b.bop == BOP_GEN_ACC && gun_of(aux) >= 0) {
-                    const uint32_t pr = alloc(1);
-                    F_(mk(rop_un(gun_of(aux), RSRC_ACC, false), pr, 0, 0));
-                    R_(mk(ROP_R_UN, pr, 0, 0));
-                } else if (b.bop == BOP_GEN_ACC) {
-                    const uint32_t pr = alloc(1);
-                    F_(mk(rop_gen(RSRC_ACC), pr | (aux << 24), 0, 0));
-                    R_(mk(ROP_R_UN, pr, 0, 0));
-                } else if (b.bop == BOP_GEN_PARAM) { // operand = parameter row prm = LDS leaf row F + prm
-                    const uint32_t prm = b.arg & 0xFFFFu, prow = ((uint32_t)F + prm) * RB;
-                    int k = -1, ku = -1;
-                    switch (aux) {
-                    case DE_B_ADD: k = 0; break;
-                    case DE_B_SUB: k = 1; break;
-                    case DOP_RSUB: k = 2; break;
-                    case DE_B_MUL: k = 3; break;
-                    case DE_B_DIV: k = 4; break;
-                    case DOP_RDIV: k = 5; break;
-                    case DE_B_MAX: k = hot_const_unary ? 6 : -1; break;
-                    case DE_B_MIN: k = hot_const_unary ? 7 : -1; break;
-                    default: ku = gun_of(aux); break;
-                    }
-                    if (aux == (uint32_t)DOP_LOAD) {
-                        F_(mk(rop_load(RSRC_LEAF), prow, 0, 0));
-                        if (param_col(prm) != NONE) R_(mk(ROP_R_LEAF, 0, param_col(prm), 0), true);
-                    } else if (k >= 0) {
-                        const uint32_t pr = k >= 3 ? alloc(2) : 0;
-                        F_(mk(rop_bin(k, RSRC_LEAF, false), prow, pr, 0));
-                        back_binary(k == 0 ? 1 : (k == 1 ? 2 : (k == 2 ? 3 : 0)), pr, false, 0, param_col(prm));
-                    } else if (ku >= 0) {
-                        const uint32_t pr = alloc(1);
-                        F_(mk(rop_un(ku, RSRC_LEAF, false), prow, pr, 0));
-                        back_unary_leaf(pr, param_col(prm));
-                    } else {
-                        const bool unary = aux < (uint32_t)DE_B_ADD;
-                        const uint32_t pr = alloc(unary ? 1 : 2);
-                        F_(mk(rop_gen(RSRC_LEAF), prow, pr | (aux << 24), 0));
-                        if (unary) back_unary_leaf(pr, param_col(prm));
-                        else back_binary(0, pr, false, 0, param_col(prm));
-                    }
-                } else if (b.bop == BOP_TERN) {
-                    if (is_leaf || b.lo < (uint32_t)F || row > 0xFFFFu || b.lo > 0xFFFFu) { ok = false; break; }
-                    if (p->cse_generic) { ok = false; break; } // (a ternary operator's slot operands may be shared rows: r_tern stores; such populations keep forward duals)
-                    const uint32_t pr = alloc(3);
-                    const uint32_t rb_ = row + (FE - (uint32_t)F), rc_ = b.lo + (FE - (uint32_t)F);
-                    if (rb_ > 0xFFFFu || rc_ > 0xFFFFu) { ok = false; break; }
-                    F_(mk(ROP_TERN, pr | (aux << 24), rb_ | (rc_ << 16), 0));
-                    R_(mk(ROP_R_TERN, pr, rb_ | (rc_ << 16), 0));
-                } else ok = false; // INJ_*: only bound with early_exit=false, never for gradients
-            }
-            if (!ok) break;
-            // end record of the forward sweep (r_end: the table slot of round 1's parameter handler); the backward sweep's
-            // first record follows it
-            p->rtcode.push_back(mk(ROP_PARAM, 0, 0, 0));
-            p->rtcode_mid[(size_t)t] = (int32_t)p->rtcode.size();
-            // Gradient rows several leaves share (features, parameters): the leaves' contributions are added per
-            // SAMPLE in an LDS row and reduced once, at the last of them — paths that cancel within a sample then
-            // cancel before the reduction, as they do in the forward Jacobian.
-            // column word: [15:0] column, [29:16] accumulation row, [31:30] 0 reduce now, 1 first, 2 middle, 3 last
-            occ.clear();
-            for (size_t k = 0; k < rv.size(); k++)
-                if (rv_col[k] && (rv[k].lo & ACC)) occ[rv[k].lo & 0xFFFFu].first++;
-            uint32_t n_acc = 0;
-            bw.clear();
-            bw_rop.clear();
-            for (size_t k = rv.size(); k-- > 0;) { // execution order
-                BoundInstr o = rv[k];
-                if (rv_col[k]) {
-                    const uint32_t col = o.lo & 0xFFFFu;
-                    if ((o.lo & 0x7FFFFFFFu) > 0xFFFFu) { ok = false; break; }
-                    uint32_t word = col;
-                    if (o.lo & ACC) {
-                        auto &oc = occ[col];
-                        if (oc.first > 1) {
-                            if (oc.second.first == 0) oc.second.second = n_acc++;
-                            const uint32_t nth = ++oc.second.first;
-                            const uint32_t md = nth == 1 ? 1u : (nth == oc.first ? 3u : 2u);
-                            word = col | ((PR0 + n_prows + oc.second.second) << 16) | (md << 30);
-                        }
-                    }
-                    o.lo = word;
-                }
-                bw.push_back(o);
-                bw_rop.push_back(rv_rop[k]);
-            }
-            if (!ok) break;
-            for (size_t k = 0; k < bw.size();) { // fused backward sequences: [r_un] r_leaf [r_pop]  and  r_bin<PK, column> r_leaf [r_pop]
-                auto is = [&](size_t q, uint32_t rop) { return q < bw.size() && bw_rop[q] == rop; };
-                auto small = [&](size_t q) { return q >= bw.size() || bw[q].arg < 65536u; };
-                if (rfuse && is(k, ROP_R_UN) && is(k + 1, ROP_R_LEAF) && small(k) && (!is(k + 2, ROP_R_POP) || small(k + 2))) {
-                    const bool pop = is(k + 2, ROP_R_POP);
-                    p->rtcode.push_back(mk(rop_leafx(true, pop), bw[k].arg | (pop ? bw[k + 2].arg << 16 : 0u), bw[k + 1].lo, 0));
-                    k += pop ? 3 : 2;
-                } else if (rfuse && is(k, ROP_R_LEAF) && is(k + 1, ROP_R_POP) && small(k + 1)) {
-                    p->rtcode.push_back(mk(rop_leafx(false, true), bw[k + 1].arg << 16, bw[k].lo, 0));
-                    k += 2;
-                } else if (rfuse && k < bw.size() && bw_rop[k] >= ROP_R_BIN_BASE && bw_rop[k] < ROP_R_TERN && ((bw_rop[k] - ROP_R_BIN_BASE) & 1u) && is(k + 1, ROP_R_LEAF) &&
-                           small(k) && (!is(k + 2, ROP_R_POP) || small(k + 2))) {
-                    const bool pop = is(k + 2, ROP_R_POP);
-                    p->rtcode.push_back(mk(rop_bincolx((int)((bw_rop[k] - ROP_R_BIN_BASE) >> 1), pop), bw[k].arg | (pop ? bw[k + 2].arg << 16 : 0u), bw[k].lo, bw[k + 1].lo));
-                    k += pop ? 3 : 2;
-                } else {
-                    p->rtcode.push_back(bw[k]);
-                    k += 1;
-                }
-            }
-            if (PR0 + n_prows + n_acc > 0x3FFFu) { ok = false; break; }
-            p->rtcode.push_back(mk(ROP_PARAM, 0, 0, 0)); // end record of the backward sweep
-            p->rtcode_off[(size_t)t + 1] = (int32_t)p->rtcode.size();
-            max_prows = std::max(max_prows, n_prows + n_acc);
-            need[(size_t)t] = n_prows + n_acc;
-        }
-        if (getenv("DE_REV_STATS") && ok) { // dispatch classes and adjacent pairs of the two sweeps (what a fusion would save)
-            auto cls = [&](uint32_t off) -> std::string {
-                const uint32_t r = rop_of_off.count(off) ? rop_of_off[off] : 9999u;
-                char buf[48];
-                if (r < 3) snprintf(buf, sizeof buf, "LOAD%c", "LSC"[r]);
-                else if (r == ROP_PUSH) return "PUSH";
-                else if (r == ROP_CHECK) return "CHECK";
-                else if (r >= ROP_BIN_BASE && r < ROP_UN_BASE) snprintf(buf, sizeof buf, "BIN%c", "LSC"[((r - ROP_BIN_BASE) / 2) % 3]);
-                else if (r >= ROP_UN_BASE && r < ROP_GEN_BASE) snprintf(buf, sizeof buf, "UN%c", ((r - ROP_UN_BASE) / 2) % 2 ? 'L' : 'A');
-                else if (r >= ROP_GEN_BASE && r < ROP_TERN) return "GEN";
-                else if (r == ROP_PARAM) return "END";
-                else if (r == ROP_R_UN) return "r_un";
-                else if (r == ROP_R_NEG) return "r_neg";
-                else if (r == ROP_R_POP) return "r_pop";
-                else if (r == ROP_R_LEAF) return "r_leaf";
-                else if (r >= ROP_R_BIN_BASE && r < ROP_R_TERN) snprintf(buf, sizeof buf, "r_bin%s", (r - ROP_R_BIN_BASE) % 2 ? "col" : "slot");
-                else if (r >= ROP_F_PUSHLOAD_BASE && r < ROP_R_LEAFX_BASE) return "PUSH+";
-                else if (r >= ROP_R_LEAFX_BASE && r < ROP_R_BINCOLX_BASE) return "r_leafx";
-                else if (r >= ROP_R_BINCOLX_BASE && r < ROP_COUNT) return "r_bincolx";
-                else return "other";
-                return buf;
-            };
-            std::map<std::string, int64_t> one, two;
-            for (size_t i = 0; i < p->rtcode.size(); i++) {
-                const std::string a = cls(p->rtcode[i].bop);
-                one[a]++;
-                if (i + 1 < p->rtcode.size() && a != "END") two[a + " " + cls(p->rtcode[i + 1].bop)]++;
-            }
-            fprintf(stderr, "DE_REV_STATS: %zu records, %lld trees: %.2f dispatches per tree\n", p->rtcode.size(), (long long)p->n_trees, (double)p->rtcode.size() / (double)p->n_trees);
-            for (auto &kv : one) fprintf(stderr, "  %-10s %8.3f per tree\n", kv.first.c_str(), (double)kv.second / (double)p->n_trees);
-            std::vector<std::pair<int64_t, std::string>> v;
-            for (auto &kv : two) v.push_back({kv.second, kv.first});
-            std::sort(v.rbegin(), v.rend());
-            for (size_t i = 0; i < v.size() && i < 24; i++) fprintf(stderr, "  pair %-22s %8.3f per tree\n", v[i].second.c_str(), (double)v[i].first / (double)p->n_trees);
-        }
-        // per-wave staging of the column sums: one LDS row, or the widest tree's columns
-        int64_t stage_cols = 64;
-        for (int64_t t = 0; t < p->n_trees; t++) stage_cols = std::max<int64_t>(stage_cols, 1 + de_program_n_grad(p, t, mode));
-        const uint64_t stage_rows = ((uint64_t)stage_cols * es32 + RB - 1) / RB;
-        const uint64_t rows = (uint64_t)PR0 + max_prows + stage_rows;
-        if (!ok || 4 * rows * RB > 160 * 1024 || rows * RB >= (1u << 24)) { p->rtsite_of_gb.clear(); p->site_gen++; return DE_OK; }
-        // The kernel is latency-bound and its occupancy is set by the LDS rows of the neediest tree of a launch
-        // (5 -> 4 workgroups per CU: +17 % time): trees are grouped by the number of workgroups per CU their own
-        // need allows and every group is a launch of its own (small groups join the next needier one).
-        auto wgs_of = [&](uint32_t nd) { return (int)std::min<uint64_t>(8, (160 * 1024) / (4 * ((uint64_t)PR0 + nd + stage_rows) * RB)); };
-        std::vector<int32_t> ids((size_t)p->n_trees);
-        for (int64_t t = 0; t < p->n_trees; t++) ids[(size_t)t] = (int32_t)t;
-        std::stable_sort(ids.begin(), ids.end(), [&](int32_t x, int32_t y) { return need[(size_t)x] < need[(size_t)y]; });
-        p->rt_n_groups = 0;
-        const bool grouping = true;
-        for (int64_t k = 0; k < p->n_trees;) {
-            int64_t e = k;
-            const int w = wgs_of(need[(size_t)ids[(size_t)k]]);
-            while (e < p->n_trees && grouping && wgs_of(need[(size_t)ids[(size_t)e]]) == w) e++;
-            if (!grouping) e = p->n_trees;
-            // a group too small to fill the chip, or the last slot: extend to the end / absorb into the next group
-            if (p->rt_n_groups == 7) e = p->n_trees;
-            while (e < p->n_trees && e - k < std::max<int64_t>(64, p->n_trees / 16)) e++;
-            if (p->n_trees - e < std::max<int64_t>(64, p->n_trees / 16)) e = p->n_trees;
-            GradArgs::RevGroup &gr = p->rt_groups[p->rt_n_groups++];
-            gr.first = (int32_t)k;
-            gr.n = (int32_t)(e - k);
-            gr.rows = (int32_t)(PR0 + need[(size_t)ids[(size_t)e - 1]] + stage_rows);
-            std::sort(ids.begin() + k, ids.begin() + e); // tree order inside a group: adjacent trees share staging batches
-            k = e;
-        }
-        for (int64_t t = 0; t < p->n_trees; t++) {
-            successor_words(p->rtcode, p->rtcode_off[(size_t)t], p->rtcode_mid[(size_t)t]);
-            successor_words(p->rtcode, p->rtcode_mid[(size_t)t], p->rtcode_off[(size_t)t + 1]);
-        }
+        if (enc != GRAD_ENC_OK) return DE_OK;
+        if (getenv("DE_REV_STATS")) reverse_stream_stats(r, p->n_trees, h);
+        p->rtcode = std::move(r.rtcode);
+        p->rtcode_off = std::move(r.rtcode_off);
+        p->rtcode_mid = std::move(r.rtcode_mid);
+        p->rtsite_of_gb = std::move(r.rtsite_of_gb);
+        p->rt_n_groups = r.n_groups;
+        for (int k = 0; k < r.n_groups; k++) p->rt_groups[k] = GradArgs::RevGroup{r.groups[k].first, r.groups[k].n, r.groups[k].rows};
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // the previous form may be in use by queued work
         if (p->d_rtcode) { // sizes depend on the mode
             prog_free(c, p->d_rtcode);
             p->d_rtcode = nullptr;
         }
-        { // (inside one 4 GiB window: the handlers bump the record pointer without a carry)
-            const size_t rbytes = (p->rtcode.size() + 1) * sizeof(BoundInstr);
-            const hipError_t ast = prog_malloc(c, reinterpret_cast<void **>(&p->d_rtcode), rbytes);
-            if (ast != hipSuccess) return fail(c, DE_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(ast));
-            if (!in_one_window(p->d_rtcode, rbytes)) return fail(c, DE_ERR_HIP, "reverse instruction stream straddles a 4 GiB boundary");
-        }
-        HIP_TRY(c, hipMemset(p->d_rtcode, 0, (p->rtcode.size() + 1) * sizeof(BoundInstr)));
+        const int rc = stream_alloc(c, &p->d_rtcode, p->rtcode.size() + 1, "reverse");
+        if (rc != DE_OK) return rc;
         if (!p->d_rtcode_off) {
             HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_rtcode_off), p->rtcode_off.size() * sizeof(int32_t)));
             HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_rtcode_mid), std::max<size_t>(p->rtcode_mid.size(), 1) * sizeof(int32_t)));
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_rt_ids), std::max<size_t>(ids.size(), 1) * sizeof(int32_t)));
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_rt_ids), std::max<size_t>(r.ids.size(), 1) * sizeof(int32_t)));
         }
-        if (!p->rtcode.empty())
-            HIP_TRY(c, hipMemcpy(p->d_rtcode, p->rtcode.data(), p->rtcode.size() * sizeof(BoundInstr), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(p->d_rtcode_off, p->rtcode_off.data(), p->rtcode_off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!ids.empty()) {
-            HIP_TRY(c, hipMemcpy(p->d_rtcode_mid, p->rtcode_mid.data(), p->rtcode_mid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(p->d_rt_ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        p->rt_stage_cols = (int)stage_cols;
-        p->rt_handler_base = base;
-        p->rt_param_off = (uint32_t)(table[ROP_PARAM] - base);
+        HIP_TRY(c, upload(p->d_rtcode, p->rtcode));
+        HIP_TRY(c, upload(p->d_rtcode_off, p->rtcode_off));
+        HIP_TRY(c, upload(p->d_rtcode_mid, p->rtcode_mid));
+        HIP_TRY(c, upload(p->d_rt_ids, r.ids));
+        p->rt_stage_cols = (int)r.stage_cols;
+        p->rt_handler_base = h.base;
+        p->rt_param_off = (uint32_t)(table[ROP_PARAM] - h.base);
         p->rt_mode = mode;
         p->rt_valid = true;
     }
@@ -893,6 +233,76 @@ static int ensure_rev_threaded(de_ctx *c, de_program *p, int mode, GradArgs *g) 
     g->rev_handler_base = p->rt_handler_base;
     g->rev_param_off = p->rt_param_off;
     return DE_OK;
+}
+
+// Host-only hook (no HIP call, like de_lower_tape_stage): one tape lowered and bound as ensure_generic_code does (unfolded, early-exit
+// binding), then encoded by encode_grad_forward (form 0; 1: `wide`; 2: shared leaf rows, the four variants one behind the other) or
+// encode_grad_reverse (form 3) against an identity handler table — a record's handler word is then a plain gop_* / ROP_* id.
+// meta[8], forward: GC, VS, windows, slots, records per variant, variants; reverse: mid, need, stage_cols, LDS rows per wave, n_slots;
+// both: [6] constants whose site (the record set_consts patches) holds their bits, [7] a hash of the site table.  Returns the words, 0: not expressible, < 0: -status.
+int64_t de_lower_tape_grad(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
+                           int32_t n_params, uint32_t options, int mode, int form, uint32_t *words, int64_t cap, int32_t *meta) {
+    if (dtype != DE_F32 && dtype != DE_F64) return -DE_ERR_INVALID_ARG;
+    if (mode != DE_GRAD_VARIABLE && mode != DE_GRAD_CONSTANT && mode != DE_GRAD_BOTH) return -DE_ERR_INVALID_ARG;
+    if (form < 0 || form > 3 || !meta) return -DE_ERR_INVALID_ARG;
+    int32_t lmeta[4] = {0, 0, 0, 0};
+    int64_t nw = de_lower_tape(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, nullptr, 0, lmeta);
+    if (nw < 0) return nw;
+    try {
+        std::vector<uint32_t> gen((size_t)nw);
+        nw = de_lower_tape(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, gen.data(), nw, lmeta);
+        if (nw < 0) return nw;
+        std::vector<BoundInstr> gb;
+        bind_tree(reinterpret_cast<const Instr *>(gen.data()), (size_t)nw / 4, true, n_features, &gb);
+        const std::vector<int32_t> gb_off = {0, (int32_t)gb.size()};
+        bool cse = false; // (a CSE tape announces itself by its markers)
+        for (int64_t i = 0; i < n_nodes; i++)
+            cse = cse || (nodes[i].degree == 1 && nodes[i].op == DE_OP_SHARE) || (nodes[i].degree == 0 && nodes[i].op == DE_LEAF_SHARED);
+        const int32_t nv = n_features + n_params;
+        const int32_t ng = mode == DE_GRAD_VARIABLE ? nv : (mode == DE_GRAD_CONSTANT ? (int32_t)n_consts : nv + (int32_t)n_consts);
+        const GradSource src{gb, gb_off, 1, n_features, n_params, lmeta[3] != 0, dtype, mode, &ng};
+        GradEncodeOptions opt = grad_encode_env();
+        opt.wide = form == 1;
+        opt.share = form == 2;
+        opt.vs2_rows = lmeta[3] ? 18 : 15;
+        std::vector<uint64_t> identity(std::max<size_t>(GOP_MAX, ROP_COUNT));
+        for (size_t i = 0; i < identity.size(); i++) identity[i] = i;
+        const std::vector<BoundInstr> *code = nullptr;
+        const std::vector<int32_t> *site = nullptr;
+        GradForwardStream f;
+        GradReverseStream r;
+        std::memset(meta, 0, 8 * sizeof(int32_t));
+        if (form == 3) {
+            const int enc = encode_grad_reverse(src, opt, lmeta[0], cse, GradHandlers{identity.data(), 0}, &r);
+            if (enc != GRAD_ENC_OK) return enc < 0 ? -DE_ERR_HIP : 0;
+            const int32_t m[5] = {r.rtcode_mid[0], (int32_t)r.need[0], (int32_t)r.stage_cols, r.groups[0].rows, lmeta[0]};
+            std::memcpy(meta, m, sizeof m);
+            code = &r.rtcode;
+            site = &r.rtsite_of_gb;
+        } else {
+            const GradHandlerSource handlers = [&](int, int, GradHandlers *h) { *h = GradHandlers{identity.data(), 0}; return (int)GRAD_ENC_OK; };
+            const int enc = encode_grad_forward(src, opt, grad_threaded_has, handlers, &f);
+            if (enc != GRAD_ENC_OK) return enc < 0 ? -DE_ERR_HIP : 0;
+            const GradForwardStream::Bucket &bk = f.buckets[0];
+            const int32_t m[6] = {bk.GC, bk.VS, bk.windows, bk.slots, f.gtcode_off[1], f.share ? 4 : 1};
+            std::memcpy(meta, m, sizeof m);
+            code = &f.gtcode;
+            site = &f.gtsite_of_gb;
+        }
+        uint32_t hash = 2166136261u;
+        for (size_t i = 0; i < gb.size(); i++) {
+            const int32_t at = (*site)[i]; // (where de_program_set_consts would patch this constant: the record must hold its bits)
+            if (bop_is_const_source(gb[i].bop) && at >= 0 && (*code)[(size_t)at].lo == gb[i].lo && (*code)[(size_t)at].hi == gb[i].hi) meta[6]++;
+            hash = (hash ^ (uint32_t)(*site)[i]) * 16777619u;
+        }
+        meta[7] = (int32_t)hash;
+        const int64_t n = (int64_t)code->size() * 4;
+        if (!words || cap < n) return n;
+        std::memcpy(words, code->data(), (size_t)n * 4);
+        return n;
+    } catch (...) {
+        return -DE_ERR_HIP;
+    }
 }
 
 // Shared body of de_eval_grad / de_eval_diff.

@@ -1420,8 +1420,9 @@ int de_eval_plan(const de_program_t *p, int64_t N, int32_t *plan) {
     return DE_OK;
 }
 
-// Host-only test hook (no HIP call): n items over the pool of host threads that de_program_create's per-tree passes run on; returns how
-// many items were visited exactly once (n when all is well), *n_ranges = the ranges the items were split into (1 = ran inline).
+// Test hook: one 64-bit FNV-1a hash over every host-side stream, table and flag de_program_create built (lengths included), and over the
+// auxiliary program of constant subtrees — equal for every DE_HOST_THREADS and for a de_program_update against a fresh creation.  The
+// gradient streams (gbcode, gtcode, rtcode) are made lazily by the gradient entry points and are not part of it.
 uint64_t de_program_stream_hash(const de_program_t *p) {
     if (!p) return 0;
     uint64_t h = 1469598103934665603ull;

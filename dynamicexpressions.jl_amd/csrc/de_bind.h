@@ -209,6 +209,15 @@ inline bool top_reads_acc(uint32_t top, int generic_degree) {
     return true; // max / min handlers, anything unknown
 }
 
+// True when a BOUND instruction reads the LDS row arg[23:0] names — a feature row or a spill slot / shared row: a load, a hot or generic
+// operator with a row operand.  (PUSH writes its row; BOP_TERN names two, both slots.)  The gradient encoders (de_grad_encode.cpp) size a
+// tree's slot area and find the consumers of a shared row with it.
+inline bool bop_reads_row(uint32_t bop) {
+    if (bop == BOP_LOAD_ROW || bop == BOP_GEN_ROW) return true;
+    if (bop >= BOP_BIN_BASE && bop < BOP_BIN_END) return ((bop - BOP_BIN_BASE) & 2u) == 0; // bit 1 = the operand is a constant
+    return bop >= BOP_UN_BASE && bop < BOP_UN_END && ((bop - BOP_UN_BASE) & 2u) != 0;       // bit 1 = the operand is a row
+}
+
 // True when a (bound or fused) instruction carries a constant's bits in lo/hi.  Every generic
 // instruction with a constant operand becomes exactly one such instruction, in program order, in the
 // bound and in the fused stream — which is how de_program_set_consts patches immediates in place.

@@ -75,7 +75,8 @@ extern "C" {
  *      19 opcodes that have a Complex method with a Complex result) for the same calls, except that the host lowering
  *      hooks keep their real dtype domain and complex tapes lower through the new de_lower_tape_complex / de_lower_tape_stage_complex;
  *      the same entry points answer DE_ERR_UNSUPPORTED, and so does de_program_create with n_params > 0.
- *      (e) de_program_update: replace some trees of a program in place, for every dtype. */
+ *      (e) de_program_update: replace some trees of a program in place, for every dtype.
+ *      (f) de_lower_tape_grad: the host-only hook of the two gradient stream encoders, DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -337,6 +338,17 @@ int64_t de_lower_tape_stage_complex(int dtype, const de_tape_node_t *nodes, int6
                                     const void *consts, int64_t n_consts, int32_t n_features,
                                     int32_t n_params, uint32_t options, int stage, uint32_t *words,
                                     int64_t cap);
+/* Host-only hook of the GRADIENT streams (csrc/de_grad_encode.h; DE_F32 / DE_F64 only): the tape lowered and bound as the gradient entry
+ * points do (unfolded, every tested value tested), then encoded for `mode` (DE_GRAD_*) against an identity handler table, so that the
+ * handler word of a record is a plain gop_* / ROP_* id of csrc/de_bind.h (successor-rotated, as the kernels read it).
+ * form 0: forward duals; 1: the same with two samples per lane allowed; 2: with shared leaf rows (the four stream variants one behind
+ * the other); 3: reverse accumulation.  meta[8] — forward: {window width GC, samples per lane, windows, spill slots, records per variant,
+ * variants}; reverse: {first backward record, partial + accumulation rows, staged columns, LDS rows per wave, spill slots}; both: meta[6] =
+ * constants whose site (the record de_program_set_consts patches) holds their bits, meta[7] = a hash of the constant-site table.  Returns the number of words, 0 when the tree has
+ * no such stream (the flat kernel / the forward duals run it), or -status. */
+int64_t de_lower_tape_grad(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                           int32_t n_features, int32_t n_params, uint32_t options, int mode, int form, uint32_t *words,
+                           int64_t cap, int32_t *meta);
 
 /* ---- evaluation ------------------------------------------------------------ */
 /* Optional per-call inputs of a parametric population
