@@ -47,7 +47,7 @@ EXPORTS = [
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
     "de_program_set_consts", "de_program_update", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
     "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_lower_tape_grad", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
-    "de_loss_spec_check", "de_eval_loss_ex", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
+    "de_loss_spec_check", "de_eval_loss_ex", "de_eval_fit_stats", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
@@ -88,6 +88,64 @@ def loss_spec(loss: str, loss_param: float = 0.0, with_gradient: bool = True) ->
     if library().de_loss_spec_check(C.byref(spec), int(with_gradient)) != 0:
         raise ValueError(f"loss {loss!r}: parameter {loss_param!r} is not finite or outside the kind's range (include/de_hip.h de_loss_kind_t)")
     return spec
+
+
+class FitStats:
+    """The weighted second-order statistics ``de_eval_fit_stats`` returns for a population against a target ``y`` — per tree ``mean_p``
+    (the weighted mean of the tree's values), ``m2_p = sum w (yhat - mean_p)^2`` and ``cov = sum w (yhat - mean_p)(y - mean_y)``; for
+    the target ``W = sum w``, ``mean_y`` and ``m2_y`` — and, as properties computed in float64 on the host, the fitness functions
+    they determine.  Incomplete trees hold NaN throughout."""
+
+    def __init__(self, mean_p, m2_p, cov, W, mean_y, m2_y):
+        self.mean_p, self.m2_p, self.cov = (np.array(v, dtype=np.float64) for v in (mean_p, m2_p, cov))
+        if self.mean_p.ndim != 1 or self.m2_p.shape != self.mean_p.shape or self.cov.shape != self.mean_p.shape:
+            raise ValueError("mean_p, m2_p and cov are one-dimensional arrays of one length (one entry per tree)")
+        self.W, self.mean_y, self.m2_y = float(W), float(mean_y), float(m2_y)
+
+    def __len__(self) -> int:
+        return self.mean_p.shape[0]
+
+    def _flat(self):  # trees without variance: m2_p == 0 (NaN, an incomplete tree, is not flat)
+        return self.m2_p == 0.0
+
+    @property
+    def pearson_r(self):
+        """Pearson's correlation of the tree's values and y; NaN where either has no variance."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = self.cov / np.sqrt(self.m2_p * self.m2_y)
+        return np.where(self._flat(), np.nan, r)
+
+    @property
+    def slope(self):
+        """b of the least-squares fit ``y ~ a + b * yhat`` (Keijzer's linear scaling); 0 where the tree is constant."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b = self.cov / self.m2_p
+        return np.where(self._flat(), 0.0, b)
+
+    @property
+    def intercept(self):
+        """a of that fit: ``mean_y - slope * mean_p`` (``mean_y`` where the tree is constant)."""
+        return np.where(self._flat(), self.mean_y, self.mean_y - self.slope * self.mean_p)
+
+    @property
+    def scaled_sse(self):
+        """The weighted squared error left after the linear scaling: ``m2_y - cov^2 / m2_p`` (``m2_y`` where the tree is constant)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e = self.m2_y - self.cov * self.cov / self.m2_p
+        return np.where(self._flat(), np.where(np.isnan(self.cov), np.nan, self.m2_y), e)
+
+    @property
+    def sse(self):
+        """``sum w (yhat - y)^2`` — the L2 loss of ``eval_loss`` — from the moments."""
+        d = self.mean_p - self.mean_y
+        with np.errstate(over="ignore", invalid="ignore"):
+            return self.m2_y - 2.0 * self.cov + self.m2_p + self.W * d * d
+
+    @property
+    def r2(self):
+        """The coefficient of determination of the tree's values themselves: ``1 - sse / m2_y``."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 1.0 - self.sse / self.m2_y
 
 
 _lib: Optional[C.CDLL] = None
@@ -166,6 +224,7 @@ def library() -> C.CDLL:
     lib.de_eval_loss_grad_by_class.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.de_loss_spec_check.argtypes = [C.POINTER(LossSpec), C.c_int]
     lib.de_eval_loss_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), vp, vp]
+    lib.de_eval_fit_stats.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -826,6 +885,57 @@ class Population:
         self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
                                            yp, wp, C.byref(spec), out.ctypes.data, ok.ctypes.data))
         return out, ok.astype(bool)
+
+    def eval_fit_stats(self, X, y, weights=None, params=None, classes=None, class_base: int = 1):
+        """The fused second-order statistics of every tree's values against ``y`` (``de_eval_fit_stats``): what Pearson correlation,
+        R^2 and the fit "up to a linear transform" (the optimal ``a + b * yhat`` and its residual) are functions of, without
+        materialising the [n_trees, N] output.  ``weights`` as in ``eval_loss`` (0 excludes a sample).  Returns ``(FitStats, ok)``;
+        the statistics of a tree that is not ok are NaN."""
+        self._refuse_f16("eval_fit_stats")
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        pa = self._param_args(params, classes, class_base, N, keep)
+        lib = library()
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                if v.numel() != N:
+                    raise ValueError(f"{name} must have {N} entries")
+                keep.append(v)
+                return v.data_ptr()
+            v = np.ascontiguousarray(v, dtype=self.dtype)
+            if v.size != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return v.ctypes.data
+
+        if y is None:
+            raise ValueError("y is required")
+        yp, wp = vec(y, "y"), vec(weights, "weights")
+        if is_t:
+            import torch
+            st = torch.empty(3 * self.n_trees + 3, dtype=torch.float64, device=keep_x.device)  # stats, then ystats
+            ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
+            self.ctx.check(lib.de_eval_fit_stats(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp,
+                                                 st.data_ptr(), st.data_ptr() + 24 * self.n_trees, ok.data_ptr()))
+            ok = ok.bool()
+            st = st.cpu().numpy()
+        else:
+            st = np.empty(3 * self.n_trees + 3, dtype=np.float64)
+            ok = np.zeros(self.n_trees, dtype=np.uint8)
+            self.ctx.check(lib.de_eval_fit_stats(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp,
+                                                 st.ctypes.data, st.ctypes.data + 24 * self.n_trees, ok.ctypes.data))
+            ok = ok.astype(bool)
+        per_tree, ys = st[:3 * self.n_trees].reshape(self.n_trees, 3), st[3 * self.n_trees:]
+        return FitStats(per_tree[:, 0], per_tree[:, 1], per_tree[:, 2], ys[0], ys[1], ys[2]), ok
 
     def eval_loss_grad(self, X, y, weights=None, loss: str = "L2", variable: Union[bool, str] = False,
                        params=None, classes=None, class_base: int = 1, loss_param: float = 0.0):

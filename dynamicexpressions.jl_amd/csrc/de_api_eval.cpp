@@ -52,6 +52,7 @@ struct LossReq {
     int32_t kind;
     double param; // de_loss_spec_t::param
     void *loss;
+    double *stats = nullptr, *ystats = nullptr; // de_eval_fit_stats (kind == FIT_STATS_KIND, loss == null)
 };
 
 struct CertReq {
@@ -163,6 +164,20 @@ int de_eval_loss_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int6
     const LossReq lr{y, w, spec->kind, spec->param, loss};
     DE_NOTHROW(c, eval_impl(c, p, X, N, ldX, pa, nullptr, N, ok, &lr));
 }
+// The fit statistics: a loss launch of the internal kind FIT_STATS_KIND (de_kernels.h), which no de_loss_spec_t reaches.
+int de_eval_fit_stats(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                      const void *y, const void *w, double *stats, double *ystats, uint8_t *ok) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_fit_stats: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_fit_stats: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (N < 0 || !ok || !ystats || (p->n_trees > 0 && (!stats || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (!p->threaded)
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_fit_stats needs the LDS-tiled kernel (feature matrix too wide for this build)");
+    LossReq lr{y, w, FIT_STATS_KIND, 0.0, nullptr};
+    lr.stats = stats;
+    lr.ystats = ystats;
+    DE_NOTHROW(c, eval_impl(c, p, X, N, ldX, pa, nullptr, N, ok, &lr));
+}
 
 static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                      void *out, int64_t ld_out, uint8_t *ok, const LossReq *lr, const CertReq *cr) {
@@ -180,6 +195,18 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     if (N == 0) { // nothing to evaluate: only the constant part of the flag (sum(empty) is finite)
         if (ok_dev) HIP_TRY(c, hipMemcpyAsync(ok, p->host_ok_eval.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
         else std::memcpy(ok, p->host_ok_eval.data(), (size_t)p->n_trees);
+        if (lr && lr->stats) { // W == 0: the means are NaN, M2 and C are 0; NaN x 3 where a constant already failed the flag
+            const double nan = std::nan("");
+            std::vector<double> z((size_t)p->n_trees * 3);
+            for (int64_t t = 0; t < p->n_trees; t++) {
+                const bool good = p->host_ok_eval[(size_t)t] != 0;
+                z[3 * (size_t)t] = nan;
+                z[3 * (size_t)t + 1] = z[3 * (size_t)t + 2] = good ? 0.0 : nan;
+            }
+            const double ys[3] = {0.0, nan, 0.0};
+            HIP_TRY(c, hipMemcpy(lr->stats, z.data(), z.size() * sizeof(double), hipMemcpyDefault));
+            HIP_TRY(c, hipMemcpy(lr->ystats, ys, sizeof ys, hipMemcpyDefault));
+        } else
         if (lr) { // empty sum = 0; NaN where a constant already failed the flag
             std::vector<unsigned char> z((size_t)p->n_trees * es);
             for (int64_t t = 0; t < p->n_trees; t++) {
@@ -196,7 +223,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     }
     const bool direct = p->direct && !(p->threaded && !cr); // (the threaded kernel stages a wider X than the flat-switch kernel can: de_api_program.cpp make_threaded)
 
-    Staged sX, sOut, sOk, sPar, sCls, sY, sW, sLoss;
+    Staged sX, sOut, sOk, sPar, sCls, sY, sW, sLoss, sStats, sYstats;
     LossArgs la;
     std::memset(&la, 0, sizeof la);
     rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX);
@@ -211,6 +238,15 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         rc = stage_out(c, c->sLoss, lr->loss, (size_t)p->n_trees * es, &sLoss);
         if (rc) return rc;
         size_t pb = 0, sb = 0;
+        if (lr->stats) {
+            rc = stage_out(c, c->sStats, lr->stats, (size_t)p->n_trees * 3 * sizeof(double), &sStats);
+            if (rc) return rc;
+            rc = stage_out(c, c->sYstats, lr->ystats, 3 * sizeof(double), &sYstats);
+            if (rc) return rc;
+            la.stats = static_cast<double *>(sStats.dev);
+            la.ystats = static_cast<double *>(sYstats.dev);
+            fit_stats_scratch_bytes(p->dtype, p->n_trees, N, &pb, &sb);
+        } else
         loss_scratch_bytes(p->dtype, p->n_trees, N, &pb, &sb);
         HIP_TRY(c, c->sPartial.reserve(pb));
         HIP_TRY(c, c->sSeg.reserve(sb));
@@ -310,6 +346,8 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
     HIP_TRY(c, time_end(c));
     if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
+    if (sStats.staged) HIP_TRY(c, hipMemcpyAsync(lr->stats, sStats.dev, (size_t)p->n_trees * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sYstats.staged) HIP_TRY(c, hipMemcpyAsync(lr->ystats, sYstats.dev, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sOut.staged) {
         if (ld_out == N) // one block (the constant-folding population is 10^3..10^5 one-sample rows)
             HIP_TRY(c, hipMemcpyAsync(out, sOut.dev, (size_t)p->n_trees * (size_t)N * es, hipMemcpyDeviceToHost, c->stream));
@@ -349,7 +387,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
             if (!std::isfinite(m) && okh[(size_t)t]) cr->certified[t] = 0;
         }
     }
-    if (sX.staged || sOut.staged || sOk.staged || sPar.staged || sCls.staged || sY.staged || sW.staged || sLoss.staged)
+    if (sX.staged || sOut.staged || sOk.staged || sPar.staged || sCls.staged || sY.staged || sW.staged || sLoss.staged || sStats.staged || sYstats.staged)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (sOut.staged && a.skip_flagged) {
         // host output buffer: the rows of incomplete trees were only partly written on the device, and the staging buffer is shared by

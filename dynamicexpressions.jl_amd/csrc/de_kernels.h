@@ -48,7 +48,15 @@ struct LossArgs {
     void *partial;    // device scratch, loss_scratch_bytes().partial
     void *seg_sum;    // device scratch (double), loss_scratch_bytes().seg
     void *loss;       // device, n_trees values of the program's dtype
+    // fit statistics (de_eval_fit_stats; kind == FIT_STATS_KIND, loss == null): partial holds FIT_STATS_VALUES values per (tile, tree)
+    // and seg_sum the scratch of fit_stats_scratch_bytes
+    double *stats;    // device, 3 * n_trees: {mean_p, M2_p, C} per tree
+    double *ystats;   // device, 3: {W, mean_y, M2_y}
 };
+// The internal loss kind of a fit-statistics launch: behind the public kinds of de_loss_kind_t (de_loss_spec_check refuses it), inside
+// the five bits the kind travels in (de_kernels.hip HF_LOSS_KIND_MASK); and the values per (tile, tree) of its partial buffer.
+constexpr int32_t FIT_STATS_KIND = 25;
+constexpr int FIT_STATS_VALUES = 4;
 
 struct EvalArgs {
     // program
@@ -216,6 +224,9 @@ void eval_plan(int io, int64_t n_trees, int64_t N, int32_t *tile, int32_t *n_chu
 
 // Scratch the fused-loss reduction needs for (dtype, n_trees, N).
 void loss_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_bytes, size_t *seg_bytes);
+// ... and the fit statistics: the loss launch's partial buffer x FIT_STATS_VALUES; seg = three per-tile arrays of the pre-pass over
+// y / w, then three [segments][n_trees] arrays of the recombination, all double.
+void fit_stats_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_bytes, size_t *seg_bytes);
 
 // Pass 2 of the fused-loss reductions: seg_sum[seg][col] = sum over the tiles of a segment of
 // partial[tile][col] (fixed order, double).  n_cols counts (column, wave) pairs.

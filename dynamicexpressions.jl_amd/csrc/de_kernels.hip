@@ -98,6 +98,9 @@ template <typename T> struct KArgs {
     // fused loss, parameterised kinds (loss_kind >= DE_LOSS_HUBER; de_loss_kinds.h): the kind's parameter.  The LOSS kernel writes it to
     // LDS (LossParamLds) before the first chain call — a handler has no kernel arguments (h_tree_end_loss)
     T loss_param;
+    // fit statistics (de_eval_fit_stats, loss_kind == FIT_STATS_KIND): {W, mean_y, M2_y} as the pre-pass over y / w left them on the
+    // device (de_fit_ymean_kernel) — the kernel centres its targets on T(mean_y); partial is then [n_tiles][n_trees] x {m, S1, B, Cc}
+    const double *fit_ystats;
 };
 
 
@@ -265,6 +268,7 @@ enum : uint32_t { HF_SLOW_STORE = 1u << 30, HF_NO_STORE = 1u << 29, HF_VALID_MAS
                   HF_LOSS_KIND = 1u << 26, HF_LOSS_KIND_MASK = 0x1Fu };
 static_assert(HF_LOSS_KIND == HF_LOSS_L1 && (HF_LOSS_KIND & HF_LOSS) == 0, "bit 26 is read as a parameterised kind only where HF_LOSS is clear");
 static_assert((HF_LOSS_KIND_MASK & ~HF_VALID_MASK) == 0 && DE_LOSS_L1_HINGE <= (int)HF_LOSS_KIND_MASK, "the kind travels in store-only bits of flags");
+static_assert(FIT_STATS_KIND > DE_LOSS_L1_HINGE && FIT_STATS_KIND <= (int)HF_LOSS_KIND_MASK, "the internal kind of de_eval_fit_stats: behind the public ones, inside the five bits");
 template <typename T> __device__ __forceinline__ HandlerFn<T> arg_next(uint32_t w1, uint64_t w23);
 template <> __device__ __forceinline__ HandlerFn<float> arg_next<float>(uint32_t, uint64_t w23) { return reinterpret_cast<HandlerFn<float>>(w23); }
 template <> __device__ __forceinline__ HandlerFn<double> arg_next<double>(uint32_t w1, uint64_t) {
@@ -419,6 +423,69 @@ template <typename T> __device__ __noinline__ HState<T> h_tree_end_loss(HCHAIN_A
 #endif
     HTREE_END_TAIL(w, code_at(code, 1), code_at(code, -1));
 }
+// the value of lane 63 (where wave_sum_to_lane63 leaves its total) in every lane
+__device__ __forceinline__ float wave_lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
+__device__ __forceinline__ double wave_lane63(double v) {
+    const long long b = __double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), 63);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// The end of a tree in a FIT-STATISTICS launch (de_eval_fit_stats: flags & HF_LOSS_KIND with the internal kind FIT_STATS_KIND;
+// h_tree_end_slow tail-calls it like h_tree_end_loss).  ly holds the CENTRED targets yc = y - T(mean_y) (the kernel's prologue), lw
+// the weights.  Per wave: the shift m = the weighted mean of the tree's values over the samples that count, formed in T — any shift
+// makes the recombination (de_fit_reduce_*_kernel) an identity, this one keeps the three sums free of cancellation — and
+//   S1 = sum w (yhat - m)    B = sum w (yhat - m)^2    Cc = sum w (yhat - m) yc        -> partial[tile, tree] = {m, S1, B, Cc}
+// Weight 0 (samples past N) excludes a sample by a select, never by the product; HF_LOSS_PLAIN drops the selects; no sample: zeros.
+template <typename T> __device__ __noinline__ HState<T> h_tree_end_stats(HCHAIN_ARGS) { // la = the tree's index
+    constexpr int VW = VecOf<T>::W;
+    const U32x4 w = *code;
+    const uint32_t tree = la;
+    const GPtr row = reinterpret_cast<GPtr>(outp + (uint64_t)tree * ldo);
+#if !DE_NO_LOSS
+    HL_BOTH(ly, lw);
+    const int lane = (int)(((lds0 - DE_SKIPLIST_BYTES) >> 4) & 63u);
+    const bool plain = (flags & HF_LOSS_PLAIN) != 0;
+    T sw = T(0), sy = T(0);
+    FOR_PLANES DE_UNROLL for (int i = 0; i < VW; i++) {
+        if (plain) sy += st.acc[g][i];
+        else {
+            sw += lw.v[g][i];
+            sy += lw.v[g][i] != T(0) ? lw.v[g][i] * st.acc[g][i] : T(0);
+        }
+    }
+    sy = wave_lane63(wave_sum_to_lane63(sy, lane));
+    T m;
+    if (plain) m = sy * (T(1) / T(64 * VW * TG<T>::G)); // (the tile's sample count is a power of two: an exact division)
+    else {
+        sw = wave_lane63(wave_sum_to_lane63(sw, lane));
+        m = sw != T(0) ? sy / sw : T(0);
+    }
+    // (the sums of products accumulate by FMA: these are the library's own statistics, no reference arithmetic to reproduce)
+    T s1 = T(0), b = T(0), cc = T(0);
+    FOR_PLANES DE_UNROLL for (int i = 0; i < VW; i++) {
+        const T d = st.acc[g][i] - m;
+        if (plain) {
+            s1 += d;
+            b = M<T>::fma(d, d, b);
+            cc = M<T>::fma(d, ly.v[g][i], cc);
+        } else {
+            const T wd = lw.v[g][i] * d;
+            const bool in = lw.v[g][i] != T(0);
+            s1 += in ? wd : T(0);
+            b = in ? M<T>::fma(wd, d, b) : b;
+            cc = in ? M<T>::fma(wd, ly.v[g][i], cc) : cc;
+        }
+    }
+    s1 = wave_sum_to_lane63(s1, lane);
+    b = wave_sum_to_lane63(b, lane);
+    cc = wave_sum_to_lane63(cc, lane);
+    if (lane == 63) {
+        typedef T Q4 __attribute__((ext_vector_type(4)));
+        *reinterpret_cast<__attribute__((address_space(1))) Q4 *>(row) = Q4{m, s1, b, cc};
+    }
+#endif
+    HTREE_END_TAIL(w, code_at(code, 1), code_at(code, -1));
+}
 // The other ends of a tree (flags & HF_SLOW), out of line so that h_tree_end itself is straight-line code: HF_LOSS (fused loss:
 // the tree's loss partial of this tile), HF_SLOW_STORE (ragged last tile / output rows that are not 16-byte aligned; LDS base = 0:
 // lds0 = DE_SKIPLIST_BYTES + 16 * thread), HF_NO_STORE (DE_DEBUG_NO_STORE, measurement only: keep the value alive, write nothing).
@@ -461,7 +528,8 @@ template <typename T> __device__ __noinline__ HState<T> h_tree_end_slow(HCHAIN_A
         // an INDIRECT tail call (the address goes through an empty asm): behind a direct one the backend hands the registers
         // h_tree_end_loss uses — the transcendental kinds take callee-saved ones — up the chain of tail calls, and h_tree_end_slow,
         // h_tree_end and every h_chain_end would open with a stack frame that saves them (Float64: 225 instead of 64 instructions)
-        uint64_t fa = (uint64_t)(uintptr_t)&h_tree_end_loss<T>;
+        // (the fit statistics of de_eval_fit_stats are one more kind of this route, internal to the library: h_tree_end_stats)
+        uint64_t fa = (flags & HF_LOSS_KIND_MASK) == (uint32_t)FIT_STATS_KIND ? (uint64_t)(uintptr_t)&h_tree_end_stats<T> : (uint64_t)(uintptr_t)&h_tree_end_loss<T>;
         asm volatile("" : "+s"(fa));
         [[clang::musttail]] return reinterpret_cast<HandlerFn<T>>(fa)(st, HL_PASS_C lds0, code, outp, la, w1, w23, okp, ldo, skip, left, flags);
     }
@@ -1574,6 +1642,10 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
             yv.v[g][i] = a.y[jj];
             wv.v[g][i] = j <= last ? (a.w ? a.w[jj] : T(1)) : T(0);
         }
+        if (a.loss_kind == FIT_STATS_KIND) { // the centred targets yc of h_tree_end_stats (de_fit_ytile_centred_kernel forms the same values)
+            const T ym = (T)a.fit_ystats[1];
+            DE_UNROLL for (int g = 0; g < G; g++) DE_UNROLL for (int i = 0; i < VW; i++) yv.v[g][i] = yv.v[g][i] - ym;
+        }
     }
 
     if (tA >= tB) return;
@@ -1645,6 +1717,10 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
             if (a.loss_kind >= DE_LOSS_HUBER) flags = (flags & ~(uint32_t)(HF_LOSS | HF_LOSS_L1)) | HF_LOSS_KIND | ((uint32_t)a.loss_kind & HF_LOSS_KIND_MASK);
             outp = (uint64_t)(uintptr_t)(a.partial + ((int64_t)tm.tile * a.n_trees) * TWAVES + __builtin_amdgcn_readfirstlane(tid >> 6)); // (wave-uniform: an SGPR argument; a wave group: tid < 64)
             ldo_arg = (uint64_t)TWAVES * sizeof(T);
+            if (a.loss_kind == FIT_STATS_KIND) { // four values per (tile, tree): h_tree_end_stats
+                outp = (uint64_t)(uintptr_t)(a.partial + ((int64_t)tm.tile * a.n_trees) * FIT_STATS_VALUES);
+                ldo_arg = (uint64_t)FIT_STATS_VALUES * sizeof(T);
+            }
         } else {
             flags |= a.vec_store == 2 ? (HF_SLOW | HF_NO_STORE) : ((full && a.vec_store) ? 0u : (HF_SLOW | HF_SLOW_STORE | (uint32_t)in_tile));
             outp = (uint64_t)(uintptr_t)(a.out + base) - (uint64_t)(uint32_t)(uintptr_t)smem_raw;
@@ -1688,6 +1764,179 @@ __global__ void __launch_bounds__(256) de_loss_finish_kernel(const double *__res
     for (int32_t g = 0; g < n_segs; ++g)
         for (int w = 0; w < TWAVES; ++w) s += seg_sum[((int64_t)g * n_trees + t) * TWAVES + w];
     loss[t] = ok[t] ? (T)s : M<T>::nan();
+}
+
+// ---- fit statistics (de_eval_fit_stats): the pre-pass over y / w and the recombination of the per-tile quadruples
+// {m, S1, B, Cc} of h_tree_end_stats.  Everything in double, every sum in a fixed order.
+__device__ __forceinline__ double fit_block_sum(double v, double *sh) { // 256 threads, a fixed tree; the total in every thread
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// One wave per sample tile of the eval kernel.  CENTRED = false: tile_w = sum w, tile_r = sum w y.  CENTRED = true (behind
+// de_fit_ysum_kernel: ystats[1] = mean_y): tile_r = sum w yc over the values yc = y - T(mean_y) the eval kernel forms in T, and
+// tile_q = sum w (y - mean_y)^2.  Weight 0 excludes a sample, as in the eval kernel.
+template <typename T, bool CENTRED>
+__global__ void __launch_bounds__(256) de_fit_ytile_kernel(const T *__restrict__ y, const T *__restrict__ w, int64_t N, int64_t n_tiles, int tile,
+                                                          const double *__restrict__ ystats, double *__restrict__ tile_w,
+                                                          double *__restrict__ tile_r, double *__restrict__ tile_q) {
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63u);
+    if (t >= n_tiles) return; // (wave-uniform)
+    const double my = CENTRED ? ystats[1] : 0.0;
+    const T my_t = (T)my;
+    double a = 0.0, b = 0.0;
+    for (int k = lane; k < tile; k += 64) {
+        const int64_t j = t * tile + k;
+        if (j >= N) break;
+        const T wj = w ? w[j] : T(1);
+        if (wj == T(0)) continue;
+        if (CENTRED) {
+            const T yc = y[j] - my_t;
+            const double d = (double)y[j] - my;
+            a += (double)wj * (double)yc;
+            b += ((double)wj * d) * d;
+        } else {
+            a += (double)wj;
+            b += (double)wj * (double)y[j];
+        }
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        a += __shfl_xor(a, m, 64);
+        b += __shfl_xor(b, m, 64);
+    }
+    if (lane == 0) {
+        if (CENTRED) { tile_r[t] = a; tile_q[t] = b; }
+        else { tile_w[t] = a; tile_r[t] = b; }
+    }
+}
+// One block: mode 0: ystats[0] = W = sum a, ystats[1] = mean_y = sum b / W (NaN where W == 0); mode 1: ystats[2] = M2_y = sum a.
+__global__ void __launch_bounds__(256) de_fit_ysum_kernel(const double *__restrict__ a, const double *__restrict__ b, int64_t n, double *__restrict__ ystats, int mode) {
+    __shared__ double sh[256];
+    double sa = 0.0, sb = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        sa += a[i];
+        if (b) sb += b[i];
+    }
+    sa = fit_block_sum(sa, sh);
+    sb = fit_block_sum(sb, sh);
+    if (threadIdx.x != 0) return;
+    if (mode == 0) {
+        ystats[0] = sa;
+        ystats[1] = sa != 0.0 ? sb / sa : __longlong_as_double(0x7FF8000000000000ll);
+    } else ystats[2] = sa;
+}
+// Recombination, pass 1: thread = one tree, block row = one segment of tiles: seg_a = sum_tiles (m W_tile + S1) — the numerator of
+// the tree's mean mu.
+template <typename T>
+__global__ void __launch_bounds__(256) de_fit_reduce_mu_kernel(const T *__restrict__ partial, int64_t n_trees, int64_t n_tiles, int64_t tiles_per_seg,
+                                                              const double *__restrict__ tile_w, double *__restrict__ seg_a) {
+    typedef T Q4 __attribute__((ext_vector_type(4)));
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_trees) return;
+    const int64_t r0 = (int64_t)blockIdx.y * tiles_per_seg;
+    const int64_t r1 = r0 + tiles_per_seg < n_tiles ? r0 + tiles_per_seg : n_tiles;
+    double s = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const Q4 q = reinterpret_cast<const Q4 *>(partial)[r * n_trees + t];
+        s += (double)q[0] * tile_w[r] + (double)q[1];
+    }
+    seg_a[(int64_t)blockIdx.y * n_trees + t] = s;
+}
+__device__ __forceinline__ double fit_tree_mean(const double *__restrict__ seg_a, int64_t n_trees, int32_t n_segs, int64_t t, double W) {
+    double s = 0.0;
+    for (int32_t g = 0; g < n_segs; ++g) s += seg_a[(int64_t)g * n_trees + t];
+    return s / W;
+}
+// Pass 2, with mu known: seg_b = sum_tiles [B + 2 (m - mu) S1 + W_tile (m - mu)^2], seg_c = sum_tiles [Cc + (m - mu) R_tile] —
+// identities for any shift m; the terms stay of the size of the centred moments (the expanded form sum W m^2 - W mu^2 cancels).
+template <typename T>
+__global__ void __launch_bounds__(256) de_fit_reduce_m2_kernel(const T *__restrict__ partial, int64_t n_trees, int64_t n_tiles, int64_t tiles_per_seg,
+                                                              int32_t n_segs, const double *__restrict__ tile_w, const double *__restrict__ tile_r,
+                                                              const double *__restrict__ ystats, const double *__restrict__ seg_a,
+                                                              double *__restrict__ seg_b, double *__restrict__ seg_c) {
+    typedef T Q4 __attribute__((ext_vector_type(4)));
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_trees) return;
+    const double mu = fit_tree_mean(seg_a, n_trees, n_segs, t, ystats[0]);
+    const int64_t r0 = (int64_t)blockIdx.y * tiles_per_seg;
+    const int64_t r1 = r0 + tiles_per_seg < n_tiles ? r0 + tiles_per_seg : n_tiles;
+    double sb = 0.0, sc = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const Q4 q = reinterpret_cast<const Q4 *>(partial)[r * n_trees + t];
+        const double dm = (double)q[0] - mu;
+        sb += ((double)q[2] + (2.0 * dm) * (double)q[1]) + (tile_w[r] * dm) * dm;
+        sc += (double)q[3] + dm * tile_r[r];
+    }
+    seg_b[(int64_t)blockIdx.y * n_trees + t] = sb;
+    seg_c[(int64_t)blockIdx.y * n_trees + t] = sc;
+}
+// Pass 3: thread = one tree: {mean_p, M2_p, C}; NaN x 3 where the evaluation was incomplete; W == 0: the mean is NaN, M2 and C are 0.
+__global__ void __launch_bounds__(256) de_fit_finish_kernel(const double *__restrict__ seg_a, const double *__restrict__ seg_b, const double *__restrict__ seg_c,
+                                                           int64_t n_trees, int32_t n_segs, const double *__restrict__ ystats,
+                                                           const uint8_t *__restrict__ ok, double *__restrict__ stats) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_trees) return;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double W = ystats[0];
+    double mu = fit_tree_mean(seg_a, n_trees, n_segs, t, W), m2 = 0.0, c = 0.0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        m2 += seg_b[(int64_t)g * n_trees + t];
+        c += seg_c[(int64_t)g * n_trees + t];
+    }
+    if (m2 < 0.0) m2 = 0.0; // (a sum of squares: only the roundings of a constant tree can take it below 0)
+    if (W == 0.0) { mu = nan; m2 = 0.0; c = 0.0; }
+    if (!ok[t]) mu = m2 = c = nan;
+    stats[3 * t + 0] = mu;
+    stats[3 * t + 1] = m2;
+    stats[3 * t + 2] = c;
+}
+// the scratch of the passes above inside LossArgs::seg_sum (fit_stats_scratch_bytes)
+struct FitScratch {
+    double *tile_w, *tile_r, *tile_q, *seg_a, *seg_b, *seg_c;
+    int32_t n_segs;
+    int64_t tiles_per_seg;
+};
+static FitScratch fit_scratch(void *seg_sum, int64_t n_trees, int64_t n_tiles) {
+    FitScratch f;
+    f.n_segs = loss_segments(n_tiles);
+    f.tiles_per_seg = (n_tiles + f.n_segs - 1) / f.n_segs;
+    f.tile_w = static_cast<double *>(seg_sum);
+    f.tile_r = f.tile_w + n_tiles;
+    f.tile_q = f.tile_r + n_tiles;
+    f.seg_a = f.tile_q + n_tiles;
+    f.seg_b = f.seg_a + (int64_t)f.n_segs * n_trees;
+    f.seg_c = f.seg_b + (int64_t)f.n_segs * n_trees;
+    return f;
+}
+// in front of the eval launch: ystats = {W, mean_y, M2_y} and the per-tile W_tile / R_tile
+template <typename T> static hipError_t launch_fit_prepass(const LossArgs &l, int64_t n_trees, int64_t N, int64_t n_tiles, int tile, hipStream_t stream) {
+    const FitScratch f = fit_scratch(l.seg_sum, n_trees, n_tiles);
+    const dim3 grid((unsigned)((n_tiles + 3) / 4));
+    const T *y = static_cast<const T *>(l.y), *w = static_cast<const T *>(l.w);
+    hipLaunchKernelGGL((de_fit_ytile_kernel<T, false>), grid, dim3(256), 0, stream, y, w, N, n_tiles, tile, (const double *)l.ystats, f.tile_w, f.tile_r, f.tile_q);
+    hipLaunchKernelGGL(de_fit_ysum_kernel, dim3(1), dim3(256), 0, stream, (const double *)f.tile_w, (const double *)f.tile_r, n_tiles, l.ystats, 0);
+    hipLaunchKernelGGL((de_fit_ytile_kernel<T, true>), grid, dim3(256), 0, stream, y, w, N, n_tiles, tile, (const double *)l.ystats, f.tile_w, f.tile_r, f.tile_q);
+    hipLaunchKernelGGL(de_fit_ysum_kernel, dim3(1), dim3(256), 0, stream, (const double *)f.tile_q, (const double *)nullptr, n_tiles, l.ystats, 1);
+    return hipGetLastError();
+}
+// behind it: the three recombination passes
+template <typename T> static hipError_t launch_fit_reduce(const LossArgs &l, int64_t n_trees, int64_t n_tiles, const uint8_t *ok, hipStream_t stream) {
+    const FitScratch f = fit_scratch(l.seg_sum, n_trees, n_tiles);
+    const dim3 grid((unsigned)((n_trees + 255) / 256), (unsigned)f.n_segs);
+    const T *partial = static_cast<const T *>(l.partial);
+    hipLaunchKernelGGL(de_fit_reduce_mu_kernel<T>, grid, dim3(256), 0, stream, partial, n_trees, n_tiles, f.tiles_per_seg, (const double *)f.tile_w, f.seg_a);
+    hipLaunchKernelGGL(de_fit_reduce_m2_kernel<T>, grid, dim3(256), 0, stream, partial, n_trees, n_tiles, f.tiles_per_seg, f.n_segs, (const double *)f.tile_w,
+                       (const double *)f.tile_r, (const double *)l.ystats, (const double *)f.seg_a, f.seg_b, f.seg_c);
+    hipLaunchKernelGGL(de_fit_finish_kernel, dim3((unsigned)((n_trees + 255) / 256)), dim3(256), 0, stream, (const double *)f.seg_a, (const double *)f.seg_b,
+                       (const double *)f.seg_c, n_trees, f.n_segs, (const double *)l.ystats, ok, l.stats);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -1989,6 +2238,14 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
         a.loss_param = (T)e.loss->param;
         if (a.loss_kind >= DE_LOSS_HUBER && ((uint32_t)a.loss_kind & ~(uint32_t)HF_LOSS_KIND_MASK)) return hipErrorInvalidValue; // (the kind travels in five bits of `flags`)
     }
+    const bool fit = e.loss && e.loss->kind == FIT_STATS_KIND; // de_eval_fit_stats: pre-pass over y / w, the loss launch, recombination
+    a.fit_ystats = nullptr;
+    if (fit) {
+        if (TWAVES != 1 || !e.loss->stats || !e.loss->ystats) return hipErrorInvalidValue; // (one quadruple per tile: a tile is one wave)
+        a.fit_ystats = e.loss->ystats;
+        const hipError_t fs = launch_fit_prepass<T>(*e.loss, e.n_trees, a.N, a.n_tiles, TILE, stream);
+        if (fs != hipSuccess) return fs;
+    }
     if (kname) *kname = "de_eval_threaded_kernel";
     if (lds > 64 * 1024) {
         hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2048,6 +2305,7 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(TBLK * WW), lds, stream, a);
     hipError_t st = hipGetLastError();
     if (st != hipSuccess || !e.loss) return st;
+    if (fit) return launch_fit_reduce<T>(*e.loss, e.n_trees, a.n_tiles, e.ok, stream);
     int32_t n_segs = 1;
     st = launch_loss_reduce_tiles(sizeof(T) == 4 ? DE_F32 : DE_F64, a.partial, (int64_t)e.n_trees * TWAVES, a.n_tiles, e.loss->seg_sum, &n_segs, stream);
     if (st != hipSuccess) return st;
@@ -2077,6 +2335,13 @@ void loss_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_b
     const int64_t n_tiles = (N + tile - 1) / tile;
     *partial_bytes = (size_t)n_tiles * (size_t)n_trees * TWAVES * (dtype == DE_F32 ? 4 : 8);
     *seg_bytes = (size_t)loss_segments(n_tiles) * (size_t)n_trees * TWAVES * sizeof(double);
+}
+
+void fit_stats_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *partial_bytes, size_t *seg_bytes) {
+    const int64_t tile = ttile_samples(dtype);
+    const int64_t n_tiles = (N + tile - 1) / tile;
+    *partial_bytes = (size_t)n_tiles * (size_t)n_trees * FIT_STATS_VALUES * (dtype == DE_F32 ? 4 : 8);
+    *seg_bytes = (3 * (size_t)n_tiles + 3 * (size_t)loss_segments(n_tiles) * (size_t)n_trees) * sizeof(double);
 }
 
 // ---- multi-GPU flag exchange (de_dist.cpp): the two re-orderings around the one ncclAllGather of a step.  Rank r owns trees r, r + world,

@@ -634,6 +634,35 @@ function eval_population_loss(
 end
 
 """
+    eval_population_fit_stats(pop, X, y; weights=nothing) -> (stats::NamedTuple, ok)
+
+The weighted second-order statistics of every tree's values `ŷ` against `y`, reduced on the device (`de_eval_fit_stats`; the
+`N × n_trees` output matrix is never written).  `stats` holds, per tree, `mean_p`, `m2_p = Σ w (ŷ - mean_p)²` and
+`cov = Σ w (ŷ - mean_p)(y - mean_y)` as `Vector{Float64}` (NaN where `ok[t]` is false), and the scalars `W = Σ w`, `mean_y`, `m2_y`.
+Pearson's `r = cov / sqrt(m2_p * m2_y)`, the linear scaling `y ≈ a + b ŷ` with `b = cov / m2_p`, `a = mean_y - b * mean_p` and its
+residual `m2_y - cov² / m2_p`, and `sum(abs2, ŷ .- y) = m2_y - 2cov + m2_p + W * (mean_p - mean_y)²` are functions of these.
+A weight of zero excludes its sample.
+"""
+function eval_population_fit_stats(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+) where {T}
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    stats = Matrix{Float64}(undef, 3, pop.n_trees)
+    ystats = Vector{Float64}(undef, 3)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights stats ystats ok ccall(
+            (:de_eval_fit_stats, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
+             Ptr{UInt8}),
+            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), stats, ystats, ok))
+    end
+    return (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3]), ok .!= 0x00
+end
+
+"""
     set_population_constants!(pop, constants::Vector{T})
 
 New constants for the trees of `pop`, same shapes: `constants` = the trees' `get_scalar_constants` vectors

@@ -444,6 +444,23 @@ int de_eval_loss_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N,
                     const de_param_args_t *pargs, const void *y, const void *w, const de_loss_spec_t *spec,
                     void *loss, uint8_t *ok);
 
+/* Per tree, the weighted second-order statistics of its values against y, fused into the evaluation
+ * (nothing of size N is written):
+ *   W = sum_j w_j     mean_y = sum w y / W        M2_y = sum w (y - mean_y)^2          -> ystats[0..2]
+ *   mean_p = sum w yhat / W    M2_p = sum w (yhat - mean_p)^2    C = sum w (yhat - mean_p)(y - mean_y)
+ *                                                                                     -> stats[3 t + 0..2]
+ * w == NULL: w_j = 1; w_j == 0 excludes sample j (as in de_eval_loss).  stats / ystats are DOUBLE whatever
+ * the program's dtype; stats[3t..] is NaN where ok[t] == 0.  W == 0 (N == 0 included): the means are NaN,
+ * M2 and C are 0.  Fixed reduction order: reproducible run to run.
+ * Pearson's r^2 = C^2 / (M2_p M2_y), the least-squares a + b yhat (b = C / M2_p, a = mean_y - b mean_p) and its
+ * residual M2_y - C^2 / M2_p, R^2 and the plain L2 loss are all functions of these.
+ * Pointers, parametric populations and refusals as for de_eval_loss_ex: DE_F16 / complex programs and programs that do
+ * not run the LDS-tiled kernel are DE_ERR_UNSUPPORTED, a null y / stats / ystats / ok DE_ERR_INVALID_ARG, both before
+ * any output is touched. */
+int de_eval_fit_stats(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                      const de_param_args_t *pargs, const void *y, const void *w,
+                      double *stats, double *ystats, uint8_t *ok);
+
 /* Fused loss + its gradient (the pullback of the reduction through eval_grad_tree_array):
  *   loss[t]              = sum_j w_j * l(tree_t(x_j) - y_j)
  *   dloss[off_t + k]     = sum_j w_j * l'(tree_t(x_j) - y_j) * d tree_t(x_j) / d theta_k
