@@ -47,7 +47,7 @@ EXPORTS = [
     "de_ctx_synchronize", "de_ctx_declare_dataset", "de_ctx_stream", "de_last_error", "de_program_create", "de_program_create_cse",
     "de_program_set_consts", "de_program_update", "de_program_destroy", "de_program_n_trees", "de_program_n_nodes",
     "de_program_n_grad", "de_program_dump", "de_program_verify", "de_program_stream_hash", "de_host_pool_selftest", "de_lower_tape", "de_lower_tape_stage", "de_lower_tape_complex", "de_lower_tape_stage_complex", "de_lower_tape_grad", "de_eval", "de_eval_grad", "de_eval_diff", "de_eval_loss", "de_eval_loss_grad", "de_eval_loss_grad_by_class",
-    "de_loss_spec_check", "de_eval_loss_ex", "de_eval_fit_stats", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
+    "de_loss_spec_check", "de_eval_loss_ex", "de_eval_fit_stats", "de_eval_loss_gn", "de_gn_max_rows", "de_eval_loss_grad_ex", "de_eval_loss_grad_by_class_ex",
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
@@ -148,6 +148,90 @@ class FitStats:
             return 1.0 - self.sse / self.m2_y
 
 
+GN_MAX_ROWS = 8  # de_gn_max_rows(): the widest tree (gradient rows of the library's layout) de_eval_loss_gn forms the matrix of
+
+
+def gn_offsets(n_grad):
+    """The element offsets ``Population.eval_gauss_newton`` hands ``de_eval_loss_gn`` for trees of ``n_grad[t]`` gradient rows: (dloss
+    offsets, jtj offsets), ``n_trees + 1`` entries each — tree t owns ``n_grad[t]`` gradient entries and, packed behind one another, a
+    column-major ``n_grad[t] x n_grad[t]`` block whatever its width (a wider tree than ``GN_MAX_ROWS`` gets its block NaN-filled)."""
+    ng = np.asarray(n_grad, dtype=np.int64).reshape(-1)
+    doff, joff = np.zeros(ng.size + 1, dtype=np.int64), np.zeros(ng.size + 1, dtype=np.int64)
+    np.cumsum(ng, out=doff[1:])
+    np.cumsum(ng * ng, out=joff[1:])
+    return doff, joff
+
+
+def _sum_occurrence_rows(g, o):
+    """Rows of ``g`` in the library's per-occurrence layout -> one row per unique constant: the last ``len(o)`` rows are summed into
+    row ``lead + o[k]`` (``Population._combine_rows``); the leading (params,) features rows stay."""
+    o = np.asarray(o, dtype=np.int64)
+    lead = g.shape[0] - len(o)
+    nu = int(o.max()) + 1 if len(o) else 0
+    if _is_torch(g):
+        import torch
+        out = torch.zeros((lead + nu,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
+        out[:lead] = g[:lead]
+        out.index_add_(0, torch.as_tensor(o + lead, device=g.device), g[lead:])
+        return out
+    out = np.zeros((lead + nu,) + g.shape[1:], dtype=g.dtype)
+    out[:lead] = g[:lead]
+    np.add.at(out, o + lead, g[lead:])
+    return out
+
+
+def gn_combine(H, o):
+    """``S H S^T`` for the occurrence map ``o`` of a GraphNode tree: the Gauss-Newton matrix over per-occurrence rows -> over unique
+    constants (S sums the rows of a shared constant, as ``_combine_rows`` does for the gradient)."""
+    if o is None:
+        return H
+    half = _sum_occurrence_rows(H, o)
+    return _sum_occurrence_rows(half.T if not _is_torch(half) else half.t(), o).T
+
+
+class GaussNewton:
+    """What ``Population.eval_gauss_newton`` returns (``de_eval_loss_gn``): per tree the L2 ``loss``, its gradient
+    ``grad[t]`` (``[G_t]``), the Gauss-Newton matrix ``jtj[t] = sum_j w_j d(j) d(j)^T`` (``[G_t, G_t]``; the Hessian of the loss is
+    ``2 jtj``), the flag ``ok`` and ``has_jtj``: ok and narrow enough for the library to have formed the matrix (else it is NaN)."""
+
+    def __init__(self, loss, grad, jtj, ok, has_jtj=None):
+        self.loss, self.grad, self.jtj, self.ok = loss, list(grad), list(jtj), ok
+        if len(self.grad) != len(self.jtj) or len(self.grad) != len(ok):
+            raise ValueError("loss, grad, jtj and ok hold one entry per tree")
+        if has_jtj is None:
+            has_jtj = _host(ok).astype(bool) & np.array([h.shape[0] <= GN_MAX_ROWS for h in self.jtj], dtype=bool)
+        self.has_jtj = has_jtj
+
+    def __len__(self) -> int:
+        return len(self.grad)
+
+    def lm_step(self, lam, tree: Optional[int] = None):
+        """The Levenberg-Marquardt step of every tree (a list of float64 vectors), or of ``tree``, in float64 on the host:
+        ``solve(H + lam * diag(H), -grad / 2)`` with ``H = jtj`` (Marquardt's scaling; ``lam`` a scalar or one value per tree).  The
+        zero vector where ``has_jtj`` is false, an entry is not finite or the system is singular."""
+        lams = np.broadcast_to(np.asarray(lam, dtype=np.float64), (len(self),))
+        has = _host(self.has_jtj).astype(bool)
+
+        def one(t):
+            g, H = _host(self.grad[t]).astype(np.float64), _host(self.jtj[t]).astype(np.float64)
+            zero = np.zeros(g.shape[0], dtype=np.float64)
+            if not has[t] or g.shape[0] == 0 or not (np.isfinite(H).all() and np.isfinite(g).all() and np.isfinite(lams[t])):
+                return zero
+            A = H + lams[t] * np.diag(np.diag(H))
+            try:
+                with np.errstate(all="ignore"):
+                    step = np.linalg.solve(A, -0.5 * g)
+            except np.linalg.LinAlgError:
+                return zero
+            return step if np.isfinite(step).all() else zero
+
+        return one(tree) if tree is not None else [one(t) for t in range(len(self))]
+
+
+def _host(v) -> np.ndarray:
+    return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -225,6 +309,8 @@ def library() -> C.CDLL:
     lib.de_loss_spec_check.argtypes = [C.POINTER(LossSpec), C.c_int]
     lib.de_eval_loss_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), vp, vp]
     lib.de_eval_fit_stats.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, vp, vp, vp]
+    lib.de_eval_loss_gn.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.de_gn_max_rows.argtypes = []
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -992,6 +1078,109 @@ class Population:
         self.ctx.check(lib.de_eval_loss_grad_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode,
                                                 yp, wp, C.byref(spec), lo.ctypes.data, dl.ctypes.data, offs.ctypes.data, ok.ctypes.data))
         return lo, [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))], ok.astype(bool)
+
+    def eval_gauss_newton(self, X, y, weights=None, variable: Union[bool, str] = False, params=None, classes=None,
+                          class_base: int = 1) -> GaussNewton:
+        """Fused Gauss-Newton normal equations per tree (``de_eval_loss_gn``): the L2 loss and its gradient exactly as
+        ``eval_loss_grad(loss="L2")`` returns them, and ``jtj[t] = sum_j w_j d(j) d(j)^T`` over the gradient rows ``variable`` selects
+        (default: the constants) — what a Levenberg-Marquardt step needs, without the [n_grad, N] Jacobian.  numpy in -> numpy out,
+        torch device tensors in -> tensors out.  A tree of more than ``GN_MAX_ROWS`` rows (the library's per-occurrence rows, for a
+        GraphNode) has ``has_jtj`` False and a NaN matrix; its loss and gradient are filled as usual."""
+        self._refuse_f16("eval_gauss_newton")
+        mode = _grad_mode(variable)
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        pa = self._param_args(params, classes, class_base, N, keep)
+        lib = library()
+        ng = self._n_grad_all(mode)
+        offs, joffs = gn_offsets(ng)
+        total, jtotal = max(int(offs[-1]), 1), max(int(joffs[-1]), 1)
+        narrow = ng <= GN_MAX_ROWS
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                n, p_ = v.numel(), v.data_ptr()
+            else:
+                v = np.ascontiguousarray(v, dtype=self.dtype)
+                n, p_ = v.size, v.ctypes.data
+            if n != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return p_
+
+        yp, wp = vec(y, "y"), vec(weights, "weights")
+        occ = self._occ if self._occ is not None and mode != GRAD_VARIABLE else None
+        if is_t:
+            import torch
+            kw = dict(dtype=keep_x.dtype, device=keep_x.device)
+            lo, dl, jt = torch.empty(self.n_trees, **kw), torch.empty(total, **kw), torch.empty(jtotal, **kw)
+            ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
+            self.ctx.check(lib.de_eval_loss_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                               lo.data_ptr(), dl.data_ptr(), offs.ctypes.data, jt.data_ptr(), joffs.ctypes.data, ok.data_ptr()))
+            grads = [self._combine_rows(t, d, mode) for t, d in enumerate(torch.split(dl[:int(offs[-1])], ng.tolist()))]
+            mats = [jt[joffs[t]:joffs[t + 1]].view(int(ng[t]), int(ng[t])).t() for t in range(self.n_trees)]
+            okb = ok.bool()
+            has = okb & torch.as_tensor(narrow, device=keep_x.device)
+        else:
+            lo, dl, jt = np.empty(self.n_trees, dtype=self.dtype), np.empty(total, dtype=self.dtype), np.empty(jtotal, dtype=self.dtype)
+            ok = np.zeros(self.n_trees, dtype=np.uint8)
+            self.ctx.check(lib.de_eval_loss_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                               lo.ctypes.data, dl.ctypes.data, offs.ctypes.data, jt.ctypes.data, joffs.ctypes.data, ok.ctypes.data))
+            grads = [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))]
+            mats = [jt[joffs[t]:joffs[t + 1]].reshape((int(ng[t]), int(ng[t])), order="F") for t in range(self.n_trees)]
+            okb = ok.astype(bool)
+            has = okb & narrow
+        if occ is not None:
+            mats = [gn_combine(H, occ[t]) for t, H in enumerate(mats)]
+        return GaussNewton(lo, grads, mats, okb, has)
+
+    def fit_constants_lm(self, X, y, consts0, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0, down: float = 0.1,
+                         history: Optional[list] = None):
+        """Levenberg-Marquardt on the constants of every tree at once (the plain loop; one ``eval_gauss_newton`` per iteration behind
+        the one at ``consts0``): per tree the step ``GaussNewton.lm_step(lam_t)`` is accepted if the loss decreased (``lam_t *= down``,
+        floor 1e-12), else the tree's constants are restored (``lam_t *= up``).  ``consts0``: ``set_constants``' layout.  Trees without
+        ``has_jtj`` keep ``consts0``.  Returns (consts, loss[n_trees] in float64, ok) at the accepted constants, which the population
+        holds afterwards; ``history`` (a list) receives the accepted losses after every evaluation."""
+        consts = np.array(consts0, dtype=self.dtype).reshape(-1).copy()
+        if consts.size != int(self.n_consts.sum()):
+            raise ValueError("wrong number of constants")
+        at = np.zeros(self.n_trees + 1, dtype=np.int64)
+        np.cumsum(self.n_consts, out=at[1:])
+        self.set_constants(consts)
+        gn = self.eval_gauss_newton(X, y, weights=weights)
+        loss, ok, has = _host(gn.loss).astype(np.float64), _host(gn.ok).astype(bool), _host(gn.has_jtj).astype(bool)
+        grad, jtj = [_host(g) for g in gn.grad], [_host(h) for h in gn.jtj]
+        lam = np.full(self.n_trees, float(lam0), dtype=np.float64)
+        if history is not None:
+            history.append(loss.copy())
+        for _ in range(int(iters)):
+            steps = GaussNewton(loss, grad, jtj, ok, has).lm_step(lam)
+            trial = consts.copy()
+            for t in range(self.n_trees):
+                if has[t]:
+                    trial[at[t]:at[t + 1]] = (consts[at[t]:at[t + 1]].astype(np.float64) + steps[t]).astype(self.dtype)
+            self.set_constants(trial)
+            gt = self.eval_gauss_newton(X, y, weights=weights)
+            loss_t, ok_t, has_t = _host(gt.loss).astype(np.float64), _host(gt.ok).astype(bool), _host(gt.has_jtj).astype(bool)
+            with np.errstate(invalid="ignore"):
+                accept = has & has_t & (loss_t < loss)
+            for t in np.flatnonzero(accept):
+                consts[at[t]:at[t + 1]] = trial[at[t]:at[t + 1]]
+                loss[t], ok[t] = loss_t[t], ok_t[t]
+                grad[t], jtj[t] = _host(gt.grad[t]), _host(gt.jtj[t])
+            lam = np.where(accept, np.maximum(lam * down, 1e-12), lam * up)
+            if history is not None:
+                history.append(loss.copy())
+        self.set_constants(consts)
+        return consts, loss, ok
 
     def eval_loss_grad_by_class(self, X, y, params, classes, weights=None, loss: str = "L2",
                                 variable: Union[bool, str] = "both", class_base: int = 1, grouped: bool = False, loss_param: float = 0.0):

@@ -518,9 +518,15 @@ struct ByClassPlan {
     void *loss_c, *dloss_c;
     bool done;
 };
+// de_eval_loss_gn: the same launch with the kernels' Gauss-Newton tree end and G (G + 1) / 2 more reduction columns per tree of at most
+// DE_GN_MAX_ROWS rows; jtj_offsets: host, element offset of every tree's G x G block (null: packed)
+struct GnPlan {
+    void *jtj;
+    const int64_t *jtj_offsets;
+};
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false);
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr);
 // DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
 static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
@@ -548,12 +554,22 @@ int de_eval_loss_grad_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
     DE_REFUSE_F16("de_eval_loss_grad");
     DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr));
 }
+int de_gn_max_rows(void) { return DE_GN_MAX_ROWS; }
+int de_eval_loss_gn(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                    const void *y, const void *w, void *loss, void *dloss, const int64_t *dloss_offsets,
+                    void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_gn");
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    const GnPlan gn{jtj, jtj_offsets};
+    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, loss, dloss, dloss_offsets, ok, nullptr, true, &gn));
+}
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only) {
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only, const GnPlan *gn) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (N < 0 || !ok || (p->n_trees > 0 && (!dloss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (gn && p->n_trees > 0 && (!gn->jtj || !y)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
     if (mode != DE_GRAD_VARIABLE && mode != DE_GRAD_CONSTANT && mode != DE_GRAD_BOTH) return fail(c, DE_ERR_INVALID_ARG, "bad gradient mode");
     if (first_kinds_only && spec->kind != DE_LOSS_L2 && spec->kind != DE_LOSS_L1 && spec->kind != DE_LOSS_PULLBACK)
@@ -567,8 +583,8 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     const size_t es = p->dtype == DE_F32 ? 4 : 8;
     // per-tree geometry: tree t owns reduction columns col_off[t] (loss) .. col_off[t] + n_grad[t]
     std::vector<int32_t> ng((size_t)p->n_trees);
-    std::vector<int64_t> coloff((size_t)p->n_trees + 1, 0), doff((size_t)p->n_trees);
-    int64_t span = 0, run = 0;
+    std::vector<int64_t> coloff((size_t)p->n_trees + 1, 0), doff((size_t)p->n_trees), joff(gn ? (size_t)p->n_trees : 0);
+    int64_t span = 0, run = 0, jspan = 0, jrun = 0;
     int32_t maxg = 0;
     for (int64_t t = 0; t < p->n_trees; t++) {
         const int32_t g = (int32_t)de_program_n_grad(p, t, mode);
@@ -580,6 +596,14 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
         run += g;
         span = std::max(span, off + g);
         coloff[(size_t)t + 1] = coloff[(size_t)t] + 1 + g;
+        if (gn) { // ... then the lower triangle of its Gauss-Newton matrix, where the tree's rows share a window
+            const int64_t jo = gn->jtj_offsets ? gn->jtj_offsets[t] : jrun;
+            if (jo < 0) return fail(c, DE_ERR_INVALID_ARG, "negative jtj offset");
+            joff[(size_t)t] = jo;
+            jrun += (int64_t)g * g;
+            jspan = std::max(jspan, jo + (int64_t)g * g);
+            if (g <= DE_GN_MAX_ROWS) coloff[(size_t)t + 1] += (int64_t)g * (g + 1) / 2;
+        }
     }
     const int64_t n_cols = coloff[(size_t)p->n_trees];
     const bool ok_dev = is_device_ptr(ok);
@@ -593,6 +617,18 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
             const double v = p->host_ok_grad[(size_t)t] ? 0.0 : std::nan("");
             put(zl.data(), t, v);
             for (int32_t k = 0; k < ng[(size_t)t]; k++) put(zd.data(), doff[(size_t)t] + k, v);
+        }
+        if (gn) { // (a wider tree's block is NaN whatever N is)
+            std::vector<unsigned char> zj((size_t)std::max<int64_t>(jspan, 1) * es);
+            for (int64_t t = 0; t < p->n_trees; t++) {
+                const int64_t gg = (int64_t)ng[(size_t)t] * ng[(size_t)t];
+                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= DE_GN_MAX_ROWS ? 0.0 : std::nan("");
+                for (int64_t e = 0; e < gg; e++) put(zj.data(), joff[(size_t)t] + e, v);
+            }
+            for (int64_t t = 0; t < p->n_trees; t++)
+                if (ng[(size_t)t] > 0)
+                    HIP_TRY(c, hipMemcpy(static_cast<char *>(gn->jtj) + (size_t)joff[(size_t)t] * es, zj.data() + (size_t)joff[(size_t)t] * es,
+                                         (size_t)ng[(size_t)t] * (size_t)ng[(size_t)t] * es, hipMemcpyDefault));
         }
         for (int64_t t = 0; t < p->n_trees; t++) // only the entries each tree owns are written
             if (ng[(size_t)t] > 0)
@@ -608,7 +644,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     if (rc) return rc;
     const auto tg1 = std::chrono::steady_clock::now();
 
-    Staged sX, sY, sW, sLoss, sDl, sOk, sPar, sCls;
+    Staged sX, sY, sW, sLoss, sDl, sOk, sPar, sCls, sJ;
     rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX);
     if (rc) return rc;
     rc = stage_in(c, c->sY, y, (size_t)N * es, &sY);
@@ -623,6 +659,10 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     }
     rc = stage_out(c, c->sDloss, dloss, (size_t)std::max<int64_t>(span, 1) * es, &sDl);
     if (rc) return rc;
+    if (gn) {
+        rc = stage_out(c, c->sJtj, gn->jtj, (size_t)std::max<int64_t>(jspan, 1) * es, &sJ);
+        if (rc) return rc;
+    }
     if (ok_dev) sOk.dev = ok;
     else {
         HIP_TRY(c, c->sOk.reserve((size_t)p->n_trees));
@@ -655,6 +695,10 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     HIP_TRY(c, hipMemcpyAsync(c->sNg.p, ng.data(), ng.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sColOff.p, coloff.data(), coloff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sDoff.p, doff.data(), doff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (gn) {
+        HIP_TRY(c, c->sJoff.reserve(joff.size() * sizeof(int64_t)));
+        HIP_TRY(c, hipMemcpyAsync(c->sJoff.p, joff.data(), joff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    }
     if (p->uses_params) {
         rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar);
         if (rc) return rc;
@@ -710,8 +754,14 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     g.n_cols = n_cols;
     g.dloss = sDl.dev;
     g.dloss_off = static_cast<const int64_t *>(c->sDoff.p);
-    rc = ensure_rev_threaded(c, p, mode, &g);
-    if (rc) return rc;
+    if (gn) { // always forward duals: the reverse kernel has no dual rows
+        g.gn = true;
+        g.jtj = sJ.dev;
+        g.jtj_off = static_cast<const int64_t *>(c->sJoff.p);
+    } else {
+        rc = ensure_rev_threaded(c, p, mode, &g);
+        if (rc) return rc;
+    }
     if (plan && !g.rev_code) return DE_OK; // forward duals: the caller runs one call per class (plan->done stays false)
     if (plan) {
         HIP_TRY(c, c->sBcTiles.reserve(std::max<size_t>(tile_range.size(), 2) * sizeof(int64_t)));
@@ -749,8 +799,14 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
                 HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(dloss) + (size_t)doff[(size_t)t] * es,
                                           static_cast<char *>(sDl.dev) + (size_t)doff[(size_t)t] * es, (size_t)ng[(size_t)t] * es,
                                           hipMemcpyDeviceToHost, c->stream));
+    if (sJ.staged)
+        for (int64_t t = 0; t < p->n_trees; t++)
+            if (ng[(size_t)t] > 0)
+                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(gn->jtj) + (size_t)joff[(size_t)t] * es,
+                                          static_cast<char *>(sJ.dev) + (size_t)joff[(size_t)t] * es,
+                                          (size_t)ng[(size_t)t] * (size_t)ng[(size_t)t] * es, hipMemcpyDeviceToHost, c->stream));
     if (sOk.staged) HIP_TRY(c, hipMemcpyAsync(ok, sOk.dev, (size_t)p->n_trees, hipMemcpyDeviceToHost, c->stream));
-    if (sX.staged || sY.staged || sW.staged || sLoss.staged || sDl.staged || sOk.staged || sPar.staged || sCls.staged)
+    if (sX.staged || sY.staged || sW.staged || sLoss.staged || sDl.staged || sJ.staged || sOk.staged || sPar.staged || sCls.staged)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DE_OK;
 }

@@ -81,7 +81,7 @@ struct de_ctx {
     // megabytes), and the next creation faults the same pages in again.  Up to four destroyed programs are parked with their vectors
     // cleared; a creation takes the vectors' capacity over (park_program / adopt_parked).
     std::vector<struct de_program *> parked;
-    DevBuf sX, sOut, sGrad, sOk, sParams, sClasses, sOut2, sGoff, sNg, sY, sW, sLoss, sPartial, sSeg, sDloss, sColOff, sDoff, sPrio, sStats, sYstats;
+    DevBuf sX, sOut, sGrad, sOk, sParams, sClasses, sOut2, sGoff, sNg, sY, sW, sLoss, sPartial, sSeg, sDloss, sColOff, sDoff, sPrio, sStats, sYstats, sJtj, sJoff;
     DevBuf sCert; // de_eval_sum_certificate: per-tree maxima
     DevBuf sBcLoss, sBcDloss, sBcOk, sBcNg, sBcDoff, sBcOut, sBcTiles; // de_eval_loss_grad_by_class
     int nested = 0; // > 0 inside a call made of several inner calls: those do not touch the timing events

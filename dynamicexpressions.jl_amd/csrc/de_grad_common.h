@@ -292,7 +292,8 @@ template <typename T> __device__ __forceinline__ LossTerm<T> loss_term(int loss_
 
 // What a module of the threaded kernels (de_grad_threaded.hip: 18, de_rev_threaded.hip: 2) hands to the one launch path
 // (de_grad_kernels.hip): the host stubs of its handler-table fill kernel and of its kernel, kernel[PARAMS][SHARE] (the reverse kernel
-// has no SHARE form).  Every kernel takes (GArgs<T>, handler base, parameter handler offset).
-struct GradModule { const void *fill; const void *kernel[2][2]; };
+// has no SHARE form); kernel_gn: the same kernels with the Gauss-Newton tree end (de_eval_loss_gn; forward modules only).  Every kernel
+// takes (GArgs<T>, handler base, parameter handler offset).
+struct GradModule { const void *fill; const void *kernel[2][2]; const void *kernel_gn[2][2]; };
 
 } // namespace de

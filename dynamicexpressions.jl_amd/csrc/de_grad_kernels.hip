@@ -25,7 +25,10 @@ namespace de {
 
 // One sample per thread; LDS rows of GBLK(+4) elements: rows [0,F) = X tile, then each spill
 // slot s owns 1+GC rows (x, d[0..GC)).
-template <typename T, int GC>
+// GN: the launch of de_eval_loss_gn — behind the loss and its gradient the tree end also reduces the products
+// sum_j w_j d_i(j) d_k(j), i <= k < G, of a tree whose rows lie in this one window (de_grad_threaded.hip g_epilogue_gn: same columns, same
+// association order).  A template parameter: the other instantiations keep the code they had.
+template <typename T, int GC, bool GN = false>
 __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
     constexpr int RS = GBLK + 4; // row stride (elements)
     extern __shared__ __align__(16) unsigned char gsmem[];
@@ -230,6 +233,19 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
                     if ((tid & 63) == 63) pp[(int64_t)(1 + g0 + k) * 4] = s;
                 }
             }
+            if constexpr (GN) {
+                if (g0 == 0 && G <= GC) {
+                    T *__restrict__ pj = pp + (int64_t)(1 + G) * 4;
+                    DE_UNROLL for (int k = 0; k < GC; k++) {
+                        if (k < G) { // wave-uniform
+                            DE_UNROLL for (int i = 0; i <= k; i++) {
+                                const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wv * d[i]) * d[k]);
+                                if ((tid & 63) == 63) pj[(k * (k + 1) / 2 + i) * 4] = s;
+                            }
+                        }
+                    }
+                }
+            }
         } else if (live) {
             if (a.diff_g0 >= 0) {
                 if (a.out) a.out[(int64_t)tree * a.ld_out + base + tid] = x;
@@ -270,6 +286,49 @@ __global__ void __launch_bounds__(256) de_loss_grad_finish_kernel(const double *
     const T v = ok[t] != 0 ? (T)s : M<T>::nan();
     if (c == 0) { if (loss) loss[t] = v; }
     else dloss[dloss_off[t] + c - 1] = v;
+}
+
+// ... of de_eval_loss_gn: a tree of G <= gn_max rows owns G (G + 1) / 2 more columns, entry (i, k), i <= k, of its Gauss-Newton matrix at
+// 1 + G + k (k + 1) / 2 + i.  Loss and gradient exactly as above (same segment order, same bits); every triangle entry goes into both halves of
+// the tree's column-major G x G block at jtj_off[t]; the thread of a wider tree's loss column fills its block with NaN.
+template <typename T>
+__global__ void __launch_bounds__(256) de_loss_gn_finish_kernel(const double *__restrict__ seg_sum, int64_t n_trees, int64_t n_cols,
+                                                               int32_t n_segs, const int64_t *__restrict__ col_off,
+                                                               const int32_t *__restrict__ n_grad, const uint8_t *__restrict__ ok,
+                                                               T *__restrict__ loss, T *__restrict__ dloss,
+                                                               const int64_t *__restrict__ dloss_off, T *__restrict__ jtj,
+                                                               const int64_t *__restrict__ jtj_off, int32_t gn_max) {
+    const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (col >= n_cols) return;
+    int64_t lo = 0, hi = n_trees; // col_off[lo] <= col < col_off[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (col_off[mid] <= col) lo = mid;
+        else hi = mid;
+    }
+    const int64_t t = lo;
+    const int c = (int)(col - col_off[t]);
+    const int G = n_grad[t];
+    double s = 0.0;
+    for (int32_t g = 0; g < n_segs; ++g)
+        for (int w = 0; w < 4; ++w) s += seg_sum[((int64_t)g * n_cols + col) * 4 + w];
+    const T v = ok[t] != 0 ? (T)s : M<T>::nan();
+    if (c == 0) {
+        if (loss) loss[t] = v;
+        if (G > gn_max) {
+            T *__restrict__ blk = jtj + jtj_off[t];
+            for (int64_t e = 0; e < (int64_t)G * G; e++) blk[e] = M<T>::nan();
+        }
+    } else if (c <= G) dloss[dloss_off[t] + c - 1] = v;
+    else {
+        const int e = c - 1 - G;
+        int k = 0;
+        while ((k + 1) * (k + 2) / 2 <= e) ++k;
+        const int i = e - k * (k + 1) / 2;
+        T *__restrict__ blk = jtj + jtj_off[t];
+        blk[i + (int64_t)G * k] = v;
+        blk[k + (int64_t)G * i] = v;
+    }
 }
 
 // ---- one launch path for the three gradient kernels ----------------------------------------------------------------------------------
@@ -345,7 +404,7 @@ static hipError_t launch_grad_kernel(const void *kern, GArgs<T> a, int windows, 
     return hipLaunchKernel(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), args, lds, stream);
 }
 
-template <typename T, int GC>
+template <typename T, int GC, bool GN = false>
 static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t stream) {
     const EvalArgs &e = ga.e;
     GArgs<T> a = make_gargs<T>(ga);
@@ -357,7 +416,7 @@ static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t str
     a.check = ga.diff_direction >= 0 ? 0 : 1;
     a.diff_g0 = ga.diff_direction >= 0 ? ga.P + ga.diff_direction : -1;
     const size_t lds = (size_t)(a.F + (size_t)a.n_slots * (1 + GC)) * (GBLK + 4) * sizeof(T);
-    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
+    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC, GN>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
     if (st != hipSuccess || !ga.loss) return st;
     return launch_loss_grad_finish(sizeof(T) == 4 ? DE_F32 : DE_F64, ga, a.n_tiles, stream);
 }
@@ -368,6 +427,13 @@ template <typename T> static hipError_t loss_grad_finish_t(const GradArgs &ga, i
     hipError_t st = launch_loss_reduce_tiles(sizeof(T) == 4 ? DE_F32 : DE_F64, ga.loss->partial, ga.n_cols * 4, n_tiles, ga.loss->seg_sum,
                                              &n_segs, stream);
     if (st != hipSuccess) return st;
+    if (ga.gn) {
+        hipLaunchKernelGGL(de_loss_gn_finish_kernel<T>, dim3((unsigned)((ga.n_cols + 255) / 256)), dim3(256), 0, stream,
+                           static_cast<const double *>(ga.loss->seg_sum), (int64_t)ga.e.n_trees, ga.n_cols, n_segs, ga.col_off, ga.n_grad,
+                           ga.e.ok, static_cast<T *>(ga.loss->loss), static_cast<T *>(ga.dloss), ga.dloss_off, static_cast<T *>(ga.jtj),
+                           ga.jtj_off, (int32_t)DE_GN_MAX_ROWS);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(de_loss_grad_finish_kernel<T>, dim3((unsigned)((ga.n_cols + 255) / 256)), dim3(256), 0, stream,
                        static_cast<const double *>(ga.loss->seg_sum), (int64_t)ga.e.n_trees, ga.n_cols, n_segs, ga.col_off,
                        ga.e.ok, static_cast<T *>(ga.loss->loss), static_cast<T *>(ga.dloss), ga.dloss_off);
@@ -386,16 +452,16 @@ hipError_t launch_loss_grad_finish(int dtype, const GradArgs &ga, int64_t n_tile
     return dtype == DE_F32 ? loss_grad_finish_t<float>(ga, n_tiles, stream) : loss_grad_finish_t<double>(ga, n_tiles, stream);
 }
 
-template <typename T> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
+template <typename T, bool GN = false> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
     const int maxg = ga.max_grad < 1 ? 1 : ga.max_grad;
     // smallest window that covers the widest gradient in one pass, else windows of 8
-    if (maxg <= 1) return launch_grad_t<T, 1>(ga, 1, stream);
-    if (maxg <= 2) return launch_grad_t<T, 2>(ga, 1, stream);
-    if (maxg <= 3) return launch_grad_t<T, 3>(ga, 1, stream);
-    if (maxg <= 4) return launch_grad_t<T, 4>(ga, 1, stream);
-    if (maxg <= 5) return launch_grad_t<T, 5>(ga, 1, stream);
-    if (maxg <= 6) return launch_grad_t<T, 6>(ga, 1, stream);
-    return launch_grad_t<T, 8>(ga, (maxg + 7) / 8, stream);
+    if (maxg <= 1) return launch_grad_t<T, 1, GN>(ga, 1, stream);
+    if (maxg <= 2) return launch_grad_t<T, 2, GN>(ga, 1, stream);
+    if (maxg <= 3) return launch_grad_t<T, 3, GN>(ga, 1, stream);
+    if (maxg <= 4) return launch_grad_t<T, 4, GN>(ga, 1, stream);
+    if (maxg <= 5) return launch_grad_t<T, 5, GN>(ga, 1, stream);
+    if (maxg <= 6) return launch_grad_t<T, 6, GN>(ga, 1, stream);
+    return launch_grad_t<T, 8, GN>(ga, (maxg + 7) / 8, stream);
 }
 
 // ---- de_eval_loss_grad_by_class: fold the per-class passes into the outputs ---------------------------
@@ -611,11 +677,11 @@ template <typename T> static hipError_t launch_grad_bucket(const GradArgs &ga, c
     a.n_tiles = share ? 4 * ((e.N + GBLK * VS - 1) / (GBLK * VS)) : (e.N + tile_samples - 1) / tile_samples;
     const size_t slot_rows = std::max<size_t>((size_t)a.n_slots * (1 + GC), (size_t)GC);
     const size_t lds = (share ? (size_t)a.F + 4 * slot_rows : 4 * ((size_t)a.F + slot_rows)) * 64 * VS * sizeof(T); // 4 waves x rows x one wave's samples (shared leaf rows: once)
-    return launch_grad_kernel(m.kernel[e.uses_params ? 1 : 0][share ? 1 : 0], a, bk.windows, lds, ga.prio_ready ? e.prio_keys : nullptr, tile_samples,
+    return launch_grad_kernel((ga.gn ? m.kernel_gn : m.kernel)[e.uses_params ? 1 : 0][share ? 1 : 0], a, bk.windows, lds, ga.prio_ready ? e.prio_keys : nullptr, tile_samples,
                               ga.prio_ready, bk.handler_base, bk.param_handler_off, stream); // the loss reduction passes run once, after the last bucket
 }
 hipError_t launch_grad_threaded(int dtype, const GradArgs &a0, hipStream_t stream, const char **kernel_name) {
-    if (kernel_name) *kernel_name = "de_grad_threaded_kernel";
+    if (kernel_name) *kernel_name = a0.gn ? "de_grad_threaded_kernel<GN>" : "de_grad_threaded_kernel";
     GradArgs a;
     { const hipError_t ps = grad_prio_prepass(dtype, a0, stream, &a); if (ps != hipSuccess) return ps; }
     if (a.loss) { // two-sample modules use 512-sample tiles: the 256-sample tile slots they never write must read as 0
@@ -697,8 +763,9 @@ hipError_t launch_rev_threaded(int dtype, const GradArgs &a0, hipStream_t stream
 
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name) {
     if (a.threaded_code && a.diff_direction < 0) return launch_grad_threaded(dtype, a, stream, kernel_name);
-    if (kernel_name) *kernel_name = "de_grad_tape_kernel";
+    if (kernel_name) *kernel_name = a.gn ? "de_grad_tape_kernel<GN>" : "de_grad_tape_kernel";
     if (a.diff_direction >= 0) return dtype == DE_F32 ? launch_grad_t<float, 1>(a, 1, stream) : launch_grad_t<double, 1>(a, 1, stream);
+    if (a.gn) return dtype == DE_F32 ? launch_grad_dt<float, true>(a, stream) : launch_grad_dt<double, true>(a, stream);
     if (dtype == DE_F32) return launch_grad_dt<float>(a, stream);
     return launch_grad_dt<double>(a, stream);
 }

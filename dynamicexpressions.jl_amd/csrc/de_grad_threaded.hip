@@ -394,6 +394,54 @@ __device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const
         }
     }
 }
+// Tree end of de_eval_loss_gn: the L2 loss and its gradient as g_epilogue_loss forms them, then the Gauss-Newton products
+//   sum_j w_j d_i(j) d_k(j),  i <= k < G,
+// of a tree whose rows lie in this one window (g0 == 0 && G <= GC: every tree of at most de_gn_max_rows() rows), into the columns behind the
+// gradient's: entry (i, k) at 1 + G + k (k + 1) / 2 + i.  One association order, (w d_i) d_k, everywhere — scaling every weight by a power of
+// two scales every sum exactly.  Called by the GN instantiations of the kernel only: the others keep the register budget they had.
+template <typename T, int GC, bool SHARE>
+__device__ __noinline__ void g_epilogue_gn(GState<T, GC> st, const T *y, const T *w, T *pp, int64_t N, int G, int g0, int64_t tile) {
+    constexpr int TILE = GBLK * VS, WSAMP = 64 * VS;
+    const int tid = threadIdx.x, wave = SHARE ? (int)(tile & 3) : tid >> 6, lane = tid & 63;
+    const int64_t jl = SHARE ? tile * WSAMP + (int64_t)lane * VS : tile * TILE + (int64_t)tid * VS, last = N - 1; // this lane's first sample
+    T l = T(0);
+    LV(T) lp, wv;
+    DE_UNROLL for (int i = 0; i < VS; i++) {
+        const int64_t j = jl + i;
+        const int64_t jj = j < last ? j : last;
+        const T yv = y[jj];
+        wv[i] = j <= last ? (w ? w[jj] : T(1)) : T(0);
+        const LossTerm<T> lt = loss_term<T>(1 + DE_LOSS_L2, st.x[i], yv, wv[i], T(0));
+        lp[i] = lt.lp;
+        l += lt.l;
+    }
+    pp += wave;
+    if (g0 == 0) {
+        const T s = wave_sum_to_lane63(l);
+        if (lane == 63) pp[0] = s;
+    }
+    DE_UNROLL for (int k = 0; k < GC; k++) {
+        if (g0 + k < G) { // wave-uniform
+            T c = T(0);
+            DE_UNROLL for (int i = 0; i < VS; i++) c += wv[i] == T(0) ? T(0) : lp[i] * st.d[k][i];
+            const T s = wave_sum_to_lane63(c);
+            if (lane == 63) pp[(int64_t)(1 + g0 + k) * 4] = s;
+        }
+    }
+    if (g0 == 0 && G <= GC) {
+        T *__restrict__ pj = pp + (int64_t)(1 + G) * 4;
+        DE_UNROLL for (int k = 0; k < GC; k++) {
+            if (k < G) { // wave-uniform
+                DE_UNROLL for (int i = 0; i <= k; i++) {
+                    T c = T(0);
+                    DE_UNROLL for (int s = 0; s < VS; s++) c += wv[s] == T(0) ? T(0) : (wv[s] * st.d[i][s]) * st.d[k][s];
+                    const T sum = wave_sum_to_lane63(c);
+                    if (lane == 63) pj[(k * (k + 1) / 2 + i) * 4] = sum;
+                }
+            }
+        }
+    }
+}
 // The Jacobian block and the values are written once and never read by the kernel: non-temporal stores (round 5: the eval kernel's output
 // stream gained 2 % from them; -DDE_GRAD_NT_STORE=0 for the A/B)
 #ifndef DE_GRAD_NT_STORE
@@ -453,7 +501,8 @@ __device__ __noinline__ void g_epilogue_store(GState<T, GC> st, T *out_row, T *g
 
 // VS consecutive samples per thread; wave-major LDS: per wave, rows [0,F) = its slice of the X tile, then each
 // spill slot s owns 1+GC rows (x, d[0..GC)); at least GC rows follow the X rows (output staging).
-template <typename T, int GC, bool PARAMS, bool SHARE = false>
+// GN: the launch of de_eval_loss_gn — the tree end is g_epilogue_gn
+template <typename T, int GC, bool PARAMS, bool SHARE = false, bool GN = false>
 __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a, const uint64_t hbase, const uint32_t param_off) {
     constexpr int TILE = GBLK * VS, WSAMP = 64 * VS; // samples per workgroup / per wave
     extern __shared__ __align__(16) unsigned char gtsmem[];
@@ -541,7 +590,10 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
         // n_grad (the lone column of a tree without constants in constant mode) holds g*0 terms that are NaN
         // for an infinite partial although the reference's gradient matrix has no such row
         DE_UNROLL for (int k = 0; k < GC; k++) gpoison<T>(poison, g0 + k < G ? st.d[k] : lv_splat<T>(T(0)));
-        if (a.loss_mode) {
+        if constexpr (GN) {
+            const int64_t n_cols = col_off[a.n_all_trees];
+            g_epilogue_gn<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, G, g0, (int64_t)tm.tile);
+        } else if (a.loss_mode) {
             const int64_t n_cols = col_off[a.n_all_trees];
             g_epilogue_loss<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, a.loss_mode, a.loss_param, G, g0, (int64_t)tm.tile);
         } else {
@@ -564,6 +616,10 @@ GradModule DE_GT_NAME(grad_thr_module_)() {
     m.kernel[0][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, false>);
     m.kernel[1][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, true>);
     m.kernel[0][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, true>);
+    m.kernel_gn[1][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, false, true>);
+    m.kernel_gn[0][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, false, true>);
+    m.kernel_gn[1][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, true, true>);
+    m.kernel_gn[0][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, true, true>);
     return m;
 }
 

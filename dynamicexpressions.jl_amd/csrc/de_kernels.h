@@ -121,6 +121,7 @@ hipError_t launch_tile_extremes(int dtype, const void *X, int64_t N, int64_t ldX
                                 uint8_t *ok = nullptr, int32_t n_ok = 0);
 bool prio_tiles_wanted(int64_t N, int F, int64_t n_trees);
 
+constexpr int DE_GN_MAX_ROWS = 8; // de_gn_max_rows(): the widest window of the forward-dual kernels (a wider tree's rows never meet in one wave)
 struct GradArgs {
     EvalArgs e;               // e.code is unused: the gradient kernel runs the bound UNFOLDED program
     const BoundInstr *generic_code; // device, +1 pad (bound form of the unfolded generic program)
@@ -137,6 +138,11 @@ struct GradArgs {
     int64_t n_cols;           // = col_off[n_trees]
     void *dloss;              // device: tree t's n_grad[t] reduced gradient entries at dloss_off[t]
     const int64_t *dloss_off; // device, n_trees
+    // de_eval_loss_gn: the kernels' Gauss-Newton tree end; a tree of G <= DE_GN_MAX_ROWS rows owns G (G + 1) / 2 further columns (the
+    // triangle of sum w d_i d_k) behind its gradient's, finished into both halves of its column-major G x G block at jtj_off[t]
+    bool gn;
+    void *jtj;                // device
+    const int64_t *jtj_off;   // device, n_trees
     // threaded-code variant (de_grad_threaded.hip): non-null = use it.  Trees are grouped into buckets by
     // gradient width; each bucket is one launch of the module built for its window width.
     const BoundInstr *threaded_code;

@@ -732,6 +732,47 @@ function eval_population_loss_grad(
 end
 
 """
+    eval_population_gauss_newton(pop, X, y; weights=nothing, variable=Val(false))
+        -> (loss::Vector{T}, dloss::Vector{Vector{T}}, jtj::Vector{Matrix{T}}, ok, has_jtj)
+
+The normal equations of a Levenberg-Marquardt step for a whole population in one launch (`de_eval_loss_gn`): the L2 loss and its
+gradient exactly as `eval_population_loss_grad` returns them, and `jtj[t] = sum_j w_j d(j) d(j)'` over the gradient rows of
+`variable` (the Gauss-Newton Hessian of the loss is `2 jtj[t]`), without the `n_grad × N` Jacobian.  A tree of more than
+`de_gn_max_rows()` rows in the library's per-occurrence layout has `has_jtj[t] == false` and a NaN matrix; its loss and gradient
+are filled as usual.  For a GraphNode the rows and columns of a shared constant are summed (`combine_rows` on both sides).
+"""
+function eval_population_gauss_newton(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing, variable=Val(false),
+) where {T}
+    mode = grad_mode(variable)
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    dl, jt, ng, offs, joffs = with_pop(pop) do hc, hp
+        ng, offs = grad_widths(hp, pop.n_trees, mode)
+        joffs = Int64[0; cumsum(ng .* ng)]
+        dl = Vector{T}(undef, max(offs[end], 1))
+        jt = Vector{T}(undef, max(joffs[end], 1))
+        check(pop.ctx, GC.@preserve X y weights lossv dl jt offs joffs ok ccall(
+            (:de_eval_loss_gn, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid},
+             Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), lossv, dl, offs, jt, joffs, ok))
+        (dl, jt, ng, offs, joffs)
+    end
+    max_rows = ccall((:de_gn_max_rows, LIBDE), Cint, ())
+    okb = ok .!= 0x00
+    jtj = map(1:pop.n_trees) do t
+        H = reshape(jt[(joffs[t] + 1):joffs[t + 1]], ng[t], ng[t])
+        half = combine_rows(pop, t, H, mode)                              # S H
+        Matrix(transpose(combine_rows(pop, t, Matrix(transpose(half)), mode)))   # (S (S H)')' = S H S'
+    end
+    return lossv, [combine_rows(pop, t, dl[(offs[t] + 1):offs[t + 1]], mode) for t in 1:pop.n_trees], jtj, okb,
+           okb .& (ng .<= max_rows)
+end
+
+"""
     eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(:both))
         -> (loss, dloss::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)
 

@@ -482,6 +482,25 @@ int de_eval_loss_grad_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64
                          const de_loss_spec_t *spec, void *loss, void *dloss, const int64_t *dloss_offsets,
                          uint8_t *ok);
 
+/* Fused Gauss-Newton normal equations per tree (Levenberg-Marquardt on constants), L2 only:
+ *   loss[t]                 = sum_j w_j e_j^2,   dloss[off_t + k] = sum_j 2 w_j e_j d_k(j)      (exactly de_eval_loss_grad, DE_LOSS_L2: same bits)
+ *   jtj[joff_t + i + G_t k] = sum_j w_j d_i(j) d_k(j)       (G_t x G_t, column-major, BOTH triangles written, exactly symmetric)
+ * e_j = tree_t(x_j) - y_j, d_k = d tree_t(x_j) / d theta_k over the gradient rows of `mode`, in de_eval_grad's order,
+ * G_t = de_program_n_grad(prog, t, mode).  The Gauss-Newton Hessian of the loss is 2 jtj.  Nothing of size N is written.
+ * Pointers, staging and offsets as for de_eval_loss_grad (`loss` may be NULL; offsets are host arrays; jtj_offsets == NULL: packed,
+ * G_t^2 entries each; a negative offset is DE_ERR_INVALID_ARG).  w == NULL: weight 1; a weight of 0 excludes the sample.
+ * ok[t] is de_eval_loss_grad's forward-dual flag; loss, dloss and jtj of a tree with ok[t] == 0 are NaN.  Always forward duals:
+ * DE_OPT_REVERSE_GRAD is ignored by this call.  A tree with G_t > de_gn_max_rows() runs in several windows of dual rows, so its
+ * cross-window products exist nowhere: its loss / dloss are filled as usual and its jtj block is NaN — a documented limit, not an
+ * error.  DE_F16 / complex programs: DE_ERR_UNSUPPORTED; a null y / dloss / jtj / ok on a non-empty population or a bad mode:
+ * DE_ERR_INVALID_ARG; both before any output is touched.  The sums are additive over samples: a caller short of scratch memory
+ * (n_tiles x columns x 4 partial sums) may split the samples and add the results. */
+int de_eval_loss_gn(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                    const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                    void *loss, void *dloss, const int64_t *dloss_offsets,
+                    void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
+int de_gn_max_rows(void); /* 8 */
+
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
  * i.e. the gradient w.r.t. the [n_params, n_classes] parameter matrix of tree t (column-major, like
