@@ -51,7 +51,7 @@ EXPORTS = [
     "de_eval_pullback_dX", "de_eval_tree_array", "de_eval_plan", "de_prio_tiles_wanted", "de_program_last_live_trees", "de_dist_unique_id", "de_dist_init", "de_dist_destroy", "de_dist_shard_size", "de_dist_world_size",
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
-    "de_dist_set_timeout", "de_ctx_trim",
+    "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
 ]
 
 
@@ -277,6 +277,9 @@ def library() -> C.CDLL:
     lib.de_program_create.argtypes = [vp, C.c_int, vp, vp, i64, vp, vp, i32, i32, u32, C.POINTER(vp)]
     lib.de_program_create_cse.argtypes = [vp, C.c_int, vp, vp, vp, vp, i64, vp, vp, i32, i32, u32, C.POINTER(vp)]
     lib.de_program_set_consts.argtypes = [vp, vp]
+    lib.de_program_set_consts_device.argtypes = [vp, vp]
+    lib.de_program_get_consts.argtypes = [vp, vp]
+    lib.de_program_consts_device_path.argtypes = [vp]
     lib.de_program_update.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.de_program_destroy.argtypes = [vp]
     lib.de_program_n_trees.restype = i64
@@ -722,11 +725,58 @@ class Population:
         self._occ = all_occ if any(o is not None for o in all_occ) else None
         self.n_nodes = int(lib.de_program_n_nodes(self._h))
         self.__dict__.pop("_ng_cache", None)
+        self.__dict__.pop("_occ_cache", None)
 
     # -- constants (optimiser inner loop, src/NodeUtils.jl:99-143) ------------------
-    def set_constants(self, consts: np.ndarray) -> None:
+    def _occ_index(self):
+        """GraphNode fan-out as two index arrays (cached; ``update`` drops them): ``fan[s]`` = the unique constant of occurrence slot
+        ``s`` (one value per unique constant -> one per slot) and ``first[u]`` = the first slot of unique constant ``u`` (the way back).
+        ``None`` when no tree shares a constant."""
+        if self._occ is None:
+            return None
+        cache = self.__dict__.setdefault("_occ_cache", {})
+        if "fan" not in cache:
+            fan, first, at, slot0 = [], [], 0, 0
+            for o, nu, ns in zip(self._occ, self.n_consts, self._slots_per_tree):
+                o = np.arange(int(nu), dtype=np.int64) if o is None else np.asarray(o, dtype=np.int64)
+                fan.append(o + at)
+                first.append(np.unique(o, return_index=True)[1].astype(np.int64) + slot0)  # (unique ids are 0 .. nu - 1: sorted = in order)
+                at += int(nu)
+                slot0 += int(ns)
+            cache["fan"] = np.concatenate(fan) if fan else np.zeros(0, dtype=np.int64)
+            cache["first"] = np.concatenate(first) if first else np.zeros(0, dtype=np.int64)
+        return cache
+
+    def _occ_index_torch(self, which: str, device):
+        import torch
+        cache = self._occ_index()
+        key = (which, str(device))
+        if key not in cache:
+            cache[key] = torch.as_tensor(cache[which], device=device)
+        return cache[key]
+
+    def set_constants(self, consts) -> None:
+        """New values for all constants (the optimiser's inner loop), one per constant as the user counts them.  A numpy array goes
+        through ``de_program_set_consts``; a torch device tensor of the population's dtype through ``de_program_set_consts_device``:
+        stream-ordered on the current stream, the host never sees the values (``consts_on_device_path`` tells whether the library
+        patched its streams on the device or staged the values through the host)."""
+        n_expected = int(self.n_consts.sum())
+        if _is_torch(consts):
+            if consts.dtype != _torch_dtype(self.dtype):
+                raise ValueError(f"set_constants: tensor of {consts.dtype}, the population is {self.dtype}")
+            if consts.numel() != n_expected:
+                raise ValueError("wrong number of constants")
+            if not consts.is_cuda:
+                raise ValueError("set_constants: a torch tensor must live on the device (pass a numpy array for host values)")
+            self.ctx.use_torch_stream()
+            consts = consts.reshape(-1).contiguous()
+            if self._occ is not None:  # one value per unique constant -> one per occurrence slot, gathered on the device
+                consts = consts.index_select(0, self._occ_index_torch("fan", consts.device))
+            self._consts_keep = consts  # (read in stream order: alive until the next set)
+            self.ctx.check(library().de_program_set_consts_device(self._h, consts.data_ptr() if consts.numel() else None))
+            return
         consts = np.ascontiguousarray(consts, dtype=self.dtype)
-        if consts.size != int(self.n_consts.sum()):
+        if consts.size != n_expected:
             raise ValueError("wrong number of constants")
         if self._occ is not None:  # one value per unique constant -> one per occurrence slot
             parts, at = [], 0
@@ -736,6 +786,27 @@ class Population:
                 at += int(nu)
             consts = np.ascontiguousarray(np.concatenate(parts) if parts else consts, dtype=self.dtype)
         self.ctx.check(library().de_program_set_consts(self._h, consts.ctypes.data if consts.size else None))
+
+    def constants(self, device: bool = False):
+        """The current constants, one per constant as the user counts them (``de_program_get_consts``): a numpy array, or with
+        ``device=True`` a torch tensor on the context's device — filled in stream order, without a copy through the host when the
+        constants were last set from a device tensor.  A shared constant of a GraphNode tree is read from its first occurrence."""
+        n_slots = int(self._slots_per_tree.sum())
+        if device:
+            import torch
+            self.ctx.use_torch_stream()
+            out = torch.empty(n_slots, dtype=_torch_dtype(self.dtype), device=f"cuda:{self.ctx.device}")
+            self.ctx.check(library().de_program_get_consts(self._h, out.data_ptr() if n_slots else None))
+            return out.index_select(0, self._occ_index_torch("first", out.device)) if self._occ is not None else out
+        out = np.empty(n_slots, dtype=self.dtype)
+        self.ctx.check(library().de_program_get_consts(self._h, out.ctypes.data if n_slots else None))
+        return out[self._occ_index()["first"]] if self._occ is not None else out
+
+    @property
+    def consts_on_device_path(self) -> bool:
+        """True when the last ``set_constants`` came from a device tensor and the library patched its streams on the device
+        (``de_program_consts_device_path``); False when it went through the host (numpy values, or a program that is staged)."""
+        return library().de_program_consts_device_path(self._h) == 1
 
     def verify(self) -> None:
         """Program sanitizer (``de_program_verify``): raises ValueError naming the offending instruction."""

@@ -119,6 +119,7 @@ int de_eval_sum_certificate(de_ctx_t *c, de_program_t *p, const void *X, int64_t
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (N < 0 || !ok || !certified || (p->n_trees > 0 && N > 0 && !X)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (is_device_ptr(certified) || (max_abs && is_device_ptr(max_abs))) return fail(c, DE_ERR_INVALID_ARG, "certified / max_abs are host arrays");
+    if (const int mrc = consts_materialise(p)) return mrc; // (the certificate program and the flags below are made from the host side: §3.5)
     if (p->direct) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_sum_certificate needs the LDS-tiled kernel (feature matrix too wide)");
     if (!(p->options & DE_OPT_EARLY_EXIT) || N == 0) {
         // early_exit = false: the reference sums nothing (src/Evaluate.jl:16-32 are no-ops), the flag is the constant part alone; N = 0: sum(empty) = 0
@@ -192,6 +193,10 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     const bool half = p->io == DE_F16;
     const bool cplx = is_complex_io(p->io);
     const bool ok_dev = is_device_ptr(ok);
+    if (p->consts_dev_ahead && (N == 0 || cr || !p->d_ok_eval)) { // (the paths below that read host state: §3.5)
+        rc = consts_materialise(p);
+        if (rc != DE_OK) return rc;
+    }
     if (N == 0) { // nothing to evaluate: only the constant part of the flag (sum(empty) is finite)
         if (ok_dev) HIP_TRY(c, hipMemcpyAsync(ok, p->host_ok_eval.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
         else std::memcpy(ok, p->host_ok_eval.data(), (size_t)p->n_trees);

@@ -27,6 +27,7 @@ template <class T> static hipError_t upload(T *dst, const std::vector<T> &v) {
 extern "C" {
 static int ensure_generic_code(de_ctx *c, de_program *p) {
     if (p->gcode_stale || !p->d_gcode) {
+        if (const int mrc = consts_materialise(p)) return mrc; // (bound from the host code: its immediates must be current, §3.5)
         // gradients flow through constant subtrees, so this is the UNFOLDED program; every value the
         // reference tests is tested (ee binding) whatever the eval options were
         p->gt_valid = false;
@@ -101,9 +102,19 @@ static int ensure_grad_threaded(de_ctx *c, de_program *p, int mode, const std::v
         };
         const GradSource src{p->gbcode, p->gbcode_off, p->n_trees, p->n_features, p->n_params, p->uses_params, p->dtype, mode, ng.data()};
         GradForwardStream r;
-        const int enc = encode_grad_forward(src, opt, grad_threaded_has, handlers, &r);
+        int enc = encode_grad_forward(src, opt, grad_threaded_has, handlers, &r);
         if (hst != hipSuccess) return fail(c, DE_ERR_HIP, "gradient handler table: %s", hipGetErrorString(hst));
-        if (enc == GRAD_ENC_NO_PLAN) return DE_OK;
+        if (enc == GRAD_ENC_NO_PLAN) return DE_OK; // (nothing is kept: a program without a plan asks again at every call)
+        if (enc == GRAD_ENC_OK && p->consts_dev_ahead) {
+            // a stream that will be kept, encoded from a gbcode whose immediates are behind a device set (§3.5): the host side is
+            // brought up first — only now, so that a program without a plan never pays for it — and the stream encoded again
+            if (const int mrc = consts_materialise(p)) return mrc;
+            tables.clear();
+            r = GradForwardStream();
+            enc = encode_grad_forward(src, opt, grad_threaded_has, handlers, &r);
+            if (hst != hipSuccess) return fail(c, DE_ERR_HIP, "gradient handler table: %s", hipGetErrorString(hst));
+            if (enc == GRAD_ENC_NO_PLAN) return DE_OK;
+        }
         p->gtsite_of_gb.clear();
         p->site_gen++;
         if (enc < 0) return fail(c, DE_ERR_HIP, "gradient program: the host threads' partitions disagree");
@@ -190,7 +201,12 @@ static int ensure_rev_threaded(de_ctx *c, de_program *p, int mode, GradArgs *g) 
         for (int64_t t = 0; t < p->n_trees; t++) ng[(size_t)t] = (int32_t)de_program_n_grad(p, t, mode);
         const GradSource src{p->gbcode, p->gbcode_off, p->n_trees, p->n_features, p->n_params, p->uses_params, p->dtype, mode, ng.data()};
         GradReverseStream r;
-        const int enc = encode_grad_reverse(src, opt, p->n_slots, p->cse_generic, h, &r);
+        int enc = encode_grad_reverse(src, opt, p->n_slots, p->cse_generic, h, &r);
+        if (enc == GRAD_ENC_OK && p->consts_dev_ahead) { // (as ensure_grad_threaded: the host side first, then the stream that is kept, §3.5)
+            if (const int mrc = consts_materialise(p)) return mrc;
+            r = GradReverseStream();
+            enc = encode_grad_reverse(src, opt, p->n_slots, p->cse_generic, h, &r);
+        }
         p->rtsite_of_gb.clear();
         p->site_gen++;
         if (enc != GRAD_ENC_OK) return DE_OK;
@@ -324,6 +340,10 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
     const size_t es = p->dtype == DE_F32 ? 4 : 8;
     const bool ok_dev = is_device_ptr(ok);
     std::vector<uint8_t> ones;
+    if (N == 0 && !diff) { // (the flags alone: from the host side, §3.5)
+        rc = consts_materialise(p);
+        if (rc != DE_OK) return rc;
+    }
     const uint8_t *ok_init = p->host_ok_grad.data();
     if (diff) { // no validity test on this path: always complete (src/EvaluateDerivative.jl:117)
         ones.assign((size_t)p->n_trees, 1);
@@ -388,7 +408,8 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         }
         if (p->tab_ok_stale || p->tab_mode != mode || p->tab_N != N) {
             HIP_TRY(c, hipStreamSynchronize(c->stream)); // earlier calls may still read the tables
-            HIP_TRY(c, hipMemcpy(p->d_ok_grad, p->host_ok_grad.data(), nt, hipMemcpyHostToDevice));
+            // (behind a device set the flag kernel has written d_ok_grad, and host_ok_grad is not current: §3.5)
+            if (!p->consts_dev_ahead) HIP_TRY(c, hipMemcpy(p->d_ok_grad, p->host_ok_grad.data(), nt, hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(p->d_ng, ng.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(p->d_goff, goff.data(), nt * sizeof(int64_t), hipMemcpyHostToDevice));
             p->tab_ok_stale = false;
@@ -399,7 +420,8 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         d_goff_use = p->d_goff;
         d_ng_use = p->d_ng;
     } else {
-        HIP_TRY(c, hipMemcpyAsync(sOk.dev, ok_init, (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
+        if (p->consts_dev_ahead && !diff) HIP_TRY(c, hipMemcpyAsync(sOk.dev, p->d_ok_grad, (size_t)p->n_trees, hipMemcpyDeviceToDevice, c->stream));
+        else HIP_TRY(c, hipMemcpyAsync(sOk.dev, ok_init, (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, c->sGoff.reserve(goff.size() * sizeof(int64_t)));
         HIP_TRY(c, c->sNg.reserve(ng.size() * sizeof(int32_t)));
         HIP_TRY(c, hipMemcpyAsync(c->sGoff.p, goff.data(), goff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -608,6 +630,8 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     const int64_t n_cols = coloff[(size_t)p->n_trees];
     const bool ok_dev = is_device_ptr(ok);
     if (N == 0) { // empty sums: 0, or NaN where a constant already fails the flag
+        rc = consts_materialise(p); // (from the host's flags: §3.5)
+        if (rc != DE_OK) return rc;
         std::vector<unsigned char> zl((size_t)p->n_trees * es), zd((size_t)std::max<int64_t>(span, 1) * es);
         auto put = [&](unsigned char *b, int64_t i, double v) {
             if (p->dtype == DE_F32) reinterpret_cast<float *>(b)[i] = (float)v;
@@ -691,7 +715,9 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     HIP_TRY(c, c->sNg.reserve(ng.size() * sizeof(int32_t)));
     HIP_TRY(c, c->sColOff.reserve(coloff.size() * sizeof(int64_t)));
     HIP_TRY(c, c->sDoff.reserve(doff.size() * sizeof(int64_t)));
-    HIP_TRY(c, hipMemcpyAsync(sOk.dev, p->host_ok_grad.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
+    // (behind a device set the initial flags are the device's: §3.5)
+    if (p->consts_dev_ahead) HIP_TRY(c, hipMemcpyAsync(sOk.dev, p->d_ok_grad, (size_t)p->n_trees, hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(c, hipMemcpyAsync(sOk.dev, p->host_ok_grad.data(), (size_t)p->n_trees, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sNg.p, ng.data(), ng.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sColOff.p, coloff.data(), coloff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sDoff.p, doff.data(), doff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));

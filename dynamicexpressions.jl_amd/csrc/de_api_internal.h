@@ -244,6 +244,27 @@ struct de_program {
     std::vector<int32_t> tree_slots;    // per tree: spill slots of its plain and folded lowerings (the larger)
     std::vector<uint8_t> tree_bits;     // per tree: TREE_PARAMS | TREE_CSE_PLAIN | TREE_CSE_FOLDED
     bool allow_fold = true;             // the creation folded constant subtrees (DE_NO_FOLD unset; false for an auxiliary program)
+    // de_program_set_consts_device (kernels: de_const_patch.hip).  consts_dev_ahead: the device streams, flags and
+    // d_cp_vals hold constants the host copies (consts, code, fcode, bcode ..., host_ok_*, fold_ok) have not seen yet — every reader of
+    // host state calls consts_materialise() first.  d_cp_vals: [constants | de_fold_kernel-route fold values | host-route fold values]
+    // in the element type, then the folds' flags; d_cp: the tables (sites, per-tree lists, the host-route folds' image), rebuilt when
+    // cp_key no longer describes the program's streams.
+    bool consts_dev_ahead = false, consts_dev_path = false;
+    char *d_cp_vals = nullptr, *d_cp = nullptr;
+    struct ConstPatchKey {
+        uint64_t site_gen = 0;
+        const void *code = nullptr, *gcode = nullptr, *gtcode = nullptr, *rtcode = nullptr, *ok_grad = nullptr;
+        int64_t gt_stride = 0;
+        int gt_variants = 0;
+        bool operator==(const ConstPatchKey &o) const {
+            return site_gen == o.site_gen && code == o.code && gcode == o.gcode && gtcode == o.gtcode && rtcode == o.rtcode &&
+                   ok_grad == o.ok_grad && gt_stride == o.gt_stride && gt_variants == o.gt_variants;
+        }
+    } cp_key;
+    int cp_eligible = -1; // what the program's folds allow (decided once): 1 device path, 0 staged
+    int64_t cp_n_sites = 0, cp_nk = 0, cp_nh = 0, cp_nkc = 0, cp_nhc = 0;
+    size_t cp_o_fok = 0, cp_o_addr = 0, cp_o_src = 0, cp_o_coff = 0, cp_o_checks = 0, cp_o_tfoff = 0, cp_o_tfold = 0, cp_o_gidx = 0, cp_o_hnodes = 0,
+           cp_o_hnoff = 0, cp_o_hcoff = 0, cp_o_hcvals = 0;
 };
 enum : uint8_t { TREE_PARAMS = 1, TREE_CSE_PLAIN = 2, TREE_CSE_FOLDED = 4 };
 
@@ -276,6 +297,8 @@ struct Staged {
 int stage_in(de_ctx *c, DevBuf &buf, const void *user, size_t bytes, Staged *s);
 int stage_out(de_ctx *c, DevBuf &buf, void *user, size_t bytes, Staged *s);
 int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, int64_t N);
+// the host copies of a program brought up to its device constants (de_api_program.cpp); DE_OK at once when they are current
+int consts_materialise(de_program *p);
 }
 
 // de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)

@@ -1,6 +1,7 @@
 // de_api_program.cpp — C ABI (include/de_hip.h): de_program_create / _create_cse / _set_consts / _destroy, constant folding (host, de_fold_kernel,
 // auxiliary program), the bound / threaded / chained streams of the eval program, and the program hooks (verify, dump, hash, host-only lowering).
 #include "de_api_internal.h"
+#include "de_const_patch.h"
 
 // (src/Evaluate.jl:1002-1067: every node's output is validity-tested; the arithmetic goes on, IEEE propagates what it must).
 // half: a DE_F16 program (T = float) — every result rounded to binary16, as de_half.hip does (+ - * / in Float32 rounded once more to
@@ -570,6 +571,7 @@ static int update_impl(de_program_t *p, const int64_t *tree_ids, int64_t n_updat
     de_ctx *ctx = p->ctx;
     if (n_update < 0) return fail(ctx, DE_ERR_INVALID_ARG, "n_update < 0");
     if (n_update == 0) return DE_OK;
+    if (const int mrc = consts_materialise(p)) return mrc; // (the kept trees' constants and code are copied from the host side: §3.5)
     if (!tree_ids || !nodes || !node_offsets || !const_offsets) return fail(ctx, DE_ERR_INVALID_ARG, "null tree ids or tape pointers");
     if (cse_nodes && !cse_offsets) return fail(ctx, DE_ERR_INVALID_ARG, "cse_offsets is null");
     const int64_t n = p->n_trees;
@@ -1194,12 +1196,39 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
     return DE_OK;
 }
 
+// The compact site lists (eval_sites / grad_sites) of a threaded, patched-in-place program, rebuilt when site_gen moved: one pass over
+// all instructions, afterwards only the immediates are visited.  de_program_set_consts patches by them, and the device tables of
+// de_program_set_consts_device are derived from them.
+static void refresh_site_lists(de_program *p) {
+    if (p->lists_gen == p->site_gen) return;
+    const std::vector<Instr> &src = p->folded ? p->fcode : p->code;
+    p->eval_sites.clear();
+    p->grad_sites.clear();
+    for (size_t i = 0; i < src.size(); i++)
+        if (p->bsite[i] >= 0) {
+            // record of tcode[j] in the chained stream: one end record per preceding tree, behind the head record
+            const int32_t j = p->tsite[i];
+            const int64_t tree = (std::upper_bound(p->tcode_off.begin(), p->tcode_off.end(), j) - p->tcode_off.begin()) - 1;
+            p->eval_sites.push_back({(int32_t)i, p->bsite[i], j, (int32_t)(j + tree + 1)}); // + the head record
+        }
+    if (!p->gbsite.empty())
+        for (size_t i = 0; i < p->code.size(); i++) {
+            const int32_t gj = p->gbsite[i];
+            if (gj < 0) continue;
+            p->grad_sites.push_back({(int32_t)i, gj, p->gtsite_of_gb.empty() ? -1 : p->gtsite_of_gb[(size_t)gj],
+                                     p->rtsite_of_gb.empty() ? -1 : p->rtsite_of_gb[(size_t)gj]});
+        }
+    p->lists_gen = p->site_gen;
+}
+
 static int set_consts_impl(de_program_t *p, const void *consts);
 static int set_consts_nothrow(de_program_t *p, const void *consts) {
     if (!p) return DE_ERR_INVALID_ARG;
     DE_NOTHROW(p->ctx, set_consts_impl(p, consts));
 }
 int de_program_set_consts(de_program_t *p, const void *consts) {
+    // (every host copy and every device stream is overwritten below: constants a device set left ahead of the host need no materialising)
+    if (p && (consts || p->consts.empty())) p->consts_dev_ahead = p->consts_dev_path = false;
     const int rc = set_consts_nothrow(p, consts);
     if (rc == DE_OK && p && getenv("DE_VERIFY") && *getenv("DE_VERIFY") == '1') return de_program_verify(p);
     return rc;
@@ -1250,25 +1279,7 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
         const bool gpatch = p->d_gcode && !p->gcode_stale && !p->gbsite.empty();
         const bool tpatch = gpatch && p->gt_valid && !p->gtsite_of_gb.empty();
         const bool rpatch = gpatch && p->rt_valid && !p->rtsite_of_gb.empty();
-        if (p->lists_gen != p->site_gen) { // one pass over all instructions, then only the immediates are visited
-            p->eval_sites.clear();
-            p->grad_sites.clear();
-            for (size_t i = 0; i < src.size(); i++)
-                if (p->bsite[i] >= 0) {
-                    // record of tcode[j] in the chained stream: one end record per preceding tree, behind the head record
-                    const int32_t j = p->tsite[i];
-                    const int64_t tree = (std::upper_bound(p->tcode_off.begin(), p->tcode_off.end(), j) - p->tcode_off.begin()) - 1;
-                    p->eval_sites.push_back({(int32_t)i, p->bsite[i], j, (int32_t)(j + tree + 1)}); // + the head record
-                }
-            if (!p->gbsite.empty())
-                for (size_t i = 0; i < p->code.size(); i++) {
-                    const int32_t gj = p->gbsite[i];
-                    if (gj < 0) continue;
-                    p->grad_sites.push_back({(int32_t)i, gj, p->gtsite_of_gb.empty() ? -1 : p->gtsite_of_gb[(size_t)gj],
-                                             p->rtsite_of_gb.empty() ? -1 : p->rtsite_of_gb[(size_t)gj]});
-                }
-            p->lists_gen = p->site_gen;
-        }
+        refresh_site_lists(p);
         try {
         parallel_tree_ranges((int64_t)p->eval_sites.size(), [&](int, int64_t sb, int64_t se) {
             for (size_t q = (size_t)sb; q < (size_t)se; q++) {
@@ -1347,6 +1358,286 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
     return DE_OK;
 }
 
+// ---- de_program_set_consts_device (kernels: de_const_patch.hip) -------------------------------------------------------
+// The host side brought up to the device's constants: one device-to-host copy of the owned buffer, then the host function — which
+// writes the same bits into every device stream once more and rebuilds every host copy.
+int consts_materialise(de_program *p) {
+    if (!p || !p->consts_dev_ahead) return DE_OK;
+    de_ctx *c = p->ctx;
+    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    try {
+        std::vector<unsigned char> h(std::max<size_t>(p->consts.size(), 1) * es);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemcpyAsync(h.data(), p->d_cp_vals, p->consts.size() * es, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        p->consts_dev_ahead = false;
+        const int rc = set_consts_nothrow(p, h.data());
+        if (rc != DE_OK) p->consts_dev_ahead = true;
+        return rc;
+    } catch (const std::bad_alloc &) { return fail(c, DE_ERR_HIP, "out of host memory"); }
+}
+
+// What the program's kind and folds allow, decided once: DE_F32 / DE_F64, threaded, no turbo operators, every fold evaluated by
+// de_fold_kernel — its own route, or the host route (+ - * /) where the subtree's evaluation stack fits the kernel's.
+static bool const_patch_kind_ok(de_program *p) {
+    if (p->cp_eligible >= 0) return p->cp_eligible == 1;
+    bool ok = (p->io == DE_F32 || p->io == DE_F64) && p->threaded && !p->aux && p->n_trees > 0 && !(p->options & DE_OPT_TURBO);
+    if (!p->folds.empty() && (p->fold_noff.size() != p->folds.size() + 1 || p->fold_coff.size() != p->folds.size() + 1)) ok = false;
+    for (size_t j = 0; ok && j < p->folds.size(); j++) {
+        if (j >= p->fold_host.size() || p->fold_host[j] == 0) { ok = false; break; }
+        if (p->fold_host[j] != 1) continue;
+        int depth = 0, worst = 0;
+        for (int64_t i = p->fold_noff[j]; i < p->fold_noff[j + 1]; i++) { depth += 1 - (int)p->fold_nodes[(size_t)i].degree; worst = std::max(worst, depth); }
+        if (worst > DE_FOLD_STACK) ok = false;
+    }
+    p->cp_eligible = ok ? 1 : 0;
+    return ok;
+}
+
+// The device tables of the present streams: 1 built, 0 the program cannot be served (a site without a source: never expected), < 0 -status.
+static int build_const_patch_tables(de_ctx *c, de_program *p, const de_program::ConstPatchKey &key, bool gpatch, bool tpatch, bool rpatch) {
+    refresh_site_lists(p);
+    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    const size_t nc = p->consts.size(), nf = p->folds.size(), nt = (size_t)p->n_trees;
+    const std::vector<Instr> &src = p->folded ? p->fcode : p->code;
+    // sources: constant k = k; fold j = nc + its place among the de_fold_kernel-route folds, or behind them among the host-route ones
+    std::vector<uint32_t> pos(nf, 0);
+    std::vector<int32_t> hfold;
+    for (size_t k = 0; k < p->kfold.size(); k++) pos[(size_t)p->kfold[k]] = (uint32_t)k;
+    for (size_t j = 0; j < nf; j++)
+        if (p->fold_host[j] == 1) { pos[j] = (uint32_t)(p->kfold.size() + hfold.size()); hfold.push_back((int32_t)j); }
+    const size_t nk = p->kfold.size(), nh = hfold.size();
+    if (nc + nk + nh > 0xFFFFFFFFull) return 0;
+    std::vector<int64_t> src_eval(src.size(), -1), src_code(p->code.size(), -1);
+    for (size_t k = 0; k < nc; k++) { // (occurrence slots of a shared constant name one instruction of a CSE program: the last one wins, as on the host)
+        const int32_t ie = p->folded ? p->fconst_instr[k] : p->const_instr[k];
+        if (ie >= 0) src_eval[(size_t)ie] = (int64_t)k;
+        if (p->const_instr[k] >= 0) src_code[(size_t)p->const_instr[k]] = (int64_t)k;
+    }
+    if (p->folded)
+        for (size_t j = 0; j < nf; j++) src_eval[(size_t)p->folds[j].instr] = (int64_t)(nc + pos[j]);
+    std::vector<uint64_t> addr;
+    std::vector<uint32_t> srcs;
+    auto site = [&](const BoundInstr *rec, bool word32, int64_t s) {
+        addr.push_back(word32 ? ((uint64_t)(uintptr_t)&rec->arg | CONST_SITE_32) : (uint64_t)(uintptr_t)&rec->lo);
+        srcs.push_back((uint32_t)s);
+    };
+    const size_t nvar = p->var_stride && !p->ccode.empty() ? 1 + p->ccode_w.size() / p->ccode.size() : 1; // (wave groups: every wave's variant)
+    if (nvar > 1 && (size_t)p->var_stride < p->ccode.size()) return 0;
+    for (const de_program::EvalSite &e : p->eval_sites) {
+        const int64_t s = src_eval[(size_t)e.src];
+        if (s < 0 || e.c < 0 || (size_t)e.c >= p->ccode.size()) return 0;
+        for (size_t w = 0; w < nvar; w++) site(p->d_code + w * (size_t)p->var_stride + (size_t)e.c, p->dtype == DE_F32, s);
+    }
+    if (gpatch)
+        for (const de_program::GradSite &g : p->grad_sites) {
+            const int64_t s = src_code[(size_t)g.src];
+            if (s < 0 || g.gb < 0 || (size_t)g.gb >= p->gbcode.size()) return 0;
+            site(p->d_gcode + g.gb, false, s);
+            if (tpatch && g.gt >= 0)
+                for (int64_t w = 0; w < (p->gt_share ? 4 : 1); w++) { // (every stream variant of a shared-leaf-row program)
+                    const size_t at = (size_t)(g.gt + w * p->gt_stride);
+                    if (at >= p->gtcode.size() || at >= p->gt_cap) return 0;
+                    site(p->d_gtcode + at, false, s);
+                }
+            if (rpatch && g.rt >= 0) {
+                if ((size_t)g.rt >= p->rtcode.size()) return 0;
+                site(p->d_rtcode + g.rt, false, s);
+            }
+        }
+    // the flag kernel's lists: the folds of every tree
+    std::vector<int32_t> tfoff(nt + 1, 0);
+    std::vector<uint32_t> tfold(std::max<size_t>(nf, 1), 0);
+    for (size_t j = 0; j < nf; j++) tfoff[(size_t)p->folds[j].tree + 1]++;
+    for (size_t t = 0; t < nt; t++) tfoff[t + 1] += tfoff[t];
+    {
+        std::vector<int32_t> at(tfoff.begin(), tfoff.end() - 1);
+        for (size_t j = 0; j < nf; j++) tfold[(size_t)at[(size_t)p->folds[j].tree]++] = (pos[j] << 1) | (p->folds[j].tested_always ? 1u : 0u);
+    }
+    // the gather list [de_fold_kernel route | host route] and the host-route folds' image for de_fold_kernel
+    std::vector<int64_t> gidx(p->kf_csrc.begin(), p->kf_csrc.end()), hnoff{0}, hcoff{0};
+    std::vector<de_tape_node_t> hnodes;
+    for (const int32_t j : hfold) {
+        hnodes.insert(hnodes.end(), p->fold_nodes.begin() + p->fold_noff[(size_t)j], p->fold_nodes.begin() + p->fold_noff[(size_t)j + 1]);
+        gidx.insert(gidx.end(), p->aux_const_src.begin() + p->fold_coff[(size_t)j], p->aux_const_src.begin() + p->fold_coff[(size_t)j + 1]);
+        hnoff.push_back((int64_t)hnodes.size());
+        hcoff.push_back((int64_t)(gidx.size() - p->kf_csrc.size()));
+    }
+    for (const int64_t k : gidx)
+        if (k < 0 || (size_t)k >= nc) return 0;
+    const size_t nkc = p->kf_csrc.size(), nhc = gidx.size() - nkc;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t o = 0;
+    auto place = [&](size_t bytes) { const size_t at = o; o += al(std::max<size_t>(bytes, 1)); return at; };
+    p->cp_o_addr = place(addr.size() * sizeof(uint64_t));
+    p->cp_o_src = place(srcs.size() * sizeof(uint32_t));
+    p->cp_o_coff = place((nt + 1) * sizeof(int64_t));
+    p->cp_o_checks = place(nc);
+    p->cp_o_tfoff = place((nt + 1) * sizeof(int32_t));
+    p->cp_o_tfold = place(nf * sizeof(uint32_t));
+    p->cp_o_gidx = place(gidx.size() * sizeof(int64_t));
+    p->cp_o_hnodes = place(hnodes.size() * sizeof(de_tape_node_t));
+    p->cp_o_hnoff = place(hnoff.size() * sizeof(int64_t));
+    p->cp_o_hcoff = place(hcoff.size() * sizeof(int64_t));
+    p->cp_o_hcvals = place(nhc * es);
+    std::vector<unsigned char> img(o, 0);
+    auto put = [&](size_t at, const void *data, size_t bytes) { if (bytes) std::memcpy(img.data() + at, data, bytes); };
+    put(p->cp_o_addr, addr.data(), addr.size() * sizeof(uint64_t));
+    put(p->cp_o_src, srcs.data(), srcs.size() * sizeof(uint32_t));
+    put(p->cp_o_coff, p->const_off.data(), (nt + 1) * sizeof(int64_t));
+    put(p->cp_o_checks, p->const_checks.data(), nc);
+    put(p->cp_o_tfoff, tfoff.data(), (nt + 1) * sizeof(int32_t));
+    put(p->cp_o_tfold, tfold.data(), nf * sizeof(uint32_t));
+    put(p->cp_o_gidx, gidx.data(), gidx.size() * sizeof(int64_t));
+    put(p->cp_o_hnodes, hnodes.data(), hnodes.size() * sizeof(de_tape_node_t));
+    put(p->cp_o_hnoff, hnoff.data(), hnoff.size() * sizeof(int64_t));
+    put(p->cp_o_hcoff, hcoff.data(), hcoff.size() * sizeof(int64_t));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (an earlier device set may still read the old tables)
+    prog_free(c, p->d_cp);
+    p->d_cp = nullptr;
+    p->cp_key = de_program::ConstPatchKey();
+    {
+        const hipError_t st = prog_malloc(c, reinterpret_cast<void **>(&p->d_cp), o);
+        if (st != hipSuccess) return -fail(c, DE_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(st));
+    }
+    if (!p->d_cp_vals) { // [constants | fold values] in the element type, then the folds' flags: the program's own copy of its constants
+        p->cp_o_fok = al((nc + nk + nh) * es);
+        const hipError_t st = prog_malloc(c, reinterpret_cast<void **>(&p->d_cp_vals), p->cp_o_fok + al(std::max<size_t>(nk + nh, 1)));
+        if (st != hipSuccess) return -fail(c, DE_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(st));
+    }
+    {
+        const hipError_t st = hipMemcpy(p->d_cp, img.data(), img.size(), hipMemcpyHostToDevice);
+        if (st != hipSuccess) return -fail(c, DE_ERR_HIP, "constant site tables: upload failed: %s", hipGetErrorString(st));
+    }
+    p->cp_n_sites = (int64_t)addr.size();
+    p->cp_nk = (int64_t)nk;
+    p->cp_nh = (int64_t)nh;
+    p->cp_nkc = (int64_t)nkc;
+    p->cp_nhc = (int64_t)nhc;
+    p->cp_key = key;
+    return 1;
+}
+
+static int set_consts_device_impl(de_program_t *p, const void *d_consts) {
+    de_ctx *c = p->ctx;
+    const size_t nc = p->consts.size();
+    if (nc == 0) return DE_OK;
+    if (!d_consts) return fail(c, DE_ERR_INVALID_ARG, "d_consts is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!is_device_ptr(d_consts))
+        return fail(c, DE_ERR_INVALID_ARG, "d_consts is a host pointer: de_program_set_consts takes constants from host memory");
+    const char *nopatch = getenv("DE_NO_CONST_PATCH");
+    bool device = const_patch_kind_ok(p) && !(nopatch && *nopatch == '1') && !p->tsite.empty() && !p->bsite.empty();
+    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    if (device) {
+        // which gradient streams are patched and which are dropped: as de_program_set_consts decides it
+        const bool gpatch = p->d_gcode && !p->gcode_stale && !p->gbsite.empty();
+        const bool tpatch = gpatch && p->gt_valid && !p->gtsite_of_gb.empty();
+        const bool rpatch = gpatch && p->rt_valid && !p->rtsite_of_gb.empty();
+        if (!p->d_ok_grad) { // (the tables de_eval_grad keeps per program: the flag kernel writes the first of them)
+            const size_t nt = (size_t)p->n_trees;
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_ok_grad), nt));
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_ng), nt * sizeof(int32_t)));
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&p->d_goff), nt * sizeof(int64_t)));
+            p->tab_mode = -1;
+        }
+        de_program::ConstPatchKey key;
+        key.site_gen = p->site_gen;
+        key.code = p->d_code;
+        key.gcode = gpatch ? p->d_gcode : nullptr;
+        key.gtcode = tpatch ? p->d_gtcode : nullptr;
+        key.rtcode = rpatch ? p->d_rtcode : nullptr;
+        key.ok_grad = p->d_ok_grad;
+        key.gt_stride = tpatch ? p->gt_stride : 0;
+        key.gt_variants = tpatch ? (p->gt_share ? 4 : 1) : 0;
+        if (!p->d_cp || !(key == p->cp_key)) {
+            const int rc = build_const_patch_tables(c, p, key, gpatch, tpatch, rpatch);
+            if (rc < 0) return -rc;
+            if (rc == 0) { p->cp_eligible = 0; device = false; }
+        }
+        if (device) {
+            char *vals = p->d_cp_vals;
+            uint8_t *fok = reinterpret_cast<uint8_t *>(vals + p->cp_o_fok);
+            const int64_t *gidx = reinterpret_cast<const int64_t *>(p->d_cp + p->cp_o_gidx);
+            if (!c->nested) HIP_TRY(c, time_begin(c));
+            HIP_TRY(c, hipMemcpyAsync(vals, d_consts, nc * es, hipMemcpyDeviceToDevice, c->stream)); // (from here on the caller's buffer is free)
+            HIP_TRY(c, launch_const_gather(p->dtype, vals, gidx, p->cp_nkc, p->d_kf ? p->d_kf + p->kf_o_cvals : nullptr, p->cp_nhc,
+                                           p->d_cp + p->cp_o_hcvals, c->stream));
+            if (p->cp_nk > 0)
+                HIP_TRY(c, launch_fold(p->dtype, p->d_kf, reinterpret_cast<const int64_t *>(p->d_kf + p->kf_o_noff),
+                                       reinterpret_cast<const int64_t *>(p->d_kf + p->kf_o_coff), p->d_kf + p->kf_o_cvals, p->cp_nk, vals + nc * es, fok,
+                                       c->stream));
+            if (p->cp_nh > 0)
+                HIP_TRY(c, launch_fold(p->dtype, p->d_cp + p->cp_o_hnodes, reinterpret_cast<const int64_t *>(p->d_cp + p->cp_o_hnoff),
+                                       reinterpret_cast<const int64_t *>(p->d_cp + p->cp_o_hcoff), p->d_cp + p->cp_o_hcvals, p->cp_nh,
+                                       vals + (nc + (size_t)p->cp_nk) * es, fok + p->cp_nk, c->stream));
+            HIP_TRY(c, launch_const_scatter(p->dtype, vals, reinterpret_cast<const uint64_t *>(p->d_cp + p->cp_o_addr),
+                                            reinterpret_cast<const uint32_t *>(p->d_cp + p->cp_o_src), p->cp_n_sites, c->stream));
+            HIP_TRY(c, launch_const_flags(p->dtype, vals, reinterpret_cast<const int64_t *>(p->d_cp + p->cp_o_coff),
+                                          reinterpret_cast<const uint8_t *>(p->d_cp + p->cp_o_checks), reinterpret_cast<const int32_t *>(p->d_cp + p->cp_o_tfoff),
+                                          reinterpret_cast<const uint32_t *>(p->d_cp + p->cp_o_tfold), fok, p->n_trees, (p->options & DE_OPT_EARLY_EXIT) != 0,
+                                          p->d_ok_eval, p->d_ok_grad, c->stream));
+            if (!c->nested) HIP_TRY(c, time_end(c));
+            p->consts_gen++; // (the cached certificate program belongs to the old constants)
+            if (gpatch) {
+                if (!tpatch) p->gt_valid = false;
+                if (!rpatch) p->rt_valid = false;
+            } else {
+                p->gcode_stale = true;
+            }
+            p->tab_ok_stale = false; // (d_ok_grad is current: the flag kernel wrote it)
+            p->consts_dev_ahead = true;
+            p->consts_dev_path = true;
+            return DE_OK;
+        }
+    }
+    // staged: one device-to-host copy, then the host function
+    std::vector<unsigned char> h(nc * dtype_bytes(p->io));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), d_consts, h.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return de_program_set_consts(p, h.data());
+}
+int de_program_set_consts_device(de_program_t *p, const void *d_consts) {
+    if (!p) return DE_ERR_INVALID_ARG;
+    int rc = DE_OK;
+    try { rc = set_consts_device_impl(p, d_consts); }
+    catch (const std::bad_alloc &) { return fail(p->ctx, DE_ERR_HIP, "out of host memory"); }
+    catch (const std::exception &e) { return fail(p->ctx, DE_ERR_HIP, "internal error: %s", e.what()); }
+    catch (...) { return fail(p->ctx, DE_ERR_HIP, "internal error (unknown exception)"); }
+    if (rc == DE_OK && p->consts_dev_ahead && getenv("DE_VERIFY") && *getenv("DE_VERIFY") == '1') return de_program_verify(p);
+    return rc;
+}
+int de_program_consts_device_path(const de_program_t *p) { return p ? (p->consts_dev_path ? 1 : 0) : -1; }
+
+static int get_consts_impl(de_program_t *p, void *out) {
+    de_ctx *c = p->ctx;
+    const size_t nc = p->consts.size();
+    if (nc == 0) return DE_OK;
+    if (!out) return fail(c, DE_ERR_INVALID_ARG, "out is null");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t ies = dtype_bytes(p->io);
+    const bool dev = is_device_ptr(out);
+    if (dev && p->consts_dev_ahead) { // (a device-path program: io is the compute type)
+        HIP_TRY(c, hipMemcpyAsync(out, p->d_cp_vals, nc * ies, hipMemcpyDeviceToDevice, c->stream));
+        return DE_OK;
+    }
+    const int rc = consts_materialise(p);
+    if (rc != DE_OK) return rc;
+    std::vector<unsigned char> h;
+    unsigned char *dst = static_cast<unsigned char *>(out);
+    if (dev) { h.resize(nc * ies); dst = h.data(); }
+    for (size_t k = 0; k < nc; k++) store_elem(p->io, dst, k, p->consts[k], p->consts_im.empty() ? 0.0 : p->consts_im[k]);
+    if (dev) {
+        HIP_TRY(c, hipMemcpyAsync(out, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the pageable host vector must outlive its copy)
+    }
+    return DE_OK;
+}
+int de_program_get_consts(de_program_t *p, void *out) {
+    if (!p) return DE_ERR_INVALID_ARG;
+    DE_NOTHROW(p->ctx, get_consts_impl(p, out));
+}
+
 int de_program_destroy(de_program_t *p) {
     if (!p) return DE_OK;
     (void)hipSetDevice(p->ctx->device);
@@ -1366,6 +1657,9 @@ int de_program_destroy(de_program_t *p) {
     if (p->aux) de_program_destroy(p->aux);
     prog_free(c, p->d_kf);
     p->d_kf = nullptr;
+    prog_free(c, p->d_cp); // (de_program_set_consts_device: site tables, the program's own constants)
+    prog_free(c, p->d_cp_vals);
+    p->d_cp = p->d_cp_vals = nullptr;
     dbg_lap(nullptr);
     prog_free(c, p->d_gcode);
     if (p->d_gcode_off) (void)hipFree(p->d_gcode_off);
@@ -1425,6 +1719,7 @@ int de_eval_plan(const de_program_t *p, int64_t N, int32_t *plan) {
 // gradient streams (gbcode, gtcode, rtcode) are made lazily by the gradient entry points and are not part of it.
 uint64_t de_program_stream_hash(const de_program_t *p) {
     if (!p) return 0;
+    if (consts_materialise(const_cast<de_program_t *>(p)) != DE_OK) return 0; // (host streams behind a device set: §3.5)
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void *data, size_t bytes) {
         const unsigned char *b = static_cast<const unsigned char *>(data);
@@ -1457,6 +1752,7 @@ uint64_t de_program_stream_hash(const de_program_t *p) {
 // record).  DE_VERIFY=1 runs it after every de_program_create / de_program_set_consts.
 int de_program_verify(const de_program_t *p) {
     if (!p) return DE_ERR_INVALID_ARG;
+    if (const int mrc = consts_materialise(const_cast<de_program_t *>(p))) return mrc; // (host streams behind a device set: §3.5)
     de_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device)); // the handler tables are cached per device: the program's addresses are its OWN device's
     const int64_t rows = eval_rows(p), spill_end = (int64_t)p->n_features + p->n_slots;
@@ -1617,6 +1913,7 @@ int de_program_verify(const de_program_t *p) {
 
 int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, int64_t cap, int which) {
     if (!p || tree < 0 || tree >= p->n_trees) return -DE_ERR_INVALID_ARG;
+    if (const int mrc = consts_materialise(const_cast<de_program_t *>(p))) return -mrc; // (host streams behind a device set: §3.5)
     if (which == 1) { // metadata: n_slots, host_ok_eval, host_ok_grad, uses_params
         if (cap < 4) return -DE_ERR_INVALID_ARG;
         words[0] = (uint32_t)p->n_slots;

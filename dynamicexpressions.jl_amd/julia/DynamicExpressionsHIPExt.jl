@@ -691,6 +691,51 @@ function set_population_constants!(pop::HIPPopulation{T}, constants::Vector{T}) 
     return pop
 end
 
+"""
+    set_population_constants_device!(pop, ptr::Ptr{Cvoid})
+
+The same from DEVICE memory (`de_program_set_consts_device`): `ptr` names `sum(pop.n_slots)` values of type `T` on the population's
+device — the LIBRARY's layout, one value per occurrence slot (a GraphNode caller gathers its shared constants on the device first).  The
+buffer is read in stream order on the context's stream; it may be reused as soon as that stream has passed the call.  Nothing is copied
+to the host where the library can patch its streams on the device (`population_constants_on_device_path(pop)` says so); any other
+program is staged through the host by the library itself.
+"""
+function set_population_constants_device!(pop::HIPPopulation{T}, ptr::Ptr{Cvoid}) where {T}
+    with_pop(pop) do hc, hp
+        check(pop.ctx, ccall((:de_program_set_consts_device, LIBDE), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), hp, ptr))
+    end
+    return pop
+end
+population_constants_on_device_path(pop::HIPPopulation) =
+    with_pop(pop) do hc, hp
+        ccall((:de_program_consts_device_path, LIBDE), Cint, (Ptr{Cvoid},), hp) == 1
+    end
+
+"""
+    get_population_constants!(out::Vector{T}, pop) -> out
+
+The current constants of `pop` in `set_population_constants!`'s layout (a GraphNode's shared constant once: its first occurrence),
+from whichever side holds them (`de_program_get_consts`).
+"""
+function get_population_constants!(out::Vector{T}, pop::HIPPopulation{T}) where {T}
+    length(out) == sum(pop.n_consts) || throw(ArgumentError("wrong number of constants"))
+    vals = any(o -> o !== nothing, pop.occ) ? Vector{T}(undef, sum(pop.n_slots)) : out
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve vals ccall((:de_program_get_consts, LIBDE), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), hp, vals))
+    end
+    if vals !== out                              # one value per occurrence slot -> one per unique constant
+        at, to = 0, 0
+        for t in 1:pop.n_trees
+            o = pop.occ[t]
+            for k in pop.n_slots[t]:-1:1             # (descending: the FIRST occurrence is written last)
+                out[at + (o === nothing ? k : o[k])] = vals[to + k]
+            end
+            at += pop.n_consts[t]; to += pop.n_slots[t]
+        end
+    end
+    return out
+end
+
 grad_mode(variable) = variable isa Val{true} || variable === true ? Cint(0) : variable isa Val{:both} ? Cint(2) : Cint(1)
 """Gradient widths of the trees in the LIBRARY's layout (one row per occurrence slot) and their packed offsets."""
 function grad_widths(hp::Ptr{Cvoid}, n_trees::Int, mode::Cint)

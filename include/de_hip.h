@@ -258,6 +258,26 @@ int de_program_create_cse(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes,
 /* Replace all constants (same counts, same order) without re-flattening: the
  * optimiser inner loop of get/set_scalar_constants (src/NodeUtils.jl:99-143). */
 int de_program_set_consts(de_program_t *prog, const void *consts);
+/* The same from a DEVICE buffer: d_consts holds the program's constants in its element type, in
+ * de_program_set_consts' order.  It is read in stream order on the context's stream — the first thing queued is a device-to-device
+ * copy into a buffer the program owns, so the caller may reuse d_consts once the stream has passed that point.  Afterwards every entry
+ * point behaves exactly as if de_program_set_consts had been called with the same values (outputs, flags, de_program_stream_hash,
+ * de_program_dump, a later de_program_update: the same bits).
+ *   - DE_F32 / DE_F64 programs whose streams are patched in place take the DEVICE PATH: the constants are scattered into every
+ *     device stream, the constant subtrees re-evaluated and the per-tree flags recomputed by kernels on the context's stream.  From the
+ *     second call on nothing is copied to or from the host and the stream is never synchronised; the host copies follow lazily, when
+ *     an entry point needs them (de_program_update, _verify, _dump, _stream_hash, the first gradient call that builds a stream ...).
+ *   - Every other program (DE_F16, complex, turbo, a constant subtree deeper than the fold kernel's stack, DE_NO_CONST_PATCH=1) is
+ *     STAGED: one device-to-host copy, then de_program_set_consts.  The call never fails for being unsupported;
+ *     de_program_consts_device_path tells which path ran.
+ *   - DE_ERR_INVALID_ARG: prog is null; d_consts is null while the program has constants; d_consts is a host pointer (the message
+ *     names de_program_set_consts).  A program without constants returns DE_OK and launches nothing. */
+int de_program_set_consts_device(de_program_t *prog, const void *d_consts);
+/* The current constants (de_program_set_consts' layout and element type) to a host or device buffer, from whichever side is current. */
+int de_program_get_consts(de_program_t *prog, void *out);
+/* 1: the last de_program_set_consts_device ran on the device path; 0: it was staged through the host (or the constants were last set
+ * by de_program_create / de_program_set_consts / de_program_update); -1: prog is null. */
+int de_program_consts_device_path(const de_program_t *prog);
 /* Replace trees tree_ids[0 .. n_update) of `prog` with the n_update trees given in de_program_create's layout
  * (nodes / node_offsets / consts / const_offsets describe the NEW trees only, in the order of tree_ids).
  * cse_nodes / cse_offsets may be NULL (no sharing in the new trees), else as de_program_create_cse.
