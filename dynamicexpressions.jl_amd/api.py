@@ -52,6 +52,7 @@ EXPORTS = [
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
+    "de_lower_tape_assured",
 ]
 
 
@@ -303,6 +304,9 @@ def library() -> C.CDLL:
         fn.restype = i64
     lib.de_lower_tape_complex.argtypes = lib.de_lower_tape.argtypes
     lib.de_lower_tape_stage_complex.argtypes = lib.de_lower_tape_stage.argtypes
+    if hasattr(lib, "de_lower_tape_assured"):  # (absent from a library built before the assured stream: DE_HIP_LIB in an A/B run)
+        lib.de_lower_tape_assured.restype = i64
+        lib.de_lower_tape_assured.argtypes = [vp, i64, vp, i64, i32, u32, C.c_double, vp, i64]
     lib.de_lower_tape_grad.restype = i64
     lib.de_lower_tape_grad.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, C.c_int, C.c_int, vp, i64, vp]
     lib.de_eval.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, i64, vp]
@@ -577,7 +581,8 @@ def lower_tape(tape, consts, n_features: int, n_params: int = 0, options: int = 
 
 def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 0, options: int = 7,
                      dtype=np.float32) -> np.ndarray:
-    """Host-only: the bound (stage 2) or fused (stage 3) instruction words of one tape, [n, 4] uint32."""
+    """Host-only: the bound (stage 2) or fused (stage 3) instruction words of one tape, [n, 4] uint32; stage 4 (float32): the fused
+    words with the handler ids of the assured stream."""
     lib = library()
     dtype = np.dtype(dtype)
     tape = np.ascontiguousarray(tape)
@@ -591,6 +596,22 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     w = np.zeros(max(int(n), 1), dtype=np.uint32)
     stage_fn(*args, w.ctypes.data, w.size)
     return w[:int(n)].reshape(-1, 4)
+
+
+def lower_tape_assured(tape, consts, n_features: int, xmax: float = 64.0, options: int = 7) -> np.ndarray:
+    """Host-only: the interval pass of the assured stream over one float32 tape (``de_lower_tape_assured``): [n fused instructions, 6]
+    float64 {lo, hi, amin, finite, assured handler id, elision bits} — the accumulator behind each instruction of the stage-3 words."""
+    lib = library()
+    tape = np.ascontiguousarray(tape)
+    consts = np.ascontiguousarray(consts, dtype=np.float32)
+    cp = consts.ctypes.data if consts.size else None
+    args = (tape.ctypes.data, len(tape), cp, consts.size, n_features, options, float(xmax))
+    n = lib.de_lower_tape_assured(*args, None, 0)
+    if n < 0:
+        raise ValueError(lib.de_status_string(int(-n)).decode())
+    w = np.zeros(max(int(n), 1), dtype=np.float64)
+    lib.de_lower_tape_assured(*args, w.ctypes.data, w.size)
+    return w[:int(n)].reshape(-1, 6)
 
 
 def lower_tape_grad(tape, consts, n_features: int, mode: int, form: int, n_params: int = 0, options: int = 7, dtype=np.float32):
@@ -868,9 +889,18 @@ class Population:
         return w[:int(got)].reshape(-1, 4)
 
     def meta(self, tree: int) -> dict:
-        w = np.zeros(5, dtype=np.uint32)
-        library().de_program_dump(self._h, tree, w.ctypes.data, 5, 1)
-        return dict(n_slots=int(w[0]), host_ok_eval=bool(w[1]), host_ok_grad=bool(w[2]), uses_params=bool(w[3]), waves=int(w[4]))
+        w = np.zeros(7, dtype=np.uint32)
+        library().de_program_dump(self._h, tree, w.ctypes.data, 7, 1)
+        return dict(n_slots=int(w[0]), host_ok_eval=bool(w[1]), host_ok_grad=bool(w[2]), uses_params=bool(w[3]), waves=int(w[4]),
+                    assured=bool(w[5]), assured_valid=bool(w[6]))
+
+    def dump_stage(self, tree: int, which: int) -> np.ndarray:
+        """``de_program_dump`` words of one tree: which = 2 bound, 3 fused, 4 fused with the assured stream's handler ids — test hook."""
+        lib = library()
+        n = lib.de_program_dump(self._h, tree, None, 0, which)
+        w = np.zeros(max(int(n), 1), dtype=np.uint32)
+        got = lib.de_program_dump(self._h, tree, w.ctypes.data, w.size, which)
+        return w[:int(got)].reshape(-1, 4)
 
     # -- evaluation -------------------------------------------------------------------
     def _param_args(self, params, classes, class_base, N, keep):

@@ -177,11 +177,38 @@ static int choose_waves(const de_program *p) {
     }
     return best;
 }
+static void make_assured(de_program *p, const uint64_t *table);
+// DE_ASSURED_XMAX as the pass and the kernel both take it: rounded to Float32 (the kernel compares in Float32), 64 when unset or out of range
+static double assured_xmax_env() {
+    const char *ax = getenv("DE_ASSURED_XMAX");
+    const double xm = ax ? (double)(float)atof(ax) : 64.0;
+    return (xm >= 0x1p-40 && xm <= 0x1p100) ? xm : 64.0;
+}
+// DE_ASSURED_PARTS: which tests the pass may elide (de_bind.h ASSURED_PART_*; default: the parts that measured faster, TUNING_LOG.md)
+static uint32_t assured_parts_env() {
+    const char *ap = getenv("DE_ASSURED_PARTS");
+    const int v = ap && *ap ? atoi(ap) : (int)ASSURED_PARTS_SHIPPED;
+    return (uint32_t)v & ASSURED_PARTS_ALL;
+}
 static int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr) {
     p->threaded = false;
     p->waves = 1;
     p->var_stride = 0;
     p->ccode_w.clear();
+    p->assured = p->assured_valid = false;
+    p->aids.clear();
+    if (p->assured_cfg == 0) { // DE_ASSURED / DE_ASSURED_XMAX: read once per program (an update keeps what its program was created with)
+        if (ru && ru->old && ru->old->assured_cfg != 0) {
+            p->assured_cfg = ru->old->assured_cfg;
+            p->assured_xmax = ru->old->assured_xmax;
+            p->assured_parts = ru->old->assured_parts;
+        } else {
+            const char *as = getenv("DE_ASSURED");
+            p->assured_parts = assured_parts_env();
+            p->assured_cfg = ((as && *as == '0') || p->assured_parts == 0) ? -1 : 1;
+            p->assured_xmax = assured_xmax_env();
+        }
+    }
     dbg_lap(nullptr);
     // the LDS-staged kernels need (n_features + n_slots) rows of 4112 B; wider X uses the direct variant
     p->direct = (size_t)eval_rows(p) * FLAT_ROW_BYTES > 150 * 1024; // (the flat-switch kernel's geometry: 256 threads x 16 bytes per row; it gathers the features of a wider X from global memory)
@@ -334,6 +361,12 @@ static int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr) {
         } else p->ccode_w.clear(); // (a fusion decided differently with shifted rows: never seen — rows are < 128 apart — but then one wave)
         dbg_lap("wave-group stream variants");
     } else if (W > 1 && fuse) p->waves = W; // no slot: one stream for every wave
+    // the assured stream (de_api_internal.h `assured`): Float32 values, no parameters, exact operators, one-wave workgroups
+    if (p->assured_cfg > 0 && p->waves == 1 && p->var_stride == 0 && p->io == DE_F32 && p->dtype == DE_F32 && !p->uses_params &&
+        !(p->options & DE_OPT_TURBO) && p->n_trees >= 8 && p->allow_fold) { // (not the auxiliary programs of constant subtrees, not a handful of trees: the second stream would cost more than it saves)
+        make_assured(p, table);
+        dbg_lap("assured stream");
+    }
     return DE_OK;
 }
 
@@ -411,6 +444,47 @@ static inline void patch_chained_imm(de_program *p, int32_t c, uint32_t lo, uint
         if (p->dtype == DE_F32) r.arg = lo;
         else { r.lo = lo; r.hi = hi; }
     }
+}
+// The assured variant's handler words of trees [tb, te): the interval pass over the fused code (de_bind.h assure_tree; the constants as
+// fbcode holds them NOW), then every instruction's handler — its twin's where a test is elided, its own otherwise — named where
+// make_chained names it: in the record in front (the first instruction's: in the header record, and in the last instruction record of an
+// end-fused predecessor).  A tree writes records no other tree writes: tree ranges may run on the host threads.
+static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb, int64_t te, bool touched_only = false) {
+    BoundInstr *cw = p->ccode_w.data();
+    std::vector<AssuredInstr> info;
+    auto name_next = [](BoundInstr &r, uint64_t handler) { r.lo = (uint32_t)handler; r.hi = (uint32_t)(handler >> 32); }; // (Float32 records)
+    auto ev_of = [&](int64_t t) -> int {
+        const int32_t i0 = p->tcode_off[(size_t)t], i1 = p->tcode_off[(size_t)t + 1];
+        return i1 - i0 >= 2 ? topx_endv_of(p->fbcode[(size_t)i1 - 1].bop) : -1;
+    };
+    for (int64_t t = tb; t < te; t++) {
+        const int32_t i0 = p->tcode_off[(size_t)t], i1 = p->tcode_off[(size_t)t + 1];
+        if (i1 <= i0) continue;
+        if (touched_only && p->const_off[(size_t)t + 1] == p->const_off[(size_t)t]) continue; // (a set of the constants touches the trees that have some)
+        info.resize((size_t)(i1 - i0));
+        assure_tree(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_xmax, info.data(), p->assured_parts);
+        const size_t h = (size_t)p->ccode_off[(size_t)t];
+        const int ev = ev_of(t);
+        for (int32_t i = i0; i < i1; i++) {
+            const uint32_t id = info[(size_t)(i - i0)].id;
+            p->aids[(size_t)i] = id;
+            if (i == i1 - 1 && ev >= 0) continue; // (the end-fused handler, as in the guarded stream)
+            const uint64_t handler = id == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[id];
+            if (i > i0) name_next(cw[h + (size_t)(i - i0) - 1], handler);
+            else {
+                name_next(cw[h - 1], handler);
+                if (t > 0 && ev_of(t - 1) >= 0) name_next(cw[h - 2], handler);
+            }
+        }
+    }
+}
+// ccode_w = the guarded stream with the assured handler words; var_stride as a wave group's variants lie (de_program_create sizes the arena by it)
+static void make_assured(de_program *p, const uint64_t *table) {
+    p->ccode_w = p->ccode;
+    p->aids.assign(p->fbcode.size(), 0u);
+    parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) { assured_link_trees(p, table, tb, te); });
+    p->var_stride = (int64_t)(p->bcode.size() + (size_t)p->n_trees + 2);
+    p->assured = p->assured_valid = true;
 }
 // the stream variants of waves 1 .. (wave groups) to their places behind variant 0
 static hipError_t upload_wave_variants(de_program *p) {
@@ -1142,7 +1216,7 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         // compaction control ints | initial flags], one allocation from the context's pool; a small program (the one-tree call of
         // de_eval_tree_array) goes up in ONE copy from a zero-filled host image, a large one in one memset + three copies.
         // (wave groups: `waves` variants of the stream var_stride = cbytes / 16 records apart, and as much room again for their compacted forms)
-        const size_t nvar = p->threaded && p->var_stride ? (size_t)p->waves : 1;
+        const size_t nvar = p->threaded && p->var_stride ? (p->assured ? 2 : (size_t)p->waves) : 1; // (the assured stream: one more variant of a one-wave program)
         if (nvar > 1 && (size_t)p->var_stride * sizeof(BoundInstr) != cbytes) return fail(ctx, DE_ERR_HIP, "wave-group stream variants: stride and arena disagree");
         const size_t abytes = p->threaded ? 2 * nvar * cbytes : cbytes;
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -1319,6 +1393,13 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
             if (!rpatch) p->rt_valid = false;
         } else {
             p->gcode_stale = true;
+        }
+        if (p->assured) { // new constants, new intervals: the assured handler words of every tree (its immediates were patched above)
+            uint64_t table[TOPX_TABLE];
+            const hipError_t hs = eval_handler_table(p->dtype, (p->options & DE_OPT_TURBO) != 0, table);
+            if (hs != hipSuccess) return fail(ctx, DE_ERR_HIP, "handler table: %s", hipGetErrorString(hs));
+            parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) { assured_link_trees(p, table, tb, te, true); });
+            p->assured_valid = true;
         }
         const auto t4 = now();
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the program may be in use by work already queued
@@ -1588,6 +1669,7 @@ static int set_consts_device_impl(de_program_t *p, const void *d_consts) {
             p->tab_ok_stale = false; // (d_ok_grad is current: the flag kernel wrote it)
             p->consts_dev_ahead = true;
             p->consts_dev_path = true;
+            p->assured_valid = false; // (the intervals belong to the old constants: the guarded stream until the host sees the new ones)
             return DE_OK;
         }
     }
@@ -1907,12 +1989,43 @@ int de_program_verify(const de_program_t *p) {
                 }
             }
         }
+        // the assured stream: the guarded stream in everything but handler words, and every handler word the one the interval pass over
+        // the present fused code (its constants) picks — the instruction's own handler or its untested twin's
+        if (p->assured) {
+            if (p->waves != 1 || !f32 || p->ccode_w.size() != p->ccode.size() || p->aids.size() != p->fbcode.size() || (size_t)p->var_stride < p->ccode.size())
+                return bad("assured stream layout", -1, p->waves, p->ccode_w.size());
+            const BoundInstr *cw = p->ccode_w.data();
+            std::vector<AssuredInstr> info;
+            auto named = [](const BoundInstr &q) { return ((uint64_t)q.hi << 32) | q.lo; };
+            for (size_t r = 0; r < p->ccode.size(); r++)
+                if (cw[r].bop != p->ccode[r].bop || cw[r].arg != p->ccode[r].arg) return bad("assured stream: operand words differ", -1, (int64_t)r, cw[r].bop);
+            for (int64_t t = 0; t < p->n_trees; t++) {
+                const int32_t i0 = p->tcode_off[(size_t)t], i1 = p->tcode_off[(size_t)t + 1], h = p->ccode_off[(size_t)t];
+                if (i1 <= i0) continue;
+                info.resize((size_t)(i1 - i0));
+                assure_tree(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_xmax, info.data(), p->assured_parts);
+                const int ev = i1 - i0 >= 2 ? topx_endv_of(p->fbcode[(size_t)i1 - 1].bop) : -1;
+                for (int32_t i = i0; i < i1; i++) {
+                    const uint32_t id = info[(size_t)(i - i0)].id;
+                    if (p->assured_valid && id != p->aids[(size_t)i]) return bad("assured stream: stale twin id", t, i - i0, p->aids[(size_t)i]);
+                    const uint32_t have = p->aids[(size_t)i];
+                    if (have >= TOPX_COUNT) return bad("assured stream: handler id", t, i - i0, have);
+                    const uint64_t want = (i == i1 - 1 && ev >= 0) ? p->endv_handler[ev]
+                                          : (have == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[have]);
+                    if (named(cw[(size_t)(h + (i - i0) - 1)]) != want) return bad("assured stream: handler word", t, i - i0, named(cw[(size_t)(h + (i - i0) - 1)]));
+                }
+                // the end record is named as in the guarded stream (by the last instruction, or stepped over by an end-fused one)
+                if (ev < 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != p->end_handler) return bad("assured stream: tree does not end in the end record", t, i1 - i0, 0);
+                if (ev >= 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != named(cw[(size_t)(h + (i1 - i0))])) return bad("assured stream: end-fused instruction and end record disagree", t, i1 - i0, 0);
+            }
+        }
     }
     return DE_OK;
 }
 
 int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, int64_t cap, int which) {
     if (!p || tree < 0 || tree >= p->n_trees) return -DE_ERR_INVALID_ARG;
+    const bool assured_valid = p->assured && p->assured_valid; // (as the launches see it NOW: materialising the constants below re-runs the pass)
     if (const int mrc = consts_materialise(const_cast<de_program_t *>(p))) return -mrc; // (host streams behind a device set: §3.5)
     if (which == 1) { // metadata: n_slots, host_ok_eval, host_ok_grad, uses_params
         if (cap < 4) return -DE_ERR_INVALID_ARG;
@@ -1922,7 +2035,19 @@ int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, in
         words[3] = p->uses_params;
         if (cap < 5) return 4;
         words[4] = (uint32_t)(p->threaded ? p->waves : 1); // waves per workgroup of the eval kernel (wave groups: 2 / 4 / 8)
-        return 5;
+        if (cap < 7) return 5;
+        words[5] = p->threaded && p->assured ? 1u : 0u; // the program has an assured stream ...
+        words[6] = p->threaded && assured_valid ? 1u : 0u; // ... and the launches use it (0 behind de_program_set_consts_device)
+        return 7;
+    }
+    if (which == 4) { // the fused form with the handler ids of the ASSURED stream; empty when the program has none
+        if (!p->threaded || !p->assured) return 0;
+        const int32_t b0 = p->tcode_off[(size_t)tree], b1 = p->tcode_off[(size_t)tree + 1];
+        const int64_t nb = (int64_t)(b1 - b0) * 4;
+        if (!words || cap < nb) return nb;
+        std::memcpy(words, p->fbcode.data() + b0, (size_t)nb * 4);
+        for (int32_t i = b0; i < b1; i++) words[(size_t)(i - b0) * 4] = p->aids[(size_t)i];
+        return nb;
     }
     if (which == 2) { // bound instructions (de_bind.h)
         const int32_t b0 = p->bcode_off[(size_t)tree], b1 = p->bcode_off[(size_t)tree + 1];
@@ -2027,9 +2152,36 @@ static int64_t lower_tape_impl(int dtype, const de_tape_node_t *nodes, int64_t n
     }
 }
 
+// Host-only: the interval pass of the assured stream over ONE Float32 tape (de_bind.h assure_tree) — per fused instruction six doubles
+// {lo, hi, amin, proven finite (0 / 1), assured handler id, elision bits (ASSURED_OUT | ASSURED_ROW)}: the accumulator behind it.
+int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
+                              uint32_t options, double xmax, double *out, int64_t cap) {
+    if (!(xmax >= 0x1p-40 && xmax <= 0x1p100)) return -DE_ERR_INVALID_ARG;
+    int64_t nw = lower_tape_stage_impl(DE_F32, nodes, n_nodes, consts, n_consts, n_features, 0, options, 3, nullptr, 0);
+    if (nw < 0) return nw;
+    try {
+        std::vector<BoundInstr> f((size_t)nw / 4);
+        nw = lower_tape_stage_impl(DE_F32, nodes, n_nodes, consts, n_consts, n_features, 0, options, 3, reinterpret_cast<uint32_t *>(f.data()), nw);
+        if (nw < 0) return nw;
+        const int64_t n = (int64_t)f.size() * 6;
+        if (!out || cap < n) return n;
+        std::vector<AssuredInstr> info(f.size());
+        assure_tree(f.data(), f.size(), n_features, xmax, info.data());
+        for (size_t i = 0; i < f.size(); i++) {
+            double *o = out + 6 * i;
+            o[0] = info[i].acc.lo; o[1] = info[i].acc.hi; o[2] = info[i].acc.amin; o[3] = info[i].acc.fin ? 1.0 : 0.0;
+            o[4] = (double)info[i].id; o[5] = (double)info[i].bits;
+        }
+        return n;
+    } catch (...) {
+        return -DE_ERR_HIP;
+    }
+}
+
 static int64_t lower_tape_stage_impl(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
                                      int32_t n_features, int32_t n_params, uint32_t options, int stage, uint32_t *words, int64_t cap) {
-    if (stage != 2 && stage != 3) return -DE_ERR_INVALID_ARG;
+    if (stage != 2 && stage != 3 && stage != 4) return -DE_ERR_INVALID_ARG;
+    if (stage == 4 && dtype != DE_F32) return -DE_ERR_INVALID_ARG; // (the assured form exists for Float32 programs only)
     std::vector<uint32_t> g;
     int64_t nw = lower_tape_impl(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, nullptr, 0, nullptr);
     if (nw < 0) return nw;
@@ -2039,8 +2191,13 @@ static int64_t lower_tape_stage_impl(int dtype, const de_tape_node_t *nodes, int
         if (nw < 0) return nw;
         std::vector<BoundInstr> b, f;
         bind_tree(reinterpret_cast<const Instr *>(g.data()), (size_t)nw / 4, (options & DE_OPT_EARLY_EXIT) != 0, n_features, &b);
-        if (stage == 3 && dtype != DE_F16 && !is_complex_io(dtype)) fuse_tree(b.data(), b.size(), &f); // (a DE_F16 program never runs the threaded kernel: no fused form)
-        const std::vector<BoundInstr> &o = stage == 3 ? f : b;
+        if (stage >= 3 && dtype != DE_F16 && !is_complex_io(dtype)) fuse_tree(b.data(), b.size(), &f); // (a DE_F16 program never runs the threaded kernel: no fused form)
+        if (stage == 4) { // the fused words with the assured stream's handler ids (de_bind.h assure_tree; DE_ASSURED_XMAX as a program reads it)
+            std::vector<AssuredInstr> info(f.size());
+            assure_tree(f.data(), f.size(), n_features, assured_xmax_env(), info.data(), assured_parts_env());
+            for (size_t i = 0; i < f.size(); i++) f[i].bop = info[i].id;
+        }
+        const std::vector<BoundInstr> &o = stage >= 3 ? f : b;
         const int64_t n = (int64_t)o.size() * 4;
         if (!words || cap < n) return n;
         std::memcpy(words, o.data(), (size_t)n * 4);

@@ -1,6 +1,11 @@
 // de_bind.cpp — see de_bind.h.
 #include "de_bind.h"
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+
 #include "../../include/de_opcodes.h"
 
 namespace de {
@@ -220,6 +225,176 @@ void fuse_tree(const BoundInstr *b, size_t n, std::vector<BoundInstr> *out, cons
         }
         out->push_back(b[i]); // unfused: same id as the bound form
         i++;
+    }
+}
+
+// ---- interval pass over a fused tree (de_bind.h assure_tree) ---------------------------------------------------------------------
+namespace {
+const double A_INF = std::numeric_limits<double>::infinity();
+AssuredVal a_unbounded() { return AssuredVal{-A_INF, A_INF, 0.0, false}; }
+// [lo, hi] and |v| >= amin as computed in double from sound operand bounds -> sound bounds of the ROUNDED Float32 result
+AssuredVal a_make(double lo, double hi, double amin) {
+    // (T covers the rounding of a SUBNORMAL result only because the kernels keep denormals — gradual underflow, the eval modules are built
+    // without flush-to-zero; a flushed result would be 0 where amin claims 2^-14x.  With BIG = 2^120 no reciprocal of a value the pass
+    // still calls bounded away from 0 can overflow.)
+    const double W = 0x1p-20, T = 0x1p-140, BIG = 0x1p120;
+    lo -= std::fabs(lo) * W + T;
+    hi += std::fabs(hi) * W + T;
+    if (!(lo >= -BIG && hi <= BIG && lo <= hi)) return a_unbounded(); // (written so that NaN fails)
+    amin = amin * (1.0 - W) - T;
+    if (!(amin > 0.0)) amin = 0.0;
+    if (lo > 0.0) amin = std::max(amin, lo);
+    if (hi < 0.0) amin = std::max(amin, -hi);
+    return AssuredVal{lo, hi, amin, true};
+}
+AssuredVal a_const(uint32_t bits) {
+    float c;
+    std::memcpy(&c, &bits, 4);
+    if (!std::isfinite(c)) return a_unbounded();
+    return AssuredVal{(double)c, (double)c, std::fabs((double)c), true};
+}
+double a_absmax(const AssuredVal &a) { return std::max(std::fabs(a.lo), std::fabs(a.hi)); }
+AssuredVal a_div(const AssuredVal &n, const AssuredVal &d) {
+    if (!n.fin || !d.fin || !(d.amin > 0.0)) return a_unbounded();
+    const double amin = n.amin / a_absmax(d);
+    if (d.lo > 0.0 || d.hi < 0.0) { // a denominator of one sign: |d| in [dl, dh]
+        const double dl = std::max(d.amin, std::min(std::fabs(d.lo), std::fabs(d.hi))), dh = a_absmax(d), s = d.lo > 0.0 ? 1.0 : -1.0;
+        const double q[4] = {s * n.lo / dl, s * n.lo / dh, s * n.hi / dl, s * n.hi / dh};
+        return a_make(std::min(std::min(q[0], q[1]), std::min(q[2], q[3])), std::max(std::max(q[0], q[1]), std::max(q[2], q[3])), amin);
+    }
+    const double m = a_absmax(n) / d.amin;
+    return a_make(-m, m, amin);
+}
+// K: 0 ADD 1 SUB 2 RSUB 3 MUL 4 DIV 5 RDIV — x op b (R*: b op x), as de_kernels.hip bin_apply
+AssuredVal a_bin(int k, const AssuredVal &x, const AssuredVal &b) {
+    if (!x.fin || !b.fin) return a_unbounded();
+    switch (k) {
+    case 0: return a_make(x.lo + b.lo, x.hi + b.hi, 0.0);
+    case 1: return a_make(x.lo - b.hi, x.hi - b.lo, 0.0);
+    case 2: return a_make(b.lo - x.hi, b.hi - x.lo, 0.0);
+    case 3: {
+        const double q[4] = {x.lo * b.lo, x.lo * b.hi, x.hi * b.lo, x.hi * b.hi};
+        return a_make(std::min(std::min(q[0], q[1]), std::min(q[2], q[3])), std::max(std::max(q[0], q[1]), std::max(q[2], q[3])), x.amin * b.amin);
+    }
+    case 4: return a_div(x, b);
+    case 5: return a_div(b, x);
+    default: return a_unbounded();
+    }
+}
+// K: 0 COS 1 EXP (2 SIN and everything else: no rule)
+AssuredVal a_un(int k, const AssuredVal &x) {
+    if (!x.fin) return a_unbounded();
+    if (k == 0) return a_make(-1.0, 1.0, 0.0);
+    if (k == 1) return a_make(std::exp(x.lo), std::exp(x.hi), 0.0);
+    return a_unbounded();
+}
+} // namespace
+
+void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts) {
+    static thread_local std::vector<AssuredVal> slots; // rows >= n_features an instruction of THIS tree has written
+    slots.clear();
+    const AssuredVal feature{-xmax, xmax, 0x1p-40, true};
+    auto row_val = [&](uint32_t row) -> AssuredVal {
+        if (row < (uint32_t)n_features) return feature;
+        const size_t s = row - (uint32_t)n_features;
+        return s < slots.size() ? slots[s] : a_unbounded();
+    };
+    auto push = [&](uint32_t row, const AssuredVal &v) {
+        if (row < (uint32_t)n_features) return; // (never: de_program_verify)
+        const size_t s = row - (uint32_t)n_features;
+        if (s >= slots.size()) slots.resize(s + 1, a_unbounded());
+        slots[s] = v;
+    };
+    AssuredVal acc = a_unbounded();
+    for (size_t i = 0; i < n; i++) {
+        const BoundInstr &b = f[i];
+        const uint32_t id = b.bop, row = b.arg & 0xFFFFFFu;
+        const uint32_t prow = (uint32_t)((int32_t)row + (int32_t)(int8_t)(b.arg >> 24)); // (superinstructions with a spill)
+        uint32_t twin = id, bits = 0;
+        AssuredVal un_arg = a_unbounded(), div_acc = a_unbounded(), div_row = a_unbounded(); // operands of a cos / exp, of a division
+        const bool validity = (parts & ASSURED_PART_VALIDITY) != 0;
+        if (id == BOP_LOAD_ROW) acc = row_val(row);
+        else if (id == BOP_LOAD_CONST) acc = a_const(b.lo);
+        else if (id == BOP_PUSH) push(row, acc);
+        else if (id == BOP_CHECK_ROW || id == BOP_CHECK_ACC) ; // (a test on its own keeps its record: no twin)
+        else if (id >= BOP_BIN_BASE && id < BOP_BIN_END) {
+            const uint32_t v = id - BOP_BIN_BASE;
+            div_acc = acc;
+            div_row = (v & 2) ? a_const(b.lo) : row_val(row);
+            acc = a_bin((int)(v >> 2), acc, div_row);
+            if (validity && (v & 1) && acc.fin) { twin = id - 1; bits |= ASSURED_OUT; }
+        } else if (id >= BOP_UN_BASE && id < BOP_UN_END) {
+            const uint32_t v = id - BOP_UN_BASE;
+            un_arg = (v & 2) ? row_val(row) : acc;
+            acc = a_un((int)(v >> 2), un_arg);
+            if (validity && (v & 1) && acc.fin) { twin = id - 1; bits |= ASSURED_OUT; }
+        } else if (id >= TOP_LOADROW_BASE && id < TOP_LOADCONST_PUSH) {
+            const uint32_t v = id - TOP_LOADROW_BASE;
+            if (v & 2) push(prow, acc);
+            acc = row_val(row);
+            if (validity && (v & 1) && acc.fin) { twin = top_loadrow((v & 2) != 0, false); bits |= ASSURED_ROW; }
+        } else if (id == TOP_LOADCONST_PUSH) {
+            push(b.arg & 0xFFFFFFu, acc);
+            acc = a_const(b.lo);
+        } else if (id >= TOP_UNROW_BASE && id < TOP_BINROWC_BASE) {
+            const uint32_t v = id - TOP_UNROW_BASE;
+            bool chk = (v & 1) != 0, outc = ((v >> 2) & 1) != 0;
+            const bool psh = ((v >> 1) & 1) != 0;
+            if (psh) push(prow, acc);
+            const AssuredVal x = row_val(row);
+            un_arg = x;
+            acc = a_un((int)(v >> 3), x);
+            if (validity && chk && x.fin) { chk = false; bits |= ASSURED_ROW; }
+            if (validity && outc && acc.fin) { outc = false; bits |= ASSURED_OUT; }
+            twin = top_unrow((int)(v >> 3), outc, psh, chk);
+        } else if (id >= TOP_BINROWC_BASE && id < TOP_BIN2_BASE) {
+            const uint32_t v = id - TOP_BINROWC_BASE;
+            const int k = (int)(v >> 1);
+            bool outc = (v & 1) != 0;
+            const AssuredVal x = row_val(row);
+            div_acc = acc;
+            div_row = x;
+            acc = a_bin(k, acc, x);
+            if (validity && outc && acc.fin) { outc = false; bits |= ASSURED_OUT; }
+            if (validity && x.fin) { twin = BOP_BIN_BASE + 4 * (uint32_t)k + (outc ? 1u : 0u); bits |= ASSURED_ROW; } // the plain row form: same operand word
+            else twin = top_binrowc(k, outc);
+        } else if (id >= TOP_BIN2_BASE && id < TOP_COUNT) {
+            const uint32_t v = id - TOP_BIN2_BASE;
+            const bool psh = (v & 1) != 0, cst = ((v >> 2) & 1) != 0;
+            bool outc = ((v >> 1) & 1) != 0;
+            if (psh) push(prow, acc);
+            const AssuredVal x = row_val(row);
+            acc = a_bin((int)(v >> 3), x, cst ? a_const(b.lo) : row_val((uint32_t)((int32_t)row + (int32_t)b.lo)));
+            if (validity && outc && acc.fin) { outc = false; bits |= ASSURED_OUT; }
+            twin = top_bin2((int)(v >> 3), cst, outc, psh);
+        } else if (id == BOP_GEN_CONST && ((b.arg >> 24) == (uint32_t)DE_U_COS || (b.arg >> 24) == (uint32_t)DE_U_EXP)) {
+            acc = a_un((b.arg >> 24) == (uint32_t)DE_U_COS ? 0 : 1, a_const(b.lo)); // cos / exp of a constant (an unfolded program)
+        } else acc = a_unbounded(); // generic operators, parameters, ternaries, Inf injection: no rule
+        // the range guards, on the id the validity part left: cos / exp without the pre-test, a division that tests only the
+        // operand halves the intervals do not cover (forms without such a handler keep their id)
+        auto pre_idle = [](int k, const AssuredVal &x) { return x.fin && a_absmax(x) <= (k == 0 ? 9.0e4 : 125.0 / 1.4426950408889634); };
+        auto half_idle = [](const AssuredVal &x) { return x.fin && x.amin >= 0x1p-39 && a_absmax(x) <= 0x1p39; };
+        if ((parts & ASSURED_PART_PRETEST) && twin >= BOP_UN_BASE && twin < BOP_UN_BASE + 8 && pre_idle((int)((twin - BOP_UN_BASE) >> 2), un_arg)) {
+            twin = topa_un((int)((twin - BOP_UN_BASE) >> 2), (twin - BOP_UN_BASE) & 3u);
+            bits |= ASSURED_PRE;
+        } else if ((parts & ASSURED_PART_PRETEST) && twin >= TOP_UNROW_BASE && twin < TOP_UNROW_BASE + 16 && pre_idle((int)((twin - TOP_UNROW_BASE) >> 3), un_arg)) {
+            twin = TOPA_UNROW_BASE + (twin - TOP_UNROW_BASE);
+            bits |= ASSURED_PRE;
+        } else if ((parts & ASSURED_PART_DIVISION) && twin >= BOP_BIN_BASE + 16 && twin < BOP_BIN_END) {
+            const uint32_t v = twin - BOP_BIN_BASE, var = v & 3u;
+            const bool ia = half_idle(div_acc), ir = (var & 2) ? false : half_idle(div_row); // (a constant operand keeps its scalar test)
+            if (ia || ir) {
+                twin = topa_div((int)(v >> 2), var, (var & 2) ? 0u : ((ia ? 0u : 1u) | (ir ? 0u : 2u)));
+                bits |= (ia ? ASSURED_DIV_ACC : 0u) | (ir ? ASSURED_DIV_ROW : 0u);
+            }
+        }
+        out[i].acc = acc;
+        out[i].id = twin;
+        out[i].bits = bits;
+    }
+    if (n >= 2 && topx_endv_of(f[n - 1].bop) >= 0) { // the end-fused last instruction: the twin has no such form
+        out[n - 1].id = f[n - 1].bop;
+        out[n - 1].bits = 0;
     }
 }
 

@@ -173,7 +173,17 @@ static_assert(gop_count(8) <= GOP_MAX, "GOP_MAX too small");
 // threaded code is made (de_api_program.cpp make_threaded) instead of the generic handler; ids follow TOP_COUNT.
 constexpr uint32_t TOPX_UN_BASE = TOP_COUNT;                 // + (k - 3) * 2 + (src == ACC)
 constexpr uint32_t TOPX_BIN_BASE = TOPX_UN_BASE + 2 * (GUN_K - 3); // max / min: + (k - 6) * 2 + (src == CONST)
-constexpr uint32_t TOPX_COUNT = TOPX_BIN_BASE + 4;
+// ... and the ASSURED fast-path-only forms (Float32, exact mode; de_kernels.hip NT / M template arguments): the cos / exp handlers without
+// the wave-uniform range pre-test, the exact divisions with the range test of only the operand halves that still need it.  Named by the
+// assured stream alone (assure_tree below), where the interval pass proves the test idle; for every other element type and for turbo
+// programs the entries hold the guarded handler of the same instruction.
+constexpr uint32_t TOPA_UN_BASE = TOPX_BIN_BASE + 4;        // + k * 4 + var                      k < 2 (cos, exp), var as BOP_UN_BASE   (8)
+constexpr uint32_t TOPA_UNROW_BASE = TOPA_UN_BASE + 8;      // + ((k*2 + out)*2 + push)*2 + chk   k < 2, as TOP_UNROW_BASE               (16)
+constexpr uint32_t TOPA_DIV_BASE = TOPA_UNROW_BASE + 16;    // + ((k - 4) * 4 + var) * 3 + m      k = DIV, RDIV; var as BOP_BIN_BASE;
+                                                            //   m = the halves still tested: 0 none, 1 the accumulator, 2 the row  (24)
+constexpr uint32_t TOPX_COUNT = TOPA_DIV_BASE + 24;
+constexpr uint32_t topa_un(int k, uint32_t var) { return TOPA_UN_BASE + (uint32_t)k * 4 + var; }
+constexpr uint32_t topa_div(int k, uint32_t var, uint32_t m) { return TOPA_DIV_BASE + ((uint32_t)(k - 4) * 4 + var) * 3 + m; }
 // handler table of the threaded eval kernel: the ids above + the end-of-tree handler every chain finishes in
 constexpr uint32_t TOPX_END = TOPX_COUNT;
 // ... and "last instruction of a tree + its end" variants of the handlers most trees finish in (a validity-tested hot binary or
@@ -236,6 +246,36 @@ struct FuseRows { uint32_t slot_lo, slot_hi; int32_t shift, headroom; };
 void fuse_tree(const BoundInstr *b, size_t n, std::vector<BoundInstr> *out, const FuseRows *rows = nullptr);
 // True when the fused instruction's operand is an inline constant (arg carries no operand row).
 bool top_is_const_source(uint32_t top);
+
+// ---- the ASSURED form of a fused tree ------------------------------------------------------------------------
+// An interval pass over the fused instructions of one Float32 tree under ASSUMPTION A: every feature value of the sample tile is
+// finite with 2^-40 <= |x| <= xmax (the eval kernel tests that once per workgroup while it stages the tile).  Constants enter with
+// their values; + - * /, cos (-> [-1, 1]) and exp have rules; every other operator, a parameter or ternary operand and a slot row no
+// instruction of the tree has written give the unbounded value.  Bounds are computed in double and widened outward by a relative
+// 2^-20 and an absolute 2^-140 (Float32 rounding, subnormal results); a value counts as finite only while |v| <= 2^120, a quotient
+// only when |denominator| has a positive lower bound.  A validity test of a value that is proven finite cannot fire under A: the
+// instruction is given the id of its twin WITHOUT that test — the same operator on the same operand words, so the assured stream is
+// the fused stream in everything but handler ids.  (An end-fused last instruction keeps its id: the twin has no end-fused form.)
+struct AssuredVal {
+    double lo, hi; // lo <= v <= hi
+    double amin;   // |v| >= amin (0: nothing known)
+    bool fin;      // proven finite under A; false: lo / hi / amin mean nothing
+};
+enum : uint32_t { ASSURED_OUT = 1u,      // the validity test of the instruction's result is elided
+                  ASSURED_ROW = 2u,      // the validity test of its row operand (a leaf check) is elided
+                  ASSURED_PRE = 4u,      // cos / exp: the range pre-test is elided (|arg| <= 9e4 / |arg log2 e| <= 125 proven)
+                  ASSURED_DIV_ACC = 8u,  // division: the range test of the accumulator operand is elided (|v| in [2^-39, 2^39] proven)
+                  ASSURED_DIV_ROW = 16u }; // ... of the row operand
+// the parts of the pass (DE_ASSURED_PARTS, a bit mask; measured one by one, TUNING_LOG.md: the validity tests and the pre-tests pay and are
+// the default, the division halves measured inside the run-to-run spread and are opt-in)
+constexpr uint32_t ASSURED_PARTS_SHIPPED = 3u;
+enum : uint32_t { ASSURED_PART_VALIDITY = 1u, ASSURED_PART_PRETEST = 2u, ASSURED_PART_DIVISION = 4u, ASSURED_PARTS_ALL = 7u };
+struct AssuredInstr {
+    AssuredVal acc; // the accumulator behind the instruction
+    uint32_t id;    // the handler id of the assured stream (== the fused id: nothing elided)
+    uint32_t bits;  // ASSURED_*
+};
+void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts = ASSURED_PARTS_ALL);
 
 // Append the bound form of `code` (one tree) to `out`.
 // param_row_base >= 0: parameter operands are LDS rows param_row_base + p (the eval kernels stage the tile's parameter values like

@@ -101,7 +101,15 @@ template <typename T> struct KArgs {
     // fit statistics (de_eval_fit_stats, loss_kind == FIT_STATS_KIND): {W, mean_y, M2_y} as the pre-pass over y / w left them on the
     // device (de_fit_ymean_kernel) — the kernel centres its targets on T(mean_y); partial is then [n_tiles][n_trees] x {m, S1, B, Cc}
     const double *fit_ystats;
+    // THE ASSURED STREAM (one-wave Float32 workgroups): assured != 0 = var_stride records behind `code` lies the variant of
+    // the stream without the validity tests that cannot fire on a tile of ordinary feature values.  The workgroup tests its tile while it
+    // stages it — every value finite with 2^-40 <= |x| <= assured_xmax, one ballot — and runs that variant when the tile passes.
+    int32_t assured;
+    float assured_xmax;
 };
+// the per-value test of the tile fact (NaN fails both compares)
+__device__ __forceinline__ bool assured_value_ok(float v, float xmax) { return (__builtin_fabsf(v) <= xmax) & (__builtin_fabsf(v) >= 0x1p-40f); }
+__device__ __forceinline__ bool assured_value_ok(double, float) { return false; } // (Float64 programs have no assured stream)
 
 
 // The same map with the CHUNK slower than a group of `grp` sample tiles (per XCD): the workgroups resident on a CU at one time then walk
@@ -930,7 +938,9 @@ template <int K, bool TB, int G> __device__ __forceinline__ void un_finish_plane
 // (the planes of a fast handler: every plane's range test first — one wave-uniform decision for the whole dispatch: a wavefront
 // that fails it on ANY plane tail-calls the full handler, which redoes all planes —, then every plane's arithmetic)
 // cos / exp / sin on the accumulator or a row (VAR as in b_un)
-template <int K, int VAR, bool TB> __device__ __noinline__ HState<float> h_un_fast(HFAST_ARGS) {
+// NT (the assured stream, de_bind.h TOPA_*): no range pre-test — the interval pass proved it idle for every tile that runs this stream;
+// the arithmetic, the near-extremum branch of cos included, is the same
+template <int K, int VAR, bool TB, bool NT = false> __device__ __noinline__ HState<float> h_un_fast(HFAST_ARGS) {
     typedef float T;
     constexpr int G = TG<T>::G;
     const U32x4 w = *code;
@@ -939,7 +949,7 @@ template <int K, int VAR, bool TB> __device__ __noinline__ HState<float> h_un_fa
     UnPre p[G];
     bool slow = false;
     FOR_PLANES slow |= un_pretest<K, TB>(x[g], p[g]);
-    if (__builtin_expect(__ballot(slow) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_un<T, K, VAR, TB>>(HFAST_PASS);
+    if constexpr (!NT) if (__builtin_expect(__ballot(slow) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_un<T, K, VAR, TB>>(HFAST_PASS);
 #if DE_TG == 1
     FOR_PLANES {
         st.acc[g] = un_finish<K, TB>(x[g], p[g]);
@@ -972,7 +982,7 @@ template <int K, bool TB> __device__ __noinline__ HState<float> h_un_end_fast(HF
     HFAST_END_TAIL()
 }
 // ... fused with a spill of the accumulator and / or the validity test of its row operand (b_unrow_f)
-template <int K, bool OUT, bool PUSH, bool CHK, bool TB> __device__ __noinline__ HState<float> h_unrow_fast(HFAST_ARGS) {
+template <int K, bool OUT, bool PUSH, bool CHK, bool TB, bool NT = false> __device__ __noinline__ HState<float> h_unrow_fast(HFAST_ARGS) {
     typedef float T;
     constexpr int G = TG<T>::G;
     const U32x4 w = *code;
@@ -985,7 +995,7 @@ template <int K, bool OUT, bool PUSH, bool CHK, bool TB> __device__ __noinline__
     UnPre p[G];
     bool slow = false;
     FOR_PLANES slow |= un_pretest<K, TB>(x[g], p[g]);
-    if (__builtin_expect(__ballot(slow) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_unrow_f<T, K, OUT, PUSH, CHK, TB>>(HFAST_PASS);
+    if constexpr (!NT) if (__builtin_expect(__ballot(slow) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_unrow_f<T, K, OUT, PUSH, CHK, TB>>(HFAST_PASS);
 #if DE_TG == 1
     FOR_PLANES {
         if constexpr (CHK) hpoison<T>(st.poison, x[g]);
@@ -1001,16 +1011,20 @@ template <int K, bool OUT, bool PUSH, bool CHK, bool TB> __device__ __noinline__
 }
 // The exact Float32 divisions (K = 4: acc / operand, 5: operand / acc; VAR as in b_bin) likewise: range test, then either the
 // tail call into the full handler (generic IEEE expansion) or the packed fast path computed in place.
-template <int K, int VAR> __device__ __noinline__ HState<float> h_div_fast(HFAST_ARGS) {
+// M (the assured stream, de_bind.h TOPA_DIV_BASE): the operand halves whose range test is still run — bit 0 the accumulator's four
+// samples, bit 1 the row's; 3 = both, the guarded handler.  A half the interval pass proved inside [2^-39, 2^39] is not tested.
+template <int K, int VAR, int M = 3> __device__ __noinline__ HState<float> h_div_fast(HFAST_ARGS) {
     typedef float T;
     typedef VecOf<float>::type V;
     constexpr int G = TG<T>::G;
     const U32x4 w = *code;
     if constexpr (VAR & 2) { // constant operand
-        bool unsafe = false;
-        FOR_PLANES unsafe |= !div_samples_safe(st.acc[g]);
         if (__builtin_expect(!div_const_in_range(w1), 0)) [[clang::musttail]] return h_chain<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
-        if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
+        if constexpr (M & 1) {
+            bool unsafe = false;
+            FOR_PLANES unsafe |= !div_samples_safe(st.acc[g]);
+            if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
+        }
         FOR_PLANES st.acc[g] = div_const<K>(st.acc[g], w1);
     } else {
         V num[G], den[G];
@@ -1019,9 +1033,11 @@ template <int K, int VAR> __device__ __noinline__ HState<float> h_div_fast(HFAST
             const V b = *LDSP(T, PLANE_ADDR(lds0 + la, g));
             num[g] = K == 4 ? st.acc[g] : b;
             den[g] = K == 4 ? b : st.acc[g];
-            unsafe |= !div_operands_safe(num[g], den[g]);
+            if constexpr (M == 3) unsafe |= !div_operands_safe(num[g], den[g]);
+            else if constexpr (M == 1) unsafe |= !div_samples_safe(st.acc[g]);
+            else if constexpr (M == 2) unsafe |= !div_samples_safe(b);
         }
-        if (__builtin_expect(__ballot(unsafe) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
+        if constexpr (M != 0) if (__builtin_expect(__ballot(unsafe) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
         FOR_PLANES st.acc[g] = div_safe(num[g], den[g]);
     }
     if constexpr (VAR & 1) FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
@@ -1265,6 +1281,13 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
 #undef TBC
 #undef TB1
 #undef TBF
+    // the assured forms (de_bind.h TOPA_*): every slot starts as the FULL handler of the same instruction (h_chain over the body: what the
+    // table holds at this point); exact-mode Float32 replaces the slots the assured stream can name below.  The rest — other element types,
+    // turbo, the m = 1 / 2 slots of a division by a constant — is never named by assure_tree and only keeps the table dense and inside
+    // the address window the host checks
+    for (uint32_t k = 0; k < 2; k++) for (uint32_t v = 0; v < 4; v++) t[topa_un((int)k, v)] = t[BOP_UN_BASE + 4 * k + v];
+    for (uint32_t i = 0; i < 16; i++) t[TOPA_UNROW_BASE + i] = t[TOP_UNROW_BASE + i];
+    for (uint32_t k = 4; k < 6; k++) for (uint32_t v = 0; v < 4; v++) for (uint32_t m = 0; m < 3; m++) t[topa_div((int)k, v, m)] = t[BOP_BIN_BASE + 4 * k + v];
     if constexpr (sizeof(T) == 4) { // Float32: the fast-path-only forms (h_*_fast above) replace the full handlers in the table
 #define HUF(K) t[BOP_UN_BASE + 4 * K + 0] = (uint64_t)&h_un_fast<K, 0, TB>; t[BOP_UN_BASE + 4 * K + 1] = (uint64_t)&h_un_fast<K, 1, TB>; \
                t[BOP_UN_BASE + 4 * K + 2] = (uint64_t)&h_un_fast<K, 2, TB>; t[BOP_UN_BASE + 4 * K + 3] = (uint64_t)&h_un_fast<K, 3, TB>; \
@@ -1281,6 +1304,23 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
 #define HD2(K, C, O) t[top_bin2(K, C, O, false)] = (uint64_t)&h_div2_fast<K, C, O, false>; t[top_bin2(K, C, O, true)] = (uint64_t)&h_div2_fast<K, C, O, true>;
 #define HD2K(K) HD2(K, false, false) HD2(K, false, true) HD2(K, true, false) HD2(K, true, true)
             HDF(4) HDF(5) HD2K(4) HD2K(5)
+            // ... and for exact-mode Float32 the forms without the tests the assured stream's interval pass proves idle
+#define HAU(K) t[topa_un(K, 0)] = (uint64_t)&h_un_fast<K, 0, false, true>; t[topa_un(K, 1)] = (uint64_t)&h_un_fast<K, 1, false, true>; \
+               t[topa_un(K, 2)] = (uint64_t)&h_un_fast<K, 2, false, true>; t[topa_un(K, 3)] = (uint64_t)&h_un_fast<K, 3, false, true>;
+#define HAUR1(K, O, P) t[TOPA_UNROW_BASE + top_unrow(K, O, P, false) - TOP_UNROW_BASE] = (uint64_t)&h_unrow_fast<K, O, P, false, false, true>; \
+                       t[TOPA_UNROW_BASE + top_unrow(K, O, P, true) - TOP_UNROW_BASE] = (uint64_t)&h_unrow_fast<K, O, P, true, false, true>;
+#define HAUR(K) HAUR1(K, false, false) HAUR1(K, false, true) HAUR1(K, true, false) HAUR1(K, true, true)
+            HAU(0) HAU(1) HAUR(0) HAUR(1)
+#define HAD1(K, V) t[topa_div(K, V, 0)] = (uint64_t)&h_div_fast<K, V, 0>; t[topa_div(K, V, 1)] = (uint64_t)&h_div_fast<K, V, 1>; t[topa_div(K, V, 2)] = (uint64_t)&h_div_fast<K, V, 2>;
+#define HAD2(K, V) t[topa_div(K, V, 0)] = (uint64_t)&h_div_fast<K, V, 0>; /* (a constant operand: m = 0 only; 1 and 2 keep the guarded handler) */
+#define HAD(K) HAD1(K, 0) HAD1(K, 1) HAD2(K, 2) HAD2(K, 3)
+            HAD(4) HAD(5)
+#undef HAD
+#undef HAD2
+#undef HAD1
+#undef HAUR
+#undef HAUR1
+#undef HAU
 #undef HD2K
 #undef HD2
 #undef HDF
@@ -1524,6 +1564,9 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
     // one tree per workgroup (the reference's own call shape, 1 tree x 5e7 samples) a load issued behind the barrier was +50 %
     int32_t co_first = 0;
     if (a.skip_flagged && tA + (tid & 63) < tB) co_first = a.code_off[tA + (tid & 63)];
+    // the tile fact of the assured stream (KArgs::assured): this lane's values of the tile are ordinary numbers
+    constexpr bool ASSURABLE = WW == 1 && !PARAMS && sizeof(T) == 4 && DE_TBLK == 64;
+    bool x_ok = true;
     {
         const uint32_t F = (uint32_t)a.F;
         const uint32_t total = (uint32_t)TILE * F;
@@ -1564,6 +1607,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
                         uint32_t j = a.f_magic ? __umulhi(e, a.f_magic) : e;
                         uint32_t f = e - j * F;
                         DE_UNROLL for (int c = 0; c < VW; c++) {
+                            if constexpr (ASSURABLE) x_ok &= assured_value_ok(buf[u][c], a.assured_xmax);
                             rows[f * (ROWV * VW) + j] = buf[u][c];
                             ++f;
                             if (f == F) { f = 0; ++j; }
@@ -1575,14 +1619,18 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
             const T *__restrict__ src = a.X + base * (int64_t)F;
             for (uint32_t e = stid; e < total; e += SBLK) {
                 const uint32_t j = e / F, f = e - j * F;
-                rows[f * (ROWV * VW) + j] = src[e];
+                const T v = src[e];
+                if constexpr (ASSURABLE) x_ok &= assured_value_ok(v, a.assured_xmax);
+                rows[f * (ROWV * VW) + j] = v;
             }
         } else {
             for (uint32_t e = stid; e < total; e += SBLK) {
                 const uint32_t j = e / F, f = e - j * F;
                 int64_t jj = base + j;
                 jj = jj < last ? jj : last;
-                rows[f * (ROWV * VW) + j] = a.X[f + a.ldX * jj];
+                const T v = a.X[f + a.ldX * jj];
+                if constexpr (ASSURABLE) x_ok &= assured_value_ok(v, a.assured_xmax);
+                rows[f * (ROWV * VW) + j] = v;
             }
         }
     }
@@ -1623,7 +1671,9 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
     }
     __syncthreads();
 
-    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)(a.code + (WW > 1 ? (int64_t)wave * a.var_stride : (int64_t)0));
+    // (one wave = the workgroup: the ballot decides for the whole tile, and the choice lives in this wave's scalar registers)
+    const bool assured_tile = ASSURABLE && a.assured != 0 && __ballot(!x_ok) == 0ull;
+    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)(a.code + (WW > 1 ? (int64_t)wave * a.var_stride : (assured_tile ? a.var_stride : (int64_t)0)));
     // this wave's live-tree list (h_tree_skip): wave 0 / a one-wave workgroup at LDS address 0, wave w of a group behind the rows
     const uint32_t list_at = (WW > 1 && wave > 0) ? a.list_off + (uint32_t)(wave - 1) * DE_SKIPLIST_BYTES : 0u;
     const ConstI32Ptr code_off = (ConstI32Ptr)(uintptr_t)a.code_off;
@@ -2135,6 +2185,11 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
     // wave groups (KArgs::var_stride): parametric programs with staged parameter rows whose stream exists in e.waves variants
     const int WW = (TBLK == 64 && (e.waves == 2 || e.waves == 4 || e.waves == 8) && (!e.uses_params || e.n_prows > 0)) ? e.waves : 1;
     a.var_stride = WW > 1 ? e.var_stride : 0;
+    // the assured stream of a one-wave Float32 program: variant 1 of the stream (DE_TBLK == 64: the workgroup is one wave, one ballot decides)
+    a.assured = (WW == 1 && TBLK == 64 && sizeof(T) == 4 && e.assured && e.var_stride != 0 && !e.uses_params) ? 1 : 0;
+    a.assured_xmax = e.assured_xmax;
+    if (a.assured) a.var_stride = e.var_stride;
+    const unsigned n_variants = a.var_stride ? (a.assured ? 2u : (unsigned)WW) : 1u; // (what de_compact_live_kernel re-links: a workgroup each)
     int32_t tpc, nch, nc0;
     plan_chunks(e.n_trees, a.n_tiles, &nch, &tpc, &nc0, WW);
     a.trees_per_chunk = tpc;
@@ -2286,10 +2341,10 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
                 }
             }
             if (sizeof(T) == 4)
-                hipLaunchKernelGGL(de_compact_live_kernel<true>, dim3(a.var_stride ? WW : 1), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
+                hipLaunchKernelGGL(de_compact_live_kernel<true>, dim3(n_variants), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
                                    e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride);
             else
-                hipLaunchKernelGGL(de_compact_live_kernel<false>, dim3(a.var_stride ? WW : 1), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
+                hipLaunchKernelGGL(de_compact_live_kernel<false>, dim3(n_variants), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
                                    e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride);
             const hipError_t cs = hipGetLastError();
             if (cs != hipSuccess) return cs;

@@ -76,7 +76,9 @@ extern "C" {
  *      hooks keep their real dtype domain and complex tapes lower through the new de_lower_tape_complex / de_lower_tape_stage_complex;
  *      the same entry points answer DE_ERR_UNSUPPORTED, and so does de_program_create with n_params > 0.
  *      (e) de_program_update: replace some trees of a program in place, for every dtype.
- *      (f) de_lower_tape_grad: the host-only hook of the two gradient stream encoders, DE_F32 / DE_F64. */
+ *      (f) de_lower_tape_grad: the host-only hook of the two gradient stream encoders, DE_F32 / DE_F64.
+ *      (g) de_lower_tape_assured, stage 4 of de_lower_tape_stage and words 5 / 6 and which = 4 of de_program_dump: the assured
+ *      stream of Float32 programs. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -312,7 +314,9 @@ int64_t de_program_n_grad(const de_program_t *prog, int64_t tree, int mode);
  * which: 0 generic program, 1 metadata (n_slots, host_ok_eval, host_ok_grad, uses_params and,
  * with cap >= 5, the waves per workgroup the eval kernel runs this program with), 2 bound
  * program, 3 fused (superinstruction) program of the threaded eval kernel (0 words when that
- * kernel is not in use). */
+ * kernel is not in use), 4 the fused program with the handler ids of the assured stream (0 words
+ * when the program has none).  Metadata with cap >= 7 adds: the program has an assured stream,
+ * and the launches use it (0 behind de_program_set_consts_device until the host sees the constants). */
 int64_t de_program_dump(const de_program_t *prog, int64_t tree, uint32_t *words, int64_t cap,
                         int which);
 
@@ -348,6 +352,16 @@ int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_no
                             const void *consts, int64_t n_consts, int32_t n_features,
                             int32_t n_params, uint32_t options, int stage, uint32_t *words,
                             int64_t cap);
+/* Stage 4 (DE_F32 only): the stage-3 words with the handler ids of the ASSURED stream — the same records, a
+ * validity test that cannot fire while every feature value has 2^-40 <= |x| <= DE_ASSURED_XMAX (default 64) left out by naming the
+ * untested twin of the instruction's handler.  de_lower_tape_assured returns what decides it: per fused instruction six doubles
+ * {lo, hi, amin, finite, id, bits} — the interval [lo, hi] and the lower bound amin of |value| of the accumulator behind the
+ * instruction (meaningful when finite == 1), the assured handler id and the elision bits (1: the result's validity test, 2: the row
+ * operand's, 4: the cos / exp range pre-test, 8 / 16: the division range test of the accumulator / row operand) with every part of
+ * the pass on; stage 4 applies the parts a program would (DE_ASSURED_PARTS, default 3 = bits 1, 2 and 4).
+ * Returns the number of doubles or -status.  Host-only. */
+int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                              int32_t n_features, uint32_t options, double xmax, double *out, int64_t cap);
 /* The two hooks above take the real dtypes (DE_F32, DE_F64, DE_F16) and answer -DE_ERR_INVALID_ARG for any other code; complex tapes
  * (DE_CF32 / DE_CF64, interleaved (re, im) constants) lower through these two, which take nothing else.  The generic words carry, for a
  * constant operand, the index of its (re, im) pair in the program's constant table (slot k of the tape: index k) instead of its value. */

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""What the assured stream can remove, from the VALU slot table: CPU only.
+
+For the benchmark population (seed 0xDE02) this prices every fused instruction of the guarded stream (stage 3 of
+`de_lower_tape_stage`) and of the assured stream (stage 4) with `profiles/valu_slots.json` (VALU cycles of the handler each id names;
+an end-fused last instruction is priced as its plain form in both) and reports, per tree-wave: the cycles of the guarded stream, the
+share of each guard (validity tests: a tested handler minus its untested twin; the cos / exp pre-test and the division range test:
+the guarded handler minus its form without the test), how many of each the intervals prove idle, and what each part of the pass
+(`DE_ASSURED_PARTS`: 1 validity, 2 pre-tests, 4 division halves) removes.
+
+    python tools/exp_guard_bound.py [--trees 1000] [--xmax 64] > profiles/exp_guard_bound.json
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import dynamicexpressions_jl_amd as de  # noqa: E402
+from dynamicexpressions_jl_amd import api  # noqa: E402
+
+BIN, UN, GEN_ROW = 5, 29, 41
+LOADROW, LOADCONST_PUSH, UNROW, BINROWC, BIN2, TOP_COUNT = 48, 52, 53, 77, 89, 137
+
+
+def untested(top: int) -> int:
+    """The id of the same operator without any validity test (what the pass could reach at best)."""
+    if BIN <= top < GEN_ROW:
+        return top - ((top - BIN) & 1)
+    if LOADROW <= top < LOADCONST_PUSH:
+        return top - ((top - LOADROW) & 1)
+    if UNROW <= top < BINROWC:
+        return UNROW + ((top - UNROW) & ~5)
+    if BINROWC <= top < BIN2:
+        return BIN + 4 * ((top - BINROWC) >> 1)
+    if BIN2 <= top < TOP_COUNT:
+        return BIN2 + ((top - BIN2) & ~2)
+    return top
+
+
+def guard_cycles(top, cyc):
+    """(validity tests, cos / exp pre-test, division range test) VALU cycles inside the guarded handler `top`."""
+    val = cyc[top] - cyc[untested(top)]
+    pre = div = 0.0
+    k = un = None
+    if BIN <= top < UN: k, cst = (top - BIN) >> 2, (top - BIN) & 2
+    elif BINROWC <= top < BIN2: k, cst = (top - BINROWC) >> 1, 0
+    elif BIN2 <= top < TOP_COUNT: k, cst = (top - BIN2) >> 3, (top - BIN2) & 4
+    elif UN <= top < GEN_ROW: un = (top - UN) >> 2
+    elif UNROW <= top < BINROWC: un = (top - UNROW) >> 3
+    if k is not None and k >= 4:  # priced on the plain forms: row / row 21 -> 185, constant 23 -> 191
+        div = cyc[BIN + 16 + (2 if cst else 0)] - cyc[A_DIV + (2 if cst else 0) * 3]
+    if un is not None and un < 2:
+        pre = cyc[UN + 4 * un] - cyc[A_UN + 4 * un]
+    return val, pre, div
+
+
+A_UN, A_UNROW, A_DIV = 161, 169, 185  # csrc/de_bind.h TOPA_*: cos / exp without the pre-test, divisions by tested operand halves
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trees", type=int, default=1000)
+    ap.add_argument("--xmax", type=float, default=64.0)
+    args = ap.parse_args()
+    os.environ["DE_ASSURED_XMAX"] = repr(args.xmax)
+    with open(os.path.join(ROOT, "profiles", "valu_slots.json")) as fh:
+        tab = json.load(fh)
+    cyc = {int(k): v["valu_cycles"] for k, v in tab["handlers"].items()}
+    ops = de.synth.BENCH_OPERATORS
+    trees = de.synth.random_population(args.trees, seed=0xDE02)
+    n = float(len(trees))
+    over = tab["per_tree_overhead_cycles"]
+    guarded = val = pre = div = 0.0
+    n_instr = n_pre = n_half = 0
+    bits_n = {1: 0, 2: 0, 4: 0, 8: 0, 16: 0}
+    by_parts = {p: 0.0 for p in (1, 2, 4, 3, 5, 7)}
+    for tree in trees:
+        tape, consts = de.flatten(tree, ops, np.float32)
+        f3 = api.lower_tape_stage(tape, consts, 5, 3)
+        for top in f3[:, 0]:
+            g = guard_cycles(int(top), cyc)
+            n_instr += 1
+            guarded += cyc[int(top)]
+            val, pre, div = val + g[0], pre + g[1], div + g[2]
+            n_pre += g[1] > 0
+            n_half += (2 if g[2] > 30 else 1) if g[2] > 0 else 0
+        for b in api.lower_tape_assured(tape, consts, 5, args.xmax)[:, 5].astype(int):
+            for k in bits_n:
+                bits_n[k] += bool(b & k)
+        for p in by_parts:
+            os.environ["DE_ASSURED_PARTS"] = str(p)
+            by_parts[p] += sum(cyc[int(t)] for t in api.lower_tape_stage(tape, consts, 5, 4)[:, 0])
+    tot = guarded + over * n
+    out = {
+        "source": "tools/exp_guard_bound.py: profiles/valu_slots.json over the fused programs of the bench population (seed 0xDE02, UNFOLDED "
+                  "tapes as de_lower_tape_stage lowers them; an end-fused last instruction priced as its plain form)",
+        "trees": len(trees), "xmax": args.xmax,
+        "fused_instructions_per_tree": n_instr / n,
+        "valu_cycles_per_tree_wave_guarded": tot / n,
+        "guards_share_of_guarded": {"validity_tests": val / tot, "cos_exp_pre_tests": pre / tot, "division_range_tests": div / tot,
+                                    "all": (val + pre + div) / tot},
+        "guards_per_tree": {"cos_exp_pre_tests": n_pre / n, "division_operand_halves": n_half / n},
+        "elided_per_tree": {"validity_result": bits_n[1] / n, "validity_row": bits_n[2] / n, "cos_exp_pre_tests": bits_n[4] / n,
+                            "division_halves_accumulator": bits_n[8] / n, "division_halves_row": bits_n[16] / n},
+        "provably_idle_share": {"cos_exp_pre_tests": bits_n[4] / max(n_pre, 1), "division_operand_halves_with_a_handler": (bits_n[8] + bits_n[16]) / max(n_half, 1)},
+        "removed_share_of_guarded_by_DE_ASSURED_PARTS": {str(p): (guarded - c) / tot for p, c in sorted(by_parts.items())},
+    }
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()

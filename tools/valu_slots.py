@@ -168,7 +168,23 @@ def handler_names(ty: str, turbo: bool = False):
     XB = TOP_COUNT + 20
     for i, (k, s) in enumerate(((6, 0), (6, 1), (7, 0), (7, 1))):
         names[XB + i] = f"h_maxmin<{ty}, {k}, {s}>"
-    return names, dict(BOP_COUNT=BOP_COUNT, TOP_COUNT=TOP_COUNT, TOPX_COUNT=XB + 4)
+    # the assured forms (csrc/de_bind.h TOPA_*): Float32 exact mode.  Any other slot is never dispatched (the table holds the full handler of the
+    # same instruction there); it is listed under the name of the handler its guarded id resolves to, so that every id has an entry
+    plain = ty == "float" and not turbo
+    AUN = XB + 4
+    for k in range(2):
+        for v in range(4):
+            names[AUN + 4 * k + v] = f"h_un_assured<{k}, {v}>" if plain else names[UN_BASE + 4 * k + v]
+    AUNROW = AUN + 8
+    for i in range(16):
+        names[AUNROW + i] = names[UNROW + i].replace("h_unrow_f<float, ", "h_unrow_assured<").replace(", false>", ">") if plain else names[UNROW + i]
+    ADIV = AUNROW + 16
+    for k in (4, 5):
+        for v in range(4):
+            for m in range(3):
+                names[ADIV + ((k - 4) * 4 + v) * 3 + m] = (f"h_div_assured<{k}, {v}, {m}>" if plain and (v < 2 or m == 0)
+                                                           else names[BIN_BASE + 4 * k + v])
+    return names, dict(BOP_COUNT=BOP_COUNT, TOP_COUNT=TOP_COUNT, TOPX_COUNT=ADIV + 24)
 
 
 def table(obj, ty="float", turbo=False):
@@ -184,17 +200,17 @@ def table(obj, ty="float", turbo=False):
         if m:
             by_short[m.group(1)] = code
             continue
-        m = re.search(r"de::h_un_fast<(\d), (\d), (true|false)>\(", full)  # Float32 hot unary handlers: the fast-path-only forms are what the table points at
-        if m:
-            fast[f"h_un<float, {m.group(1)}, {m.group(2)}, {m.group(3)}>"] = code
+        m = re.search(r"de::h_un_fast<(\d), (\d), (true|false), (true|false)>\(", full)  # Float32 hot unary handlers: the fast-path-only forms are what the table points at
+        if m:  # (last argument true: the form without the range pre-test, named by the assured stream only)
+            fast[f"h_un_assured<{m.group(1)}, {m.group(2)}>" if m.group(4) == "true" else f"h_un<float, {m.group(1)}, {m.group(2)}, {m.group(3)}>"] = code
             continue
-        m = re.search(r"de::h_div_fast<(\d), (\d)>\(", full)  # ... and of the exact Float32 divisions
+        m = re.search(r"de::h_div_fast<(\d), (\d), (\d)>\(", full)  # ... and of the exact Float32 divisions (last argument: the operand halves still tested, 3 = guarded)
         if m:
-            fast[f"h_bin<float, {m.group(1)}, {m.group(2)}, false>"] = code
+            fast[f"h_bin<float, {m.group(1)}, {m.group(2)}, false>" if m.group(3) == "3" else "h_div_assured<%s, %s, %s>" % m.groups()] = code
             continue
-        m = re.search(r"de::h_unrow_fast<(\d), (true|false), (true|false), (true|false), (true|false)>\(", full)  # ... and their fused forms
+        m = re.search(r"de::h_unrow_fast<(\d), (true|false), (true|false), (true|false), (true|false), (true|false)>\(", full)  # ... and their fused forms
         if m:
-            fast["h_unrow_f<float, %s, %s, %s, %s, %s>" % m.groups()] = code
+            fast[("h_unrow_assured<%s, %s, %s, %s>" if m.group(6) == "true" else "h_unrow_f<float, %s, %s, %s, %s, %s>") % m.groups()[:4 if m.group(6) == "true" else 5]] = code
             continue
         m = re.search(r"de::h_divrowc_fast<(\d), (true|false)>\(", full)
         if m:
