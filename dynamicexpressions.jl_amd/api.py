@@ -52,7 +52,7 @@ EXPORTS = [
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
-    "de_lower_tape_assured",
+    "de_lower_tape_assured", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
 ]
 
 
@@ -73,6 +73,12 @@ class ParamArgs(C.Structure):
 class LossSpec(C.Structure):
     """``de_loss_spec_t``: a loss kind of ``de_loss_kind_t`` and its one scalar parameter."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("param", C.c_double)]
+
+
+class LmOpts(C.Structure):
+    """``de_lm_opts_t``: what ``de_fit_consts_lm`` takes besides the data (null: 10 iterations, lam0 1e-3, up 10, down 0.1, floor 1e-12)."""
+    _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("lam0", C.c_double), ("up", C.c_double), ("down", C.c_double),
+                ("lam_min", C.c_double)]
 
 
 # de_loss_kind_t (include/de_hip.h): name -> enum value.  "pullback" belongs to the gradient entry points only.
@@ -228,6 +234,50 @@ class GaussNewton:
 
         return one(tree) if tree is not None else [one(t) for t in range(len(self))]
 
+    def lm_step_device(self, lam):
+        """``lm_step`` of every tree on the device (``de_gn_lm_step``) over the packed buffers ``eval_gauss_newton``
+        filled — nothing is copied, nothing synchronises when they are device tensors: a float64 array / tensor in the gradient's
+        packed layout (tree t at ``sum(n_grad[:t])``).  A Cholesky solve: where the matrix is rank-deficient and ``lam`` is 0 the step is
+        zero (numpy's LU may return a huge vector).  ``ValueError`` for a population with shared GraphNode constants (their rows are
+        combined on the host: ``lm_step``) and for an object that ``eval_gauss_newton`` did not make."""
+        pk = getattr(self, "_packed", None)
+        if pk is None:
+            raise ValueError("lm_step_device needs the packed buffers of Population.eval_gauss_newton")
+        if pk["occ"]:
+            raise ValueError("lm_step_device: the population shares GraphNode constants (per-occurrence rows): use lm_step")
+        ctx, dl, jt, ng, n = pk["ctx"], pk["dloss"], pk["jtj"], pk["n_grad"], len(self)
+        total = max(int(ng.sum()), 1)
+        lib = library()
+        if _is_torch(dl):
+            import torch
+            ctx.use_torch_stream()
+            lams = torch.as_tensor(lam, dtype=torch.float64, device=dl.device).expand(n).contiguous()
+            has = self.has_jtj.to(torch.uint8).contiguous()
+            step = torch.zeros(total, dtype=torch.float64, device=dl.device)
+            ctx.check(lib.de_gn_lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.data_ptr(), None, jt.data_ptr(), None, has.data_ptr(),
+                                        lams.data_ptr(), step.data_ptr()))
+            self._lm_keep = (lams, has)  # (read in stream order)
+            return step[:int(ng.sum())]
+        lams = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (n,)))
+        has = np.ascontiguousarray(np.asarray(self.has_jtj), dtype=np.uint8)
+        step = np.zeros(total, dtype=np.float64)
+        ctx.check(lib.de_gn_lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.ctypes.data, None, jt.ctypes.data, None, has.ctypes.data,
+                                    lams.ctypes.data, step.ctypes.data))
+        return step[:int(ng.sum())]
+
+
+def lm_solve_host(H, g, lam: float):
+    """``de_lm_solve_host``: the arithmetic of the device's Levenberg-Marquardt step (csrc/de_lm_solve.h) for one system on the host, no
+    GPU needed — (step[G] float64, produced): ``produced`` False means the zero step (see ``GaussNewton.lm_step_device``)."""
+    H = np.asfortranarray(H, dtype=np.float64)
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+    G = g.size
+    if H.shape != (G, G):
+        raise ValueError("H must be G x G for a gradient of G entries")
+    step = np.full(max(G, 1), np.nan, dtype=np.float64)
+    rc = library().de_lm_solve_host(G, H.ctypes.data, g.ctypes.data, float(lam), step.ctypes.data)
+    return step[:G], bool(rc)
+
 
 def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
@@ -318,6 +368,10 @@ def library() -> C.CDLL:
     lib.de_eval_fit_stats.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, vp, vp, vp]
     lib.de_eval_loss_gn.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.de_gn_max_rows.argtypes = []
+    if hasattr(lib, "de_fit_consts_lm"):  # (absent from a library built before the device Levenberg-Marquardt loop: DE_HIP_LIB in an A/B run)
+        lib.de_gn_lm_step.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.de_fit_consts_lm.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LmOpts), vp, vp, vp, vp]
+        lib.de_lm_solve_host.argtypes = [C.c_int, vp, vp, C.c_double, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1241,7 +1295,11 @@ class Population:
             has = okb & narrow
         if occ is not None:
             mats = [gn_combine(H, occ[t]) for t, H in enumerate(mats)]
-        return GaussNewton(lo, grads, mats, okb, has)
+        gn = GaussNewton(lo, grads, mats, okb, has)
+        # the packed buffers the views above look into: GaussNewton.lm_step_device hands them to de_gn_lm_step as they are
+        gn._packed = dict(ctx=self.ctx, dtype=_dtype_code(self.dtype), n_grad=np.ascontiguousarray(ng, dtype=np.int32), dloss=dl, jtj=jt,
+                          occ=occ is not None)
+        return gn
 
     def fit_constants_lm(self, X, y, consts0, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0, down: float = 0.1,
                          history: Optional[list] = None):
@@ -1282,6 +1340,72 @@ class Population:
                 history.append(loss.copy())
         self.set_constants(consts)
         return consts, loss, ok
+
+    def fit_constants_lm_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
+                                down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+        """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm``): the steps are solved, the trial constants
+        set, and the accept rule applied on the device; no constant, gradient or matrix reaches the host.  ``consts0``: a numpy array or a
+        torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.  Returns (consts, loss[n_trees] in
+        the population's dtype, ok) at the accepted constants, which the population holds afterwards; with torch inputs all three are
+        device tensors and nothing synchronises beyond what ``eval_gauss_newton`` does.  ``history`` (a list) receives the ``iters + 1``
+        rows of accepted losses (float64); ``self.lm_accepts`` holds the number of accepted steps per tree.  The step is a Cholesky solve
+        (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it."""
+        self._refuse_f16("fit_constants_lm_device")
+        if self._occ is not None:
+            raise ValueError("fit_constants_lm_device: the population shares GraphNode constants (their per-occurrence rows are combined "
+                             "on the host): use fit_constants_lm")
+        opts = LmOpts(int(iters), 0, float(lam0), float(up), float(down), 1e-12)
+        if opts.iters < 0 or not all(np.isfinite(v) and v > 0 for v in (opts.lam0, opts.up, opts.down)):
+            raise ValueError("fit_constants_lm_device: iters >= 0 and finite positive lam0, up, down")
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        pa = self._param_args(params, classes, class_base, N, keep)
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                n, p_ = v.numel(), v.data_ptr()
+            else:
+                v = np.ascontiguousarray(v, dtype=self.dtype)
+                n, p_ = v.size, v.ctypes.data
+            if n != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return p_
+
+        if y is None:
+            raise ValueError("fit_constants_lm_device: y is required")
+        yp, wp = vec(y, "y"), vec(weights, "weights")
+        if consts0 is not None:
+            n_expected = int(self.n_consts.sum())
+            if (consts0.numel() if _is_torch(consts0) else np.size(consts0)) != n_expected:
+                raise ValueError("wrong number of constants")
+            self.set_constants(consts0 if _is_torch(consts0) else np.asarray(consts0).reshape(-1))
+        lib, nt, rows = library(), self.n_trees, int(iters) + 1
+        if is_t:
+            import torch
+            dev = keep_x.device
+            lo = torch.empty(nt, dtype=keep_x.dtype, device=dev)
+            ok = torch.empty(nt, dtype=torch.uint8, device=dev)
+            hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
+            acc = torch.empty(nt, dtype=torch.int32, device=dev)
+            ptrs = (lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
+        else:
+            lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
+            hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
+            ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
+        self.ctx.check(lib.de_fit_consts_lm(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
+        self.lm_accepts = acc
+        if history is not None:
+            history.extend(hist[r] for r in range(rows))
+        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
 
     def eval_loss_grad_by_class(self, X, y, params, classes, weights=None, loss: str = "L2",
                                 variable: Union[bool, str] = "both", class_base: int = 1, grouped: bool = False, loss_param: float = 0.0):

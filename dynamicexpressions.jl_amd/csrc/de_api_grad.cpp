@@ -1,8 +1,11 @@
 // de_api_grad.cpp — C ABI (include/de_hip.h): de_eval_grad / de_eval_diff / de_eval_pullback_dX, de_eval_loss_grad, de_eval_loss_grad_by_class: the
 // generic gradient program, the glue around the host encoders of its direct-threaded and reverse-accumulation forms (de_grad_encode.cpp)
-// with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels.
+// with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels; de_gn_lm_step / de_fit_consts_lm /
+// de_lm_solve_host: Levenberg-Marquardt on the constants around de_eval_loss_gn's launch (kernels de_lm.hip).
 #include "de_api_internal.h"
 #include "de_grad_encode.h"
+#include "de_lm.h"
+#include "de_lm_solve.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -1000,6 +1003,264 @@ int de_eval_diff(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t
     if (direction < 0) return fail(c, DE_ERR_INVALID_ARG, "direction < 0");
     if (p && p->uses_params) return fail(c, DE_ERR_UNSUPPORTED, "eval_diff on parametric trees");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, nullptr, DE_GRAD_VARIABLE, direction, out, ld_out, dout, nullptr, ok));
+}
+
+// ---- de_gn_lm_step / de_fit_consts_lm / de_lm_solve_host (kernels: de_lm.hip, arithmetic: de_lm_solve.h) ----------------
+int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step) {
+    double x[LM_MAX_ROWS];
+    const bool args = G <= 0 || (H && g);
+    const int solved = args ? lm_solve8<double>(G, H, g, lam, x) : 0;
+    if (step)
+        for (int k = 0; k < G; k++) step[k] = solved && k < LM_MAX_ROWS ? x[k] : 0.0;
+    return solved;
+}
+
+// The geometry tables of a step / fit on the device: [dloss offsets | jtj offsets | widths].  Uploaded only when they differ from what the
+// device holds, through a pinned image: a call whose buffers are device pointers is stream-ordered and never waits for the stream.
+struct LmTables {
+    const int64_t *doff = nullptr, *joff = nullptr;
+    const int32_t *ng = nullptr;
+    int64_t span = 0, jspan = 0;
+};
+static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out) {
+    const size_t nn = (size_t)n;
+    std::vector<unsigned char> img(nn * (2 * sizeof(int64_t) + sizeof(int32_t)));
+    int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn;
+    int32_t *w = reinterpret_cast<int32_t *>(joff + nn);
+    int64_t run = 0, jrun = 0, span = 0, jspan = 0;
+    for (size_t t = 0; t < nn; t++) {
+        const int64_t g = ng[t];
+        if (g < 0) return fail(c, DE_ERR_INVALID_ARG, "negative n_grad");
+        doff[t] = doffs ? doffs[t] : run;
+        joff[t] = joffs ? joffs[t] : jrun;
+        if (doff[t] < 0 || joff[t] < 0) return fail(c, DE_ERR_INVALID_ARG, "negative offset");
+        w[t] = (int32_t)g;
+        run += g;
+        jrun += g * g;
+        span = std::max(span, doff[t] + g);
+        jspan = std::max(jspan, joff[t] + g * g);
+    }
+    if (img != c->lm_tab || !c->sLmTab.p) {
+        if (c->lm_ev) HIP_TRY(c, hipEventSynchronize(c->lm_ev)); // (the previous upload reads the pinned image)
+        else HIP_TRY(c, hipEventCreateWithFlags(&c->lm_ev, hipEventDisableTiming));
+        if (c->lm_pin_cap < img.size()) {
+            if (c->lm_pin) (void)hipHostFree(c->lm_pin);
+            c->lm_pin = nullptr;
+            c->lm_pin_cap = 0;
+            HIP_TRY(c, hipHostMalloc(&c->lm_pin, img.size(), hipHostMallocDefault));
+            c->lm_pin_cap = img.size();
+        }
+        c->lm_tab.clear();
+        if (c->sLmTab.cap < img.size()) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees the tables queued work may read)
+        HIP_TRY(c, c->sLmTab.reserve(img.size()));
+        std::memcpy(c->lm_pin, img.data(), img.size());
+        HIP_TRY(c, hipMemcpyAsync(c->sLmTab.p, c->lm_pin, img.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->lm_ev, c->stream));
+        c->lm_tab = std::move(img);
+    }
+    out->doff = static_cast<const int64_t *>(c->sLmTab.p);
+    out->joff = out->doff + nn;
+    out->ng = reinterpret_cast<const int32_t *>(out->joff + nn);
+    out->span = span;
+    out->jspan = jspan;
+    return DE_OK;
+}
+// a region of `bytes` in a buffer laid out by successive calls (256-byte granules)
+static size_t lm_place(size_t *at, size_t bytes) {
+    const size_t o = *at;
+    *at += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+}
+
+static int gn_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                           const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+    if (!c) return DE_ERR_INVALID_ARG;
+    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_gn_lm_step: dtype must be DE_F32 or DE_F64");
+    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
+    if (n_trees == 0) return DE_OK;
+    if (!n_grad || !dloss || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
+    // (offsets are checked before anything is written; a growing state buffer is shared with de_fit_consts_lm, which does not run now)
+    LmTables tab;
+    int rc = lm_tables(c, n_trees, n_grad, dloss_offsets, jtj_offsets, &tab);
+    if (rc != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
+    const bool h_dl = !is_device_ptr(dloss), h_j = !is_device_ptr(jtj), h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step);
+    size_t at = 0;
+    const size_t o_dl = h_dl ? lm_place(&at, span * es) : 0, o_j = h_j ? lm_place(&at, jspan * es) : 0, o_has = h_has ? lm_place(&at, nt) : 0,
+                 o_lam = h_lam ? lm_place(&at, nt * 8) : 0, o_step = h_step ? lm_place(&at, span * 8) : 0;
+    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sLm.reserve(at));
+    char *base = static_cast<char *>(c->sLm.p);
+    LmStepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = n_trees;
+    a.n_grad = tab.ng;
+    a.doff = tab.doff;
+    a.joff = tab.joff;
+    a.dloss = dloss;
+    a.jtj = jtj;
+    a.has = has;
+    a.lam = lam;
+    a.step = step;
+    if (h_dl) { HIP_TRY(c, hipMemcpyAsync(base + o_dl, dloss, span * es, hipMemcpyHostToDevice, c->stream)); a.dloss = base + o_dl; }
+    if (h_j) { HIP_TRY(c, hipMemcpyAsync(base + o_j, jtj, jspan * es, hipMemcpyHostToDevice, c->stream)); a.jtj = base + o_j; }
+    if (h_has) { HIP_TRY(c, hipMemcpyAsync(base + o_has, has, nt, hipMemcpyHostToDevice, c->stream)); a.has = reinterpret_cast<const uint8_t *>(base + o_has); }
+    if (h_lam) { HIP_TRY(c, hipMemcpyAsync(base + o_lam, lam, nt * 8, hipMemcpyHostToDevice, c->stream)); a.lam = reinterpret_cast<const double *>(base + o_lam); }
+    if (h_step) { // entries no tree owns keep the caller's values: the staged image starts as a copy
+        HIP_TRY(c, hipMemcpyAsync(base + o_step, step, span * 8, hipMemcpyHostToDevice, c->stream));
+        a.step = reinterpret_cast<double *>(base + o_step);
+    }
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    HIP_TRY(c, launch_lm_step(dtype, a, c->stream));
+    c->last_kernel = "de_lm_step_kernel";
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (h_step) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, span * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_dl || h_j || h_has || h_lam || h_step) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_gn_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                  const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step));
+}
+
+static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                              const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
+    const de_lm_opts_t o = opts ? *opts : defaults;
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm: a program made by de_program_create_cse has one gradient row per occurrence of a "
+                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
+    for (int64_t t = 0; t < p->n_trees; t++)
+        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
+            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm: tree %lld has %lld constant rows for %lld constants", (long long)t,
+                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
+    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: reserved must be 0");
+    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: iters < 0");
+    for (const double v : {o.lam0, o.up, o.down, o.lam_min})
+        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: lam0, up, down and lam_min must be finite and positive");
+    if (N < 0 || (p->n_trees > 0 && (!ok || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
+    int rc = check_param_args(c, p, pa, N);
+    if (rc != DE_OK) return rc;
+    if (p->n_trees == 0) return DE_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
+    std::vector<int32_t> ng(nt);
+    for (size_t t = 0; t < nt; t++) ng[t] = (int32_t)p->n_consts_tree[t];
+    LmTables tab; // packed: the dloss offsets are the constants' offsets
+    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, nullptr, &tab);
+    if (rc != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
+    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
+    Staged sX, sY, sW, sPar, sCls;
+    de_param_args_t pad;
+    const de_param_args_t *pa_use = pa;
+    if (N > 0) {
+        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
+        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
+        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
+        if (p->uses_params) {
+            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
+            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
+            pad = *pa;
+            pad.params = sPar.dev;
+            pad.classes = sCls.dev;
+            pa_use = &pad;
+        }
+        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
+    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
+    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok);
+    const size_t rows = (size_t)o.iters + 1;
+    size_t at = 0;
+    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_la = lm_place(&at, nt * es), o_lt = lm_place(&at, nt * es),
+                 o_da = lm_place(&at, span * es), o_dt = lm_place(&at, span * es), o_ja = lm_place(&at, jspan * es), o_jt = lm_place(&at, jspan * es),
+                 o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt), o_lam = lm_place(&at, nt * 8), o_step = lm_place(&at, span * 8),
+                 o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0, o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
+    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sLm.reserve(at));
+    char *base = static_cast<char *>(c->sLm.p);
+    void *cA = base + o_ca, *cT = base + o_ct, *lA = base + o_la, *lT = base + o_lt, *dA = base + o_da, *dT = base + o_dt, *jA = base + o_ja, *jT = base + o_jt;
+    uint8_t *okA = reinterpret_cast<uint8_t *>(base + o_oka), *okT = reinterpret_cast<uint8_t *>(base + o_okt);
+    double *lam = reinterpret_cast<double *>(base + o_lam), *step = reinterpret_cast<double *>(base + o_step);
+    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
+    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
+
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
+        de_ctx *c;
+        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
+        ~Nest() { c->nested--; }
+    };
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    {
+        Nest nest(c);
+        const GnPlan gnA{jA, nullptr}, gnT{jT, nullptr};
+        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lA, dA, nullptr, okA, nullptr, true, &gnA);
+        if (rc != DE_OK) return rc;
+        HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
+        HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist, c->stream));
+        const bool loop = N > 0 && o.iters > 0 && nc > 0;
+        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
+            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist + r * nt, c->stream));
+        if (loop) {
+            rc = de_program_get_consts(p, cA); // (device to device behind a device set)
+            if (rc != DE_OK) return rc;
+            LmStepArgs s;
+            std::memset(&s, 0, sizeof s);
+            s.n_trees = p->n_trees;
+            s.n_grad = tab.ng;
+            s.doff = s.coff = tab.doff;
+            s.joff = tab.joff;
+            s.dloss = dA;
+            s.jtj = jA;
+            s.has = okA;
+            s.lam = lam;
+            s.step = step;
+            s.consts = cA;
+            s.trial = cT;
+            LmAcceptArgs a;
+            std::memset(&a, 0, sizeof a);
+            a.n_trees = p->n_trees;
+            a.n_grad = tab.ng;
+            a.doff = a.coff = tab.doff;
+            a.joff = tab.joff;
+            a.consts_acc = cA; a.loss_acc = lA; a.dloss_acc = dA; a.jtj_acc = jA; a.ok_acc = okA;
+            a.consts_trial = cT; a.loss_trial = lT; a.dloss_trial = dT; a.jtj_trial = jT; a.ok_trial = okT;
+            a.lam = lam;
+            a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
+            a.n_accept = acc;
+            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
+                HIP_TRY(c, launch_lm_step(p->dtype, s, c->stream));
+                rc = set_consts_device_impl(p, cT);
+                if (rc == DE_OK) rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lT, dT, nullptr, okT, nullptr, true, &gnT);
+                if (rc != DE_OK) break;
+                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
+                HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
+            }
+            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
+            const int rc2 = set_consts_device_impl(p, cA);
+            if (rc != DE_OK) return rc;
+            if (rc2 != DE_OK) return rc2;
+        }
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, lA, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ok, okA, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_consts_lm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                     const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, opts, loss, ok, history, n_accept));
 }
 
 } // extern "C"

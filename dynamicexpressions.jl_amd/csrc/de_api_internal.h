@@ -84,6 +84,15 @@ struct de_ctx {
     DevBuf sX, sOut, sGrad, sOk, sParams, sClasses, sOut2, sGoff, sNg, sY, sW, sLoss, sPartial, sSeg, sDloss, sColOff, sDoff, sPrio, sStats, sYstats, sJtj, sJoff;
     DevBuf sCert; // de_eval_sum_certificate: per-tree maxima
     DevBuf sBcLoss, sBcDloss, sBcOk, sBcNg, sBcDoff, sBcOut, sBcTiles; // de_eval_loss_grad_by_class
+    // de_gn_lm_step / de_fit_consts_lm: sLm — the fit's state (accepted and trial constants, two sets of loss / dloss /
+    // jtj / ok, lam, the step) or the staged buffers of a host-pointer de_gn_lm_step; sLmTab — the geometry tables [dloss offsets | jtj
+    // offsets | widths] of the last call, uploaded through the pinned image lm_pin only when they differ from lm_tab (what the device
+    // holds): lm_ev marks the end of that copy, so a call with device pointers never waits for the stream
+    DevBuf sLm, sLmTab;
+    std::vector<unsigned char> lm_tab;
+    void *lm_pin = nullptr;
+    size_t lm_pin_cap = 0;
+    hipEvent_t lm_ev = nullptr;
     int nested = 0; // > 0 inside a call made of several inner calls: those do not touch the timing events
     // de_ctx_declare_dataset: a device-resident X the caller promises not to modify — its priority-tile keys are computed once
     const void *ds_X = nullptr;
@@ -311,6 +320,8 @@ int stage_out(de_ctx *c, DevBuf &buf, void *user, size_t bytes, Staged *s);
 int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, int64_t N);
 // the host copies of a program brought up to its device constants (de_api_program.cpp); DE_OK at once when they are current
 int consts_materialise(de_program *p);
+// the body of de_program_set_consts_device (de_api_program.cpp): de_fit_consts_lm sets its trial and accepted constants through it
+int set_consts_device_impl(de_program *p, const void *d_consts);
 }
 
 // de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)

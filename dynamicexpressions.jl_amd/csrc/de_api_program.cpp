@@ -1599,7 +1599,7 @@ static int build_const_patch_tables(de_ctx *c, de_program *p, const de_program::
     return 1;
 }
 
-static int set_consts_device_impl(de_program_t *p, const void *d_consts) {
+int set_consts_device_impl(de_program_t *p, const void *d_consts) {
     de_ctx *c = p->ctx;
     const size_t nc = p->consts.size();
     if (nc == 0) return DE_OK;

@@ -817,6 +817,83 @@ function eval_population_gauss_newton(
            okb .& (ng .<= max_rows)
 end
 
+struct LmOpts               # de_lm_opts_t
+    iters::Int32
+    reserved::Int32
+    lam0::Float64
+    up::Float64
+    down::Float64
+    lam_min::Float64
+end
+
+"""
+    population_lm_step(ctx, dloss::Vector{Vector{T}}, jtj::Vector{Matrix{T}}, has_jtj, lam) -> Vector{Vector{Float64}}
+
+The Levenberg-Marquardt step of every tree on the device (`de_gn_lm_step`): `solve(H + lam_t * Diagonal(diag(H)), -g / 2)` by a
+Cholesky factorisation in Float64, from what `eval_population_gauss_newton` returned (`lam`: a number or one value per tree).  The
+zero vector where `has_jtj[t]` is false, the tree has no or more than `de_gn_max_rows()` rows, an entry is not finite or a pivot is not
+positive — a rank-deficient matrix with `lam == 0` gives the zero step.
+"""
+function population_lm_step(
+    ctx::HIPContext, dloss::Vector{Vector{T}}, jtj::Vector{Matrix{T}}, has_jtj::AbstractVector{Bool}, lam,
+) where {T<:Union{Float32,Float64}}
+    n = length(dloss)
+    @assert length(jtj) == n && length(has_jtj) == n
+    ng = Int32[length(g) for g in dloss]
+    @assert all(size(jtj[t]) == (ng[t], ng[t]) for t in 1:n)
+    offs = Int64[0; cumsum(Int64.(ng))]
+    dl = T[v for g in dloss for v in g]
+    jt = T[v for H in jtj for v in H]
+    isempty(dl) && push!(dl, zero(T))
+    isempty(jt) && push!(jt, zero(T))
+    has = UInt8[h ? 0x01 : 0x00 for h in has_jtj]
+    lams = lam isa Number ? fill(Float64(lam), n) : Vector{Float64}(lam)
+    @assert length(lams) == n
+    step = zeros(Float64, max(offs[end], 1))
+    with_ctx(ctx) do hc
+        check(ctx, GC.@preserve ng dl jt has lams step ccall(
+            (:de_gn_lm_step, LIBDE), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}),
+            hc, T === Float32 ? Cint(0) : Cint(1), n, ng, dl, C_NULL, jt, C_NULL, has, lams, step))
+    end
+    return [step[(offs[t] + 1):offs[t + 1]] for t in 1:n]
+end
+
+"""
+    fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1)
+        -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
+
+Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm`): it starts from the
+constants `pop` holds (`set_population_constants!`), and per iteration solves the damped normal equations on the device, sets the trial
+constants there, evaluates, and accepts a tree's step when its loss decreased (`lam_t *= down`, floor 1e-12; else `lam_t *= up`).
+Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the accepted losses
+after `r - 1` iterations.  Trees that are incomplete at the start or wider than `de_gn_max_rows()` keep their constants.  A population
+with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrence rows need folding on the host).
+"""
+function fit_population_constants_lm!(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+    iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1,
+) where {T}
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lm!: shared GraphNode constants need the host loop"))
+    opts = Ref(LmOpts(Int32(iters), Int32(0), Float64(lam0), Float64(up), Float64(down), 1e-12))
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_accept = zeros(Int32, pop.n_trees)
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+            (:de_fit_consts_lm, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
+             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, lossv, ok, history, n_accept))
+    end
+    constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+    return constants, lossv, ok .!= 0x00, history, n_accept
+end
+
 """
     eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(:both))
         -> (loss, dloss::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)

@@ -78,7 +78,9 @@ extern "C" {
  *      (e) de_program_update: replace some trees of a program in place, for every dtype.
  *      (f) de_lower_tape_grad: the host-only hook of the two gradient stream encoders, DE_F32 / DE_F64.
  *      (g) de_lower_tape_assured, stage 4 of de_lower_tape_stage and words 5 / 6 and which = 4 of de_program_dump: the assured
- *      stream of Float32 programs. */
+ *      stream of Float32 programs.
+ *      (h) de_gn_lm_step, de_fit_consts_lm (with de_lm_opts_t) and the host-only hook de_lm_solve_host: Levenberg-Marquardt on the
+ *      constants of a population on the device, DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -534,6 +536,48 @@ int de_eval_loss_gn(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N,
                     void *loss, void *dloss, const int64_t *dloss_offsets,
                     void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
 int de_gn_max_rows(void); /* 8 */
+
+/* Levenberg-Marquardt on the constants, on the device.
+ *
+ * de_gn_lm_step: per tree t with G = n_grad[t] rows the step of Population.fit_constants_lm, all arithmetic in double:
+ *   step[off_t .. off_t + G) = delta,  A delta = -g / 2,  A = H + lam[t] diag(diag H)
+ * with g = dloss[off_t ..] and H = the G x G block jtj[joff_t ..] (column-major, both triangles present, the lower is read) as
+ * de_eval_loss_gn wrote them, solved by a Cholesky factorisation without pivoting (pivot d = A_jj - sum_k L_jk^2).  The step is ZERO
+ * where has[t] == 0, G == 0, G > de_gn_max_rows(), lam[t] is not finite, an entry of H, g or delta is not finite, or a pivot has
+ * !(d > 0) — a rank-deficient H with lam == 0 gives the zero step (an LU solve may return a huge vector there).  Entries of `step` no
+ * tree owns are not written.  n_grad and the offsets are host arrays (NULL offsets: packed, G resp. G^2 entries per tree); dloss / jtj
+ * (elements of `dtype`: DE_F32 or DE_F64), has, lam (one double per tree) and step (doubles, dloss layout) are host or device pointers,
+ * staged like every other buffer.  With device pointers the call is stream-ordered and does not synchronise.
+ *
+ * de_lm_solve_host: the same arithmetic for ONE system on the host (no HIP call; H column-major G x G doubles): returns 1 if a step
+ * was produced, 0 for the zero step.  The kernel and this hook run one source (csrc/de_lm_solve.h): the same bits.
+ *
+ * de_fit_consts_lm: the whole loop in one call.  It starts from the constants the program holds (de_program_set_consts[_device]),
+ * evaluates as de_eval_loss_gn (mode DE_GRAD_CONSTANT, L2) and then `iters` times: step -> device set of the trial constants
+ * T(double(c) + delta) -> evaluation -> per tree  accept = has && has_trial && loss_trial < loss  (has: ok and G <= de_gn_max_rows();
+ * a NaN compares false); an accepted tree takes the trial constants, loss, gradient, matrix and flag; lam[t] = accept ?
+ * max(lam[t] down, lam_min) : lam[t] up.  It ends with a device set of the accepted constants: the program holds them afterwards,
+ * de_program_get_consts returns them and de_eval_loss_grad reproduces loss[t] bit for bit.  loss[t] / ok[t]: the accepted loss and
+ * its flag (a tree with ok == 0 at the start, or wider than de_gn_max_rows(), keeps its constants; its loss is de_eval_loss_gn's).
+ * history (may be NULL): (iters + 1) x n_trees doubles, row r = the accepted losses after r iterations; n_accept (may be NULL): accepted
+ * steps per tree.  X, y, w, loss, ok, history, n_accept: host or device pointers; with device pointers the call synchronises only
+ * where de_eval_loss_gn does, and neither a constant nor a gradient nor a matrix reaches the host.  opts == NULL: {10, 0, 1e-3, 10.0,
+ * 0.1, 1e-12}.  iters == 0 and N == 0: de_eval_loss_gn's loss and flags, the constants unchanged.
+ * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED for a DE_F16 / complex program, a program made by
+ * de_program_create_cse (its occurrence rows need the S H S^T fold of the caller: the host loop) and a tree whose constant rows differ
+ * from its constants; DE_ERR_INVALID_ARG for a null y / ok on a non-empty population, iters < 0, reserved != 0 or a lam0 / up / down /
+ * lam_min that is not finite and positive. */
+typedef struct de_lm_opts {
+    int32_t iters;
+    int32_t reserved; /* 0 */
+    double lam0, up, down, lam_min;
+} de_lm_opts_t;
+int de_gn_lm_step(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                  const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step);
+int de_fit_consts_lm(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                     const void *y, const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                     int32_t *n_accept);
+int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
