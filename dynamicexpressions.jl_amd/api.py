@@ -53,6 +53,7 @@ EXPORTS = [
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
     "de_lower_tape_assured", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
+    "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex",
 ]
 
 
@@ -94,6 +95,21 @@ def loss_spec(loss: str, loss_param: float = 0.0, with_gradient: bool = True) ->
     spec = LossSpec(LOSS_KINDS[loss], 0, float(loss_param))
     if library().de_loss_spec_check(C.byref(spec), int(with_gradient)) != 0:
         raise ValueError(f"loss {loss!r}: parameter {loss_param!r} is not finite or outside the kind's range (include/de_hip.h de_loss_kind_t)")
+    return spec
+
+
+def gn_loss_spec(loss: str, loss_param: float = 0.0, e_floor: float = 1e-4) -> LossSpec:
+    """The ``LossSpec`` of a loss name for the Gauss-Newton entry points (``eval_gauss_newton``, ``fit_constants_lm[_device]``), checked by
+    ``de_gn_spec_check``: an unknown name is a ``KeyError``; "pullback", "l1_hinge" (no curvature), a parameter outside the kind's range
+    and — for the kinds that read it ("L1", "l1_eps", "quantile", "lp" with p < 2) — an ``e_floor`` that is not finite and positive are a
+    ``ValueError``."""
+    spec = LossSpec(LOSS_KINDS[loss], 0, float(loss_param))
+    rc = library().de_gn_spec_check(C.byref(spec), float(e_floor))
+    if rc == 7:  # DE_ERR_UNSUPPORTED
+        raise ValueError(f"loss {loss!r} has no curvature: no Gauss-Newton matrix (DESIGN.md 4.4.5)")
+    if rc != 0:
+        raise ValueError(f"loss {loss!r}: no Gauss-Newton kind, or parameter {loss_param!r} / e_floor {e_floor!r} outside its range "
+                         "(include/de_hip.h de_gn_spec_check)")
     return spec
 
 
@@ -372,6 +388,12 @@ def library() -> C.CDLL:
         lib.de_gn_lm_step.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.de_fit_consts_lm.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LmOpts), vp, vp, vp, vp]
         lib.de_lm_solve_host.argtypes = [C.c_int, vp, vp, C.c_double, vp]
+    if hasattr(lib, "de_gn_spec_check"):  # (absent from a library built before the Gauss-Newton loss kinds: DE_HIP_LIB in an A/B run)
+        lib.de_gn_spec_check.argtypes = [C.POINTER(LossSpec), C.c_double]
+        lib.de_eval_loss_gn_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), C.c_double,
+                                           vp, vp, vp, vp, vp, vp]
+        lib.de_fit_consts_lm_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.c_double,
+                                            C.POINTER(LmOpts), vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1235,13 +1257,17 @@ class Population:
         return lo, [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))], ok.astype(bool)
 
     def eval_gauss_newton(self, X, y, weights=None, variable: Union[bool, str] = False, params=None, classes=None,
-                          class_base: int = 1) -> GaussNewton:
-        """Fused Gauss-Newton normal equations per tree (``de_eval_loss_gn``): the L2 loss and its gradient exactly as
-        ``eval_loss_grad(loss="L2")`` returns them, and ``jtj[t] = sum_j w_j d(j) d(j)^T`` over the gradient rows ``variable`` selects
-        (default: the constants) — what a Levenberg-Marquardt step needs, without the [n_grad, N] Jacobian.  numpy in -> numpy out,
-        torch device tensors in -> tensors out.  A tree of more than ``GN_MAX_ROWS`` rows (the library's per-occurrence rows, for a
-        GraphNode) has ``has_jtj`` False and a NaN matrix; its loss and gradient are filled as usual."""
+                          class_base: int = 1, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4) -> GaussNewton:
+        """Fused Gauss-Newton normal equations per tree (``de_eval_loss_gn_ex``): the loss and its gradient exactly as
+        ``eval_loss_grad(loss=loss, loss_param=loss_param)`` returns them, and ``jtj[t] = sum_j w_j c_j d(j) d(j)^T`` over the gradient
+        rows ``variable`` selects (default: the constants) — what a Levenberg-Marquardt step needs, without the [n_grad, N] Jacobian.
+        ``c_j`` is the kind's curvature weight (1 for "L2"), ``e_floor`` the residual floor of the kinds whose weight is
+        unbounded at a zero residual ("L1", "l1_eps", "quantile", "lp" with p < 2; the others ignore it); "l1_hinge" and "pullback" have no
+        such matrix (``gn_loss_spec``).  numpy in -> numpy out, torch device tensors in -> tensors out.  A tree of more than
+        ``GN_MAX_ROWS`` rows (the library's per-occurrence rows, for a GraphNode) has ``has_jtj`` False and a NaN matrix; its loss and
+        gradient are filled as usual."""
         self._refuse_f16("eval_gauss_newton")
+        spec = gn_loss_spec(loss, loss_param, e_floor)
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -1278,8 +1304,9 @@ class Population:
             kw = dict(dtype=keep_x.dtype, device=keep_x.device)
             lo, dl, jt = torch.empty(self.n_trees, **kw), torch.empty(total, **kw), torch.empty(jtotal, **kw)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
-            self.ctx.check(lib.de_eval_loss_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
-                                               lo.data_ptr(), dl.data_ptr(), offs.ctypes.data, jt.data_ptr(), joffs.ctypes.data, ok.data_ptr()))
+            self.ctx.check(lib.de_eval_loss_gn_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                                  C.byref(spec), float(e_floor), lo.data_ptr(), dl.data_ptr(), offs.ctypes.data,
+                                                  jt.data_ptr(), joffs.ctypes.data, ok.data_ptr()))
             grads = [self._combine_rows(t, d, mode) for t, d in enumerate(torch.split(dl[:int(offs[-1])], ng.tolist()))]
             mats = [jt[joffs[t]:joffs[t + 1]].view(int(ng[t]), int(ng[t])).t() for t in range(self.n_trees)]
             okb = ok.bool()
@@ -1287,8 +1314,9 @@ class Population:
         else:
             lo, dl, jt = np.empty(self.n_trees, dtype=self.dtype), np.empty(total, dtype=self.dtype), np.empty(jtotal, dtype=self.dtype)
             ok = np.zeros(self.n_trees, dtype=np.uint8)
-            self.ctx.check(lib.de_eval_loss_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
-                                               lo.ctypes.data, dl.ctypes.data, offs.ctypes.data, jt.ctypes.data, joffs.ctypes.data, ok.ctypes.data))
+            self.ctx.check(lib.de_eval_loss_gn_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                                  C.byref(spec), float(e_floor), lo.ctypes.data, dl.ctypes.data, offs.ctypes.data,
+                                                  jt.ctypes.data, joffs.ctypes.data, ok.ctypes.data))
             grads = [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))]
             mats = [jt[joffs[t]:joffs[t + 1]].reshape((int(ng[t]), int(ng[t])), order="F") for t in range(self.n_trees)]
             okb = ok.astype(bool)
@@ -1302,9 +1330,9 @@ class Population:
         return gn
 
     def fit_constants_lm(self, X, y, consts0, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0, down: float = 0.1,
-                         history: Optional[list] = None):
+                         history: Optional[list] = None, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4):
         """Levenberg-Marquardt on the constants of every tree at once (the plain loop; one ``eval_gauss_newton`` per iteration behind
-        the one at ``consts0``): per tree the step ``GaussNewton.lm_step(lam_t)`` is accepted if the loss decreased (``lam_t *= down``,
+        the one at ``consts0``), minimising the loss kind ``loss`` (``eval_gauss_newton``'s keywords): per tree the step ``GaussNewton.lm_step(lam_t)`` is accepted if the loss decreased (``lam_t *= down``,
         floor 1e-12), else the tree's constants are restored (``lam_t *= up``).  ``consts0``: ``set_constants``' layout.  Trees without
         ``has_jtj`` keep ``consts0``.  Returns (consts, loss[n_trees] in float64, ok) at the accepted constants, which the population
         holds afterwards; ``history`` (a list) receives the accepted losses after every evaluation."""
@@ -1313,8 +1341,10 @@ class Population:
             raise ValueError("wrong number of constants")
         at = np.zeros(self.n_trees + 1, dtype=np.int64)
         np.cumsum(self.n_consts, out=at[1:])
+        gn_loss_spec(loss, loss_param, e_floor)  # (refused before the population's constants are touched)
+        kind = dict(loss=loss, loss_param=loss_param, e_floor=e_floor)
         self.set_constants(consts)
-        gn = self.eval_gauss_newton(X, y, weights=weights)
+        gn = self.eval_gauss_newton(X, y, weights=weights, **kind)
         loss, ok, has = _host(gn.loss).astype(np.float64), _host(gn.ok).astype(bool), _host(gn.has_jtj).astype(bool)
         grad, jtj = [_host(g) for g in gn.grad], [_host(h) for h in gn.jtj]
         lam = np.full(self.n_trees, float(lam0), dtype=np.float64)
@@ -1327,7 +1357,7 @@ class Population:
                 if has[t]:
                     trial[at[t]:at[t + 1]] = (consts[at[t]:at[t + 1]].astype(np.float64) + steps[t]).astype(self.dtype)
             self.set_constants(trial)
-            gt = self.eval_gauss_newton(X, y, weights=weights)
+            gt = self.eval_gauss_newton(X, y, weights=weights, **kind)
             loss_t, ok_t, has_t = _host(gt.loss).astype(np.float64), _host(gt.ok).astype(bool), _host(gt.has_jtj).astype(bool)
             with np.errstate(invalid="ignore"):
                 accept = has & has_t & (loss_t < loss)
@@ -1342,8 +1372,9 @@ class Population:
         return consts, loss, ok
 
     def fit_constants_lm_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
-                                down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
-        """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm``): the steps are solved, the trial constants
+                                down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1,
+                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4):
+        """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm_ex``): the steps are solved, the trial constants
         set, and the accept rule applied on the device; no constant, gradient or matrix reaches the host.  ``consts0``: a numpy array or a
         torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.  Returns (consts, loss[n_trees] in
         the population's dtype, ok) at the accepted constants, which the population holds afterwards; with torch inputs all three are
@@ -1351,6 +1382,7 @@ class Population:
         rows of accepted losses (float64); ``self.lm_accepts`` holds the number of accepted steps per tree.  The step is a Cholesky solve
         (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it."""
         self._refuse_f16("fit_constants_lm_device")
+        spec = gn_loss_spec(loss, loss_param, e_floor)
         if self._occ is not None:
             raise ValueError("fit_constants_lm_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_lm")
@@ -1401,7 +1433,8 @@ class Population:
             lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
             hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
             ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-        self.ctx.check(lib.de_fit_consts_lm(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
+        self.ctx.check(lib.de_fit_consts_lm_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
+                                               float(e_floor), C.byref(opts), *ptrs))
         self.lm_accepts = acc
         if history is not None:
             history.extend(hist[r] for r in range(rows))

@@ -545,10 +545,31 @@ struct ByClassPlan {
 };
 // de_eval_loss_gn: the same launch with the kernels' Gauss-Newton tree end and G (G + 1) / 2 more reduction columns per tree of at most
 // DE_GN_MAX_ROWS rows; jtj_offsets: host, element offset of every tree's G x G block (null: packed)
+// e_floor: the residual floor of the kind's curvature weight (the spec itself is loss_grad_impl's argument)
 struct GnPlan {
     void *jtj;
     const int64_t *jtj_offsets;
+    double e_floor;
 };
+// de_gn_spec_check with its reason (null = good; *rc: DE_ERR_INVALID_ARG or DE_ERR_UNSUPPORTED).  dtype < 0: the element type is not known.
+static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap) {
+    *rc = DE_ERR_INVALID_ARG;
+    if (loss_spec_problem(spec, 1, buf, cap)) return buf;
+    if (spec->kind == DE_LOSS_PULLBACK) { std::snprintf(buf, cap, "DE_LOSS_PULLBACK has no Gauss-Newton matrix"); return buf; }
+    if (spec->kind == DE_LOSS_L1_HINGE) {
+        *rc = DE_ERR_UNSUPPORTED;
+        std::snprintf(buf, cap, "DE_LOSS_L1_HINGE has no curvature, and the IRLS weight of a margin is no majoriser: no Gauss-Newton matrix");
+        return buf;
+    }
+    const bool reads_floor = spec->kind == DE_LOSS_L1 || spec->kind == DE_LOSS_L1_EPS || spec->kind == DE_LOSS_QUANTILE ||
+                             (spec->kind == DE_LOSS_LP && spec->param < 2.0);
+    if (!reads_floor) return nullptr;
+    if (!(std::isfinite(e_floor) && e_floor > 0.0) || (dtype == DE_F32 && !((float)e_floor > 0.0f))) {
+        std::snprintf(buf, cap, "loss_kind %d: e_floor %g must be finite and > 0%s", (int)spec->kind, e_floor, dtype == DE_F32 ? " in Float32" : "");
+        return buf;
+    }
+    return nullptr;
+}
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
                           const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr);
@@ -580,13 +601,23 @@ int de_eval_loss_grad_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
     DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr));
 }
 int de_gn_max_rows(void) { return DE_GN_MAX_ROWS; }
+int de_gn_spec_check(const de_loss_spec_t *spec, double e_floor) {
+    char buf[160];
+    int rc;
+    return gn_spec_problem(spec, e_floor, -1, &rc, buf, sizeof buf) ? rc : DE_OK;
+}
+int de_eval_loss_gn_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                       const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss,
+                       const int64_t *dloss_offsets, void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_gn");
+    const GnPlan gn{jtj, jtj_offsets, e_floor};
+    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr, false, &gn));
+}
 int de_eval_loss_gn(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
                     const void *y, const void *w, void *loss, void *dloss, const int64_t *dloss_offsets,
                     void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
-    DE_REFUSE_F16("de_eval_loss_gn");
     const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
-    const GnPlan gn{jtj, jtj_offsets};
-    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, loss, dloss, dloss_offsets, ok, nullptr, true, &gn));
+    return de_eval_loss_gn_ex(c, p, X, N, ldX, pa, mode, y, w, &spec, 0.0, loss, dloss, dloss_offsets, jtj, jtj_offsets, ok);
 }
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
@@ -601,7 +632,9 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
         return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", (int)spec->kind);
     char why[160];
     if (loss_spec_problem(spec, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-    int rc = check_param_args(c, p, pa, N);
+    int rc = DE_OK;
+    if (gn && gn_spec_problem(spec, gn->e_floor, p->dtype, &rc, why, sizeof why)) return fail(c, rc, "%s", why);
+    rc = check_param_args(c, p, pa, N);
     if (rc != DE_OK) return rc;
     if (p->n_trees == 0) return DE_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -742,6 +775,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     la.w = w ? sW.dev : nullptr;
     la.kind = spec->kind;
     la.param = spec->param;
+    la.e_floor = gn ? gn->e_floor : 0.0;
     la.partial = c->sPartial.p;
     la.seg_sum = c->sSeg.p;
     la.loss = loss ? sLoss.dev : nullptr;
@@ -1126,9 +1160,15 @@ int de_gn_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad
 }
 
 static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                              const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+                              const void *w, const de_loss_spec_t *spec_in, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                              double *history, int32_t *n_accept) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    {
+        char why[160];
+        int src;
+        if (gn_spec_problem(spec_in, e_floor, p->dtype, &src, why, sizeof why)) return fail(c, src, "%s", why);
+    }
     const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
     const de_lm_opts_t o = opts ? *opts : defaults;
     if (!p->in_cse.empty())
@@ -1197,11 +1237,11 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
         explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
         ~Nest() { c->nested--; }
     };
-    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    const de_loss_spec_t spec = *spec_in;
     {
         Nest nest(c);
-        const GnPlan gnA{jA, nullptr}, gnT{jT, nullptr};
-        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lA, dA, nullptr, okA, nullptr, true, &gnA);
+        const GnPlan gnA{jA, nullptr, e_floor}, gnT{jT, nullptr, e_floor};
+        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lA, dA, nullptr, okA, nullptr, false, &gnA);
         if (rc != DE_OK) return rc;
         HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
         HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist, c->stream));
@@ -1238,7 +1278,7 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
             for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
                 HIP_TRY(c, launch_lm_step(p->dtype, s, c->stream));
                 rc = set_consts_device_impl(p, cT);
-                if (rc == DE_OK) rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lT, dT, nullptr, okT, nullptr, true, &gnT);
+                if (rc == DE_OK) rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lT, dT, nullptr, okT, nullptr, false, &gnT);
                 if (rc != DE_OK) break;
                 a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
                 HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
@@ -1257,10 +1297,16 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
     if (h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DE_OK;
 }
+int de_fit_consts_lm_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                        const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                        double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept));
+}
 int de_fit_consts_lm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                      const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_lm");
-    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, opts, loss, ok, history, n_accept));
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    return de_fit_consts_lm_ex(c, p, X, N, ldX, pa, y, w, &spec, 0.0, opts, loss, ok, history, n_accept);
 }
 
 } // extern "C"

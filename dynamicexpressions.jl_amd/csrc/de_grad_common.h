@@ -57,6 +57,7 @@ template <typename T> struct GArgs {
     int32_t share;
     int64_t var_stride;
     T loss_param; // the parameter of a parameterised loss kind (de_loss_kinds.h), in T; 0 for the kinds that have none
+    T loss_floor; // Gauss-Newton tree ends: the residual floor of the kind's curvature weight (de_loss_kinds.h loss_kind_curv), in T
 };
 
 // Early exit at tree granularity (src/Evaluate.jl:26-32, src/EvaluateDerivative.jl:230-243: the reference returns at the first
@@ -289,6 +290,19 @@ template <typename T> __device__ __forceinline__ LossTerm<T> loss_term(int loss_
     if (wv == T(0)) { r.l = T(0); r.lp = T(0); }
     return r;
 }
+// A wave-uniform value that reached an out-of-line function in a vector register (the calling convention passes every argument in one):
+// back into scalar registers, so that it costs no vector register across the function's own calls and branches on it are scalar.
+__device__ __forceinline__ int guni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t guni(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+template <typename P> __device__ __forceinline__ const P *guni(const P *p) { return reinterpret_cast<const P *>((uintptr_t)guni((int64_t)(uintptr_t)p)); }
+__device__ __forceinline__ float guni(float v) { return __int_as_float(guni(__float_as_int(v))); }
+__device__ __forceinline__ double guni(double v) { return __longlong_as_double((long long)guni((int64_t)__double_as_longlong(v))); }
+// The curvature weight of one sample for the Gauss-Newton tree ends (de_loss_kinds.h loss_kind_curv; loss_mode != 1 + DE_LOSS_L2, whose
+// weight is 1 and whose tree ends keep the code they had): out of line like the loss table, f = GArgs::loss_floor.
+template <typename T> __device__ __noinline__ T loss_kind_curv_ool(int kind, T x, T yv, T p, T f) { return loss_kind_curv_term<T>(guni(kind), x, yv, guni(p), guni(f)); }
 
 // What a module of the threaded kernels (de_grad_threaded.hip: 18, de_rev_threaded.hip: 2) hands to the one launch path
 // (de_grad_kernels.hip): the host stubs of its handler-table fill kernel and of its kernel, kernel[PARAMS][SHARE] (the reverse kernel

@@ -26,7 +26,7 @@ namespace de {
 // One sample per thread; LDS rows of GBLK(+4) elements: rows [0,F) = X tile, then each spill
 // slot s owns 1+GC rows (x, d[0..GC)).
 // GN: the launch of de_eval_loss_gn — behind the loss and its gradient the tree end also reduces the products
-// sum_j w_j d_i(j) d_k(j), i <= k < G, of a tree whose rows lie in this one window (de_grad_threaded.hip g_epilogue_gn: same columns, same
+// sum_j w_j c_j d_i(j) d_k(j), i <= k < G (c = the loss kind's curvature weight, 1 for L2), of a tree whose rows lie in this one window (de_grad_threaded.hip g_epilogue_gn: same columns, same
 // association order).  A template parameter: the other instantiations keep the code they had.
 template <typename T, int GC, bool GN = false>
 __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
@@ -236,10 +236,13 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
             if constexpr (GN) {
                 if (g0 == 0 && G <= GC) {
                     T *__restrict__ pj = pp + (int64_t)(1 + G) * 4;
+                    // w c: the kind's curvature weight (de_loss_kinds.h loss_kind_curv); L2 keeps the plain weight it had
+                    T wc = wv;
+                    if (a.loss_mode != 1 + DE_LOSS_L2) wc = wv * loss_kind_curv_ool<T>(a.loss_mode - 1, x, yv, a.loss_param, a.loss_floor);
                     DE_UNROLL for (int k = 0; k < GC; k++) {
                         if (k < G) { // wave-uniform
                             DE_UNROLL for (int i = 0; i <= k; i++) {
-                                const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wv * d[i]) * d[k]);
+                                const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wc * d[i]) * d[k]);
                                 if ((tid & 63) == 63) pj[(k * (k + 1) / 2 + i) * 4] = s;
                             }
                         }
@@ -364,6 +367,7 @@ template <typename T> static GArgs<T> make_gargs(const GradArgs &ga) {
     if (ga.loss) {
         a.loss_mode = 1 + ga.loss->kind;
         a.loss_param = (T)ga.loss->param;
+        a.loss_floor = (T)ga.loss->e_floor;
         a.y = static_cast<const T *>(ga.loss->y);
         a.w = static_cast<const T *>(ga.loss->w);
         a.partial = static_cast<T *>(ga.loss->partial);

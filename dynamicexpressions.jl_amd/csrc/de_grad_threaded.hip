@@ -394,7 +394,7 @@ __device__ __noinline__ void g_epilogue_loss(GState<T, GC> st, const T *y, const
         }
     }
 }
-// Tree end of de_eval_loss_gn: the L2 loss and its gradient as g_epilogue_loss forms them, then the Gauss-Newton products
+// Tree end of de_eval_loss_gn under L2 (the other kinds: g_epilogue_gn_kind below): the L2 loss and its gradient as g_epilogue_loss forms them, then the Gauss-Newton products
 //   sum_j w_j d_i(j) d_k(j),  i <= k < G,
 // of a tree whose rows lie in this one window (g0 == 0 && G <= GC: every tree of at most de_gn_max_rows() rows), into the columns behind the
 // gradient's: entry (i, k) at 1 + G + k (k + 1) / 2 + i.  One association order, (w d_i) d_k, everywhere — scaling every weight by a power of
@@ -435,6 +435,73 @@ __device__ __noinline__ void g_epilogue_gn(GState<T, GC> st, const T *y, const T
                 DE_UNROLL for (int i = 0; i <= k; i++) {
                     T c = T(0);
                     DE_UNROLL for (int s = 0; s < VS; s++) c += wv[s] == T(0) ? T(0) : (wv[s] * st.d[i][s]) * st.d[k][s];
+                    const T sum = wave_sum_to_lane63(c);
+                    if (lane == 63) pj[(k * (k + 1) / 2 + i) * 4] = sum;
+                }
+            }
+        }
+    }
+}
+// The same tree end under any other loss kind, in two functions the kernel calls one after the other: the loss and
+// gradient columns as g_epilogue_loss forms them (loss_term with the launch's kind: de_eval_loss_grad_ex's bits), the products
+// ((w c) d_i) d_k with the kind's curvature weight c (de_loss_kinds.h loss_kind_curv).  g_gn_terms forms the per-sample terms, which need the
+// tree's value alone, and calls both tables out of line.  What it keeps across those calls lives in callee-saved registers — every second
+// block of eight from v40 on — and a kernel of this module is allotted the registers of the module's most expensive function, so it
+// takes neither the dual rows (they wait in the kernel) nor any wave-uniform argument in a vector register (guni).
+// g_epilogue_gn_kind then reduces the terms with the rows: a leaf, like g_epilogue_gn, that takes the rows alone and the terms one by one —
+// structs of more than 16 dwords in all leave the argument registers and travel through scratch memory.  L2 never comes here: it keeps
+// g_epilogue_gn, instruction for instruction.
+template <typename T> struct GnTerms {
+    T l;           // the lane's loss terms, summed over its samples
+    LV(T) lp, wv;  // w l' and w (0 past N) per sample
+    LV(T) wc;      // w c
+};
+template <typename T, int GC> struct GnRows { LV(T) d[GC]; };
+template <typename T, bool SHARE>
+__device__ __noinline__ GnTerms<T> g_gn_terms(LV(T) x, const T *y_, const T *w_, int64_t N_, int loss_mode_, T loss_param_, T loss_floor_, int64_t tile_) {
+    constexpr int TILE = GBLK * VS, WSAMP = 64 * VS;
+    const T *y = guni(y_), *w = guni(w_);
+    const int64_t last = guni(N_) - 1, tile = guni(tile_);
+    const int loss_mode = guni(loss_mode_);
+    const T loss_param = guni(loss_param_), loss_floor = guni(loss_floor_);
+    GnTerms<T> r;
+    r.l = T(0);
+    DE_UNROLL for (int i = 0; i < VS; i++) {
+        const int tid = threadIdx.x;
+        const int64_t j = (SHARE ? tile * WSAMP + (int64_t)(tid & 63) * VS : tile * TILE + (int64_t)tid * VS) + i;
+        const int64_t jj = j < last ? j : last;
+        const T yv = y[jj];
+        r.wv[i] = j <= last ? (w ? w[jj] : T(1)) : T(0);
+        const LossTerm<T> lt = loss_term<T>(loss_mode, x[i], yv, r.wv[i], loss_param);
+        r.lp[i] = lt.lp;
+        r.l += lt.l;
+        r.wc[i] = r.wv[i] * loss_kind_curv_ool<T>(loss_mode - 1, x[i], yv, loss_param, loss_floor);
+    }
+    return r;
+}
+template <typename T, int GC, bool SHARE>
+__device__ __noinline__ void g_epilogue_gn_kind(GnRows<T, GC> st, T l, LV(T) lp, LV(T) wv, LV(T) wc, T *pp, int G, int g0, int wave_of_tile) {
+    const int tid = threadIdx.x, wave = SHARE ? wave_of_tile : tid >> 6, lane = tid & 63;
+    pp += wave;
+    if (g0 == 0) {
+        const T s = wave_sum_to_lane63(l);
+        if (lane == 63) pp[0] = s;
+    }
+    DE_UNROLL for (int k = 0; k < GC; k++) {
+        if (g0 + k < G) { // wave-uniform
+            T c = T(0);
+            DE_UNROLL for (int i = 0; i < VS; i++) c += wv[i] == T(0) ? T(0) : lp[i] * st.d[k][i];
+            const T s = wave_sum_to_lane63(c);
+            if (lane == 63) pp[(int64_t)(1 + g0 + k) * 4] = s;
+        }
+    }
+    if (g0 == 0 && G <= GC) {
+        T *__restrict__ pj = pp + (int64_t)(1 + G) * 4;
+        DE_UNROLL for (int k = 0; k < GC; k++) {
+            if (k < G) { // wave-uniform
+                DE_UNROLL for (int i = 0; i <= k; i++) {
+                    T c = T(0);
+                    DE_UNROLL for (int s = 0; s < VS; s++) c += wv[s] == T(0) ? T(0) : (wc[s] * st.d[i][s]) * st.d[k][s];
                     const T sum = wave_sum_to_lane63(c);
                     if (lane == 63) pj[(k * (k + 1) / 2 + i) * 4] = sum;
                 }
@@ -592,7 +659,14 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
         DE_UNROLL for (int k = 0; k < GC; k++) gpoison<T>(poison, g0 + k < G ? st.d[k] : lv_splat<T>(T(0)));
         if constexpr (GN) {
             const int64_t n_cols = col_off[a.n_all_trees];
-            g_epilogue_gn<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, G, g0, (int64_t)tm.tile);
+            T *pp = a.partial + (ptile * n_cols + col_off[tree]) * 4;
+            if (a.loss_mode == 1 + DE_LOSS_L2) g_epilogue_gn<T, GC, SHARE>(st, a.y, a.w, pp, a.N, G, g0, (int64_t)tm.tile);
+            else {
+                GnRows<T, GC> rows_;
+                DE_UNROLL for (int k = 0; k < GC; k++) rows_.d[k] = st.d[k];
+                const GnTerms<T> t_ = g_gn_terms<T, SHARE>(st.x, a.y, a.w, a.N, a.loss_mode, a.loss_param, a.loss_floor, (int64_t)tm.tile);
+                g_epilogue_gn_kind<T, GC, SHARE>(rows_, t_.l, t_.lp, t_.wv, t_.wc, pp, G, g0, (int)(tm.tile & 3));
+            }
         } else if (a.loss_mode) {
             const int64_t n_cols = col_off[a.n_all_trees];
             g_epilogue_loss<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, a.loss_mode, a.loss_param, G, g0, (int64_t)tm.tile);

@@ -45,6 +45,7 @@ struct LossArgs {
     const void *w;    // device, N, or null (= 1)
     int32_t kind;     // de_loss_kind
     double param;     // the kind's parameter (de_loss_spec_t; 0 for the kinds that have none), converted to the element type at the launch
+    double e_floor;   // Gauss-Newton launches (GradArgs::gn): the residual floor of the kind's curvature weight (de_gn_spec_check), converted likewise
     void *partial;    // device scratch, loss_scratch_bytes().partial
     void *seg_sum;    // device scratch (double), loss_scratch_bytes().seg
     void *loss;       // device, n_trees values of the program's dtype

@@ -69,6 +69,49 @@ template <int KIND, typename T> __device__ __forceinline__ LossKindTerm<T> loss_
     }
     return r;
 }
+// The curvature weight c >= 0 of ONE sample under kind KIND: the Gauss-Newton tree ends sum w c d_i d_k, so that
+// (M + lam diag M) delta = -g / 2 is the damped generalised Gauss-Newton / IRLS step of the kind; c == 1 for L2.  2c = l'(e) / e, the IRLS
+// weight, for the distance kinds and the true l'' for the logistic margin.  f = the residual floor of the kinds whose weight is unbounded
+// at e = 0 (L1, L1_EPS, QUANTILE, LP with p < 2; already converted to T on the host, as p is); the others ignore it.  tanh(t) / t is 1 to
+// half an ulp below tau = 2^-12 (Float32) / 2^-27 (Float64): 1 - t^2 / 3 + ...
+template <typename T> __device__ __forceinline__ T lk_curv_tau() { return sizeof(T) == 4 ? T(0x1p-12) : T(0x1p-27); }
+template <int KIND, typename T> __device__ __forceinline__ T loss_kind_curv(T x, T y, T p, T f) {
+    const T e = x - y, ae = M<T>::abs(e);
+    if constexpr (KIND == DE_LOSS_L2) return T(1);
+    else if constexpr (KIND == DE_LOSS_L1) return T(1) / (T(2) * (ae > f ? ae : f));
+    else if constexpr (KIND == DE_LOSS_HUBER) return ae <= p ? T(0.5) : p / (T(2) * ae);
+    else if constexpr (KIND == DE_LOSS_LOGCOSH) return ae < lk_curv_tau<T>() ? T(0.5) : M<T>::tanh(e) / (T(2) * e);
+    else if constexpr (KIND == DE_LOSS_L1_EPS) return ae > p ? T(1) / (T(2) * (ae > f ? ae : f)) : T(0);
+    else if constexpr (KIND == DE_LOSS_L2_EPS) return ae > p ? (ae - p) / ae : T(0);
+    else if constexpr (KIND == DE_LOSS_QUANTILE) return M<T>::abs((e > T(0) ? T(1) : T(0)) - p) / (T(2) * (ae > f ? ae : f));
+    else if constexpr (KIND == DE_LOSS_LP) {
+        if (p == T(2)) return T(1);
+        return (p * lk_pow(p < T(2) && !(ae > f) ? f : ae, p - T(2))) * T(0.5);
+    } else if constexpr (KIND == DE_LOSS_LOGIT_DIST) {
+        const T h = T(0.5) * e;
+        return M<T>::abs(h) < lk_curv_tau<T>() ? T(0.25) : M<T>::tanh(h) / (T(4) * h);
+    } else {
+        static_assert(KIND == DE_LOSS_LOGIT_MARGIN, "a kind without a curvature: the host refuses it (de_gn_spec_check)");
+        const T a = y * x; // each sigmoid on its own: 1 - s(a) would cancel
+        const T s1 = T(1) / (T(1) + lk_exp(a)), s2 = T(1) / (T(1) + lk_exp(-a));
+        return (((y * y) * s1) * s2) * T(0.5);
+    }
+}
+// (the run-time kind is one the host admitted: neither DE_LOSS_PULLBACK nor DE_LOSS_L1_HINGE gets here)
+template <typename T> __device__ __forceinline__ T loss_kind_curv_term(int kind, T x, T y, T p, T f) {
+    switch (kind) {
+    case DE_LOSS_L1: return loss_kind_curv<DE_LOSS_L1, T>(x, y, p, f);
+    case DE_LOSS_HUBER: return loss_kind_curv<DE_LOSS_HUBER, T>(x, y, p, f);
+    case DE_LOSS_LOGCOSH: return loss_kind_curv<DE_LOSS_LOGCOSH, T>(x, y, p, f);
+    case DE_LOSS_L1_EPS: return loss_kind_curv<DE_LOSS_L1_EPS, T>(x, y, p, f);
+    case DE_LOSS_L2_EPS: return loss_kind_curv<DE_LOSS_L2_EPS, T>(x, y, p, f);
+    case DE_LOSS_QUANTILE: return loss_kind_curv<DE_LOSS_QUANTILE, T>(x, y, p, f);
+    case DE_LOSS_LP: return loss_kind_curv<DE_LOSS_LP, T>(x, y, p, f);
+    case DE_LOSS_LOGIT_DIST: return loss_kind_curv<DE_LOSS_LOGIT_DIST, T>(x, y, p, f);
+    case DE_LOSS_LOGIT_MARGIN: return loss_kind_curv<DE_LOSS_LOGIT_MARGIN, T>(x, y, p, f);
+    default: return loss_kind_curv<DE_LOSS_L2, T>(x, y, p, f);
+    }
+}
 // STMT with `KIND` = the compile-time constant of the run-time kind (the host admits no other: de_loss_spec_check)
 #define DE_LOSS_KIND_SWITCH(kind, STMT)                                        \
     switch (kind) {                                                            \

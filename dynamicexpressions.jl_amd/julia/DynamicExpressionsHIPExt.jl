@@ -777,21 +777,25 @@ function eval_population_loss_grad(
 end
 
 """
-    eval_population_gauss_newton(pop, X, y; weights=nothing, variable=Val(false))
+    eval_population_gauss_newton(pop, X, y; weights=nothing, variable=Val(false), loss=:L2, loss_param=0.0, e_floor=1e-4)
         -> (loss::Vector{T}, dloss::Vector{Vector{T}}, jtj::Vector{Matrix{T}}, ok, has_jtj)
 
-The normal equations of a Levenberg-Marquardt step for a whole population in one launch (`de_eval_loss_gn`): the L2 loss and its
-gradient exactly as `eval_population_loss_grad` returns them, and `jtj[t] = sum_j w_j d(j) d(j)'` over the gradient rows of
-`variable` (the Gauss-Newton Hessian of the loss is `2 jtj[t]`), without the `n_grad × N` Jacobian.  A tree of more than
+The normal equations of a Levenberg-Marquardt step for a whole population in one launch (`de_eval_loss_gn_ex`): the loss `loss` and its
+gradient exactly as `eval_population_loss_grad` returns them for the same kind, and `jtj[t] = sum_j w_j c_j d(j) d(j)'` over the gradient
+rows of `variable`, without the `n_grad × N` Jacobian.  `c_j` is the kind's curvature weight (1 for `:L2`, where the Gauss-Newton Hessian
+of the loss is `2 jtj[t]`; DESIGN.md §4.4.5) and `e_floor` the residual floor of the kinds whose weight is unbounded at a zero residual
+(`:L1`, `:l1_eps`, `:quantile`, `:lp` with p < 2).  `:l1_hinge` (`DE_ERR_UNSUPPORTED`) and `:pullback` have no such matrix.  A tree of more than
 `de_gn_max_rows()` rows in the library's per-occurrence layout has `has_jtj[t] == false` and a NaN matrix; its loss and gradient
 are filled as usual.  For a GraphNode the rows and columns of a shared constant are summed (`combine_rows` on both sides).
 """
 function eval_population_gauss_newton(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing, variable=Val(false),
+    loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
 ) where {T}
     mode = grad_mode(variable)
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
+    spec = loss_spec(loss, loss_param)
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
     dl, jt, ng, offs, joffs = with_pop(pop) do hc, hp
@@ -800,10 +804,11 @@ function eval_population_gauss_newton(
         dl = Vector{T}(undef, max(offs[end], 1))
         jt = Vector{T}(undef, max(joffs[end], 1))
         check(pop.ctx, GC.@preserve X y weights lossv dl jt offs joffs ok ccall(
-            (:de_eval_loss_gn, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid},
+            (:de_eval_loss_gn_ex, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble,
              Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
-            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), lossv, dl, offs, jt, joffs, ok))
+            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), spec, Float64(e_floor),
+            lossv, dl, offs, jt, joffs, ok))
         (dl, jt, ng, offs, joffs)
     end
     max_rows = ccall((:de_gn_max_rows, LIBDE), Cint, ())
@@ -860,10 +865,11 @@ function population_lm_step(
 end
 
 """
-    fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1)
+    fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1, loss=:L2, loss_param=0.0, e_floor=1e-4)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
-Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm`): it starts from the
+Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm_ex`), minimising the loss
+kind `loss` (the keywords of `eval_population_gauss_newton`; the damped generalised Gauss-Newton step of DESIGN.md §4.4.5): it starts from the
 constants `pop` holds (`set_population_constants!`), and per iteration solves the damped normal equations on the device, sets the trial
 constants there, evaluates, and accepts a tree's step when its loss decreased (`lam_t *= down`, floor 1e-12; else `lam_t *= up`).
 Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the accepted losses
@@ -872,23 +878,25 @@ with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrenc
 """
 function fit_population_constants_lm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
-    iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1,
+    iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1, loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
 ) where {T}
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
     any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lm!: shared GraphNode constants need the host loop"))
     opts = Ref(LmOpts(Int32(iters), Int32(0), Float64(lam0), Float64(up), Float64(down), 1e-12))
+    spec = loss_spec(loss, loss_param)
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
     history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
     n_accept = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
         check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
-            (:de_fit_consts_lm, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
+            (:de_fit_consts_lm_ex, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
              Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, lossv, ok, history, n_accept))
+            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), spec, Float64(e_floor), opts,
+            lossv, ok, history, n_accept))
     end
     constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
     return constants, lossv, ok .!= 0x00, history, n_accept

@@ -80,7 +80,9 @@ extern "C" {
  *      (g) de_lower_tape_assured, stage 4 of de_lower_tape_stage and words 5 / 6 and which = 4 of de_program_dump: the assured
  *      stream of Float32 programs.
  *      (h) de_gn_lm_step, de_fit_consts_lm (with de_lm_opts_t) and the host-only hook de_lm_solve_host: Levenberg-Marquardt on the
- *      constants of a population on the device, DE_F32 / DE_F64. */
+ *      constants of a population on the device, DE_F32 / DE_F64.
+ *      (i) de_gn_spec_check, de_eval_loss_gn_ex, de_fit_consts_lm_ex: the Gauss-Newton matrix and the fit under every loss kind that has a
+ *      curvature; de_eval_loss_gn and de_fit_consts_lm forward to them with {DE_LOSS_L2, 0, 0}: the same bits. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -518,7 +520,8 @@ int de_eval_loss_grad_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64
                          const de_loss_spec_t *spec, void *loss, void *dloss, const int64_t *dloss_offsets,
                          uint8_t *ok);
 
-/* Fused Gauss-Newton normal equations per tree (Levenberg-Marquardt on constants), L2 only:
+/* Fused Gauss-Newton normal equations per tree (Levenberg-Marquardt on constants), under L2 (any other kind:
+ * de_eval_loss_gn_ex below):
  *   loss[t]                 = sum_j w_j e_j^2,   dloss[off_t + k] = sum_j 2 w_j e_j d_k(j)      (exactly de_eval_loss_grad, DE_LOSS_L2: same bits)
  *   jtj[joff_t + i + G_t k] = sum_j w_j d_i(j) d_k(j)       (G_t x G_t, column-major, BOTH triangles written, exactly symmetric)
  * e_j = tree_t(x_j) - y_j, d_k = d tree_t(x_j) / d theta_k over the gradient rows of `mode`, in de_eval_grad's order,
@@ -536,6 +539,35 @@ int de_eval_loss_gn(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N,
                     void *loss, void *dloss, const int64_t *dloss_offsets,
                     void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
 int de_gn_max_rows(void); /* 8 */
+
+/* The same under any loss kind that has a curvature: generalised Gauss-Newton / iteratively reweighted least squares.
+ *   loss[t], dloss[..]      = de_eval_loss_grad_ex's for the same spec, bit for bit
+ *   jtj[joff_t + i + G_t k] = M[i, k] = sum_j w_j c_j d_i(j) d_k(j)
+ * c_j >= 0 is the kind's curvature weight of sample j, formed in the element type from e = yhat - y (a = y * yhat for the margin kind),
+ * the kind's parameter p and the residual floor f = e_floor, both converted to the element type:
+ *   DE_LOSS_L2            1                                          DE_LOSS_L1            1 / (2 max(|e|, f))
+ *   DE_LOSS_HUBER         |e| <= delta ? 1/2 : delta / (2 |e|)       DE_LOSS_LOGCOSH       |e| < tau ? 1/2 : tanh(e) / (2 e)
+ *   DE_LOSS_L1_EPS        |e| > eps ? 1 / (2 max(|e|, f)) : 0        DE_LOSS_L2_EPS        |e| > eps ? (|e| - eps) / |e| : 0
+ *   DE_LOSS_QUANTILE      |(e > 0) - tau_q| / (2 max(|e|, f))        DE_LOSS_LOGIT_DIST    h = e / 2; |h| < tau ? 1/4 : tanh(h) / (4 h)
+ *   DE_LOSS_LP            p < 2 ? p max(|e|, f)^(p - 2) / 2 : p |e|^(p - 2) / 2   (exactly 1 at p = 2)
+ *   DE_LOSS_LOGIT_MARGIN  y^2 s(a) s(-a) / 2,  s(a) = 1 / (1 + exp(a))
+ * (tau = 2^-12 for DE_F32, 2^-27 for DE_F64).  2c is the IRLS weight l'(e) / e of a distance kind and the true l'' of the logistic
+ * margin, so (M + lam diag M) delta = -dloss / 2 is the damped step of the kind: for de_gn_lm_step and de_lm_solve_host, H is M.
+ * Everything else — offsets, symmetry, NaN fills, zero weights, staging, the refusals for DE_F16 / complex programs — is
+ * de_eval_loss_gn's, which is this call with {DE_LOSS_L2, 0, 0} and e_floor = 0.
+ *
+ * de_gn_spec_check (host only, no context): DE_OK for a spec these calls take; DE_ERR_UNSUPPORTED for DE_LOSS_L1_HINGE (no curvature, and
+ * the IRLS weight of a margin is no majoriser); DE_ERR_INVALID_ARG for a null spec, DE_LOSS_PULLBACK, an unknown kind, a parameter
+ * outside its range (de_loss_spec_check) and — for DE_LOSS_L1, DE_LOSS_L1_EPS, DE_LOSS_QUANTILE and DE_LOSS_LP with p < 2, the kinds that
+ * read the floor — an e_floor that is not finite and > 0.  The other kinds ignore e_floor: any value is accepted.  The entry points
+ * apply the same check and, knowing the element type, also refuse a floor that rounds to 0 in it (1e-60 for DE_F32); all of it before
+ * any output or constant is touched.  The floor bounds the weight of a sample with a tiny residual; de_fit_consts_lm_ex only takes
+ * steps that lower the loss, so it affects how fast a fit proceeds, not what it may return. */
+int de_gn_spec_check(const de_loss_spec_t *spec, double e_floor);
+int de_eval_loss_gn_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                       const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                       const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets,
+                       void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
 
 /* Levenberg-Marquardt on the constants, on the device.
  *
@@ -566,7 +598,12 @@ int de_gn_max_rows(void); /* 8 */
  * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED for a DE_F16 / complex program, a program made by
  * de_program_create_cse (its occurrence rows need the S H S^T fold of the caller: the host loop) and a tree whose constant rows differ
  * from its constants; DE_ERR_INVALID_ARG for a null y / ok on a non-empty population, iters < 0, reserved != 0 or a lam0 / up / down /
- * lam_min that is not finite and positive. */
+ * lam_min that is not finite and positive.
+ *
+ * de_fit_consts_lm_ex: the same loop under any kind de_gn_spec_check admits: every evaluation is de_eval_loss_gn_ex
+ * with (spec, e_floor), the step, the accept rule, the trial constants and the history are unchanged, and afterwards
+ * de_eval_loss_grad_ex with the same spec reproduces loss[t] bit for bit.  A spec or floor de_gn_spec_check refuses is refused here
+ * with the same code, before any output or constant is touched.  de_fit_consts_lm is this call with {DE_LOSS_L2, 0, 0}. */
 typedef struct de_lm_opts {
     int32_t iters;
     int32_t reserved; /* 0 */
@@ -577,6 +614,9 @@ int de_gn_lm_step(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_gr
 int de_fit_consts_lm(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                      const void *y, const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history,
                      int32_t *n_accept);
+int de_fit_consts_lm_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                        const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts,
+                        void *loss, uint8_t *ok, double *history, int32_t *n_accept);
 int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:

@@ -5,8 +5,9 @@ process.  Populations of 1000 and 10^4 trees c0 * cos(c1 * x1) + c2 (3 constants
 fits alternate (device, host, device, host ...), every fit from the same starting constants; per leg the median over its fits of
   wall ms / iteration   host clock around the call, the stream synchronised before and after, divided by the 10 iterations
   device ms / iteration the context's event ring over the fit (one entry for the device loop; the host loop's evaluations summed)
+--loss / --loss-param: the loss kind both legs minimise (api.LOSS_KINDS), L2 by default.
 One JSON line per (trees, dtype, leg), then a table.  There is no CPU fallback: without a GPU the script fails.
-    python tools/bench_fit_lm.py [--reps 3] [--warmup 1] [--samples 100000] [--iters 10] [--trees 1000,10000]"""
+    python tools/bench_fit_lm.py [--reps 3] [--warmup 1] [--samples 100000] [--iters 10] [--trees 1000,10000] [--loss huber] [--loss-param 1.0]"""
 import argparse
 import json
 import os
@@ -23,6 +24,8 @@ def main():
     ap.add_argument("--samples", type=int, default=10**5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--trees", default="1000,10000")
+    ap.add_argument("--loss", default="L2")
+    ap.add_argument("--loss-param", type=float, default=0.0)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -33,6 +36,7 @@ def main():
         raise SystemExit("tools/bench_fit_lm.py needs a GPU (no CPU fallback)")
     ops = de.OperatorEnum(binary_operators=("+", "-", "*", "/"), unary_operators=("cos", "exp"))
     ctx = api.Context(0)
+    kind = {} if a.loss == "L2" else dict(loss=a.loss, loss_param=a.loss_param)  # (L2: the call as it always was)
     N = a.samples
     g = np.random.default_rng(0)
     x = g.uniform(-2, 2, N)
@@ -58,9 +62,9 @@ def main():
                 ctx.timing_ring(4 * a.iters + 8)
                 t0 = time.perf_counter()
                 if leg == "device":
-                    consts, loss, ok = pop.fit_constants_lm_device(X, y, c0d, iters=a.iters)
+                    consts, loss, ok = pop.fit_constants_lm_device(X, y, c0d, iters=a.iters, **kind)
                 else:
-                    consts, loss, ok = pop.fit_constants_lm(X, y, c0, iters=a.iters)
+                    consts, loss, ok = pop.fit_constants_lm(X, y, c0, iters=a.iters, **kind)
                 ctx.synchronize()
                 wall = (time.perf_counter() - t0) * 1e3
                 dev = ctx.timing_read()
@@ -76,7 +80,7 @@ def main():
                     got[leg].append(fit(leg))
             for leg, runs in got.items():
                 wall, dev = np.median([r[0] for r in runs]), np.median([r[1] for r in runs])
-                row = dict(leg=leg, trees=n_trees, dtype=np.dtype(dtype).name, N=N, iters=a.iters, reps=a.reps,
+                row = dict(leg=leg, loss=a.loss, loss_param=a.loss_param, trees=n_trees, dtype=np.dtype(dtype).name, N=N, iters=a.iters, reps=a.reps,
                            wall_ms_per_iter=round(float(wall) / max(a.iters, 1), 4), device_ms_per_iter=round(float(dev) / max(a.iters, 1), 4),
                            wall_ms_min=round(min(r[0] for r in runs) / max(a.iters, 1), 4), wall_ms_max=round(max(r[0] for r in runs) / max(a.iters, 1), 4),
                            timed_calls=runs[0][2], median_final_loss=runs[0][3])

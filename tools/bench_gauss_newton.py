@@ -5,9 +5,15 @@ of --steps calls that is synchronised once, when the ring is read; the median of
 gradient's of the same run, the bytes of the per-tile partial buffer and the share of trees that get a matrix (has_jtj).
 At --jac-samples (10^5, where the Jacobian fits) the alternative is timed as well: de_eval_grad, then the matrices by torch — the trees
 of one width gathered into a [n, N, G] batch and multiplied by torch.bmm — between two events on the stream, median of --steps.
+--loss names further loss kinds (api.LOSS_KINDS, comma-separated): behind the L2 rows each adds its own pair, the loss
+gradient of the kind (de_eval_loss_grad_ex) and its Gauss-Newton matrix (de_eval_loss_gn_ex, residual floor 1e-4), with the ratio between
+the two; --loss-param is the parameter of every such kind that takes one (default: 1).  The L2 rows always run, through the entry points
+they always ran through.
 One JSON line per row, then a table.  There is no CPU fallback: without a GPU the script fails.
-    python tools/bench_gauss_newton.py [--steps 10] [--warmup 3] [--samples 1000000] [--jac-samples 100000] [--trees 1000]"""
+    python tools/bench_gauss_newton.py [--steps 10] [--warmup 3] [--samples 1000000] [--jac-samples 100000] [--trees 1000]
+                                       [--loss huber,logcosh,L1] [--loss-param 1.0]"""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -22,6 +28,8 @@ def main():
     ap.add_argument("--samples", type=int, default=10**6)
     ap.add_argument("--jac-samples", type=int, default=10**5)
     ap.add_argument("--trees", type=int, default=1000)
+    ap.add_argument("--loss", default="")
+    ap.add_argument("--loss-param", type=float, default=1.0)
     a = ap.parse_args()
     if a.steps < 10:
         raise SystemExit("--steps must be at least 10 (the median of a window)")
@@ -35,6 +43,8 @@ def main():
     lib = api.library()
     ctx = api.Context(0)
     trees = de.synth.random_population(a.trees, seed=0xDE02)
+    kinds = [k for k in a.loss.split(",") if k and k != "L2"]
+    specs = {k: api.gn_loss_spec(k, a.loss_param, 1e-4) for k in kinds}  # (an unknown or unsupported kind fails here)
     rows = []
     for dtype, tdt in ((np.float32, torch.float32), (np.float64, torch.float64)):
         es = np.dtype(dtype).itemsize
@@ -50,7 +60,8 @@ def main():
         jt = torch.empty(max(int(joff[-1]), 1), device="cuda", dtype=tdt)
         ok = torch.empty(len(trees), device="cuda", dtype=torch.uint8)
         base = {}
-        for N, whats in ((a.samples, ("loss grad L2", "gauss newton")), (a.jac_samples, ("loss grad L2", "gauss newton", "eval_grad + bmm"))):
+        kind_rows = tuple(w for k in kinds for w in (f"loss grad {k}", f"gauss newton {k}"))
+        for N, whats in ((a.samples, ("loss grad L2", "gauss newton") + kind_rows), (a.jac_samples, ("loss grad L2", "gauss newton", "eval_grad + bmm"))):
             X = torch.from_numpy(np.ascontiguousarray(de.synth.random_X(5, N, seed=1, dtype=dtype).T)).cuda().t()  # bench.py's X
             y = torch.randn(N, generator=g, device="cuda", dtype=tdt)
             n_tiles = (N + 255) // 256
@@ -86,6 +97,13 @@ def main():
                         if what == "loss grad L2":
                             ctx.check(lib.de_eval_loss_grad(ctx._h, pop._h, X.data_ptr(), N, 5, None, 1, y.data_ptr(), None, 0, lossv.data_ptr(),
                                                             dl.data_ptr(), None, ok.data_ptr()))
+                        elif what.startswith("loss grad "):
+                            ctx.check(lib.de_eval_loss_grad_ex(ctx._h, pop._h, X.data_ptr(), N, 5, None, 1, y.data_ptr(), None,
+                                                               C.byref(specs[what[10:]]), lossv.data_ptr(), dl.data_ptr(), None, ok.data_ptr()))
+                        elif what != "gauss newton":
+                            ctx.check(lib.de_eval_loss_gn_ex(ctx._h, pop._h, X.data_ptr(), N, 5, None, 1, y.data_ptr(), None,
+                                                             C.byref(specs[what[13:]]), 1e-4, lossv.data_ptr(), dl.data_ptr(), None,
+                                                             jt.data_ptr(), None, ok.data_ptr()))
                         else:
                             ctx.check(lib.de_eval_loss_gn(ctx._h, pop._h, X.data_ptr(), N, 5, None, 1, y.data_ptr(), None, lossv.data_ptr(),
                                                           dl.data_ptr(), None, jt.data_ptr(), None, ok.data_ptr()))
@@ -98,9 +116,10 @@ def main():
                     ms = ctx.timing_read()  # (waits for the last call: the window's one synchronisation)
                     ctx.timing_ring(0)
                     assert len(ms) == a.steps, (len(ms), a.steps)
-                    partial = n_tiles * (n_cols_gn if what == "gauss newton" else n_cols_grad) * 4 * es
+                    partial = n_tiles * (n_cols_gn if what.startswith("gauss newton") else n_cols_grad) * 4 * es
                 med = float(np.median(ms))
-                base.setdefault(N, med)  # the loss gradient comes first
+                if what.startswith("loss grad "):  # the loss gradient of a kind comes before its matrix
+                    base[N] = med
                 okh = ok.cpu().numpy().astype(bool)
                 row = dict(what=what, dtype=np.dtype(dtype).name, N=N, trees=len(trees), ms=round(med, 4), ms_min=round(min(ms), 4),
                            ms_max=round(max(ms), 4), ratio_to_loss_grad=round(med / base[N], 4), steps=a.steps, complete_trees=int(okh.sum()),
@@ -110,9 +129,9 @@ def main():
                 rows.append(row)
             del X, y
         pop.close()
-    print(f"\n{'what':16s} {'dtype':8s} {'N':>9s} {'ms':>9s} {'min':>9s} {'max':>9s} {'/ grad':>7s} {'scratch MB':>11s} {'has_jtj':>8s}")
+    print(f"\n{'what':24s} {'dtype':8s} {'N':>9s} {'ms':>9s} {'min':>9s} {'max':>9s} {'/ grad':>7s} {'scratch MB':>11s} {'has_jtj':>8s}")
     for r in rows:
-        print(f"{r['what']:16s} {r['dtype']:8s} {r['N']:9d} {r['ms']:9.3f} {r['ms_min']:9.3f} {r['ms_max']:9.3f} {r['ratio_to_loss_grad']:7.3f} "
+        print(f"{r['what']:24s} {r['dtype']:8s} {r['N']:9d} {r['ms']:9.3f} {r['ms_min']:9.3f} {r['ms_max']:9.3f} {r['ratio_to_loss_grad']:7.3f} "
               f"{r['scratch_bytes'] / 1e6:11.1f} {r['has_jtj_share']:8.3f}")
 
 
