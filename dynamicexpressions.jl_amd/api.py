@@ -52,7 +52,7 @@ EXPORTS = [
     "de_dist_broadcast", "de_dist_gather_flags", "de_dist_last_error", "de_ctx_last_kernel_ms", "de_ctx_last_kernel_name",
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
-    "de_lower_tape_assured", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
+    "de_lower_tape_assured", "de_lower_tape_assured_parts", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
     "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex",
 ]
 
@@ -373,6 +373,9 @@ def library() -> C.CDLL:
     if hasattr(lib, "de_lower_tape_assured"):  # (absent from a library built before the assured stream: DE_HIP_LIB in an A/B run)
         lib.de_lower_tape_assured.restype = i64
         lib.de_lower_tape_assured.argtypes = [vp, i64, vp, i64, i32, u32, C.c_double, vp, i64]
+    if hasattr(lib, "de_lower_tape_assured_parts"):
+        lib.de_lower_tape_assured_parts.restype = i64
+        lib.de_lower_tape_assured_parts.argtypes = [vp, i64, vp, i64, i32, u32, C.c_double, u32, vp, i64]
     lib.de_lower_tape_grad.restype = i64
     lib.de_lower_tape_grad.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, C.c_int, C.c_int, vp, i64, vp]
     lib.de_eval.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, i64, vp]
@@ -674,19 +677,23 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     return w[:int(n)].reshape(-1, 4)
 
 
-def lower_tape_assured(tape, consts, n_features: int, xmax: float = 64.0, options: int = 7) -> np.ndarray:
+def lower_tape_assured(tape, consts, n_features: int, xmax: float = 64.0, options: int = 7, parts: Optional[int] = None) -> np.ndarray:
     """Host-only: the interval pass of the assured stream over one float32 tape (``de_lower_tape_assured``): [n fused instructions, 6]
-    float64 {lo, hi, amin, finite, assured handler id, elision bits} — the accumulator behind each instruction of the stage-3 words."""
+    float64 {lo, hi, amin, finite, assured handler id, elision bits} — the accumulator behind each instruction of the stage-3 words.
+    ``parts``: the parts of the pass (``de_lower_tape_assured_parts``; a ``DE_ASSURED_PARTS`` mask); None: the first three, 7."""
     lib = library()
     tape = np.ascontiguousarray(tape)
     consts = np.ascontiguousarray(consts, dtype=np.float32)
     cp = consts.ctypes.data if consts.size else None
     args = (tape.ctypes.data, len(tape), cp, consts.size, n_features, options, float(xmax))
-    n = lib.de_lower_tape_assured(*args, None, 0)
+    fn = lib.de_lower_tape_assured
+    if parts is not None:
+        fn, args = lib.de_lower_tape_assured_parts, args + (int(parts),)
+    n = fn(*args, None, 0)
     if n < 0:
         raise ValueError(lib.de_status_string(int(-n)).decode())
     w = np.zeros(max(int(n), 1), dtype=np.float64)
-    lib.de_lower_tape_assured(*args, w.ctypes.data, w.size)
+    fn(*args, w.ctypes.data, w.size)
     return w[:int(n)].reshape(-1, 6)
 
 

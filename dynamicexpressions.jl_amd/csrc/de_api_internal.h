@@ -180,7 +180,7 @@ struct de_program {
     std::vector<BoundInstr> ccode_w;
     // The ASSURED stream (de_bind.h assure_tree): Float32, non-parametric, exact-mode programs with one-wave workgroups
     // keep ONE more variant of the chained stream in ccode_w — the same records, but validity tests that cannot fire on a tile of ordinary
-    // feature values (|x| in [2^-40, assured_xmax]) are left out by naming the untested twin handlers (aids: the twin id of every fused
+    // feature values (|x| in [2^-39, assured_xmax]) are left out by naming the untested twin handlers (aids: the twin id of every fused
     // instruction).  It lies var_stride records behind the guarded stream like a wave's variant; a workgroup whose tile passes the test
     // runs it.  assured_cfg: 0 not decided yet, 1 wanted, -1 off (DE_ASSURED=0), read once when the program is created.
     // assured_valid: false behind a de_program_set_consts_device (the host cannot see the values: launches use the guarded stream until a

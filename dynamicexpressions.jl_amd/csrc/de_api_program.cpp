@@ -184,7 +184,7 @@ static double assured_xmax_env() {
     const double xm = ax ? (double)(float)atof(ax) : 64.0;
     return (xm >= 0x1p-40 && xm <= 0x1p100) ? xm : 64.0;
 }
-// DE_ASSURED_PARTS: which tests the pass may elide (de_bind.h ASSURED_PART_*; default: the parts that measured faster, TUNING_LOG.md)
+// DE_ASSURED_PARTS: which tests the pass may elide (de_bind.h ASSURED_PART_*; default: the parts that measured faster)
 static uint32_t assured_parts_env() {
     const char *ap = getenv("DE_ASSURED_PARTS");
     const int v = ap && *ap ? atoi(ap) : (int)ASSURED_PARTS_SHIPPED;
@@ -468,8 +468,9 @@ static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb,
         for (int32_t i = i0; i < i1; i++) {
             const uint32_t id = info[(size_t)(i - i0)].id;
             p->aids[(size_t)i] = id;
-            if (i == i1 - 1 && ev >= 0) continue; // (the end-fused handler, as in the guarded stream)
-            const uint64_t handler = id == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[id];
+            // (an end-fused last instruction: the end-fused twin of its assured id, or the end-fused handler of the guarded stream)
+            const uint64_t handler = (i == i1 - 1 && ev >= 0) ? (topx_enda_of(id) >= 0 && id != p->fbcode[(size_t)i].bop ? table[TOPX_ENDA_BASE + (uint32_t)topx_enda_of(id)] : p->endv_handler[ev])
+                                     : id == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[id];
             if (i > i0) name_next(cw[h + (size_t)(i - i0) - 1], handler);
             else {
                 name_next(cw[h - 1], handler);
@@ -2010,7 +2011,7 @@ int de_program_verify(const de_program_t *p) {
                     if (p->assured_valid && id != p->aids[(size_t)i]) return bad("assured stream: stale twin id", t, i - i0, p->aids[(size_t)i]);
                     const uint32_t have = p->aids[(size_t)i];
                     if (have >= TOPX_COUNT) return bad("assured stream: handler id", t, i - i0, have);
-                    const uint64_t want = (i == i1 - 1 && ev >= 0) ? p->endv_handler[ev]
+                    const uint64_t want = (i == i1 - 1 && ev >= 0) ? (topx_enda_of(have) >= 0 && have != p->fbcode[(size_t)i].bop ? table[TOPX_ENDA_BASE + (uint32_t)topx_enda_of(have)] : p->endv_handler[ev])
                                           : (have == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[have]);
                     if (named(cw[(size_t)(h + (i - i0) - 1)]) != want) return bad("assured stream: handler word", t, i - i0, named(cw[(size_t)(h + (i - i0) - 1)]));
                 }
@@ -2153,9 +2154,15 @@ static int64_t lower_tape_impl(int dtype, const de_tape_node_t *nodes, int64_t n
 }
 
 // Host-only: the interval pass of the assured stream over ONE Float32 tape (de_bind.h assure_tree) — per fused instruction six doubles
-// {lo, hi, amin, proven finite (0 / 1), assured handler id, elision bits (ASSURED_OUT | ASSURED_ROW)}: the accumulator behind it.
+// {lo, hi, amin, proven finite (0 / 1), assured handler id, elision bits (ASSURED_*)}: the accumulator behind it.
 int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
-                              uint32_t options, double xmax, double *out, int64_t cap) {
+                              uint32_t options, double xmax, double *out, int64_t cap) { // (the first three parts, whatever the environment says)
+    return de_lower_tape_assured_parts(nodes, n_nodes, consts, n_consts, n_features, options, xmax, ASSURED_PARTS_CLASSIC, out, cap);
+}
+// ... with the parts of the pass (ASSURED_PART_*, de_bind.h) given by the caller
+int64_t de_lower_tape_assured_parts(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
+                                    uint32_t options, double xmax, uint32_t parts, double *out, int64_t cap) {
+    if (parts & ~ASSURED_PARTS_ALL) return -DE_ERR_INVALID_ARG;
     if (!(xmax >= 0x1p-40 && xmax <= 0x1p100)) return -DE_ERR_INVALID_ARG;
     int64_t nw = lower_tape_stage_impl(DE_F32, nodes, n_nodes, consts, n_consts, n_features, 0, options, 3, nullptr, 0);
     if (nw < 0) return nw;
@@ -2166,7 +2173,7 @@ int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, cons
         const int64_t n = (int64_t)f.size() * 6;
         if (!out || cap < n) return n;
         std::vector<AssuredInstr> info(f.size());
-        assure_tree(f.data(), f.size(), n_features, xmax, info.data());
+        assure_tree(f.data(), f.size(), n_features, xmax, info.data(), parts);
         for (size_t i = 0; i < f.size(); i++) {
             double *o = out + 6 * i;
             o[0] = info[i].acc.lo; o[1] = info[i].acc.hi; o[2] = info[i].acc.amin; o[3] = info[i].acc.fin ? 1.0 : 0.0;

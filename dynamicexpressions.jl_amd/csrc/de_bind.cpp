@@ -293,7 +293,8 @@ AssuredVal a_un(int k, const AssuredVal &x) {
 void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts) {
     static thread_local std::vector<AssuredVal> slots; // rows >= n_features an instruction of THIS tree has written
     slots.clear();
-    const AssuredVal feature{-xmax, xmax, 0x1p-40, true};
+    // (the feature bound: what the tile test guarantees, taken only with the new part — the classic parts keep their intervals id for id)
+    const AssuredVal feature{-xmax, xmax, (parts & ASSURED_PART_FUSED_DIV) ? 0x1p-39 : 0x1p-40, true};
     auto row_val = [&](uint32_t row) -> AssuredVal {
         if (row < (uint32_t)n_features) return feature;
         const size_t s = row - (uint32_t)n_features;
@@ -364,7 +365,9 @@ void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, Ass
             bool outc = ((v >> 1) & 1) != 0;
             if (psh) push(prow, acc);
             const AssuredVal x = row_val(row);
-            acc = a_bin((int)(v >> 3), x, cst ? a_const(b.lo) : row_val((uint32_t)((int32_t)row + (int32_t)b.lo)));
+            div_acc = x; // (the two halves of a TOP_BIN2 division: row A, and row B or the constant)
+            div_row = cst ? a_const(b.lo) : row_val((uint32_t)((int32_t)row + (int32_t)b.lo));
+            acc = a_bin((int)(v >> 3), x, div_row);
             if (validity && outc && acc.fin) { outc = false; bits |= ASSURED_OUT; }
             twin = top_bin2((int)(v >> 3), cst, outc, psh);
         } else if (id == BOP_GEN_CONST && ((b.arg >> 24) == (uint32_t)DE_U_COS || (b.arg >> 24) == (uint32_t)DE_U_EXP)) {
@@ -387,12 +390,21 @@ void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, Ass
                 twin = topa_div((int)(v >> 2), var, (var & 2) ? 0u : ((ia ? 0u : 1u) | (ir ? 0u : 2u)));
                 bits |= (ia ? ASSURED_DIV_ACC : 0u) | (ir ? ASSURED_DIV_ROW : 0u);
             }
+        } else if ((parts & ASSURED_PART_FUSED_DIV) && twin >= top_bin2(4, false, false, false) && twin < TOP_COUNT) {
+            const uint32_t v = twin - TOP_BIN2_BASE;
+            const bool cst = ((v >> 2) & 1) != 0;
+            const bool ia = half_idle(div_acc), ib = cst ? false : half_idle(div_row); // (a constant operand keeps its scalar test)
+            if (ia && (cst || ib) && topa_div2_has((int)(v >> 3), cst)) { // (the twins test neither row)
+                twin = topa_div2((int)(v >> 3), cst, ((v >> 1) & 1) != 0, (v & 1) != 0);
+                bits |= ASSURED_DIV_A | (ib ? ASSURED_DIV_B : 0u);
+            }
         }
         out[i].acc = acc;
         out[i].id = twin;
         out[i].bits = bits;
     }
-    if (n >= 2 && topx_endv_of(f[n - 1].bop) >= 0) { // the end-fused last instruction: the twin has no such form
+    // the end-fused last instruction: its twin's end-fused form (TOPX_ENDA_BASE) with ASSURED_PART_END, the guarded one otherwise
+    if (n >= 2 && topx_endv_of(f[n - 1].bop) >= 0 && (!(parts & ASSURED_PART_END) || topx_enda_of(out[n - 1].id) < 0)) {
         out[n - 1].id = f[n - 1].bop;
         out[n - 1].bits = 0;
     }

@@ -181,9 +181,20 @@ constexpr uint32_t TOPA_UN_BASE = TOPX_BIN_BASE + 4;        // + k * 4 + var    
 constexpr uint32_t TOPA_UNROW_BASE = TOPA_UN_BASE + 8;      // + ((k*2 + out)*2 + push)*2 + chk   k < 2, as TOP_UNROW_BASE               (16)
 constexpr uint32_t TOPA_DIV_BASE = TOPA_UNROW_BASE + 16;    // + ((k - 4) * 4 + var) * 3 + m      k = DIV, RDIV; var as BOP_BIN_BASE;
                                                             //   m = the halves still tested: 0 none, 1 the accumulator, 2 the row  (24)
-constexpr uint32_t TOPX_COUNT = TOPA_DIV_BASE + 24;
+// ... the same for the divisions among the superinstructions (ASSURED_PART_FUSED_DIV; behind the ids above, which keep their values):
+// (TOP_BINROWC needs none: it tests a LEAF row, which the validity part always proves — the instruction becomes the plain row form above)
+constexpr uint32_t TOPA_DIV2_BASE = TOPA_DIV_BASE + 24;     // + (((k - 4)*2 + const)*2 + out)*2 + push     TOP_BIN2, k = DIV, RDIV: neither row tested  (16)
+constexpr uint32_t TOPX_COUNT = TOPA_DIV2_BASE + 16;
 constexpr uint32_t topa_un(int k, uint32_t var) { return TOPA_UN_BASE + (uint32_t)k * 4 + var; }
 constexpr uint32_t topa_div(int k, uint32_t var, uint32_t m) { return TOPA_DIV_BASE + ((uint32_t)(k - 4) * 4 + var) * 3 + m; }
+// The TOP_BIN2 twins test NEITHER row, and the pass names one only when BOTH rows are proven (or the one beside a constant).  A division
+// with exactly one proven row keeps its guarded id — sound, and no twin is lost that a stream has been seen to want: row A is loaded by
+// the instruction itself, row B is a leaf or the slot the same instruction has just spilled, and a slot row that an EARLIER instruction
+// wrote is divided through the plain forms (TOPA_DIV_BASE, which do have the half-tested twins); over 3 600 random trees and every mask
+// of parts no TOP_BIN2 division had one row proven and the other not.  Nor does the lowering mirror a row / row division (k = DIV only:
+// the four k = RDIV row / row slots hold the guarded handler and assure_tree does not name them).  A constant keeps its scalar test.
+constexpr bool topa_div2_has(int k, bool cst) { return cst || k == 4; }
+constexpr uint32_t topa_div2(int k, bool cst, bool out, bool push) { return TOPA_DIV2_BASE + (((uint32_t)(k - 4) * 2 + cst) * 2 + out) * 2 + push; }
 // handler table of the threaded eval kernel: the ids above + the end-of-tree handler every chain finishes in
 constexpr uint32_t TOPX_END = TOPX_COUNT;
 // ... and "last instruction of a tree + its end" variants of the handlers most trees finish in (a validity-tested hot binary or
@@ -192,7 +203,29 @@ constexpr uint32_t TOPX_ENDV_BASE = TOPX_END + 1;                 // + k * 2 + (
 constexpr uint32_t TOPX_ENDV_COUNT = 15;
 // ... and two handlers no record names but every chain can reach (the out-of-line end of a tree, the early-exit walk over skipped
 // trees): in the table so that the host's address-window checks (32-bit offsets; Float64: one 4 GiB window) cover them too
-constexpr uint32_t TOPX_AUX_BASE = TOPX_ENDV_BASE + TOPX_ENDV_COUNT; // + 0: h_tree_end_slow, + 1: h_tree_skip
+// ... and their ASSURED twins (ASSURED_PART_END): the end-fused handler of the last instruction's assured id — without the validity test, the
+// cos / exp pre-test, the division halves the interval pass proved idle.  No stream id of their own: the last instruction carries its plain
+// assured id (what assure_tree reports), and where that id has a slot here the assured stream names this handler instead of TOPX_ENDV's.
+//   + k * 2 + const, k < 6                    the hot binary operator without the validity test (BOP_BIN_BASE + 4 k + 2 const)          (12)
+//   + 12 + ((k - 4) * 4 + var) * 3 + m        a division with a halves mask (topa_div(k, var, m))                                       (24)
+//   + 36 + k, k < 2                           cos / exp of the accumulator without the validity test (BOP_UN_BASE + 4 k)                (2)
+//   + 38 + k * 2 + out, k < 2                 ... without the pre-test (topa_un(k, out))                                                (4)
+constexpr uint32_t TOPX_ENDA_BASE = TOPX_ENDV_BASE + TOPX_ENDV_COUNT;
+constexpr uint32_t TOPX_ENDA_COUNT = 42;
+constexpr int topx_enda_of(uint32_t aid) { // the slot of an end-fused last instruction's assured id, or -1: the guarded end-fused handler
+    return (aid >= BOP_BIN_BASE && aid < BOP_BIN_END && !((aid - BOP_BIN_BASE) & 1)) ? (int)(((aid - BOP_BIN_BASE) >> 2) * 2 + (((aid - BOP_BIN_BASE) >> 1) & 1))
+         : (aid >= TOPA_DIV_BASE && aid < TOPA_DIV_BASE + 24) ? 12 + (int)(aid - TOPA_DIV_BASE)
+         : (aid == BOP_UN_BASE || aid == BOP_UN_BASE + 4) ? 36 + (int)((aid - BOP_UN_BASE) >> 2)
+         : (aid >= TOPA_UN_BASE && aid < TOPA_UN_BASE + 8 && !((aid - TOPA_UN_BASE) & 2)) ? 38 + (int)(((aid - TOPA_UN_BASE) >> 2) * 2 + ((aid - TOPA_UN_BASE) & 1)) : -1;
+}
+constexpr uint32_t topx_enda_id(int q) { // ... inverted: the assured id slot q stands for (its PLAIN form: what a fused-loss launch re-names it to)
+    return q < 12 ? BOP_BIN_BASE + 4 * (uint32_t)(q / 2) + 2 * (uint32_t)(q & 1) : q < 36 ? TOPA_DIV_BASE + (uint32_t)(q - 12)
+         : q < 38 ? BOP_UN_BASE + 4 * (uint32_t)(q - 36) : TOPA_UN_BASE + 4 * (uint32_t)((q - 38) / 2) + (uint32_t)((q - 38) & 1);
+}
+constexpr int topx_enda_guarded(int q) { // ... and the TOPX_ENDV slot of the guarded instruction it is a twin of
+    return q < 12 ? q : q < 36 ? (4 + (q - 12) / 12) * 2 + ((((q - 12) / 3) & 3) >> 1) : q < 38 ? 12 + (q - 36) : 12 + (q - 38) / 2;
+}
+constexpr uint32_t TOPX_AUX_BASE = TOPX_ENDA_BASE + TOPX_ENDA_COUNT; // + 0: h_tree_end_slow, + 1: h_tree_skip
 constexpr uint32_t TOPX_TABLE = TOPX_AUX_BASE + 2;
 // chained stream (de_api_program.cpp make_chained): bit 31 of a tree header's length word = the tree finishes in an end-fused handler
 constexpr uint32_t DE_HDR_FUSED_END = 0x80000000u;
@@ -249,13 +282,14 @@ bool top_is_const_source(uint32_t top);
 
 // ---- the ASSURED form of a fused tree ------------------------------------------------------------------------
 // An interval pass over the fused instructions of one Float32 tree under ASSUMPTION A: every feature value of the sample tile is
-// finite with 2^-40 <= |x| <= xmax (the eval kernel tests that once per workgroup while it stages the tile).  Constants enter with
+// finite with 2^-39 <= |x| <= xmax (the eval kernel tests that once per workgroup while it stages the tile; the pass itself takes 2^-40
+// unless ASSURED_PART_FUSED_DIV is on).  Constants enter with
 // their values; + - * /, cos (-> [-1, 1]) and exp have rules; every other operator, a parameter or ternary operand and a slot row no
 // instruction of the tree has written give the unbounded value.  Bounds are computed in double and widened outward by a relative
 // 2^-20 and an absolute 2^-140 (Float32 rounding, subnormal results); a value counts as finite only while |v| <= 2^120, a quotient
 // only when |denominator| has a positive lower bound.  A validity test of a value that is proven finite cannot fire under A: the
 // instruction is given the id of its twin WITHOUT that test — the same operator on the same operand words, so the assured stream is
-// the fused stream in everything but handler ids.  (An end-fused last instruction keeps its id: the twin has no end-fused form.)
+// the fused stream in everything but handler ids.  (An end-fused last instruction keeps its id unless ASSURED_PART_END is on.)
 struct AssuredVal {
     double lo, hi; // lo <= v <= hi
     double amin;   // |v| >= amin (0: nothing known)
@@ -265,17 +299,26 @@ enum : uint32_t { ASSURED_OUT = 1u,      // the validity test of the instruction
                   ASSURED_ROW = 2u,      // the validity test of its row operand (a leaf check) is elided
                   ASSURED_PRE = 4u,      // cos / exp: the range pre-test is elided (|arg| <= 9e4 / |arg log2 e| <= 125 proven)
                   ASSURED_DIV_ACC = 8u,  // division: the range test of the accumulator operand is elided (|v| in [2^-39, 2^39] proven)
-                  ASSURED_DIV_ROW = 16u }; // ... of the row operand
-// the parts of the pass (DE_ASSURED_PARTS, a bit mask; measured one by one, TUNING_LOG.md: the validity tests and the pre-tests pay and are
-// the default, the division halves measured inside the run-to-run spread and are opt-in)
-constexpr uint32_t ASSURED_PARTS_SHIPPED = 3u;
-enum : uint32_t { ASSURED_PART_VALIDITY = 1u, ASSURED_PART_PRETEST = 2u, ASSURED_PART_DIVISION = 4u, ASSURED_PARTS_ALL = 7u };
+                  ASSURED_DIV_ROW = 16u, // ... of the row operand
+                  ASSURED_DIV_A = 32u,   // division of TOP_BIN2: the range test of row A is elided
+                  ASSURED_DIV_B = 64u }; // ... of row B
+// the parts of the pass (DE_ASSURED_PARTS, a bit mask; measured one by one, DESIGN.md 4.1.1 with the raw lines in
+// profiles/assured_forms_ab.txt: every part clears the run-to-run spread on the headline and is in the default — the division halves of
+// the plain forms, which did not on their own, do since a bare feature is a proven operand)
+// ASSURED_PART_FUSED_DIV: the division halves of the fused form TOP_BIN2 — and with it the FEATURE BOUND: a feature enters
+// the pass with |x| >= 2^-39, what the tile test guarantees, instead of 2^-40, so that a bare feature is a proven division operand (of the
+// plain forms too).  Without the bit the pass is the pass of ASSURED_PARTS_CLASSIC, id for id.
+constexpr uint32_t ASSURED_PARTS_SHIPPED = 31u;
+// ASSURED_PART_END: the end-fused last instruction of a tree takes its assured id too (TOPX_ENDA_BASE: the end-fused twins); without the bit
+// it keeps the guarded id and handler.
+enum : uint32_t { ASSURED_PART_VALIDITY = 1u, ASSURED_PART_PRETEST = 2u, ASSURED_PART_DIVISION = 4u, ASSURED_PART_FUSED_DIV = 8u, ASSURED_PART_END = 16u,
+                  ASSURED_PARTS_CLASSIC = 7u, ASSURED_PARTS_ALL = 31u };
 struct AssuredInstr {
     AssuredVal acc; // the accumulator behind the instruction
     uint32_t id;    // the handler id of the assured stream (== the fused id: nothing elided)
     uint32_t bits;  // ASSURED_*
 };
-void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts = ASSURED_PARTS_ALL);
+void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts);
 
 // Append the bound form of `code` (one tree) to `out`.
 // param_row_base >= 0: parameter operands are LDS rows param_row_base + p (the eval kernels stage the tile's parameter values like

@@ -105,7 +105,7 @@ struct EvalArgs {
     int32_t waves, wave_slots;
     int64_t var_stride;
     // the ASSURED stream (de_api_internal.h; one-wave Float32 programs): variant 1, var_stride records behind `code`, is the stream without
-    // the validity tests that cannot fire while every feature value of a tile has 2^-40 <= |x| <= assured_xmax; the kernel tests the tile
+    // the validity tests that cannot fire while every feature value of a tile has 2^-39 <= |x| <= assured_xmax; the kernel tests the tile
     bool assured = false;
     float assured_xmax = 0.0f;
     // de_eval_sum_certificate: device array of n_trees zeroed words of the element type's size; non-null selects the CERT variant of the

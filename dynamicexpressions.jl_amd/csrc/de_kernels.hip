@@ -103,12 +103,14 @@ template <typename T> struct KArgs {
     const double *fit_ystats;
     // THE ASSURED STREAM (one-wave Float32 workgroups): assured != 0 = var_stride records behind `code` lies the variant of
     // the stream without the validity tests that cannot fire on a tile of ordinary feature values.  The workgroup tests its tile while it
-    // stages it — every value finite with 2^-40 <= |x| <= assured_xmax, one ballot — and runs that variant when the tile passes.
+    // stages it — every value finite with 2^-39 <= |x| <= assured_xmax, one ballot — and runs that variant when the tile passes.
     int32_t assured;
     float assured_xmax;
 };
 // the per-value test of the tile fact (NaN fails both compares)
-__device__ __forceinline__ bool assured_value_ok(float v, float xmax) { return (__builtin_fabsf(v) <= xmax) & (__builtin_fabsf(v) >= 0x1p-40f); }
+// (2^-39, not the 2^-40 of the division range test: a bare feature is then a proven division operand, de_bind.h ASSURED_PART_FUSED_DIV; a tile
+// with a value in [2^-40, 2^-39) runs the guarded stream, which is right for every part of the pass)
+__device__ __forceinline__ bool assured_value_ok(float v, float xmax) { return (__builtin_fabsf(v) <= xmax) & (__builtin_fabsf(v) >= 0x1p-39f); }
 __device__ __forceinline__ bool assured_value_ok(double, float) { return false; } // (Float64 programs have no assured stream)
 
 
@@ -962,22 +964,23 @@ template <int K, int VAR, bool TB, bool NT = false> __device__ __noinline__ HSta
     HFAST_NEXT(w);
 }
 // ... as the last instruction of a tree (the end-fused form of b_un<K, 1>: accumulator operand, tested result)
-template <int K, bool TB> __device__ __noinline__ HState<float> h_un_end_fast(HFAST_ARGS) {
+// NT / OUT = false (the assured stream's end-fused twins, de_bind.h TOPX_ENDA_BASE): without the pre-test / the validity test of the result
+template <int K, bool TB, bool NT = false, bool OUT = true> __device__ __noinline__ HState<float> h_un_end_fast(HFAST_ARGS) {
     typedef float T;
     constexpr int G = TG<T>::G;
     UnPre p[G];
     bool slow = false;
     FOR_PLANES slow |= un_pretest<K, TB>(st.acc[g], p[g]);
-    if (__builtin_expect((int32_t)flags < 0, 0)) [[clang::musttail]] return h_chain_end<T, &b_un<T, K, 1, TB>>(HFAST_PASS);
-    if (__builtin_expect(wave_any(slow), 0)) [[clang::musttail]] return h_chain_end<T, &b_un<T, K, 1, TB>>(HFAST_PASS);
+    if (__builtin_expect((int32_t)flags < 0, 0)) [[clang::musttail]] return h_chain_end<T, &b_un<T, K, OUT ? 1 : 0, TB>>(HFAST_PASS);
+    if constexpr (!NT) if (__builtin_expect(wave_any(slow), 0)) [[clang::musttail]] return h_chain_end<T, &b_un<T, K, OUT ? 1 : 0, TB>>(HFAST_PASS);
 #if DE_TG == 1
     FOR_PLANES {
         st.acc[g] = un_finish<K, TB>(st.acc[g], p[g]);
-        hpoison<T>(st.poison, st.acc[g]);
+        if constexpr (OUT) hpoison<T>(st.poison, st.acc[g]);
     }
 #else
     un_finish_planes<K, TB, G>(st.acc, st.acc, p);
-    FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
+    if constexpr (OUT) FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
 #endif
     HFAST_END_TAIL()
 }
@@ -1044,30 +1047,35 @@ template <int K, int VAR, int M = 3> __device__ __noinline__ HState<float> h_div
     HFAST_NEXT(w);
 }
 // ... as the last instruction of a tree (the end-fused forms of b_bin<K, 1> / <K, 3>: tested result)
-template <int K, bool CST> __device__ __noinline__ HState<float> h_div_end_fast(HFAST_ARGS) {
+// OUT = false / M (the assured stream's end-fused twins, de_bind.h TOPX_ENDA_BASE): without the validity test of the result / M as in h_div_fast
+template <int K, bool CST, bool OUT = true, int M = 3> __device__ __noinline__ HState<float> h_div_end_fast(HFAST_ARGS) {
     typedef float T;
     typedef VecOf<float>::type V;
     constexpr int G = TG<T>::G;
     if constexpr (CST) {
+        constexpr int VAR = 2 + (OUT ? 1 : 0);
         bool unsafe = false;
-        FOR_PLANES unsafe |= !div_samples_safe(st.acc[g]);
-        if (__builtin_expect(((int32_t)flags < 0) | !div_const_in_range(w1), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, 3, false>>(HFAST_PASS);
-        if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, 3, false>>(HFAST_PASS);
+        if constexpr (M & 1) FOR_PLANES unsafe |= !div_samples_safe(st.acc[g]);
+        if (__builtin_expect(((int32_t)flags < 0) | !div_const_in_range(w1), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
+        if constexpr (M & 1) if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
         FOR_PLANES st.acc[g] = div_const<K>(st.acc[g], w1);
     } else {
+        constexpr int VAR = OUT ? 1 : 0;
         V num[G], den[G];
         bool unsafe = false;
         FOR_PLANES {
             const V b = *LDSP(T, PLANE_ADDR(lds0 + la, g));
             num[g] = K == 4 ? st.acc[g] : b;
             den[g] = K == 4 ? b : st.acc[g];
-            unsafe |= !div_operands_safe(num[g], den[g]);
+            if constexpr (M == 3) unsafe |= !div_operands_safe(num[g], den[g]);
+            else if constexpr (M == 1) unsafe |= !div_samples_safe(st.acc[g]);
+            else if constexpr (M == 2) unsafe |= !div_samples_safe(b);
         }
-        if (__builtin_expect((int32_t)flags < 0, 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, 1, false>>(HFAST_PASS);
-        if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, 1, false>>(HFAST_PASS);
+        if (__builtin_expect((int32_t)flags < 0, 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
+        if constexpr (M != 0) if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain_end<T, &b_bin<T, K, VAR, false>>(HFAST_PASS);
         FOR_PLANES st.acc[g] = div_safe(num[g], den[g]);
     }
-    FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
+    if constexpr (OUT) FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
     HFAST_END_TAIL()
 }
 // ... fused with the validity test of the row operand (b_binrowc) / with the load of row A, a constant or row B as the other
@@ -1093,7 +1101,9 @@ template <int K, bool OUT> __device__ __noinline__ HState<float> h_divrowc_fast(
     }
     HFAST_NEXT(w);
 }
-template <int K, bool CST, bool OUT, bool PUSH> __device__ __noinline__ HState<float> h_div2_fast(HFAST_ARGS) {
+// NT (the assured stream, de_bind.h TOPA_DIV2_BASE): no range test of the rows — the interval pass proved both (or the one beside a constant,
+// which keeps its scalar test) inside [2^-39, 2^39] for every tile that runs this stream
+template <int K, bool CST, bool OUT, bool PUSH, bool NT = false> __device__ __noinline__ HState<float> h_div2_fast(HFAST_ARGS) {
     typedef float T;
     typedef VecOf<float>::type V;
     constexpr int G = TG<T>::G;
@@ -1107,9 +1117,9 @@ template <int K, bool CST, bool OUT, bool PUSH> __device__ __noinline__ HState<f
     }
     if constexpr (CST) {
         bool unsafe = false;
-        FOR_PLANES unsafe |= !div_samples_safe(x[g]);
+        if constexpr (!NT) FOR_PLANES unsafe |= !div_samples_safe(x[g]);
         if (__builtin_expect(!div_const_in_range(w1), 0)) [[clang::musttail]] return h_chain<T, &b_bin2<T, K, CST, OUT, PUSH, false>>(HFAST_PASS);
-        if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain<T, &b_bin2<T, K, CST, OUT, PUSH, false>>(HFAST_PASS);
+        if constexpr (!NT) if (__builtin_expect(wave_any(unsafe), 0)) [[clang::musttail]] return h_chain<T, &b_bin2<T, K, CST, OUT, PUSH, false>>(HFAST_PASS);
         FOR_PLANES st.acc[g] = div_const<K>(x[g], w1);
     } else {
         V num[G], den[G];
@@ -1119,9 +1129,9 @@ template <int K, bool CST, bool OUT, bool PUSH> __device__ __noinline__ HState<f
             const V b = *LDSP(T, (PUSH ? row_a(ag) : ag) + w1);
             num[g] = K == 4 ? x[g] : b;
             den[g] = K == 4 ? b : x[g];
-            unsafe |= !div_operands_safe(num[g], den[g]);
+            if constexpr (!NT) unsafe |= !div_operands_safe(num[g], den[g]);
         }
-        if (__builtin_expect(__ballot(unsafe) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_bin2<T, K, CST, OUT, PUSH, false>>(HFAST_PASS);
+        if constexpr (!NT) if (__builtin_expect(__ballot(unsafe) != 0ull, 0)) [[clang::musttail]] return h_chain<T, &b_bin2<T, K, CST, OUT, PUSH, false>>(HFAST_PASS);
         FOR_PLANES st.acc[g] = div_safe(num[g], den[g]);
     }
     if constexpr (OUT) FOR_PLANES hpoison<T>(st.poison, st.acc[g]);
@@ -1283,11 +1293,12 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
 #undef TBF
     // the assured forms (de_bind.h TOPA_*): every slot starts as the FULL handler of the same instruction (h_chain over the body: what the
     // table holds at this point); exact-mode Float32 replaces the slots the assured stream can name below.  The rest — other element types,
-    // turbo, the m = 1 / 2 slots of a division by a constant — is never named by assure_tree and only keeps the table dense and inside
+    // turbo, the m = 1 / 2 slots of a division by a constant, a mirrored row / row TOP_BIN2 — is never named by assure_tree and only keeps the table dense and inside
     // the address window the host checks
     for (uint32_t k = 0; k < 2; k++) for (uint32_t v = 0; v < 4; v++) t[topa_un((int)k, v)] = t[BOP_UN_BASE + 4 * k + v];
     for (uint32_t i = 0; i < 16; i++) t[TOPA_UNROW_BASE + i] = t[TOP_UNROW_BASE + i];
     for (uint32_t k = 4; k < 6; k++) for (uint32_t v = 0; v < 4; v++) for (uint32_t m = 0; m < 3; m++) t[topa_div((int)k, v, m)] = t[BOP_BIN_BASE + 4 * k + v];
+    for (uint32_t k = 4; k < 6; k++) for (uint32_t v = 0; v < 8; v++) t[topa_div2((int)k, (v & 4) != 0, (v & 2) != 0, (v & 1) != 0)] = t[top_bin2((int)k, (v & 4) != 0, (v & 2) != 0, (v & 1) != 0)];
     if constexpr (sizeof(T) == 4) { // Float32: the fast-path-only forms (h_*_fast above) replace the full handlers in the table
 #define HUF(K) t[BOP_UN_BASE + 4 * K + 0] = (uint64_t)&h_un_fast<K, 0, TB>; t[BOP_UN_BASE + 4 * K + 1] = (uint64_t)&h_un_fast<K, 1, TB>; \
                t[BOP_UN_BASE + 4 * K + 2] = (uint64_t)&h_un_fast<K, 2, TB>; t[BOP_UN_BASE + 4 * K + 3] = (uint64_t)&h_un_fast<K, 3, TB>; \
@@ -1315,6 +1326,14 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
 #define HAD2(K, V) t[topa_div(K, V, 0)] = (uint64_t)&h_div_fast<K, V, 0>; /* (a constant operand: m = 0 only; 1 and 2 keep the guarded handler) */
 #define HAD(K) HAD1(K, 0) HAD1(K, 1) HAD2(K, 2) HAD2(K, 3)
             HAD(4) HAD(5)
+            // (the fused divisions: the twins of de_bind.h topa_div2_has)
+#define HAD2C(K, O, P) t[topa_div2(K, true, O, P)] = (uint64_t)&h_div2_fast<K, true, O, P, true>;
+#define HAD2R(O, P) t[topa_div2(4, false, O, P)] = (uint64_t)&h_div2_fast<4, false, O, P, true>;
+#define HADF(K) HAD2C(K, false, false) HAD2C(K, false, true) HAD2C(K, true, false) HAD2C(K, true, true)
+            HADF(4) HADF(5) HAD2R(false, false) HAD2R(false, true) HAD2R(true, false) HAD2R(true, true)
+#undef HADF
+#undef HAD2R
+#undef HAD2C
 #undef HAD
 #undef HAD2
 #undef HAD1
@@ -1328,6 +1347,27 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
 #undef HURF
 #undef HURF1
 #undef HUF
+    }
+    // the end-fused twins of the assured stream (de_bind.h TOPX_ENDA_BASE): every slot starts as the guarded end-fused handler of the same
+    // instruction; exact-mode Float32 replaces the slots assure_tree can name
+    for (int q = 0; q < (int)TOPX_ENDA_COUNT; q++) t[TOPX_ENDA_BASE + q] = t[TOPX_ENDV_BASE + topx_enda_guarded(q)];
+    if constexpr (sizeof(T) == 4 && !TB) {
+#define HEA(K) t[TOPX_ENDA_BASE + K * 2] = (uint64_t)&h_chain_end<T, &b_bin<T, K, 0, false>>; t[TOPX_ENDA_BASE + K * 2 + 1] = (uint64_t)&h_chain_end<T, &b_bin<T, K, 2, false>>;
+        HEA(0) HEA(1) HEA(2) HEA(3)
+#undef HEA
+#define HEDM(K, C, O) t[TOPX_ENDA_BASE + 12 + topa_div(K, (C ? 2 : 0) + (O ? 1 : 0), 0) - TOPA_DIV_BASE] = (uint64_t)&h_div_end_fast<K, C, O, 0>;
+#define HEDR(K, O) HEDM(K, false, O) t[TOPX_ENDA_BASE + 12 + topa_div(K, O ? 1 : 0, 1) - TOPA_DIV_BASE] = (uint64_t)&h_div_end_fast<K, false, O, 1>; \
+                   t[TOPX_ENDA_BASE + 12 + topa_div(K, O ? 1 : 0, 2) - TOPA_DIV_BASE] = (uint64_t)&h_div_end_fast<K, false, O, 2>;
+#define HED(K) t[TOPX_ENDA_BASE + K * 2] = (uint64_t)&h_div_end_fast<K, false, false>; t[TOPX_ENDA_BASE + K * 2 + 1] = (uint64_t)&h_div_end_fast<K, true, false>; \
+               HEDR(K, false) HEDR(K, true) HEDM(K, true, false) HEDM(K, true, true)
+        HED(4) HED(5)
+#undef HED
+#undef HEDR
+#undef HEDM
+#define HEU(K) t[TOPX_ENDA_BASE + 36 + K] = (uint64_t)&h_un_end_fast<K, false, false, false>; \
+               t[TOPX_ENDA_BASE + 38 + K * 2] = (uint64_t)&h_un_end_fast<K, false, true, false>; t[TOPX_ENDA_BASE + 38 + K * 2 + 1] = (uint64_t)&h_un_end_fast<K, false, true, true>;
+        HEU(0) HEU(1)
+#undef HEU
     }
 #undef TBK
 }
@@ -1408,7 +1448,7 @@ __global__ void __launch_bounds__(256) de_tile_extremes_kernel(const T *__restri
 // of a loss launch the last instruction is named in its PLAIN form (plain[k] for endv[k]) and names h_tree_end_slow (`slow_end`) directly.
 struct LossEnds {
     uint64_t end, slow_end; // h_tree_end, h_tree_end_slow; slow_end == 0: not a loss launch, nothing is re-named
-    uint64_t endv[TOPX_ENDV_COUNT], plain[TOPX_ENDV_COUNT];
+    uint64_t endv[TOPX_ENDV_COUNT + TOPX_ENDA_COUNT], plain[TOPX_ENDV_COUNT + TOPX_ENDA_COUNT]; // (behind the guarded forms: the assured stream's twins, 0: no such twin)
 };
 template <bool F32> __device__ __forceinline__ uint64_t rec_next(const U32x4 &r, uint64_t hi) { return F32 ? (((uint64_t)r.w << 32) | r.z) : (hi | r.y); }
 template <bool F32> __device__ __forceinline__ void rec_set_next(U32x4 &r, uint64_t h) {
@@ -1494,6 +1534,9 @@ __global__ void __launch_bounds__(1024) de_compact_live_kernel(const U32x4 *__re
                 const uint64_t named = rec_next<F32>(f, hi);
                 DE_UNROLL for (int q2 = 0; q2 < (int)TOPX_ENDV_COUNT; q2++)
                     if (named == (F32 ? le.endv[q2] : (hi | (uint32_t)le.endv[q2]))) rec_set_next<F32>(f, le.plain[q2]);
+                if (F32) // (the assured stream: Float32 programs only)
+                    for (int q2 = (int)TOPX_ENDV_COUNT; q2 < (int)(TOPX_ENDV_COUNT + TOPX_ENDA_COUNT); q2++)
+                        if (le.endv[q2] != 0 && named == le.endv[q2]) rec_set_next<F32>(f, le.plain[q2]);
                 ccode[dst + len - 3] = f;
             }
         }
@@ -2339,6 +2382,13 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
                     le.endv[k] = table[TOPX_ENDV_BASE + k];
                     le.plain[k] = k < 12 ? table[BOP_BIN_BASE + 4 * (k / 2) + ((k & 1) ? 3 : 1)] : table[BOP_UN_BASE + 4 * (k - 12) + 1]; // (de_bind.h topx_endv_of, inverted)
                 }
+                // the end-fused twins of the assured stream: each to the plain handler of its assured id (a slot that holds the guarded
+                // end-fused handler — no such twin in this table — is left out: that handler has its entry above)
+                for (int q = 0; q < (int)TOPX_ENDA_COUNT; q++)
+                    if (table[TOPX_ENDA_BASE + q] != table[TOPX_ENDV_BASE + topx_enda_guarded(q)]) {
+                        le.endv[TOPX_ENDV_COUNT + q] = table[TOPX_ENDA_BASE + q];
+                        le.plain[TOPX_ENDV_COUNT + q] = table[topx_enda_id(q)];
+                    }
             }
             if (sizeof(T) == 4)
                 hipLaunchKernelGGL(de_compact_live_kernel<true>, dim3(n_variants), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,

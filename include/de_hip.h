@@ -357,15 +357,20 @@ int64_t de_lower_tape_stage(int dtype, const de_tape_node_t *nodes, int64_t n_no
                             int32_t n_params, uint32_t options, int stage, uint32_t *words,
                             int64_t cap);
 /* Stage 4 (DE_F32 only): the stage-3 words with the handler ids of the ASSURED stream — the same records, a
- * validity test that cannot fire while every feature value has 2^-40 <= |x| <= DE_ASSURED_XMAX (default 64) left out by naming the
+ * validity test that cannot fire while every feature value has 2^-39 <= |x| <= DE_ASSURED_XMAX (default 64) left out by naming the
  * untested twin of the instruction's handler.  de_lower_tape_assured returns what decides it: per fused instruction six doubles
  * {lo, hi, amin, finite, id, bits} — the interval [lo, hi] and the lower bound amin of |value| of the accumulator behind the
  * instruction (meaningful when finite == 1), the assured handler id and the elision bits (1: the result's validity test, 2: the row
  * operand's, 4: the cos / exp range pre-test, 8 / 16: the division range test of the accumulator / row operand) with every part of
- * the pass on; stage 4 applies the parts a program would (DE_ASSURED_PARTS, default 3 = bits 1, 2 and 4).
+ * the first three parts of the pass on; stage 4 applies the parts a program would (DE_ASSURED_PARTS, default 31 = every part).
  * Returns the number of doubles or -status.  Host-only. */
 int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
                               int32_t n_features, uint32_t options, double xmax, double *out, int64_t cap);
+/* ... with the parts of the pass named by the caller: a mask of 1 validity tests, 2 cos / exp pre-tests, 4 division halves of the plain
+ * forms, 8 the TOP_BIN2 divisions and the feature bound 2^-39, 16 the end-fused last instruction (bits 32 / 64 of the elision bits: the
+ * range test of row A / row B of a TOP_BIN2 division).  de_lower_tape_assured is parts = 7. */
+int64_t de_lower_tape_assured_parts(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                                    int32_t n_features, uint32_t options, double xmax, uint32_t parts, double *out, int64_t cap);
 /* The two hooks above take the real dtypes (DE_F32, DE_F64, DE_F16) and answer -DE_ERR_INVALID_ARG for any other code; complex tapes
  * (DE_CF32 / DE_CF64, interleaved (re, im) constants) lower through these two, which take nothing else.  The generic words carry, for a
  * constant operand, the index of its (re, im) pair in the program's constant table (slot k of the tape: index k) instead of its value. */

@@ -184,7 +184,15 @@ def handler_names(ty: str, turbo: bool = False):
             for m in range(3):
                 names[ADIV + ((k - 4) * 4 + v) * 3 + m] = (f"h_div_assured<{k}, {v}, {m}>" if plain and (v < 2 or m == 0)
                                                            else names[BIN_BASE + 4 * k + v])
-    return names, dict(BOP_COUNT=BOP_COUNT, TOP_COUNT=TOP_COUNT, TOPX_COUNT=ADIV + 24)
+    # ... and the TOP_BIN2 divisions without the range test of their rows (TOPA_DIV2_BASE; a mirrored row / row form has no twin: csrc/de_bind.h topa_div2_has)
+    ADIV2 = ADIV + 24
+    for k in (4, 5):
+        for cst in (0, 1):
+            for o in (0, 1):
+                for p in (0, 1):
+                    names[ADIV2 + (((k - 4) * 2 + cst) * 2 + o) * 2 + p] = (f"h_div2_assured<{k}, {b(cst)}, {b(o)}, {b(p)}>" if plain and (cst or k == 4)
+                                                                            else names[BIN2 + ((k * 2 + cst) * 2 + o) * 2 + p])
+    return names, dict(BOP_COUNT=BOP_COUNT, TOP_COUNT=TOP_COUNT, TOPX_COUNT=ADIV2 + 16)
 
 
 def table(obj, ty="float", turbo=False):
@@ -216,9 +224,9 @@ def table(obj, ty="float", turbo=False):
         if m:
             fast["h_binrowc<float, %s, %s, false>" % m.groups()] = code
             continue
-        m = re.search(r"de::h_div2_fast<(\d), (true|false), (true|false), (true|false)>\(", full)
+        m = re.search(r"de::h_div2_fast<(\d), (true|false), (true|false), (true|false), (true|false)>\(", full)  # (last argument true: no range test of the rows)
         if m:
-            fast["h_bin2<float, %s, %s, %s, %s, false>" % m.groups()] = code
+            fast[("h_div2_assured<%s, %s, %s, %s>" if m.group(5) == "true" else "h_bin2<float, %s, %s, %s, %s, false>") % m.groups()[:4]] = code
     if ty == "float":
         by_short.update(fast)
     names, counts = handler_names(ty, turbo)
