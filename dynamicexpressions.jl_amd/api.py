@@ -53,7 +53,7 @@ EXPORTS = [
     "de_ctx_device", "de_ctx_timing_ring", "de_ctx_timing_read", "de_dist_reorder_selftest", "de_eval_sum_certificate",
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
     "de_lower_tape_assured", "de_lower_tape_assured_parts", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
-    "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex",
+    "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex", "de_eval_fit_stats_grad",
 ]
 
 
@@ -282,6 +282,101 @@ class GaussNewton:
         return step[:int(ng.sum())]
 
 
+class FitStatsGrad:
+    """What ``Population.eval_fit_stats_grad`` returns (``de_eval_fit_stats_grad``): the ``FitStats`` of the population
+    with their gradients over the rows ``theta`` the call selected.  Per tree ``d_sum[t] = D = sum w d``, ``d_pred[t] = P = sum w (yhat -
+    mean_p) d``, ``d_targ[t] = Q = sum w (y - mean_y) d`` (``[G_t]`` each, float64) and ``jtj[t] = sum w d d^T`` (``[G_t, G_t]``, the
+    population's dtype; NaN where ``has_jtj`` is false); ``ok``; ``has_jtj = ok & (G_t <= GN_MAX_ROWS) & want_jtj``.  Everything derived is
+    computed in float64 on the host and returned as one numpy vector (or matrix) per tree.  Where a tree is constant over the samples
+    (``m2_p == 0``) the gradients of the scaled quantities and the projected matrix are 0; an incomplete tree holds NaN throughout."""
+
+    def __init__(self, stats: FitStats, d_sum, d_pred, d_targ, jtj, ok, has_jtj=None):
+        self.stats, self.d_sum, self.d_pred, self.d_targ, self.jtj, self.ok = stats, list(d_sum), list(d_pred), list(d_targ), list(jtj), ok
+        n = len(stats)
+        if not (len(self.d_sum) == len(self.d_pred) == len(self.d_targ) == len(self.jtj) == len(ok) == n):
+            raise ValueError("stats, d_sum, d_pred, d_targ, jtj and ok hold one entry per tree")
+        if has_jtj is None:
+            has_jtj = _host(ok).astype(bool) & np.array([h.shape[0] <= GN_MAX_ROWS for h in self.jtj], dtype=bool)
+        self.has_jtj = has_jtj
+
+    def __len__(self) -> int:
+        return len(self.d_sum)
+
+    def _dpq(self, t):
+        return tuple(_host(v[t]).astype(np.float64) for v in (self.d_sum, self.d_pred, self.d_targ))
+
+    def mean_grad(self):
+        """d mean_p / d theta = D / W (0 where W == 0)."""
+        W = self.stats.W
+        return [self._dpq(t)[0] / W if W != 0.0 else 0.0 * self._dpq(t)[0] for t in range(len(self))]
+
+    def m2_grad(self):
+        """d m2_p / d theta = 2 P."""
+        return [2.0 * self._dpq(t)[1] for t in range(len(self))]
+
+    def cov_grad(self):
+        """d cov / d theta = Q."""
+        return [self._dpq(t)[2] for t in range(len(self))]
+
+    def scaled_sse_grad(self):
+        """d scaled_sse / d theta = 2 b (b P - Q) with b = cov / m2_p, the slope at its optimum (the envelope theorem: the optimal a and b
+        need no derivative of their own); 0 where m2_p == 0."""
+        b = self.stats.slope
+        out = []
+        for t in range(len(self)):
+            _, P, Q = self._dpq(t)
+            out.append(np.zeros_like(P) if self.stats.m2_p[t] == 0.0 else 2.0 * b[t] * (b[t] * P - Q))
+        return out
+
+    def pearson_r2_grad(self):
+        """d (r^2) / d theta = 2 cov Q / (m2_p m2_y) - 2 cov^2 P / (m2_p^2 m2_y); 0 where m2_p == 0 (NaN where y has no variance)."""
+        st, out = self.stats, []
+        for t in range(len(self)):
+            _, P, Q = self._dpq(t)
+            if st.m2_p[t] == 0.0:
+                out.append(np.zeros_like(P))
+                continue
+            with np.errstate(divide="ignore", invalid="ignore"):
+                c, m = st.cov[t], st.m2_p[t]
+                out.append(2.0 * c * Q / (m * st.m2_y) - 2.0 * c * c * P / (m * m * st.m2_y))
+        return out
+
+    def sse_grad(self):
+        """d sse / d theta of the plain L2 loss ``FitStats.sse`` — what ``eval_loss_grad(loss="L2")`` returns — from the moments:
+        ``2 P - 2 Q + 2 (mean_p - mean_y) D``."""
+        st, out = self.stats, []
+        for t in range(len(self)):
+            D, P, Q = self._dpq(t)
+            if st.W == 0.0:
+                out.append(0.0 * D)
+                continue
+            out.append(2.0 * P - 2.0 * Q + 2.0 * (st.mean_p[t] - st.mean_y) * D)
+        return out
+
+    def projected(self) -> GaussNewton:
+        """The Gauss-Newton system of the residual under linear scaling, (a, b) projected out (variable projection, Kaufman's form):
+        ``GaussNewton(loss=scaled_sse, grad=scaled_sse_grad, jtj=b^2 (H - D D^T / W - P P^T / m2_p), ok, has_jtj)`` in float64, so that
+        ``lm_step`` / ``lm_step_device`` give the Levenberg-Marquardt step under scaling.  m2_p == 0: a zero gradient and matrix (``lm_step``
+        returns the zero step for a singular system)."""
+        st, b, grads, mats = self.stats, self.stats.slope, self.scaled_sse_grad(), []
+        for t in range(len(self)):
+            D, P, _ = self._dpq(t)
+            H = _host(self.jtj[t]).astype(np.float64)
+            if st.m2_p[t] == 0.0 or st.W == 0.0:
+                mats.append(np.zeros_like(H))
+                continue
+            with np.errstate(invalid="ignore", over="ignore"):
+                mats.append(b[t] * b[t] * (H - np.outer(D, D) / st.W - np.outer(P, P) / st.m2_p[t]))
+        gn = GaussNewton(st.scaled_sse, grads, mats, _host(self.ok).astype(bool), _host(self.has_jtj).astype(bool))
+        ctx = getattr(self, "_ctx", None)
+        if ctx is not None:  # (lm_step_device: the float64 system packed as eval_gauss_newton packs its own, in host buffers)
+            G = np.array([g.shape[0] for g in grads], dtype=np.int32)
+            dl = np.concatenate([g.reshape(-1) for g in grads] + [np.zeros(1)])
+            jt = np.concatenate([h.reshape(-1, order="F") for h in mats] + [np.zeros(1)])
+            gn._packed = dict(ctx=ctx, dtype=DE_F64, n_grad=G, dloss=dl, jtj=jt, occ=False)
+        return gn
+
+
 def lm_solve_host(H, g, lam: float):
     """``de_lm_solve_host``: the arithmetic of the device's Levenberg-Marquardt step (csrc/de_lm_solve.h) for one system on the host, no
     GPU needed — (step[G] float64, produced): ``produced`` False means the zero step (see ``GaussNewton.lm_step_device``)."""
@@ -397,6 +492,8 @@ def library() -> C.CDLL:
                                            vp, vp, vp, vp, vp, vp]
         lib.de_fit_consts_lm_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.c_double,
                                             C.POINTER(LmOpts), vp, vp, vp, vp]
+    if hasattr(lib, "de_eval_fit_stats_grad"):  # (absent from a library built before the fit statistics had gradients: DE_HIP_LIB in an A/B run)
+        lib.de_eval_fit_stats_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1207,6 +1304,85 @@ class Population:
         per_tree, ys = st[:3 * self.n_trees].reshape(self.n_trees, 3), st[3 * self.n_trees:]
         return FitStats(per_tree[:, 0], per_tree[:, 1], per_tree[:, 2], ys[0], ys[1], ys[2]), ok
 
+    def eval_fit_stats_grad(self, X, y, weights=None, variable: Union[bool, str] = False, params=None, classes=None,
+                            class_base: int = 1, want_jtj: bool = True) -> FitStatsGrad:
+        """The fit statistics of ``eval_fit_stats`` with their gradients over the rows ``variable`` selects (default: the constants), fused
+        into one forward-dual launch (``de_eval_fit_stats_grad``): what optimising constants under a fitness "up to a
+        linear transform" — ``scaled_sse``, Pearson's r^2 — needs, without the [n_grad, N] Jacobian.  ``want_jtj=False`` leaves the
+        Gauss-Newton matrix out (``jtj[t]`` is then NaN, ``has_jtj`` False).  numpy in -> numpy out, torch device tensors in -> tensors
+        out (the ``FitStats`` are host float64 either way).  For a GraphNode population the occurrence rows of a shared constant are summed
+        before anything is derived."""
+        self._refuse_f16("eval_fit_stats_grad")
+        mode = _grad_mode(variable)
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        pa = self._param_args(params, classes, class_base, N, keep)
+        lib = library()
+        ng = self._n_grad_all(mode)
+        offs, joffs = gn_offsets(ng)
+        moffs = 3 * offs
+        total, jtotal = max(int(moffs[-1]), 1), max(int(joffs[-1]), 1)
+        narrow = (ng <= GN_MAX_ROWS) & bool(want_jtj)
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                n, p_ = v.numel(), v.data_ptr()
+            else:
+                v = np.ascontiguousarray(v, dtype=self.dtype)
+                n, p_ = v.size, v.ctypes.data
+            if n != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return p_
+
+        if y is None:
+            raise ValueError("y is required")
+        yp, wp = vec(y, "y"), vec(weights, "weights")
+        occ = self._occ if self._occ is not None and mode != GRAD_VARIABLE else None
+        nt = self.n_trees
+        if is_t:
+            import torch
+            dev = keep_x.device
+            st = torch.empty(3 * nt + 3, dtype=torch.float64, device=dev)  # stats, then ystats
+            dm = torch.empty(total, dtype=torch.float64, device=dev)
+            jt = torch.full((jtotal,), float("nan"), dtype=keep_x.dtype, device=dev)
+            ok = torch.empty(nt, dtype=torch.uint8, device=dev)
+            self.ctx.check(lib.de_eval_fit_stats_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                                      st.data_ptr(), st.data_ptr() + 24 * nt, dm.data_ptr(), moffs.ctypes.data,
+                                                      jt.data_ptr() if want_jtj else None, joffs.ctypes.data, ok.data_ptr()))
+            okb = ok.bool()
+            has = okb & torch.as_tensor(narrow, device=dev)
+            sth = st.cpu().numpy()
+            mats = [jt[joffs[t]:joffs[t + 1]].view(int(ng[t]), int(ng[t])).t() for t in range(nt)]
+        else:
+            st = np.empty(3 * nt + 3, dtype=np.float64)
+            dm = np.empty(total, dtype=np.float64)
+            jt = np.full(jtotal, np.nan, dtype=self.dtype)
+            ok = np.zeros(nt, dtype=np.uint8)
+            self.ctx.check(lib.de_eval_fit_stats_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                                      st.ctypes.data, st.ctypes.data + 24 * nt, dm.ctypes.data, moffs.ctypes.data,
+                                                      jt.ctypes.data if want_jtj else None, joffs.ctypes.data, ok.ctypes.data))
+            okb = ok.astype(bool)
+            has = okb & narrow
+            sth = st
+            mats = [jt[joffs[t]:joffs[t + 1]].reshape((int(ng[t]), int(ng[t])), order="F") for t in range(nt)]
+        per_tree, ys = sth[:3 * nt].reshape(nt, 3), sth[3 * nt:]
+        stats = FitStats(per_tree[:, 0], per_tree[:, 1], per_tree[:, 2], ys[0], ys[1], ys[2])
+        rows = [[self._combine_rows(t, dm[moffs[t] + q * int(ng[t]):moffs[t] + (q + 1) * int(ng[t])], mode) for t in range(nt)] for q in range(3)]
+        if occ is not None:
+            mats = [gn_combine(H, occ[t]) for t, H in enumerate(mats)]
+        out = FitStatsGrad(stats, rows[0], rows[1], rows[2], mats, okb, has)
+        out._ctx = self.ctx  # (projected(): lm_step_device needs a context)
+        return out
+
     def eval_loss_grad(self, X, y, weights=None, loss: str = "L2", variable: Union[bool, str] = False,
                        params=None, classes=None, class_base: int = 1, loss_param: float = 0.0):
         """Fused loss and its gradient w.r.t. the rows ``variable`` selects (default: the constants) —
@@ -1337,12 +1513,22 @@ class Population:
         return gn
 
     def fit_constants_lm(self, X, y, consts0, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0, down: float = 0.1,
-                         history: Optional[list] = None, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4):
+                         history: Optional[list] = None, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4,
+                         scaled: bool = False):
         """Levenberg-Marquardt on the constants of every tree at once (the plain loop; one ``eval_gauss_newton`` per iteration behind
         the one at ``consts0``), minimising the loss kind ``loss`` (``eval_gauss_newton``'s keywords): per tree the step ``GaussNewton.lm_step(lam_t)`` is accepted if the loss decreased (``lam_t *= down``,
         floor 1e-12), else the tree's constants are restored (``lam_t *= up``).  ``consts0``: ``set_constants``' layout.  Trees without
         ``has_jtj`` keep ``consts0``.  Returns (consts, loss[n_trees] in float64, ok) at the accepted constants, which the population
-        holds afterwards; ``history`` (a list) receives the accepted losses after every evaluation."""
+        holds afterwards; ``history`` (a list) receives the accepted losses after every evaluation.
+
+        ``scaled=True`` (``loss="L2"`` only; any other kind is a ``ValueError`` before the constants are touched) fits under Keijzer's linear
+        scaling instead: the objective is ``FitStats.scaled_sse``, the residual of the best ``a + b * yhat``, and every evaluation is
+        ``eval_fit_stats_grad(...).projected()`` — the same loop, the same accept rule.  Returns (consts, scaled_sse,
+        ok); the caller reads ``slope`` and ``intercept`` from ``eval_fit_stats`` at the result.  Resolution of the accept rule:
+        ``scaled_sse = m2_y - cov^2 / m2_p`` cancels near a perfect fit, so the statistics' bounds resolve it to about ``1024 u m2_y`` (u =
+        2^-24 / 2^-53); the loop only takes steps that lower it, so that noise bounds how far a fit proceeds, not what it may return."""
+        if scaled and loss != "L2":
+            raise ValueError(f"fit_constants_lm(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
         consts = np.array(consts0, dtype=self.dtype).reshape(-1).copy()
         if consts.size != int(self.n_consts.sum()):
             raise ValueError("wrong number of constants")
@@ -1350,8 +1536,10 @@ class Population:
         np.cumsum(self.n_consts, out=at[1:])
         gn_loss_spec(loss, loss_param, e_floor)  # (refused before the population's constants are touched)
         kind = dict(loss=loss, loss_param=loss_param, e_floor=e_floor)
+        evaluate = (lambda: self.eval_fit_stats_grad(X, y, weights=weights).projected()) if scaled else \
+            (lambda: self.eval_gauss_newton(X, y, weights=weights, **kind))
         self.set_constants(consts)
-        gn = self.eval_gauss_newton(X, y, weights=weights, **kind)
+        gn = evaluate()
         loss, ok, has = _host(gn.loss).astype(np.float64), _host(gn.ok).astype(bool), _host(gn.has_jtj).astype(bool)
         grad, jtj = [_host(g) for g in gn.grad], [_host(h) for h in gn.jtj]
         lam = np.full(self.n_trees, float(lam0), dtype=np.float64)
@@ -1364,7 +1552,7 @@ class Population:
                 if has[t]:
                     trial[at[t]:at[t + 1]] = (consts[at[t]:at[t + 1]].astype(np.float64) + steps[t]).astype(self.dtype)
             self.set_constants(trial)
-            gt = self.eval_gauss_newton(X, y, weights=weights, **kind)
+            gt = evaluate()
             loss_t, ok_t, has_t = _host(gt.loss).astype(np.float64), _host(gt.ok).astype(bool), _host(gt.has_jtj).astype(bool)
             with np.errstate(invalid="ignore"):
                 accept = has & has_t & (loss_t < loss)

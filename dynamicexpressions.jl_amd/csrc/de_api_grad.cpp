@@ -551,6 +551,14 @@ struct GnPlan {
     const int64_t *jtj_offsets;
     double e_floor;
 };
+// de_eval_fit_stats_grad: the same launch with the kernels' fit-statistics tree end.  A tree owns FIT_COLS + 3 G reduction
+// columns and, where a matrix is wanted and G <= DE_GN_MAX_ROWS, G (G + 1) / 2 more; loss_grad_impl's dloss / dloss_offsets carry dmom and
+// its offsets (3 G doubles per tree), its loss is null and its spec L2 (unused).  Always forward duals.
+struct FitPlan {
+    double *stats, *ystats;
+    void *jtj; // may be null: no matrix wanted
+    const int64_t *jtj_offsets;
+};
 // de_gn_spec_check with its reason (null = good; *rc: DE_ERR_INVALID_ARG or DE_ERR_UNSUPPORTED).  dtype < 0: the element type is not known.
 static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap) {
     *rc = DE_ERR_INVALID_ARG;
@@ -572,7 +580,8 @@ static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, i
 }
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr);
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr,
+                          const FitPlan *fit = nullptr);
 // DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
 static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
@@ -619,13 +628,23 @@ int de_eval_loss_gn(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int6
     const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
     return de_eval_loss_gn_ex(c, p, X, N, ldX, pa, mode, y, w, &spec, 0.0, loss, dloss, dloss_offsets, jtj, jtj_offsets, ok);
 }
+int de_eval_fit_stats_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                           const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets,
+                           void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_fit_stats_grad");
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    const FitPlan fit{stats, ystats, jtj, jtj_offsets};
+    DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, nullptr, dmom, dmom_offsets, ok, nullptr, false, nullptr, &fit));
+}
 static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                           int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only, const GnPlan *gn) {
+                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only, const GnPlan *gn,
+                          const FitPlan *fit) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (N < 0 || !ok || (p->n_trees > 0 && (!dloss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (gn && p->n_trees > 0 && (!gn->jtj || !y)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (fit && p->n_trees > 0 && (!fit->stats || !fit->ystats || !y)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
     if (mode != DE_GRAD_VARIABLE && mode != DE_GRAD_CONSTANT && mode != DE_GRAD_BOTH) return fail(c, DE_ERR_INVALID_ARG, "bad gradient mode");
     if (first_kinds_only && spec->kind != DE_LOSS_L2 && spec->kind != DE_LOSS_L1 && spec->kind != DE_LOSS_PULLBACK)
@@ -641,7 +660,11 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     const size_t es = p->dtype == DE_F32 ? 4 : 8;
     // per-tree geometry: tree t owns reduction columns col_off[t] (loss) .. col_off[t] + n_grad[t]
     std::vector<int32_t> ng((size_t)p->n_trees);
-    std::vector<int64_t> coloff((size_t)p->n_trees + 1, 0), doff((size_t)p->n_trees), joff(gn ? (size_t)p->n_trees : 0);
+    void *const jtj_out = gn ? gn->jtj : (fit ? fit->jtj : nullptr); // the matrices' buffer and offsets, of either plan
+    const int64_t *const jtj_offsets = gn ? gn->jtj_offsets : (fit ? fit->jtj_offsets : nullptr);
+    const int rows_per_g = fit ? 3 : 1; // entries of dloss per gradient row (fit: D, P, Q)
+    const size_t des = fit ? sizeof(double) : (p->dtype == DE_F32 ? 4 : 8); // element size of dloss
+    std::vector<int64_t> coloff((size_t)p->n_trees + 1, 0), doff((size_t)p->n_trees), joff(jtj_out ? (size_t)p->n_trees : 0);
     int64_t span = 0, run = 0, jspan = 0, jrun = 0;
     int32_t maxg = 0;
     for (int64_t t = 0; t < p->n_trees; t++) {
@@ -651,11 +674,11 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
         const int64_t off = dloss_offsets ? dloss_offsets[t] : run;
         if (off < 0) return fail(c, DE_ERR_INVALID_ARG, "negative dloss offset");
         doff[(size_t)t] = off;
-        run += g;
-        span = std::max(span, off + g);
-        coloff[(size_t)t + 1] = coloff[(size_t)t] + 1 + g;
-        if (gn) { // ... then the lower triangle of its Gauss-Newton matrix, where the tree's rows share a window
-            const int64_t jo = gn->jtj_offsets ? gn->jtj_offsets[t] : jrun;
+        run += (int64_t)rows_per_g * g;
+        span = std::max(span, off + (int64_t)rows_per_g * g);
+        coloff[(size_t)t + 1] = coloff[(size_t)t] + (fit ? FIT_COLS + 3 * g : 1 + g);
+        if (jtj_out) { // ... then the lower triangle of its Gauss-Newton matrix, where the tree's rows share a window
+            const int64_t jo = jtj_offsets ? jtj_offsets[t] : jrun;
             if (jo < 0) return fail(c, DE_ERR_INVALID_ARG, "negative jtj offset");
             joff[(size_t)t] = jo;
             jrun += (int64_t)g * g;
@@ -665,6 +688,39 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     }
     const int64_t n_cols = coloff[(size_t)p->n_trees];
     const bool ok_dev = is_device_ptr(ok);
+    if (N == 0 && fit) { // W == 0: the means are NaN, every moment 0; NaN throughout where a constant already fails the flag
+        rc = consts_materialise(p); // (from the host's flags: §3.5)
+        if (rc != DE_OK) return rc;
+        const double nan = std::nan("");
+        std::vector<double> zs((size_t)p->n_trees * 3), zd((size_t)std::max<int64_t>(span, 1));
+        for (int64_t t = 0; t < p->n_trees; t++) {
+            const double v = p->host_ok_grad[(size_t)t] ? 0.0 : nan;
+            zs[3 * (size_t)t] = nan;
+            zs[3 * (size_t)t + 1] = zs[3 * (size_t)t + 2] = v;
+            for (int32_t k = 0; k < 3 * ng[(size_t)t]; k++) zd[(size_t)(doff[(size_t)t] + k)] = v;
+        }
+        const double ys[3] = {0.0, nan, 0.0};
+        HIP_TRY(c, hipMemcpy(fit->stats, zs.data(), zs.size() * sizeof(double), hipMemcpyDefault));
+        HIP_TRY(c, hipMemcpy(fit->ystats, ys, sizeof ys, hipMemcpyDefault));
+        for (int64_t t = 0; t < p->n_trees; t++)
+            if (ng[(size_t)t] > 0)
+                HIP_TRY(c, hipMemcpy(static_cast<double *>(dloss) + doff[(size_t)t], zd.data() + doff[(size_t)t], (size_t)3 * (size_t)ng[(size_t)t] * sizeof(double),
+                                     hipMemcpyDefault));
+        if (jtj_out) {
+            std::vector<unsigned char> zj((size_t)std::max<int64_t>(jspan, 1) * es);
+            for (int64_t t = 0; t < p->n_trees; t++) {
+                const int64_t gg = (int64_t)ng[(size_t)t] * ng[(size_t)t];
+                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= DE_GN_MAX_ROWS ? 0.0 : nan;
+                for (int64_t e = 0; e < gg; e++) {
+                    if (p->dtype == DE_F32) reinterpret_cast<float *>(zj.data())[joff[(size_t)t] + e] = (float)v;
+                    else reinterpret_cast<double *>(zj.data())[joff[(size_t)t] + e] = v;
+                }
+                if (gg > 0) HIP_TRY(c, hipMemcpy(static_cast<char *>(jtj_out) + (size_t)joff[(size_t)t] * es, zj.data() + (size_t)joff[(size_t)t] * es, (size_t)gg * es, hipMemcpyDefault));
+            }
+        }
+        HIP_TRY(c, hipMemcpy(ok, p->host_ok_grad.data(), (size_t)p->n_trees, hipMemcpyDefault));
+        return DE_OK;
+    }
     if (N == 0) { // empty sums: 0, or NaN where a constant already fails the flag
         rc = consts_materialise(p); // (from the host's flags: §3.5)
         if (rc != DE_OK) return rc;
@@ -704,7 +760,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     if (rc) return rc;
     const auto tg1 = std::chrono::steady_clock::now();
 
-    Staged sX, sY, sW, sLoss, sDl, sOk, sPar, sCls, sJ;
+    Staged sX, sY, sW, sLoss, sDl, sOk, sPar, sCls, sJ, sStats, sYstats;
     rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX);
     if (rc) return rc;
     rc = stage_in(c, c->sY, y, (size_t)N * es, &sY);
@@ -717,10 +773,16 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
         rc = stage_out(c, c->sLoss, loss, (size_t)p->n_trees * es, &sLoss);
         if (rc) return rc;
     }
-    rc = stage_out(c, c->sDloss, dloss, (size_t)std::max<int64_t>(span, 1) * es, &sDl);
+    rc = stage_out(c, c->sDloss, dloss, (size_t)std::max<int64_t>(span, 1) * des, &sDl);
     if (rc) return rc;
-    if (gn) {
-        rc = stage_out(c, c->sJtj, gn->jtj, (size_t)std::max<int64_t>(jspan, 1) * es, &sJ);
+    if (jtj_out) {
+        rc = stage_out(c, c->sJtj, jtj_out, (size_t)std::max<int64_t>(jspan, 1) * es, &sJ);
+        if (rc) return rc;
+    }
+    if (fit) {
+        rc = stage_out(c, c->sStats, fit->stats, (size_t)p->n_trees * 3 * sizeof(double), &sStats);
+        if (rc) return rc;
+        rc = stage_out(c, c->sYstats, fit->ystats, 3 * sizeof(double), &sYstats);
         if (rc) return rc;
     }
     if (ok_dev) sOk.dev = ok;
@@ -747,7 +809,9 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     // (by class: three regions — the finish passes of the classes run on the caller's stream and two side streams, launch_loss_grad_finish_ranges)
     const size_t seg_region = (size_t)loss_segments(n_tiles) * (size_t)n_cols * 4 * sizeof(double);
     const int seg_regions = plan ? 3 : 1;
-    HIP_TRY(c, c->sSeg.reserve(seg_region * (size_t)seg_regions));
+    // (fit statistics: the three per-tile arrays of the pre-pass over y / w, then the recombination's segment sums)
+    const size_t fit_pre_bytes = (size_t)3 * (size_t)n_tiles * sizeof(double);
+    HIP_TRY(c, c->sSeg.reserve(fit ? fit_pre_bytes + fit_grad_seg_bytes(p->n_trees, n_cols, N) : seg_region * (size_t)seg_regions));
     HIP_TRY(c, c->sNg.reserve(ng.size() * sizeof(int32_t)));
     HIP_TRY(c, c->sColOff.reserve(coloff.size() * sizeof(int64_t)));
     HIP_TRY(c, c->sDoff.reserve(doff.size() * sizeof(int64_t)));
@@ -757,7 +821,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     HIP_TRY(c, hipMemcpyAsync(c->sNg.p, ng.data(), ng.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sColOff.p, coloff.data(), coloff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->sDoff.p, doff.data(), doff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    if (gn) {
+    if (jtj_out) {
         HIP_TRY(c, c->sJoff.reserve(joff.size() * sizeof(int64_t)));
         HIP_TRY(c, hipMemcpyAsync(c->sJoff.p, joff.data(), joff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     }
@@ -766,6 +830,11 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
         if (rc) return rc;
         rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls);
         if (rc) return rc;
+    }
+    double ys_host[3] = {0.0, 0.0, 0.0};
+    if (fit) { // the pre-pass over y / w: {W, mean_y, M2_y}; the kernels take T(mean_y) by value
+        HIP_TRY(c, launch_fit_ystats(p->dtype, sY.dev, w ? sW.dev : nullptr, N, static_cast<double *>(sYstats.dev), c->sSeg.p, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ys_host, sYstats.dev, sizeof ys_host, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the pageable host vectors above must outlive their async copies
 
@@ -779,6 +848,12 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     la.partial = c->sPartial.p;
     la.seg_sum = c->sSeg.p;
     la.loss = loss ? sLoss.dev : nullptr;
+    if (fit) {
+        la.kind = (jtj_out ? FIT_MODE_JTJ : FIT_MODE_PLAIN) - 1;
+        la.param = ys_host[1];
+        la.stats = static_cast<double *>(sStats.dev);
+        la.ystats = static_cast<double *>(sYstats.dev);
+    }
     GradArgs g;
     std::memset(&g, 0, sizeof g);
     g.generic_code = p->d_gcode;
@@ -817,7 +892,15 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     g.n_cols = n_cols;
     g.dloss = sDl.dev;
     g.dloss_off = static_cast<const int64_t *>(c->sDoff.p);
-    if (gn) { // always forward duals: the reverse kernel has no dual rows
+    if (fit) { // always forward duals as well
+        g.fit = true;
+        g.fit_jtj = jtj_out != nullptr;
+        g.fit_seg = reinterpret_cast<double *>(static_cast<char *>(c->sSeg.p) + fit_pre_bytes);
+        if (jtj_out) {
+            g.jtj = sJ.dev;
+            g.jtj_off = static_cast<const int64_t *>(c->sJoff.p);
+        }
+    } else if (gn) { // always forward duals: the reverse kernel has no dual rows
         g.gn = true;
         g.jtj = sJ.dev;
         g.jtj_off = static_cast<const int64_t *>(c->sJoff.p);
@@ -859,17 +942,19 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
     if (sDl.staged)
         for (int64_t t = 0; t < p->n_trees; t++)
             if (ng[(size_t)t] > 0)
-                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(dloss) + (size_t)doff[(size_t)t] * es,
-                                          static_cast<char *>(sDl.dev) + (size_t)doff[(size_t)t] * es, (size_t)ng[(size_t)t] * es,
+                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(dloss) + (size_t)doff[(size_t)t] * des,
+                                          static_cast<char *>(sDl.dev) + (size_t)doff[(size_t)t] * des, (size_t)rows_per_g * (size_t)ng[(size_t)t] * des,
                                           hipMemcpyDeviceToHost, c->stream));
+    if (sStats.staged) HIP_TRY(c, hipMemcpyAsync(fit->stats, sStats.dev, (size_t)p->n_trees * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sYstats.staged) HIP_TRY(c, hipMemcpyAsync(fit->ystats, sYstats.dev, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sJ.staged)
         for (int64_t t = 0; t < p->n_trees; t++)
             if (ng[(size_t)t] > 0)
-                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(gn->jtj) + (size_t)joff[(size_t)t] * es,
+                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(jtj_out) + (size_t)joff[(size_t)t] * es,
                                           static_cast<char *>(sJ.dev) + (size_t)joff[(size_t)t] * es,
                                           (size_t)ng[(size_t)t] * (size_t)ng[(size_t)t] * es, hipMemcpyDeviceToHost, c->stream));
     if (sOk.staged) HIP_TRY(c, hipMemcpyAsync(ok, sOk.dev, (size_t)p->n_trees, hipMemcpyDeviceToHost, c->stream));
-    if (sX.staged || sY.staged || sW.staged || sLoss.staged || sDl.staged || sJ.staged || sOk.staged || sPar.staged || sCls.staged)
+    if (sX.staged || sY.staged || sW.staged || sLoss.staged || sDl.staged || sJ.staged || sOk.staged || sPar.staged || sCls.staged || sStats.staged || sYstats.staged)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DE_OK;
 }

@@ -307,7 +307,20 @@ template <typename T> __device__ __noinline__ T loss_kind_curv_ool(int kind, T x
 // What a module of the threaded kernels (de_grad_threaded.hip: 18, de_rev_threaded.hip: 2) hands to the one launch path
 // (de_grad_kernels.hip): the host stubs of its handler-table fill kernel and of its kernel, kernel[PARAMS][SHARE] (the reverse kernel
 // has no SHARE form); kernel_gn: the same kernels with the Gauss-Newton tree end (de_eval_loss_gn; forward modules only).  Every kernel
-// takes (GArgs<T>, handler base, parameter handler offset).
-struct GradModule { const void *fill; const void *kernel[2][2]; const void *kernel_gn[2][2]; };
+// takes (GArgs<T>, handler base, parameter handler offset).  kernel_fit: the same kernels with the fit-statistics tree end
+// (de_eval_fit_stats_grad, g_epilogue_fit; forward modules only).
+struct GradModule { const void *fill; const void *kernel[2][2]; const void *kernel_gn[2][2]; const void *kernel_fit[2][2]; };
+
+// Fit-statistics launches (de_eval_fit_stats_grad; GArgs::loss_mode = FIT_MODE_PLAIN / FIT_MODE_JTJ, GArgs::loss_param =
+// T(mean_y)).  Columns of a tree in `partial`, per (tile of 256 x VS samples, wave):
+//   0 m   1 S1   2 B   3 Cc   4 W_wave   5 R_wave   6 + k: D_k   6 + G + k: P'_k   6 + 2 G + k: Q'_k   6 + 3 G + k (k + 1) / 2 + i: the triangle
+// (the triangle where the tree has at most DE_GN_MAX_ROWS rows and the caller wants the matrix; FIT_COLS, FIT_MODE_*: de_kernels.h).
+// the value wave_sum_to_lane63 left in lane 63, in every lane
+__device__ __forceinline__ float gwave_lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
+__device__ __forceinline__ double gwave_lane63(double v) {
+    const long long b = __double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), 63);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 } // namespace de

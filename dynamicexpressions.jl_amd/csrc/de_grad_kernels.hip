@@ -28,7 +28,8 @@ namespace de {
 // GN: the launch of de_eval_loss_gn — behind the loss and its gradient the tree end also reduces the products
 // sum_j w_j c_j d_i(j) d_k(j), i <= k < G (c = the loss kind's curvature weight, 1 for L2), of a tree whose rows lie in this one window (de_grad_threaded.hip g_epilogue_gn: same columns, same
 // association order).  A template parameter: the other instantiations keep the code they had.
-template <typename T, int GC, bool GN = false>
+// FIT: the launch of de_eval_fit_stats_grad — the tree end of de_grad_threaded.hip g_epilogue_fit, one sample per lane.
+template <typename T, int GC, bool GN = false, bool FIT = false>
 __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
     constexpr int RS = GBLK + 4; // row stride (elements)
     extern __shared__ __align__(16) unsigned char gsmem[];
@@ -219,6 +220,45 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
             poison = M<T>::fma(x, T(0), poison);
             DE_UNROLL for (int k = 0; k < GC; k++) poison = M<T>::fma(g0 + k < G ? d[k] : T(0), T(0), poison); // real rows only
         }
+        if constexpr (FIT) {
+            const int64_t n_cols = col_off[a.n_trees];
+            T *__restrict__ pp = a.partial + ((int64_t)tm.tile * n_cols + col_off[tree]) * 4 + (tid >> 6);
+            const bool in = wv != T(0), l63 = (tid & 63) == 63;
+            const T yc = yv - a.loss_param; // the centred target: loss_param = T(mean_y)
+            const T sw = gwave_lane63(wave_sum_to_lane63(wv)), sy = gwave_lane63(wave_sum_to_lane63(in ? wv * x : T(0)));
+            const T m = sw != T(0) ? sy / sw : T(0);
+            const T dx = x - m;
+            if (g0 == 0) {
+                const T wd = wv * dx;
+                const T s1 = wave_sum_to_lane63(in ? wd : T(0)), b = wave_sum_to_lane63(in ? M<T>::fma(wd, dx, T(0)) : T(0));
+                const T cc = wave_sum_to_lane63(in ? M<T>::fma(wd, yc, T(0)) : T(0)), r = wave_sum_to_lane63(in ? wv * yc : T(0));
+                if (l63) { pp[0] = m; pp[4] = s1; pp[8] = b; pp[12] = cc; pp[16] = sw; pp[20] = r; }
+            }
+            T *__restrict__ pd = pp + FIT_COLS * 4;
+            DE_UNROLL for (int k = 0; k < GC; k++) {
+                if (g0 + k < G) { // wave-uniform
+                    const T wdk = wv * d[k];
+                    const T cd = wave_sum_to_lane63(in ? wdk : T(0)), cp = wave_sum_to_lane63(in ? M<T>::fma(wdk, dx, T(0)) : T(0));
+                    const T cq = wave_sum_to_lane63(in ? M<T>::fma(wdk, yc, T(0)) : T(0));
+                    if (l63) {
+                        pd[(int64_t)(g0 + k) * 4] = cd;
+                        pd[(int64_t)(G + g0 + k) * 4] = cp;
+                        pd[(int64_t)(2 * G + g0 + k) * 4] = cq;
+                    }
+                }
+            }
+            if (a.loss_mode == FIT_MODE_JTJ && g0 == 0 && G <= GC) {
+                T *__restrict__ pj = pd + (int64_t)(3 * G) * 4;
+                DE_UNROLL for (int k = 0; k < GC; k++) {
+                    if (k < G) { // wave-uniform
+                        DE_UNROLL for (int i = 0; i <= k; i++) {
+                            const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wv * d[i]) * d[k]);
+                            if (l63) pj[(k * (k + 1) / 2 + i) * 4] = s;
+                        }
+                    }
+                }
+            }
+        } else
         if (a.loss_mode) {
             const LossTerm<T> lt = loss_term<T>(a.loss_mode, x, yv, wv, a.loss_param);
             const int64_t n_cols = col_off[a.n_trees];
@@ -334,6 +374,178 @@ __global__ void __launch_bounds__(256) de_loss_gn_finish_kernel(const double *__
     }
 }
 
+// ---- de_eval_fit_stats_grad: the recombination of the per-wave columns of g_epilogue_fit, everything in double, every sum
+// in a fixed order.  Two passes over the partials, because the shift of a wave's sums, m - mu, needs the tree's mean mu first.
+struct FitGradReduce {
+    const void *partial;        // [n_tiles][n_cols][4 waves], element type
+    int64_t n_trees, n_cols, n_tiles, tiles_per_seg;
+    int32_t n_segs, gn_max, want_j;
+    const int64_t *col_off;
+    const int32_t *n_grad;
+    const uint8_t *ok;
+    const double *ystats;       // {W, mean_y, M2_y}
+    double *seg_a;              // [n_segs][n_trees]: sum over the segment's waves of m W_wave + S1
+    double *seg_b;              // [n_segs][n_cols][4 waves]
+    const double *tile_r;       // [n_tiles]: sum w yc per 256 samples, in double (the pre-pass over y / w, launch_fit_ystats)
+    double *rsum;               // their sum R = W (mean_y - T(mean_y)), the mean of y to more than a double's precision
+    double *stats, *dmom;
+    const int64_t *dmom_off;
+    void *jtj;
+    const int64_t *jtj_off;
+};
+// Pass 1: thread = one tree, block row = one segment of tiles: the numerator of the tree's mean.
+template <typename T> __global__ void __launch_bounds__(256) de_fit_grad_reduce_mu_kernel(const FitGradReduce a) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n_trees) return;
+    const T *__restrict__ partial = static_cast<const T *>(a.partial);
+    const int64_t r0 = (int64_t)blockIdx.y * a.tiles_per_seg;
+    const int64_t r1 = r0 + a.tiles_per_seg < a.n_tiles ? r0 + a.tiles_per_seg : a.n_tiles;
+    double s = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const T *__restrict__ q = partial + (r * a.n_cols + a.col_off[t]) * 4;
+        for (int w = 0; w < 4; ++w) s += (double)q[w] * (double)q[16 + w] + (double)q[4 + w];
+    }
+    a.seg_a[(int64_t)blockIdx.y * a.n_trees + t] = s;
+}
+__device__ __forceinline__ int64_t fit_grad_owner(const int64_t *__restrict__ col_off, int64_t n_trees, int64_t col) {
+    int64_t lo = 0, hi = n_trees; // col_off[lo] <= col < col_off[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (col_off[mid] <= col) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// Pass 2, with mu known: thread = one column, block row = one segment; per wave slot, over the segment's tiles,
+//   B: B + 2 (m - mu) S1 + W_wave (m - mu)^2      Cc: Cc + (m - mu) R_wave      P'_k: P'_k + (m - mu) D_k,wave      D_k, Q'_k, triangle: as they are
+// — identities for any shift m.  The triangle's sums are de_loss_reduce_tiles_kernel's: the same bits as de_eval_loss_gn's.
+template <typename T> __global__ void __launch_bounds__(256) de_fit_grad_reduce_cols_kernel(const FitGradReduce a) {
+    const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (col >= a.n_cols) return;
+    const int64_t t = fit_grad_owner(a.col_off, a.n_trees, col);
+    const int c = (int)(col - a.col_off[t]), G = a.n_grad[t];
+    const T *__restrict__ partial = static_cast<const T *>(a.partial);
+    double mu = 0.0;
+    for (int32_t g = 0; g < a.n_segs; ++g) mu += a.seg_a[(int64_t)g * a.n_trees + t];
+    mu /= a.ystats[0];
+    const int kind = c == 2 ? 1 : (c == 3 ? 2 : (c >= FIT_COLS + G && c < FIT_COLS + 2 * G ? 3 : 0));
+    const int64_t r0 = (int64_t)blockIdx.y * a.tiles_per_seg;
+    const int64_t r1 = r0 + a.tiles_per_seg < a.n_tiles ? r0 + a.tiles_per_seg : a.n_tiles;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t r = r0; r < r1; ++r) {
+        const T *__restrict__ q = partial + (r * a.n_cols + a.col_off[t]) * 4;
+        for (int w = 0; w < 4; ++w) {
+            double v = (double)q[c * 4 + w];
+            if (kind) {
+                const double dm = (double)q[w] - mu;
+                if (kind == 1) v = (v + (2.0 * dm) * (double)q[4 + w]) + ((double)q[16 + w] * dm) * dm;
+                else if (kind == 2) v = v + dm * (double)q[20 + w];
+                else v = v + dm * (double)q[(c - G) * 4 + w];
+            }
+            s[w] += v;
+        }
+    }
+    for (int w = 0; w < 4; ++w) a.seg_b[(((int64_t)blockIdx.y * a.n_cols) + col) * 4 + w] = s[w];
+}
+// R = sum_tiles tile_r, one block, a fixed order
+__global__ void __launch_bounds__(256) de_fit_grad_rsum_kernel(const double *__restrict__ tile_r, int64_t n_tiles, double *__restrict__ rsum) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n_tiles; i += 256) s += tile_r[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rsum[0] = sh[0];
+}
+// Pass 3: thread = one column: segments in order, the four wave slots inside (de_loss_gn_finish_kernel's order).  NaN where the evaluation
+// was incomplete; W == 0: the mean is NaN, everything else 0.  Q_k = sum Q'_k + (T(mean_y) - mean_y) D_k: unlike C, Q is not invariant under
+// the shift of y — and D_k (W for an additive constant) multiplies whatever error the shift carries, so mean_y is taken as T(mean_y) + R / W
+// with R = sum w (y - T(mean_y)) in double, not as the double ystats[1] (whose rounding alone, times W, exceeds Q's bound for a Float64
+// target with an offset): the shift is -R / W.  The thread of a tree's column 0 writes its mean and, where the tree is wider than
+// gn_max, the NaN block.
+template <typename T> __global__ void __launch_bounds__(256) de_fit_grad_finish_kernel(const FitGradReduce a) {
+    const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (col >= a.n_cols) return;
+    const int64_t t = fit_grad_owner(a.col_off, a.n_trees, col);
+    const int c = (int)(col - a.col_off[t]), G = a.n_grad[t];
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double W = a.ystats[0];
+    const bool good = a.ok[t] != 0, empty = W == 0.0;
+    auto total = [&](int64_t cc) {
+        double s = 0.0;
+        for (int32_t g = 0; g < a.n_segs; ++g)
+            for (int w = 0; w < 4; ++w) s += a.seg_b[(((int64_t)g * a.n_cols) + cc) * 4 + w];
+        return s;
+    };
+    if (c == 0) {
+        double mu = 0.0;
+        for (int32_t g = 0; g < a.n_segs; ++g) mu += a.seg_a[(int64_t)g * a.n_trees + t];
+        mu /= W;
+        a.stats[3 * t] = good && !empty ? mu : nan;
+        if (a.want_j && G > a.gn_max) {
+            T *__restrict__ blk = static_cast<T *>(a.jtj) + a.jtj_off[t];
+            for (int64_t e = 0; e < (int64_t)G * G; e++) blk[e] = M<T>::nan();
+        }
+        return;
+    }
+    if (c == 1 || c == 4 || c == 5) return;
+    double v = empty ? 0.0 : total(col);
+    if (c == 2 || c == 3) {
+        if (c == 2 && v < 0.0) v = 0.0; // (a sum of squares: only the roundings of a constant tree can take it below 0)
+        a.stats[3 * t + (c - 1)] = good ? v : nan;
+    } else if (c < FIT_COLS + 3 * G) {
+        if (c >= FIT_COLS + 2 * G && !empty) {
+            v -= (a.rsum[0] / W) * total(col - 2 * G);
+        }
+        a.dmom[a.dmom_off[t] + (c - FIT_COLS)] = good ? v : nan;
+    } else {
+        const int e = c - FIT_COLS - 3 * G;
+        int k = 0;
+        while ((k + 1) * (k + 2) / 2 <= e) ++k;
+        const int i = e - k * (k + 1) / 2;
+        T *__restrict__ blk = static_cast<T *>(a.jtj) + a.jtj_off[t];
+        const T vj = good ? (T)v : M<T>::nan();
+        blk[i + (int64_t)G * k] = vj;
+        blk[k + (int64_t)G * i] = vj;
+    }
+}
+size_t fit_grad_seg_bytes(int64_t n_trees, int64_t n_cols, int64_t N) {
+    const int64_t n_tiles = (N + GBLK - 1) / GBLK;
+    return ((size_t)loss_segments(n_tiles) * ((size_t)n_trees + 4 * (size_t)n_cols) + 1) * sizeof(double);
+}
+template <typename T> static hipError_t fit_grad_finish_t(const GradArgs &ga, int64_t n_tiles, hipStream_t stream) {
+    FitGradReduce a;
+    a.partial = ga.loss->partial;
+    a.n_trees = ga.e.n_trees;
+    a.n_cols = ga.n_cols;
+    a.n_tiles = n_tiles;
+    a.n_segs = loss_segments(n_tiles);
+    a.tiles_per_seg = (n_tiles + a.n_segs - 1) / a.n_segs;
+    a.gn_max = DE_GN_MAX_ROWS;
+    a.want_j = ga.fit_jtj ? 1 : 0;
+    a.col_off = ga.col_off;
+    a.n_grad = ga.n_grad;
+    a.ok = ga.e.ok;
+    a.ystats = ga.loss->ystats;
+    a.seg_a = ga.fit_seg;
+    a.seg_b = ga.fit_seg + (int64_t)a.n_segs * a.n_trees;
+    a.rsum = a.seg_b + (int64_t)a.n_segs * a.n_cols * 4;
+    a.tile_r = ga.fit_seg - 2 * n_tiles; // (GradArgs::fit_seg: behind the pre-pass's three per-tile arrays {W, R, Q})
+    a.stats = ga.loss->stats;
+    a.dmom = static_cast<double *>(ga.dloss);
+    a.dmom_off = ga.dloss_off;
+    a.jtj = ga.jtj;
+    a.jtj_off = ga.jtj_off;
+    hipLaunchKernelGGL(de_fit_grad_rsum_kernel, dim3(1), dim3(256), 0, stream, a.tile_r, n_tiles, a.rsum);
+    hipLaunchKernelGGL(de_fit_grad_reduce_mu_kernel<T>, dim3((unsigned)((a.n_trees + 255) / 256), (unsigned)a.n_segs), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(de_fit_grad_reduce_cols_kernel<T>, dim3((unsigned)((a.n_cols + 255) / 256), (unsigned)a.n_segs), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(de_fit_grad_finish_kernel<T>, dim3((unsigned)((a.n_cols + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 // ---- one launch path for the three gradient kernels ----------------------------------------------------------------------------------
 // The kernel arguments every gradient kernel shares, from the caller's GradArgs; every other field is 0.  What is particular to a
 // kernel — its code pointers, the trees of the launch (tree_ids / n_trees), n_slots, n_tiles, the parameter rows behind F, share /
@@ -408,7 +620,7 @@ static hipError_t launch_grad_kernel(const void *kern, GArgs<T> a, int windows, 
     return hipLaunchKernel(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), args, lds, stream);
 }
 
-template <typename T, int GC, bool GN = false>
+template <typename T, int GC, bool GN = false, bool FIT = false>
 static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t stream) {
     const EvalArgs &e = ga.e;
     GArgs<T> a = make_gargs<T>(ga);
@@ -420,13 +632,14 @@ static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t str
     a.check = ga.diff_direction >= 0 ? 0 : 1;
     a.diff_g0 = ga.diff_direction >= 0 ? ga.P + ga.diff_direction : -1;
     const size_t lds = (size_t)(a.F + (size_t)a.n_slots * (1 + GC)) * (GBLK + 4) * sizeof(T);
-    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC, GN>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
+    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC, GN, FIT>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
     if (st != hipSuccess || !ga.loss) return st;
     return launch_loss_grad_finish(sizeof(T) == 4 ? DE_F32 : DE_F64, ga, a.n_tiles, stream);
 }
 
 // passes 2 and 3 of the deterministic loss-gradient reduction (pass 2 is shared with de_eval_loss)
 template <typename T> static hipError_t loss_grad_finish_t(const GradArgs &ga, int64_t n_tiles, hipStream_t stream) {
+    if (ga.fit) return fit_grad_finish_t<T>(ga, n_tiles, stream);
     int32_t n_segs = 1;
     hipError_t st = launch_loss_reduce_tiles(sizeof(T) == 4 ? DE_F32 : DE_F64, ga.loss->partial, ga.n_cols * 4, n_tiles, ga.loss->seg_sum,
                                              &n_segs, stream);
@@ -456,16 +669,16 @@ hipError_t launch_loss_grad_finish(int dtype, const GradArgs &ga, int64_t n_tile
     return dtype == DE_F32 ? loss_grad_finish_t<float>(ga, n_tiles, stream) : loss_grad_finish_t<double>(ga, n_tiles, stream);
 }
 
-template <typename T, bool GN = false> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
+template <typename T, bool GN = false, bool FIT = false> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
     const int maxg = ga.max_grad < 1 ? 1 : ga.max_grad;
     // smallest window that covers the widest gradient in one pass, else windows of 8
-    if (maxg <= 1) return launch_grad_t<T, 1, GN>(ga, 1, stream);
-    if (maxg <= 2) return launch_grad_t<T, 2, GN>(ga, 1, stream);
-    if (maxg <= 3) return launch_grad_t<T, 3, GN>(ga, 1, stream);
-    if (maxg <= 4) return launch_grad_t<T, 4, GN>(ga, 1, stream);
-    if (maxg <= 5) return launch_grad_t<T, 5, GN>(ga, 1, stream);
-    if (maxg <= 6) return launch_grad_t<T, 6, GN>(ga, 1, stream);
-    return launch_grad_t<T, 8, GN>(ga, (maxg + 7) / 8, stream);
+    if (maxg <= 1) return launch_grad_t<T, 1, GN, FIT>(ga, 1, stream);
+    if (maxg <= 2) return launch_grad_t<T, 2, GN, FIT>(ga, 1, stream);
+    if (maxg <= 3) return launch_grad_t<T, 3, GN, FIT>(ga, 1, stream);
+    if (maxg <= 4) return launch_grad_t<T, 4, GN, FIT>(ga, 1, stream);
+    if (maxg <= 5) return launch_grad_t<T, 5, GN, FIT>(ga, 1, stream);
+    if (maxg <= 6) return launch_grad_t<T, 6, GN, FIT>(ga, 1, stream);
+    return launch_grad_t<T, 8, GN, FIT>(ga, (maxg + 7) / 8, stream);
 }
 
 // ---- de_eval_loss_grad_by_class: fold the per-class passes into the outputs ---------------------------
@@ -681,11 +894,11 @@ template <typename T> static hipError_t launch_grad_bucket(const GradArgs &ga, c
     a.n_tiles = share ? 4 * ((e.N + GBLK * VS - 1) / (GBLK * VS)) : (e.N + tile_samples - 1) / tile_samples;
     const size_t slot_rows = std::max<size_t>((size_t)a.n_slots * (1 + GC), (size_t)GC);
     const size_t lds = (share ? (size_t)a.F + 4 * slot_rows : 4 * ((size_t)a.F + slot_rows)) * 64 * VS * sizeof(T); // 4 waves x rows x one wave's samples (shared leaf rows: once)
-    return launch_grad_kernel((ga.gn ? m.kernel_gn : m.kernel)[e.uses_params ? 1 : 0][share ? 1 : 0], a, bk.windows, lds, ga.prio_ready ? e.prio_keys : nullptr, tile_samples,
+    return launch_grad_kernel((ga.fit ? m.kernel_fit : ga.gn ? m.kernel_gn : m.kernel)[e.uses_params ? 1 : 0][share ? 1 : 0], a, bk.windows, lds, ga.prio_ready ? e.prio_keys : nullptr, tile_samples,
                               ga.prio_ready, bk.handler_base, bk.param_handler_off, stream); // the loss reduction passes run once, after the last bucket
 }
 hipError_t launch_grad_threaded(int dtype, const GradArgs &a0, hipStream_t stream, const char **kernel_name) {
-    if (kernel_name) *kernel_name = a0.gn ? "de_grad_threaded_kernel<GN>" : "de_grad_threaded_kernel";
+    if (kernel_name) *kernel_name = a0.fit ? "de_grad_threaded_kernel<FIT>" : a0.gn ? "de_grad_threaded_kernel<GN>" : "de_grad_threaded_kernel";
     GradArgs a;
     { const hipError_t ps = grad_prio_prepass(dtype, a0, stream, &a); if (ps != hipSuccess) return ps; }
     if (a.loss) { // two-sample modules use 512-sample tiles: the 256-sample tile slots they never write must read as 0
@@ -767,8 +980,9 @@ hipError_t launch_rev_threaded(int dtype, const GradArgs &a0, hipStream_t stream
 
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name) {
     if (a.threaded_code && a.diff_direction < 0) return launch_grad_threaded(dtype, a, stream, kernel_name);
-    if (kernel_name) *kernel_name = a.gn ? "de_grad_tape_kernel<GN>" : "de_grad_tape_kernel";
+    if (kernel_name) *kernel_name = a.fit ? "de_grad_tape_kernel<FIT>" : a.gn ? "de_grad_tape_kernel<GN>" : "de_grad_tape_kernel";
     if (a.diff_direction >= 0) return dtype == DE_F32 ? launch_grad_t<float, 1>(a, 1, stream) : launch_grad_t<double, 1>(a, 1, stream);
+    if (a.fit) return dtype == DE_F32 ? launch_grad_dt<float, false, true>(a, stream) : launch_grad_dt<double, false, true>(a, stream);
     if (a.gn) return dtype == DE_F32 ? launch_grad_dt<float, true>(a, stream) : launch_grad_dt<double, true>(a, stream);
     if (dtype == DE_F32) return launch_grad_dt<float>(a, stream);
     return launch_grad_dt<double>(a, stream);

@@ -509,6 +509,92 @@ __device__ __noinline__ void g_epilogue_gn_kind(GnRows<T, GC> st, T l, LV(T) lp,
         }
     }
 }
+// Tree end of de_eval_fit_stats_grad: the fit statistics of h_tree_end_stats (de_kernels.hip) with their gradient
+// moments.  ym = T(mean_y) of the pre-pass over y / w; per wave, over the samples that count (weight != 0, inside N — by selects):
+//   m = the weighted mean of the tree's values, formed in T (any shift makes the recombination an identity; this one keeps the sums
+//       free of cancellation)                                   W_wave = sum w              R_wave = sum w yc,  yc = y - ym
+//   S1 = sum w (yhat - m)    B = sum w (yhat - m)^2    Cc = sum w (yhat - m) yc                      (window 0 writes the six)
+//   D_k = sum w d_k          P'_k = sum (w d_k) (yhat - m)          Q'_k = sum (w d_k) yc             (every window: its rows)
+// and, where the caller wants the matrix (want_j) and the tree's rows lie in this one window, the triangle ((w d_i) d_k) in
+// g_epilogue_gn's association and column order, behind the 6 + 3 G columns.  Every product has one factor w: doubling every weight
+// doubles every sum exactly and leaves m alone.  Called by the FIT instantiations of the kernel only.
+template <typename T, int GC, bool SHARE>
+__device__ __noinline__ void g_epilogue_fit(GState<T, GC> st, const T *y_, const T *w_, T *pp_, int64_t N_, T ym_, int G_, int g0_, int64_t tile_, int want_j_) {
+    constexpr int TILE = GBLK * VS, WSAMP = 64 * VS;
+    const T *y = guni(y_), *w = guni(w_);
+    T *pp = const_cast<T *>(guni(static_cast<const T *>(pp_)));
+    const int64_t last = guni(N_) - 1, tile = guni(tile_);
+    const T ym = guni(ym_);
+    const int G = guni(G_), g0 = guni(g0_), want_j = guni(want_j_);
+    const int tid = threadIdx.x, wave = SHARE ? (int)(tile & 3) : tid >> 6, lane = tid & 63;
+    const int64_t jl = SHARE ? tile * WSAMP + (int64_t)lane * VS : tile * TILE + (int64_t)tid * VS; // this lane's first sample
+    LV(T) wv, yc;
+    T sw = T(0), sy = T(0);
+    DE_UNROLL for (int i = 0; i < VS; i++) {
+        const int64_t j = jl + i;
+        const int64_t jj = j < last ? j : last;
+        yc[i] = y[jj] - ym;
+        wv[i] = j <= last ? (w ? w[jj] : T(1)) : T(0);
+        sw += wv[i];
+        sy += wv[i] != T(0) ? wv[i] * st.x[i] : T(0);
+    }
+    sw = gwave_lane63(wave_sum_to_lane63(sw));
+    sy = gwave_lane63(wave_sum_to_lane63(sy));
+    const T m = sw != T(0) ? sy / sw : T(0);
+    LV(T) dx;
+    DE_UNROLL for (int i = 0; i < VS; i++) dx[i] = st.x[i] - m;
+    pp += wave;
+    if (g0 == 0) {
+        T s1 = T(0), b = T(0), cc = T(0), r = T(0);
+        DE_UNROLL for (int i = 0; i < VS; i++) {
+            const bool in = wv[i] != T(0);
+            const T wd = wv[i] * dx[i];
+            s1 += in ? wd : T(0);
+            b = in ? M<T>::fma(wd, dx[i], b) : b;
+            cc = in ? M<T>::fma(wd, yc[i], cc) : cc;
+            r += in ? wv[i] * yc[i] : T(0);
+        }
+        s1 = wave_sum_to_lane63(s1);
+        b = wave_sum_to_lane63(b);
+        cc = wave_sum_to_lane63(cc);
+        r = wave_sum_to_lane63(r);
+        if (lane == 63) { pp[0] = m; pp[4] = s1; pp[8] = b; pp[12] = cc; pp[16] = sw; pp[20] = r; }
+    }
+    T *__restrict__ pd = pp + FIT_COLS * 4;
+    DE_UNROLL for (int k = 0; k < GC; k++) {
+        if (g0 + k < G) { // wave-uniform
+            T cd = T(0), cp = T(0), cq = T(0);
+            DE_UNROLL for (int i = 0; i < VS; i++) {
+                const bool in = wv[i] != T(0);
+                const T wdk = wv[i] * st.d[k][i];
+                cd += in ? wdk : T(0);
+                cp = in ? M<T>::fma(wdk, dx[i], cp) : cp;
+                cq = in ? M<T>::fma(wdk, yc[i], cq) : cq;
+            }
+            cd = wave_sum_to_lane63(cd);
+            cp = wave_sum_to_lane63(cp);
+            cq = wave_sum_to_lane63(cq);
+            if (lane == 63) {
+                pd[(int64_t)(g0 + k) * 4] = cd;
+                pd[(int64_t)(G + g0 + k) * 4] = cp;
+                pd[(int64_t)(2 * G + g0 + k) * 4] = cq;
+            }
+        }
+    }
+    if (want_j && g0 == 0 && G <= GC) {
+        T *__restrict__ pj = pd + (int64_t)(3 * G) * 4;
+        DE_UNROLL for (int k = 0; k < GC; k++) {
+            if (k < G) { // wave-uniform
+                DE_UNROLL for (int i = 0; i <= k; i++) {
+                    T c = T(0);
+                    DE_UNROLL for (int s = 0; s < VS; s++) c += wv[s] == T(0) ? T(0) : (wv[s] * st.d[i][s]) * st.d[k][s];
+                    const T sum = wave_sum_to_lane63(c);
+                    if (lane == 63) pj[(k * (k + 1) / 2 + i) * 4] = sum;
+                }
+            }
+        }
+    }
+}
 // The Jacobian block and the values are written once and never read by the kernel: non-temporal stores (round 5: the eval kernel's output
 // stream gained 2 % from them; -DDE_GRAD_NT_STORE=0 for the A/B)
 #ifndef DE_GRAD_NT_STORE
@@ -568,8 +654,8 @@ __device__ __noinline__ void g_epilogue_store(GState<T, GC> st, T *out_row, T *g
 
 // VS consecutive samples per thread; wave-major LDS: per wave, rows [0,F) = its slice of the X tile, then each
 // spill slot s owns 1+GC rows (x, d[0..GC)); at least GC rows follow the X rows (output staging).
-// GN: the launch of de_eval_loss_gn — the tree end is g_epilogue_gn
-template <typename T, int GC, bool PARAMS, bool SHARE = false, bool GN = false>
+// GN: the launch of de_eval_loss_gn — the tree end is g_epilogue_gn; FIT: the launch of de_eval_fit_stats_grad — g_epilogue_fit
+template <typename T, int GC, bool PARAMS, bool SHARE = false, bool GN = false, bool FIT = false>
 __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a, const uint64_t hbase, const uint32_t param_off) {
     constexpr int TILE = GBLK * VS, WSAMP = 64 * VS; // samples per workgroup / per wave
     extern __shared__ __align__(16) unsigned char gtsmem[];
@@ -657,7 +743,10 @@ __global__ void __launch_bounds__(GBLK) de_grad_threaded_kernel(const GArgs<T> a
         // n_grad (the lone column of a tree without constants in constant mode) holds g*0 terms that are NaN
         // for an infinite partial although the reference's gradient matrix has no such row
         DE_UNROLL for (int k = 0; k < GC; k++) gpoison<T>(poison, g0 + k < G ? st.d[k] : lv_splat<T>(T(0)));
-        if constexpr (GN) {
+        if constexpr (FIT) {
+            const int64_t n_cols = col_off[a.n_all_trees];
+            g_epilogue_fit<T, GC, SHARE>(st, a.y, a.w, a.partial + (ptile * n_cols + col_off[tree]) * 4, a.N, a.loss_param, G, g0, (int64_t)tm.tile, a.loss_mode == FIT_MODE_JTJ);
+        } else if constexpr (GN) {
             const int64_t n_cols = col_off[a.n_all_trees];
             T *pp = a.partial + (ptile * n_cols + col_off[tree]) * 4;
             if (a.loss_mode == 1 + DE_LOSS_L2) g_epilogue_gn<T, GC, SHARE>(st, a.y, a.w, pp, a.N, G, g0, (int64_t)tm.tile);
@@ -694,6 +783,10 @@ GradModule DE_GT_NAME(grad_thr_module_)() {
     m.kernel_gn[0][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, false, true>);
     m.kernel_gn[1][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, true, true>);
     m.kernel_gn[0][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, true, true>);
+    m.kernel_fit[1][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, false, false, true>);
+    m.kernel_fit[0][0] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, false, false, true>);
+    m.kernel_fit[1][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, true, true, false, true>);
+    m.kernel_fit[0][1] = reinterpret_cast<const void *>(&de_grad_threaded_kernel<T, GC, false, true, false, true>);
     return m;
 }
 

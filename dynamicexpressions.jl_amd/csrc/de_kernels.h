@@ -127,6 +127,10 @@ hipError_t launch_tile_extremes(int dtype, const void *X, int64_t N, int64_t ldX
 bool prio_tiles_wanted(int64_t N, int F, int64_t n_trees);
 
 constexpr int DE_GN_MAX_ROWS = 8; // de_gn_max_rows(): the widest window of the forward-dual kernels (a wider tree's rows never meet in one wave)
+// de_eval_fit_stats_grad: the stat columns in front of a tree's gradient-moment columns, and the two values
+// GArgs::loss_mode takes in such a launch (without / with the triangle of the Gauss-Newton matrix)
+constexpr int FIT_COLS = 6;
+constexpr int FIT_MODE_PLAIN = 1, FIT_MODE_JTJ = 2;
 struct GradArgs {
     EvalArgs e;               // e.code is unused: the gradient kernel runs the bound UNFOLDED program
     const BoundInstr *generic_code; // device, +1 pad (bound form of the unfolded generic program)
@@ -148,6 +152,13 @@ struct GradArgs {
     bool gn;
     void *jtj;                // device
     const int64_t *jtj_off;   // device, n_trees
+    // de_eval_fit_stats_grad: the kernels' fit-statistics tree end (loss->kind = FIT_MODE_* - 1, loss->param = mean_y, loss->stats /
+    // loss->ystats as in a fit-statistics launch); a tree owns FIT_COLS + 3 G columns and, where fit_jtj and G <= DE_GN_MAX_ROWS, the
+    // triangle's G (G + 1) / 2 behind them.  dloss / dloss_off: the tree's 3 G doubles {D, P, Q}; jtj / jtj_off as above (fit_jtj).
+    // fit_seg: device scratch (double) of the recombination, fit_grad_seg_bytes(), directly BEHIND the 3 * ceil(N / 256) doubles
+    // launch_fit_ystats was given (the finish pass reads the pre-pass's per-tile sums of w yc)
+    bool fit, fit_jtj;
+    double *fit_seg;
     // threaded-code variant (de_grad_threaded.hip): non-null = use it.  Trees are grouped into buckets by
     // gradient width; each bucket is one launch of the module built for its window width.
     const BoundInstr *threaded_code;
@@ -244,5 +255,10 @@ void fit_stats_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *part
 hipError_t launch_loss_reduce_tiles(int dtype, const void *partial, int64_t n_cols, int64_t n_tiles, void *seg_sum,
                                     int32_t *n_segs, hipStream_t stream);
 int32_t loss_segments(int64_t n_tiles);
+// The pre-pass over y / w of the fit statistics alone (de_eval_fit_stats_grad): ystats = {W, mean_y, M2_y} on the device; scratch:
+// 3 * ceil(N / 256) doubles
+hipError_t launch_fit_ystats(int dtype, const void *y, const void *w, int64_t N, double *ystats, void *scratch, hipStream_t stream);
+// ... and the scratch of its recombination (de_grad_kernels.hip): [segments][n_trees] numerators of the means, [segments][n_cols][4 waves], R
+size_t fit_grad_seg_bytes(int64_t n_trees, int64_t n_cols, int64_t N);
 
 } // namespace de

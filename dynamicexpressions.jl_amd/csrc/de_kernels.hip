@@ -2019,6 +2019,16 @@ template <typename T> static hipError_t launch_fit_prepass(const LossArgs &l, in
     hipLaunchKernelGGL(de_fit_ysum_kernel, dim3(1), dim3(256), 0, stream, (const double *)f.tile_q, (const double *)nullptr, n_tiles, l.ystats, 1);
     return hipGetLastError();
 }
+// the pre-pass alone, over tiles of 256 samples (de_eval_fit_stats_grad: its gradient launch centres the targets on T(mean_y) as well)
+hipError_t launch_fit_ystats(int dtype, const void *y, const void *w, int64_t N, double *ystats, void *scratch, hipStream_t stream) {
+    LossArgs l = {};
+    l.y = y;
+    l.w = w;
+    l.ystats = ystats;
+    l.seg_sum = scratch;
+    const int64_t n_tiles = (N + 255) / 256;
+    return dtype == DE_F32 ? launch_fit_prepass<float>(l, 0, N, n_tiles, 256, stream) : launch_fit_prepass<double>(l, 0, N, n_tiles, 256, stream);
+}
 // behind it: the three recombination passes
 template <typename T> static hipError_t launch_fit_reduce(const LossArgs &l, int64_t n_trees, int64_t n_tiles, const uint8_t *ok, hipStream_t stream) {
     const FitScratch f = fit_scratch(l.seg_sum, n_trees, n_tiles);

@@ -822,6 +822,53 @@ function eval_population_gauss_newton(
            okb .& (ng .<= max_rows)
 end
 
+"""
+    eval_population_fit_stats_grad(pop, X, y; weights=nothing, variable=Val(false), want_jtj=true)
+        -> (stats::NamedTuple, d_sum, d_pred, d_targ, jtj::Vector{Matrix{T}}, ok, has_jtj)
+
+The fit statistics of `eval_population_fit_stats` with their gradients over the rows of `variable`, in one forward-dual launch
+(`de_eval_fit_stats_grad`, DESIGN.md §4.4.6): per tree `d_sum[t] = D = Σ w d`, `d_pred[t] = P = Σ w (ŷ - mean_p) d`,
+`d_targ[t] = Q = Σ w (y - mean_y) d` (`Vector{Float64}`) and `jtj[t] = Σ w d d'` (NaN where `has_jtj[t]` is false).  With
+`b = cov / m2_p` the gradient of the residual under linear scaling is `2b (b P - Q)` and `b² (jtj - D D' / W - P P' / m2_p)` its
+Gauss-Newton matrix with the scale and offset projected out.  For a GraphNode the rows of a shared constant are summed.
+"""
+function eval_population_fit_stats_grad(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing, variable=Val(false),
+    want_jtj::Bool=true,
+) where {T}
+    mode = grad_mode(variable)
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    stats = Matrix{Float64}(undef, 3, pop.n_trees)
+    ystats = Vector{Float64}(undef, 3)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    dm, jt, ng, moffs, joffs = with_pop(pop) do hc, hp
+        ng, offs = grad_widths(hp, pop.n_trees, mode)
+        moffs = 3 .* offs
+        joffs = Int64[0; cumsum(ng .* ng)]
+        dm = Vector{Float64}(undef, max(moffs[end], 1))
+        jt = fill(T(NaN), max(joffs[end], 1))
+        check(pop.ctx, GC.@preserve X y weights stats ystats dm jt moffs joffs ok ccall(
+            (:de_eval_fit_stats_grad, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), stats, ystats,
+            dm, moffs, want_jtj ? pointer(jt) : C_NULL, joffs, ok))
+        (dm, jt, ng, moffs, joffs)
+    end
+    max_rows = ccall((:de_gn_max_rows, LIBDE), Cint, ())
+    okb = ok .!= 0x00
+    rows(q) = [combine_rows(pop, t, dm[(moffs[t] + q * ng[t] + 1):(moffs[t] + (q + 1) * ng[t])], mode) for t in 1:pop.n_trees]
+    jtj = map(1:pop.n_trees) do t
+        H = reshape(jt[(joffs[t] + 1):joffs[t + 1]], ng[t], ng[t])
+        half = combine_rows(pop, t, H, mode)
+        Matrix(transpose(combine_rows(pop, t, Matrix(transpose(half)), mode)))
+    end
+    st = (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3])
+    return st, rows(0), rows(1), rows(2), jtj, okb, okb .& (ng .<= max_rows) .& want_jtj
+end
+
 struct LmOpts               # de_lm_opts_t
     iters::Int32
     reserved::Int32

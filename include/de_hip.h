@@ -82,7 +82,9 @@ extern "C" {
  *      (h) de_gn_lm_step, de_fit_consts_lm (with de_lm_opts_t) and the host-only hook de_lm_solve_host: Levenberg-Marquardt on the
  *      constants of a population on the device, DE_F32 / DE_F64.
  *      (i) de_gn_spec_check, de_eval_loss_gn_ex, de_fit_consts_lm_ex: the Gauss-Newton matrix and the fit under every loss kind that has a
- *      curvature; de_eval_loss_gn and de_fit_consts_lm forward to them with {DE_LOSS_L2, 0, 0}: the same bits. */
+ *      curvature; de_eval_loss_gn and de_fit_consts_lm forward to them with {DE_LOSS_L2, 0, 0}: the same bits.
+ *      (j) de_eval_fit_stats_grad: the fit statistics with their gradient moments and the Gauss-Newton matrix — what a
+ *      fit of the constants under linear scaling a + b yhat needs. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -544,6 +546,29 @@ int de_eval_loss_gn(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N,
                     void *loss, void *dloss, const int64_t *dloss_offsets,
                     void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
 int de_gn_max_rows(void); /* 8 */
+
+/* The fit statistics of de_eval_fit_stats with their gradients: per tree, fused into ONE forward-dual launch,
+ *   stats[3 t + 0..2], ystats[0..2]                     de_eval_fit_stats' values, layout and rules (same bounds, not the same bits)
+ *   dmom[doff_t + k]           D_k = sum_j w_j d_k(j)                          d mean_p / d theta_k = D_k / W
+ *   dmom[doff_t + G_t + k]     P_k = sum_j w_j (yhat_j - mean_p) d_k(j)        d M2_p / d theta_k   = 2 P_k
+ *   dmom[doff_t + 2 G_t + k]   Q_k = sum_j w_j (y_j - mean_y) d_k(j)           d C / d theta_k      = Q_k
+ *   jtj[joff_t + i + G_t k]    sum_j w_j d_i(j) d_k(j): de_eval_loss_gn's block, bit for bit (jtj == NULL: no matrix wanted)
+ * d_k over the gradient rows of `mode` in de_eval_grad's order, G_t = de_program_n_grad(prog, t, mode).  With b = C / M2_p the gradient
+ * of the residual of the least-squares a + b yhat is 2 b (b P_k - Q_k), and b^2 (jtj - D D^T / W - P P^T / M2_p) is its Gauss-Newton
+ * matrix with (a, b) projected out: the Levenberg-Marquardt step under linear scaling.  stats, ystats and dmom are DOUBLE whatever the
+ * dtype; jtj has the program's element type, both triangles written, exactly symmetric.  dmom_offsets == NULL: packed, 3 G_t doubles
+ * each; jtj_offsets as for de_eval_loss_gn; a negative offset is DE_ERR_INVALID_ARG.  Pointers may be host or device.  w == NULL:
+ * weight 1; a weight of 0 excludes the sample.  ok[t] is de_eval_loss_grad's forward-dual flag (always forward duals:
+ * DE_OPT_REVERSE_GRAD is ignored); where ok[t] == 0, stats[3t..], the tree's dmom entries and its jtj block are NaN.  W == 0 (N == 0
+ * included): the means are NaN, every second moment, dmom entry and jtj entry 0.  A tree with G_t > de_gn_max_rows() gets stats and dmom
+ * as usual and a NaN jtj block.  DE_F16 / complex programs: DE_ERR_UNSUPPORTED; a null y / stats / ystats / dmom / ok on a non-empty
+ * population or a bad mode: DE_ERR_INVALID_ARG; both before any output is touched.  Scratch, from the context's pools like the
+ * loss: ceil(N / 256) x columns x 4 partial sums of the element type, columns = sum_t [6 + 3 G_t + (jtj && G_t <= 8 ? G_t (G_t + 1) / 2 : 0)],
+ * and min(ceil(N / 256), 64) x (n_trees + 4 columns) + 3 ceil(N / 256) + 1 doubles.  Fixed reduction order: reproducible run to run. */
+int de_eval_fit_stats_grad(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                           const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                           double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets,
+                           void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
 
 /* The same under any loss kind that has a curvature: generalised Gauss-Newton / iteratively reweighted least squares.
  *   loss[t], dloss[..]      = de_eval_loss_grad_ex's for the same spec, bit for bit
