@@ -54,6 +54,7 @@ EXPORTS = [
     "de_dist_set_timeout", "de_ctx_trim", "de_program_set_consts_device", "de_program_get_consts", "de_program_consts_device_path",
     "de_lower_tape_assured", "de_lower_tape_assured_parts", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
     "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex", "de_eval_fit_stats_grad",
+    "de_gn_wide_max_rows", "de_eval_loss_gn_wide", "de_lm_solve_host_wide", "de_gn_lm_step_wide", "de_fit_consts_lm_wide",
 ]
 
 
@@ -172,6 +173,7 @@ class FitStats:
 
 
 GN_MAX_ROWS = 8  # de_gn_max_rows(): the widest tree (gradient rows of the library's layout) de_eval_loss_gn forms the matrix of
+GN_WIDE_MAX_ROWS = 32  # de_gn_wide_max_rows(): ... and de_eval_loss_gn_wide (``wide=True``)
 
 
 def gn_offsets(n_grad):
@@ -264,21 +266,22 @@ class GaussNewton:
         ctx, dl, jt, ng, n = pk["ctx"], pk["dloss"], pk["jtj"], pk["n_grad"], len(self)
         total = max(int(ng.sum()), 1)
         lib = library()
+        lm_step = lib.de_gn_lm_step_wide if pk.get("wide") else lib.de_gn_lm_step  # (eval_gauss_newton(wide=True): trees of up to 32 rows)
         if _is_torch(dl):
             import torch
             ctx.use_torch_stream()
             lams = torch.as_tensor(lam, dtype=torch.float64, device=dl.device).expand(n).contiguous()
             has = self.has_jtj.to(torch.uint8).contiguous()
             step = torch.zeros(total, dtype=torch.float64, device=dl.device)
-            ctx.check(lib.de_gn_lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.data_ptr(), None, jt.data_ptr(), None, has.data_ptr(),
-                                        lams.data_ptr(), step.data_ptr()))
+            ctx.check(lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.data_ptr(), None, jt.data_ptr(), None, has.data_ptr(),
+                              lams.data_ptr(), step.data_ptr()))
             self._lm_keep = (lams, has)  # (read in stream order)
             return step[:int(ng.sum())]
         lams = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (n,)))
         has = np.ascontiguousarray(np.asarray(self.has_jtj), dtype=np.uint8)
         step = np.zeros(total, dtype=np.float64)
-        ctx.check(lib.de_gn_lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.ctypes.data, None, jt.ctypes.data, None, has.ctypes.data,
-                                    lams.ctypes.data, step.ctypes.data))
+        ctx.check(lm_step(ctx._h, pk["dtype"], n, ng.ctypes.data, dl.ctypes.data, None, jt.ctypes.data, None, has.ctypes.data,
+                          lams.ctypes.data, step.ctypes.data))
         return step[:int(ng.sum())]
 
 
@@ -390,6 +393,19 @@ def lm_solve_host(H, g, lam: float):
     return step[:G], bool(rc)
 
 
+def lm_solve_host_wide(H, g, lam: float):
+    """``de_lm_solve_host_wide``: ``lm_solve_host`` for systems of up to ``GN_WIDE_MAX_ROWS`` rows — ``lm_solve_host``'s bits for G <= 8,
+    the same arithmetic without the padding (csrc/de_lm_solve_wide.h) beyond; the zero step for any other G."""
+    H = np.asfortranarray(H, dtype=np.float64)
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+    G = g.size
+    if H.shape != (G, G):
+        raise ValueError("H must be G x G for a gradient of G entries")
+    step = np.full(max(G, 1), np.nan, dtype=np.float64)
+    rc = library().de_lm_solve_host_wide(G, H.ctypes.data, g.ctypes.data, float(lam), step.ctypes.data)
+    return step[:G], bool(rc)
+
+
 def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
 
@@ -494,6 +510,12 @@ def library() -> C.CDLL:
                                             C.POINTER(LmOpts), vp, vp, vp, vp]
     if hasattr(lib, "de_eval_fit_stats_grad"):  # (absent from a library built before the fit statistics had gradients: DE_HIP_LIB in an A/B run)
         lib.de_eval_fit_stats_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "de_eval_loss_gn_wide"):  # (absent from a library built before the wide Gauss-Newton route: DE_HIP_LIB in an A/B run)
+        lib.de_gn_wide_max_rows.argtypes = []
+        lib.de_eval_loss_gn_wide.argtypes = lib.de_eval_loss_gn_ex.argtypes
+        lib.de_lm_solve_host_wide.argtypes = lib.de_lm_solve_host.argtypes
+        lib.de_gn_lm_step_wide.argtypes = lib.de_gn_lm_step.argtypes
+        lib.de_fit_consts_lm_wide.argtypes = lib.de_fit_consts_lm_ex.argtypes
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1440,7 +1462,8 @@ class Population:
         return lo, [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))], ok.astype(bool)
 
     def eval_gauss_newton(self, X, y, weights=None, variable: Union[bool, str] = False, params=None, classes=None,
-                          class_base: int = 1, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4) -> GaussNewton:
+                          class_base: int = 1, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4,
+                          wide: bool = False) -> GaussNewton:
         """Fused Gauss-Newton normal equations per tree (``de_eval_loss_gn_ex``): the loss and its gradient exactly as
         ``eval_loss_grad(loss=loss, loss_param=loss_param)`` returns them, and ``jtj[t] = sum_j w_j c_j d(j) d(j)^T`` over the gradient
         rows ``variable`` selects (default: the constants) — what a Levenberg-Marquardt step needs, without the [n_grad, N] Jacobian.
@@ -1448,7 +1471,9 @@ class Population:
         unbounded at a zero residual ("L1", "l1_eps", "quantile", "lp" with p < 2; the others ignore it); "l1_hinge" and "pullback" have no
         such matrix (``gn_loss_spec``).  numpy in -> numpy out, torch device tensors in -> tensors out.  A tree of more than
         ``GN_MAX_ROWS`` rows (the library's per-occurrence rows, for a GraphNode) has ``has_jtj`` False and a NaN matrix; its loss and
-        gradient are filled as usual."""
+        gradient are filled as usual.  ``wide=True`` (``de_eval_loss_gn_wide``) also forms the matrix of a tree of up to
+        ``GN_WIDE_MAX_ROWS`` rows — ``has_jtj = ok & (G <= 32)``; everything else keeps the bits of the default call — and makes
+        ``lm_step_device`` solve those trees too; a population with shared GraphNode subtrees is refused by the library."""
         self._refuse_f16("eval_gauss_newton")
         spec = gn_loss_spec(loss, loss_param, e_floor)
         mode = _grad_mode(variable)
@@ -1463,7 +1488,8 @@ class Population:
         ng = self._n_grad_all(mode)
         offs, joffs = gn_offsets(ng)
         total, jtotal = max(int(offs[-1]), 1), max(int(joffs[-1]), 1)
-        narrow = ng <= GN_MAX_ROWS
+        narrow = ng <= (GN_WIDE_MAX_ROWS if wide else GN_MAX_ROWS)
+        eval_gn = lib.de_eval_loss_gn_wide if wide else lib.de_eval_loss_gn_ex
 
         def vec(v, name):
             if v is None:
@@ -1487,9 +1513,9 @@ class Population:
             kw = dict(dtype=keep_x.dtype, device=keep_x.device)
             lo, dl, jt = torch.empty(self.n_trees, **kw), torch.empty(total, **kw), torch.empty(jtotal, **kw)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
-            self.ctx.check(lib.de_eval_loss_gn_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
-                                                  C.byref(spec), float(e_floor), lo.data_ptr(), dl.data_ptr(), offs.ctypes.data,
-                                                  jt.data_ptr(), joffs.ctypes.data, ok.data_ptr()))
+            self.ctx.check(eval_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                   C.byref(spec), float(e_floor), lo.data_ptr(), dl.data_ptr(), offs.ctypes.data,
+                                   jt.data_ptr(), joffs.ctypes.data, ok.data_ptr()))
             grads = [self._combine_rows(t, d, mode) for t, d in enumerate(torch.split(dl[:int(offs[-1])], ng.tolist()))]
             mats = [jt[joffs[t]:joffs[t + 1]].view(int(ng[t]), int(ng[t])).t() for t in range(self.n_trees)]
             okb = ok.bool()
@@ -1497,9 +1523,9 @@ class Population:
         else:
             lo, dl, jt = np.empty(self.n_trees, dtype=self.dtype), np.empty(total, dtype=self.dtype), np.empty(jtotal, dtype=self.dtype)
             ok = np.zeros(self.n_trees, dtype=np.uint8)
-            self.ctx.check(lib.de_eval_loss_gn_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
-                                                  C.byref(spec), float(e_floor), lo.ctypes.data, dl.ctypes.data, offs.ctypes.data,
-                                                  jt.ctypes.data, joffs.ctypes.data, ok.ctypes.data))
+            self.ctx.check(eval_gn(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+                                   C.byref(spec), float(e_floor), lo.ctypes.data, dl.ctypes.data, offs.ctypes.data,
+                                   jt.ctypes.data, joffs.ctypes.data, ok.ctypes.data))
             grads = [self._combine_rows(t, d, mode) for t, d in enumerate(np.split(dl[:int(offs[-1])], offs[1:-1]))]
             mats = [jt[joffs[t]:joffs[t + 1]].reshape((int(ng[t]), int(ng[t])), order="F") for t in range(self.n_trees)]
             okb = ok.astype(bool)
@@ -1509,12 +1535,12 @@ class Population:
         gn = GaussNewton(lo, grads, mats, okb, has)
         # the packed buffers the views above look into: GaussNewton.lm_step_device hands them to de_gn_lm_step as they are
         gn._packed = dict(ctx=self.ctx, dtype=_dtype_code(self.dtype), n_grad=np.ascontiguousarray(ng, dtype=np.int32), dloss=dl, jtj=jt,
-                          occ=occ is not None)
+                          occ=occ is not None, wide=bool(wide))
         return gn
 
     def fit_constants_lm(self, X, y, consts0, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0, down: float = 0.1,
                          history: Optional[list] = None, loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4,
-                         scaled: bool = False):
+                         scaled: bool = False, wide: bool = False):
         """Levenberg-Marquardt on the constants of every tree at once (the plain loop; one ``eval_gauss_newton`` per iteration behind
         the one at ``consts0``), minimising the loss kind ``loss`` (``eval_gauss_newton``'s keywords): per tree the step ``GaussNewton.lm_step(lam_t)`` is accepted if the loss decreased (``lam_t *= down``,
         floor 1e-12), else the tree's constants are restored (``lam_t *= up``).  ``consts0``: ``set_constants``' layout.  Trees without
@@ -1526,7 +1552,12 @@ class Population:
         ``eval_fit_stats_grad(...).projected()`` — the same loop, the same accept rule.  Returns (consts, scaled_sse,
         ok); the caller reads ``slope`` and ``intercept`` from ``eval_fit_stats`` at the result.  Resolution of the accept rule:
         ``scaled_sse = m2_y - cov^2 / m2_p`` cancels near a perfect fit, so the statistics' bounds resolve it to about ``1024 u m2_y`` (u =
-        2^-24 / 2^-53); the loop only takes steps that lower it, so that noise bounds how far a fit proceeds, not what it may return."""
+        2^-24 / 2^-53); the loop only takes steps that lower it, so that noise bounds how far a fit proceeds, not what it may return.
+
+        ``wide=True``: every evaluation is ``eval_gauss_newton(wide=True)``, so trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted
+        too (``lm_step`` solves any width); not with ``scaled=True`` (the fit statistics form no wide matrix: a ``ValueError``)."""
+        if scaled and wide:
+            raise ValueError("fit_constants_lm(scaled=True, wide=True): the fit statistics form no matrix for trees of more than 8 rows")
         if scaled and loss != "L2":
             raise ValueError(f"fit_constants_lm(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
         consts = np.array(consts0, dtype=self.dtype).reshape(-1).copy()
@@ -1535,7 +1566,7 @@ class Population:
         at = np.zeros(self.n_trees + 1, dtype=np.int64)
         np.cumsum(self.n_consts, out=at[1:])
         gn_loss_spec(loss, loss_param, e_floor)  # (refused before the population's constants are touched)
-        kind = dict(loss=loss, loss_param=loss_param, e_floor=e_floor)
+        kind = dict(loss=loss, loss_param=loss_param, e_floor=e_floor, wide=wide)
         evaluate = (lambda: self.eval_fit_stats_grad(X, y, weights=weights).projected()) if scaled else \
             (lambda: self.eval_gauss_newton(X, y, weights=weights, **kind))
         self.set_constants(consts)
@@ -1568,14 +1599,16 @@ class Population:
 
     def fit_constants_lm_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
                                 down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1,
-                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4):
+                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4, wide: bool = False):
         """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm_ex``): the steps are solved, the trial constants
         set, and the accept rule applied on the device; no constant, gradient or matrix reaches the host.  ``consts0``: a numpy array or a
         torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.  Returns (consts, loss[n_trees] in
         the population's dtype, ok) at the accepted constants, which the population holds afterwards; with torch inputs all three are
         device tensors and nothing synchronises beyond what ``eval_gauss_newton`` does.  ``history`` (a list) receives the ``iters + 1``
         rows of accepted losses (float64); ``self.lm_accepts`` holds the number of accepted steps per tree.  The step is a Cholesky solve
-        (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it."""
+        (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it.
+        ``wide=True`` (``de_fit_consts_lm_wide``): trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted too; a tree of
+        at most ``GN_MAX_ROWS`` follows the default call's trajectory bit for bit."""
         self._refuse_f16("fit_constants_lm_device")
         spec = gn_loss_spec(loss, loss_param, e_floor)
         if self._occ is not None:
@@ -1628,8 +1661,8 @@ class Population:
             lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
             hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
             ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-        self.ctx.check(lib.de_fit_consts_lm_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
-                                               float(e_floor), C.byref(opts), *ptrs))
+        fit = lib.de_fit_consts_lm_wide if wide else lib.de_fit_consts_lm_ex
+        self.ctx.check(fit(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec), float(e_floor), C.byref(opts), *ptrs))
         self.lm_accepts = acc
         if history is not None:
             history.extend(hist[r] for r in range(rows))

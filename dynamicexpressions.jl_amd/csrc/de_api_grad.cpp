@@ -6,6 +6,8 @@
 #include "de_grad_encode.h"
 #include "de_lm.h"
 #include "de_lm_solve.h"
+#include "de_gn_wide.h"
+#include "de_lm_solve_wide.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -484,11 +486,11 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         rc = stage_in(c, c->sY, dY, (size_t)N * es, &sDY);
         if (rc) return rc;
     }
-    HIP_TRY(c, time_begin(c));
+    if (!c->nested) HIP_TRY(c, time_begin(c));
     HIP_TRY(c, launch_grad(p->dtype, g, c->stream, &c->last_kernel));
     if (dY) // the pullback's dX .* dY' (and its NaN fill) on the Jacobians just written
         HIP_TRY(c, launch_pullback_scale(p->dtype, sGrad.dev, g.grad_off, g.n_grad, g.e.ok, sDY.dev, N, p->n_trees, maxg, c->stream));
-    HIP_TRY(c, time_end(c));
+    if (!c->nested) HIP_TRY(c, time_end(c));
     if (out && sOut.staged)
         for (int64_t t = 0; t < p->n_trees; t++)
             HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(out) + (size_t)t * (size_t)ld_out * es,
@@ -550,6 +552,7 @@ struct GnPlan {
     void *jtj;
     const int64_t *jtj_offsets;
     double e_floor;
+    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_loss_gn_wide: DE_GN_WIDE_MAX_ROWS)
 };
 // de_eval_fit_stats_grad: the same launch with the kernels' fit-statistics tree end.  A tree owns FIT_COLS + 3 G reduction
 // columns and, where a matrix is wanted and G <= DE_GN_MAX_ROWS, G (G + 1) / 2 more; loss_grad_impl's dloss / dloss_offsets carry dmom and
@@ -738,7 +741,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
             std::vector<unsigned char> zj((size_t)std::max<int64_t>(jspan, 1) * es);
             for (int64_t t = 0; t < p->n_trees; t++) {
                 const int64_t gg = (int64_t)ng[(size_t)t] * ng[(size_t)t];
-                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= DE_GN_MAX_ROWS ? 0.0 : std::nan("");
+                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= gn->rows_n0 ? 0.0 : std::nan("");
                 for (int64_t e = 0; e < gg; e++) put(zj.data(), joff[(size_t)t] + e, v);
             }
             for (int64_t t = 0; t < p->n_trees; t++)
@@ -1192,7 +1195,7 @@ static size_t lm_place(size_t *at, size_t bytes) {
 }
 
 static int gn_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
-                           const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+                           const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step, bool wide = false) {
     if (!c) return DE_ERR_INVALID_ARG;
     if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_gn_lm_step: dtype must be DE_F32 or DE_F64");
     if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
@@ -1234,6 +1237,10 @@ static int gn_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_
     if (!c->nested) HIP_TRY(c, time_begin(c));
     HIP_TRY(c, launch_lm_step(dtype, a, c->stream));
     c->last_kernel = "de_lm_step_kernel";
+    if (wide) { // de_gn_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step the kernel above gave them
+        HIP_TRY(c, launch_lm_step_wide(dtype, a, c->stream));
+        c->last_kernel = "de_lm_step_wide_kernel";
+    }
     if (!c->nested) HIP_TRY(c, time_end(c));
     if (h_step) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, span * 8, hipMemcpyDeviceToHost, c->stream));
     if (h_dl || h_j || h_has || h_lam || h_step) HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1244,9 +1251,14 @@ int de_gn_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad
     DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step));
 }
 
+static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
+                        const int64_t *jtj_offsets, uint8_t *ok);
+// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm: every evaluation is de_eval_loss_gn_ex's) or
+// DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_wide: de_eval_loss_gn_wide's, and the wide trees' steps by de_lm_step_wide_kernel)
 static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                               const void *w, const de_loss_spec_t *spec_in, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
-                              double *history, int32_t *n_accept) {
+                              double *history, int32_t *n_accept, int row_limit) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     {
@@ -1325,8 +1337,13 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
     const de_loss_spec_t spec = *spec_in;
     {
         Nest nest(c);
-        const GnPlan gnA{jA, nullptr, e_floor}, gnT{jT, nullptr, e_floor};
-        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lA, dA, nullptr, okA, nullptr, false, &gnA);
+        const bool wide = row_limit > DE_GN_MAX_ROWS;
+        auto evaluate = [&](void *l, void *d, void *j, uint8_t *k) {
+            if (wide) return gn_wide_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, e_floor, l, d, nullptr, j, nullptr, k);
+            const GnPlan gn{j, nullptr, e_floor};
+            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, l, d, nullptr, k, nullptr, false, &gn);
+        };
+        rc = evaluate(lA, dA, jA, okA);
         if (rc != DE_OK) return rc;
         HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
         HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist, c->stream));
@@ -1360,10 +1377,12 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
             a.lam = lam;
             a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
             a.n_accept = acc;
+            a.row_limit = row_limit;
             for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
                 HIP_TRY(c, launch_lm_step(p->dtype, s, c->stream));
+                if (wide) HIP_TRY(c, launch_lm_step_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
                 rc = set_consts_device_impl(p, cT);
-                if (rc == DE_OK) rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, lT, dT, nullptr, okT, nullptr, false, &gnT);
+                if (rc == DE_OK) rc = evaluate(lT, dT, jT, okT);
                 if (rc != DE_OK) break;
                 a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
                 HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
@@ -1386,12 +1405,260 @@ int de_fit_consts_lm_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
                         const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
                         double *history, int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_lm");
-    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept));
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_MAX_ROWS));
 }
 int de_fit_consts_lm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                      const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
     const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
     return de_fit_consts_lm_ex(c, p, X, N, ldX, pa, y, w, &spec, 0.0, opts, loss, ok, history, n_accept);
+}
+
+// ---- de_eval_loss_gn_wide / de_gn_lm_step_wide / de_fit_consts_lm_wide / de_lm_solve_host_wide (kernels: de_gn_wide.hip) ----
+int de_gn_wide_max_rows(void) { return DE_GN_WIDE_MAX_ROWS; }
+
+int de_lm_solve_host_wide(int G, const double *H, const double *g, double lam, double *step) {
+    if (G <= LM_MAX_ROWS) return de_lm_solve_host(G, H, g, lam, step); // (lm_solve8 itself: the same bits by construction)
+    double x[LM_WIDE_MAX_ROWS], work[LMW_WORK];
+    const int solved = G <= LM_WIDE_MAX_ROWS && H && g ? lm_solve_wide<double>(G, H, g, lam, x, work) : 0;
+    if (step)
+        for (int k = 0; k < G; k++) step[k] = solved ? x[k] : 0.0;
+    return solved;
+}
+
+void gn_wide_release(de_program *p) {
+    if (!p || !p->gnw) return;
+    GnWideCache *gw = p->gnw;
+    p->gnw = nullptr;
+    if (gw->sub) de_program_destroy(gw->sub);
+    if (gw->d_cidx) (void)hipFree(gw->d_cidx);
+    if (gw->d_tab) (void)hipFree(gw->d_tab);
+    delete gw;
+}
+
+// The hidden sub-program of the wide trees in `mode` (same dtype, features, parameters and options: de_eval_grad's rows of a tree do not
+// depend on its neighbours).  Its constants are placeholders until the first mirror (gn_wide_mirror).
+static int gn_wide_cache(de_ctx *c, de_program *p, int mode, const std::vector<int32_t> &ng) {
+    if (p->gnw && p->gnw->mode == mode) return DE_OK;
+    if (p->in_noff.size() != (size_t)p->n_trees + 1)
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss_gn_wide: the program keeps no input to build the wide trees' program from");
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (queued work may still run the sub-program of another mode)
+    gn_wide_release(p);
+    std::unique_ptr<GnWideCache> gw(new GnWideCache());
+    std::vector<de_tape_node_t> nodes;
+    std::vector<int64_t> noff{0}, coff{0}, cidx;
+    for (int64_t t = 0; t < p->n_trees; t++) {
+        const int32_t g = ng[(size_t)t];
+        if (g <= DE_GN_MAX_ROWS || g > DE_GN_WIDE_MAX_ROWS) continue;
+        gw->trees.push_back((int32_t)t);
+        gw->rows.push_back(g);
+        nodes.insert(nodes.end(), p->in_nodes.begin() + p->in_noff[(size_t)t], p->in_nodes.begin() + p->in_noff[(size_t)t + 1]);
+        noff.push_back((int64_t)nodes.size());
+        for (int64_t k = p->const_off[(size_t)t]; k < p->const_off[(size_t)t + 1]; k++) cidx.push_back(k);
+        coff.push_back((int64_t)cidx.size());
+    }
+    gw->n_consts = (int64_t)cidx.size();
+    const size_t ies = dtype_bytes(p->io);
+    std::vector<unsigned char> ones(std::max<size_t>(cidx.size(), 1) * ies);
+    for (size_t k = 0; k < cidx.size(); k++) store_elem(p->io, ones.data(), k, 1.0);
+    const int rc = de_program_create(c, p->io, nodes.data(), noff.data(), (int64_t)gw->trees.size(), ones.data(), coff.data(), p->n_features, p->n_params,
+                                     p->options, &gw->sub);
+    if (rc != DE_OK) return rc;
+    if (!cidx.empty()) {
+        hipError_t st = hipMalloc(reinterpret_cast<void **>(&gw->d_cidx), cidx.size() * sizeof(int64_t));
+        if (st == hipSuccess) st = hipMemcpy(gw->d_cidx, cidx.data(), cidx.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (st != hipSuccess) {
+            (void)hipGetLastError();
+            de_program_destroy(gw->sub);
+            if (gw->d_cidx) (void)hipFree(gw->d_cidx);
+            return fail(c, DE_ERR_HIP, "de_eval_loss_gn_wide: constant index table: %s", hipGetErrorString(st));
+        }
+    }
+    gw->mode = mode;
+    p->gnw = gw.release();
+    return DE_OK;
+}
+
+// Samples per chunk (de_gn_wide.h): (rows + n_wide) * chunk * es <= 256 MiB, a multiple of 256, or DE_GN_WIDE_CHUNK rounded up to 64
+static int64_t gn_wide_chunk(int64_t N, int64_t rows, int64_t n_wide, size_t es) {
+    if (const char *env = getenv("DE_GN_WIDE_CHUNK")) {
+        const long long v = atoll(env);
+        if (v > 0) return std::min<int64_t>((int64_t)((v + 63) / 64 * 64), (N + 63) / 64 * 64);
+    }
+    const int64_t per = std::max<int64_t>((rows + n_wide) * (int64_t)es, 1);
+    int64_t chunk = ((int64_t)256 << 20) / per / 256 * 256;
+    chunk = std::max<int64_t>(chunk, 256);
+    return std::min<int64_t>(chunk, (N + 255) / 256 * 256);
+}
+
+static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
+                        const int64_t *jtj_offsets, uint8_t *ok) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss_gn_wide: a program made by de_program_create_cse has one gradient row per occurrence of a "
+                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
+    const GnPlan gn{jtj, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
+    // The wide trees.  None (or no sample, or arguments the narrow call refuses): exactly de_eval_loss_gn_ex's path, no further launch.
+    const bool mode_ok = mode == DE_GRAD_VARIABLE || mode == DE_GRAD_CONSTANT || mode == DE_GRAD_BOTH;
+    std::vector<int32_t> ng((size_t)p->n_trees);
+    std::vector<int64_t> joff((size_t)p->n_trees);
+    int64_t n_wide = 0, rows = 0, tri = 0, jspan = 0, jrun = 0;
+    bool neg = false;
+    for (int64_t t = 0; t < p->n_trees && mode_ok; t++) {
+        const int32_t g = (int32_t)de_program_n_grad(p, t, mode);
+        ng[(size_t)t] = g;
+        joff[(size_t)t] = jtj_offsets ? jtj_offsets[t] : jrun;
+        neg = neg || joff[(size_t)t] < 0 || (dloss_offsets && dloss_offsets[t] < 0);
+        jrun += (int64_t)g * g;
+        jspan = std::max(jspan, joff[(size_t)t] + (int64_t)g * g);
+        if (g > DE_GN_MAX_ROWS && g <= DE_GN_WIDE_MAX_ROWS) { n_wide++; rows += g; tri += (int64_t)g * (g + 1) / 2; }
+    }
+    char why[160];
+    int src = DE_OK;
+    const bool refused = !mode_ok || neg || N < 0 || !ok || !dloss || !jtj || !X || !y || ldX < p->n_features || loss_spec_problem(spec, 1, why, sizeof why) ||
+                         gn_spec_problem(spec, e_floor, p->dtype, &src, why, sizeof why);
+    if (n_wide == 0 || N <= 0 || refused)
+        return loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr, false, &gn);
+    int rc = check_param_args(c, p, pa, N);
+    if (rc != DE_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = gn_wide_cache(c, p, mode, ng);
+    if (rc != DE_OK) return rc;
+    GnWideCache *gw = p->gnw;
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
+    // host inputs are staged once, into the buffers a single call would stage them in (as de_fit_consts_lm does)
+    Staged sX, sY, sW, sPar, sCls;
+    de_param_args_t pad;
+    const de_param_args_t *pa_use = pa;
+    if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
+    if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
+    if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
+    if (p->uses_params) {
+        if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
+        if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
+        pad = *pa;
+        pad.params = sPar.dev;
+        pad.classes = sCls.dev;
+        pa_use = &pad;
+    }
+    if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const char *Xd = static_cast<const char *>(sX.dev), *yd = static_cast<const char *>(sY.dev), *wd = w ? static_cast<const char *>(sW.dev) : nullptr;
+    // the pool
+    const int64_t chunk = gn_wide_chunk(N, rows, n_wide, es);
+    const int64_t n_slices_max = (chunk + GNW_SLICE - 1) / GNW_SLICE;
+    const bool h_j = !is_device_ptr(jtj), h_ok = !is_device_ptr(ok);
+    size_t at = 0;
+    const size_t o_jac = lm_place(&at, (size_t)rows * (size_t)chunk * es), o_val = lm_place(&at, (size_t)n_wide * (size_t)chunk * es),
+                 o_oks = lm_place(&at, (size_t)n_wide), o_cf = lm_place(&at, nc * es), o_cs = lm_place(&at, (size_t)gw->n_consts * es),
+                 o_part = lm_place(&at, (size_t)n_slices_max * (size_t)tri * 8), o_tot = lm_place(&at, (size_t)tri * 8),
+                 o_j = h_j ? lm_place(&at, (size_t)std::max<int64_t>(jspan, 1) * es) : 0, o_ok = h_ok ? lm_place(&at, nt) : 0;
+    if (at > c->sGnw.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sGnw.reserve(at));
+    char *base = static_cast<char *>(c->sGnw.p);
+    void *jtj_d = h_j ? static_cast<void *>(base + o_j) : jtj;
+    uint8_t *ok_d = h_ok ? reinterpret_cast<uint8_t *>(base + o_ok) : ok;
+    // the table of the wide trees, uploaded when the offsets differ from what the device holds
+    {
+        std::vector<unsigned char> img((size_t)n_wide * sizeof(GnWideTree));
+        GnWideTree *tab = reinterpret_cast<GnWideTree *>(img.data());
+        int64_t r0 = 0, t0 = 0;
+        for (size_t s = 0; s < (size_t)n_wide; s++) {
+            std::memset(&tab[s], 0, sizeof tab[s]);
+            const int32_t t = gw->trees[s], g = gw->rows[s];
+            tab[s].tree = t;
+            tab[s].G = g;
+            tab[s].row0 = r0;
+            tab[s].tri0 = t0;
+            tab[s].joff = joff[(size_t)t];
+            r0 += g;
+            t0 += (int64_t)g * (g + 1) / 2;
+        }
+        if (!gw->d_tab || img != gw->tab) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream)); // (queued work may still read the table)
+            if (!gw->d_tab) HIP_TRY(c, hipMalloc(&gw->d_tab, img.size()));
+            HIP_TRY(c, hipMemcpy(gw->d_tab, img.data(), img.size(), hipMemcpyHostToDevice));
+            gw->tab = std::move(img);
+        }
+    }
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    {
+        struct Nest {
+            de_ctx *c;
+            explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
+            ~Nest() { c->nested--; }
+        } nest(c);
+        // 1. loss, dloss, ok and the narrow blocks with de_eval_loss_gn_ex's bits (the wide blocks: NaN for now)
+        const GnPlan gnd{jtj_d, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
+        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, mode, yd, wd, spec, loss, dloss, dloss_offsets, ok_d, nullptr, false, &gnd);
+        if (rc != DE_OK) return rc;
+        // 2. the wide trees' constants, device to device where the program's are on the device
+        if (gw->n_consts > 0 && gw->consts_gen != p->consts_gen) {
+            rc = de_program_get_consts(p, base + o_cf);
+            if (rc != DE_OK) return rc;
+            HIP_TRY(c, launch_gnw_gather(p->dtype, base + o_cf, gw->d_cidx, gw->n_consts, base + o_cs, c->stream));
+            rc = set_consts_device_impl(gw->sub, base + o_cs);
+            if (rc != DE_OK) return rc;
+            gw->consts_gen = p->consts_gen;
+        }
+        // 3. chunk by chunk: the rows and values of the wide trees, their Gram matrices, the running totals; behind the last chunk the blocks
+        GnWideGramArgs ga;
+        std::memset(&ga, 0, sizeof ga);
+        ga.trees = static_cast<const GnWideTree *>(gw->d_tab);
+        ga.n_wide = (int32_t)n_wide;
+        ga.jac = base + o_jac;
+        ga.vals = base + o_val;
+        ga.kind = spec->kind;
+        ga.param = spec->param;
+        ga.e_floor = e_floor;
+        ga.partial = reinterpret_cast<double *>(base + o_part);
+        ga.tri_total = tri;
+        for (int64_t j0 = 0; j0 < N; j0 += chunk) {
+            const int64_t n = std::min(chunk, N - j0);
+            de_param_args_t pac;
+            const de_param_args_t *pa_c = pa_use;
+            if (p->uses_params) {
+                pac = *pa_use;
+                pac.classes = static_cast<const char *>(pa_use->classes) + (size_t)j0 * (pa_use->classes_is_i64 ? 8 : 4);
+                pa_c = &pac;
+            }
+            rc = grad_impl(c, gw->sub, Xd + (size_t)j0 * (size_t)ldX * es, n, ldX, pa_c, mode, -1, base + o_val, n, base + o_jac, nullptr,
+                           reinterpret_cast<uint8_t *>(base + o_oks));
+            if (rc != DE_OK) return rc;
+            ga.y = yd + (size_t)j0 * es;
+            ga.w = wd ? wd + (size_t)j0 * es : nullptr;
+            ga.n = n;
+            HIP_TRY(c, launch_gnw_gram(p->dtype, ga, c->stream));
+            HIP_TRY(c, launch_gnw_fold(p->dtype, ga.trees, ga.n_wide, ga.partial, (n + GNW_SLICE - 1) / GNW_SLICE, tri, reinterpret_cast<double *>(base + o_tot),
+                                       j0 == 0, j0 + n >= N, jtj_d, ok_d, c->stream));
+        }
+        c->last_kernel = "de_gnw_gram_kernel";
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (h_j)
+        for (int64_t t = 0; t < p->n_trees; t++)
+            if (ng[(size_t)t] > 0)
+                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(jtj) + (size_t)joff[(size_t)t] * es, static_cast<char *>(jtj_d) + (size_t)joff[(size_t)t] * es,
+                                          (size_t)ng[(size_t)t] * (size_t)ng[(size_t)t] * es, hipMemcpyDeviceToHost, c->stream));
+    if (h_ok) HIP_TRY(c, hipMemcpyAsync(ok, ok_d, nt, hipMemcpyDeviceToHost, c->stream));
+    if (h_j || h_ok) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_eval_loss_gn_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                         const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss,
+                         const int64_t *dloss_offsets, void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_loss_gn_wide");
+    DE_NOTHROW(c, gn_wide_impl(c, p, X, N, ldX, pa, mode, y, w, spec, e_floor, loss, dloss, dloss_offsets, jtj, jtj_offsets, ok));
+}
+int de_gn_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                       const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step, true));
+}
+int de_fit_consts_lm_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                          const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                          double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_wide");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
 }
 
 } // extern "C"

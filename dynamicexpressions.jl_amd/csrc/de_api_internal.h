@@ -89,6 +89,9 @@ struct de_ctx {
     // offsets | widths] of the last call, uploaded through the pinned image lm_pin only when they differ from lm_tab (what the device
     // holds): lm_ev marks the end of that copy, so a call with device pointers never waits for the stream
     DevBuf sLm, sLmTab;
+    // de_eval_loss_gn_wide (csrc/de_gn_wide.h): one pool per call — the chunk's rows and values of the wide trees, the
+    // mirrored constants, the partial sums and totals, and device images of a host jtj / ok
+    DevBuf sGnw;
     std::vector<unsigned char> lm_tab;
     void *lm_pin = nullptr;
     size_t lm_pin_cap = 0;
@@ -102,8 +105,24 @@ struct de_ctx {
     DevBuf sPrioDs;
 };
 
+// de_eval_loss_gn_wide: the hidden sub-program of the trees with DE_GN_MAX_ROWS < n_grad <= DE_GN_WIDE_MAX_ROWS in one
+// gradient mode, built lazily from the tapes the program keeps for de_program_update (in_nodes / in_noff).  It belongs to the program:
+// de_program_destroy releases it, and de_program_update — which swaps a freshly created program in — leaves the new program without one.
+struct GnWideCache {
+    struct de_program *sub = nullptr;
+    int mode = -1;
+    std::vector<int32_t> trees;   // the wide trees, in population order
+    std::vector<int32_t> rows;    // their n_grad in `mode`
+    int64_t n_consts = 0;         // constants of the sub-program
+    int64_t *d_cidx = nullptr;    // device: constant k of the sub-program = constant d_cidx[k] of the program
+    uint64_t consts_gen = ~0ull;  // de_program::consts_gen the sub-program's constants mirror (~0: none yet)
+    void *d_tab = nullptr;        // device: the GnWideTree table, uploaded when the jtj offsets differ from its host image `tab`
+    std::vector<unsigned char> tab;
+};
+
 struct de_program {
     de_ctx *ctx = nullptr;
+    GnWideCache *gnw = nullptr;
     int dtype = DE_F32; // element type of the COMPUTE (and of every host-side stream): DE_F32 or DE_F64
     // element type of the caller's buffers — X, constants, parameters, outputs: DE_F16 programs compute in Float32
     // (dtype == DE_F32, constants are binary16 values Float32 holds exactly) and run de_half.hip's kernel, which rounds every operator
@@ -322,6 +341,8 @@ int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, 
 int consts_materialise(de_program *p);
 // the body of de_program_set_consts_device (de_api_program.cpp): de_fit_consts_lm sets its trial and accepted constants through it
 int set_consts_device_impl(de_program *p, const void *d_consts);
+// releases a program's GnWideCache (de_api_grad.cpp); the caller has synchronised the stream
+void gn_wide_release(de_program *p);
 }
 
 // de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)

@@ -1738,6 +1738,7 @@ int de_program_destroy(de_program_t *p) {
     if (p->d_cert_off) (void)hipFree(p->d_cert_off);
     dbg_lap("destroy: eval streams");
     if (p->aux) de_program_destroy(p->aux);
+    gn_wide_release(p);
     prog_free(c, p->d_kf);
     p->d_kf = nullptr;
     prog_free(c, p->d_cp); // (de_program_set_consts_device: site tables, the program's own constants)

@@ -24,7 +24,7 @@ struct LmStepArgs {
 hipError_t launch_lm_step(int dtype, const LmStepArgs &a, hipStream_t stream);
 
 // One thread per tree: the accept rule of Population.fit_constants_lm.  *_acc: the accepted state, *_trial: the evaluation at the trial
-// constants; ok and G <= 8 make `has`.  history_row / n_accept may be null.
+// constants; ok and G <= row_limit make `has` (8: de_fit_consts_lm, 32: de_fit_consts_lm_wide).  history_row / n_accept may be null.
 struct LmAcceptArgs {
     int64_t n_trees;
     const int32_t *n_grad;
@@ -37,6 +37,7 @@ struct LmAcceptArgs {
     double up, down, lam_min;
     double *history_row; // n_trees entries: the accepted losses after this iteration
     int32_t *n_accept;
+    int32_t row_limit;
 };
 hipError_t launch_lm_accept(int dtype, const LmAcceptArgs &a, hipStream_t stream);
 

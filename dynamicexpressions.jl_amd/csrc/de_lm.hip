@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256) de_lm_accept_kernel(LmAcceptArgs a) {
     const int G = a.n_grad[t];
     T *loss_acc = static_cast<T *>(a.loss_acc);
     const T *loss_trial = static_cast<const T *>(a.loss_trial);
-    const bool narrow = G <= LM_MAX_ROWS;
+    const bool narrow = G <= a.row_limit;
     const bool has_acc = narrow && a.ok_acc[t], has_trial = narrow && a.ok_trial[t];
     const bool accept = has_acc && has_trial && (double)loss_trial[t] < (double)loss_acc[t]; // (a NaN compares false)
     if (accept) {

@@ -777,7 +777,7 @@ function eval_population_loss_grad(
 end
 
 """
-    eval_population_gauss_newton(pop, X, y; weights=nothing, variable=Val(false), loss=:L2, loss_param=0.0, e_floor=1e-4)
+    eval_population_gauss_newton(pop, X, y; weights=nothing, variable=Val(false), loss=:L2, loss_param=0.0, e_floor=1e-4, wide=false)
         -> (loss::Vector{T}, dloss::Vector{Vector{T}}, jtj::Vector{Matrix{T}}, ok, has_jtj)
 
 The normal equations of a Levenberg-Marquardt step for a whole population in one launch (`de_eval_loss_gn_ex`): the loss `loss` and its
@@ -787,10 +787,12 @@ of the loss is `2 jtj[t]`; DESIGN.md §4.4.5) and `e_floor` the residual floor o
 (`:L1`, `:l1_eps`, `:quantile`, `:lp` with p < 2).  `:l1_hinge` (`DE_ERR_UNSUPPORTED`) and `:pullback` have no such matrix.  A tree of more than
 `de_gn_max_rows()` rows in the library's per-occurrence layout has `has_jtj[t] == false` and a NaN matrix; its loss and gradient
 are filled as usual.  For a GraphNode the rows and columns of a shared constant are summed (`combine_rows` on both sides).
+`wide=true` (`de_eval_loss_gn_wide`, DESIGN.md §4.4.7) also forms the matrix of a tree of up to `de_gn_wide_max_rows()` = 32 rows; every
+other output keeps the bits of the default call.  The library refuses it for a population with shared GraphNode subtrees.
 """
 function eval_population_gauss_newton(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing, variable=Val(false),
-    loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
+    loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4, wide::Bool=false,
 ) where {T}
     mode = grad_mode(variable)
     F, N = size(X)
@@ -803,15 +805,23 @@ function eval_population_gauss_newton(
         joffs = Int64[0; cumsum(ng .* ng)]
         dl = Vector{T}(undef, max(offs[end], 1))
         jt = Vector{T}(undef, max(joffs[end], 1))
-        check(pop.ctx, GC.@preserve X y weights lossv dl jt offs joffs ok ccall(
-            (:de_eval_loss_gn_ex, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble,
-             Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
-            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), spec, Float64(e_floor),
-            lossv, dl, offs, jt, joffs, ok))
+        wp = weights === nothing ? C_NULL : pointer(weights)
+        if wide
+            check(pop.ctx, GC.@preserve X y weights lossv dl jt offs joffs ok ccall(
+                (:de_eval_loss_gn_wide, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+                hc, hp, X, N, F, C_NULL, mode, y, wp, spec, Float64(e_floor), lossv, dl, offs, jt, joffs, ok))
+        else
+            check(pop.ctx, GC.@preserve X y weights lossv dl jt offs joffs ok ccall(
+                (:de_eval_loss_gn_ex, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+                hc, hp, X, N, F, C_NULL, mode, y, wp, spec, Float64(e_floor), lossv, dl, offs, jt, joffs, ok))
+        end
         (dl, jt, ng, offs, joffs)
     end
-    max_rows = ccall((:de_gn_max_rows, LIBDE), Cint, ())
+    max_rows = wide ? ccall((:de_gn_wide_max_rows, LIBDE), Cint, ()) : ccall((:de_gn_max_rows, LIBDE), Cint, ())
     okb = ok .!= 0x00
     jtj = map(1:pop.n_trees) do t
         H = reshape(jt[(joffs[t] + 1):joffs[t + 1]], ng[t], ng[t])
@@ -912,7 +922,8 @@ function population_lm_step(
 end
 
 """
-    fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1, loss=:L2, loss_param=0.0, e_floor=1e-4)
+    fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1, loss=:L2, loss_param=0.0, e_floor=1e-4,
+                                 wide=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
 Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm_ex`), minimising the loss
@@ -922,10 +933,13 @@ constants there, evaluates, and accepts a tree's step when its loss decreased (`
 Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the accepted losses
 after `r - 1` iterations.  Trees that are incomplete at the start or wider than `de_gn_max_rows()` keep their constants.  A population
 with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrence rows need folding on the host).
+`wide=true` (`de_fit_consts_lm_wide`, DESIGN.md §4.4.7) also fits the trees of 9 to `de_gn_wide_max_rows()` = 32 constants; a narrower tree
+follows the default call's trajectory bit for bit.
 """
 function fit_population_constants_lm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1, loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
+    wide::Bool=false,
 ) where {T}
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
@@ -938,12 +952,20 @@ function fit_population_constants_lm!(
     history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
     n_accept = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
-        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
-            (:de_fit_consts_lm_ex, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
-             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-            hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), spec, Float64(e_floor), opts,
-            lossv, ok, history, n_accept))
+        wp = weights === nothing ? C_NULL : pointer(weights)
+        if wide
+            check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+                (:de_fit_consts_lm_wide, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
+                 Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, Float64(e_floor), opts, lossv, ok, history, n_accept))
+        else
+            check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+                (:de_fit_consts_lm_ex, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
+                 Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, Float64(e_floor), opts, lossv, ok, history, n_accept))
+        end
     end
     constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
     return constants, lossv, ok .!= 0x00, history, n_accept

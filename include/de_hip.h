@@ -84,7 +84,10 @@ extern "C" {
  *      (i) de_gn_spec_check, de_eval_loss_gn_ex, de_fit_consts_lm_ex: the Gauss-Newton matrix and the fit under every loss kind that has a
  *      curvature; de_eval_loss_gn and de_fit_consts_lm forward to them with {DE_LOSS_L2, 0, 0}: the same bits.
  *      (j) de_eval_fit_stats_grad: the fit statistics with their gradient moments and the Gauss-Newton matrix — what a
- *      fit of the constants under linear scaling a + b yhat needs. */
+ *      fit of the constants under linear scaling a + b yhat needs.
+ *      (k) de_gn_wide_max_rows, de_eval_loss_gn_wide, de_gn_lm_step_wide, de_fit_consts_lm_wide and the host-only hook
+ *      de_lm_solve_host_wide: the Gauss-Newton matrix, the step and the fit for trees of 9 to 32 gradient rows; every
+ *      entry point above keeps its bits and de_gn_max_rows() stays 8. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -648,6 +651,47 @@ int de_fit_consts_lm_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_
                         const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts,
                         void *loss, uint8_t *ok, double *history, int32_t *n_accept);
 int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step);
+
+/* Gauss-Newton matrices and Levenberg-Marquardt fits for trees of 9 to 32 gradient rows.  Additions: every entry point
+ * above keeps its bits, its NaN blocks and de_gn_max_rows() == 8.
+ *
+ * de_eval_loss_gn_wide: de_eval_loss_gn_ex's arguments, pointers, staging, offsets and stream order.
+ *   loss, dloss, ok          de_eval_loss_grad_ex's for the same spec, bit for bit, for every tree
+ *   G_t <= 8                 the jtj block of de_eval_loss_gn_ex, bit for bit
+ *   8 < G_t <= 32, ok[t]     jtj[joff_t + i + G_t k] = sum_j w_j c_j d_i(j) d_k(j): both triangles written, exactly symmetric, a sample of
+ *                            weight zero excluded by a select, the association order ((w c) d_i) d_k (i <= k), c_j the curvature weight of
+ *                            de_eval_loss_gn_ex with the same floor rules.  Every product is formed in the element type and summed in
+ *                            double in a fixed order (tiles of 64 samples, slices of 1024, chunks): reproducible run to run, and
+ *                            |jtj - exact| <= 256 u sum_j |w c d_i d_k| as for the narrow blocks
+ *   ok[t] == 0 or G_t > 32   a NaN block; neither is an error
+ * The wide trees' rows are formed by de_eval_grad's kernels over chunks of samples in the context's scratch: with R = the sum of their
+ * G_t and n_w their number, the default chunk is the largest multiple of 256 with (R + n_w) * chunk * sizeof(element) <= 256 MiB (at
+ * least 256 samples); DE_GN_WIDE_CHUNK=<samples> in the environment (rounded up to a multiple of 64) overrides it.  A population without
+ * a tree of 9 .. 32 rows, and N == 0 (blocks of 0 for G_t <= 32, NaN where the flag already fails), take de_eval_loss_gn_ex's path with
+ * no further launch.  Refusals, before any output is touched: what de_eval_loss_gn_ex refuses, with the same codes, and
+ * DE_ERR_UNSUPPORTED for a program made by de_program_create_cse with a shared subtree (one gradient row per occurrence of a shared
+ * constant: the caller folds them, S H S^T, and keeps the host loop).
+ *
+ * de_lm_solve_host_wide: de_lm_solve_host for G in 1 .. 32 — de_lm_solve_host's bits for G <= 8, the same arithmetic without the padding
+ * (csrc/de_lm_solve_wide.h: Cholesky in double, every sum over k ascending) for 8 < G <= 32; the zero step and 0 for any other G.
+ * de_gn_lm_step_wide: de_gn_lm_step's arguments; a tree with G <= 8 gets de_gn_lm_step's bytes, a tree with 8 < G <= 32 the step of
+ * de_lm_solve_host_wide bit for bit (one wave per tree, the matrix in LDS), G > 32 and every other zero-step condition zeros; entries no
+ * tree owns are not written.
+ * de_fit_consts_lm_wide: de_fit_consts_lm_ex's arguments and loop with has = ok && G <= 32: every evaluation is de_eval_loss_gn_wide, a
+ * tree with G <= 8 follows de_fit_consts_lm_ex's trajectory bit for bit (constants, loss, history, n_accept), and afterwards
+ * de_eval_loss_grad_ex reproduces loss[t] bit for bit for every tree.  The same refusals; reserved stays 0.
+ * Not served: de_eval_fit_stats_grad for wide trees, programs with shared subtrees, more than 32 rows. */
+int de_gn_wide_max_rows(void); /* 32 */
+int de_eval_loss_gn_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                         const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                         const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets,
+                         void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
+int de_lm_solve_host_wide(int G, const double *H, const double *g, double lam, double *step);
+int de_gn_lm_step_wide(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                       const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step);
+int de_fit_consts_lm_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                          const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts,
+                          void *loss, uint8_t *ok, double *history, int32_t *n_accept);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
