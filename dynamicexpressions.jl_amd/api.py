@@ -55,6 +55,7 @@ EXPORTS = [
     "de_lower_tape_assured", "de_lower_tape_assured_parts", "de_gn_lm_step", "de_fit_consts_lm", "de_lm_solve_host",
     "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex", "de_eval_fit_stats_grad",
     "de_gn_wide_max_rows", "de_eval_loss_gn_wide", "de_lm_solve_host_wide", "de_gn_lm_step_wide", "de_fit_consts_lm_wide",
+    "de_lm_project_host", "de_fit_stats_lm_step", "de_fit_consts_lm_scaled",
 ]
 
 
@@ -356,6 +357,40 @@ class FitStatsGrad:
             out.append(2.0 * P - 2.0 * Q + 2.0 * (st.mean_p[t] - st.mean_y) * D)
         return out
 
+    def lm_step_device(self, lam, return_sse: bool = False):
+        """The Levenberg-Marquardt step of every tree under linear scaling on the device (``de_fit_stats_lm_step``)
+        over the packed buffers ``eval_fit_stats_grad`` filled — ``projected().lm_step_device(lam)`` without the host forming the
+        projected system; nothing is copied and nothing synchronises when they are device tensors.  A float64 array / tensor, tree t at
+        ``sum(n_grad[:t])``; bit for bit ``lm_solve_host`` of the ``g`` and ``Ht`` of ``lm_project_host``.  The zero step where ``has_jtj`` is false,
+        the tree is constant over the samples or the solve answers zero (``GaussNewton.lm_step_device``).  ``return_sse=True``: (step,
+        scaled_sse[n_trees] in float64).  ``ValueError`` for a population with shared GraphNode constants and for an object that
+        ``eval_fit_stats_grad`` did not make (or made with ``want_jtj=False``)."""
+        pk = getattr(self, "_packed", None)
+        if pk is None or pk["jtj"] is None:
+            raise ValueError("lm_step_device needs the packed buffers of Population.eval_fit_stats_grad(want_jtj=True)")
+        if pk["occ"]:
+            raise ValueError("lm_step_device: the population shares GraphNode constants (per-occurrence rows): use projected().lm_step")
+        ctx, st, dm, jt, ng, n = pk["ctx"], pk["stats"], pk["dmom"], pk["jtj"], pk["n_grad"], len(self)
+        total = int(ng.sum())
+        fn = library().de_fit_stats_lm_step
+        if _is_torch(dm):
+            import torch
+            ctx.use_torch_stream()
+            lams = torch.as_tensor(lam, dtype=torch.float64, device=dm.device).expand(n).contiguous()
+            has = self.has_jtj.to(torch.uint8).contiguous()
+            step = torch.zeros(max(total, 1), dtype=torch.float64, device=dm.device)
+            sse = torch.empty(max(n, 1), dtype=torch.float64, device=dm.device)
+            ctx.check(fn(ctx._h, pk["dtype"], n, ng.ctypes.data, st.data_ptr(), st.data_ptr() + 24 * n, dm.data_ptr(), None, jt.data_ptr(),
+                         None, has.data_ptr(), lams.data_ptr(), step.data_ptr(), sse.data_ptr()))
+            self._lm_keep = (lams, has)  # (read in stream order)
+        else:
+            lams = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (n,)))
+            has = np.ascontiguousarray(np.asarray(self.has_jtj), dtype=np.uint8)
+            step, sse = np.zeros(max(total, 1), dtype=np.float64), np.empty(max(n, 1), dtype=np.float64)
+            ctx.check(fn(ctx._h, pk["dtype"], n, ng.ctypes.data, st.ctypes.data, st.ctypes.data + 24 * n, dm.ctypes.data, None,
+                         jt.ctypes.data, None, has.ctypes.data, lams.ctypes.data, step.ctypes.data, sse.ctypes.data))
+        return (step[:total], sse[:n]) if return_sse else step[:total]
+
     def projected(self) -> GaussNewton:
         """The Gauss-Newton system of the residual under linear scaling, (a, b) projected out (variable projection, Kaufman's form):
         ``GaussNewton(loss=scaled_sse, grad=scaled_sse_grad, jtj=b^2 (H - D D^T / W - P P^T / m2_p), ok, has_jtj)`` in float64, so that
@@ -404,6 +439,26 @@ def lm_solve_host_wide(H, g, lam: float):
     step = np.full(max(G, 1), np.nan, dtype=np.float64)
     rc = library().de_lm_solve_host_wide(G, H.ctypes.data, g.ctypes.data, float(lam), step.ctypes.data)
     return step[:G], bool(rc)
+
+
+def lm_project_host(stats3, ystats3, D, P, Q, H):
+    """``de_lm_project_host``: the arithmetic of the device's step under linear scaling (csrc/de_lm_project.h) for one tree on the host, no
+    GPU needed — (scaled_sse, g[G], Ht[G, G], formed) in float64 from ``stats3 = (mean_p, m2_p, cov)``, ``ystats3 = (W, mean_y, m2_y)``,
+    the moments ``D``, ``P``, ``Q`` and the matrix ``H`` (converted to float64): bit for bit ``FitStats.scaled_sse`` and
+    ``FitStatsGrad.projected()``.  ``formed`` False: ``m2_p == 0``, ``W == 0`` or G outside 1 .. 8 — g and Ht are zero."""
+    st = np.ascontiguousarray(stats3, dtype=np.float64).reshape(-1)
+    ys = np.ascontiguousarray(ystats3, dtype=np.float64).reshape(-1)
+    rows = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (D, P, Q)]
+    G = rows[0].size
+    H = np.asfortranarray(H, dtype=np.float64)
+    if st.size != 3 or ys.size != 3 or rows[1].size != G or rows[2].size != G or H.shape != (G, G):
+        raise ValueError("stats3 and ystats3 hold three values, D, P and Q G entries each, and H is G x G")
+    dm = np.concatenate(rows + [np.zeros(1)])
+    sse = np.full(1, np.nan)
+    g, Ht = np.full(max(G, 1), np.nan), np.full((max(G, 1), max(G, 1)), np.nan, order="F")
+    Hp = np.asfortranarray(H if G else np.zeros((1, 1)))
+    rc = library().de_lm_project_host(G, st.ctypes.data, ys.ctypes.data, dm.ctypes.data, Hp.ctypes.data, sse.ctypes.data, g.ctypes.data, Ht.ctypes.data)
+    return float(sse[0]), g[:G], (Ht[:G, :G] if G else np.zeros((0, 0))), bool(rc)
 
 
 def _host(v) -> np.ndarray:
@@ -516,6 +571,10 @@ def library() -> C.CDLL:
         lib.de_lm_solve_host_wide.argtypes = lib.de_lm_solve_host.argtypes
         lib.de_gn_lm_step_wide.argtypes = lib.de_gn_lm_step.argtypes
         lib.de_fit_consts_lm_wide.argtypes = lib.de_fit_consts_lm_ex.argtypes
+    if hasattr(lib, "de_fit_consts_lm_scaled"):  # (absent from a library built before the device fit under linear scaling: DE_HIP_LIB in an A/B run)
+        lib.de_lm_project_host.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        lib.de_fit_stats_lm_step.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.de_fit_consts_lm_scaled.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LmOpts), vp, vp, vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1403,6 +1462,9 @@ class Population:
             mats = [gn_combine(H, occ[t]) for t, H in enumerate(mats)]
         out = FitStatsGrad(stats, rows[0], rows[1], rows[2], mats, okb, has)
         out._ctx = self.ctx  # (projected(): lm_step_device needs a context)
+        # the packed buffers the views above look into: FitStatsGrad.lm_step_device hands them to de_fit_stats_lm_step as they are
+        out._packed = dict(ctx=self.ctx, dtype=_dtype_code(self.dtype), n_grad=np.ascontiguousarray(ng, dtype=np.int32), stats=st, dmom=dm,
+                           jtj=jt if want_jtj else None, occ=occ is not None)
         return out
 
     def eval_loss_grad(self, X, y, weights=None, loss: str = "L2", variable: Union[bool, str] = False,
@@ -1599,7 +1661,7 @@ class Population:
 
     def fit_constants_lm_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
                                 down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1,
-                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4, wide: bool = False):
+                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4, wide: bool = False, scaled: bool = False):
         """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm_ex``): the steps are solved, the trial constants
         set, and the accept rule applied on the device; no constant, gradient or matrix reaches the host.  ``consts0``: a numpy array or a
         torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.  Returns (consts, loss[n_trees] in
@@ -1608,7 +1670,18 @@ class Population:
         rows of accepted losses (float64); ``self.lm_accepts`` holds the number of accepted steps per tree.  The step is a Cholesky solve
         (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it.
         ``wide=True`` (``de_fit_consts_lm_wide``): trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted too; a tree of
-        at most ``GN_MAX_ROWS`` follows the default call's trajectory bit for bit."""
+        at most ``GN_MAX_ROWS`` follows the default call's trajectory bit for bit.
+        ``scaled=True`` (``de_fit_consts_lm_scaled``; ``loss="L2"`` and ``wide=False`` only, anything else is a
+        ``ValueError`` before the constants are touched): ``fit_constants_lm(scaled=True)`` on the device — the objective is
+        ``FitStats.scaled_sse``.  Returns (consts, scaled_sse[n_trees] in float64, ok); ``self.lm_fit_stats`` holds the ``FitStats`` at the
+        returned constants (slope and intercept without another launch; with torch inputs reading it copies 3 n_trees + 3 doubles to
+        the host, the call itself does not).  The step is the Cholesky solve of ``lm_step_device``: a tree with a constant that is
+        redundant under scaling (an additive or multiplicative constant at the root: a zero row of the projected matrix) gets the zero
+        step and keeps its constants, where the host loop's LU solve may still move it."""
+        if scaled and wide:
+            raise ValueError("fit_constants_lm_device(scaled=True, wide=True): the fit statistics form no matrix for trees of more than 8 rows")
+        if scaled and loss != "L2":
+            raise ValueError(f"fit_constants_lm_device(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
         self._refuse_f16("fit_constants_lm_device")
         spec = gn_loss_spec(loss, loss_param, e_floor)
         if self._occ is not None:
@@ -1649,6 +1722,25 @@ class Population:
                 raise ValueError("wrong number of constants")
             self.set_constants(consts0 if _is_torch(consts0) else np.asarray(consts0).reshape(-1))
         lib, nt, rows = library(), self.n_trees, int(iters) + 1
+        if scaled:
+            if is_t:
+                import torch
+                dev = keep_x.device
+                lo, st = torch.empty(nt, dtype=torch.float64, device=dev), torch.empty(3 * nt + 3, dtype=torch.float64, device=dev)
+                ok = torch.empty(nt, dtype=torch.uint8, device=dev)
+                hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
+                acc = torch.empty(nt, dtype=torch.int32, device=dev)
+                ptrs = (lo.data_ptr(), st.data_ptr(), st.data_ptr() + 24 * nt, ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
+            else:
+                lo, st, ok = np.empty(nt, dtype=np.float64), np.full(3 * nt + 3, np.nan), np.zeros(nt, dtype=np.uint8)
+                hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
+                ptrs = (lo.ctypes.data, st.ctypes.data, st.ctypes.data + 24 * nt, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
+            self.ctx.check(lib.de_fit_consts_lm_scaled(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
+            self.lm_accepts = acc
+            self._lm_fit_raw = st if nt else None  # (lm_fit_stats reads it: a device tensor is copied only then)
+            if history is not None:
+                history.extend(hist[r] for r in range(rows))
+            return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
         if is_t:
             import torch
             dev = keep_x.device
@@ -1667,6 +1759,16 @@ class Population:
         if history is not None:
             history.extend(hist[r] for r in range(rows))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
+    @property
+    def lm_fit_stats(self) -> FitStats:
+        """The ``FitStats`` at the constants the last ``fit_constants_lm_device(scaled=True)`` returned."""
+        raw = getattr(self, "_lm_fit_raw", None)
+        if raw is None:
+            raise AttributeError("lm_fit_stats: no fit_constants_lm_device(scaled=True) has run on a non-empty population")
+        sth, nt = _host(raw), self.n_trees
+        per = sth[:3 * nt].reshape(nt, 3)
+        return FitStats(per[:, 0], per[:, 1], per[:, 2], sth[3 * nt], sth[3 * nt + 1], sth[3 * nt + 2])
 
     def eval_loss_grad_by_class(self, X, y, params, classes, weights=None, loss: str = "L2",
                                 variable: Union[bool, str] = "both", class_base: int = 1, grouped: bool = False, loss_param: float = 0.0):

@@ -8,6 +8,8 @@
 #include "de_lm_solve.h"
 #include "de_gn_wide.h"
 #include "de_lm_solve_wide.h"
+#include "de_lm_scaled.h"
+#include "de_lm_project.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -1139,27 +1141,31 @@ int de_lm_solve_host(int G, const double *H, const double *g, double lam, double
 
 // The geometry tables of a step / fit on the device: [dloss offsets | jtj offsets | widths].  Uploaded only when they differ from what the
 // device holds, through a pinned image: a call whose buffers are device pointers is stream-ordered and never waits for the stream.
+// rows_per_g = 3 (de_fit_stats_lm_step / de_fit_consts_lm_scaled: the offsets are those of dmom, 3 G doubles per tree): the image is
+// [dmom offsets | jtj offsets | packed offsets of G entries per tree | widths], soff the third table (else soff = doff).
 struct LmTables {
-    const int64_t *doff = nullptr, *joff = nullptr;
+    const int64_t *doff = nullptr, *joff = nullptr, *soff = nullptr;
     const int32_t *ng = nullptr;
-    int64_t span = 0, jspan = 0;
+    int64_t span = 0, jspan = 0, sspan = 0;
 };
-static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out) {
-    const size_t nn = (size_t)n;
-    std::vector<unsigned char> img(nn * (2 * sizeof(int64_t) + sizeof(int32_t)));
-    int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn;
-    int32_t *w = reinterpret_cast<int32_t *>(joff + nn);
-    int64_t run = 0, jrun = 0, span = 0, jspan = 0;
+static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out, int rows_per_g = 1) {
+    const size_t nn = (size_t)n, n_off = rows_per_g > 1 ? 3 : 2;
+    std::vector<unsigned char> img(nn * (n_off * sizeof(int64_t) + sizeof(int32_t)));
+    int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn, *soff = n_off > 2 ? joff + nn : nullptr;
+    int32_t *w = reinterpret_cast<int32_t *>(doff + n_off * nn);
+    int64_t run = 0, jrun = 0, span = 0, jspan = 0, srun = 0;
     for (size_t t = 0; t < nn; t++) {
         const int64_t g = ng[t];
         if (g < 0) return fail(c, DE_ERR_INVALID_ARG, "negative n_grad");
         doff[t] = doffs ? doffs[t] : run;
         joff[t] = joffs ? joffs[t] : jrun;
         if (doff[t] < 0 || joff[t] < 0) return fail(c, DE_ERR_INVALID_ARG, "negative offset");
+        if (soff) soff[t] = srun;
         w[t] = (int32_t)g;
-        run += g;
+        run += rows_per_g * g;
+        srun += g;
         jrun += g * g;
-        span = std::max(span, doff[t] + g);
+        span = std::max(span, doff[t] + rows_per_g * g);
         jspan = std::max(jspan, joff[t] + g * g);
     }
     if (img != c->lm_tab || !c->sLmTab.p) {
@@ -1182,9 +1188,11 @@ static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *dof
     }
     out->doff = static_cast<const int64_t *>(c->sLmTab.p);
     out->joff = out->doff + nn;
-    out->ng = reinterpret_cast<const int32_t *>(out->joff + nn);
+    out->soff = n_off > 2 ? out->joff + nn : out->doff;
+    out->ng = reinterpret_cast<const int32_t *>(out->doff + n_off * nn);
     out->span = span;
     out->jspan = jspan;
+    out->sspan = srun;
     return DE_OK;
 }
 // a region of `bytes` in a buffer laid out by successive calls (256-byte granules)
@@ -1659,6 +1667,223 @@ int de_fit_consts_lm_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
                           double *history, int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_lm_wide");
     DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
+}
+
+
+// ---- de_lm_project_host / de_fit_stats_lm_step / de_fit_consts_lm_scaled (kernels: de_lm_scaled.hip, arithmetic: de_lm_project.h)
+int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
+    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
+    int formed = 0;
+    if (stats && ystats && dmom && H && g && Ht && G >= 1 && G <= LM_MAX_ROWS) {
+        DE_LM_FOR_G(G, formed = lm_project_mem<GG>(stats, ystats, dmom, H, g, Ht));
+        return formed;
+    }
+    for (int k = 0; g && k < G; k++) g[k] = 0.0;
+    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
+    return 0;
+}
+
+static int fit_stats_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                                  const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets,
+                                  const uint8_t *has, const double *lam, double *step, double *sse) {
+    if (!c) return DE_ERR_INVALID_ARG;
+    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_fit_stats_lm_step: dtype must be DE_F32 or DE_F64");
+    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
+    if (n_trees == 0) return DE_OK;
+    if (!n_grad || !stats || !ystats || !dmom || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
+    LmTables tab;
+    int rc = lm_tables(c, n_trees, n_grad, dmom_offsets, jtj_offsets, &tab, 3);
+    if (rc != DE_OK) return rc;
+    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), sspan = (size_t)tab.sspan;
+    const bool h_st = !is_device_ptr(stats), h_ys = !is_device_ptr(ystats), h_dm = !is_device_ptr(dmom), h_j = !is_device_ptr(jtj),
+               h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step), h_sse = sse && !is_device_ptr(sse);
+    size_t at = 0;
+    const size_t o_st = h_st ? lm_place(&at, nt * 24) : 0, o_ys = h_ys ? lm_place(&at, 24) : 0, o_dm = h_dm ? lm_place(&at, mspan * 8) : 0,
+                 o_j = h_j ? lm_place(&at, jspan * es) : 0, o_has = h_has ? lm_place(&at, nt) : 0, o_lam = h_lam ? lm_place(&at, nt * 8) : 0,
+                 o_step = h_step ? lm_place(&at, sspan * 8) : 0, o_sse = h_sse ? lm_place(&at, nt * 8) : 0;
+    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sLm.reserve(at));
+    char *base = static_cast<char *>(c->sLm.p);
+    LmScaledStepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = n_trees;
+    a.n_grad = tab.ng;
+    a.moff = tab.doff;
+    a.joff = tab.joff;
+    a.soff = tab.soff;
+    a.stats = stats; a.ystats = ystats; a.dmom = dmom; a.jtj = jtj; a.has = has; a.lam = lam; a.step = step; a.sse = sse;
+    auto up = [&](const void *src, size_t off, size_t bytes) { return hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream); };
+    if (h_st) { HIP_TRY(c, up(stats, o_st, nt * 24)); a.stats = reinterpret_cast<const double *>(base + o_st); }
+    if (h_ys) { HIP_TRY(c, up(ystats, o_ys, 24)); a.ystats = reinterpret_cast<const double *>(base + o_ys); }
+    if (h_dm) { HIP_TRY(c, up(dmom, o_dm, mspan * 8)); a.dmom = reinterpret_cast<const double *>(base + o_dm); }
+    if (h_j) { HIP_TRY(c, up(jtj, o_j, jspan * es)); a.jtj = base + o_j; }
+    if (h_has) { HIP_TRY(c, up(has, o_has, nt)); a.has = reinterpret_cast<const uint8_t *>(base + o_has); }
+    if (h_lam) { HIP_TRY(c, up(lam, o_lam, nt * 8)); a.lam = reinterpret_cast<const double *>(base + o_lam); }
+    if (h_step) a.step = reinterpret_cast<double *>(base + o_step); // (packed: every entry is some tree's)
+    if (h_sse) a.sse = reinterpret_cast<double *>(base + o_sse);
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    HIP_TRY(c, launch_lm_step_scaled(dtype, a, c->stream));
+    c->last_kernel = "de_lm_step_scaled_kernel";
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (h_step && sspan) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, sspan * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_sse) HIP_TRY(c, hipMemcpyAsync(sse, base + o_sse, nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_st || h_ys || h_dm || h_j || h_has || h_lam || h_step || h_sse) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_stats_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                         const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
+                         const double *lam, double *step, double *sse) {
+    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse));
+}
+
+// fit_consts_lm_impl's loop with every evaluation de_eval_fit_stats_grad's (a FitPlan into the state) and the kernels of de_lm_scaled.hip
+static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                     const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
+                                     double *history, int32_t *n_accept) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
+    const de_lm_opts_t o = opts ? *opts : defaults;
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm_scaled: a program made by de_program_create_cse has one gradient row per occurrence "
+                                           "of a shared constant (the caller folds them: S H S^T); such callers keep the host loop");
+    for (int64_t t = 0; t < p->n_trees; t++)
+        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
+            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm_scaled: tree %lld has %lld constant rows for %lld constants", (long long)t,
+                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
+    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: reserved must be 0");
+    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: iters < 0");
+    for (const double v : {o.lam0, o.up, o.down, o.lam_min})
+        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: lam0, up, down and lam_min must be finite and positive");
+    if (N < 0 || (p->n_trees > 0 && (!ok || !sse || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
+    int rc = check_param_args(c, p, pa, N);
+    if (rc != DE_OK) return rc;
+    if (p->n_trees == 0) return DE_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
+    std::vector<int32_t> ng(nt);
+    for (size_t t = 0; t < nt; t++) ng[t] = (int32_t)p->n_consts_tree[t];
+    LmTables tab; // packed: dmom at 3 x the constants' offsets, the step at the constants' offsets
+    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, nullptr, &tab, 3);
+    if (rc != DE_OK) return rc;
+    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), span = std::max<size_t>(nc, 1);
+    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
+    Staged sX, sY, sW, sPar, sCls;
+    de_param_args_t pad;
+    const de_param_args_t *pa_use = pa;
+    if (N > 0) {
+        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
+        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
+        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
+        if (p->uses_params) {
+            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
+            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
+            pad = *pa;
+            pad.params = sPar.dev;
+            pad.classes = sCls.dev;
+            pa_use = &pad;
+        }
+        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
+    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
+    const bool h_sse = !is_device_ptr(sse), h_ok = !is_device_ptr(ok), h_st = stats && !is_device_ptr(stats), h_ys = ystats && !is_device_ptr(ystats);
+    const size_t rows = (size_t)o.iters + 1;
+    size_t at = 0;
+    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_sa = lm_place(&at, nt * 24), o_st = lm_place(&at, nt * 24),
+                 o_ys = lm_place(&at, 24), o_ma = lm_place(&at, mspan * 8), o_mt = lm_place(&at, mspan * 8), o_ja = lm_place(&at, jspan * es),
+                 o_jt = lm_place(&at, jspan * es), o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt), o_sse = lm_place(&at, nt * 8),
+                 o_lam = lm_place(&at, nt * 8), o_step = lm_place(&at, span * 8), o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0,
+                 o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
+    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sLm.reserve(at));
+    char *base = static_cast<char *>(c->sLm.p);
+    void *cA = base + o_ca, *cT = base + o_ct, *jA = base + o_ja, *jT = base + o_jt;
+    double *sA = reinterpret_cast<double *>(base + o_sa), *sT = reinterpret_cast<double *>(base + o_st), *ys = reinterpret_cast<double *>(base + o_ys);
+    double *mA = reinterpret_cast<double *>(base + o_ma), *mT = reinterpret_cast<double *>(base + o_mt);
+    uint8_t *okA = reinterpret_cast<uint8_t *>(base + o_oka), *okT = reinterpret_cast<uint8_t *>(base + o_okt);
+    double *sseA = reinterpret_cast<double *>(base + o_sse), *lam = reinterpret_cast<double *>(base + o_lam), *step = reinterpret_cast<double *>(base + o_step);
+    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
+    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
+
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
+        de_ctx *c;
+        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
+        ~Nest() { c->nested--; }
+    };
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    {
+        Nest nest(c);
+        auto evaluate = [&](double *s, double *m, void *j, uint8_t *k) { // (ystats: the same three values every time)
+            const FitPlan fit{s, ys, j, nullptr};
+            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, nullptr, m, nullptr, k, nullptr, false, nullptr, &fit);
+        };
+        rc = evaluate(sA, mA, jA, okA);
+        if (rc != DE_OK) return rc;
+        HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
+        HIP_TRY(c, launch_lm_sse_scaled(sA, ys, p->n_trees, sseA, hist, c->stream));
+        const bool loop = N > 0 && o.iters > 0 && nc > 0;
+        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
+            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(DE_F64, sseA, p->n_trees, hist + r * nt, c->stream));
+        if (loop) {
+            rc = de_program_get_consts(p, cA); // (device to device behind a device set)
+            if (rc != DE_OK) return rc;
+            LmScaledStepArgs s;
+            std::memset(&s, 0, sizeof s);
+            s.n_trees = p->n_trees;
+            s.n_grad = tab.ng;
+            s.moff = tab.doff; s.joff = tab.joff; s.soff = tab.soff;
+            s.stats = sA; s.ystats = ys; s.dmom = mA; s.jtj = jA;
+            s.has = okA;
+            s.lam = lam;
+            s.step = step;
+            s.consts = cA;
+            s.trial = cT;
+            LmScaledAcceptArgs a;
+            std::memset(&a, 0, sizeof a);
+            a.n_trees = p->n_trees;
+            a.n_grad = tab.ng;
+            a.moff = tab.doff; a.joff = tab.joff; a.coff = tab.soff;
+            a.ystats = ys;
+            a.consts_acc = cA; a.jtj_acc = jA; a.stats_acc = sA; a.dmom_acc = mA; a.sse_acc = sseA; a.ok_acc = okA;
+            a.consts_trial = cT; a.jtj_trial = jT; a.stats_trial = sT; a.dmom_trial = mT; a.ok_trial = okT;
+            a.lam = lam;
+            a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
+            a.n_accept = acc;
+            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
+                HIP_TRY(c, launch_lm_step_scaled(p->dtype, s, c->stream));
+                rc = set_consts_device_impl(p, cT);
+                if (rc == DE_OK) rc = evaluate(sT, mT, jT, okT);
+                if (rc != DE_OK) break;
+                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
+                HIP_TRY(c, launch_lm_accept_scaled(p->dtype, a, c->stream));
+            }
+            c->last_kernel = "de_lm_accept_scaled_kernel";
+            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
+            const int rc2 = set_consts_device_impl(p, cA);
+            if (rc != DE_OK) return rc;
+            if (rc2 != DE_OK) return rc2;
+        }
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    HIP_TRY(c, hipMemcpyAsync(sse, sseA, nt * 8, h_sse ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (stats) HIP_TRY(c, hipMemcpyAsync(stats, sA, nt * 24, h_st ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (ystats) HIP_TRY(c, hipMemcpyAsync(ystats, ys, 24, h_ys ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ok, okA, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_sse || h_st || h_ys || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_consts_lm_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                            const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
+                            int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_scaled");
+    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept));
 }
 
 } // extern "C"

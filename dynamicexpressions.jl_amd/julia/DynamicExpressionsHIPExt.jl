@@ -922,8 +922,48 @@ function population_lm_step(
 end
 
 """
+    population_fit_stats_lm_step(ctx, stats, d_sum, d_pred, d_targ, jtj::Vector{Matrix{T}}, has_jtj, lam)
+        -> (steps::Vector{Vector{Float64}}, scaled_sse::Vector{Float64})
+
+The Levenberg-Marquardt step of every tree under linear scaling on the device (`de_fit_stats_lm_step`, DESIGN.md §4.4.8), from what
+`eval_population_fit_stats_grad` returned: the system `b² (jtj - D D' / W - P P' / m2_p)`, `2b (b P - Q)` is projected and solved
+(`population_lm_step`'s Cholesky) in one kernel, in Float64.  The zero vector where `has_jtj[t]` is false, the tree has no or more than
+`de_gn_max_rows()` rows, it is constant over the samples (`m2_p == 0`), an entry is not finite or a pivot is not positive.
+"""
+function population_fit_stats_lm_step(
+    ctx::HIPContext, stats::NamedTuple, d_sum::Vector{Vector{Float64}}, d_pred::Vector{Vector{Float64}}, d_targ::Vector{Vector{Float64}},
+    jtj::Vector{Matrix{T}}, has_jtj::AbstractVector{Bool}, lam,
+) where {T<:Union{Float32,Float64}}
+    n = length(d_sum)
+    @assert length(d_pred) == n && length(d_targ) == n && length(jtj) == n && length(has_jtj) == n && length(stats.mean_p) == n
+    ng = Int32[length(g) for g in d_sum]
+    @assert all(length(d_pred[t]) == ng[t] && length(d_targ[t]) == ng[t] && size(jtj[t]) == (ng[t], ng[t]) for t in 1:n)
+    offs = Int64[0; cumsum(Int64.(ng))]
+    st = Float64[v for t in 1:n for v in (stats.mean_p[t], stats.m2_p[t], stats.cov[t])]
+    ys = Float64[stats.W, stats.mean_y, stats.m2_y]
+    dm = Float64[v for t in 1:n for rows in (d_sum[t], d_pred[t], d_targ[t]) for v in rows]
+    jt = T[v for H in jtj for v in H]
+    isempty(st) && push!(st, 0.0)
+    isempty(dm) && push!(dm, 0.0)
+    isempty(jt) && push!(jt, zero(T))
+    has = UInt8[h ? 0x01 : 0x00 for h in has_jtj]
+    lams = lam isa Number ? fill(Float64(lam), n) : Vector{Float64}(lam)
+    @assert length(lams) == n
+    step = zeros(Float64, max(offs[end], 1))
+    sse = Vector{Float64}(undef, max(n, 1))
+    with_ctx(ctx) do hc
+        check(ctx, GC.@preserve ng st ys dm jt has lams step sse ccall(
+            (:de_fit_stats_lm_step, LIBDE), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            hc, T === Float32 ? Cint(0) : Cint(1), n, ng, st, ys, dm, C_NULL, jt, C_NULL, has, lams, step, sse))
+    end
+    return [step[(offs[t] + 1):offs[t + 1]] for t in 1:n], sse[1:n]
+end
+
+"""
     fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1, loss=:L2, loss_param=0.0, e_floor=1e-4,
-                                 wide=false)
+                                 wide=false, scaled=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
 Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm_ex`), minimising the loss
@@ -935,17 +975,41 @@ after `r - 1` iterations.  Trees that are incomplete at the start or wider than 
 with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrence rows need folding on the host).
 `wide=true` (`de_fit_consts_lm_wide`, DESIGN.md §4.4.7) also fits the trees of 9 to `de_gn_wide_max_rows()` = 32 constants; a narrower tree
 follows the default call's trajectory bit for bit.
+`scaled=true` (`de_fit_consts_lm_scaled`, DESIGN.md §4.4.8; `loss=:L2` and `wide=false` only) fits under Keijzer's linear scaling `a + b ŷ`:
+the objective is `scaled_sse = m2_y - cov² / m2_p`, every evaluation `de_eval_fit_stats_grad`'s.  It returns
+`(constants, scaled_sse::Vector{Float64}, ok, history, n_accept, stats)` with `stats` the NamedTuple of `eval_population_fit_stats_grad` at the
+accepted constants (slope `cov / m2_p`, intercept `mean_y - slope * mean_p`).
 """
 function fit_population_constants_lm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1, loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
-    wide::Bool=false,
+    wide::Bool=false, scaled::Bool=false,
 ) where {T}
+    scaled && wide && throw(ArgumentError("fit_population_constants_lm!(scaled=true, wide=true): the fit statistics form no matrix for trees of more than 8 rows"))
+    scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_lm!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
     any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lm!: shared GraphNode constants need the host loop"))
     opts = Ref(LmOpts(Int32(iters), Int32(0), Float64(lam0), Float64(up), Float64(down), 1e-12))
+    if scaled
+        sse = Vector{Float64}(undef, pop.n_trees)
+        stats = Matrix{Float64}(undef, 3, pop.n_trees)
+        ystats = fill(NaN, 3)
+        oks = Vector{UInt8}(undef, pop.n_trees)
+        hist = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+        acc = zeros(Int32, pop.n_trees)
+        with_pop(pop) do hc, hp
+            check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
+                (:de_fit_consts_lm_scaled, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+        end
+        consts = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+        st = (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3])
+        return consts, sse, oks .!= 0x00, hist, acc, st
+    end
     spec = loss_spec(loss, loss_param)
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)

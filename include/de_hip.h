@@ -87,7 +87,9 @@ extern "C" {
  *      fit of the constants under linear scaling a + b yhat needs.
  *      (k) de_gn_wide_max_rows, de_eval_loss_gn_wide, de_gn_lm_step_wide, de_fit_consts_lm_wide and the host-only hook
  *      de_lm_solve_host_wide: the Gauss-Newton matrix, the step and the fit for trees of 9 to 32 gradient rows; every
- *      entry point above keeps its bits and de_gn_max_rows() stays 8. */
+ *      entry point above keeps its bits and de_gn_max_rows() stays 8.
+ *      (l) de_fit_stats_lm_step, de_fit_consts_lm_scaled and the host-only hook de_lm_project_host: the Levenberg-Marquardt step and the
+ *      whole fit under linear scaling on the device, from what de_eval_fit_stats_grad returns; DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -692,6 +694,51 @@ int de_gn_lm_step_wide(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t 
 int de_fit_consts_lm_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                           const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts,
                           void *loss, uint8_t *ok, double *history, int32_t *n_accept);
+
+/* Levenberg-Marquardt on the constants under Keijzer's linear scaling a + b * yhat, on the device.  Additions: no
+ * entry point above changes what it returns.  The objective is scaled_sse = M2_y - C^2 / M2_p of de_eval_fit_stats, the residual of
+ * the best a + b * yhat; (a, b) are projected out of the Gauss-Newton system (variable projection, Kaufman's form).
+ *
+ * de_lm_project_host: the arithmetic for ONE tree of G rows on the host (no HIP call; csrc/de_lm_project.h, the source the kernel runs:
+ * the same bits).  stats = (mean_p, M2_p, C), ystats = (W, mean_y, M2_y), dmom = D | P | Q (3 G doubles) and H (column-major G x G
+ * doubles: the block of de_eval_fit_stats_grad converted to double) give, all in double and in this association,
+ *   b = C / M2_p,  *sse = M2_y - (C C) / M2_p,  g[k] = (2 b) (b P_k - Q_k),
+ *   Ht[i + G k] = (b b) ((H_ik - (D_i D_k) / W) - (P_i P_k) / M2_p)          (the lower triangle computed, mirrored)
+ * Returns 1 if the system was formed.  M2_p == 0 or W == 0: g = 0, Ht = 0, *sse = M2_y (NaN where C is NaN), returns 0; NaN
+ * statistics propagate (and de_lm_solve_host answers the zero step); a NaN *sse is the quiet NaN 0x7ff8000000000000 on both sides.  G outside 1 .. 8: returns 0, *sse as above, and (G > 8) the G
+ * entries of g and G^2 of Ht zero.
+ *
+ * de_fit_stats_lm_step: per tree t with G = n_grad[t] rows, step[soff_t .. soff_t + G) = de_lm_solve_host(Ht, g, lam[t]) of the
+ * projected system above, from the buffers de_eval_fit_stats_grad filled: stats (3 doubles per tree), ystats (3 doubles), dmom (tree t
+ * at dmom_offsets[t], 3 G doubles), jtj (elements of `dtype`, the block of tree t at jtj_offsets[t]); NULL offsets: packed.  step is
+ * packed (soff_t = the sum of the G before t); sse (may be NULL): one double per tree, its scaled_sse.  The step is ZERO where
+ * has[t] == 0, G == 0, G > 8, the system was not formed or de_gn_lm_step's solve answers zero.  n_grad and the offsets are host
+ * arrays; every other pointer is host or device, staged as in de_gn_lm_step.  With device pointers the call is stream-ordered and does
+ * not synchronise.
+ *
+ * de_fit_consts_lm_scaled: de_fit_consts_lm's loop with every evaluation de_eval_fit_stats_grad (mode DE_GRAD_CONSTANT, the matrix
+ * wanted) and  accept = has && has_trial && sse_trial < sse  on scaled_sse, in double; an accepted tree takes the trial constants,
+ * statistics, moments, matrix and flag.  The program holds the accepted constants afterwards.  sse[t] (doubles), stats (may be NULL:
+ * 3 doubles per tree — slope C / M2_p and intercept mean_y - slope mean_p without another launch; de_eval_fit_stats_grad at the
+ * result reproduces them bit for bit), ystats (may be NULL: 3 doubles), ok, history (may be NULL: (iters + 1) x n_trees doubles of
+ * scaled_sse), n_accept (may be NULL): host or device pointers.  opts == NULL: de_fit_consts_lm's defaults.  iters == 0, N == 0 or
+ * no constants: the first evaluation's values, every history row equal, the constants untouched.  A tree with ok == 0 at the start or
+ * G > 8 keeps its constant bits.  With device pointers it synchronises only where de_eval_fit_stats_grad does.  The refusals are
+ * de_fit_consts_lm's (DE_F16 / complex / de_program_create_cse programs, constant rows that differ from the constants:
+ * DE_ERR_UNSUPPORTED; a null y / ok / sse on a non-empty population, iters < 0, reserved != 0, a lam0 / up / down / lam_min that is not
+ * finite and positive: DE_ERR_INVALID_ARG), before any output or constant is touched.
+ * Not served: the scaled fit under non-L2 kinds, for trees of more than 8 rows and for programs made by de_program_create_cse; a tree
+ * with a constant that is redundant under scaling (an additive or multiplicative constant at the root) has a projected matrix with a
+ * zero row: the Cholesky step is zero for every lam and the tree keeps its constants. */
+int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H,
+                       double *sse, double *g, double *Ht);
+int de_fit_stats_lm_step(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_grad,
+                         const double *stats, const double *ystats, const double *dmom, const int64_t *dmom_offsets,
+                         const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam,
+                         double *step, double *sse);
+int de_fit_consts_lm_scaled(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                            const void *y, const void *w, const de_lm_opts_t *opts,
+                            double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_accept);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]

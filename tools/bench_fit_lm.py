@@ -6,8 +6,10 @@ fits alternate (device, host, device, host ...), every fit from the same startin
   wall ms / iteration   host clock around the call, the stream synchronised before and after, divided by the 10 iterations
   device ms / iteration the context's event ring over the fit (one entry for the device loop; the host loop's evaluations summed)
 --loss / --loss-param: the loss kind both legs minimise (api.LOSS_KINDS), L2 by default.
+--scaled: both legs fit under linear scaling: the device loop fit_constants_lm_device(scaled=True) =
+de_fit_consts_lm_scaled next to the host loop fit_constants_lm(scaled=True); the same shapes and alternation (L2 only).
 One JSON line per (trees, dtype, leg), then a table.  There is no CPU fallback: without a GPU the script fails.
-    python tools/bench_fit_lm.py [--reps 3] [--warmup 1] [--samples 100000] [--iters 10] [--trees 1000,10000] [--loss huber] [--loss-param 1.0]"""
+    python tools/bench_fit_lm.py [--reps 3] [--warmup 1] [--samples 100000] [--iters 10] [--trees 1000,10000] [--loss huber] [--loss-param 1.0] [--scaled]"""
 import argparse
 import json
 import os
@@ -26,7 +28,10 @@ def main():
     ap.add_argument("--trees", default="1000,10000")
     ap.add_argument("--loss", default="L2")
     ap.add_argument("--loss-param", type=float, default=0.0)
+    ap.add_argument("--scaled", action="store_true")
     a = ap.parse_args()
+    if a.scaled and a.loss != "L2":
+        raise SystemExit("tools/bench_fit_lm.py --scaled: the fit under linear scaling minimises the L2 residual only")
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -37,6 +42,8 @@ def main():
     ops = de.OperatorEnum(binary_operators=("+", "-", "*", "/"), unary_operators=("cos", "exp"))
     ctx = api.Context(0)
     kind = {} if a.loss == "L2" else dict(loss=a.loss, loss_param=a.loss_param)  # (L2: the call as it always was)
+    if a.scaled:
+        kind = dict(scaled=True)
     N = a.samples
     g = np.random.default_rng(0)
     x = g.uniform(-2, 2, N)
@@ -80,7 +87,7 @@ def main():
                     got[leg].append(fit(leg))
             for leg, runs in got.items():
                 wall, dev = np.median([r[0] for r in runs]), np.median([r[1] for r in runs])
-                row = dict(leg=leg, loss=a.loss, loss_param=a.loss_param, trees=n_trees, dtype=np.dtype(dtype).name, N=N, iters=a.iters, reps=a.reps,
+                row = dict(leg=leg, loss=a.loss, loss_param=a.loss_param, scaled=bool(a.scaled), trees=n_trees, dtype=np.dtype(dtype).name, N=N, iters=a.iters, reps=a.reps,
                            wall_ms_per_iter=round(float(wall) / max(a.iters, 1), 4), device_ms_per_iter=round(float(dev) / max(a.iters, 1), 4),
                            wall_ms_min=round(min(r[0] for r in runs) / max(a.iters, 1), 4), wall_ms_max=round(max(r[0] for r in runs) / max(a.iters, 1), 4),
                            timed_calls=runs[0][2], median_final_loss=runs[0][3])
