@@ -56,6 +56,7 @@ EXPORTS = [
     "de_gn_spec_check", "de_eval_loss_gn_ex", "de_fit_consts_lm_ex", "de_eval_fit_stats_grad",
     "de_gn_wide_max_rows", "de_eval_loss_gn_wide", "de_lm_solve_host_wide", "de_gn_lm_step_wide", "de_fit_consts_lm_wide",
     "de_lm_project_host", "de_fit_stats_lm_step", "de_fit_consts_lm_scaled",
+    "de_eval_fit_stats_grad_wide", "de_lm_project_host_wide", "de_fit_stats_lm_step_wide", "de_fit_consts_lm_scaled_wide",
 ]
 
 
@@ -290,7 +291,7 @@ class FitStatsGrad:
     """What ``Population.eval_fit_stats_grad`` returns (``de_eval_fit_stats_grad``): the ``FitStats`` of the population
     with their gradients over the rows ``theta`` the call selected.  Per tree ``d_sum[t] = D = sum w d``, ``d_pred[t] = P = sum w (yhat -
     mean_p) d``, ``d_targ[t] = Q = sum w (y - mean_y) d`` (``[G_t]`` each, float64) and ``jtj[t] = sum w d d^T`` (``[G_t, G_t]``, the
-    population's dtype; NaN where ``has_jtj`` is false); ``ok``; ``has_jtj = ok & (G_t <= GN_MAX_ROWS) & want_jtj``.  Everything derived is
+    population's dtype; NaN where ``has_jtj`` is false); ``ok``; ``has_jtj = ok & (G_t <= GN_MAX_ROWS) & want_jtj`` (``GN_WIDE_MAX_ROWS`` where ``eval_fit_stats_grad(wide=True)`` made it).  Everything derived is
     computed in float64 on the host and returned as one numpy vector (or matrix) per tree.  Where a tree is constant over the samples
     (``m2_p == 0``) the gradients of the scaled quantities and the projected matrix are 0; an incomplete tree holds NaN throughout."""
 
@@ -364,7 +365,9 @@ class FitStatsGrad:
         ``sum(n_grad[:t])``; bit for bit ``lm_solve_host`` of the ``g`` and ``Ht`` of ``lm_project_host``.  The zero step where ``has_jtj`` is false,
         the tree is constant over the samples or the solve answers zero (``GaussNewton.lm_step_device``).  ``return_sse=True``: (step,
         scaled_sse[n_trees] in float64).  ``ValueError`` for a population with shared GraphNode constants and for an object that
-        ``eval_fit_stats_grad`` did not make (or made with ``want_jtj=False``)."""
+        ``eval_fit_stats_grad`` did not make (or made with ``want_jtj=False``).  An object made by ``eval_fit_stats_grad(wide=True)`` calls
+        ``de_fit_stats_lm_step_wide``: trees of up to ``GN_WIDE_MAX_ROWS`` rows get ``lm_solve_host_wide`` of
+        ``lm_project_host_wide``'s system, the others keep their bytes."""
         pk = getattr(self, "_packed", None)
         if pk is None or pk["jtj"] is None:
             raise ValueError("lm_step_device needs the packed buffers of Population.eval_fit_stats_grad(want_jtj=True)")
@@ -372,7 +375,7 @@ class FitStatsGrad:
             raise ValueError("lm_step_device: the population shares GraphNode constants (per-occurrence rows): use projected().lm_step")
         ctx, st, dm, jt, ng, n = pk["ctx"], pk["stats"], pk["dmom"], pk["jtj"], pk["n_grad"], len(self)
         total = int(ng.sum())
-        fn = library().de_fit_stats_lm_step
+        fn = library().de_fit_stats_lm_step_wide if pk.get("wide") else library().de_fit_stats_lm_step
         if _is_torch(dm):
             import torch
             ctx.use_torch_stream()
@@ -458,6 +461,26 @@ def lm_project_host(stats3, ystats3, D, P, Q, H):
     g, Ht = np.full(max(G, 1), np.nan), np.full((max(G, 1), max(G, 1)), np.nan, order="F")
     Hp = np.asfortranarray(H if G else np.zeros((1, 1)))
     rc = library().de_lm_project_host(G, st.ctypes.data, ys.ctypes.data, dm.ctypes.data, Hp.ctypes.data, sse.ctypes.data, g.ctypes.data, Ht.ctypes.data)
+    return float(sse[0]), g[:G], (Ht[:G, :G] if G else np.zeros((0, 0))), bool(rc)
+
+
+def lm_project_host_wide(stats3, ystats3, D, P, Q, H):
+    """``de_lm_project_host_wide``: ``lm_project_host`` for trees of up to ``GN_WIDE_MAX_ROWS`` rows — ``lm_project_host``'s bits for G <= 8,
+    the same formulas in the same association with run-time loops (csrc/de_lm_project_wide.h, the source the wide step kernel runs)
+    beyond.  ``formed`` False: ``m2_p == 0``, ``W == 0`` or G outside 1 .. 32 — g and Ht are zero."""
+    st = np.ascontiguousarray(stats3, dtype=np.float64).reshape(-1)
+    ys = np.ascontiguousarray(ystats3, dtype=np.float64).reshape(-1)
+    rows = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (D, P, Q)]
+    G = rows[0].size
+    H = np.asfortranarray(H, dtype=np.float64)
+    if st.size != 3 or ys.size != 3 or rows[1].size != G or rows[2].size != G or H.shape != (G, G):
+        raise ValueError("stats3 and ystats3 hold three values, D, P and Q G entries each, and H is G x G")
+    dm = np.concatenate(rows + [np.zeros(1)])
+    sse = np.full(1, np.nan)
+    g, Ht = np.full(max(G, 1), np.nan), np.full((max(G, 1), max(G, 1)), np.nan, order="F")
+    Hp = np.asfortranarray(H if G else np.zeros((1, 1)))
+    rc = library().de_lm_project_host_wide(G, st.ctypes.data, ys.ctypes.data, dm.ctypes.data, Hp.ctypes.data, sse.ctypes.data, g.ctypes.data,
+                                           Ht.ctypes.data)
     return float(sse[0]), g[:G], (Ht[:G, :G] if G else np.zeros((0, 0))), bool(rc)
 
 
@@ -575,6 +598,11 @@ def library() -> C.CDLL:
         lib.de_lm_project_host.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp]
         lib.de_fit_stats_lm_step.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.de_fit_consts_lm_scaled.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LmOpts), vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "de_fit_consts_lm_scaled_wide"):  # (absent from a library built before the wide scaled fit: DE_HIP_LIB in an A/B run)
+        lib.de_eval_fit_stats_grad_wide.argtypes = lib.de_eval_fit_stats_grad.argtypes
+        lib.de_lm_project_host_wide.argtypes = lib.de_lm_project_host.argtypes
+        lib.de_fit_stats_lm_step_wide.argtypes = lib.de_fit_stats_lm_step.argtypes
+        lib.de_fit_consts_lm_scaled_wide.argtypes = lib.de_fit_consts_lm_scaled.argtypes
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1386,13 +1414,15 @@ class Population:
         return FitStats(per_tree[:, 0], per_tree[:, 1], per_tree[:, 2], ys[0], ys[1], ys[2]), ok
 
     def eval_fit_stats_grad(self, X, y, weights=None, variable: Union[bool, str] = False, params=None, classes=None,
-                            class_base: int = 1, want_jtj: bool = True) -> FitStatsGrad:
+                            class_base: int = 1, want_jtj: bool = True, wide: bool = False) -> FitStatsGrad:
         """The fit statistics of ``eval_fit_stats`` with their gradients over the rows ``variable`` selects (default: the constants), fused
         into one forward-dual launch (``de_eval_fit_stats_grad``): what optimising constants under a fitness "up to a
         linear transform" — ``scaled_sse``, Pearson's r^2 — needs, without the [n_grad, N] Jacobian.  ``want_jtj=False`` leaves the
         Gauss-Newton matrix out (``jtj[t]`` is then NaN, ``has_jtj`` False).  numpy in -> numpy out, torch device tensors in -> tensors
         out (the ``FitStats`` are host float64 either way).  For a GraphNode population the occurrence rows of a shared constant are summed
-        before anything is derived."""
+        before anything is derived.  ``wide=True`` (``de_eval_fit_stats_grad_wide``) also forms the matrix of a tree of
+        up to ``GN_WIDE_MAX_ROWS`` rows — ``has_jtj = ok & (G <= 32) & want_jtj``, the block that of ``eval_gauss_newton(wide=True)`` under
+        L2; everything else keeps the bits of the default call — and makes ``lm_step_device`` serve those trees."""
         self._refuse_f16("eval_fit_stats_grad")
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
@@ -1407,7 +1437,8 @@ class Population:
         offs, joffs = gn_offsets(ng)
         moffs = 3 * offs
         total, jtotal = max(int(moffs[-1]), 1), max(int(joffs[-1]), 1)
-        narrow = (ng <= GN_MAX_ROWS) & bool(want_jtj)
+        narrow = (ng <= (GN_WIDE_MAX_ROWS if wide else GN_MAX_ROWS)) & bool(want_jtj)
+        eval_fsg = lib.de_eval_fit_stats_grad_wide if wide else lib.de_eval_fit_stats_grad
 
         def vec(v, name):
             if v is None:
@@ -1436,7 +1467,7 @@ class Population:
             dm = torch.empty(total, dtype=torch.float64, device=dev)
             jt = torch.full((jtotal,), float("nan"), dtype=keep_x.dtype, device=dev)
             ok = torch.empty(nt, dtype=torch.uint8, device=dev)
-            self.ctx.check(lib.de_eval_fit_stats_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+            self.ctx.check(eval_fsg(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
                                                       st.data_ptr(), st.data_ptr() + 24 * nt, dm.data_ptr(), moffs.ctypes.data,
                                                       jt.data_ptr() if want_jtj else None, joffs.ctypes.data, ok.data_ptr()))
             okb = ok.bool()
@@ -1448,7 +1479,7 @@ class Population:
             dm = np.empty(total, dtype=np.float64)
             jt = np.full(jtotal, np.nan, dtype=self.dtype)
             ok = np.zeros(nt, dtype=np.uint8)
-            self.ctx.check(lib.de_eval_fit_stats_grad(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
+            self.ctx.check(eval_fsg(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, mode, yp, wp,
                                                       st.ctypes.data, st.ctypes.data + 24 * nt, dm.ctypes.data, moffs.ctypes.data,
                                                       jt.ctypes.data if want_jtj else None, joffs.ctypes.data, ok.ctypes.data))
             okb = ok.astype(bool)
@@ -1464,7 +1495,7 @@ class Population:
         out._ctx = self.ctx  # (projected(): lm_step_device needs a context)
         # the packed buffers the views above look into: FitStatsGrad.lm_step_device hands them to de_fit_stats_lm_step as they are
         out._packed = dict(ctx=self.ctx, dtype=_dtype_code(self.dtype), n_grad=np.ascontiguousarray(ng, dtype=np.int32), stats=st, dmom=dm,
-                           jtj=jt if want_jtj else None, occ=occ is not None)
+                           jtj=jt if want_jtj else None, occ=occ is not None, wide=bool(wide))
         return out
 
     def eval_loss_grad(self, X, y, weights=None, loss: str = "L2", variable: Union[bool, str] = False,
@@ -1617,9 +1648,8 @@ class Population:
         2^-24 / 2^-53); the loop only takes steps that lower it, so that noise bounds how far a fit proceeds, not what it may return.
 
         ``wide=True``: every evaluation is ``eval_gauss_newton(wide=True)``, so trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted
-        too (``lm_step`` solves any width); not with ``scaled=True`` (the fit statistics form no wide matrix: a ``ValueError``)."""
-        if scaled and wide:
-            raise ValueError("fit_constants_lm(scaled=True, wide=True): the fit statistics form no matrix for trees of more than 8 rows")
+        too (``lm_step`` solves any width); with ``scaled=True`` every evaluation is ``eval_fit_stats_grad(wide=True).projected()``
+        (DESIGN.md §4.4.9)."""
         if scaled and loss != "L2":
             raise ValueError(f"fit_constants_lm(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
         consts = np.array(consts0, dtype=self.dtype).reshape(-1).copy()
@@ -1629,7 +1659,7 @@ class Population:
         np.cumsum(self.n_consts, out=at[1:])
         gn_loss_spec(loss, loss_param, e_floor)  # (refused before the population's constants are touched)
         kind = dict(loss=loss, loss_param=loss_param, e_floor=e_floor, wide=wide)
-        evaluate = (lambda: self.eval_fit_stats_grad(X, y, weights=weights).projected()) if scaled else \
+        evaluate = (lambda: self.eval_fit_stats_grad(X, y, weights=weights, wide=wide).projected()) if scaled else \
             (lambda: self.eval_gauss_newton(X, y, weights=weights, **kind))
         self.set_constants(consts)
         gn = evaluate()
@@ -1677,18 +1707,42 @@ class Population:
         returned constants (slope and intercept without another launch; with torch inputs reading it copies 3 n_trees + 3 doubles to
         the host, the call itself does not).  The step is the Cholesky solve of ``lm_step_device``: a tree with a constant that is
         redundant under scaling (an additive or multiplicative constant at the root: a zero row of the projected matrix) gets the zero
-        step and keeps its constants, where the host loop's LU solve may still move it."""
+        step and keeps its constants, where the host loop's LU solve may still move it.  The scaled fit of trees of
+        more than ``GN_MAX_ROWS`` constants is ``fit_constants_lm_scaled_device(wide=True)``."""
         if scaled and wide:
-            raise ValueError("fit_constants_lm_device(scaled=True, wide=True): the fit statistics form no matrix for trees of more than 8 rows")
+            raise ValueError("fit_constants_lm_device(scaled=True, wide=True): the scaled fit of trees of more than 8 rows is "
+                             "fit_constants_lm_scaled_device(wide=True)")
         if scaled and loss != "L2":
             raise ValueError(f"fit_constants_lm_device(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
+        return self._fit_constants_lm_device(X, y, consts0, weights, iters, lam0, up, down, 1e-12, history, params, classes, class_base, loss,
+                                             loss_param, e_floor, wide, scaled)
+
+    def fit_constants_lm_scaled_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
+                                       down: float = 0.1, lam_min: float = 1e-12, history: Optional[list] = None, wide: bool = False,
+                                       params=None, classes=None, class_base: int = 1):
+        """The fit under Keijzer's linear scaling as ONE library call.  ``wide=False``: exactly ``fit_constants_lm_device(scaled=True)``
+        (``de_fit_consts_lm_scaled``; ``lam_min`` is then that call's 1e-12, any other value a ``ValueError``).
+        ``wide=True`` (``de_fit_consts_lm_scaled_wide``): trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted too —
+        every evaluation is ``eval_fit_stats_grad(wide=True)``'s, a wide tree's step ``lm_solve_host_wide`` of ``lm_project_host_wide``'s
+        system — and a tree of at most ``GN_MAX_ROWS`` follows the narrow call's trajectory bit for bit.  Returns (consts,
+        scaled_sse[n_trees] in float64, ok) and sets ``lm_fit_stats`` and ``lm_accepts`` as ``fit_constants_lm_device(scaled=True)`` does."""
+        if not wide:
+            if float(lam_min) != 1e-12:
+                raise ValueError("fit_constants_lm_scaled_device(wide=False) is fit_constants_lm_device(scaled=True): lam_min is 1e-12")
+            return self.fit_constants_lm_device(X, y, consts0, weights=weights, iters=iters, lam0=lam0, up=up, down=down, history=history,
+                                                params=params, classes=classes, class_base=class_base, scaled=True)
+        return self._fit_constants_lm_device(X, y, consts0, weights, iters, lam0, up, down, lam_min, history, params, classes, class_base, "L2",
+                                             0.0, 1e-4, True, True)
+
+    def _fit_constants_lm_device(self, X, y, consts0, weights, iters, lam0, up, down, lam_min, history, params, classes, class_base, loss,
+                                 loss_param, e_floor, wide, scaled):
         self._refuse_f16("fit_constants_lm_device")
         spec = gn_loss_spec(loss, loss_param, e_floor)
         if self._occ is not None:
             raise ValueError("fit_constants_lm_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_lm")
-        opts = LmOpts(int(iters), 0, float(lam0), float(up), float(down), 1e-12)
-        if opts.iters < 0 or not all(np.isfinite(v) and v > 0 for v in (opts.lam0, opts.up, opts.down)):
+        opts = LmOpts(int(iters), 0, float(lam0), float(up), float(down), float(lam_min))
+        if opts.iters < 0 or not all(np.isfinite(v) and v > 0 for v in (opts.lam0, opts.up, opts.down, opts.lam_min)):
             raise ValueError("fit_constants_lm_device: iters >= 0 and finite positive lam0, up, down")
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -1735,7 +1789,8 @@ class Population:
                 lo, st, ok = np.empty(nt, dtype=np.float64), np.full(3 * nt + 3, np.nan), np.zeros(nt, dtype=np.uint8)
                 hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
                 ptrs = (lo.ctypes.data, st.ctypes.data, st.ctypes.data + 24 * nt, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-            self.ctx.check(lib.de_fit_consts_lm_scaled(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
+            fit = lib.de_fit_consts_lm_scaled_wide if wide else lib.de_fit_consts_lm_scaled
+            self.ctx.check(fit(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
             self.lm_accepts = acc
             self._lm_fit_raw = st if nt else None  # (lm_fit_stats reads it: a device tensor is copied only then)
             if history is not None:

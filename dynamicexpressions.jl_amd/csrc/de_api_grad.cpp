@@ -2,6 +2,8 @@
 // generic gradient program, the glue around the host encoders of its direct-threaded and reverse-accumulation forms (de_grad_encode.cpp)
 // with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels; de_gn_lm_step / de_fit_consts_lm /
 // de_lm_solve_host: Levenberg-Marquardt on the constants around de_eval_loss_gn's launch (kernels de_lm.hip).
+#include <functional>
+
 #include "de_api_internal.h"
 #include "de_grad_encode.h"
 #include "de_lm.h"
@@ -10,6 +12,7 @@
 #include "de_lm_solve_wide.h"
 #include "de_lm_scaled.h"
 #include "de_lm_project.h"
+#include "de_lm_project_wide.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -563,6 +566,7 @@ struct FitPlan {
     double *stats, *ystats;
     void *jtj; // may be null: no matrix wanted
     const int64_t *jtj_offsets;
+    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_fit_stats_grad_wide: DE_GN_WIDE_MAX_ROWS)
 };
 // de_gn_spec_check with its reason (null = good; *rc: DE_ERR_INVALID_ARG or DE_ERR_UNSUPPORTED).  dtype < 0: the element type is not known.
 static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap) {
@@ -715,7 +719,7 @@ static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N
             std::vector<unsigned char> zj((size_t)std::max<int64_t>(jspan, 1) * es);
             for (int64_t t = 0; t < p->n_trees; t++) {
                 const int64_t gg = (int64_t)ng[(size_t)t] * ng[(size_t)t];
-                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= DE_GN_MAX_ROWS ? 0.0 : nan;
+                const double v = p->host_ok_grad[(size_t)t] && ng[(size_t)t] <= fit->rows_n0 ? 0.0 : nan;
                 for (int64_t e = 0; e < gg; e++) {
                     if (p->dtype == DE_F32) reinterpret_cast<float *>(zj.data())[joff[(size_t)t] + e] = (float)v;
                     else reinterpret_cast<double *>(zj.data())[joff[(size_t)t] + e] = v;
@@ -1498,40 +1502,43 @@ static int64_t gn_wide_chunk(int64_t N, int64_t rows, int64_t n_wide, size_t es)
     return std::min<int64_t>(chunk, (N + 255) / 256 * 256);
 }
 
-static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
-                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
-                        const int64_t *jtj_offsets, uint8_t *ok) {
-    if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
-    if (!p->in_cse.empty())
-        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss_gn_wide: a program made by de_program_create_cse has one gradient row per occurrence of a "
-                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
-    const GnPlan gn{jtj, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
-    // The wide trees.  None (or no sample, or arguments the narrow call refuses): exactly de_eval_loss_gn_ex's path, no further launch.
-    const bool mode_ok = mode == DE_GRAD_VARIABLE || mode == DE_GRAD_CONSTANT || mode == DE_GRAD_BOTH;
-    std::vector<int32_t> ng((size_t)p->n_trees);
-    std::vector<int64_t> joff((size_t)p->n_trees);
-    int64_t n_wide = 0, rows = 0, tri = 0, jspan = 0, jrun = 0;
-    bool neg = false;
-    for (int64_t t = 0; t < p->n_trees && mode_ok; t++) {
+// What a wide call knows of its trees before anything runs: the widths in `mode`, the blocks' offsets, and the trees of 9 .. 32 rows
+struct GnWideScan {
+    std::vector<int32_t> ng;
+    std::vector<int64_t> joff;
+    int64_t n_wide = 0, rows = 0, tri = 0, jspan = 0;
+    bool mode_ok = false, neg = false; // neg: a negative offset (refused by the narrow call)
+};
+static GnWideScan gn_wide_scan(const de_program_t *p, int mode, const int64_t *jtj_offsets, const int64_t *dloss_offsets) {
+    GnWideScan sc;
+    sc.mode_ok = mode == DE_GRAD_VARIABLE || mode == DE_GRAD_CONSTANT || mode == DE_GRAD_BOTH;
+    sc.ng.assign((size_t)p->n_trees, 0);
+    sc.joff.assign((size_t)p->n_trees, 0);
+    int64_t jrun = 0;
+    for (int64_t t = 0; t < p->n_trees && sc.mode_ok; t++) {
         const int32_t g = (int32_t)de_program_n_grad(p, t, mode);
-        ng[(size_t)t] = g;
-        joff[(size_t)t] = jtj_offsets ? jtj_offsets[t] : jrun;
-        neg = neg || joff[(size_t)t] < 0 || (dloss_offsets && dloss_offsets[t] < 0);
+        sc.ng[(size_t)t] = g;
+        sc.joff[(size_t)t] = jtj_offsets ? jtj_offsets[t] : jrun;
+        sc.neg = sc.neg || sc.joff[(size_t)t] < 0 || (dloss_offsets && dloss_offsets[t] < 0);
         jrun += (int64_t)g * g;
-        jspan = std::max(jspan, joff[(size_t)t] + (int64_t)g * g);
-        if (g > DE_GN_MAX_ROWS && g <= DE_GN_WIDE_MAX_ROWS) { n_wide++; rows += g; tri += (int64_t)g * (g + 1) / 2; }
+        sc.jspan = std::max(sc.jspan, sc.joff[(size_t)t] + (int64_t)g * g);
+        if (g > DE_GN_MAX_ROWS && g <= DE_GN_WIDE_MAX_ROWS) { sc.n_wide++; sc.rows += g; sc.tri += (int64_t)g * (g + 1) / 2; }
     }
-    char why[160];
-    int src = DE_OK;
-    const bool refused = !mode_ok || neg || N < 0 || !ok || !dloss || !jtj || !X || !y || ldX < p->n_features || loss_spec_problem(spec, 1, why, sizeof why) ||
-                         gn_spec_problem(spec, e_floor, p->dtype, &src, why, sizeof why);
-    if (n_wide == 0 || N <= 0 || refused)
-        return loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr, false, &gn);
+    return sc;
+}
+
+// The wide route behind either narrow call (de_eval_loss_gn_wide: a GnPlan, de_eval_fit_stats_grad_wide: a FitPlan).  The inputs are staged
+// once, narrow(Xd, yd, wd, pargs, jtj_d, ok_d) runs the narrow call on them — everything but the wide blocks, into the device images of
+// jtj and ok — and then the wide trees' constants, chunks, Gram matrices and folds follow, which do not depend on which plan ran: (spec,
+// e_floor) alone select the curvature weight ({DE_LOSS_L2, 0, 0}: c = 1).  sc.n_wide > 0, N > 0, and arguments the narrow call takes.
+using GnWideNarrow = std::function<int(const void *Xd, const void *yd, const void *wd, const de_param_args_t *pargs, void *jtj_d, uint8_t *ok_d)>;
+static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                       const void *w, const de_loss_spec_t *spec, double e_floor, void *jtj, uint8_t *ok, const GnWideScan &sc,
+                       const GnWideNarrow &narrow) {
     int rc = check_param_args(c, p, pa, N);
     if (rc != DE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = gn_wide_cache(c, p, mode, ng);
+    rc = gn_wide_cache(c, p, mode, sc.ng);
     if (rc != DE_OK) return rc;
     GnWideCache *gw = p->gnw;
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
@@ -1553,14 +1560,14 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
     if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
     const char *Xd = static_cast<const char *>(sX.dev), *yd = static_cast<const char *>(sY.dev), *wd = w ? static_cast<const char *>(sW.dev) : nullptr;
     // the pool
-    const int64_t chunk = gn_wide_chunk(N, rows, n_wide, es);
+    const int64_t chunk = gn_wide_chunk(N, sc.rows, sc.n_wide, es);
     const int64_t n_slices_max = (chunk + GNW_SLICE - 1) / GNW_SLICE;
     const bool h_j = !is_device_ptr(jtj), h_ok = !is_device_ptr(ok);
     size_t at = 0;
-    const size_t o_jac = lm_place(&at, (size_t)rows * (size_t)chunk * es), o_val = lm_place(&at, (size_t)n_wide * (size_t)chunk * es),
-                 o_oks = lm_place(&at, (size_t)n_wide), o_cf = lm_place(&at, nc * es), o_cs = lm_place(&at, (size_t)gw->n_consts * es),
-                 o_part = lm_place(&at, (size_t)n_slices_max * (size_t)tri * 8), o_tot = lm_place(&at, (size_t)tri * 8),
-                 o_j = h_j ? lm_place(&at, (size_t)std::max<int64_t>(jspan, 1) * es) : 0, o_ok = h_ok ? lm_place(&at, nt) : 0;
+    const size_t o_jac = lm_place(&at, (size_t)sc.rows * (size_t)chunk * es), o_val = lm_place(&at, (size_t)sc.n_wide * (size_t)chunk * es),
+                 o_oks = lm_place(&at, (size_t)sc.n_wide), o_cf = lm_place(&at, nc * es), o_cs = lm_place(&at, (size_t)gw->n_consts * es),
+                 o_part = lm_place(&at, (size_t)n_slices_max * (size_t)sc.tri * 8), o_tot = lm_place(&at, (size_t)sc.tri * 8),
+                 o_j = h_j ? lm_place(&at, (size_t)std::max<int64_t>(sc.jspan, 1) * es) : 0, o_ok = h_ok ? lm_place(&at, nt) : 0;
     if (at > c->sGnw.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
     HIP_TRY(c, c->sGnw.reserve(at));
     char *base = static_cast<char *>(c->sGnw.p);
@@ -1568,17 +1575,17 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
     uint8_t *ok_d = h_ok ? reinterpret_cast<uint8_t *>(base + o_ok) : ok;
     // the table of the wide trees, uploaded when the offsets differ from what the device holds
     {
-        std::vector<unsigned char> img((size_t)n_wide * sizeof(GnWideTree));
+        std::vector<unsigned char> img((size_t)sc.n_wide * sizeof(GnWideTree));
         GnWideTree *tab = reinterpret_cast<GnWideTree *>(img.data());
         int64_t r0 = 0, t0 = 0;
-        for (size_t s = 0; s < (size_t)n_wide; s++) {
+        for (size_t s = 0; s < (size_t)sc.n_wide; s++) {
             std::memset(&tab[s], 0, sizeof tab[s]);
             const int32_t t = gw->trees[s], g = gw->rows[s];
             tab[s].tree = t;
             tab[s].G = g;
             tab[s].row0 = r0;
             tab[s].tri0 = t0;
-            tab[s].joff = joff[(size_t)t];
+            tab[s].joff = sc.joff[(size_t)t];
             r0 += g;
             t0 += (int64_t)g * (g + 1) / 2;
         }
@@ -1596,9 +1603,8 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
             explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
             ~Nest() { c->nested--; }
         } nest(c);
-        // 1. loss, dloss, ok and the narrow blocks with de_eval_loss_gn_ex's bits (the wide blocks: NaN for now)
-        const GnPlan gnd{jtj_d, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
-        rc = loss_grad_impl(c, p, Xd, N, ldX, pa_use, mode, yd, wd, spec, loss, dloss, dloss_offsets, ok_d, nullptr, false, &gnd);
+        // 1. everything but the wide blocks, with the narrow call's bits (the wide blocks: NaN for now)
+        rc = narrow(Xd, yd, wd, pa_use, jtj_d, ok_d);
         if (rc != DE_OK) return rc;
         // 2. the wide trees' constants, device to device where the program's are on the device
         if (gw->n_consts > 0 && gw->consts_gen != p->consts_gen) {
@@ -1613,14 +1619,14 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
         GnWideGramArgs ga;
         std::memset(&ga, 0, sizeof ga);
         ga.trees = static_cast<const GnWideTree *>(gw->d_tab);
-        ga.n_wide = (int32_t)n_wide;
+        ga.n_wide = (int32_t)sc.n_wide;
         ga.jac = base + o_jac;
         ga.vals = base + o_val;
         ga.kind = spec->kind;
         ga.param = spec->param;
         ga.e_floor = e_floor;
         ga.partial = reinterpret_cast<double *>(base + o_part);
-        ga.tri_total = tri;
+        ga.tri_total = sc.tri;
         for (int64_t j0 = 0; j0 < N; j0 += chunk) {
             const int64_t n = std::min(chunk, N - j0);
             de_param_args_t pac;
@@ -1637,7 +1643,7 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
             ga.w = wd ? wd + (size_t)j0 * es : nullptr;
             ga.n = n;
             HIP_TRY(c, launch_gnw_gram(p->dtype, ga, c->stream));
-            HIP_TRY(c, launch_gnw_fold(p->dtype, ga.trees, ga.n_wide, ga.partial, (n + GNW_SLICE - 1) / GNW_SLICE, tri, reinterpret_cast<double *>(base + o_tot),
+            HIP_TRY(c, launch_gnw_fold(p->dtype, ga.trees, ga.n_wide, ga.partial, (n + GNW_SLICE - 1) / GNW_SLICE, sc.tri, reinterpret_cast<double *>(base + o_tot),
                                        j0 == 0, j0 + n >= N, jtj_d, ok_d, c->stream));
         }
         c->last_kernel = "de_gnw_gram_kernel";
@@ -1645,18 +1651,71 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
     if (!c->nested) HIP_TRY(c, time_end(c));
     if (h_j)
         for (int64_t t = 0; t < p->n_trees; t++)
-            if (ng[(size_t)t] > 0)
-                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(jtj) + (size_t)joff[(size_t)t] * es, static_cast<char *>(jtj_d) + (size_t)joff[(size_t)t] * es,
-                                          (size_t)ng[(size_t)t] * (size_t)ng[(size_t)t] * es, hipMemcpyDeviceToHost, c->stream));
+            if (sc.ng[(size_t)t] > 0)
+                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(jtj) + (size_t)sc.joff[(size_t)t] * es, static_cast<char *>(jtj_d) + (size_t)sc.joff[(size_t)t] * es,
+                                          (size_t)sc.ng[(size_t)t] * (size_t)sc.ng[(size_t)t] * es, hipMemcpyDeviceToHost, c->stream));
     if (h_ok) HIP_TRY(c, hipMemcpyAsync(ok, ok_d, nt, hipMemcpyDeviceToHost, c->stream));
     if (h_j || h_ok) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DE_OK;
+}
+static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
+                        const int64_t *jtj_offsets, uint8_t *ok) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss_gn_wide: a program made by de_program_create_cse has one gradient row per occurrence of a "
+                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
+    const GnPlan gn{jtj, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
+    // The wide trees.  None (or no sample, or arguments the narrow call refuses): exactly de_eval_loss_gn_ex's path, no further launch.
+    const GnWideScan sc = gn_wide_scan(p, mode, jtj_offsets, dloss_offsets);
+    char why[160];
+    int src = DE_OK;
+    const bool refused = !sc.mode_ok || sc.neg || N < 0 || !ok || !dloss || !jtj || !X || !y || ldX < p->n_features || loss_spec_problem(spec, 1, why, sizeof why) ||
+                         gn_spec_problem(spec, e_floor, p->dtype, &src, why, sizeof why);
+    if (sc.n_wide == 0 || N <= 0 || refused)
+        return loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, loss, dloss, dloss_offsets, ok, nullptr, false, &gn);
+    // loss, dloss, ok and the narrow blocks with de_eval_loss_gn_ex's bits
+    return gn_wide_run(c, p, X, N, ldX, pa, mode, y, w, spec, e_floor, jtj, ok, sc,
+                       [&](const void *Xd, const void *yd, const void *wd, const de_param_args_t *pa_use, void *jtj_d, uint8_t *ok_d) {
+                           const GnPlan gnd{jtj_d, jtj_offsets, e_floor, DE_GN_WIDE_MAX_ROWS};
+                           return loss_grad_impl(c, p, Xd, N, ldX, pa_use, mode, yd, wd, spec, loss, dloss, dloss_offsets, ok_d, nullptr, false, &gnd);
+                       });
+}
+// de_eval_fit_stats_grad_wide: the same route behind de_eval_fit_stats_grad (a FitPlan), the wide blocks those of {DE_LOSS_L2, 0, 0}
+static int fit_stats_grad_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                                    const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets, void *jtj,
+                                    const int64_t *jtj_offsets, uint8_t *ok) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_fit_stats_grad_wide: a program made by de_program_create_cse has one gradient row per occurrence of a "
+                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
+    static const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    const FitPlan fit{stats, ystats, jtj, jtj_offsets, DE_GN_WIDE_MAX_ROWS};
+    // No matrix wanted, no wide tree, no sample, or arguments the narrow call refuses: exactly de_eval_fit_stats_grad's path, no further launch.
+    const GnWideScan sc = gn_wide_scan(p, mode, jtj_offsets, dmom_offsets);
+    const bool refused = !sc.mode_ok || sc.neg || N < 0 || !ok || !dmom || !stats || !ystats || !X || !y || ldX < p->n_features;
+    if (!jtj || sc.n_wide == 0 || N <= 0 || refused)
+        return loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, nullptr, dmom, dmom_offsets, ok, nullptr, false, nullptr, &fit);
+    // stats, ystats, dmom, ok and the narrow blocks with de_eval_fit_stats_grad's bits
+    return gn_wide_run(c, p, X, N, ldX, pa, mode, y, w, &spec, 0.0, jtj, ok, sc,
+                       [&](const void *Xd, const void *yd, const void *wd, const de_param_args_t *pa_use, void *jtj_d, uint8_t *ok_d) {
+                           const FitPlan fd{stats, ystats, jtj_d, jtj_offsets, DE_GN_WIDE_MAX_ROWS};
+                           return loss_grad_impl(c, p, Xd, N, ldX, pa_use, mode, yd, wd, &spec, nullptr, dmom, dmom_offsets, ok_d, nullptr, false, nullptr, &fd);
+                       });
 }
 int de_eval_loss_gn_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
                          const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss,
                          const int64_t *dloss_offsets, void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
     DE_REFUSE_F16("de_eval_loss_gn_wide");
     DE_NOTHROW(c, gn_wide_impl(c, p, X, N, ldX, pa, mode, y, w, spec, e_floor, loss, dloss, dloss_offsets, jtj, jtj_offsets, ok));
+}
+int de_eval_fit_stats_grad_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                                const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets,
+                                void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
+    DE_REFUSE_F16("de_eval_fit_stats_grad_wide");
+    DE_NOTHROW(c, fit_stats_grad_wide_impl(c, p, X, N, ldX, pa, mode, y, w, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, ok));
 }
 int de_gn_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
                        const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
@@ -1685,7 +1744,7 @@ int de_lm_project_host(int G, const double *stats, const double *ystats, const d
 
 static int fit_stats_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
                                   const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets,
-                                  const uint8_t *has, const double *lam, double *step, double *sse) {
+                                  const uint8_t *has, const double *lam, double *step, double *sse, bool wide = false) {
     if (!c) return DE_ERR_INVALID_ARG;
     if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_fit_stats_lm_step: dtype must be DE_F32 or DE_F64");
     if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
@@ -1726,6 +1785,10 @@ static int fit_stats_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const
     if (!c->nested) HIP_TRY(c, time_begin(c));
     HIP_TRY(c, launch_lm_step_scaled(dtype, a, c->stream));
     c->last_kernel = "de_lm_step_scaled_kernel";
+    if (wide) { // de_fit_stats_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step (and the sse) the kernel above gave them
+        HIP_TRY(c, launch_lm_step_scaled_wide(dtype, a, c->stream));
+        c->last_kernel = "de_lm_step_scaled_wide_kernel";
+    }
     if (!c->nested) HIP_TRY(c, time_end(c));
     if (h_step && sspan) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, sspan * 8, hipMemcpyDeviceToHost, c->stream));
     if (h_sse) HIP_TRY(c, hipMemcpyAsync(sse, base + o_sse, nt * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1738,10 +1801,12 @@ int de_fit_stats_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t 
     DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse));
 }
 
-// fit_consts_lm_impl's loop with every evaluation de_eval_fit_stats_grad's (a FitPlan into the state) and the kernels of de_lm_scaled.hip
+// fit_consts_lm_impl's loop with every evaluation de_eval_fit_stats_grad's (a FitPlan into the state) and the kernels of de_lm_scaled.hip.
+// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm_scaled) or DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_scaled_wide:
+// every evaluation de_eval_fit_stats_grad_wide's, and the wide trees' steps by de_lm_step_scaled_wide_kernel)
 static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                                      const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
-                                     double *history, int32_t *n_accept) {
+                                     double *history, int32_t *n_accept, int row_limit) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
@@ -1818,7 +1883,9 @@ static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X
     const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
     {
         Nest nest(c);
+        const bool wide = row_limit > DE_GN_MAX_ROWS;
         auto evaluate = [&](double *s, double *m, void *j, uint8_t *k) { // (ystats: the same three values every time)
+            if (wide) return fit_stats_grad_wide_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, s, ys, m, nullptr, j, nullptr, k);
             const FitPlan fit{s, ys, j, nullptr};
             return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, nullptr, m, nullptr, k, nullptr, false, nullptr, &fit);
         };
@@ -1854,8 +1921,10 @@ static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X
             a.lam = lam;
             a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
             a.n_accept = acc;
+            a.row_limit = row_limit;
             for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
                 HIP_TRY(c, launch_lm_step_scaled(p->dtype, s, c->stream));
+                if (wide) HIP_TRY(c, launch_lm_step_scaled_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
                 rc = set_consts_device_impl(p, cT);
                 if (rc == DE_OK) rc = evaluate(sT, mT, jT, okT);
                 if (rc != DE_OK) break;
@@ -1883,7 +1952,30 @@ int de_fit_consts_lm_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t
                             const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
                             int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_lm_scaled");
-    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept));
+    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_MAX_ROWS));
+}
+
+// ---- de_lm_project_host_wide / de_fit_stats_lm_step_wide / de_fit_consts_lm_scaled_wide (kernel: de_lm_scaled_wide.hip,
+// arithmetic: de_lm_project_wide.h; de_eval_fit_stats_grad_wide stands beside de_eval_loss_gn_wide above)
+int de_lm_project_host_wide(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
+    if (G >= 0 && G <= LM_MAX_ROWS) return de_lm_project_host(G, stats, ystats, dmom, H, sse, g, Ht); // (lm_project itself: the same bits by construction)
+    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
+    if (G < 0) return 0; // (nothing else is written)
+    if (stats && ystats && dmom && H && g && Ht && G <= LM_WIDE_MAX_ROWS) return lm_project_wide(G, stats, ystats, dmom, H, g, Ht);
+    for (int k = 0; g && k < G; k++) g[k] = 0.0;
+    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
+    return 0;
+}
+int de_fit_stats_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                              const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
+                              const double *lam, double *step, double *sse) {
+    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse, true));
+}
+int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                 const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
+                                 int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_scaled_wide");
+    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
 }
 
 } // extern "C"

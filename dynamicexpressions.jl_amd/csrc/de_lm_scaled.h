@@ -24,9 +24,14 @@ struct LmScaledStepArgs {
     void *trial;
 };
 hipError_t launch_lm_step_scaled(int dtype, const LmScaledStepArgs &a, hipStream_t stream);
+// One wave per tree with 8 < n_grad <= 32 (de_lm_scaled_wide.hip): the same contract with the projection of de_lm_project_wide.h folded
+// into the load of the matrix and lm_solve_wide's arithmetic (de_lm_solve_wide.h); every other tree is left alone (launch_lm_step_scaled
+// has served it, and has given the wide trees the zero step and their sse).
+hipError_t launch_lm_step_scaled_wide(int dtype, const LmScaledStepArgs &a, hipStream_t stream);
 
 // One thread per tree: the accept rule of Population.fit_constants_lm(scaled=True) on scaled_sse, in double.  *_acc: the accepted state,
-// *_trial: the evaluation at the trial constants; ok and G <= 8 make `has`.  history_row / n_accept may be null.
+// *_trial: the evaluation at the trial constants; ok and G <= row_limit make `has` (8: de_fit_consts_lm_scaled, 32:
+// de_fit_consts_lm_scaled_wide).  history_row / n_accept may be null.
 struct LmScaledAcceptArgs {
     int64_t n_trees;
     const int32_t *n_grad;
@@ -42,6 +47,7 @@ struct LmScaledAcceptArgs {
     double up, down, lam_min;
     double *history_row; // n_trees entries: the accepted scaled_sse after this iteration
     int32_t *n_accept;
+    int32_t row_limit;
 };
 hipError_t launch_lm_accept_scaled(int dtype, const LmScaledAcceptArgs &a, hipStream_t stream);
 

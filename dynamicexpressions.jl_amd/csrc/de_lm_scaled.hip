@@ -57,8 +57,8 @@ __global__ void __launch_bounds__(256) de_lm_accept_scaled_kernel(LmScaledAccept
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n_trees) return;
     const int G = a.n_grad[t];
-    const bool narrow = G <= LM_MAX_ROWS;
-    const bool has_acc = narrow && a.ok_acc[t], has_trial = narrow && a.ok_trial[t];
+    const bool fitted = G <= a.row_limit;
+    const bool has_acc = fitted && a.ok_acc[t], has_trial = fitted && a.ok_trial[t];
     const double *stt = a.stats_trial + 3 * t;
     const double sse_trial = lm_scaled_sse(stt[1], stt[2], a.ystats[0], a.ystats[2]);
     const bool accept = has_acc && has_trial && sse_trial < a.sse_acc[t]; // (a NaN compares false)

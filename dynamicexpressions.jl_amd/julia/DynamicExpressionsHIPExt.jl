@@ -833,7 +833,7 @@ function eval_population_gauss_newton(
 end
 
 """
-    eval_population_fit_stats_grad(pop, X, y; weights=nothing, variable=Val(false), want_jtj=true)
+    eval_population_fit_stats_grad(pop, X, y; weights=nothing, variable=Val(false), want_jtj=true, wide=false)
         -> (stats::NamedTuple, d_sum, d_pred, d_targ, jtj::Vector{Matrix{T}}, ok, has_jtj)
 
 The fit statistics of `eval_population_fit_stats` with their gradients over the rows of `variable`, in one forward-dual launch
@@ -841,10 +841,12 @@ The fit statistics of `eval_population_fit_stats` with their gradients over the 
 `d_targ[t] = Q = Σ w (y - mean_y) d` (`Vector{Float64}`) and `jtj[t] = Σ w d d'` (NaN where `has_jtj[t]` is false).  With
 `b = cov / m2_p` the gradient of the residual under linear scaling is `2b (b P - Q)` and `b² (jtj - D D' / W - P P' / m2_p)` its
 Gauss-Newton matrix with the scale and offset projected out.  For a GraphNode the rows of a shared constant are summed.
+`wide=true` (`de_eval_fit_stats_grad_wide`, DESIGN.md §4.4.9) also forms the matrix of a tree of 9 to `de_gn_wide_max_rows()` = 32 rows —
+the block of `eval_population_gauss_newton(wide=true)` under L2 — and keeps every other bit of the default call.
 """
 function eval_population_fit_stats_grad(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing, variable=Val(false),
-    want_jtj::Bool=true,
+    want_jtj::Bool=true, wide::Bool=false,
 ) where {T}
     mode = grad_mode(variable)
     F, N = size(X)
@@ -859,15 +861,24 @@ function eval_population_fit_stats_grad(
         joffs = Int64[0; cumsum(ng .* ng)]
         dm = Vector{Float64}(undef, max(moffs[end], 1))
         jt = fill(T(NaN), max(joffs[end], 1))
-        check(pop.ctx, GC.@preserve X y weights stats ystats dm jt moffs joffs ok ccall(
-            (:de_eval_fit_stats_grad, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
-             Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
-            hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), stats, ystats,
-            dm, moffs, want_jtj ? pointer(jt) : C_NULL, joffs, ok))
+        if wide
+            check(pop.ctx, GC.@preserve X y weights stats ystats dm jt moffs joffs ok ccall(
+                (:de_eval_fit_stats_grad_wide, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+                hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), stats, ystats,
+                dm, moffs, want_jtj ? pointer(jt) : C_NULL, joffs, ok))
+        else
+            check(pop.ctx, GC.@preserve X y weights stats ystats dm jt moffs joffs ok ccall(
+                (:de_eval_fit_stats_grad, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}),
+                hc, hp, X, N, F, C_NULL, mode, y, weights === nothing ? C_NULL : pointer(weights), stats, ystats,
+                dm, moffs, want_jtj ? pointer(jt) : C_NULL, joffs, ok))
+        end
         (dm, jt, ng, moffs, joffs)
     end
-    max_rows = ccall((:de_gn_max_rows, LIBDE), Cint, ())
+    max_rows = wide ? ccall((:de_gn_wide_max_rows, LIBDE), Cint, ()) : ccall((:de_gn_max_rows, LIBDE), Cint, ())
     okb = ok .!= 0x00
     rows(q) = [combine_rows(pop, t, dm[(moffs[t] + q * ng[t] + 1):(moffs[t] + (q + 1) * ng[t])], mode) for t in 1:pop.n_trees]
     jtj = map(1:pop.n_trees) do t
@@ -922,17 +933,19 @@ function population_lm_step(
 end
 
 """
-    population_fit_stats_lm_step(ctx, stats, d_sum, d_pred, d_targ, jtj::Vector{Matrix{T}}, has_jtj, lam)
+    population_fit_stats_lm_step(ctx, stats, d_sum, d_pred, d_targ, jtj::Vector{Matrix{T}}, has_jtj, lam; wide=false)
         -> (steps::Vector{Vector{Float64}}, scaled_sse::Vector{Float64})
 
 The Levenberg-Marquardt step of every tree under linear scaling on the device (`de_fit_stats_lm_step`, DESIGN.md §4.4.8), from what
 `eval_population_fit_stats_grad` returned: the system `b² (jtj - D D' / W - P P' / m2_p)`, `2b (b P - Q)` is projected and solved
 (`population_lm_step`'s Cholesky) in one kernel, in Float64.  The zero vector where `has_jtj[t]` is false, the tree has no or more than
 `de_gn_max_rows()` rows, it is constant over the samples (`m2_p == 0`), an entry is not finite or a pivot is not positive.
+`wide=true` (`de_fit_stats_lm_step_wide`, DESIGN.md §4.4.9) also solves the trees of 9 to 32 rows that
+`eval_population_fit_stats_grad(wide=true)` formed the matrix of; a narrower tree keeps the default call's bytes.
 """
 function population_fit_stats_lm_step(
     ctx::HIPContext, stats::NamedTuple, d_sum::Vector{Vector{Float64}}, d_pred::Vector{Vector{Float64}}, d_targ::Vector{Vector{Float64}},
-    jtj::Vector{Matrix{T}}, has_jtj::AbstractVector{Bool}, lam,
+    jtj::Vector{Matrix{T}}, has_jtj::AbstractVector{Bool}, lam; wide::Bool=false,
 ) where {T<:Union{Float32,Float64}}
     n = length(d_sum)
     @assert length(d_pred) == n && length(d_targ) == n && length(jtj) == n && length(has_jtj) == n && length(stats.mean_p) == n
@@ -952,11 +965,19 @@ function population_fit_stats_lm_step(
     step = zeros(Float64, max(offs[end], 1))
     sse = Vector{Float64}(undef, max(n, 1))
     with_ctx(ctx) do hc
-        check(ctx, GC.@preserve ng st ys dm jt has lams step sse ccall(
-            (:de_fit_stats_lm_step, LIBDE), Cint,
-            (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8},
-             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-            hc, T === Float32 ? Cint(0) : Cint(1), n, ng, st, ys, dm, C_NULL, jt, C_NULL, has, lams, step, sse))
+        if wide
+            check(ctx, GC.@preserve ng st ys dm jt has lams step sse ccall(
+                (:de_fit_stats_lm_step_wide, LIBDE), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                hc, T === Float32 ? Cint(0) : Cint(1), n, ng, st, ys, dm, C_NULL, jt, C_NULL, has, lams, step, sse))
+        else
+            check(ctx, GC.@preserve ng st ys dm jt has lams step sse ccall(
+                (:de_fit_stats_lm_step, LIBDE), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                hc, T === Float32 ? Cint(0) : Cint(1), n, ng, st, ys, dm, C_NULL, jt, C_NULL, has, lams, step, sse))
+        end
     end
     return [step[(offs[t] + 1):offs[t + 1]] for t in 1:n], sse[1:n]
 end
@@ -975,7 +996,8 @@ after `r - 1` iterations.  Trees that are incomplete at the start or wider than 
 with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrence rows need folding on the host).
 `wide=true` (`de_fit_consts_lm_wide`, DESIGN.md §4.4.7) also fits the trees of 9 to `de_gn_wide_max_rows()` = 32 constants; a narrower tree
 follows the default call's trajectory bit for bit.
-`scaled=true` (`de_fit_consts_lm_scaled`, DESIGN.md §4.4.8; `loss=:L2` and `wide=false` only) fits under Keijzer's linear scaling `a + b ŷ`:
+`scaled=true` (`de_fit_consts_lm_scaled`, DESIGN.md §4.4.8; `loss=:L2` only; with `wide=true` `de_fit_consts_lm_scaled_wide`, §4.4.9: trees of up
+to 32 constants, a narrower tree on the default call's trajectory bit for bit) fits under Keijzer's linear scaling `a + b ŷ`:
 the objective is `scaled_sse = m2_y - cov² / m2_p`, every evaluation `de_eval_fit_stats_grad`'s.  It returns
 `(constants, scaled_sse::Vector{Float64}, ok, history, n_accept, stats)` with `stats` the NamedTuple of `eval_population_fit_stats_grad` at the
 accepted constants (slope `cov / m2_p`, intercept `mean_y - slope * mean_p`).
@@ -985,7 +1007,6 @@ function fit_population_constants_lm!(
     iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1, loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
     wide::Bool=false, scaled::Bool=false,
 ) where {T}
-    scaled && wide && throw(ArgumentError("fit_population_constants_lm!(scaled=true, wide=true): the fit statistics form no matrix for trees of more than 8 rows"))
     scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_lm!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
@@ -1000,11 +1021,19 @@ function fit_population_constants_lm!(
         hist = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
         acc = zeros(Int32, pop.n_trees)
         with_pop(pop) do hc, hp
-            check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
-                (:de_fit_consts_lm_scaled, LIBDE), Cint,
-                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
-                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-                hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+            if wide
+                check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
+                    (:de_fit_consts_lm_scaled_wide, LIBDE), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                    hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+            else
+                check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
+                    (:de_fit_consts_lm_scaled, LIBDE), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LmOpts},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                    hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+            end
         end
         consts = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
         st = (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3])

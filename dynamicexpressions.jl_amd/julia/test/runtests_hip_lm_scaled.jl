@@ -29,6 +29,6 @@ const HIP = DynamicExpressionsHIPExt
     @test sse_fit[1] <= max(1e-9 * history[1, 1], 4 * 1024 * 2.0^-53 * stats.m2_y)
     slope = stats.cov[1] / stats.m2_p[1]
     @test isapprox(slope, -3.0; atol=1e-4) && isapprox(stats.mean_y - slope * stats.mean_p[1], 2.0; atol=1e-4)
-    @test_throws ArgumentError HIP.fit_population_constants_lm!(pop, X, y; scaled=true, wide=true)
+    # (scaled=true with wide=true is served since DESIGN.md §4.4.9: test/runtests_hip_lm_scaled_wide.jl)
     @test_throws ArgumentError HIP.fit_population_constants_lm!(pop, X, y; scaled=true, loss=:huber, loss_param=1.0)
 end

@@ -89,7 +89,9 @@ extern "C" {
  *      de_lm_solve_host_wide: the Gauss-Newton matrix, the step and the fit for trees of 9 to 32 gradient rows; every
  *      entry point above keeps its bits and de_gn_max_rows() stays 8.
  *      (l) de_fit_stats_lm_step, de_fit_consts_lm_scaled and the host-only hook de_lm_project_host: the Levenberg-Marquardt step and the
- *      whole fit under linear scaling on the device, from what de_eval_fit_stats_grad returns; DE_F32 / DE_F64. */
+ *      whole fit under linear scaling on the device, from what de_eval_fit_stats_grad returns; DE_F32 / DE_F64.
+ *      (m) de_eval_fit_stats_grad_wide, de_fit_stats_lm_step_wide, de_fit_consts_lm_scaled_wide and the host-only hook
+ *      de_lm_project_host_wide: the same for trees of 9 to 32 gradient rows; every entry point above keeps its bits. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -682,7 +684,7 @@ int de_lm_solve_host(int G, const double *H, const double *g, double lam, double
  * de_fit_consts_lm_wide: de_fit_consts_lm_ex's arguments and loop with has = ok && G <= 32: every evaluation is de_eval_loss_gn_wide, a
  * tree with G <= 8 follows de_fit_consts_lm_ex's trajectory bit for bit (constants, loss, history, n_accept), and afterwards
  * de_eval_loss_grad_ex reproduces loss[t] bit for bit for every tree.  The same refusals; reserved stays 0.
- * Not served: de_eval_fit_stats_grad for wide trees, programs with shared subtrees, more than 32 rows. */
+ * Not served: programs with shared subtrees, more than 32 rows.  (de_eval_fit_stats_grad for wide trees: de_eval_fit_stats_grad_wide below.) */
 int de_gn_wide_max_rows(void); /* 32 */
 int de_eval_loss_gn_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
                          const de_param_args_t *pargs, int mode, const void *y, const void *w,
@@ -727,7 +729,8 @@ int de_fit_consts_lm_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int6
  * de_fit_consts_lm's (DE_F16 / complex / de_program_create_cse programs, constant rows that differ from the constants:
  * DE_ERR_UNSUPPORTED; a null y / ok / sse on a non-empty population, iters < 0, reserved != 0, a lam0 / up / down / lam_min that is not
  * finite and positive: DE_ERR_INVALID_ARG), before any output or constant is touched.
- * Not served: the scaled fit under non-L2 kinds, for trees of more than 8 rows and for programs made by de_program_create_cse; a tree
+ * Not served: the scaled fit under non-L2 kinds and for programs made by de_program_create_cse (trees of 9 to 32 rows:
+ * de_fit_consts_lm_scaled_wide below; these three calls keep their limit of 8); a tree
  * with a constant that is redundant under scaling (an additive or multiplicative constant at the root) has a projected matrix with a
  * zero row: the Cholesky step is zero for every lam and the tree keeps its constants. */
 int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H,
@@ -739,6 +742,55 @@ int de_fit_stats_lm_step(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_
 int de_fit_consts_lm_scaled(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                             const void *y, const void *w, const de_lm_opts_t *opts,
                             double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_accept);
+
+/* The fit under linear scaling for trees of 9 to 32 gradient rows: the wide route (§4.4.7) and the scaled fit (§4.4.8)
+ * joined.  Additions: every entry point above keeps its bits, its NaN blocks, its zero steps and its refusals; de_gn_max_rows() == 8 and
+ * de_gn_wide_max_rows() == 32.
+ *
+ * de_eval_fit_stats_grad_wide: de_eval_fit_stats_grad's arguments, pointers, staging, offsets and stream order.
+ *   stats, ystats, dmom, ok  de_eval_fit_stats_grad's, bit for bit, for every tree
+ *   G_t <= 8                 the jtj block of de_eval_fit_stats_grad, bit for bit
+ *   8 < G_t <= 32, ok[t]     the block de_eval_loss_gn_wide writes for the same population, mode, X, w and {DE_LOSS_L2, 0, 0}, bit for bit:
+ *                            the same sub-program, chunk rule (DE_GN_WIDE_CHUNK included), Gram and fold kernels with c = 1, so the same
+ *                            bound |jtj - exact| <= 256 u sum_j |w d_i d_k| and the same run-to-run reproducibility
+ *   ok[t] == 0 or G_t > 32   a NaN block; neither is an error
+ * jtj == NULL (no matrix wanted), a population without a tree of 9 .. 32 rows, and N == 0 (blocks of 0 for G_t <= 32, NaN where the flag
+ * already fails) take de_eval_fit_stats_grad's path with no further launch.  Weights that are all zero at N > 0 give wide blocks of exact
+ * 0 (the Gram kernel's select excludes every sample).  Refusals, before any output is touched: what de_eval_fit_stats_grad refuses,
+ * with the same codes, and DE_ERR_UNSUPPORTED for a program made by de_program_create_cse (one gradient row per occurrence of a shared
+ * constant: the caller folds them, S H S^T, and keeps the host loop).  Scratch: de_eval_fit_stats_grad's and de_eval_loss_gn_wide's.
+ *
+ * de_lm_project_host_wide: de_lm_project_host for G in 1 .. 32 (host only) — de_lm_project_host's bits for G <= 8; for 8 < G <= 32 the
+ * same formulas in the same association, in double, with run-time loops (csrc/de_lm_project_wide.h, the source the kernel runs: the same
+ * bits), the lower triangle of H read and the result mirrored.  The not-formed rules (M2_p == 0 or W == 0: g = 0, Ht = 0, returns 0),
+ * the NaN propagation and the canonical quiet NaN of *sse are de_lm_project_host's.  G > 32: returns 0, *sse as above, the G entries of
+ * g and G^2 of Ht zero; G < 1: returns 0.
+ *
+ * de_fit_stats_lm_step_wide: de_fit_stats_lm_step's arguments.  A tree with G <= 8 gets de_fit_stats_lm_step's bytes, step and sse (that
+ * call's kernel runs first).  A tree with 8 < G <= 32 gets, bit for bit, de_lm_solve_host_wide(Ht, g, lam[t]) of
+ * de_lm_project_host_wide's system and that hook's sse: one wave per tree, the projection folded into the load of the matrix into LDS,
+ * then de_gn_lm_step_wide's Cholesky.  The step is ZERO where has[t] == 0, G == 0, G > 32, the system was not formed or the solve
+ * answers zero.  Entries of `step` no tree owns are not written.
+ *
+ * de_fit_consts_lm_scaled_wide: de_fit_consts_lm_scaled's arguments and loop with has = ok && G <= 32: every evaluation is
+ * de_eval_fit_stats_grad_wide, the wide trees' steps are de_fit_stats_lm_step_wide's, a tree with G <= 8 follows
+ * de_fit_consts_lm_scaled's trajectory bit for bit (constants, sse, stats, history, n_accept).  Afterwards the program holds the accepted
+ * constants and de_eval_fit_stats_grad at the result reproduces stats bit for bit.  Inside the fit no constant, statistic, moment or
+ * matrix reaches the host.  The refusals and the iters == 0, N == 0 and no-constants rules are de_fit_consts_lm_scaled's.
+ * Not served: the scaled fit under non-L2 kinds, programs made by de_program_create_cse, more than 32 rows. */
+int de_eval_fit_stats_grad_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
+                                const de_param_args_t *pargs, int mode, const void *y, const void *w,
+                                double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets,
+                                void *jtj, const int64_t *jtj_offsets, uint8_t *ok);
+int de_lm_project_host_wide(int G, const double *stats, const double *ystats, const double *dmom, const double *H,
+                            double *sse, double *g, double *Ht);
+int de_fit_stats_lm_step_wide(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_grad,
+                              const double *stats, const double *ystats, const double *dmom, const int64_t *dmom_offsets,
+                              const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam,
+                              double *step, double *sse);
+int de_fit_consts_lm_scaled_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                                 const void *y, const void *w, const de_lm_opts_t *opts,
+                                 double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_accept);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
