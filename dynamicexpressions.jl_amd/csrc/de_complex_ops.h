@@ -198,8 +198,15 @@ template <typename T> __device__ __forceinline__ Cx<T> c_cos(Cx<T> z) {
 template <typename T> __device__ __forceinline__ Cx<T> c_tanh(Cx<T> z) {
     const T xi = z.re, eta = z.im;
     if (xi != xi && eta == T(0)) return {xi, eta};
-    if (T(4) * M<T>::abs(xi) > CR<T>::asinh_omega())
-        return {M<T>::copysign(T(1), xi), M<T>::copysign(T(0), eta * (__builtin_isfinite(eta) ? M<T>::sin(T(2) * M<T>::abs(eta)) : T(1)))};
+    if (T(4) * M<T>::abs(xi) > CR<T>::asinh_omega()) {
+        // the sign of the zero is that of eta sin(2|eta|); where 2|eta| overflows (Julia's sin(Inf) throws) sin(2a) = 2 sin a cos a gives it
+        T sg = T(1);
+        if (__builtin_isfinite(eta)) {
+            const T a = M<T>::abs(eta), a2 = T(2) * a;
+            sg = __builtin_isfinite(a2) ? M<T>::sin(a2) : M<T>::sin(a) * M<T>::cos(a);
+        }
+        return {M<T>::copysign(T(1), xi), M<T>::copysign(T(0), eta * sg)};
+    }
     const T t = CR<T>::tan(eta), beta = T(1) + t * t, s = M<T>::sinh(xi), rho = M<T>::sqrt(T(1) + s * s);
     if (__builtin_isinf(t)) return {rho / s, T(1) / t};
     const T den = T(1) + beta * s * s;

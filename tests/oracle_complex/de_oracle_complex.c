@@ -142,8 +142,11 @@ static int o_parse(const de_tape_node_t *tape, int64_t n, int64_t n_consts, int 
     static CT ctanh_jl##S(CT z) {                                                                                              \
         R xi = crealf_##S(z), eta = cimagf_##S(z);                                                                              \
         if (isnan(xi) && eta == 0) return z;                                                                                     \
-        if (4 * fabs##FS(xi) > (R)(OMEGA))                                                                                       \
-            return mk##S(copysign##FS(1, xi), copysign##FS(0, eta * (isfinite(eta) ? sin##FS(2 * fabs##FS(eta)) : (R)1)));      \
+        if (4 * fabs##FS(xi) > (R)(OMEGA)) { /* 2|eta| overflowing: the sign of sin(2a) from sin a cos a */      \
+            R sg = 1, a = fabs##FS(eta);                                                                                         \
+            if (isfinite(eta)) sg = isfinite(2 * a) ? sin##FS(2 * a) : sin##FS(a) * cos##FS(a);                                  \
+            return mk##S(copysign##FS(1, xi), copysign##FS(0, eta * sg));                                                        \
+        }                                                                                                                        \
         R t = tan##FS(eta), be = 1 + t * t, s = sinh##FS(xi), rho = sqrt##FS(1 + s * s);                                        \
         if (isinf(t)) return mk##S(rho / s, 1 / t);                                                                             \
         R den = 1 + be * s * s;                                                                                                  \
