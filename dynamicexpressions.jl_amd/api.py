@@ -22,6 +22,7 @@ PyTorch is used only as the owner of device memory / streams.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple, Union
@@ -57,6 +58,7 @@ EXPORTS = [
     "de_gn_wide_max_rows", "de_eval_loss_gn_wide", "de_lm_solve_host_wide", "de_gn_lm_step_wide", "de_fit_consts_lm_wide",
     "de_lm_project_host", "de_fit_stats_lm_step", "de_fit_consts_lm_scaled",
     "de_eval_fit_stats_grad_wide", "de_lm_project_host_wide", "de_fit_stats_lm_step_wide", "de_fit_consts_lm_scaled_wide",
+    "de_bfgs_max_rows", "de_bfgs_direction_host", "de_bfgs_update_host", "de_fit_consts_bfgs",
 ]
 
 
@@ -83,6 +85,12 @@ class LmOpts(C.Structure):
     """``de_lm_opts_t``: what ``de_fit_consts_lm`` takes besides the data (null: 10 iterations, lam0 1e-3, up 10, down 0.1, floor 1e-12)."""
     _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("lam0", C.c_double), ("up", C.c_double), ("down", C.c_double),
                 ("lam_min", C.c_double)]
+
+
+class BfgsOpts(C.Structure):
+    """``de_bfgs_opts_t``: what ``de_fit_consts_bfgs`` takes besides the data (null: 20 iterations, step0 1, shrink 0.5, c1 1e-4, curv 1e-8)."""
+    _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("step0", C.c_double), ("shrink", C.c_double), ("c1", C.c_double),
+                ("curv", C.c_double)]
 
 
 # de_loss_kind_t (include/de_hip.h): name -> enum value.  "pullback" belongs to the gradient entry points only.
@@ -176,6 +184,7 @@ class FitStats:
 
 GN_MAX_ROWS = 8  # de_gn_max_rows(): the widest tree (gradient rows of the library's layout) de_eval_loss_gn forms the matrix of
 GN_WIDE_MAX_ROWS = 32  # de_gn_wide_max_rows(): ... and de_eval_loss_gn_wide (``wide=True``)
+BFGS_MAX_ROWS = 32  # de_bfgs_max_rows(): the widest tree de_fit_consts_bfgs fits
 
 
 def gn_offsets(n_grad):
@@ -484,6 +493,56 @@ def lm_project_host_wide(stats3, ystats3, D, P, Q, H):
     return float(sse[0]), g[:G], (Ht[:G, :G] if G else np.zeros((0, 0))), bool(rc)
 
 
+def bfgs_direction_host(B, fresh, alpha: float, g, step0: float = 1.0):
+    """``de_bfgs_direction_host``: the direction of the device's BFGS fit (csrc/de_bfgs.h) for one tree on the host, no GPU needed.  ``B``:
+    the G x G inverse-Hessian approximation (symmetric), ``fresh`` / ``alpha``: the rest of the tree's state, ``g``: the gradient.
+    Returns (p[G], slope, produced, B, fresh, alpha) in float64 — the state after the call (new objects; reset to ``I``, True and
+    ``a0(g)`` where ``-B g`` is no descent direction).  ``produced`` False: ``p`` is zero (G outside 1 .. 32, a non-finite entry, g = 0)."""
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+    G = g.size
+    B = np.array(B, dtype=np.float64, order="C").reshape(G, G)
+    fr, al = np.array([1 if fresh else 0], dtype=np.uint8), np.array([float(alpha)])
+    p, slope = np.full(max(G, 1), np.nan), np.full(1, np.nan)
+    rc = library().de_bfgs_direction_host(G, B.ctypes.data, fr.ctypes.data, al.ctypes.data, g.ctypes.data, float(step0), p.ctypes.data,
+                                          slope.ctypes.data)
+    return p[:G], float(slope[0]), bool(rc), B, bool(fr[0]), float(al[0])
+
+
+def bfgs_update_host(B, fresh, s, yv, curv: float = 1e-8):
+    """``de_bfgs_update_host``: the rank-two update of the device's BFGS fit (csrc/de_bfgs.h) for one tree on the host.  ``s``: the step
+    taken, ``yv``: the change of the gradient.  Returns (updated, B, fresh) — new objects; unchanged where ``updated`` is False (the
+    curvature test ``s.yv > curv |s| |yv|`` failed, a non-finite sum, or G outside 1 .. 32)."""
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+    yv = np.ascontiguousarray(yv, dtype=np.float64).reshape(-1)
+    G = s.size
+    if yv.size != G:
+        raise ValueError("s and yv have G entries each")
+    B = np.array(B, dtype=np.float64, order="C").reshape(G, G)
+    fr = np.array([1 if fresh else 0], dtype=np.uint8)
+    rc = library().de_bfgs_update_host(G, B.ctypes.data, fr.ctypes.data, s.ctypes.data, yv.ctypes.data, float(curv))
+    return bool(rc), B, bool(fr[0])
+
+
+def _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param):
+    """(``BfgsOpts``, ``LossSpec``) of a BFGS fit, refused as ``de_fit_consts_bfgs`` refuses them: a ``ValueError``."""
+    if loss == "pullback":
+        raise ValueError("loss 'pullback' is the cotangent of a pullback, not an objective")
+    spec = loss_spec(loss, loss_param)
+    opts = BfgsOpts(int(iters), 0, float(step0), float(shrink), float(c1), float(curv))
+    if opts.iters < 0 or not all(np.isfinite(v) and v > 0 for v in (opts.step0, opts.c1, opts.curv)) or not 0.0 < opts.shrink < 1.0:
+        raise ValueError("BFGS fit: iters >= 0, finite positive step0, c1 and curv, and shrink in (0, 1)")
+    return opts, spec
+
+
+def _bfgs_a0(g, step0: float) -> float:
+    """The first trial step's length of the BFGS fit, ``|g| > step0 ? step0 / |g| : 1``, in csrc/de_bfgs.h's summation order."""
+    gg = 0.0
+    for v in np.asarray(g, dtype=np.float64).reshape(-1).tolist():
+        gg = gg + v * v
+    n = math.sqrt(gg)
+    return step0 / n if n > step0 else 1.0
+
+
 def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
 
@@ -603,6 +662,12 @@ def library() -> C.CDLL:
         lib.de_lm_project_host_wide.argtypes = lib.de_lm_project_host.argtypes
         lib.de_fit_stats_lm_step_wide.argtypes = lib.de_fit_stats_lm_step.argtypes
         lib.de_fit_consts_lm_scaled_wide.argtypes = lib.de_fit_consts_lm_scaled.argtypes
+    if hasattr(lib, "de_fit_consts_bfgs"):  # (absent from a library built before the device BFGS fit: DE_HIP_LIB in an A/B run)
+        lib.de_bfgs_max_rows.argtypes = []
+        lib.de_bfgs_direction_host.argtypes = [C.c_int, vp, vp, vp, vp, C.c_double, vp, vp]
+        lib.de_bfgs_update_host.argtypes = [C.c_int, vp, vp, vp, vp, C.c_double]
+        lib.de_fit_consts_bfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
+                                           vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -1811,6 +1876,135 @@ class Population:
         fit = lib.de_fit_consts_lm_wide if wide else lib.de_fit_consts_lm_ex
         self.ctx.check(fit(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec), float(e_floor), C.byref(opts), *ptrs))
         self.lm_accepts = acc
+        if history is not None:
+            history.extend(hist[r] for r in range(rows))
+        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
+    def fit_constants_bfgs(self, X, y, consts0, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
+                           curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None,
+                           classes=None, class_base: int = 1):
+        """BFGS on the constants of every tree at once, from the loss and its gradient alone (the plain loop; one ``eval_loss_grad`` per
+        iteration behind the one at ``consts0``) — the reference's ``optimize(f, g!, tree, BFGS())`` with a backtracking
+        line search.  Every kind ``eval_loss_grad`` takes except "pullback" is an objective, "l1_hinge" included, and every tree of up to
+        ``BFGS_MAX_ROWS`` constants is fitted.  Per tree and iteration: ``bfgs_direction_host`` gives the direction ``p`` and its slope, the
+        trial constants are ``T(c + alpha p)``, and the trial is accepted if its tree is complete and ``f_trial < f`` and ``f_trial <= f +
+        (c1 alpha) slope`` (Armijo); an accepted tree's ``B`` takes ``bfgs_update_host`` of the step actually taken and ``alpha`` returns
+        to 1, a rejected tree's ``alpha`` shrinks by ``shrink``.  ``consts0``: ``set_constants``' layout.  Incomplete trees, trees without
+        constants and trees of more than ``BFGS_MAX_ROWS`` constants keep ``consts0``.  Returns (consts, loss[n_trees] in the population's
+        dtype, ok) at the accepted constants, which the population holds afterwards; ``history`` (a list) receives the accepted losses
+        (float64) after every evaluation, ``self.bfgs_accepts`` the number of accepted steps per tree."""
+        self._refuse_f16("fit_constants_bfgs")
+        _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)  # (refused before the population's constants are touched)
+        consts = np.array(_host(consts0), dtype=self.dtype).reshape(-1).copy()
+        if consts.size != int(self.n_consts.sum()):
+            raise ValueError("wrong number of constants")
+        nt, f64 = self.n_trees, np.float64
+        at = np.zeros(nt + 1, dtype=np.int64)
+        np.cumsum(self.n_consts, out=at[1:])
+        fitted = [1 <= int(at[t + 1] - at[t]) <= BFGS_MAX_ROWS for t in range(nt)]
+
+        def evaluate():
+            lo, gr, ok = self.eval_loss_grad(X, y, weights=weights, loss=loss, loss_param=loss_param, params=params, classes=classes,
+                                             class_base=class_base)
+            return _host(lo).copy(), [_host(g).astype(f64) for g in gr], _host(ok).astype(bool).copy()
+
+        self.set_constants(consts)
+        lo, gr, ok = evaluate()
+        B = [np.eye(int(at[t + 1] - at[t])) for t in range(nt)]
+        fresh, alpha = [True] * nt, [_bfgs_a0(gr[t], step0) if fitted[t] else 1.0 for t in range(nt)]
+        acc = np.zeros(nt, dtype=np.int32)
+        if history is not None:
+            history.append(lo.astype(f64))
+        for _ in range(int(iters)):
+            trial, produced, slope = consts.copy(), [False] * nt, [0.0] * nt
+            for t in range(nt):
+                if fitted[t] and ok[t]:
+                    p, slope[t], produced[t], B[t], fresh[t], alpha[t] = bfgs_direction_host(B[t], fresh[t], alpha[t], gr[t], step0)
+                    if produced[t]:
+                        trial[at[t]:at[t + 1]] = (consts[at[t]:at[t + 1]].astype(f64) + alpha[t] * p).astype(self.dtype)
+            self.set_constants(trial)
+            lo_t, gr_t, ok_t = evaluate()
+            for t in range(nt):
+                f, ft = float(lo[t]), float(lo_t[t])
+                if (fitted[t] and ok[t] and produced[t] and ok_t[t] and math.isfinite(ft) and ft < f
+                        and ft <= f + (c1 * alpha[t]) * slope[t]):
+                    a, b = at[t], at[t + 1]
+                    _, B[t], fresh[t] = bfgs_update_host(B[t], fresh[t], trial[a:b].astype(f64) - consts[a:b].astype(f64), gr_t[t] - gr[t], curv)
+                    consts[a:b] = trial[a:b]
+                    lo[t], gr[t], ok[t] = lo_t[t], gr_t[t], ok_t[t]
+                    alpha[t] = _bfgs_a0(gr[t], step0) if fresh[t] else 1.0
+                    acc[t] += 1
+                else:
+                    alpha[t] = alpha[t] * shrink
+            if history is not None:
+                history.append(lo.astype(f64))
+        self.set_constants(consts)
+        self.bfgs_accepts = acc
+        return consts, lo, ok
+
+    def fit_constants_bfgs_device(self, X, y, consts0=None, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5,
+                                  c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                                  history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+        """``fit_constants_bfgs`` as ONE library call (``de_fit_consts_bfgs``): the directions, the trial constants, the
+        accept rule and the updates of ``B`` run on the device; no constant, gradient or matrix reaches the host, and the trajectory is
+        the host loop's bit for bit.  ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the
+        population's current constants.  Returns (consts, loss[n_trees] in the population's dtype, ok) at the accepted constants, which
+        the population holds afterwards; with torch inputs all three are device tensors and nothing synchronises beyond what
+        ``eval_loss_grad`` does.  ``history`` (a list) receives the ``iters + 1`` rows of accepted losses (float64); ``self.bfgs_accepts``
+        holds the number of accepted steps per tree.  A population with shared GraphNode constants raises ``ValueError``:
+        ``fit_constants_bfgs`` serves it."""
+        self._refuse_f16("fit_constants_bfgs_device")
+        opts, spec = _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
+        if self._occ is not None:
+            raise ValueError("fit_constants_bfgs_device: the population shares GraphNode constants (their per-occurrence rows are combined "
+                             "on the host): use fit_constants_bfgs")
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        pa = self._param_args(params, classes, class_base, N, keep)
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                n, p_ = v.numel(), v.data_ptr()
+            else:
+                v = np.ascontiguousarray(v, dtype=self.dtype)
+                n, p_ = v.size, v.ctypes.data
+            if n != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return p_
+
+        if y is None:
+            raise ValueError("fit_constants_bfgs_device: y is required")
+        yp, wp = vec(y, "y"), vec(weights, "weights")
+        if consts0 is not None:
+            n_expected = int(self.n_consts.sum())
+            if (consts0.numel() if _is_torch(consts0) else np.size(consts0)) != n_expected:
+                raise ValueError("wrong number of constants")
+            self.set_constants(consts0 if _is_torch(consts0) else np.asarray(consts0).reshape(-1))
+        nt, rows = self.n_trees, int(iters) + 1
+        if is_t:
+            import torch
+            dev = keep_x.device
+            lo = torch.empty(nt, dtype=keep_x.dtype, device=dev)
+            ok = torch.empty(nt, dtype=torch.uint8, device=dev)
+            hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
+            acc = torch.empty(nt, dtype=torch.int32, device=dev)
+            ptrs = (lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
+        else:
+            lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
+            hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
+            ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
+        self.ctx.check(library().de_fit_consts_bfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
+                                                    C.byref(opts), *ptrs))
+        self.bfgs_accepts = acc
         if history is not None:
             history.extend(hist[r] for r in range(rows))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))

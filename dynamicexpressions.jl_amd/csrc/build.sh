@@ -124,8 +124,10 @@ build_obj de_gn_wide.hip $OBJ/de_gn_wide.o &
 build_obj de_lm_scaled.hip $OBJ/de_lm_scaled.o &
 # de_fit_stats_lm_step_wide / de_fit_consts_lm_scaled_wide: the scaled step of trees of 9 .. 32 constants, one wave per tree (plain hipcc)
 build_obj de_lm_scaled_wide.hip $OBJ/de_lm_scaled_wide.o &
+# de_fit_consts_bfgs: the init, direction and accept kernels of the BFGS fit, one wave per tree (plain hipcc)
+build_obj de_bfgs.hip $OBJ/de_bfgs.o &
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

@@ -1,7 +1,8 @@
 // de_api_grad.cpp — C ABI (include/de_hip.h): de_eval_grad / de_eval_diff / de_eval_pullback_dX, de_eval_loss_grad, de_eval_loss_grad_by_class: the
 // generic gradient program, the glue around the host encoders of its direct-threaded and reverse-accumulation forms (de_grad_encode.cpp)
 // with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels; de_gn_lm_step / de_fit_consts_lm /
-// de_lm_solve_host: Levenberg-Marquardt on the constants around de_eval_loss_gn's launch (kernels de_lm.hip).
+// de_lm_solve_host: Levenberg-Marquardt on the constants around de_eval_loss_gn's launch (kernels de_lm.hip);
+// de_fit_consts_bfgs and its host hooks: BFGS on the constants around de_eval_loss_grad_ex's launch (kernels de_bfgs.hip, §4.4.10).
 #include <functional>
 
 #include "de_api_internal.h"
@@ -13,6 +14,8 @@
 #include "de_lm_scaled.h"
 #include "de_lm_project.h"
 #include "de_lm_project_wide.h"
+#include "de_bfgs.h"
+#include "de_bfgs_dev.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -1976,6 +1979,164 @@ int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, in
                                  int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_lm_scaled_wide");
     DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
+}
+
+// ---- de_fit_consts_bfgs / de_bfgs_direction_host / de_bfgs_update_host (kernels: de_bfgs.hip, arithmetic: de_bfgs.h) ----
+int de_bfgs_max_rows(void) { return BFGS_MAX_ROWS; }
+
+int de_bfgs_direction_host(int G, double *B, uint8_t *fresh, double *alpha, const double *g, double step0, double *p, double *slope) {
+    const bool args = B && fresh && alpha && g && p && slope;
+    if (args && G >= 1 && G <= BFGS_MAX_ROWS) return bfgs_direction(G, B, fresh, alpha, g, step0, p, slope);
+    for (int k = 0; p && k < G; k++) p[k] = 0.0;
+    return 0;
+}
+int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const double *yv, double curv) {
+    if (!B || !fresh || !s || !yv) return 0;
+    return bfgs_update(G, B, fresh, s, yv, curv);
+}
+
+// fit_consts_lm_impl's structure with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip
+static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
+                                double *history, int32_t *n_accept) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    {
+        char why[160];
+        if (loss_spec_problem(spec_in, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_bfgs: DE_LOSS_PULLBACK is no objective");
+    }
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_bfgs: a program made by de_program_create_cse has one gradient row per occurrence of a "
+                                           "shared constant (the caller sums them); such callers keep the host loop");
+    for (int64_t t = 0; t < p->n_trees; t++)
+        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
+            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_bfgs: tree %lld has %lld constant rows for %lld constants", (long long)t,
+                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
+    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: reserved must be 0");
+    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: iters < 0");
+    for (const double v : {o.step0, o.c1, o.curv})
+        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: step0, c1 and curv must be finite and positive");
+    if (!(o.shrink > 0.0 && o.shrink < 1.0)) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: shrink must lie in (0, 1)");
+    if (N < 0 || (p->n_trees > 0 && (!ok || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
+    int rc = check_param_args(c, p, pa, N);
+    if (rc != DE_OK) return rc;
+    if (p->n_trees == 0) return DE_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
+    std::vector<int32_t> ng(nt);
+    std::vector<int64_t> boff(nt); // B: G^2 doubles of every tree that is fitted, none of the others
+    int64_t bspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        ng[t] = (int32_t)p->n_consts_tree[t];
+        boff[t] = bspan;
+        if (ng[t] >= 1 && ng[t] <= BFGS_MAX_ROWS) bspan += (int64_t)ng[t] * ng[t];
+    }
+    LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's
+    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, boff.data(), &tab);
+    if (rc != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
+    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
+    Staged sX, sY, sW, sPar, sCls;
+    de_param_args_t pad;
+    const de_param_args_t *pa_use = pa;
+    if (N > 0) {
+        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
+        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
+        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
+        if (p->uses_params) {
+            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
+            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
+            pad = *pa;
+            pad.params = sPar.dev;
+            pad.classes = sCls.dev;
+            pa_use = &pad;
+        }
+        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
+    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
+    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok);
+    const size_t rows = (size_t)o.iters + 1;
+    size_t at = 0;
+    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_la = lm_place(&at, nt * es), o_lt = lm_place(&at, nt * es),
+                 o_da = lm_place(&at, span * es), o_dt = lm_place(&at, span * es), o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt),
+                 o_B = lm_place(&at, (size_t)bspan * 8), o_al = lm_place(&at, nt * 8), o_sl = lm_place(&at, nt * 8), o_p = lm_place(&at, span * 8),
+                 o_fr = lm_place(&at, nt), o_pr = lm_place(&at, nt), o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0,
+                 o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
+    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
+    HIP_TRY(c, c->sLm.reserve(at));
+    char *base = static_cast<char *>(c->sLm.p);
+    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
+    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
+    BfgsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.coff = tab.doff;
+    a.boff = tab.joff;
+    a.consts_acc = base + o_ca; a.loss_acc = base + o_la; a.dloss_acc = base + o_da; a.ok_acc = reinterpret_cast<uint8_t *>(base + o_oka);
+    void *lT = base + o_lt, *dT = base + o_dt;
+    uint8_t *okT = reinterpret_cast<uint8_t *>(base + o_okt);
+    a.consts_trial = base + o_ct; a.loss_trial = lT; a.dloss_trial = dT; a.ok_trial = okT;
+    a.B = reinterpret_cast<double *>(base + o_B); a.alpha = reinterpret_cast<double *>(base + o_al);
+    a.slope = reinterpret_cast<double *>(base + o_sl); a.p = reinterpret_cast<double *>(base + o_p);
+    a.fresh = reinterpret_cast<uint8_t *>(base + o_fr); a.produced = reinterpret_cast<uint8_t *>(base + o_pr);
+    a.step0 = o.step0; a.shrink = o.shrink; a.c1 = o.c1; a.curv = o.curv;
+    a.n_accept = acc;
+
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
+        de_ctx *c;
+        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
+        ~Nest() { c->nested--; }
+    };
+    const de_loss_spec_t spec = *spec_in;
+    {
+        Nest nest(c);
+        auto evaluate = [&](void *l, void *d, uint8_t *k) {
+            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, l, d, nullptr, k, nullptr);
+        };
+        rc = evaluate(a.loss_acc, a.dloss_acc, a.ok_acc);
+        if (rc != DE_OK) return rc;
+        HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream));
+        HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist, c->stream));
+        const bool loop = N > 0 && o.iters > 0 && nc > 0;
+        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
+            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist + r * nt, c->stream));
+        if (loop) {
+            rc = de_program_get_consts(p, a.consts_acc); // (device to device behind a device set)
+            if (rc != DE_OK) return rc;
+            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
+                HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream));
+                rc = set_consts_device_impl(p, a.consts_trial);
+                if (rc == DE_OK) rc = evaluate(lT, dT, okT);
+                if (rc != DE_OK) break;
+                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
+                HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
+            }
+            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
+            const int rc2 = set_consts_device_impl(p, a.consts_acc);
+            if (rc != DE_OK) return rc;
+            if (rc2 != DE_OK) return rc2;
+        }
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, a.loss_acc, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ok, a.ok_acc, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                       const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                       int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_bfgs");
+    DE_NOTHROW(c, fit_consts_bfgs_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_accept));
 }
 
 } // extern "C"

@@ -1064,6 +1064,54 @@ function fit_population_constants_lm!(
     return constants, lossv, ok .!= 0x00, history, n_accept
 end
 
+struct BfgsOpts             # de_bfgs_opts_t
+    iters::Int32
+    reserved::Int32
+    step0::Float64
+    shrink::Float64
+    c1::Float64
+    curv::Float64
+end
+
+"""
+    fit_population_constants_bfgs!(pop, X, y; weights=nothing, iters=20, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0)
+        -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
+
+BFGS on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_bfgs`, DESIGN.md §4.4.10) — the reference's
+`optimize(f, g!, tree, BFGS())` with a backtracking line search, from the loss and its gradient alone: every kind of
+`eval_population_loss_grad` except `:pullback` is an objective (`:l1_hinge` included), and every tree of up to `de_bfgs_max_rows()` = 32
+constants is fitted.  It starts from the constants `pop` holds; per iteration the direction `-B g`, the trial constants, the evaluation
+there, the Armijo accept rule and the update of `B` run on the device.  Afterwards `pop` holds the accepted constants, which are returned
+with their losses and flags; `history[:, r]` are the accepted losses after `r - 1` iterations.  Trees that are incomplete at the start,
+have no constants or more than 32 keep their constants.  A population with a shared GraphNode constant is refused.
+"""
+function fit_population_constants_bfgs!(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+    iters::Integer=20, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8, loss::Symbol=:L2, loss_param::Real=0.0,
+) where {T}
+    loss === :pullback && throw(ArgumentError("fit_population_constants_bfgs!: :pullback is the cotangent of a pullback, not an objective"))
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_bfgs!: shared GraphNode constants need the host loop"))
+    opts = Ref(BfgsOpts(Int32(iters), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
+    spec = loss_spec(loss, loss_param)
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_accept = zeros(Int32, pop.n_trees)
+    with_pop(pop) do hc, hp
+        wp = weights === nothing ? C_NULL : pointer(weights)
+        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+            (:de_fit_consts_bfgs, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
+             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+    end
+    constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+    return constants, lossv, ok .!= 0x00, history, n_accept
+end
+
 """
     eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(:both))
         -> (loss, dloss::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)

@@ -91,7 +91,10 @@ extern "C" {
  *      (l) de_fit_stats_lm_step, de_fit_consts_lm_scaled and the host-only hook de_lm_project_host: the Levenberg-Marquardt step and the
  *      whole fit under linear scaling on the device, from what de_eval_fit_stats_grad returns; DE_F32 / DE_F64.
  *      (m) de_eval_fit_stats_grad_wide, de_fit_stats_lm_step_wide, de_fit_consts_lm_scaled_wide and the host-only hook
- *      de_lm_project_host_wide: the same for trees of 9 to 32 gradient rows; every entry point above keeps its bits. */
+ *      de_lm_project_host_wide: the same for trees of 9 to 32 gradient rows; every entry point above keeps its bits.
+ *      (n) de_bfgs_max_rows, de_fit_consts_bfgs (with de_bfgs_opts_t) and the host-only hooks de_bfgs_direction_host and
+ *      de_bfgs_update_host: BFGS on the constants of a population on the device, from the loss and its gradient alone (DESIGN.md
+ *      §4.4.10), under every loss kind that has a gradient, for trees of up to 32 constants; DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -791,6 +794,56 @@ int de_fit_stats_lm_step_wide(de_ctx_t *ctx, int dtype, int64_t n_trees, const i
 int de_fit_consts_lm_scaled_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                                  const void *y, const void *w, const de_lm_opts_t *opts,
                                  double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_accept);
+
+/* BFGS on the constants of a population, on the device — the optimiser the reference tests, optimize(f, g!, tree,
+ * BFGS()) of test/test_optim.jl:25,56,104, with de_eval_loss_grad_ex as f and g!.  It needs the loss and its gradient only: no
+ * Gauss-Newton matrix, so every kind of de_loss_kind_t that has a gradient is served (DE_LOSS_L1_HINGE included), and every tree of up to
+ * de_bfgs_max_rows() = 32 constants through one path.  Per tree, in double, every sum over k ascending, no atomics; B is the tree's
+ * approximation of the inverse Hessian (G x G, row-major, exactly symmetric), has = ok && 1 <= G <= 32:
+ *   direction  p = -B g, slope = g . p.  !(slope < 0), NaN included: the state is reset — B = I, fresh = 1, p = -g, slope = -g . g and
+ *              alpha = a0(g) = |g| > step0 ? step0 / |g| : 1 (the first trial step is no longer than step0).  produced = 0 and p = 0 where
+ *              an entry of g or of B (before a reset) is not finite or the slope is still not < 0 (g = 0).
+ *   trial      T(double(c_i) + alpha p_i); the bits of c_i where !has or nothing was produced
+ *   accept     has && produced && ok_trial && finite(f_trial) && f_trial < f && double(f_trial) <= double(f) + (c1 alpha) slope (Armijo)
+ *              accepted: s = double(c_trial) - double(c) (the rounded step actually taken), yv = double(g_trial) - double(g), the update
+ *              below, the tree takes the trial constants, loss, gradient and flag, alpha = fresh ? a0(g_trial) : 1, n_accept += 1
+ *              rejected: alpha *= shrink, B unchanged
+ *   update     sy = s . yv, ss = s . s, yy = yv . yv; only where all three are finite and sy > curv sqrt(ss) sqrt(yy).  From a fresh
+ *              state B = (sy / yy) I and fresh = 0 first.  Then u = B yv, yBy = yv . u and
+ *              B_ik = B_ik + (((sy + yBy) / (sy sy)) (s_i s_k) - (u_i s_k + s_i u_k) / sy)
+ *
+ * de_bfgs_direction_host / de_bfgs_update_host: the direction and the update of ONE tree on the host (no HIP call; csrc/de_bfgs.h, the
+ * source the kernels run: the same bits).  B: G x G doubles, row-major; fresh, alpha: one entry each, read and (on a reset / an update)
+ * written; p: G doubles out, slope: one out.  They return `produced` / `updated`.  G outside 1 .. 32 or a null pointer: 0, the state
+ * untouched, the G entries of p zero.
+ *
+ * de_fit_consts_bfgs: the whole loop in one call.  It starts from the constants the program holds, evaluates de_eval_loss_grad_ex (mode
+ * DE_GRAD_CONSTANT, `spec`), then `iters` times: direction, the trial constants set on the device, the evaluation there, accept.
+ * Afterwards the program holds the accepted constants and de_eval_loss_grad_ex with the same spec reproduces loss[t] bit for bit.  No
+ * constant, gradient or matrix reaches the host; host inputs are staged once; with device pointers the call synchronises only where
+ * de_eval_loss_grad_ex does.  X .. w: as de_eval_loss_grad_ex; loss (may be NULL), ok: n_trees entries; history (may be NULL): (iters + 1)
+ * x n_trees doubles, row r the accepted losses after r iterations; n_accept (may be NULL): accepted steps per tree; host or device
+ * pointers.  opts == NULL: {20, 0, 1.0, 0.5, 1e-4, 1e-8}.  A tree with ok == 0, no constants or more than 32 keeps its constants, its
+ * loss is de_eval_loss_grad_ex's.  iters == 0, N == 0 or no constants: nothing is accepted, every history row is the first.
+ * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED as de_fit_consts_lm (DE_F16 / complex /
+ * de_program_create_cse programs, constant rows that differ from the constants); DE_ERR_INVALID_ARG for a spec de_loss_spec_check(spec, 1)
+ * refuses, DE_LOSS_PULLBACK (no objective), null y or ok on a non-empty population, iters < 0, reserved != 0, step0 / c1 / curv not
+ * finite and positive, shrink outside (0, 1).
+ * Not served: programs made by de_program_create_cse, more than 32 constants, the scaled objective, parameter rows. */
+typedef struct de_bfgs_opts {
+    int32_t iters;    /* iterations: one direction, one evaluation and one accept each */
+    int32_t reserved; /* 0 */
+    double step0;     /* the longest first trial step after a reset */
+    double shrink;    /* alpha *= shrink on a rejected trial, in (0, 1) */
+    double c1;        /* the Armijo constant */
+    double curv;      /* the update needs s . yv > curv |s| |yv| */
+} de_bfgs_opts_t;
+int de_bfgs_max_rows(void);
+int de_bfgs_direction_host(int G, double *B, uint8_t *fresh, double *alpha, const double *g, double step0, double *p, double *slope);
+int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const double *yv, double curv);
+int de_fit_consts_bfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                       const void *y, const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
+                       double *history, int32_t *n_accept);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
