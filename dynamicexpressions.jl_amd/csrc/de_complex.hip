@@ -155,6 +155,7 @@ template <typename T> struct ComplexPolicy {
     static __device__ __forceinline__ V exp(const V &x) { return c_cold<T>(DE_U_EXP, x, x); }
     static __device__ __forceinline__ V sin(const V &x) { return c_cold<T>(DE_U_SIN, x, x); }
     static __device__ __forceinline__ V cold(uint32_t op, const V &x, const V &y) { return c_cold<T>(op, x, y); }
+    static __device__ __forceinline__ V cold_inj(uint32_t op, const V &x, const V &y) { return cold(op, x, y); }
     static __device__ __forceinline__ V cold3(uint32_t, V x, const V &y, const V &z) { // +(x, y, z) = (x + y) + z: DE_T_ADD3, the lowering admits no other
 #pragma unroll
         for (int i = 0; i < VW; i++) {

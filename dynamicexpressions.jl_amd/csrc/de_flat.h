@@ -156,8 +156,9 @@ __global__ void __launch_bounds__(FLAT_BLK) de_eval_flat_kernel(const FlatArgs<t
             case BOP_TERN: acc = P::cold3(w.y >> 24, ROW(w.y & 0xFFFFFFu), ROW(w.z), acc); break; // op3(slot, slot, acc)
             // is_valid(x_l) ? op(x_l) : Inf   (src/Evaluate.jl:722,787): the fused kernels, early_exit = false — x_l is the operand (the
             // accumulator or a row); a binary operator combines the accumulator with it, as the generic cases do
-            case BOP_INJ_ACC: { const V x = acc; acc = P::inject(x, P::cold(w.y >> 24, acc, x)); } break;
-            case BOP_INJ_ROW: { const uint32_t op = w.y >> 24; const V x = ROW(w.y & 0xFFFFFFu); acc = P::inject(x, GEN(op, x)); } break;
+            // (P::cold_inj: cold, but cos / sin of a real Float32 program are the functions of BOP_UN — the bits of the threaded kernel's b_gen<INJ>)
+            case BOP_INJ_ACC: { const V x = acc; acc = P::inject(x, P::cold_inj(w.y >> 24, acc, x)); } break;
+            case BOP_INJ_ROW: { const uint32_t op = w.y >> 24; const V x = ROW(w.y & 0xFFFFFFu); acc = P::inject(x, P::cold_inj(op, op < 64u ? x : acc, x)); } break;
             case BOP_GEN_PARAM:
                 if constexpr (PARAMS) {
                     const uint32_t op = w.y >> 24;

@@ -87,6 +87,13 @@ template <typename T> struct RealPolicy {
         return out[0];
     }
     static __device__ __forceinline__ V cold(uint32_t op, V x, V y) { return cold_op<T, 1>(op, VG<T, 1>{{x}}, VG<T, 1>{{y}}).v[0]; } // (a unary operator maps y = x)
+    static __device__ __forceinline__ V cold_inj(uint32_t op, V x, V y) { // the operator of a fused deg1 kernel (BOP_INJ_*): cos / sin as BOP_UN computes them
+        if constexpr (sizeof(T) == 4) {
+            if (op == (uint32_t)DE_U_COS) return cos(y);
+            if (op == (uint32_t)DE_U_SIN) return sin(y);
+        }
+        return cold(op, x, y);
+    }
     static __device__ __forceinline__ V cold3(uint32_t op, V x, V y, V z) { return cold_op3<T, 1>(op, VG<T, 1>{{z}}, VG<T, 1>{{x}}, VG<T, 1>{{y}}).v[0]; }
 
     template <bool CERT> static __device__ __forceinline__ void test(T &poison, T &vmax, V v) {

@@ -119,6 +119,7 @@ struct HalfPolicy {
     static __device__ __forceinline__ V exp(V x) { return h_round(V{h_exp(x[0]), h_exp(x[1]), h_exp(x[2]), h_exp(x[3])}); }
     static __device__ __forceinline__ V sin(V x) { return h_round(V{h_sin(x[0]), h_sin(x[1]), h_sin(x[2]), h_sin(x[3])}); }
     static __device__ __forceinline__ V cold(uint32_t op, V x, V y) { return h16_cold(op, x, y); }
+    static __device__ __forceinline__ V cold_inj(uint32_t op, V x, V y) { return cold(op, x, y); }
     static __device__ __forceinline__ V cold3(uint32_t op, V x, V y, V z) { return h16_cold3(op, x, y, z); }
 
     template <bool CERT> static __device__ __forceinline__ void test(float &poison, float &vmax, V v) {

@@ -1147,8 +1147,17 @@ template <typename T, int SRC, bool INJ> __device__ __forceinline__ BState<T> b_
     else if constexpr (SRC == 1) { const T c = imm_from<T>(imm); DE_UNROLL for (int i = 0; i < VecOf<T>::W; i++) b.v[0][i] = c; }
     else b.v[0] = st.acc;
     const V in = b.v[0];
-    a = cold_op<T, 1>(aux, a, b);
-    st.acc = a.v[0];
+    // cos / sin of a fused deg1 kernel (early_exit = false): the function of the hot handlers, not cold_op's library call, so that
+    // cos(x1 + x2) carries the bits of cos(x1) (both are within 2 ulp; tests/test_gpu_operator_accuracy.py measures the leaf form)
+    bool hot = false;
+    if constexpr (INJ && sizeof(T) == 4) {
+        if (aux == (uint32_t)DE_U_COS) { st.acc = un_apply<T, 0>(in); hot = true; }
+        else if (aux == (uint32_t)DE_U_SIN) { st.acc = un_apply<T, 2>(in); hot = true; }
+    }
+    if (!hot) {
+        a = cold_op<T, 1>(aux, a, b);
+        st.acc = a.v[0];
+    }
     if constexpr (INJ) { DE_UNROLL for (int i = 0; i < VecOf<T>::W; i++) st.acc[i] = M<T>::isfinite(in[i]) ? st.acc[i] : M<T>::inf(); }
     return st;
 }

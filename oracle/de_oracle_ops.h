@@ -61,7 +61,8 @@ static inline OT ON(o_jlmod)(OT x, OT y) {
 }
 static inline OT ON(o_sign)(OT x) { return x > 0 ? (OT)1 : (x < 0 ? (OT)-1 : x); }
 
-/* digamma for the gamma derivative (SpecialFunctions.digamma; unpinned). */
+/* digamma for the gamma derivative (SpecialFunctions.digamma): bounded pointwise against
+ * mpmath's, tests/operator_accuracy.py digamma_error. */
 static inline OW ON(o_digamma)(OW x) {
     OW r = 0;
     if (x <= 0) {
