@@ -59,6 +59,8 @@ EXPORTS = [
     "de_lm_project_host", "de_fit_stats_lm_step", "de_fit_consts_lm_scaled",
     "de_eval_fit_stats_grad_wide", "de_lm_project_host_wide", "de_fit_stats_lm_step_wide", "de_fit_consts_lm_scaled_wide",
     "de_bfgs_max_rows", "de_bfgs_direction_host", "de_bfgs_update_host", "de_fit_consts_bfgs",
+    "de_tape_params_to_consts", "de_eval_tree_params", "de_eval_loss_tree_params", "de_eval_loss_grad_tree_params",
+    "de_tree_params_accumulate_host",
 ]
 
 
@@ -85,6 +87,12 @@ class LmOpts(C.Structure):
     """``de_lm_opts_t``: what ``de_fit_consts_lm`` takes besides the data (null: 10 iterations, lam0 1e-3, up 10, down 0.1, floor 1e-12)."""
     _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("lam0", C.c_double), ("up", C.c_double), ("down", C.c_double),
                 ("lam_min", C.c_double)]
+
+
+class TreeParams(C.Structure):
+    """``de_tree_params_t``: the per-tree parameter matrices of one ``de_eval*_tree_params`` call."""
+    _fields_ = [("params", C.c_void_p), ("ld_params", C.c_int64), ("n_classes", C.c_int64), ("n_params", C.c_int32),
+                ("reserved", C.c_int32), ("class_starts", C.c_void_p), ("slot_param", C.c_void_p)]
 
 
 class BfgsOpts(C.Structure):
@@ -668,6 +676,13 @@ def library() -> C.CDLL:
         lib.de_bfgs_update_host.argtypes = [C.c_int, vp, vp, vp, vp, C.c_double]
         lib.de_fit_consts_bfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
                                            vp, vp, vp, vp]
+    if hasattr(lib, "de_eval_tree_params"):  # (absent from a library built before the per-tree parameter entry points: DE_HIP_LIB in an A/B run)
+        lib.de_tape_params_to_consts.restype = i64
+        lib.de_tape_params_to_consts.argtypes = [vp, i64, i32, vp, vp, i64]
+        lib.de_eval_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, i64, vp]
+        lib.de_eval_loss_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp]
+        lib.de_eval_loss_grad_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp]
+        lib.de_tree_params_accumulate_host.argtypes = [C.c_int, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -2334,3 +2349,418 @@ class ParametricExpression:
         from .node import get_scalar_constants
         cs, refs = get_scalar_constants(self.tree)
         return np.concatenate([cs, self.parameters.reshape(-1, order="F")]), refs
+
+
+# ---- per-tree parameter matrices (include/de_hip.h de_eval*_tree_params) ---------------------------------------
+def tape_params_to_consts(tape, n_params: int):
+    """``de_tape_params_to_consts`` (host only, no GPU needed): ``(tape', slot_param)`` — every constant and every parameter leaf of the
+    post-order ``tape`` as a constant leaf whose slot is its ordinal among those leaves, ``slot_param[s]`` = -1 for a real constant, else
+    the 0-based parameter row.  A parameter row >= ``n_params`` is a ``ValueError`` (DE_ERR_OUT_OF_RANGE), a CSE node a ``DeviceError``
+    (DE_ERR_UNSUPPORTED)."""
+    tape = np.ascontiguousarray(tape, dtype=TAPE_DTYPE)
+    out = np.empty_like(tape)
+    sp = np.empty(max(len(tape), 1), dtype=np.int32)
+    n = int(library().de_tape_params_to_consts(tape.ctypes.data, len(tape), int(n_params), out.ctypes.data, sp.ctypes.data, len(sp)))
+    if n < 0:
+        name = library().de_status_string(-n).decode()
+        if -n == 6:
+            raise ValueError(f"{name}: the tape uses a parameter row >= n_params = {n_params} (DE_ERR_OUT_OF_RANGE)")
+        if -n == 7:
+            raise DeviceError(f"{name}: shared subtrees (CSE tapes) have no per-tree parameter form (DE_ERR_UNSUPPORTED)")
+        raise ValueError(f"{name}: de_tape_params_to_consts")
+    return out, sp[:n].copy()
+
+
+def tree_params_accumulate_host(slot_param, n_params: int, class_used, loss_c, dloss_c, ok_c, dtype=np.float64):
+    """``de_tree_params_accumulate_host``: the accumulate-and-finish arithmetic of one ``de_eval_loss_grad_tree_params`` call for ONE tree on
+    the host (csrc/de_tree_params.h, the code the kernels run).  ``loss_c[c]``, ``dloss_c[c, s]``, ``ok_c[c]``: one model result per class;
+    ``class_used[c]`` false: the class is skipped.  Returns (loss, dloss[n_slots], dparams[n_classes, n_params], ok)."""
+    dtype = np.dtype(dtype)
+    sp = np.ascontiguousarray(slot_param, dtype=np.int32)
+    used = np.ascontiguousarray(class_used, dtype=np.uint8)
+    lc = np.ascontiguousarray(loss_c, dtype=dtype)
+    dc = np.ascontiguousarray(dloss_c, dtype=dtype).reshape(len(used), len(sp))
+    okc = np.ascontiguousarray(ok_c, dtype=np.uint8)
+    lo, dl, dp = np.zeros(1, dtype=dtype), np.zeros(max(len(sp), 1), dtype=dtype), np.zeros((len(used), int(n_params)), dtype=dtype)
+    ok = np.zeros(1, dtype=np.uint8)
+    rc = library().de_tree_params_accumulate_host(_dtype_code(dtype), len(sp), sp.ctypes.data, int(n_params), len(used), used.ctypes.data,
+                                                  lc.ctypes.data, dc.ctypes.data, okc.ctypes.data, lo.ctypes.data, dl.ctypes.data,
+                                                  dp.ctypes.data if dp.size else None, ok.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"{library().de_status_string(rc).decode()}: de_tree_params_accumulate_host")
+    return lo[0], dl[:len(sp)], dp, bool(ok[0])
+
+
+def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
+                         curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
+    """The host loop of ``Population.fit_constants_bfgs`` over each tree's combined vector ``vcat(constants, params[t].T.reshape(-1))`` —
+    the reference's order (src/ParametricExpression.jl:258-278) — through ``bfgs_direction_host`` / ``bfgs_update_host``.
+    ``evaluate(consts_list, params[n_trees, n_params, n_classes]) -> (loss[n_trees], dconsts_list, dparams[n_trees, n_params, n_classes],
+    ok[n_trees])`` serves all trees at once (``ParametricPopulation.eval_loss_grad``, or any stand-in: the loop itself needs no GPU).
+    Trees with more than ``BFGS_MAX_ROWS`` unknowns, without unknowns or incomplete at the start keep their values.  Returns (consts_list,
+    params, loss, ok, accepts); ``history`` (a list) receives the accepted losses (float64) after every evaluation."""
+    dtype, f64 = np.dtype(dtype), np.float64
+    params = np.array(_host(params0), dtype=dtype).copy()
+    if params.ndim != 3:
+        raise ValueError("params0 must be [n_trees, n_params, n_classes]")
+    nt = params.shape[0]
+    consts = [np.array(_host(c), dtype=dtype).reshape(-1).copy() for c in consts0]
+    if len(consts) != nt:
+        raise ValueError("consts0 must hold one array per tree")
+
+    def pack(cs, ps):  # vcat(constants, parameters[:])
+        return [np.concatenate([cs[t], ps[t].T.reshape(-1)]) for t in range(nt)]
+
+    def unpack(vs):
+        cs = [v[:len(consts[t])].copy() for t, v in enumerate(vs)]
+        ps = np.stack([v[len(consts[t]):].reshape(params.shape[2], params.shape[1]).T for t, v in enumerate(vs)]) if nt else params.copy()
+        return cs, np.ascontiguousarray(ps, dtype=dtype)
+
+    def run(vs):
+        cs, ps = unpack(vs)
+        lo, dc, dp, ok = evaluate(cs, ps)
+        lo, dp, ok = _host(lo).copy(), _host(dp), _host(ok).astype(bool).copy()
+        gr = [np.concatenate([_host(dc[t]).astype(f64).reshape(-1), dp[t].astype(f64).T.reshape(-1)]) for t in range(nt)]
+        return lo, gr, ok
+
+    x = pack(consts, params)
+    fitted = [1 <= len(v) <= BFGS_MAX_ROWS for v in x]
+    lo, gr, ok = run(x)
+    B = [np.eye(len(v)) for v in x]
+    fresh, alpha = [True] * nt, [_bfgs_a0(gr[t], step0) if fitted[t] else 1.0 for t in range(nt)]
+    acc = np.zeros(nt, dtype=np.int32)
+    if history is not None:
+        history.append(lo.astype(f64))
+    for _ in range(int(iters)):
+        trial, produced, slope = [v.copy() for v in x], [False] * nt, [0.0] * nt
+        for t in range(nt):
+            if fitted[t] and ok[t]:
+                p, slope[t], produced[t], B[t], fresh[t], alpha[t] = bfgs_direction_host(B[t], fresh[t], alpha[t], gr[t], step0)
+                if produced[t]:
+                    trial[t] = (x[t].astype(f64) + alpha[t] * p).astype(dtype)
+        lo_t, gr_t, ok_t = run(trial)
+        for t in range(nt):
+            f, ft = float(lo[t]), float(lo_t[t])
+            if (fitted[t] and ok[t] and produced[t] and ok_t[t] and math.isfinite(ft) and ft < f
+                    and ft <= f + (c1 * alpha[t]) * slope[t]):
+                _, B[t], fresh[t] = bfgs_update_host(B[t], fresh[t], trial[t].astype(f64) - x[t].astype(f64), gr_t[t] - gr[t], curv)
+                x[t] = trial[t]
+                lo[t], gr[t], ok[t] = lo_t[t], gr_t[t], ok_t[t]
+                alpha[t] = _bfgs_a0(gr[t], step0) if fresh[t] else 1.0
+                acc[t] += 1
+            else:
+                alpha[t] = alpha[t] * shrink
+        if history is not None:
+            history.append(lo.astype(f64))
+    cs, ps = unpack(x)
+    return cs, ps, lo, ok, acc
+
+
+class ParametricPopulation:
+    """A population whose members each own their parameter matrix — what a search over ``ParametricExpression`` s holds (DESIGN.md
+    §4.4.11).  ``expressions_or_trees``: ``ParametricExpression`` s (their ``parameters`` are the default ``params``) or ``ParametricNode``
+    trees.  Every tree is rewritten by ``de_tape_params_to_consts`` into an ordinary tree in which some constant slots stand for parameters
+    (``slot_param``); the population is an ordinary ``Population`` of those (``self.pop``), evaluated one class segment at a time by
+    ``de_eval_tree_params`` / ``de_eval_loss_tree_params`` / ``de_eval_loss_grad_tree_params``.  ``params`` is ``[n_trees, n_params,
+    n_classes]`` everywhere (numpy, or a torch device tensor)."""
+
+    def __init__(self, expressions_or_trees, operators: OperatorEnum, dtype=np.float32, n_features: Optional[int] = None,
+                 n_params: int = 0, eval_context: Optional[EvalContext] = None, ctx: Optional[Context] = None):
+        self.dtype, self.operators, self.n_params = np.dtype(dtype), operators, int(n_params)
+        self.params = None
+        items = list(expressions_or_trees)
+        if items and all(isinstance(e, ParametricExpression) for e in items):
+            for e in items:
+                if e.parameters.ndim != 2 or e.parameters.shape[0] != self.n_params:
+                    raise ValueError(f"a ParametricExpression has parameters of shape {e.parameters.shape}; n_params = {self.n_params}")
+            if len({e.parameters.shape[1] for e in items}) != 1:
+                raise ValueError("the ParametricExpressions differ in their number of classes")
+            self.params = np.stack([np.asarray(e.parameters, dtype=self.dtype) for e in items])
+            items = [e.tree for e in items]
+        plain, slot_param = self._rewrite(items)
+        self.slot_param = slot_param  # per tree: int32[n_slots]
+        self.pop = Population(plain, operators, self.dtype, n_features=n_features, n_params=0, eval_context=eval_context, ctx=ctx)
+        self.ctx, self.n_trees, self.n_features = self.pop.ctx, self.pop.n_trees, self.pop.n_features
+        self._index()
+
+    def _rewrite(self, trees):
+        """Host only: the trees with every parameter leaf as a constant leaf (value 0), and their ``slot_param``."""
+        from .node import flatten
+        plain, slot_param = [], []
+        for tree in trees:
+            if preserve_sharing(tree):
+                raise DeviceError(f"{library().de_status_string(7).decode()}: GraphNode trees have no per-tree parameter form (DE_ERR_UNSUPPORTED)")
+            tape, _ = flatten(tree, self.operators, self.dtype)
+            tape2, sp = tape_params_to_consts(tape, self.n_params)
+            q = tree.copy()
+            for n in q:
+                if n.degree == 0 and getattr(n, "is_parameter", False):
+                    n.is_parameter, n.parameter, n.constant, n.val = False, 0, True, 0.0
+            if not np.array_equal(flatten(q, self.operators, self.dtype)[0], tape2):
+                raise RuntimeError("de_tape_params_to_consts and the rewritten tree disagree")
+            plain.append(q)
+            slot_param.append(sp)
+        return plain, slot_param
+
+    def _index(self):
+        sp = np.concatenate(self.slot_param) if self.slot_param else np.zeros(0, dtype=np.int32)
+        self._slot_param_all = np.ascontiguousarray(sp, dtype=np.int32)
+        self._real = np.nonzero(self._slot_param_all < 0)[0]
+        self._slot_off = np.zeros(self.n_trees + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in self.slot_param], out=self._slot_off[1:])
+        self.n_consts = np.array([int(np.sum(s < 0)) for s in self.slot_param], dtype=np.int64)  # real constants per tree
+
+    def update(self, indices, trees) -> None:
+        """Replace members ``indices[i]`` by ``trees[i]`` (``ParametricExpression`` s or trees) in place (``Population.update``)."""
+        trees = list(trees)
+        ids = check_update_ids(indices, len(trees), self.n_trees)
+        exprs = [e for e in trees if isinstance(e, ParametricExpression)]
+        for e in exprs:
+            if e.parameters.shape[0] != self.n_params:
+                raise ValueError(f"a ParametricExpression has parameters of shape {e.parameters.shape}; n_params = {self.n_params}")
+        plain, sps = self._rewrite([e.tree if isinstance(e, ParametricExpression) else e for e in trees])
+        self.pop.update(ids, plain)
+        for i, t in enumerate(ids):
+            self.slot_param[t] = sps[i]
+            if self.params is not None and isinstance(trees[i], ParametricExpression):
+                self.params[t] = np.asarray(trees[i].parameters, dtype=self.dtype)
+        self._index()
+
+    # -- the real constants -----------------------------------------------------------
+    def set_constants(self, consts) -> None:
+        """New values for the REAL constants (``get_scalar_constants`` order, tree after tree); parameter slots keep no value."""
+        consts = np.ascontiguousarray(_host(consts), dtype=self.dtype).reshape(-1)
+        if consts.size != len(self._real):
+            raise ValueError("wrong number of constants")
+        full = np.zeros(len(self._slot_param_all), dtype=self.dtype)
+        full[self._real] = consts
+        self.pop.set_constants(full)
+
+    def constants(self) -> np.ndarray:
+        """The current real constants (numpy)."""
+        return self.pop.constants()[self._real]
+
+    # -- argument checks (host only) ----------------------------------------------------
+    @staticmethod
+    def check_args(params, classes, n_trees: int, n_params: int, N: Optional[int] = None, class_base: int = 1):
+        """The checks of every entry point that need no device: ``params`` is ``[n_trees, n_params, n_classes]`` and every class id lies in
+        ``[class_base, class_base + n_classes)`` (``_param_args``' rule); ``ValueError`` otherwise.  Returns n_classes."""
+        shape = tuple(params.shape)
+        if len(shape) != 3:
+            raise ValueError(f"params must be [n_trees, n_params, n_classes]: got {len(shape)} dimension(s)")
+        if shape[0] != n_trees or shape[1] != n_params:
+            raise ValueError(f"params must be [n_trees = {n_trees}, n_params = {n_params}, n_classes]: got {list(shape)}")
+        ncls = int(shape[2])
+        if ncls <= 0:
+            raise ValueError("params needs at least one class")
+        n_c = int(classes.numel() if _is_torch(classes) else np.asarray(classes).size)
+        if N is not None and n_c != N:
+            raise ValueError(f"length(classes) == size(X, 2) violated: {n_c} class ids for {N} samples")
+        if n_c:
+            mn, mx = (int(classes.min().item()), int(classes.max().item())) if _is_torch(classes) else (int(np.min(classes)), int(np.max(classes)))
+            if mn < class_base or mx - class_base >= ncls:
+                raise ValueError(f"class ids must lie in [{class_base}, {class_base + ncls}): got [{mn}, {mx}] "
+                                 "(maximum(classes) <= size(parameters, 2))")
+        return ncls
+
+    def _prepare(self, X, params, classes, class_base, grouped, y=None, weights=None):
+        """Everything a call needs: the data ordered by class (a stable sort unless ``grouped``), the parameter block in the library's
+        layout and the filled ``TreeParams``.  Returns (ptr, N, ldX, y ptr, w ptr, TreeParams, order or None, is_torch, keepalives)."""
+        if params is None:
+            params = self.params
+        if params is None:
+            raise ValueError("params is required (the population was not built from ParametricExpressions)")
+        is_t = _is_torch(X)
+        N = int(X.shape[1]) if X.ndim == 2 else 1
+        ncls = self.check_args(params, classes, self.n_trees, self.n_params, N, class_base)
+        order = None
+        if is_t:
+            import torch
+            classes = torch.as_tensor(classes, device=X.device)
+            if not grouped:
+                order = torch.argsort(classes, stable=True)
+                X, classes = X[:, order], classes[order]
+                y = None if y is None else torch.as_tensor(y, device=X.device)[order]
+                weights = None if weights is None else torch.as_tensor(weights, device=X.device)[order]
+            counts = torch.bincount((classes - class_base).to(torch.int64), minlength=ncls).cpu().numpy()
+        else:
+            classes = np.asarray(classes)
+            if not grouped:
+                order = np.argsort(classes, kind="stable")
+                X, classes = np.asfortranarray(np.asarray(X)[:, order]), classes[order]
+                y = None if y is None else np.asarray(y)[order]
+                weights = None if weights is None else np.asarray(weights)[order]
+            elif classes.size and np.any(np.diff(classes) < 0):
+                raise ValueError("grouped=True: the class ids are not in ascending order")
+            counts = np.bincount((classes - class_base).astype(np.int64), minlength=ncls)
+        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
+        if is_t:
+            self.ctx.use_torch_stream()
+        if F < self.n_features:
+            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
+        keep = [keep_x]
+        starts = np.zeros(ncls + 1, dtype=np.int64)
+        np.cumsum(counts[:ncls], out=starts[1:])
+        # the parameter block: element (p, c, t) at p + ld * (c + n_classes * t); a [n_trees, n_classes, ld] block is used in place
+        P = self.n_params
+        tp = TreeParams()
+        if _is_torch(params):
+            blk = params.to(_torch_dtype(self.dtype)).transpose(1, 2)
+            ld = blk.stride(1)
+            if not (blk.is_cuda and blk.numel() > 0 and blk.stride(2) == 1 and ld >= max(P, 1) and blk.stride(0) == ncls * ld):
+                blk, ld = blk.contiguous().to(f"cuda:{self.ctx.device}"), max(P, 1)
+            tp.params = blk.data_ptr() if blk.numel() else None
+        else:
+            blk = np.asarray(params, dtype=self.dtype).transpose(0, 2, 1)
+            es = self.dtype.itemsize
+            ld = blk.strides[1] // es
+            if not (blk.size > 0 and blk.strides[2] == es and ld >= max(P, 1) and blk.strides[1] == ld * es and blk.strides[0] == ncls * ld * es):
+                blk, ld = np.ascontiguousarray(blk), max(P, 1)
+            tp.params = blk.ctypes.data if blk.size else None
+        keep += [blk, starts]
+        tp.ld_params, tp.n_classes, tp.n_params, tp.reserved = int(ld), ncls, P, 0
+        tp.class_starts = starts.ctypes.data
+        tp.slot_param = self._slot_param_all.ctypes.data if len(self._slot_param_all) else None
+
+        def vec(v, name):
+            if v is None:
+                return None
+            if is_t:
+                import torch
+                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                n, p_ = v.numel(), v.data_ptr()
+            else:
+                v = np.ascontiguousarray(v, dtype=self.dtype)
+                n, p_ = v.size, v.ctypes.data
+            if n != N:
+                raise ValueError(f"{name} must have {N} entries")
+            keep.append(v)
+            return p_
+
+        return ptr, N, ldX, vec(y, "y"), vec(weights, "weights"), tp, order, is_t, keep
+
+    # -- entry points -------------------------------------------------------------------
+    def eval(self, X, params=None, classes=None, class_base: int = 1, grouped: bool = False):
+        """``(out[n_trees, N], ok[n_trees])``: every member on every sample with its own parameters (``de_eval_tree_params``).  Columns
+        are in the order of ``X`` (ungrouped data is sorted by class for the call and un-permuted afterwards)."""
+        ptr, N, ldX, _, _, tp, order, is_t, keep = self._prepare(X, params, classes, class_base, grouped)
+        lib = library()
+        if is_t:
+            import torch
+            kx = keep[0]
+            out = torch.empty((self.n_trees, N), dtype=kx.dtype, device=kx.device)
+            ok = torch.empty(self.n_trees, dtype=torch.uint8, device=kx.device)
+            self.ctx.check(lib.de_eval_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), out.data_ptr(), N, ok.data_ptr()))
+            if order is not None:
+                res = torch.empty_like(out)
+                res[:, order] = out
+                out = res
+            return out, ok.bool()
+        out = np.empty((self.n_trees, N), dtype=self.dtype)
+        ok = np.zeros(self.n_trees, dtype=np.uint8)
+        self.ctx.check(lib.de_eval_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), out.ctypes.data, N, ok.ctypes.data))
+        if order is not None:
+            res = np.empty_like(out)
+            res[:, order] = out
+            out = res
+        return out, ok.astype(bool)
+
+    def eval_loss(self, X, y, params=None, classes=None, weights=None, loss: str = "L2", loss_param: float = 0.0, class_base: int = 1,
+                  grouped: bool = False):
+        """``(loss[n_trees], ok[n_trees])`` as ``Population.eval_loss``, every member with its own parameters
+        (``de_eval_loss_tree_params``)."""
+        self.pop._refuse_f16("eval_loss")
+        spec = loss_spec(loss, loss_param, with_gradient=False)
+        ptr, N, ldX, yp, wp, tp, _, is_t, keep = self._prepare(X, params, classes, class_base, grouped, y, weights)
+        lib = library()
+        if is_t:
+            import torch
+            kx = keep[0]
+            out = torch.empty(self.n_trees, dtype=kx.dtype, device=kx.device)
+            ok = torch.empty(self.n_trees, dtype=torch.uint8, device=kx.device)
+            self.ctx.check(lib.de_eval_loss_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                        out.data_ptr(), ok.data_ptr()))
+            return out, ok.bool()
+        out = np.empty(self.n_trees, dtype=self.dtype)
+        ok = np.zeros(self.n_trees, dtype=np.uint8)
+        self.ctx.check(lib.de_eval_loss_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                    out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def eval_loss_grad(self, X, y, params=None, classes=None, weights=None, loss: str = "L2", loss_param: float = 0.0,
+                       class_base: int = 1, grouped: bool = False, return_slots: bool = False):
+        """``(loss[n_trees], dconsts_list, dparams[n_trees, n_params, n_classes], ok)`` (``de_eval_loss_grad_tree_params``):
+        ``dconsts_list[t]`` covers the real constants of member t in ``get_scalar_constants`` order, ``dparams[t]`` is the gradient
+        w.r.t. its parameter matrix.  ``return_slots=True`` appends the library's ``dloss`` (every slot, parameter slots included)."""
+        self.pop._refuse_f16("eval_loss_grad")
+        spec = loss_spec(loss, loss_param)
+        ptr, N, ldX, yp, wp, tp, _, is_t, keep = self._prepare(X, params, classes, class_base, grouped, y, weights)
+        lib = library()
+        ncls, P, off = int(tp.n_classes), self.n_params, self._slot_off
+        total = max(int(off[-1]), 1)
+        if is_t:
+            import torch
+            kx = keep[0]
+            kw = dict(dtype=kx.dtype, device=kx.device)
+            lo, dl, dp = torch.empty(self.n_trees, **kw), torch.empty(total, **kw), torch.empty((self.n_trees, ncls, P), **kw)
+            ok = torch.empty(self.n_trees, dtype=torch.uint8, device=kx.device)
+            self.ctx.check(lib.de_eval_loss_grad_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                             lo.data_ptr(), dl.data_ptr(), off.ctypes.data, dp.data_ptr(), ok.data_ptr()))
+            dl = dl[:int(off[-1])]
+            real = torch.as_tensor(self._real, device=kx.device)
+            dc = list(torch.split(dl.index_select(0, real), self.n_consts.tolist()))
+            res = (lo, dc, dp.transpose(1, 2), ok.bool())
+            return res + (dl,) if return_slots else res
+        lo, dl = np.empty(self.n_trees, dtype=self.dtype), np.empty(total, dtype=self.dtype)
+        dp = np.empty((self.n_trees, ncls, P), dtype=self.dtype)
+        ok = np.zeros(self.n_trees, dtype=np.uint8)
+        self.ctx.check(lib.de_eval_loss_grad_tree_params(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                         lo.ctypes.data, dl.ctypes.data, off.ctypes.data, dp.ctypes.data, ok.ctypes.data))
+        dl = dl[:int(off[-1])]
+        dc = np.split(dl[self._real], np.cumsum(self.n_consts)[:-1]) if self.n_trees else []
+        res = (lo, dc, dp.transpose(0, 2, 1), ok.astype(bool))
+        return res + (dl,) if return_slots else res
+
+    def fit_bfgs(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, step0: float = 1.0,
+                 shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                 history: Optional[list] = None, class_base: int = 1, evaluate=None):
+        """BFGS over each member's ``vcat(constants, parameters[:])`` (``tree_params_fit_bfgs``: the host loop of
+        ``Population.fit_constants_bfgs``), one ``eval_loss_grad`` per iteration for all members.  ``consts0``: the real constants
+        (``set_constants``' layout; default: the current ones); ``params0``: ``[n_trees, n_params, n_classes]`` (default: the
+        expressions' parameters).  ``evaluate`` replaces the device evaluator (see ``tree_params_fit_bfgs``).  Returns (consts, params,
+        loss, ok); the population holds the fitted constants afterwards, ``self.params`` the fitted parameters and
+        ``self.bfgs_accepts`` the accepted steps per member."""
+        _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
+        params0 = self.params if params0 is None else params0
+        c0 = self.constants() if consts0 is None else np.ascontiguousarray(_host(consts0), dtype=self.dtype).reshape(-1)
+        if c0.size != len(self._real):
+            raise ValueError("wrong number of constants")
+        at = np.cumsum(self.n_consts)[:-1]
+        if evaluate is None:
+            # the data is ordered by class once for the whole fit
+            if _is_torch(X):
+                import torch
+                cls = torch.as_tensor(classes, device=X.device)
+                order = torch.argsort(cls, stable=True)
+                Xs, cs, ys = X[:, order], cls[order], torch.as_tensor(y, device=X.device)[order]
+                ws = None if weights is None else torch.as_tensor(weights, device=X.device)[order]
+            else:
+                cls = np.asarray(classes)
+                order = np.argsort(cls, kind="stable")
+                Xs, cs, ys = np.asfortranarray(np.asarray(X)[:, order]), cls[order], np.asarray(y)[order]
+                ws = None if weights is None else np.asarray(weights)[order]
+
+            def evaluate(consts_list, params):
+                self.set_constants(np.concatenate(consts_list) if consts_list else np.zeros(0, dtype=self.dtype))
+                return self.eval_loss_grad(Xs, ys, params, cs, weights=ws, loss=loss, loss_param=loss_param, class_base=class_base,
+                                           grouped=True)
+
+        cs_fit, ps, lo, ok, acc = tree_params_fit_bfgs(evaluate, np.split(c0, at) if self.n_trees else [], params0, iters, step0, shrink,
+                                                      c1, curv, self.dtype, history)
+        consts = np.concatenate(cs_fit) if cs_fit else np.zeros(0, dtype=self.dtype)
+        self.set_constants(consts)
+        self.params, self.bfgs_accepts = ps, acc
+        return consts, ps, lo, ok
+
+    def close(self) -> None:
+        self.pop.close()

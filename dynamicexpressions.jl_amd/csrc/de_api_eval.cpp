@@ -339,7 +339,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         a.compact_code = nullptr;
         a.compact_ints = nullptr;
     }
-    HIP_TRY(c, time_begin(c));
+    if (!c->nested) HIP_TRY(c, time_begin(c)); // (nested: one class segment of de_eval*_tree_params, which times the whole call)
     a.compacted = &p->last_compacted;
     p->last_compacted = false;
     if (half || cplx) { // the flat-switch interpreter only: no threaded kernel, priority tiles or compaction (de_api_internal.h de_program::io)
@@ -351,7 +351,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     if (half) HIP_TRY(c, launch_eval_f16(a, c->stream, &c->last_kernel));
     else if (cplx) HIP_TRY(c, launch_eval_complex(p->io, a, p->d_ctab, c->stream, &c->last_kernel)); // (+ the program's constant table)
     else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
-    HIP_TRY(c, time_end(c));
+    if (!c->nested) HIP_TRY(c, time_end(c));
     if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
     if (sStats.staged) HIP_TRY(c, hipMemcpyAsync(lr->stats, sStats.dev, (size_t)p->n_trees * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sYstats.staged) HIP_TRY(c, hipMemcpyAsync(lr->ystats, sYstats.dev, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));

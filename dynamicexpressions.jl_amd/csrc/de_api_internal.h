@@ -4,6 +4,7 @@
 //   de_api_eval.cpp     de_eval, de_eval_loss, de_eval_sum_certificate, de_eval_tree_array (staging, launch planning)
 //   de_api_grad.cpp     de_eval_grad / _diff / _pullback_dX, de_eval_loss_grad(_by_class): the generic gradient program; glue around the
 //                       host-only encoders of the threaded and reverse streams (de_grad_encode.cpp), de_lower_tape_grad
+//   de_api_tree_params.cpp  de_tape_params_to_consts, de_eval*_tree_params: per-tree parameter matrices, class by class around the calls above
 // No behaviour changed in the split: de_program_stream_hash and the whole test suite are the check.
 #ifndef DE_API_INTERNAL_H
 #define DE_API_INTERNAL_H
@@ -92,6 +93,9 @@ struct de_ctx {
     // de_eval_loss_gn_wide (csrc/de_gn_wide.h): one pool per call — the chunk's rows and values of the wide trees, the
     // mirrored constants, the partial sums and totals, and device images of a host jtj / ok
     DevBuf sGnw;
+    // de_eval*_tree_params (de_api_tree_params.cpp): sTp — the tables, the base and the class's constant vector, the
+    // class's results and the double accumulators of one call; sTpOut — the device image of a host `out` of de_eval_tree_params
+    DevBuf sTp, sTpOut;
     std::vector<unsigned char> lm_tab;
     void *lm_pin = nullptr;
     size_t lm_pin_cap = 0;

@@ -16,7 +16,7 @@ module DynamicExpressionsHIPExt
 
 using DynamicExpressions:
     AbstractExpressionNode, Node, GraphNode, OperatorEnum, EvalContext, get_child, get_children,
-    count_constant_nodes, preserve_sharing
+    count_constant_nodes, preserve_sharing, ParametricExpression, get_contents, get_metadata
 import DynamicExpressions.ExtensionInterfaceModule: is_extension_loaded
 
 const LIBDE = get(ENV, "DE_HIP_LIB", "libde_hip")
@@ -1161,6 +1161,192 @@ function eval_population_loss_grad_by_class(
     end
     return lossv, [combine_rows(pop, t, dl[(offs[t] + 1):offs[t + 1]], mode) for t in 1:pop.n_trees],
            [dp[:, :, t] for t in 1:pop.n_trees], ok .!= 0x00
+end
+
+# ---- per-tree parameter matrices (include/de_hip.h de_eval*_tree_params, DESIGN.md §4.4.11) ------------------------------------------
+# Every ParametricExpression owns its parameter matrix (`metadata.parameters`, n_params × n_classes); `eval_population(pop, X,
+# parameters, classes)` above reads ONE matrix for all trees.  Inside one class segment a parameter is a constant of its tree: the trees
+# are rewritten by `de_tape_params_to_consts` into ordinary trees in which some constant slots stand for parameters (`slot_param`), and
+# a call serves the population one class at a time, the slots patched on the device — the mirror of api.py's `ParametricPopulation`.
+struct TreeParams           # de_tree_params_t
+    params::Ptr{Cvoid}
+    ld_params::Int64
+    n_classes::Int64
+    n_params::Int32
+    reserved::Int32
+    class_starts::Ptr{Int64}
+    slot_param::Ptr{Int32}
+end
+
+mutable struct HIPParametricPopulation{T}
+    pop::HIPPopulation{T}                # the rewritten trees: an ordinary population, n_params = 0
+    slot_param::Vector{Int32}            # per constant slot of `pop`: -1 a real constant, else the 0-based parameter row
+    slot_off::Vector{Int64}              # n_trees + 1: first slot of every tree
+    n_params::Int
+    parameters::Array{T,3}               # n_params × n_classes × n_trees: the expressions' own matrices
+end
+
+"""
+    HIPParametricPopulation(exprs::Vector{<:ParametricExpression}, n_features; eval_context=EvalContext())
+
+A population of `ParametricExpression`s that each carry their own parameters.  Tapes are flattened as `HIPPopulation` does, rewritten by
+`de_tape_params_to_consts` and handed to `de_program_create` with `n_params = 0`.
+"""
+function HIPParametricPopulation(
+    exprs::AbstractVector{<:ParametricExpression{T}}, n_features::Integer; eval_context::EvalContext=EvalContext(),
+) where {T<:Union{Float32,Float64}}
+    isempty(exprs) && error("empty population")
+    operators = get_metadata(first(exprs)).operators
+    optable = opcode_table(operators)
+    P, C = size(get_metadata(first(exprs)).parameters)
+    nodes, consts, slot_param = TapeNode[], T[], Int32[]
+    node_off, const_off = Int64[0], Int64[0]
+    parameters = Array{T,3}(undef, P, C, length(exprs))
+    ctx = task_context()
+    for (t, ex) in enumerate(exprs)
+        size(get_metadata(ex).parameters) == (P, C) || error("the expressions differ in the shape of their parameters")
+        parameters[:, :, t] .= get_metadata(ex).parameters
+        tape, tconsts = TapeNode[], T[]
+        flatten!(tape, tconsts, get_contents(ex), optable, 0)
+        sp = Vector{Int32}(undef, length(tape))
+        n = with_ctx(ctx) do _   # (a host-only hook; every library call of the shim goes under the context's lock)
+            GC.@preserve tape sp ccall((:de_tape_params_to_consts, LIBDE), Int64,
+                (Ptr{TapeNode}, Int64, Int32, Ptr{TapeNode}, Ptr{Int32}, Int64), tape, length(tape), P, tape, sp, length(sp))
+        end
+        n < 0 && error("de_tape_params_to_consts: status $(-n) (6: a parameter row >= n_params, 7: a shared subtree)")
+        resize!(sp, n)
+        k = 0                                   # the constant pool in slot order: the tree's constants, 0 in parameter slots
+        for r in sp
+            push!(consts, r < 0 ? tconsts[k += 1] : zero(T))
+        end
+        append!(nodes, tape); append!(slot_param, sp)
+        push!(node_off, length(nodes)); push!(const_off, length(consts))
+    end
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    with_ctx(ctx) do hc
+        check(ctx, GC.@preserve nodes consts node_off const_off ccall(
+            (:de_program_create, LIBDE), Cint,
+            (Ptr{Cvoid}, Cint, Ptr{TapeNode}, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int32, Int32, UInt32, Ref{Ptr{Cvoid}}),
+            hc, dtype_code(T), nodes, node_off, length(exprs), consts, const_off, n_features, 0,
+            option_bits(operators, eval_context), h))
+    end
+    n_slots = Int.(diff(const_off))
+    pop = HIPPopulation{T}(ctx, h[], length(exprs), n_features, fill(nothing, length(exprs)), n_slots, copy(n_slots), optable)
+    finalizer(finalize_population, pop)
+    return HIPParametricPopulation{T}(pop, slot_param, const_off, P, parameters)
+end
+
+# the data ordered by class (stable) and the class_starts of de_tree_params_t
+function group_by_class(X::Matrix{T}, classes::Vector{Int64}, C::Int, grouped::Bool, vecs...) where {T}
+    @assert isempty(classes) || (minimum(classes) >= 1 && maximum(classes) <= C)   # src/ParametricExpression.jl:378-379
+    perm = grouped ? nothing : sortperm(classes; alg=MergeSort)
+    if perm !== nothing
+        X, classes = X[:, perm], classes[perm]
+        vecs = map(v -> v === nothing ? nothing : v[perm], vecs)
+    end
+    starts = zeros(Int64, C + 1)
+    for c in classes
+        starts[c + 1] += 1
+    end
+    cumsum!(starts, starts)
+    return X, starts, perm, vecs
+end
+
+"""
+    eval_parametric_population(pp, X, classes; parameters=pp.parameters, grouped=false) -> (out::Matrix{T}(N × n_trees), ok)
+
+Every expression on every sample with ITS OWN parameters (`de_eval_tree_params`); `parameters` is `n_params × n_classes × n_trees`.
+Columns of `out` are the reference's `Vector{T}(N)` results in the order of `X`.
+"""
+function eval_parametric_population(
+    pp::HIPParametricPopulation{T}, X::Matrix{T}, classes::Vector{Int64}; parameters::Array{T,3}=pp.parameters, grouped::Bool=false,
+) where {T}
+    pop = pp.pop
+    F, N = size(X)
+    P, C, nt = size(parameters)
+    @assert F >= pop.n_features && length(classes) == N && P == pp.n_params && nt == pop.n_trees
+    X, starts, perm, _ = group_by_class(X, classes, C, grouped)
+    out = Matrix{T}(undef, N, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    sp = pp.slot_param
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X parameters starts sp out ok begin
+            tp = Ref(TreeParams(pointer(parameters), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
+            ccall((:de_eval_tree_params, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Int64, Ptr{UInt8}),
+                hc, hp, X, N, F, tp, out, N, ok)
+        end)
+    end
+    if perm !== nothing
+        out[perm, :] = out
+    end
+    return out, ok .!= 0x00
+end
+
+"""
+    eval_parametric_population_loss(pp, X, y, classes; parameters, weights=nothing, loss=:L2, loss_param=0.0, grouped=false) -> (loss, ok)
+
+`eval_population_loss` for expressions that each carry their own parameters (`de_eval_loss_tree_params`).
+"""
+function eval_parametric_population_loss(
+    pp::HIPParametricPopulation{T}, X::Matrix{T}, y::Vector{T}, classes::Vector{Int64}; parameters::Array{T,3}=pp.parameters,
+    weights::Union{Nothing,Vector{T}}=nothing, loss::Symbol=:L2, loss_param::Real=0.0, grouped::Bool=false,
+) where {T}
+    pop = pp.pop
+    F, N = size(X)
+    P, C, nt = size(parameters)
+    @assert F >= pop.n_features && length(y) == N && length(classes) == N && P == pp.n_params && nt == pop.n_trees
+    X, starts, _, (y, weights) = group_by_class(X, classes, C, grouped, y, weights)
+    spec = loss_spec(loss, loss_param; with_gradient=false)
+    out = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    sp = pp.slot_param
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights parameters starts sp out ok begin
+            tp = Ref(TreeParams(pointer(parameters), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
+            ccall((:de_eval_loss_tree_params, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ptr{Cvoid},
+                 Ptr{UInt8}),
+                hc, hp, X, N, F, tp, y, weights === nothing ? C_NULL : pointer(weights), spec, out, ok)
+        end)
+    end
+    return out, ok .!= 0x00
+end
+
+"""
+    eval_parametric_population_loss_grad(pp, X, y, classes; parameters, weights=nothing, loss=:L2, loss_param=0.0, grouped=false)
+        -> (loss, dconstants::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)
+
+The fused loss, its gradient w.r.t. every expression's real constants (`get_scalar_constants` order without the parameters) and
+w.r.t. its own `n_params × n_classes` parameter matrix (`de_eval_loss_grad_tree_params`): `vcat(dconstants[t], dparameters[t][:])` is the
+gradient of the optimiser's combined vector (src/ParametricExpression.jl:258-278).
+"""
+function eval_parametric_population_loss_grad(
+    pp::HIPParametricPopulation{T}, X::Matrix{T}, y::Vector{T}, classes::Vector{Int64}; parameters::Array{T,3}=pp.parameters,
+    weights::Union{Nothing,Vector{T}}=nothing, loss::Symbol=:L2, loss_param::Real=0.0, grouped::Bool=false,
+) where {T}
+    pop = pp.pop
+    F, N = size(X)
+    P, C, nt = size(parameters)
+    @assert F >= pop.n_features && length(y) == N && length(classes) == N && P == pp.n_params && nt == pop.n_trees
+    X, starts, _, (y, weights) = group_by_class(X, classes, C, grouped, y, weights)
+    spec = loss_spec(loss, loss_param)
+    lossv = Vector{T}(undef, pop.n_trees)
+    dl = Vector{T}(undef, max(length(pp.slot_param), 1))
+    dp = Array{T,3}(undef, P, C, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    sp, offs = pp.slot_param, pp.slot_off
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights parameters starts sp offs lossv dl dp ok begin
+            tp = Ref(TreeParams(pointer(parameters), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
+            ccall((:de_eval_loss_grad_tree_params, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ptr{Cvoid},
+                 Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{UInt8}),
+                hc, hp, X, N, F, tp, y, weights === nothing ? C_NULL : pointer(weights), spec, lossv, dl, offs, dp, ok)
+        end)
+    end
+    dconsts = [T[dl[s] for s in (offs[t] + 1):offs[t + 1] if sp[s] < 0] for t in 1:pop.n_trees]
+    return lossv, dconsts, [dp[:, :, t] for t in 1:pop.n_trees], ok .!= 0x00
 end
 
 """Forward-mode gradient of one tree: `(evaluation, gradient(n_grad × N), complete)` like

@@ -94,7 +94,10 @@ extern "C" {
  *      de_lm_project_host_wide: the same for trees of 9 to 32 gradient rows; every entry point above keeps its bits.
  *      (n) de_bfgs_max_rows, de_fit_consts_bfgs (with de_bfgs_opts_t) and the host-only hooks de_bfgs_direction_host and
  *      de_bfgs_update_host: BFGS on the constants of a population on the device, from the loss and its gradient alone (DESIGN.md
- *      §4.4.10), under every loss kind that has a gradient, for trees of up to 32 constants; DE_F32 / DE_F64. */
+ *      §4.4.10), under every loss kind that has a gradient, for trees of up to 32 constants; DE_F32 / DE_F64.
+ *      (o) de_tape_params_to_consts, de_eval_tree_params, de_eval_loss_tree_params, de_eval_loss_grad_tree_params (with de_tree_params_t)
+ *      and the host-only hook de_tree_params_accumulate_host: a population whose trees each own their parameter matrix, served one class
+ *      segment at a time as a non-parametric program whose parameter slots are patched on the device; DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -404,6 +407,15 @@ int64_t de_lower_tape_stage_complex(int dtype, const de_tape_node_t *nodes, int6
 int64_t de_lower_tape_grad(int dtype, const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
                            int32_t n_features, int32_t n_params, uint32_t options, int mode, int form, uint32_t *words,
                            int64_t cap, int32_t *meta);
+/* Host-only hook (no HIP call) of the per-tree parameter entry points below: rewrite ONE post-order tape so that every
+ * DE_LEAF_CONST and every DE_LEAF_PARAM leaf becomes a DE_LEAF_CONST whose slot is its ordinal among those leaves in tape order (the
+ * depth-first constant order de_program_create requires); every other node is copied.  slot_param[s] = -1 for a real constant, else the
+ * 0-based parameter row of slot s; a parameter that occurs twice gets two slots with the same row; a tape without parameters comes back
+ * unchanged.  out_nodes has room for n_nodes nodes (it may be `nodes` itself), slot_param for `cap` entries.  Returns the number of
+ * slots, or -status: DE_ERR_INVALID_ARG for a null pointer, a negative count or more slots than `cap`; DE_ERR_OUT_OF_RANGE for a
+ * parameter row >= n_params; DE_ERR_UNSUPPORTED for a DE_LEAF_SHARED or DE_OP_SHARE node (CSE tapes are not served). */
+int64_t de_tape_params_to_consts(const de_tape_node_t *nodes, int64_t n_nodes, int32_t n_params, de_tape_node_t *out_nodes,
+                                 int32_t *slot_param, int64_t cap);
 
 /* ---- evaluation ------------------------------------------------------------ */
 /* Optional per-call inputs of a parametric population
@@ -869,6 +881,57 @@ int de_eval_loss_grad_by_class_ex(de_ctx_t *ctx, de_program_t *prog, const void 
                                   const de_param_args_t *pargs, int mode, const void *y, const void *w,
                                   const de_loss_spec_t *spec, const int64_t *class_starts, void *loss, void *dloss,
                                   const int64_t *dloss_offsets, void *dparams, uint8_t *ok);
+
+/* ---- per-tree parameter matrices ---------------------------------------------------------------------------
+ * In the reference every ParametricExpression owns its parameter matrix (metadata.parameters, [n_params, n_classes]); the entry points
+ * above read ONE matrix for the whole population.  These three serve a population whose trees each carry their own: inside one class
+ * segment a parameter is a constant of its tree, so the population is an ORDINARY program (n_params == 0) made from tapes rewritten by
+ * de_tape_params_to_consts, in which some constant slots stand for parameters.  The samples are grouped by class (class_starts as for
+ * de_eval_loss_grad_by_class).  One call, in stream order on the context's stream:
+ *   1. the program's current constants are read into device scratch: the base vector;
+ *   2. for every class c with at least one sample, ascending: a kernel forms the class's constant vector (base values in real slots,
+ *      params[p, c, tree of the slot] in parameter slots), de_program_set_consts_device installs it, the model entry point (de_eval /
+ *      de_eval_loss_ex / de_eval_loss_grad_ex in mode DE_GRAD_CONSTANT) runs on the class's sample range, and a kernel adds the class's
+ *      per-tree results into DOUBLE accumulators and ANDs the flags (de_eval_tree_params writes straight into out + class_starts[c]);
+ *   3. a last kernel writes the accumulators in the program's element type, NaN where the final ok[t] == 0;
+ *   4. the base vector is set back: de_program_get_consts returns the bits it returned before the call.
+ * Every returned quantity is a plain sum over samples, so the class segments add.  The order of the additions is fixed (classes
+ * ascending, occurrences in slot order, in double): two runs give the same bits.  A class without samples is skipped entirely — its
+ * parameter columns are never read (an Inf there clears no flag) and its dparams cells are 0.  ok[t] is the AND over the non-empty
+ * classes of the model call's flag.  Host inputs are staged once per call.
+ *   de_eval_tree_params            as de_eval: rows of trees with ok[t] == 0 are unspecified (device) / NaN (host buffer)
+ *   de_eval_loss_tree_params       as de_eval_loss_ex
+ *   de_eval_loss_grad_tree_params  as de_eval_loss_grad_by_class_ex: dloss has the DE_GRAD_CONSTANT layout of the program (every slot;
+ *                                  a parameter slot holds its occurrence's sum over all classes), `loss` may be NULL, and
+ *                                  dparams[(t*n_classes + c)*n_params + p] = the sum over the occurrences of row p in tree t of that
+ *                                  slot's gradient over class c (the layout of de_eval_loss_grad_by_class)
+ * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED for DE_F16 / complex programs, programs made by
+ * de_program_create_cse and programs with n_params != 0; DE_ERR_INVALID_ARG for a null tp / class_starts, a null params or slot_param on
+ * a program with constants, reserved != 0, n_params < 0, n_classes <= 0, class_starts not monotone from 0 to N, a slot_param entry
+ * outside [-1, n_params), ld_params < n_params and whatever the model entry point refuses (a bad spec, a null y / ok, ...).
+ *
+ * de_tree_params_accumulate_host: the accumulate-and-finish arithmetic of ONE tree on the host (no HIP call; csrc/de_tree_params.h, the
+ * code the kernels run: the same bits).  Inputs in `dtype` (DE_F32 / DE_F64): loss_c[c], dloss_c[c*n_slots + s], ok_c[c] — one model
+ * result per class; class_used[c] == 0: class c is skipped, its entries are never read.  Outputs: loss (1), dloss (n_slots),
+ * dparams[c*n_params + p], ok (1 byte).  Returns DE_OK or DE_ERR_INVALID_ARG. */
+typedef struct de_tree_params {
+    const void *params;          /* [n_params, n_classes, n_trees], dtype elements: params[p + ld_params*(c + n_classes*t)]; host or device */
+    int64_t ld_params;           /* >= n_params */
+    int64_t n_classes;
+    int32_t n_params, reserved;  /* reserved = 0 */
+    const int64_t *class_starts; /* host, n_classes + 1 sample offsets, as de_eval_loss_grad_by_class */
+    const int32_t *slot_param;   /* host, one entry per constant slot of the program in de_program_set_consts' order */
+} de_tree_params_t;
+int de_eval_tree_params(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                        void *out, int64_t ld_out, uint8_t *ok);
+int de_eval_loss_tree_params(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                             const void *y, const void *w, const de_loss_spec_t *spec, void *loss, uint8_t *ok);
+int de_eval_loss_grad_tree_params(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                                  const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
+                                  const int64_t *dloss_offsets, void *dparams, uint8_t *ok);
+int de_tree_params_accumulate_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
+                                   const uint8_t *class_used, const void *loss_c, const void *dloss_c, const uint8_t *ok_c,
+                                   void *loss, void *dloss, void *dparams, uint8_t *ok);
 
 /* The `dX` of the ChainRules pullback of eval_tree_array (EvalPullback, src/ChainRules.jl:56-77):
  *   dX_t[f, j] = d tree_t(x_j) / d x_f * dY[j]      (`dX = dX_dY .* reshape(dY, 1, length(dY))`, :74)
