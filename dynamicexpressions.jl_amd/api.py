@@ -61,6 +61,7 @@ EXPORTS = [
     "de_bfgs_max_rows", "de_bfgs_direction_host", "de_bfgs_update_host", "de_fit_consts_bfgs",
     "de_tape_params_to_consts", "de_eval_tree_params", "de_eval_loss_tree_params", "de_eval_loss_grad_tree_params",
     "de_tree_params_accumulate_host",
+    "de_fit_tree_params_bfgs", "de_tree_params_pack_host", "de_tree_params_unpack_host",
 ]
 
 
@@ -683,6 +684,11 @@ def library() -> C.CDLL:
         lib.de_eval_loss_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp]
         lib.de_eval_loss_grad_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp]
         lib.de_tree_params_accumulate_host.argtypes = [C.c_int, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "de_fit_tree_params_bfgs"):  # (absent from a library built before the device fit over parameters: DE_HIP_LIB in an A/B run)
+        lib.de_fit_tree_params_bfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
+                                                vp, vp, vp, vp, vp]
+        lib.de_tree_params_pack_host.argtypes = [C.c_int, i32, vp, i32, i64, i64, vp, vp, vp]
+        lib.de_tree_params_unpack_host.argtypes = [C.c_int, i32, vp, i32, i64, i64, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -2391,6 +2397,61 @@ def tree_params_accumulate_host(slot_param, n_params: int, class_used, loss_c, d
     return lo[0], dl[:len(sp)], dp, bool(ok[0])
 
 
+def _tree_params_block(params_tree, n_params: int, dtype):
+    """One tree's ``[n_params, n_classes]`` matrix as the library's block: ``[n_classes, ld]`` rows, ld >= n_params (a 2-D array whose
+    rows are ``ld`` apart is used in place, e.g. a slice ``block[:, :n_params]`` of a padded block).  Returns (array, ld, n_classes)."""
+    m = np.asarray(params_tree, dtype=dtype)
+    if m.ndim != 2 or m.shape[0] != n_params:
+        raise ValueError(f"params_tree must be [n_params = {n_params}, n_classes]")
+    rows = m.T  # [n_classes, n_params]
+    es = m.dtype.itemsize
+    if rows.size and rows.strides[1] == es and rows.strides[0] % es == 0 and rows.strides[0] // es >= max(n_params, 1):
+        return rows, rows.strides[0] // es, rows.shape[0]
+    return np.ascontiguousarray(rows), max(n_params, 1), rows.shape[0]
+
+
+def tree_params_pack_host(slot_param, n_params: int, slot_values, params_tree, dtype=np.float64):
+    """``de_tree_params_pack_host``: ONE tree's vector of unknowns ``vcat(constants, parameters[:])`` (csrc/de_tree_params_fit.h, the index
+    map the kernels of ``de_fit_tree_params_bfgs`` run; no GPU needed).  ``slot_values[n_slots]``: every constant slot (parameter slots
+    are skipped); ``params_tree[n_params, n_classes]``.  Returns x[G], every bit copied."""
+    dtype = np.dtype(dtype)
+    sp = np.ascontiguousarray(slot_param, dtype=np.int32)
+    sv = np.ascontiguousarray(slot_values, dtype=dtype).reshape(-1)
+    if sv.size != sp.size:
+        raise ValueError("slot_values has one entry per slot")
+    blk, ld, ncls = _tree_params_block(params_tree, int(n_params), dtype)
+    x = np.empty(int(np.sum(sp < 0)) + int(n_params) * ncls, dtype=dtype)
+    G = library().de_tree_params_pack_host(_dtype_code(dtype), len(sp), sp.ctypes.data if sp.size else None, int(n_params), ncls, ld,
+                                           sv.ctypes.data if sv.size else None, blk.ctypes.data if blk.size else None,
+                                           x.ctypes.data if x.size else None)
+    if G < 0:
+        raise ValueError(f"{library().de_status_string(-G).decode()}: de_tree_params_pack_host")
+    return x[:G]
+
+
+def tree_params_unpack_host(slot_param, n_params: int, x, slot_values, params_tree):
+    """``de_tree_params_unpack_host``: the inverse of ``tree_params_pack_host``, IN PLACE — ``slot_values`` (a contiguous numpy vector) and
+    ``params_tree`` (``[n_params, n_classes]``, numpy, e.g. a view into a padded block) take the entries of ``x``; parameter slots and
+    padding keep their bits.  The dtype is ``slot_values``'."""
+    if not isinstance(slot_values, np.ndarray) or not slot_values.flags.c_contiguous or not isinstance(params_tree, np.ndarray):
+        raise ValueError("slot_values and params_tree are numpy arrays written in place")
+    dtype = slot_values.dtype
+    sp = np.ascontiguousarray(slot_param, dtype=np.int32)
+    if slot_values.size != sp.size or params_tree.dtype != dtype:
+        raise ValueError("slot_values has one entry per slot; params_tree has its dtype")
+    blk, ld, ncls = _tree_params_block(params_tree, int(n_params), dtype)
+    x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+    if x.size != int(np.sum(sp < 0)) + int(n_params) * ncls:
+        raise ValueError("x has one entry per unknown")
+    rc = library().de_tree_params_unpack_host(_dtype_code(dtype), len(sp), sp.ctypes.data if sp.size else None, int(n_params), ncls, ld,
+                                              x.ctypes.data if x.size else None, slot_values.ctypes.data if sp.size else None,
+                                              blk.ctypes.data if blk.size else None)
+    if rc != 0:
+        raise ValueError(f"{library().de_status_string(rc).decode()}: de_tree_params_unpack_host")
+    if blk.size and not np.shares_memory(blk, params_tree):
+        params_tree[...] = blk.T
+
+
 def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
                          curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
     """The host loop of ``Population.fit_constants_bfgs`` over each tree's combined vector ``vcat(constants, params[t].T.reshape(-1))`` —
@@ -2761,6 +2822,65 @@ class ParametricPopulation:
         self.set_constants(consts)
         self.params, self.bfgs_accepts = ps, acc
         return consts, ps, lo, ok
+
+    @staticmethod
+    def check_fit_args(n_real: int, consts0, iters, step0, shrink, c1, curv, loss, loss_param):
+        """The checks of ``fit_bfgs_device`` that need no device: ``_bfgs_opts``' refusals and the length of ``consts0`` (``None``: the
+        current constants).  Returns (BfgsOpts, LossSpec); ``ValueError`` otherwise."""
+        opts, spec = _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
+        if consts0 is not None and int(consts0.numel() if _is_torch(consts0) else np.size(consts0)) != int(n_real):
+            raise ValueError("wrong number of constants")
+        return opts, spec
+
+    def fit_bfgs_device(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, step0: float = 1.0,
+                        shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                        class_base: int = 1, grouped: bool = False, history: bool = False):
+        """``fit_bfgs`` as ONE library call (``de_fit_tree_params_bfgs``): the packed vectors, the directions, the
+        trials, the class loop of every evaluation, the accept rule and the updates of ``B`` run on the device; no constant, gradient or
+        parameter reaches the host, and the trajectory is the host loop's bit for bit.  ``consts0`` / ``params0``: as ``fit_bfgs`` (numpy
+        arrays or torch device tensors).  The data is ordered by class once (``grouped=True``: it already is).  Returns (consts, params
+        [n_trees, n_params, n_classes], loss, ok); the population holds the fitted constants afterwards, ``self.params`` the fitted
+        parameters, ``self.bfgs_accepts`` the accepted steps per member and, with ``history=True``, ``self.bfgs_history`` the
+        ``[iters + 1, n_trees]`` accepted losses (float64).  With torch inputs everything is a device tensor on torch's stream."""
+        self.pop._refuse_f16("fit_bfgs_device")
+        opts, spec = self.check_fit_args(len(self._real), consts0, iters, step0, shrink, c1, curv, loss, loss_param)
+        if y is None:
+            raise ValueError("fit_bfgs_device: y is required")
+        ptr, N, ldX, yp, wp, tp, _, is_t, keep = self._prepare(X, params0, classes, class_base, grouped, y, weights)
+        nt, P, ncls, ld, rows = self.n_trees, self.n_params, int(tp.n_classes), int(tp.ld_params), int(iters) + 1
+        if consts0 is not None:
+            if _is_torch(consts0):
+                import torch
+                full = torch.zeros(len(self._slot_param_all), dtype=_torch_dtype(self.dtype), device=consts0.device)
+                full[torch.as_tensor(self._real, device=consts0.device)] = consts0.reshape(-1).to(full.dtype)
+                self.pop.set_constants(full)
+            else:
+                self.set_constants(consts0)
+        if is_t:
+            import torch
+            kx = keep[0]
+            kw = dict(dtype=kx.dtype, device=kx.device)
+            lo, outb = torch.empty(nt, **kw), torch.empty((nt, ncls, ld), **kw)
+            ok = torch.empty(nt, dtype=torch.uint8, device=kx.device)
+            hist = torch.empty((rows, nt), dtype=torch.float64, device=kx.device)
+            acc = torch.empty(nt, dtype=torch.int32, device=kx.device)
+            ptrs = (outb.data_ptr() if nt * ncls * P else None, lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
+        else:
+            lo, outb = np.empty(nt, dtype=self.dtype), np.empty((nt, ncls, ld), dtype=self.dtype)
+            ok = np.zeros(nt, dtype=np.uint8)
+            hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
+            ptrs = (outb.ctypes.data if nt * ncls * P else None, lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
+        self.ctx.check(library().de_fit_tree_params_bfgs(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                         C.byref(opts), *ptrs))
+        self.bfgs_accepts, self.bfgs_history = acc, (hist if history else None)
+        if is_t:
+            ps = outb[:, :, :P].transpose(1, 2)
+            consts = self.pop.constants(device=True)[torch.as_tensor(self._real, device=kx.device)]
+            self.params = ps
+            return consts, ps, lo, ok.bool()
+        ps = np.ascontiguousarray(outb[:, :, :P].transpose(0, 2, 1))
+        self.params = ps
+        return self.constants(), ps, lo, ok.astype(bool)
 
     def close(self) -> None:
         self.pop.close()

@@ -127,7 +127,8 @@ build_obj de_lm_scaled.hip $OBJ/de_lm_scaled.o &
 build_obj de_lm_scaled_wide.hip $OBJ/de_lm_scaled_wide.o &
 # de_fit_consts_bfgs: the init, direction and accept kernels of the BFGS fit, one wave per tree (plain hipcc)
 build_obj de_bfgs.hip $OBJ/de_bfgs.o &
-# de_eval*_tree_params: the scatter, accumulate and finish kernels of the per-tree parameter entry points (plain hipcc)
+# de_eval*_tree_params: the scatter, accumulate and finish kernels of the per-tree parameter entry points, and the pack / unpack kernels
+# of de_fit_tree_params_bfgs (plain hipcc; no new object: the fit's kernels live next to the ones whose tables they share)
 build_obj de_tree_params.hip $OBJ/de_tree_params.o &
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_tree_params.o"

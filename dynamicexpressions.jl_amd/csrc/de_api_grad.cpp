@@ -1995,6 +1995,15 @@ int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const
     return bfgs_update(G, B, fresh, s, yv, curv);
 }
 
+const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
+    if (o->reserved != 0) return "de_bfgs_opts_t: reserved must be 0";
+    if (o->iters < 0) return "de_bfgs_opts_t: iters < 0";
+    for (const double v : {o->step0, o->c1, o->curv})
+        if (!(std::isfinite(v) && v > 0.0)) return "de_bfgs_opts_t: step0, c1 and curv must be finite and positive";
+    if (!(o->shrink > 0.0 && o->shrink < 1.0)) return "de_bfgs_opts_t: shrink must lie in (0, 1)";
+    return nullptr;
+}
+
 // fit_consts_lm_impl's structure with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip
 static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                                 const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
@@ -2015,11 +2024,7 @@ static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int
         if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
             return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_bfgs: tree %lld has %lld constant rows for %lld constants", (long long)t,
                         (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
-    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: reserved must be 0");
-    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: iters < 0");
-    for (const double v : {o.step0, o.c1, o.curv})
-        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: step0, c1 and curv must be finite and positive");
-    if (!(o.shrink > 0.0 && o.shrink < 1.0)) return fail(c, DE_ERR_INVALID_ARG, "de_bfgs_opts_t: shrink must lie in (0, 1)");
+    if (const char *why = bfgs_opts_problem(&o)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
     if (N < 0 || (p->n_trees > 0 && (!ok || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
     int rc = check_param_args(c, p, pa, N);

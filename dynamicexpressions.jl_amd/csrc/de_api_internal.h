@@ -345,6 +345,8 @@ int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, 
 int consts_materialise(de_program *p);
 // the body of de_program_set_consts_device (de_api_program.cpp): de_fit_consts_lm sets its trial and accepted constants through it
 int set_consts_device_impl(de_program *p, const void *d_consts);
+// what de_fit_consts_bfgs and de_fit_tree_params_bfgs refuse about their options (de_api_grad.cpp): null = good, else the reason
+const char *bfgs_opts_problem(const de_bfgs_opts_t *o);
 // releases a program's GnWideCache (de_api_grad.cpp); the caller has synchronised the stream
 void gn_wide_release(de_program *p);
 }

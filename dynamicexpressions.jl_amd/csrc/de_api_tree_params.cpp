@@ -4,9 +4,16 @@
 // segment at a time: the class's constant vector is formed and installed on the device (de_program_set_consts_device), the model entry
 // point runs on the class's sample range, and the per-tree results are added in double (kernels: de_tree_params.hip, arithmetic:
 // de_tree_params.h).  No existing kernel, record format or lowering pass is involved.
+// ... and de_fit_tree_params_bfgs with its host-only hooks de_tree_params_pack_host / de_tree_params_unpack_host: BFGS
+// over each tree's vcat(constants, parameters[:]) with that class loop as the evaluator (kernels: de_bfgs.hip unchanged on packed
+// vectors, the pack / unpack kernels of de_tree_params.hip; index map: de_tree_params_fit.h).
 #include "de_api_internal.h"
 #include "de_tree_params_dev.h"
 #include "de_tree_params.h"
+#include "de_tree_params_fit.h"
+#include "de_bfgs.h"
+#include "de_bfgs_dev.h"
+#include "de_lm.h"
 
 template <typename T>
 static void accumulate_host(int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes, const uint8_t *class_used,
@@ -29,7 +36,56 @@ static void accumulate_host(int32_t n_slots, const int32_t *slot_param, int32_t 
     for (int64_t j = 0; j < n_classes * n_params; j++) dparams[j] = tp_finish<T>(acc_dp[(size_t)j], acc_ok);
 }
 
+// one tree's unknowns gathered from / scattered to (slot values, its parameter block): the table and the copies the kernels run
+template <typename T>
+static void pack_host(bool unpack, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes, int64_t ld, T *slots,
+                      T *cells, T *x) {
+    std::vector<int64_t> map((size_t)tpf_unknowns(n_slots, n_params, n_classes));
+    const int64_t G = tpf_map_tree(n_slots, slot_param, n_params, n_classes, 0, 0, map.data());
+    for (int64_t u = 0; u < G; u++) {
+        if (unpack) tpf_store(map[(size_t)u], x[u], slots, cells, n_params, ld);
+        else x[u] = tpf_load(map[(size_t)u], static_cast<const T *>(slots), static_cast<const T *>(cells), n_params, ld);
+    }
+}
+
+// the shared body of de_tree_params_pack_host / de_tree_params_unpack_host: G, or -status with nothing written
+static int pack_host_checked(bool unpack, int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
+                             int64_t ld, void *slots, void *cells, void *x) {
+    if ((dtype != DE_F32 && dtype != DE_F64) || n_slots < 0 || n_params < 0 || n_classes < 0 || n_classes > INT32_MAX || ld < n_params)
+        return -DE_ERR_INVALID_ARG;
+    if (n_slots > 0 && !slot_param) return -DE_ERR_INVALID_ARG;
+    int64_t n_real = 0;
+    for (int32_t s = 0; s < n_slots; s++) {
+        if (slot_param[s] < -1 || slot_param[s] >= n_params) return -DE_ERR_INVALID_ARG;
+        n_real += slot_param[s] < 0 ? 1 : 0;
+    }
+    const int64_t G = tpf_unknowns(n_real, n_params, n_classes);
+    if (G > INT32_MAX) return -DE_ERR_INVALID_ARG;
+    if ((n_real > 0 && !slots) || ((int64_t)n_params * n_classes > 0 && !cells) || (G > 0 && !x)) return -DE_ERR_INVALID_ARG;
+    try {
+        if (dtype == DE_F32)
+            pack_host<float>(unpack, n_slots, slot_param, n_params, n_classes, ld, static_cast<float *>(slots), static_cast<float *>(cells),
+                             static_cast<float *>(x));
+        else
+            pack_host<double>(unpack, n_slots, slot_param, n_params, n_classes, ld, static_cast<double *>(slots), static_cast<double *>(cells),
+                              static_cast<double *>(x));
+    } catch (...) { return -DE_ERR_HIP; }
+    return (int)G;
+}
+
 extern "C" {
+
+int de_tree_params_pack_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes, int64_t ld_params,
+                             const void *slot_values, const void *params_tree, void *x) {
+    return pack_host_checked(false, dtype, n_slots, slot_param, n_params, n_classes, ld_params, const_cast<void *>(slot_values),
+                             const_cast<void *>(params_tree), x);
+}
+int de_tree_params_unpack_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes, int64_t ld_params,
+                               const void *x, void *slot_values, void *params_tree) {
+    const int g = pack_host_checked(true, dtype, n_slots, slot_param, n_params, n_classes, ld_params, slot_values, params_tree,
+                                    const_cast<void *>(x));
+    return g < 0 ? -g : DE_OK;
+}
 
 int64_t de_tape_params_to_consts(const de_tape_node_t *nodes, int64_t n_nodes, int32_t n_params, de_tape_node_t *out_nodes,
                                  int32_t *slot_param, int64_t cap) {
@@ -86,6 +142,25 @@ struct TpOut { // what the model returns
     const de_loss_spec_t *spec = nullptr;
     void *loss = nullptr, *dloss = nullptr, *dparams = nullptr;
     const int64_t *dloss_offsets = nullptr;
+    bool fit = false; // de_fit_tree_params_bfgs: loss, dloss, dparams and ok are buffers of the pool, set per evaluation
+};
+struct TpPlan { // a call that passed every refusal
+    size_t nt = 0, nc = 0, es = 4;
+    int64_t C = 0, span = 1;
+    int32_t P = 0;
+    bool any_param = false, grad = false;
+    std::vector<int64_t> doff;
+};
+struct TpDev { // what a call holds on the device: one pooled allocation and the staged inputs
+    TreeParamsArgs a;
+    char *pool = nullptr;
+    void *base = nullptr;  // the base vector (a.base)
+    void *lc = nullptr, *dc = nullptr; // one class's loss / dloss
+    uint8_t *okc = nullptr;
+    size_t o_acc = 0, acc_bytes = 0, o_fit_tab = 0, o_fit = 0;
+    Staged sX, sY, sW, sPar;
+    bool h_ok = false, h_loss = false, h_dl = false, h_dp = false, h_out = false;
+    size_t n_dp = 0;
 };
 
 static size_t tp_place(size_t *at, size_t bytes) { // 16-byte aligned pieces of one pooled allocation
@@ -94,8 +169,9 @@ static size_t tp_place(size_t *at, size_t bytes) { // 16-byte aligned pieces of 
     return o;
 }
 
-static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpModel model, const void *X, int64_t N, int64_t ldX,
-                            const de_tree_params_t *tp, const TpOut &o, uint8_t *ok) {
+// every refusal of the three entry points (and the fit's, which adds its own): nothing has been touched when it returns an error
+static int tp_check(de_ctx_t *c, de_program_t *p, const char *what, TpModel model, const void *X, int64_t N, int64_t ldX,
+                    const de_tree_params_t *tp, const TpOut &o, uint8_t *ok, TpPlan *pl) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     // ---- refusals: before any output or constant is touched ----
@@ -133,7 +209,7 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
     } else {
         if (nt > 0 && N > 0 && (!X || !o.y)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
         if (model == TP_LOSS && nt > 0 && !o.loss) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-        if (model == TP_LOSS_GRAD && nt > 0 && (!o.dloss || !o.dparams)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+        if (model == TP_LOSS_GRAD && nt > 0 && !o.fit && (!o.dloss || !o.dparams)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
         if (loss_spec_problem(o.spec, model == TP_LOSS_GRAD ? 1 : 0, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
         if (model == TP_LOSS && !p->threaded)
             return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss needs the LDS-tiled kernel (feature matrix too wide for this build)");
@@ -151,17 +227,31 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
         doff[t] = off;
         span = std::max(span, off + g);
     }
-    if (nt == 0) return DE_OK;
+    pl->nt = nt; pl->nc = nc; pl->es = p->dtype == DE_F32 ? 4 : 8;
+    pl->C = C; pl->P = P; pl->span = std::max<int64_t>(span, 1);
+    pl->any_param = any_param; pl->grad = grad;
+    pl->doff = std::move(doff);
+    return DE_OK;
+}
+
+// The pooled allocation, the tables and the staged host inputs of a checked call (n_trees > 0).  `fit_tab` (may be null) is uploaded
+// behind the call's own tables, at d->o_fit_tab; `fit_bytes` more bytes of the pool start at d->o_fit.  The stream is idle afterwards.
+static int tp_setup(de_ctx_t *c, de_program_t *p, TpModel model, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                    const TpOut &o, uint8_t *ok, const TpPlan &pl, const std::vector<unsigned char> *fit_tab, size_t fit_bytes, TpDev *d) {
+    const size_t nt = pl.nt, nc = pl.nc, es = pl.es;
+    const int64_t C = pl.C, span = pl.span;
+    const int32_t P = pl.P;
+    const bool grad = pl.grad, any_param = pl.any_param;
+    const std::vector<int64_t> &doff = pl.doff;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8;
-    span = std::max<int64_t>(span, 1);
 
     // ---- one pooled allocation: tables, the two constant vectors, one class's results, the accumulators, images of host outputs ----
     const size_t n_dp = grad ? nt * (size_t)C * (size_t)P : 0;
-    const bool h_ok = !is_device_ptr(ok), h_loss = o.loss && !is_device_ptr(o.loss), h_dl = grad && !is_device_ptr(o.dloss),
-               h_dp = grad && n_dp > 0 && !is_device_ptr(o.dparams), h_out = model == TP_EVAL && N > 0 && !is_device_ptr(o.out);
+    const bool h_ok = !o.fit && !is_device_ptr(ok), h_loss = o.loss && !is_device_ptr(o.loss), h_dl = grad && !o.fit && !is_device_ptr(o.dloss),
+               h_dp = grad && !o.fit && n_dp > 0 && !is_device_ptr(o.dparams), h_out = model == TP_EVAL && N > 0 && !is_device_ptr(o.out);
     size_t at = 0;
     const size_t o_stree = tp_place(&at, nc * 4), o_sparam = tp_place(&at, nc * 4), o_coff = tp_place(&at, (nt + 1) * 8), o_doff = tp_place(&at, nt * 8);
+    const size_t o_fit_tab = tp_place(&at, fit_tab ? fit_tab->size() : 0);
     const size_t tab_bytes = at;
     const size_t o_base = tp_place(&at, nc * es), o_cvec = tp_place(&at, nc * es), o_lc = tp_place(&at, nt * es),
                  o_dc = tp_place(&at, grad ? (size_t)span * es : 0), o_okc = tp_place(&at, nt);
@@ -171,11 +261,13 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
     const size_t o_aok = tp_place(&at, nt);
     const size_t o_hok = h_ok ? tp_place(&at, nt) : 0, o_hl = h_loss ? tp_place(&at, nt * es) : 0,
                  o_hd = h_dl ? tp_place(&at, (size_t)span * es) : 0, o_hp = h_dp ? tp_place(&at, n_dp * es) : 0;
+    const size_t o_fit = tp_place(&at, fit_bytes);
     if (at > c->sTp.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
     HIP_TRY(c, c->sTp.reserve(at));
     char *base = static_cast<char *>(c->sTp.p);
 
     std::vector<unsigned char> tab(tab_bytes, 0);
+    if (fit_tab && !fit_tab->empty()) std::memcpy(tab.data() + o_fit_tab, fit_tab->data(), fit_tab->size());
     {
         int32_t *st = reinterpret_cast<int32_t *>(tab.data() + o_stree), *sp = reinterpret_cast<int32_t *>(tab.data() + o_sparam);
         int64_t *co = reinterpret_cast<int64_t *>(tab.data() + o_coff), *dof = reinterpret_cast<int64_t *>(tab.data() + o_doff);
@@ -189,24 +281,18 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
     }
     HIP_TRY(c, hipMemcpyAsync(base, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     // host inputs are staged once for the whole call, into the buffers a single model call would stage them in
-    Staged sX, sY, sW, sPar;
+    Staged &sX = d->sX, &sY = d->sY, &sW = d->sW, &sPar = d->sPar;
     int rc = DE_OK;
     if (N > 0) {
         if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
         if (o.y && (rc = stage_in(c, c->sY, o.y, (size_t)N * es, &sY))) return rc;
         if (o.w && (rc = stage_in(c, c->sW, o.w, (size_t)N * es, &sW))) return rc;
-        if (any_param && (rc = stage_in(c, c->sParams, tp->params, (size_t)tp->ld_params * (size_t)C * nt * es, &sPar))) return rc;
+        // (the fit reads and writes a parameter block of its own in the pool)
+        if (any_param && !o.fit && (rc = stage_in(c, c->sParams, tp->params, (size_t)tp->ld_params * (size_t)C * nt * es, &sPar))) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the tables and the staged inputs come from pageable memory)
-    void *out_dev = o.out;
-    int64_t ld_dev = o.ld_out;
-    if (h_out) {
-        HIP_TRY(c, c->sTpOut.reserve(nt * (size_t)N * es));
-        out_dev = c->sTpOut.p;
-        ld_dev = N;
-    }
 
-    TreeParamsArgs a;
+    TreeParamsArgs &a = d->a;
     std::memset(&a, 0, sizeof a);
     a.n_trees = p->n_trees; a.n_consts = (int64_t)nc; a.n_classes = C; a.ld_params = tp->ld_params; a.n_params = P;
     a.slot_tree = reinterpret_cast<const int32_t *>(base + o_stree); a.slot_param = reinterpret_cast<const int32_t *>(base + o_sparam);
@@ -221,40 +307,80 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
     a.dloss = grad ? (h_dl ? static_cast<void *>(base + o_hd) : o.dloss) : nullptr;
     a.dparams = grad ? (h_dp ? static_cast<void *>(base + o_hp) : o.dparams) : nullptr;
     a.ok = h_ok ? reinterpret_cast<uint8_t *>(base + o_hok) : ok;
+    d->pool = base; d->base = base + o_base; d->lc = base + o_lc; d->dc = base + o_dc; d->okc = reinterpret_cast<uint8_t *>(base + o_okc);
+    d->o_acc = o_acc; d->acc_bytes = acc_bytes; d->o_fit_tab = o_fit_tab; d->o_fit = o_fit;
+    d->h_ok = h_ok; d->h_loss = h_loss; d->h_dl = h_dl; d->h_dp = h_dp; d->h_out = h_out; d->n_dp = n_dp;
+    return DE_OK;
+}
+
+// The class loop of one evaluation: the accumulators cleared, then every class with a sample, ascending — scatter (base values in real
+// slots, the class's column of a.params in parameter slots), the vector installed, the model entry point on the class's range, the
+// accumulate launch.  Everything it reads is on the device already: it queues work on the context's stream and never waits for it, so
+// de_fit_tree_params_bfgs runs it once per trial.  *patched: the program no longer holds the base vector (also when the loop fails).  The
+// caller sets the program's constants back and launches the finish kernel.
+static int tp_run_classes(de_ctx_t *c, de_program_t *p, TpModel model, const TpPlan &pl, TpDev &d, const int64_t *class_starts, int64_t ldX,
+                          const TpOut &o, void *out_dev, int64_t ld_dev, bool *patched) {
+    TreeParamsArgs &a = d.a;
+    const size_t es = pl.es;
+    HIP_TRY(c, hipMemsetAsync(d.pool + d.o_acc, 0, d.acc_bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(a.acc_ok, 1, pl.nt, c->stream));
+    if (pl.grad) HIP_TRY(c, hipMemsetAsync(d.dc, 0, (size_t)pl.span * es, c->stream)); // (entries no tree owns are never read)
+    int rc = DE_OK;
+    for (int64_t k = 0; k < pl.C && rc == DE_OK; k++) {
+        const int64_t j0 = class_starts[k], n = class_starts[k + 1] - j0;
+        if (n <= 0) continue; // a class without samples: its columns are never read
+        a.cls = k;
+        if (pl.any_param) {
+            HIP_TRY(c, launch_tree_params_scatter(p->dtype, a, c->stream));
+            *patched = true;
+            rc = set_consts_device_impl(p, a.cvec);
+            if (rc != DE_OK) break;
+        }
+        const char *Xk = static_cast<const char *>(d.sX.dev) + (size_t)j0 * (size_t)ldX * es;
+        const char *yk = o.y ? static_cast<const char *>(d.sY.dev) + (size_t)j0 * es : nullptr;
+        const char *wk = o.w ? static_cast<const char *>(d.sW.dev) + (size_t)j0 * es : nullptr;
+        if (model == TP_EVAL) rc = de_eval(c, p, Xk, n, ldX, nullptr, static_cast<char *>(out_dev) + (size_t)j0 * es, ld_dev, d.okc);
+        else if (model == TP_LOSS) rc = de_eval_loss_ex(c, p, Xk, n, ldX, nullptr, yk, wk, o.spec, d.lc, d.okc);
+        else rc = de_eval_loss_grad_ex(c, p, Xk, n, ldX, nullptr, DE_GRAD_CONSTANT, yk, wk, o.spec, d.lc, d.dc, o.dloss_offsets, d.okc);
+        if (rc != DE_OK) break;
+        HIP_TRY(c, launch_tree_params_accumulate(p->dtype, a, c->stream));
+    }
+    return rc;
+}
+
+struct TpNest { // the inner calls leave the timing events alone: the ring sees one call
+    de_ctx *c;
+    explicit TpNest(de_ctx *c_) : c(c_) { c->nested++; }
+    ~TpNest() { c->nested--; }
+};
+
+static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpModel model, const void *X, int64_t N, int64_t ldX,
+                            const de_tree_params_t *tp, const TpOut &o, uint8_t *ok) {
+    TpPlan pl;
+    int rc = tp_check(c, p, what, model, X, N, ldX, tp, o, ok, &pl);
+    if (rc != DE_OK) return rc;
+    if (pl.nt == 0) return DE_OK;
+    TpDev d;
+    rc = tp_setup(c, p, model, X, N, ldX, tp, o, ok, pl, nullptr, 0, &d);
+    if (rc != DE_OK) return rc;
+    const size_t nt = pl.nt, nc = pl.nc, es = pl.es, n_dp = d.n_dp;
+    const std::vector<int64_t> &doff = pl.doff;
+    const bool h_ok = d.h_ok, h_loss = d.h_loss, h_dl = d.h_dl, h_dp = d.h_dp, h_out = d.h_out;
+    TreeParamsArgs &a = d.a;
+    void *out_dev = o.out;
+    int64_t ld_dev = o.ld_out;
+    if (h_out) {
+        HIP_TRY(c, c->sTpOut.reserve(nt * (size_t)N * es));
+        out_dev = c->sTpOut.p;
+        ld_dev = N;
+    }
 
     if (!c->nested) HIP_TRY(c, time_begin(c));
-    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
-        de_ctx *c;
-        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-        ~Nest() { c->nested--; }
-    };
     {
-        Nest nest(c);
-        HIP_TRY(c, hipMemsetAsync(base + o_acc, 0, acc_bytes, c->stream));
-        HIP_TRY(c, hipMemsetAsync(a.acc_ok, 1, nt, c->stream));
-        if (grad) HIP_TRY(c, hipMemsetAsync(base + o_dc, 0, (size_t)span * es, c->stream)); // (entries no tree owns are never read)
-        if (nc > 0 && (rc = de_program_get_consts(p, base + o_base)) != DE_OK) return rc; // the base vector
+        TpNest nest(c);
+        if (nc > 0 && (rc = de_program_get_consts(p, d.base)) != DE_OK) return rc; // the base vector
         bool patched = false;
-        for (int64_t k = 0; k < C && rc == DE_OK; k++) {
-            const int64_t j0 = tp->class_starts[k], n = tp->class_starts[k + 1] - j0;
-            if (n <= 0) continue; // a class without samples: its columns are never read
-            a.cls = k;
-            if (any_param) {
-                HIP_TRY(c, launch_tree_params_scatter(p->dtype, a, c->stream));
-                patched = true;
-                rc = set_consts_device_impl(p, a.cvec);
-                if (rc != DE_OK) break;
-            }
-            const char *Xk = static_cast<const char *>(sX.dev) + (size_t)j0 * (size_t)ldX * es;
-            const char *yk = o.y ? static_cast<const char *>(sY.dev) + (size_t)j0 * es : nullptr;
-            const char *wk = o.w ? static_cast<const char *>(sW.dev) + (size_t)j0 * es : nullptr;
-            uint8_t *okc = reinterpret_cast<uint8_t *>(base + o_okc);
-            if (model == TP_EVAL) rc = de_eval(c, p, Xk, n, ldX, nullptr, static_cast<char *>(out_dev) + (size_t)j0 * es, ld_dev, okc);
-            else if (model == TP_LOSS) rc = de_eval_loss_ex(c, p, Xk, n, ldX, nullptr, yk, wk, o.spec, base + o_lc, okc);
-            else rc = de_eval_loss_grad_ex(c, p, Xk, n, ldX, nullptr, DE_GRAD_CONSTANT, yk, wk, o.spec, base + o_lc, base + o_dc, o.dloss_offsets, okc);
-            if (rc != DE_OK) break;
-            HIP_TRY(c, launch_tree_params_accumulate(p->dtype, a, c->stream));
-        }
+        rc = tp_run_classes(c, p, model, pl, d, tp->class_starts, ldX, o, out_dev, ld_dev, &patched);
         // the program holds its own constants again afterwards (after a failure too)
         const int rc2 = patched ? set_consts_device_impl(p, a.base) : DE_OK;
         if (rc != DE_OK) return rc;
@@ -305,6 +431,188 @@ int de_eval_loss_grad_tree_params(de_ctx_t *c, de_program_t *p, const void *X, i
     TpOut o;
     o.y = y; o.w = w; o.spec = spec; o.loss = loss; o.dloss = dloss; o.dloss_offsets = dloss_offsets; o.dparams = dparams;
     DE_NOTHROW(c, tree_params_impl(c, p, "de_eval_loss_grad_tree_params", TP_LOSS_GRAD, X, N, ldX, tp, o, ok));
+}
+
+// ---- de_fit_tree_params_bfgs: fit_consts_bfgs_impl's loop over each tree's packed vcat(constants, parameters[:]) ----
+// Every evaluation is the class loop above followed by the finish kernel — de_eval_loss_grad_tree_params without its staging, its
+// synchronisation and its copies — and the kernels of de_bfgs.hip see packed vectors only: pack / unpack (de_tree_params.hip) move the
+// values between them and (the base vector's real slots, the pool's parameter block).
+static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                                     const void *y, const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *params_out,
+                                     void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+    const char *what = "de_fit_tree_params_bfgs";
+    TpOut o;
+    o.y = y; o.w = w; o.spec = spec_in; o.fit = true;
+    TpPlan pl;
+    int rc = tp_check(c, p, what, TP_LOSS_GRAD, X, N, ldX, tp, o, ok, &pl);
+    if (rc != DE_OK) return rc;
+    if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "%s: DE_LOSS_PULLBACK is no objective", what);
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t bo = opts ? *opts : defaults;
+    if (const char *why = bfgs_opts_problem(&bo)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+    const size_t nt = pl.nt, nc = pl.nc, es = pl.es;
+    const int64_t C = pl.C, ld = tp->ld_params;
+    const int32_t P = pl.P;
+    if (nt > 0 && !y) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    const size_t n_cells = nt * (size_t)C * (size_t)P; // the unknown parameter entries: every one, used by a leaf or not
+    if (n_cells > 0 && (!tp->params || !params_out)) return fail(c, DE_ERR_INVALID_ARG, "%s: params / params_out is null", what);
+    if (nt == 0) return DE_OK;
+
+    // ---- the geometry of the packed vectors: [widths | packed offsets | B offsets | unknown -> slot or cell] ----
+    std::vector<int32_t> ng(nt);
+    std::vector<int64_t> poff(nt), boff(nt);
+    int64_t npk = 0, bspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        int64_t n_real = 0;
+        for (int64_t s = p->const_off[t]; s < p->const_off[t + 1]; s++) n_real += tp->slot_param[s] < 0 ? 1 : 0;
+        const int64_t G = tpf_unknowns(n_real, P, C);
+        if (G > INT32_MAX) return fail(c, DE_ERR_INVALID_ARG, "%s: tree %lld has %lld unknowns", what, (long long)t, (long long)G);
+        ng[t] = (int32_t)G;
+        poff[t] = npk;
+        boff[t] = bspan;
+        npk += G;
+        if (G >= 1 && G <= BFGS_MAX_ROWS) bspan += G * G;
+    }
+    size_t tat = 0;
+    const size_t t_ng = tp_place(&tat, nt * 4), t_poff = tp_place(&tat, nt * 8), t_boff = tp_place(&tat, nt * 8), t_map = tp_place(&tat, (size_t)npk * 8);
+    std::vector<unsigned char> ftab(tat, 0);
+    std::memcpy(ftab.data() + t_ng, ng.data(), nt * 4);
+    std::memcpy(ftab.data() + t_poff, poff.data(), nt * 8);
+    std::memcpy(ftab.data() + t_boff, boff.data(), nt * 8);
+    {
+        int64_t *map = reinterpret_cast<int64_t *>(ftab.data() + t_map);
+        for (size_t t = 0; t < nt; t++)
+            tpf_map_tree(p->const_off[t + 1] - p->const_off[t], nc > 0 ? tp->slot_param + p->const_off[t] : nullptr, P, C, p->const_off[t],
+                         (int64_t)t * C * P, map + poff[t]);
+    }
+
+    // ---- the fit's part of the pool ----
+    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
+    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok), h_par = n_cells > 0 && !is_device_ptr(params_out);
+    const size_t rows = (size_t)bo.iters + 1, pk = (size_t)npk, blk = nt * (size_t)C * (size_t)ld;
+    size_t at = 0;
+    const size_t o_pw = tp_place(&at, blk * es), o_ca = tp_place(&at, pk * es), o_ct = tp_place(&at, pk * es), o_la = tp_place(&at, nt * es),
+                 o_lt = tp_place(&at, nt * es), o_da = tp_place(&at, pk * es), o_dt = tp_place(&at, pk * es), o_oka = tp_place(&at, nt),
+                 o_okt = tp_place(&at, nt), o_dl = tp_place(&at, (size_t)pl.span * es), o_dp = tp_place(&at, n_cells * es),
+                 o_B = tp_place(&at, (size_t)bspan * 8), o_al = tp_place(&at, nt * 8), o_sl = tp_place(&at, nt * 8), o_p = tp_place(&at, pk * 8),
+                 o_fr = tp_place(&at, nt), o_pr = tp_place(&at, nt), o_hist = h_hist ? tp_place(&at, rows * nt * 8) : 0,
+                 o_acc = h_acc ? tp_place(&at, nt * 4) : 0;
+    TpDev d;
+    rc = tp_setup(c, p, TP_LOSS_GRAD, X, N, ldX, tp, o, ok, pl, &ftab, at, &d);
+    if (rc != DE_OK) return rc;
+    char *fit = d.pool + d.o_fit;
+    const char *tab = d.pool + d.o_fit_tab;
+    void *pw = fit + o_pw; // the parameter block the class loop reads: tp's layout, padding included
+    if (blk > 0 && tp->params) {
+        HIP_TRY(c, hipMemcpyAsync(pw, tp->params, blk * es, is_device_ptr(tp->params) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        if (!is_device_ptr(tp->params)) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (pageable memory)
+    }
+    TreeParamsArgs &ta = d.a;
+    ta.params = pw;
+    ta.dloss = fit + o_dl;
+    ta.dparams = fit + o_dp;
+    double *hist = history ? (h_hist ? reinterpret_cast<double *>(fit + o_hist) : history) : nullptr;
+    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(fit + o_acc) : n_accept) : nullptr;
+    BfgsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = reinterpret_cast<const int32_t *>(tab + t_ng);
+    a.coff = reinterpret_cast<const int64_t *>(tab + t_poff);
+    a.boff = reinterpret_cast<const int64_t *>(tab + t_boff);
+    a.consts_acc = fit + o_ca; a.loss_acc = fit + o_la; a.dloss_acc = fit + o_da; a.ok_acc = reinterpret_cast<uint8_t *>(fit + o_oka);
+    void *lT = fit + o_lt, *dT = fit + o_dt;
+    uint8_t *okT = reinterpret_cast<uint8_t *>(fit + o_okt);
+    a.consts_trial = fit + o_ct; a.loss_trial = lT; a.dloss_trial = dT; a.ok_trial = okT;
+    a.B = reinterpret_cast<double *>(fit + o_B); a.alpha = reinterpret_cast<double *>(fit + o_al);
+    a.slope = reinterpret_cast<double *>(fit + o_sl); a.p = reinterpret_cast<double *>(fit + o_p);
+    a.fresh = reinterpret_cast<uint8_t *>(fit + o_fr); a.produced = reinterpret_cast<uint8_t *>(fit + o_pr);
+    a.step0 = bo.step0; a.shrink = bo.shrink; a.c1 = bo.c1; a.curv = bo.curv;
+    a.n_accept = acc;
+    TreeParamsFitArgs fx; // the unknowns' values: (base vector, parameter block)
+    fx.n_unknowns = npk; fx.ld = ld; fx.n_params = P;
+    fx.map = reinterpret_cast<const int64_t *>(tab + t_map);
+    fx.packed = nullptr; fx.slots = d.base; fx.cells = pw;
+    TreeParamsFitArgs fg = fx; // their gradient: (dloss, dparams)
+    fg.ld = P; fg.slots = ta.dloss; fg.cells = ta.dparams;
+
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    const de_loss_spec_t spec = *spec_in;
+    o.spec = &spec;
+    {
+        TpNest nest(c);
+        bool patched = false, begun = false;
+        // one evaluation at (d.base, pw): de_eval_loss_grad_tree_params' launches, then the gradient packed
+        auto evaluate = [&](void *l, void *g, uint8_t *k, bool install) -> int {
+            ta.loss = l;
+            ta.ok = k;
+            if (install && !pl.any_param && nc > 0) { // (no parameter slot: the class loop installs nothing)
+                patched = true;
+                const int r = set_consts_device_impl(p, d.base);
+                if (r != DE_OK) return r;
+            }
+            const int r = tp_run_classes(c, p, TP_LOSS_GRAD, pl, d, tp->class_starts, ldX, o, nullptr, 0, &patched);
+            if (r != DE_OK) return r;
+            HIP_TRY(c, launch_tree_params_finish(p->dtype, ta, c->stream));
+            fg.packed = g;
+            HIP_TRY(c, launch_tree_params_pack(p->dtype, fg, c->stream));
+            return DE_OK;
+        };
+        auto body = [&]() -> int {
+            if (nc > 0) {
+                const int r = de_program_get_consts(p, d.base); // the base vector: the start of the real constants
+                if (r != DE_OK) return r;
+            }
+            int r = evaluate(a.loss_acc, a.dloss_acc, a.ok_acc, false);
+            if (r != DE_OK) return r;
+            fx.packed = a.consts_acc;
+            HIP_TRY(c, launch_tree_params_pack(p->dtype, fx, c->stream));
+            HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream));
+            HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist, c->stream));
+            const bool loop = N > 0 && bo.iters > 0 && npk > 0;
+            if (!loop) // (no sample or no unknown: nothing can be accepted, every row of the history is the first)
+                for (size_t r2 = 1; r2 < rows && hist; r2++) HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist + r2 * nt, c->stream));
+            if (!loop) return DE_OK;
+            begun = true;
+            for (int32_t it = 0; it < bo.iters; it++) {
+                HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream));
+                fx.packed = a.consts_trial;
+                HIP_TRY(c, launch_tree_params_unpack(p->dtype, fx, c->stream));
+                r = evaluate(lT, dT, okT, true);
+                if (r != DE_OK) return r;
+                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
+                HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
+            }
+            return DE_OK;
+        };
+        rc = body();
+        // the program holds the accepted real constants afterwards and its parameter slots their base values (after a failure too: the
+        // last accepted ones); the parameter block holds the accepted parameters
+        int rc2 = DE_OK;
+        if (begun) {
+            fx.packed = a.consts_acc;
+            if (launch_tree_params_unpack(p->dtype, fx, c->stream) != hipSuccess) rc2 = fail(c, DE_ERR_HIP, "%s: the unpack launch failed", what);
+        }
+        if (patched && rc2 == DE_OK) rc2 = set_consts_device_impl(p, d.base);
+        if (rc != DE_OK) return rc;
+        if (rc2 != DE_OK) return rc2;
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (n_cells > 0) { // the accepted parameters in tp's layout; padding entries are not written
+        const hipMemcpyKind kind = h_par ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (ld == P) HIP_TRY(c, hipMemcpyAsync(params_out, pw, blk * es, kind, c->stream));
+        else HIP_TRY(c, hipMemcpy2DAsync(params_out, (size_t)ld * es, pw, (size_t)ld * es, (size_t)P * es, nt * (size_t)C, kind, c->stream));
+    }
+    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, a.loss_acc, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ok, a.ok_acc, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_par || h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_tree_params_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp, const void *y,
+                            const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *params_out, void *loss, uint8_t *ok,
+                            double *history, int32_t *n_accept) {
+    DE_NOTHROW(c, fit_tree_params_bfgs_impl(c, p, X, N, ldX, tp, y, w, spec, opts, params_out, loss, ok, history, n_accept));
 }
 
 } // extern "C"

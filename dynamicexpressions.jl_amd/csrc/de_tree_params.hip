@@ -3,12 +3,16 @@
 //   de_tree_params_scatter_kernel     the constant vector of one class: base values in real slots, the tree's own column in parameter slots
 //   de_tree_params_accumulate_kernel  one class's per-tree results added into double accumulators, its dparams cells formed, flags ANDed
 //   de_tree_params_finish_kernel      the accumulators in the element type, NaN where the tree's flag is 0
+//   de_tree_params_pack_kernel        de_fit_tree_params_bfgs (§4.4.12): the packed unknowns gathered from (slot vector, parameter cells) —
+//                                     pack_x from (constants, parameter block), pack_g from (dloss, dparams)
+//   de_tree_params_unpack_kernel      ... and scattered back: real constant slots and parameter cells, nothing else
 // One thread per entry, every entry owned by one thread: plain vector stores, no atomics; the order of the additions is the stream
 // order of the launches (classes ascending).  The arithmetic is de_tree_params.h, the code the host hook runs.
 #include "../../include/de_hip.h"
 
 #include "de_tree_params_dev.h"
 #include "de_tree_params.h"
+#include "de_tree_params_fit.h"
 
 namespace de {
 
@@ -68,6 +72,22 @@ __global__ void __launch_bounds__(256) de_tree_params_finish_kernel(TreeParamsAr
     static_cast<T *>(a.dparams)[i] = tp_finish<T>(a.acc_dparams[i], a.acc_ok[i / per_tree]);
 }
 
+// (consecutive threads read consecutive table entries and packed elements; the other side is slot order / cell order, so it is
+// consecutive too inside a tree's constants and inside its matrix)
+template <typename T>
+__global__ void __launch_bounds__(256) de_tree_params_pack_kernel(TreeParamsFitArgs a) {
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= a.n_unknowns) return;
+    static_cast<T *>(a.packed)[u] = tpf_load(a.map[u], static_cast<const T *>(a.slots), static_cast<const T *>(a.cells), a.n_params, a.ld);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) de_tree_params_unpack_kernel(TreeParamsFitArgs a) {
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= a.n_unknowns) return;
+    tpf_store(a.map[u], static_cast<const T *>(a.packed)[u], static_cast<T *>(a.slots), static_cast<T *>(a.cells), a.n_params, a.ld);
+}
+
 #define DE_TP_LAUNCH(KERNEL, COUNT)                                                                                     \
     const int64_t n_ = (COUNT);                                                                                         \
     if (n_ <= 0) return hipSuccess;                                                                                     \
@@ -84,6 +104,12 @@ hipError_t launch_tree_params_accumulate(int dtype, const TreeParamsArgs &a, hip
 }
 hipError_t launch_tree_params_finish(int dtype, const TreeParamsArgs &a, hipStream_t stream) {
     DE_TP_LAUNCH(de_tree_params_finish_kernel, a.n_trees + (a.dloss ? a.n_consts + a.n_trees * a.n_classes * a.n_params : 0));
+}
+hipError_t launch_tree_params_pack(int dtype, const TreeParamsFitArgs &a, hipStream_t stream) {
+    DE_TP_LAUNCH(de_tree_params_pack_kernel, a.n_unknowns);
+}
+hipError_t launch_tree_params_unpack(int dtype, const TreeParamsFitArgs &a, hipStream_t stream) {
+    DE_TP_LAUNCH(de_tree_params_unpack_kernel, a.n_unknowns);
 }
 
 } // namespace de

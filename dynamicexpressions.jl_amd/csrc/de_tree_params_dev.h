@@ -31,5 +31,19 @@ hipError_t launch_tree_params_accumulate(int dtype, const TreeParamsArgs &a, hip
 // the accumulators rounded to the element type, NaN where the tree's flag is 0; ok = acc_ok
 hipError_t launch_tree_params_finish(int dtype, const TreeParamsArgs &a, hipStream_t stream);
 
+// de_fit_tree_params_bfgs: the packed vector of unknowns of every tree, n_unknowns entries in all, and where each
+// lives (map: de_tree_params_fit.h).  `slots`: a vector in the program's slot layout; `cells`: parameter cells, columns ld apart.
+struct TreeParamsFitArgs {
+    int64_t n_unknowns, ld;
+    int32_t n_params;
+    const int64_t *map;
+    void *packed;
+    void *slots, *cells;
+};
+// packed[u] = slots / cells at map[u]: pack_x with (constants, parameter block), pack_g with (dloss, dparams; ld = n_params)
+hipError_t launch_tree_params_pack(int dtype, const TreeParamsFitArgs &a, hipStream_t stream);
+// slots / cells at map[u] = packed[u]; parameter slots and padding are not written
+hipError_t launch_tree_params_unpack(int dtype, const TreeParamsFitArgs &a, hipStream_t stream);
+
 } // namespace de
 #endif

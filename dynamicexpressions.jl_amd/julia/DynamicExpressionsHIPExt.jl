@@ -1349,6 +1349,53 @@ function eval_parametric_population_loss_grad(
     return lossv, dconsts, [dp[:, :, t] for t in 1:pop.n_trees], ok .!= 0x00
 end
 
+"""
+    fit_parametric_population_bfgs!(pp, X, y, classes; parameters=pp.parameters, weights=nothing, iters=20, step0=1.0, shrink=0.5,
+                                    c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0, grouped=false)
+        -> (constants::Vector{Vector{T}}, parameters::Array{T,3}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
+
+BFGS over every expression's `vcat(constants, parameters[:])` — the vector the reference optimises
+(test/test_parametric_expression.jl:140-199) — the whole loop in one library call (`de_fit_tree_params_bfgs`, DESIGN.md §4.4.12).  The
+real constants start from what `pp` holds, the parameters from `parameters`; afterwards `pp` holds the accepted constants and
+`pp.parameters` the accepted parameters, which are returned with their losses and flags; `history[:, r]` are the accepted losses after
+`r - 1` iterations.  An expression with more than `de_bfgs_max_rows()` = 32 unknowns, without unknowns or incomplete at the start keeps
+its values.
+"""
+function fit_parametric_population_bfgs!(
+    pp::HIPParametricPopulation{T}, X::Matrix{T}, y::Vector{T}, classes::Vector{Int64}; parameters::Array{T,3}=pp.parameters,
+    weights::Union{Nothing,Vector{T}}=nothing, iters::Integer=20, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8,
+    loss::Symbol=:L2, loss_param::Real=0.0, grouped::Bool=false,
+) where {T}
+    loss === :pullback && throw(ArgumentError("fit_parametric_population_bfgs!: :pullback is the cotangent of a pullback, not an objective"))
+    pop = pp.pop
+    F, N = size(X)
+    P, C, nt = size(parameters)
+    @assert F >= pop.n_features && length(y) == N && length(classes) == N && P == pp.n_params && nt == pop.n_trees
+    @assert weights === nothing || length(weights) == N
+    X, starts, _, (y, weights) = group_by_class(X, classes, C, grouped, y, weights)
+    opts = Ref(BfgsOpts(Int32(iters), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
+    spec = loss_spec(loss, loss_param)
+    fitted = copy(parameters)               # params_out: the start is read before anything is written, so it may be the same block
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_accept = zeros(Int32, pop.n_trees)
+    sp, offs = pp.slot_param, pp.slot_off
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights fitted starts sp lossv ok history n_accept begin
+            tp = Ref(TreeParams(pointer(fitted), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
+            ccall((:de_fit_tree_params_bfgs, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, tp, y, weights === nothing ? C_NULL : pointer(weights), spec, opts, fitted, lossv, ok, history, n_accept)
+        end)
+    end
+    slots = get_population_constants!(Vector{T}(undef, length(sp)), pop)
+    constants = [T[slots[s] for s in (offs[t] + 1):offs[t + 1] if sp[s] < 0] for t in 1:pop.n_trees]
+    pp.parameters = fitted
+    return constants, fitted, lossv, ok .!= 0x00, history, n_accept
+end
+
 """Forward-mode gradient of one tree: `(evaluation, gradient(n_grad × N), complete)` like
 `eval_grad_tree_array(tree, cX, operators; variable)` (src/EvaluateDerivative.jl:193-228); a GraphNode's shared constant has
 ONE row (the sum over its occurrences)."""

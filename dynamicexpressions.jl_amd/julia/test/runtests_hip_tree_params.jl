@@ -66,4 +66,14 @@ const HIP = DynamicExpressionsHIPExt
     perm = sortperm(classes; alg=MergeSort)
     l4, _, dp4, _ = HIP.eval_parametric_population_loss_grad(pp, X[:, perm], true_out[perm], classes[perm]; grouped=true)
     @test l4 == l2 && dp4 == dparams
+
+    # the reference's fit (:180-199) in one library call (de_fit_tree_params_bfgs, DESIGN.md §4.4.12): from zeros, 60 iterations
+    consts, fitted, lf, okf, history, n_accept = HIP.fit_parametric_population_bfgs!(pp, X, true_out, classes; iters=60)
+    @test all(okf) && all(isempty, consts) && size(history) == (2, 61) && pp.parameters === fitted
+    @test history[1, 1] > 0.1 && lf[1] < 1e-5             # init_loss, result.minimum
+    @test isapprox(fitted[:, :, 1], true_parameters; rtol=sqrt(eps(Float64)))
+    @test lf[2] == 0 && fitted[:, :, 2] == true_parameters && n_accept[2] == 0 && n_accept[1] >= 3
+    @test all(diff(history[1, :]) .<= 0)                  # only steps that lower the loss are taken
+    l5, _, _, _ = HIP.eval_parametric_population_loss_grad(pp, X, true_out, classes)
+    @test l5 == lf                                        # the evaluation at the result reproduces the loss
 end

@@ -97,7 +97,9 @@ extern "C" {
  *      §4.4.10), under every loss kind that has a gradient, for trees of up to 32 constants; DE_F32 / DE_F64.
  *      (o) de_tape_params_to_consts, de_eval_tree_params, de_eval_loss_tree_params, de_eval_loss_grad_tree_params (with de_tree_params_t)
  *      and the host-only hook de_tree_params_accumulate_host: a population whose trees each own their parameter matrix, served one class
- *      segment at a time as a non-parametric program whose parameter slots are patched on the device; DE_F32 / DE_F64. */
+ *      segment at a time as a non-parametric program whose parameter slots are patched on the device; DE_F32 / DE_F64.
+ *      (p) de_fit_tree_params_bfgs and the host-only hooks de_tree_params_pack_host / de_tree_params_unpack_host: BFGS over each tree's
+ *      vcat(constants, parameters[:]) of such a population on the device, up to 32 unknowns per tree; DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -841,7 +843,8 @@ int de_fit_consts_lm_scaled_wide(de_ctx_t *ctx, de_program_t *prog, const void *
  * de_program_create_cse programs, constant rows that differ from the constants); DE_ERR_INVALID_ARG for a spec de_loss_spec_check(spec, 1)
  * refuses, DE_LOSS_PULLBACK (no objective), null y or ok on a non-empty population, iters < 0, reserved != 0, step0 / c1 / curv not
  * finite and positive, shrink outside (0, 1).
- * Not served: programs made by de_program_create_cse, more than 32 constants, the scaled objective, parameter rows. */
+ * Not served: programs made by de_program_create_cse, more than 32 constants, the scaled objective, parameter rows (the per-tree
+ * parameter matrices of §4.4.11 are fitted by de_fit_tree_params_bfgs). */
 typedef struct de_bfgs_opts {
     int32_t iters;    /* iterations: one direction, one evaluation and one accept each */
     int32_t reserved; /* 0 */
@@ -932,6 +935,45 @@ int de_eval_loss_grad_tree_params(de_ctx_t *ctx, de_program_t *prog, const void 
 int de_tree_params_accumulate_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
                                    const uint8_t *class_used, const void *loss_c, const void *dloss_c, const uint8_t *ok_c,
                                    void *loss, void *dloss, void *dparams, uint8_t *ok);
+
+/* ---- BFGS over constants AND parameters of a per-tree parametric population, on the device -------------------
+ * The reference fits a ParametricExpression by optimising vcat(constants, parameters[:]) (test/test_parametric_expression.jl:140-199).
+ * THE UNKNOWNS of tree t are that vector: its real constant slots (slot_param[s] < 0) in slot order, then all n_params * n_classes
+ * entries of its matrix, column-major — unknown n_real + c*n_params + p is params[p, c, t].  Every entry is an unknown, whether a leaf
+ * uses it or its class has a sample or not (the gradient of an unused entry is dparams' 0: it never moves).  G_t = n_real_t +
+ * n_params*n_classes; a tree is fitted where 1 <= G_t <= de_bfgs_max_rows() and its first evaluation is complete.
+ *
+ * de_fit_tree_params_bfgs: de_fit_consts_bfgs' loop with de_eval_loss_grad_tree_params as the evaluator.  The real constants start
+ * from what the program holds, the parameters from tp->params; the gradient of the vector is double(dloss[real slot]) followed by
+ * double(dparams cell); direction, trial T(double(x) + alpha p), Armijo accept, update, has / produced / fresh / alpha / n_accept are
+ * those documented at de_fit_consts_bfgs.  Kernels gather the unknowns into packed vectors and scatter the trials back into the base
+ * vector and a device-resident parameter block; the tables and host inputs are staged once, the stream is not synchronised inside the
+ * iterations and no constant, gradient or parameter reaches the host.  Afterwards:
+ *   - the program holds the accepted real constants, its parameter slots their base values again (as de_eval_loss_grad_tree_params
+ *     leaves them), after a failure too;
+ *   - params_out holds the accepted parameters in tp's layout (ld_params; padding entries are not written); it may be tp->params, a
+ *     host or a device pointer, and NULL only when n_params*n_classes*n_trees == 0;
+ *   - de_eval_loss_grad_tree_params with params_out reproduces loss[t] bit for bit; a tree that is not fitted keeps every bit of its
+ *     constants and parameters;
+ *   - loss (may be NULL), ok, history ((iters + 1) x n_trees doubles, may be NULL), n_accept (may be NULL): as de_fit_consts_bfgs.
+ * iters == 0, N == 0 or no unknown anywhere: nothing is accepted, every history row is the first.
+ * Refusals, before any output, constant or parameter is touched: everything de_eval_loss_grad_tree_params refuses; what
+ * de_fit_consts_bfgs refuses about spec and opts (DE_LOSS_PULLBACK, iters < 0, reserved != 0, step0 / c1 / curv not finite and
+ * positive, shrink outside (0, 1)); null y or ok on a non-empty population; null tp->params or params_out where a parameter entry exists.
+ * Not served: more than 32 unknowns per tree, LM / Gauss-Newton over parameters, the scaled objective, per-sample classes.
+ *
+ * de_tree_params_pack_host / de_tree_params_unpack_host: the index map of ONE tree on the host (no HIP call; csrc/de_tree_params_fit.h,
+ * the code the kernels run).  slot_values: n_slots entries (parameter slots are skipped on pack and left untouched on unpack);
+ * params_tree: ld_params * n_classes entries (padding is neither read nor written); x: G entries.  pack returns G or -status; unpack
+ * returns DE_OK or a status.  A null pointer where one is needed, a negative count, ld_params < n_params or a slot_param entry outside
+ * [-1, n_params): DE_ERR_INVALID_ARG, nothing written. */
+int de_fit_tree_params_bfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                            const void *y, const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *params_out,
+                            void *loss, uint8_t *ok, double *history, int32_t *n_accept);
+int de_tree_params_pack_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
+                             int64_t ld_params, const void *slot_values, const void *params_tree, void *x);
+int de_tree_params_unpack_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
+                               int64_t ld_params, const void *x, void *slot_values, void *params_tree);
 
 /* The `dX` of the ChainRules pullback of eval_tree_array (EvalPullback, src/ChainRules.jl:56-77):
  *   dX_t[f, j] = d tree_t(x_j) / d x_f * dY[j]      (`dX = dX_dY .* reshape(dY, 1, length(dY))`, :74)
