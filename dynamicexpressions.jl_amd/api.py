@@ -62,6 +62,7 @@ EXPORTS = [
     "de_tape_params_to_consts", "de_eval_tree_params", "de_eval_loss_tree_params", "de_eval_loss_grad_tree_params",
     "de_tree_params_accumulate_host",
     "de_fit_tree_params_bfgs", "de_tree_params_pack_host", "de_tree_params_unpack_host",
+    "de_lower_tape_assured_fact",
 ]
 
 
@@ -633,6 +634,9 @@ def library() -> C.CDLL:
     if hasattr(lib, "de_lower_tape_assured_parts"):
         lib.de_lower_tape_assured_parts.restype = i64
         lib.de_lower_tape_assured_parts.argtypes = [vp, i64, vp, i64, i32, u32, C.c_double, u32, vp, i64]
+    if hasattr(lib, "de_lower_tape_assured_fact"):  # (absent from a library built before the assured tiers)
+        lib.de_lower_tape_assured_fact.restype = i64
+        lib.de_lower_tape_assured_fact.argtypes = [vp, i64, vp, i64, i32, u32, C.c_double, C.c_double, u32, vp, i64]
     lib.de_lower_tape_grad.restype = i64
     lib.de_lower_tape_grad.argtypes = [C.c_int, vp, i64, vp, i64, i32, i32, u32, C.c_int, C.c_int, vp, i64, vp]
     lib.de_eval.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, i64, vp]
@@ -969,17 +973,22 @@ def lower_tape_stage(tape, consts, n_features: int, stage: int, n_params: int = 
     return w[:int(n)].reshape(-1, 4)
 
 
-def lower_tape_assured(tape, consts, n_features: int, xmax: float = 64.0, options: int = 7, parts: Optional[int] = None) -> np.ndarray:
+def lower_tape_assured(tape, consts, n_features: int, xmax: float = 64.0, options: int = 7, parts: Optional[int] = None,
+                       amin: Optional[float] = None) -> np.ndarray:
     """Host-only: the interval pass of the assured stream over one float32 tape (``de_lower_tape_assured``): [n fused instructions, 6]
     float64 {lo, hi, amin, finite, assured handler id, elision bits} — the accumulator behind each instruction of the stage-3 words.
-    ``parts``: the parts of the pass (``de_lower_tape_assured_parts``; a ``DE_ASSURED_PARTS`` mask); None: the first three, 7."""
+    ``parts``: the parts of the pass (``de_lower_tape_assured_parts``; a ``DE_ASSURED_PARTS`` mask); None: the first three, 7.
+    ``amin``: the lower bound of the feature fact, amin <= |x| <= xmax (``de_lower_tape_assured_fact``: the pass of a tight tier);
+    None: 2^-39 with part 8, 2^-40 without."""
     lib = library()
     tape = np.ascontiguousarray(tape)
     consts = np.ascontiguousarray(consts, dtype=np.float32)
     cp = consts.ctypes.data if consts.size else None
     args = (tape.ctypes.data, len(tape), cp, consts.size, n_features, options, float(xmax))
     fn = lib.de_lower_tape_assured
-    if parts is not None:
+    if amin is not None:
+        fn, args = lib.de_lower_tape_assured_fact, args + (float(amin), 7 if parts is None else int(parts))
+    elif parts is not None:
         fn, args = lib.de_lower_tape_assured_parts, args + (int(parts),)
     n = fn(*args, None, 0)
     if n < 0:
@@ -1264,13 +1273,16 @@ class Population:
         return w[:int(got)].reshape(-1, 4)
 
     def meta(self, tree: int) -> dict:
-        w = np.zeros(7, dtype=np.uint32)
-        library().de_program_dump(self._h, tree, w.ctypes.data, 7, 1)
+        w = np.zeros(8, dtype=np.uint32)
+        got = library().de_program_dump(self._h, tree, w.ctypes.data, 8, 1)
+        if got < 8:  # (a library built before the assured tiers: seven words)
+            w[7] = w[5]
         return dict(n_slots=int(w[0]), host_ok_eval=bool(w[1]), host_ok_grad=bool(w[2]), uses_params=bool(w[3]), waves=int(w[4]),
-                    assured=bool(w[5]), assured_valid=bool(w[6]))
+                    assured=bool(w[5]), assured_valid=bool(w[6]), assured_tiers=int(w[7]))
 
     def dump_stage(self, tree: int, which: int) -> np.ndarray:
-        """``de_program_dump`` words of one tree: which = 2 bound, 3 fused, 4 fused with the assured stream's handler ids — test hook."""
+        """``de_program_dump`` words of one tree: which = 2 bound, 3 fused, 4 fused with the assured stream's handler ids, 5 with its tight tier's
+        (empty: the program has one tier) — test hook."""
         lib = library()
         n = lib.de_program_dump(self._h, tree, None, 0, which)
         w = np.zeros(max(int(n), 1), dtype=np.uint32)

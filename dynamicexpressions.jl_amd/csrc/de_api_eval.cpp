@@ -327,8 +327,10 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     a.waves = p->waves; // (wave groups: de_api_internal.h)
     a.wave_slots = p->n_slots;
     a.var_stride = p->var_stride;
-    a.assured = p->assured && p->assured_valid && p->var_stride != 0; // (the assured stream: de_api_internal.h)
+    a.assured = p->assured && p->assured_valid && p->var_stride != 0 ? p->assured_tiers : 0; // (the assured streams: de_api_internal.h)
     a.assured_xmax = (float)p->assured_xmax;
+    a.assured_tight_xmax = (float)p->assured_tight_xmax;
+    a.assured_tight_amin = (float)p->assured_tight_amin;
     if (cr) { // the certificate pass: the un-elided program through the flat-switch kernel's CERT variant, nothing stored
         a.code = p->d_cert_code;
         a.code_off = p->d_cert_off;

@@ -213,6 +213,15 @@ struct de_program {
     double assured_xmax = 64.0;
     uint32_t assured_parts = 0; // ASSURED_PART_* the pass may use (DE_ASSURED_PARTS, read with DE_ASSURED)
     std::vector<uint32_t> aids;
+    // TIERS: tier 1 is the stream above (variant 1); tier 2 is ONE more variant (variant 2, the second ccode.size() records of ccode_w) made by
+    // the same pass under the TIGHT feature fact |x| in [assured_tight_amin, assured_tight_xmax] (de_bind.h assure_tree_fact; aids2 its twin
+    // ids, always a superset of tier 1's elisions).  A tile runs the tightest stream whose fact it passes.  assured_tiers_cfg: what the program
+    // may build (DE_ASSURED_TIERS, 1 or 2; read and inherited like assured_cfg); assured_tiers: what it has — 2 only where the tight pass names
+    // an id the wide pass does not, else 1 (0: no assured stream).
+    // assured_tiers_room: the tiers the device arena was sized for (0: not allocated yet) — a re-bind of the same program keeps that many.
+    int assured_tiers_cfg = 2, assured_tiers = 0, assured_tiers_room = 0;
+    double assured_tight_xmax = 8.0, assured_tight_amin = 0x1p-19;
+    std::vector<uint32_t> aids2;
     uint64_t end_handler = 0;
     uint64_t endv_handler[TOPX_ENDV_COUNT] = {0}; // "last instruction + end of tree" variants (de_bind.h topx_endv_of)
     bool threaded = false;

@@ -190,23 +190,46 @@ static uint32_t assured_parts_env() {
     const int v = ap && *ap ? atoi(ap) : (int)ASSURED_PARTS_SHIPPED;
     return (uint32_t)v & ASSURED_PARTS_ALL;
 }
+// The tight tier's fact (de_api_internal.h assured_tiers): DE_ASSURED_TIGHT_XMAX / DE_ASSURED_TIGHT_AMIN, rounded to Float32 like the wide
+// bound; the defaults when unset or out of range, and never wider than the wide fact [2^-39, xmax] (a tight fact equal to the wide one
+// proves nothing more: such a program builds one tier).  DE_ASSURED_TIERS=1: one tier, the behaviour before tiers, for A/B runs.
+static void assured_tight_env(double xmax, double *txmax, double *tamin) {
+    const char *ax = getenv("DE_ASSURED_TIGHT_XMAX"), *am = getenv("DE_ASSURED_TIGHT_AMIN");
+    double tx = ax && *ax ? (double)(float)atof(ax) : ASSURED_TIGHT_XMAX, ta = am && *am ? (double)(float)atof(am) : ASSURED_TIGHT_AMIN;
+    if (!(tx >= 0x1p-40 && tx <= 0x1p100)) tx = ASSURED_TIGHT_XMAX;
+    if (!(ta >= 0x1p-39 && ta <= 0x1p100)) ta = ASSURED_TIGHT_AMIN;
+    tx = std::min(tx, xmax);
+    *txmax = tx;
+    *tamin = std::min(ta, tx);
+}
+static int assured_tiers_env() {
+    const char *at = getenv("DE_ASSURED_TIERS");
+    return at && *at == '1' ? 1 : 2;
+}
 static int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr) {
     p->threaded = false;
     p->waves = 1;
     p->var_stride = 0;
     p->ccode_w.clear();
     p->assured = p->assured_valid = false;
+    p->assured_tiers = 0;
     p->aids.clear();
+    p->aids2.clear();
     if (p->assured_cfg == 0) { // DE_ASSURED / DE_ASSURED_XMAX: read once per program (an update keeps what its program was created with)
         if (ru && ru->old && ru->old->assured_cfg != 0) {
             p->assured_cfg = ru->old->assured_cfg;
             p->assured_xmax = ru->old->assured_xmax;
             p->assured_parts = ru->old->assured_parts;
+            p->assured_tiers_cfg = ru->old->assured_tiers_cfg;
+            p->assured_tight_xmax = ru->old->assured_tight_xmax;
+            p->assured_tight_amin = ru->old->assured_tight_amin;
         } else {
             const char *as = getenv("DE_ASSURED");
             p->assured_parts = assured_parts_env();
             p->assured_cfg = ((as && *as == '0') || p->assured_parts == 0) ? -1 : 1;
             p->assured_xmax = assured_xmax_env();
+            p->assured_tiers_cfg = assured_tiers_env();
+            assured_tight_env(p->assured_xmax, &p->assured_tight_xmax, &p->assured_tight_amin);
         }
     }
     dbg_lap(nullptr);
@@ -449,8 +472,14 @@ static inline void patch_chained_imm(de_program *p, int32_t c, uint32_t lo, uint
 // fbcode holds them NOW), then every instruction's handler — its twin's where a test is elided, its own otherwise — named where
 // make_chained names it: in the record in front (the first instruction's: in the header record, and in the last instruction record of an
 // end-fused predecessor).  A tree writes records no other tree writes: tree ranges may run on the host threads.
-static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb, int64_t te, bool touched_only = false) {
-    BoundInstr *cw = p->ccode_w.data();
+// tier 1: the wide fact, variant 1, aids; tier 2: the tight fact, variant 2, aids2 (de_api_internal.h assured_tiers).
+static void assure_program_tree(const de_program *p, int tier, int32_t i0, int32_t i1, AssuredInstr *info) {
+    if (tier == 2) assure_tree_fact(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_tight_xmax, p->assured_tight_amin, info, p->assured_parts);
+    else assure_tree(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_xmax, info, p->assured_parts);
+}
+static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb, int64_t te, bool touched_only = false, int tier = 1) {
+    BoundInstr *cw = p->ccode_w.data() + (size_t)(tier - 1) * p->ccode.size();
+    std::vector<uint32_t> &aids = tier == 2 ? p->aids2 : p->aids;
     std::vector<AssuredInstr> info;
     auto name_next = [](BoundInstr &r, uint64_t handler) { r.lo = (uint32_t)handler; r.hi = (uint32_t)(handler >> 32); }; // (Float32 records)
     auto ev_of = [&](int64_t t) -> int {
@@ -462,12 +491,12 @@ static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb,
         if (i1 <= i0) continue;
         if (touched_only && p->const_off[(size_t)t + 1] == p->const_off[(size_t)t]) continue; // (a set of the constants touches the trees that have some)
         info.resize((size_t)(i1 - i0));
-        assure_tree(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_xmax, info.data(), p->assured_parts);
+        assure_program_tree(p, tier, i0, i1, info.data());
         const size_t h = (size_t)p->ccode_off[(size_t)t];
         const int ev = ev_of(t);
         for (int32_t i = i0; i < i1; i++) {
             const uint32_t id = info[(size_t)(i - i0)].id;
-            p->aids[(size_t)i] = id;
+            aids[(size_t)i] = id;
             // (an end-fused last instruction: the end-fused twin of its assured id, or the end-fused handler of the guarded stream)
             const uint64_t handler = (i == i1 - 1 && ev >= 0) ? (topx_enda_of(id) >= 0 && id != p->fbcode[(size_t)i].bop ? table[TOPX_ENDA_BASE + (uint32_t)topx_enda_of(id)] : p->endv_handler[ev])
                                      : id == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[id];
@@ -481,9 +510,22 @@ static void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb,
 }
 // ccode_w = the guarded stream with the assured handler words; var_stride as a wave group's variants lie (de_program_create sizes the arena by it)
 static void make_assured(de_program *p, const uint64_t *table) {
+    const bool tight = p->assured_tiers_room ? p->assured_tiers_room >= 2
+                                             : p->assured_tiers_cfg >= 2 && (p->assured_tight_xmax < p->assured_xmax || p->assured_tight_amin > assured_wide_amin(p->assured_parts));
     p->ccode_w = p->ccode;
+    if (tight) p->ccode_w.insert(p->ccode_w.end(), p->ccode.begin(), p->ccode.end()); // variant 2: the tight tier
     p->aids.assign(p->fbcode.size(), 0u);
-    parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) { assured_link_trees(p, table, tb, te); });
+    p->aids2.assign(tight ? p->fbcode.size() : 0, 0u);
+    parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) {
+        assured_link_trees(p, table, tb, te);
+        if (tight) assured_link_trees(p, table, tb, te, false, 2);
+    });
+    // (a tight pass that names no id the wide pass does not name: one tier — no third variant to keep, upload and re-link)
+    if (tight && !p->assured_tiers_room && p->aids2 == p->aids) {
+        p->ccode_w.resize(p->ccode.size());
+        p->aids2.clear();
+    }
+    p->assured_tiers = p->aids2.empty() ? 1 : 2;
     p->var_stride = (int64_t)(p->bcode.size() + (size_t)p->n_trees + 2);
     p->assured = p->assured_valid = true;
 }
@@ -1217,7 +1259,8 @@ static int create_impl(de_ctx_t *ctx, int dtype, const de_tape_node_t *nodes, co
         // compaction control ints | initial flags], one allocation from the context's pool; a small program (the one-tree call of
         // de_eval_tree_array) goes up in ONE copy from a zero-filled host image, a large one in one memset + three copies.
         // (wave groups: `waves` variants of the stream var_stride = cbytes / 16 records apart, and as much room again for their compacted forms)
-        const size_t nvar = p->threaded && p->var_stride ? (p->assured ? 2 : (size_t)p->waves) : 1; // (the assured stream: one more variant of a one-wave program)
+        const size_t nvar = p->threaded && p->var_stride ? (p->assured ? 1 + (size_t)p->assured_tiers : (size_t)p->waves) : 1; // (the assured streams: one more variant per tier of a one-wave program)
+        if (p->assured) p->assured_tiers_room = p->assured_tiers;
         if (nvar > 1 && (size_t)p->var_stride * sizeof(BoundInstr) != cbytes) return fail(ctx, DE_ERR_HIP, "wave-group stream variants: stride and arena disagree");
         const size_t abytes = p->threaded ? 2 * nvar * cbytes : cbytes;
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -1399,7 +1442,10 @@ static int set_consts_impl(de_program_t *p, const void *consts) {
             uint64_t table[TOPX_TABLE];
             const hipError_t hs = eval_handler_table(p->dtype, (p->options & DE_OPT_TURBO) != 0, table);
             if (hs != hipSuccess) return fail(ctx, DE_ERR_HIP, "handler table: %s", hipGetErrorString(hs));
-            parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) { assured_link_trees(p, table, tb, te, true); });
+            parallel_tree_ranges(p->n_trees, [&](int, int64_t tb, int64_t te) {
+                assured_link_trees(p, table, tb, te, true);
+                if (p->assured_tiers >= 2) assured_link_trees(p, table, tb, te, true, 2); // (both passes, the touched trees only)
+            });
             p->assured_valid = true;
         }
         const auto t4 = now();
@@ -1994,31 +2040,38 @@ int de_program_verify(const de_program_t *p) {
         // the assured stream: the guarded stream in everything but handler words, and every handler word the one the interval pass over
         // the present fused code (its constants) picks — the instruction's own handler or its untested twin's
         if (p->assured) {
-            if (p->waves != 1 || !f32 || p->ccode_w.size() != p->ccode.size() || p->aids.size() != p->fbcode.size() || (size_t)p->var_stride < p->ccode.size())
+            const size_t tiers = (size_t)p->assured_tiers;
+            if (p->waves != 1 || !f32 || tiers < 1 || tiers > 2 || p->ccode_w.size() != tiers * p->ccode.size() || p->aids.size() != p->fbcode.size() ||
+                p->aids2.size() != (tiers == 2 ? p->fbcode.size() : 0) || (size_t)p->var_stride < p->ccode.size())
                 return bad("assured stream layout", -1, p->waves, p->ccode_w.size());
-            const BoundInstr *cw = p->ccode_w.data();
-            std::vector<AssuredInstr> info;
-            auto named = [](const BoundInstr &q) { return ((uint64_t)q.hi << 32) | q.lo; };
-            for (size_t r = 0; r < p->ccode.size(); r++)
-                if (cw[r].bop != p->ccode[r].bop || cw[r].arg != p->ccode[r].arg) return bad("assured stream: operand words differ", -1, (int64_t)r, cw[r].bop);
-            for (int64_t t = 0; t < p->n_trees; t++) {
-                const int32_t i0 = p->tcode_off[(size_t)t], i1 = p->tcode_off[(size_t)t + 1], h = p->ccode_off[(size_t)t];
-                if (i1 <= i0) continue;
-                info.resize((size_t)(i1 - i0));
-                assure_tree(p->fbcode.data() + i0, (size_t)(i1 - i0), p->n_features, p->assured_xmax, info.data(), p->assured_parts);
-                const int ev = i1 - i0 >= 2 ? topx_endv_of(p->fbcode[(size_t)i1 - 1].bop) : -1;
-                for (int32_t i = i0; i < i1; i++) {
-                    const uint32_t id = info[(size_t)(i - i0)].id;
-                    if (p->assured_valid && id != p->aids[(size_t)i]) return bad("assured stream: stale twin id", t, i - i0, p->aids[(size_t)i]);
-                    const uint32_t have = p->aids[(size_t)i];
-                    if (have >= TOPX_COUNT) return bad("assured stream: handler id", t, i - i0, have);
-                    const uint64_t want = (i == i1 - 1 && ev >= 0) ? (topx_enda_of(have) >= 0 && have != p->fbcode[(size_t)i].bop ? table[TOPX_ENDA_BASE + (uint32_t)topx_enda_of(have)] : p->endv_handler[ev])
-                                          : (have == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[have]);
-                    if (named(cw[(size_t)(h + (i - i0) - 1)]) != want) return bad("assured stream: handler word", t, i - i0, named(cw[(size_t)(h + (i - i0) - 1)]));
+            for (size_t tier = 1; tier <= tiers; tier++) { // (tier 2: the tight fact's pass, variant 2 — de_api_internal.h assured_tiers)
+                const BoundInstr *cw = p->ccode_w.data() + (tier - 1) * p->ccode.size();
+                const std::vector<uint32_t> &aids = tier == 2 ? p->aids2 : p->aids;
+                std::vector<AssuredInstr> info;
+                auto named = [](const BoundInstr &q) { return ((uint64_t)q.hi << 32) | q.lo; };
+                for (size_t r = 0; r < p->ccode.size(); r++)
+                    if (cw[r].bop != p->ccode[r].bop || cw[r].arg != p->ccode[r].arg) return bad("assured stream: operand words differ", -1, (int64_t)r, cw[r].bop);
+                for (int64_t t = 0; t < p->n_trees; t++) {
+                    const int32_t i0 = p->tcode_off[(size_t)t], i1 = p->tcode_off[(size_t)t + 1], h = p->ccode_off[(size_t)t];
+                    if (i1 <= i0) continue;
+                    info.resize((size_t)(i1 - i0));
+                    assure_program_tree(p, (int)tier, i0, i1, info.data());
+                    const int ev = i1 - i0 >= 2 ? topx_endv_of(p->fbcode[(size_t)i1 - 1].bop) : -1;
+                    for (int32_t i = i0; i < i1; i++) {
+                        const uint32_t id = info[(size_t)(i - i0)].id;
+                        if (p->assured_valid && id != aids[(size_t)i]) return bad("assured stream: stale twin id", t, i - i0, aids[(size_t)i]);
+                        const uint32_t have = aids[(size_t)i];
+                        if (have >= TOPX_COUNT) return bad("assured stream: handler id", t, i - i0, have);
+                        if (tier == 2 && have != p->aids[(size_t)i] && p->aids[(size_t)i] != p->fbcode[(size_t)i].bop && have == p->fbcode[(size_t)i].bop)
+                            return bad("assured stream: the tight tier tests what the wide tier elides", t, i - i0, have);
+                        const uint64_t want = (i == i1 - 1 && ev >= 0) ? (topx_enda_of(have) >= 0 && have != p->fbcode[(size_t)i].bop ? table[TOPX_ENDA_BASE + (uint32_t)topx_enda_of(have)] : p->endv_handler[ev])
+                                              : (have == p->fbcode[(size_t)i].bop ? p->handler_base + p->tcode[(size_t)i].bop : table[have]);
+                        if (named(cw[(size_t)(h + (i - i0) - 1)]) != want) return bad("assured stream: handler word", t, i - i0, named(cw[(size_t)(h + (i - i0) - 1)]));
+                    }
+                    // the end record is named as in the guarded stream (by the last instruction, or stepped over by an end-fused one)
+                    if (ev < 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != p->end_handler) return bad("assured stream: tree does not end in the end record", t, i1 - i0, 0);
+                    if (ev >= 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != named(cw[(size_t)(h + (i1 - i0))])) return bad("assured stream: end-fused instruction and end record disagree", t, i1 - i0, 0);
                 }
-                // the end record is named as in the guarded stream (by the last instruction, or stepped over by an end-fused one)
-                if (ev < 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != p->end_handler) return bad("assured stream: tree does not end in the end record", t, i1 - i0, 0);
-                if (ev >= 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != named(cw[(size_t)(h + (i1 - i0))])) return bad("assured stream: end-fused instruction and end record disagree", t, i1 - i0, 0);
             }
         }
     }
@@ -2040,15 +2093,18 @@ int64_t de_program_dump(const de_program_t *p, int64_t tree, uint32_t *words, in
         if (cap < 7) return 5;
         words[5] = p->threaded && p->assured ? 1u : 0u; // the program has an assured stream ...
         words[6] = p->threaded && assured_valid ? 1u : 0u; // ... and the launches use it (0 behind de_program_set_consts_device)
-        return 7;
+        if (cap < 8) return 7;
+        words[7] = p->threaded && p->assured ? (uint32_t)p->assured_tiers : 0u; // the assured tiers the program has (0, 1, 2)
+        return 8;
     }
-    if (which == 4) { // the fused form with the handler ids of the ASSURED stream; empty when the program has none
-        if (!p->threaded || !p->assured) return 0;
+    if (which == 4 || which == 5) { // the fused form with the handler ids of the ASSURED stream (5: of its tight tier); empty when the program has none
+        if (!p->threaded || !p->assured || (which == 5 && p->assured_tiers < 2)) return 0;
+        const std::vector<uint32_t> &aids = which == 5 ? p->aids2 : p->aids;
         const int32_t b0 = p->tcode_off[(size_t)tree], b1 = p->tcode_off[(size_t)tree + 1];
         const int64_t nb = (int64_t)(b1 - b0) * 4;
         if (!words || cap < nb) return nb;
         std::memcpy(words, p->fbcode.data() + b0, (size_t)nb * 4);
-        for (int32_t i = b0; i < b1; i++) words[(size_t)(i - b0) * 4] = p->aids[(size_t)i];
+        for (int32_t i = b0; i < b1; i++) words[(size_t)(i - b0) * 4] = aids[(size_t)i];
         return nb;
     }
     if (which == 2) { // bound instructions (de_bind.h)
@@ -2163,8 +2219,14 @@ int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, cons
 // ... with the parts of the pass (ASSURED_PART_*, de_bind.h) given by the caller
 int64_t de_lower_tape_assured_parts(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
                                     uint32_t options, double xmax, uint32_t parts, double *out, int64_t cap) {
+    return de_lower_tape_assured_fact(nodes, n_nodes, consts, n_consts, n_features, options, xmax, assured_wide_amin(parts), parts, out, cap);
+}
+// ... and with the feature fact amin <= |x| <= xmax given by the caller (de_bind.h assure_tree_fact: the pass of a program's tight tier)
+int64_t de_lower_tape_assured_fact(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts, int32_t n_features,
+                                   uint32_t options, double xmax, double amin, uint32_t parts, double *out, int64_t cap) {
     if (parts & ~ASSURED_PARTS_ALL) return -DE_ERR_INVALID_ARG;
     if (!(xmax >= 0x1p-40 && xmax <= 0x1p100)) return -DE_ERR_INVALID_ARG;
+    if (!(amin >= 0x1p-40 && amin <= xmax)) return -DE_ERR_INVALID_ARG;
     int64_t nw = lower_tape_stage_impl(DE_F32, nodes, n_nodes, consts, n_consts, n_features, 0, options, 3, nullptr, 0);
     if (nw < 0) return nw;
     try {
@@ -2174,7 +2236,7 @@ int64_t de_lower_tape_assured_parts(const de_tape_node_t *nodes, int64_t n_nodes
         const int64_t n = (int64_t)f.size() * 6;
         if (!out || cap < n) return n;
         std::vector<AssuredInstr> info(f.size());
-        assure_tree(f.data(), f.size(), n_features, xmax, info.data(), parts);
+        assure_tree_fact(f.data(), f.size(), n_features, xmax, amin, info.data(), parts);
         for (size_t i = 0; i < f.size(); i++) {
             double *o = out + 6 * i;
             o[0] = info[i].acc.lo; o[1] = info[i].acc.hi; o[2] = info[i].acc.amin; o[3] = info[i].acc.fin ? 1.0 : 0.0;

@@ -291,10 +291,14 @@ AssuredVal a_un(int k, const AssuredVal &x) {
 } // namespace
 
 void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts) {
+    // (the wide feature bound: what the tile test guarantees, taken only with the new part — the classic parts keep their intervals id for id)
+    assure_tree_fact(f, n, n_features, xmax, assured_wide_amin(parts), out, parts);
+}
+
+void assure_tree_fact(const BoundInstr *f, size_t n, int n_features, double xmax, double amin, AssuredInstr *out, uint32_t parts) {
     static thread_local std::vector<AssuredVal> slots; // rows >= n_features an instruction of THIS tree has written
     slots.clear();
-    // (the feature bound: what the tile test guarantees, taken only with the new part — the classic parts keep their intervals id for id)
-    const AssuredVal feature{-xmax, xmax, (parts & ASSURED_PART_FUSED_DIV) ? 0x1p-39 : 0x1p-40, true};
+    const AssuredVal feature{-xmax, xmax, amin, true};
     auto row_val = [&](uint32_t row) -> AssuredVal {
         if (row < (uint32_t)n_features) return feature;
         const size_t s = row - (uint32_t)n_features;

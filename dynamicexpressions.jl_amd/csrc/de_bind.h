@@ -319,6 +319,13 @@ struct AssuredInstr {
     uint32_t bits;  // ASSURED_*
 };
 void assure_tree(const BoundInstr *f, size_t n, int n_features, double xmax, AssuredInstr *out, uint32_t parts);
+// ... with the FEATURE FACT as data: every feature value of the tile is finite with amin <= |x| <= xmax.  assure_tree is this pass with the
+// wide fact (xmax, assured_wide_amin(parts)); the TIGHT tier of a program (de_api_internal.h assured_tiers) runs it with a smaller xmax and a
+// larger amin, which proves more tests idle — the thresholds of the tests themselves (pre_idle, half_idle) are the handlers' and do not move,
+// and the tight pass names the same twins, no id of its own.  A tighter fact never un-proves anything: its elision bits are a superset.
+constexpr double assured_wide_amin(uint32_t parts) { return (parts & 8u /* ASSURED_PART_FUSED_DIV */) ? 0x1p-39 : 0x1p-40; }
+constexpr double ASSURED_TIGHT_XMAX = 8.0, ASSURED_TIGHT_AMIN = 0x1p-19; // the defaults of the tight tier
+void assure_tree_fact(const BoundInstr *f, size_t n, int n_features, double xmax, double amin, AssuredInstr *out, uint32_t parts);
 
 // Append the bound form of `code` (one tree) to `out`.
 // param_row_base >= 0: parameter operands are LDS rows param_row_base + p (the eval kernels stage the tile's parameter values like

@@ -106,8 +106,10 @@ struct EvalArgs {
     int64_t var_stride;
     // the ASSURED stream (de_api_internal.h; one-wave Float32 programs): variant 1, var_stride records behind `code`, is the stream without
     // the validity tests that cannot fire while every feature value of a tile has 2^-39 <= |x| <= assured_xmax; the kernel tests the tile
-    bool assured = false;
-    float assured_xmax = 0.0f;
+    // assured = the number of assured TIERS in use (0: none): tier 2, two var_strides behind `code`, is the stream of the tight fact
+    // assured_tight_amin <= |x| <= assured_tight_xmax; a tile runs the tightest stream whose fact it passes
+    int32_t assured = 0;
+    float assured_xmax = 0.0f, assured_tight_xmax = 0.0f, assured_tight_amin = 0.0f;
     // de_eval_sum_certificate: device array of n_trees zeroed words of the element type's size; non-null selects the CERT variant of the
     // flat-switch kernel (no output): the bits of the largest |validity-tested value| of every tree
     void *cert_max;

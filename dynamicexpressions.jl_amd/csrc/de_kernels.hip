@@ -104,14 +104,27 @@ template <typename T> struct KArgs {
     // THE ASSURED STREAM (one-wave Float32 workgroups): assured != 0 = var_stride records behind `code` lies the variant of
     // the stream without the validity tests that cannot fire on a tile of ordinary feature values.  The workgroup tests its tile while it
     // stages it — every value finite with 2^-39 <= |x| <= assured_xmax, one ballot — and runs that variant when the tile passes.
+    // TIERS: assured = the number of assured variants (1 or 2).  Variant 2, two var_strides behind `code`, is the stream of the TIGHT fact
+    // assured_tight_amin <= |x| <= assured_tight_xmax (inside the wide one); a tile runs the tightest variant whose fact it passes.
     int32_t assured;
-    float assured_xmax;
+    float assured_xmax, assured_tight_xmax, assured_tight_amin;
 };
-// the per-value test of the tile fact (NaN fails both compares)
-// (2^-39, not the 2^-40 of the division range test: a bare feature is then a proven division operand, de_bind.h ASSURED_PART_FUSED_DIV; a tile
-// with a value in [2^-40, 2^-39) runs the guarded stream, which is right for every part of the pass)
-__device__ __forceinline__ bool assured_value_ok(float v, float xmax) { return (__builtin_fabsf(v) <= xmax) & (__builtin_fabsf(v) >= 0x1p-39f); }
-__device__ __forceinline__ bool assured_value_ok(double, float) { return false; } // (Float64 programs have no assured stream)
+// The tile facts, per lane: the largest and the smallest |x| of the lane's values AS BIT PATTERNS (bits & 0x7fffffff, unsigned).  For
+// non-negative floats the integer order of the bits is the order of the values, Inf is above every finite value and a NaN above Inf: one
+// max and one min per value in the staging loops, and behind them `largest <= bits(xmax) & smallest >= bits(amin)` per fact — the compares
+// of  |x| <= xmax  and  |x| >= amin  on every value, NaN and Inf failing both facts (xmax is finite), +-0 failing the lower bound.
+// (wide fact: 2^-39, not the 2^-40 of the division range test: a bare feature is then a proven division operand, de_bind.h ASSURED_PART_FUSED_DIV;
+// a tile with a value in [2^-40, 2^-39) runs the guarded stream, which is right for every part of the pass)
+struct TileFact {
+    uint32_t hi = 0u, lo = 0xFFFFFFFFu;
+    __device__ __forceinline__ void see(float v) {
+        const uint32_t m = __float_as_uint(v) & 0x7FFFFFFFu;
+        hi = hi > m ? hi : m;
+        lo = lo < m ? lo : m;
+    }
+    __device__ __forceinline__ void see(double) {} // (Float64 programs have no assured stream)
+    __device__ __forceinline__ bool holds(float xmax, float amin) const { return ((int)(hi <= __float_as_uint(xmax)) & (int)(lo >= __float_as_uint(amin))) != 0; }
+};
 
 
 // The same map with the CHUNK slower than a group of `grp` sample tiles (per XCD): the workgroups resident on a CU at one time then walk
@@ -1618,7 +1631,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
     if (a.skip_flagged && tA + (tid & 63) < tB) co_first = a.code_off[tA + (tid & 63)];
     // the tile fact of the assured stream (KArgs::assured): this lane's values of the tile are ordinary numbers
     constexpr bool ASSURABLE = WW == 1 && !PARAMS && sizeof(T) == 4 && DE_TBLK == 64;
-    bool x_ok = true;
+    TileFact x_fact;
     {
         const uint32_t F = (uint32_t)a.F;
         const uint32_t total = (uint32_t)TILE * F;
@@ -1659,7 +1672,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
                         uint32_t j = a.f_magic ? __umulhi(e, a.f_magic) : e;
                         uint32_t f = e - j * F;
                         DE_UNROLL for (int c = 0; c < VW; c++) {
-                            if constexpr (ASSURABLE) x_ok &= assured_value_ok(buf[u][c], a.assured_xmax);
+                            if constexpr (ASSURABLE) x_fact.see(buf[u][c]);
                             rows[f * (ROWV * VW) + j] = buf[u][c];
                             ++f;
                             if (f == F) { f = 0; ++j; }
@@ -1672,7 +1685,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
             for (uint32_t e = stid; e < total; e += SBLK) {
                 const uint32_t j = e / F, f = e - j * F;
                 const T v = src[e];
-                if constexpr (ASSURABLE) x_ok &= assured_value_ok(v, a.assured_xmax);
+                if constexpr (ASSURABLE) x_fact.see(v);
                 rows[f * (ROWV * VW) + j] = v;
             }
         } else {
@@ -1681,7 +1694,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
                 int64_t jj = base + j;
                 jj = jj < last ? jj : last;
                 const T v = a.X[f + a.ldX * jj];
-                if constexpr (ASSURABLE) x_ok &= assured_value_ok(v, a.assured_xmax);
+                if constexpr (ASSURABLE) x_fact.see(v);
                 rows[f * (ROWV * VW) + j] = v;
             }
         }
@@ -1724,8 +1737,16 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
     __syncthreads();
 
     // (one wave = the workgroup: the ballot decides for the whole tile, and the choice lives in this wave's scalar registers)
-    const bool assured_tile = ASSURABLE && a.assured != 0 && __ballot(!x_ok) == 0ull;
-    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)(a.code + (WW > 1 ? (int64_t)wave * a.var_stride : (assured_tile ? a.var_stride : (int64_t)0)));
+    // (two ballots: the variant — 2 the tight tier, 1 the wide one, 0 the guarded stream — and with it the offset are scalar)
+    int assured_var = 0;
+    if constexpr (ASSURABLE) {
+        if (a.assured != 0) {
+            const bool wide = __ballot(!x_fact.holds(a.assured_xmax, 0x1p-39f)) == 0ull;
+            const bool tight = a.assured > 1 && __ballot(!x_fact.holds(a.assured_tight_xmax, a.assured_tight_amin)) == 0ull;
+            assured_var = wide ? (tight ? 2 : 1) : 0; // (the tight fact lies inside the wide one: the host clamps it, `wide` is tested all the same)
+        }
+    }
+    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)(a.code + (WW > 1 ? (int64_t)wave * a.var_stride : (int64_t)assured_var * a.var_stride));
     // this wave's live-tree list (h_tree_skip): wave 0 / a one-wave workgroup at LDS address 0, wave w of a group behind the rows
     const uint32_t list_at = (WW > 1 && wave > 0) ? a.list_off + (uint32_t)(wave - 1) * DE_SKIPLIST_BYTES : 0u;
     const ConstI32Ptr code_off = (ConstI32Ptr)(uintptr_t)a.code_off;
@@ -2248,10 +2269,12 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
     const int WW = (TBLK == 64 && (e.waves == 2 || e.waves == 4 || e.waves == 8) && (!e.uses_params || e.n_prows > 0)) ? e.waves : 1;
     a.var_stride = WW > 1 ? e.var_stride : 0;
     // the assured stream of a one-wave Float32 program: variant 1 of the stream (DE_TBLK == 64: the workgroup is one wave, one ballot decides)
-    a.assured = (WW == 1 && TBLK == 64 && sizeof(T) == 4 && e.assured && e.var_stride != 0 && !e.uses_params) ? 1 : 0;
+    a.assured = (WW == 1 && TBLK == 64 && sizeof(T) == 4 && e.assured && e.var_stride != 0 && !e.uses_params) ? (e.assured >= 2 ? 2 : 1) : 0;
     a.assured_xmax = e.assured_xmax;
+    a.assured_tight_xmax = e.assured_tight_xmax;
+    a.assured_tight_amin = e.assured_tight_amin;
     if (a.assured) a.var_stride = e.var_stride;
-    const unsigned n_variants = a.var_stride ? (a.assured ? 2u : (unsigned)WW) : 1u; // (what de_compact_live_kernel re-links: a workgroup each)
+    const unsigned n_variants = a.var_stride ? (a.assured ? 1u + (unsigned)a.assured : (unsigned)WW) : 1u; // (what de_compact_live_kernel re-links: a workgroup each)
     int32_t tpc, nch, nc0;
     plan_chunks(e.n_trees, a.n_tiles, &nch, &tpc, &nc0, WW);
     a.trees_per_chunk = tpc;

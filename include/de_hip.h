@@ -336,8 +336,10 @@ int64_t de_program_n_grad(const de_program_t *prog, int64_t tree, int mode);
  * with cap >= 5, the waves per workgroup the eval kernel runs this program with), 2 bound
  * program, 3 fused (superinstruction) program of the threaded eval kernel (0 words when that
  * kernel is not in use), 4 the fused program with the handler ids of the assured stream (0 words
- * when the program has none).  Metadata with cap >= 7 adds: the program has an assured stream,
- * and the launches use it (0 behind de_program_set_consts_device until the host sees the constants). */
+ * when the program has none), 5 the same with the ids of its TIGHT tier (0 words when the program
+ * has one tier).  Metadata with cap >= 7 adds: the program has an assured stream, and the launches
+ * use it (0 behind de_program_set_consts_device until the host sees the constants); with cap >= 8:
+ * the number of assured tiers (0, 1, 2). */
 int64_t de_program_dump(const de_program_t *prog, int64_t tree, uint32_t *words, int64_t cap,
                         int which);
 
@@ -388,6 +390,11 @@ int64_t de_lower_tape_assured(const de_tape_node_t *nodes, int64_t n_nodes, cons
  * range test of row A / row B of a TOP_BIN2 division).  de_lower_tape_assured is parts = 7. */
 int64_t de_lower_tape_assured_parts(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
                                     int32_t n_features, uint32_t options, double xmax, uint32_t parts, double *out, int64_t cap);
+/* ... and with the feature fact named by the caller: every feature value finite with amin <= |x| <= xmax (2^-40 <= amin <= xmax).  The pass
+ * of a program's TIGHT assured tier (DE_ASSURED_TIGHT_XMAX = 8, DE_ASSURED_TIGHT_AMIN = 2^-19 by default; de_program_dump stage 5), which names
+ * the same twin ids and elides a superset of the wide fact's tests.  de_lower_tape_assured_parts is amin = 2^-39 with part 8, 2^-40 without. */
+int64_t de_lower_tape_assured_fact(const de_tape_node_t *nodes, int64_t n_nodes, const void *consts, int64_t n_consts,
+                                   int32_t n_features, uint32_t options, double xmax, double amin, uint32_t parts, double *out, int64_t cap);
 /* The two hooks above take the real dtypes (DE_F32, DE_F64, DE_F16) and answer -DE_ERR_INVALID_ARG for any other code; complex tapes
  * (DE_CF32 / DE_CF64, interleaved (re, im) constants) lower through these two, which take nothing else.  The generic words carry, for a
  * constant operand, the index of its (re, im) pair in the program's constant table (slot k of the tape: index k) instead of its value. */

@@ -9,7 +9,10 @@ the guarded handler minus its form without the test), how many of each the inter
 (`DE_ASSURED_PARTS`: 1 validity, 2 pre-tests, 4 division halves of the plain forms, 8 the TOP_BIN2 divisions + the feature bound,
 16 the end-fused last instruction) removes.  `--fold` folds constant subtrees first (numpy Float32), as a program does.
 
-    python tools/exp_guard_bound.py [--trees 1000] [--xmax 64] [--fold] > profiles/exp_guard_bound.json
+`--amin A` prices the pass under the feature fact A <= |x| <= xmax (`de_lower_tape_assured_fact`: `--xmax 8 --amin 1.9073486328125e-06`
+is the tight tier of a program) instead of the wide fact's lower bound (2^-39 with part 8, 2^-40 without).
+
+    python tools/exp_guard_bound.py [--trees 1000] [--xmax 64] [--amin A] [--fold] > profiles/exp_guard_bound.json
 """
 import argparse
 import json
@@ -84,6 +87,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trees", type=int, default=1000)
     ap.add_argument("--xmax", type=float, default=64.0)
+    ap.add_argument("--amin", type=float, default=None, help="lower bound of the feature fact, amin <= |x| <= xmax (default: the wide fact's, 2^-39 / 2^-40 by parts)")
     ap.add_argument("--fold", action="store_true", help="fold constant subtrees before lowering, as a program does")
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "tests"))  # (prog_interp: the numpy operators)
@@ -112,7 +116,7 @@ def main():
             val, pre, div = val + g[0], pre + g[1], div + g[2]
             n_pre += g[1] > 0
             n_half += (2 if g[2] > 30 else 1) if g[2] > 0 else 0
-        info = api.lower_tape_assured(tape, consts, 5, args.xmax, parts=31)  # (every part)
+        info = api.lower_tape_assured(tape, consts, 5, args.xmax, parts=31, amin=args.amin)  # (every part)
         for b in info[:, 5].astype(int):
             for k in bits_n:
                 bits_n[k] += bool(b & k)
@@ -121,15 +125,19 @@ def main():
             n_end += 1
             end_changed += int(info[-1, 4]) != g
         for p in by_parts:
-            os.environ["DE_ASSURED_PARTS"] = str(p)
-            by_parts[p] += sum(cyc[int(t)] for t in api.lower_tape_stage(tape, consts, 5, 4)[:, 0])
+            if args.amin is not None:  # (the ids of the pass under the given fact: what stage 4 / 5 of a program with that fact names)
+                ids = api.lower_tape_assured(tape, consts, 5, args.xmax, parts=p, amin=args.amin)[:, 4]
+            else:
+                os.environ["DE_ASSURED_PARTS"] = str(p)
+                ids = api.lower_tape_stage(tape, consts, 5, 4)[:, 0]
+            by_parts[p] += sum(cyc[int(t)] for t in ids)
     tot = guarded + over * n
     out = {
         "source": "tools/exp_guard_bound.py: profiles/valu_slots.json over the fused programs of the bench population (seed 0xDE02, "
                   + ("constant subtrees FOLDED" if args.fold else "UNFOLDED tapes as de_lower_tape_stage lowers them") +
                   "; an end-fused last instruction priced as its plain form in both streams — the end-fused twins have no stream id and no "
                   "entry in the slot table, so what part 16 removes is priced by the guards of the plain forms: a proxy)",
-        "trees": len(trees), "xmax": args.xmax,
+        "trees": len(trees), "xmax": args.xmax, "amin": args.amin,
         "fused_instructions_per_tree": n_instr / n,
         "valu_cycles_per_tree_wave_guarded": tot / n,
         "guards_share_of_guarded": {"validity_tests": val / tot, "cos_exp_pre_tests": pre / tot, "division_range_tests": div / tot,
