@@ -12,6 +12,12 @@
 namespace de {
 
 __device__ __forceinline__ float r16(float x) { return (float)(_Float16)x; }
+// The Float32 value of a step in a register of its own, before r16 reads it.  Where two roundings follow each other the compiler otherwise
+// contracts the operation and the conversion into v_fma_mixlo_f16, which rounds the EXACT result to binary16 once: for fma that is not
+// Julia's Float16(muladd(Float32...)) (exact -> Float32 -> binary16: the two differ where the Float32 value lands on a binary16 tie), and a
+// product becomes fma(x, y, +0), whose zero is +0 where the product is -0 (cube of a negative x whose square underflows to +0).  Both
+// found by tests/test_gpu_f16_accuracy.py.
+__device__ __forceinline__ float f32_step(float v) { asm("" : "+v"(v)); return v; }
 
 // cos / sin / exp: the functions of the Float32 kernels' hot handlers.  Every finite binary16 lies inside the fast trigonometric range
 // (|x| <= 65504 < DE_TRIG_FAST_BOUND), so no Payne-Hanek fix-up path; Inf and NaN give NaN there as in OCML.
@@ -26,7 +32,7 @@ __device__ __forceinline__ float h16_op(uint32_t op, float x, float y) {
     case DE_U_NEG: return -x;
     case DE_U_ABS: return m::abs(x);
     case DE_U_SQUARE: return r16(x * x);
-    case DE_U_CUBE: return r16(r16(x * x) * x);
+    case DE_U_CUBE: return r16(f32_step(r16(x * x) * x));
     case DE_U_RELU: return x < 0.0f ? 0.0f : x;
     case DE_U_SIGN: return jl_sign(x);
     case DE_U_ROUND: return m::rint(x);
@@ -83,11 +89,11 @@ __device__ __forceinline__ float h16_op(uint32_t op, float x, float y) {
     }
 }
 
-// acc = op3(x, y, z): fma is Julia's Float16 fma (Float32 muladd — the product of two binary16 values is exact in Float32 — rounded once),
-// +(x, y, z) two additions, clamp and max exact
+// acc = op3(x, y, z): fma is Julia's Float16 fma, Float16(muladd(Float32...)): the exact x y + z rounded to Float32, and that value rounded
+// to binary16 (two roundings: f32_step); +(x, y, z) two additions, clamp and max exact
 __device__ __forceinline__ float h16_op3(uint32_t op, float x, float y, float z) {
     switch (op) {
-    case DE_T_FMA: return r16(M<float>::fma(x, y, z));
+    case DE_T_FMA: return r16(f32_step(M<float>::fma(x, y, z)));
     case DE_T_CLAMP: return x > z ? z : (x < y ? y : x);
     case DE_T_ADD3: return r16(r16(x + y) + z);
     default: return jl_max(jl_max(x, y), z);
