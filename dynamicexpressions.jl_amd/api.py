@@ -1842,6 +1842,33 @@ class Population:
         opts = LmOpts(int(iters), 0, float(lam0), float(up), float(down), float(lam_min))
         if opts.iters < 0 or not all(np.isfinite(v) and v > 0 for v in (opts.lam0, opts.up, opts.down, opts.lam_min)):
             raise ValueError("fit_constants_lm_device: iters >= 0 and finite positive lam0, up, down")
+        ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_lm_device", X, y, weights, consts0, params, classes,
+                                                                                class_base)
+        lib, nt, rows = library(), self.n_trees, int(iters) + 1
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, np.float64 if scaled else self.dtype)
+        head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
+        if scaled:
+            if is_t:
+                import torch
+                st = torch.empty(3 * nt + 3, dtype=torch.float64, device=keep_x.device)
+                stp = st.data_ptr()
+            else:
+                st = np.full(3 * nt + 3, np.nan)
+                stp = st.ctypes.data
+            fit = lib.de_fit_consts_lm_scaled_wide if wide else lib.de_fit_consts_lm_scaled
+            self.ctx.check(fit(*head, C.byref(opts), ptrs[0], stp, stp + 24 * nt, *ptrs[1:]))
+            self._lm_fit_raw = st if nt else None  # (lm_fit_stats reads it: a device tensor is copied only then)
+        else:
+            fit = lib.de_fit_consts_lm_wide if wide else lib.de_fit_consts_lm_ex
+            self.ctx.check(fit(*head, C.byref(spec), float(e_floor), C.byref(opts), *ptrs))
+        self.lm_accepts = acc
+        if history is not None:
+            history.extend(hist[r] for r in range(rows))
+        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
+    def _fit_device_inputs(self, what, X, y, weights, consts0, params, classes, class_base):
+        """The inputs of a device fit (``fit_constants_lm_device``, ``fit_constants_bfgs_device``): X, the parameter arguments, ``y`` and the
+        weights as pointers of the population's dtype, ``consts0`` installed.  Returns (ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x)."""
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()
@@ -1866,52 +1893,30 @@ class Population:
             return p_
 
         if y is None:
-            raise ValueError("fit_constants_lm_device: y is required")
+            raise ValueError(f"{what}: y is required")
         yp, wp = vec(y, "y"), vec(weights, "weights")
         if consts0 is not None:
             n_expected = int(self.n_consts.sum())
             if (consts0.numel() if _is_torch(consts0) else np.size(consts0)) != n_expected:
                 raise ValueError("wrong number of constants")
             self.set_constants(consts0 if _is_torch(consts0) else np.asarray(consts0).reshape(-1))
-        lib, nt, rows = library(), self.n_trees, int(iters) + 1
-        if scaled:
-            if is_t:
-                import torch
-                dev = keep_x.device
-                lo, st = torch.empty(nt, dtype=torch.float64, device=dev), torch.empty(3 * nt + 3, dtype=torch.float64, device=dev)
-                ok = torch.empty(nt, dtype=torch.uint8, device=dev)
-                hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
-                acc = torch.empty(nt, dtype=torch.int32, device=dev)
-                ptrs = (lo.data_ptr(), st.data_ptr(), st.data_ptr() + 24 * nt, ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
-            else:
-                lo, st, ok = np.empty(nt, dtype=np.float64), np.full(3 * nt + 3, np.nan), np.zeros(nt, dtype=np.uint8)
-                hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
-                ptrs = (lo.ctypes.data, st.ctypes.data, st.ctypes.data + 24 * nt, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-            fit = lib.de_fit_consts_lm_scaled_wide if wide else lib.de_fit_consts_lm_scaled
-            self.ctx.check(fit(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(opts), *ptrs))
-            self.lm_accepts = acc
-            self._lm_fit_raw = st if nt else None  # (lm_fit_stats reads it: a device tensor is copied only then)
-            if history is not None:
-                history.extend(hist[r] for r in range(rows))
-            return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+        return ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x
+
+    def _fit_device_outputs(self, is_t, keep_x, iters, loss_dtype):
+        """The outputs of a device fit, on the side its inputs are on: the objective per tree (``loss_dtype``), the flags, the ``iters + 1``
+        history rows and the accept counts.  Returns (lo, ok, hist, acc, their pointers in that order)."""
+        nt, rows = self.n_trees, int(iters) + 1
         if is_t:
             import torch
             dev = keep_x.device
-            lo = torch.empty(nt, dtype=keep_x.dtype, device=dev)
+            lo = torch.empty(nt, dtype=_torch_dtype(loss_dtype), device=dev)
             ok = torch.empty(nt, dtype=torch.uint8, device=dev)
             hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
             acc = torch.empty(nt, dtype=torch.int32, device=dev)
-            ptrs = (lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
-        else:
-            lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
-            hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
-            ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-        fit = lib.de_fit_consts_lm_wide if wide else lib.de_fit_consts_lm_ex
-        self.ctx.check(fit(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec), float(e_floor), C.byref(opts), *ptrs))
-        self.lm_accepts = acc
-        if history is not None:
-            history.extend(hist[r] for r in range(rows))
-        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+            return lo, ok, hist, acc, (lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
+        lo, ok = np.empty(nt, dtype=loss_dtype), np.zeros(nt, dtype=np.uint8)
+        hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
+        return lo, ok, hist, acc, (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
 
     def fit_constants_bfgs(self, X, y, consts0, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
                            curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None,
@@ -1991,55 +1996,14 @@ class Population:
         if self._occ is not None:
             raise ValueError("fit_constants_bfgs_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_bfgs")
-        ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
-        if is_t:
-            self.ctx.use_torch_stream()
-        if F < self.n_features:
-            raise ValueError(f"X has {F} features but the trees use feature {self.n_features}")
-        keep = [keep_x]
-        pa = self._param_args(params, classes, class_base, N, keep)
-
-        def vec(v, name):
-            if v is None:
-                return None
-            if is_t:
-                import torch
-                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
-                n, p_ = v.numel(), v.data_ptr()
-            else:
-                v = np.ascontiguousarray(v, dtype=self.dtype)
-                n, p_ = v.size, v.ctypes.data
-            if n != N:
-                raise ValueError(f"{name} must have {N} entries")
-            keep.append(v)
-            return p_
-
-        if y is None:
-            raise ValueError("fit_constants_bfgs_device: y is required")
-        yp, wp = vec(y, "y"), vec(weights, "weights")
-        if consts0 is not None:
-            n_expected = int(self.n_consts.sum())
-            if (consts0.numel() if _is_torch(consts0) else np.size(consts0)) != n_expected:
-                raise ValueError("wrong number of constants")
-            self.set_constants(consts0 if _is_torch(consts0) else np.asarray(consts0).reshape(-1))
-        nt, rows = self.n_trees, int(iters) + 1
-        if is_t:
-            import torch
-            dev = keep_x.device
-            lo = torch.empty(nt, dtype=keep_x.dtype, device=dev)
-            ok = torch.empty(nt, dtype=torch.uint8, device=dev)
-            hist = torch.empty((rows, nt), dtype=torch.float64, device=dev)
-            acc = torch.empty(nt, dtype=torch.int32, device=dev)
-            ptrs = (lo.data_ptr(), ok.data_ptr(), hist.data_ptr(), acc.data_ptr())
-        else:
-            lo, ok = np.empty(nt, dtype=self.dtype), np.zeros(nt, dtype=np.uint8)
-            hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
-            ptrs = (lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
+        ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_bfgs_device", X, y, weights, consts0, params,
+                                                                                classes, class_base)
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
         self.ctx.check(library().de_fit_consts_bfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
                                                     C.byref(opts), *ptrs))
         self.bfgs_accepts = acc
         if history is not None:
-            history.extend(hist[r] for r in range(rows))
+            history.extend(hist[r] for r in range(int(iters) + 1))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
 
     @property

@@ -22,6 +22,33 @@ int stage_out(de_ctx *c, DevBuf &buf, void *user, size_t bytes, Staged *s) {
     s->staged = true;
     return DE_OK;
 }
+int stage_fit_inputs(de_ctx *c, const de_program *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                     const void *w, FitInputs *out) {
+    out->Xd = X;
+    out->yd = y;
+    out->wd = w;
+    out->pa = pa;
+    if (N <= 0) return DE_OK;
+    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    Staged sX, sY, sW, sPar, sCls;
+    int rc;
+    if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
+    if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
+    if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
+    if (p->uses_params) {
+        if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
+        if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
+        out->pad = *pa;
+        out->pad.params = sPar.dev;
+        out->pad.classes = sCls.dev;
+        out->pa = &out->pad;
+    }
+    if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out->Xd = sX.dev;
+    out->yd = sY.dev;
+    if (w) out->wd = sW.dev;
+    return DE_OK;
+}
 
 int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, int64_t N) {
     if (!p->uses_params) return DE_OK;

@@ -1,0 +1,639 @@
+// de_api_fit.cpp — C ABI (include/de_hip.h): what CONSUMES the gradients and matrices de_api_grad.cpp produces.  de_gn_lm_step /
+// de_fit_stats_lm_step (and _wide): one Levenberg-Marquardt step per tree (kernels de_lm.hip, de_gn_wide.hip, de_lm_scaled.hip,
+// de_lm_scaled_wide.hip); de_fit_consts_lm(_ex, _wide), de_fit_consts_lm_scaled(_wide) and
+// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10): three fits on the constants that are ONE driver — fit_check, stage_fit_inputs, a
+// Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host hooks that run the kernels' arithmetic.
+#include "de_api_internal.h"
+#include "de_lm.h"
+#include "de_lm_solve.h"
+#include "de_gn_wide.h"
+#include "de_lm_solve_wide.h"
+#include "de_lm_scaled.h"
+#include "de_lm_project.h"
+#include "de_lm_project_wide.h"
+#include "de_bfgs.h"
+#include "de_bfgs_dev.h"
+
+extern "C" {
+// ---- the host hooks: the arithmetic of the step, projection and BFGS kernels on host buffers (de_lm_solve.h, de_lm_solve_wide.h,
+// de_lm_project.h, de_lm_project_wide.h, de_bfgs.h) -----------------------------------------------------------------------------------------
+int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step) {
+    double x[LM_MAX_ROWS];
+    const bool args = G <= 0 || (H && g);
+    const int solved = args ? lm_solve8<double>(G, H, g, lam, x) : 0;
+    if (step)
+        for (int k = 0; k < G; k++) step[k] = solved && k < LM_MAX_ROWS ? x[k] : 0.0;
+    return solved;
+}
+int de_lm_solve_host_wide(int G, const double *H, const double *g, double lam, double *step) {
+    if (G <= LM_MAX_ROWS) return de_lm_solve_host(G, H, g, lam, step); // (lm_solve8 itself: the same bits by construction)
+    double x[LM_WIDE_MAX_ROWS], work[LMW_WORK];
+    const int solved = G <= LM_WIDE_MAX_ROWS && H && g ? lm_solve_wide<double>(G, H, g, lam, x, work) : 0;
+    if (step)
+        for (int k = 0; k < G; k++) step[k] = solved ? x[k] : 0.0;
+    return solved;
+}
+int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
+    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
+    int formed = 0;
+    if (stats && ystats && dmom && H && g && Ht && G >= 1 && G <= LM_MAX_ROWS) {
+        DE_LM_FOR_G(G, formed = lm_project_mem<GG>(stats, ystats, dmom, H, g, Ht));
+        return formed;
+    }
+    for (int k = 0; g && k < G; k++) g[k] = 0.0;
+    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
+    return 0;
+}
+int de_lm_project_host_wide(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
+    if (G >= 0 && G <= LM_MAX_ROWS) return de_lm_project_host(G, stats, ystats, dmom, H, sse, g, Ht); // (lm_project itself: the same bits by construction)
+    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
+    if (G < 0) return 0; // (nothing else is written)
+    if (stats && ystats && dmom && H && g && Ht && G <= LM_WIDE_MAX_ROWS) return lm_project_wide(G, stats, ystats, dmom, H, g, Ht);
+    for (int k = 0; g && k < G; k++) g[k] = 0.0;
+    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
+    return 0;
+}
+int de_bfgs_max_rows(void) { return BFGS_MAX_ROWS; }
+int de_bfgs_direction_host(int G, double *B, uint8_t *fresh, double *alpha, const double *g, double step0, double *p, double *slope) {
+    const bool args = B && fresh && alpha && g && p && slope;
+    if (args && G >= 1 && G <= BFGS_MAX_ROWS) return bfgs_direction(G, B, fresh, alpha, g, step0, p, slope);
+    for (int k = 0; p && k < G; k++) p[k] = 0.0;
+    return 0;
+}
+int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const double *yv, double curv) {
+    if (!B || !fresh || !s || !yv) return 0;
+    return bfgs_update(G, B, fresh, s, yv, curv);
+}
+
+// what the fits refuse about their options: null = good, else the reason
+const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
+    if (o->reserved != 0) return "de_bfgs_opts_t: reserved must be 0";
+    if (o->iters < 0) return "de_bfgs_opts_t: iters < 0";
+    for (const double v : {o->step0, o->c1, o->curv})
+        if (!(std::isfinite(v) && v > 0.0)) return "de_bfgs_opts_t: step0, c1 and curv must be finite and positive";
+    if (!(o->shrink > 0.0 && o->shrink < 1.0)) return "de_bfgs_opts_t: shrink must lie in (0, 1)";
+    return nullptr;
+}
+static const char *lm_opts_problem(const de_lm_opts_t *o) {
+    if (o->reserved != 0) return "de_lm_opts_t: reserved must be 0";
+    if (o->iters < 0) return "de_lm_opts_t: iters < 0";
+    for (const double v : {o->lam0, o->up, o->down, o->lam_min})
+        if (!(std::isfinite(v) && v > 0.0)) return "de_lm_opts_t: lam0, up, down and lam_min must be finite and positive";
+    return nullptr;
+}
+
+// ---- the geometry tables -------------------------------------------------------------------------------------------------
+// The geometry tables of a step / fit on the device: [dloss offsets | jtj offsets | widths].  Uploaded only when they differ from what the
+// device holds, through a pinned image: a call whose buffers are device pointers is stream-ordered and never waits for the stream.
+// rows_per_g = 3 (de_fit_stats_lm_step / de_fit_consts_lm_scaled: the offsets are those of dmom, 3 G doubles per tree): the image is
+// [dmom offsets | jtj offsets | packed offsets of G entries per tree | widths], soff the third table (else soff = doff).
+struct LmTables {
+    const int64_t *doff = nullptr, *joff = nullptr, *soff = nullptr;
+    const int32_t *ng = nullptr;
+    int64_t span = 0, jspan = 0, sspan = 0;
+};
+static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out, int rows_per_g = 1) {
+    const size_t nn = (size_t)n, n_off = rows_per_g > 1 ? 3 : 2;
+    std::vector<unsigned char> img(nn * (n_off * sizeof(int64_t) + sizeof(int32_t)));
+    int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn, *soff = n_off > 2 ? joff + nn : nullptr;
+    int32_t *w = reinterpret_cast<int32_t *>(doff + n_off * nn);
+    int64_t run = 0, jrun = 0, span = 0, jspan = 0, srun = 0;
+    for (size_t t = 0; t < nn; t++) {
+        const int64_t g = ng[t];
+        if (g < 0) return fail(c, DE_ERR_INVALID_ARG, "negative n_grad");
+        doff[t] = doffs ? doffs[t] : run;
+        joff[t] = joffs ? joffs[t] : jrun;
+        if (doff[t] < 0 || joff[t] < 0) return fail(c, DE_ERR_INVALID_ARG, "negative offset");
+        if (soff) soff[t] = srun;
+        w[t] = (int32_t)g;
+        run += rows_per_g * g;
+        srun += g;
+        jrun += g * g;
+        span = std::max(span, doff[t] + rows_per_g * g);
+        jspan = std::max(jspan, joff[t] + g * g);
+    }
+    if (img != c->lm_tab || !c->sLmTab.p) {
+        if (c->lm_ev) HIP_TRY(c, hipEventSynchronize(c->lm_ev)); // (the previous upload reads the pinned image)
+        else HIP_TRY(c, hipEventCreateWithFlags(&c->lm_ev, hipEventDisableTiming));
+        if (c->lm_pin_cap < img.size()) {
+            if (c->lm_pin) (void)hipHostFree(c->lm_pin);
+            c->lm_pin = nullptr;
+            c->lm_pin_cap = 0;
+            HIP_TRY(c, hipHostMalloc(&c->lm_pin, img.size(), hipHostMallocDefault));
+            c->lm_pin_cap = img.size();
+        }
+        c->lm_tab.clear();
+        if (c->sLmTab.cap < img.size()) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees the tables queued work may read)
+        HIP_TRY(c, c->sLmTab.reserve(img.size()));
+        std::memcpy(c->lm_pin, img.data(), img.size());
+        HIP_TRY(c, hipMemcpyAsync(c->sLmTab.p, c->lm_pin, img.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->lm_ev, c->stream));
+        c->lm_tab = std::move(img);
+    }
+    out->doff = static_cast<const int64_t *>(c->sLmTab.p);
+    out->joff = out->doff + nn;
+    out->soff = n_off > 2 ? out->joff + nn : out->doff;
+    out->ng = reinterpret_cast<const int32_t *>(out->doff + n_off * nn);
+    out->span = span;
+    out->jspan = jspan;
+    out->sspan = srun;
+    return DE_OK;
+}
+
+// ---- de_gn_lm_step(_wide) (kernels: de_lm.hip, de_gn_wide.hip; arithmetic: de_lm_solve.h, de_lm_solve_wide.h) ----
+static int gn_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                           const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step, bool wide = false) {
+    if (!c) return DE_ERR_INVALID_ARG;
+    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_gn_lm_step: dtype must be DE_F32 or DE_F64");
+    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
+    if (n_trees == 0) return DE_OK;
+    if (!n_grad || !dloss || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
+    // (offsets are checked before anything is written; a growing state buffer is shared with de_fit_consts_lm, which does not run now)
+    LmTables tab;
+    int rc = lm_tables(c, n_trees, n_grad, dloss_offsets, jtj_offsets, &tab);
+    if (rc != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
+    const bool h_dl = !is_device_ptr(dloss), h_j = !is_device_ptr(jtj), h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step);
+    Workspace ws; // the staged images of the host buffers
+    const auto r_dl = ws.place<char>(span * es, h_dl), r_j = ws.place<char>(jspan * es, h_j);
+    const auto r_has = ws.place<uint8_t>(nt, h_has);
+    const auto r_lam = ws.place<double>(nt, h_lam), r_step = ws.place<double>(span, h_step);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    LmStepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = n_trees;
+    a.n_grad = tab.ng;
+    a.doff = tab.doff;
+    a.joff = tab.joff;
+    a.dloss = dloss;
+    a.jtj = jtj;
+    a.has = has;
+    a.lam = lam;
+    a.step = step;
+    if (h_dl) { HIP_TRY(c, hipMemcpyAsync(ws.ptr(r_dl), dloss, span * es, hipMemcpyHostToDevice, c->stream)); a.dloss = ws.ptr(r_dl); }
+    if (h_j) { HIP_TRY(c, hipMemcpyAsync(ws.ptr(r_j), jtj, jspan * es, hipMemcpyHostToDevice, c->stream)); a.jtj = ws.ptr(r_j); }
+    if (h_has) { HIP_TRY(c, hipMemcpyAsync(ws.ptr(r_has), has, nt, hipMemcpyHostToDevice, c->stream)); a.has = ws.ptr(r_has); }
+    if (h_lam) { HIP_TRY(c, hipMemcpyAsync(ws.ptr(r_lam), lam, nt * 8, hipMemcpyHostToDevice, c->stream)); a.lam = ws.ptr(r_lam); }
+    if (h_step) { // entries no tree owns keep the caller's values: the staged image starts as a copy
+        HIP_TRY(c, hipMemcpyAsync(ws.ptr(r_step), step, span * 8, hipMemcpyHostToDevice, c->stream));
+        a.step = ws.ptr(r_step);
+    }
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    HIP_TRY(c, launch_lm_step(dtype, a, c->stream));
+    c->last_kernel = "de_lm_step_kernel";
+    if (wide) { // de_gn_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step the kernel above gave them
+        HIP_TRY(c, launch_lm_step_wide(dtype, a, c->stream));
+        c->last_kernel = "de_lm_step_wide_kernel";
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (h_step) HIP_TRY(c, hipMemcpyAsync(step, ws.ptr(r_step), span * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_dl || h_j || h_has || h_lam || h_step) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_gn_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                  const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step));
+}
+int de_gn_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
+                       const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
+    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step, true));
+}
+
+// ---- de_fit_stats_lm_step(_wide) (kernels: de_lm_scaled.hip, de_lm_scaled_wide.hip; arithmetic: de_lm_project.h,
+// de_lm_project_wide.h) ------------------------------------------------------------------------------------------------------------------------
+static int fit_stats_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                                  const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets,
+                                  const uint8_t *has, const double *lam, double *step, double *sse, bool wide = false) {
+    if (!c) return DE_ERR_INVALID_ARG;
+    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_fit_stats_lm_step: dtype must be DE_F32 or DE_F64");
+    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
+    if (n_trees == 0) return DE_OK;
+    if (!n_grad || !stats || !ystats || !dmom || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
+    LmTables tab;
+    int rc = lm_tables(c, n_trees, n_grad, dmom_offsets, jtj_offsets, &tab, 3);
+    if (rc != DE_OK) return rc;
+    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), sspan = (size_t)tab.sspan;
+    const bool h_st = !is_device_ptr(stats), h_ys = !is_device_ptr(ystats), h_dm = !is_device_ptr(dmom), h_j = !is_device_ptr(jtj),
+               h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step), h_sse = sse && !is_device_ptr(sse);
+    Workspace ws; // the staged images of the host buffers
+    const auto r_st = ws.place<double>(nt * 3, h_st), r_ys = ws.place<double>(3, h_ys), r_dm = ws.place<double>(mspan, h_dm);
+    const auto r_j = ws.place<char>(jspan * es, h_j);
+    const auto r_has = ws.place<uint8_t>(nt, h_has);
+    const auto r_lam = ws.place<double>(nt, h_lam), r_step = ws.place<double>(sspan, h_step), r_sse = ws.place<double>(nt, h_sse);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    LmScaledStepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = n_trees;
+    a.n_grad = tab.ng;
+    a.moff = tab.doff;
+    a.joff = tab.joff;
+    a.soff = tab.soff;
+    a.stats = stats; a.ystats = ystats; a.dmom = dmom; a.jtj = jtj; a.has = has; a.lam = lam; a.step = step; a.sse = sse;
+    auto up = [&](const void *src, void *dst, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
+    if (h_st) { HIP_TRY(c, up(stats, ws.ptr(r_st), nt * 24)); a.stats = ws.ptr(r_st); }
+    if (h_ys) { HIP_TRY(c, up(ystats, ws.ptr(r_ys), 24)); a.ystats = ws.ptr(r_ys); }
+    if (h_dm) { HIP_TRY(c, up(dmom, ws.ptr(r_dm), mspan * 8)); a.dmom = ws.ptr(r_dm); }
+    if (h_j) { HIP_TRY(c, up(jtj, ws.ptr(r_j), jspan * es)); a.jtj = ws.ptr(r_j); }
+    if (h_has) { HIP_TRY(c, up(has, ws.ptr(r_has), nt)); a.has = ws.ptr(r_has); }
+    if (h_lam) { HIP_TRY(c, up(lam, ws.ptr(r_lam), nt * 8)); a.lam = ws.ptr(r_lam); }
+    if (h_step) a.step = ws.ptr(r_step); // (packed: every entry is some tree's)
+    if (h_sse) a.sse = ws.ptr(r_sse);
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    HIP_TRY(c, launch_lm_step_scaled(dtype, a, c->stream));
+    c->last_kernel = "de_lm_step_scaled_kernel";
+    if (wide) { // de_fit_stats_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step (and the sse) the kernel above gave them
+        HIP_TRY(c, launch_lm_step_scaled_wide(dtype, a, c->stream));
+        c->last_kernel = "de_lm_step_scaled_wide_kernel";
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    if (h_step && sspan) HIP_TRY(c, hipMemcpyAsync(step, ws.ptr(r_step), sspan * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_sse) HIP_TRY(c, hipMemcpyAsync(sse, ws.ptr(r_sse), nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_st || h_ys || h_dm || h_j || h_has || h_lam || h_step || h_sse) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_fit_stats_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                         const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
+                         const double *lam, double *step, double *sse) {
+    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse));
+}
+int de_fit_stats_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
+                              const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
+                              const double *lam, double *step, double *sse) {
+    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse, true));
+}
+
+// ---- what the three fits share ---------------------------------------------------------------------------------------------------------------
+// The refusals, in their order: the context; the spec (spec_check: the driver's own, empty where the fit takes none); a CSE program
+// (fold_hint: what its caller does with the rows of a shared constant); a tree whose constant rows are not its constants; the options
+// (opts_why: lm_opts_problem / bfgs_opts_problem); N and the null buffers (`required` must not be null when there is a tree); ldX; the
+// parameter arguments.  `what`: the name in the texts (the narrow entry point's, for its _ex and _wide forms too).
+static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char *fold_hint, const std::function<int()> &spec_check,
+                     const char *opts_why, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                     std::initializer_list<const void *> required) {
+    if (!c || !p) return DE_ERR_INVALID_ARG;
+    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
+    if (spec_check)
+        if (const int rc = spec_check()) return rc;
+    if (!p->in_cse.empty())
+        return fail(c, DE_ERR_UNSUPPORTED, "%s: a program made by de_program_create_cse has one gradient row per occurrence of a shared constant "
+                                           "(%s); such callers keep the host loop", what, fold_hint);
+    for (int64_t t = 0; t < p->n_trees; t++)
+        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
+            return fail(c, DE_ERR_UNSUPPORTED, "%s: tree %lld has %lld constant rows for %lld constants", what, (long long)t,
+                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
+    if (opts_why) return fail(c, DE_ERR_INVALID_ARG, "%s", opts_why);
+    bool missing = N > 0 && !X;
+    for (const void *q : required) missing = missing || !q;
+    if (N < 0 || (p->n_trees > 0 && missing)) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
+    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
+    return check_param_args(c, p, pa, N);
+}
+
+// The loop of a fit, written once.  evaluate(trial): the objective (and what the step needs) at the program's constants, into the accepted
+// (false) or the trial (true) state; init: the per-tree state; first_history(row 0) behind it; then, where nothing can move (no sample, no
+// constant, no iteration), fill_history for every further row, else `iters` times: propose (the step or direction kernel: trial constants
+// from the accepted state), the trial constants installed, evaluate(true), accept(history row).  The program holds the accepted constants
+// afterwards.  The inner calls leave the timing events alone: the ring sees one call.
+struct FitLoop {
+    std::function<int(bool)> evaluate;
+    std::function<int()> init, propose;
+    std::function<int(double *)> first_history, fill_history, accept;
+    void *consts_acc = nullptr, *consts_trial = nullptr;
+    const char *last_kernel = nullptr; // what the context reports behind the loop (null: what the last inner call set)
+};
+static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, double *hist, const FitLoop &f) {
+    const size_t nt = (size_t)p->n_trees;
+    if (!c->nested) HIP_TRY(c, time_begin(c));
+    {
+        NestGuard nest(c);
+        int rc = f.evaluate(false);
+        if (rc == DE_OK) rc = f.init();
+        if (rc == DE_OK) rc = f.first_history(hist);
+        if (rc != DE_OK) return rc;
+        if (!(can_move && iters > 0)) { // (nothing can be accepted: every row of the history is the first)
+            for (int32_t r = 1; r <= iters && hist; r++)
+                if ((rc = f.fill_history(hist + (size_t)r * nt)) != DE_OK) return rc;
+        } else {
+            rc = de_program_get_consts(p, f.consts_acc); // (device to device behind a device set)
+            if (rc != DE_OK) return rc;
+            for (int32_t it = 0; it < iters; it++) {
+                if ((rc = f.propose()) != DE_OK) return rc;
+                rc = set_consts_device_impl(p, f.consts_trial);
+                if (rc == DE_OK) rc = f.evaluate(true);
+                if (rc != DE_OK) break;
+                if ((rc = f.accept(hist ? hist + ((size_t)it + 1) * nt : nullptr)) != DE_OK) return rc;
+            }
+            if (f.last_kernel) c->last_kernel = f.last_kernel;
+            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
+            const int rc2 = set_consts_device_impl(p, f.consts_acc);
+            if (rc != DE_OK) return rc;
+            if (rc2 != DE_OK) return rc2;
+        }
+    }
+    if (!c->nested) HIP_TRY(c, time_end(c));
+    return DE_OK;
+}
+
+// ---- de_fit_consts_lm(_ex, _wide) (kernels: de_lm.hip, de_gn_wide.hip) -----------------------------------
+// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm: every evaluation is de_eval_loss_gn_ex's) or
+// DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_wide: de_eval_loss_gn_wide's, and the wide trees' steps by de_lm_step_wide_kernel)
+static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                              const void *w, const de_loss_spec_t *spec_in, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                              double *history, int32_t *n_accept, int row_limit) {
+    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
+    const de_lm_opts_t o = opts ? *opts : defaults;
+    const auto spec_check = [&]() -> int {
+        char why[160];
+        int src;
+        return gn_spec_problem(spec_in, e_floor, p->dtype, &src, why, sizeof why) ? fail(c, src, "%s", why) : (int)DE_OK;
+    };
+    int rc = fit_check(c, p, "de_fit_consts_lm", "the caller folds them: S H S^T", spec_check, lm_opts_problem(&o), X, N, ldX, pa, {ok, y});
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    LmTables tab; // packed: the dloss offsets are the constants' offsets
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, nullptr, &tab)) != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, losses, gradients, matrices and flags; lam and the step; images of a host history / n_accept
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
+               dA = ws.place<char>(span * es), dT = ws.place<char>(span * es), jA = ws.place<char>(jspan * es), jT = ws.place<char>(jspan * es);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
+    const auto lam = ws.place<double>(nt), step = ws.place<double>(span), r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto r_acc = ws.place<int32_t>(nt, h_acc);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(loss, ws.ptr(lA), nt * es);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    int32_t *acc = out.in_place(n_accept, h_acc, ws.ptr(r_acc), nt);
+    LmStepArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.n_trees = p->n_trees;
+    s.n_grad = tab.ng;
+    s.doff = s.coff = tab.doff;
+    s.joff = tab.joff;
+    s.dloss = ws.ptr(dA); s.jtj = ws.ptr(jA); s.has = ws.ptr(okA);
+    s.lam = ws.ptr(lam);
+    s.step = ws.ptr(step);
+    s.consts = ws.ptr(cA);
+    s.trial = ws.ptr(cT);
+    LmAcceptArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.doff = a.coff = tab.doff;
+    a.joff = tab.joff;
+    a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.dloss_acc = ws.ptr(dA); a.jtj_acc = ws.ptr(jA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.dloss_trial = ws.ptr(dT); a.jtj_trial = ws.ptr(jT); a.ok_trial = ws.ptr(okT);
+    a.lam = ws.ptr(lam);
+    a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
+    a.n_accept = acc;
+    a.row_limit = row_limit;
+    const de_loss_spec_t spec = *spec_in;
+    const bool wide = row_limit > DE_GN_MAX_ROWS;
+    FitLoop f;
+    f.consts_acc = ws.ptr(cA);
+    f.consts_trial = ws.ptr(cT);
+    f.evaluate = [&](bool trial) -> int {
+        void *l = ws.ptr(trial ? lT : lA), *d = ws.ptr(trial ? dT : dA), *j = ws.ptr(trial ? jT : jA);
+        uint8_t *k = ws.ptr(trial ? okT : okA);
+        if (wide) return gn_wide_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, e_floor, l, d, nullptr, j, nullptr, k);
+        const GnPlan gn{j, nullptr, e_floor};
+        return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, l, d, nullptr, k, nullptr, false, &gn);
+    };
+    f.init = [&]() -> int { HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, ws.ptr(lam), acc, c->stream)); return DE_OK; };
+    f.first_history = f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(p->dtype, ws.ptr(lA), p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int {
+        HIP_TRY(c, launch_lm_step(p->dtype, s, c->stream));
+        if (wide) HIP_TRY(c, launch_lm_step_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
+        return DE_OK;
+    };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
+        return DE_OK;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_lm_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                        const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                        double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_MAX_ROWS));
+}
+int de_fit_consts_lm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                     const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    return de_fit_consts_lm_ex(c, p, X, N, ldX, pa, y, w, &spec, 0.0, opts, loss, ok, history, n_accept);
+}
+int de_fit_consts_lm_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                          const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
+                          double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_wide");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
+}
+
+// ---- de_fit_consts_lm_scaled(_wide) (kernels: de_lm_scaled.hip, de_lm_scaled_wide.hip) ---------------------------
+// The fit above with every evaluation de_eval_fit_stats_grad's (a FitPlan into the state) and the objective the scaled sse.
+// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm_scaled) or DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_scaled_wide:
+// every evaluation de_eval_fit_stats_grad_wide's, and the wide trees' steps by de_lm_step_scaled_wide_kernel)
+static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                     const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
+                                     double *history, int32_t *n_accept, int row_limit) {
+    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
+    const de_lm_opts_t o = opts ? *opts : defaults;
+    int rc = fit_check(c, p, "de_fit_consts_lm_scaled", "the caller folds them: S H S^T", nullptr, lm_opts_problem(&o), X, N, ldX, pa, {ok, sse, y});
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    LmTables tab; // packed: dmom at 3 x the constants' offsets, the step at the constants' offsets
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, nullptr, &tab, 3)) != DE_OK) return rc;
+    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), span = std::max<size_t>(nc, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, statistics, dmom, matrices and flags; ystats; the accepted sse, lam and the step; the images
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), jA = ws.place<char>(jspan * es), jT = ws.place<char>(jspan * es);
+    const auto sA = ws.place<double>(nt * 3), sT = ws.place<double>(nt * 3), ys = ws.place<double>(3), mA = ws.place<double>(mspan),
+               mT = ws.place<double>(mspan), sseA = ws.place<double>(nt), lam = ws.place<double>(nt), step = ws.place<double>(span),
+               r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
+    const auto r_acc = ws.place<int32_t>(nt, h_acc);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(sse, ws.ptr(sseA), nt * 8);
+    out.from_state(stats, ws.ptr(sA), nt * 24);
+    out.from_state(ystats, ws.ptr(ys), 24);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    int32_t *acc = out.in_place(n_accept, h_acc, ws.ptr(r_acc), nt);
+    LmScaledStepArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.n_trees = p->n_trees;
+    s.n_grad = tab.ng;
+    s.moff = tab.doff; s.joff = tab.joff; s.soff = tab.soff;
+    s.stats = ws.ptr(sA); s.ystats = ws.ptr(ys); s.dmom = ws.ptr(mA); s.jtj = ws.ptr(jA);
+    s.has = ws.ptr(okA);
+    s.lam = ws.ptr(lam);
+    s.step = ws.ptr(step);
+    s.consts = ws.ptr(cA);
+    s.trial = ws.ptr(cT);
+    LmScaledAcceptArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.moff = tab.doff; a.joff = tab.joff; a.coff = tab.soff;
+    a.ystats = ws.ptr(ys);
+    a.consts_acc = ws.ptr(cA); a.jtj_acc = ws.ptr(jA); a.stats_acc = ws.ptr(sA); a.dmom_acc = ws.ptr(mA); a.sse_acc = ws.ptr(sseA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.jtj_trial = ws.ptr(jT); a.stats_trial = ws.ptr(sT); a.dmom_trial = ws.ptr(mT); a.ok_trial = ws.ptr(okT);
+    a.lam = ws.ptr(lam);
+    a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
+    a.n_accept = acc;
+    a.row_limit = row_limit;
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    const bool wide = row_limit > DE_GN_MAX_ROWS;
+    FitLoop f;
+    f.consts_acc = ws.ptr(cA);
+    f.consts_trial = ws.ptr(cT);
+    f.last_kernel = "de_lm_accept_scaled_kernel";
+    f.evaluate = [&](bool trial) -> int { // (ystats: the same three values every time)
+        double *st = ws.ptr(trial ? sT : sA), *m = ws.ptr(trial ? mT : mA);
+        void *j = ws.ptr(trial ? jT : jA);
+        uint8_t *k = ws.ptr(trial ? okT : okA);
+        if (wide) return fit_stats_grad_wide_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, st, ws.ptr(ys), m, nullptr, j, nullptr, k);
+        const FitPlan fit{st, ws.ptr(ys), j, nullptr};
+        return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, nullptr, m, nullptr, k, nullptr, false, nullptr, &fit);
+    };
+    f.init = [&]() -> int { HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, ws.ptr(lam), acc, c->stream)); return DE_OK; };
+    f.first_history = [&](double *row) -> int { // (the accepted sse itself comes from here)
+        HIP_TRY(c, launch_lm_sse_scaled(ws.ptr(sA), ws.ptr(ys), p->n_trees, ws.ptr(sseA), row, c->stream));
+        return DE_OK;
+    };
+    f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(DE_F64, ws.ptr(sseA), p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int {
+        HIP_TRY(c, launch_lm_step_scaled(p->dtype, s, c->stream));
+        if (wide) HIP_TRY(c, launch_lm_step_scaled_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
+        return DE_OK;
+    };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_lm_accept_scaled(p->dtype, a, c->stream));
+        return DE_OK;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_lm_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                            const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
+                            int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_scaled");
+    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_MAX_ROWS));
+}
+int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                 const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
+                                 int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_scaled_wide");
+    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
+}
+
+// ---- de_fit_consts_bfgs (kernels: de_bfgs.hip, arithmetic: de_bfgs.h) ----------------------------------------------------
+// The same fit with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip
+static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                                const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
+                                double *history, int32_t *n_accept) {
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    const auto spec_check = [&]() -> int {
+        char why[160];
+        if (loss_spec_problem(spec_in, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_bfgs: DE_LOSS_PULLBACK is no objective");
+        return DE_OK;
+    };
+    int rc = fit_check(c, p, "de_fit_consts_bfgs", "the caller sums them", spec_check, bfgs_opts_problem(&o), X, N, ldX, pa, {ok, y});
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    std::vector<int64_t> boff(nt); // B: G^2 doubles of every tree that is fitted, none of the others
+    int64_t bspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t g = p->n_consts_tree[t];
+        boff[t] = bspan;
+        if (g >= 1 && g <= BFGS_MAX_ROWS) bspan += g * g;
+    }
+    LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, boff.data(), &tab)) != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, losses, gradients and flags; B, alpha, the slope and the direction, two flags per tree; the images
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
+               dA = ws.place<char>(span * es), dT = ws.place<char>(span * es);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt), fresh = ws.place<uint8_t>(nt), produced = ws.place<uint8_t>(nt);
+    const auto B = ws.place<double>((size_t)bspan), alpha = ws.place<double>(nt), slope = ws.place<double>(nt), dir = ws.place<double>(span),
+               r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto r_acc = ws.place<int32_t>(nt, h_acc);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(loss, ws.ptr(lA), nt * es);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    BfgsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.coff = tab.doff;
+    a.boff = tab.joff;
+    a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.dloss_acc = ws.ptr(dA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.dloss_trial = ws.ptr(dT); a.ok_trial = ws.ptr(okT);
+    a.B = ws.ptr(B); a.alpha = ws.ptr(alpha); a.slope = ws.ptr(slope); a.p = ws.ptr(dir);
+    a.fresh = ws.ptr(fresh); a.produced = ws.ptr(produced);
+    a.step0 = o.step0; a.shrink = o.shrink; a.c1 = o.c1; a.curv = o.curv;
+    a.n_accept = out.in_place(n_accept, h_acc, ws.ptr(r_acc), nt);
+    const de_loss_spec_t spec = *spec_in;
+    FitLoop f;
+    f.consts_acc = a.consts_acc;
+    f.consts_trial = a.consts_trial;
+    f.evaluate = [&](bool trial) -> int {
+        return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, ws.ptr(trial ? lT : lA), ws.ptr(trial ? dT : dA),
+                              nullptr, ws.ptr(trial ? okT : okA), nullptr);
+    };
+    f.init = [&]() -> int { HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream)); return DE_OK; };
+    f.first_history = f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int { HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream)); return DE_OK; };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
+        return DE_OK;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                       const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                       int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_bfgs");
+    DE_NOTHROW(c, fit_consts_bfgs_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_accept));
+}
+
+} // extern "C"

@@ -1,21 +1,13 @@
-// de_api_grad.cpp — C ABI (include/de_hip.h): de_eval_grad / de_eval_diff / de_eval_pullback_dX, de_eval_loss_grad, de_eval_loss_grad_by_class: the
-// generic gradient program, the glue around the host encoders of its direct-threaded and reverse-accumulation forms (de_grad_encode.cpp)
-// with their host-only hook de_lower_tape_grad, launch planning of the bucketed gradient kernels; de_gn_lm_step / de_fit_consts_lm /
-// de_lm_solve_host: Levenberg-Marquardt on the constants around de_eval_loss_gn's launch (kernels de_lm.hip);
-// de_fit_consts_bfgs and its host hooks: BFGS on the constants around de_eval_loss_grad_ex's launch (kernels de_bfgs.hip, §4.4.10).
+// de_api_grad.cpp — C ABI (include/de_hip.h): what PRODUCES gradients and matrices from X.  de_eval_grad / de_eval_diff /
+// de_eval_pullback_dX, de_eval_loss_grad, de_eval_loss_grad_by_class: the generic gradient program, the glue around the host encoders of its
+// direct-threaded and reverse-accumulation forms (de_grad_encode.cpp) with their host-only hook de_lower_tape_grad, launch planning of the
+// bucketed gradient kernels; de_eval_loss_gn(_ex) and de_eval_fit_stats_grad: the same launch with a GnPlan / FitPlan; their _wide forms
+// (kernels de_gn_wide.hip).  The steps and fits that consume all this: de_api_fit.cpp.
 #include <functional>
 
 #include "de_api_internal.h"
 #include "de_grad_encode.h"
-#include "de_lm.h"
-#include "de_lm_solve.h"
 #include "de_gn_wide.h"
-#include "de_lm_solve_wide.h"
-#include "de_lm_scaled.h"
-#include "de_lm_project.h"
-#include "de_lm_project_wide.h"
-#include "de_bfgs.h"
-#include "de_bfgs_dev.h"
 
 // A direct-threaded stream inside one 4 GiB window (the handlers bump the record pointer without a carry), cleared.
 static int stream_alloc(de_ctx *c, BoundInstr **d, size_t records, const char *what) {
@@ -553,26 +545,8 @@ struct ByClassPlan {
     void *loss_c, *dloss_c;
     bool done;
 };
-// de_eval_loss_gn: the same launch with the kernels' Gauss-Newton tree end and G (G + 1) / 2 more reduction columns per tree of at most
-// DE_GN_MAX_ROWS rows; jtj_offsets: host, element offset of every tree's G x G block (null: packed)
-// e_floor: the residual floor of the kind's curvature weight (the spec itself is loss_grad_impl's argument)
-struct GnPlan {
-    void *jtj;
-    const int64_t *jtj_offsets;
-    double e_floor;
-    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_loss_gn_wide: DE_GN_WIDE_MAX_ROWS)
-};
-// de_eval_fit_stats_grad: the same launch with the kernels' fit-statistics tree end.  A tree owns FIT_COLS + 3 G reduction
-// columns and, where a matrix is wanted and G <= DE_GN_MAX_ROWS, G (G + 1) / 2 more; loss_grad_impl's dloss / dloss_offsets carry dmom and
-// its offsets (3 G doubles per tree), its loss is null and its spec L2 (unused).  Always forward duals.
-struct FitPlan {
-    double *stats, *ystats;
-    void *jtj; // may be null: no matrix wanted
-    const int64_t *jtj_offsets;
-    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_fit_stats_grad_wide: DE_GN_WIDE_MAX_ROWS)
-};
 // de_gn_spec_check with its reason (null = good; *rc: DE_ERR_INVALID_ARG or DE_ERR_UNSUPPORTED).  dtype < 0: the element type is not known.
-static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap) {
+const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap) {
     *rc = DE_ERR_INVALID_ARG;
     if (loss_spec_problem(spec, 1, buf, cap)) return buf;
     if (spec->kind == DE_LOSS_PULLBACK) { std::snprintf(buf, cap, "DE_LOSS_PULLBACK has no Gauss-Newton matrix"); return buf; }
@@ -590,23 +564,14 @@ static const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, i
     }
     return nullptr;
 }
-static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                          int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr,
-                          const FitPlan *fit = nullptr);
 // DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
-static int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
+int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
 }
 // ... and so do they complex programs
-static int refuse_complex(de_ctx_t *c, const char *what) {
+int refuse_complex(de_ctx_t *c, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: complex (DE_CF32 / DE_CF64) programs evaluate only (de_eval, de_eval_sum_certificate); no complex gradients or losses", what);
 }
-#define DE_REFUSE_F16(WHAT)                                                 \
-    do {                                                                    \
-        if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT);      \
-        if (c && p && is_complex_io(p->io)) return refuse_complex(c, WHAT); \
-    } while (0)
 
 int de_eval_loss_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                       int mode, const void *y, const void *w, int32_t loss_kind, void *loss, void *dloss,
@@ -648,10 +613,9 @@ int de_eval_fit_stats_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t 
     const FitPlan fit{stats, ystats, jtj, jtj_offsets};
     DE_NOTHROW(c, loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, &spec, nullptr, dmom, dmom_offsets, ok, nullptr, false, nullptr, &fit));
 }
-static int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                          int mode, const void *y, const void *w, const de_loss_spec_t *spec, void *loss, void *dloss,
-                          const int64_t *dloss_offsets, uint8_t *ok, ByClassPlan *plan, bool first_kinds_only, const GnPlan *gn,
-                          const FitPlan *fit) {
+int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                   const void *w, const de_loss_spec_t *spec, void *loss, void *dloss, const int64_t *dloss_offsets, uint8_t *ok,
+                   ByClassPlan *plan, bool first_kinds_only, const GnPlan *gn, const FitPlan *fit) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (N < 0 || !ok || (p->n_trees > 0 && (!dloss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
@@ -1043,23 +1007,17 @@ static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
     {
         const char *env1 = getenv("DE_BY_CLASS_ONE_PASS");
         if (!(env1 && *env1 == '0') && N > 0) {
-            c->nested++;
+            NestGuard nest(c);
             const int rc1 = loss_grad_impl(c, p, X, N, ldX, pa, mode, y, w, spec, c->sBcLoss.p, c->sBcDloss.p, dloss_offsets,
                                            static_cast<uint8_t *>(c->sBcOk.p), &plan, first_kinds_only);
-            c->nested--;
             if (rc1 != DE_OK) return rc1;
             shared_ok = plan.done;
         }
     }
-    struct Nest { // inner calls leave the timing events alone; restored on every exit path
-        de_ctx *c;
-        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-        ~Nest() { c->nested--; }
-    };
     int rc = DE_OK;
     const size_t cls_es = pa->classes_is_i64 ? 8 : 4;
     {
-    Nest nest(c);
+    NestGuard nest(c);
     for (int64_t k = 0; k < C && rc == DE_OK && !plan.done; k++) {
         const int64_t j0 = class_starts[k], n = class_starts[k + 1] - j0;
         de_param_args_t sub = *pa;
@@ -1136,309 +1094,8 @@ int de_eval_diff(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, nullptr, DE_GRAD_VARIABLE, direction, out, ld_out, dout, nullptr, ok));
 }
 
-// ---- de_gn_lm_step / de_fit_consts_lm / de_lm_solve_host (kernels: de_lm.hip, arithmetic: de_lm_solve.h) ----------------
-int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step) {
-    double x[LM_MAX_ROWS];
-    const bool args = G <= 0 || (H && g);
-    const int solved = args ? lm_solve8<double>(G, H, g, lam, x) : 0;
-    if (step)
-        for (int k = 0; k < G; k++) step[k] = solved && k < LM_MAX_ROWS ? x[k] : 0.0;
-    return solved;
-}
-
-// The geometry tables of a step / fit on the device: [dloss offsets | jtj offsets | widths].  Uploaded only when they differ from what the
-// device holds, through a pinned image: a call whose buffers are device pointers is stream-ordered and never waits for the stream.
-// rows_per_g = 3 (de_fit_stats_lm_step / de_fit_consts_lm_scaled: the offsets are those of dmom, 3 G doubles per tree): the image is
-// [dmom offsets | jtj offsets | packed offsets of G entries per tree | widths], soff the third table (else soff = doff).
-struct LmTables {
-    const int64_t *doff = nullptr, *joff = nullptr, *soff = nullptr;
-    const int32_t *ng = nullptr;
-    int64_t span = 0, jspan = 0, sspan = 0;
-};
-static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out, int rows_per_g = 1) {
-    const size_t nn = (size_t)n, n_off = rows_per_g > 1 ? 3 : 2;
-    std::vector<unsigned char> img(nn * (n_off * sizeof(int64_t) + sizeof(int32_t)));
-    int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn, *soff = n_off > 2 ? joff + nn : nullptr;
-    int32_t *w = reinterpret_cast<int32_t *>(doff + n_off * nn);
-    int64_t run = 0, jrun = 0, span = 0, jspan = 0, srun = 0;
-    for (size_t t = 0; t < nn; t++) {
-        const int64_t g = ng[t];
-        if (g < 0) return fail(c, DE_ERR_INVALID_ARG, "negative n_grad");
-        doff[t] = doffs ? doffs[t] : run;
-        joff[t] = joffs ? joffs[t] : jrun;
-        if (doff[t] < 0 || joff[t] < 0) return fail(c, DE_ERR_INVALID_ARG, "negative offset");
-        if (soff) soff[t] = srun;
-        w[t] = (int32_t)g;
-        run += rows_per_g * g;
-        srun += g;
-        jrun += g * g;
-        span = std::max(span, doff[t] + rows_per_g * g);
-        jspan = std::max(jspan, joff[t] + g * g);
-    }
-    if (img != c->lm_tab || !c->sLmTab.p) {
-        if (c->lm_ev) HIP_TRY(c, hipEventSynchronize(c->lm_ev)); // (the previous upload reads the pinned image)
-        else HIP_TRY(c, hipEventCreateWithFlags(&c->lm_ev, hipEventDisableTiming));
-        if (c->lm_pin_cap < img.size()) {
-            if (c->lm_pin) (void)hipHostFree(c->lm_pin);
-            c->lm_pin = nullptr;
-            c->lm_pin_cap = 0;
-            HIP_TRY(c, hipHostMalloc(&c->lm_pin, img.size(), hipHostMallocDefault));
-            c->lm_pin_cap = img.size();
-        }
-        c->lm_tab.clear();
-        if (c->sLmTab.cap < img.size()) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees the tables queued work may read)
-        HIP_TRY(c, c->sLmTab.reserve(img.size()));
-        std::memcpy(c->lm_pin, img.data(), img.size());
-        HIP_TRY(c, hipMemcpyAsync(c->sLmTab.p, c->lm_pin, img.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipEventRecord(c->lm_ev, c->stream));
-        c->lm_tab = std::move(img);
-    }
-    out->doff = static_cast<const int64_t *>(c->sLmTab.p);
-    out->joff = out->doff + nn;
-    out->soff = n_off > 2 ? out->joff + nn : out->doff;
-    out->ng = reinterpret_cast<const int32_t *>(out->doff + n_off * nn);
-    out->span = span;
-    out->jspan = jspan;
-    out->sspan = srun;
-    return DE_OK;
-}
-// a region of `bytes` in a buffer laid out by successive calls (256-byte granules)
-static size_t lm_place(size_t *at, size_t bytes) {
-    const size_t o = *at;
-    *at += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-}
-
-static int gn_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
-                           const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step, bool wide = false) {
-    if (!c) return DE_ERR_INVALID_ARG;
-    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_gn_lm_step: dtype must be DE_F32 or DE_F64");
-    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
-    if (n_trees == 0) return DE_OK;
-    if (!n_grad || !dloss || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
-    // (offsets are checked before anything is written; a growing state buffer is shared with de_fit_consts_lm, which does not run now)
-    LmTables tab;
-    int rc = lm_tables(c, n_trees, n_grad, dloss_offsets, jtj_offsets, &tab);
-    if (rc != DE_OK) return rc;
-    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
-    const bool h_dl = !is_device_ptr(dloss), h_j = !is_device_ptr(jtj), h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step);
-    size_t at = 0;
-    const size_t o_dl = h_dl ? lm_place(&at, span * es) : 0, o_j = h_j ? lm_place(&at, jspan * es) : 0, o_has = h_has ? lm_place(&at, nt) : 0,
-                 o_lam = h_lam ? lm_place(&at, nt * 8) : 0, o_step = h_step ? lm_place(&at, span * 8) : 0;
-    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sLm.reserve(at));
-    char *base = static_cast<char *>(c->sLm.p);
-    LmStepArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_trees = n_trees;
-    a.n_grad = tab.ng;
-    a.doff = tab.doff;
-    a.joff = tab.joff;
-    a.dloss = dloss;
-    a.jtj = jtj;
-    a.has = has;
-    a.lam = lam;
-    a.step = step;
-    if (h_dl) { HIP_TRY(c, hipMemcpyAsync(base + o_dl, dloss, span * es, hipMemcpyHostToDevice, c->stream)); a.dloss = base + o_dl; }
-    if (h_j) { HIP_TRY(c, hipMemcpyAsync(base + o_j, jtj, jspan * es, hipMemcpyHostToDevice, c->stream)); a.jtj = base + o_j; }
-    if (h_has) { HIP_TRY(c, hipMemcpyAsync(base + o_has, has, nt, hipMemcpyHostToDevice, c->stream)); a.has = reinterpret_cast<const uint8_t *>(base + o_has); }
-    if (h_lam) { HIP_TRY(c, hipMemcpyAsync(base + o_lam, lam, nt * 8, hipMemcpyHostToDevice, c->stream)); a.lam = reinterpret_cast<const double *>(base + o_lam); }
-    if (h_step) { // entries no tree owns keep the caller's values: the staged image starts as a copy
-        HIP_TRY(c, hipMemcpyAsync(base + o_step, step, span * 8, hipMemcpyHostToDevice, c->stream));
-        a.step = reinterpret_cast<double *>(base + o_step);
-    }
-    if (!c->nested) HIP_TRY(c, time_begin(c));
-    HIP_TRY(c, launch_lm_step(dtype, a, c->stream));
-    c->last_kernel = "de_lm_step_kernel";
-    if (wide) { // de_gn_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step the kernel above gave them
-        HIP_TRY(c, launch_lm_step_wide(dtype, a, c->stream));
-        c->last_kernel = "de_lm_step_wide_kernel";
-    }
-    if (!c->nested) HIP_TRY(c, time_end(c));
-    if (h_step) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, span * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_dl || h_j || h_has || h_lam || h_step) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
-}
-int de_gn_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
-                  const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
-    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step));
-}
-
-static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
-                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
-                        const int64_t *jtj_offsets, uint8_t *ok);
-// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm: every evaluation is de_eval_loss_gn_ex's) or
-// DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_wide: de_eval_loss_gn_wide's, and the wide trees' steps by de_lm_step_wide_kernel)
-static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                              const void *w, const de_loss_spec_t *spec_in, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
-                              double *history, int32_t *n_accept, int row_limit) {
-    if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
-    {
-        char why[160];
-        int src;
-        if (gn_spec_problem(spec_in, e_floor, p->dtype, &src, why, sizeof why)) return fail(c, src, "%s", why);
-    }
-    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
-    const de_lm_opts_t o = opts ? *opts : defaults;
-    if (!p->in_cse.empty())
-        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm: a program made by de_program_create_cse has one gradient row per occurrence of a "
-                                           "shared constant (the caller folds them: S H S^T); such callers keep the host loop");
-    for (int64_t t = 0; t < p->n_trees; t++)
-        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
-            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm: tree %lld has %lld constant rows for %lld constants", (long long)t,
-                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
-    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: reserved must be 0");
-    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: iters < 0");
-    for (const double v : {o.lam0, o.up, o.down, o.lam_min})
-        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: lam0, up, down and lam_min must be finite and positive");
-    if (N < 0 || (p->n_trees > 0 && (!ok || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
-    int rc = check_param_args(c, p, pa, N);
-    if (rc != DE_OK) return rc;
-    if (p->n_trees == 0) return DE_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
-    std::vector<int32_t> ng(nt);
-    for (size_t t = 0; t < nt; t++) ng[t] = (int32_t)p->n_consts_tree[t];
-    LmTables tab; // packed: the dloss offsets are the constants' offsets
-    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, nullptr, &tab);
-    if (rc != DE_OK) return rc;
-    const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
-    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
-    Staged sX, sY, sW, sPar, sCls;
-    de_param_args_t pad;
-    const de_param_args_t *pa_use = pa;
-    if (N > 0) {
-        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
-        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
-        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
-        if (p->uses_params) {
-            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
-            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
-            pad = *pa;
-            pad.params = sPar.dev;
-            pad.classes = sCls.dev;
-            pa_use = &pad;
-        }
-        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
-    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
-    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok);
-    const size_t rows = (size_t)o.iters + 1;
-    size_t at = 0;
-    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_la = lm_place(&at, nt * es), o_lt = lm_place(&at, nt * es),
-                 o_da = lm_place(&at, span * es), o_dt = lm_place(&at, span * es), o_ja = lm_place(&at, jspan * es), o_jt = lm_place(&at, jspan * es),
-                 o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt), o_lam = lm_place(&at, nt * 8), o_step = lm_place(&at, span * 8),
-                 o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0, o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
-    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sLm.reserve(at));
-    char *base = static_cast<char *>(c->sLm.p);
-    void *cA = base + o_ca, *cT = base + o_ct, *lA = base + o_la, *lT = base + o_lt, *dA = base + o_da, *dT = base + o_dt, *jA = base + o_ja, *jT = base + o_jt;
-    uint8_t *okA = reinterpret_cast<uint8_t *>(base + o_oka), *okT = reinterpret_cast<uint8_t *>(base + o_okt);
-    double *lam = reinterpret_cast<double *>(base + o_lam), *step = reinterpret_cast<double *>(base + o_step);
-    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
-    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
-
-    if (!c->nested) HIP_TRY(c, time_begin(c));
-    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
-        de_ctx *c;
-        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-        ~Nest() { c->nested--; }
-    };
-    const de_loss_spec_t spec = *spec_in;
-    {
-        Nest nest(c);
-        const bool wide = row_limit > DE_GN_MAX_ROWS;
-        auto evaluate = [&](void *l, void *d, void *j, uint8_t *k) {
-            if (wide) return gn_wide_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, e_floor, l, d, nullptr, j, nullptr, k);
-            const GnPlan gn{j, nullptr, e_floor};
-            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, l, d, nullptr, k, nullptr, false, &gn);
-        };
-        rc = evaluate(lA, dA, jA, okA);
-        if (rc != DE_OK) return rc;
-        HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
-        HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist, c->stream));
-        const bool loop = N > 0 && o.iters > 0 && nc > 0;
-        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
-            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(p->dtype, lA, p->n_trees, hist + r * nt, c->stream));
-        if (loop) {
-            rc = de_program_get_consts(p, cA); // (device to device behind a device set)
-            if (rc != DE_OK) return rc;
-            LmStepArgs s;
-            std::memset(&s, 0, sizeof s);
-            s.n_trees = p->n_trees;
-            s.n_grad = tab.ng;
-            s.doff = s.coff = tab.doff;
-            s.joff = tab.joff;
-            s.dloss = dA;
-            s.jtj = jA;
-            s.has = okA;
-            s.lam = lam;
-            s.step = step;
-            s.consts = cA;
-            s.trial = cT;
-            LmAcceptArgs a;
-            std::memset(&a, 0, sizeof a);
-            a.n_trees = p->n_trees;
-            a.n_grad = tab.ng;
-            a.doff = a.coff = tab.doff;
-            a.joff = tab.joff;
-            a.consts_acc = cA; a.loss_acc = lA; a.dloss_acc = dA; a.jtj_acc = jA; a.ok_acc = okA;
-            a.consts_trial = cT; a.loss_trial = lT; a.dloss_trial = dT; a.jtj_trial = jT; a.ok_trial = okT;
-            a.lam = lam;
-            a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
-            a.n_accept = acc;
-            a.row_limit = row_limit;
-            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
-                HIP_TRY(c, launch_lm_step(p->dtype, s, c->stream));
-                if (wide) HIP_TRY(c, launch_lm_step_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
-                rc = set_consts_device_impl(p, cT);
-                if (rc == DE_OK) rc = evaluate(lT, dT, jT, okT);
-                if (rc != DE_OK) break;
-                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
-                HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
-            }
-            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
-            const int rc2 = set_consts_device_impl(p, cA);
-            if (rc != DE_OK) return rc;
-            if (rc2 != DE_OK) return rc2;
-        }
-    }
-    if (!c->nested) HIP_TRY(c, time_end(c));
-    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, lA, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ok, okA, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
-}
-int de_fit_consts_lm_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                        const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
-                        double *history, int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_lm");
-    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_MAX_ROWS));
-}
-int de_fit_consts_lm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                     const void *w, const de_lm_opts_t *opts, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
-    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
-    return de_fit_consts_lm_ex(c, p, X, N, ldX, pa, y, w, &spec, 0.0, opts, loss, ok, history, n_accept);
-}
-
-// ---- de_eval_loss_gn_wide / de_gn_lm_step_wide / de_fit_consts_lm_wide / de_lm_solve_host_wide (kernels: de_gn_wide.hip) ----
+// ---- de_eval_loss_gn_wide / de_eval_fit_stats_grad_wide (kernels: de_gn_wide.hip) ----
 int de_gn_wide_max_rows(void) { return DE_GN_WIDE_MAX_ROWS; }
-
-int de_lm_solve_host_wide(int G, const double *H, const double *g, double lam, double *step) {
-    if (G <= LM_MAX_ROWS) return de_lm_solve_host(G, H, g, lam, step); // (lm_solve8 itself: the same bits by construction)
-    double x[LM_WIDE_MAX_ROWS], work[LMW_WORK];
-    const int solved = G <= LM_WIDE_MAX_ROWS && H && g ? lm_solve_wide<double>(G, H, g, lam, x, work) : 0;
-    if (step)
-        for (int k = 0; k < G; k++) step[k] = solved ? x[k] : 0.0;
-    return solved;
-}
 
 void gn_wide_release(de_program *p) {
     if (!p || !p->gnw) return;
@@ -1545,37 +1202,22 @@ static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
     if (rc != DE_OK) return rc;
     GnWideCache *gw = p->gnw;
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
-    // host inputs are staged once, into the buffers a single call would stage them in (as de_fit_consts_lm does)
-    Staged sX, sY, sW, sPar, sCls;
-    de_param_args_t pad;
-    const de_param_args_t *pa_use = pa;
-    if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
-    if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
-    if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
-    if (p->uses_params) {
-        if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
-        if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
-        pad = *pa;
-        pad.params = sPar.dev;
-        pad.classes = sCls.dev;
-        pa_use = &pad;
-    }
-    if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const char *Xd = static_cast<const char *>(sX.dev), *yd = static_cast<const char *>(sY.dev), *wd = w ? static_cast<const char *>(sW.dev) : nullptr;
+    FitInputs in; // (staged once for the narrow call and every chunk, as the fits do)
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    const de_param_args_t *pa_use = in.pa;
+    const char *Xd = static_cast<const char *>(in.Xd), *yd = static_cast<const char *>(in.yd), *wd = static_cast<const char *>(in.wd);
     // the pool
     const int64_t chunk = gn_wide_chunk(N, sc.rows, sc.n_wide, es);
     const int64_t n_slices_max = (chunk + GNW_SLICE - 1) / GNW_SLICE;
     const bool h_j = !is_device_ptr(jtj), h_ok = !is_device_ptr(ok);
-    size_t at = 0;
-    const size_t o_jac = lm_place(&at, (size_t)sc.rows * (size_t)chunk * es), o_val = lm_place(&at, (size_t)sc.n_wide * (size_t)chunk * es),
-                 o_oks = lm_place(&at, (size_t)sc.n_wide), o_cf = lm_place(&at, nc * es), o_cs = lm_place(&at, (size_t)gw->n_consts * es),
-                 o_part = lm_place(&at, (size_t)n_slices_max * (size_t)sc.tri * 8), o_tot = lm_place(&at, (size_t)sc.tri * 8),
-                 o_j = h_j ? lm_place(&at, (size_t)std::max<int64_t>(sc.jspan, 1) * es) : 0, o_ok = h_ok ? lm_place(&at, nt) : 0;
-    if (at > c->sGnw.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sGnw.reserve(at));
-    char *base = static_cast<char *>(c->sGnw.p);
-    void *jtj_d = h_j ? static_cast<void *>(base + o_j) : jtj;
-    uint8_t *ok_d = h_ok ? reinterpret_cast<uint8_t *>(base + o_ok) : ok;
+    Workspace ws;
+    const auto jac = ws.place<char>((size_t)sc.rows * (size_t)chunk * es), vals = ws.place<char>((size_t)sc.n_wide * (size_t)chunk * es),
+               cf = ws.place<char>(nc * es), cs = ws.place<char>((size_t)gw->n_consts * es), r_j = ws.place<char>((size_t)std::max<int64_t>(sc.jspan, 1) * es, h_j);
+    const auto oks = ws.place<uint8_t>((size_t)sc.n_wide), r_ok = ws.place<uint8_t>(nt, h_ok);
+    const auto part = ws.place<double>((size_t)n_slices_max * (size_t)sc.tri), tot = ws.place<double>((size_t)sc.tri);
+    if ((rc = ws.reserve(c, c->sGnw)) != DE_OK) return rc;
+    void *jtj_d = h_j ? static_cast<void *>(ws.ptr(r_j)) : jtj;
+    uint8_t *ok_d = h_ok ? ws.ptr(r_ok) : ok;
     // the table of the wide trees, uploaded when the offsets differ from what the device holds
     {
         std::vector<unsigned char> img((size_t)sc.n_wide * sizeof(GnWideTree));
@@ -1601,20 +1243,16 @@ static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
     }
     if (!c->nested) HIP_TRY(c, time_begin(c));
     {
-        struct Nest {
-            de_ctx *c;
-            explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-            ~Nest() { c->nested--; }
-        } nest(c);
+        NestGuard nest(c);
         // 1. everything but the wide blocks, with the narrow call's bits (the wide blocks: NaN for now)
         rc = narrow(Xd, yd, wd, pa_use, jtj_d, ok_d);
         if (rc != DE_OK) return rc;
         // 2. the wide trees' constants, device to device where the program's are on the device
         if (gw->n_consts > 0 && gw->consts_gen != p->consts_gen) {
-            rc = de_program_get_consts(p, base + o_cf);
+            rc = de_program_get_consts(p, ws.ptr(cf));
             if (rc != DE_OK) return rc;
-            HIP_TRY(c, launch_gnw_gather(p->dtype, base + o_cf, gw->d_cidx, gw->n_consts, base + o_cs, c->stream));
-            rc = set_consts_device_impl(gw->sub, base + o_cs);
+            HIP_TRY(c, launch_gnw_gather(p->dtype, ws.ptr(cf), gw->d_cidx, gw->n_consts, ws.ptr(cs), c->stream));
+            rc = set_consts_device_impl(gw->sub, ws.ptr(cs));
             if (rc != DE_OK) return rc;
             gw->consts_gen = p->consts_gen;
         }
@@ -1623,12 +1261,12 @@ static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
         std::memset(&ga, 0, sizeof ga);
         ga.trees = static_cast<const GnWideTree *>(gw->d_tab);
         ga.n_wide = (int32_t)sc.n_wide;
-        ga.jac = base + o_jac;
-        ga.vals = base + o_val;
+        ga.jac = ws.ptr(jac);
+        ga.vals = ws.ptr(vals);
         ga.kind = spec->kind;
         ga.param = spec->param;
         ga.e_floor = e_floor;
-        ga.partial = reinterpret_cast<double *>(base + o_part);
+        ga.partial = ws.ptr(part);
         ga.tri_total = sc.tri;
         for (int64_t j0 = 0; j0 < N; j0 += chunk) {
             const int64_t n = std::min(chunk, N - j0);
@@ -1639,14 +1277,13 @@ static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
                 pac.classes = static_cast<const char *>(pa_use->classes) + (size_t)j0 * (pa_use->classes_is_i64 ? 8 : 4);
                 pa_c = &pac;
             }
-            rc = grad_impl(c, gw->sub, Xd + (size_t)j0 * (size_t)ldX * es, n, ldX, pa_c, mode, -1, base + o_val, n, base + o_jac, nullptr,
-                           reinterpret_cast<uint8_t *>(base + o_oks));
+            rc = grad_impl(c, gw->sub, Xd + (size_t)j0 * (size_t)ldX * es, n, ldX, pa_c, mode, -1, ws.ptr(vals), n, ws.ptr(jac), nullptr, ws.ptr(oks));
             if (rc != DE_OK) return rc;
             ga.y = yd + (size_t)j0 * es;
             ga.w = wd ? wd + (size_t)j0 * es : nullptr;
             ga.n = n;
             HIP_TRY(c, launch_gnw_gram(p->dtype, ga, c->stream));
-            HIP_TRY(c, launch_gnw_fold(p->dtype, ga.trees, ga.n_wide, ga.partial, (n + GNW_SLICE - 1) / GNW_SLICE, sc.tri, reinterpret_cast<double *>(base + o_tot),
+            HIP_TRY(c, launch_gnw_fold(p->dtype, ga.trees, ga.n_wide, ga.partial, (n + GNW_SLICE - 1) / GNW_SLICE, sc.tri, ws.ptr(tot),
                                        j0 == 0, j0 + n >= N, jtj_d, ok_d, c->stream));
         }
         c->last_kernel = "de_gnw_gram_kernel";
@@ -1661,9 +1298,9 @@ static int gn_wide_run(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
     if (h_j || h_ok) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DE_OK;
 }
-static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
-                        const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
-                        const int64_t *jtj_offsets, uint8_t *ok) {
+int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                 const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
+                 const int64_t *jtj_offsets, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (!p->in_cse.empty())
@@ -1686,9 +1323,9 @@ static int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
                        });
 }
 // de_eval_fit_stats_grad_wide: the same route behind de_eval_fit_stats_grad (a FitPlan), the wide blocks those of {DE_LOSS_L2, 0, 0}
-static int fit_stats_grad_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
-                                    const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets, void *jtj,
-                                    const int64_t *jtj_offsets, uint8_t *ok) {
+int fit_stats_grad_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                             const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets, void *jtj,
+                             const int64_t *jtj_offsets, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (!p->in_cse.empty())
@@ -1719,429 +1356,6 @@ int de_eval_fit_stats_grad_wide(de_ctx_t *c, de_program_t *p, const void *X, int
                                 void *jtj, const int64_t *jtj_offsets, uint8_t *ok) {
     DE_REFUSE_F16("de_eval_fit_stats_grad_wide");
     DE_NOTHROW(c, fit_stats_grad_wide_impl(c, p, X, N, ldX, pa, mode, y, w, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, ok));
-}
-int de_gn_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const void *dloss, const int64_t *dloss_offsets,
-                       const void *jtj, const int64_t *jtj_offsets, const uint8_t *has, const double *lam, double *step) {
-    DE_NOTHROW(c, gn_lm_step_impl(c, dtype, n_trees, n_grad, dloss, dloss_offsets, jtj, jtj_offsets, has, lam, step, true));
-}
-int de_fit_consts_lm_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                          const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
-                          double *history, int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_lm_wide");
-    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
-}
-
-
-// ---- de_lm_project_host / de_fit_stats_lm_step / de_fit_consts_lm_scaled (kernels: de_lm_scaled.hip, arithmetic: de_lm_project.h)
-int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
-    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
-    int formed = 0;
-    if (stats && ystats && dmom && H && g && Ht && G >= 1 && G <= LM_MAX_ROWS) {
-        DE_LM_FOR_G(G, formed = lm_project_mem<GG>(stats, ystats, dmom, H, g, Ht));
-        return formed;
-    }
-    for (int k = 0; g && k < G; k++) g[k] = 0.0;
-    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
-    return 0;
-}
-
-static int fit_stats_lm_step_impl(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
-                                  const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets,
-                                  const uint8_t *has, const double *lam, double *step, double *sse, bool wide = false) {
-    if (!c) return DE_ERR_INVALID_ARG;
-    if (dtype != DE_F32 && dtype != DE_F64) return fail(c, DE_ERR_INVALID_ARG, "de_fit_stats_lm_step: dtype must be DE_F32 or DE_F64");
-    if (n_trees < 0) return fail(c, DE_ERR_INVALID_ARG, "n_trees < 0");
-    if (n_trees == 0) return DE_OK;
-    if (!n_grad || !stats || !ystats || !dmom || !jtj || !has || !lam || !step) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = dtype == DE_F32 ? 4 : 8, nt = (size_t)n_trees;
-    LmTables tab;
-    int rc = lm_tables(c, n_trees, n_grad, dmom_offsets, jtj_offsets, &tab, 3);
-    if (rc != DE_OK) return rc;
-    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), sspan = (size_t)tab.sspan;
-    const bool h_st = !is_device_ptr(stats), h_ys = !is_device_ptr(ystats), h_dm = !is_device_ptr(dmom), h_j = !is_device_ptr(jtj),
-               h_has = !is_device_ptr(has), h_lam = !is_device_ptr(lam), h_step = !is_device_ptr(step), h_sse = sse && !is_device_ptr(sse);
-    size_t at = 0;
-    const size_t o_st = h_st ? lm_place(&at, nt * 24) : 0, o_ys = h_ys ? lm_place(&at, 24) : 0, o_dm = h_dm ? lm_place(&at, mspan * 8) : 0,
-                 o_j = h_j ? lm_place(&at, jspan * es) : 0, o_has = h_has ? lm_place(&at, nt) : 0, o_lam = h_lam ? lm_place(&at, nt * 8) : 0,
-                 o_step = h_step ? lm_place(&at, sspan * 8) : 0, o_sse = h_sse ? lm_place(&at, nt * 8) : 0;
-    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sLm.reserve(at));
-    char *base = static_cast<char *>(c->sLm.p);
-    LmScaledStepArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_trees = n_trees;
-    a.n_grad = tab.ng;
-    a.moff = tab.doff;
-    a.joff = tab.joff;
-    a.soff = tab.soff;
-    a.stats = stats; a.ystats = ystats; a.dmom = dmom; a.jtj = jtj; a.has = has; a.lam = lam; a.step = step; a.sse = sse;
-    auto up = [&](const void *src, size_t off, size_t bytes) { return hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream); };
-    if (h_st) { HIP_TRY(c, up(stats, o_st, nt * 24)); a.stats = reinterpret_cast<const double *>(base + o_st); }
-    if (h_ys) { HIP_TRY(c, up(ystats, o_ys, 24)); a.ystats = reinterpret_cast<const double *>(base + o_ys); }
-    if (h_dm) { HIP_TRY(c, up(dmom, o_dm, mspan * 8)); a.dmom = reinterpret_cast<const double *>(base + o_dm); }
-    if (h_j) { HIP_TRY(c, up(jtj, o_j, jspan * es)); a.jtj = base + o_j; }
-    if (h_has) { HIP_TRY(c, up(has, o_has, nt)); a.has = reinterpret_cast<const uint8_t *>(base + o_has); }
-    if (h_lam) { HIP_TRY(c, up(lam, o_lam, nt * 8)); a.lam = reinterpret_cast<const double *>(base + o_lam); }
-    if (h_step) a.step = reinterpret_cast<double *>(base + o_step); // (packed: every entry is some tree's)
-    if (h_sse) a.sse = reinterpret_cast<double *>(base + o_sse);
-    if (!c->nested) HIP_TRY(c, time_begin(c));
-    HIP_TRY(c, launch_lm_step_scaled(dtype, a, c->stream));
-    c->last_kernel = "de_lm_step_scaled_kernel";
-    if (wide) { // de_fit_stats_lm_step_wide: the trees of 9 .. 32 rows, behind the zero step (and the sse) the kernel above gave them
-        HIP_TRY(c, launch_lm_step_scaled_wide(dtype, a, c->stream));
-        c->last_kernel = "de_lm_step_scaled_wide_kernel";
-    }
-    if (!c->nested) HIP_TRY(c, time_end(c));
-    if (h_step && sspan) HIP_TRY(c, hipMemcpyAsync(step, base + o_step, sspan * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_sse) HIP_TRY(c, hipMemcpyAsync(sse, base + o_sse, nt * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_st || h_ys || h_dm || h_j || h_has || h_lam || h_step || h_sse) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
-}
-int de_fit_stats_lm_step(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
-                         const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
-                         const double *lam, double *step, double *sse) {
-    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse));
-}
-
-// fit_consts_lm_impl's loop with every evaluation de_eval_fit_stats_grad's (a FitPlan into the state) and the kernels of de_lm_scaled.hip.
-// row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm_scaled) or DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_scaled_wide:
-// every evaluation de_eval_fit_stats_grad_wide's, and the wide trees' steps by de_lm_step_scaled_wide_kernel)
-static int fit_consts_lm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                                     const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
-                                     double *history, int32_t *n_accept, int row_limit) {
-    if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
-    const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
-    const de_lm_opts_t o = opts ? *opts : defaults;
-    if (!p->in_cse.empty())
-        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm_scaled: a program made by de_program_create_cse has one gradient row per occurrence "
-                                           "of a shared constant (the caller folds them: S H S^T); such callers keep the host loop");
-    for (int64_t t = 0; t < p->n_trees; t++)
-        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
-            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_lm_scaled: tree %lld has %lld constant rows for %lld constants", (long long)t,
-                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
-    if (o.reserved != 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: reserved must be 0");
-    if (o.iters < 0) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: iters < 0");
-    for (const double v : {o.lam0, o.up, o.down, o.lam_min})
-        if (!(std::isfinite(v) && v > 0.0)) return fail(c, DE_ERR_INVALID_ARG, "de_lm_opts_t: lam0, up, down and lam_min must be finite and positive");
-    if (N < 0 || (p->n_trees > 0 && (!ok || !sse || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
-    int rc = check_param_args(c, p, pa, N);
-    if (rc != DE_OK) return rc;
-    if (p->n_trees == 0) return DE_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
-    std::vector<int32_t> ng(nt);
-    for (size_t t = 0; t < nt; t++) ng[t] = (int32_t)p->n_consts_tree[t];
-    LmTables tab; // packed: dmom at 3 x the constants' offsets, the step at the constants' offsets
-    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, nullptr, &tab, 3);
-    if (rc != DE_OK) return rc;
-    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1), span = std::max<size_t>(nc, 1);
-    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
-    Staged sX, sY, sW, sPar, sCls;
-    de_param_args_t pad;
-    const de_param_args_t *pa_use = pa;
-    if (N > 0) {
-        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
-        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
-        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
-        if (p->uses_params) {
-            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
-            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
-            pad = *pa;
-            pad.params = sPar.dev;
-            pad.classes = sCls.dev;
-            pa_use = &pad;
-        }
-        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
-    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
-    const bool h_sse = !is_device_ptr(sse), h_ok = !is_device_ptr(ok), h_st = stats && !is_device_ptr(stats), h_ys = ystats && !is_device_ptr(ystats);
-    const size_t rows = (size_t)o.iters + 1;
-    size_t at = 0;
-    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_sa = lm_place(&at, nt * 24), o_st = lm_place(&at, nt * 24),
-                 o_ys = lm_place(&at, 24), o_ma = lm_place(&at, mspan * 8), o_mt = lm_place(&at, mspan * 8), o_ja = lm_place(&at, jspan * es),
-                 o_jt = lm_place(&at, jspan * es), o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt), o_sse = lm_place(&at, nt * 8),
-                 o_lam = lm_place(&at, nt * 8), o_step = lm_place(&at, span * 8), o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0,
-                 o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
-    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sLm.reserve(at));
-    char *base = static_cast<char *>(c->sLm.p);
-    void *cA = base + o_ca, *cT = base + o_ct, *jA = base + o_ja, *jT = base + o_jt;
-    double *sA = reinterpret_cast<double *>(base + o_sa), *sT = reinterpret_cast<double *>(base + o_st), *ys = reinterpret_cast<double *>(base + o_ys);
-    double *mA = reinterpret_cast<double *>(base + o_ma), *mT = reinterpret_cast<double *>(base + o_mt);
-    uint8_t *okA = reinterpret_cast<uint8_t *>(base + o_oka), *okT = reinterpret_cast<uint8_t *>(base + o_okt);
-    double *sseA = reinterpret_cast<double *>(base + o_sse), *lam = reinterpret_cast<double *>(base + o_lam), *step = reinterpret_cast<double *>(base + o_step);
-    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
-    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
-
-    if (!c->nested) HIP_TRY(c, time_begin(c));
-    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
-        de_ctx *c;
-        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-        ~Nest() { c->nested--; }
-    };
-    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
-    {
-        Nest nest(c);
-        const bool wide = row_limit > DE_GN_MAX_ROWS;
-        auto evaluate = [&](double *s, double *m, void *j, uint8_t *k) { // (ystats: the same three values every time)
-            if (wide) return fit_stats_grad_wide_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, s, ys, m, nullptr, j, nullptr, k);
-            const FitPlan fit{s, ys, j, nullptr};
-            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, nullptr, m, nullptr, k, nullptr, false, nullptr, &fit);
-        };
-        rc = evaluate(sA, mA, jA, okA);
-        if (rc != DE_OK) return rc;
-        HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, lam, acc, c->stream));
-        HIP_TRY(c, launch_lm_sse_scaled(sA, ys, p->n_trees, sseA, hist, c->stream));
-        const bool loop = N > 0 && o.iters > 0 && nc > 0;
-        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
-            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(DE_F64, sseA, p->n_trees, hist + r * nt, c->stream));
-        if (loop) {
-            rc = de_program_get_consts(p, cA); // (device to device behind a device set)
-            if (rc != DE_OK) return rc;
-            LmScaledStepArgs s;
-            std::memset(&s, 0, sizeof s);
-            s.n_trees = p->n_trees;
-            s.n_grad = tab.ng;
-            s.moff = tab.doff; s.joff = tab.joff; s.soff = tab.soff;
-            s.stats = sA; s.ystats = ys; s.dmom = mA; s.jtj = jA;
-            s.has = okA;
-            s.lam = lam;
-            s.step = step;
-            s.consts = cA;
-            s.trial = cT;
-            LmScaledAcceptArgs a;
-            std::memset(&a, 0, sizeof a);
-            a.n_trees = p->n_trees;
-            a.n_grad = tab.ng;
-            a.moff = tab.doff; a.joff = tab.joff; a.coff = tab.soff;
-            a.ystats = ys;
-            a.consts_acc = cA; a.jtj_acc = jA; a.stats_acc = sA; a.dmom_acc = mA; a.sse_acc = sseA; a.ok_acc = okA;
-            a.consts_trial = cT; a.jtj_trial = jT; a.stats_trial = sT; a.dmom_trial = mT; a.ok_trial = okT;
-            a.lam = lam;
-            a.up = o.up; a.down = o.down; a.lam_min = o.lam_min;
-            a.n_accept = acc;
-            a.row_limit = row_limit;
-            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
-                HIP_TRY(c, launch_lm_step_scaled(p->dtype, s, c->stream));
-                if (wide) HIP_TRY(c, launch_lm_step_scaled_wide(p->dtype, s, c->stream)); // (behind it: the narrow kernel gave the wide trees the zero step)
-                rc = set_consts_device_impl(p, cT);
-                if (rc == DE_OK) rc = evaluate(sT, mT, jT, okT);
-                if (rc != DE_OK) break;
-                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
-                HIP_TRY(c, launch_lm_accept_scaled(p->dtype, a, c->stream));
-            }
-            c->last_kernel = "de_lm_accept_scaled_kernel";
-            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
-            const int rc2 = set_consts_device_impl(p, cA);
-            if (rc != DE_OK) return rc;
-            if (rc2 != DE_OK) return rc2;
-        }
-    }
-    if (!c->nested) HIP_TRY(c, time_end(c));
-    HIP_TRY(c, hipMemcpyAsync(sse, sseA, nt * 8, h_sse ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (stats) HIP_TRY(c, hipMemcpyAsync(stats, sA, nt * 24, h_st ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (ystats) HIP_TRY(c, hipMemcpyAsync(ystats, ys, 24, h_ys ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ok, okA, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_sse || h_st || h_ys || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
-}
-int de_fit_consts_lm_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                            const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
-                            int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_lm_scaled");
-    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_MAX_ROWS));
-}
-
-// ---- de_lm_project_host_wide / de_fit_stats_lm_step_wide / de_fit_consts_lm_scaled_wide (kernel: de_lm_scaled_wide.hip,
-// arithmetic: de_lm_project_wide.h; de_eval_fit_stats_grad_wide stands beside de_eval_loss_gn_wide above)
-int de_lm_project_host_wide(int G, const double *stats, const double *ystats, const double *dmom, const double *H, double *sse, double *g, double *Ht) {
-    if (G >= 0 && G <= LM_MAX_ROWS) return de_lm_project_host(G, stats, ystats, dmom, H, sse, g, Ht); // (lm_project itself: the same bits by construction)
-    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
-    if (G < 0) return 0; // (nothing else is written)
-    if (stats && ystats && dmom && H && g && Ht && G <= LM_WIDE_MAX_ROWS) return lm_project_wide(G, stats, ystats, dmom, H, g, Ht);
-    for (int k = 0; g && k < G; k++) g[k] = 0.0;
-    for (int64_t k = 0; Ht && k < (int64_t)G * G; k++) Ht[k] = 0.0;
-    return 0;
-}
-int de_fit_stats_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int32_t *n_grad, const double *stats, const double *ystats,
-                              const double *dmom, const int64_t *dmom_offsets, const void *jtj, const int64_t *jtj_offsets, const uint8_t *has,
-                              const double *lam, double *step, double *sse) {
-    DE_NOTHROW(c, fit_stats_lm_step_impl(c, dtype, n_trees, n_grad, stats, ystats, dmom, dmom_offsets, jtj, jtj_offsets, has, lam, step, sse, true));
-}
-int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                                 const void *w, const de_lm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok, double *history,
-                                 int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_lm_scaled_wide");
-    DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
-}
-
-// ---- de_fit_consts_bfgs / de_bfgs_direction_host / de_bfgs_update_host (kernels: de_bfgs.hip, arithmetic: de_bfgs.h) ----
-int de_bfgs_max_rows(void) { return BFGS_MAX_ROWS; }
-
-int de_bfgs_direction_host(int G, double *B, uint8_t *fresh, double *alpha, const double *g, double step0, double *p, double *slope) {
-    const bool args = B && fresh && alpha && g && p && slope;
-    if (args && G >= 1 && G <= BFGS_MAX_ROWS) return bfgs_direction(G, B, fresh, alpha, g, step0, p, slope);
-    for (int k = 0; p && k < G; k++) p[k] = 0.0;
-    return 0;
-}
-int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const double *yv, double curv) {
-    if (!B || !fresh || !s || !yv) return 0;
-    return bfgs_update(G, B, fresh, s, yv, curv);
-}
-
-const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
-    if (o->reserved != 0) return "de_bfgs_opts_t: reserved must be 0";
-    if (o->iters < 0) return "de_bfgs_opts_t: iters < 0";
-    for (const double v : {o->step0, o->c1, o->curv})
-        if (!(std::isfinite(v) && v > 0.0)) return "de_bfgs_opts_t: step0, c1 and curv must be finite and positive";
-    if (!(o->shrink > 0.0 && o->shrink < 1.0)) return "de_bfgs_opts_t: shrink must lie in (0, 1)";
-    return nullptr;
-}
-
-// fit_consts_lm_impl's structure with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip
-static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                                const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
-                                double *history, int32_t *n_accept) {
-    if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
-    {
-        char why[160];
-        if (loss_spec_problem(spec_in, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_bfgs: DE_LOSS_PULLBACK is no objective");
-    }
-    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
-    const de_bfgs_opts_t o = opts ? *opts : defaults;
-    if (!p->in_cse.empty())
-        return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_bfgs: a program made by de_program_create_cse has one gradient row per occurrence of a "
-                                           "shared constant (the caller sums them); such callers keep the host loop");
-    for (int64_t t = 0; t < p->n_trees; t++)
-        if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
-            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_bfgs: tree %lld has %lld constant rows for %lld constants", (long long)t,
-                        (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
-    if (const char *why = bfgs_opts_problem(&o)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-    if (N < 0 || (p->n_trees > 0 && (!ok || !y || (N > 0 && !X)))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
-    if (ldX < p->n_features) return fail(c, DE_ERR_INVALID_ARG, "ldX < n_features");
-    int rc = check_param_args(c, p, pa, N);
-    if (rc != DE_OK) return rc;
-    if (p->n_trees == 0) return DE_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size();
-    std::vector<int32_t> ng(nt);
-    std::vector<int64_t> boff(nt); // B: G^2 doubles of every tree that is fitted, none of the others
-    int64_t bspan = 0;
-    for (size_t t = 0; t < nt; t++) {
-        ng[t] = (int32_t)p->n_consts_tree[t];
-        boff[t] = bspan;
-        if (ng[t] >= 1 && ng[t] <= BFGS_MAX_ROWS) bspan += (int64_t)ng[t] * ng[t];
-    }
-    LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's
-    rc = lm_tables(c, p->n_trees, ng.data(), nullptr, boff.data(), &tab);
-    if (rc != DE_OK) return rc;
-    const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
-    // host inputs are staged once for the whole fit, into the buffers a single call would stage them in
-    Staged sX, sY, sW, sPar, sCls;
-    de_param_args_t pad;
-    const de_param_args_t *pa_use = pa;
-    if (N > 0) {
-        if ((rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX))) return rc;
-        if ((rc = stage_in(c, c->sY, y, (size_t)N * es, &sY))) return rc;
-        if (w && (rc = stage_in(c, c->sW, w, (size_t)N * es, &sW))) return rc;
-        if (p->uses_params) {
-            if ((rc = stage_in(c, c->sParams, pa->params, (size_t)pa->ld_params * (size_t)pa->n_classes * es, &sPar))) return rc;
-            if ((rc = stage_in(c, c->sClasses, pa->classes, (size_t)N * (pa->classes_is_i64 ? 8 : 4), &sCls))) return rc;
-            pad = *pa;
-            pad.params = sPar.dev;
-            pad.classes = sCls.dev;
-            pa_use = &pad;
-        }
-        if (sX.staged || sY.staged || sW.staged || sPar.staged || sCls.staged) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    const void *Xd = N > 0 ? sX.dev : X, *yd = N > 0 ? sY.dev : y, *wd = N > 0 && w ? sW.dev : w;
-    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
-    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok);
-    const size_t rows = (size_t)o.iters + 1;
-    size_t at = 0;
-    const size_t o_ca = lm_place(&at, nc * es), o_ct = lm_place(&at, nc * es), o_la = lm_place(&at, nt * es), o_lt = lm_place(&at, nt * es),
-                 o_da = lm_place(&at, span * es), o_dt = lm_place(&at, span * es), o_oka = lm_place(&at, nt), o_okt = lm_place(&at, nt),
-                 o_B = lm_place(&at, (size_t)bspan * 8), o_al = lm_place(&at, nt * 8), o_sl = lm_place(&at, nt * 8), o_p = lm_place(&at, span * 8),
-                 o_fr = lm_place(&at, nt), o_pr = lm_place(&at, nt), o_hist = h_hist ? lm_place(&at, rows * nt * 8) : 0,
-                 o_acc = h_acc ? lm_place(&at, nt * 4) : 0;
-    if (at > c->sLm.cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (growing frees what queued work may still use)
-    HIP_TRY(c, c->sLm.reserve(at));
-    char *base = static_cast<char *>(c->sLm.p);
-    double *hist = history ? (h_hist ? reinterpret_cast<double *>(base + o_hist) : history) : nullptr;
-    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(base + o_acc) : n_accept) : nullptr;
-    BfgsArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_trees = p->n_trees;
-    a.n_grad = tab.ng;
-    a.coff = tab.doff;
-    a.boff = tab.joff;
-    a.consts_acc = base + o_ca; a.loss_acc = base + o_la; a.dloss_acc = base + o_da; a.ok_acc = reinterpret_cast<uint8_t *>(base + o_oka);
-    void *lT = base + o_lt, *dT = base + o_dt;
-    uint8_t *okT = reinterpret_cast<uint8_t *>(base + o_okt);
-    a.consts_trial = base + o_ct; a.loss_trial = lT; a.dloss_trial = dT; a.ok_trial = okT;
-    a.B = reinterpret_cast<double *>(base + o_B); a.alpha = reinterpret_cast<double *>(base + o_al);
-    a.slope = reinterpret_cast<double *>(base + o_sl); a.p = reinterpret_cast<double *>(base + o_p);
-    a.fresh = reinterpret_cast<uint8_t *>(base + o_fr); a.produced = reinterpret_cast<uint8_t *>(base + o_pr);
-    a.step0 = o.step0; a.shrink = o.shrink; a.c1 = o.c1; a.curv = o.curv;
-    a.n_accept = acc;
-
-    if (!c->nested) HIP_TRY(c, time_begin(c));
-    struct Nest { // the inner calls leave the timing events alone: the ring sees one call
-        de_ctx *c;
-        explicit Nest(de_ctx *c_) : c(c_) { c->nested++; }
-        ~Nest() { c->nested--; }
-    };
-    const de_loss_spec_t spec = *spec_in;
-    {
-        Nest nest(c);
-        auto evaluate = [&](void *l, void *d, uint8_t *k) {
-            return loss_grad_impl(c, p, Xd, N, ldX, pa_use, DE_GRAD_CONSTANT, yd, wd, &spec, l, d, nullptr, k, nullptr);
-        };
-        rc = evaluate(a.loss_acc, a.dloss_acc, a.ok_acc);
-        if (rc != DE_OK) return rc;
-        HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream));
-        HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist, c->stream));
-        const bool loop = N > 0 && o.iters > 0 && nc > 0;
-        if (!loop) // (no sample or no constant: nothing can be accepted, every row of the history is the first)
-            for (size_t r = 1; r < rows && hist; r++) HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist + r * nt, c->stream));
-        if (loop) {
-            rc = de_program_get_consts(p, a.consts_acc); // (device to device behind a device set)
-            if (rc != DE_OK) return rc;
-            for (int32_t it = 0; it < o.iters && rc == DE_OK; it++) {
-                HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream));
-                rc = set_consts_device_impl(p, a.consts_trial);
-                if (rc == DE_OK) rc = evaluate(lT, dT, okT);
-                if (rc != DE_OK) break;
-                a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
-                HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
-            }
-            // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
-            const int rc2 = set_consts_device_impl(p, a.consts_acc);
-            if (rc != DE_OK) return rc;
-            if (rc2 != DE_OK) return rc2;
-        }
-    }
-    if (!c->nested) HIP_TRY(c, time_end(c));
-    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, a.loss_acc, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ok, a.ok_acc, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
-}
-int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                       const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
-                       int32_t *n_accept) {
-    DE_REFUSE_F16("de_fit_consts_bfgs");
-    DE_NOTHROW(c, fit_consts_bfgs_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_accept));
 }
 
 } // extern "C"

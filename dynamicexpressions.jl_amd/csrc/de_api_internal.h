@@ -2,8 +2,11 @@
 //   de_api.cpp          registry, contexts, the pool of host threads, the pools of device buffers and parked programs
 //   de_api_program.cpp  de_program_create / _set_consts / _destroy, constant folding, the threaded and chained streams, verify / dump / hash
 //   de_api_eval.cpp     de_eval, de_eval_loss, de_eval_sum_certificate, de_eval_tree_array (staging, launch planning)
-//   de_api_grad.cpp     de_eval_grad / _diff / _pullback_dX, de_eval_loss_grad(_by_class): the generic gradient program; glue around the
+//   de_api_grad.cpp     what PRODUCES gradients and matrices from X: de_eval_grad / _diff / _pullback_dX, de_eval_loss_grad(_by_class),
+//                       de_eval_loss_gn(_ex, _wide), de_eval_fit_stats_grad(_wide): the generic gradient program; glue around the
 //                       host-only encoders of the threaded and reverse streams (de_grad_encode.cpp), de_lower_tape_grad
+//   de_api_fit.cpp      what CONSUMES them: de_gn_lm_step / de_fit_stats_lm_step (and _wide), de_fit_consts_lm(_ex, _wide),
+//                       de_fit_consts_lm_scaled(_wide), de_fit_consts_bfgs — one driver (run_fit) — and their host hooks
 //   de_api_tree_params.cpp  de_tape_params_to_consts, de_eval*_tree_params: per-tree parameter matrices, class by class around the calls above
 // No behaviour changed in the split: de_program_stream_hash and the whole test suite are the check.
 #ifndef DE_API_INTERNAL_H
@@ -354,11 +357,121 @@ int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, 
 int consts_materialise(de_program *p);
 // the body of de_program_set_consts_device (de_api_program.cpp): de_fit_consts_lm sets its trial and accepted constants through it
 int set_consts_device_impl(de_program *p, const void *d_consts);
-// what de_fit_consts_bfgs and de_fit_tree_params_bfgs refuse about their options (de_api_grad.cpp): null = good, else the reason
+// what de_fit_consts_bfgs and de_fit_tree_params_bfgs refuse about their options (de_api_fit.cpp): null = good, else the reason
 const char *bfgs_opts_problem(const de_bfgs_opts_t *o);
 // releases a program's GnWideCache (de_api_grad.cpp); the caller has synchronised the stream
 void gn_wide_release(de_program *p);
 }
+
+// The host inputs of a fit or of a wide evaluation, staged ONCE for all its inner calls (de_api_eval.cpp) into the buffers a single call would
+// stage them in (sX, sY, sW, sParams, sClasses), with one synchronisation if anything was staged; device pointers, and every pointer when
+// N == 0, pass through.  `pa` is the caller's or &pad (a FitInputs is not copied).
+struct FitInputs {
+    const void *Xd = nullptr, *yd = nullptr, *wd = nullptr;
+    de_param_args_t pad;
+    const de_param_args_t *pa = nullptr;
+};
+extern "C" int stage_fit_inputs(de_ctx *c, const de_program *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                                const void *y, const void *w, FitInputs *out);
+
+// Inside a call made of several inner calls: those leave the timing events alone (the ring sees one call); restored on every exit path.
+struct NestGuard {
+    de_ctx *c;
+    explicit NestGuard(de_ctx *c_) : c(c_) { c->nested++; }
+    ~NestGuard() { c->nested--; }
+    NestGuard(const NestGuard &) = delete;
+    NestGuard &operator=(const NestGuard &) = delete;
+};
+
+// A device buffer laid out in 256-byte granules.  place<T>(count) hands out regions (wanted = false: none, its pointer is null); reserve()
+// grows the buffer — behind a synchronisation, for growing frees what queued work may still use — and from then on ptr(region) is typed.
+struct Workspace {
+    template <class T> struct Region { size_t off; bool wanted; };
+    size_t at = 0;
+    char *base = nullptr;
+    template <class T> Region<T> place(size_t count, bool wanted = true) {
+        const Region<T> r{at, wanted};
+        if (wanted) at += (std::max<size_t>(count * sizeof(T), 1) + 255) & ~(size_t)255;
+        return r;
+    }
+    int reserve(de_ctx *c, DevBuf &buf) {
+        if (at > buf.cap) HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, buf.reserve(at));
+        base = static_cast<char *>(buf.p);
+        return DE_OK;
+    }
+    template <class T> T *ptr(Region<T> r) const { return r.wanted ? reinterpret_cast<T *>(base + r.off) : nullptr; }
+};
+
+// The outputs of a fit, each resolved once.  An output the kernels write in place (history, n_accept) is the caller's device pointer or a
+// device image copied to the host at the end; an output the fit's state holds (loss / sse, stats, ystats, ok) is copied to the caller
+// whichever side its pointer is on (null: not wanted).  finish() issues the copies and waits once if any went to the host (or `wait`).
+struct FitOutputs {
+    struct Copy { void *user; const void *dev; size_t bytes; bool host; };
+    Copy q[6];
+    int n = 0;
+    static bool on_host(const void *user) { return user && !is_device_ptr(user); }
+    template <class T> T *in_place(T *user, bool host, T *image, size_t count) {
+        if (!host) return user;
+        q[n++] = Copy{user, image, count * sizeof(T), true};
+        return image;
+    }
+    void from_state(void *user, const void *dev, size_t bytes) {
+        if (user) q[n++] = Copy{user, dev, bytes, !is_device_ptr(user)};
+    }
+    int finish(de_ctx *c, bool wait = false) {
+        for (int k = 0; k < n; k++) {
+            HIP_TRY(c, hipMemcpyAsync(q[k].user, q[k].dev, q[k].bytes, q[k].host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+            wait = wait || q[k].host;
+        }
+        if (wait) HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return DE_OK;
+    }
+};
+
+// What loss_grad_impl adds to its launch (de_api_grad.cpp).  GnPlan — de_eval_loss_gn: the kernels' Gauss-Newton tree end and G (G + 1) / 2
+// more reduction columns per tree of at most DE_GN_MAX_ROWS rows; jtj_offsets: host, element offset of every tree's G x G block (null:
+// packed); e_floor: the residual floor of the kind's curvature weight (the spec itself is loss_grad_impl's argument)
+struct GnPlan {
+    void *jtj;
+    const int64_t *jtj_offsets;
+    double e_floor;
+    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_loss_gn_wide: DE_GN_WIDE_MAX_ROWS)
+};
+// FitPlan — de_eval_fit_stats_grad: the kernels' fit-statistics tree end.  A tree owns FIT_COLS + 3 G reduction columns
+// and, where a matrix is wanted and G <= DE_GN_MAX_ROWS, G (G + 1) / 2 more; loss_grad_impl's dloss / dloss_offsets carry dmom and its
+// offsets (3 G doubles per tree), its loss is null and its spec L2 (unused).  Always forward duals.
+struct FitPlan {
+    double *stats, *ystats;
+    void *jtj; // may be null: no matrix wanted
+    const int64_t *jtj_offsets;
+    int rows_n0 = DE_GN_MAX_ROWS; // N == 0: the widest tree whose block is 0 rather than NaN (de_eval_fit_stats_grad_wide: DE_GN_WIDE_MAX_ROWS)
+};
+struct ByClassPlan;
+extern "C" {
+// The evaluations the fits of de_api_fit.cpp are made of (de_api_grad.cpp): the bodies of de_eval_loss_grad_ex / de_eval_loss_gn_ex /
+// de_eval_fit_stats_grad (a GnPlan / FitPlan), de_eval_loss_gn_wide and de_eval_fit_stats_grad_wide
+int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                   const void *w, const de_loss_spec_t *spec, void *loss, void *dloss, const int64_t *dloss_offsets, uint8_t *ok,
+                   ByClassPlan *plan, bool first_kinds_only = false, const GnPlan *gn = nullptr, const FitPlan *fit = nullptr);
+int gn_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode, const void *y,
+                 const void *w, const de_loss_spec_t *spec, double e_floor, void *loss, void *dloss, const int64_t *dloss_offsets, void *jtj,
+                 const int64_t *jtj_offsets, uint8_t *ok);
+int fit_stats_grad_wide_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, int mode,
+                             const void *y, const void *w, double *stats, double *ystats, double *dmom, const int64_t *dmom_offsets, void *jtj,
+                             const int64_t *jtj_offsets, uint8_t *ok);
+// de_gn_spec_check with its reason (null = good; *rc: DE_ERR_INVALID_ARG or DE_ERR_UNSUPPORTED).  dtype < 0: the element type is not known.
+const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtype, int *rc, char *buf, size_t cap);
+// DE_F16 and complex programs evaluate only: every gradient / fused-loss / fit entry point refuses them before it
+// touches an output (de_api_grad.cpp)
+int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what);
+int refuse_complex(de_ctx_t *c, const char *what);
+}
+#define DE_REFUSE_F16(WHAT)                                                 \
+    do {                                                                    \
+        if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT);      \
+        if (c && p && is_complex_io(p->io)) return refuse_complex(c, WHAT); \
+    } while (0)
 
 // de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)
 const char *loss_spec_problem(const de_loss_spec_t *spec, int with_gradient, char *buf, size_t cap);

@@ -348,12 +348,6 @@ static int tp_run_classes(de_ctx_t *c, de_program_t *p, TpModel model, const TpP
     return rc;
 }
 
-struct TpNest { // the inner calls leave the timing events alone: the ring sees one call
-    de_ctx *c;
-    explicit TpNest(de_ctx *c_) : c(c_) { c->nested++; }
-    ~TpNest() { c->nested--; }
-};
-
 static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpModel model, const void *X, int64_t N, int64_t ldX,
                             const de_tree_params_t *tp, const TpOut &o, uint8_t *ok) {
     TpPlan pl;
@@ -377,7 +371,7 @@ static int tree_params_impl(de_ctx_t *c, de_program_t *p, const char *what, TpMo
 
     if (!c->nested) HIP_TRY(c, time_begin(c));
     {
-        TpNest nest(c);
+        NestGuard nest(c);
         if (nc > 0 && (rc = de_program_get_consts(p, d.base)) != DE_OK) return rc; // the base vector
         bool patched = false;
         rc = tp_run_classes(c, p, model, pl, d, tp->class_starts, ldX, o, out_dev, ld_dev, &patched);
@@ -487,8 +481,7 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
     }
 
     // ---- the fit's part of the pool ----
-    const bool h_hist = history && !is_device_ptr(history), h_acc = n_accept && !is_device_ptr(n_accept);
-    const bool h_loss = loss && !is_device_ptr(loss), h_ok = !is_device_ptr(ok), h_par = n_cells > 0 && !is_device_ptr(params_out);
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept), h_par = n_cells > 0 && !is_device_ptr(params_out);
     const size_t rows = (size_t)bo.iters + 1, pk = (size_t)npk, blk = nt * (size_t)C * (size_t)ld;
     size_t at = 0;
     const size_t o_pw = tp_place(&at, blk * es), o_ca = tp_place(&at, pk * es), o_ct = tp_place(&at, pk * es), o_la = tp_place(&at, nt * es),
@@ -511,8 +504,11 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
     ta.params = pw;
     ta.dloss = fit + o_dl;
     ta.dparams = fit + o_dp;
-    double *hist = history ? (h_hist ? reinterpret_cast<double *>(fit + o_hist) : history) : nullptr;
-    int32_t *acc = n_accept ? (h_acc ? reinterpret_cast<int32_t *>(fit + o_acc) : n_accept) : nullptr;
+    FitOutputs out; // (de_api_internal.h: the fits of de_api_fit.cpp resolve and copy theirs the same way)
+    out.from_state(loss, fit + o_la, nt * es);
+    out.from_state(ok, fit + o_oka, nt);
+    double *hist = out.in_place(history, h_hist, reinterpret_cast<double *>(fit + o_hist), rows * nt);
+    int32_t *acc = out.in_place(n_accept, h_acc, reinterpret_cast<int32_t *>(fit + o_acc), nt);
     BfgsArgs a;
     std::memset(&a, 0, sizeof a);
     a.n_trees = p->n_trees;
@@ -539,7 +535,7 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
     const de_loss_spec_t spec = *spec_in;
     o.spec = &spec;
     {
-        TpNest nest(c);
+        NestGuard nest(c);
         bool patched = false, begun = false;
         // one evaluation at (d.base, pw): de_eval_loss_grad_tree_params' launches, then the gradient packed
         auto evaluate = [&](void *l, void *g, uint8_t *k, bool install) -> int {
@@ -602,12 +598,7 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
         if (ld == P) HIP_TRY(c, hipMemcpyAsync(params_out, pw, blk * es, kind, c->stream));
         else HIP_TRY(c, hipMemcpy2DAsync(params_out, (size_t)ld * es, pw, (size_t)ld * es, (size_t)P * es, nt * (size_t)C, kind, c->stream));
     }
-    if (loss) HIP_TRY(c, hipMemcpyAsync(loss, a.loss_acc, nt * es, h_loss ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ok, a.ok_acc, nt, h_ok ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-    if (h_hist) HIP_TRY(c, hipMemcpyAsync(history, hist, rows * nt * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_acc) HIP_TRY(c, hipMemcpyAsync(n_accept, acc, nt * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_par || h_loss || h_ok || h_hist || h_acc) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DE_OK;
+    return out.finish(c, h_par);
 }
 int de_fit_tree_params_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp, const void *y,
                             const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *params_out, void *loss, uint8_t *ok,
