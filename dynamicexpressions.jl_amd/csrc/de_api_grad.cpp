@@ -40,7 +40,7 @@ static int ensure_generic_code(de_ctx *c, de_program *p) {
         // bound per worker into a vector of its own, then concatenated (10^4 trees: 3 ms on one thread)
         build_stream_by_trees<BoundInstr>(p->n_trees, &p->gbcode, &p->gbcode_off, [&](int64_t t, std::vector<BoundInstr> *out) {
             const int32_t i0 = p->code_off[(size_t)t], i1 = p->code_off[(size_t)t + 1];
-            bind_tree(p->code.data() + i0, (size_t)(i1 - i0), true, p->n_features, out);
+            bind_tree_grad(p->code.data() + i0, (size_t)(i1 - i0), p->n_features, out);
         });
         match_const_sites(p->code, p->code_off, p->gbcode, p->gbcode_off, p->n_trees,
                           [](const BoundInstr &b) { return bop_is_const_source(b.bop); }, &p->gbsite);
@@ -274,7 +274,7 @@ int64_t de_lower_tape_grad(int dtype, const de_tape_node_t *nodes, int64_t n_nod
         nw = de_lower_tape(dtype, nodes, n_nodes, consts, n_consts, n_features, n_params, options, gen.data(), nw, lmeta);
         if (nw < 0) return nw;
         std::vector<BoundInstr> gb;
-        bind_tree(reinterpret_cast<const Instr *>(gen.data()), (size_t)nw / 4, true, n_features, &gb);
+        bind_tree_grad(reinterpret_cast<const Instr *>(gen.data()), (size_t)nw / 4, n_features, &gb);
         const std::vector<int32_t> gb_off = {0, (int32_t)gb.size()};
         bool cse = false; // (a CSE tape announces itself by its markers)
         for (int64_t i = 0; i < n_nodes; i++)

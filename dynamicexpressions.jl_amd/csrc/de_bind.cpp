@@ -91,6 +91,18 @@ void bind_tree(const Instr *code, size_t n, bool ee, int n_features, std::vector
     }
 }
 
+void bind_tree_grad(const Instr *code, size_t n, int n_features, std::vector<BoundInstr> *out) {
+    bool any = false;
+    for (size_t i = 0; i < n && !any; i++) any = (code[i].hdr & H_SWAPPED) != 0;
+    if (!any) return bind_tree(code, n, true, n_features, out);
+    std::vector<Instr> named(code, code + n);
+    for (Instr &ins : named) {
+        const uint32_t op = ins.hdr & H_OP_MASK;
+        if ((ins.hdr & H_SWAPPED) && (op == DE_B_MAX || op == DE_B_MIN)) ins.hdr = (ins.hdr & ~H_OP_MASK) | (op == DE_B_MAX ? DOP_RMAX : DOP_RMIN);
+    }
+    bind_tree(named.data(), n, true, n_features, out);
+}
+
 // ---- superinstruction pass ---------------------------------------------------------------------
 namespace {
 struct HotBin { int k; bool cst, out; };

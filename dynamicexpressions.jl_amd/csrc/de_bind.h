@@ -130,7 +130,7 @@ constexpr uint32_t top_bin2(int k, bool cst, bool out, bool push) { return TOP_B
 // the dense  g1*d1[k] + g2*d2[k]  then needs no one-hot materialisation.  Window width GC gives
 // NS = GC + 2 seed variants; ids depend on GC (one module per GC anyway).
 constexpr int GOP_MAX = 760; // >= gop_count(8)
-// hot binary operators of the gradient kernels: ADD SUB RSUB MUL DIV RDIV | MAX MIN  (the lowering treats max/min as commutative)
+// hot binary operators of the gradient kernels: ADD SUB RSUB MUL DIV RDIV | MAX MIN  (a max / min the lowering swapped is bound DOP_RMAX / DOP_RMIN and stays generic)
 constexpr int GBIN_K = 8;
 // hot unary operators of the gradient kernels: cos exp sin | neg square cube abs log safe_log sqrt safe_sqrt tanh relu
 constexpr int GUN_K = 13;
@@ -333,5 +333,8 @@ void assure_tree_fact(const BoundInstr *f, size_t n, int n_features, double xmax
 // slot_shift: added to every SPILL-SLOT row (rows >= n_features of the lowering: pushes, popped operands, ternary operands, shared rows) —
 // the stream variant of wave w > 0 of a wave group keeps its slots behind the staged parameter rows (de_api_program.cpp make_wave_variants)
 void bind_tree(const Instr *code, size_t n, bool early_exit, int n_features, std::vector<BoundInstr> *out, int param_row_base = -1, int slot_shift = 0);
+// The binding of the GRADIENT program (early-exit binding: every value the reference tests is tested): as bind_tree, but a max / min that
+// the lowering swapped (H_SWAPPED) is bound as DOP_RMAX / DOP_RMIN, whose partials at a tie go to the operator's own argument order
+void bind_tree_grad(const Instr *code, size_t n, int n_features, std::vector<BoundInstr> *out);
 
 } // namespace de

@@ -172,6 +172,8 @@ __global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
             case DOP_RREM: fop = DE_B_REM; rev = true; break;                                      \
             case DOP_RGREATER: fop = DE_B_GREATER; rev = true; break;                              \
             case DOP_RPOW_ABS2: fop = DE_B_POW_ABS2; rev = true; break;                            \
+            case DOP_RMAX: fop = DE_B_MAX; rev = true; break;                                      \
+            case DOP_RMIN: fop = DE_B_MIN; rev = true; break;                                      \
             default: break;                                                                        \
             }                                                                                      \
             const BG<T> r = rev ? binary_vg<T>(fop, xb, x) : binary_vg<T>(fop, x, xb);             \

@@ -271,6 +271,8 @@ template <typename T, int GC> __device__ __noinline__ GState<T, GC> g_gen_apply(
         case DOP_RREM: fop = DE_B_REM; rev = true; break;
         case DOP_RGREATER: fop = DE_B_GREATER; rev = true; break;
         case DOP_RPOW_ABS2: fop = DE_B_POW_ABS2; rev = true; break;
+    case DOP_RMAX: fop = DE_B_MAX; rev = true; break;
+    case DOP_RMIN: fop = DE_B_MIN; rev = true; break;
         default: break;
         }
         LV(T) gx, gy;

@@ -231,6 +231,10 @@ struct Lowerer {
         default: *unsupported = true; return op;
         }
     }
+    // max / min keep their opcode when swapped (the value commutes); the partials at a tie do not: the gradient binding reads the mark
+    static void mark_swapped(Instr &ins, uint32_t op) {
+        if (op == DE_B_MAX || op == DE_B_MIN) ins.hdr |= H_SWAPPED;
+    }
     void op_flags(Instr &ins, const LNode &n) {
         if (n.constfold) ins.hdr |= H_CHECK_ALWAYS;
         if (n.inject) ins.hdr |= H_INJECT;
@@ -281,6 +285,7 @@ struct Lowerer {
                 gen(r, depth);
                 bool flag;
                 Instr &ins = emit(swapped(n.op, &flag));
+                mark_swapped(ins, n.op);
                 set_leaf_operand(ins, l);
                 op_flags(ins, n);
                 return;
@@ -299,6 +304,7 @@ struct Lowerer {
             gen(second, next_depth);
             bool flag;
             Instr &ins = emit(lf ? swapped(n.op, &flag) : n.op); // left first: result = op(pop = l, acc = r)
+            if (lf) mark_swapped(ins, n.op);
             set_pop_operand(ins, pop_slot);
             op_flags(ins, n);
             return;

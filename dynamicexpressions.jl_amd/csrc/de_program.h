@@ -28,6 +28,11 @@ enum : uint32_t {
     DOP_RREM = 0xF5,
     DOP_RGREATER = 0xF6,
     DOP_RPOW_ABS2 = 0xF7,
+    // max / min with their operands swapped.  The VALUES commute, so the lowering keeps DE_B_MAX / DE_B_MIN and only marks the
+    // instruction H_SWAPPED, which every eval path ignores; the PARTIALS at a tie do not (a tie of max goes to the second
+    // argument, of min to the first), so the gradient binding (bind_tree_grad, de_bind.h) names these reversed forms
+    DOP_RMAX = 0xF8,
+    DOP_RMIN = 0xF9,
 };
 
 // Operand-B kinds (hdr bits 8..10).  SRC_ROW reads an LDS row: rows 0..F-1 are the
@@ -47,6 +52,7 @@ constexpr uint32_t H_INJECT = 1u << 14;       // reference fused deg1 kernels: n
 // tested output (x+y, x-y, x*y, numerator of x/y, cos, ...): the flag stays exact while most
 // tests disappear from the instruction stream.
 constexpr uint32_t H_CHECK_OUT = 1u << 15;
+constexpr uint32_t H_SWAPPED = 1u << 16;      // max / min only: acc = op(B, acc) (read by the gradient binding alone, see DOP_RMAX)
 constexpr uint32_t H_PUSH_SHIFT = 20;         // bits 20..23: slot written by H_PUSH
 constexpr uint32_t H_POPC_SHIFT = 24;         // bits 24..27: second slot of a ternary op
 constexpr uint32_t H_SLOT_MASK = 0xFu;

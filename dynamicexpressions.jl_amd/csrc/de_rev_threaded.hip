@@ -5,8 +5,10 @@
 // for EVERY gradient row k, never the [n_grad, N] Jacobian itself.  Forward duals (de_grad_threaded.hip, the
 // arithmetic of eval_grad_tree_array, src/EvaluateDerivative.jl:340-365) cost (1 + n_grad) values per node;
 // one forward sweep that keeps every operator's PARTIALS plus one backward sweep over the same instruction
-// stream costs ~2 values per node whatever n_grad is.  Same partial functions (ChainRules scalar rules,
-// de_grad_common.h), same validity rule — a tree is incomplete iff a tested value, a partial or a gradient
+// stream costs ~2 values per node whatever n_grad is.  Same partials (ChainRules scalar rules, de_grad_common.h): the
+// generic and ternary handlers call unary_vg / binary_vg / ternary_vg, the hot handlers f_bin (* / max min) and f_un
+// (Float32 cos exp sin; gun_inline) restate their expressions and tests/test_gpu_loss_grad_accuracy.py holds every
+// handler to the same per-operator table.  Same validity rule — a tree is incomplete iff a tested value, a partial or a gradient
 // entry of some sample is non-finite (a non-finite partial always reaches the reference's gradient matrix:
 // g * 0 = NaN in its dense update, :355-361) — but the products of a gradient entry are associated leaf-wards
 // instead of root-wards, so entries agree with the forward Jacobian to rounding, not bit for bit.
@@ -124,7 +126,7 @@ template <typename T, int K, int SRC, bool CHK> __device__ __forceinline__ GStat
             gl = (K == 6) == gt ? T(1) : T(0);
             gr = (K == 6) == gt ? T(0) : T(1);
         }
-        else { v = lx / ly; gl = T(1) / ly; gr = -(v * gl); }
+        else { v = lx / ly; gl = T(1) / ly; gr = -(v / ly); } // binary_vg's expressions: -(v * gl) rounds twice more (E up to 1.2 of a bound of 1)
         const uint32_t pr = rprow<T, SRC>(st, la, imm);
         const T ga = REV ? gr : gl, gb = REV ? gl : gr;
         *RLDS(T, pr) = ga;
@@ -184,6 +186,8 @@ template <typename T> __device__ __noinline__ GState<T> r_gen_apply(GState<T> st
     case DOP_RREM: fop = DE_B_REM; rev = true; break;
     case DOP_RGREATER: fop = DE_B_GREATER; rev = true; break;
     case DOP_RPOW_ABS2: fop = DE_B_POW_ABS2; rev = true; break;
+    case DOP_RMAX: fop = DE_B_MAX; rev = true; break;
+    case DOP_RMIN: fop = DE_B_MIN; rev = true; break;
     default: break;
     }
     const BG<T> r = rev ? binary_vg<T>(fop, b, st.x) : binary_vg<T>(fop, st.x, b);
