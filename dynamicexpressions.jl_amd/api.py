@@ -63,6 +63,7 @@ EXPORTS = [
     "de_tree_params_accumulate_host",
     "de_fit_tree_params_bfgs", "de_tree_params_pack_host", "de_tree_params_unpack_host",
     "de_lower_tape_assured_fact",
+    "de_nm_max_rows", "de_nm_ask_host", "de_nm_tell_host", "de_fit_consts_nm",
 ]
 
 
@@ -101,6 +102,11 @@ class BfgsOpts(C.Structure):
     """``de_bfgs_opts_t``: what ``de_fit_consts_bfgs`` takes besides the data (null: 20 iterations, step0 1, shrink 0.5, c1 1e-4, curv 1e-8)."""
     _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("step0", C.c_double), ("shrink", C.c_double), ("c1", C.c_double),
                 ("curv", C.c_double)]
+
+
+class NmOpts(C.Structure):
+    """``de_nm_opts_t``: what ``de_fit_consts_nm`` takes besides the data (null: 200 rounds, a 0.025, b 0.5, f_tol 0)."""
+    _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("f_tol", C.c_double)]
 
 
 # de_loss_kind_t (include/de_hip.h): name -> enum value.  "pullback" belongs to the gradient entry points only.
@@ -195,6 +201,9 @@ class FitStats:
 GN_MAX_ROWS = 8  # de_gn_max_rows(): the widest tree (gradient rows of the library's layout) de_eval_loss_gn forms the matrix of
 GN_WIDE_MAX_ROWS = 32  # de_gn_wide_max_rows(): ... and de_eval_loss_gn_wide (``wide=True``)
 BFGS_MAX_ROWS = 32  # de_bfgs_max_rows(): the widest tree de_fit_consts_bfgs fits
+NM_MAX_ROWS = 32  # de_nm_max_rows(): the widest tree de_fit_consts_nm fits
+# the phases of the Nelder-Mead state (csrc/de_nm.h; ``NmState.st[0]``)
+NM_BUILD, NM_REFLECT, NM_EXPAND, NM_CONTRACT_OUT, NM_CONTRACT_IN, NM_SHRINK, NM_DONE = range(7)
 
 
 def gn_offsets(n_grad):
@@ -557,6 +566,112 @@ def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
 
 
+class NmState:
+    """The Nelder-Mead state of one tree of ``G`` constants (include/de_hip.h de_fit_consts_nm), as ``nm_ask_host`` / ``nm_tell_host``
+    take it, all float64: ``V[G + 1, G]`` the vertices, ``f[G + 1]`` their losses (+inf: failed or not evaluated yet), ``c``, ``xr``,
+    ``fr``, and ``st = [phase, cursor, l0]`` (int32).  A fresh state is BUILD(1) around ``x0`` (values of ``dtype``) with loss ``f0``."""
+
+    def __init__(self, x0, f0: float, dtype, ok0: bool = True):
+        x0 = np.asarray(x0, dtype=dtype).astype(np.float64).reshape(-1)
+        G = x0.size
+        self.G, self.dtype = G, np.dtype(dtype)
+        self.V = np.zeros((G + 1, G))
+        self.V[0] = x0
+        self.f = np.full(G + 1, np.inf)
+        f0 = float(f0)
+        self.f[0] = f0 if ok0 and math.isfinite(f0) else np.inf
+        self.st = np.array([NM_BUILD, 1, 0], dtype=np.int32)
+        self.c, self.xr, self.fr = np.zeros(G), np.zeros(G), np.zeros(1)
+
+    @property
+    def phase(self) -> int:
+        return int(self.st[0])
+
+    @property
+    def best(self) -> int:
+        """l: the vertex of the smallest loss, ties to the lowest index — the accepted vertex."""
+        return int(np.argmin(self.f))
+
+
+def nm_ask_host(state: NmState, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0):
+    """``de_nm_ask_host``: the trial constants of the state's phase (csrc/de_nm.h, the code the kernels run; no GPU needed), an array of
+    the state's dtype; the state moves in place (BUILD and SHRINK write the vertex, REFLECT ``c`` and ``xr`` or the phase DONE).
+    ``None`` with the state untouched: G outside 1 .. ``NM_MAX_ROWS``."""
+    opts = NmOpts(0, 0, float(a), float(b), float(f_tol))
+    trial = np.zeros(max(state.G, 1), dtype=state.dtype)
+    rc = library().de_nm_ask_host(state.G, _dtype_code(state.dtype), C.byref(opts), state.V.ctypes.data, state.f.ctypes.data,
+                                  state.st.ctypes.data, state.c.ctypes.data, state.xr.ctypes.data, trial.ctypes.data)
+    return trial[:state.G] if rc else None
+
+
+def nm_tell_host(state: NmState, f_trial: float, ok_trial: bool = True) -> bool:
+    """``de_nm_tell_host``: the phase's decision on the loss of the trial ``nm_ask_host`` returned (stored as +inf where ``ok_trial`` is
+    False or the loss is not finite); the state moves in place.  False with the state untouched: G outside 1 .. ``NM_MAX_ROWS``."""
+    return bool(library().de_nm_tell_host(state.G, _dtype_code(state.dtype), state.V.ctypes.data, state.f.ctypes.data, state.st.ctypes.data,
+                                          state.c.ctypes.data, state.xr.ctypes.data, state.fr.ctypes.data, float(f_trial), int(bool(ok_trial))))
+
+
+def _nm_opts(iters, a, b, f_tol, loss, loss_param):
+    """(``NmOpts``, ``LossSpec``) of a Nelder-Mead fit, refused as ``de_fit_consts_nm`` refuses them: a ``ValueError``."""
+    if loss == "pullback":
+        raise ValueError("loss 'pullback' is the cotangent of a pullback, not an objective")
+    spec = loss_spec(loss, loss_param, with_gradient=False)
+    opts = NmOpts(int(iters), 0, float(a), float(b), float(f_tol))
+    if (opts.iters < 0 or not (np.isfinite(opts.a) and np.isfinite(opts.b)) or (opts.a == 0.0 and opts.b == 0.0)
+            or not (np.isfinite(opts.f_tol) and opts.f_tol >= 0.0)):
+        raise ValueError("Nelder-Mead fit: iters >= 0, finite a and b that are not both 0, and a finite f_tol >= 0")
+    return opts, spec
+
+
+def nm_fit(evaluate, install, consts0, n_consts, dtype, iters: int = 200, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0,
+           history: Optional[list] = None):
+    """The host loop of ``de_fit_consts_nm`` over the two hooks: ``evaluate(consts)`` installs a vector of all constants (``n_consts[t]``
+    per tree, values of ``dtype``) and returns (loss[n_trees], ok[n_trees]) there; ``install(consts)`` only installs.  One round is one
+    ``nm_ask_host`` per fitted tree, ONE ``evaluate`` for the whole population and one ``nm_tell_host`` per fitted tree; behind every tell
+    the tree's accepted constants and loss are the vertex of the smallest loss.  A tree that is incomplete at ``consts0`` or has no or
+    more than ``NM_MAX_ROWS`` constants keeps its constants.  Returns (consts, loss in ``dtype``, ok, n_improve); ``history`` receives
+    ``iters + 1`` rows of accepted losses (float64)."""
+    dtype, f64 = np.dtype(dtype), np.float64
+    consts = np.array(_host(consts0), dtype=dtype).reshape(-1).copy()
+    n_consts = np.asarray(n_consts, dtype=np.int64).reshape(-1)
+    nt = n_consts.size
+    if consts.size != int(n_consts.sum()):
+        raise ValueError("wrong number of constants")
+    at = np.zeros(nt + 1, dtype=np.int64)
+    np.cumsum(n_consts, out=at[1:])
+    lo, ok = evaluate(consts)
+    lo, ok = np.array(_host(lo), dtype=dtype).copy(), _host(ok).astype(bool).copy()
+    states = [NmState(consts[at[t]:at[t + 1]], lo[t], dtype) if ok[t] and 1 <= n_consts[t] <= NM_MAX_ROWS else None for t in range(nt)]
+    improve = np.zeros(nt, dtype=np.int32)
+    if history is not None:
+        history.append(lo.astype(f64))
+    for _ in range(int(iters)):
+        if all(s is None for s in states):  # (nothing can move: every row of the history is the first)
+            if history is not None:
+                history.append(lo.astype(f64))
+            continue
+        trial = consts.copy()
+        for t, s in enumerate(states):
+            if s is not None:
+                trial[at[t]:at[t + 1]] = nm_ask_host(s, a, b, f_tol)
+        lo_t, ok_t = evaluate(trial)
+        lo_t, ok_t = _host(lo_t), _host(ok_t)
+        for t, s in enumerate(states):
+            if s is None:
+                continue
+            before = s.f[s.best]
+            nm_tell_host(s, float(lo_t[t]), bool(ok_t[t]))
+            now = s.f[s.best]
+            if now < np.inf:  # the accepted state is vertex l
+                consts[at[t]:at[t + 1]] = s.V[s.best].astype(dtype)
+                lo[t] = dtype.type(now)
+                improve[t] += int(now < before)
+        if history is not None:
+            history.append(lo.astype(f64))
+    install(consts)
+    return consts, lo, ok, improve
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -693,6 +808,12 @@ def library() -> C.CDLL:
                                                 vp, vp, vp, vp, vp]
         lib.de_tree_params_pack_host.argtypes = [C.c_int, i32, vp, i32, i64, i64, vp, vp, vp]
         lib.de_tree_params_unpack_host.argtypes = [C.c_int, i32, vp, i32, i64, i64, vp, vp, vp]
+    if hasattr(lib, "de_fit_consts_nm"):  # (absent from a library built before the device Nelder-Mead fit: DE_HIP_LIB in an A/B run)
+        lib.de_nm_max_rows.argtypes = []
+        lib.de_nm_ask_host.argtypes = [C.c_int, C.c_int, C.POINTER(NmOpts), vp, vp, vp, vp, vp, vp]
+        lib.de_nm_tell_host.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int]
+        lib.de_fit_consts_nm.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(NmOpts),
+                                         vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -2002,6 +2123,57 @@ class Population:
         self.ctx.check(library().de_fit_consts_bfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
                                                     C.byref(opts), *ptrs))
         self.bfgs_accepts = acc
+        if history is not None:
+            history.extend(hist[r] for r in range(int(iters) + 1))
+        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
+    def fit_constants_nm(self, X, y, consts0, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0,
+                         loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None, classes=None,
+                         class_base: int = 1):
+        """Nelder-Mead on the constants of every tree at once, from the fused loss alone (``nm_fit``: the plain loop over ``nm_ask_host``
+        / ``nm_tell_host``; one ``eval_loss`` per round behind the one at ``consts0``) — the reference's
+        ``optimize(f, tree)``, which runs Optim's default method.  Every kind ``eval_loss`` takes is an objective, and a constant whose
+        partial is zero almost everywhere (under ``round``, ``floor``, ``sign``, ...) moves.  ``iters`` counts rounds, the ``G`` rounds
+        that build a tree's start simplex (``a``, ``b``) included; a tree stops where ``f_h - f_l <= f_tol |f_l|``.  ``consts0``:
+        ``set_constants``' layout (a shared GraphNode constant is ONE coordinate).  Incomplete trees, trees without constants and trees
+        of more than ``NM_MAX_ROWS`` constants keep ``consts0``.  Returns (consts, loss[n_trees] in the population's dtype, ok) at the
+        accepted constants, which the population holds afterwards; ``history`` (a list) receives the ``iters + 1`` rows of accepted
+        losses (float64), ``self.nm_improves`` the number of rounds that lowered each tree's accepted loss."""
+        self._refuse_f16("fit_constants_nm")
+        _nm_opts(iters, a, b, f_tol, loss, loss_param)  # (refused before the population's constants are touched)
+
+        def evaluate(consts):
+            self.set_constants(consts)
+            return self.eval_loss(X, y, weights=weights, loss=loss, loss_param=loss_param, params=params, classes=classes,
+                                  class_base=class_base)
+
+        consts, lo, ok, self.nm_improves = nm_fit(evaluate, self.set_constants, consts0, self.n_consts, self.dtype, iters, a, b, f_tol,
+                                                  history)
+        return consts, lo, ok
+
+    def fit_constants_nm_device(self, X, y, consts0=None, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5,
+                                f_tol: float = 0.0, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None,
+                                params=None, classes=None, class_base: int = 1):
+        """``fit_constants_nm`` as ONE library call (``de_fit_consts_nm``): the simplex, the trial constants and every
+        decision live on the device; no constant or loss reaches the host, and the trajectory is the host loop's bit for bit.
+        ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.
+        Returns (consts, loss[n_trees] in the population's dtype, ok) at the accepted constants, which the population holds afterwards;
+        with torch inputs all three are device tensors and nothing synchronises beyond what ``eval_loss`` does.  ``history`` (a list)
+        receives the ``iters + 1`` rows of accepted losses (float64); ``self.nm_improves`` holds the number of rounds that lowered each
+        tree's accepted loss.  GraphNode populations are served (the library call has no gradient rows to combine) unless a CONSTANT is
+        shared: the library moves one coordinate per occurrence, which would untie the occurrences — a ``ValueError``;
+        ``fit_constants_nm`` serves those."""
+        self._refuse_f16("fit_constants_nm_device")
+        opts, spec = _nm_opts(iters, a, b, f_tol, loss, loss_param)
+        if self._occ is not None:
+            raise ValueError("fit_constants_nm_device: the population shares GraphNode constants (the library moves every occurrence on "
+                             "its own): use fit_constants_nm")
+        ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_nm_device", X, y, weights, consts0, params,
+                                                                                classes, class_base)
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
+        self.ctx.check(library().de_fit_consts_nm(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
+                                                  C.byref(opts), *ptrs))
+        self.nm_improves = acc
         if history is not None:
             history.extend(hist[r] for r in range(int(iters) + 1))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))

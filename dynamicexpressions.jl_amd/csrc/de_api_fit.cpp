@@ -1,8 +1,9 @@
 // de_api_fit.cpp — C ABI (include/de_hip.h): what CONSUMES the gradients and matrices de_api_grad.cpp produces.  de_gn_lm_step /
 // de_fit_stats_lm_step (and _wide): one Levenberg-Marquardt step per tree (kernels de_lm.hip, de_gn_wide.hip, de_lm_scaled.hip,
 // de_lm_scaled_wide.hip); de_fit_consts_lm(_ex, _wide), de_fit_consts_lm_scaled(_wide) and
-// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10): three fits on the constants that are ONE driver — fit_check, stage_fit_inputs, a
-// Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host hooks that run the kernels' arithmetic.
+// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10) and de_fit_consts_nm (kernels de_nm.hip, §4.4.13): four fits on the constants that are
+// ONE driver — fit_check, stage_fit_inputs, a Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host
+// hooks that run the kernels' arithmetic.
 #include "de_api_internal.h"
 #include "de_lm.h"
 #include "de_lm_solve.h"
@@ -13,6 +14,8 @@
 #include "de_lm_project_wide.h"
 #include "de_bfgs.h"
 #include "de_bfgs_dev.h"
+#include "de_nm.h"
+#include "de_nm_dev.h"
 
 extern "C" {
 // ---- the host hooks: the arithmetic of the step, projection and BFGS kernels on host buffers (de_lm_solve.h, de_lm_solve_wide.h,
@@ -64,6 +67,26 @@ int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const
     if (!B || !fresh || !s || !yv) return 0;
     return bfgs_update(G, B, fresh, s, yv, curv);
 }
+int de_nm_max_rows(void) { return NM_MAX_ROWS; }
+static bool nm_hook_args(int G, int dtype, const int32_t *st) {
+    return G >= 1 && G <= NM_MAX_ROWS && (dtype == DE_F32 || dtype == DE_F64) && st && st[0] >= NM_BUILD && st[0] <= NM_DONE &&
+           (st[0] == NM_REFLECT || st[0] == NM_DONE || (st[1] >= 0 && st[1] <= G && st[2] >= 0 && st[2] <= G));
+}
+int de_nm_ask_host(int G, int dtype, const de_nm_opts_t *opts, double *V, const double *f, int32_t *st, double *c, double *xr, void *trial) {
+    if (!V || !f || !c || !xr || !trial || !nm_hook_args(G, dtype, st)) return 0;
+    const double a = opts ? opts->a : 0.025, b = opts ? opts->b : 0.5, f_tol = opts ? opts->f_tol : 0.0;
+    if (dtype == DE_F32) nm_ask_tree<float>(G, 0, G, true, a, b, f_tol, V, f, st, c, xr, static_cast<float *>(trial));
+    else nm_ask_tree<double>(G, 0, G, true, a, b, f_tol, V, f, st, c, xr, static_cast<double *>(trial));
+    return 1;
+}
+int de_nm_tell_host(int G, int dtype, double *V, double *f, int32_t *st, const double *c, const double *xr, double *fr, double f_trial,
+                    int ok_trial) {
+    if (!V || !f || !c || !xr || !fr || !nm_hook_args(G, dtype, st)) return 0;
+    const double F = nm_loss(f_trial, ok_trial != 0);
+    if (dtype == DE_F32) nm_tell_tree<float>(G, 0, G, true, V, f, st, c, xr, fr, F);
+    else nm_tell_tree<double>(G, 0, G, true, V, f, st, c, xr, fr, F);
+    return 1;
+}
 
 // what the fits refuse about their options: null = good, else the reason
 const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
@@ -72,6 +95,13 @@ const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
     for (const double v : {o->step0, o->c1, o->curv})
         if (!(std::isfinite(v) && v > 0.0)) return "de_bfgs_opts_t: step0, c1 and curv must be finite and positive";
     if (!(o->shrink > 0.0 && o->shrink < 1.0)) return "de_bfgs_opts_t: shrink must lie in (0, 1)";
+    return nullptr;
+}
+static const char *nm_opts_problem(const de_nm_opts_t *o) {
+    if (o->reserved != 0) return "de_nm_opts_t: reserved must be 0";
+    if (o->iters < 0) return "de_nm_opts_t: iters < 0";
+    if (!(std::isfinite(o->a) && std::isfinite(o->b)) || (o->a == 0.0 && o->b == 0.0)) return "de_nm_opts_t: a and b must be finite and not both 0";
+    if (!(std::isfinite(o->f_tol) && o->f_tol >= 0.0)) return "de_nm_opts_t: f_tol must be finite and not negative";
     return nullptr;
 }
 static const char *lm_opts_problem(const de_lm_opts_t *o) {
@@ -270,18 +300,19 @@ int de_fit_stats_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int
 // The refusals, in their order: the context; the spec (spec_check: the driver's own, empty where the fit takes none); a CSE program
 // (fold_hint: what its caller does with the rows of a shared constant); a tree whose constant rows are not its constants; the options
 // (opts_why: lm_opts_problem / bfgs_opts_problem); N and the null buffers (`required` must not be null when there is a tree); ldX; the
-// parameter arguments.  `what`: the name in the texts (the narrow entry point's, for its _ex and _wide forms too).
+// parameter arguments.  `what`: the name in the texts (the narrow entry point's, for its _ex and _wide forms too).  gradient_rows = false
+// (de_fit_consts_nm: no gradient): the two refusals about constant rows are skipped.
 static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char *fold_hint, const std::function<int()> &spec_check,
                      const char *opts_why, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                     std::initializer_list<const void *> required) {
+                     std::initializer_list<const void *> required, bool gradient_rows = true) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (spec_check)
         if (const int rc = spec_check()) return rc;
-    if (!p->in_cse.empty())
+    if (gradient_rows && !p->in_cse.empty())
         return fail(c, DE_ERR_UNSUPPORTED, "%s: a program made by de_program_create_cse has one gradient row per occurrence of a shared constant "
                                            "(%s); such callers keep the host loop", what, fold_hint);
-    for (int64_t t = 0; t < p->n_trees; t++)
+    for (int64_t t = 0; gradient_rows && t < p->n_trees; t++)
         if (de_program_n_grad(p, t, DE_GRAD_CONSTANT) != p->const_off[(size_t)t + 1] - p->const_off[(size_t)t])
             return fail(c, DE_ERR_UNSUPPORTED, "%s: tree %lld has %lld constant rows for %lld constants", what, (long long)t,
                         (long long)de_program_n_grad(p, t, DE_GRAD_CONSTANT), (long long)(p->const_off[(size_t)t + 1] - p->const_off[(size_t)t]));
@@ -634,6 +665,99 @@ int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
                        int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_bfgs");
     DE_NOTHROW(c, fit_consts_bfgs_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_accept));
+}
+
+// ---- de_fit_consts_nm (kernels: de_nm.hip, arithmetic: de_nm.h) ----------------------------------------------------------
+// The same fit with every evaluation de_eval_loss_ex's — the fused loss alone, no gradient program — and the kernels of de_nm.hip: one
+// round is ask, the trial constants installed, one loss launch, tell.  No gradient rows: programs made by de_program_create_cse are served.
+static int fit_consts_nm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                              const void *w, const de_loss_spec_t *spec_in, const de_nm_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                              int32_t *n_improve) {
+    const de_nm_opts_t defaults{200, 0, 0.025, 0.5, 0.0};
+    const de_nm_opts_t o = opts ? *opts : defaults;
+    const auto spec_check = [&]() -> int {
+        char why[160];
+        if (loss_spec_problem(spec_in, 0, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_nm: DE_LOSS_PULLBACK is no objective");
+        if (!p->threaded)
+            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_nm needs the LDS-tiled kernel (feature matrix too wide for this build)");
+        return DE_OK;
+    };
+    int rc = fit_check(c, p, "de_fit_consts_nm", "", spec_check, nm_opts_problem(&o), X, N, ldX, pa, {ok, y}, false);
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    std::vector<int64_t> voff(nt); // the simplex: (G + 1) G vertices and G + 1 losses of every tree that can be fitted, none of the others
+    int64_t vspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t g = p->n_consts_tree[t];
+        voff[t] = vspan;
+        if (g >= 1 && g <= NM_MAX_ROWS) vspan += (g + 1) * (g + 1);
+    }
+    LmTables tab; // packed: the constants' offsets; the matrix offsets are the simplex's
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, voff.data(), &tab)) != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, losses and flags; the simplex, c, xr, fr and three ints per tree; the images
+    const bool h_hist = FitOutputs::on_host(history), h_imp = FitOutputs::on_host(n_improve);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
+    const auto V = ws.place<double>((size_t)vspan), cen = ws.place<double>(span), xr = ws.place<double>(span), fr = ws.place<double>(nt),
+               r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto st = ws.place<int32_t>(3 * nt), r_imp = ws.place<int32_t>(nt, h_imp);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(loss, ws.ptr(lA), nt * es);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    NmArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.coff = tab.doff;
+    a.voff = tab.joff;
+    a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.ok_trial = ws.ptr(okT);
+    a.V = ws.ptr(V); a.c = ws.ptr(cen); a.xr = ws.ptr(xr); a.fr = ws.ptr(fr);
+    a.st = ws.ptr(st);
+    a.a = o.a; a.b = o.b; a.f_tol = o.f_tol;
+    a.n_improve = out.in_place(n_improve, h_imp, ws.ptr(r_imp), nt);
+    const de_loss_spec_t spec = *spec_in;
+    FitLoop f;
+    f.consts_acc = a.consts_acc;
+    f.consts_trial = a.consts_trial;
+    f.last_kernel = "de_nm_tell_kernel";
+    f.evaluate = [&](bool trial) -> int {
+        return de_eval_loss_ex(c, p, in.Xd, N, ldX, in.pa, in.yd, in.wd, &spec, ws.ptr(trial ? lT : lA), ws.ptr(trial ? okT : okA));
+    };
+    f.init = [&]() -> int {
+        if (nc > 0) { // (the accepted constants are the kernel's V_0: it needs them before run_fit reads them for the loop)
+            const int rc1 = de_program_get_consts(p, a.consts_acc);
+            if (rc1 != DE_OK) return rc1;
+        }
+        HIP_TRY(c, launch_nm_init(p->dtype, a, c->stream));
+        return DE_OK;
+    };
+    f.first_history = f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int { HIP_TRY(c, launch_nm_ask(p->dtype, a, c->stream)); return DE_OK; };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_nm_tell(p->dtype, a, c->stream));
+        return DE_OK;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_nm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                     const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                     int32_t *n_improve) {
+    DE_REFUSE_F16("de_fit_consts_nm");
+    DE_NOTHROW(c, fit_consts_nm_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_improve));
 }
 
 } // extern "C"

@@ -1112,6 +1112,54 @@ function fit_population_constants_bfgs!(
     return constants, lossv, ok .!= 0x00, history, n_accept
 end
 
+struct NmOpts               # de_nm_opts_t
+    iters::Int32
+    reserved::Int32
+    a::Float64
+    b::Float64
+    f_tol::Float64
+end
+
+"""
+    fit_population_constants_nm!(pop, X, y; weights=nothing, iters=200, a=0.025, b=0.5, f_tol=0.0, loss=:L2, loss_param=0.0)
+        -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_improve::Vector{Int32})
+
+Nelder-Mead on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_nm`, DESIGN.md §4.4.13) — the
+reference's `optimize(f, tree)` (test/test_optim.jl:6), which passes no gradient and so runs Optim's default method.  It needs the fused
+loss alone: every kind of `eval_population_loss` is an objective, and a constant under `round`, `floor`, `sign`, ... moves.  It starts
+from the constants `pop` holds; `iters` counts rounds of one evaluation each, the `G` rounds that build a tree's start simplex (`a`, `b`)
+included.  Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the
+accepted losses after `r - 1` rounds and never increase; `n_improve` counts the rounds that lowered them.  Trees that are incomplete at
+the start, have no constants or more than `de_nm_max_rows()` = 32 keep their constants.  A population with a shared GraphNode constant is
+refused (the library moves every occurrence on its own).
+"""
+function fit_population_constants_nm!(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+    iters::Integer=200, a::Real=0.025, b::Real=0.5, f_tol::Real=0.0, loss::Symbol=:L2, loss_param::Real=0.0,
+) where {T}
+    loss === :pullback && throw(ArgumentError("fit_population_constants_nm!: :pullback is the cotangent of a pullback, not an objective"))
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_nm!: shared GraphNode constants need the host loop"))
+    opts = Ref(NmOpts(Int32(iters), Int32(0), Float64(a), Float64(b), Float64(f_tol)))
+    spec = loss_spec(loss, loss_param; with_gradient=false)
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_improve = zeros(Int32, pop.n_trees)
+    with_pop(pop) do hc, hp
+        wp = weights === nothing ? C_NULL : pointer(weights)
+        check(pop.ctx, GC.@preserve X y weights lossv ok history n_improve ccall(
+            (:de_fit_consts_nm, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{NmOpts},
+             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_improve))
+    end
+    constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+    return constants, lossv, ok .!= 0x00, history, n_improve
+end
+
 """
     eval_population_loss_grad_by_class(pop, X, y, parameters, classes; weights=nothing, loss=:L2, loss_param=0.0, variable=Val(:both))
         -> (loss, dloss::Vector{Vector{T}}, dparameters::Vector{Matrix{T}}, ok)

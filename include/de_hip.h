@@ -99,7 +99,10 @@ extern "C" {
  *      and the host-only hook de_tree_params_accumulate_host: a population whose trees each own their parameter matrix, served one class
  *      segment at a time as a non-parametric program whose parameter slots are patched on the device; DE_F32 / DE_F64.
  *      (p) de_fit_tree_params_bfgs and the host-only hooks de_tree_params_pack_host / de_tree_params_unpack_host: BFGS over each tree's
- *      vcat(constants, parameters[:]) of such a population on the device, up to 32 unknowns per tree; DE_F32 / DE_F64. */
+ *      vcat(constants, parameters[:]) of such a population on the device, up to 32 unknowns per tree; DE_F32 / DE_F64.
+ *      (q) de_nm_max_rows, de_fit_consts_nm (with de_nm_opts_t) and the host-only hooks de_nm_ask_host / de_nm_tell_host: Nelder-Mead on
+ *      the constants of a population on the device, from the fused loss alone — every kind de_eval_loss_ex takes,
+ *      programs made by de_program_create_cse included, trees of up to 32 constants; DE_F32 / DE_F64. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -866,6 +869,69 @@ int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const
 int de_fit_consts_bfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                        const void *y, const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
                        double *history, int32_t *n_accept);
+
+/* Nelder-Mead on the constants of a population, on the device — what the reference's first tested fit runs:
+ * optimize(f, tree) of test/test_optim.jl:6 passes no gradient, so Optim takes its default, NelderMead().  It needs the loss alone
+ * (de_eval_loss_ex, the cheapest launch of the library): every kind de_loss_spec_check(spec, 0) admits is served, DE_LOSS_L1_HINGE
+ * included; a constant under round / floor / ceil / sign / greater / mod / rem or on the flat side of relu / clamp — whose partial is 0 or
+ * NaN almost everywhere — moves; and programs made by de_program_create_cse are served (there are no gradient rows: the constants of tree
+ * t are the entries de_program_set_consts takes for it).  The method is a restatement, from the papers, of the steps of Lagarias, Reeds,
+ * Wright & Wright (1998) with the adaptive coefficients of Gao & Han (2012) and the affine start simplex; one evaluation per round.
+ *
+ * State of a tree of G constants, has = ok at the start && 1 <= G <= de_nm_max_rows() = 32, all double: the vertices V[(G + 1) x G]
+ * (row-major), f[G + 1], the centroid c[G], the reflected point xr[G], fr, and st[3] = {phase, cursor, l0} (int32).  ROUNDING: every
+ * coordinate that is evaluated is first rounded to the program's element type T, and the double of that value is what the state holds;
+ * every f is the double of the T loss the evaluation returned, +Inf where it failed (ok == 0 or a loss that is not finite), never NaN.
+ * Coefficients: G >= 2: alpha = 1, beta = 1 + 2/G, gamma = 0.75 - 1/(2G), delta = 1 - 1/G; G == 1: 1, 2, 0.5, 0.5.
+ * Order: l = argmin f (ties: lowest index), h = argmax f (ties: highest), s = argmax over i != h (ties: highest).
+ * A ROUND is one ask (the trial constants), one evaluation, one tell (F = the trial's loss as stored):
+ *   phase 0 BUILD(k), k = cursor = 1 .. G   ask: V_k = V_0 but coordinate k - 1 = T((1 + b) V_0[k-1] + a); trial V_k.  tell: f[k] = F;
+ *                                           behind k = G: REFLECT.  (V_0: the start constants, f[0] their loss, every other f +Inf.)
+ *   phase 1 REFLECT       ask: f_h - f_l <= f_tol |f_l|: DONE.  Else c_j = (sum over i != h, ascending, of V_i[j]) / G and
+ *                         xr_j = T(c_j + alpha (c_j - V_h[j])); trial xr.  tell: fr = F; F < f_l: EXPAND; else F < f_s: V_h = xr, f_h = F;
+ *                         else F < f_h: CONTRACT_OUT; else CONTRACT_IN.
+ *   phase 2 EXPAND        trial T(c + beta (xr - c)).  tell: F < fr: the trial and F go to V_h, f_h; else xr and fr.  REFLECT.
+ *   phase 3 CONTRACT_OUT  trial T(c + gamma (xr - c)).  tell: F <= fr: the trial and F go to V_h, f_h, REFLECT; else SHRINK.
+ *   phase 4 CONTRACT_IN   trial T(c - gamma (xr - c)).  tell: F < f_h: the trial and F go to V_h, f_h, REFLECT; else SHRINK.
+ *   phase 5 SHRINK        l0 = l when the shrink begins; cursor = every i != l0, ascending, one round each:
+ *                         ask: V_i[j] = T(V_l0[j] + delta (V_i[j] - V_l0[j])); trial V_i.  tell: f[i] = F; behind the last: REFLECT.
+ *   phase 6 DONE          trial: vertex l — the accepted constants.  tell: nothing.
+ * After every tell the accepted state of the tree (constants, loss, flag 1) is vertex l of the simplex — where f_l is finite; a tree
+ * whose every evaluation failed keeps its start — so the accepted loss never increases; n_improve counts the tells behind which it is
+ * strictly smaller.
+ *
+ * de_nm_ask_host / de_nm_tell_host: one tree's ask / tell on host buffers (no HIP call; csrc/de_nm.h, the source the kernels run: the
+ * same bits).  dtype: DE_F32 / DE_F64 (T); opts: a, b and f_tol are read (NULL: the defaults); trial: G elements of T out; f_trial: the
+ * double of the loss at the trial, ok_trial its flag.  V (from row 1 on), c, xr and fr need no initial values.  They return 1, or 0 with
+ * everything untouched for G outside 1 .. 32, a null pointer, another dtype, or a phase / cursor / l0 outside their ranges.
+ *
+ * de_fit_consts_nm: the whole loop in one call.  It starts from the constants the program holds, evaluates de_eval_loss_ex (`spec`),
+ * then `iters` times: ask, the trial constants set on the device, the evaluation there, tell — `iters` counts rounds behind the first
+ * evaluation, BUILD rounds included: a tree of G constants spends its first G rounds on the simplex.  Trees move through the phases at
+ * their own pace; every round evaluates exactly one point per tree (a DONE tree and a tree that is not fitted: its accepted constants, bit
+ * for bit).  Afterwards the program holds the accepted constants and de_eval_loss_ex with the same spec reproduces loss[t] bit for bit.
+ * No constant or loss reaches the host; host inputs are staged once; with device pointers the call synchronises only where
+ * de_eval_loss_ex does.  X .. w: as de_eval_loss_ex (pargs: the constants move, the parameters do not); loss (may be NULL), ok: n_trees
+ * entries; history (may be NULL): (iters + 1) x n_trees doubles, row r the accepted losses after r rounds, non-increasing; n_improve
+ * (may be NULL); host or device pointers.  opts == NULL: {200, 0, 0.025, 0.5, 0.0}.  A tree with ok == 0, no constants or more than 32
+ * keeps its constants, its loss is de_eval_loss_ex's.  iters == 0, N == 0 or no constants: nothing moves, every history row is the first.
+ * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED for DE_F16 / complex programs (and a feature matrix too wide
+ * for de_eval_loss_ex); DE_ERR_INVALID_ARG for a spec de_loss_spec_check(spec, 0) refuses, DE_LOSS_PULLBACK, null y or ok on a non-empty
+ * population, iters < 0, reserved != 0, a or b not finite or both 0, f_tol negative or not finite.
+ * Not served: more than 32 constants per tree, the scaled objective, parameter rows. */
+typedef struct de_nm_opts {
+    int32_t iters;    /* rounds: one ask, one evaluation and one tell each */
+    int32_t reserved; /* 0 */
+    double a, b;      /* the start simplex: coordinate k - 1 of vertex k is (1 + b) V_0[k-1] + a */
+    double f_tol;     /* a tree is DONE where f_h - f_l <= f_tol |f_l| */
+} de_nm_opts_t;
+int de_nm_max_rows(void);
+int de_nm_ask_host(int G, int dtype, const de_nm_opts_t *opts, double *V, const double *f, int32_t *st, double *c, double *xr, void *trial);
+int de_nm_tell_host(int G, int dtype, double *V, double *f, int32_t *st, const double *c, const double *xr, double *fr, double f_trial,
+                    int ok_trial);
+int de_fit_consts_nm(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                     const void *y, const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, void *loss, uint8_t *ok,
+                     double *history, int32_t *n_improve);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
