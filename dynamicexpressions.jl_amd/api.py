@@ -64,6 +64,7 @@ EXPORTS = [
     "de_fit_tree_params_bfgs", "de_tree_params_pack_host", "de_tree_params_unpack_host",
     "de_lower_tape_assured_fact",
     "de_nm_max_rows", "de_nm_ask_host", "de_nm_tell_host", "de_fit_consts_nm",
+    "de_scaled_objective_host", "de_fit_consts_bfgs_scaled", "de_fit_consts_nm_scaled",
 ]
 
 
@@ -542,6 +543,37 @@ def bfgs_update_host(B, fresh, s, yv, curv: float = 1e-8):
     return bool(rc), B, bool(fr[0])
 
 
+def scaled_objective_host(stats3, ystats3, D, P, Q):
+    """``de_scaled_objective_host``: the objective of the matrix-free fits under linear scaling and its gradient (csrc/de_fit_scaled.h,
+    the code the adapter kernel runs) for one tree on the host, no GPU needed — (scaled_sse, g[G], formed) in float64 from ``stats3 =
+    (mean_p, m2_p, cov)``, ``ystats3 = (W, mean_y, m2_y)`` and the moments ``D`` (not read), ``P``, ``Q``: bit for bit
+    ``FitStats.scaled_sse`` and ``FitStatsGrad.scaled_sse_grad`` — ``g = (2 b) (b P - Q)`` with ``b = cov / m2_p`` — and the ``sse`` and
+    ``g`` of ``lm_project_host``.  ``formed`` False: ``m2_p == 0``, ``W == 0`` or G outside 1 .. ``BFGS_MAX_ROWS`` — g is zero."""
+    st = np.ascontiguousarray(stats3, dtype=np.float64).reshape(-1)
+    ys = np.ascontiguousarray(ystats3, dtype=np.float64).reshape(-1)
+    rows = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (D, P, Q)]
+    G = rows[0].size
+    if st.size != 3 or ys.size != 3 or rows[1].size != G or rows[2].size != G:
+        raise ValueError("stats3 and ystats3 hold three values, D, P and Q G entries each")
+    dm = np.concatenate(rows + [np.zeros(1)])
+    sse, g = np.full(1, np.nan), np.full(max(G, 1), np.nan)
+    rc = library().de_scaled_objective_host(G, st.ctypes.data, ys.ctypes.data, dm.ctypes.data, sse.ctypes.data, g.ctypes.data)
+    return float(sse[0]), g[:G], bool(rc)
+
+
+def _scaled_sse64(stats: "FitStats") -> np.ndarray:
+    """``stats.scaled_sse`` as the fits under scaling keep it: float64, a NaN THE quiet NaN (the bits ``de_scaled_objective_host`` gives)."""
+    with np.errstate(over="ignore"):
+        sse = np.array(stats.scaled_sse, dtype=np.float64)
+    sse[np.isnan(sse)] = np.nan
+    return sse
+
+
+def _refuse_scaled_kind(what: str, scaled: bool, loss: str) -> None:
+    if scaled and loss != "L2":
+        raise ValueError(f"{what}(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
+
+
 def _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param):
     """(``BfgsOpts``, ``LossSpec``) of a BFGS fit, refused as ``de_fit_consts_bfgs`` refuses them: a ``ValueError``."""
     if loss == "pullback":
@@ -624,14 +656,16 @@ def _nm_opts(iters, a, b, f_tol, loss, loss_param):
 
 
 def nm_fit(evaluate, install, consts0, n_consts, dtype, iters: int = 200, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0,
-           history: Optional[list] = None):
+           history: Optional[list] = None, loss_dtype=None):
     """The host loop of ``de_fit_consts_nm`` over the two hooks: ``evaluate(consts)`` installs a vector of all constants (``n_consts[t]``
     per tree, values of ``dtype``) and returns (loss[n_trees], ok[n_trees]) there; ``install(consts)`` only installs.  One round is one
     ``nm_ask_host`` per fitted tree, ONE ``evaluate`` for the whole population and one ``nm_tell_host`` per fitted tree; behind every tell
     the tree's accepted constants and loss are the vertex of the smallest loss.  A tree that is incomplete at ``consts0`` or has no or
     more than ``NM_MAX_ROWS`` constants keeps its constants.  Returns (consts, loss in ``dtype``, ok, n_improve); ``history`` receives
-    ``iters + 1`` rows of accepted losses (float64)."""
+    ``iters + 1`` rows of accepted losses (float64).  ``loss_dtype`` (default ``dtype``): the type the losses are kept in — float64 for
+    the scaled objective, whose double is never rounded to the element type."""
     dtype, f64 = np.dtype(dtype), np.float64
+    ldt = dtype if loss_dtype is None else np.dtype(loss_dtype)
     consts = np.array(_host(consts0), dtype=dtype).reshape(-1).copy()
     n_consts = np.asarray(n_consts, dtype=np.int64).reshape(-1)
     nt = n_consts.size
@@ -640,7 +674,7 @@ def nm_fit(evaluate, install, consts0, n_consts, dtype, iters: int = 200, a: flo
     at = np.zeros(nt + 1, dtype=np.int64)
     np.cumsum(n_consts, out=at[1:])
     lo, ok = evaluate(consts)
-    lo, ok = np.array(_host(lo), dtype=dtype).copy(), _host(ok).astype(bool).copy()
+    lo, ok = np.array(_host(lo), dtype=ldt).copy(), _host(ok).astype(bool).copy()
     states = [NmState(consts[at[t]:at[t + 1]], lo[t], dtype) if ok[t] and 1 <= n_consts[t] <= NM_MAX_ROWS else None for t in range(nt)]
     improve = np.zeros(nt, dtype=np.int32)
     if history is not None:
@@ -664,7 +698,7 @@ def nm_fit(evaluate, install, consts0, n_consts, dtype, iters: int = 200, a: flo
             now = s.f[s.best]
             if now < np.inf:  # the accepted state is vertex l
                 consts[at[t]:at[t + 1]] = s.V[s.best].astype(dtype)
-                lo[t] = dtype.type(now)
+                lo[t] = ldt.type(now)
                 improve[t] += int(now < before)
         if history is not None:
             history.append(lo.astype(f64))
@@ -814,6 +848,10 @@ def library() -> C.CDLL:
         lib.de_nm_tell_host.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int]
         lib.de_fit_consts_nm.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(NmOpts),
                                          vp, vp, vp, vp]
+    if hasattr(lib, "de_fit_consts_bfgs_scaled"):  # (absent from a library built before the matrix-free scaled fits: DE_HIP_LIB in an A/B run)
+        lib.de_scaled_objective_host.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+        lib.de_fit_consts_bfgs_scaled.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(BfgsOpts), vp, vp, vp, vp, vp, vp]
+        lib.de_fit_consts_nm_scaled.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(NmOpts), vp, vp, vp, vp, vp, vp]
     lib.de_eval_loss_grad_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp]
     lib.de_eval_loss_grad_by_class_ex.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp, vp]
     lib.de_eval_grad.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), C.c_int, vp, i64, vp, vp, vp]
@@ -2041,7 +2079,7 @@ class Population:
 
     def fit_constants_bfgs(self, X, y, consts0, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
                            curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None,
-                           classes=None, class_base: int = 1):
+                           classes=None, class_base: int = 1, scaled: bool = False):
         """BFGS on the constants of every tree at once, from the loss and its gradient alone (the plain loop; one ``eval_loss_grad`` per
         iteration behind the one at ``consts0``) — the reference's ``optimize(f, g!, tree, BFGS())`` with a backtracking
         line search.  Every kind ``eval_loss_grad`` takes except "pullback" is an objective, "l1_hinge" included, and every tree of up to
@@ -2051,7 +2089,14 @@ class Population:
         to 1, a rejected tree's ``alpha`` shrinks by ``shrink``.  ``consts0``: ``set_constants``' layout.  Incomplete trees, trees without
         constants and trees of more than ``BFGS_MAX_ROWS`` constants keep ``consts0``.  Returns (consts, loss[n_trees] in the population's
         dtype, ok) at the accepted constants, which the population holds afterwards; ``history`` (a list) receives the accepted losses
-        (float64) after every evaluation, ``self.bfgs_accepts`` the number of accepted steps per tree."""
+        (float64) after every evaluation, ``self.bfgs_accepts`` the number of accepted steps per tree.
+
+        ``scaled=True`` (``loss="L2"`` only; any other kind is a ``ValueError`` before the constants are touched) fits
+        under Keijzer's linear scaling: every evaluation is ``eval_fit_stats_grad(want_jtj=False)``, the objective ``scaled_sse`` and the
+        gradient ``scaled_sse_grad()``, both float64 from the statistics to the accept rule — the same loop otherwise.  Returns (consts,
+        scaled_sse float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` of one more evaluation at the result (slope,
+        intercept).  A constant that is redundant under scaling, which the scaled Levenberg-Marquardt fits leave alone, moves."""
+        _refuse_scaled_kind("fit_constants_bfgs", scaled, loss)
         self._refuse_f16("fit_constants_bfgs")
         _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)  # (refused before the population's constants are touched)
         consts = np.array(_host(consts0), dtype=self.dtype).reshape(-1).copy()
@@ -2062,7 +2107,14 @@ class Population:
         np.cumsum(self.n_consts, out=at[1:])
         fitted = [1 <= int(at[t + 1] - at[t]) <= BFGS_MAX_ROWS for t in range(nt)]
 
+        def evaluate_scaled():
+            return self.eval_fit_stats_grad(X, y, weights=weights, params=params, classes=classes, class_base=class_base, want_jtj=False)
+
         def evaluate():
+            if scaled:
+                fs = evaluate_scaled()
+                return _scaled_sse64(fs.stats), [np.array(g, dtype=f64) for g in fs.scaled_sse_grad()], \
+                    _host(fs.ok).astype(bool).copy()
             lo, gr, ok = self.eval_loss_grad(X, y, weights=weights, loss=loss, loss_param=loss_param, params=params, classes=classes,
                                              class_base=class_base)
             return _host(lo).copy(), [_host(g).astype(f64) for g in gr], _host(ok).astype(bool).copy()
@@ -2099,11 +2151,13 @@ class Population:
                 history.append(lo.astype(f64))
         self.set_constants(consts)
         self.bfgs_accepts = acc
+        if scaled:
+            self._scaled_fit = evaluate_scaled().stats if nt else None
         return consts, lo, ok
 
     def fit_constants_bfgs_device(self, X, y, consts0=None, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5,
                                   c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
-                                  history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+                                  history: Optional[list] = None, params=None, classes=None, class_base: int = 1, scaled: bool = False):
         """``fit_constants_bfgs`` as ONE library call (``de_fit_consts_bfgs``): the directions, the trial constants, the
         accept rule and the updates of ``B`` run on the device; no constant, gradient or matrix reaches the host, and the trajectory is
         the host loop's bit for bit.  ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the
@@ -2111,7 +2165,12 @@ class Population:
         the population holds afterwards; with torch inputs all three are device tensors and nothing synchronises beyond what
         ``eval_loss_grad`` does.  ``history`` (a list) receives the ``iters + 1`` rows of accepted losses (float64); ``self.bfgs_accepts``
         holds the number of accepted steps per tree.  A population with shared GraphNode constants raises ``ValueError``:
-        ``fit_constants_bfgs`` serves it."""
+        ``fit_constants_bfgs`` serves it.
+        ``scaled=True`` (``de_fit_consts_bfgs_scaled``; ``loss="L2"`` only, anything else is a ``ValueError`` before the
+        constants are touched): ``fit_constants_bfgs(scaled=True)`` on the device, bit for bit.  Returns (consts, scaled_sse[n_trees] in
+        float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` at the returned constants (with torch inputs reading it copies 3
+        n_trees + 3 doubles to the host, the call itself does not)."""
+        _refuse_scaled_kind("fit_constants_bfgs_device", scaled, loss)
         self._refuse_f16("fit_constants_bfgs_device")
         opts, spec = _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
         if self._occ is not None:
@@ -2119,9 +2178,12 @@ class Population:
                              "on the host): use fit_constants_bfgs")
         ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_bfgs_device", X, y, weights, consts0, params,
                                                                                 classes, class_base)
-        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
-        self.ctx.check(library().de_fit_consts_bfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
-                                                    C.byref(opts), *ptrs))
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, np.float64 if scaled else self.dtype)
+        head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
+        if scaled:
+            self._fit_scaled_device(library().de_fit_consts_bfgs_scaled, head, opts, ptrs, is_t, keep_x)
+        else:
+            self.ctx.check(library().de_fit_consts_bfgs(*head, C.byref(spec), C.byref(opts), *ptrs))
         self.bfgs_accepts = acc
         if history is not None:
             history.extend(hist[r] for r in range(int(iters) + 1))
@@ -2129,7 +2191,7 @@ class Population:
 
     def fit_constants_nm(self, X, y, consts0, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0,
                          loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None, classes=None,
-                         class_base: int = 1):
+                         class_base: int = 1, scaled: bool = False):
         """Nelder-Mead on the constants of every tree at once, from the fused loss alone (``nm_fit``: the plain loop over ``nm_ask_host``
         / ``nm_tell_host``; one ``eval_loss`` per round behind the one at ``consts0``) — the reference's
         ``optimize(f, tree)``, which runs Optim's default method.  Every kind ``eval_loss`` takes is an objective, and a constant whose
@@ -2138,22 +2200,34 @@ class Population:
         ``set_constants``' layout (a shared GraphNode constant is ONE coordinate).  Incomplete trees, trees without constants and trees
         of more than ``NM_MAX_ROWS`` constants keep ``consts0``.  Returns (consts, loss[n_trees] in the population's dtype, ok) at the
         accepted constants, which the population holds afterwards; ``history`` (a list) receives the ``iters + 1`` rows of accepted
-        losses (float64), ``self.nm_improves`` the number of rounds that lowered each tree's accepted loss."""
+        losses (float64), ``self.nm_improves`` the number of rounds that lowered each tree's accepted loss.
+
+        ``scaled=True`` (``loss="L2"`` only; any other kind is a ``ValueError`` before the constants are touched) fits
+        under Keijzer's linear scaling: every evaluation is ``eval_fit_stats`` and the objective its ``scaled_sse``, kept in float64 — the
+        same loop otherwise.  Returns (consts, scaled_sse float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` of one more
+        evaluation at the result (slope, intercept)."""
+        _refuse_scaled_kind("fit_constants_nm", scaled, loss)
         self._refuse_f16("fit_constants_nm")
         _nm_opts(iters, a, b, f_tol, loss, loss_param)  # (refused before the population's constants are touched)
 
         def evaluate(consts):
             self.set_constants(consts)
+            if scaled:
+                st, ok = self.eval_fit_stats(X, y, weights=weights, params=params, classes=classes, class_base=class_base)
+                return _scaled_sse64(st), ok
             return self.eval_loss(X, y, weights=weights, loss=loss, loss_param=loss_param, params=params, classes=classes,
                                   class_base=class_base)
 
         consts, lo, ok, self.nm_improves = nm_fit(evaluate, self.set_constants, consts0, self.n_consts, self.dtype, iters, a, b, f_tol,
-                                                  history)
+                                                  history, np.float64 if scaled else None)
+        if scaled:
+            self._scaled_fit = self.eval_fit_stats(X, y, weights=weights, params=params, classes=classes, class_base=class_base)[0] \
+                if self.n_trees else None
         return consts, lo, ok
 
     def fit_constants_nm_device(self, X, y, consts0=None, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5,
                                 f_tol: float = 0.0, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None,
-                                params=None, classes=None, class_base: int = 1):
+                                params=None, classes=None, class_base: int = 1, scaled: bool = False):
         """``fit_constants_nm`` as ONE library call (``de_fit_consts_nm``): the simplex, the trial constants and every
         decision live on the device; no constant or loss reaches the host, and the trajectory is the host loop's bit for bit.
         ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.
@@ -2162,7 +2236,11 @@ class Population:
         receives the ``iters + 1`` rows of accepted losses (float64); ``self.nm_improves`` holds the number of rounds that lowered each
         tree's accepted loss.  GraphNode populations are served (the library call has no gradient rows to combine) unless a CONSTANT is
         shared: the library moves one coordinate per occurrence, which would untie the occurrences — a ``ValueError``;
-        ``fit_constants_nm`` serves those."""
+        ``fit_constants_nm`` serves those.
+        ``scaled=True`` (``de_fit_consts_nm_scaled``; ``loss="L2"`` only, anything else is a ``ValueError`` before the
+        constants are touched): ``fit_constants_nm(scaled=True)`` on the device, bit for bit.  Returns (consts, scaled_sse[n_trees] in
+        float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` at the returned constants."""
+        _refuse_scaled_kind("fit_constants_nm_device", scaled, loss)
         self._refuse_f16("fit_constants_nm_device")
         opts, spec = _nm_opts(iters, a, b, f_tol, loss, loss_param)
         if self._occ is not None:
@@ -2170,13 +2248,43 @@ class Population:
                              "its own): use fit_constants_nm")
         ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_nm_device", X, y, weights, consts0, params,
                                                                                 classes, class_base)
-        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
-        self.ctx.check(library().de_fit_consts_nm(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
-                                                  C.byref(opts), *ptrs))
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, np.float64 if scaled else self.dtype)
+        head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
+        if scaled:
+            self._fit_scaled_device(library().de_fit_consts_nm_scaled, head, opts, ptrs, is_t, keep_x)
+        else:
+            self.ctx.check(library().de_fit_consts_nm(*head, C.byref(spec), C.byref(opts), *ptrs))
         self.nm_improves = acc
         if history is not None:
             history.extend(hist[r] for r in range(int(iters) + 1))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
+    def _fit_scaled_device(self, fit, head, opts, ptrs, is_t, keep_x) -> None:
+        """One ``de_fit_consts_bfgs_scaled`` / ``de_fit_consts_nm_scaled`` call: the statistics land in a buffer on the inputs' side, which
+        ``scaled_fit_stats`` reads."""
+        nt = self.n_trees
+        if is_t:
+            import torch
+            st = torch.empty(3 * nt + 3, dtype=torch.float64, device=keep_x.device)
+            stp = st.data_ptr()
+        else:
+            st = np.full(3 * nt + 3, np.nan)
+            stp = st.ctypes.data
+        self.ctx.check(fit(*head, C.byref(opts), ptrs[0], stp, stp + 24 * nt, *ptrs[1:]))
+        self._scaled_fit = st if nt else None
+
+    @property
+    def scaled_fit_stats(self) -> FitStats:
+        """The ``FitStats`` at the constants the last ``fit_constants_bfgs[_device](scaled=True)`` / ``fit_constants_nm[_device](scaled=True)``
+        returned (a device tensor is copied to the host only here)."""
+        raw = getattr(self, "_scaled_fit", None)
+        if raw is None:
+            raise AttributeError("scaled_fit_stats: no fit_constants_bfgs / fit_constants_nm (scaled=True) has run on a non-empty population")
+        if isinstance(raw, FitStats):
+            return raw
+        sth, nt = _host(raw), self.n_trees
+        per = sth[:3 * nt].reshape(nt, 3)
+        return FitStats(per[:, 0], per[:, 1], per[:, 2], sth[3 * nt], sth[3 * nt + 1], sth[3 * nt + 2])
 
     @property
     def lm_fit_stats(self) -> FitStats:

@@ -1,7 +1,8 @@
 // de_api_fit.cpp — C ABI (include/de_hip.h): what CONSUMES the gradients and matrices de_api_grad.cpp produces.  de_gn_lm_step /
 // de_fit_stats_lm_step (and _wide): one Levenberg-Marquardt step per tree (kernels de_lm.hip, de_gn_wide.hip, de_lm_scaled.hip,
 // de_lm_scaled_wide.hip); de_fit_consts_lm(_ex, _wide), de_fit_consts_lm_scaled(_wide) and
-// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10) and de_fit_consts_nm (kernels de_nm.hip, §4.4.13): four fits on the constants that are
+// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10), de_fit_consts_nm (kernels de_nm.hip, §4.4.13) and the scaled forms of those two
+// (de_fit_consts_bfgs_scaled / de_fit_consts_nm_scaled, adapter kernel de_fit_scaled.hip, §4.4.14): fits on the constants that are
 // ONE driver — fit_check, stage_fit_inputs, a Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host
 // hooks that run the kernels' arithmetic.
 #include "de_api_internal.h"
@@ -16,6 +17,8 @@
 #include "de_bfgs_dev.h"
 #include "de_nm.h"
 #include "de_nm_dev.h"
+#include "de_fit_scaled.h"
+#include "de_fit_scaled_dev.h"
 
 extern "C" {
 // ---- the host hooks: the arithmetic of the step, projection and BFGS kernels on host buffers (de_lm_solve.h, de_lm_solve_wide.h,
@@ -66,6 +69,15 @@ int de_bfgs_direction_host(int G, double *B, uint8_t *fresh, double *alpha, cons
 int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const double *yv, double curv) {
     if (!B || !fresh || !s || !yv) return 0;
     return bfgs_update(G, B, fresh, s, yv, curv);
+}
+int de_scaled_objective_host(int G, const double *stats, const double *ystats, const double *dmom, double *sse, double *g) {
+    if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
+    if (stats && ystats && dmom && g && G >= 1 && G <= FIT_SCALED_MAX_ROWS) {
+        double e;
+        return fit_scaled_objective(G, stats, ystats, dmom, &e, g);
+    }
+    for (int k = 0; g && k < G; k++) g[k] = 0.0;
+    return 0;
 }
 int de_nm_max_rows(void) { return NM_MAX_ROWS; }
 static bool nm_hook_args(int G, int dtype, const int32_t *st) {
@@ -328,10 +340,11 @@ static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char 
 // (false) or the trial (true) state; init: the per-tree state; first_history(row 0) behind it; then, where nothing can move (no sample, no
 // constant, no iteration), fill_history for every further row, else `iters` times: propose (the step or direction kernel: trial constants
 // from the accepted state), the trial constants installed, evaluate(true), accept(history row).  The program holds the accepted constants
-// afterwards.  The inner calls leave the timing events alone: the ring sees one call.
+// afterwards; finish (may be empty) runs behind that, where the loop ran.  The inner calls leave the timing events alone: the ring sees
+// one call.
 struct FitLoop {
     std::function<int(bool)> evaluate;
-    std::function<int()> init, propose;
+    std::function<int()> init, propose, finish;
     std::function<int(double *)> first_history, fill_history, accept;
     void *consts_acc = nullptr, *consts_trial = nullptr;
     const char *last_kernel = nullptr; // what the context reports behind the loop (null: what the last inner call set)
@@ -363,6 +376,7 @@ static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, d
             const int rc2 = set_consts_device_impl(p, f.consts_acc);
             if (rc != DE_OK) return rc;
             if (rc2 != DE_OK) return rc2;
+            if (f.finish && (rc = f.finish()) != DE_OK) return rc;
         }
     }
     if (!c->nested) HIP_TRY(c, time_end(c));
@@ -758,6 +772,222 @@ int de_fit_consts_nm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
                      int32_t *n_improve) {
     DE_REFUSE_F16("de_fit_consts_nm");
     DE_NOTHROW(c, fit_consts_nm_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_improve));
+}
+
+// ---- de_fit_consts_bfgs_scaled / de_fit_consts_nm_scaled (kernels: de_fit_scaled.hip and those of de_bfgs.hip / de_nm.hip
+// with a double objective; arithmetic: de_fit_scaled.h) ---------------------------------------------------------------------------------------
+// de_fit_consts_bfgs's loop with every evaluation de_eval_fit_stats_grad's without a matrix (a FitPlan into the state) and the adapter kernel
+// behind it: the loss slot takes scaled_sse and the gradient slots g, both doubles.  The statistics of the accepted constants are those of
+// ONE more evaluation behind the loop (FitLoop::finish): it rewrites the accepted objective, gradient and flag with the same bits.
+static int fit_consts_bfgs_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                                       const void *y, const void *w, const de_bfgs_opts_t *opts, double *sse, double *stats, double *ystats,
+                                       uint8_t *ok, double *history, int32_t *n_accept) {
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    int rc = fit_check(c, p, "de_fit_consts_bfgs_scaled", "the caller sums them", nullptr, bfgs_opts_problem(&o), X, N, ldX, pa, {ok, sse, y});
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    std::vector<int64_t> boff(nt); // B: G^2 doubles of every tree that is fitted, none of the others
+    int64_t bspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t g = p->n_consts_tree[t];
+        boff[t] = bspan;
+        if (g >= 1 && g <= BFGS_MAX_ROWS) bspan += g * g;
+    }
+    LmTables tab; // packed: dmom at 3 x the constants' offsets, the gradients at the constants' offsets; the matrix offsets are B's
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, boff.data(), &tab, 3)) != DE_OK) return rc;
+    const size_t mspan = (size_t)std::max<int64_t>(tab.span, 1), span = std::max<size_t>(nc, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, objectives, gradients (doubles) and flags; the statistics and moments of both evaluations and
+    // ystats; B, alpha, the slope and the direction, two flags per tree; the images
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es);
+    const auto lA = ws.place<double>(nt), lT = ws.place<double>(nt), dA = ws.place<double>(span), dT = ws.place<double>(span),
+               sA = ws.place<double>(nt * 3), sT = ws.place<double>(nt * 3), ys = ws.place<double>(3), mom = ws.place<double>(mspan);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt), fresh = ws.place<uint8_t>(nt), produced = ws.place<uint8_t>(nt);
+    const auto B = ws.place<double>((size_t)bspan), alpha = ws.place<double>(nt), slope = ws.place<double>(nt), dir = ws.place<double>(span),
+               r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto r_acc = ws.place<int32_t>(nt, h_acc);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(sse, ws.ptr(lA), nt * 8);
+    out.from_state(stats, ws.ptr(sA), nt * 24);
+    out.from_state(ystats, ws.ptr(ys), 24);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    BfgsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.coff = tab.soff;
+    a.boff = tab.joff;
+    a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.dloss_acc = ws.ptr(dA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.dloss_trial = ws.ptr(dT); a.ok_trial = ws.ptr(okT);
+    a.B = ws.ptr(B); a.alpha = ws.ptr(alpha); a.slope = ws.ptr(slope); a.p = ws.ptr(dir);
+    a.fresh = ws.ptr(fresh); a.produced = ws.ptr(produced);
+    a.step0 = o.step0; a.shrink = o.shrink; a.c1 = o.c1; a.curv = o.curv;
+    a.n_accept = out.in_place(n_accept, h_acc, ws.ptr(r_acc), nt);
+    FitScaledArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.n_trees = p->n_trees;
+    s.n_grad = tab.ng;
+    s.moff = tab.doff;
+    s.coff = tab.soff;
+    s.ystats = ws.ptr(ys);
+    s.dmom = ws.ptr(mom); // (one buffer: the adapter has consumed an evaluation's moments before the next one writes them)
+    const de_loss_spec_t spec{DE_LOSS_L2, 0, 0.0};
+    FitLoop f;
+    f.consts_acc = a.consts_acc;
+    f.consts_trial = a.consts_trial;
+    f.last_kernel = "de_bfgs_accept_kernel";
+    f.evaluate = [&](bool trial) -> int { // (ystats: the same three values every time)
+        double *st = ws.ptr(trial ? sT : sA);
+        const FitPlan fit{st, ws.ptr(ys), nullptr, nullptr};
+        const int rc1 = loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, nullptr, ws.ptr(mom), nullptr,
+                                       ws.ptr(trial ? okT : okA), nullptr, false, nullptr, &fit);
+        if (rc1 != DE_OK) return rc1;
+        s.stats = st;
+        s.sse = ws.ptr(trial ? lT : lA);
+        s.grad = ws.ptr(trial ? dT : dA);
+        HIP_TRY(c, launch_fit_scaled_objective(s, c->stream));
+        return DE_OK;
+    };
+    f.init = [&]() -> int { HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream, true)); return DE_OK; };
+    f.first_history = f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(DE_F64, a.loss_acc, p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int { HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream, true)); return DE_OK; };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream, true));
+        return DE_OK;
+    };
+    f.finish = [&]() -> int { // the statistics at the accepted constants, which the program holds now
+        const int rc1 = f.evaluate(false);
+        c->last_kernel = f.last_kernel;
+        return rc1;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_bfgs_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                              const void *w, const de_bfgs_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
+                              double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_bfgs_scaled");
+    DE_NOTHROW(c, fit_consts_bfgs_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept));
+}
+
+// de_fit_consts_nm's loop with every evaluation de_eval_fit_stats's and the adapter kernel behind it (the objective alone: no gradient
+// rows, so programs made by de_program_create_cse are served).  The statistics of the accepted constants: as above, one more evaluation.
+static int fit_consts_nm_scaled_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
+                                     const void *y, const void *w, const de_nm_opts_t *opts, double *sse, double *stats, double *ystats,
+                                     uint8_t *ok, double *history, int32_t *n_improve) {
+    const de_nm_opts_t defaults{200, 0, 0.025, 0.5, 0.0};
+    const de_nm_opts_t o = opts ? *opts : defaults;
+    const auto spec_check = [&]() -> int {
+        if (!p->threaded)
+            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_nm_scaled needs the LDS-tiled kernel (feature matrix too wide for this build)");
+        return DE_OK;
+    };
+    int rc = fit_check(c, p, "de_fit_consts_nm_scaled", "", spec_check, nm_opts_problem(&o), X, N, ldX, pa, {ok, sse, y}, false);
+    if (rc != DE_OK || p->n_trees == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    std::vector<int64_t> voff(nt); // the simplex: (G + 1) G vertices and G + 1 losses of every tree that can be fitted, none of the others
+    int64_t vspan = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t g = p->n_consts_tree[t];
+        voff[t] = vspan;
+        if (g >= 1 && g <= NM_MAX_ROWS) vspan += (g + 1) * (g + 1);
+    }
+    LmTables tab; // packed: the constants' offsets; the matrix offsets are the simplex's
+    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, voff.data(), &tab)) != DE_OK) return rc;
+    const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
+    FitInputs in;
+    if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
+    // the state: accepted and trial constants, objectives (doubles) and flags; the statistics of both evaluations and ystats; the simplex, c,
+    // xr, fr and three ints per tree; the images
+    const bool h_hist = FitOutputs::on_host(history), h_imp = FitOutputs::on_host(n_improve);
+    Workspace ws;
+    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es);
+    const auto lA = ws.place<double>(nt), lT = ws.place<double>(nt), sA = ws.place<double>(nt * 3), sT = ws.place<double>(nt * 3),
+               ys = ws.place<double>(3);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
+    const auto V = ws.place<double>((size_t)vspan), cen = ws.place<double>(span), xr = ws.place<double>(span), fr = ws.place<double>(nt),
+               r_hist = ws.place<double>(rows * nt, h_hist);
+    const auto st = ws.place<int32_t>(3 * nt), r_imp = ws.place<int32_t>(nt, h_imp);
+    if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    FitOutputs out;
+    out.from_state(sse, ws.ptr(lA), nt * 8);
+    out.from_state(stats, ws.ptr(sA), nt * 24);
+    out.from_state(ystats, ws.ptr(ys), 24);
+    out.from_state(ok, ws.ptr(okA), nt);
+    double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
+    NmArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_trees = p->n_trees;
+    a.n_grad = tab.ng;
+    a.coff = tab.doff;
+    a.voff = tab.joff;
+    a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.ok_acc = ws.ptr(okA);
+    a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.ok_trial = ws.ptr(okT);
+    a.V = ws.ptr(V); a.c = ws.ptr(cen); a.xr = ws.ptr(xr); a.fr = ws.ptr(fr);
+    a.st = ws.ptr(st);
+    a.a = o.a; a.b = o.b; a.f_tol = o.f_tol;
+    a.n_improve = out.in_place(n_improve, h_imp, ws.ptr(r_imp), nt);
+    FitScaledArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.n_trees = p->n_trees;
+    s.n_grad = tab.ng;
+    s.ystats = ws.ptr(ys);
+    FitLoop f;
+    f.consts_acc = a.consts_acc;
+    f.consts_trial = a.consts_trial;
+    f.last_kernel = "de_nm_tell_kernel";
+    f.evaluate = [&](bool trial) -> int { // (ystats: the same three values every time)
+        double *sts = ws.ptr(trial ? sT : sA);
+        const int rc1 = de_eval_fit_stats(c, p, in.Xd, N, ldX, in.pa, in.yd, in.wd, sts, ws.ptr(ys), ws.ptr(trial ? okT : okA));
+        if (rc1 != DE_OK) return rc1;
+        s.stats = sts;
+        s.sse = ws.ptr(trial ? lT : lA);
+        HIP_TRY(c, launch_fit_scaled_objective(s, c->stream));
+        return DE_OK;
+    };
+    f.init = [&]() -> int {
+        if (nc > 0) { // (the accepted constants are the kernel's V_0: it needs them before run_fit reads them for the loop)
+            const int rc1 = de_program_get_consts(p, a.consts_acc);
+            if (rc1 != DE_OK) return rc1;
+        }
+        HIP_TRY(c, launch_nm_init(p->dtype, a, c->stream, true));
+        return DE_OK;
+    };
+    f.first_history = f.fill_history = [&](double *row) -> int {
+        HIP_TRY(c, launch_lm_history(DE_F64, a.loss_acc, p->n_trees, row, c->stream));
+        return DE_OK;
+    };
+    f.propose = [&]() -> int { HIP_TRY(c, launch_nm_ask(p->dtype, a, c->stream, true)); return DE_OK; };
+    f.accept = [&](double *row) -> int {
+        a.history_row = row;
+        HIP_TRY(c, launch_nm_tell(p->dtype, a, c->stream, true));
+        return DE_OK;
+    };
+    f.finish = [&]() -> int { // the statistics at the accepted constants, which the program holds now
+        const int rc1 = f.evaluate(false);
+        c->last_kernel = f.last_kernel;
+        return rc1;
+    };
+    if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
+    return out.finish(c);
+}
+int de_fit_consts_nm_scaled(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                            const void *w, const de_nm_opts_t *opts, double *sse, double *stats, double *ystats, uint8_t *ok,
+                            double *history, int32_t *n_improve) {
+    DE_REFUSE_F16("de_fit_consts_nm_scaled");
+    DE_NOTHROW(c, fit_consts_nm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_improve));
 }
 
 } // extern "C"

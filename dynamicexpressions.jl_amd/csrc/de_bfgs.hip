@@ -5,6 +5,8 @@
 //   de_bfgs_accept_kernel     the Armijo accept rule, the rank-two update of B and a row of the loss history
 // One wave per tree, lane i < G owns row i of B (the arithmetic: de_bfgs.h, the code the host hooks run); the scalars are summed in index
 // order from LDS by every lane.  All on the context's stream, plain vector stores only, no atomics.
+// T: the element type of the constants; LT: the type of the loss and gradient slots — T itself for de_fit_consts_bfgs, double whatever T is
+// for de_fit_consts_bfgs_scaled (the scaled objective is never rounded to Float32).
 #include "../../include/de_hip.h"
 
 #include "de_bfgs_dev.h"
@@ -12,7 +14,7 @@
 
 namespace de {
 
-template <typename T>
+template <typename T, typename LT = T>
 __global__ void __launch_bounds__(64) de_bfgs_init_kernel(BfgsArgs a) {
     const int64_t t = blockIdx.x;
     const int lane = threadIdx.x;
@@ -21,7 +23,7 @@ __global__ void __launch_bounds__(64) de_bfgs_init_kernel(BfgsArgs a) {
     if (G < 1 || G > BFGS_MAX_ROWS) return; // (the whole workgroup: one wave)
     __shared__ double g[BFGS_MAX_ROWS];
     if (lane < G) {
-        g[lane] = (double)(static_cast<const T *>(a.dloss_acc) + a.coff[t])[lane];
+        g[lane] = (double)(static_cast<const LT *>(a.dloss_acc) + a.coff[t])[lane];
         bfgs_identity_row(a.B + a.boff[t] + (int64_t)lane * G, lane, G, 1.0);
     }
     __syncthreads();
@@ -31,7 +33,7 @@ __global__ void __launch_bounds__(64) de_bfgs_init_kernel(BfgsArgs a) {
     }
 }
 
-template <typename T>
+template <typename T, typename LT = T>
 __global__ void __launch_bounds__(64) de_bfgs_direction_kernel(BfgsArgs a) {
     const int64_t t = blockIdx.x;
     const int lane = threadIdx.x;
@@ -54,7 +56,7 @@ __global__ void __launch_bounds__(64) de_bfgs_direction_kernel(BfgsArgs a) {
     __shared__ double g[BFGS_MAX_ROWS], p[BFGS_MAX_ROWS];
     double al = a.alpha[t];
     double *row = a.B + a.boff[t] + (int64_t)lane * G;
-    if (lane < G) g[lane] = (double)(static_cast<const T *>(a.dloss_acc) + off)[lane];
+    if (lane < G) g[lane] = (double)(static_cast<const LT *>(a.dloss_acc) + off)[lane];
     __syncthreads();
     bool fin = true;
     double pv = 0.0;
@@ -88,13 +90,13 @@ __global__ void __launch_bounds__(64) de_bfgs_direction_kernel(BfgsArgs a) {
     tr[lane] = produced ? (T)bfgs_trial((double)c[lane], al, pv) : c[lane];
 }
 
-template <typename T>
+template <typename T, typename LT = T>
 __global__ void __launch_bounds__(64) de_bfgs_accept_kernel(BfgsArgs a) {
     const int64_t t = blockIdx.x;
     const int lane = threadIdx.x;
     const int G = a.n_grad[t];
-    T *la = static_cast<T *>(a.loss_acc);
-    const double f = (double)la[t], ft = (double)static_cast<const T *>(a.loss_trial)[t];
+    LT *la = static_cast<LT *>(a.loss_acc);
+    const double f = (double)la[t], ft = (double)static_cast<const LT *>(a.loss_trial)[t];
     const double al = a.alpha[t];
     const bool has = a.ok_acc[t] != 0 && G >= 1 && G <= BFGS_MAX_ROWS;
     const bool accept = has && a.produced[t] != 0 && a.ok_trial[t] != 0 && bfgs_armijo(ft, f, a.c1, al, a.slope[t]);
@@ -107,8 +109,10 @@ __global__ void __launch_bounds__(64) de_bfgs_accept_kernel(BfgsArgs a) {
     }
     __shared__ double s[BFGS_MAX_ROWS], yv[BFGS_MAX_ROWS], u[BFGS_MAX_ROWS], gn[BFGS_MAX_ROWS];
     const int64_t off = a.coff[t];
-    T *ca = static_cast<T *>(a.consts_acc) + off, *ga = static_cast<T *>(a.dloss_acc) + off;
-    const T *ct = static_cast<const T *>(a.consts_trial) + off, *gt = static_cast<const T *>(a.dloss_trial) + off;
+    T *ca = static_cast<T *>(a.consts_acc) + off;
+    LT *ga = static_cast<LT *>(a.dloss_acc) + off;
+    const T *ct = static_cast<const T *>(a.consts_trial) + off;
+    const LT *gt = static_cast<const LT *>(a.dloss_trial) + off;
     if (lane < G) {
         s[lane] = (double)ct[lane] - (double)ca[lane]; // the rounded step actually taken
         gn[lane] = (double)gt[lane];
@@ -132,7 +136,7 @@ __global__ void __launch_bounds__(64) de_bfgs_accept_kernel(BfgsArgs a) {
         ga[lane] = gt[lane];
     }
     if (lane == 0) {
-        la[t] = static_cast<const T *>(a.loss_trial)[t];
+        la[t] = static_cast<const LT *>(a.loss_trial)[t];
         a.ok_acc[t] = a.ok_trial[t];
         a.fresh[t] = fr;
         a.alpha[t] = fr ? bfgs_a0(bfgs_dot(gn, gn, G), a.step0) : 1.0;
@@ -142,12 +146,14 @@ __global__ void __launch_bounds__(64) de_bfgs_accept_kernel(BfgsArgs a) {
 
 #define DE_BFGS_LAUNCH(KERNEL)                                                                                         \
     if (a.n_trees <= 0) return hipSuccess;                                                                             \
-    if (dtype == DE_F32) hipLaunchKernelGGL(KERNEL<float>, dim3((unsigned)a.n_trees), dim3(64), 0, stream, a);         \
+    if (dtype == DE_F32 && f64_objective)                                                                              \
+        hipLaunchKernelGGL((KERNEL<float, double>), dim3((unsigned)a.n_trees), dim3(64), 0, stream, a);                \
+    else if (dtype == DE_F32) hipLaunchKernelGGL(KERNEL<float>, dim3((unsigned)a.n_trees), dim3(64), 0, stream, a);    \
     else hipLaunchKernelGGL(KERNEL<double>, dim3((unsigned)a.n_trees), dim3(64), 0, stream, a);                        \
     return hipGetLastError()
 
-hipError_t launch_bfgs_init(int dtype, const BfgsArgs &a, hipStream_t stream) { DE_BFGS_LAUNCH(de_bfgs_init_kernel); }
-hipError_t launch_bfgs_direction(int dtype, const BfgsArgs &a, hipStream_t stream) { DE_BFGS_LAUNCH(de_bfgs_direction_kernel); }
-hipError_t launch_bfgs_accept(int dtype, const BfgsArgs &a, hipStream_t stream) { DE_BFGS_LAUNCH(de_bfgs_accept_kernel); }
+hipError_t launch_bfgs_init(int dtype, const BfgsArgs &a, hipStream_t stream, bool f64_objective) { DE_BFGS_LAUNCH(de_bfgs_init_kernel); }
+hipError_t launch_bfgs_direction(int dtype, const BfgsArgs &a, hipStream_t stream, bool f64_objective) { DE_BFGS_LAUNCH(de_bfgs_direction_kernel); }
+hipError_t launch_bfgs_accept(int dtype, const BfgsArgs &a, hipStream_t stream, bool f64_objective) { DE_BFGS_LAUNCH(de_bfgs_accept_kernel); }
 
 } // namespace de

@@ -9,6 +9,8 @@ namespace de {
 // One wave per tree.  Tree t has G = n_grad[t] constants at coff[t] (constants, c and xr alike: packed) and, where 1 <= G <= 32, its
 // (G + 1) x G vertices followed by its G + 1 losses at voff[t] (doubles).  *_acc: the accepted state, *_trial: the evaluation at the trial
 // constants, both in the element type `dtype`; a tree is fitted where ok_acc && 1 <= G <= 32 at the start (st[3 t] != NM_OFF afterwards).
+// f64_objective (de_fit_consts_nm_scaled): the losses (loss_*) are doubles whatever `dtype` is — the kernels' second
+// template argument; the constants stay `dtype`.
 struct NmArgs {
     int64_t n_trees;
     const int32_t *n_grad;
@@ -25,12 +27,12 @@ struct NmArgs {
     int32_t *n_improve;  // may be null
 };
 // V_0 = the accepted constants, f_0 = their loss, every other f +Inf, phase BUILD(1) (NM_OFF where the tree is not fitted), n_improve = 0
-hipError_t launch_nm_init(int dtype, const NmArgs &a, hipStream_t stream);
+hipError_t launch_nm_init(int dtype, const NmArgs &a, hipStream_t stream, bool f64_objective = false);
 // consts_trial = the trial of the tree's phase (de_nm.h nm_ask_tree); the bits of consts_acc where the tree is not fitted
-hipError_t launch_nm_ask(int dtype, const NmArgs &a, hipStream_t stream);
+hipError_t launch_nm_ask(int dtype, const NmArgs &a, hipStream_t stream, bool f64_objective = false);
 // de_nm.h nm_tell_tree with the trial's loss; then the accepted constants and loss are vertex l of the simplex (where its loss is finite),
 // n_improve += 1 where the accepted loss became strictly smaller, and the history row is the accepted loss
-hipError_t launch_nm_tell(int dtype, const NmArgs &a, hipStream_t stream);
+hipError_t launch_nm_tell(int dtype, const NmArgs &a, hipStream_t stream, bool f64_objective = false);
 
 } // namespace de
 #endif

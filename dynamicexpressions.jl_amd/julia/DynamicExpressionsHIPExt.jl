@@ -1084,17 +1084,41 @@ constants is fitted.  It starts from the constants `pop` holds; per iteration th
 there, the Armijo accept rule and the update of `B` run on the device.  Afterwards `pop` holds the accepted constants, which are returned
 with their losses and flags; `history[:, r]` are the accepted losses after `r - 1` iterations.  Trees that are incomplete at the start,
 have no constants or more than 32 keep their constants.  A population with a shared GraphNode constant is refused.
+`scaled=true` (`de_fit_consts_bfgs_scaled`, DESIGN.md §4.4.14; `loss=:L2` only) fits under Keijzer's linear scaling `a + b ŷ`: the objective is
+`scaled_sse = m2_y - cov² / m2_p` and its gradient from the moments of `de_eval_fit_stats_grad` without a matrix, both in Float64.  It returns
+`(constants, scaled_sse::Vector{Float64}, ok, history, n_accept, stats)` with `stats` the NamedTuple of `fit_population_constants_lm!(scaled=true)`
+at the accepted constants.  A tree with a constant that is redundant under scaling, which the scaled Levenberg-Marquardt fit leaves alone, is fitted.
 """
 function fit_population_constants_bfgs!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=20, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8, loss::Symbol=:L2, loss_param::Real=0.0,
+    scaled::Bool=false,
 ) where {T}
+    scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_bfgs!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     loss === :pullback && throw(ArgumentError("fit_population_constants_bfgs!: :pullback is the cotangent of a pullback, not an objective"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
     any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_bfgs!: shared GraphNode constants need the host loop"))
     opts = Ref(BfgsOpts(Int32(iters), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
+    if scaled
+        sse = Vector{Float64}(undef, pop.n_trees)
+        stats = Matrix{Float64}(undef, 3, pop.n_trees)
+        ystats = fill(NaN, 3)
+        oks = Vector{UInt8}(undef, pop.n_trees)
+        hist = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+        acc = zeros(Int32, pop.n_trees)
+        with_pop(pop) do hc, hp
+            check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
+                (:de_fit_consts_bfgs_scaled, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{BfgsOpts},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+        end
+        consts = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+        st = (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3])
+        return consts, sse, oks .!= 0x00, hist, acc, st
+    end
     spec = loss_spec(loss, loss_param)
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
@@ -1132,17 +1156,41 @@ included.  Afterwards `pop` holds the accepted constants, which are returned wit
 accepted losses after `r - 1` rounds and never increase; `n_improve` counts the rounds that lowered them.  Trees that are incomplete at
 the start, have no constants or more than `de_nm_max_rows()` = 32 keep their constants.  A population with a shared GraphNode constant is
 refused (the library moves every occurrence on its own).
+`scaled=true` (`de_fit_consts_nm_scaled`, DESIGN.md §4.4.14; `loss=:L2` only) fits under Keijzer's linear scaling `a + b ŷ`: every evaluation is
+`de_eval_fit_stats`, the objective `scaled_sse = m2_y - cov² / m2_p` in Float64.  It returns
+`(constants, scaled_sse::Vector{Float64}, ok, history, n_improve, stats)` with `stats` the NamedTuple of `fit_population_constants_lm!(scaled=true)`
+at the accepted constants.
 """
 function fit_population_constants_nm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=200, a::Real=0.025, b::Real=0.5, f_tol::Real=0.0, loss::Symbol=:L2, loss_param::Real=0.0,
+    scaled::Bool=false,
 ) where {T}
+    scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_nm!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     loss === :pullback && throw(ArgumentError("fit_population_constants_nm!: :pullback is the cotangent of a pullback, not an objective"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
     any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_nm!: shared GraphNode constants need the host loop"))
     opts = Ref(NmOpts(Int32(iters), Int32(0), Float64(a), Float64(b), Float64(f_tol)))
+    if scaled
+        sse = Vector{Float64}(undef, pop.n_trees)
+        stats = Matrix{Float64}(undef, 3, pop.n_trees)
+        ystats = fill(NaN, 3)
+        oks = Vector{UInt8}(undef, pop.n_trees)
+        hist = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+        acc = zeros(Int32, pop.n_trees)
+        with_pop(pop) do hc, hp
+            check(pop.ctx, GC.@preserve X y weights sse stats ystats oks hist acc ccall(
+                (:de_fit_consts_nm_scaled, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{NmOpts},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, weights === nothing ? C_NULL : pointer(weights), opts, sse, stats, ystats, oks, hist, acc))
+        end
+        consts = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+        st = (mean_p=stats[1, :], m2_p=stats[2, :], cov=stats[3, :], W=ystats[1], mean_y=ystats[2], m2_y=ystats[3])
+        return consts, sse, oks .!= 0x00, hist, acc, st
+    end
     spec = loss_spec(loss, loss_param; with_gradient=false)
     lossv = Vector{T}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)

@@ -102,7 +102,9 @@ extern "C" {
  *      vcat(constants, parameters[:]) of such a population on the device, up to 32 unknowns per tree; DE_F32 / DE_F64.
  *      (q) de_nm_max_rows, de_fit_consts_nm (with de_nm_opts_t) and the host-only hooks de_nm_ask_host / de_nm_tell_host: Nelder-Mead on
  *      the constants of a population on the device, from the fused loss alone — every kind de_eval_loss_ex takes,
- *      programs made by de_program_create_cse included, trees of up to 32 constants; DE_F32 / DE_F64. */
+ *      programs made by de_program_create_cse included, trees of up to 32 constants; DE_F32 / DE_F64.
+ *      (r) de_fit_consts_bfgs_scaled, de_fit_consts_nm_scaled and the host-only hook de_scaled_objective_host: the two fits above under
+ *      linear scaling (the objective scaled_sse, in double); every entry point above keeps its bits. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -756,10 +758,11 @@ int de_fit_consts_lm_wide(de_ctx_t *ctx, de_program_t *prog, const void *X, int6
  * de_fit_consts_lm's (DE_F16 / complex / de_program_create_cse programs, constant rows that differ from the constants:
  * DE_ERR_UNSUPPORTED; a null y / ok / sse on a non-empty population, iters < 0, reserved != 0, a lam0 / up / down / lam_min that is not
  * finite and positive: DE_ERR_INVALID_ARG), before any output or constant is touched.
- * Not served: the scaled fit under non-L2 kinds and for programs made by de_program_create_cse (trees of 9 to 32 rows:
- * de_fit_consts_lm_scaled_wide below; these three calls keep their limit of 8); a tree
+ * Not served: the scaled fit under non-L2 kinds and for programs made by de_program_create_cse (de_fit_consts_nm_scaled fits those
+ * without a gradient; trees of 9 to 32 rows: de_fit_consts_lm_scaled_wide below; these three calls keep their limit of 8); a tree
  * with a constant that is redundant under scaling (an additive or multiplicative constant at the root) has a projected matrix with a
- * zero row: the Cholesky step is zero for every lam and the tree keeps its constants. */
+ * zero row: the Cholesky step is zero for every lam and the tree keeps its constants (de_fit_consts_bfgs_scaled and
+ * de_fit_consts_nm_scaled, which factor no matrix, fit it). */
 int de_lm_project_host(int G, const double *stats, const double *ystats, const double *dmom, const double *H,
                        double *sse, double *g, double *Ht);
 int de_fit_stats_lm_step(de_ctx_t *ctx, int dtype, int64_t n_trees, const int32_t *n_grad,
@@ -853,8 +856,8 @@ int de_fit_consts_lm_scaled_wide(de_ctx_t *ctx, de_program_t *prog, const void *
  * de_program_create_cse programs, constant rows that differ from the constants); DE_ERR_INVALID_ARG for a spec de_loss_spec_check(spec, 1)
  * refuses, DE_LOSS_PULLBACK (no objective), null y or ok on a non-empty population, iters < 0, reserved != 0, step0 / c1 / curv not
  * finite and positive, shrink outside (0, 1).
- * Not served: programs made by de_program_create_cse, more than 32 constants, the scaled objective, parameter rows (the per-tree
- * parameter matrices of §4.4.11 are fitted by de_fit_tree_params_bfgs). */
+ * Not served: programs made by de_program_create_cse, more than 32 constants, parameter rows (the per-tree parameter matrices of
+ * §4.4.11 are fitted by de_fit_tree_params_bfgs).  The scaled objective: de_fit_consts_bfgs_scaled below. */
 typedef struct de_bfgs_opts {
     int32_t iters;    /* iterations: one direction, one evaluation and one accept each */
     int32_t reserved; /* 0 */
@@ -918,7 +921,7 @@ int de_fit_consts_bfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t
  * Refusals, before any output or constant is touched: DE_ERR_UNSUPPORTED for DE_F16 / complex programs (and a feature matrix too wide
  * for de_eval_loss_ex); DE_ERR_INVALID_ARG for a spec de_loss_spec_check(spec, 0) refuses, DE_LOSS_PULLBACK, null y or ok on a non-empty
  * population, iters < 0, reserved != 0, a or b not finite or both 0, f_tol negative or not finite.
- * Not served: more than 32 constants per tree, the scaled objective, parameter rows. */
+ * Not served: more than 32 constants per tree, parameter rows.  The scaled objective: de_fit_consts_nm_scaled below. */
 typedef struct de_nm_opts {
     int32_t iters;    /* rounds: one ask, one evaluation and one tell each */
     int32_t reserved; /* 0 */
@@ -932,6 +935,47 @@ int de_nm_tell_host(int G, int dtype, double *V, double *f, int32_t *st, const d
 int de_fit_consts_nm(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
                      const void *y, const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, void *loss, uint8_t *ok,
                      double *history, int32_t *n_improve);
+
+/* The matrix-free fits under Keijzer's linear scaling a + b yhat: de_fit_consts_bfgs and de_fit_consts_nm with the
+ * objective scaled_sse = M2_y - C^2 / M2_p of de_fit_consts_lm_scaled.  Additions: every entry point above keeps its bits, its refusals
+ * and its return values.  Objective and gradient stay in double from the statistics to the decision, whatever the program's element type
+ * (the constants keep it).
+ *
+ * de_scaled_objective_host: the objective and its gradient of ONE tree on the host (no HIP call; csrc/de_fit_scaled.h, the source the
+ * adapter kernel runs: the same bits).  stats = (mean_p, M2_p, C), ystats = (W, mean_y, M2_y), dmom = D | P | Q (3 G doubles; D is not
+ * read).  *sse = de_lm_project_host's (a NaN is the canonical quiet NaN); with b = C / M2_p, g_k = (2 b) (b P_k - Q_k) in that
+ * association, de_lm_project_host's g bit for bit.  M2_p == 0 or W == 0: *sse = M2_y (NaN where C is NaN), g = 0, returns 0.  NaN
+ * statistics propagate.  It returns 1 where the gradient was formed; G outside 1 .. 32 or a null dmom: 0, the G entries of g zero (G < 1:
+ * g is not written); *sse is written whenever stats, ystats and sse are not null.
+ *
+ * de_fit_consts_bfgs_scaled: de_fit_consts_bfgs's loop — direction, Armijo rule, update of B, alpha rules, options and their defaults —
+ * with every evaluation de_eval_fit_stats_grad in mode DE_GRAD_CONSTANT with jtj == NULL (no matrix is formed), f = scaled_sse and g as
+ * above, for trees of 1 .. de_bfgs_max_rows() constants through one path.  A tree with a constant that is redundant under scaling (an
+ * additive or multiplicative constant at the root), which de_fit_consts_lm_scaled leaves alone, is fitted: B needs no factorisation.
+ *
+ * de_fit_consts_nm_scaled: de_fit_consts_nm's loop with every evaluation de_eval_fit_stats and f = scaled_sse (the double itself: the
+ * state's f is not rounded to the element type).  No gradient rows: programs made by de_program_create_cse are served, and a constant
+ * whose partial is zero almost everywhere moves.  It needs the LDS-tiled kernel as de_fit_consts_nm does.
+ *
+ * Both: sse (doubles), stats (may be NULL: 3 doubles per tree at the returned constants), ystats (may be NULL: 3 doubles), ok, history
+ * (may be NULL: (iters + 1) x n_trees doubles of accepted scaled_sse, non-increasing), n_accept / n_improve (may be NULL): host or device
+ * pointers.  Where the loop ran, the statistics are those of ONE more evaluation of the fit's own kind behind it, at the accepted
+ * constants, which the program holds then: stats equal that evaluation's bit for bit, and sse is their scaled_sse.  iters == 0, N == 0
+ * or no constants: the first evaluation's values, every history row equal, the constants untouched.  A tree with ok == 0 at the start,
+ * without constants or with more than 32 keeps its constant bits, -0 and NaN payloads included.  With device pointers the calls
+ * synchronise only where the evaluation they call does.  Refusals, before any output or constant is touched: de_fit_consts_bfgs_scaled
+ * what de_fit_consts_bfgs refuses (DE_F16 / complex / de_program_create_cse programs, constant rows that differ from the constants:
+ * DE_ERR_UNSUPPORTED; its options); de_fit_consts_nm_scaled what de_fit_consts_nm refuses (DE_F16 / complex programs, a feature matrix
+ * too wide for the LDS-tiled kernel: DE_ERR_UNSUPPORTED; its options); both a null y / ok / sse on a non-empty population
+ * (DE_ERR_INVALID_ARG).
+ * Not served: non-L2 kinds under scaling, more than 32 constants per tree, parameter rows. */
+int de_scaled_objective_host(int G, const double *stats, const double *ystats, const double *dmom, double *sse, double *g);
+int de_fit_consts_bfgs_scaled(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                              const void *y, const void *w, const de_bfgs_opts_t *opts,
+                              double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_accept);
+int de_fit_consts_nm_scaled(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                            const void *y, const void *w, const de_nm_opts_t *opts,
+                            double *sse, double *stats, double *ystats, uint8_t *ok, double *history, int32_t *n_improve);
 
 /* Fused loss + gradient of a PARAMETRIC population with the parameter rows reduced BY CLASS:
  *   dparams[(t*n_classes + c)*n_params + p] = sum_{j : class_j = c} w_j l'(e_j) d tree_t(x_j) / d params[p, c]
