@@ -21,6 +21,9 @@ build_obj() { # src obj extra...
 build_obj de_lower.cpp $OBJ/de_lower.o &
 build_obj de_api.cpp $OBJ/de_api.o &
 build_obj de_api_program.cpp $OBJ/de_api_program.o &
+build_obj de_api_program_stream.cpp $OBJ/de_api_program_stream.o &
+build_obj de_api_program_consts.cpp $OBJ/de_api_program_consts.o &
+build_obj de_api_program_inspect.cpp $OBJ/de_api_program_inspect.o &
 build_obj de_api_eval.cpp $OBJ/de_api_eval.o &
 build_obj de_api_grad.cpp $OBJ/de_api_grad.o &
 build_obj de_api_fit.cpp $OBJ/de_api_fit.o &
@@ -136,7 +139,7 @@ build_obj de_fit_scaled.hip $OBJ/de_fit_scaled.o &
 # of de_fit_tree_params_bfgs (plain hipcc; no new object: the fit's kernels live next to the ones whose tables they share)
 build_obj de_tree_params.hip $OBJ/de_tree_params.o &
 wait
-API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o"
+API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_program_stream.o $OBJ/de_api_program_consts.o $OBJ/de_api_program_inspect.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o"
 for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

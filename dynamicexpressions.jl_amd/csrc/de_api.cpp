@@ -1,5 +1,5 @@
 // de_api.cpp — C ABI (include/de_hip.h): registry, contexts, the pool of host threads, recycled device buffers and parked programs.
-// The rest of the ABI: de_api_program.cpp, de_api_eval.cpp, de_api_grad.cpp, de_api_fit.cpp, de_api_tree_params.cpp (de_api_internal.h says what lives where).
+// The rest of the ABI: de_api_program*.cpp, de_api_eval.cpp, de_api_grad.cpp, de_api_fit.cpp, de_api_tree_params.cpp (de_api_internal.h says what lives where).
 #include "de_api_internal.h"
 
 extern "C" {

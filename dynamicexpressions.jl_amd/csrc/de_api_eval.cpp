@@ -253,7 +253,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
         }
         return DE_OK;
     }
-    const bool direct = p->direct && !(p->threaded && !cr); // (the threaded kernel stages a wider X than the flat-switch kernel can: de_api_program.cpp make_threaded)
+    const bool direct = p->direct && !(p->threaded && !cr); // (the threaded kernel stages a wider X than the flat-switch kernel can: de_api_program_stream.cpp make_threaded)
 
     Staged sX, sOut, sOk, sPar, sCls, sY, sW, sLoss, sStats, sYstats;
     LossArgs la;

@@ -1,6 +1,7 @@
 // de_api_internal.h — what the translation units of the C ABI share (round 6: de_api.cpp was one 3 900-line file):
 //   de_api.cpp          registry, contexts, the pool of host threads, the pools of device buffers and parked programs
-//   de_api_program.cpp  de_program_create / _set_consts / _destroy, constant folding, the threaded and chained streams, verify / dump / hash
+//   de_api_program*.cpp de_program_create / _update / _set_consts / _destroy, constant folding, the threaded and chained streams, verify / dump /
+//                       hash — four files, de_api_program.h says what lives where
 //   de_api_eval.cpp     de_eval, de_eval_loss, de_eval_sum_certificate, de_eval_tree_array (staging, launch planning)
 //   de_api_grad.cpp     what PRODUCES gradients and matrices from X: de_eval_grad / _diff / _pullback_dX, de_eval_loss_grad(_by_class),
 //                       de_eval_loss_gn(_ex, _wide), de_eval_fit_stats_grad(_wide): the generic gradient program; glue around the
@@ -193,7 +194,7 @@ struct de_program {
     // {operand word, immediate, address of its handler} and an end record per tree; made from tcode
     std::vector<BoundInstr> ccode;
     std::vector<int32_t> ccode_off;     // n_trees + 1: first record of each tree
-    // WAVE GROUPS (round 6; de_kernels.hip KArgs::var_stride; de_api_program.cpp choose_waves): a program whose one-wave workgroup is short of
+    // WAVE GROUPS (round 6; de_kernels.hip KArgs::var_stride; de_api_program_stream.cpp choose_waves): a program whose one-wave workgroup is short of
     // resident waves (staged parameter rows, many features) runs `waves` (2 / 4 / 8) waves per workgroup on one sample tile — X and the
     // parameter rows staged once, every wave a chunk and spill-slot rows of its own.  Slot rows
     // are host data, so the chained stream exists once per wave: ccode_w = variants 1 .. waves - 1 (each ccode.size() records; the same
@@ -353,9 +354,9 @@ struct Staged {
 int stage_in(de_ctx *c, DevBuf &buf, const void *user, size_t bytes, Staged *s);
 int stage_out(de_ctx *c, DevBuf &buf, void *user, size_t bytes, Staged *s);
 int check_param_args(de_ctx *c, const de_program *p, const de_param_args_t *pa, int64_t N);
-// the host copies of a program brought up to its device constants (de_api_program.cpp); DE_OK at once when they are current
+// the host copies of a program brought up to its device constants (de_api_program_consts.cpp); DE_OK at once when they are current
 int consts_materialise(de_program *p);
-// the body of de_program_set_consts_device (de_api_program.cpp): de_fit_consts_lm sets its trial and accepted constants through it
+// the body of de_program_set_consts_device (de_api_program_consts.cpp): de_fit_consts_lm sets its trial and accepted constants through it
 int set_consts_device_impl(de_program *p, const void *d_consts);
 // what de_fit_consts_bfgs and de_fit_tree_params_bfgs refuse about their options (de_api_fit.cpp): null = good, else the reason
 const char *bfgs_opts_problem(const de_bfgs_opts_t *o);

@@ -280,7 +280,7 @@ def test_ctx_trim_releases_the_retained_buffers_and_the_context_stays_usable(api
     assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)
 
 
-# ---- wave groups (csrc/de_api_program.cpp choose_waves, de_kernels.hip KArgs::var_stride) ----------------------------------------------------
+# ---- wave groups (csrc/de_api_program_stream.cpp choose_waves, de_kernels.hip KArgs::var_stride) ----------------------------------------------------
 def _wave_case(kind, dtype, g):
     """(trees, operators, X, params, classes, P): a population whose one-wave workgroup is short of resident waves."""
     ops = de.synth.BENCH_OPERATORS

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Wave groups (DE_EVAL_WAVES = 1 | 2 | 4, csrc/de_api_program.cpp choose_waves): parametric evaluation with W waves per workgroup sharing
+"""Wave groups (DE_EVAL_WAVES = 1 | 2 | 4, csrc/de_api_program_stream.cpp choose_waves): parametric evaluation with W waves per workgroup sharing
 the staged X / parameter rows.  Bit-equality of values, flags and fused losses against one-wave workgroups, and the time of each.
 
     gpurun -- 'timeout 600 python tools/experiments/wave_groups.py'
