@@ -65,6 +65,8 @@ EXPORTS = [
     "de_lower_tape_assured_fact",
     "de_nm_max_rows", "de_nm_ask_host", "de_nm_tell_host", "de_fit_consts_nm",
     "de_scaled_objective_host", "de_fit_consts_bfgs_scaled", "de_fit_consts_nm_scaled",
+    "de_lbfgs_max_rows", "de_lbfgs_max_memory", "de_lbfgs_direction_host", "de_lbfgs_update_host", "de_fit_consts_lbfgs",
+    "de_fit_tree_params_lbfgs",
 ]
 
 
@@ -103,6 +105,13 @@ class BfgsOpts(C.Structure):
     """``de_bfgs_opts_t``: what ``de_fit_consts_bfgs`` takes besides the data (null: 20 iterations, step0 1, shrink 0.5, c1 1e-4, curv 1e-8)."""
     _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("step0", C.c_double), ("shrink", C.c_double), ("c1", C.c_double),
                 ("curv", C.c_double)]
+
+
+class LbfgsOpts(C.Structure):
+    """``de_lbfgs_opts_t``: what ``de_fit_consts_lbfgs`` / ``de_fit_tree_params_lbfgs`` take besides the data (null: 20 iterations, memory
+    8, step0 1, shrink 0.5, c1 1e-4, curv 1e-8)."""
+    _fields_ = [("iters", C.c_int32), ("reserved", C.c_int32), ("memory", C.c_int32), ("reserved2", C.c_int32), ("step0", C.c_double),
+                ("shrink", C.c_double), ("c1", C.c_double), ("curv", C.c_double)]
 
 
 class NmOpts(C.Structure):
@@ -201,6 +210,8 @@ class FitStats:
 
 GN_MAX_ROWS = 8  # de_gn_max_rows(): the widest tree (gradient rows of the library's layout) de_eval_loss_gn forms the matrix of
 GN_WIDE_MAX_ROWS = 32  # de_gn_wide_max_rows(): ... and de_eval_loss_gn_wide (``wide=True``)
+LBFGS_MAX_ROWS = 4096  # de_lbfgs_max_rows(): the widest tree de_fit_consts_lbfgs / de_fit_tree_params_lbfgs fit
+LBFGS_MAX_MEMORY = 16  # de_lbfgs_max_memory(): the longest ring of (s, yv) pairs
 BFGS_MAX_ROWS = 32  # de_bfgs_max_rows(): the widest tree de_fit_consts_bfgs fits
 NM_MAX_ROWS = 32  # de_nm_max_rows(): the widest tree de_fit_consts_nm fits
 # the phases of the Nelder-Mead state (csrc/de_nm.h; ``NmState.st[0]``)
@@ -543,6 +554,131 @@ def bfgs_update_host(B, fresh, s, yv, curv: float = 1e-8):
     return bool(rc), B, bool(fr[0])
 
 
+class LbfgsState:
+    """The L-BFGS state of one tree of ``G`` unknowns (include/de_hip.h), all float64 / int32: the ring ``S[memory, G]``,
+    ``Y[memory, G]``, ``rho[memory]``, ``count`` stored pairs, ``head`` the next slot to write, and ``alpha`` the line-search step.  A
+    fresh state is empty; the hooks change it in place."""
+
+    def __init__(self, G: int, memory: int = 8, alpha: float = 1.0):
+        self.G, self.memory = int(G), int(memory)
+        shape = (max(self.memory, 1), max(self.G, 1))
+        self.S, self.Y, self.rho = np.zeros(shape), np.zeros(shape), np.zeros(shape[0])
+        self.count, self.head, self.alpha = 0, 0, float(alpha)
+
+    def newest_first(self):
+        """The slots of the stored pairs, newest first."""
+        return [(self.head - 1 - i) % self.memory for i in range(self.count)]
+
+
+def lbfgs_direction_host(state: LbfgsState, g, step0: float = 1.0):
+    """``de_lbfgs_direction_host``: the two-loop recursion of the device's L-BFGS fit (csrc/de_lbfgs.h) for one tree on the host, no GPU
+    needed.  Returns (p[G], slope, produced) in float64; ``state.count`` / ``state.alpha`` become 0 / ``a0(g)`` where the ring gives no
+    descent direction.  ``produced`` False: ``p`` is zero (a non-finite entry of ``g`` or of a stored pair, g = 0).  A ``G`` or a state
+    the library does not take (G outside 1 .. ``LBFGS_MAX_ROWS``, memory outside 1 .. ``LBFGS_MAX_MEMORY``): nothing is written — ``p``
+    and the slope come back NaN."""
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+    G = g.size
+    if G != state.G:
+        raise ValueError("g must have state.G entries")
+    cnt, head = np.array([state.count], dtype=np.int32), np.array([state.head], dtype=np.int32)
+    al, p, slope = np.array([float(state.alpha)]), np.full(max(G, 1), np.nan), np.full(1, np.nan)
+    rc = library().de_lbfgs_direction_host(G, state.memory, state.S.ctypes.data, state.Y.ctypes.data, state.rho.ctypes.data, cnt.ctypes.data,
+                                           head.ctypes.data, al.ctypes.data, g.ctypes.data, float(step0), p.ctypes.data, slope.ctypes.data)
+    state.count, state.alpha = int(cnt[0]), float(al[0])
+    return p[:G], float(slope[0]), bool(rc)
+
+
+def lbfgs_update_host(state: LbfgsState, s, yv, curv: float = 1e-8) -> bool:
+    """``de_lbfgs_update_host``: the pair ``(s, yv)`` — the step taken and the change of the gradient — stored in slot ``state.head`` of
+    the ring where ``s.yv > curv |s| |yv|`` (csrc/de_lbfgs.h) for one tree on the host.  Returns ``updated``; a refused pair leaves every
+    byte of the state."""
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+    yv = np.ascontiguousarray(yv, dtype=np.float64).reshape(-1)
+    if s.size != state.G or yv.size != state.G:
+        raise ValueError("s and yv have state.G entries each")
+    cnt, head = np.array([state.count], dtype=np.int32), np.array([state.head], dtype=np.int32)
+    rc = library().de_lbfgs_update_host(state.G, state.memory, state.S.ctypes.data, state.Y.ctypes.data, state.rho.ctypes.data,
+                                        cnt.ctypes.data, head.ctypes.data, s.ctypes.data, yv.ctypes.data, float(curv))
+    state.count, state.head = int(cnt[0]), int(head[0])
+    return bool(rc)
+
+
+def lbfgs_dot(p, q) -> float:
+    """The dot product of the L-BFGS fit in csrc/de_lbfgs.h's order: 64 partial sums, partial ``l`` over ``k = l, l + 64, ...`` ascending
+    from 0.0, then the partials added in the order ``l = 0 .. 63`` from 0.0."""
+    pq = np.asarray(p, dtype=np.float64).reshape(-1) * np.asarray(q, dtype=np.float64).reshape(-1)
+    part = np.zeros(64)
+    for r in range(0, pq.size, 64):
+        row = pq[r:r + 64]
+        part[:row.size] = part[:row.size] + row
+    s = 0.0
+    for v in part.tolist():
+        s = s + v
+    return s
+
+
+def _lbfgs_a0(g, step0: float) -> float:
+    """The first trial step's length, ``|g| > step0 ? step0 / |g| : 1``, with ``g . g`` in ``lbfgs_dot``'s order."""
+    n = math.sqrt(lbfgs_dot(g, g))
+    return step0 / n if n > step0 else 1.0
+
+
+def _lbfgs_opts(iters, memory, step0, shrink, c1, curv, loss, loss_param):
+    """(``LbfgsOpts``, ``LossSpec``) of an L-BFGS fit, refused as ``de_fit_consts_lbfgs`` refuses them: a ``ValueError``."""
+    b, spec = _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
+    if not 1 <= int(memory) <= LBFGS_MAX_MEMORY:
+        raise ValueError(f"L-BFGS fit: memory in 1 .. {LBFGS_MAX_MEMORY}")
+    return LbfgsOpts(b.iters, 0, int(memory), 0, b.step0, b.shrink, b.c1, b.curv), spec
+
+
+def lbfgs_fit(evaluate, x0, iters: int = 20, memory: int = 8, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
+              curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
+    """The host loop of the device's L-BFGS fits over one vector of unknowns per tree, through
+    ``lbfgs_direction_host`` / ``lbfgs_update_host``: per tree and iteration the direction ``p`` and its slope, the trial ``T(x + alpha
+    p)``, accepted if its tree is complete and ``f_trial < f`` and ``f_trial <= f + (c1 alpha) slope`` (Armijo); an accepted tree's ring
+    takes the pair of the step actually taken and ``alpha`` returns to 1 (``a0(g)`` while the ring is empty), a rejected tree's ``alpha``
+    shrinks.  ``evaluate(xs) -> (loss[n_trees], grads (one float64 array per tree), ok[n_trees])`` serves all trees at once (any
+    stand-in: the loop itself needs no GPU).  Trees with more than ``LBFGS_MAX_ROWS`` unknowns, without unknowns or incomplete at the
+    start keep their values.  Returns (xs, loss, ok, accepts); ``history`` (a list) receives the accepted losses (float64) after every
+    evaluation."""
+    dtype, f64 = np.dtype(dtype), np.float64
+    x = [np.array(_host(v), dtype=dtype).reshape(-1).copy() for v in x0]
+    nt = len(x)
+
+    def run(vs):
+        lo, gr, ok = evaluate(vs)
+        return _host(lo).copy(), [np.array(_host(g), dtype=f64).reshape(-1) for g in gr], _host(ok).astype(bool).copy()
+
+    fitted = [1 <= len(v) <= LBFGS_MAX_ROWS for v in x]
+    lo, gr, ok = run(x)
+    st = [LbfgsState(len(v), memory, _lbfgs_a0(gr[t], step0)) if fitted[t] else None for t, v in enumerate(x)]
+    acc = np.zeros(nt, dtype=np.int32)
+    if history is not None:
+        history.append(lo.astype(f64))
+    for _ in range(int(iters)):
+        trial, produced, slope = [v.copy() for v in x], [False] * nt, [0.0] * nt
+        for t in range(nt):
+            if fitted[t] and ok[t]:
+                p, slope[t], produced[t] = lbfgs_direction_host(st[t], gr[t], step0)
+                if produced[t]:
+                    trial[t] = (x[t].astype(f64) + st[t].alpha * p).astype(dtype)
+        lo_t, gr_t, ok_t = run(trial)
+        for t in range(nt):
+            f, ft = float(lo[t]), float(lo_t[t])
+            if (fitted[t] and ok[t] and produced[t] and ok_t[t] and math.isfinite(ft) and ft < f
+                    and ft <= f + (c1 * st[t].alpha) * slope[t]):
+                lbfgs_update_host(st[t], trial[t].astype(f64) - x[t].astype(f64), gr_t[t] - gr[t], curv)
+                x[t] = trial[t]
+                lo[t], gr[t], ok[t] = lo_t[t], gr_t[t], ok_t[t]
+                st[t].alpha = _lbfgs_a0(gr[t], step0) if st[t].count == 0 else 1.0
+                acc[t] += 1
+            elif st[t] is not None:
+                st[t].alpha = st[t].alpha * shrink
+        if history is not None:
+            history.append(lo.astype(f64))
+    return x, lo, ok, acc
+
+
 def scaled_objective_host(stats3, ystats3, D, P, Q):
     """``de_scaled_objective_host``: the objective of the matrix-free fits under linear scaling and its gradient (csrc/de_fit_scaled.h,
     the code the adapter kernel runs) for one tree on the host, no GPU needed — (scaled_sse, g[G], formed) in float64 from ``stats3 =
@@ -837,6 +973,15 @@ def library() -> C.CDLL:
         lib.de_eval_loss_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp]
         lib.de_eval_loss_grad_tree_params.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), vp, vp, vp, vp, vp]
         lib.de_tree_params_accumulate_host.argtypes = [C.c_int, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "de_fit_consts_lbfgs"):  # (absent from a library built before the device L-BFGS fits: DE_HIP_LIB in an A/B run)
+        lib.de_lbfgs_max_rows.argtypes = []
+        lib.de_lbfgs_max_memory.argtypes = []
+        lib.de_lbfgs_direction_host.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp]
+        lib.de_lbfgs_update_host.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double]
+        lib.de_fit_consts_lbfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(LbfgsOpts),
+                                            vp, vp, vp, vp]
+        lib.de_fit_tree_params_lbfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec),
+                                                 C.POINTER(LbfgsOpts), vp, vp, vp, vp, vp]
     if hasattr(lib, "de_fit_tree_params_bfgs"):  # (absent from a library built before the device fit over parameters: DE_HIP_LIB in an A/B run)
         lib.de_fit_tree_params_bfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
                                                 vp, vp, vp, vp, vp]
@@ -2189,6 +2334,56 @@ class Population:
             history.extend(hist[r] for r in range(int(iters) + 1))
         return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
 
+    def fit_constants_lbfgs(self, X, y, consts0, weights=None, iters: int = 20, memory: int = 8, step0: float = 1.0, shrink: float = 0.5,
+                            c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                            history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+        """L-BFGS on the constants of every tree at once (``lbfgs_fit``: the plain loop over ``eval_loss_grad``) — the
+        reference's ``optimize(f, g!, tree, LBFGS())`` with a backtracking line search, for the trees ``fit_constants_bfgs`` leaves
+        alone: every tree of up to ``LBFGS_MAX_ROWS`` constants is fitted, with a ring of ``memory`` pairs.  Arguments, objectives and
+        results as ``fit_constants_bfgs``, but the returned loss and flags are those of one ``eval_loss`` at the accepted constants (the
+        fused loss alone: ``eval_loss`` there reproduces them bit for bit; ``history`` keeps the losses of the accept rule, which are
+        ``eval_loss_grad``'s and may differ from it in the last bits).  ``self.lbfgs_accepts`` holds the accepted steps per tree."""
+        self._refuse_f16("fit_constants_lbfgs")
+        _lbfgs_opts(iters, memory, step0, shrink, c1, curv, loss, loss_param)  # (refused before the population's constants are touched)
+        consts = np.array(_host(consts0), dtype=self.dtype).reshape(-1).copy()
+        if consts.size != int(self.n_consts.sum()):
+            raise ValueError("wrong number of constants")
+        at = np.cumsum(self.n_consts)[:-1]
+
+        def evaluate(xs):
+            self.set_constants(np.concatenate(xs) if xs else np.zeros(0, dtype=self.dtype))
+            return self.eval_loss_grad(X, y, weights=weights, loss=loss, loss_param=loss_param, params=params, classes=classes,
+                                       class_base=class_base)
+
+        xs, lo, ok, acc = lbfgs_fit(evaluate, np.split(consts, at) if self.n_trees else [], iters, memory, step0, shrink, c1, curv,
+                                    self.dtype, history)
+        consts = np.concatenate(xs) if xs else consts
+        self.set_constants(consts)
+        self.lbfgs_accepts = acc
+        lo, ok = self.eval_loss(X, y, weights=weights, loss=loss, params=params, classes=classes, class_base=class_base, loss_param=loss_param)
+        return consts, _host(lo).copy(), _host(ok).astype(bool).copy()
+
+    def fit_constants_lbfgs_device(self, X, y, consts0=None, weights=None, iters: int = 20, memory: int = 8, step0: float = 1.0,
+                                   shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                                   history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+        """``fit_constants_lbfgs`` as ONE library call (``de_fit_consts_lbfgs``): the two-loop recursions, the trial
+        constants, the accept rule and the rings run on the device, and the trajectory is the host loop's bit for bit.  Arguments and
+        results as ``fit_constants_bfgs_device``, the loss and flags being ``eval_loss``'s at the accepted constants as there; ``self.lbfgs_accepts`` holds the number of accepted steps per tree."""
+        self._refuse_f16("fit_constants_lbfgs_device")
+        opts, spec = _lbfgs_opts(iters, memory, step0, shrink, c1, curv, loss, loss_param)
+        if self._occ is not None:
+            raise ValueError("fit_constants_lbfgs_device: the population shares GraphNode constants (their per-occurrence rows are combined "
+                             "on the host): use fit_constants_lbfgs")
+        ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_lbfgs_device", X, y, weights, consts0, params,
+                                                                                classes, class_base)
+        lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
+        self.ctx.check(library().de_fit_consts_lbfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
+                                                     C.byref(opts), *ptrs))
+        self.lbfgs_accepts = acc
+        if history is not None:
+            history.extend(hist[r] for r in range(int(iters) + 1))
+        return self.constants(device=is_t), lo, (ok.bool() if is_t else ok.astype(bool))
+
     def fit_constants_nm(self, X, y, consts0, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5, f_tol: float = 0.0,
                          loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None, params=None, classes=None,
                          class_base: int = 1, scaled: bool = False):
@@ -2708,14 +2903,10 @@ def tree_params_unpack_host(slot_param, n_params: int, x, slot_values, params_tr
         params_tree[...] = blk.T
 
 
-def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
-                         curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
-    """The host loop of ``Population.fit_constants_bfgs`` over each tree's combined vector ``vcat(constants, params[t].T.reshape(-1))`` —
-    the reference's order (src/ParametricExpression.jl:258-278) — through ``bfgs_direction_host`` / ``bfgs_update_host``.
-    ``evaluate(consts_list, params[n_trees, n_params, n_classes]) -> (loss[n_trees], dconsts_list, dparams[n_trees, n_params, n_classes],
-    ok[n_trees])`` serves all trees at once (``ParametricPopulation.eval_loss_grad``, or any stand-in: the loop itself needs no GPU).
-    Trees with more than ``BFGS_MAX_ROWS`` unknowns, without unknowns or incomplete at the start keep their values.  Returns (consts_list,
-    params, loss, ok, accepts); ``history`` (a list) receives the accepted losses (float64) after every evaluation."""
+def _tree_params_packed(evaluate, consts0, params0, dtype):
+    """The combined vectors ``vcat(constants, params[t].T.reshape(-1))`` of ``tree_params_fit_bfgs`` / ``tree_params_fit_lbfgs``: (x,
+    run, unpack) — one vector per tree, ``run(vs) -> (loss, grads (float64, the same order), ok)`` over their ``evaluate`` and
+    ``unpack(vs) -> (consts_list, params)``."""
     dtype, f64 = np.dtype(dtype), np.float64
     params = np.array(_host(params0), dtype=dtype).copy()
     if params.ndim != 3:
@@ -2724,9 +2915,6 @@ def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: flo
     consts = [np.array(_host(c), dtype=dtype).reshape(-1).copy() for c in consts0]
     if len(consts) != nt:
         raise ValueError("consts0 must hold one array per tree")
-
-    def pack(cs, ps):  # vcat(constants, parameters[:])
-        return [np.concatenate([cs[t], ps[t].T.reshape(-1)]) for t in range(nt)]
 
     def unpack(vs):
         cs = [v[:len(consts[t])].copy() for t, v in enumerate(vs)]
@@ -2740,7 +2928,30 @@ def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: flo
         gr = [np.concatenate([_host(dc[t]).astype(f64).reshape(-1), dp[t].astype(f64).T.reshape(-1)]) for t in range(nt)]
         return lo, gr, ok
 
-    x = pack(consts, params)
+    return [np.concatenate([consts[t], params[t].T.reshape(-1)]) for t in range(nt)], run, unpack
+
+
+def tree_params_fit_lbfgs(evaluate, consts0, params0, iters: int = 20, memory: int = 8, step0: float = 1.0, shrink: float = 0.5,
+                          c1: float = 1e-4, curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
+    """``tree_params_fit_bfgs`` with ``lbfgs_fit`` as the loop: the same combined vectors, the same ``evaluate``, and
+    every tree of up to ``LBFGS_MAX_ROWS`` unknowns is fitted.  Returns (consts_list, params, loss, ok, accepts)."""
+    x, run, unpack = _tree_params_packed(evaluate, consts0, params0, dtype)
+    xs, lo, ok, acc = lbfgs_fit(run, x, iters, memory, step0, shrink, c1, curv, dtype, history)
+    cs, ps = unpack(xs)
+    return cs, ps, lo, ok, acc
+
+
+def tree_params_fit_bfgs(evaluate, consts0, params0, iters: int = 20, step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4,
+                         curv: float = 1e-8, dtype=np.float64, history: Optional[list] = None):
+    """The host loop of ``Population.fit_constants_bfgs`` over each tree's combined vector ``vcat(constants, params[t].T.reshape(-1))`` —
+    the reference's order (src/ParametricExpression.jl:258-278) — through ``bfgs_direction_host`` / ``bfgs_update_host``.
+    ``evaluate(consts_list, params[n_trees, n_params, n_classes]) -> (loss[n_trees], dconsts_list, dparams[n_trees, n_params, n_classes],
+    ok[n_trees])`` serves all trees at once (``ParametricPopulation.eval_loss_grad``, or any stand-in: the loop itself needs no GPU).
+    Trees with more than ``BFGS_MAX_ROWS`` unknowns, without unknowns or incomplete at the start keep their values.  Returns (consts_list,
+    params, loss, ok, accepts); ``history`` (a list) receives the accepted losses (float64) after every evaluation."""
+    dtype, f64 = np.dtype(dtype), np.float64
+    x, run, unpack = _tree_params_packed(evaluate, consts0, params0, dtype)  # vcat(constants, parameters[:])
+    nt = len(x)
     fitted = [1 <= len(v) <= BFGS_MAX_ROWS for v in x]
     lo, gr, ok = run(x)
     B = [np.eye(len(v)) for v in x]
@@ -3040,14 +3251,17 @@ class ParametricPopulation:
 
     def fit_bfgs(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, step0: float = 1.0,
                  shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
-                 history: Optional[list] = None, class_base: int = 1, evaluate=None):
+                 history: Optional[list] = None, class_base: int = 1, evaluate=None, _memory: int = 0):
         """BFGS over each member's ``vcat(constants, parameters[:])`` (``tree_params_fit_bfgs``: the host loop of
         ``Population.fit_constants_bfgs``), one ``eval_loss_grad`` per iteration for all members.  ``consts0``: the real constants
         (``set_constants``' layout; default: the current ones); ``params0``: ``[n_trees, n_params, n_classes]`` (default: the
         expressions' parameters).  ``evaluate`` replaces the device evaluator (see ``tree_params_fit_bfgs``).  Returns (consts, params,
         loss, ok); the population holds the fitted constants afterwards, ``self.params`` the fitted parameters and
         ``self.bfgs_accepts`` the accepted steps per member."""
-        _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
+        if _memory:  # (fit_lbfgs: the same method around tree_params_fit_lbfgs)
+            _lbfgs_opts(iters, _memory, step0, shrink, c1, curv, loss, loss_param)
+        else:
+            _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
         params0 = self.params if params0 is None else params0
         c0 = self.constants() if consts0 is None else np.ascontiguousarray(_host(consts0), dtype=self.dtype).reshape(-1)
         if c0.size != len(self._real):
@@ -3072,12 +3286,41 @@ class ParametricPopulation:
                 return self.eval_loss_grad(Xs, ys, params, cs, weights=ws, loss=loss, loss_param=loss_param, class_base=class_base,
                                            grouped=True)
 
-        cs_fit, ps, lo, ok, acc = tree_params_fit_bfgs(evaluate, np.split(c0, at) if self.n_trees else [], params0, iters, step0, shrink,
-                                                      c1, curv, self.dtype, history)
+        cs0 = np.split(c0, at) if self.n_trees else []
+        if _memory:
+            cs_fit, ps, lo, ok, acc = tree_params_fit_lbfgs(evaluate, cs0, params0, iters, _memory, step0, shrink, c1, curv, self.dtype, history)
+        else:
+            cs_fit, ps, lo, ok, acc = tree_params_fit_bfgs(evaluate, cs0, params0, iters, step0, shrink, c1, curv, self.dtype, history)
         consts = np.concatenate(cs_fit) if cs_fit else np.zeros(0, dtype=self.dtype)
         self.set_constants(consts)
-        self.params, self.bfgs_accepts = ps, acc
+        self.params = ps
+        if _memory:
+            self.lbfgs_accepts = acc
+        else:
+            self.bfgs_accepts = acc
         return consts, ps, lo, ok
+
+    def fit_lbfgs(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, memory: int = 8, step0: float = 1.0,
+                  shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
+                  history: Optional[list] = None, class_base: int = 1, evaluate=None):
+        """``fit_bfgs`` with L-BFGS (``tree_params_fit_lbfgs``): members of up to ``LBFGS_MAX_ROWS`` unknowns are
+        fitted — ``n_real + n_params * n_classes`` passes ``BFGS_MAX_ROWS`` with a handful of classes — with a ring of ``memory`` pairs
+        each.  Arguments and results as ``fit_bfgs``; ``self.lbfgs_accepts`` holds the accepted steps per member."""
+        if not 1 <= int(memory) <= LBFGS_MAX_MEMORY:
+            raise ValueError(f"L-BFGS fit: memory in 1 .. {LBFGS_MAX_MEMORY}")
+        return self.fit_bfgs(X, y, params0, classes, consts0, weights, iters, step0, shrink, c1, curv, loss, loss_param, history, class_base,
+                             evaluate, _memory=int(memory))
+
+    def fit_lbfgs_device(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, memory: int = 8,
+                         step0: float = 1.0, shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2",
+                         loss_param: float = 0.0, class_base: int = 1, grouped: bool = False, history: bool = False):
+        """``fit_lbfgs`` as ONE library call (``de_fit_tree_params_lbfgs``), the trajectory the host loop's bit for
+        bit.  Arguments and results as ``fit_bfgs_device``; ``self.lbfgs_accepts`` / ``self.lbfgs_history`` take the accepted steps and,
+        with ``history=True``, the accepted losses."""
+        if not 1 <= int(memory) <= LBFGS_MAX_MEMORY:
+            raise ValueError(f"L-BFGS fit: memory in 1 .. {LBFGS_MAX_MEMORY}")
+        return self.fit_bfgs_device(X, y, params0, classes, consts0, weights, iters, step0, shrink, c1, curv, loss, loss_param, class_base,
+                                    grouped, history, _memory=int(memory))
 
     @staticmethod
     def check_fit_args(n_real: int, consts0, iters, step0, shrink, c1, curv, loss, loss_param):
@@ -3090,7 +3333,7 @@ class ParametricPopulation:
 
     def fit_bfgs_device(self, X, y, params0=None, classes=None, consts0=None, weights=None, iters: int = 20, step0: float = 1.0,
                         shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
-                        class_base: int = 1, grouped: bool = False, history: bool = False):
+                        class_base: int = 1, grouped: bool = False, history: bool = False, _memory: int = 0):
         """``fit_bfgs`` as ONE library call (``de_fit_tree_params_bfgs``): the packed vectors, the directions, the
         trials, the class loop of every evaluation, the accept rule and the updates of ``B`` run on the device; no constant, gradient or
         parameter reaches the host, and the trajectory is the host loop's bit for bit.  ``consts0`` / ``params0``: as ``fit_bfgs`` (numpy
@@ -3126,9 +3369,15 @@ class ParametricPopulation:
             ok = np.zeros(nt, dtype=np.uint8)
             hist, acc = np.empty((rows, nt), dtype=np.float64), np.zeros(nt, dtype=np.int32)
             ptrs = (outb.ctypes.data if nt * ncls * P else None, lo.ctypes.data, ok.ctypes.data, hist.ctypes.data, acc.ctypes.data)
-        self.ctx.check(library().de_fit_tree_params_bfgs(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
-                                                         C.byref(opts), *ptrs))
-        self.bfgs_accepts, self.bfgs_history = acc, (hist if history else None)
+        if _memory:  # (fit_lbfgs_device: the same call around de_fit_tree_params_lbfgs)
+            lopts = LbfgsOpts(opts.iters, 0, _memory, 0, opts.step0, opts.shrink, opts.c1, opts.curv)
+            self.ctx.check(library().de_fit_tree_params_lbfgs(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                              C.byref(lopts), *ptrs))
+            self.lbfgs_accepts, self.lbfgs_history = acc, (hist if history else None)
+        else:
+            self.ctx.check(library().de_fit_tree_params_bfgs(self.ctx._h, self.pop._h, ptr, N, ldX, C.byref(tp), yp, wp, C.byref(spec),
+                                                             C.byref(opts), *ptrs))
+            self.bfgs_accepts, self.bfgs_history = acc, (hist if history else None)
         if is_t:
             ps = outb[:, :, :P].transpose(1, 2)
             consts = self.pop.constants(device=True)[torch.as_tensor(self._real, device=kx.device)]

@@ -131,6 +131,8 @@ build_obj de_lm_scaled.hip $OBJ/de_lm_scaled.o &
 build_obj de_lm_scaled_wide.hip $OBJ/de_lm_scaled_wide.o &
 # de_fit_consts_bfgs: the init, direction and accept kernels of the BFGS fit, one wave per tree (plain hipcc)
 build_obj de_bfgs.hip $OBJ/de_bfgs.o &
+# de_fit_consts_lbfgs / de_fit_tree_params_lbfgs: the init, direction and accept kernels of the L-BFGS fit, one wave per tree (plain hipcc)
+build_obj de_lbfgs.hip $OBJ/de_lbfgs.o &
 # de_fit_consts_nm: the init, ask and tell kernels of the Nelder-Mead fit, one wave per tree (plain hipcc)
 build_obj de_nm.hip $OBJ/de_nm.o &
 # de_fit_consts_bfgs_scaled / de_fit_consts_nm_scaled: the adapter kernel from fit statistics to a double objective and gradient (plain hipcc)
@@ -140,6 +142,6 @@ build_obj de_fit_scaled.hip $OBJ/de_fit_scaled.o &
 build_obj de_tree_params.hip $OBJ/de_tree_params.o &
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_program_stream.o $OBJ/de_api_program_consts.o $OBJ/de_api_program_inspect.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

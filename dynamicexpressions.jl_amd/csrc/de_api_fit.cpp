@@ -1,7 +1,7 @@
 // de_api_fit.cpp — C ABI (include/de_hip.h): what CONSUMES the gradients and matrices de_api_grad.cpp produces.  de_gn_lm_step /
 // de_fit_stats_lm_step (and _wide): one Levenberg-Marquardt step per tree (kernels de_lm.hip, de_gn_wide.hip, de_lm_scaled.hip,
 // de_lm_scaled_wide.hip); de_fit_consts_lm(_ex, _wide), de_fit_consts_lm_scaled(_wide) and
-// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10), de_fit_consts_nm (kernels de_nm.hip, §4.4.13) and the scaled forms of those two
+// de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10), de_fit_consts_lbfgs (kernels de_lbfgs.hip, §4.4.15), de_fit_consts_nm (kernels de_nm.hip, §4.4.13) and the scaled forms of those two
 // (de_fit_consts_bfgs_scaled / de_fit_consts_nm_scaled, adapter kernel de_fit_scaled.hip, §4.4.14): fits on the constants that are
 // ONE driver — fit_check, stage_fit_inputs, a Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host
 // hooks that run the kernels' arithmetic.
@@ -15,6 +15,8 @@
 #include "de_lm_project_wide.h"
 #include "de_bfgs.h"
 #include "de_bfgs_dev.h"
+#include "de_lbfgs.h"
+#include "de_lbfgs_dev.h"
 #include "de_nm.h"
 #include "de_nm_dev.h"
 #include "de_fit_scaled.h"
@@ -22,7 +24,7 @@
 
 extern "C" {
 // ---- the host hooks: the arithmetic of the step, projection and BFGS kernels on host buffers (de_lm_solve.h, de_lm_solve_wide.h,
-// de_lm_project.h, de_lm_project_wide.h, de_bfgs.h) -----------------------------------------------------------------------------------------
+// de_lm_project.h, de_lm_project_wide.h, de_bfgs.h, de_lbfgs.h) -----------------------------------------------------------------------------------------
 int de_lm_solve_host(int G, const double *H, const double *g, double lam, double *step) {
     double x[LM_MAX_ROWS];
     const bool args = G <= 0 || (H && g);
@@ -70,6 +72,28 @@ int de_bfgs_update_host(int G, double *B, uint8_t *fresh, const double *s, const
     if (!B || !fresh || !s || !yv) return 0;
     return bfgs_update(G, B, fresh, s, yv, curv);
 }
+int de_lbfgs_max_rows(void) { return LBFGS_MAX_ROWS; }
+int de_lbfgs_max_memory(void) { return LBFGS_MAX_MEMORY; }
+static bool lbfgs_hook_args(int G, int memory, const int32_t *count, const int32_t *head) {
+    return G >= 1 && G <= LBFGS_MAX_ROWS && memory >= 1 && memory <= LBFGS_MAX_MEMORY && count && head && *count >= 0 && *count <= memory &&
+           *head >= 0 && *head < memory;
+}
+int de_lbfgs_direction_host(int G, int memory, const double *S, const double *Y, const double *rho, int32_t *count, int32_t *head,
+                            double *alpha, const double *g, double step0, double *p, double *slope) {
+    if (!S || !Y || !rho || !alpha || !g || !p || !slope || !lbfgs_hook_args(G, memory, count, head)) return 0; // (nothing is written)
+    LbfgsHostTeam tm;
+    const LbfgsDir r = lbfgs_direction(tm, G, memory, S, Y, rho, *count, *head, *alpha, g, step0, p);
+    *count = r.count;
+    *alpha = r.alpha;
+    *slope = r.slope;
+    return r.produced;
+}
+int de_lbfgs_update_host(int G, int memory, double *S, double *Y, double *rho, int32_t *count, int32_t *head, const double *s,
+                         const double *yv, double curv) {
+    if (!S || !Y || !rho || !s || !yv || !lbfgs_hook_args(G, memory, count, head)) return 0;
+    LbfgsHostTeam tm;
+    return lbfgs_update(tm, G, memory, S, Y, rho, count, head, s, yv, curv);
+}
 int de_scaled_objective_host(int G, const double *stats, const double *ystats, const double *dmom, double *sse, double *g) {
     if (stats && ystats && sse) *sse = lm_scaled_sse(stats[1], stats[2], ystats[0], ystats[2]);
     if (stats && ystats && dmom && g && G >= 1 && G <= FIT_SCALED_MAX_ROWS) {
@@ -107,6 +131,17 @@ const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
     for (const double v : {o->step0, o->c1, o->curv})
         if (!(std::isfinite(v) && v > 0.0)) return "de_bfgs_opts_t: step0, c1 and curv must be finite and positive";
     if (!(o->shrink > 0.0 && o->shrink < 1.0)) return "de_bfgs_opts_t: shrink must lie in (0, 1)";
+    return nullptr;
+}
+// de_lbfgs_opts_t: bfgs_opts_problem's refusals of the fields they share, and of its own two; *o: the shared fields
+const char *lbfgs_opts_problem(const de_lbfgs_opts_t *l, de_bfgs_opts_t *o) {
+    *o = de_bfgs_opts_t{l->iters, l->reserved, l->step0, l->shrink, l->c1, l->curv};
+    if (l->reserved != 0 || l->reserved2 != 0) return "de_lbfgs_opts_t: reserved and reserved2 must be 0";
+    if (l->memory < 1 || l->memory > LBFGS_MAX_MEMORY) return "de_lbfgs_opts_t: memory must lie in 1 .. de_lbfgs_max_memory()";
+    if (l->iters < 0) return "de_lbfgs_opts_t: iters < 0";
+    for (const double v : {l->step0, l->c1, l->curv})
+        if (!(std::isfinite(v) && v > 0.0)) return "de_lbfgs_opts_t: step0, c1 and curv must be finite and positive";
+    if (!(l->shrink > 0.0 && l->shrink < 1.0)) return "de_lbfgs_opts_t: shrink must lie in (0, 1)";
     return nullptr;
 }
 static const char *nm_opts_problem(const de_nm_opts_t *o) {
@@ -340,11 +375,11 @@ static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char 
 // (false) or the trial (true) state; init: the per-tree state; first_history(row 0) behind it; then, where nothing can move (no sample, no
 // constant, no iteration), fill_history for every further row, else `iters` times: propose (the step or direction kernel: trial constants
 // from the accepted state), the trial constants installed, evaluate(true), accept(history row).  The program holds the accepted constants
-// afterwards; finish (may be empty) runs behind that, where the loop ran.  The inner calls leave the timing events alone: the ring sees
-// one call.
+// afterwards; finish (may be empty) runs behind that, where the loop ran; report (may be empty) runs last, whether it ran or not.  The
+// inner calls leave the timing events alone: the ring sees one call.
 struct FitLoop {
     std::function<int(bool)> evaluate;
-    std::function<int()> init, propose, finish;
+    std::function<int()> init, propose, finish, report;
     std::function<int(double *)> first_history, fill_history, accept;
     void *consts_acc = nullptr, *consts_trial = nullptr;
     const char *last_kernel = nullptr; // what the context reports behind the loop (null: what the last inner call set)
@@ -378,6 +413,7 @@ static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, d
             if (rc2 != DE_OK) return rc2;
             if (f.finish && (rc = f.finish()) != DE_OK) return rc;
         }
+        if (f.report && (rc = f.report()) != DE_OK) return rc;
     }
     if (!c->nested) HIP_TRY(c, time_end(c));
     return DE_OK;
@@ -597,59 +633,74 @@ int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, in
     DE_NOTHROW(c, fit_consts_lm_scaled_impl(c, p, X, N, ldX, pa, y, w, opts, sse, stats, ystats, ok, history, n_accept, DE_GN_WIDE_MAX_ROWS));
 }
 
-// ---- de_fit_consts_bfgs (kernels: de_bfgs.hip, arithmetic: de_bfgs.h) ----------------------------------------------------
-// The same fit with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip
-static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
-                                const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok,
-                                double *history, int32_t *n_accept) {
-    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
-    const de_bfgs_opts_t o = opts ? *opts : defaults;
+// ---- de_fit_consts_bfgs (kernels: de_bfgs.hip, arithmetic: de_bfgs.h) and de_fit_consts_lbfgs (§4.4.15; kernels:
+// de_lbfgs.hip, arithmetic: de_lbfgs.h) -------------------------------------------------------------------------------------------------------
+// The same fit with every evaluation de_eval_loss_grad_ex's (no matrix) and the kernels of de_bfgs.hip (memory = 0) or, with a ring of
+// `memory` pairs per tree instead of B, those of de_lbfgs.hip.  o: the options both share; opts_why: what is wrong with the caller's.
+// de_fit_consts_lbfgs ends with one de_eval_loss_ex at the accepted constants (FitLoop::report): loss and ok are that call's.
+static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, int memory, const de_bfgs_opts_t &o, const char *opts_why,
+                              const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y, const void *w,
+                              const de_loss_spec_t *spec_in, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
     const auto spec_check = [&]() -> int {
         char why[160];
         if (loss_spec_problem(spec_in, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_bfgs: DE_LOSS_PULLBACK is no objective");
+        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "%s: DE_LOSS_PULLBACK is no objective", what);
+        if (memory > 0 && !p->threaded) // (the loss it reports is de_eval_loss_ex's)
+            return fail(c, DE_ERR_UNSUPPORTED, "%s needs the LDS-tiled kernel (feature matrix too wide for this build)", what);
         return DE_OK;
     };
-    int rc = fit_check(c, p, "de_fit_consts_bfgs", "the caller sums them", spec_check, bfgs_opts_problem(&o), X, N, ldX, pa, {ok, y});
+    int rc = fit_check(c, p, what, "the caller sums them", spec_check, opts_why, X, N, ldX, pa, {ok, y});
     if (rc != DE_OK || p->n_trees == 0) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
-    std::vector<int64_t> boff(nt); // B: G^2 doubles of every tree that is fitted, none of the others
+    QnKernels q;
+    std::memset(&q.x, 0, sizeof q.x);
+    q.memory = memory;
+    std::vector<int64_t> boff(nt); // B: G^2 doubles (the ring: memory x G, twice) of every tree that is fitted, none of the others
     int64_t bspan = 0;
     for (size_t t = 0; t < nt; t++) {
-        const int64_t g = p->n_consts_tree[t];
         boff[t] = bspan;
-        if (g >= 1 && g <= BFGS_MAX_ROWS) bspan += g * g;
+        bspan += q.state_doubles(p->n_consts_tree[t]);
     }
-    LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's
+    LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's (the ring's)
     if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, boff.data(), &tab)) != DE_OK) return rc;
     const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
     FitInputs in;
     if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
-    // the state: accepted and trial constants, losses, gradients and flags; B, alpha, the slope and the direction, two flags per tree; the images
-    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
+    // the state: accepted and trial constants, losses, gradients and flags; B (or S, Y, rho, count, head and a scratch vector), alpha, the
+    // slope and the direction, two flags per tree; the images
+    const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept), ring = memory > 0;
     Workspace ws;
     const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
                dA = ws.place<char>(span * es), dT = ws.place<char>(span * es);
-    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt), fresh = ws.place<uint8_t>(nt), produced = ws.place<uint8_t>(nt);
+    const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt), fresh = ws.place<uint8_t>(nt, !ring), produced = ws.place<uint8_t>(nt);
     const auto B = ws.place<double>((size_t)bspan), alpha = ws.place<double>(nt), slope = ws.place<double>(nt), dir = ws.place<double>(span),
+               Yr = ws.place<double>((size_t)bspan, ring), rho = ws.place<double>(nt * (size_t)memory, ring), tmp = ws.place<double>(span, ring),
                r_hist = ws.place<double>(rows * nt, h_hist);
-    const auto r_acc = ws.place<int32_t>(nt, h_acc);
+    const auto count = ws.place<int32_t>(nt, ring), head = ws.place<int32_t>(nt, ring), r_acc = ws.place<int32_t>(nt, h_acc);
     if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
     FitOutputs out;
     out.from_state(loss, ws.ptr(lA), nt * es);
     out.from_state(ok, ws.ptr(okA), nt);
     double *hist = out.in_place(history, h_hist, ws.ptr(r_hist), rows * nt);
-    BfgsArgs a;
-    std::memset(&a, 0, sizeof a);
+    BfgsArgs &a = q.x.b;
     a.n_trees = p->n_trees;
     a.n_grad = tab.ng;
     a.coff = tab.doff;
-    a.boff = tab.joff;
     a.consts_acc = ws.ptr(cA); a.loss_acc = ws.ptr(lA); a.dloss_acc = ws.ptr(dA); a.ok_acc = ws.ptr(okA);
     a.consts_trial = ws.ptr(cT); a.loss_trial = ws.ptr(lT); a.dloss_trial = ws.ptr(dT); a.ok_trial = ws.ptr(okT);
-    a.B = ws.ptr(B); a.alpha = ws.ptr(alpha); a.slope = ws.ptr(slope); a.p = ws.ptr(dir);
-    a.fresh = ws.ptr(fresh); a.produced = ws.ptr(produced);
+    a.alpha = ws.ptr(alpha); a.slope = ws.ptr(slope); a.p = ws.ptr(dir);
+    a.produced = ws.ptr(produced);
+    if (ring) {
+        q.x.roff = tab.joff;
+        q.x.S = ws.ptr(B); q.x.Y = ws.ptr(Yr); q.x.rho = ws.ptr(rho); q.x.tmp = ws.ptr(tmp);
+        q.x.count = ws.ptr(count); q.x.head = ws.ptr(head);
+        q.x.memory = memory;
+    } else {
+        a.boff = tab.joff;
+        a.B = ws.ptr(B);
+        a.fresh = ws.ptr(fresh);
+    }
     a.step0 = o.step0; a.shrink = o.shrink; a.c1 = o.c1; a.curv = o.curv;
     a.n_accept = out.in_place(n_accept, h_acc, ws.ptr(r_acc), nt);
     const de_loss_spec_t spec = *spec_in;
@@ -660,17 +711,19 @@ static int fit_consts_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int
         return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, ws.ptr(trial ? lT : lA), ws.ptr(trial ? dT : dA),
                               nullptr, ws.ptr(trial ? okT : okA), nullptr);
     };
-    f.init = [&]() -> int { HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream)); return DE_OK; };
+    f.init = [&]() -> int { HIP_TRY(c, q.init(p->dtype, c->stream)); return DE_OK; };
     f.first_history = f.fill_history = [&](double *row) -> int {
         HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, row, c->stream));
         return DE_OK;
     };
-    f.propose = [&]() -> int { HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream)); return DE_OK; };
+    f.propose = [&]() -> int { HIP_TRY(c, q.direction(p->dtype, c->stream)); return DE_OK; };
     f.accept = [&](double *row) -> int {
         a.history_row = row;
-        HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
+        HIP_TRY(c, q.accept(p->dtype, c->stream));
         return DE_OK;
     };
+    if (ring) // de_fit_consts_lbfgs reports the fused loss alone at the accepted constants: what de_eval_loss_ex gives there, bit for bit
+        f.report = [&]() -> int { return de_eval_loss_ex(c, p, in.Xd, N, ldX, in.pa, in.yd, in.wd, &spec, ws.ptr(lA), ws.ptr(okA)); };
     if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
     return out.finish(c);
 }
@@ -678,7 +731,22 @@ int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, i
                        const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
                        int32_t *n_accept) {
     DE_REFUSE_F16("de_fit_consts_bfgs");
-    DE_NOTHROW(c, fit_consts_bfgs_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_accept));
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    DE_NOTHROW(c, fit_consts_qn_impl(c, p, "de_fit_consts_bfgs", 0, o, bfgs_opts_problem(&o), X, N, ldX, pa, y, w, spec, loss, ok, history, n_accept));
+}
+int de_fit_consts_lbfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                        const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
+                        int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lbfgs");
+    const de_lbfgs_opts_t defaults{20, 0, 8, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_lbfgs_opts_t lo = opts ? *opts : defaults;
+    de_bfgs_opts_t o;
+    const char *why = lbfgs_opts_problem(&lo, &o);
+    char named[200]; // (the text names the call)
+    if (why) std::snprintf(named, sizeof named, "de_fit_consts_lbfgs: %s", why);
+    DE_NOTHROW(c, fit_consts_qn_impl(c, p, "de_fit_consts_lbfgs", lo.memory, o, why ? named : nullptr, X, N, ldX, pa, y, w, spec, loss, ok, history,
+                                     n_accept));
 }
 
 // ---- de_fit_consts_nm (kernels: de_nm.hip, arithmetic: de_nm.h) ----------------------------------------------------------

@@ -360,6 +360,8 @@ int consts_materialise(de_program *p);
 int set_consts_device_impl(de_program *p, const void *d_consts);
 // what de_fit_consts_bfgs and de_fit_tree_params_bfgs refuse about their options (de_api_fit.cpp): null = good, else the reason
 const char *bfgs_opts_problem(const de_bfgs_opts_t *o);
+// ... and de_fit_consts_lbfgs / de_fit_tree_params_lbfgs about theirs; *shared receives the fields de_bfgs_opts_t has too
+const char *lbfgs_opts_problem(const de_lbfgs_opts_t *o, de_bfgs_opts_t *shared);
 // releases a program's GnWideCache (de_api_grad.cpp); the caller has synchronised the stream
 void gn_wide_release(de_program *p);
 }

@@ -7,12 +7,14 @@
 // ... and de_fit_tree_params_bfgs with its host-only hooks de_tree_params_pack_host / de_tree_params_unpack_host: BFGS
 // over each tree's vcat(constants, parameters[:]) with that class loop as the evaluator (kernels: de_bfgs.hip unchanged on packed
 // vectors, the pack / unpack kernels of de_tree_params.hip; index map: de_tree_params_fit.h).
+// ... and de_fit_tree_params_lbfgs: the same loop with the kernels of de_lbfgs.hip, for trees of more than 32 unknowns.
 #include "de_api_internal.h"
 #include "de_tree_params_dev.h"
 #include "de_tree_params.h"
 #include "de_tree_params_fit.h"
 #include "de_bfgs.h"
 #include "de_bfgs_dev.h"
+#include "de_lbfgs_dev.h"
 #include "de_lm.h"
 
 template <typename T>
@@ -427,23 +429,23 @@ int de_eval_loss_grad_tree_params(de_ctx_t *c, de_program_t *p, const void *X, i
     DE_NOTHROW(c, tree_params_impl(c, p, "de_eval_loss_grad_tree_params", TP_LOSS_GRAD, X, N, ldX, tp, o, ok));
 }
 
-// ---- de_fit_tree_params_bfgs: fit_consts_bfgs_impl's loop over each tree's packed vcat(constants, parameters[:]) ----
+// ---- de_fit_tree_params_bfgs and de_fit_tree_params_lbfgs (§4.4.15): fit_consts_qn_impl's loop over each tree's packed
+// vcat(constants, parameters[:]) ----
 // Every evaluation is the class loop above followed by the finish kernel — de_eval_loss_grad_tree_params without its staging, its
-// synchronisation and its copies — and the kernels of de_bfgs.hip see packed vectors only: pack / unpack (de_tree_params.hip) move the
-// values between them and (the base vector's real slots, the pool's parameter block).
-static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
-                                     const void *y, const void *w, const de_loss_spec_t *spec_in, const de_bfgs_opts_t *opts, void *params_out,
-                                     void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
-    const char *what = "de_fit_tree_params_bfgs";
+// synchronisation and its copies — and the kernels of de_bfgs.hip (memory = 0) or de_lbfgs.hip (a ring of `memory` pairs per tree) see
+// packed vectors only: pack / unpack (de_tree_params.hip) move the values between them and (the base vector's real slots, the pool's
+// parameter block).  bo: the options both kernel sets share; opts_why: what is wrong with the caller's (null: nothing).
+static int fit_tree_params_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, int memory, const de_bfgs_opts_t &bo, const char *opts_why,
+                                   const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp, const void *y, const void *w,
+                                   const de_loss_spec_t *spec_in, void *params_out, void *loss, uint8_t *ok, double *history,
+                                   int32_t *n_accept) {
     TpOut o;
     o.y = y; o.w = w; o.spec = spec_in; o.fit = true;
     TpPlan pl;
     int rc = tp_check(c, p, what, TP_LOSS_GRAD, X, N, ldX, tp, o, ok, &pl);
     if (rc != DE_OK) return rc;
     if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "%s: DE_LOSS_PULLBACK is no objective", what);
-    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
-    const de_bfgs_opts_t bo = opts ? *opts : defaults;
-    if (const char *why = bfgs_opts_problem(&bo)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
+    if (opts_why) return fail(c, DE_ERR_INVALID_ARG, "%s", opts_why);
     const size_t nt = pl.nt, nc = pl.nc, es = pl.es;
     const int64_t C = pl.C, ld = tp->ld_params;
     const int32_t P = pl.P;
@@ -453,6 +455,10 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
     if (nt == 0) return DE_OK;
 
     // ---- the geometry of the packed vectors: [widths | packed offsets | B offsets | unknown -> slot or cell] ----
+    QnKernels q;
+    std::memset(&q.x, 0, sizeof q.x);
+    q.memory = memory;
+    const bool ring = memory > 0;
     std::vector<int32_t> ng(nt);
     std::vector<int64_t> poff(nt), boff(nt);
     int64_t npk = 0, bspan = 0;
@@ -465,7 +471,7 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
         poff[t] = npk;
         boff[t] = bspan;
         npk += G;
-        if (G >= 1 && G <= BFGS_MAX_ROWS) bspan += G * G;
+        bspan += q.state_doubles(G); // B, or each of S and Y: of the trees that are fitted
     }
     size_t tat = 0;
     const size_t t_ng = tp_place(&tat, nt * 4), t_poff = tp_place(&tat, nt * 8), t_boff = tp_place(&tat, nt * 8), t_map = tp_place(&tat, (size_t)npk * 8);
@@ -490,6 +496,9 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
                  o_B = tp_place(&at, (size_t)bspan * 8), o_al = tp_place(&at, nt * 8), o_sl = tp_place(&at, nt * 8), o_p = tp_place(&at, pk * 8),
                  o_fr = tp_place(&at, nt), o_pr = tp_place(&at, nt), o_hist = h_hist ? tp_place(&at, rows * nt * 8) : 0,
                  o_acc = h_acc ? tp_place(&at, nt * 4) : 0;
+    // (the ring: S in B's place, and Y, rho, a scratch vector, count and head)
+    const size_t o_Y = tp_place(&at, ring ? (size_t)bspan * 8 : 0), o_rho = tp_place(&at, ring ? nt * (size_t)memory * 8 : 0),
+                 o_tmp = tp_place(&at, ring ? pk * 8 : 0), o_cnt = tp_place(&at, ring ? nt * 4 : 0), o_head = tp_place(&at, ring ? nt * 4 : 0);
     TpDev d;
     rc = tp_setup(c, p, TP_LOSS_GRAD, X, N, ldX, tp, o, ok, pl, &ftab, at, &d);
     if (rc != DE_OK) return rc;
@@ -509,19 +518,28 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
     out.from_state(ok, fit + o_oka, nt);
     double *hist = out.in_place(history, h_hist, reinterpret_cast<double *>(fit + o_hist), rows * nt);
     int32_t *acc = out.in_place(n_accept, h_acc, reinterpret_cast<int32_t *>(fit + o_acc), nt);
-    BfgsArgs a;
-    std::memset(&a, 0, sizeof a);
+    BfgsArgs &a = q.x.b;
     a.n_trees = p->n_trees;
     a.n_grad = reinterpret_cast<const int32_t *>(tab + t_ng);
     a.coff = reinterpret_cast<const int64_t *>(tab + t_poff);
-    a.boff = reinterpret_cast<const int64_t *>(tab + t_boff);
     a.consts_acc = fit + o_ca; a.loss_acc = fit + o_la; a.dloss_acc = fit + o_da; a.ok_acc = reinterpret_cast<uint8_t *>(fit + o_oka);
     void *lT = fit + o_lt, *dT = fit + o_dt;
     uint8_t *okT = reinterpret_cast<uint8_t *>(fit + o_okt);
     a.consts_trial = fit + o_ct; a.loss_trial = lT; a.dloss_trial = dT; a.ok_trial = okT;
-    a.B = reinterpret_cast<double *>(fit + o_B); a.alpha = reinterpret_cast<double *>(fit + o_al);
+    a.alpha = reinterpret_cast<double *>(fit + o_al);
     a.slope = reinterpret_cast<double *>(fit + o_sl); a.p = reinterpret_cast<double *>(fit + o_p);
-    a.fresh = reinterpret_cast<uint8_t *>(fit + o_fr); a.produced = reinterpret_cast<uint8_t *>(fit + o_pr);
+    a.produced = reinterpret_cast<uint8_t *>(fit + o_pr);
+    if (ring) {
+        q.x.roff = reinterpret_cast<const int64_t *>(tab + t_boff);
+        q.x.S = reinterpret_cast<double *>(fit + o_B); q.x.Y = reinterpret_cast<double *>(fit + o_Y);
+        q.x.rho = reinterpret_cast<double *>(fit + o_rho); q.x.tmp = reinterpret_cast<double *>(fit + o_tmp);
+        q.x.count = reinterpret_cast<int32_t *>(fit + o_cnt); q.x.head = reinterpret_cast<int32_t *>(fit + o_head);
+        q.x.memory = memory;
+    } else {
+        a.boff = reinterpret_cast<const int64_t *>(tab + t_boff);
+        a.B = reinterpret_cast<double *>(fit + o_B);
+        a.fresh = reinterpret_cast<uint8_t *>(fit + o_fr);
+    }
     a.step0 = bo.step0; a.shrink = bo.shrink; a.c1 = bo.c1; a.curv = bo.curv;
     a.n_accept = acc;
     TreeParamsFitArgs fx; // the unknowns' values: (base vector, parameter block)
@@ -562,7 +580,7 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
             if (r != DE_OK) return r;
             fx.packed = a.consts_acc;
             HIP_TRY(c, launch_tree_params_pack(p->dtype, fx, c->stream));
-            HIP_TRY(c, launch_bfgs_init(p->dtype, a, c->stream));
+            HIP_TRY(c, q.init(p->dtype, c->stream));
             HIP_TRY(c, launch_lm_history(p->dtype, a.loss_acc, p->n_trees, hist, c->stream));
             const bool loop = N > 0 && bo.iters > 0 && npk > 0;
             if (!loop) // (no sample or no unknown: nothing can be accepted, every row of the history is the first)
@@ -570,13 +588,13 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
             if (!loop) return DE_OK;
             begun = true;
             for (int32_t it = 0; it < bo.iters; it++) {
-                HIP_TRY(c, launch_bfgs_direction(p->dtype, a, c->stream));
+                HIP_TRY(c, q.direction(p->dtype, c->stream));
                 fx.packed = a.consts_trial;
                 HIP_TRY(c, launch_tree_params_unpack(p->dtype, fx, c->stream));
                 r = evaluate(lT, dT, okT, true);
                 if (r != DE_OK) return r;
                 a.history_row = hist ? hist + ((size_t)it + 1) * nt : nullptr;
-                HIP_TRY(c, launch_bfgs_accept(p->dtype, a, c->stream));
+                HIP_TRY(c, q.accept(p->dtype, c->stream));
             }
             return DE_OK;
         };
@@ -603,7 +621,22 @@ static int fit_tree_params_bfgs_impl(de_ctx_t *c, de_program_t *p, const void *X
 int de_fit_tree_params_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp, const void *y,
                             const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *params_out, void *loss, uint8_t *ok,
                             double *history, int32_t *n_accept) {
-    DE_NOTHROW(c, fit_tree_params_bfgs_impl(c, p, X, N, ldX, tp, y, w, spec, opts, params_out, loss, ok, history, n_accept));
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    DE_NOTHROW(c, fit_tree_params_qn_impl(c, p, "de_fit_tree_params_bfgs", 0, o, bfgs_opts_problem(&o), X, N, ldX, tp, y, w, spec, params_out, loss,
+                                          ok, history, n_accept));
+}
+int de_fit_tree_params_lbfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp, const void *y,
+                             const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, void *params_out, void *loss, uint8_t *ok,
+                             double *history, int32_t *n_accept) {
+    const de_lbfgs_opts_t defaults{20, 0, 8, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_lbfgs_opts_t lo = opts ? *opts : defaults;
+    de_bfgs_opts_t o;
+    const char *why = lbfgs_opts_problem(&lo, &o);
+    char named[200]; // (the text names the call)
+    if (why) std::snprintf(named, sizeof named, "de_fit_tree_params_lbfgs: %s", why);
+    DE_NOTHROW(c, fit_tree_params_qn_impl(c, p, "de_fit_tree_params_lbfgs", lo.memory, o, why ? named : nullptr, X, N, ldX, tp, y, w, spec,
+                                          params_out, loss, ok, history, n_accept));
 }
 
 } // extern "C"

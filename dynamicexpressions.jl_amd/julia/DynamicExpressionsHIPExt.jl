@@ -1136,6 +1136,55 @@ function fit_population_constants_bfgs!(
     return constants, lossv, ok .!= 0x00, history, n_accept
 end
 
+struct LbfgsOpts            # de_lbfgs_opts_t
+    iters::Int32
+    reserved::Int32
+    memory::Int32
+    reserved2::Int32
+    step0::Float64
+    shrink::Float64
+    c1::Float64
+    curv::Float64
+end
+
+"""
+    fit_population_constants_lbfgs!(pop, X, y; weights=nothing, iters=20, memory=8, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0)
+        -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
+
+L-BFGS on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lbfgs`, DESIGN.md §4.4.15) — the
+reference's `optimize(f, g!, tree, LBFGS())` with a backtracking line search — for the trees `fit_population_constants_bfgs!` leaves
+alone: every tree of up to `de_lbfgs_max_rows()` = 4096 constants is fitted, its curvature a ring of `memory` (1 .. 16) pairs instead of
+`B`.  Arguments, objectives and results as `fit_population_constants_bfgs!`; the returned losses and flags are those of one fused loss
+evaluation at the accepted constants (`eval_population_loss` there reproduces them bit for bit), `history` keeps the accept rule's.
+"""
+function fit_population_constants_lbfgs!(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+    iters::Integer=20, memory::Integer=8, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8, loss::Symbol=:L2,
+    loss_param::Real=0.0,
+) where {T}
+    loss === :pullback && throw(ArgumentError("fit_population_constants_lbfgs!: :pullback is the cotangent of a pullback, not an objective"))
+    F, N = size(X)
+    @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || length(weights) == N
+    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lbfgs!: shared GraphNode constants need the host loop"))
+    opts = Ref(LbfgsOpts(Int32(iters), Int32(0), Int32(memory), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
+    spec = loss_spec(loss, loss_param)
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_accept = zeros(Int32, pop.n_trees)
+    with_pop(pop) do hc, hp
+        wp = weights === nothing ? C_NULL : pointer(weights)
+        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+            (:de_fit_consts_lbfgs, LIBDE), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{LbfgsOpts},
+             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+    end
+    constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
+    return constants, lossv, ok .!= 0x00, history, n_accept
+end
+
 struct NmOpts               # de_nm_opts_t
     iters::Int32
     reserved::Int32
@@ -1482,6 +1531,51 @@ function fit_parametric_population_bfgs!(
             tp = Ref(TreeParams(pointer(fitted), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
             ccall((:de_fit_tree_params_bfgs, LIBDE), Cint,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, tp, y, weights === nothing ? C_NULL : pointer(weights), spec, opts, fitted, lossv, ok, history, n_accept)
+        end)
+    end
+    slots = get_population_constants!(Vector{T}(undef, length(sp)), pop)
+    constants = [T[slots[s] for s in (offs[t] + 1):offs[t + 1] if sp[s] < 0] for t in 1:pop.n_trees]
+    pp.parameters = fitted
+    return constants, fitted, lossv, ok .!= 0x00, history, n_accept
+end
+
+"""
+    fit_parametric_population_lbfgs!(pp, X, y, classes; parameters=pp.parameters, weights=nothing, iters=20, memory=8, step0=1.0,
+                                     shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0, grouped=false)
+        -> (constants::Vector{Vector{T}}, parameters::Array{T,3}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
+
+L-BFGS over every expression's `vcat(constants, parameters[:])`, the whole loop in one library call (`de_fit_tree_params_lbfgs`, DESIGN.md
+§4.4.15): `fit_parametric_population_bfgs!` for expressions of up to `de_lbfgs_max_rows()` = 4096 unknowns — `n_real + n_params *
+n_classes` passes 32 with a handful of classes — with a ring of `memory` (1 .. 16) pairs per expression.  Arguments and results as
+`fit_parametric_population_bfgs!`.
+"""
+function fit_parametric_population_lbfgs!(
+    pp::HIPParametricPopulation{T}, X::Matrix{T}, y::Vector{T}, classes::Vector{Int64}; parameters::Array{T,3}=pp.parameters,
+    weights::Union{Nothing,Vector{T}}=nothing, iters::Integer=20, memory::Integer=8, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4,
+    curv::Real=1e-8, loss::Symbol=:L2, loss_param::Real=0.0, grouped::Bool=false,
+) where {T}
+    loss === :pullback && throw(ArgumentError("fit_parametric_population_lbfgs!: :pullback is the cotangent of a pullback, not an objective"))
+    pop = pp.pop
+    F, N = size(X)
+    P, C, nt = size(parameters)
+    @assert F >= pop.n_features && length(y) == N && length(classes) == N && P == pp.n_params && nt == pop.n_trees
+    @assert weights === nothing || length(weights) == N
+    X, starts, _, (y, weights) = group_by_class(X, classes, C, grouped, y, weights)
+    opts = Ref(LbfgsOpts(Int32(iters), Int32(0), Int32(memory), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
+    spec = loss_spec(loss, loss_param)
+    fitted = copy(parameters)               # params_out: the start is read before anything is written, so it may be the same block
+    lossv = Vector{T}(undef, pop.n_trees)
+    ok = Vector{UInt8}(undef, pop.n_trees)
+    history = Matrix{Float64}(undef, pop.n_trees, Int(iters) + 1)
+    n_accept = zeros(Int32, pop.n_trees)
+    sp, offs = pp.slot_param, pp.slot_off
+    with_pop(pop) do hc, hp
+        check(pop.ctx, GC.@preserve X y weights fitted starts sp lossv ok history n_accept begin
+            tp = Ref(TreeParams(pointer(fitted), max(P, 1), C, P, 0, pointer(starts), pointer(sp)))
+            ccall((:de_fit_tree_params_lbfgs, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{TreeParams}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{LbfgsOpts},
                  Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
                 hc, hp, X, N, F, tp, y, weights === nothing ? C_NULL : pointer(weights), spec, opts, fitted, lossv, ok, history, n_accept)
         end)

@@ -104,7 +104,10 @@ extern "C" {
  *      the constants of a population on the device, from the fused loss alone — every kind de_eval_loss_ex takes,
  *      programs made by de_program_create_cse included, trees of up to 32 constants; DE_F32 / DE_F64.
  *      (r) de_fit_consts_bfgs_scaled, de_fit_consts_nm_scaled and the host-only hook de_scaled_objective_host: the two fits above under
- *      linear scaling (the objective scaled_sse, in double); every entry point above keeps its bits. */
+ *      linear scaling (the objective scaled_sse, in double); every entry point above keeps its bits.
+ *      (s) de_lbfgs_max_rows, de_lbfgs_max_memory, de_fit_consts_lbfgs, de_fit_tree_params_lbfgs (with de_lbfgs_opts_t) and the host-only
+ *      hooks de_lbfgs_direction_host / de_lbfgs_update_host: L-BFGS for trees of up to 4096 unknowns, the two BFGS fits' contracts with
+ *      a ring of (s, yv) pairs per tree instead of B; every entry point above keeps its bits. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -1077,7 +1080,8 @@ int de_tree_params_accumulate_host(int dtype, int32_t n_slots, const int32_t *sl
  * Refusals, before any output, constant or parameter is touched: everything de_eval_loss_grad_tree_params refuses; what
  * de_fit_consts_bfgs refuses about spec and opts (DE_LOSS_PULLBACK, iters < 0, reserved != 0, step0 / c1 / curv not finite and
  * positive, shrink outside (0, 1)); null y or ok on a non-empty population; null tp->params or params_out where a parameter entry exists.
- * Not served: more than 32 unknowns per tree, LM / Gauss-Newton over parameters, the scaled objective, per-sample classes.
+ * Not served: more than 32 unknowns per tree (such a tree keeps every bit here; de_fit_tree_params_lbfgs below fits up to
+ * de_lbfgs_max_rows() unknowns), LM / Gauss-Newton over parameters, the scaled objective, per-sample classes.
  *
  * de_tree_params_pack_host / de_tree_params_unpack_host: the index map of ONE tree on the host (no HIP call; csrc/de_tree_params_fit.h,
  * the code the kernels run).  slot_values: n_slots entries (parameter slots are skipped on pack and left untouched on unpack);
@@ -1091,6 +1095,59 @@ int de_tree_params_pack_host(int dtype, int32_t n_slots, const int32_t *slot_par
                              int64_t ld_params, const void *slot_values, const void *params_tree, void *x);
 int de_tree_params_unpack_host(int dtype, int32_t n_slots, const int32_t *slot_param, int32_t n_params, int64_t n_classes,
                                int64_t ld_params, const void *x, void *slot_values, void *params_tree);
+
+/* ---- L-BFGS: the two BFGS fits for trees of more than 32 unknowns, on the device -------------------------------
+ * B of de_fit_consts_bfgs is G^2 doubles with one lane per row; a member of a parametric population has G = n_real + n_params*n_classes
+ * unknowns, which passes 32 with a handful of classes.  Here the curvature of a tree is a ring of up to `memory` pairs (s_j, y_j) with
+ * rho_j = 1 / (s_j . y_j) — O(memory * G) — for 1 <= G <= de_lbfgs_max_rows() = 4096, memory in 1 .. de_lbfgs_max_memory() = 16.
+ * Per tree, in double, no atomics.  EVERY dot product is 64 partial sums — partial l over k = l, l + 64, ... ascending from 0.0, one
+ * product at a time (-ffp-contract=off) — added in the order l = 0 .. 63 from 0.0.  count of the slots are stored, head is the next
+ * slot to write; the i-th newest pair is slot (head - 1 - i) mod memory.
+ *   direction  q = g; for the stored pairs newest to oldest a_i = rho_i (s_i . q), q -= a_i y_i; r = (s . y / y . y of the newest) q;
+ *              oldest to newest b = rho_i (y_i . r), r += (a_i - b) s_i; p = -r, slope = g . p.  count == 0: p = -g.
+ *              !(slope < 0): count = 0, p = -g, slope = -g . g, alpha = a0(g).  produced = every entry of g and of the stored pairs
+ *              is finite && slope < 0; else p = 0.
+ *   trial, accept rule, shrink: those of de_fit_consts_bfgs (trial = T(double(c) + alpha p); Armijo; alpha *= shrink on a reject).
+ *   update     on an accepted step s = double(c_trial) - double(c), yv = g_trial - g; only where s . yv > curv |s| |yv| the pair goes to
+ *              slot head, rho = 1 / s . yv, head = (head + 1) mod memory, count = min(count + 1, memory); a refused pair leaves every
+ *              byte of the state.  Then alpha = count == 0 ? a0(g_new) : 1.
+ *
+ * de_lbfgs_direction_host / de_lbfgs_update_host: ONE tree on the host (no HIP call; csrc/de_lbfgs.h, the templates the kernels
+ * instantiate — the same bits).  S, Y: memory x G doubles, slot j at j*G; rho: memory doubles.  direction returns `produced`, writes p
+ * and *slope, and *count / *alpha where the state was reset; update returns `updated`.  G outside 1 .. de_lbfgs_max_rows(), memory
+ * outside 1 .. de_lbfgs_max_memory(), *count outside 0 .. memory, *head outside 0 .. memory - 1 or a null pointer: 0, nothing written.
+ *
+ * de_fit_consts_lbfgs: de_fit_consts_bfgs' contract — arguments, outputs, history, n_accept, where the accepted constants live
+ * afterwards, host or device pointers, stream order — with these kernels: a tree is fitted where it has 1 .. de_lbfgs_max_rows()
+ * constants and its first evaluation is complete; any other keeps every bit of its constants.  One difference: the call ends with one
+ * de_eval_loss_ex at the accepted constants, and loss[t] / ok[t] are that evaluation's — de_eval_loss_ex with the same spec reproduces
+ * loss[t] bit for bit.  The history rows stay the losses of the accept rule, de_eval_loss_grad_ex's: that kernel sums a tree's samples
+ * in another order, so the last row and loss[t] may differ in the last bits.  (So it also refuses what de_eval_loss_ex refuses: a
+ * feature matrix too wide for the LDS-tiled kernel.)
+ * de_fit_tree_params_lbfgs: de_fit_tree_params_bfgs' contract likewise (params_out, its padding, the program's constants afterwards).
+ * Refusals, before any output, constant or parameter is touched: everything the matching BFGS call refuses (DE_F16 / complex programs,
+ * programs made by de_program_create_cse, DE_LOSS_PULLBACK, its option checks, null buffers); memory outside 1 ..
+ * de_lbfgs_max_memory(); reserved or reserved2 != 0.  The texts name the call.
+ * Not served: the scaled objective, a Wolfe line search, per-sample classes. */
+typedef struct de_lbfgs_opts {
+    int32_t iters;    /* trial evaluations per tree (>= 0) */
+    int32_t reserved; /* 0 */
+    int32_t memory;   /* pairs kept per tree, 1 .. de_lbfgs_max_memory() */
+    int32_t reserved2; /* 0 */
+    double step0, shrink, c1, curv; /* as de_bfgs_opts_t */
+} de_lbfgs_opts_t; /* NULL: {20, 0, 8, 0, 1.0, 0.5, 1e-4, 1e-8} */
+int de_lbfgs_max_rows(void);
+int de_lbfgs_max_memory(void);
+int de_lbfgs_direction_host(int G, int memory, const double *S, const double *Y, const double *rho, int32_t *count, int32_t *head,
+                            double *alpha, const double *g, double step0, double *p, double *slope);
+int de_lbfgs_update_host(int G, int memory, double *S, double *Y, double *rho, int32_t *count, int32_t *head, const double *s,
+                         const double *yv, double curv);
+int de_fit_consts_lbfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                        const void *y, const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, void *loss, uint8_t *ok,
+                        double *history, int32_t *n_accept);
+int de_fit_tree_params_lbfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
+                             const void *y, const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, void *params_out,
+                             void *loss, uint8_t *ok, double *history, int32_t *n_accept);
 
 /* The `dX` of the ChainRules pullback of eval_tree_array (EvalPullback, src/ChainRules.jl:56-77):
  *   dX_t[f, j] = d tree_t(x_j) / d x_f * dY[j]      (`dX = dX_dY .* reshape(dY, 1, length(dY))`, :74)
