@@ -67,6 +67,8 @@ EXPORTS = [
     "de_scaled_objective_host", "de_fit_consts_bfgs_scaled", "de_fit_consts_nm_scaled",
     "de_lbfgs_max_rows", "de_lbfgs_max_memory", "de_lbfgs_direction_host", "de_lbfgs_update_host", "de_fit_consts_lbfgs",
     "de_fit_tree_params_lbfgs",
+    "de_ties_pack_host", "de_ties_unpack_host", "de_ties_fold_host", "de_ties_fold_matrix_host",
+    "de_fit_consts_bfgs_tied", "de_fit_consts_lbfgs_tied", "de_fit_consts_nm_tied", "de_fit_consts_lm_tied",
 ]
 
 
@@ -254,6 +256,59 @@ def gn_combine(H, o):
         return H
     half = _sum_occurrence_rows(H, o)
     return _sum_occurrence_rows(half.T if not _is_torch(half) else half.t(), o).T
+
+
+def _ties_hook(name: str, tie, src, n_out_of, dtype):
+    """One ``de_ties_*_host`` call: ``tie`` is one tree's map (``Population._occ[t]``), ``src`` its input in ``dtype``
+    (float32 or float64).  Returns the output array; ``ValueError`` where the library answers -1 (a map that is not in first-occurrence
+    order; the output is then untouched)."""
+    dt = np.dtype(dtype)
+    tie = np.ascontiguousarray(tie, dtype=np.int32).reshape(-1)
+    src = np.ascontiguousarray(src, dtype=dt)
+    ids = np.unique(tie)
+    nu = int(ids.size)
+    out = np.empty(n_out_of(tie.size, nu), dtype=dt)
+    pad = lambda a: a if a.size else np.zeros(1, dtype=a.dtype)  # (an empty array may have no address to pass)
+    tie_p, src_p, out_p = pad(tie), pad(src.reshape(-1)), pad(out)
+    rc = getattr(library(), name)(_dtype_code(dt), int(tie.size), tie_p.ctypes.data, src_p.ctypes.data, out_p.ctypes.data)
+    if rc != nu:
+        raise ValueError(f"{name}: the tie map must list its ids 0, 1, ... in first-occurrence order (the library answered {rc})")
+    return out_p[:out.size] if out.size else out
+
+
+def ties_pack_host(tie, slots, dtype=np.float64):
+    """``de_ties_pack_host``: one value per occurrence slot -> one per unique constant, read from its first slot (the bits)."""
+    if np.size(slots) != np.size(tie):
+        raise ValueError("ties_pack_host: one value per slot")
+    return _ties_hook("de_ties_pack_host", tie, slots, lambda ns, nu: nu, dtype)
+
+
+def ties_unpack_host(tie, unique, dtype=np.float64):
+    """``de_ties_unpack_host``: one value per unique constant -> one per occurrence slot, ``unique[tie[s]]`` (the bits)."""
+    tie = np.asarray(tie).reshape(-1)
+    if np.size(unique) != (int(tie.max()) + 1 if tie.size else 0):
+        raise ValueError("ties_unpack_host: one value per unique constant")
+    return _ties_hook("de_ties_unpack_host", tie, unique, lambda ns, nu: ns, dtype)
+
+
+def ties_fold_host(tie, g, dtype=np.float64):
+    """``de_ties_fold_host``: the gradient rows of the occurrence slots summed per unique constant, ascending from +0 — the bits of
+    ``_sum_occurrence_rows``."""
+    if np.size(g) != np.size(tie):
+        raise ValueError("ties_fold_host: one row per slot")
+    return _ties_hook("de_ties_fold_host", tie, g, lambda ns, nu: nu, dtype)
+
+
+def ties_fold_matrix_host(tie, H, dtype=np.float64):
+    """``de_ties_fold_matrix_host``: ``S H S^T`` of an ``[n_slots, n_slots]`` matrix, rows first then columns — the bits of ``gn_combine``.
+    Returns ``[U, U]``."""
+    ns = int(np.size(tie))
+    H = np.asarray(H, dtype=dtype)
+    if H.shape != (ns, ns):
+        raise ValueError("ties_fold_matrix_host: H must be [n_slots, n_slots]")
+    out = _ties_hook("de_ties_fold_matrix_host", tie, np.asfortranarray(H).reshape(-1, order="F"), lambda ns_, nu: nu * nu, dtype)
+    nu = int(round(math.sqrt(out.size)))
+    return out.reshape((nu, nu), order="F")
 
 
 class GaussNewton:
@@ -982,6 +1037,17 @@ def library() -> C.CDLL:
                                             vp, vp, vp, vp]
         lib.de_fit_tree_params_lbfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec),
                                                  C.POINTER(LbfgsOpts), vp, vp, vp, vp, vp]
+    if hasattr(lib, "de_fit_consts_bfgs_tied"):  # (absent from a library built before the tied device fits: DE_HIP_LIB in an A/B run)
+        for hook in (lib.de_ties_pack_host, lib.de_ties_unpack_host, lib.de_ties_fold_host, lib.de_ties_fold_matrix_host):
+            hook.argtypes = [C.c_int, i32, vp, vp, vp]
+        lib.de_fit_consts_bfgs_tied.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
+                                                vp, vp, vp, vp, vp]
+        lib.de_fit_consts_lbfgs_tied.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(LbfgsOpts),
+                                                 vp, vp, vp, vp, vp]
+        lib.de_fit_consts_nm_tied.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.POINTER(NmOpts),
+                                              vp, vp, vp, vp, vp]
+        lib.de_fit_consts_lm_tied.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, C.POINTER(LossSpec), C.c_double,
+                                              C.POINTER(LmOpts), vp, vp, vp, vp, vp]
     if hasattr(lib, "de_fit_tree_params_bfgs"):  # (absent from a library built before the device fit over parameters: DE_HIP_LIB in an A/B run)
         lib.de_fit_tree_params_bfgs.argtypes = [vp, vp, vp, i64, i64, C.POINTER(TreeParams), vp, vp, C.POINTER(LossSpec), C.POINTER(BfgsOpts),
                                                 vp, vp, vp, vp, vp]
@@ -1524,6 +1590,19 @@ class Population:
     def stream_hash(self) -> int:
         """Test hook (``de_program_stream_hash``): one number over every host-side stream ``de_program_create`` built."""
         return int(library().de_program_stream_hash(self._h))
+
+    def _tie_map(self):
+        """The ``tie`` argument of the tied device fits (``de_fit_consts_*_tied``): ``_occ`` of every tree behind one
+        another as int32, the identity for a tree that shares nothing — one id per constant slot; ``None`` (the library's identity) when no
+        tree shares a constant.  Cached; ``update`` drops it."""
+        if self._occ is None:
+            return None
+        cache = self.__dict__.setdefault("_occ_cache", {})
+        if "tie" not in cache:
+            parts = [np.arange(int(ns), dtype=np.int32) if o is None else np.asarray(o, dtype=np.int32)
+                     for o, ns in zip(self._occ, self._slots_per_tree)]
+            cache["tie"] = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32))
+        return cache["tie"]
 
     def _combine_rows(self, t: int, g, mode: int):
         """Gradient rows (or entries) of tree t in the library's per-occurrence layout -> the reference's layout for a
@@ -2093,14 +2172,20 @@ class Population:
 
     def fit_constants_lm_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
                                 down: float = 0.1, history: Optional[list] = None, params=None, classes=None, class_base: int = 1,
-                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4, wide: bool = False, scaled: bool = False):
+                                loss: str = "L2", loss_param: float = 0.0, e_floor: float = 1e-4, wide: bool = False, scaled: bool = False,
+                                tied: bool = False):
         """``fit_constants_lm`` as ONE library call (``de_fit_consts_lm_ex``): the steps are solved, the trial constants
         set, and the accept rule applied on the device; no constant, gradient or matrix reaches the host.  ``consts0``: a numpy array or a
         torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.  Returns (consts, loss[n_trees] in
         the population's dtype, ok) at the accepted constants, which the population holds afterwards; with torch inputs all three are
         device tensors and nothing synchronises beyond what ``eval_gauss_newton`` does.  ``history`` (a list) receives the ``iters + 1``
         rows of accepted losses (float64); ``self.lm_accepts`` holds the number of accepted steps per tree.  The step is a Cholesky solve
-        (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError``: ``fit_constants_lm`` serves it.
+        (``GaussNewton.lm_step_device``).  A population with shared GraphNode constants raises ``ValueError`` unless ``tied=True``
+        (``de_fit_consts_lm_tied``): a shared constant is then ONE unknown — the occurrence rows and the matrix are folded
+        on the device (``ties_fold_host`` / ``ties_fold_matrix_host``: ``S H S^T``), ``consts0`` and the result stay in ``set_constants``'
+        layout, and a tree is fitted where its occurrence block exists (at most ``GN_MAX_ROWS`` occurrence slots).  ``tied=True`` with
+        ``scaled=True`` or ``wide=True`` is a ``ValueError`` before the constants are touched; on a population without shared constants it
+        is the default call bit for bit.
         ``wide=True`` (``de_fit_consts_lm_wide``): trees of up to ``GN_WIDE_MAX_ROWS`` constants are fitted too; a tree of
         at most ``GN_MAX_ROWS`` follows the default call's trajectory bit for bit.
         ``scaled=True`` (``de_fit_consts_lm_scaled``; ``loss="L2"`` and ``wide=False`` only, anything else is a
@@ -2111,13 +2196,15 @@ class Population:
         redundant under scaling (an additive or multiplicative constant at the root: a zero row of the projected matrix) gets the zero
         step and keeps its constants, where the host loop's LU solve may still move it.  The scaled fit of trees of
         more than ``GN_MAX_ROWS`` constants is ``fit_constants_lm_scaled_device(wide=True)``."""
+        if tied and (scaled or wide):
+            raise ValueError("fit_constants_lm_device(tied=True): the scaled and the wide fits are not served under ties")
         if scaled and wide:
             raise ValueError("fit_constants_lm_device(scaled=True, wide=True): the scaled fit of trees of more than 8 rows is "
                              "fit_constants_lm_scaled_device(wide=True)")
         if scaled and loss != "L2":
             raise ValueError(f"fit_constants_lm_device(scaled=True) minimises the L2 residual under linear scaling: loss {loss!r} is not supported")
         return self._fit_constants_lm_device(X, y, consts0, weights, iters, lam0, up, down, 1e-12, history, params, classes, class_base, loss,
-                                             loss_param, e_floor, wide, scaled)
+                                             loss_param, e_floor, wide, scaled, tied)
 
     def fit_constants_lm_scaled_device(self, X, y, consts0=None, weights=None, iters: int = 10, lam0: float = 1e-3, up: float = 10.0,
                                        down: float = 0.1, lam_min: float = 1e-12, history: Optional[list] = None, wide: bool = False,
@@ -2137,10 +2224,10 @@ class Population:
                                              0.0, 1e-4, True, True)
 
     def _fit_constants_lm_device(self, X, y, consts0, weights, iters, lam0, up, down, lam_min, history, params, classes, class_base, loss,
-                                 loss_param, e_floor, wide, scaled):
+                                 loss_param, e_floor, wide, scaled, tied=False):
         self._refuse_f16("fit_constants_lm_device")
         spec = gn_loss_spec(loss, loss_param, e_floor)
-        if self._occ is not None:
+        if self._occ is not None and not tied:
             raise ValueError("fit_constants_lm_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_lm")
         opts = LmOpts(int(iters), 0, float(lam0), float(up), float(down), float(lam_min))
@@ -2162,6 +2249,10 @@ class Population:
             fit = lib.de_fit_consts_lm_scaled_wide if wide else lib.de_fit_consts_lm_scaled
             self.ctx.check(fit(*head, C.byref(opts), ptrs[0], stp, stp + 24 * nt, *ptrs[1:]))
             self._lm_fit_raw = st if nt else None  # (lm_fit_stats reads it: a device tensor is copied only then)
+        elif tied:
+            tie = self._tie_map()
+            self.ctx.check(lib.de_fit_consts_lm_tied(*head, C.byref(spec), float(e_floor), C.byref(opts),
+                                                     tie.ctypes.data if tie is not None else None, *ptrs))
         else:
             fit = lib.de_fit_consts_lm_wide if wide else lib.de_fit_consts_lm_ex
             self.ctx.check(fit(*head, C.byref(spec), float(e_floor), C.byref(opts), *ptrs))
@@ -2302,23 +2393,29 @@ class Population:
 
     def fit_constants_bfgs_device(self, X, y, consts0=None, weights=None, iters: int = 20, step0: float = 1.0, shrink: float = 0.5,
                                   c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
-                                  history: Optional[list] = None, params=None, classes=None, class_base: int = 1, scaled: bool = False):
+                                  history: Optional[list] = None, params=None, classes=None, class_base: int = 1, scaled: bool = False,
+                                  tied: bool = False):
         """``fit_constants_bfgs`` as ONE library call (``de_fit_consts_bfgs``): the directions, the trial constants, the
         accept rule and the updates of ``B`` run on the device; no constant, gradient or matrix reaches the host, and the trajectory is
         the host loop's bit for bit.  ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the
         population's current constants.  Returns (consts, loss[n_trees] in the population's dtype, ok) at the accepted constants, which
         the population holds afterwards; with torch inputs all three are device tensors and nothing synchronises beyond what
         ``eval_loss_grad`` does.  ``history`` (a list) receives the ``iters + 1`` rows of accepted losses (float64); ``self.bfgs_accepts``
-        holds the number of accepted steps per tree.  A population with shared GraphNode constants raises ``ValueError``:
-        ``fit_constants_bfgs`` serves it.
+        holds the number of accepted steps per tree.  A population with shared GraphNode constants raises ``ValueError`` unless
+        ``tied=True`` (``de_fit_consts_bfgs_tied``): a shared constant is then ONE unknown, its occurrence rows summed on
+        the device — ``fit_constants_bfgs``' trajectory bit for bit; a tree of up to ``BFGS_MAX_ROWS`` UNIQUE constants is fitted,
+        ``consts0`` and the result stay in ``set_constants``' layout.  ``tied=True`` with ``scaled=True`` is a ``ValueError`` before the
+        constants are touched; on a population without shared constants it is the default call bit for bit.
         ``scaled=True`` (``de_fit_consts_bfgs_scaled``; ``loss="L2"`` only, anything else is a ``ValueError`` before the
         constants are touched): ``fit_constants_bfgs(scaled=True)`` on the device, bit for bit.  Returns (consts, scaled_sse[n_trees] in
         float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` at the returned constants (with torch inputs reading it copies 3
         n_trees + 3 doubles to the host, the call itself does not)."""
+        if tied and scaled:
+            raise ValueError("fit_constants_bfgs_device(tied=True): the scaled fit is not served under ties")
         _refuse_scaled_kind("fit_constants_bfgs_device", scaled, loss)
         self._refuse_f16("fit_constants_bfgs_device")
         opts, spec = _bfgs_opts(iters, step0, shrink, c1, curv, loss, loss_param)
-        if self._occ is not None:
+        if self._occ is not None and not tied:
             raise ValueError("fit_constants_bfgs_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_bfgs")
         ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_bfgs_device", X, y, weights, consts0, params,
@@ -2327,6 +2424,10 @@ class Population:
         head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
         if scaled:
             self._fit_scaled_device(library().de_fit_consts_bfgs_scaled, head, opts, ptrs, is_t, keep_x)
+        elif tied:
+            tie = self._tie_map()
+            self.ctx.check(library().de_fit_consts_bfgs_tied(*head, C.byref(spec), C.byref(opts), tie.ctypes.data if tie is not None else None,
+                                                             *ptrs))
         else:
             self.ctx.check(library().de_fit_consts_bfgs(*head, C.byref(spec), C.byref(opts), *ptrs))
         self.bfgs_accepts = acc
@@ -2365,20 +2466,28 @@ class Population:
 
     def fit_constants_lbfgs_device(self, X, y, consts0=None, weights=None, iters: int = 20, memory: int = 8, step0: float = 1.0,
                                    shrink: float = 0.5, c1: float = 1e-4, curv: float = 1e-8, loss: str = "L2", loss_param: float = 0.0,
-                                   history: Optional[list] = None, params=None, classes=None, class_base: int = 1):
+                                   history: Optional[list] = None, params=None, classes=None, class_base: int = 1, tied: bool = False):
         """``fit_constants_lbfgs`` as ONE library call (``de_fit_consts_lbfgs``): the two-loop recursions, the trial
         constants, the accept rule and the rings run on the device, and the trajectory is the host loop's bit for bit.  Arguments and
-        results as ``fit_constants_bfgs_device``, the loss and flags being ``eval_loss``'s at the accepted constants as there; ``self.lbfgs_accepts`` holds the number of accepted steps per tree."""
+        results as ``fit_constants_bfgs_device``, the loss and flags being ``eval_loss``'s at the accepted constants as there; ``self.lbfgs_accepts`` holds the number of accepted steps per tree.
+        A population with shared GraphNode constants raises ``ValueError`` unless ``tied=True`` (``de_fit_consts_lbfgs_tied``, DESIGN.md
+        §4.4.16): a shared constant is ONE unknown, ``fit_constants_lbfgs``' trajectory bit for bit, for trees of up to ``LBFGS_MAX_ROWS``
+        unique constants."""
         self._refuse_f16("fit_constants_lbfgs_device")
         opts, spec = _lbfgs_opts(iters, memory, step0, shrink, c1, curv, loss, loss_param)
-        if self._occ is not None:
+        if self._occ is not None and not tied:
             raise ValueError("fit_constants_lbfgs_device: the population shares GraphNode constants (their per-occurrence rows are combined "
                              "on the host): use fit_constants_lbfgs")
         ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_lbfgs_device", X, y, weights, consts0, params,
                                                                                 classes, class_base)
         lo, ok, hist, acc, ptrs = self._fit_device_outputs(is_t, keep_x, iters, self.dtype)
-        self.ctx.check(library().de_fit_consts_lbfgs(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp, C.byref(spec),
-                                                     C.byref(opts), *ptrs))
+        head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
+        if tied:
+            tie = self._tie_map()
+            self.ctx.check(library().de_fit_consts_lbfgs_tied(*head, C.byref(spec), C.byref(opts), tie.ctypes.data if tie is not None else None,
+                                                              *ptrs))
+        else:
+            self.ctx.check(library().de_fit_consts_lbfgs(*head, C.byref(spec), C.byref(opts), *ptrs))
         self.lbfgs_accepts = acc
         if history is not None:
             history.extend(hist[r] for r in range(int(iters) + 1))
@@ -2422,7 +2531,7 @@ class Population:
 
     def fit_constants_nm_device(self, X, y, consts0=None, weights=None, iters: int = 200, a: float = 0.025, b: float = 0.5,
                                 f_tol: float = 0.0, loss: str = "L2", loss_param: float = 0.0, history: Optional[list] = None,
-                                params=None, classes=None, class_base: int = 1, scaled: bool = False):
+                                params=None, classes=None, class_base: int = 1, scaled: bool = False, tied: bool = False):
         """``fit_constants_nm`` as ONE library call (``de_fit_consts_nm``): the simplex, the trial constants and every
         decision live on the device; no constant or loss reaches the host, and the trajectory is the host loop's bit for bit.
         ``consts0``: a numpy array or a torch device tensor in ``set_constants``' layout, ``None``: the population's current constants.
@@ -2430,15 +2539,19 @@ class Population:
         with torch inputs all three are device tensors and nothing synchronises beyond what ``eval_loss`` does.  ``history`` (a list)
         receives the ``iters + 1`` rows of accepted losses (float64); ``self.nm_improves`` holds the number of rounds that lowered each
         tree's accepted loss.  GraphNode populations are served (the library call has no gradient rows to combine) unless a CONSTANT is
-        shared: the library moves one coordinate per occurrence, which would untie the occurrences — a ``ValueError``;
-        ``fit_constants_nm`` serves those.
+        shared: the library moves one coordinate per occurrence, which would untie the occurrences — a ``ValueError`` unless
+        ``tied=True`` (``de_fit_consts_nm_tied``): ask and tell then work on the unique constants, which are fanned out
+        to their slots before every install — ``fit_constants_nm``'s trajectory bit for bit.  ``tied=True`` with ``scaled=True`` is a
+        ``ValueError`` before the constants are touched.
         ``scaled=True`` (``de_fit_consts_nm_scaled``; ``loss="L2"`` only, anything else is a ``ValueError`` before the
         constants are touched): ``fit_constants_nm(scaled=True)`` on the device, bit for bit.  Returns (consts, scaled_sse[n_trees] in
         float64, ok); ``self.scaled_fit_stats`` holds the ``FitStats`` at the returned constants."""
+        if tied and scaled:
+            raise ValueError("fit_constants_nm_device(tied=True): the scaled fit is not served under ties")
         _refuse_scaled_kind("fit_constants_nm_device", scaled, loss)
         self._refuse_f16("fit_constants_nm_device")
         opts, spec = _nm_opts(iters, a, b, f_tol, loss, loss_param)
-        if self._occ is not None:
+        if self._occ is not None and not tied:
             raise ValueError("fit_constants_nm_device: the population shares GraphNode constants (the library moves every occurrence on "
                              "its own): use fit_constants_nm")
         ptr, N, ldX, pa, yp, wp, keep, is_t, keep_x = self._fit_device_inputs("fit_constants_nm_device", X, y, weights, consts0, params,
@@ -2447,6 +2560,10 @@ class Population:
         head = (self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None, yp, wp)
         if scaled:
             self._fit_scaled_device(library().de_fit_consts_nm_scaled, head, opts, ptrs, is_t, keep_x)
+        elif tied:
+            tie = self._tie_map()
+            self.ctx.check(library().de_fit_consts_nm_tied(*head, C.byref(spec), C.byref(opts), tie.ctypes.data if tie is not None else None,
+                                                           *ptrs))
         else:
             self.ctx.check(library().de_fit_consts_nm(*head, C.byref(spec), C.byref(opts), *ptrs))
         self.nm_improves = acc

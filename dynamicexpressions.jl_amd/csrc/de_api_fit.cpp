@@ -3,8 +3,9 @@
 // de_lm_scaled_wide.hip); de_fit_consts_lm(_ex, _wide), de_fit_consts_lm_scaled(_wide) and
 // de_fit_consts_bfgs (kernels de_bfgs.hip, §4.4.10), de_fit_consts_lbfgs (kernels de_lbfgs.hip, §4.4.15), de_fit_consts_nm (kernels de_nm.hip, §4.4.13) and the scaled forms of those two
 // (de_fit_consts_bfgs_scaled / de_fit_consts_nm_scaled, adapter kernel de_fit_scaled.hip, §4.4.14): fits on the constants that are
-// ONE driver — fit_check, stage_fit_inputs, a Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; and the host
-// hooks that run the kernels' arithmetic.
+// ONE driver — fit_check, stage_fit_inputs, a Workspace in sLm, run_fit, FitOutputs — around their own evaluation and kernels; the _tied forms
+// of four of them (de_fit_consts_{bfgs,lbfgs,nm,lm}_tied, §4.4.16: a shared GraphNode constant as one unknown; kernels de_ties.hip, arithmetic
+// de_ties.h), which are the same functions with a TiedState; and the host hooks that run the kernels' arithmetic.
 #include "de_api_internal.h"
 #include "de_lm.h"
 #include "de_lm_solve.h"
@@ -21,6 +22,49 @@
 #include "de_nm_dev.h"
 #include "de_fit_scaled.h"
 #include "de_fit_scaled_dev.h"
+#include "de_ties.h"
+#include "de_ties_dev.h"
+
+// the tie hooks (de_ties.h): one tree's map on host buffers of the element type.  Each returns U, or -1 with nothing written
+template <class Body>
+static int ties_hook(int32_t n_slots, const int32_t *tie, const Body &body) {
+    const int64_t U = ties_unknowns(n_slots, tie);
+    if (U < 0) return -1;
+    std::vector<int64_t> off((size_t)U + 1), list((size_t)n_slots);
+    ties_csr(n_slots, tie, U, 0, off.data(), list.data());
+    body(U, off.data(), list.data());
+    return (int)U;
+}
+static bool ties_hook_args(int dtype, int32_t n_slots, const int32_t *tie, const void *in, const void *out) {
+    return (dtype == DE_F32 || dtype == DE_F64) && n_slots >= 0 && tie && in && out;
+}
+template <typename T>
+static int ties_pack_t(int32_t n, const int32_t *tie, const void *slots, void *unique) {
+    return ties_hook(n, tie, [&](int64_t U, const int64_t *off, const int64_t *list) {
+        for (int64_t u = 0; u < U; u++) std::memcpy(static_cast<T *>(unique) + u, static_cast<const T *>(slots) + list[off[u]], sizeof(T));
+    });
+}
+template <typename T>
+static int ties_unpack_t(int32_t n, const int32_t *tie, const void *unique, void *slots) {
+    return ties_hook(n, tie, [&](int64_t, const int64_t *, const int64_t *) {
+        for (int32_t s = 0; s < n; s++) std::memcpy(static_cast<T *>(slots) + s, static_cast<const T *>(unique) + tie[s], sizeof(T));
+    });
+}
+template <typename T>
+static int ties_fold_t(int32_t n, const int32_t *tie, const void *g, void *gu) {
+    return ties_hook(n, tie, [&](int64_t U, const int64_t *off, const int64_t *list) {
+        for (int64_t u = 0; u < U; u++) static_cast<T *>(gu)[u] = ties_fold<T>(static_cast<const T *>(g), list + off[u], off[u + 1] - off[u]);
+    });
+}
+template <typename T>
+static int ties_fold_matrix_t(int32_t n, const int32_t *tie, const void *H, void *Hu) {
+    return ties_hook(n, tie, [&](int64_t U, const int64_t *off, const int64_t *list) {
+        for (int64_t v = 0; v < U; v++)
+            for (int64_t u = 0; u < U; u++)
+                static_cast<T *>(Hu)[u + U * v] = ties_fold_matrix<T>(static_cast<const T *>(H), n, 0, list + off[u], off[u + 1] - off[u],
+                                                                      list + off[v], off[v + 1] - off[v]);
+    });
+}
 
 extern "C" {
 // ---- the host hooks: the arithmetic of the step, projection and BFGS kernels on host buffers (de_lm_solve.h, de_lm_solve_wide.h,
@@ -123,6 +167,17 @@ int de_nm_tell_host(int G, int dtype, double *V, double *f, int32_t *st, const d
     else nm_tell_tree<double>(G, 0, G, true, V, f, st, c, xr, fr, F);
     return 1;
 }
+#define DE_TIES_HOOK(NAME, BODY)                                                                         \
+    int NAME(int dtype, int32_t n_slots, const int32_t *tie, const void *in, void *out) {                \
+        if (!ties_hook_args(dtype, n_slots, tie, in, out)) return -1;                                    \
+        try { return dtype == DE_F32 ? BODY<float>(n_slots, tie, in, out) : BODY<double>(n_slots, tie, in, out); }      \
+        catch (...) { return -1; }                                                                       \
+    }
+DE_TIES_HOOK(de_ties_pack_host, ties_pack_t)
+DE_TIES_HOOK(de_ties_unpack_host, ties_unpack_t)
+DE_TIES_HOOK(de_ties_fold_host, ties_fold_t)
+DE_TIES_HOOK(de_ties_fold_matrix_host, ties_fold_matrix_t)
+#undef DE_TIES_HOOK
 
 // what the fits refuse about their options: null = good, else the reason
 const char *bfgs_opts_problem(const de_bfgs_opts_t *o) {
@@ -169,9 +224,13 @@ struct LmTables {
     const int32_t *ng = nullptr;
     int64_t span = 0, jspan = 0, sspan = 0;
 };
-static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out, int rows_per_g = 1) {
+// extra (may be null): a table of the caller's own behind them, 8-byte aligned — the tie tables of a tied fit; *extra_dev: where it lies.
+static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *doffs, const int64_t *joffs, LmTables *out, int rows_per_g = 1,
+                     const std::vector<unsigned char> *extra = nullptr, const unsigned char **extra_dev = nullptr) {
     const size_t nn = (size_t)n, n_off = rows_per_g > 1 ? 3 : 2;
-    std::vector<unsigned char> img(nn * (n_off * sizeof(int64_t) + sizeof(int32_t)));
+    const size_t own = nn * (n_off * sizeof(int64_t) + sizeof(int32_t)), extra_at = (own + 7) & ~(size_t)7;
+    std::vector<unsigned char> img(extra ? extra_at + extra->size() : own);
+    if (extra && !extra->empty()) std::memcpy(img.data() + extra_at, extra->data(), extra->size());
     int64_t *doff = reinterpret_cast<int64_t *>(img.data()), *joff = doff + nn, *soff = n_off > 2 ? joff + nn : nullptr;
     int32_t *w = reinterpret_cast<int32_t *>(doff + n_off * nn);
     int64_t run = 0, jrun = 0, span = 0, jspan = 0, srun = 0;
@@ -214,6 +273,65 @@ static int lm_tables(de_ctx *c, int64_t n, const int32_t *ng, const int64_t *dof
     out->span = span;
     out->jspan = jspan;
     out->sspan = srun;
+    if (extra_dev) *extra_dev = static_cast<const unsigned char *>(c->sLmTab.p) + extra_at;
+    return DE_OK;
+}
+
+// ---- the tie tables ------------------------------------------------------------------------------------------------------
+// A tied fit's view of the program: U_t unknowns per tree (what the optimiser kernels take for n_grad) and the device tables of TieArgs as
+// one image of int64 words [slot_unk | unk_off | unk_slots | slot_off | unk_tree_off | hoff], uploaded behind the geometry tables.
+struct TiePlan {
+    std::vector<int32_t> ng;
+    std::vector<unsigned char> blob;
+    int64_t nu = 0, hspan = 0; // the unknowns of the population; the elements of its packed S x S occurrence blocks
+    size_t nc = 0, nt = 0;
+    void bind(const unsigned char *dev, const int64_t *huoff, int32_t max_slots, TieArgs *a) const {
+        const int64_t *w = reinterpret_cast<const int64_t *>(dev);
+        a->n_trees = (int64_t)nt; a->n_slots = (int64_t)nc; a->n_unknowns = nu;
+        a->slot_unk = w;
+        a->unk_off = a->slot_unk + nc;
+        a->unk_slots = a->unk_off + nu + 1;
+        a->slot_off = a->unk_slots + nc;
+        a->unk_tree_off = a->slot_off + nt + 1;
+        a->hoff = a->unk_tree_off + nt + 1;
+        a->huoff = huoff;
+        a->max_slots = max_slots;
+    }
+};
+// tie: host, one id per constant slot in de_program_set_consts order.  Refused: a negative id, or an id out of first-occurrence order.
+static int tie_plan(de_ctx *c, const de_program *p, const char *what, const int32_t *tie, TiePlan *pl) {
+    const size_t nt = (size_t)p->n_trees, nc = (size_t)p->const_off[nt];
+    pl->nt = nt;
+    pl->nc = nc;
+    pl->ng.resize(nt);
+    int64_t nu = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t S = p->const_off[t + 1] - p->const_off[t], U = ties_unknowns(S, tie + p->const_off[t]);
+        if (U < 0)
+            return fail(c, DE_ERR_INVALID_ARG, "%s: tree %lld: the tie map has a negative id or is not in first-occurrence order", what, (long long)t);
+        pl->ng[t] = (int32_t)U;
+        nu += U;
+    }
+    pl->nu = nu;
+    pl->blob.assign((2 * nc + (size_t)nu + 1 + 3 * nt + 2) * sizeof(int64_t), 0);
+    int64_t *slot_unk = reinterpret_cast<int64_t *>(pl->blob.data()), *unk_off = slot_unk + nc, *unk_slots = unk_off + nu + 1,
+            *slot_off = unk_slots + nc, *unk_tree_off = slot_off + nt + 1, *hoff = unk_tree_off + nt + 1;
+    int64_t u0 = 0, h = 0;
+    for (size_t t = 0; t < nt; t++) {
+        const int64_t s0 = p->const_off[t], S = p->const_off[t + 1] - s0, U = pl->ng[t];
+        slot_off[t] = s0;
+        unk_tree_off[t] = u0;
+        hoff[t] = h;
+        for (int64_t s = 0; s < S; s++) slot_unk[s0 + s] = u0 + tie[s0 + s];
+        // (the tree's CSR offsets count from 0: shifted to its first entry of unk_slots, which is its first slot)
+        ties_csr(S, tie + s0, U, s0, unk_off + u0, unk_slots + s0);
+        for (int64_t u = 0; u <= U; u++) unk_off[u0 + u] += s0;
+        u0 += U;
+        h += S * S;
+    }
+    slot_off[nt] = (int64_t)nc;
+    unk_tree_off[nt] = nu;
+    pl->hspan = h;
     return DE_OK;
 }
 
@@ -348,15 +466,16 @@ int de_fit_stats_lm_step_wide(de_ctx_t *c, int dtype, int64_t n_trees, const int
 // (fold_hint: what its caller does with the rows of a shared constant); a tree whose constant rows are not its constants; the options
 // (opts_why: lm_opts_problem / bfgs_opts_problem); N and the null buffers (`required` must not be null when there is a tree); ldX; the
 // parameter arguments.  `what`: the name in the texts (the narrow entry point's, for its _ex and _wide forms too).  gradient_rows = false
-// (de_fit_consts_nm: no gradient): the two refusals about constant rows are skipped.
+// (de_fit_consts_nm: no gradient): the two refusals about constant rows are skipped.  tied (the _tied entry points):
+// the occurrence rows are folded on the device, so a CSE program is served.
 static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char *fold_hint, const std::function<int()> &spec_check,
                      const char *opts_why, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
-                     std::initializer_list<const void *> required, bool gradient_rows = true) {
+                     std::initializer_list<const void *> required, bool gradient_rows = true, bool tied = false) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
     if (p->ctx != c) return fail(c, DE_ERR_INVALID_ARG, "program belongs to another context");
     if (spec_check)
         if (const int rc = spec_check()) return rc;
-    if (gradient_rows && !p->in_cse.empty())
+    if (gradient_rows && !tied && !p->in_cse.empty())
         return fail(c, DE_ERR_UNSUPPORTED, "%s: a program made by de_program_create_cse has one gradient row per occurrence of a shared constant "
                                            "(%s); such callers keep the host loop", what, fold_hint);
     for (int64_t t = 0; gradient_rows && t < p->n_trees; t++)
@@ -380,6 +499,10 @@ static int fit_check(de_ctx_t *c, de_program_t *p, const char *what, const char 
 struct FitLoop {
     std::function<int(bool)> evaluate;
     std::function<int()> init, propose, finish, report;
+    // a tied fit (both may be empty): prepare runs before the first evaluation where the loop will run — the program takes
+    // unpack(pack(its constants)), the accepted unknowns are packed; settle runs before the accepted constants are installed at the end —
+    // consts_acc, the slot vector, takes unpack of the accepted unknowns
+    std::function<int()> prepare, settle;
     std::function<int(double *)> first_history, fill_history, accept;
     void *consts_acc = nullptr, *consts_trial = nullptr;
     const char *last_kernel = nullptr; // what the context reports behind the loop (null: what the last inner call set)
@@ -389,7 +512,8 @@ static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, d
     if (!c->nested) HIP_TRY(c, time_begin(c));
     {
         NestGuard nest(c);
-        int rc = f.evaluate(false);
+        int rc = can_move && iters > 0 && f.prepare ? f.prepare() : (int)DE_OK;
+        if (rc == DE_OK) rc = f.evaluate(false);
         if (rc == DE_OK) rc = f.init();
         if (rc == DE_OK) rc = f.first_history(hist);
         if (rc != DE_OK) return rc;
@@ -408,7 +532,8 @@ static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, d
             }
             if (f.last_kernel) c->last_kernel = f.last_kernel;
             // the program holds the accepted constants afterwards (after a failure too: the last accepted ones)
-            const int rc2 = set_consts_device_impl(p, f.consts_acc);
+            int rc2 = f.settle ? f.settle() : (int)DE_OK;
+            if (rc2 == DE_OK) rc2 = set_consts_device_impl(p, f.consts_acc);
             if (rc != DE_OK) return rc;
             if (rc2 != DE_OK) return rc2;
             if (f.finish && (rc = f.finish()) != DE_OK) return rc;
@@ -419,12 +544,64 @@ static int run_fit(de_ctx_t *c, de_program_t *p, int32_t iters, bool can_move, d
     return DE_OK;
 }
 
+// What a tied fit adds to its driver: the optimiser kernels see U_t unknowns per tree (ng) and vectors of unknowns; the
+// program is set from SLOT vectors (sA accepted, sT trial), and an evaluation writes its occurrence rows (gO) and blocks (jO: the
+// Levenberg-Marquardt fit alone) into buffers of their own, which fold / fold_matrix reduce into the state the kernels read.
+// on = false (tie == NULL: the identity): nothing of this exists and the call runs its untied twin's launches.
+struct TiedState {
+    bool on = false;
+    TiePlan plan;
+    TieArgs a;
+    const unsigned char *dev = nullptr;
+    Workspace::Region<char> sA{0, false}, sT{0, false}, gO{0, false}, jO{0, false};
+    int begin(de_ctx *c, const de_program *p, const char *what, const int32_t *tie) {
+        std::memset(&a, 0, sizeof a);
+        if (!tie) return DE_OK;
+        on = true;
+        return tie_plan(c, p, what, tie, &plan);
+    }
+    const int32_t *widths(const de_program *p) const { return on ? plan.ng.data() : p->n_consts_tree.data(); }
+    void place(Workspace &ws, size_t es, bool gradient, bool matrix) {
+        if (!on) return;
+        sA = ws.place<char>(plan.nc * es);
+        sT = ws.place<char>(plan.nc * es);
+        gO = ws.place<char>(plan.nc * es, gradient);
+        jO = ws.place<char>((size_t)std::max<int64_t>(plan.hspan, 1) * es, matrix);
+    }
+    // FitLoop's slot vectors and hooks: u_acc / u_trial are the kernels' vectors of unknowns
+    void hook(de_ctx *c, de_program *p, const Workspace &ws, void *u_acc, void *u_trial, FitLoop *f) {
+        if (!on) return;
+        void *acc = ws.ptr(sA), *trial = ws.ptr(sT);
+        f->consts_acc = acc;
+        f->consts_trial = trial;
+        const std::function<int()> propose = f->propose;
+        f->propose = [=]() -> int {
+            const int rc = propose();
+            if (rc != DE_OK) return rc;
+            HIP_TRY(c, launch_ties_unpack(p->dtype, a, u_trial, trial, c->stream));
+            return DE_OK;
+        };
+        f->prepare = [=]() -> int { // the first occurrence decides: the program starts from unpack(pack(its constants))
+            int rc = de_program_get_consts(p, acc);
+            if (rc != DE_OK) return rc;
+            HIP_TRY(c, launch_ties_pack(p->dtype, a, acc, u_acc, c->stream));
+            HIP_TRY(c, launch_ties_unpack(p->dtype, a, u_acc, acc, c->stream));
+            return set_consts_device_impl(p, acc);
+        };
+        f->settle = [=]() -> int {
+            HIP_TRY(c, launch_ties_unpack(p->dtype, a, u_acc, acc, c->stream));
+            return DE_OK;
+        };
+    }
+};
+
 // ---- de_fit_consts_lm(_ex, _wide) (kernels: de_lm.hip, de_gn_wide.hip) -----------------------------------
 // row_limit: the widest tree that is fitted — DE_GN_MAX_ROWS (de_fit_consts_lm: every evaluation is de_eval_loss_gn_ex's) or
 // DE_GN_WIDE_MAX_ROWS (de_fit_consts_lm_wide: de_eval_loss_gn_wide's, and the wide trees' steps by de_lm_step_wide_kernel)
 static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                               const void *w, const de_loss_spec_t *spec_in, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
-                              double *history, int32_t *n_accept, int row_limit) {
+                              double *history, int32_t *n_accept, int row_limit, bool tied = false, const int32_t *tie = nullptr) {
+    const char *what = tied ? "de_fit_consts_lm_tied" : "de_fit_consts_lm";
     const de_lm_opts_t defaults{10, 0, 1e-3, 10.0, 0.1, 1e-12};
     const de_lm_opts_t o = opts ? *opts : defaults;
     const auto spec_check = [&]() -> int {
@@ -432,24 +609,29 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
         int src;
         return gn_spec_problem(spec_in, e_floor, p->dtype, &src, why, sizeof why) ? fail(c, src, "%s", why) : (int)DE_OK;
     };
-    int rc = fit_check(c, p, "de_fit_consts_lm", "the caller folds them: S H S^T", spec_check, lm_opts_problem(&o), X, N, ldX, pa, {ok, y});
+    int rc = fit_check(c, p, what, "the caller folds them: S H S^T", spec_check, lm_opts_problem(&o), X, N, ldX, pa, {ok, y}, true, tied);
     if (rc != DE_OK || p->n_trees == 0) return rc;
+    TiedState ts; // (tied: the gradient and the U x U matrix of the unique constants, folded from the occurrence rows and block)
+    if (tied && (rc = ts.begin(c, p, what, tie)) != DE_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    const size_t nu = ts.on ? (size_t)ts.plan.nu : nc;
     LmTables tab; // packed: the dloss offsets are the constants' offsets
-    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, nullptr, &tab)) != DE_OK) return rc;
+    if ((rc = lm_tables(c, p->n_trees, ts.widths(p), nullptr, nullptr, &tab, 1, ts.on ? &ts.plan.blob : nullptr, &ts.dev)) != DE_OK) return rc;
     const size_t span = (size_t)std::max<int64_t>(tab.span, 1), jspan = (size_t)std::max<int64_t>(tab.jspan, 1);
     FitInputs in;
     if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
     // the state: accepted and trial constants, losses, gradients, matrices and flags; lam and the step; images of a host history / n_accept
     const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept);
     Workspace ws;
-    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
+    const auto cA = ws.place<char>(nu * es), cT = ws.place<char>(nu * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
                dA = ws.place<char>(span * es), dT = ws.place<char>(span * es), jA = ws.place<char>(jspan * es), jT = ws.place<char>(jspan * es);
+    ts.place(ws, es, true, true);
     const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
     const auto lam = ws.place<double>(nt), step = ws.place<double>(span), r_hist = ws.place<double>(rows * nt, h_hist);
     const auto r_acc = ws.place<int32_t>(nt, h_acc);
     if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    if (ts.on) ts.plan.bind(ts.dev, tab.joff, DE_GN_MAX_ROWS, &ts.a);
     FitOutputs out;
     out.from_state(loss, ws.ptr(lA), nt * es);
     out.from_state(ok, ws.ptr(okA), nt);
@@ -487,8 +669,14 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
         void *l = ws.ptr(trial ? lT : lA), *d = ws.ptr(trial ? dT : dA), *j = ws.ptr(trial ? jT : jA);
         uint8_t *k = ws.ptr(trial ? okT : okA);
         if (wide) return gn_wide_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, e_floor, l, d, nullptr, j, nullptr, k);
-        const GnPlan gn{j, nullptr, e_floor};
-        return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, l, d, nullptr, k, nullptr, false, &gn);
+        // (tied: the occurrence rows and packed S x S blocks land in buffers of their own and are folded into d and j)
+        const GnPlan gn{ts.on ? ws.ptr(ts.jO) : j, nullptr, e_floor};
+        const int rc1 = loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, l, ts.on ? ws.ptr(ts.gO) : d, nullptr, k,
+                                       nullptr, false, &gn);
+        if (rc1 != DE_OK || !ts.on) return rc1;
+        HIP_TRY(c, launch_ties_fold(p->dtype, ts.a, ws.ptr(ts.gO), d, c->stream));
+        HIP_TRY(c, launch_ties_fold_matrix(p->dtype, ts.a, ws.ptr(ts.jO), j, c->stream));
+        return DE_OK;
     };
     f.init = [&]() -> int { HIP_TRY(c, launch_lm_init(p->n_trees, o.lam0, ws.ptr(lam), acc, c->stream)); return DE_OK; };
     f.first_history = f.fill_history = [&](double *row) -> int {
@@ -505,8 +693,15 @@ static int fit_consts_lm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
         HIP_TRY(c, launch_lm_accept(p->dtype, a, c->stream));
         return DE_OK;
     };
+    ts.hook(c, p, ws, ws.ptr(cA), ws.ptr(cT), &f);
     if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
     return out.finish(c);
+}
+int de_fit_consts_lm_tied(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                          const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, const int32_t *tie, void *loss,
+                          uint8_t *ok, double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lm_tied");
+    DE_NOTHROW(c, fit_consts_lm_impl(c, p, X, N, ldX, pa, y, w, spec, e_floor, opts, loss, ok, history, n_accept, DE_GN_MAX_ROWS, true, tie));
 }
 int de_fit_consts_lm_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                         const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts, void *loss, uint8_t *ok,
@@ -640,7 +835,8 @@ int de_fit_consts_lm_scaled_wide(de_ctx_t *c, de_program_t *p, const void *X, in
 // de_fit_consts_lbfgs ends with one de_eval_loss_ex at the accepted constants (FitLoop::report): loss and ok are that call's.
 static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, int memory, const de_bfgs_opts_t &o, const char *opts_why,
                               const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y, const void *w,
-                              const de_loss_spec_t *spec_in, void *loss, uint8_t *ok, double *history, int32_t *n_accept) {
+                              const de_loss_spec_t *spec_in, void *loss, uint8_t *ok, double *history, int32_t *n_accept,
+                              bool tied = false, const int32_t *tie = nullptr) {
     const auto spec_check = [&]() -> int {
         char why[160];
         if (loss_spec_problem(spec_in, 1, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
@@ -649,10 +845,14 @@ static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, in
             return fail(c, DE_ERR_UNSUPPORTED, "%s needs the LDS-tiled kernel (feature matrix too wide for this build)", what);
         return DE_OK;
     };
-    int rc = fit_check(c, p, what, "the caller sums them", spec_check, opts_why, X, N, ldX, pa, {ok, y});
+    int rc = fit_check(c, p, what, "the caller sums them", spec_check, opts_why, X, N, ldX, pa, {ok, y}, true, tied);
     if (rc != DE_OK || p->n_trees == 0) return rc;
+    TiedState ts; // (tied: the unknowns are the unique constants)
+    if (tied && (rc = ts.begin(c, p, what, tie)) != DE_OK) return rc;
+    const int32_t *ng = ts.widths(p);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    const size_t nu = ts.on ? (size_t)ts.plan.nu : nc;
     QnKernels q;
     std::memset(&q.x, 0, sizeof q.x);
     q.memory = memory;
@@ -660,10 +860,10 @@ static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, in
     int64_t bspan = 0;
     for (size_t t = 0; t < nt; t++) {
         boff[t] = bspan;
-        bspan += q.state_doubles(p->n_consts_tree[t]);
+        bspan += q.state_doubles(ng[t]);
     }
     LmTables tab; // packed: the dloss offsets are the constants' offsets; the matrix offsets are B's (the ring's)
-    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, boff.data(), &tab)) != DE_OK) return rc;
+    if ((rc = lm_tables(c, p->n_trees, ng, nullptr, boff.data(), &tab, 1, ts.on ? &ts.plan.blob : nullptr, &ts.dev)) != DE_OK) return rc;
     const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
     FitInputs in;
     if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
@@ -671,14 +871,16 @@ static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, in
     // slope and the direction, two flags per tree; the images
     const bool h_hist = FitOutputs::on_host(history), h_acc = FitOutputs::on_host(n_accept), ring = memory > 0;
     Workspace ws;
-    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
+    const auto cA = ws.place<char>(nu * es), cT = ws.place<char>(nu * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es),
                dA = ws.place<char>(span * es), dT = ws.place<char>(span * es);
+    ts.place(ws, es, true, false);
     const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt), fresh = ws.place<uint8_t>(nt, !ring), produced = ws.place<uint8_t>(nt);
     const auto B = ws.place<double>((size_t)bspan), alpha = ws.place<double>(nt), slope = ws.place<double>(nt), dir = ws.place<double>(span),
                Yr = ws.place<double>((size_t)bspan, ring), rho = ws.place<double>(nt * (size_t)memory, ring), tmp = ws.place<double>(span, ring),
                r_hist = ws.place<double>(rows * nt, h_hist);
     const auto count = ws.place<int32_t>(nt, ring), head = ws.place<int32_t>(nt, ring), r_acc = ws.place<int32_t>(nt, h_acc);
     if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    if (ts.on) ts.plan.bind(ts.dev, tab.joff, 0, &ts.a);
     FitOutputs out;
     out.from_state(loss, ws.ptr(lA), nt * es);
     out.from_state(ok, ws.ptr(okA), nt);
@@ -708,8 +910,12 @@ static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, in
     f.consts_acc = a.consts_acc;
     f.consts_trial = a.consts_trial;
     f.evaluate = [&](bool trial) -> int {
-        return loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, ws.ptr(trial ? lT : lA), ws.ptr(trial ? dT : dA),
-                              nullptr, ws.ptr(trial ? okT : okA), nullptr);
+        char *d = ws.ptr(trial ? dT : dA); // (tied: the occurrence rows land in a buffer of their own and are folded into d)
+        const int rc1 = loss_grad_impl(c, p, in.Xd, N, ldX, in.pa, DE_GRAD_CONSTANT, in.yd, in.wd, &spec, ws.ptr(trial ? lT : lA),
+                                       ts.on ? ws.ptr(ts.gO) : d, nullptr, ws.ptr(trial ? okT : okA), nullptr);
+        if (rc1 != DE_OK || !ts.on) return rc1;
+        HIP_TRY(c, launch_ties_fold(p->dtype, ts.a, ws.ptr(ts.gO), d, c->stream));
+        return DE_OK;
     };
     f.init = [&]() -> int { HIP_TRY(c, q.init(p->dtype, c->stream)); return DE_OK; };
     f.first_history = f.fill_history = [&](double *row) -> int {
@@ -722,10 +928,33 @@ static int fit_consts_qn_impl(de_ctx_t *c, de_program_t *p, const char *what, in
         HIP_TRY(c, q.accept(p->dtype, c->stream));
         return DE_OK;
     };
+    ts.hook(c, p, ws, a.consts_acc, a.consts_trial, &f);
     if (ring) // de_fit_consts_lbfgs reports the fused loss alone at the accepted constants: what de_eval_loss_ex gives there, bit for bit
         f.report = [&]() -> int { return de_eval_loss_ex(c, p, in.Xd, N, ldX, in.pa, in.yd, in.wd, &spec, ws.ptr(lA), ws.ptr(okA)); };
     if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
     return out.finish(c);
+}
+int de_fit_consts_bfgs_tied(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                            const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, const int32_t *tie, void *loss, uint8_t *ok,
+                            double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_bfgs_tied");
+    const de_bfgs_opts_t defaults{20, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_bfgs_opts_t o = opts ? *opts : defaults;
+    DE_NOTHROW(c, fit_consts_qn_impl(c, p, "de_fit_consts_bfgs_tied", 0, o, bfgs_opts_problem(&o), X, N, ldX, pa, y, w, spec, loss, ok, history,
+                                     n_accept, true, tie));
+}
+int de_fit_consts_lbfgs_tied(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                             const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, const int32_t *tie, void *loss, uint8_t *ok,
+                             double *history, int32_t *n_accept) {
+    DE_REFUSE_F16("de_fit_consts_lbfgs_tied");
+    const de_lbfgs_opts_t defaults{20, 0, 8, 0, 1.0, 0.5, 1e-4, 1e-8};
+    const de_lbfgs_opts_t lo = opts ? *opts : defaults;
+    de_bfgs_opts_t o;
+    const char *why = lbfgs_opts_problem(&lo, &o);
+    char named[200]; // (the text names the call)
+    if (why) std::snprintf(named, sizeof named, "de_fit_consts_lbfgs_tied: %s", why);
+    DE_NOTHROW(c, fit_consts_qn_impl(c, p, "de_fit_consts_lbfgs_tied", lo.memory, o, why ? named : nullptr, X, N, ldX, pa, y, w, spec, loss, ok,
+                                     history, n_accept, true, tie));
 }
 int de_fit_consts_bfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                        const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, void *loss, uint8_t *ok, double *history,
@@ -754,42 +983,49 @@ int de_fit_consts_lbfgs(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
 // round is ask, the trial constants installed, one loss launch, tell.  No gradient rows: programs made by de_program_create_cse are served.
 static int fit_consts_nm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                               const void *w, const de_loss_spec_t *spec_in, const de_nm_opts_t *opts, void *loss, uint8_t *ok, double *history,
-                              int32_t *n_improve) {
+                              int32_t *n_improve, bool tied = false, const int32_t *tie = nullptr) {
+    const char *what = tied ? "de_fit_consts_nm_tied" : "de_fit_consts_nm";
     const de_nm_opts_t defaults{200, 0, 0.025, 0.5, 0.0};
     const de_nm_opts_t o = opts ? *opts : defaults;
     const auto spec_check = [&]() -> int {
         char why[160];
         if (loss_spec_problem(spec_in, 0, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "de_fit_consts_nm: DE_LOSS_PULLBACK is no objective");
+        if (spec_in->kind == DE_LOSS_PULLBACK) return fail(c, DE_ERR_INVALID_ARG, "%s: DE_LOSS_PULLBACK is no objective", what);
         if (!p->threaded)
-            return fail(c, DE_ERR_UNSUPPORTED, "de_fit_consts_nm needs the LDS-tiled kernel (feature matrix too wide for this build)");
+            return fail(c, DE_ERR_UNSUPPORTED, "%s needs the LDS-tiled kernel (feature matrix too wide for this build)", what);
         return DE_OK;
     };
-    int rc = fit_check(c, p, "de_fit_consts_nm", "", spec_check, nm_opts_problem(&o), X, N, ldX, pa, {ok, y}, false);
+    int rc = fit_check(c, p, what, "", spec_check, nm_opts_problem(&o), X, N, ldX, pa, {ok, y}, false);
     if (rc != DE_OK || p->n_trees == 0) return rc;
+    TiedState ts; // (tied: ask and tell work on the unique constants)
+    if (tied && (rc = ts.begin(c, p, what, tie)) != DE_OK) return rc;
+    const int32_t *ng = ts.widths(p);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t es = p->dtype == DE_F32 ? 4 : 8, nt = (size_t)p->n_trees, nc = p->consts.size(), rows = (size_t)o.iters + 1;
+    const size_t nu = ts.on ? (size_t)ts.plan.nu : nc;
     std::vector<int64_t> voff(nt); // the simplex: (G + 1) G vertices and G + 1 losses of every tree that can be fitted, none of the others
     int64_t vspan = 0;
     for (size_t t = 0; t < nt; t++) {
-        const int64_t g = p->n_consts_tree[t];
+        const int64_t g = ng[t];
         voff[t] = vspan;
         if (g >= 1 && g <= NM_MAX_ROWS) vspan += (g + 1) * (g + 1);
     }
     LmTables tab; // packed: the constants' offsets; the matrix offsets are the simplex's
-    if ((rc = lm_tables(c, p->n_trees, p->n_consts_tree.data(), nullptr, voff.data(), &tab)) != DE_OK) return rc;
+    if ((rc = lm_tables(c, p->n_trees, ng, nullptr, voff.data(), &tab, 1, ts.on ? &ts.plan.blob : nullptr, &ts.dev)) != DE_OK) return rc;
     const size_t span = (size_t)std::max<int64_t>(tab.span, 1);
     FitInputs in;
     if ((rc = stage_fit_inputs(c, p, X, N, ldX, pa, y, w, &in)) != DE_OK) return rc;
     // the state: accepted and trial constants, losses and flags; the simplex, c, xr, fr and three ints per tree; the images
     const bool h_hist = FitOutputs::on_host(history), h_imp = FitOutputs::on_host(n_improve);
     Workspace ws;
-    const auto cA = ws.place<char>(nc * es), cT = ws.place<char>(nc * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es);
+    const auto cA = ws.place<char>(nu * es), cT = ws.place<char>(nu * es), lA = ws.place<char>(nt * es), lT = ws.place<char>(nt * es);
+    ts.place(ws, es, false, false);
     const auto okA = ws.place<uint8_t>(nt), okT = ws.place<uint8_t>(nt);
     const auto V = ws.place<double>((size_t)vspan), cen = ws.place<double>(span), xr = ws.place<double>(span), fr = ws.place<double>(nt),
                r_hist = ws.place<double>(rows * nt, h_hist);
     const auto st = ws.place<int32_t>(3 * nt), r_imp = ws.place<int32_t>(nt, h_imp);
     if ((rc = ws.reserve(c, c->sLm)) != DE_OK) return rc;
+    if (ts.on) ts.plan.bind(ts.dev, tab.joff, 0, &ts.a);
     FitOutputs out;
     out.from_state(loss, ws.ptr(lA), nt * es);
     out.from_state(ok, ws.ptr(okA), nt);
@@ -816,8 +1052,9 @@ static int fit_consts_nm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
     };
     f.init = [&]() -> int {
         if (nc > 0) { // (the accepted constants are the kernel's V_0: it needs them before run_fit reads them for the loop)
-            const int rc1 = de_program_get_consts(p, a.consts_acc);
+            const int rc1 = de_program_get_consts(p, ts.on ? ws.ptr(ts.sA) : a.consts_acc);
             if (rc1 != DE_OK) return rc1;
+            if (ts.on) HIP_TRY(c, launch_ties_pack(p->dtype, ts.a, ws.ptr(ts.sA), a.consts_acc, c->stream));
         }
         HIP_TRY(c, launch_nm_init(p->dtype, a, c->stream));
         return DE_OK;
@@ -832,8 +1069,15 @@ static int fit_consts_nm_impl(de_ctx_t *c, de_program_t *p, const void *X, int64
         HIP_TRY(c, launch_nm_tell(p->dtype, a, c->stream));
         return DE_OK;
     };
+    ts.hook(c, p, ws, a.consts_acc, a.consts_trial, &f);
     if ((rc = run_fit(c, p, o.iters, N > 0 && nc > 0, hist, f)) != DE_OK) return rc;
     return out.finish(c);
+}
+int de_fit_consts_nm_tied(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
+                          const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, const int32_t *tie, void *loss, uint8_t *ok,
+                          double *history, int32_t *n_improve) {
+    DE_REFUSE_F16("de_fit_consts_nm_tied");
+    DE_NOTHROW(c, fit_consts_nm_impl(c, p, X, N, ldX, pa, y, w, spec, opts, loss, ok, history, n_improve, true, tie));
 }
 int de_fit_consts_nm(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa, const void *y,
                      const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, void *loss, uint8_t *ok, double *history,

@@ -7,7 +7,7 @@
 //                       de_eval_loss_gn(_ex, _wide), de_eval_fit_stats_grad(_wide): the generic gradient program; glue around the
 //                       host-only encoders of the threaded and reverse streams (de_grad_encode.cpp), de_lower_tape_grad
 //   de_api_fit.cpp      what CONSUMES them: de_gn_lm_step / de_fit_stats_lm_step (and _wide), de_fit_consts_lm(_ex, _wide),
-//                       de_fit_consts_lm_scaled(_wide), de_fit_consts_bfgs, de_fit_consts_nm — one driver (run_fit) — and their host hooks
+//                       de_fit_consts_lm_scaled(_wide), de_fit_consts_bfgs, de_fit_consts_nm, the _tied fits — one driver (run_fit) — and their host hooks
 //   de_api_tree_params.cpp  de_tape_params_to_consts, de_eval*_tree_params: per-tree parameter matrices, class by class around the calls above
 // No behaviour changed in the split: de_program_stream_hash and the whole test suite are the check.
 #ifndef DE_API_INTERNAL_H

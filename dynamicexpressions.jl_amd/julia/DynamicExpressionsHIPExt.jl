@@ -983,8 +983,23 @@ function population_fit_stats_lm_step(
 end
 
 """
+The `tie` argument of the tied device fits (`de_fit_consts_*_tied`, DESIGN.md §4.4.16): one 0-based id per constant slot of `pop` — the
+unique constant of the slot within its tree, in first-occurrence order (`occurrence_map`, 1-based there), the identity for a tree that
+shares nothing.  `nothing` (the library's identity) when no constant of the population is shared.
+"""
+function tie_map(pop::HIPPopulation)
+    any(o -> o !== nothing, pop.occ) || return nothing
+    tie = Int32[]
+    for t in 1:pop.n_trees
+        o = pop.occ[t]
+        append!(tie, o === nothing ? (Int32(0):Int32(pop.n_slots[t] - 1)) : Int32.(o .- 1))
+    end
+    return tie
+end
+
+"""
     fit_population_constants_lm!(pop, X, y; weights=nothing, iters=10, lam0=1e-3, up=10.0, down=0.1, loss=:L2, loss_param=0.0, e_floor=1e-4,
-                                 wide=false, scaled=false)
+                                 wide=false, scaled=false, tied=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
 Levenberg-Marquardt on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lm_ex`), minimising the loss
@@ -993,7 +1008,9 @@ constants `pop` holds (`set_population_constants!`), and per iteration solves th
 constants there, evaluates, and accepts a tree's step when its loss decreased (`lam_t *= down`, floor 1e-12; else `lam_t *= up`).
 Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the accepted losses
 after `r - 1` iterations.  Trees that are incomplete at the start or wider than `de_gn_max_rows()` keep their constants.  A population
-with a shared GraphNode constant is refused (`DE_ERR_UNSUPPORTED`: its occurrence rows need folding on the host).
+with a shared GraphNode constant is refused (its occurrence rows need folding) unless `tied=true` (`de_fit_consts_lm_tied`, DESIGN.md
+§4.4.16): a shared constant is then ONE unknown, the occurrence rows and the matrix (`S H Sᵀ`) are folded on the device, and a tree is
+fitted where it has at most `de_gn_max_rows()` occurrence slots; not with `wide` or `scaled`.
 `wide=true` (`de_fit_consts_lm_wide`, DESIGN.md §4.4.7) also fits the trees of 9 to `de_gn_wide_max_rows()` = 32 constants; a narrower tree
 follows the default call's trajectory bit for bit.
 `scaled=true` (`de_fit_consts_lm_scaled`, DESIGN.md §4.4.8; `loss=:L2` only; with `wide=true` `de_fit_consts_lm_scaled_wide`, §4.4.9: trees of up
@@ -1005,13 +1022,14 @@ accepted constants (slope `cov / m2_p`, intercept `mean_y - slope * mean_p`).
 function fit_population_constants_lm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=10, lam0::Real=1e-3, up::Real=10.0, down::Real=0.1, loss::Symbol=:L2, loss_param::Real=0.0, e_floor::Real=1e-4,
-    wide::Bool=false, scaled::Bool=false,
+    wide::Bool=false, scaled::Bool=false, tied::Bool=false,
 ) where {T}
+    tied && (wide || scaled) && throw(ArgumentError("fit_population_constants_lm!(tied=true): the scaled and the wide fits are not served under ties"))
     scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_lm!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
-    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lm!: shared GraphNode constants need the host loop"))
+    !tied && any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lm!: shared GraphNode constants need tied=true or the host loop"))
     opts = Ref(LmOpts(Int32(iters), Int32(0), Float64(lam0), Float64(up), Float64(down), 1e-12))
     if scaled
         sse = Vector{Float64}(undef, pop.n_trees)
@@ -1046,7 +1064,14 @@ function fit_population_constants_lm!(
     n_accept = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
         wp = weights === nothing ? C_NULL : pointer(weights)
-        if wide
+        if tied
+            tie = tie_map(pop)
+            check(pop.ctx, GC.@preserve X y weights tie lossv ok history n_accept ccall(
+                (:de_fit_consts_lm_tied, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
+                 Ptr{Int32}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, Float64(e_floor), opts, tie === nothing ? C_NULL : pointer(tie), lossv, ok, history, n_accept))
+        elseif wide
             check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
                 (:de_fit_consts_lm_wide, LIBDE), Cint,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Cdouble, Ref{LmOpts},
@@ -1074,7 +1099,8 @@ struct BfgsOpts             # de_bfgs_opts_t
 end
 
 """
-    fit_population_constants_bfgs!(pop, X, y; weights=nothing, iters=20, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0)
+    fit_population_constants_bfgs!(pop, X, y; weights=nothing, iters=20, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0,
+                                   scaled=false, tied=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
 BFGS on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_bfgs`, DESIGN.md §4.4.10) — the reference's
@@ -1083,7 +1109,9 @@ BFGS on the constants of every tree at once, the whole loop in one library call 
 constants is fitted.  It starts from the constants `pop` holds; per iteration the direction `-B g`, the trial constants, the evaluation
 there, the Armijo accept rule and the update of `B` run on the device.  Afterwards `pop` holds the accepted constants, which are returned
 with their losses and flags; `history[:, r]` are the accepted losses after `r - 1` iterations.  Trees that are incomplete at the start,
-have no constants or more than 32 keep their constants.  A population with a shared GraphNode constant is refused.
+have no constants or more than 32 keep their constants.  A population with a shared GraphNode constant is refused unless `tied=true`
+(`de_fit_consts_bfgs_tied`, DESIGN.md §4.4.16): a shared constant is then ONE unknown, its occurrence rows summed on the device, and a tree
+of up to 32 UNIQUE constants is fitted; not with `scaled`.
 `scaled=true` (`de_fit_consts_bfgs_scaled`, DESIGN.md §4.4.14; `loss=:L2` only) fits under Keijzer's linear scaling `a + b ŷ`: the objective is
 `scaled_sse = m2_y - cov² / m2_p` and its gradient from the moments of `de_eval_fit_stats_grad` without a matrix, both in Float64.  It returns
 `(constants, scaled_sse::Vector{Float64}, ok, history, n_accept, stats)` with `stats` the NamedTuple of `fit_population_constants_lm!(scaled=true)`
@@ -1092,14 +1120,15 @@ at the accepted constants.  A tree with a constant that is redundant under scali
 function fit_population_constants_bfgs!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=20, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8, loss::Symbol=:L2, loss_param::Real=0.0,
-    scaled::Bool=false,
+    scaled::Bool=false, tied::Bool=false,
 ) where {T}
+    tied && scaled && throw(ArgumentError("fit_population_constants_bfgs!(tied=true): the scaled fit is not served under ties"))
     scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_bfgs!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     loss === :pullback && throw(ArgumentError("fit_population_constants_bfgs!: :pullback is the cotangent of a pullback, not an objective"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
-    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_bfgs!: shared GraphNode constants need the host loop"))
+    !tied && any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_bfgs!: shared GraphNode constants need tied=true or the host loop"))
     opts = Ref(BfgsOpts(Int32(iters), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
     if scaled
         sse = Vector{Float64}(undef, pop.n_trees)
@@ -1126,11 +1155,20 @@ function fit_population_constants_bfgs!(
     n_accept = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
         wp = weights === nothing ? C_NULL : pointer(weights)
-        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
-            (:de_fit_consts_bfgs, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
-             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+        if tied
+            tie = tie_map(pop)
+            check(pop.ctx, GC.@preserve X y weights tie lossv ok history n_accept ccall(
+                (:de_fit_consts_bfgs_tied, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
+                 Ptr{Int32}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, tie === nothing ? C_NULL : pointer(tie), lossv, ok, history, n_accept))
+        else
+            check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+                (:de_fit_consts_bfgs, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{BfgsOpts},
+                 Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+        end
     end
     constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
     return constants, lossv, ok .!= 0x00, history, n_accept
@@ -1148,7 +1186,8 @@ struct LbfgsOpts            # de_lbfgs_opts_t
 end
 
 """
-    fit_population_constants_lbfgs!(pop, X, y; weights=nothing, iters=20, memory=8, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0)
+    fit_population_constants_lbfgs!(pop, X, y; weights=nothing, iters=20, memory=8, step0=1.0, shrink=0.5, c1=1e-4, curv=1e-8, loss=:L2, loss_param=0.0,
+                                    tied=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_accept::Vector{Int32})
 
 L-BFGS on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_lbfgs`, DESIGN.md §4.4.15) — the
@@ -1156,17 +1195,18 @@ reference's `optimize(f, g!, tree, LBFGS())` with a backtracking line search —
 alone: every tree of up to `de_lbfgs_max_rows()` = 4096 constants is fitted, its curvature a ring of `memory` (1 .. 16) pairs instead of
 `B`.  Arguments, objectives and results as `fit_population_constants_bfgs!`; the returned losses and flags are those of one fused loss
 evaluation at the accepted constants (`eval_population_loss` there reproduces them bit for bit), `history` keeps the accept rule's.
+`tied=true` (`de_fit_consts_lbfgs_tied`, DESIGN.md §4.4.16) serves a population with a shared GraphNode constant: ONE unknown per constant.
 """
 function fit_population_constants_lbfgs!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=20, memory::Integer=8, step0::Real=1.0, shrink::Real=0.5, c1::Real=1e-4, curv::Real=1e-8, loss::Symbol=:L2,
-    loss_param::Real=0.0,
+    loss_param::Real=0.0, tied::Bool=false,
 ) where {T}
     loss === :pullback && throw(ArgumentError("fit_population_constants_lbfgs!: :pullback is the cotangent of a pullback, not an objective"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
-    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lbfgs!: shared GraphNode constants need the host loop"))
+    !tied && any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_lbfgs!: shared GraphNode constants need tied=true or the host loop"))
     opts = Ref(LbfgsOpts(Int32(iters), Int32(0), Int32(memory), Int32(0), Float64(step0), Float64(shrink), Float64(c1), Float64(curv)))
     spec = loss_spec(loss, loss_param)
     lossv = Vector{T}(undef, pop.n_trees)
@@ -1175,11 +1215,20 @@ function fit_population_constants_lbfgs!(
     n_accept = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
         wp = weights === nothing ? C_NULL : pointer(weights)
-        check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
-            (:de_fit_consts_lbfgs, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{LbfgsOpts},
-             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+        if tied
+            tie = tie_map(pop)
+            check(pop.ctx, GC.@preserve X y weights tie lossv ok history n_accept ccall(
+                (:de_fit_consts_lbfgs_tied, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{LbfgsOpts},
+                 Ptr{Int32}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, tie === nothing ? C_NULL : pointer(tie), lossv, ok, history, n_accept))
+        else
+            check(pop.ctx, GC.@preserve X y weights lossv ok history n_accept ccall(
+                (:de_fit_consts_lbfgs, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{LbfgsOpts},
+                 Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_accept))
+        end
     end
     constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
     return constants, lossv, ok .!= 0x00, history, n_accept
@@ -1194,7 +1243,7 @@ struct NmOpts               # de_nm_opts_t
 end
 
 """
-    fit_population_constants_nm!(pop, X, y; weights=nothing, iters=200, a=0.025, b=0.5, f_tol=0.0, loss=:L2, loss_param=0.0)
+    fit_population_constants_nm!(pop, X, y; weights=nothing, iters=200, a=0.025, b=0.5, f_tol=0.0, loss=:L2, loss_param=0.0, scaled=false, tied=false)
         -> (constants::Vector{T}, loss::Vector{T}, ok, history::Matrix{Float64}, n_improve::Vector{Int32})
 
 Nelder-Mead on the constants of every tree at once, the whole loop in one library call (`de_fit_consts_nm`, DESIGN.md §4.4.13) — the
@@ -1204,7 +1253,8 @@ from the constants `pop` holds; `iters` counts rounds of one evaluation each, th
 included.  Afterwards `pop` holds the accepted constants, which are returned with their losses and flags; `history[:, r]` are the
 accepted losses after `r - 1` rounds and never increase; `n_improve` counts the rounds that lowered them.  Trees that are incomplete at
 the start, have no constants or more than `de_nm_max_rows()` = 32 keep their constants.  A population with a shared GraphNode constant is
-refused (the library moves every occurrence on its own).
+refused (the library moves every occurrence on its own) unless `tied=true` (`de_fit_consts_nm_tied`, DESIGN.md §4.4.16): ask and tell then
+work on the unique constants, which are fanned out to their slots before every install; not with `scaled`.
 `scaled=true` (`de_fit_consts_nm_scaled`, DESIGN.md §4.4.14; `loss=:L2` only) fits under Keijzer's linear scaling `a + b ŷ`: every evaluation is
 `de_eval_fit_stats`, the objective `scaled_sse = m2_y - cov² / m2_p` in Float64.  It returns
 `(constants, scaled_sse::Vector{Float64}, ok, history, n_improve, stats)` with `stats` the NamedTuple of `fit_population_constants_lm!(scaled=true)`
@@ -1213,14 +1263,15 @@ at the accepted constants.
 function fit_population_constants_nm!(
     pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
     iters::Integer=200, a::Real=0.025, b::Real=0.5, f_tol::Real=0.0, loss::Symbol=:L2, loss_param::Real=0.0,
-    scaled::Bool=false,
+    scaled::Bool=false, tied::Bool=false,
 ) where {T}
+    tied && scaled && throw(ArgumentError("fit_population_constants_nm!(tied=true): the scaled fit is not served under ties"))
     scaled && loss !== :L2 && throw(ArgumentError("fit_population_constants_nm!(scaled=true) minimises the L2 residual under linear scaling: loss $loss is not supported"))
     loss === :pullback && throw(ArgumentError("fit_population_constants_nm!: :pullback is the cotangent of a pullback, not an objective"))
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
     @assert weights === nothing || length(weights) == N
-    any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_nm!: shared GraphNode constants need the host loop"))
+    !tied && any(o -> o !== nothing, pop.occ) && throw(ArgumentError("fit_population_constants_nm!: shared GraphNode constants need tied=true or the host loop"))
     opts = Ref(NmOpts(Int32(iters), Int32(0), Float64(a), Float64(b), Float64(f_tol)))
     if scaled
         sse = Vector{Float64}(undef, pop.n_trees)
@@ -1247,11 +1298,20 @@ function fit_population_constants_nm!(
     n_improve = zeros(Int32, pop.n_trees)
     with_pop(pop) do hc, hp
         wp = weights === nothing ? C_NULL : pointer(weights)
-        check(pop.ctx, GC.@preserve X y weights lossv ok history n_improve ccall(
-            (:de_fit_consts_nm, LIBDE), Cint,
-            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{NmOpts},
-             Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-            hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_improve))
+        if tied
+            tie = tie_map(pop)
+            check(pop.ctx, GC.@preserve X y weights tie lossv ok history n_improve ccall(
+                (:de_fit_consts_nm_tied, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{NmOpts},
+                 Ptr{Int32}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, tie === nothing ? C_NULL : pointer(tie), lossv, ok, history, n_improve))
+        else
+            check(pop.ctx, GC.@preserve X y weights lossv ok history n_improve ccall(
+                (:de_fit_consts_nm, LIBDE), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{LossSpec}, Ref{NmOpts},
+                 Ptr{Cvoid}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                hc, hp, X, N, F, C_NULL, y, wp, spec, opts, lossv, ok, history, n_improve))
+        end
     end
     constants = get_population_constants!(Vector{T}(undef, sum(pop.n_consts)), pop)
     return constants, lossv, ok .!= 0x00, history, n_improve

@@ -107,7 +107,10 @@ extern "C" {
  *      linear scaling (the objective scaled_sse, in double); every entry point above keeps its bits.
  *      (s) de_lbfgs_max_rows, de_lbfgs_max_memory, de_fit_consts_lbfgs, de_fit_tree_params_lbfgs (with de_lbfgs_opts_t) and the host-only
  *      hooks de_lbfgs_direction_host / de_lbfgs_update_host: L-BFGS for trees of up to 4096 unknowns, the two BFGS fits' contracts with
- *      a ring of (s, yv) pairs per tree instead of B; every entry point above keeps its bits. */
+ *      a ring of (s, yv) pairs per tree instead of B; every entry point above keeps its bits.
+ *      (t) de_fit_consts_bfgs_tied, de_fit_consts_lbfgs_tied, de_fit_consts_nm_tied, de_fit_consts_lm_tied and the host-only hooks
+ *      de_ties_pack_host / de_ties_unpack_host / de_ties_fold_host / de_ties_fold_matrix_host: the device fits with a shared GraphNode
+ *      constant as ONE unknown, for programs made by de_program_create_cse; every entry point above keeps its bits. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -1148,6 +1151,54 @@ int de_fit_consts_lbfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_
 int de_fit_tree_params_lbfgs(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_tree_params_t *tp,
                              const void *y, const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, void *params_out,
                              void *loss, uint8_t *ok, double *history, int32_t *n_accept);
+
+/* ---- tied device fits: a shared GraphNode constant is ONE unknown -------------------------------
+ * The library keeps one constant slot and one gradient row per OCCURRENCE of a shared constant (de_program_create_cse), the reference
+ * one coordinate per constant (count_constant_nodes and the shared NodeIndex entry, src/NodeUtils.jl:43-51, 184-201).  The calls below
+ * are the four device fits with the optimiser kernels running unchanged on vectors of UNIQUE constants; small pack / unpack / fold
+ * kernels (csrc/de_ties.hip) sit around every evaluation, whose kernels are unchanged too.
+ *
+ * tie (host): one int32 per constant slot of the program, in de_program_set_consts order — the 0-based index of the slot's unique
+ * constant within its tree, in first-occurrence order (a tree's first slot has id 0, every new id is the largest id before it + 1).
+ * U_t = max + 1 unknowns, S_t slots.  NULL: the identity.  In the program's element type T, every sum from +0 in ascending slot order
+ * (np.add.at into zeros: a lone -0 row becomes +0):
+ *   pack         unique[u] = slots[first slot of u]          (bits: NaN payloads and -0 stay)
+ *   unpack       slots[s] = unique[tie[s]]                   (bits)
+ *   fold         g_u = sum_{s : tie[s] = u} g_s
+ *   fold_matrix  half[u][k] = sum_{s in u} H[s][k], Hu[u][v] = sum_{k in v} half[u][k]      (S H S^T, rows first; column-major blocks)
+ * de_ties_*_host: ONE tree on host buffers of `dtype` (no HIP call, no program; csrc/de_ties.h, the code the kernels run — the same
+ * bits).  in -> out: pack slots[n_slots] -> unique[U]; unpack unique[U] -> slots[n_slots]; fold g[n_slots] -> g_unique[U]; fold_matrix
+ * H[n_slots^2] -> Hu[U^2].  Each returns U; -1 with nothing written for a null pointer, a dtype other than DE_F32 / DE_F64, n_slots < 0
+ * or a map that is not in first-occurrence order.
+ *
+ * de_fit_consts_{bfgs,lbfgs,nm}_tied: the untied twin's signature with `tie` before the outputs; de_fit_consts_lm_tied:
+ * de_fit_consts_lm_ex's, serving every kind de_gn_spec_check admits.  The twin's contract, except:
+ *   - n_grad, the offsets and the optimiser state are those of the unique constants: BFGS and Nelder-Mead fit a tree with 1 <= U_t <= 32
+ *     (S_t may be larger), L-BFGS 1 <= U_t <= de_lbfgs_max_rows(), Levenberg-Marquardt a tree whose occurrence block
+ *     de_eval_loss_gn_ex forms (S_t <= de_gn_max_rows()); any other tree keeps its first occurrences' bits.
+ *   - the fit starts from pack of the program's constants (the first occurrence decides); where the loop ran, every slot s of every
+ *     tree holds the bits of unique[tie[s]] afterwards.  iters == 0, N == 0 or no constants: nothing is written to the program.
+ *   - tie == NULL on a program NOT made by de_program_create_cse: the untied twin bit for bit.
+ *   - a program made by de_program_create_cse is served; refused in addition, before any output or constant is touched:
+ *     DE_ERR_INVALID_ARG (the text names the tree) for a map with a negative id or out of first-occurrence order.
+ * Afterwards de_eval_loss_grad_ex (BFGS), de_eval_loss_ex (L-BFGS, Nelder-Mead) or de_eval_loss_gn_ex (LM) reproduces loss[t] bit for bit.
+ * Not served: the scaled fits, de_fit_consts_lm_wide and the per-tree parameter fits under ties. */
+int de_ties_pack_host(int dtype, int32_t n_slots, const int32_t *tie, const void *slots, void *unique);
+int de_ties_unpack_host(int dtype, int32_t n_slots, const int32_t *tie, const void *unique, void *slots);
+int de_ties_fold_host(int dtype, int32_t n_slots, const int32_t *tie, const void *g, void *g_unique);
+int de_ties_fold_matrix_host(int dtype, int32_t n_slots, const int32_t *tie, const void *H, void *Hu);
+int de_fit_consts_bfgs_tied(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                            const void *y, const void *w, const de_loss_spec_t *spec, const de_bfgs_opts_t *opts, const int32_t *tie,
+                            void *loss, uint8_t *ok, double *history, int32_t *n_accept);
+int de_fit_consts_lbfgs_tied(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                             const void *y, const void *w, const de_loss_spec_t *spec, const de_lbfgs_opts_t *opts, const int32_t *tie,
+                             void *loss, uint8_t *ok, double *history, int32_t *n_accept);
+int de_fit_consts_nm_tied(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                          const void *y, const void *w, const de_loss_spec_t *spec, const de_nm_opts_t *opts, const int32_t *tie, void *loss,
+                          uint8_t *ok, double *history, int32_t *n_improve);
+int de_fit_consts_lm_tied(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pargs,
+                          const void *y, const void *w, const de_loss_spec_t *spec, double e_floor, const de_lm_opts_t *opts,
+                          const int32_t *tie, void *loss, uint8_t *ok, double *history, int32_t *n_accept);
 
 /* The `dX` of the ChainRules pullback of eval_tree_array (EvalPullback, src/ChainRules.jl:56-77):
  *   dX_t[f, j] = d tree_t(x_j) / d x_f * dY[j]      (`dX = dX_dY .* reshape(dY, 1, length(dY))`, :74)
