@@ -41,6 +41,7 @@ COMPLEX_DTYPES = (np.dtype(np.complex64), np.dtype(np.complex128))
 GRAD_VARIABLE, GRAD_CONSTANT, GRAD_BOTH = 0, 1, 2
 ABI_VERSION = 3  # DE_HIP_ABI_VERSION of include/de_hip.h this module was written for
 OPT_EARLY_EXIT, OPT_FUSE_DEG1, OPT_FUSE_DEG2, OPT_BUMPER_CHECKS, OPT_TURBO, OPT_FULL_EVAL, OPT_FORWARD_GRAD, OPT_REVERSE_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
+OPT_F16_GRAD = 1 << 8  # DE_OPT_F16_GRAD (include/de_hip.h): Float16 populations serve eval_grad / eval_diff
 
 EXPORTS = [
     "de_abi_version", "de_opcode_table_version", "de_opcode_by_name", "de_opcode_name",
@@ -1141,13 +1142,16 @@ class EvalContext:
     # lists the trees whose element-wise flag is NOT provably the reference's isfinite(sum(x)) flag (src/ValueInterface.jl:9) — the only
     # trees a caller who needs the reference's bit has to re-derive on the CPU; the one-tree sugar raises UncertifiedFlag for such a tree
     strict_flags: bool = False
+    # half_grad: DE_OPT_F16_GRAD — a Float16 population made with it serves eval_grad / eval_diff in binary16 steps;
+    # every other element type ignores it, and without it Float16 stays evaluation only
+    half_grad: bool = False
 
     def option_bits(self, operators: OperatorEnum) -> int:
         f1, f2 = operators.fuse_flags(self.use_fused)
         return ((OPT_EARLY_EXIT if self.early_exit else 0) | (OPT_FUSE_DEG1 if f1 else 0) |
                 (OPT_FUSE_DEG2 if f2 else 0) | (OPT_BUMPER_CHECKS if self.bumper else 0) | (OPT_TURBO if self.turbo else 0) |
                 (OPT_FULL_EVAL if self.full_eval else 0) | (OPT_FORWARD_GRAD if self.forward_grad else 0) |
-                (OPT_REVERSE_GRAD if self.reverse_grad else 0))
+                (OPT_REVERSE_GRAD if self.reverse_grad else 0) | (OPT_F16_GRAD if self.half_grad else 0))
 
 
 class Context:
@@ -1730,10 +1734,11 @@ class Population:
         keep.extend([params, classes])
         return pa
 
-    def _refuse_f16(self, what: str) -> None:
+    def _refuse_f16(self, what: str, half_grad: bool = False) -> None:
         # Float16 and complex populations evaluate only (eval, sum_certificate): the library answers DE_ERR_UNSUPPORTED for their gradient
-        # and loss entry points, said here before any buffer is prepared
-        if self.dtype == np.float16:
+        # and loss entry points, said here before any buffer is prepared.  half_grad: eval_grad / eval_diff, which a Float16 population
+        # made with EvalContext(half_grad=True) serves (DE_OPT_F16_GRAD)
+        if self.dtype == np.float16 and not (half_grad and self.eval_context.half_grad):
             name = library().de_status_string(7).decode()
             raise DeviceError(f"{name}: {what} of a Float16 population (DE_ERR_UNSUPPORTED): Float16 is evaluation only")
         if self.dtype in COMPLEX_DTYPES:
@@ -2696,7 +2701,7 @@ class Population:
         """All trees' forward-mode gradients.  Returns (out[n_trees,N], grads, ok) where
         grads is a list of per-tree [n_grad_t, N] Fortran-ordered arrays (views of one
         packed buffer)."""
-        self._refuse_f16("eval_grad")
+        self._refuse_f16("eval_grad", half_grad=True)
         mode = _grad_mode(variable)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
@@ -2763,7 +2768,7 @@ class Population:
 
     def eval_diff(self, X, direction: int):
         """``direction`` is the 1-based feature index, as in the reference."""
-        self._refuse_f16("eval_diff")
+        self._refuse_f16("eval_diff", half_grad=True)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()

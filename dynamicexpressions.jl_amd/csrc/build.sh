@@ -118,6 +118,7 @@ build_obj de_grad_kernels.hip $OBJ/de_grad_kernels.o &
 # the flat-switch interpreter (de_flat.h), one translation unit per value policy: plain hipcc, none of the IR / assembly passes (no handler in them)
 build_obj de_flat_real.hip $OBJ/de_flat_real.o & # Float32 / Float64
 build_obj de_half.hip $OBJ/de_half.o &           # binary16 (DE_F16)
+build_obj de_half_grad.hip $OBJ/de_half_grad.o & # binary16 forward-mode gradients (DE_OPT_F16_GRAD): plain hipcc too
 build_obj de_complex.hip $OBJ/de_complex.o &     # complex (DE_CF32 / DE_CF64)
 # de_program_set_consts_device: the gather / scatter / flag kernels (plain hipcc too)
 build_obj de_const_patch.hip $OBJ/de_const_patch.o &
@@ -144,6 +145,6 @@ build_obj de_tree_params.hip $OBJ/de_tree_params.o &
 build_obj de_ties.hip $OBJ/de_ties.o &
 wait
 API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_program_stream.o $OBJ/de_api_program_consts.o $OBJ/de_api_program_inspect.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS -ldl
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

@@ -342,7 +342,8 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
     if (rc != DE_OK) return rc;
     if (p->n_trees == 0) return DE_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t es = p->dtype == DE_F32 ? 4 : 8;
+    const bool half = p->io == DE_F16; // (a program with DE_OPT_F16_GRAD: de_half_grad.hip, binary16 buffers)
+    const size_t es = dtype_bytes(p->io);
     const bool ok_dev = is_device_ptr(ok);
     std::vector<uint8_t> ones;
     if (N == 0 && !diff) { // (the flags alone: from the host side, §3.5)
@@ -376,7 +377,9 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         run += (int64_t)g * N;
         span = std::max(span, off + (int64_t)g * N);
     }
-    const size_t lds_need = ((size_t)p->n_features + (size_t)p->n_slots * (1 + (size_t)std::min(maxg, 8))) * 260 * es;
+    // (the kernel's real row size: the binary16 kernel's LDS rows are Float32, and its window is one of 1 .. 6, 8)
+    const size_t lds_need = half ? grad_f16_lds_bytes(p->n_features, p->n_slots, maxg <= 6 ? std::max(maxg, 1) : 8)
+                                 : ((size_t)p->n_features + (size_t)p->n_slots * (1 + (size_t)std::min(maxg, 8))) * 260 * es;
     if (lds_need > 160 * 1024) return fail(c, DE_ERR_UNSUPPORTED, "gradient kernel: LDS footprint too large for this tree shape");
     rc = ensure_generic_code(c, p);
     if (rc) return rc;
@@ -449,9 +452,10 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
     g.e.code_off = nullptr;
     g.e.n_trees = (int32_t)p->n_trees;
     g.e.skip_flagged = !(p->options & DE_OPT_FULL_EVAL) && tree_skip_enabled(); // (the gradient entry points always test validity)
-    if (c->sPrio.reserve((size_t)3 * DE_PRIO_MAX_F * sizeof(unsigned long long)) == hipSuccess) g.e.prio_keys = c->sPrio.p; // priority tiles (de_kernels.hip)
+    // (a binary16 program runs neither the priority tiles nor a declared dataset's keys)
+    if (!half && c->sPrio.reserve((size_t)3 * DE_PRIO_MAX_F * sizeof(unsigned long long)) == hipSuccess) g.e.prio_keys = c->sPrio.p; // priority tiles (de_kernels.hip)
     g.prio_ready = false;
-    g.e.prio_keys_ready = !sX.staged && g.e.prio_keys && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &g.e.prio_keys);
+    g.e.prio_keys_ready = !half && !sX.staged && g.e.prio_keys && dataset_keys(c, p->dtype, X, N, ldX, p->n_features, &g.e.prio_keys);
     g.e.n_slots = p->n_slots;
     g.e.uses_params = p->uses_params;
     g.e.X = sX.dev;
@@ -477,7 +481,7 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
     g.max_grad = maxg;
     g.diff_direction = diff ? diff_direction : -1;
     g.e.code_off = p->d_gcode_off;
-    if (!diff) {
+    if (!diff && !half) { // (binary16: the flat-switch dual kernel alone)
         rc = ensure_grad_threaded(c, p, mode, ng, N, &g);
         if (rc) return rc;
     }
@@ -487,7 +491,8 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         if (rc) return rc;
     }
     if (!c->nested) HIP_TRY(c, time_begin(c));
-    HIP_TRY(c, launch_grad(p->dtype, g, c->stream, &c->last_kernel));
+    if (half) HIP_TRY(c, launch_grad_f16(g, c->stream, &c->last_kernel));
+    else HIP_TRY(c, launch_grad(p->dtype, g, c->stream, &c->last_kernel));
     if (dY) // the pullback's dX .* dY' (and its NaN fill) on the Jacobians just written
         HIP_TRY(c, launch_pullback_scale(p->dtype, sGrad.dev, g.grad_off, g.n_grad, g.e.ok, sDY.dev, N, p->n_trees, maxg, c->stream));
     if (!c->nested) HIP_TRY(c, time_end(c));
@@ -523,7 +528,8 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
             okp = okh.data();
         }
         auto fill = [&](void *base, size_t off, size_t n) {
-            if (p->dtype == DE_F32) std::fill_n(static_cast<float *>(base) + off, n, std::nanf(""));
+            if (half) std::fill_n(static_cast<_Float16 *>(base) + off, n, (_Float16)std::nanf(""));
+            else if (p->dtype == DE_F32) std::fill_n(static_cast<float *>(base) + off, n, std::nanf(""));
             else std::fill_n(static_cast<double *>(base) + off, n, std::nan(""));
         };
         for (int64_t t = 0; t < p->n_trees; t++) {
@@ -564,7 +570,8 @@ const char *gn_spec_problem(const de_loss_spec_t *spec, double e_floor, int dtyp
     }
     return nullptr;
 }
-// DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output.
+// DE_F16 programs evaluate only: every gradient / fused-loss entry point refuses them before it touches an output —
+// but de_eval_grad and de_eval_diff serve a program created with DE_OPT_F16_GRAD (DE_REFUSE_F16_NO_GRAD).
 int refuse_f16(de_ctx_t *c, const de_program_t *p, const char *what) {
     return fail(c, DE_ERR_UNSUPPORTED, "%s: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate); no binary16 gradients or losses", what);
 }
@@ -1075,7 +1082,7 @@ static int by_class_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N,
 
 int de_eval_grad(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                  int mode, void *out, int64_t ld_out, void *grad, const int64_t *grad_offsets, uint8_t *ok) {
-    DE_REFUSE_F16("de_eval_grad");
+    DE_REFUSE_F16_NO_GRAD("de_eval_grad");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, pa, mode, -1, out, ld_out, grad, grad_offsets, ok));
 }
 
@@ -1088,7 +1095,7 @@ int de_eval_pullback_dX(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, 
 
 int de_eval_diff(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, int32_t direction, void *out,
                  void *dout, int64_t ld_out, uint8_t *ok) {
-    DE_REFUSE_F16("de_eval_diff");
+    DE_REFUSE_F16_NO_GRAD("de_eval_diff");
     if (direction < 0) return fail(c, DE_ERR_INVALID_ARG, "direction < 0");
     if (p && p->uses_params) return fail(c, DE_ERR_UNSUPPORTED, "eval_diff on parametric trees");
     DE_NOTHROW(c, grad_impl(c, p, X, N, ldX, nullptr, DE_GRAD_VARIABLE, direction, out, ld_out, dout, nullptr, ok));

@@ -475,6 +475,12 @@ int refuse_complex(de_ctx_t *c, const char *what);
         if (c && p && p->io == DE_F16) return refuse_f16(c, p, WHAT);      \
         if (c && p && is_complex_io(p->io)) return refuse_complex(c, WHAT); \
     } while (0)
+// de_eval_grad and de_eval_diff alone: a DE_F16 program created with DE_OPT_F16_GRAD passes
+#define DE_REFUSE_F16_NO_GRAD(WHAT)                                                                                  \
+    do {                                                                                                             \
+        if (c && p && p->io == DE_F16 && !(p->options & DE_OPT_F16_GRAD)) return refuse_f16(c, p, WHAT);            \
+        if (c && p && is_complex_io(p->io)) return refuse_complex(c, WHAT);                                          \
+    } while (0)
 
 // de_loss_spec_check with its reason (de_api.cpp): null = the spec is good, else a text that names the kind (`buf` holds it)
 const char *loss_spec_problem(const de_loss_spec_t *spec, int with_gradient, char *buf, size_t cap);

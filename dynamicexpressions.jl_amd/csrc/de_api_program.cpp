@@ -626,7 +626,11 @@ static int create_phases(de_ctx *ctx, de_program *p, const Population &in, const
     p->const_checks.assign(total_consts, 0);
     if (cplx) p->consts_im.resize(total_consts);
     Units us{reuse, {}, {}};
-    if (!lower_units(in, lower_options(p->options, p->n_features, p->n_params, p->dtype), p->allow_fold, env, &us)) return fail(ctx, DE_ERR_HIP, "out of host memory");
+    // A DE_F16 program with DE_OPT_F16_GRAD lowers its GENERIC (gradient) program from the expanded tape, as DE_NO_GRAD_CSE=1 does: every
+    // occurrence of a shared constant keeps a row that holds its own partial.  The eval program keeps its CSE lowering.
+    CreateEnv lenv = env;
+    if (p->io == DE_F16 && (p->options & DE_OPT_F16_GRAD)) lenv.grad_cse = false;
+    if (!lower_units(in, lower_options(p->options, p->n_features, p->n_params, p->dtype), p->allow_fold, lenv, &us)) return fail(ctx, DE_ERR_HIP, "out of host memory");
     tm.lap("lower (host threads)");
     if (const int rc = link_generic(ctx, p, in, us, keep_input)) return rc;
     tm.lap("merge plain");

@@ -34,6 +34,7 @@ const DE_OP_SHARE = UInt8(0xFE)   # include/de_opcodes.h: "the subtree just emit
 const DE_F32, DE_F64, DE_F16, DE_CF32, DE_CF64 = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
 const DE_OPT_EARLY_EXIT, DE_OPT_FUSE_DEG1, DE_OPT_FUSE_DEG2, DE_OPT_BUMPER_CHECKS, DE_OPT_TURBO, DE_OPT_FULL_EVAL, DE_OPT_FORWARD_GRAD, DE_OPT_REVERSE_GRAD =
     UInt32(1), UInt32(2), UInt32(4), UInt32(8), UInt32(16), UInt32(32), UInt32(64), UInt32(128)
+const DE_OPT_F16_GRAD = UInt32(256)   # a Float16 program with it serves de_eval_grad / de_eval_diff (DESIGN.md §13.6)
 # The ABI this file was written for (include/de_hip.h lists what changed between versions).  Version 2: the rows / gradients of a tree
 # with `complete == false` are NOT evaluated to the end (the reference's early exit, src/Evaluate.jl:26-32): with the host arrays this
 # shim passes, the library NaN-fills them; `full_eval=true` (DE_OPT_FULL_EVAL) evaluates every tree on every sample instead.
@@ -51,8 +52,8 @@ end
 const OPERATOR_LIMIT_BEFORE_SLOWDOWN = 15   # src/Evaluate.jl:14
 dtype_code(::Type{Float32}) = DE_F32
 dtype_code(::Type{Float64}) = DE_F64
-# Float16: evaluation only (every operator step rounded to binary16, DESIGN.md §13); the gradient methods below stay
-# Float32 / Float64, so a Float16 gradient keeps the reference CPU path
+# Float16: every operator step rounded to binary16 (DESIGN.md §13).  eval_grad_tree_array / eval_diff_tree_array create their program
+# with DE_OPT_F16_GRAD (binary16 duals, DESIGN.md §13.6); losses, pullbacks and fits stay Float32 / Float64 and keep the reference CPU path
 dtype_code(::Type{Float16}) = DE_F16
 # ComplexF32 / ComplexF64: evaluation only (Julia's Complex methods of 19 opcodes, DESIGN.md §14); a tree with another operator and every
 # complex gradient keep the reference CPU path
@@ -154,7 +155,7 @@ function opcode_table(operators::OperatorEnum)
 end
 
 """EvalContext knobs that change RESULTS -> de_options bits (src/Evaluate.jl:156-181,496,607)."""
-function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=false, forward_grad::Bool=false, reverse_grad::Bool=false)
+function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=false, forward_grad::Bool=false, reverse_grad::Bool=false, half_grad::Bool=false)
     nops(d) = d <= length(operators.ops) ? length(operators.ops[d]) : 0
     fused = ctx.use_fused isa Val{true}
     bits = UInt32(0)
@@ -165,6 +166,7 @@ function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=
     ctx.turbo isa Val{true} && (bits |= DE_OPT_TURBO)   # the LoopVectorization knob = the relaxed-accuracy device operators
     full_eval && (bits |= DE_OPT_FULL_EVAL)             # no early exit at tree granularity: rows of incomplete trees are fully evaluated
     forward_grad && (bits |= DE_OPT_FORWARD_GRAD)       # ABI 2's spelling of what is the default since ABI 3: fused loss gradients by forward duals (the reference's flag semantics exactly)
+    half_grad && (bits |= DE_OPT_F16_GRAD)              # Float16 programs: de_eval_grad / de_eval_diff in binary16 steps (other element types ignore it)
     reverse_grad && (bits |= DE_OPT_REVERSE_GRAD)       # permission for reverse accumulation (faster from 8 gradient rows per tree on; `ok` may differ in ~0.03 % of Float32 cases)
     return bits
 end
@@ -391,7 +393,7 @@ end
 function HIPPopulation(
     trees::AbstractVector{<:AbstractExpressionNode{T}}, operators::OperatorEnum, n_features::Integer;
     eval_context::EvalContext=EvalContext(), n_params::Integer=0, full_eval::Bool=false, forward_grad::Bool=false,
-    reverse_grad::Bool=false,
+    reverse_grad::Bool=false, half_grad::Bool=false,
 ) where {T<:Union{Float16,Float32,Float64,ComplexF32,ComplexF64}}
     optable = opcode_table(operators)
     nodes, consts, cse = TapeNode[], T[], TapeNode[]
@@ -422,7 +424,7 @@ function HIPPopulation(
             (Ptr{Cvoid}, Cint, Ptr{TapeNode}, Ptr{Int64}, Ptr{TapeNode}, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int32, Int32,
              UInt32, Ref{Ptr{Cvoid}}),
             hc, dtype_code(T), nodes, node_off, isempty(cse) ? C_NULL : pointer(cse), cse_off, length(trees), consts,
-            const_off, n_features, n_params, option_bits(operators, eval_context; full_eval, forward_grad, reverse_grad), h))
+            const_off, n_features, n_params, option_bits(operators, eval_context; full_eval, forward_grad, reverse_grad, half_grad), h))
     end
     pop = HIPPopulation{T}(ctx, h[], length(trees), n_features, occ, n_slots, n_consts, optable)
     finalizer(finalize_population, pop)
@@ -1651,10 +1653,10 @@ end
 ONE row (the sum over its occurrences)."""
 function _hip_eval_grad_tree_array(
     tree::AbstractExpressionNode{T}, cX::Matrix{T}, operators::OperatorEnum; variable=Val(false)
-) where {T<:Union{Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64}}
     mode = grad_mode(variable)
     F, N = size(cX)
-    pop = HIPPopulation([tree], operators, F)
+    pop = HIPPopulation([tree], operators, F; half_grad=(T === Float16))
     out = Vector{T}(undef, N)
     ok = Ref{UInt8}(0)
     grad = with_pop(pop) do hc, hp
@@ -1675,10 +1677,10 @@ end
 1-based feature, `complete` is always true on this path as in the reference, :68-119)."""
 function _hip_eval_diff_tree_array(
     tree::AbstractExpressionNode{T}, cX::Matrix{T}, operators::OperatorEnum, direction::Integer
-) where {T<:Union{Float32,Float64}}
+) where {T<:Union{Float16,Float32,Float64}}
     F, N = size(cX)
     1 <= direction <= F || throw(ArgumentError("direction must be a feature of cX"))
-    pop = HIPPopulation([tree], operators, F)
+    pop = HIPPopulation([tree], operators, F; half_grad=(T === Float16))
     out = Vector{T}(undef, N)
     dout = Vector{T}(undef, N)
     ok = Ref{UInt8}(0)

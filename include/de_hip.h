@@ -110,7 +110,9 @@ extern "C" {
  *      a ring of (s, yv) pairs per tree instead of B; every entry point above keeps its bits.
  *      (t) de_fit_consts_bfgs_tied, de_fit_consts_lbfgs_tied, de_fit_consts_nm_tied, de_fit_consts_lm_tied and the host-only hooks
  *      de_ties_pack_host / de_ties_unpack_host / de_ties_fold_host / de_ties_fold_matrix_host: the device fits with a shared GraphNode
- *      constant as ONE unknown, for programs made by de_program_create_cse; every entry point above keeps its bits. */
+ *      constant as ONE unknown, for programs made by de_program_create_cse; every entry point above keeps its bits.
+ *      (u) DE_OPT_F16_GRAD (new option bit 8): a DE_F16 program created with it is served by de_eval_grad and de_eval_diff, in binary16
+ *      steps; without the bit, and for every other dtype, nothing changes. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -127,7 +129,8 @@ typedef enum de_status {
 
 /* DE_F16: binary16 elements (2 bytes) everywhere the dtype sizes a buffer; computed in Float32 registers and rounded to binary16 after
  * every operator step.  Evaluation only: de_eval_grad / _diff / _pullback_dX, de_eval_loss(_grad, _grad_by_class) and
- * de_ctx_declare_dataset return DE_ERR_UNSUPPORTED for an F16 program or dtype and leave their outputs untouched.  F16 programs never
+ * de_ctx_declare_dataset return DE_ERR_UNSUPPORTED for an F16 program or dtype and leave their outputs untouched — except that a program
+ * created with DE_OPT_F16_GRAD is served by de_eval_grad and de_eval_diff (binary16 X, constants, parameters, out and grad).  F16 programs never
  * run the threaded kernel (de_eval_plan / de_program_dump report the flat-switch kernel's form); a feature matrix too wide for its LDS
  * tile is gathered from global memory as for Float32.  de_eval_sum_certificate refuses such wide programs for every dtype. */
 /* DE_CF32 / DE_CF64: complex elements, (re, im) interleaved — 8 bytes (numpy complex64, Julia ComplexF32) / 16 bytes (complex128,
@@ -195,6 +198,14 @@ enum de_options {
      * `ok` (~0.03 % of Float32 fuzz cases, never seen in Float64).  Without the bit (the default since ABI 3, VERDICT r5
      * item 4) every fused loss gradient runs forward duals: the reference's flag semantics exactly. */
     DE_OPT_REVERSE_GRAD = 1u << 7,
+    /* Float16 forward-mode gradients.  Means something for dtype == DE_F16 only, every other dtype ignores it.  A
+     * DE_F16 program created with it (de_program_create, de_program_create_cse; de_program_update keeps a program's options) is served
+     * by de_eval_grad — all three modes, with or without `out`, packed or caller-supplied grad_offsets, host or device pointers — and by
+     * de_eval_diff: Julia's Float16 arithmetic through grad_degn_eval, every value, partial and chain-rule operation rounded to binary16.
+     * X, the constants, the parameters, out and grad are binary16; offsets and ld_out count binary16 elements.  Every other entry point
+     * that refuses DE_F16 keeps refusing it, with the same text.  The gradient program of a de_program_create_cse program with the bit
+     * is lowered from the EXPANDED tape: every occurrence of a shared constant has a row of its own that holds its own partial. */
+    DE_OPT_F16_GRAD = 1u << 8,
     DE_OPT_DEFAULT = (1u << 0) | (1u << 1) | (1u << 2)
 };
 
