@@ -42,6 +42,7 @@ GRAD_VARIABLE, GRAD_CONSTANT, GRAD_BOTH = 0, 1, 2
 ABI_VERSION = 3  # DE_HIP_ABI_VERSION of include/de_hip.h this module was written for
 OPT_EARLY_EXIT, OPT_FUSE_DEG1, OPT_FUSE_DEG2, OPT_BUMPER_CHECKS, OPT_TURBO, OPT_FULL_EVAL, OPT_FORWARD_GRAD, OPT_REVERSE_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
 OPT_F16_GRAD = 1 << 8  # DE_OPT_F16_GRAD (include/de_hip.h): Float16 populations serve eval_grad / eval_diff
+OPT_TYPED_LOSS = 1 << 9  # DE_OPT_TYPED_LOSS: Float16 and complex populations serve eval_loss (L2 / L1)
 
 EXPORTS = [
     "de_abi_version", "de_opcode_table_version", "de_opcode_by_name", "de_opcode_name",
@@ -1145,13 +1146,17 @@ class EvalContext:
     # half_grad: DE_OPT_F16_GRAD — a Float16 population made with it serves eval_grad / eval_diff in binary16 steps;
     # every other element type ignores it, and without it Float16 stays evaluation only
     half_grad: bool = False
+    # typed_loss: DE_OPT_TYPED_LOSS — a Float16 or complex population made with it serves eval_loss ("L2" / "L1");
+    # Float32 / Float64 ignore it, and without it Float16 and complex stay evaluation only
+    typed_loss: bool = False
 
     def option_bits(self, operators: OperatorEnum) -> int:
         f1, f2 = operators.fuse_flags(self.use_fused)
         return ((OPT_EARLY_EXIT if self.early_exit else 0) | (OPT_FUSE_DEG1 if f1 else 0) |
                 (OPT_FUSE_DEG2 if f2 else 0) | (OPT_BUMPER_CHECKS if self.bumper else 0) | (OPT_TURBO if self.turbo else 0) |
                 (OPT_FULL_EVAL if self.full_eval else 0) | (OPT_FORWARD_GRAD if self.forward_grad else 0) |
-                (OPT_REVERSE_GRAD if self.reverse_grad else 0) | (OPT_F16_GRAD if self.half_grad else 0))
+                (OPT_REVERSE_GRAD if self.reverse_grad else 0) | (OPT_F16_GRAD if self.half_grad else 0) |
+                (OPT_TYPED_LOSS if self.typed_loss else 0))
 
 
 class Context:
@@ -1734,10 +1739,13 @@ class Population:
         keep.extend([params, classes])
         return pa
 
-    def _refuse_f16(self, what: str, half_grad: bool = False) -> None:
+    def _refuse_f16(self, what: str, half_grad: bool = False, typed_loss: bool = False) -> None:
         # Float16 and complex populations evaluate only (eval, sum_certificate): the library answers DE_ERR_UNSUPPORTED for their gradient
         # and loss entry points, said here before any buffer is prepared.  half_grad: eval_grad / eval_diff, which a Float16 population
-        # made with EvalContext(half_grad=True) serves (DE_OPT_F16_GRAD)
+        # made with EvalContext(half_grad=True) serves (DE_OPT_F16_GRAD).  typed_loss: eval_loss, which a Float16 or complex population
+        # made with EvalContext(typed_loss=True) serves (DE_OPT_TYPED_LOSS)
+        if typed_loss and self.eval_context.typed_loss:
+            return
         if self.dtype == np.float16 and not (half_grad and self.eval_context.half_grad):
             name = library().de_status_string(7).decode()
             raise DeviceError(f"{name}: {what} of a Float16 population (DE_ERR_UNSUPPORTED): Float16 is evaluation only")
@@ -1806,9 +1814,25 @@ class Population:
         consumers compute right after eval_tree_array (``sum(abs2, tree(X, operators) .- y)``,
         test/test_optim.jl:95,99).  ``loss`` may also name a parameterised kind of ``LOSS_KINDS`` ("huber", "logcosh", "l1_eps", "l2_eps",
         "quantile", "lp", "logit_dist", "logit_margin", "l1_hinge"; include/de_hip.h de_loss_kind_t has the formulas) with its parameter
-        in ``loss_param``.  Returns (loss[n_trees], ok[n_trees]); loss is NaN where not ok."""
-        self._refuse_f16("eval_loss")
+        in ``loss_param``.  Returns (loss[n_trees], ok[n_trees]); loss is NaN where not ok.
+
+        Float16 and complex populations made with ``EvalContext(typed_loss=True)`` are served for "L2" and "L1" (DESIGN.md §4.4.17):
+        ``y`` is converted to the population's dtype and ``weights`` to its real component type; the losses are ``float32`` for
+        Float16 (binary16 terms, summed in Float32) and ``float32`` / ``float64`` for complex64 / complex128."""
+        self._refuse_f16("eval_loss", typed_loss=True)
         spec = loss_spec(loss, loss_param, with_gradient=False)
+        typed = self.dtype == np.float16 or self.dtype in COMPLEX_DTYPES
+        if typed and spec.kind not in (0, 1):  # (DE_LOSS_L2, DE_LOSS_L1) — said before any buffer is prepared, as the library does
+            name = library().de_status_string(7).decode()
+            raise DeviceError(f"{name}: eval_loss kind {loss!r} of a {np.dtype(self.dtype)} population (DE_ERR_UNSUPPORTED): "
+                              "Float16 and complex populations serve L2 and L1")
+        # element types of the buffers: y as the population, weights real, losses in the compute type (include/de_hip.h de_eval_loss)
+        w_dtype = np.dtype(self.dtype)
+        out_dtype = np.dtype(self.dtype)
+        if self.dtype in COMPLEX_DTYPES:
+            w_dtype = out_dtype = np.dtype(np.float32 if np.dtype(self.dtype) == np.complex64 else np.float64)
+        elif self.dtype == np.float16:
+            out_dtype = np.dtype(np.float32)
         ptr, F, N, ldX, keep_x, is_t = _prep_X(X, self.dtype)
         if is_t:
             self.ctx.use_torch_stream()
@@ -1818,31 +1842,31 @@ class Population:
         pa = self._param_args(params, classes, class_base, N, keep)
         lib = library()
 
-        def vec(v, name):
+        def vec(v, name, dt):
             if v is None:
                 return None
             if is_t:
                 import torch
-                v = torch.as_tensor(v, dtype=keep_x.dtype, device=keep_x.device).contiguous()
+                v = torch.as_tensor(v, dtype=_torch_dtype(dt), device=keep_x.device).contiguous()
                 if v.numel() != N:
                     raise ValueError(f"{name} must have {N} entries")
                 keep.append(v)
                 return v.data_ptr()
-            v = np.ascontiguousarray(v, dtype=self.dtype)
+            v = np.ascontiguousarray(v, dtype=dt)
             if v.size != N:
                 raise ValueError(f"{name} must have {N} entries")
             keep.append(v)
             return v.ctypes.data
 
-        yp, wp = vec(y, "y"), vec(weights, "weights")
+        yp, wp = vec(y, "y", np.dtype(self.dtype)), vec(weights, "weights", w_dtype)
         if is_t:
             import torch
-            out = torch.empty(self.n_trees, dtype=keep_x.dtype, device=keep_x.device)
+            out = torch.empty(self.n_trees, dtype=_torch_dtype(out_dtype), device=keep_x.device)
             ok = torch.empty(self.n_trees, dtype=torch.uint8, device=keep_x.device)
             self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
                                                yp, wp, C.byref(spec), out.data_ptr(), ok.data_ptr()))
             return out, ok.bool()
-        out = np.empty(self.n_trees, dtype=self.dtype)
+        out = np.empty(self.n_trees, dtype=out_dtype)
         ok = np.zeros(self.n_trees, dtype=np.uint8)
         self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
                                            yp, wp, C.byref(spec), out.ctypes.data, ok.ctypes.data))

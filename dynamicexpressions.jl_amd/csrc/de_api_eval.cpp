@@ -82,6 +82,14 @@ struct LossReq {
     double *stats = nullptr, *ystats = nullptr; // de_eval_fit_stats (kind == FIT_STATS_KIND, loss == null)
 };
 
+// de_eval_loss / de_eval_loss_ex: a DE_F16 / complex program passes only when it was created with DE_OPT_TYPED_LOSS
+static int refuse_untyped_loss(de_ctx *c, const de_program *p) {
+    if (p->options & DE_OPT_TYPED_LOSS) return DE_OK;
+    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
+    return DE_OK;
+}
+
 struct CertReq {
     uint8_t *certified; // host, n_trees
     double *max_abs;    // host, n_trees, or null
@@ -170,25 +178,23 @@ int de_eval(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX,
 int de_eval_loss(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                  const void *y, const void *w, int32_t loss_kind, void *loss, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
-    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (const int rc = refuse_untyped_loss(c, p)) return rc;
     if (N < 0 || !ok || (p->n_trees > 0 && (!loss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     if (loss_kind != DE_LOSS_L2 && loss_kind != DE_LOSS_L1) return fail(c, DE_ERR_INVALID_ARG, "unknown loss_kind %d", loss_kind);
-    if (!p->threaded)
-        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss needs the LDS-tiled kernel (feature matrix too wide for this build)");
     const de_loss_spec_t spec{loss_kind, 0, 0.0};
     return de_eval_loss_ex(c, p, X, N, ldX, pa, y, w, &spec, loss, ok);
 }
 int de_eval_loss_ex(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64_t ldX, const de_param_args_t *pa,
                     const void *y, const void *w, const de_loss_spec_t *spec, void *loss, uint8_t *ok) {
     if (!c || !p) return DE_ERR_INVALID_ARG;
-    if (p->io == DE_F16) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: DE_F16 programs evaluate only (de_eval, de_eval_sum_certificate)");
-    if (is_complex_io(p->io)) return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: complex programs evaluate only (de_eval, de_eval_sum_certificate)");
+    if (const int rc = refuse_untyped_loss(c, p)) return rc;
     if (N < 0 || !ok || (p->n_trees > 0 && (!loss || (N > 0 && (!X || !y))))) return fail(c, DE_ERR_INVALID_ARG, "null buffer");
     char why[160];
     if (loss_spec_problem(spec, 0, why, sizeof why)) return fail(c, DE_ERR_INVALID_ARG, "%s", why);
-    if (!p->threaded)
-        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss needs the LDS-tiled kernel (feature matrix too wide for this build)");
+    // Float16 and complex programs (DE_OPT_TYPED_LOSS): the two kinds whose term the reference's arithmetic of the type defines
+    if ((p->io == DE_F16 || is_complex_io(p->io)) && spec->kind != DE_LOSS_L2 && spec->kind != DE_LOSS_L1)
+        return fail(c, DE_ERR_UNSUPPORTED, "de_eval_loss: loss kind %d is not served for %s programs (DE_LOSS_L2 and DE_LOSS_L1 are)", (int)spec->kind,
+                    p->io == DE_F16 ? "DE_F16" : p->io == DE_CF32 ? "DE_CF32" : "DE_CF64");
     const LossReq lr{y, w, spec->kind, spec->param, loss};
     DE_NOTHROW(c, eval_impl(c, p, X, N, ldX, pa, nullptr, N, ok, &lr));
 }
@@ -240,7 +246,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
             HIP_TRY(c, hipMemcpy(lr->ystats, ys, sizeof ys, hipMemcpyDefault));
         } else
         if (lr) { // empty sum = 0; NaN where a constant already failed the flag
-            std::vector<unsigned char> z((size_t)p->n_trees * es);
+            std::vector<unsigned char> z((size_t)p->n_trees * ces); // (values of the compute type: Float32 for DE_F16, the component type of a complex program)
             for (int64_t t = 0; t < p->n_trees; t++) {
                 const double v = p->host_ok_eval[(size_t)t] ? 0.0 : std::nan("");
                 if (p->dtype == DE_F32) reinterpret_cast<float *>(z.data())[t] = (float)v;
@@ -261,13 +267,14 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     rc = stage_in(c, c->sX, X, (size_t)ldX * (size_t)N * es, &sX);
     if (rc) return rc;
     if (lr) {
+        // y: elements of the program; w: real — the component type of a complex program; loss: the compute type (Float32 for DE_F16)
         rc = stage_in(c, c->sY, lr->y, (size_t)N * es, &sY);
         if (rc) return rc;
         if (lr->w) {
-            rc = stage_in(c, c->sW, lr->w, (size_t)N * es, &sW);
+            rc = stage_in(c, c->sW, lr->w, (size_t)N * (cplx ? ces : es), &sW);
             if (rc) return rc;
         }
-        rc = stage_out(c, c->sLoss, lr->loss, (size_t)p->n_trees * es, &sLoss);
+        rc = stage_out(c, c->sLoss, lr->loss, (size_t)p->n_trees * ces, &sLoss);
         if (rc) return rc;
         size_t pb = 0, sb = 0;
         if (lr->stats) {
@@ -278,8 +285,8 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
             la.stats = static_cast<double *>(sStats.dev);
             la.ystats = static_cast<double *>(sYstats.dev);
             fit_stats_scratch_bytes(p->dtype, p->n_trees, N, &pb, &sb);
-        } else
-        loss_scratch_bytes(p->dtype, p->n_trees, N, &pb, &sb);
+        } else if (p->threaded && !direct && !half && !cplx) loss_scratch_bytes(p->dtype, p->n_trees, N, &pb, &sb);
+        else flat_loss_scratch_bytes(p->io, p->n_trees, N, &pb, &sb); // (the flat-switch interpreter's tiles and waves)
         HIP_TRY(c, c->sPartial.reserve(pb));
         HIP_TRY(c, c->sSeg.reserve(sb));
         la.y = sY.dev;
@@ -381,7 +388,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     else if (cplx) HIP_TRY(c, launch_eval_complex(p->io, a, p->d_ctab, c->stream, &c->last_kernel)); // (+ the program's constant table)
     else HIP_TRY(c, launch_eval(p->dtype, a, c->stream, &c->last_kernel));
     if (!c->nested) HIP_TRY(c, time_end(c));
-    if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * es, hipMemcpyDeviceToHost, c->stream));
+    if (sLoss.staged) HIP_TRY(c, hipMemcpyAsync(lr->loss, sLoss.dev, (size_t)p->n_trees * ces, hipMemcpyDeviceToHost, c->stream));
     if (sStats.staged) HIP_TRY(c, hipMemcpyAsync(lr->stats, sStats.dev, (size_t)p->n_trees * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sYstats.staged) HIP_TRY(c, hipMemcpyAsync(lr->ystats, sYstats.dev, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sOut.staged) {

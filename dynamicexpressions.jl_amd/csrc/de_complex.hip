@@ -46,6 +46,10 @@ template <typename T> __device__ __noinline__ void c_store_ragged(T *o, CV<T> v,
 }
 __device__ __forceinline__ float c_fma0(float v, float p) { return __builtin_fmaf(v, 0.0f, p); }
 __device__ __forceinline__ double c_fma0(double v, double p) { return __builtin_fma(v, 0.0, p); }
+// |e| of a loss term (LOSS launches): OCML's hypot — de_complex_ops.h forms no modulus of its own (its sqrt and log go through c_ssqs);
+// a loss term claims no bit parity with a CPU library
+__device__ __forceinline__ float c_hypot(float x, float y) { return ::hypotf(x, y); }
+__device__ __forceinline__ double c_hypot(double x, double y) { return ::hypot(x, y); }
 
 template <typename T> struct ComplexPolicy {
     using G = CGeom<T>;
@@ -55,7 +59,11 @@ template <typename T> struct ComplexPolicy {
     static constexpr int VW = G::VW, TILE = G::TILE, EPS = 2;
     static constexpr size_t ROW_BYTES = CROW_BYTES, STORE_BYTES = 16;
     static constexpr bool HAS_PARAMS = false;
-    static constexpr const char *NAMES[3] = {"de_eval_complex_kernel", "de_eval_complex_kernel<direct>", "de_eval_complex_kernel<cert>"};
+    static constexpr const char *NAMES[5] = {"de_eval_complex_kernel", "de_eval_complex_kernel<direct>", "de_eval_complex_kernel<cert>",
+                                             "de_eval_complex_kernel<loss>", "de_eval_complex_kernel<direct,loss>"};
+    typedef CV<T> LY;                 // complex targets, interleaved in memory
+    struct LW { T v[G::VW]; };        // REAL weights
+    static constexpr bool LOSS_ALL_KINDS = false;
 
     // coalesced reads of the interleaved pairs, transposed writes (sample j of feature f: re at rows[f * ROW + j], im at rows[f * ROW + TILE + j])
     static __device__ __forceinline__ void stage_x(const FlatArgs<T> &a, unsigned char *smem, int64_t base, int tid) {
@@ -198,6 +206,52 @@ template <typename T> struct ComplexPolicy {
         *reinterpret_cast<Q *>(o) = q;
     }
     static __device__ __forceinline__ void store_ragged(T *o, const V &v, int64_t remaining) { c_store_ragged<T>(o, v, remaining); }
+
+    // ---- LOSS: e = yhat - y per component in T; L2 l = abs2(e) = re * re + im * im (two products, one sum; the build never contracts),
+    // L1 l = abs(e) = hypot(re, im); real weights, a real sum
+    static __device__ __forceinline__ LY load_y(const FlatArgs<T> &a, int64_t j0, bool vec) {
+        LY v;
+        if (vec) { // this lane's samples, interleaved: one 16-byte load
+            typedef T Q __attribute__((ext_vector_type(16 / sizeof(T))));
+            const Q q = *reinterpret_cast<const Q *>(a.y + 2 * j0);
+#pragma unroll
+            for (int i = 0; i < VW; i++) {
+                v.re[i] = q[2 * i];
+                v.im[i] = q[2 * i + 1];
+            }
+            return v;
+        }
+#pragma unroll
+        for (int i = 0; i < VW; i++) {
+            const T *q = a.y + 2 * (j0 + i < a.N - 1 ? j0 + i : a.N - 1);
+            v.re[i] = q[0];
+            v.im[i] = q[1];
+        }
+        return v;
+    }
+    static __device__ __forceinline__ LW load_w(const FlatArgs<T> &a, int64_t j0, bool vec) {
+        LW v;
+        if (a.w && vec) { // 8 bytes per lane
+            typedef T Q __attribute__((ext_vector_type(VW)));
+            const Q q = *reinterpret_cast<const Q *>(a.w + j0);
+#pragma unroll
+            for (int i = 0; i < VW; i++) v.v[i] = q[i];
+            return v;
+        }
+#pragma unroll
+        for (int i = 0; i < VW; i++) v.v[i] = j0 + i < a.N ? (a.w ? a.w[j0 + i < a.N - 1 ? j0 + i : a.N - 1] : T(1)) : T(0);
+        return v;
+    }
+    static __device__ __forceinline__ T loss_sum(int kind, T, const V &acc, const LY &y, const LW &w) { // (DE_LOSS_L2 / DE_LOSS_L1: launch_flat admits no other)
+        T s = T(0);
+#pragma unroll
+        for (int i = 0; i < VW; i++) {
+            const T er = acc.re[i] - y.re[i], ei = acc.im[i] - y.im[i];
+            const T l = kind == (int)DE_LOSS_L1 ? c_hypot(er, ei) : er * er + ei * ei;
+            s += w.v[i] != T(0) ? w.v[i] * l : T(0);
+        }
+        return s;
+    }
 };
 static_assert(ComplexPolicy<float>::TILE == flat_tile_samples(DE_CF32) && ComplexPolicy<double>::TILE == flat_tile_samples(DE_CF64), "de_kernels.h flat_tile_samples");
 

@@ -4,6 +4,7 @@
 // rows of 256 vectors (+ one of padding), so a leaf read is one conflict-free ds_read_b128 per lane.  The operators are those of the
 // threaded kernel's handlers (de_real_vec.h): the two kernels agree bit for bit.
 #include "de_flat.h"
+#include "de_loss_kinds.h"
 #include "de_real_vec.h"
 
 namespace de {
@@ -12,16 +13,29 @@ template <typename T> __device__ __noinline__ void real_store_ragged(T *o, VG<T,
     DE_UNROLL for (int i = 0; i < VecOf<T>::W; i++) if (i < remaining) o[i] = v.v[0][i];
 }
 
+// The lane's sum of a PARAMETERISED kind's terms (LOSS launches; de_loss_kinds.h): the threaded kernel's h_tree_end_loss on one vector.
+// The kind is wave-uniform: a scalar switch, outside the loop over the samples.
+template <typename T> __device__ __noinline__ T real_loss_kind_sum(int kind, T p, VG<T, 1> acc, VG<T, 1> y, VG<T, 1> w) {
+    typename VecOf<T>::type l;
+    DE_LOSS_KIND_SWITCH(kind, DE_UNROLL for (int i = 0; i < VecOf<T>::W; i++) l[i] = (loss_kind_one<KIND, T>(acc.v[0][i], y.v[0][i], p).l))
+    T s = T(0);
+    DE_UNROLL for (int i = 0; i < VecOf<T>::W; i++) s += w.v[0][i] != T(0) ? w.v[0][i] * l[i] : T(0);
+    return s;
+}
+
 template <typename T> struct RealPolicy {
     typedef T Elem;
     typedef T Scalar;
     typedef typename VecOf<T>::type V;
+    typedef V LY, LW;
+    static constexpr bool LOSS_ALL_KINDS = true;
     static constexpr int VW = VecOf<T>::W, TILE = FLAT_BLK * VW, EPS = 1;
     static constexpr int ROWV = FLAT_BLK + 1; // LDS row stride in vectors (+1: bank spread for the staging writes)
     static constexpr size_t ROW_BYTES = FLAT_ROW_BYTES, STORE_BYTES = 16;
     static_assert(ROWV * 16 == FLAT_ROW_BYTES, "de_kernels.h FLAT_ROW_BYTES");
     static constexpr bool HAS_PARAMS = true;
-    static constexpr const char *NAMES[3] = {"de_eval_tape_kernel", "de_eval_tape_kernel<direct>", "de_eval_tape_kernel<cert>"};
+    static constexpr const char *NAMES[5] = {"de_eval_tape_kernel", "de_eval_tape_kernel<direct>", "de_eval_tape_kernel<cert>",
+                                             "de_eval_tape_kernel<loss>", "de_eval_tape_kernel<direct,loss>"};
 
     // coalesced HBM / L2 read, transposed LDS write: sample j of the tile lives at rows[f * ROWV * VW + j]
     static __device__ __forceinline__ void stage_x(const FlatArgs<T> &a, unsigned char *smem, int64_t base, int tid) {
@@ -106,6 +120,35 @@ template <typename T> struct RealPolicy {
     }
     static __device__ __forceinline__ void store_vec(T *o, V v) { *reinterpret_cast<V *>(o) = v; } // one 16-byte store per lane, coalesced over the wave
     static __device__ __forceinline__ void store_ragged(T *o, V v, int64_t remaining) { real_store_ragged<T>(o, VG<T, 1>{{v}}, remaining); }
+
+    // ---- LOSS: the threaded kernel's terms — e = yhat - y in T, L2 e * e, L1 |e|, kinds >= 16 through loss_kind_one
+    static __device__ __forceinline__ V load_y(const FlatArgs<T> &a, int64_t j0, bool vec) {
+        if (vec) return *reinterpret_cast<const V *>(a.y + j0);
+        V v;
+        DE_UNROLL for (int i = 0; i < VW; i++) v[i] = a.y[j0 + i < a.N - 1 ? j0 + i : a.N - 1];
+        return v;
+    }
+    static __device__ __forceinline__ V load_w(const FlatArgs<T> &a, int64_t j0, bool vec) {
+        if (!a.w) {
+            V v;
+            DE_UNROLL for (int i = 0; i < VW; i++) v[i] = j0 + i < a.N ? T(1) : T(0);
+            return v;
+        }
+        if (vec) return *reinterpret_cast<const V *>(a.w + j0);
+        V v;
+        DE_UNROLL for (int i = 0; i < VW; i++) v[i] = j0 + i < a.N ? a.w[j0 + i < a.N - 1 ? j0 + i : a.N - 1] : T(0);
+        return v;
+    }
+    static __device__ __forceinline__ T loss_sum(int kind, T p, V acc, V y, V w) {
+        if (kind >= (int)DE_LOSS_HUBER) return real_loss_kind_sum<T>(kind, p, VG<T, 1>{{acc}}, VG<T, 1>{{y}}, VG<T, 1>{{w}});
+        const V e = acc - y;
+        T s = T(0);
+        DE_UNROLL for (int i = 0; i < VW; i++) {
+            const T l = kind == (int)DE_LOSS_L1 ? M<T>::abs(e[i]) : e[i] * e[i];
+            s += w[i] != T(0) ? w[i] * l : T(0);
+        }
+        return s;
+    }
 };
 static_assert(RealPolicy<float>::TILE == flat_tile_samples(DE_F32) && RealPolicy<double>::TILE == flat_tile_samples(DE_F64), "de_kernels.h flat_tile_samples");
 

@@ -48,7 +48,10 @@ struct HalfPolicy {
     static constexpr size_t ROW_BYTES = FLAT_ROW_BYTES, STORE_BYTES = 8;
     static_assert(ROWV * 16 == FLAT_ROW_BYTES, "de_kernels.h FLAT_ROW_BYTES");
     static constexpr bool HAS_PARAMS = true;
-    static constexpr const char *NAMES[3] = {"de_eval_half_kernel", "de_eval_half_kernel<direct>", "de_eval_half_kernel<cert>"};
+    static constexpr const char *NAMES[5] = {"de_eval_half_kernel", "de_eval_half_kernel<direct>", "de_eval_half_kernel<cert>",
+                                             "de_eval_half_kernel<loss>", "de_eval_half_kernel<direct,loss>"};
+    typedef HV LY, LW; // (binary16 targets and weights, widened exactly)
+    static constexpr bool LOSS_ALL_KINDS = false;
 
     // coalesced read of binary16 pairs, transposed Float32 write (sample j of row f at rows[f * ROWV * 4 + j])
     static __device__ __forceinline__ void stage_x(const FlatArgs<_Float16> &a, unsigned char *smem, int64_t base, int tid) {
@@ -141,6 +144,37 @@ struct HalfPolicy {
         *reinterpret_cast<HH4 *>(o) = h;                    // four samples, one 8-byte store per lane
     }
     static __device__ __forceinline__ void store_ragged(_Float16 *o, V v, int64_t remaining) { h_store_ragged(o, v, remaining); }
+
+    // ---- LOSS: Julia's Float16 steps per term — e = r16(yhat - y); L2 l = r16(e * e), L1 l = |e|; weighted r16(w * l).  The term is the
+    // reference's, the sum is the library's: the binary16 terms are summed in Float32 (a binary16 sum of N terms overflows at 65504)
+    static __device__ __forceinline__ V widen4(const _Float16 *q) {
+        const HH4 h = *reinterpret_cast<const HH4 *>(q); // four samples, one 8-byte load per lane
+        return V{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    }
+    static __device__ __forceinline__ V load_y(const FlatArgs<_Float16> &a, int64_t j0, bool vec) {
+        if (vec) return widen4(a.y + j0);
+        V v;
+#pragma unroll
+        for (int i = 0; i < VW; i++) v[i] = (float)a.y[j0 + i < a.N - 1 ? j0 + i : a.N - 1];
+        return v;
+    }
+    static __device__ __forceinline__ V load_w(const FlatArgs<_Float16> &a, int64_t j0, bool vec) {
+        if (a.w && vec) return widen4(a.w + j0);
+        V v;
+#pragma unroll
+        for (int i = 0; i < VW; i++) v[i] = j0 + i < a.N ? (a.w ? (float)a.w[j0 + i < a.N - 1 ? j0 + i : a.N - 1] : 1.0f) : 0.0f;
+        return v;
+    }
+    static __device__ __forceinline__ float loss_sum(int kind, float, V acc, V y, V w) { // (DE_LOSS_L2 / DE_LOSS_L1: launch_flat admits no other)
+        const V e = h_round(acc - y);
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < VW; i++) {
+            const float l = kind == (int)DE_LOSS_L1 ? __builtin_fabsf(e[i]) : r16(e[i] * e[i]);
+            s += w[i] != 0.0f ? r16(w[i] * l) : 0.0f;
+        }
+        return s;
+    }
 };
 static_assert(HalfPolicy::TILE == flat_tile_samples(DE_F16), "de_kernels.h flat_tile_samples");
 

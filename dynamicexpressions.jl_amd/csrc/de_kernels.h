@@ -90,7 +90,8 @@ struct EvalArgs {
     // LDS byte offsets in the low 24 bits of word 1
     bool threaded;
     bool direct; // feature matrix too wide for the LDS tile: gather features from global memory (flat-switch kernel)
-    const LossArgs *loss; // non-null: fused loss instead of the output store (threaded kernel only)
+    const LossArgs *loss; // non-null: fused loss instead of the output store (the threaded kernel; the flat-switch kernel's LOSS variant,
+                          // whose scratch is flat_loss_scratch_bytes and which serves no fit statistics)
     void *prio_keys;      // device scratch, 3 * DE_PRIO_MAX_F 64-bit keys: the priority tiles of a large early-exit launch (de_kernels.hip de_tile_extremes_kernel); null: none
     bool prio_keys_ready; // prio_keys already hold the keys of THIS X (de_ctx_declare_dataset: computed once for a dataset that does not change between calls): no pre-pass
     // compaction of the live trees behind the probe launch of the priority tiles (de_kernels.hip de_compact_live_kernel; threaded kernel only):
@@ -263,6 +264,17 @@ void fit_stats_scratch_bytes(int dtype, int64_t n_trees, int64_t N, size_t *part
 hipError_t launch_loss_reduce_tiles(int dtype, const void *partial, int64_t n_cols, int64_t n_tiles, void *seg_sum,
                                     int32_t *n_segs, hipStream_t stream);
 int32_t loss_segments(int64_t n_tiles);
+// ... of a loss launch of the flat-switch interpreter (de_flat.h; io = any of the five): one partial per (tile, tree, wave) over ITS
+// tiles (flat_tile_samples) and its four waves; the partials are Float32 for DE_F32 / DE_F16 / DE_CF32 and Float64 for DE_F64 / DE_CF64
+// (flat_loss_dtype: also the type of loss[]), the segment sums double.
+constexpr int FLAT_WAVES = 4;
+constexpr int flat_loss_dtype(int io) { return io == DE_F64 || io == DE_CF64 ? DE_F64 : DE_F32; }
+inline void flat_loss_scratch_bytes(int io, int64_t n_trees, int64_t N, size_t *partial_bytes, size_t *seg_bytes) {
+    const int64_t tile = flat_tile_samples(io);
+    const int64_t n_tiles = (N + tile - 1) / tile;
+    *partial_bytes = (size_t)n_tiles * (size_t)n_trees * FLAT_WAVES * (flat_loss_dtype(io) == DE_F32 ? 4 : 8);
+    *seg_bytes = (size_t)loss_segments(n_tiles) * (size_t)n_trees * FLAT_WAVES * sizeof(double);
+}
 // The pre-pass over y / w of the fit statistics alone (de_eval_fit_stats_grad): ystats = {W, mean_y, M2_y} on the device; scratch:
 // 3 * ceil(N / 256) doubles
 hipError_t launch_fit_ystats(int dtype, const void *y, const void *w, int64_t N, double *ystats, void *scratch, hipStream_t stream);

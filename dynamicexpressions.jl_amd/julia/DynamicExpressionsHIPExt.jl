@@ -35,6 +35,7 @@ const DE_F32, DE_F64, DE_F16, DE_CF32, DE_CF64 = Cint(0), Cint(1), Cint(2), Cint
 const DE_OPT_EARLY_EXIT, DE_OPT_FUSE_DEG1, DE_OPT_FUSE_DEG2, DE_OPT_BUMPER_CHECKS, DE_OPT_TURBO, DE_OPT_FULL_EVAL, DE_OPT_FORWARD_GRAD, DE_OPT_REVERSE_GRAD =
     UInt32(1), UInt32(2), UInt32(4), UInt32(8), UInt32(16), UInt32(32), UInt32(64), UInt32(128)
 const DE_OPT_F16_GRAD = UInt32(256)   # a Float16 program with it serves de_eval_grad / de_eval_diff (DESIGN.md §13.6)
+const DE_OPT_TYPED_LOSS = UInt32(512) # a Float16 / complex program with it serves de_eval_loss(_ex), L2 and L1 (DESIGN.md §4.4.17)
 # The ABI this file was written for (include/de_hip.h lists what changed between versions).  Version 2: the rows / gradients of a tree
 # with `complete == false` are NOT evaluated to the end (the reference's early exit, src/Evaluate.jl:26-32): with the host arrays this
 # shim passes, the library NaN-fills them; `full_eval=true` (DE_OPT_FULL_EVAL) evaluates every tree on every sample instead.
@@ -155,7 +156,7 @@ function opcode_table(operators::OperatorEnum)
 end
 
 """EvalContext knobs that change RESULTS -> de_options bits (src/Evaluate.jl:156-181,496,607)."""
-function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=false, forward_grad::Bool=false, reverse_grad::Bool=false, half_grad::Bool=false)
+function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=false, forward_grad::Bool=false, reverse_grad::Bool=false, half_grad::Bool=false, typed_loss::Bool=false)
     nops(d) = d <= length(operators.ops) ? length(operators.ops[d]) : 0
     fused = ctx.use_fused isa Val{true}
     bits = UInt32(0)
@@ -167,6 +168,7 @@ function option_bits(operators::OperatorEnum, ctx::EvalContext; full_eval::Bool=
     full_eval && (bits |= DE_OPT_FULL_EVAL)             # no early exit at tree granularity: rows of incomplete trees are fully evaluated
     forward_grad && (bits |= DE_OPT_FORWARD_GRAD)       # ABI 2's spelling of what is the default since ABI 3: fused loss gradients by forward duals (the reference's flag semantics exactly)
     half_grad && (bits |= DE_OPT_F16_GRAD)              # Float16 programs: de_eval_grad / de_eval_diff in binary16 steps (other element types ignore it)
+    typed_loss && (bits |= DE_OPT_TYPED_LOSS)           # Float16 / complex programs: de_eval_loss(_ex) for L2 and L1 (Float32 / Float64 ignore it)
     reverse_grad && (bits |= DE_OPT_REVERSE_GRAD)       # permission for reverse accumulation (faster from 8 gradient rows per tree on; `ok` may differ in ~0.03 % of Float32 cases)
     return bits
 end
@@ -393,7 +395,7 @@ end
 function HIPPopulation(
     trees::AbstractVector{<:AbstractExpressionNode{T}}, operators::OperatorEnum, n_features::Integer;
     eval_context::EvalContext=EvalContext(), n_params::Integer=0, full_eval::Bool=false, forward_grad::Bool=false,
-    reverse_grad::Bool=false, half_grad::Bool=false,
+    reverse_grad::Bool=false, half_grad::Bool=false, typed_loss::Bool=false,
 ) where {T<:Union{Float16,Float32,Float64,ComplexF32,ComplexF64}}
     optable = opcode_table(operators)
     nodes, consts, cse = TapeNode[], T[], TapeNode[]
@@ -424,7 +426,7 @@ function HIPPopulation(
             (Ptr{Cvoid}, Cint, Ptr{TapeNode}, Ptr{Int64}, Ptr{TapeNode}, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int32, Int32,
              UInt32, Ref{Ptr{Cvoid}}),
             hc, dtype_code(T), nodes, node_off, isempty(cse) ? C_NULL : pointer(cse), cse_off, length(trees), consts,
-            const_off, n_features, n_params, option_bits(operators, eval_context; full_eval, forward_grad, reverse_grad, half_grad), h))
+            const_off, n_features, n_params, option_bits(operators, eval_context; full_eval, forward_grad, reverse_grad, half_grad, typed_loss), h))
     end
     pop = HIPPopulation{T}(ctx, h[], length(trees), n_features, occ, n_slots, n_consts, optable)
     finalizer(finalize_population, pop)
@@ -608,6 +610,13 @@ function loss_spec(loss::Symbol, loss_param::Real; with_gradient::Bool=true)
     return Ref(LossSpec(LOSS_KINDS[loss], Int32(0), Float64(loss_param)))
 end
 
+# element types of a fused loss's weights and values (include/de_hip.h de_eval_loss): real weights; Float32 sums of binary16 terms
+loss_weight_type(::Type{T}) where {T<:Real} = T
+loss_weight_type(::Type{Complex{T}}) where {T} = T
+loss_value_type(::Type{T}) where {T<:Real} = T
+loss_value_type(::Type{Float16}) = Float32
+loss_value_type(::Type{Complex{T}}) where {T} = T
+
 """
     eval_population_loss(pop, X, y; weights=nothing, loss=:L2, loss_param=0.0) -> (loss::Vector{T}, ok)
 
@@ -615,15 +624,20 @@ end
 the `N × n_trees` output matrix is never written.  `loss[t]` is NaN where `ok[t]` is false.
 `loss` is `:L2`, `:L1` or a parameterised kind — `:huber` (δ), `:logcosh`, `:l1_eps` (ε), `:l2_eps` (ε), `:quantile` (τ), `:lp` (p),
 `:logit_dist`, `:logit_margin`, `:l1_hinge` — with its parameter in `loss_param`.
+
+A `Float16` or `Complex{T}` population made with `typed_loss=true` is served for `:L2` and `:L1` (DESIGN.md §4.4.17): the weights are
+real (`Vector{Float16}` / `Vector{T}`), and the losses come back as `Vector{Float32}` (binary16 terms, summed in Float32) /
+`Vector{T}` (`abs2` / `abs` of the complex residual).  Without `typed_loss` the library answers `DE_ERR_UNSUPPORTED` for them.
 """
 function eval_population_loss(
-    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{T}}=nothing,
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}; weights::Union{Nothing,Vector{<:Real}}=nothing,
     loss::Symbol=:L2, loss_param::Real=0.0,
 ) where {T}
     F, N = size(X)
     @assert F >= pop.n_features && length(y) == N
+    @assert weights === nothing || (eltype(weights) === loss_weight_type(T) && length(weights) == N)
     spec = loss_spec(loss, loss_param; with_gradient=false)
-    out = Vector{T}(undef, pop.n_trees)
+    out = Vector{loss_value_type(T)}(undef, pop.n_trees)
     ok = Vector{UInt8}(undef, pop.n_trees)
     with_pop(pop) do hc, hp
         check(pop.ctx, GC.@preserve X y weights out ok ccall(

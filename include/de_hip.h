@@ -112,7 +112,11 @@ extern "C" {
  *      de_ties_pack_host / de_ties_unpack_host / de_ties_fold_host / de_ties_fold_matrix_host: the device fits with a shared GraphNode
  *      constant as ONE unknown, for programs made by de_program_create_cse; every entry point above keeps its bits.
  *      (u) DE_OPT_F16_GRAD (new option bit 8): a DE_F16 program created with it is served by de_eval_grad and de_eval_diff, in binary16
- *      steps; without the bit, and for every other dtype, nothing changes. */
+ *      steps; without the bit, and for every other dtype, nothing changes.
+ *      (v) DE_OPT_TYPED_LOSS (new option bit 9): a DE_F16 / DE_CF32 / DE_CF64 program created with it is served by de_eval_loss and
+ *      de_eval_loss_ex (DE_LOSS_L2 / DE_LOSS_L1; the buffer table at de_eval_loss); without the bit nothing changes for them.  And, with
+ *      no bit: de_eval_loss / de_eval_loss_ex serve the DE_F32 / DE_F64 programs that do not run the LDS-tiled kernel (a feature matrix
+ *      too wide for its tile, DE_EVAL_THREADED=0), every kind — calls that answered DE_ERR_UNSUPPORTED before. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -130,13 +134,15 @@ typedef enum de_status {
 /* DE_F16: binary16 elements (2 bytes) everywhere the dtype sizes a buffer; computed in Float32 registers and rounded to binary16 after
  * every operator step.  Evaluation only: de_eval_grad / _diff / _pullback_dX, de_eval_loss(_grad, _grad_by_class) and
  * de_ctx_declare_dataset return DE_ERR_UNSUPPORTED for an F16 program or dtype and leave their outputs untouched — except that a program
- * created with DE_OPT_F16_GRAD is served by de_eval_grad and de_eval_diff (binary16 X, constants, parameters, out and grad).  F16 programs never
+ * created with DE_OPT_F16_GRAD is served by de_eval_grad and de_eval_diff (binary16 X, constants, parameters, out and grad), and one created
+ * with DE_OPT_TYPED_LOSS by de_eval_loss / de_eval_loss_ex (DE_LOSS_L2 / DE_LOSS_L1; binary16 y and w, Float32 losses).  F16 programs never
  * run the threaded kernel (de_eval_plan / de_program_dump report the flat-switch kernel's form); a feature matrix too wide for its LDS
  * tile is gathered from global memory as for Float32.  de_eval_sum_certificate refuses such wide programs for every dtype. */
 /* DE_CF32 / DE_CF64: complex elements, (re, im) interleaved — 8 bytes (numpy complex64, Julia ComplexF32) / 16 bytes (complex128,
  * ComplexF64) everywhere the dtype sizes a buffer; a constant is one (re, im) pair.  Opcodes: neg square cube inv sqrt exp log sin cos
  * tan sinh cosh tanh custom_cos + - * / +(x, y, z); every other one fails program creation with DE_ERR_UNSUPPORTED_OP (de_last_error names
- * it).  A value is valid when both components are finite.  Evaluation only, as DE_F16 (parameters included: n_params > 0 is refused);
+ * it).  A value is valid when both components are finite.  Evaluation only, as DE_F16 — with DE_OPT_TYPED_LOSS also de_eval_loss /
+ * de_eval_loss_ex (DE_LOSS_L2 / DE_LOSS_L1; complex y, REAL w and losses of the component type) — (parameters included: n_params > 0 is refused);
  * DE_OPT_TURBO is ignored.  de_eval_sum_certificate certifies when N * max(|re|, |im|) * 1.001 stays below the component type's floatmax. */
 typedef enum de_dtype { DE_F32 = 0, DE_F64 = 1, DE_F16 = 2, DE_CF32 = 3, DE_CF64 = 4 } de_dtype_t;
 
@@ -206,6 +212,11 @@ enum de_options {
      * that refuses DE_F16 keeps refusing it, with the same text.  The gradient program of a de_program_create_cse program with the bit
      * is lowered from the EXPANDED tape: every occurrence of a shared constant has a row of its own that holds its own partial. */
     DE_OPT_F16_GRAD = 1u << 8,
+    /* Fused losses of Float16 and complex programs.  Means something for dtype == DE_F16 / DE_CF32 / DE_CF64 only,
+     * DE_F32 / DE_F64 ignore it.  A program created with it is served by de_eval_loss and de_eval_loss_ex for DE_LOSS_L2 and DE_LOSS_L1
+     * (any other kind: DE_ERR_UNSUPPORTED, de_last_error names the kind and the element type, no output touched); the buffer types are
+     * in the table at de_eval_loss.  Every other entry point that refuses these programs keeps refusing them, with the same text. */
+    DE_OPT_TYPED_LOSS = 1u << 9,
     DE_OPT_DEFAULT = (1u << 0) | (1u << 1) | (1u << 2)
 };
 
@@ -506,7 +517,23 @@ int de_eval_diff(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, in
  * [n_trees, N] output never goes to HBM.  loss[t] is NaN where ok[t] == 0 (the callable sugar
  * NaN-fills incomplete evaluations, src/EvaluationHelpers.jl:29-33).  The reduction order is
  * fixed (per-wavefront partials, then two fixed-order passes in double), so results are
- * reproducible run to run.  `loss` holds n_trees values of the program's dtype. */
+ * reproducible run to run.  `loss` holds n_trees values of the program's dtype.
+ *
+ * Programs served, and their buffers (y / w hold N elements, loss n_trees):
+ *   DE_F32 / DE_F64                        y, w, loss of the dtype; every kind.  The LDS-tiled kernel, or — a feature matrix too wide for
+ *                                          its tile, DE_EVAL_THREADED=0 — the flat-switch interpreter's loss variant: the same arithmetic
+ *                                          per term, another summation order (each deterministic; the two agree to rounding).
+ *   DE_F16 with DE_OPT_TYPED_LOSS          y, w binary16; loss FLOAT32.  Julia's Float16 steps per term: e = r16(yhat - y), L2
+ *                                          l = r16(e * e), L1 l = |e|, weighted r16(w * l) (r16: a Float32 result rounded to binary16).
+ *                                          The term is the reference's, the SUM is the library's: the binary16 terms are widened exactly
+ *                                          and summed in Float32 (a binary16 sum of N terms overflows at 65504) — the stance
+ *                                          de_eval_fit_stats takes with its double outputs.  A term that overflows binary16 (|e| >= 256
+ *                                          under L2) is +Inf and so is the loss, with ok still 1.
+ *   DE_CF32 / DE_CF64 with the option      y interleaved (re, im) pairs; w REAL, loss REAL, both of the component type.  e = yhat - y
+ *                                          per component; L2 l = re_e * re_e + im_e * im_e (abs2: two products, one sum, no contraction),
+ *                                          L1 l = hypot(re_e, im_e) (abs).
+ * DE_F16 / complex programs: DE_LOSS_L2 and DE_LOSS_L1 only (DE_ERR_UNSUPPORTED for another kind); without DE_OPT_TYPED_LOSS they are
+ * refused as before.  As for every fused loss, the term claims no bit parity with a CPU library. */
 typedef enum de_loss_kind {
     DE_LOSS_L2 = 0,      /* l(e) = e^2,  l'(e) = 2e                                              */
     DE_LOSS_L1 = 1,      /* l(e) = |e|,  l'(e) = sign(e)                                         */
@@ -552,8 +579,8 @@ int de_eval_loss_ex(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N,
  * M2 and C are 0.  Fixed reduction order: reproducible run to run.
  * Pearson's r^2 = C^2 / (M2_p M2_y), the least-squares a + b yhat (b = C / M2_p, a = mean_y - b mean_p) and its
  * residual M2_y - C^2 / M2_p, R^2 and the plain L2 loss are all functions of these.
- * Pointers, parametric populations and refusals as for de_eval_loss_ex: DE_F16 / complex programs and programs that do
- * not run the LDS-tiled kernel are DE_ERR_UNSUPPORTED, a null y / stats / ystats / ok DE_ERR_INVALID_ARG, both before
+ * Pointers and parametric populations as for de_eval_loss_ex; DE_F16 / complex programs (with or without DE_OPT_TYPED_LOSS) and
+ * programs that do not run the LDS-tiled kernel are DE_ERR_UNSUPPORTED, a null y / stats / ystats / ok DE_ERR_INVALID_ARG, both before
  * any output is touched. */
 int de_eval_fit_stats(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
                       const de_param_args_t *pargs, const void *y, const void *w,
