@@ -377,10 +377,6 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         run += (int64_t)g * N;
         span = std::max(span, off + (int64_t)g * N);
     }
-    // (the kernel's real row size: the binary16 kernel's LDS rows are Float32, and its window is one of 1 .. 6, 8)
-    const size_t lds_need = half ? grad_f16_lds_bytes(p->n_features, p->n_slots, maxg <= 6 ? std::max(maxg, 1) : 8)
-                                 : ((size_t)p->n_features + (size_t)p->n_slots * (1 + (size_t)std::min(maxg, 8))) * 260 * es;
-    if (lds_need > 160 * 1024) return fail(c, DE_ERR_UNSUPPORTED, "gradient kernel: LDS footprint too large for this tree shape");
     rc = ensure_generic_code(c, p);
     if (rc) return rc;
 
@@ -485,6 +481,10 @@ static int grad_impl(de_ctx *c, de_program *p, const void *X, int64_t N, int64_t
         rc = ensure_grad_threaded(c, p, mode, ng, N, &g);
         if (rc) return rc;
     }
+    // the tape kernel launches (launch_grad / launch_grad_f16): the launch's own window and row size (the binary16 kernel's LDS rows are
+    // Float32).  A program the threaded kernels serve has passed their own limit (de_grad_encode.cpp forward_plan).
+    if (!g.threaded_code && grad_tape_lds_bytes(p->n_features, p->n_slots, grad_window(maxg), half ? 4 : es) > 160 * 1024)
+        return fail(c, DE_ERR_UNSUPPORTED, "gradient kernel: LDS footprint too large for this tree shape");
     Staged sDY;
     if (dY) {
         rc = stage_in(c, c->sY, dY, (size_t)N * es, &sDY);
@@ -901,10 +901,10 @@ int loss_grad_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int64
         g.rev_n_tiles = n_tiles;
     }
     if (!g.rev_code) {
-        const size_t lds_need = ((size_t)p->n_features + (size_t)p->n_slots * (1 + (size_t)std::min(maxg, 8))) * 260 * es;
-        if (lds_need > 160 * 1024) return fail(c, DE_ERR_UNSUPPORTED, "gradient kernel: LDS footprint too large for this tree shape");
         rc = ensure_grad_threaded(c, p, mode, ng, N, &g);
         if (rc) return rc;
+        if (!g.threaded_code && grad_tape_lds_bytes(p->n_features, p->n_slots, grad_window(maxg), es) > 160 * 1024) // (the tape kernel launches: grad_impl)
+            return fail(c, DE_ERR_UNSUPPORTED, "gradient kernel: LDS footprint too large for this tree shape");
     }
     if (timing) {
         const auto tg2 = std::chrono::steady_clock::now();

@@ -1,8 +1,8 @@
-// de_grad_common.h — device code shared by the three gradient kernels (de_grad_kernels.hip: flat switch,
+// de_grad_common.h — device code shared by the three gradient kernels (de_grad_tape.h: flat switch,
 // eval_diff and wide gradients; de_grad_threaded.hip: threaded code; de_rev_threaded.hip: reverse accumulation):
 // kernel arguments, value+partial functions of every operator (ChainRules scalar rules, same table as
 // oracle/de_oracle_ops.h), tile map, tile prologue (X rows, parameter rows), loss term.  What a module of the two
-// threaded kernels exports (GradModule).  The launch itself is host code in de_grad_kernels.hip.
+// threaded kernels exports (GradModule).  The launch itself is host code in de_grad_tape.h and de_grad_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,18 +1,8 @@
-// de_grad_kernels.hip — forward-mode gradient of a population of trees on gfx950.
-// Replaces the reference's src/EvaluateDerivative.jl: eval_grad_tree_array (:193-243),
-// grad_degn_eval (:340-365), grad_deg0_eval (:367-404) and eval_diff_tree_array (:40-168).
-//
-// Every sample carries a dual number (x, d[0..GC)) through the same accumulator program the
-// eval kernel runs (de_program.h, generic form).  GC = the window of gradient components a
-// launch handles; wider gradients (constant mode with many constants, :both mode) are covered by
-// several windows (blockIdx.y), each recomputing x — the alternative, (1+n_grad) live values
-// per spill slot, would wreck occupancy.  Semantics follow the reference exactly:
-//   * d[k] = g1*d1[k] + g2*d2[k] with dense arithmetic, leaf gradients materialised as 0/1
-//     (so an infinite partial times a zero seed is NaN, as in grad_degn_eval);
-//   * after EVERY node (leaves included) x and all d[k] are validity-tested (:239-242);
-//   * eval_diff (single direction) performs NO validity test (:99-119).
+// de_grad_kernels.hip — forward-mode gradient of a population of trees on gfx950: the Float32 / Float64 arithmetic policy of the tape
+// interpreter (de_grad_tape.h: the kernel, its semantics and the one launch path), the finish kernels of the fused reductions, and the
+// launch of the threaded and reverse kernels (de_grad_threaded.hip, de_rev_threaded.hip).
 // Partial derivatives restate ChainRules' scalar rules (same table as oracle/de_oracle_ops.h).
-#include "de_grad_common.h"
+#include "de_grad_tape.h"
 #include <memory>
 #include <mutex>
 #include <utility>
@@ -22,289 +12,51 @@
 
 namespace de {
 
+// The real policy of de_grad_tape_kernel: a value is a T, in memory, in registers and in LDS; plain IEEE arithmetic.
+template <typename T> struct RealGrad {
+    typedef T Elem;
+    typedef T V;
+    static constexpr bool TREE_ENDS = true;
+    static constexpr const char *NAMES[3] = {"de_grad_tape_kernel", "de_grad_tape_kernel<GN>", "de_grad_tape_kernel<FIT>"};
 
-// One sample per thread; LDS rows of GBLK(+4) elements: rows [0,F) = X tile, then each spill
-// slot s owns 1+GC rows (x, d[0..GC)).
-// GN: the launch of de_eval_loss_gn — behind the loss and its gradient the tree end also reduces the products
-// sum_j w_j c_j d_i(j) d_k(j), i <= k < G (c = the loss kind's curvature weight, 1 for L2), of a tree whose rows lie in this one window (de_grad_threaded.hip g_epilogue_gn: same columns, same
-// association order).  A template parameter: the other instantiations keep the code they had.
-// FIT: the launch of de_eval_fit_stats_grad — the tree end of de_grad_threaded.hip g_epilogue_fit, one sample per lane.
-template <typename T, int GC, bool GN = false, bool FIT = false>
-__global__ void __launch_bounds__(GBLK) de_grad_tape_kernel(const GArgs<T> a) {
-    constexpr int RS = GBLK + 4; // row stride (elements)
-    extern __shared__ __align__(16) unsigned char gsmem[];
-    T *__restrict__ rows = reinterpret_cast<T *>(gsmem);
-
-    const TileMap tm = map_block(blockIdx.x, a.n_chunks, a.n_tiles);
-    if (!tm.valid) return;
-    const int tid = threadIdx.x;
-    const int64_t base = tm.tile * GBLK;
-    const int64_t last = a.N - 1;
-    const int g0 = a.diff_g0 >= 0 ? a.diff_g0 : (int)blockIdx.y * GC; // first gradient component of this window
-    const int F = a.F, P = a.P;
-
-    stage_x_rows<T>(rows, a.X, a.ldX, (uint32_t)F, GBLK, base, last, [](uint32_t j, uint32_t f) { return f * RS + j; });
-    int64_t jj0 = base + tid;
-    const bool live = jj0 < a.N;
-    jj0 = jj0 < last ? jj0 : last;
-    int64_t cls = 0;
-    if (a.uses_params)
-        cls = clamp_class((a.classes_is_i64 ? reinterpret_cast<const int64_t *>(a.classes)[jj0]
-                                            : (int64_t) reinterpret_cast<const int32_t *>(a.classes)[jj0]) - a.class_base, a.n_classes);
-    T yv = T(0), wv = T(0);
-    if (a.loss_mode) {
-        yv = a.y[jj0];
-        wv = live ? (a.w ? a.w[jj0] : T(1)) : T(0);
+    static __device__ __forceinline__ void stage_x(T *rows, const T *X, int64_t ldX, uint32_t F, int64_t base, int64_t N, int) {
+        stage_x_rows<T>(rows, X, ldX, F, GBLK, base, N - 1, [](uint32_t j, uint32_t f) { return f * GRAD_TAPE_ROW + j; });
     }
-    __syncthreads();
+    static __device__ __forceinline__ T imm(U32x4 w) { return gimm<T>(w.z, w.w); }
 
-    const ConstU4Ptr code = (ConstU4Ptr)(uintptr_t)a.code;
-    const ConstI32Ptr code_off = (ConstI32Ptr)(uintptr_t)a.code_off;
-    const ConstI64Ptr col_off = (ConstI64Ptr)(uintptr_t)a.col_off;
-    const ConstI32Ptr n_grad = (ConstI32Ptr)(uintptr_t)a.n_grad;
-    const ConstI64Ptr grad_off = (ConstI64Ptr)(uintptr_t)a.grad_off;
-    const int t0 = tm.chunk * a.trees_per_chunk;
-    const int t1 = (t0 + a.trees_per_chunk < a.n_trees) ? t0 + a.trees_per_chunk : a.n_trees;
-    T *__restrict__ stk = rows + (size_t)F * RS;
-
-    // window-local seed of a leaf = its gradient row - g0 (or < 0: no gradient in this mode/window)
-    const int feat_seed0 = a.mode != DE_GRAD_CONSTANT ? P - g0 : -0x40000000;
-    const int param_seed0 = a.mode != DE_GRAD_CONSTANT ? -g0 : -0x40000000;
-    const int const_seed0 = a.mode == DE_GRAD_CONSTANT ? -g0 : (a.mode == DE_GRAD_BOTH ? P + F - g0 : -0x40000000);
-
-    const uint64_t skip = gskip_mask(a.ok, (const int32_t *)nullptr, t0, t1, a.check ? a.skip_flagged : 0, (int64_t)tm.tile);
-    for (int tree = t0; tree < t1; ++tree) {
-        if ((skip >> (tree - t0)) & 1ull) continue; // already incomplete (early exit)
-        const int G = a.diff_g0 >= 0 ? 1 : n_grad[tree];
-        if (a.diff_g0 < 0 && g0 >= G && g0 > 0) continue; // window without a component of this tree (window 0 always runs: x, flag)
-        int pc = code_off[tree];
-        const int pe = code_off[tree + 1];
-        T x = T(0), d[GC];
-        DE_UNROLL for (int k = 0; k < GC; k++) d[k] = T(0);
-        T poison = T(0);
-        U32x4 nxt = code[pc];
-        for (; pc < pe; ++pc) {
-            const U32x4 w = nxt;
-            nxt = code[pc + 1];
-            // One flat wave-uniform switch over the bound handler id (de_bind.h); the operand is a LEAF
-            // row (< F: one-hot seed), a spill ROW (>= F: a popped dual number) or a constant (seed).
-#define G_SLOT(r) (stk + ((r) - (uint32_t)F) * (1 + GC) * RS + tid)
-#define G_LEAF_ROW(r) { xb = rows[(r) * RS + tid]; seed = (int)(r) + feat_seed0; if (a.check) poison = M<T>::fma(xb, T(0), poison); }
-#define G_ROW_OPERAND(r)                                                                           \
-    T xb, db[GC];                                                                                  \
-    if ((r) < (uint32_t)F) {                                                                       \
-        int seed;                                                                                  \
-        G_LEAF_ROW(r)                                                                              \
-        DE_UNROLL for (int k = 0; k < GC; k++) db[k] = (k == seed) ? T(1) : T(0);                  \
-    } else {                                                                                       \
-        const T *__restrict__ s_ = G_SLOT(r);                                                      \
-        xb = s_[0];                                                                                \
-        DE_UNROLL for (int k = 0; k < GC; k++) db[k] = s_[(1 + k) * RS];                           \
+    template <int K> static __device__ __forceinline__ BG<T> bin(T lx, T ly) {
+        BG<T> r;
+        if (K == 0) { r.v = lx + ly; r.gx = T(1); r.gy = T(1); }
+        else if (K == 1 || K == 2) { r.v = lx - ly; r.gx = T(1); r.gy = T(-1); }
+        else if (K == 3) { r.v = lx * ly; r.gx = ly; r.gy = lx; }
+        else { r.v = lx / ly; r.gx = T(1) / ly; r.gy = -(r.v / ly); }
+        return r;
     }
-#define G_CONST_OPERAND()                                                                          \
-    const T xb = gimm<T>(w.z, w.w);                                                                \
-    T db[GC];                                                                                      \
-    { const int seed = (int)(w.y & 0xFFFFu) + const_seed0;                                         \
-      DE_UNROLL for (int k = 0; k < GC; k++) db[k] = (k == seed) ? T(1) : T(0); }
-#define G_CHK() if (a.check) poison = M<T>::fma(x, T(0), poison);
-            // binary hot ops: value v and partials (gl, gr) w.r.t. (left, right); REV: left = operand
-#define G_BIN_APPLY(K)                                                                             \
-    {                                                                                              \
-        constexpr bool REV = (K == 2 || K == 5);                                                   \
-        const T lx = REV ? xb : x, ly = REV ? x : xb;                                              \
-        T v, gl, gr;                                                                               \
-        if (K == 0) { v = lx + ly; gl = T(1); gr = T(1); }                                         \
-        else if (K == 1 || K == 2) { v = lx - ly; gl = T(1); gr = T(-1); }                         \
-        else if (K == 3) { v = lx * ly; gl = ly; gr = lx; }                                        \
-        else { v = lx / ly; gl = T(1) / ly; gr = -(v / ly); }                                      \
-        x = v;                                                                                     \
-        if (REV) { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = gl * db[k] + gr * d[k]; }         \
-        else { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = gl * d[k] + gr * db[k]; }             \
-    }
-#define G_BIN4(K)                                                                                  \
-    case BOP_BIN_BASE + 4 * K + 0: { G_ROW_OPERAND(w.y) G_BIN_APPLY(K) } break;                    \
-    case BOP_BIN_BASE + 4 * K + 1: { G_ROW_OPERAND(w.y) G_BIN_APPLY(K) G_CHK() } break;            \
-    case BOP_BIN_BASE + 4 * K + 2: { G_CONST_OPERAND() G_BIN_APPLY(K) } break;                     \
-    case BOP_BIN_BASE + 4 * K + 3: { G_CONST_OPERAND() G_BIN_APPLY(K) G_CHK() } break;
-            // unary hot ops (K: 0 cos, 1 exp, 2 sin) on xin with incoming gradient din[]
-#define G_UN_APPLY(K, XIN, DIN)                                                                    \
-    {                                                                                              \
-        const T xin_ = (XIN);                                                                      \
-        UG<T> r;                                                                                   \
-        if (sizeof(T) == 4) {                                                                      \
-            if (K == 1) { r.y = (T)fast_exp_f32((float)xin_); r.g = r.y; }                         \
-            else {                                                                                 \
-                float sn, cs;                                                                      \
-                fast_sincos_f32((float)xin_, &sn, &cs);                                            \
-                if (K == 0) { r.y = (T)cs; r.g = (T)-sn; } else { r.y = (T)sn; r.g = (T)cs; }      \
-                /* per ELEMENT: a sample's value must not depend on its wave neighbours */         \
-                if (__ballot(M<T>::abs(xin_) > T(DE_TRIG_FAST_BOUND)) != 0ull) {                   \
-                    const UG<T> slow = unary_vg<T>(K == 0 ? DE_U_COS : DE_U_SIN, xin_);            \
-                    if (M<T>::abs(xin_) > T(DE_TRIG_FAST_BOUND)) r = slow;                         \
-                }                                                                                  \
-            }                                                                                      \
-        } else r = unary_vg<T>(K == 0 ? DE_U_COS : (K == 1 ? DE_U_EXP : DE_U_SIN), xin_);          \
-        x = r.y;                                                                                   \
-        DE_UNROLL for (int k = 0; k < GC; k++) d[k] = r.g * DIN[k];                                \
-    }
-#define G_UN4(K)                                                                                   \
-    case BOP_UN_BASE + 4 * K + 0: G_UN_APPLY(K, x, d) break;                                       \
-    case BOP_UN_BASE + 4 * K + 1: G_UN_APPLY(K, x, d) G_CHK() break;                               \
-    case BOP_UN_BASE + 4 * K + 2: { G_ROW_OPERAND(w.y) G_UN_APPLY(K, xb, db) } break;              \
-    case BOP_UN_BASE + 4 * K + 3: { G_ROW_OPERAND(w.y) G_UN_APPLY(K, xb, db) G_CHK() } break;
-            // generic (cold) operators through the noinline value+partials functions
-#define G_GEN_APPLY(OP, SRC_IS_ACC)                                                                \
-    {                                                                                              \
-        const uint32_t gop_ = (OP);                                                                 \
-        if (gop_ < DE_B_ADD) {                                                                      \
-            const UG<T> r = unary_vg<T>(gop_, SRC_IS_ACC ? x : xb);                                 \
-            x = r.y;                                                                               \
-            if (SRC_IS_ACC) { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = r.g * d[k]; }          \
-            else { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = r.g * db[k]; }                    \
-        } else {                                                                                   \
-            uint32_t fop = gop_;                                                                    \
-            bool rev = false;                                                                      \
-            switch (gop_) {                                                                         \
-            case DOP_RSUB: fop = DE_B_SUB; rev = true; break;                                      \
-            case DOP_RDIV: fop = DE_B_DIV; rev = true; break;                                      \
-            case DOP_RPOW: fop = DE_B_POW; rev = true; break;                                      \
-            case DOP_RMOD: fop = DE_B_MOD; rev = true; break;                                      \
-            case DOP_RREM: fop = DE_B_REM; rev = true; break;                                      \
-            case DOP_RGREATER: fop = DE_B_GREATER; rev = true; break;                              \
-            case DOP_RPOW_ABS2: fop = DE_B_POW_ABS2; rev = true; break;                            \
-            case DOP_RMAX: fop = DE_B_MAX; rev = true; break;                                      \
-            case DOP_RMIN: fop = DE_B_MIN; rev = true; break;                                      \
-            default: break;                                                                        \
-            }                                                                                      \
-            const BG<T> r = rev ? binary_vg<T>(fop, xb, x) : binary_vg<T>(fop, x, xb);             \
-            x = r.v;                                                                               \
-            if (rev) { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = r.gx * db[k] + r.gy * d[k]; } \
-            else { DE_UNROLL for (int k = 0; k < GC; k++) d[k] = r.gx * d[k] + r.gy * db[k]; }     \
-        }                                                                                          \
-    }
-            switch (w.x) {
-            case BOP_LOAD_ROW: { G_ROW_OPERAND(w.y) x = xb; DE_UNROLL for (int k = 0; k < GC; k++) d[k] = db[k]; } break;
-            case BOP_LOAD_CONST: { G_CONST_OPERAND() x = xb; DE_UNROLL for (int k = 0; k < GC; k++) d[k] = db[k]; } break;
-            case BOP_PUSH: {
-                T *__restrict__ s_ = G_SLOT(w.y);
-                s_[0] = x;
-                DE_UNROLL for (int k = 0; k < GC; k++) s_[(1 + k) * RS] = d[k];
-            } break;
-            case BOP_CHECK_ROW: break; // every leaf operand is tested where it is read (G_LEAF_ROW)
-            case BOP_CHECK_ACC: G_CHK() break;
-            G_BIN4(0) G_BIN4(1) G_BIN4(2) G_BIN4(3) G_BIN4(4) G_BIN4(5)
-            G_UN4(0) G_UN4(1) G_UN4(2)
-            case BOP_GEN_ROW: { G_ROW_OPERAND(w.y & 0xFFFFFFu) G_GEN_APPLY(w.y >> 24, false) } break;
-            case BOP_GEN_CONST: { G_CONST_OPERAND() G_GEN_APPLY(w.y >> 24, false) } break;
-            case BOP_GEN_ACC: { const T xb = x; T db[GC]; DE_UNROLL for (int k = 0; k < GC; k++) db[k] = d[k]; G_GEN_APPLY(w.y >> 24, true) } break;
-            case BOP_GEN_PARAM: {
-                const uint32_t prow = w.y & 0xFFFFu, op_ = w.y >> 24;
-                const T xb = a.params[prow + a.ld_params * cls];
-                if (a.check) poison = M<T>::fma(xb, T(0), poison);
-                T db[GC];
-                { const int seed = (int)prow + param_seed0; DE_UNROLL for (int k = 0; k < GC; k++) db[k] = (k == seed) ? T(1) : T(0); }
-                if (op_ == DOP_LOAD) { x = xb; DE_UNROLL for (int k = 0; k < GC; k++) d[k] = db[k]; }
-                else G_GEN_APPLY(op_, false)
-            } break;
-            case BOP_TERN: { // acc = op3(row B, row C, acc)
-                const T *__restrict__ sb = G_SLOT(w.y & 0xFFFFFFu);
-                const T *__restrict__ sc = G_SLOT(w.z);
-                const TG<T> r = ternary_vg<T>(w.y >> 24, sb[0], sc[0], x);
-                x = r.v;
-                DE_UNROLL for (int k = 0; k < GC; k++) d[k] = (r.g0 * sb[(1 + k) * RS] + r.g1 * sc[(1 + k) * RS]) + r.g2 * d[k];
-            } break;
-            default: break;
-            }
-        }
-        // a non-finite d[k] always survives to the root (every update is linear in it), so the gradient
-        // is validity-tested once, here; x was tested where the lowering kept a test (H_CHECK_OUT)
-        if (a.check) {
-            poison = M<T>::fma(x, T(0), poison);
-            DE_UNROLL for (int k = 0; k < GC; k++) poison = M<T>::fma(g0 + k < G ? d[k] : T(0), T(0), poison); // real rows only
-        }
-        if constexpr (FIT) {
-            const int64_t n_cols = col_off[a.n_trees];
-            T *__restrict__ pp = a.partial + ((int64_t)tm.tile * n_cols + col_off[tree]) * 4 + (tid >> 6);
-            const bool in = wv != T(0), l63 = (tid & 63) == 63;
-            const T yc = yv - a.loss_param; // the centred target: loss_param = T(mean_y)
-            const T sw = gwave_lane63(wave_sum_to_lane63(wv)), sy = gwave_lane63(wave_sum_to_lane63(in ? wv * x : T(0)));
-            const T m = sw != T(0) ? sy / sw : T(0);
-            const T dx = x - m;
-            if (g0 == 0) {
-                const T wd = wv * dx;
-                const T s1 = wave_sum_to_lane63(in ? wd : T(0)), b = wave_sum_to_lane63(in ? M<T>::fma(wd, dx, T(0)) : T(0));
-                const T cc = wave_sum_to_lane63(in ? M<T>::fma(wd, yc, T(0)) : T(0)), r = wave_sum_to_lane63(in ? wv * yc : T(0));
-                if (l63) { pp[0] = m; pp[4] = s1; pp[8] = b; pp[12] = cc; pp[16] = sw; pp[20] = r; }
-            }
-            T *__restrict__ pd = pp + FIT_COLS * 4;
-            DE_UNROLL for (int k = 0; k < GC; k++) {
-                if (g0 + k < G) { // wave-uniform
-                    const T wdk = wv * d[k];
-                    const T cd = wave_sum_to_lane63(in ? wdk : T(0)), cp = wave_sum_to_lane63(in ? M<T>::fma(wdk, dx, T(0)) : T(0));
-                    const T cq = wave_sum_to_lane63(in ? M<T>::fma(wdk, yc, T(0)) : T(0));
-                    if (l63) {
-                        pd[(int64_t)(g0 + k) * 4] = cd;
-                        pd[(int64_t)(G + g0 + k) * 4] = cp;
-                        pd[(int64_t)(2 * G + g0 + k) * 4] = cq;
-                    }
+    template <int K> static __device__ __forceinline__ T bin_dual(T gl, T dl, T gr, T dr) { return gl * dl + gr * dr; }
+    template <int K> static __device__ __forceinline__ UG<T> un(T xin) {
+        UG<T> r;
+        if (sizeof(T) == 4) {
+            if (K == 1) { r.y = (T)fast_exp_f32((float)xin); r.g = r.y; }
+            else {
+                float sn, cs;
+                fast_sincos_f32((float)xin, &sn, &cs);
+                if (K == 0) { r.y = (T)cs; r.g = (T)-sn; } else { r.y = (T)sn; r.g = (T)cs; }
+                // per ELEMENT: a sample's value must not depend on its wave neighbours
+                if (__ballot(M<T>::abs(xin) > T(DE_TRIG_FAST_BOUND)) != 0ull) {
+                    const UG<T> slow = unary_vg<T>(K == 0 ? DE_U_COS : DE_U_SIN, xin);
+                    if (M<T>::abs(xin) > T(DE_TRIG_FAST_BOUND)) r = slow;
                 }
             }
-            if (a.loss_mode == FIT_MODE_JTJ && g0 == 0 && G <= GC) {
-                T *__restrict__ pj = pd + (int64_t)(3 * G) * 4;
-                DE_UNROLL for (int k = 0; k < GC; k++) {
-                    if (k < G) { // wave-uniform
-                        DE_UNROLL for (int i = 0; i <= k; i++) {
-                            const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wv * d[i]) * d[k]);
-                            if (l63) pj[(k * (k + 1) / 2 + i) * 4] = s;
-                        }
-                    }
-                }
-            }
-        } else
-        if (a.loss_mode) {
-            const LossTerm<T> lt = loss_term<T>(a.loss_mode, x, yv, wv, a.loss_param);
-            const int64_t n_cols = col_off[a.n_trees];
-            T *__restrict__ pp = a.partial + ((int64_t)tm.tile * n_cols + col_off[tree]) * 4 + (tid >> 6);
-            if (g0 == 0) {
-                const T s = wave_sum_to_lane63(lt.l);
-                if ((tid & 63) == 63) pp[0] = s;
-            }
-            DE_UNROLL for (int k = 0; k < GC; k++) {
-                if (g0 + k < G) { // wave-uniform
-                    const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : lt.lp * d[k]);
-                    if ((tid & 63) == 63) pp[(int64_t)(1 + g0 + k) * 4] = s;
-                }
-            }
-            if constexpr (GN) {
-                if (g0 == 0 && G <= GC) {
-                    T *__restrict__ pj = pp + (int64_t)(1 + G) * 4;
-                    // w c: the kind's curvature weight (de_loss_kinds.h loss_kind_curv); L2 keeps the plain weight it had
-                    T wc = wv;
-                    if (a.loss_mode != 1 + DE_LOSS_L2) wc = wv * loss_kind_curv_ool<T>(a.loss_mode - 1, x, yv, a.loss_param, a.loss_floor);
-                    DE_UNROLL for (int k = 0; k < GC; k++) {
-                        if (k < G) { // wave-uniform
-                            DE_UNROLL for (int i = 0; i <= k; i++) {
-                                const T s = wave_sum_to_lane63(wv == T(0) ? T(0) : (wc * d[i]) * d[k]);
-                                if ((tid & 63) == 63) pj[(k * (k + 1) / 2 + i) * 4] = s;
-                            }
-                        }
-                    }
-                }
-            }
-        } else if (live) {
-            if (a.diff_g0 >= 0) {
-                if (a.out) a.out[(int64_t)tree * a.ld_out + base + tid] = x;
-                a.grad[(int64_t)tree * a.ld_out + base + tid] = d[0];
-            } else {
-                if (a.out && g0 == 0) a.out[(int64_t)tree * a.ld_out + base + tid] = x;
-                T *__restrict__ gp = a.grad + grad_off[tree] + (int64_t)G * (base + tid) + g0;
-                DE_UNROLL for (int k = 0; k < GC; k++)
-                    if (g0 + k < G) gp[k] = d[k];
-            }
-        }
-        if (a.check && __ballot(poison != poison) != 0ull) gflag_incomplete(a.ok + tree, a.skip_flagged == 1);
+        } else r = unary_vg<T>(K == 0 ? DE_U_COS : (K == 1 ? DE_U_EXP : DE_U_SIN), xin);
+        return r;
     }
-}
+    static __device__ __forceinline__ T scale(T g, T d) { return g * d; }
+    static __device__ __forceinline__ T chain2(T g1, T d1, T g2, T d2) { return g1 * d1 + g2 * d2; }
+    static __device__ __forceinline__ T chain3(T g0, T a, T g1, T b, T g2, T c) { return (g0 * a + g1 * b) + g2 * c; }
+    static __device__ __forceinline__ UG<T> unary(uint32_t op, T x) { return unary_vg<T>(op, x); }
+    static __device__ __forceinline__ BG<T> binary(uint32_t op, T x, T y) { return binary_vg<T>(op, x, y); }
+    static __device__ __forceinline__ TG<T> ternary(uint32_t op, T x, T y, T z) { return ternary_vg<T>(op, x, y, z); }
+};
 
 // Pass 3 of the fused loss+pullback reduction: thread = one reduction column (a tree's loss or one of its
 // gradient rows; the owner is found by bisection in col_off); fixed summation order.  NaN where the evaluation
@@ -548,96 +300,6 @@ template <typename T> static hipError_t fit_grad_finish_t(const GradArgs &ga, in
     return hipGetLastError();
 }
 
-// ---- one launch path for the three gradient kernels ----------------------------------------------------------------------------------
-// The kernel arguments every gradient kernel shares, from the caller's GradArgs; every other field is 0.  What is particular to a
-// kernel — its code pointers, the trees of the launch (tree_ids / n_trees), n_slots, n_tiles, the parameter rows behind F, share /
-// var_stride, rev_*, tile_range, diff_g0 / check — is set by that kernel's own lines below.
-template <typename T> static GArgs<T> make_gargs(const GradArgs &ga) {
-    const EvalArgs &e = ga.e;
-    GArgs<T> a = {};
-    a.X = static_cast<const T *>(e.X);
-    a.out = static_cast<T *>(e.out);
-    a.grad = static_cast<T *>(ga.grad);
-    a.grad_off = ga.grad_off;
-    a.n_grad = ga.n_grad;
-    a.ok = e.ok;
-    a.params = static_cast<const T *>(e.params);
-    a.classes = e.classes;
-    a.N = e.N;
-    a.ldX = e.ldX;
-    a.ld_out = e.ld_out;
-    a.ld_params = e.ld_params;
-    a.F = a.FX = e.F;
-    a.P = ga.P;
-    a.n_all_trees = e.n_trees;
-    a.mode = ga.mode;
-    a.classes_is_i64 = e.classes_is_i64;
-    a.class_base = e.class_base;
-    a.n_classes = e.n_classes > 0 ? e.n_classes : 1;
-    a.uses_params = e.uses_params ? 1 : 0;
-    a.check = 1;
-    a.skip_flagged = e.skip_flagged ? 1 : 0;
-    a.diff_g0 = -1;
-    if (ga.loss) {
-        a.loss_mode = 1 + ga.loss->kind;
-        a.loss_param = (T)ga.loss->param;
-        a.loss_floor = (T)ga.loss->e_floor;
-        a.y = static_cast<const T *>(ga.loss->y);
-        a.w = static_cast<const T *>(ga.loss->w);
-        a.partial = static_cast<T *>(ga.loss->partial);
-        a.col_off = ga.col_off;
-    }
-    return a;
-}
-
-// Plans and starts one gradient launch: a.n_trees trees x a.n_tiles sample tiles x `windows` gradient windows (grid.y) of `kern`, the
-// host stub of a kernel that takes (GArgs<T>, handler base, parameter handler offset) — the flat kernel: the first of them —, with
-// `lds` bytes of dynamic LDS.  prio_keys != null: the launch has priority tiles (de_kernels.hip de_tile_extremes_kernel) of
-// prio_tile_samples samples each; prio_cached: grad_flag_protocol (de_plan.h).
-template <typename T>
-static hipError_t launch_grad_kernel(const void *kern, GArgs<T> a, int windows, size_t lds, const void *prio_keys, int prio_tile_samples,
-                                     bool prio_cached, uint64_t handler_base, uint32_t param_off, hipStream_t stream) {
-    grad_chunk_plan(a.n_trees, a.n_tiles, windows, cu_count(), &a.trees_per_chunk, &a.n_chunks);
-    if (a.skip_flagged) a.skip_flagged = grad_flag_protocol(a.trees_per_chunk, prio_cached, env_int("DE_SKIP_PROTOCOL", 0));
-    const int64_t blocks = ((a.n_tiles + 7) / 8) * 8 * a.n_chunks;
-    if (blocks <= 0 || blocks > 0x7fffffffLL || windows > 65535) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        const hipError_t st = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (st != hipSuccess) return st;
-    }
-    if (a.skip_flagged && prio_keys) { // the priority tiles as a launch of their own in front, in short chunks (de_kernels.hip launch_threaded_t: no blind first wave)
-        GArgs<T> pa = a;
-        pa.prio = static_cast<const unsigned long long *>(prio_keys);
-        pa.n_prio = (uint32_t)(3 * a.FX);
-        while ((64 << pa.prio_shift) < prio_tile_samples) ++pa.prio_shift;
-        pa.trees_per_chunk = 4;
-        pa.n_chunks = (int32_t)((a.n_trees + 3) / 4);
-        pa.n_prio_blocks = (uint32_t)(((int64_t)pa.n_prio * pa.n_chunks + 7) / 8 * 8);
-        void *pargs[] = {&pa, &handler_base, &param_off};
-        const hipError_t ps = hipLaunchKernel(kern, dim3(pa.n_prio_blocks, (unsigned)windows), dim3(GBLK), pargs, lds, stream);
-        if (ps != hipSuccess) return ps;
-    }
-    void *args[] = {&a, &handler_base, &param_off};
-    return hipLaunchKernel(kern, dim3((unsigned)blocks, (unsigned)windows), dim3(GBLK), args, lds, stream);
-}
-
-template <typename T, int GC, bool GN = false, bool FIT = false>
-static hipError_t launch_grad_t(const GradArgs &ga, int windows, hipStream_t stream) {
-    const EvalArgs &e = ga.e;
-    GArgs<T> a = make_gargs<T>(ga);
-    a.code = ga.generic_code;
-    a.code_off = e.code_off;
-    a.n_trees = e.n_trees;
-    a.n_slots = e.n_slots;
-    a.n_tiles = (e.N + GBLK - 1) / GBLK;
-    a.check = ga.diff_direction >= 0 ? 0 : 1;
-    a.diff_g0 = ga.diff_direction >= 0 ? ga.P + ga.diff_direction : -1;
-    const size_t lds = (size_t)(a.F + (size_t)a.n_slots * (1 + GC)) * (GBLK + 4) * sizeof(T);
-    const hipError_t st = launch_grad_kernel(reinterpret_cast<const void *>(&de_grad_tape_kernel<T, GC, GN, FIT>), a, windows, lds, nullptr, 0, false, 0, 0, stream);
-    if (st != hipSuccess || !ga.loss) return st;
-    return launch_loss_grad_finish(sizeof(T) == 4 ? DE_F32 : DE_F64, ga, a.n_tiles, stream);
-}
 
 // passes 2 and 3 of the deterministic loss-gradient reduction (pass 2 is shared with de_eval_loss)
 template <typename T> static hipError_t loss_grad_finish_t(const GradArgs &ga, int64_t n_tiles, hipStream_t stream) {
@@ -669,18 +331,6 @@ hipError_t launch_loss_grad_finish_range(int dtype, const GradArgs &ga, int64_t 
 }
 hipError_t launch_loss_grad_finish(int dtype, const GradArgs &ga, int64_t n_tiles, hipStream_t stream) {
     return dtype == DE_F32 ? loss_grad_finish_t<float>(ga, n_tiles, stream) : loss_grad_finish_t<double>(ga, n_tiles, stream);
-}
-
-template <typename T, bool GN = false, bool FIT = false> static hipError_t launch_grad_dt(const GradArgs &ga, hipStream_t stream) {
-    const int maxg = ga.max_grad < 1 ? 1 : ga.max_grad;
-    // smallest window that covers the widest gradient in one pass, else windows of 8
-    if (maxg <= 1) return launch_grad_t<T, 1, GN, FIT>(ga, 1, stream);
-    if (maxg <= 2) return launch_grad_t<T, 2, GN, FIT>(ga, 1, stream);
-    if (maxg <= 3) return launch_grad_t<T, 3, GN, FIT>(ga, 1, stream);
-    if (maxg <= 4) return launch_grad_t<T, 4, GN, FIT>(ga, 1, stream);
-    if (maxg <= 5) return launch_grad_t<T, 5, GN, FIT>(ga, 1, stream);
-    if (maxg <= 6) return launch_grad_t<T, 6, GN, FIT>(ga, 1, stream);
-    return launch_grad_t<T, 8, GN, FIT>(ga, (maxg + 7) / 8, stream);
 }
 
 // ---- de_eval_loss_grad_by_class: fold the per-class passes into the outputs ---------------------------
@@ -982,12 +632,11 @@ hipError_t launch_rev_threaded(int dtype, const GradArgs &a0, hipStream_t stream
 
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name) {
     if (a.threaded_code && a.diff_direction < 0) return launch_grad_threaded(dtype, a, stream, kernel_name);
-    if (kernel_name) *kernel_name = a.fit ? "de_grad_tape_kernel<FIT>" : a.gn ? "de_grad_tape_kernel<GN>" : "de_grad_tape_kernel";
-    if (a.diff_direction >= 0) return dtype == DE_F32 ? launch_grad_t<float, 1>(a, 1, stream) : launch_grad_t<double, 1>(a, 1, stream);
-    if (a.fit) return dtype == DE_F32 ? launch_grad_dt<float, false, true>(a, stream) : launch_grad_dt<double, false, true>(a, stream);
-    if (a.gn) return dtype == DE_F32 ? launch_grad_dt<float, true>(a, stream) : launch_grad_dt<double, true>(a, stream);
-    if (dtype == DE_F32) return launch_grad_dt<float>(a, stream);
-    return launch_grad_dt<double>(a, stream);
+    // (eval_diff — diff_direction >= 0: launch_grad_dt's window of 1 — comes from grad_impl alone, which sets neither fit nor gn: the plain kernel)
+    if (kernel_name) *kernel_name = RealGrad<float>::NAMES[a.fit ? 2 : a.gn ? 1 : 0];
+    if (a.fit) return dtype == DE_F32 ? launch_grad_dt<RealGrad<float>, false, true>(a, stream) : launch_grad_dt<RealGrad<double>, false, true>(a, stream);
+    if (a.gn) return dtype == DE_F32 ? launch_grad_dt<RealGrad<float>, true>(a, stream) : launch_grad_dt<RealGrad<double>, true>(a, stream);
+    return dtype == DE_F32 ? launch_grad_dt<RealGrad<float>>(a, stream) : launch_grad_dt<RealGrad<double>>(a, stream);
 }
 
 } // namespace de

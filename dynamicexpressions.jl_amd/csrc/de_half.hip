@@ -53,40 +53,9 @@ struct HalfPolicy {
     typedef HV LY, LW; // (binary16 targets and weights, widened exactly)
     static constexpr bool LOSS_ALL_KINDS = false;
 
-    // coalesced read of binary16 pairs, transposed Float32 write (sample j of row f at rows[f * ROWV * 4 + j])
+    // coalesced read of binary16 pairs, transposed Float32 write (sample j of row f at rows[f * ROWV * 4 + j]): de_half_ops.h
     static __device__ __forceinline__ void stage_x(const FlatArgs<_Float16> &a, unsigned char *smem, int64_t base, int tid) {
-        float *__restrict__ rows = reinterpret_cast<float *>(smem);
-        const uint32_t F = (uint32_t)a.F;
-        const uint32_t total = (uint32_t)TILE * F;
-        if (a.ldX == (int64_t)F && base + TILE <= a.N) {
-            const _Float16 *__restrict__ src = a.X + base * (int64_t)F; // contiguous TILE * F elements (an even count)
-            if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0) {
-                const uint32_t *__restrict__ s2 = reinterpret_cast<const uint32_t *>(src);
-                for (uint32_t e2 = tid; e2 < total / 2; e2 += FLAT_BLK) {
-                    const uint32_t w = s2[e2];
-                    _Float16 h[2];
-                    __builtin_memcpy(h, &w, 4);
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const uint32_t e = 2 * e2 + k, j = e / F, f = e - j * F;
-                        rows[f * (ROWV * VW) + j] = (float)h[k];
-                    }
-                }
-            } else {
-                for (uint32_t e = tid; e < total; e += FLAT_BLK) {
-                    const uint32_t j = e / F, f = e - j * F;
-                    rows[f * (ROWV * VW) + j] = (float)src[e];
-                }
-            }
-        } else { // ragged tail / strided X: samples past N repeat the last one
-            const int64_t last = a.N - 1;
-            for (uint32_t e = tid; e < total; e += FLAT_BLK) {
-                const uint32_t j = e / F, f = e - j * F;
-                int64_t jj = base + j;
-                jj = jj < last ? jj : last;
-                rows[f * (ROWV * VW) + j] = (float)a.X[f + a.ldX * jj];
-            }
-        }
+        h16_stage_x(reinterpret_cast<float *>(smem), a.X, a.ldX, (uint32_t)a.F, base, a.N, tid, TILE, ROWV * VW, FLAT_BLK);
     }
     static __device__ __forceinline__ V load_row(const unsigned char *smem, uint32_t r, int tid) { return reinterpret_cast<const V *>(smem)[(size_t)r * ROWV + tid]; }
     static __device__ __forceinline__ void store_row(unsigned char *smem, uint32_t r, int tid, V v) { reinterpret_cast<V *>(smem)[(size_t)r * ROWV + tid] = v; }

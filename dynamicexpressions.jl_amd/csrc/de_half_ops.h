@@ -1,4 +1,5 @@
-// de_half_ops.h — the binary16 (DE_F16) operator table of de_half.hip: Julia's Float16 arithmetic as STEPS in Float32 registers.
+// de_half_ops.h — the binary16 (DE_F16) operator table of de_half.hip and de_half_grad.hip, and the staging of their X tile
+// (h16_stage_x): Julia's Float16 arithmetic as STEPS in Float32 registers.
 //
 // Every operand is a binary16 value held exactly in a float; every step computes in Float32 with the Float32 operator code of
 // de_device_ops.h and rounds its result to binary16 (r16: v_cvt_f16_f32, round to nearest even, then back), so an F16 cos is exactly
@@ -97,6 +98,44 @@ __device__ __forceinline__ float h16_op3(uint32_t op, float x, float y, float z)
     case DE_T_CLAMP: return x > z ? z : (x < y ? y : x);
     case DE_T_ADD3: return r16(r16(x + y) + z);
     default: return jl_max(jl_max(x, y), z);
+    }
+}
+
+// A workgroup's binary16 X tile — `samples` samples from sample `base`, F features each — read once with coalesced loads by `threads`
+// threads and written TRANSPOSED into LDS as Float32 rows (binary16 -> Float32 is exact): sample j of feature f at rows[f * stride + j].
+// Aligned pairs where the tile is contiguous and its first element 4-byte aligned, single elements where the pointer is 2 mod 4, and the
+// clamped path for a ragged or strided tile.  (de_half.hip: the eval tile; de_half_grad.hip: the gradient tile.)
+__device__ __forceinline__ void h16_stage_x(float *__restrict__ rows, const _Float16 *__restrict__ X, int64_t ldX, uint32_t F, int64_t base, int64_t N,
+                                            int tid, uint32_t samples, uint32_t stride, uint32_t threads) {
+    const uint32_t total = samples * F;
+    if (ldX == (int64_t)F && base + samples <= N) {
+        const _Float16 *__restrict__ src = X + base * (int64_t)F; // contiguous samples * F elements (an even count)
+        if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0) {
+            const uint32_t *__restrict__ s2 = reinterpret_cast<const uint32_t *>(src);
+            for (uint32_t e2 = tid; e2 < total / 2; e2 += threads) {
+                const uint32_t w = s2[e2];
+                _Float16 h[2];
+                __builtin_memcpy(h, &w, 4);
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const uint32_t e = 2 * e2 + k, j = e / F, f = e - j * F;
+                    rows[f * stride + j] = (float)h[k];
+                }
+            }
+        } else {
+            for (uint32_t e = tid; e < total; e += threads) {
+                const uint32_t j = e / F, f = e - j * F;
+                rows[f * stride + j] = (float)src[e];
+            }
+        }
+    } else { // ragged tail / strided X: samples past N repeat the last one
+        const int64_t last = N - 1;
+        for (uint32_t e = tid; e < total; e += threads) {
+            const uint32_t j = e / F, f = e - j * F;
+            int64_t jj = base + j;
+            jj = jj < last ? jj : last;
+            rows[f * stride + j] = (float)X[f + ldX * jj];
+        }
     }
 }
 

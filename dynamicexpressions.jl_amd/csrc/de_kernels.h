@@ -204,11 +204,14 @@ hipError_t launch_eval_flat(int dtype, const EvalArgs &a, hipStream_t stream, co
 hipError_t launch_eval_f16(const EvalArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t launch_eval_complex(int io, const EvalArgs &a, const void *ctab, hipStream_t stream, const char **kernel_name);
 hipError_t launch_grad(int dtype, const GradArgs &a, hipStream_t stream, const char **kernel_name);
+// The tape kernel (de_grad_tape.h), for the caller's check and for the launch: the window a gradient of max_grad rows is launched with
+// — the gradient itself up to 6 rows (at least 1), else windows of 8 — and the LDS bytes of a launch: rows of 256 samples + 4 of padding,
+// X, then 1 + window rows per spill slot, in the kernel's value type (v_bytes: 4 for Float32 and for binary16, whose rows are Float32; 8).
+constexpr int grad_window(int max_grad) { return max_grad <= 1 ? 1 : (max_grad <= 6 ? max_grad : 8); }
+constexpr int GRAD_TAPE_ROW = 260;
+constexpr size_t grad_tape_lds_bytes(int64_t F, int64_t n_slots, int window, size_t v_bytes) { return (size_t)(F + n_slots * (1 + window)) * GRAD_TAPE_ROW * v_bytes; }
 // DE_F16 programs with DE_OPT_F16_GRAD (de_half_grad.hip): de_eval_grad / de_eval_diff in binary16 steps.  X, params,
-// out and grad are binary16; a.generic_code is the program's generic bound stream (Float32 immediates that hold binary16 values).  Its
-// LDS rows — X, then 1 + window rows per spill slot — are Float32: 256 samples + 4 of padding.
-constexpr size_t GRAD_F16_ROW_BYTES = 260 * 4;
-constexpr size_t grad_f16_lds_bytes(int64_t F, int64_t n_slots, int64_t window) { return (size_t)(F + n_slots * (1 + window)) * GRAD_F16_ROW_BYTES; }
+// out and grad are binary16; a.generic_code is the program's generic bound stream (Float32 immediates that hold binary16 values).
 hipError_t launch_grad_f16(const GradArgs &a, hipStream_t stream, const char **kernel_name);
 
 // Threaded gradient kernels: handler addresses for (dtype, window, samples per lane), launch; pass 2+3 of the fused loss-gradient reduction.
