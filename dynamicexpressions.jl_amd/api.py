@@ -71,7 +71,22 @@ EXPORTS = [
     "de_fit_tree_params_lbfgs",
     "de_ties_pack_host", "de_ties_unpack_host", "de_ties_fold_host", "de_ties_fold_matrix_host",
     "de_fit_consts_bfgs_tied", "de_fit_consts_lbfgs_tied", "de_fit_consts_nm_tied", "de_fit_consts_lm_tied",
+    "de_memo_rows_max", "de_memo_rows_assign", "de_program_memo_rows", "de_program_last_memo_named",
 ]
+
+
+MEMO_ROWS_MAX = 6  # csrc/de_bind.h DE_MEMO_MAX: the entries of the memo-row arrays
+
+
+def memo_rows_assign(words, n_features: int, n_rows: int) -> list:
+    """``de_memo_rows_assign`` (host-only): ``[(operator, feature, uses)]`` for stage-4 words (uint32, 4 per instruction) of any
+    number of trees behind each other."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+    k, f, u = np.zeros(MEMO_ROWS_MAX, np.int32), np.zeros(MEMO_ROWS_MAX, np.int32), np.zeros(MEMO_ROWS_MAX, np.int64)
+    n = int(library().de_memo_rows_assign(w.ctypes.data if w.size else None, w.size // 4, n_features, n_rows, k.ctypes.data, f.ctypes.data, u.ctypes.data))
+    if n < 0:
+        raise DeviceError(f"de_memo_rows_assign failed ({-n})")
+    return [(int(k[r]), int(f[r]), int(u[r])) for r in range(n)]
 
 
 class DeviceError(RuntimeError):
@@ -1074,6 +1089,14 @@ def library() -> C.CDLL:
     lib.de_eval_plan.argtypes = [vp, i64, vp]
     lib.de_prio_tiles_wanted.argtypes = [i64, i32, i64]
     lib.de_program_last_live_trees.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(lib, "de_memo_rows_assign"):  # (absent from a library built before the memo rows: DE_HIP_LIB in an A/B run)
+        lib.de_memo_rows_max.restype = i32
+        lib.de_memo_rows_max.argtypes = []
+        lib.de_memo_rows_assign.restype = i32
+        lib.de_memo_rows_assign.argtypes = [vp, i64, i32, i32, vp, vp, vp]
+        lib.de_program_memo_rows.restype = i32
+        lib.de_program_memo_rows.argtypes = [vp, vp, vp, vp]
+        lib.de_program_last_memo_named.argtypes = [vp, vp]
     lib.de_dist_unique_id.argtypes = [vp]
     lib.de_dist_init.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.de_dist_destroy.argtypes = [vp]
@@ -1644,6 +1667,22 @@ class Population:
         n = C.c_int64(-1)
         self.ctx.check(library().de_program_last_live_trees(self._h, C.byref(n)))
         return int(n.value)
+
+    def memo_rows(self) -> list:
+        """The memo rows of the program (``de_program_memo_rows``): ``[(operator, feature, uses)]`` — row r of the eval chain remembers
+        operator (0 cos, 1 exp) of the 0-based feature for the rest of a chunk; empty without assured streams."""
+        k, f, u = np.zeros(MEMO_ROWS_MAX, np.int32), np.zeros(MEMO_ROWS_MAX, np.int32), np.zeros(MEMO_ROWS_MAX, np.int64)
+        n = int(library().de_program_memo_rows(self._h, k.ctypes.data, f.ctypes.data, u.ctypes.data))
+        if n < 0:
+            raise DeviceError("de_program_memo_rows failed")
+        return [(int(k[r]), int(f[r]), int(u[r])) for r in range(n)]
+
+    def last_memo_named(self) -> list:
+        """Records of the tightest assured tier's compact stream that the most recent ``eval`` handed to each memo row's handlers
+        (``de_program_last_memo_named``); -1 everywhere when that call did not compact its live trees."""
+        v = np.zeros(MEMO_ROWS_MAX, np.int64)
+        self.ctx.check(library().de_program_last_memo_named(self._h, v.ctypes.data))
+        return [int(x) for x in v]
 
     def n_grad(self, tree: int, mode: int) -> int:
         return int(library().de_program_n_grad(self._h, tree, mode))

@@ -365,6 +365,7 @@ static int eval_impl(de_ctx_t *c, de_program_t *p, const void *X, int64_t N, int
     a.assured_xmax = (float)p->assured_xmax;
     a.assured_tight_xmax = (float)p->assured_tight_xmax;
     a.assured_tight_amin = (float)p->assured_tight_amin;
+    a.memo = a.assured > 0 && p->memo.n > 0 ? &p->memo : nullptr; // (the memo rows of a compacted store launch: de_kernels.h)
     if (cr) { // the certificate pass: the un-elided program through the flat-switch kernel's CERT variant, nothing stored
         a.code = p->d_cert_code;
         a.code_off = p->d_cert_off;

@@ -224,6 +224,10 @@ struct de_program {
     // an id the wide pass does not, else 1 (0: no assured stream).
     // assured_tiers_room: the tiers the device arena was sized for (0: not allocated yet) — a re-bind of the same program keeps that many.
     int assured_tiers_cfg = 2, assured_tiers = 0, assured_tiers_room = 0;
+    // MEMO ROWS (de_bind.h memo_assign, de_kernels.hip h_unrow_fast<.., MROW>): which cos / exp of a feature gets which memo row of the eval chain — the
+    // most frequent pairs among the tightest assured tier's untested unary(feature row) instructions.  Made with the assured streams
+    // (creation, de_program_update); a set of the constants keeps it: a feature leaf has no constant.  n == 0: none.
+    MemoAssign memo;
     double assured_tight_xmax = 8.0, assured_tight_amin = 0x1p-19;
     std::vector<uint32_t> aids2;
     uint64_t end_handler = 0;

@@ -565,7 +565,7 @@ static int upload_program(de_ctx *ctx, de_program *p, CreateTimer &tm) {
     const size_t abytes = p->threaded ? 2 * nvar * cbytes : cbytes;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t off_bytes = p->bcode_off.size() * sizeof(int32_t);
-    const size_t ints_bytes = p->threaded ? ((size_t)2 * (size_t)p->n_trees + 5) * sizeof(int32_t) : 0;
+    const size_t ints_bytes = p->threaded ? ((size_t)2 * (size_t)p->n_trees + 5 + (size_t)DE_MEMO_MAX) * sizeof(int32_t) : 0; // (+ the records re-named per memo row)
     const size_t o_off = al(abytes), o_ints = o_off + al(off_bytes), o_ok = o_ints + al(ints_bytes);
     const size_t total = o_ok + al((size_t)std::max<int64_t>(p->n_trees, 1));
     const hipError_t ast = prog_malloc(ctx, reinterpret_cast<void **>(&p->d_code), total); // (one 4 GiB window: prog_malloc's contract)
@@ -859,6 +859,32 @@ int de_program_last_live_trees(de_program_t *p, int64_t *n_live) {
     int32_t v = -1;
     HIP_TRY(c, hipMemcpy(&v, p->d_compact_ints + (2 * (size_t)p->n_trees + 1), sizeof v, hipMemcpyDeviceToHost));
     *n_live = v;
+    return DE_OK;
+}
+
+// The memo rows of the program (de_api_internal.h `memo`): row r remembers operator k[r] (0 cos, 1 exp) of feature feat[r] (0-based), which
+// uses[r] instructions of the tightest assured tier evaluate.  Arrays of de_memo_rows_max() entries, any may be null.  Returns the rows.
+int32_t de_program_memo_rows(const de_program_t *p, int32_t *k, int32_t *feat, int64_t *uses) {
+    if (!p) return -1;
+    for (int r = 0; r < p->memo.n; r++) {
+        if (k) k[r] = p->memo.k[r];
+        if (feat) feat[r] = p->memo.feat[r];
+        if (uses) uses[r] = p->memo.uses[r];
+    }
+    return p->memo.n;
+}
+// What the most recent eval launch re-named: named[r] = the records of the LAST stream variant handed to memo row r's handlers
+// (de_memo_rows_max() entries); all -1 when that launch did not compact its live trees (synchronises the stream like de_program_last_live_trees).
+int de_program_last_memo_named(de_program_t *p, int64_t *named) {
+    if (!p || !named) return DE_ERR_INVALID_ARG;
+    for (int r = 0; r < DE_MEMO_MAX; r++) named[r] = -1;
+    if (!p->last_compacted || !p->d_compact_ints) return DE_OK;
+    de_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int32_t v[DE_MEMO_MAX];
+    HIP_TRY(c, hipMemcpy(v, p->d_compact_ints + (2 * (size_t)p->n_trees + 5), sizeof v, hipMemcpyDeviceToHost));
+    for (int r = 0; r < DE_MEMO_MAX; r++) named[r] = v[r];
     return DE_OK;
 }
 

@@ -76,6 +76,7 @@ void rebind(de_program *p, const Reuse *ru = nullptr);
 int make_threaded(de_ctx *c, de_program *p, const Reuse *ru = nullptr);
 void assure_program_tree(const de_program *p, int tier, int32_t i0, int32_t i1, AssuredInstr *info);
 void assured_link_trees(de_program *p, const uint64_t *table, int64_t tb, int64_t te, bool touched_only = false, int tier = 1);
+void program_memo_assign(const de_program *p, MemoAssign *out); // (what make_assured stores in p->memo; de_program_verify re-derives it)
 hipError_t upload_wave_variants(de_program *p);
 double assured_xmax_env();
 uint32_t assured_parts_env();

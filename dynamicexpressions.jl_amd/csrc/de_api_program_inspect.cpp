@@ -243,6 +243,19 @@ static int verify_assured(const de_program *p, const uint64_t *table) {
             if (ev >= 0 && named(cw[(size_t)(h + (i1 - i0) - 1)]) != named(cw[(size_t)(h + (i1 - i0))])) return verify_bad(p, "assured stream: end-fused instruction and end record disagree", t, i1 - i0, 0);
         }
     }
+    // the memo rows: what the count over the present ids gives, every row a FEATURE row (a slot row differs from tree to tree), no pair twice
+    MemoAssign want;
+    program_memo_assign(p, &want);
+    if (p->memo.n < 0 || p->memo.n > eval_memo_rows() || (p->assured_valid && p->memo.n != want.n)) return verify_bad(p, "memo rows: count", -1, p->memo.n, (uint64_t)want.n);
+    for (int r = 0; r < p->memo.n; r++) {
+        if (p->memo.k[r] < 0 || p->memo.k[r] > 1 || p->memo.feat[r] < 0 || p->memo.feat[r] >= p->n_features) return verify_bad(p, "memo rows: not a feature row", -1, r, (uint64_t)p->memo.feat[r]);
+        for (int q = 0; q < r; q++)
+            if (p->memo.k[q] == p->memo.k[r] && p->memo.feat[q] == p->memo.feat[r]) return verify_bad(p, "memo rows: a pair assigned twice", -1, r, (uint64_t)q);
+        if (p->assured_valid && (p->memo.k[r] != want.k[r] || p->memo.feat[r] != want.feat[r] || p->memo.uses[r] != want.uses[r]))
+            return verify_bad(p, "memo rows: stale assignment", -1, r, (uint64_t)want.feat[r]);
+    }
+    for (int k = 0; k < 2; k++) for (int ps = 0; ps < 2; ps++) for (int r = 0; r < DE_MEMO_MAX; r++) // (a row the build lacks keeps the handler it would stand in for)
+        if ((r < eval_memo_rows()) == (table[topx_memo(k, ps != 0, r)] == table[topa_unrow_plain(k, ps != 0)])) return verify_bad(p, "memo rows: handler table", -1, r, table[topx_memo(k, ps != 0, r)]);
     return DE_OK;
 }
 // Program sanitizer (SURVEY.md §5 "sanitizer / bounds-checked debug"): the kernels trust the instruction streams —
@@ -424,6 +437,25 @@ int64_t de_lower_tape_assured_fact(const de_tape_node_t *nodes, int64_t n_nodes,
             o[4] = (double)info[i].id; o[5] = (double)info[i].bits;
         }
         return n;
+    } catch (...) {
+        return -DE_ERR_HIP;
+    }
+}
+
+// Host-only: which cos / exp of a feature gets which memo row of the eval chain (de_bind.h memo_assign — the function a program calls on
+// its tightest assured tier).  words = n_instr instructions of stage-4 words (de_lower_tape_stage: {assured id, operand word, immediate}),
+// any number of trees behind each other; n_rows = the rows to give out (de_memo_rows_max() is what the library's kernels have).
+int32_t de_memo_rows_max(void) { return eval_memo_rows(); }
+int32_t de_memo_rows_assign(const uint32_t *words, int64_t n_instr, int32_t n_features, int32_t n_rows, int32_t *k, int32_t *feat, int64_t *uses) {
+    if (n_instr < 0 || (n_instr > 0 && !words) || n_features < 0 || n_rows < 0) return -DE_ERR_INVALID_ARG;
+    try {
+        const MemoAssign m = memo_assign(words, 4, words ? words + 1 : nullptr, 4, (size_t)n_instr, n_features, n_rows);
+        for (int r = 0; r < m.n; r++) {
+            if (k) k[r] = m.k[r];
+            if (feat) feat[r] = m.feat[r];
+            if (uses) uses[r] = m.uses[r];
+        }
+        return m.n;
     } catch (...) {
         return -DE_ERR_HIP;
     }

@@ -244,6 +244,7 @@ int make_threaded(de_ctx *c, de_program *p, const Reuse *ru) {
     p->assured_tiers = 0;
     p->aids.clear();
     p->aids2.clear();
+    p->memo = MemoAssign{};
     assured_configure(p, ru ? ru->old : nullptr);
     dbg_lap(nullptr);
     if (!wants_threaded(p)) return DE_OK;
@@ -435,6 +436,14 @@ static void make_assured(de_program *p, const uint64_t *table) {
     p->assured_tiers = p->aids2.empty() ? 1 : 2;
     p->var_stride = (int64_t)(p->bcode.size() + (size_t)p->n_trees + 2);
     p->assured = p->assured_valid = true;
+    program_memo_assign(p, &p->memo);
+}
+// the program's memo rows (de_api_internal.h `memo`): counted over the tightest tier, the stream nearly every tile of bounded data runs
+void program_memo_assign(const de_program *p, MemoAssign *out) {
+    const std::vector<uint32_t> &ids = p->aids2.empty() ? p->aids : p->aids2;
+    *out = MemoAssign{};
+    if (!p->assured || ids.size() != p->fbcode.size() || ids.empty()) return;
+    *out = memo_assign(ids.data(), 1, &p->fbcode[0].arg, sizeof(BoundInstr) / sizeof(uint32_t), ids.size(), p->n_features, eval_memo_rows());
 }
 // the stream variants of waves 1 .. (wave groups) to their places behind variant 0
 hipError_t upload_wave_variants(de_program *p) {

@@ -426,4 +426,29 @@ void assure_tree_fact(const BoundInstr *f, size_t n, int n_features, double xmax
     }
 }
 
+MemoAssign memo_assign(const uint32_t *ids, size_t id_stride, const uint32_t *args, size_t arg_stride, size_t n, int32_t n_features, int32_t n_rows) {
+    MemoAssign m;
+    if (n_rows > DE_MEMO_MAX) n_rows = DE_MEMO_MAX;
+    if (!ids || !args || n_features <= 0 || n_rows <= 0) return m;
+    std::vector<int64_t> count((size_t)2 * (size_t)n_features, 0); // [k][feature row]
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t id = ids[i * id_stride], row = args[i * arg_stride] & 0xFFFFFFu;
+        if (row >= (uint32_t)n_features) continue;
+        for (int k = 0; k < 2; k++)
+            if (id == topa_unrow_plain(k, false) || id == topa_unrow_plain(k, true)) count[(size_t)k * (size_t)n_features + row]++;
+    }
+    // the n_rows largest counts; `count` is in (k, feature) order, so the first of equal counts is the smaller pair
+    for (; m.n < n_rows; m.n++) {
+        size_t best = count.size();
+        for (size_t j = 0; j < count.size(); j++)
+            if (count[j] > 0 && (best == count.size() || count[j] > count[best])) best = j;
+        if (best == count.size()) break;
+        m.k[m.n] = (int32_t)(best / (size_t)n_features);
+        m.feat[m.n] = (int32_t)(best % (size_t)n_features);
+        m.uses[m.n] = count[best];
+        count[best] = 0;
+    }
+    return m;
+}
+
 } // namespace de

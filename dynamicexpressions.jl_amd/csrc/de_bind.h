@@ -226,7 +226,23 @@ constexpr int topx_enda_guarded(int q) { // ... and the TOPX_ENDV slot of the gu
     return q < 12 ? q : q < 36 ? (4 + (q - 12) / 12) * 2 + ((((q - 12) / 3) & 3) >> 1) : q < 38 ? 12 + (q - 36) : 12 + (q - 38) / 2;
 }
 constexpr uint32_t TOPX_AUX_BASE = TOPX_ENDA_BASE + TOPX_ENDA_COUNT; // + 0: h_tree_end_slow, + 1: h_tree_skip
-constexpr uint32_t TOPX_TABLE = TOPX_AUX_BASE + 2;
+// ... and the MEMO handlers of the eval kernel (de_kernels.hip h_unrow_fast<.., MROW>; Float32, exact mode): cos / exp of a feature row that remembers its
+// result for the rest of the chunk in argument row `row`.  Table entries only, like the twins above: no stream names them, the
+// compaction kernel does, by address, in the compact stream of a store launch.  + ((k * 2 + push) * DE_MEMO_MAX + row), k < 2; a row
+// the build does not have (and every entry of another element type or of turbo) holds the assured handler it would stand in for.
+constexpr int DE_MEMO_MAX = 6; // rows a build can have: the two loss vectors + DE_MEMO_ROWS <= 4 (de_kernels.h)
+constexpr uint32_t TOPX_MEMO_BASE = TOPX_AUX_BASE + 2;
+constexpr uint32_t TOPX_MEMO_COUNT = 4 * (uint32_t)DE_MEMO_MAX;
+constexpr uint32_t topx_memo(int k, bool push, int row) { return TOPX_MEMO_BASE + (uint32_t)((k * 2 + (push ? 1 : 0)) * DE_MEMO_MAX + row); }
+constexpr uint32_t topa_unrow_plain(int k, bool push) { return TOPA_UNROW_BASE + top_unrow(k, false, push, false) - TOP_UNROW_BASE; } // the id a memo handler stands in for
+constexpr uint32_t TOPX_TABLE = TOPX_MEMO_BASE + TOPX_MEMO_COUNT;
+// WHICH (operator, feature) pair gets which memo row: the n_rows most frequent pairs among the instructions whose ASSURED id is
+// topa_unrow_plain(k, push) and whose operand row is a feature (row < n_features; a spill slot holds another value in every tree), ties to
+// the smaller (k, feature).  ids[i] / args[i]: the assured id and the operand word (BoundInstr::arg) of fused instruction i.  Returns the
+// rows assigned (<= n_rows; fewer pairs than rows: that many); row r holds operator k[r] of feature row feat[r], used uses[r] times.
+struct MemoAssign { int32_t n = 0; int32_t k[DE_MEMO_MAX] = {}, feat[DE_MEMO_MAX] = {}; int64_t uses[DE_MEMO_MAX] = {}; };
+// (id_stride / arg_stride: words between two instructions' entries — 1 for a plain array, 4 for a field of BoundInstr)
+MemoAssign memo_assign(const uint32_t *ids, size_t id_stride, const uint32_t *args, size_t arg_stride, size_t n, int32_t n_features, int32_t n_rows);
 // chained stream (de_api_program.cpp make_chained): bit 31 of a tree header's length word = the tree finishes in an end-fused handler
 constexpr uint32_t DE_HDR_FUSED_END = 0x80000000u;
 // end variant of a fused / bound handler id, or -1

@@ -30,6 +30,19 @@ constexpr int TBLK = DE_TBLK, TWAVES = DE_TBLK / 64;
 #ifndef DE_TG
 #define DE_TG 1
 #endif
+// MEMO ROWS (de_kernels.hip h_unrow_fast<.., MROW>): in a store launch the two loss vectors of the Float32 eval chain and DE_MEMO_ROWS more
+// vector arguments behind them remember cos / exp of a feature row for the rest of a chunk.  The shipped build has NO further row: the
+// eval kernels stand at 79 vector + 11 accumulation registers (96 with the allocation granule: 5 waves per SIMD, what LDS allows too), a
+// row pins 4 vector registers in every handler and the heaviest ones park 4 more in accumulation registers around their calls — one
+// row is 99 -> 104 registers and the fifth wave (measured: profiles/memo_rows_ab.txt).  1 .. 4 build and pass the tests (A/B runs).
+// DE_MEMO_HANDLERS = 0: no memo handler at all.  eval_memo_rows(): the rows the module was built with.
+#ifndef DE_MEMO_ROWS
+#define DE_MEMO_ROWS 0
+#endif
+#ifndef DE_MEMO_HANDLERS
+#define DE_MEMO_HANDLERS 1
+#endif
+int eval_memo_rows(); // DE_MEMO_ROWS + 2, or 0 without the handlers (de_kernels.hip)
 constexpr int TG_F32 = DE_TG, TG_F64 = 1;
 constexpr int tg_planes(int dtype) { return dtype == DE_F32 ? TG_F32 : TG_F64; }
 constexpr int ttile_samples(int dtype) { return TBLK * tg_planes(dtype) * (dtype == DE_F32 ? 4 : 2); } // samples per workgroup tile
@@ -111,6 +124,10 @@ struct EvalArgs {
     // assured_tight_amin <= |x| <= assured_tight_xmax; a tile runs the tightest stream whose fact it passes
     int32_t assured = 0;
     float assured_xmax = 0.0f, assured_tight_xmax = 0.0f, assured_tight_amin = 0.0f;
+    // MEMO ROWS (de_bind.h MemoAssign, de_kernels.hip h_unrow_fast<.., MROW>): the program's (operator, feature) -> row table, or null.  A compacted STORE
+    // launch of a program with assured streams names the memo handlers in the assured variants of the compact stream; compact_ints then
+    // carries DE_MEMO_MAX more words behind the control words: the records re-named per row in the last variant.
+    const MemoAssign *memo = nullptr;
     // de_eval_sum_certificate: device array of n_trees zeroed words of the element type's size; non-null selects the CERT variant of the
     // flat-switch kernel (no output): the bits of the largest |validity-tested value| of every tree
     void *cert_max;

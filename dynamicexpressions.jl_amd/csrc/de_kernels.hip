@@ -251,16 +251,82 @@ template <typename T> using BodyFn = BState<T> (*)(BState<T>, uint32_t, typename
 #ifndef DE_NO_LOSS
 #define DE_NO_LOSS 0
 #endif
+// MEMO ROWS: DE_MEMO_ROWS more vectors behind (ly0, lw0), handed on untouched like them.  In a STORE launch the two
+// loss vectors are dead, so a chain carries DE_MEMO_NROWS = DE_MEMO_ROWS + 2 rows in which the first tree of a chunk that evaluates
+// cos(x_f) / exp(x_f) leaves the result for the trees behind it (h_unrow_fast<.., MROW> below); which rows are valid is a wave-uniform mask in the bits
+// of `left` that no handler reads (DE_MEMO_BIT).  DE_MEMO_ROWS = 0 (the shipped build: every further row costs the resident wave the
+// kernel cannot spare, de_kernels.h): the signature and the registers of the build without them, two rows.  DE_MEMO_HANDLERS = 0: no memo
+// handler either — that build's module.  One plane, fused-loss signature only.
+#if DE_NO_LOSS || DE_TG != 1
+#undef DE_MEMO_ROWS
+#define DE_MEMO_ROWS 0
+#undef DE_MEMO_HANDLERS
+#define DE_MEMO_HANDLERS 0
+#endif
+#if DE_MEMO_HANDLERS
+#define DE_MEMO_NROWS (DE_MEMO_ROWS + 2)
+#else
+#define DE_MEMO_NROWS 0
+#endif
+// (Float32 chains only: for every other element type the arguments are EMPTY structs, which the calling convention drops — the Float64
+// handlers, cos / sin with their stack frames among them, keep the registers and the code they had)
+struct MemoNone {};
+template <typename T> struct MemoArg { typedef MemoNone type; };
+template <> struct MemoArg<float> { typedef VecOf<float>::type type; };
+#define HM_T typename MemoArg<T>::type
+#if DE_MEMO_ROWS == 0
+#define HM_PARAMS_C(V)
+#define HM_PASS_C
+#define HM_TYPES_C(V)
+#define HM_ZERO_C(Z)
+#define HM_ROW_PTRS &ly0, &lw0
+#elif DE_MEMO_ROWS == 1
+#define HM_PARAMS_C(V) V m0,
+#define HM_PASS_C m0,
+#define HM_TYPES_C(V) V,
+#define HM_ZERO_C(Z) Z,
+#define HM_ROW_PTRS &ly0, &lw0, &m0
+#elif DE_MEMO_ROWS == 2
+#define HM_PARAMS_C(V) V m0, V m1,
+#define HM_PASS_C m0, m1,
+#define HM_TYPES_C(V) V, V,
+#define HM_ZERO_C(Z) Z, Z,
+#define HM_ROW_PTRS &ly0, &lw0, &m0, &m1
+#elif DE_MEMO_ROWS == 3
+#define HM_PARAMS_C(V) V m0, V m1, V m2,
+#define HM_PASS_C m0, m1, m2,
+#define HM_TYPES_C(V) V, V, V,
+#define HM_ZERO_C(Z) Z, Z, Z,
+#define HM_ROW_PTRS &ly0, &lw0, &m0, &m1, &m2
+#elif DE_MEMO_ROWS == 4
+#define HM_PARAMS_C(V) V m0, V m1, V m2, V m3,
+#define HM_PASS_C m0, m1, m2, m3,
+#define HM_TYPES_C(V) V, V, V, V,
+#define HM_ZERO_C(Z) Z, Z, Z, Z,
+#define HM_ROW_PTRS &ly0, &lw0, &m0, &m1, &m2, &m3
+#else
+#error "DE_MEMO_ROWS: 0 .. 4 (the calling convention passes 32 vector registers)"
+#endif
+static_assert(DE_MEMO_NROWS <= DE_MEMO_MAX, "de_bind.h DE_MEMO_MAX");
+// the memo mask lives in `left` above the count of trees (<= 63): h_tree_skip, the only reader of the count, keeps the bits
+#define DE_MEMO_BIT(ROW) (1u << (8 + (ROW)))
+#if DE_MEMO_NROWS > 0
+#define DE_LEFT_COUNT(L) ((L) & 0xFFu)
+#define DE_LEFT_KEEP(L, N) (((L) & ~0xFFu) | (N))
+#else
+#define DE_LEFT_COUNT(L) (L)
+#define DE_LEFT_KEEP(L, N) (N)
+#endif
 #if DE_NO_LOSS
 #define HL_PARAMS_C
 #define HL_PASS_C
 #define HL_BOTH(ly, lw) const HLoss<T> ly{}, lw{}
 #define HL_TYPES_C(V)
 #elif DE_TG == 1
-#define HL_PARAMS_C HL_T ly0, HL_T lw0,
-#define HL_PASS_C ly0, lw0,
+#define HL_PARAMS_C HL_T ly0, HL_T lw0, HM_PARAMS_C(HM_T)
+#define HL_PASS_C ly0, lw0, HM_PASS_C
 #define HL_BOTH(ly, lw) const HLoss<T> ly{{ly0, ly0}}, lw{{lw0, lw0}}
-#define HL_TYPES_C(V) V, V,
+#define HL_TYPES_C(V) V, V, HM_TYPES_C(HM_T)
 #else
 #define HL_PARAMS_C HL_T ly0, HL_T ly1, HL_T lw0, HL_T lw1,
 #define HL_PASS_C ly0, ly1, lw0, lw1,
@@ -364,10 +430,10 @@ __device__ __forceinline__ bool poison_set(const double &p) { return p != p; }
 // cycles per skipped tree and wavefront, 0.65 ms of the 7.9 ms headline; tools/exp_skip_cost.py.)
 template <typename T> __device__ __noinline__ HState<T> h_tree_skip(HCHAIN_ARGS) { // bit 0 of `skip` = the next tree of the stream, which is skipped
     const uint32_t n = (uint32_t)__builtin_ctzll(~skip); // the run of skipped trees (>= 1; bit `left` is the sentinel behind the last tree, nothing above it)
-    if (n >= left) return st;
+    if (n >= DE_LEFT_COUNT(left)) return st;
     skip >>= n;
-    left -= n;
-    const uint32_t r = left - (uint32_t)__builtin_popcountll(skip >> 1); // live trees after the one the chain goes on with (the count holds the sentinel)
+    left -= n; // (the count stays above 0: no borrow into the memo mask)
+    const uint32_t r = DE_LEFT_COUNT(left) - (uint32_t)__builtin_popcountll(skip >> 1); // live trees after the one the chain goes on with (the count holds the sentinel)
     const uint32_t lb = (flags >> (HF_LIST_SHIFT - 4)) & (HF_LIST_MASK << 4); // this wave's list (0 unless the workgroup is a wave group)
     const uint32_t lo = *reinterpret_cast<__attribute__((address_space(3))) uint32_t *>((uintptr_t)(lb + r * 4u)); // (wave-uniform address)
     const uint64_t hdr = ((uint64_t)(uintptr_t)code & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
@@ -397,7 +463,7 @@ template <typename T> __device__ __noinline__ HState<T> h_tree_skip(HCHAIN_ARGS)
     de_end_special:;                                                                                         \
         const uint32_t left_now = 63u - (uint32_t)__builtin_clzll(skip); /* trees left including this one = the sentinel's bit */ \
         if (left_now <= 1u) return st;                                                                       \
-        [[clang::musttail]] return h_tree_skip<T>(st, HL_PASS_C lds0, HDR, outp, la, w1, w23, okp, ldo, skip >> 1, left_now - 1u, flags); \
+        [[clang::musttail]] return h_tree_skip<T>(st, HL_PASS_C lds0, HDR, outp, la, w1, w23, okp, ldo, skip >> 1, DE_LEFT_KEEP(left, left_now - 1u), flags); \
     }
 // the output store of a tree's fast end: 16 bytes per lane, 1 KiB contiguous per wavefront.  -DDE_NT_STORE=1 (an A/B switch): non-temporal
 // (the 40 GB output stream of the headline is written once and never read by the kernel)
@@ -932,7 +998,7 @@ template <int K, bool TB, int G> __device__ __forceinline__ void un_finish_plane
 #if DE_NO_LOSS
 #define HFAST_LOSS_C
 #elif DE_TG == 1
-#define HFAST_LOSS_C VecOf<float>::type ly0, VecOf<float>::type lw0,
+#define HFAST_LOSS_C VecOf<float>::type ly0, VecOf<float>::type lw0, HM_PARAMS_C(VecOf<float>::type)
 #else
 #define HFAST_LOSS_C VecOf<float>::type ly0, VecOf<float>::type ly1, VecOf<float>::type lw0, VecOf<float>::type lw1,
 #endif
@@ -998,11 +1064,37 @@ template <int K, bool TB, bool NT = false, bool OUT = true> __device__ __noinlin
     HFAST_END_TAIL()
 }
 // ... fused with a spill of the accumulator and / or the validity test of its row operand (b_unrow_f)
-template <int K, bool OUT, bool PUSH, bool CHK, bool TB, bool NT = false> __device__ __noinline__ HState<float> h_unrow_fast(HFAST_ARGS) {
+// MROW >= 0: a MEMO HANDLER — the form <K, false, PUSH, false, false, true>, cos / exp of a FEATURE row in the assured
+// stream with no test left, with a memory of one chunk.  Every tree of a chain evaluates on the same X tile, so cos(x_f) is the same
+// vector in all of them: the first tree that needs it computes it (the same un_pretest / un_finish on the same LDS row: the same bits)
+// INTO the argument row MROW and sets the row's bit in `left`; every later one copies the row.  Named by de_compact_live_kernel alone, in
+// the compact stream of a store launch (MemoSubst): no stream id, no record of the program's own streams ever points here.  The mask
+// starts at zero with every chain call (the kernel passes the bare count) and h_tree_skip keeps it: a row filled by a tree that later
+// workgroups skip is filled by whichever tree comes first THERE.
+template <int K, bool OUT, bool PUSH, bool CHK, bool TB, bool NT = false, int MROW = -1> __device__ __noinline__ HState<float> h_unrow_fast(HFAST_ARGS) {
     typedef float T;
     constexpr int G = TG<T>::G;
     const U32x4 w = *code;
     const uint32_t a = lds0 + la;
+#if DE_MEMO_NROWS > 0
+    if constexpr (MROW >= 0) {
+        static_assert(MROW < 0 || (G == 1 && MROW < DE_MEMO_NROWS && NT && !OUT && !CHK && !TB), "one plane; a row the signature has; the untested form");
+        if constexpr (PUSH) *LDSP(T, push_addr<T>(a)) = st.acc[0];
+        VecOf<float>::type *const mrows[DE_MEMO_NROWS] = {HM_ROW_PTRS};
+        constexpr int R = MROW >= 0 ? MROW : 0;
+        if (left & DE_MEMO_BIT(R)) {
+            st.acc[0] = *mrows[R];
+            HFAST_NEXT(w);
+        }
+        const VecOf<float>::type xm = *LDSP(T, PUSH ? row_a(a) : a);
+        UnPre pm;
+        (void)un_pretest<K, false>(xm, pm);
+        *mrows[R] = un_finish<K, false>(xm, pm);
+        st.acc[0] = *mrows[R];
+        left |= DE_MEMO_BIT(R);
+        HFAST_NEXT(w);
+    }
+#endif
     VecOf<float>::type x[G];
     FOR_PLANES {
         if constexpr (PUSH) *LDSP(T, push_addr<T>(PLANE_ADDR(a, g))) = st.acc[g]; // first, as in b_unrow_f (the full handler would write it again: same value)
@@ -1391,14 +1483,28 @@ template <typename T, bool TB> __global__ void de_fill_handlers(uint64_t *t) {
         HEU(0) HEU(1)
 #undef HEU
     }
+    // the memo handlers (de_bind.h TOPX_MEMO_BASE): every slot starts as the assured handler it would stand in for; exact-mode Float32
+    // replaces the slots of the rows this build has
+    for (int k = 0; k < 2; k++) for (int ps = 0; ps < 2; ps++) for (int r = 0; r < DE_MEMO_MAX; r++) t[topx_memo(k, ps != 0, r)] = t[topa_unrow_plain(k, ps != 0)];
+#if DE_MEMO_NROWS > 0
+    if constexpr (sizeof(T) == 4 && !TB) {
+#define HMR(K, R) if constexpr (R < DE_MEMO_NROWS) { t[topx_memo(K, false, R)] = (uint64_t)&h_unrow_fast<K, false, false, false, false, true, (R < DE_MEMO_NROWS ? R : 0)>; \
+                                                     t[topx_memo(K, true, R)] = (uint64_t)&h_unrow_fast<K, false, true, false, false, true, (R < DE_MEMO_NROWS ? R : 0)>; }
+#define HMK(K) HMR(K, 0) HMR(K, 1) HMR(K, 2) HMR(K, 3) HMR(K, 4) HMR(K, 5)
+        HMK(0) HMK(1)
+#undef HMK
+#undef HMR
+    }
+#endif
 #undef TBK
 }
 
 // PRIORITY TILES (round 3).  A tree that is incomplete only on a few samples is evaluated on every tile until the workgroup holding
 // such a sample has run — 1.1 ms of the 7.6 ms headline.  Those samples are not anywhere: a value overflows where a
-// feature is largest or smallest, a quotient where one is closest to zero.  On the benchmark's data the 3 F tiles that hold, per
-// feature, its largest value, its smallest value and its value closest to zero flag 534 of the 557 incomplete trees (first 16 tiles
-// of the launch: 258; 16 random ones: 263; tools/exp_extremes.py).  So the launch first finds those tiles (this kernel: one pass over X,
+// feature is largest or smallest, a quotient where one is closest to zero.  On the X of rounds 1-4 (torch's device randn) the 3 F tiles that
+// hold, per feature, its largest value, its smallest value and its value closest to zero flag 534 of the 557 incomplete trees (first 16 tiles
+// of the launch: 258; 16 random ones: 263; tools/exp_extremes.py); on the PCG64 X the bench draws since round 5 they flag 302 of 354
+// (tools/exp_probe_coverage.py).  So the launch first finds those tiles (this kernel: one pass over X,
 // a record-breaking atomicMax per statistic and workgroup; F <= DE_PRIO_MAX_F) and runs them as its first workgroups — a second time, nothing is reordered: the pairs
 // stay where map_block puts them and find their trees flagged.  Order only: flags and the rows of complete trees cannot change.
 // key = orderable(value) << 32 | tile; statistic 3 f + 0: x, + 1: -x, + 2: -|x| (NaN / Inf rank first everywhere).
@@ -1455,7 +1561,7 @@ __global__ void __launch_bounds__(256) de_tile_extremes_kernel(const T *__restri
 }
 
 // COMPACTION OF THE LIVE TREES (round 4).  After the probe launch of the priority tiles most incomplete trees are flagged (534 of 557 on
-// the benchmark's data), but they stay where they are in the population: a 64-tree chunk of the launch proper holds ~28 live trees, so the
+// the X of rounds 1-4, 302 of 354 on today's), but they stay where they are in the population: a 64-tree chunk of the launch proper holds ~28 live trees, so the
 // launch runs 2.3 x the workgroups for the same live work, each staging X for fewer trees and walking ~15 runs of skipped trees (0.45 ms of
 // the 6.7 ms headline).  This kernel — one workgroup between the probe and the launch proper — RE-LINKS the chained stream:
 // the records of every tree whose flag is still 1 are copied, in population order, into a second stream in which the live trees follow
@@ -1472,6 +1578,24 @@ struct LossEnds {
     uint64_t end, slow_end; // h_tree_end, h_tree_end_slow; slow_end == 0: not a loss launch, nothing is re-named
     uint64_t endv[TOPX_ENDV_COUNT + TOPX_ENDA_COUNT], plain[TOPX_ENDV_COUNT + TOPX_ENDA_COUNT]; // (behind the guarded forms: the assured stream's twins, 0: no such twin)
 };
+// STORE launches of a program with assured streams re-name the MEMO candidates while they re-link (MemoSubst, by value):
+// a record of an assured variant whose handler is from[k][push] — cos / exp of a row, nothing tested — and whose operand row is
+// la[r] of a row r that holds operator k is handed to to[k][push][r] (h_unrow_fast<.., MROW>) instead.  A handler's address stands in the record IN FRONT
+// (the tree's header for its first instruction), so the test reads the operand word of the record behind the one it patches.
+// n == 0: nothing is re-named (a fused-loss launch: rows 0 and 1 hold targets and weights; DE_MEMO=0; variant 0, the guarded stream).
+struct MemoSubst {
+    int32_t n, first_variant;              // rows in use; the first stream variant (workgroup) that is an assured one
+    uint32_t la[DE_MEMO_MAX], k[DE_MEMO_MAX]; // row r: operand word (LDS byte offset of the feature row) and operator (0 cos, 1 exp)
+    uint64_t from[2][2], to[2][2][DE_MEMO_MAX];
+};
+// the handler word `h` of a record whose operand word is `la`: the memo handler of the row, or h itself; *row = the row (or stays -1)
+__device__ __forceinline__ uint64_t memo_named(const MemoSubst &ms, uint64_t h, uint32_t la, int *row) {
+    DE_UNROLL for (int k = 0; k < 2; k++) DE_UNROLL for (int ps = 0; ps < 2; ps++)
+        if (h == ms.from[k][ps])
+            for (int r = 0; r < ms.n; r++)
+                if (ms.k[r] == (uint32_t)k && ms.la[r] == (la & 0xFFFFFFu)) { *row = r; return ms.to[k][ps][r]; }
+    return h;
+}
 template <bool F32> __device__ __forceinline__ uint64_t rec_next(const U32x4 &r, uint64_t hi) { return F32 ? (((uint64_t)r.w << 32) | r.z) : (hi | r.y); }
 template <bool F32> __device__ __forceinline__ void rec_set_next(U32x4 &r, uint64_t h) {
     if (F32) { r.z = (uint32_t)h; r.w = (uint32_t)(h >> 32); } else r.y = (uint32_t)h;
@@ -1480,14 +1604,17 @@ template <bool F32>
 __global__ void __launch_bounds__(1024) de_compact_live_kernel(const U32x4 *__restrict__ code, const int32_t *__restrict__ code_off, const uint8_t *__restrict__ ok,
                                                               int32_t n_trees, U32x4 *__restrict__ ccode, int32_t *__restrict__ coff, int32_t *__restrict__ live_idx,
                                                               int32_t *__restrict__ ctrl, int64_t n_tiles, int64_t want_blocks, int32_t tpc_max, const LossEnds le,
-                                                              int64_t var_stride) {
+                                                              int64_t var_stride, const MemoSubst ms) {
     // (a wave group's stream variants, KArgs::var_stride: workgroup v re-links variant v; the offsets, the tree list and the plan it writes
     // are the same values in every workgroup, and each reads back only what it wrote itself)
     code += (int64_t)blockIdx.x * var_stride;
     ccode += (int64_t)blockIdx.x * var_stride;
     __shared__ int32_t wsum[2][16];
     __shared__ int32_t run[2]; // live trees / records placed so far
+    __shared__ int32_t memo_named_n[DE_MEMO_MAX]; // records re-named per memo row (the last variant reports them behind ctrl)
+    const bool memo = F32 && ms.n > 0 && (int32_t)blockIdx.x >= ms.first_variant;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid < DE_MEMO_MAX) memo_named_n[tid] = 0;
     if (tid == 0) { run[0] = 0; run[1] = 1; } // record 0 of the compact stream = the head record
     __syncthreads();
     for (int32_t b = 0; b < n_trees; b += 1024) {
@@ -1525,18 +1652,38 @@ __global__ void __launch_bounds__(1024) de_compact_live_kernel(const U32x4 *__re
     for (int32_t k = tid; k < n_live; k += 1024) {
         const int32_t t = live_idx[k], tn = k + 1 < n_live ? live_idx[k + 1] : -1;
         const int32_t src = code_off[t], len = code_off[t + 1] - src, dst = coff[k];
-        const U32x4 hdr = code[src - 1]; // this tree's header: length word (F32: .y, F64: .z) | DE_HDR_FUSED_END
-        if (k == 0) ccode[0] = hdr;      // the head record names the first live tree's first handler
+        U32x4 hdr = code[src - 1]; // this tree's header: length word (F32: .y, F64: .z) | DE_HDR_FUSED_END
+        // (memo: a handler word is re-named where it is WRITTEN — the first instruction's in the record that names the tree, below)
+        auto memo_fix = [&](U32x4 &r, uint32_t la_behind) {
+            int row = -1;
+            const uint64_t h = memo_named(ms, ((uint64_t)r.w << 32) | r.z, la_behind, &row);
+            if (row >= 0) { r.z = (uint32_t)h; r.w = (uint32_t)(h >> 32); atomicAdd(&memo_named_n[row], 1); }
+        };
+        if (k == 0) { // the head record names the first live tree's first handler
+            if (memo && len >= 2) memo_fix(hdr, code[src].x);
+            ccode[0] = hdr;
+        }
         { // four records in flight per thread: the copy is latency-bound (one workgroup, ~12 records per tree: 17 -> 10 us for 1000 trees)
             int32_t i = 0;
             for (; i + 4 <= len; i += 4) {
-                const U32x4 r0 = code[src + i], r1 = code[src + i + 1], r2 = code[src + i + 2], r3 = code[src + i + 3];
+                U32x4 r0 = code[src + i], r1 = code[src + i + 1], r2 = code[src + i + 2], r3 = code[src + i + 3];
+                if (memo) { // (record j names the handler of record j + 1: re-named while j + 1 is an INSTRUCTION record, j + 2 < len — the last
+                            // instruction of an end-fused tree names the next tree's first handler in front of an end record, whose operand word is a tree index)
+                    memo_fix(r0, r1.x); memo_fix(r1, r2.x);
+                    if (i + 4 < len) memo_fix(r2, r3.x);
+                    if (i + 5 < len) memo_fix(r3, code[src + i + 4].x);
+                }
                 ccode[dst + i] = r0; ccode[dst + i + 1] = r1; ccode[dst + i + 2] = r2; ccode[dst + i + 3] = r3;
             }
-            for (; i < len; i++) ccode[dst + i] = code[src + i];
+            for (; i < len; i++) {
+                U32x4 r = code[src + i];
+                if (memo && i + 2 < len) memo_fix(r, code[src + i + 1].x);
+                ccode[dst + i] = r;
+            }
         }
         if (tn >= 0) {
-            const U32x4 hn = code[code_off[tn] - 1]; // names the next live tree's first handler (and carries its length word)
+            U32x4 hn = code[code_off[tn] - 1]; // names the next live tree's first handler (and carries its length word)
+            if (memo && code_off[tn + 1] - code_off[tn] >= 2) memo_fix(hn, code[code_off[tn]].x);
             U32x4 e = code[src + len - 1];
             e.y = hn.y; e.z = hn.z; e.w = hn.w;       // the operand word stays: this tree's index
             ccode[dst + len - 1] = e;
@@ -1563,6 +1710,8 @@ __global__ void __launch_bounds__(1024) de_compact_live_kernel(const U32x4 *__re
             }
         }
     }
+    __syncthreads();
+    if (blockIdx.x == gridDim.x - 1 && tid < DE_MEMO_MAX) ctrl[4 + tid] = memo_named_n[tid]; // (de_program_last_memo_named)
 }
 
 // WW > 1: a WAVE GROUP (KArgs::var_stride) — WW waves of 64 lanes on one 64-lane tile; `tid` below is the lane's position in the TILE
@@ -1852,7 +2001,7 @@ __global__ void __launch_bounds__(DE_TBLK * WW) de_eval_threaded_kernel(const KA
         st = arg_next<T>(hp.y, ((uint64_t)hp.w << 32) | hp.z)(st,
 #if DE_NO_LOSS
 #elif DE_TG == 1
-                                                              yv.v[0], wv.v[0],
+                                                              yv.v[0], wv.v[0], HM_ZERO_C(HM_T{})
 #else
                                                               yv.v[0], yv.v[1], wv.v[0], wv.v[1],
 #endif
@@ -2124,6 +2273,7 @@ hipError_t handler_table(const void *fill, size_t n, uint64_t *table) {
     return hipSuccess;
 }
 
+int eval_memo_rows() { return DE_MEMO_NROWS; }
 hipError_t eval_handler_table(int dtype, bool turbo, uint64_t *table) { // Float32, Float64, Float32 turbo (Float64 has no relaxed operators)
     const void *const fill[3] = {reinterpret_cast<const void *>(&de_fill_handlers<float, false>), reinterpret_cast<const void *>(&de_fill_handlers<float, true>),
                                  reinterpret_cast<const void *>(&de_fill_handlers<double, false>)};
@@ -2432,12 +2582,30 @@ static hipError_t launch_threaded_t(const EvalArgs &e, hipStream_t stream, const
                         le.plain[TOPX_ENDV_COUNT + q] = table[topx_enda_id(q)];
                     }
             }
+            // a store launch of a program with assured streams: the memo handlers for the rows the program assigned (MemoSubst; DE_MEMO=0: off)
+            MemoSubst ms;
+            std::memset(&ms, 0, sizeof ms);
+            if (sizeof(T) == 4 && !e.loss && WW == 1 && a.assured > 0 && e.memo && e.memo->n > 0 && eval_memo_rows() > 0 && env_int("DE_MEMO", 1)) {
+                uint64_t table[TOPX_TABLE];
+                const hipError_t ts = eval_handler_table(DE_F32, e.turbo, table);
+                if (ts != hipSuccess) return ts;
+                ms.n = e.memo->n < eval_memo_rows() ? e.memo->n : eval_memo_rows();
+                ms.first_variant = 1;
+                for (int r = 0; r < ms.n; r++) {
+                    ms.la[r] = (uint32_t)e.memo->feat[r] * (uint32_t)trow_bytes(DE_F32);
+                    ms.k[r] = (uint32_t)e.memo->k[r];
+                }
+                for (int k = 0; k < 2; k++) for (int ps = 0; ps < 2; ps++) {
+                    ms.from[k][ps] = table[topa_unrow_plain(k, ps != 0)];
+                    for (int r = 0; r < DE_MEMO_MAX; r++) ms.to[k][ps][r] = table[topx_memo(k, ps != 0, r)];
+                }
+            }
             if (sizeof(T) == 4)
                 hipLaunchKernelGGL(de_compact_live_kernel<true>, dim3(n_variants), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
-                                   e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride);
+                                   e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride, ms);
             else
                 hipLaunchKernelGGL(de_compact_live_kernel<false>, dim3(n_variants), dim3(1024), 0, stream, reinterpret_cast<const U32x4 *>(e.code), e.code_off, e.ok,
-                                   e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride);
+                                   e.n_trees, reinterpret_cast<U32x4 *>(e.compact_code), coff, live_idx, ctrl, a.n_tiles, want_blocks, tpc_max, le, a.var_stride, ms);
             const hipError_t cs = hipGetLastError();
             if (cs != hipSuccess) return cs;
             a.code = static_cast<const BoundInstr *>(e.compact_code);

@@ -438,6 +438,19 @@ int64_t de_lower_tape_stage_complex(int dtype, const de_tape_node_t *nodes, int6
                                     const void *consts, int64_t n_consts, int32_t n_features,
                                     int32_t n_params, uint32_t options, int stage, uint32_t *words,
                                     int64_t cap);
+/* MEMO ROWS.  In a compacted store launch of a Float32 program with assured streams the first tree of a chunk that
+ * evaluates cos(x_f) / exp(x_f) leaves the vector in a register row of the chain and the trees behind it copy it: same bits, fewer
+ * instructions.  de_memo_rows_max(): the rows the library's eval kernel has (build macro DE_MEMO_ROWS + 2; 0: none).
+ * de_memo_rows_assign (host-only): the choice a program makes — over n_instr instructions of stage-4 words (de_lower_tape_stage, any
+ * number of trees behind each other) the n_rows (<= 6) most frequent (operator, feature) pairs among the untested cos / exp of a feature
+ * row, ties to the smaller (operator, feature); row r: k[r] (0 cos, 1 exp), feat[r] (0-based), uses[r].  Returns the rows given out or
+ * -status.  de_program_memo_rows: the same for a program (its tightest assured tier; 0 rows without assured streams).
+ * de_program_last_memo_named: named[r] (6 entries) = the records of the tightest tier's compact stream the most recent eval launch handed
+ * to row r's memo handlers; -1 everywhere when it did not compact.  DE_MEMO=0 (read at launch): no record is handed over. */
+int32_t de_memo_rows_max(void);
+int32_t de_memo_rows_assign(const uint32_t *words, int64_t n_instr, int32_t n_features, int32_t n_rows, int32_t *k, int32_t *feat, int64_t *uses);
+int32_t de_program_memo_rows(const de_program_t *prog, int32_t *k, int32_t *feat, int64_t *uses);
+int de_program_last_memo_named(de_program_t *prog, int64_t *named);
 /* Host-only hook of the GRADIENT streams (csrc/de_grad_encode.h; DE_F32 / DE_F64 only): the tape lowered and bound as the gradient entry
  * points do (unfolded, every tested value tested), then encoded for `mode` (DE_GRAD_*) against an identity handler table, so that the
  * handler word of a record is a plain gop_* / ROP_* id of csrc/de_bind.h (successor-rotated, as the kernels read it).

@@ -216,7 +216,8 @@ def table(obj, ty="float", turbo=False):
         if m:
             fast[f"h_bin<float, {m.group(1)}, {m.group(2)}, false>" if m.group(3) == "3" else "h_div_assured<%s, %s, %s>" % m.groups()] = code
             continue
-        m = re.search(r"de::h_unrow_fast<(\d), (true|false), (true|false), (true|false), (true|false), (true|false)>\(", full)  # ... and their fused forms
+        # ... and their fused forms (a seventh argument >= 0: a memo handler, DESIGN.md §4.1.2 — no stream id, not in the table)
+        m = re.search(r"de::h_unrow_fast<(\d), (true|false), (true|false), (true|false), (true|false), (true|false)(?:, -1)?>\(", full)
         if m:
             fast[("h_unrow_assured<%s, %s, %s, %s>" if m.group(6) == "true" else "h_unrow_f<float, %s, %s, %s, %s, %s>") % m.groups()[:4 if m.group(6) == "true" else 5]] = code
             continue
