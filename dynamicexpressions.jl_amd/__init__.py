@@ -30,7 +30,7 @@ def __getattr__(name):
     _api_names = {
         "EvalContext", "eval_tree_array", "eval_grad_tree_array", "eval_diff_tree_array",
         "Population", "ParametricExpression", "Expression", "library", "DeviceError", "UncertifiedFlag", "GaussNewton",
-        "ParametricPopulation",
+        "ParametricPopulation", "MiniBatch",
     }
     if name in _api_names:
         from . import api

@@ -72,6 +72,7 @@ EXPORTS = [
     "de_ties_pack_host", "de_ties_unpack_host", "de_ties_fold_host", "de_ties_fold_matrix_host",
     "de_fit_consts_bfgs_tied", "de_fit_consts_lbfgs_tied", "de_fit_consts_nm_tied", "de_fit_consts_lm_tied",
     "de_memo_rows_max", "de_memo_rows_assign", "de_program_memo_rows", "de_program_last_memo_named",
+    "de_batch_sample_rows", "de_batch_rows_host", "de_batch_gather", "de_batch_gather_host",
 ]
 
 
@@ -101,6 +102,17 @@ class UncertifiedFlag(DeviceError):
 class ParamArgs(C.Structure):
     _fields_ = [("params", C.c_void_p), ("ld_params", C.c_int64), ("n_classes", C.c_int64),
                 ("classes", C.c_void_p), ("classes_is_i64", C.c_int32), ("class_base", C.c_int32)]
+
+
+class BatchSrc(C.Structure):
+    """``de_batch_src_t``: the dataset a batch is gathered from."""
+    _fields_ = [("X", C.c_void_p), ("N", C.c_int64), ("ldX", C.c_int64), ("n_features", C.c_int32), ("classes_is_i64", C.c_int32),
+                ("y", C.c_void_p), ("w", C.c_void_p), ("classes", C.c_void_p)]
+
+
+class BatchDst(C.Structure):
+    """``de_batch_dst_t``: the buffers of the dense batch, allocated by the caller."""
+    _fields_ = [("X", C.c_void_p), ("ldX", C.c_int64), ("y", C.c_void_p), ("w", C.c_void_p), ("classes", C.c_void_p)]
 
 
 class LossSpec(C.Structure):
@@ -1116,6 +1128,11 @@ def library() -> C.CDLL:
     lib.de_ctx_timing_read.argtypes = [vp, vp, i32, C.POINTER(i32)]
     lib.de_dist_reorder_selftest.argtypes = [vp, vp, i64, C.c_int, vp, C.POINTER(C.c_float)]
     lib.de_eval_sum_certificate.argtypes = [vp, vp, vp, i64, i64, C.POINTER(ParamArgs), vp, vp, vp]
+    if hasattr(lib, "de_batch_gather"):
+        lib.de_batch_sample_rows.argtypes = [vp, C.c_int, i64, C.c_uint64, C.c_uint64, i64, i64, vp]
+        lib.de_batch_rows_host.argtypes = [C.c_int, i64, C.c_uint64, C.c_uint64, i64, i64, vp]
+        lib.de_batch_gather.argtypes = [vp, C.c_int, C.POINTER(BatchSrc), vp, i64, C.POINTER(BatchDst), vp]
+        lib.de_batch_gather_host.argtypes = [C.c_int, C.POINTER(BatchSrc), vp, i64, C.POINTER(BatchDst), vp]
     _lib = lib
     return lib
 
@@ -1262,6 +1279,77 @@ class Context:
         dt = DE_F32 if name == "torch.float32" else DE_F64
         self.check(lib.de_ctx_declare_dataset(self._h, dt, X.data_ptr(), N, ldX, F))
 
+    def sample_rows(self, N: int, n_rows: int, seed: int, step: int = 0, mode: str = "replace", offset: int = 0):
+        """``de_batch_sample_rows``: rows ``offset .. offset + n_rows - 1`` of the batch ``(mode, N, seed, step)`` as a device
+        ``torch.int64`` tensor, drawn on the context's stream with no synchronisation — ``batch_rows_host`` on the device, bit for bit."""
+        import torch
+        self.use_torch_stream()
+        rows = torch.empty(max(int(n_rows), 0), dtype=torch.int64, device=f"cuda:{self.device}")
+        self.check(library().de_batch_sample_rows(self._h, _batch_mode(mode), int(N), int(seed) & (2**64 - 1), int(step) & (2**64 - 1),
+                                                  int(offset), int(n_rows), rows.data_ptr() if rows.numel() else None))
+        return rows
+
+    def gather_batch(self, X, rows, y=None, weights=None, classes=None) -> MiniBatch:
+        """``de_batch_gather``: the rows ``rows`` of a dataset as a dense ``MiniBatch``.  ``X`` is ``[F, N]``, feature
+        index fastest as ``Population.eval`` takes it; ``y`` has X's dtype, ``weights`` its real component type, ``classes`` is int32 or
+        int64 (nothing is converted: a mismatch is a ``ValueError``).  Torch device tensors in, torch device tensors out — allocated by
+        torch, gathered by one launch on the context's stream, nothing synchronises; ``rows`` is an int64 device tensor (``sample_rows``)
+        and a row outside ``range(N)`` turns its batch row into NaN and is counted in ``MiniBatch.n_bad()``.  A host ``rows`` (numpy
+        int64) is checked first (``ValueError``).  numpy datasets are gathered on the host (``gather_batch_host``)."""
+        if not _is_torch(X):
+            return gather_batch_host(X, rows, y, weights, classes)
+        import torch
+        if X.dim() != 2 or not X.is_cuda:
+            raise ValueError("gather_batch: X must be a 2-d device tensor [n_features, N] (or a numpy array)")
+        dt, real = _batch_columns(X, True)
+        F, N = int(X.shape[0]), int(X.shape[1])
+        if not (X.stride(0) == 1 and (N <= 1 or X.stride(1) >= F)) and X.numel() > 0:
+            X = X.t().contiguous().t()
+        ldX = int(X.stride(1)) if N > 1 else max(F, 1)
+        if _is_torch(rows):
+            if rows.dtype != torch.int64 or rows.dim() != 1:
+                raise ValueError(f"gather_batch: rows must be a one-dimensional int64 tensor, got {rows.dtype}")
+            rows = rows.to(X.device).contiguous()
+            n, rows_ptr = int(rows.numel()), rows.data_ptr()
+        else:
+            rows = np.asarray(rows)
+            if rows.dtype != np.int64 or rows.ndim != 1:
+                raise ValueError(f"gather_batch: rows must be a one-dimensional int64 array, got {rows.dtype}")
+            rows = np.ascontiguousarray(rows)
+            n, rows_ptr = int(rows.size), rows.ctypes.data
+        if N == 0 and n:
+            raise ValueError("gather_batch: rows of an empty dataset")
+
+        def col(v, name, want):
+            if v is None:
+                return None, None
+            if not _is_torch(v) or v.device != X.device:
+                raise ValueError(f"gather_batch: {name} must be a tensor on X's device")
+            if want is None:
+                if v.dtype not in (torch.int32, torch.int64):
+                    raise ValueError(f"gather_batch: {name} must be int32 or int64, got {v.dtype}")
+            elif v.dtype != _torch_dtype(want):
+                raise ValueError(f"gather_batch: {name} must have dtype {want} for X of dtype {dt}, got {v.dtype}")
+            if v.numel() != N:
+                raise ValueError(f"gather_batch: {name} must have {N} entries, got {v.numel()}")
+            v = v.contiguous().reshape(-1)
+            return v, torch.empty(n, dtype=v.dtype, device=X.device)
+
+        (ys, yd), (ws, wd), (cs, cd) = col(y, "y", dt), col(weights, "weights", real), col(classes, "classes", None)
+        self.use_torch_stream()
+        Xd = torch.empty((n, F), dtype=X.dtype, device=X.device).t()  # [F, n], feature index fastest
+        n_bad = torch.empty(1, dtype=torch.int32, device=X.device)  # (the call zeroes it)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        src = BatchSrc(ptr(X), N, ldX, F, int(cs is not None and cs.dtype == torch.int64), ptr(ys), ptr(ws), ptr(cs))
+        dst = BatchDst(ptr(Xd), max(F, 1), ptr(yd), ptr(wd), ptr(cd))
+        if n:
+            self.check(library().de_batch_gather(self._h, _dtype_code(dt), C.byref(src), rows_ptr, n, C.byref(dst), n_bad.data_ptr()))
+        else:
+            n_bad.zero_()
+        mb = MiniBatch(Xd, yd, wd, cd, rows, n_bad)
+        mb._keep = (X, ys, ws, cs)  # (read in stream order)
+        return mb
+
     def last_kernel_ms(self) -> float:
         ms = C.c_float(0)
         self.check(library().de_ctx_last_kernel_ms(self._h, C.byref(ms)))
@@ -1329,6 +1417,109 @@ def _prep_X(X, dtype):
     Xf = np.asfortranarray(X, dtype=dtype)
     F, N = Xf.shape
     return Xf.ctypes.data, F, N, max(F, 1), Xf, False
+
+
+# ---- minibatches ---------------------------------------------------------------------------------------------
+BATCH_MODES = {"replace": 0, "permute": 1}  # de_batch_mode_t
+
+
+def _batch_mode(mode) -> int:
+    if mode in BATCH_MODES:
+        return BATCH_MODES[mode]
+    raise ValueError(f"mode must be one of {sorted(BATCH_MODES)}, got {mode!r}")
+
+
+def _batch_status(rc: int, what: str) -> None:
+    if rc != 0:
+        name = library().de_status_string(rc).decode()
+        raise (ValueError if rc in (1, 6) else DeviceError)(f"{name}: {what}")
+
+
+def batch_rows_host(N: int, n_rows: int, seed: int, step: int = 0, mode: str = "replace", offset: int = 0) -> np.ndarray:
+    """``de_batch_rows_host``: rows ``offset .. offset + n_rows - 1`` of the batch ``(mode, N, seed, step)`` as ``np.int64``, on the host,
+    no GPU needed — bit for bit what ``Context.sample_rows`` draws on the device (the definition: include/de_hip.h).  ``mode`` is
+    "replace" (with replacement) or "permute" (a slice of a keyed permutation of ``range(N)``: ``offset + n_rows <= N``)."""
+    rows = np.empty(max(int(n_rows), 0), dtype=np.int64)
+    rc = library().de_batch_rows_host(_batch_mode(mode), int(N), int(seed) & (2**64 - 1), int(step) & (2**64 - 1), int(offset), int(n_rows),
+                                      rows.ctypes.data if rows.size else None)
+    _batch_status(rc, f"batch_rows_host(N={N}, n_rows={n_rows}, mode={mode!r}, offset={offset})")
+    return rows
+
+
+class MiniBatch:
+    """A dense batch of ``n_rows`` rows of a dataset: ``X`` (``[F, n_rows]``, feature index fastest), ``y``, ``weights`` and ``classes``
+    (``None`` where the dataset has none) and the ``rows`` they were gathered from — torch device tensors, or numpy arrays for a numpy
+    dataset.  Every method of ``Population`` takes it as ``mb.X, mb.y, weights=mb.weights, classes=mb.classes``."""
+
+    def __init__(self, X, y, weights, classes, rows, n_bad):
+        self.X, self.y, self.weights, self.classes, self.rows = X, y, weights, classes, rows
+        self.n_rows = int(X.shape[1])
+        self._n_bad = n_bad
+
+    def n_bad(self) -> int:
+        """Row indices outside the dataset that the gather met (their batch rows hold NaN).  Reading it waits for the gather."""
+        return int(self._n_bad.item()) if _is_torch(self._n_bad) else int(self._n_bad)
+
+
+def _batch_columns(X, is_t):
+    """(element dtype, real component dtype) of a dataset's X as numpy dtypes; ``ValueError`` for a dtype the library has no code for."""
+    if is_t:
+        import torch
+        names = {torch.float32: np.float32, torch.float64: np.float64, torch.float16: np.float16, torch.complex64: np.complex64,
+                 torch.complex128: np.complex128}
+        if X.dtype not in names:
+            raise ValueError(f"gather_batch: X has dtype {X.dtype}; Float16/Float32/Float64/ComplexF32/ComplexF64 are served")
+        dt = np.dtype(names[X.dtype])
+    else:
+        dt = np.dtype(X.dtype)
+        if dt not in (np.float16, np.float32, np.float64, np.complex64, np.complex128):
+            raise ValueError(f"gather_batch: X has dtype {dt}; Float16/Float32/Float64/ComplexF32/ComplexF64 are served")
+    real = np.dtype(np.float32 if dt == np.complex64 else np.float64 if dt == np.complex128 else dt)
+    return dt, real
+
+
+def gather_batch_host(X, rows, y=None, weights=None, classes=None) -> MiniBatch:
+    """``de_batch_gather_host``: the rows ``rows`` (``np.int64``) of a numpy dataset as a ``MiniBatch`` of numpy arrays, no GPU needed.
+    ``X`` is ``[F, N]``; ``y`` has X's dtype, ``weights`` its real component type, ``classes`` is int32 or int64 — nothing is converted:
+    a mismatch is a ``ValueError``, and so is a row outside ``range(N)``."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("gather_batch: X must be [n_features, N]")
+    dt, real = _batch_columns(X, False)
+    Xf = np.asfortranarray(X)
+    F, N = Xf.shape
+    rows = np.asarray(rows)
+    if rows.dtype != np.int64 or rows.ndim != 1:
+        raise ValueError(f"gather_batch: rows must be a one-dimensional int64 array, got {rows.dtype}")
+    rows = np.ascontiguousarray(rows)
+    n = rows.size
+
+    def col(v, name, want):
+        if v is None:
+            return None, None
+        v = np.asarray(v)
+        if want is None:
+            if v.dtype not in (np.int32, np.int64):
+                raise ValueError(f"gather_batch: {name} must be int32 or int64, got {v.dtype}")
+        elif v.dtype != want:
+            raise ValueError(f"gather_batch: {name} must have dtype {want} for X of dtype {dt}, got {v.dtype}")
+        if v.size != N:
+            raise ValueError(f"gather_batch: {name} must have {N} entries, got {v.size}")
+        v = np.ascontiguousarray(v).reshape(-1)
+        return v, np.empty(n, dtype=v.dtype)
+
+    (ys, yd), (ws, wd), (cs, cd) = col(y, "y", dt), col(weights, "weights", real), col(classes, "classes", None)
+    Xd = np.empty((F, n), dtype=dt, order="F")
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    src = BatchSrc(ptr(Xf), N, max(F, 1), F, int(cs is not None and cs.dtype == np.int64), ptr(ys), ptr(ws), ptr(cs))
+    dst = BatchDst(ptr(Xd), max(F, 1), ptr(yd), ptr(wd), ptr(cd))
+    n_bad = C.c_int32(0)
+    if N == 0 and n:
+        raise ValueError("gather_batch: rows of an empty dataset")
+    if n:
+        rc = library().de_batch_gather_host(_dtype_code(dt), C.byref(src), rows.ctypes.data, n, C.byref(dst), C.byref(n_bad))
+        _batch_status(rc, f"gather_batch: a row index outside [0, {N})" if rc == 6 else "gather_batch")
+    return MiniBatch(Xd, yd, wd, cd, rows, int(n_bad.value))
 
 
 def lower_tape(tape, consts, n_features: int, n_params: int = 0, options: int = 7, dtype=np.float32):
@@ -1910,6 +2101,54 @@ class Population:
         self.ctx.check(lib.de_eval_loss_ex(self.ctx._h, self._h, ptr, N, ldX, C.byref(pa) if pa else None,
                                            yp, wp, C.byref(spec), out.ctypes.data, ok.ctypes.data))
         return out, ok.astype(bool)
+
+    def minibatch(self, X, y, n_rows: int, seed: int, step: int = 0, weights=None, classes=None, mode: str = "replace",
+                  offset: int = 0) -> MiniBatch:
+        """Sample and gather: a dense ``MiniBatch`` of ``n_rows`` rows of the dataset ``(X, y, weights, classes)``, drawn by the
+        counter-based sampler from ``(seed, step)`` (``Context.sample_rows`` + ``Context.gather_batch``; for a numpy
+        dataset ``batch_rows_host`` + ``gather_batch_host``).  ``mode`` "replace" samples with replacement, as SymbolicRegression.jl's
+        ``batching`` does; "permute" takes positions ``offset .. offset + n_rows - 1`` of a keyed permutation of the rows.  ``X`` and
+        ``y`` are converted to the population's dtype and ``weights`` to its real component type first, as ``eval_loss`` would.
+
+        No other method has a batch keyword: every one takes the batch as ``mb.X, mb.y, weights=mb.weights, classes=mb.classes`` and
+        computes on it bit for bit what it computes on the same rows gathered by any other means.  A fit keeps ONE batch for its whole
+        run (``fit_constants_bfgs_device(mb.X, mb.y, weights=mb.weights, ...)``), as the reference's search fixes one subset per constant
+        optimisation; a fresh ``step`` per scoring step redraws."""
+        dt = np.dtype(self.dtype)
+        real = np.dtype(np.float32 if dt == np.complex64 else np.float64 if dt == np.complex128 else dt)
+        if _is_torch(X):
+            import torch
+            if X.dim() != 2:
+                raise ValueError("minibatch: X must be [n_features, N]")
+            conv = lambda v, want: None if v is None else torch.as_tensor(v, device=X.device).to(_torch_dtype(want))
+            X, y, weights = conv(X, dt), conv(y, dt), conv(weights, real)
+            if classes is not None:
+                classes = torch.as_tensor(classes, device=X.device)
+                if classes.dtype not in (torch.int32, torch.int64):
+                    classes = classes.to(torch.int64)
+            self.ctx.use_torch_stream()
+            rows = self.ctx.sample_rows(int(X.shape[1]), n_rows, seed, step, mode, offset)
+            return self.ctx.gather_batch(X, rows, y, weights, classes)
+        X = np.asarray(X, dtype=dt)
+        if X.ndim != 2:
+            raise ValueError("minibatch: X must be [n_features, N]")
+        conv = lambda v, want: None if v is None else np.asarray(v, dtype=want)
+        if classes is not None:
+            classes = np.asarray(classes)
+            if classes.dtype not in (np.int32, np.int64):
+                classes = classes.astype(np.int64)
+        rows = batch_rows_host(X.shape[1], n_rows, seed, step, mode, offset)
+        return gather_batch_host(X, rows, conv(y, dt), conv(weights, real), classes)
+
+    def eval_loss_minibatch(self, X, y, n_rows: int, seed: int, step: int = 0, weights=None, loss: str = "L2", params=None, classes=None,
+                            class_base: int = 1, loss_param: float = 0.0, mode: str = "replace", offset: int = 0):
+        """``minibatch`` and ``eval_loss`` on it: ``(loss[n_trees], ok[n_trees], minibatch)`` — the stochastic scoring step of a search on
+        a large dataset, with nothing crossing to the host for a device dataset.  ``loss``, ``loss_param``, ``params`` and ``class_base``
+        as ``eval_loss`` takes them; the losses are sums over the batch's ``n_rows`` rows."""
+        mb = self.minibatch(X, y, n_rows, seed, step=step, weights=weights, classes=classes, mode=mode, offset=offset)
+        out, ok = self.eval_loss(mb.X, mb.y, weights=mb.weights, loss=loss, params=params, classes=mb.classes, class_base=class_base,
+                                 loss_param=loss_param)
+        return out, ok, mb
 
     def eval_fit_stats(self, X, y, weights=None, params=None, classes=None, class_base: int = 1):
         """The fused second-order statistics of every tree's values against ``y`` (``de_eval_fit_stats``): what Pearson correlation,

@@ -28,6 +28,7 @@ build_obj de_api_eval.cpp $OBJ/de_api_eval.o &
 build_obj de_api_grad.cpp $OBJ/de_api_grad.o &
 build_obj de_api_fit.cpp $OBJ/de_api_fit.o &
 build_obj de_api_tree_params.cpp $OBJ/de_api_tree_params.o &
+build_obj de_api_batch.cpp $OBJ/de_api_batch.o &
 build_obj de_bind.cpp $OBJ/de_bind.o &
 build_obj de_grad_encode.cpp $OBJ/de_grad_encode.o &
 build_obj de_dist.cpp $OBJ/de_dist.o &
@@ -143,8 +144,10 @@ build_obj de_fit_scaled.hip $OBJ/de_fit_scaled.o &
 build_obj de_tree_params.hip $OBJ/de_tree_params.o &
 # de_fit_consts_*_tied: the pack, unpack and fold kernels of the fits with a shared GraphNode constant as one unknown (plain hipcc)
 build_obj de_ties.hip $OBJ/de_ties.o &
+# de_batch_sample_rows / de_batch_gather: the row sampler and the batch gather of minibatches (plain hipcc)
+build_obj de_batch.hip $OBJ/de_batch.o &
 wait
-API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_program_stream.o $OBJ/de_api_program_consts.o $OBJ/de_api_program_inspect.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o"
-for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $GT_OBJS -ldl
+API_OBJS="$OBJ/de_api.o $OBJ/de_api_program.o $OBJ/de_api_program_stream.o $OBJ/de_api_program_consts.o $OBJ/de_api_program_inspect.o $OBJ/de_api_eval.o $OBJ/de_api_grad.o $OBJ/de_api_fit.o $OBJ/de_api_tree_params.o $OBJ/de_api_batch.o"
+for o in $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $OBJ/de_batch.o $GT_OBJS; do [ -f $o ] || { echo "missing $o"; exit 1; }; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJ/de_lower.o $OBJ/de_bind.o $OBJ/de_grad_encode.o $OBJ/de_dist.o $API_OBJS $OBJ/de_kernels.o $OBJ/de_grad_kernels.o $OBJ/de_flat_real.o $OBJ/de_half.o $OBJ/de_half_grad.o $OBJ/de_complex.o $OBJ/de_const_patch.o $OBJ/de_lm.o $OBJ/de_gn_wide.o $OBJ/de_lm_scaled.o $OBJ/de_lm_scaled_wide.o $OBJ/de_bfgs.o $OBJ/de_lbfgs.o $OBJ/de_nm.o $OBJ/de_fit_scaled.o $OBJ/de_tree_params.o $OBJ/de_ties.o $OBJ/de_batch.o $GT_OBJS -ldl
 echo "built $(pwd)/$OUT"

@@ -418,7 +418,7 @@ int de_ctx_destroy(de_ctx_t *c) {
     if (!c) return DE_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->sX, &c->sOut, &c->sGrad, &c->sOk, &c->sParams, &c->sClasses, &c->sOut2, &c->sGoff, &c->sNg, &c->sY, &c->sW, &c->sLoss, &c->sStats, &c->sYstats, &c->sJtj, &c->sJoff, &c->sPartial, &c->sSeg, &c->sDloss, &c->sColOff, &c->sDoff, &c->sPrio, &c->sPrioDs, &c->sCert, &c->sBcLoss, &c->sBcDloss, &c->sBcOk, &c->sBcNg, &c->sBcDoff, &c->sBcOut, &c->sBcTiles, &c->sLm, &c->sLmTab, &c->sGnw, &c->sTp, &c->sTpOut}) b->release();
+    for (DevBuf *b : {&c->sX, &c->sOut, &c->sGrad, &c->sOk, &c->sParams, &c->sClasses, &c->sOut2, &c->sGoff, &c->sNg, &c->sY, &c->sW, &c->sLoss, &c->sStats, &c->sYstats, &c->sJtj, &c->sJoff, &c->sPartial, &c->sSeg, &c->sDloss, &c->sColOff, &c->sDoff, &c->sPrio, &c->sPrioDs, &c->sCert, &c->sBcLoss, &c->sBcDloss, &c->sBcOk, &c->sBcNg, &c->sBcDoff, &c->sBcOut, &c->sBcTiles, &c->sLm, &c->sLmTab, &c->sGnw, &c->sTp, &c->sTpOut, &c->sBatch}) b->release();
     c->lm_tab.clear();
     for (const auto &r : c->recycled) (void)hipFree(r.first);
     for (const auto &r : c->small_free) (void)hipFree(r.first);
@@ -443,7 +443,7 @@ int de_ctx_trim(de_ctx_t *c) {
     if (!c) return DE_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (DevBuf *b : {&c->sX, &c->sOut, &c->sGrad, &c->sOk, &c->sParams, &c->sClasses, &c->sOut2, &c->sGoff, &c->sNg, &c->sY, &c->sW, &c->sLoss, &c->sStats, &c->sYstats, &c->sJtj, &c->sJoff, &c->sPartial, &c->sSeg, &c->sDloss, &c->sColOff, &c->sDoff, &c->sCert, &c->sBcLoss, &c->sBcDloss, &c->sBcOk, &c->sBcNg, &c->sBcDoff, &c->sBcOut, &c->sBcTiles, &c->sLm, &c->sLmTab, &c->sGnw, &c->sTp, &c->sTpOut}) b->release();
+    for (DevBuf *b : {&c->sX, &c->sOut, &c->sGrad, &c->sOk, &c->sParams, &c->sClasses, &c->sOut2, &c->sGoff, &c->sNg, &c->sY, &c->sW, &c->sLoss, &c->sStats, &c->sYstats, &c->sJtj, &c->sJoff, &c->sPartial, &c->sSeg, &c->sDloss, &c->sColOff, &c->sDoff, &c->sCert, &c->sBcLoss, &c->sBcDloss, &c->sBcOk, &c->sBcNg, &c->sBcDoff, &c->sBcOut, &c->sBcTiles, &c->sLm, &c->sLmTab, &c->sGnw, &c->sTp, &c->sTpOut, &c->sBatch}) b->release();
     c->lm_tab.clear();
     for (const auto &r : c->recycled) (void)hipFree(r.first);
     for (const auto &r : c->small_free) (void)hipFree(r.first);

@@ -8,6 +8,7 @@
 //                       host-only encoders of the threaded and reverse streams (de_grad_encode.cpp), de_lower_tape_grad
 //   de_api_fit.cpp      what CONSUMES them: de_gn_lm_step / de_fit_stats_lm_step (and _wide), de_fit_consts_lm(_ex, _wide),
 //                       de_fit_consts_lm_scaled(_wide), de_fit_consts_bfgs, de_fit_consts_nm, the _tied fits — one driver (run_fit) — and their host hooks
+//   de_api_batch.cpp    de_batch_sample_rows, de_batch_gather and their host-only twins: minibatches (kernels: de_batch.hip)
 //   de_api_tree_params.cpp  de_tape_params_to_consts, de_eval*_tree_params: per-tree parameter matrices, class by class around the calls above
 // No behaviour changed in the split: de_program_stream_hash and the whole test suite are the check.
 #ifndef DE_API_INTERNAL_H
@@ -100,6 +101,8 @@ struct de_ctx {
     // de_eval*_tree_params (de_api_tree_params.cpp): sTp — the tables, the base and the class's constant vector, the
     // class's results and the double accumulators of one call; sTpOut — the device image of a host `out` of de_eval_tree_params
     DevBuf sTp, sTpOut;
+    // de_batch_gather (de_api_batch.cpp): the counter of a host n_bad and the device image of a host `rows`
+    DevBuf sBatch;
     std::vector<unsigned char> lm_tab;
     void *lm_pin = nullptr;
     size_t lm_pin_cap = 0;

@@ -649,6 +649,98 @@ function eval_population_loss(
     return out, ok .!= 0x00
 end
 
+# ---- minibatches (DESIGN.md §4.4.18; include/de_hip.h has the sampler's definition) -------------------------------------------------
+struct BatchSrc             # de_batch_src_t
+    X::Ptr{Cvoid}
+    N::Int64
+    ldX::Int64
+    n_features::Int32
+    classes_is_i64::Int32
+    y::Ptr{Cvoid}
+    w::Ptr{Cvoid}
+    classes::Ptr{Cvoid}
+end
+struct BatchDst             # de_batch_dst_t
+    X::Ptr{Cvoid}
+    ldX::Int64
+    y::Ptr{Cvoid}
+    w::Ptr{Cvoid}
+    classes::Ptr{Cvoid}
+end
+const BATCH_MODES = Dict{Symbol,Cint}(:replace => 0, :permute => 1)   # de_batch_mode_t
+
+"""
+    sample_population_rows(pop, N, n_rows; seed, step=0, mode=:replace, offset=0) -> Vector{Int64}
+
+Positions `offset+1 … offset+n_rows` of the batch `(mode, N, seed, step)` as 1-based row indices into a dataset of `N` rows
+(`de_batch_sample_rows`): a pure function of its arguments, the same rows on every machine and on the device.  `:replace` samples
+with replacement, as SymbolicRegression.jl's `batching` does; `:permute` takes a slice of a keyed permutation of `1:N`
+(`offset + n_rows <= N`): batches without replacement, epochs, train / hold-out splits.
+"""
+function sample_population_rows(
+    pop::HIPPopulation, N::Integer, n_rows::Integer; seed::Integer, step::Integer=0, mode::Symbol=:replace, offset::Integer=0,
+)
+    haskey(BATCH_MODES, mode) || throw(ArgumentError("unknown batch mode $mode"))
+    rows = Vector{Int64}(undef, n_rows)
+    with_ctx(pop.ctx) do hc
+        check(pop.ctx, GC.@preserve rows ccall(
+            (:de_batch_sample_rows, LIBDE), Cint,
+            (Ptr{Cvoid}, Cint, Int64, UInt64, UInt64, Int64, Int64, Ptr{Int64}),
+            hc, BATCH_MODES[mode], N, seed % UInt64, step % UInt64, offset, n_rows, rows))
+    end
+    return rows .+ 1
+end
+
+"""
+    gather_population_batch(pop, X, rows; y=nothing, weights=nothing, classes=nothing) -> (X=…, y=…, weights=…, classes=…, rows=rows)
+
+The columns `rows` (1-based) of `X` and the same entries of `y`, `weights` and `classes` as a dense batch (`de_batch_gather`): every
+`eval_population*` / `fit_population*` call takes it like any other dataset.  A row outside `1:N` is refused before anything is written.
+"""
+function gather_population_batch(
+    pop::HIPPopulation{T}, X::Matrix{T}, rows::Vector{Int64};
+    y::Union{Nothing,Vector{T}}=nothing, weights::Union{Nothing,Vector{<:Real}}=nothing, classes::Union{Nothing,Vector{Int64}}=nothing,
+) where {T}
+    F, N = size(X)
+    n = length(rows)
+    @assert y === nothing || length(y) == N
+    @assert weights === nothing || (eltype(weights) === loss_weight_type(T) && length(weights) == N)
+    @assert classes === nothing || length(classes) == N
+    rows0 = rows .- 1
+    Xb = Matrix{T}(undef, F, n)
+    yb = y === nothing ? nothing : Vector{T}(undef, n)
+    wb = weights === nothing ? nothing : Vector{loss_weight_type(T)}(undef, n)
+    cb = classes === nothing ? nothing : Vector{Int64}(undef, n)
+    p(v) = v === nothing ? C_NULL : Ptr{Cvoid}(pointer(v))
+    with_ctx(pop.ctx) do hc
+        check(pop.ctx, GC.@preserve X y weights classes rows0 Xb yb wb cb begin
+            src = Ref(BatchSrc(p(X), N, max(F, 1), F, 1, p(y), p(weights), p(classes)))
+            dst = Ref(BatchDst(p(Xb), max(F, 1), p(yb), p(wb), p(cb)))
+            ccall((:de_batch_gather, LIBDE), Cint,
+                (Ptr{Cvoid}, Cint, Ref{BatchSrc}, Ptr{Int64}, Int64, Ref{BatchDst}, Ptr{Int32}),
+                hc, dtype_code(T), src, rows0, n, dst, C_NULL)
+        end)
+    end
+    return (X=Xb, y=yb, weights=wb, classes=cb, rows=rows)
+end
+
+"""
+    eval_population_loss_minibatch(pop, X, y, n_rows; seed, step=0, weights=nothing, loss=:L2, loss_param=0.0, mode=:replace, offset=0)
+        -> (loss, ok, batch)
+
+`sample_population_rows`, `gather_population_batch` and `eval_population_loss` on the batch: the stochastic scoring step of a search
+on a large dataset.  A fit keeps one batch for its whole run: pass `batch.X, batch.y; weights=batch.weights` to `fit_population_*`.
+"""
+function eval_population_loss_minibatch(
+    pop::HIPPopulation{T}, X::Matrix{T}, y::Vector{T}, n_rows::Integer; seed::Integer, step::Integer=0,
+    weights::Union{Nothing,Vector{<:Real}}=nothing, loss::Symbol=:L2, loss_param::Real=0.0, mode::Symbol=:replace, offset::Integer=0,
+) where {T}
+    rows = sample_population_rows(pop, size(X, 2), n_rows; seed=seed, step=step, mode=mode, offset=offset)
+    batch = gather_population_batch(pop, X, rows; y=y, weights=weights)
+    out, ok = eval_population_loss(pop, batch.X, batch.y; weights=batch.weights, loss=loss, loss_param=loss_param)
+    return out, ok, batch
+end
+
 """
     eval_population_fit_stats(pop, X, y; weights=nothing) -> (stats::NamedTuple, ok)
 

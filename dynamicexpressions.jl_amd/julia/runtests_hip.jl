@@ -263,3 +263,32 @@ end
     out2, ok2 = HIP.eval_population(HIP.HIPPopulation([plain], ops, 2), X)
     @test ok2[1] == ok[2] && agree(view(out2, :, 1), view(out, :, 2))
 end
+
+@testset "minibatches: the row sampler against its definition, the gather against indexing (DESIGN.md §4.4.18)" begin
+    # the definition of include/de_hip.h restated: wrapping UInt64 arithmetic is Julia's own
+    G = 0x9E3779B97F4A7C15
+    fin(z::UInt64) = (z ⊻= z >> 30; z *= 0xBF58476D1CE4E5B9; z ⊻= z >> 27; z *= 0x94D049BB133111EB; z ⊻ (z >> 31))
+    key(seed, step) = fin(UInt64(seed) ⊻ fin(UInt64(step) + G))
+    replace_row(k, N, i) = Int64((UInt128(fin(k + G * UInt64(i + 1))) * UInt128(N)) >> 64) + 1
+    @test fin(G) == 0xe220a8397b1dcdaf && key(1, 0) == 0x9e0160293a33aaf7
+    ops = OperatorEnum(1 => (cos, exp), 2 => (+, -, /, *))
+    x1, x2 = Node{Float32}(; feature=1), Node{Float32}(; feature=2)
+    pop = HIP.HIPPopulation([x1 * cos(x2 - 3.2f0), x1 + x2 * 0.5f0], ops, 2)
+    N = 5_000
+    rows = HIP.sample_population_rows(pop, N, 1_000; seed=1, step=3)
+    @test rows == [replace_row(key(1, 3), N, j) for j in 0:999]
+    @test HIP.sample_population_rows(pop, 10, 8; seed=1) == [5, 2, 9, 1, 3, 2, 1, 2] .+ 1
+    @test HIP.sample_population_rows(pop, 10, 3; seed=1, offset=5) == [2, 1, 2] .+ 1      # a batch drawn in pieces
+    perm = HIP.sample_population_rows(pop, 10, 10; seed=5, step=2, mode=:permute)
+    @test perm == [9, 7, 0, 1, 2, 3, 6, 8, 4, 5] .+ 1 && sort(perm) == collect(1:10)
+    @test_throws Exception HIP.sample_population_rows(pop, 10, 11; seed=5, mode=:permute)
+    X = randn(Float32, 2, N); y = randn(Float32, N); w = rand(Float32, N)
+    b = HIP.gather_population_batch(pop, X, rows; y=y, weights=w)
+    @test b.X == X[:, rows] && b.y == y[rows] && b.weights == w[rows] && b.classes === nothing
+    @test_throws Exception HIP.gather_population_batch(pop, X, [1, N + 1]; y=y)
+    # the batch is a dataset like any other: the same bits as the same rows gathered by indexing
+    l1, ok1 = HIP.eval_population_loss(pop, b.X, b.y; weights=b.weights)
+    l2, ok2 = HIP.eval_population_loss(pop, X[:, rows], y[rows]; weights=w[rows])
+    l3, ok3, b3 = HIP.eval_population_loss_minibatch(pop, X, y, 1_000; seed=1, step=3, weights=w)
+    @test ok1 == ok2 == ok3 && l1 == l2 == l3 && b3.rows == rows
+end

@@ -116,7 +116,10 @@ extern "C" {
  *      (v) DE_OPT_TYPED_LOSS (new option bit 9): a DE_F16 / DE_CF32 / DE_CF64 program created with it is served by de_eval_loss and
  *      de_eval_loss_ex (DE_LOSS_L2 / DE_LOSS_L1; the buffer table at de_eval_loss); without the bit nothing changes for them.  And, with
  *      no bit: de_eval_loss / de_eval_loss_ex serve the DE_F32 / DE_F64 programs that do not run the LDS-tiled kernel (a feature matrix
- *      too wide for its tile, DE_EVAL_THREADED=0), every kind — calls that answered DE_ERR_UNSUPPORTED before. */
+ *      too wide for its tile, DE_EVAL_THREADED=0), every kind — calls that answered DE_ERR_UNSUPPORTED before.
+ *      (w) de_batch_sample_rows, de_batch_gather and the host-only de_batch_rows_host / de_batch_gather_host (with de_batch_mode_t,
+ *      de_batch_src_t, de_batch_dst_t): minibatches — a counter-based device row sampler and a gather of the sampled rows of X, y, w
+ *      and classes into a dense batch that every entry point above serves unchanged; all five dtypes. */
 #define DE_HIP_ABI_VERSION 3
 
 typedef enum de_status {
@@ -1260,6 +1263,74 @@ int de_fit_consts_lm_tied(de_ctx_t *ctx, de_program_t *prog, const void *X, int6
 int de_eval_pullback_dX(de_ctx_t *ctx, de_program_t *prog, const void *X, int64_t N, int64_t ldX,
                         const de_param_args_t *pargs, const void *dY, void *dX,
                         const int64_t *dX_offsets, uint8_t *ok);
+
+/* ---- minibatches: a device row sampler and a batch gather -----------------------------
+ * A search on a large dataset scores each step on a random subset of the rows (SymbolicRegression.jl's `batching`).  The two calls below
+ * make that subset ON THE DEVICE as a DENSE batch — de_batch_sample_rows draws the row indices, de_batch_gather copies those rows of
+ * X, y, w and classes into buffers the caller allocated — and every entry point of this header then serves the batch unchanged, bit for
+ * bit what it computes on the same rows gathered by any other means.  Work is queued on the context's stream; nothing synchronises
+ * unless a host pointer forces it.
+ *
+ * THE SAMPLER is counter-based: row j of a batch is a pure function of (mode, N, seed, step, offset + j) — no state, a batch drawn in
+ * pieces equals the batch drawn at once, and de_batch_rows_host (no context, no device) restates the kernel bit for bit.  All arithmetic
+ * is modulo 2^64:
+ *   G      = 0x9E3779B97F4A7C15
+ *   fin(z) : z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (SplitMix64's output function;
+ *            fin(G), fin(2G), fin(3G) = e220a8397b1dcdaf 6e789e6aa1b965f4 06c45d188009454f, the published stream of seed 0)
+ *   key    : k = fin(seed ^ fin(step + G))          (`seed` names the run, `step` the batch)
+ *   DE_BATCH_REPLACE — sampling WITH replacement, what SymbolicRegression.jl's batching draws:
+ *            i = offset + j;  r = fin(k + G * (i + 1));  row = mulhi64(r, N)   (the high 64 bits of the product; bias at most N / 2^64)
+ *   DE_BATCH_PERMUTE — the slice [offset, offset + n_rows) of a keyed permutation of [0, N): batches without replacement, epochs that
+ *            visit every row exactly once, train / hold-out splits.  b = max(2, bit_length(N - 1)) rounded up to even, h = b / 2,
+ *            mask = 2^h - 1;  x = offset + j;  repeat { L = x >> h; R = x & mask;
+ *            for r = 0 .. 5: (L, R) = (R, L ^ (fin(k ^ (R + G * (r + 1))) & mask));  x = (L << h) | R } until x < N   (cycle walking: the
+ *            domain is smaller than 4 N).  offset + n_rows <= N is required: DE_ERR_OUT_OF_RANGE otherwise.
+ * Refusals, before anything is written: DE_ERR_INVALID_ARG for a null context, a null `rows` with n_rows > 0, N <= 0, n_rows < 0,
+ * offset < 0 or an unknown mode.  n_rows == 0 is DE_OK and touches nothing.  `rows` may be a device or a host pointer; a host `rows` is
+ * filled by de_batch_rows_host with no launch. */
+typedef enum de_batch_mode { DE_BATCH_REPLACE = 0, DE_BATCH_PERMUTE = 1 } de_batch_mode_t;
+int de_batch_sample_rows(de_ctx_t *ctx, int mode, int64_t N, uint64_t seed, uint64_t step, int64_t offset, int64_t n_rows, int64_t *rows);
+int de_batch_rows_host(int mode, int64_t N, uint64_t seed, uint64_t step, int64_t offset, int64_t n_rows, int64_t *rows);
+/* THE GATHER: dst.X[f + dst.ldX * j] = src.X[f + src.ldX * rows[j]] for f < n_features and j < n_rows, and likewise y[j] = y[rows[j]],
+ * w[j] = w[rows[j]], classes[j] = classes[rows[j]].  It is a copy of bytes and serves every de_dtype_t by element size: X and y 2 / 4 / 8 /
+ * 8 / 16 bytes for DE_F16 / DE_F32 / DE_F64 / DE_CF32 / DE_CF64; w the real component type (2 / 4 / 8 / 4 / 8 bytes, the buffer table at
+ * de_eval_loss); classes 4 or 8 bytes by classes_is_i64, as in de_param_args_t.  N is the number of source rows; ldX counts elements,
+ * >= n_features on both sides.  y, w and classes are optional: a column is gathered where BOTH its src and its dst pointer are given; a
+ * dst column without its src column is DE_ERR_INVALID_ARG.  X may be null on both sides when n_features == 0.  Source and destination
+ * must not overlap (not checked).  One launch gathers X and the present columns; every address is computed in 64 bits.
+ *   de_batch_gather: the data pointers (src and dst X, y, w, classes) are all device pointers — or all host pointers, which are served on
+ *   the host by the routine below.  `rows` and `n_bad` may each be on either side.
+ * Row indices outside [0, N):
+ *   - host `rows`: refused with DE_ERR_OUT_OF_RANGE before anything is written (de_last_error names the first position); *n_bad = 0.
+ *   - device `rows` cannot be tested without a synchronisation, so the kernel guards: it reads nothing for such a row and writes a quiet
+ *     NaN into that batch row's X, y and w (both components of a complex element) — every tree's loss over the batch comes out NaN, loud
+ *     rather than silent — and the class id of source row 0, which keeps the parameter lookup downstream in range.  The row is counted
+ *     in *n_bad (int32, may be NULL), which the call zeroes first; a host n_bad makes the call synchronise.
+ *   de_batch_gather_host (host pointers only, no context) always pre-checks and refuses; ONE routine serves both and fills and counts
+ *   in the same way when de_batch_gather hands it rows it copied from the device (host data with device rows).
+ * Other refusals, before anything is written: DE_ERR_INVALID_ARG for a null src / dst / rows (n_rows > 0), an unknown dtype, n_rows < 0,
+ * N <= 0, n_features < 0, ldX < n_features, a null X with n_features > 0, and (de_batch_gather) data pointers on both sides of the bus.
+ * n_rows == 0 is DE_OK and writes nothing but *n_bad = 0. */
+typedef struct de_batch_src {
+    const void *X;
+    int64_t N;
+    int64_t ldX;
+    int32_t n_features;
+    int32_t classes_is_i64;
+    const void *y;
+    const void *w;
+    const void *classes;
+} de_batch_src_t;
+typedef struct de_batch_dst {
+    void *X;
+    int64_t ldX;
+    void *y;
+    void *w;
+    void *classes;
+} de_batch_dst_t;
+int de_batch_gather(de_ctx_t *ctx, int dtype, const de_batch_src_t *src, const int64_t *rows, int64_t n_rows, const de_batch_dst_t *dst,
+                    int32_t *n_bad);
+int de_batch_gather_host(int dtype, const de_batch_src_t *src, const int64_t *rows, int64_t n_rows, const de_batch_dst_t *dst, int32_t *n_bad);
 
 /* ---- multi-GPU: one process per GPU, population tree-sharded, RCCL over xGMI -----------------------------
  * The path shards embarrassingly: rank r owns trees {t : t mod world == r} (round-robin balances node
